@@ -20,8 +20,14 @@ rank 0's JSON line (never re-executes a process that has touched the GPU).  Unde
 (the driver's way) it is one rank.  The only data-path collective of the solver is the all-reduce of the (sum, count)
 of log(twi)/tfact (src/microclimfCpp.cpp:993-1004); the terrain pre-compute exchanges halo rows point-to-point.
 
-After the timed region (outside it) a sample of cells of the LAST ring slot is fetched (mcf_plan_fetch_cells) and
-compared with the CPU oracle run on exactly those cells: `verified`.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times --steps passes and prints ONE JSON line on rank 0 (`ms_per_step`: one timed pass).
+--full adds what the headline figure does not need: the CPU baselines (before torch / HIP are touched), `verified` — after
+the timed region a sample of cells of the LAST ring slot is fetched (mcf_plan_fetch_cells) and compared with the CPU oracle
+run on exactly those cells — and, on one GPU, the `secondary` geometries.
+
+--dump-outputs DIR: after the timed region rank 0 writes what the last timed pass left in the ring — the ten outputs of a
+fixed, seeded sample of its cells that hold data (not NA) over the days still resident — as DIR/<output>.npy (float64 [cells, hours]).  The inputs
+depend on the arguments alone, so two builds given the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -65,6 +71,12 @@ def parse(argv=None):
     ap.add_argument("--ring-slots", type=int, default=2)
     ap.add_argument("--ring-gb", type=float, default=262.0, help="HBM the plan may use for tables + output ring")
     ap.add_argument("--cells-per-block", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baselines, the in-run oracle check (`verified`) and the secondary geometries "
+                         "(each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed pass's outputs for a fixed, seeded sample of the cells that hold data as "
+                         "DIR/<output>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (configs[1], array forcing, "
                                                                  "coarse array forcing)")
@@ -282,6 +294,51 @@ def fit_ring(args, cells, af):
         else:
             break
     return slots, days
+
+
+def rows_in_threads(make, rows):
+    """make(r0, r1) -> {key: array whose first axis holds rows r0 .. r1 - 1}, called on row slices in a thread pool (numpy's
+    kernels release the GIL) and assembled into one column-major array per key.  The synthetic inputs are counter-based per
+    global cell, so the slices are bit for bit the rows one call over all `rows` would give."""
+    from concurrent.futures import ThreadPoolExecutor
+    import threading
+    nthreads = max(1, min(16, len(os.sched_getaffinity(0))))
+    edges = np.linspace(0, rows, min(4 * nthreads, rows) + 1).astype(int)
+    out, lock = {}, threading.Lock()
+
+    def job(b):
+        r0, r1 = int(edges[b]), int(edges[b + 1])
+        part = make(r0, r1)
+        with lock:
+            for k, v in part.items():
+                if k not in out:
+                    out[k] = np.empty((rows,) + v.shape[1:], dtype=v.dtype, order="F")
+        for k, v in part.items():
+            out[k][r0:r1] = v
+
+    with ThreadPoolExecutor(nthreads) as ex:
+        list(ex.map(job, range(len(edges) - 1)))
+    return out
+
+
+def dump_outputs(plan, resident, outdir, has_data, names=None, budget=48e6, seed=11):
+    """--dump-outputs: what the last timed pass left in the ring — every output (or `names`), for a fixed, seeded sample of
+    the cells that hold data (`has_data`: one flag per cell, column-major; an NA cell's outputs are NaN by definition) —
+    sorted column-major indices, as many as keep the files under `budget` bytes — over the days in `resident`, in day order,
+    as <outdir>/<output>.npy, float64 [cells, hours]."""
+    from microclimf_amd._abi import OUT_NAMES
+    names = list(OUT_NAMES if names is None else names)
+    days = sorted(resident.items(), key=lambda kv: kv[1])          # ((slot, day offset in slot), absolute day)
+    has_data = np.asarray(has_data, dtype=bool).reshape(-1)
+    assert has_data.size == plan.rows * plan.cols, (has_data.size, plan.rows, plan.cols)
+    pool = np.flatnonzero(has_data)
+    n = max(1, min(pool.size, int(budget // (8 * len(names) * 24 * max(len(days), 1)))))
+    cells = np.sort(np.random.default_rng(seed).choice(pool, size=n, replace=False))
+    out = Path(outdir)
+    out.mkdir(parents=True, exist_ok=True)
+    for var in names:
+        parts = [plan.fetch_cells(slot, var, off * 24, 24, cells) for (slot, off), _ in days]
+        np.save(out / f"{var}.npy", np.concatenate(parts, axis=1) if parts else np.empty((n, 0)))
 
 
 class Clock:
@@ -566,21 +623,37 @@ def build_workload(args, synthetic, rank, world, local_rank, rows, cols, row0, r
         a, rp, cp = synthetic.coarse_workload(rows, cols, T, coarse[0], coarse[1], reqhgt=args.reqhgt, row0=row0,
                                               rows_total=rows_total)
         cpos = {"rowpos": rp, "colpos": cp}
-    else:
+    elif af:
         a = synthetic.workload(rows, cols, T, reqhgt=args.reqhgt, row0=row0, rows_total=rows_total,
-                               array_forcing=af, start_doy=152 if af else 1)
+                               array_forcing=True, start_doy=152)
+    else:
+        head = {}
+
+        def block(r0, r1):
+            w = synthetic.workload(r1 - r0, cols, T, reqhgt=args.reqhgt, row0=row0 + r0, rows_total=rows_total, start_doy=1)
+            if r0 == 0:
+                head.update(w)              # the forcing vectors and scalars: the same in every slice
+            return {(g, k): v for g in ("vegp", "soilc") for k, v in w[g].items()}
+
+        parts = rows_in_threads(block, rows)
+        a = dict(head, **{g: {k: v for (gg, k), v in parts.items() if gg == g} for g in ("vegp", "soilc")})
+
+    def dtm_rows(first, n):
+        return rows_in_threads(lambda r0, r1: {"dtm": synthetic.rasters(r1 - r0, cols, first + r0, rows_total, reqhgt=args.reqhgt)[2]},
+                               n)["dtm"]
+
     terrain_s = None
     if args.terrain == "device":
         from microclimf_amd.terrain import HALO, precompute_terrain, precompute_terrain_tiled
         if exchange_ok:
-            _, _, dtm = synthetic.rasters(rows, cols, row0, rows_total, reqhgt=args.reqhgt)
+            dtm = dtm_rows(row0, rows)
             tt0 = time.perf_counter()
             ter = precompute_terrain_tiled(dtm, 1.0, a["zref"], rank, world, row0, rows_total, device=local_rank)
         else:
             # one rank's share of a larger partition without its neighbours: the halo rows are generated, not exchanged
             hn = min(HALO, row0)
             hs = min(HALO, rows_total - (row0 + rows))
-            _, _, ext = synthetic.rasters(rows + hn + hs, cols, row0 - hn, rows_total, reqhgt=args.reqhgt)
+            ext = dtm_rows(row0 - hn, rows + hn + hs)
             tt0 = time.perf_counter()
             ter = precompute_terrain(ext, 1.0, a["zref"], halo_north=hn, halo_south=hs, row0=row0, rows_total=rows_total,
                                      device=local_rank)
@@ -590,8 +663,8 @@ def build_workload(args, synthetic, rank, world, local_rank, rows, cols, row0, r
 
 
 def measure(args, torch, dist, use_dist, rank, world, local_rank, *, rows, cols, row0, rows_total, T, af, coarse, steps, warmup,
-            ring_slots, ring_days, exchange_ok, verify):
-    """One measurement: build inputs, plan, twi all-reduce, timed passes, optional verification."""
+            ring_slots, ring_days, exchange_ok, verify, dump=None):
+    """One measurement: build inputs, plan, twi all-reduce, timed passes, optional output dump and verification."""
     from microclimf_amd import synthetic
     from microclimf_amd.api import Plan
     from microclimf_amd.distributed import allreduce_max, allreduce_sum, allreduce_twi_mean
@@ -621,6 +694,8 @@ def measure(args, torch, dist, use_dist, rank, world, local_rank, *, rows, cols,
         res = {"dt": dt, "kms": kms, "klaunches": klaunches, "valid": valid, "valid_all": valid_all, "ndays": ndays, "T": T,
                "terrain_s": terrain_s, "setup_s": setup_s, "value": valid_all * ndays * 24 * steps / dt, "verified": None,
                "plan_bytes": plan.device_bytes, "dispatch": plan.dispatch_stats()}
+        if dump and rank == 0:
+            dump_outputs(plan, resident, dump, ~np.isnan(np.asarray(a["vegp"]["hgt"])).reshape(-1, order="F"))
         if verify and rank == 0:
             res["verified"] = verify_sample(plan, a, resident, twi_mean, args.verify_cells, af=af, cpos=cpos)
     finally:
@@ -690,7 +765,7 @@ def main(argv=None):
                              "the snow kernels on one GPU")
         return run_snow_config(args, world, rank, local_rank)
     cpu_first = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # Rank 0 (a fresh process under torch.distributed.run too) times the CPU legs before torch / HIP are touched — the
         # all-cores leg forks worker processes; the other ranks wait for it at the process group's first barrier.  With
         # N > 1 ranks on the box the legs share the host with the other ranks' start-up: a reported baseline, not a target.
@@ -744,7 +819,7 @@ def main(argv=None):
     ring_slots, ring_days = fit_ring(args, rows * cols, af)
     r = measure(args, torch, dist, use_dist, rank, world, local_rank, rows=rows, cols=cols, row0=row0, rows_total=rows_total, T=T,
                 af=af, coarse=coarse, steps=args.steps, warmup=args.warmup, ring_slots=ring_slots, ring_days=ring_days,
-                exchange_ok=(nblocks == world), verify=not args.no_verify)
+                exchange_ok=(nblocks == world), verify=args.full and not args.no_verify, dump=args.dump_outputs)
     rc = 0
     if rank == 0:
         T = r["T"]
@@ -793,7 +868,7 @@ def main(argv=None):
             rc = 3
         if cpu_first is not None:
             line["cpu_baseline"], line["cpu_baseline_all_cores"] = cpu_first
-        if world == 1 and not args.no_secondary and not af and not coarse:
+        if world == 1 and args.full and not args.no_secondary and not af and not coarse:
             line["secondary"] = secondary_block(args, torch, dist, local_rank)
         sys.stdout.flush()
         os.dup2(saved_stdout, 1)

@@ -66,3 +66,64 @@ def test_gpus_2_strong_share_of_eight_blocks():
 def test_single_rank_needs_no_launcher():
     line = _run("--gpus", "1", "--stub", "--config", "1", "--rows", "24", "--cols", "8", "--steps", "1", "--warmup", "0")
     assert line["n_gpus"] == 1 and line["config"]["valid_cells"] == _valid(24, 8)
+
+
+def test_plain_run_is_the_default_and_full_adds_the_rest():
+    sys.path.insert(0, str(ROOT))
+    import bench
+    a = bench.parse(["--steps", "7"])
+    assert a.steps == 7 and not a.full and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_inputs_built_in_row_slices_are_those_of_one_call():
+    """bench.py builds a rank's block in row slices on a thread pool: bit for bit the arrays of one synthetic.workload call
+    (column-major as that returns them), and the DTM of one synthetic.rasters call — over a halo-extended block too"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    args = bench.parse(["--config", "1", "--tsteps", "48"])
+    rows, cols, row0, rows_total = 77, 23, 40, 300
+    got, cpos, terrain_s = bench.build_workload(args, synthetic, 0, 1, 0, rows, cols, row0, rows_total, 48, False, None, True)
+    want = synthetic.workload(rows, cols, 48, reqhgt=args.reqhgt, row0=row0, rows_total=rows_total, start_doy=1)
+    assert cpos is None and terrain_s is None and set(got) == set(want)
+    for g in ("vegp", "soilc"):
+        assert list(got[g]) == list(want[g])
+        for k, v in want[g].items():
+            assert got[g][k].flags.f_contiguous and np.array_equal(got[g][k], v, equal_nan=True), (g, k)
+    for g in ("climdata", "pointm", "obstime"):
+        for k, v in want[g].items():
+            assert np.array_equal(got[g][k], v), (g, k)
+    assert all(got[k] == want[k] for k in want if k not in ("vegp", "soilc", "climdata", "pointm", "obstime"))
+    dtm = bench.rows_in_threads(lambda r0, r1: {"dtm": synthetic.rasters(r1 - r0, cols, row0 - 9 + r0, rows_total)[2]}, rows + 17)
+    assert np.array_equal(dtm["dtm"], synthetic.rasters(rows + 17, cols, row0 - 9, rows_total)[2])
+
+
+def test_dump_samples_only_cells_that_hold_data(tmp_path):
+    """--dump-outputs on a stand-in plan whose NA cells read NaN: the sample is drawn from the cells that hold data only, the
+    same for the same raster, the days in day order whichever ring slot holds them, the files within the budget"""
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    class Plan:
+        rows, cols = 300, 200
+
+        def __init__(self, na):
+            self.na = na
+
+        def fetch_cells(self, slot, var, step0, nsteps, cells):
+            v = np.repeat((100.0 * slot + step0 // 24 + cells / 1e6)[None, :], nsteps, axis=0).T
+            v[self.na[cells]] = np.nan
+            return v
+
+    na = synthetic.uniform(31, np.arange(300 * 200)) < 0.2
+    resident = {(1, 0): 10, (1, 1): 11, (0, 0): 12}               # slot 1 holds days 10, 11; slot 0 day 12
+    bench.dump_outputs(Plan(na), resident, tmp_path / "a", ~na, budget=2e6)
+    bench.dump_outputs(Plan(na), resident, tmp_path / "b", ~na, budget=2e6)
+    files = sorted(tmp_path.glob("a/*.npy"))
+    assert len(files) == 10 and sum(f.stat().st_size for f in files) <= 2e6 + 10 * 256
+    for f in files:
+        a = np.load(f)
+        assert a.shape[1] == 72 and 0 < a.shape[0] < (~na).sum() and np.isfinite(a).all(), f.name
+        assert np.array_equal(a[:, ::24].round(), np.tile([100.0, 101.0, 0.0], (a.shape[0], 1)))
+        assert np.array_equal(a, np.load(tmp_path / "b" / f.name))

@@ -1,6 +1,6 @@
 """tests/golden/vignette_points.json — the reference's published result figures, digitised by tools/digitize_vignette.py.
-Here (no GPU): the fixture is self-consistent, regenerates bit for bit where the reference's images are present (the build
-container), and the one published series that needs no GPU — the host-side point model of image1b — meets it.  The grid
+Here (no GPU): the fixture is self-consistent, the digitiser recovers a curve from a figure drawn in base R's style, and the
+one published series that needs no GPU — the host-side point model of image1b — meets it.  The grid
 solver's and the snow branch's curves — and the ten published raster maps, cell by cell — are compared in
 tests/test_frontend_gpu.py::test_vignette_*."""
 import json
@@ -9,14 +9,12 @@ import sys
 from pathlib import Path
 
 import numpy as np
-import pytest
 
 import vignette_fixture as V
 from bundled import load
 from microclimf_amd import frontend as F
 
 ROOT = Path(__file__).resolve().parent.parent
-IMAGES = Path("/root/reference/vignettes/images")
 
 
 def test_fixture_is_self_consistent():
@@ -66,15 +64,41 @@ def test_map_fixtures_are_self_consistent():
     assert abs(V.map_panel("image4")["class_width"] - 0.0100) < 0.0005        # m/s
 
 
-@pytest.mark.skipif(not IMAGES.exists(), reason="the reference's images only exist in the build container")
-def test_fixture_regenerates_from_the_reference_images(tmp_path):
+def test_digitiser_recovers_a_drawn_figure(tmp_path, monkeypatch):
+    """tools/digitize_vignette.py on a figure drawn here as base R draws a line plot — a 1 px black frame, 7 px tick strokes
+    outside it, a red curve of known values: the frame, the ticks and the axis calibration are found exactly and the curve
+    comes back to within the half pixel the drawing rounded it to"""
     sys.path.insert(0, str(ROOT / "tools"))
     import digitize_vignette as D
-    fx = json.loads(V.FIXTURE.read_text())
-    for name, spec in D.SPEC.items():
-        assert D.digitize(name, spec) == fx["figures"][name], name
-    for name, spec in D.MAPS.items():
-        assert json.loads(json.dumps(D.digitize_map(name, spec))) == fx["maps"][name], name
+    from PIL import Image
+    top, bot, left, right = 40, 240, 60, 360
+    img = np.full((300, 400, 3), 255, np.uint8)
+    img[[top, bot], left:right + 1] = 0
+    img[top:bot + 1, [left, right]] = 0
+    yt, xt = [220, 180, 140, 100, 60], [80, 140, 200, 260, 320]        # y = 0 at row 220, 10 per 40 rows; x = 0 at column 80, 100 per 60
+    for r in yt:
+        img[r, left - 7:left] = 0
+    for c in xt:
+        img[bot + 1:bot + 8, c] = 0
+    cols = np.arange(left + 1, right)
+    x = (cols - 80) * 100.0 / 60
+    y = 20 + 15 * np.sin(x / 80)
+    img[np.rint(220 - 4 * y).astype(int), cols] = (220, 30, 30)
+    Image.fromarray(img).save(tmp_path / "drawn.png")
+    monkeypatch.setattr(D, "IMAGES", tmp_path)
+    spec = dict(rmd="-", what="a drawn figure", panels=[dict(xticks=[0, 100, 200, 300, 400], yticks=[0, 10, 20, 30, 40], x_is="index1",
+                                                             y_is="degC", curves={"c": "red"})])
+    p = D.digitize("drawn", spec)["panels"][0]
+    assert p["frame_px"] == {"top": top, "bottom": bot, "left": left, "right": right}
+    assert p["x"]["tick_px"] == xt and p["y"]["tick_px"] == yt                  # bottom label first
+    assert abs(p["x"]["per_px"] - 100 / 60) < 1e-12 and abs(p["y"]["per_px"] + 0.25) < 1e-12
+    assert p["x"]["fit_resid_px"] < 1e-9 and p["y"]["fit_resid_px"] < 1e-9
+    got = p["curves"]["c"]["columns"]
+    assert [c for c, _ in got] == list(cols) and all(len(flat) == 2 for _, flat in got)
+    xr = np.array([c for c, _ in got]) * p["x"]["per_px"] + p["x"]["at_px0"]
+    yr = np.array([flat[0] for _, flat in got]) * p["y"]["per_px"] + p["y"]["at_px0"]
+    assert np.abs(xr - x).max() < 1e-9
+    assert np.abs(yr - y).max() <= 0.5 * p["px"]["y"] + 1e-9
 
 
 def test_point_model_series_meet_the_published_figure():

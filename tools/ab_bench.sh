@@ -8,7 +8,7 @@ for spec in "$@"; do
   lib=${rest%%,*}; envs=""
   if [ "$rest" != "$lib" ]; then envs=${rest#*,}; fi
   ( [ "$lib" != "-" ] && export MCF_LIB=$PWD/$lib; [ -n "$envs" ] && export ${envs//,/ }; \
-    timeout -k 10 300 python3 bench.py --config 1 --steps ${STEPS:-5} --warmup 2 --no-cpu-baseline --no-secondary ${EXTRA} \
+    timeout -k 10 300 python3 bench.py --config 1 --steps ${STEPS:-5} --warmup 2 --full --no-cpu-baseline --no-secondary ${EXTRA} \
       > $out/$name.json 2> $out/$name.err )
   python3 -c "
 import json

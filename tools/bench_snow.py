@@ -58,7 +58,7 @@ def cpu_legs(args):
 
 def run_snow_config(args, world, rank, local_rank):
     cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         sys.stdout.flush()
         _saved = os.dup(1)
         os.dup2(2, 1)
@@ -276,7 +276,7 @@ def run_snow_config(args, world, rank, local_rank):
             slot = (slot + 1) % 2
         if probe is not None:
             probe["snowday"], probe["nosnowday"] = snowday.copy(), nosnowday.copy()
-        return snowday
+        return snowday, nosnowday
 
     def verify_sample(snowday, ncells=256):
         """The snow model of the year's LAST chunk with a snow day, re-run from the timed run's own checkpoint and held against
@@ -443,10 +443,19 @@ def run_snow_config(args, world, rank, local_rank):
     fence()
     dt = allreduce_max(time.perf_counter() - t0)
     timed_stats = dict(stats)           # (the verification below walks one more year)
+    if args.dump_outputs and rank == 0 and last_days is not None:
+        # the ring holds the last timed year's last two chunks (chunk ch in slot ch % 2): their days in a class, the merged output
+        import bench as B
+        from microclimf_amd._abi import OUT_NAMES
+        inclass = last_days[0] | last_days[1]
+        resident = {(ch % 2, k): ch * chunk_days + k for ch in range(max(sp.chunks - 2, 0), sp.chunks) for k in range(chunk_days)
+                    if ch * chunk_days + k < ndays and inclass[ch * chunk_days + k]}
+        has_data = ~(np.isnan(np.asarray(a["vegp"]["hgt"])) | np.isnan(np.asarray(sw["vegp"]["hgt"]))).reshape(-1, order="F")
+        B.dump_outputs(plan, resident, args.dump_outputs, has_data, names=[n for n, o in zip(OUT_NAMES, outm) if o])
     verified = None
-    if not getattr(args, "no_verify", False) and last_days is not None:
+    if args.full and not args.no_verify and last_days is not None:
         vm = verify_merged()
-        vs = verify_sample(last_days)
+        vs = verify_sample(last_days[0])
         if rank == 0:
             verified = dict(vm)
             verified["snowmodel"] = vs

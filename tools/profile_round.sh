@@ -10,7 +10,7 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 echo "$@" > $out/bench_args.txt
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py "$@" --steps 2 --warmup 1 \
-    --no-cpu-baseline --no-secondary > $out/bench_under_rocprof.json 2> $out/trace.err
+    --full --no-cpu-baseline --no-secondary > $out/bench_under_rocprof.json 2> $out/trace.err
 echo "trace done"
 S="python3 bench.py $* --tsteps 1920 --steps 1 --warmup 0 --no-cpu-baseline --no-secondary --no-verify"
 rocprofv3 --kernel-trace --output-format csv -d $out/pmc_fetch --pmc FETCH_SIZE -- $S > $out/pmc_fetch.json 2> $out/pmc_fetch.err
