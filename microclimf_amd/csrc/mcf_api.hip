@@ -15,7 +15,6 @@
 #include <future>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/mcf.h"
@@ -23,6 +22,7 @@
 #include "mcf_hostpipe.hpp"
 #include "mcf_ncfile.hpp"
 #include "mcf_nc4file.hpp"
+#include "mcf_rowblocks.hpp"
 
 namespace {
 
@@ -43,13 +43,6 @@ int fail(int code, const std::string& msg) {
             return fail(e_ == hipErrorOutOfMemory ? MCF_ERR_NOMEM : MCF_ERR_HIP, b_);        \
         }                                                                                    \
     } while (0)
-
-const uint64_t kNaBits = 0x7FF00000000007A2ULL;
-double na_real_host() {
-    double d;
-    memcpy(&d, &kNaBits, 8);
-    return d;
-}
 
 }  // namespace
 
@@ -261,11 +254,7 @@ int check_inputs(const mcf_grid_inputs* in, const mcf_options* opt) {
 }
 
 int ensure_device(int device) {
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0)
-        return fail(MCF_ERR_NO_DEVICE, "no HIP device available (libmcfhip has no CPU fallback)");
-    if (device < 0 || device >= n) return fail(MCF_ERR_ARG, "device ordinal out of range");
+    if (const int rc = mcf::check_device(device)) return rc;
     HIP_TRY(hipSetDevice(device));
     return MCF_OK;
 }
@@ -1810,7 +1799,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
                 if ((rc = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)ndays * 24, out->var[v], pitch))) return rc;
     }
     // steps past the last whole day are never computed by the reference and stay NA (cpp:2116)
-    const double na = na_real_host();
+    const double na = mcf::na_real_host();
     for (int v = 0; v < MCF_NOUT; ++v)
         if (opt->out[v])
             for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
@@ -1871,22 +1860,9 @@ static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, con
     // what row_blocks and the whole-raster twi mean read, before any plan has validated the inputs
     if (!in->vegp.hgt) return fail(MCF_ERR_ARG, "missing input array: vegp$hgt");
     if (!in->soilc.twi) return fail(MCF_ERR_ARG, "missing input array: twi");
-    int ndev_avail = 0;
-    if (hipGetDeviceCount(&ndev_avail) != hipSuccess || ndev_avail <= 0)
-        return fail(MCF_ERR_NO_DEVICE, "no HIP device available (libmcfhip has no CPU fallback)");
-    // the calling thread's current device is put back on every way out
-    int caller_dev = 0;
-    const bool have_caller_dev = hipGetDevice(&caller_dev) == hipSuccess;
-    struct RestoreDev { bool on; int d; ~RestoreDev() { if (on) (void)hipSetDevice(d); } } restore_dev{have_caller_dev, caller_dev};
     std::vector<int> devs;
-    if (mu->n_devices <= 0) for (int d = 0; d < ndev_avail; ++d) devs.push_back(d);      // every visible device
-    else {
-        if (!mu->devices) return fail(MCF_ERR_ARG, "n_devices > 0 with a null device list");
-        for (int i = 0; i < mu->n_devices; ++i) {
-            if (mu->devices[i] < 0 || mu->devices[i] >= ndev_avail) return fail(MCF_ERR_ARG, "device ordinal out of range");
-            devs.push_back(mu->devices[i]);
-        }
-    }
+    if ((rc = mcf::device_list(mu, 0, &devs))) return rc;
+    mcf::RestoreDevice restore_dev;          // (the twi reduction below runs on the first device)
     int nb = mu->n_blocks > 0 ? mu->n_blocks : (int)devs.size();
     nb = (int)std::min<int64_t>(nb, in->rows);
     const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
@@ -1895,7 +1871,6 @@ static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, con
     {
         HIP_TRY(hipSetDevice(devs[0]));
         const int64_t N = in->rows * in->cols;
-        if (!in->soilc.twi) return fail(MCF_ERR_ARG, "missing input array: twi");
         double *d_twi = nullptr, *d_ws = nullptr;
         HIP_TRY(hipMalloc((void**)&d_twi, (size_t)N * 8));
         struct G { double *&a, *&b; ~G() { (void)hipFree(a); (void)hipFree(b); } } g{d_twi, d_ws};
@@ -1908,48 +1883,21 @@ static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, con
         twi_mean = h2[0] / h2[1];
     }
     const auto blocks = row_blocks(in, nb);
-    std::vector<int> rcs(devs.size(), MCF_OK);
-    std::vector<std::string> errs(devs.size());
-    std::vector<std::thread> threads;
-    for (size_t t = 0; t < devs.size(); ++t) {
-        threads.emplace_back([&, t] {
-            // (an exception must not leave a worker thread: std::terminate would take the host R / Python process down)
-            try {
-            for (int b = (int)t; b < nb; b += (int)devs.size()) {
+    const int nt = (int)std::min<size_t>(devs.size(), (size_t)nb);
+    return mcf::run_workers(nt, [&](mcf::Worker& w) {
+        w.guarded([&] {
+            mcf_options o = *opt;
+            o.device = devs[(size_t)w.t];
+            int sharers = 0;
+            for (int d : devs) sharers += d == o.device;
+            for (int b = w.t; b < nb && !w.failed(); b += nt) {
                 const int64_t r0 = blocks[(size_t)b].first, nr = blocks[(size_t)b].second;
                 if (nr <= 0) continue;
-                mcf_grid_inputs sub = *in;
-                sub.rows = nr;
-                sub.row_pitch = pitch;
-                auto off = [&](const double*& q) { if (q) q += r0; };
-                off(sub.vegp.hgt); off(sub.vegp.pai); off(sub.vegp.x); off(sub.vegp.gsmax); off(sub.vegp.leafr); off(sub.vegp.leaft);
-                off(sub.vegp.clump); off(sub.vegp.leafd); off(sub.vegp.paia); off(sub.vegp.leafden);
-                off(sub.soilc.Smin); off(sub.soilc.Smax); off(sub.soilc.gref); off(sub.soilc.soilb); off(sub.soilc.Psie);
-                off(sub.soilc.Vq); off(sub.soilc.Vm); off(sub.soilc.Mc); off(sub.soilc.rho); off(sub.soilc.slope);
-                off(sub.soilc.aspect); off(sub.soilc.twi); off(sub.soilc.svfa); off(sub.soilc.wsa); off(sub.soilc.hor);
-                off(sub.lats); off(sub.lons); off(sub.coarse_rowpos); off(sub.fine_dtm);
-                if (in->array_forcing == 1) {
-                    off(sub.clim.tc); off(sub.clim.es); off(sub.clim.ea); off(sub.clim.tdew); off(sub.clim.pk); off(sub.clim.swdown);
-                    off(sub.clim.difrad); off(sub.clim.lwdown); off(sub.clim.windspeed);
-                    off(sub.pointm.soilm); off(sub.pointm.G); off(sub.pointm.umu); off(sub.pointm.kp); off(sub.pointm.muGp);
-                    off(sub.pointm.dtrp); off(sub.pointm.Tg); off(sub.pointm.Tbp);
-                }
-                mcf_options o = *opt;
-                o.device = devs[t];
-                int sharers = 0;
-                for (int d : devs) sharers += d == devs[t];
-                const int rcb = block_fn(sub, o, r0, &twi_mean, sharers);
-                if (rcb != MCF_OK) { rcs[t] = rcb; errs[t] = g_err; return; }
-            }
-            } catch (const std::exception& e) {
-                rcs[t] = MCF_ERR_NOMEM; errs[t] = std::string("row-block worker: ") + e.what();
+                const int rcb = block_fn(mcf::narrow_rows(*in, r0, nr, pitch), o, r0, &twi_mean, sharers);
+                if (rcb != MCF_OK) { w.fail(rcb); return; }
             }
         });
-    }
-    for (auto& th : threads) th.join();
-    for (size_t t = 0; t < devs.size(); ++t)
-        if (rcs[t] != MCF_OK) return fail(rcs[t], errs[t]);
-    return MCF_OK;
+    });
 }
 
 }  // extern "C++"

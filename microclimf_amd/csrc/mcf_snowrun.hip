@@ -18,55 +18,34 @@
 //            their own place in the ring slot; k_microsnow_ring over it; the slot's merged days to the caller's arrays
 //
 // Row blocks: the raster is cut into contiguous row blocks, block b on devices[b % n_devices], one host thread per device
-// (as mcf_snowmodel1_multi): per chunk the blocks' snow surfaces meet in one whole-raster host array, the two raster-wide
+// (mcf_rowblocks.hpp's worker pool): per chunk the blocks' snow surfaces meet in one whole-raster host array, the two raster-wide
 // means and the per-step extremes of totalSWE are combined in block order.  One block = the single-device sequence, bit for bit.
+// The snow model's own entries (mcf_snowmodel1 / 2, mcf_snowmodel1_multi, at the end) run the same chunk loop (snow_chunk).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
-#include <condition_variable>
 #include <exception>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/mcf.h"
+#include "mcf_rowblocks.hpp"
 
 namespace mcf {
-int api_fail(int code, const std::string& msg);   // mcf_api.hip
+int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);   // mcf_snow.hip
+void snowplan_print_timing(const mcf_snowplan* sp);
 }
 
 namespace {
 
-struct PhaseBarrier {
-    std::mutex m;
-    std::condition_variable cv;
-    int n, waiting = 0, generation = 0;
-    explicit PhaseBarrier(int n_) : n(n_) {}
-    void wait() {
-        std::unique_lock<std::mutex> lk(m);
-        const int g = generation;
-        if (++waiting == n) { waiting = 0; ++generation; cv.notify_all(); }
-        else cv.wait(lk, [&] { return g != generation; });
-    }
-};
-
-template <class T>
-void gather_rows(std::vector<T>& dst, const T* src, int64_t R, int64_t C, int64_t r0, int64_t nr, int64_t layers = 1) {
-    dst.resize((size_t)(nr * C * layers));
-    for (int64_t lc = 0; lc < C * layers; ++lc) memcpy(&dst[(size_t)(nr * lc)], src + r0 + R * lc, (size_t)nr * sizeof(T));
-}
-
-double na_real_host() {
-    union { uint64_t u; double d; } na;
-    na.u = 0x7FF00000000007A2ULL;
-    return na.d;
-}
+using mcf::api_fail;
+using mcf::Worker;
 
 struct Block {
     int64_t r0 = 0, nr = 0;
@@ -85,15 +64,151 @@ struct Block {
     std::vector<double> m_pai, m_hgt, m_leaft, m_clump, m_paia, m_leafd, m_leafden, m_slope, m_aspect, m_svf, m_wsa, m_hor, m_smax;
 };
 
-}  // namespace
-
-struct mcf_snowrun {
-    int64_t R = 0, C = 0, T = 0;
-    int ndays = 0, chunk_days = 5, nchunks = 0;
+// The raster in nb contiguous row blocks, block b (rows R*b/nb ..) on devs[b % nt] driven by worker b % nt, each with its snow
+// plan (and, in a snow run, its solver plan): what the snow model entries and the snow run share.
+struct SnowBlocks {
+    int64_t R = 0, C = 0;
     int nb = 1, nt = 1;
     std::vector<int> devs;
     std::vector<Block> blocks;
     std::vector<double> surface;               // the whole raster's snow surface of the current chunk (nb > 1)
+    double smean = 0, tmean = 0;               // the current chunk's two raster-wide means (nb > 1)
+    // n_blocks <= 0: one block per device; never more blocks than rows
+    void cut(int n_blocks) {
+        nb = (int)std::max<int64_t>(1, std::min<int64_t>(n_blocks > 0 ? n_blocks : (int)devs.size(), R));
+        nt = (int)std::min<size_t>(devs.size(), (size_t)nb);
+        blocks.resize((size_t)nb);
+        if (nb > 1) surface.assign((size_t)(R * C), 0.0);
+    }
+    ~SnowBlocks() {
+        mcf::RestoreDevice restore;
+        for (Block& k : blocks) {
+            if (k.plan || k.sp) (void)hipSetDevice(k.device);
+            if (k.plan) mcf_plan_destroy(k.plan);
+            if (k.sp) mcf_snowplan_destroy(k.sp);
+        }
+    }
+};
+
+// block b's snow plan on `device`: one block reads the caller's arrays in place, more gather their rows
+int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& snow) {
+    Block& k = sb.blocks[(size_t)b];
+    const int64_t R = sb.R, C = sb.C;
+    k.device = device;
+    k.r0 = R * b / sb.nb; k.nr = R * (b + 1) / sb.nb - k.r0;
+    mcf_snowdriver_in bi = snow;
+    if (sb.nb > 1) {
+        const mcf_snow_vegp& vg = snow.base.vegp;
+        const mcf_snow_other& ot = snow.base.other;
+        mcf::gather_rows(k.pai, vg.pai, R, C, k.r0, k.nr); mcf::gather_rows(k.hgt, vg.hgt, R, C, k.r0, k.nr);
+        mcf::gather_rows(k.leaft, vg.leaft, R, C, k.r0, k.nr); mcf::gather_rows(k.clump, vg.clump, R, C, k.r0, k.nr);
+        mcf::gather_rows(k.dc, ot.isnowdc, R, C, k.r0, k.nr); mcf::gather_rows(k.dg, ot.isnowdg, R, C, k.r0, k.nr);
+        mcf::gather_rows(k.ac, ot.isnowac, R, C, k.r0, k.nr); mcf::gather_rows(k.ag, ot.isnowag, R, C, k.r0, k.nr);
+        mcf::gather_rows(k.dtm, snow.dtm, R, C, k.r0, k.nr);
+        bi.base.rows = k.nr;
+        bi.base.vegp.pai = k.pai.data(); bi.base.vegp.hgt = k.hgt.data(); bi.base.vegp.leaft = k.leaft.data();
+        bi.base.vegp.clump = k.clump.data();
+        bi.base.other.isnowdc = k.dc.data(); bi.base.other.isnowdg = k.dg.data();
+        bi.base.other.isnowac = k.ac.data(); bi.base.other.isnowag = k.ag.data();
+        bi.dtm = k.dtm.data();
+    }
+    bi.base.other.slope = bi.base.other.aspect = bi.base.other.skyview = bi.base.other.wsa = bi.base.other.hor = nullptr;
+    return mcf_snowplan_create(&bi, k.r0, R, k.device, &k.sp);
+}
+
+// One chunk of the snow model over every block.  Collective: every worker calls it for the same chunk.
+// One block: the sequence of mcf_snowmodel1 (no host copy of the surface; the raster-wide surface mean only where .tpicalc's
+// raster-mean branch reads it — mcf_snowplan_prepare_chunk ignores it otherwise).  More blocks: three phases separated by the
+// workers' barrier (the phases of snow.py snowmodel1_chunks_tiled, where ranks exchange the same things over RCCL):
+//   1  every block writes its rows of the surface into one whole-raster array and reports its (sum, count)
+//   2  every block takes its rows plus halo out of that array, refreshes terrain + tpi, reports tpic's (sum, count)
+//   3  every block runs the chunk with the raster-wide tpic mean
+// Partial sums are added in block order, so a run is reproducible for a given n_blocks; against the one-block run the two
+// means differ in their last bits (another summation tree), like route 1's.
+// out (optional): the caller's whole-series snow arrays — a block's chunk goes straight into its rows through the row pitch; the
+// steps no chunk covers become NA behind the last chunk.
+void snow_chunk(SnowBlocks& sb, Worker& w, int ch, const mcf_snowdriver_out* out) {
+    const int nb = sb.nb, nt = sb.nt;
+    const int64_t R = sb.R, C = sb.C;
+    auto block_out = [&](const Block& k) {
+        mcf_snowdriver_out bo{};
+        if (out) {
+            bo = *out;
+            double** const bop[5] = {&bo.Tc, &bo.Tg, &bo.groundsnowdepth, &bo.totalSWE, &bo.snowden};
+            for (double** q : bop) if (*q) *q += k.r0;
+        }
+        return bo;
+    };
+    if (nb == 1) {
+        if (w.t == 0) w.guarded([&] {
+            Block& k = sb.blocks[0];
+            int32_t af = 1;
+            double mean = 0.0, s = 0, n = 0;
+            int rc = mcf_snowplan_chunk_af(k.sp, ch, &af);
+            if (!rc && !((double)af < std::min(R, C) / 2.0)) {
+                rc = mcf_snowplan_surface_partial(k.sp, &s, &n);
+                mean = s / n;
+            }
+            if (!rc) rc = mcf_snowplan_prepare_chunk(k.sp, ch, nullptr, 0, 0, mean, &s, &n);
+            if (!rc) { const mcf_snowdriver_out bo = block_out(k); rc = mcf_snowplan_run_chunk_pitched(k.sp, ch, s / n, &bo, R); }
+            if (rc) w.fail(rc);
+        });
+    } else {
+        w.guarded([&] {                                       // ---- phase 1: the surface
+            for (int b = w.t; b < nb && !w.failed(); b += nt) {
+                Block& k = sb.blocks[(size_t)b];
+                k.ext.resize((size_t)(k.nr * C));
+                int rc = mcf_snowplan_surface(k.sp, k.ext.data());
+                if (!rc) rc = mcf_snowplan_surface_partial(k.sp, &k.s, &k.n);
+                if (rc) { w.fail(rc); break; }
+                mcf::scatter_rows(sb.surface.data(), k.ext.data(), R, C, k.r0, k.nr);
+            }
+        });
+        w.wait();
+        if (w.t == 0 && !w.failed()) {
+            double s = 0, n = 0;
+            for (const Block& k : sb.blocks) { s += k.s; n += k.n; }
+            sb.smean = s / n;
+        }
+        w.wait();
+        w.guarded([&] {                                       // ---- phase 2: halos, terrain, tpi
+            for (int b = w.t; b < nb && !w.failed(); b += nt) {
+                Block& k = sb.blocks[(size_t)b];
+                int32_t af = 1;
+                int rc = mcf_snowplan_chunk_af(k.sp, ch, &af);
+                if (rc) { w.fail(rc); break; }
+                // what prepare_chunk asks for at most, or every row up to the raster edge
+                const int64_t want = mcf::snowplan_halo_rows(k.sp, af);
+                const int64_t hn = std::min(want, k.r0), hs = std::min(want, R - k.r0 - k.nr), RB = hn + k.nr + hs;
+                mcf::gather_rows(k.ext, sb.surface.data(), R, C, k.r0 - hn, RB);
+                rc = mcf_snowplan_prepare_chunk(k.sp, ch, (hn || hs) ? k.ext.data() : nullptr, (int32_t)hn, (int32_t)hs, sb.smean, &k.ts, &k.tn);
+                if (rc) { w.fail(rc); break; }
+            }
+        });
+        w.wait();
+        if (w.t == 0 && !w.failed()) {
+            double s = 0, n = 0;
+            for (const Block& k : sb.blocks) { s += k.ts; n += k.tn; }
+            sb.tmean = s / n;
+        }
+        w.wait();
+        w.guarded([&] {                                       // ---- phase 3: the chunk
+            for (int b = w.t; b < nb && !w.failed(); b += nt) {
+                Block& k = sb.blocks[(size_t)b];
+                const mcf_snowdriver_out bo = block_out(k);
+                const int rc = mcf_snowplan_run_chunk_pitched(k.sp, ch, sb.tmean, &bo, R);
+                if (rc) { w.fail(rc); break; }
+            }
+        });
+    }
+    w.wait();
+}
+
+}  // namespace
+
+struct mcf_snowrun : SnowBlocks {
+    int64_t T = 0;
+    int ndays = 0, chunk_days = 5, nchunks = 0;
     mcf_grid_inputs grid{};
     mcf_options opt{};
     mcf_snowdriver_in snow{};
@@ -107,49 +222,9 @@ struct mcf_snowrun {
     bool keep = false;
     // what pass 2 did not have to do (mcf_snowrun_stats)
     std::atomic<int64_t> st_tile_days{0}, st_tile_days_left_out{0}, st_chunks_kept{0}, st_chunks_rerun{0};
-    ~mcf_snowrun() {
-        for (Block& k : blocks) {
-            if (k.plan || k.sp) (void)hipSetDevice(k.device);
-            if (k.plan) mcf_plan_destroy(k.plan);
-            if (k.sp) mcf_snowplan_destroy(k.sp);
-        }
-    }
 };
 
 namespace {
-
-// runs fn(t, guarded, fail_here) on every worker thread; a phase body run under `guarded` can neither let an exception leave
-// its thread nor skip a barrier
-template <class F>
-int run_workers(mcf_snowrun* h, F&& fn) {
-    const int nt = h->nt;
-    std::vector<int> rcs((size_t)nt, MCF_OK);
-    std::vector<std::string> errs((size_t)nt);
-    std::atomic<bool> failed{false};
-    PhaseBarrier bar(nt);
-    auto worker = [&](int t) {
-        auto fail_here = [&, t](int rc) {
-            if (rcs[(size_t)t] == MCF_OK) { rcs[(size_t)t] = rc; errs[(size_t)t] = mcf_last_error(); }
-            failed = true;
-        };
-        auto guarded = [&, t](auto&& body) {
-            if (failed) return;
-            try { body(); }
-            catch (const std::exception& e) {
-                if (rcs[(size_t)t] == MCF_OK) { rcs[(size_t)t] = MCF_ERR_NOMEM; errs[(size_t)t] = std::string("snow run: ") + e.what(); }
-                failed = true;
-            }
-        };
-        fn(t, bar, failed, guarded, fail_here);
-    };
-    std::vector<std::thread> threads;
-    for (int t = 1; t < nt; ++t) threads.emplace_back(worker, t);
-    worker(0);
-    for (auto& th : threads) th.join();
-    for (int t = 0; t < nt; ++t)
-        if (rcs[(size_t)t] != MCF_OK) return mcf::api_fail(rcs[(size_t)t], errs[(size_t)t]);
-    return MCF_OK;
-}
 
 // snowdaysfun, src/microclimfCpp.cpp:5531-5550: a snow day has snow somewhere in some hour (max > 0), a no-snow day a
 // snow-free cell in some hour (min == 0); NaN compares false both ways
@@ -162,97 +237,6 @@ void snowdays_of(const double* mx, const double* mn, int nd, int32_t* snow, int3
         }
         snow[d] = s; nosnow[d] = n;
     }
-}
-
-// one chunk of the snow model over every block: phases separated by the workers' barrier.  `with_apply3`: pass 1 also takes
-// the per-step extremes of totalSWE.  Collective: every worker calls it for the same chunk.
-// smod (pass 1, optional): the caller's whole-series snow arrays — a block's chunk goes straight into its rows.
-template <class G, class FH>
-void snow_chunk(mcf_snowrun* h, int t, int ch, PhaseBarrier& bar, std::atomic<bool>& failed, G& guarded, FH& fail_here,
-                bool with_apply3, const mcf_snowdriver_out* smod, double* smean, double* tmean) {
-    const int nb = h->nb, nt = h->nt;
-    const int64_t R = h->R, C = h->C;
-    auto block_out = [&](const Block& k) {
-        mcf_snowdriver_out bo{};
-        if (smod) {
-            bo = *smod;
-            double** const bop[5] = {&bo.Tc, &bo.Tg, &bo.groundsnowdepth, &bo.totalSWE, &bo.snowden};
-            for (double** q : bop) if (*q) *q += k.r0;
-        }
-        return bo;
-    };
-    if (nb == 1) {
-        // one block: the sequence of mcf_snowmodel1 (no host copy of the surface; the raster-wide mean only where .tpicalc
-        // falls back on it — mcf_snowplan_prepare_chunk ignores it otherwise)
-        if (t == 0) guarded([&] {
-            Block& k = h->blocks[0];
-            double s = 0, n = 1, ts = 0, tn = 1;
-            int rc = mcf_snowplan_surface_partial(k.sp, &s, &n);
-            if (!rc) rc = mcf_snowplan_prepare_chunk(k.sp, ch, nullptr, 0, 0, s / n, &ts, &tn);
-            if (!rc) { const mcf_snowdriver_out bo = block_out(k); rc = mcf_snowplan_run_chunk_pitched(k.sp, ch, ts / tn, &bo, R); }
-            if (rc) fail_here(rc);
-        });
-    } else {
-        guarded([&] {                                         // ---- phase 1: the surface
-            for (int b = t; b < nb && !failed; b += nt) {
-                Block& k = h->blocks[(size_t)b];
-                k.ext.resize((size_t)(k.nr * C));
-                int rc = mcf_snowplan_surface(k.sp, k.ext.data());
-                if (!rc) rc = mcf_snowplan_surface_partial(k.sp, &k.s, &k.n);
-                if (rc) { fail_here(rc); break; }
-                for (int64_t c = 0; c < C; ++c) memcpy(&h->surface[(size_t)(k.r0 + R * c)], &k.ext[(size_t)(k.nr * c)], (size_t)k.nr * 8);
-            }
-        });
-        bar.wait();
-        if (t == 0 && !failed) {
-            double s = 0, n = 0;
-            for (const Block& k : h->blocks) { s += k.s; n += k.n; }
-            *smean = s / n;
-        }
-        bar.wait();
-        guarded([&] {                                         // ---- phase 2: halos, terrain, tpi
-            for (int b = t; b < nb && !failed; b += nt) {
-                Block& k = h->blocks[(size_t)b];
-                // what prepare_chunk asks for at most (the terrain stencil's reach, whole af x af blocks of the tpi), or every row up
-                // to the raster edge
-                int32_t af = 1;
-                int rc = mcf_snowplan_chunk_af(k.sp, ch, &af);
-                if (rc) { fail_here(rc); break; }
-                const int64_t ss = h->snow.res <= 100 ? 10 : 1;
-                const int64_t want = 100 + 3 * ss + 2 * (int64_t)af;
-                const int64_t hn = std::min(want, k.r0), hs = std::min(want, R - k.r0 - k.nr), RB = hn + k.nr + hs;
-                gather_rows(k.ext, h->surface.data(), R, C, k.r0 - hn, RB);
-                rc = mcf_snowplan_prepare_chunk(k.sp, ch, (hn || hs) ? k.ext.data() : nullptr, (int32_t)hn, (int32_t)hs, *smean, &k.ts, &k.tn);
-                if (rc) { fail_here(rc); break; }
-            }
-        });
-        bar.wait();
-        if (t == 0 && !failed) {
-            double s = 0, n = 0;
-            for (const Block& k : h->blocks) { s += k.ts; n += k.tn; }
-            *tmean = s / n;
-        }
-        bar.wait();
-        guarded([&] {                                         // ---- phase 3: the chunk
-            for (int b = t; b < nb && !failed; b += nt) {
-                Block& k = h->blocks[(size_t)b];
-                const mcf_snowdriver_out bo = block_out(k);
-                const int rc = mcf_snowplan_run_chunk_pitched(k.sp, ch, *tmean, &bo, R);
-                if (rc) { fail_here(rc); break; }
-            }
-        });
-    }
-    if (with_apply3) guarded([&] {
-        const int ns = h->chunk_days * 24;
-        for (int b = t; b < nb && !failed; b += nt) {
-            Block& k = h->blocks[(size_t)b];
-            k.mx.assign((size_t)ns, 0.0); k.cmx.assign((size_t)ns, 0.0); k.mn.assign((size_t)ns, 0.0); k.cmn.assign((size_t)ns, 0.0);
-            int rc = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
-            if (!rc) rc = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
-            if (rc) { fail_here(rc); break; }
-        }
-    });
-    bar.wait();
 }
 
 int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu) {
@@ -297,102 +281,50 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
 
 extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_snowrun** out) {
     try {
-        if (!out) return mcf::api_fail(MCF_ERR_ARG, "null snow-run argument");
+        if (!out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
         int rc = check_create(in, opt, mu);
         if (rc) return rc;
-        int nd = 0;
-        if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
-            return mcf::api_fail(MCF_ERR_NO_DEVICE, "no HIP device available (libmcfhip has no CPU fallback)");
         mcf_snowrun* h = new mcf_snowrun();
         struct Guard { mcf_snowrun* p; ~Guard() { delete p; } } guard{h};
-        if (!mu) {
-            if (opt->device < 0 || opt->device >= nd) return mcf::api_fail(MCF_ERR_ARG, "device ordinal out of range");
-            h->devs.push_back(opt->device);
-        } else if (mu->n_devices <= 0) {
-            for (int d = 0; d < nd; ++d) h->devs.push_back(d);
-        } else {
-            if (!mu->devices) return mcf::api_fail(MCF_ERR_ARG, "n_devices > 0 with a null device list");
-            for (int i = 0; i < mu->n_devices; ++i) {
-                if (mu->devices[i] < 0 || mu->devices[i] >= nd) return mcf::api_fail(MCF_ERR_ARG, "device ordinal out of range");
-                h->devs.push_back(mu->devices[i]);
-            }
-        }
+        if ((rc = mcf::device_list(mu, opt->device, &h->devs))) return rc;
         h->grid = *in->grid; h->opt = *opt; h->snow = *in->snow;
         h->af = h->grid.array_forcing != 0;
-        const int64_t R = h->R = h->grid.rows, C = h->C = h->grid.cols;
+        const int64_t R = h->R = h->grid.rows;
+        h->C = h->grid.cols;
         h->T = h->grid.tsteps;
         h->ndays = (int)(h->T / 24);
         const int chunk = h->snow.chunk_steps > 0 ? h->snow.chunk_steps : 120;
         h->chunk_days = chunk / 24;
         h->nchunks = std::max(1, (int)(h->T / chunk));          // `for (day in 1:n5days)`, R/internal.R:2553-2565
-        h->nb = (int)std::min<int64_t>(mu && mu->n_blocks > 0 ? mu->n_blocks : (int)h->devs.size(), R);
-        if (h->af) h->nb = 1;
-        h->nt = (int)std::min<size_t>(h->devs.size(), (size_t)h->nb);
-        h->blocks.resize((size_t)h->nb);
-        if (h->nb > 1) h->surface.assign((size_t)(R * C), 0.0);
+        h->cut(h->af ? 1 : mu ? mu->n_blocks : 0);
         h->snowday.assign((size_t)std::max(h->ndays, h->nchunks * h->chunk_days), 0);
         h->nosnowday.assign(h->snowday.size(), 0);
         if (const char* e = getenv("MCF_SNOW_KEEP_RESERVE_GB")) h->keep_reserve = (int64_t)(atof(e) * 1073741824.0);
         h->keep = getenv("MCF_SNOWRUN_KEEP") != nullptr;
-        const mcf_snow_inputs& base = h->snow.base;
-        rc = run_workers(h, [&](int t, PhaseBarrier& bar, std::atomic<bool>& failed, auto& guarded, auto& fail_here) {
-            guarded([&] {
-                for (int b = t; b < h->nb && !failed; b += h->nt) {
+        rc = mcf::run_workers(h->nt, [&](Worker& w) {
+            w.guarded([&] {
+                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                     Block& k = h->blocks[(size_t)b];
-                    k.device = h->devs[(size_t)t];
-                    k.r0 = R * b / h->nb; k.nr = R * (b + 1) / h->nb - k.r0;
-                    // ---- the block's snow plan
-                    mcf_snowdriver_in bi = h->snow;
-                    if (h->nb > 1) {
-                        gather_rows(k.pai, base.vegp.pai, R, C, k.r0, k.nr); gather_rows(k.hgt, base.vegp.hgt, R, C, k.r0, k.nr);
-                        gather_rows(k.leaft, base.vegp.leaft, R, C, k.r0, k.nr); gather_rows(k.clump, base.vegp.clump, R, C, k.r0, k.nr);
-                        gather_rows(k.dc, base.other.isnowdc, R, C, k.r0, k.nr); gather_rows(k.dg, base.other.isnowdg, R, C, k.r0, k.nr);
-                        gather_rows(k.ac, base.other.isnowac, R, C, k.r0, k.nr); gather_rows(k.ag, base.other.isnowag, R, C, k.r0, k.nr);
-                        gather_rows(k.dtm, h->snow.dtm, R, C, k.r0, k.nr);
-                        bi.base.rows = k.nr;
-                        bi.base.vegp.pai = k.pai.data(); bi.base.vegp.hgt = k.hgt.data(); bi.base.vegp.leaft = k.leaft.data();
-                        bi.base.vegp.clump = k.clump.data();
-                        bi.base.other.isnowdc = k.dc.data(); bi.base.other.isnowdg = k.dg.data();
-                        bi.base.other.isnowac = k.ac.data(); bi.base.other.isnowag = k.ag.data();
-                        bi.dtm = k.dtm.data();
-                    }
-                    bi.base.other.slope = bi.base.other.aspect = bi.base.other.skyview = bi.base.other.wsa = bi.base.other.hor = nullptr;
-                    int rc2 = mcf_snowplan_create(&bi, k.r0, R, k.device, &k.sp);
-                    if (rc2) { fail_here(rc2); break; }
+                    int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
+                    if (rc2) { w.fail(rc2); break; }
                     // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
-                    mcf_grid_inputs sub = h->grid;
-                    sub.rows = k.nr;
-                    sub.row_pitch = R;
-                    auto off = [&](const double*& q) { if (q) q += k.r0; };
-                    off(sub.vegp.hgt); off(sub.vegp.pai); off(sub.vegp.x); off(sub.vegp.gsmax); off(sub.vegp.leafr); off(sub.vegp.leaft);
-                    off(sub.vegp.clump); off(sub.vegp.leafd); off(sub.vegp.paia); off(sub.vegp.leafden);
-                    off(sub.soilc.Smin); off(sub.soilc.Smax); off(sub.soilc.gref); off(sub.soilc.soilb); off(sub.soilc.Psie);
-                    off(sub.soilc.Vq); off(sub.soilc.Vm); off(sub.soilc.Mc); off(sub.soilc.rho); off(sub.soilc.slope);
-                    off(sub.soilc.aspect); off(sub.soilc.twi); off(sub.soilc.svfa); off(sub.soilc.wsa); off(sub.soilc.hor);
-                    if (h->af) {                 // (layered / lat-lon arrays of the array-forcing solver, read through the same pitch)
-                        off(sub.clim.tc); off(sub.clim.es); off(sub.clim.ea); off(sub.clim.tdew); off(sub.clim.pk); off(sub.clim.swdown);
-                        off(sub.clim.difrad); off(sub.clim.lwdown); off(sub.clim.windspeed);
-                        off(sub.pointm.soilm); off(sub.pointm.Tg); off(sub.pointm.Tbp); off(sub.pointm.G); off(sub.pointm.umu);
-                        off(sub.pointm.kp); off(sub.pointm.muGp); off(sub.pointm.dtrp);
-                        off(sub.lats); off(sub.lons);
-                    }
-                    k.gsub = sub;
+                    k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
                     mcf_options o = h->opt;
                     o.device = k.device;
-                    rc2 = mcf_plan_create(&sub, &o, h->chunk_days, 2, &k.plan);
-                    if (rc2) { fail_here(rc2); break; }
-                    if (h->nb > 1 && (rc2 = mcf_plan_twi_partial(k.plan, &k.twi_s, &k.twi_n))) { fail_here(rc2); break; }
+                    rc2 = mcf_plan_create(&k.gsub, &o, h->chunk_days, 2, &k.plan);
+                    if (rc2) { w.fail(rc2); break; }
+                    if (h->nb > 1 && (rc2 = mcf_plan_twi_partial(k.plan, &k.twi_s, &k.twi_n))) { w.fail(rc2); break; }
                     k.kept.assign((size_t)h->nchunks, 0);
                 }
             });
-            bar.wait();
+            w.wait();
             // the solver's one global reduction (src/microclimfCpp.cpp:993-1004): partial sums in block order
-            if (h->nb > 1) guarded([&] {
+            if (h->nb > 1) w.guarded([&] {
                 double s = 0; int64_t n = 0;
                 for (const Block& k : h->blocks) { s += k.twi_s; n += k.twi_n; }
-                for (int b = t; b < h->nb && !failed; b += h->nt) {
+                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                     const int rc2 = mcf_plan_set_twi_mean(h->blocks[(size_t)b].plan, s / (double)n);
-                    if (rc2) { fail_here(rc2); break; }
+                    if (rc2) { w.fail(rc2); break; }
                 }
             });
         });
@@ -401,7 +333,7 @@ extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options*
         *out = h;
         return MCF_OK;
     } catch (const std::exception& e) {
-        return mcf::api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_create: ") + e.what());
+        return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_create: ") + e.what());
     }
 }
 
@@ -412,8 +344,8 @@ extern "C" void mcf_snowrun_destroy(mcf_snowrun* h) { delete h; }
 // runs a second period (mcf_snowrun_pass1 again) allocates nothing — where allocating 10 GB costs more than re-running the chunk
 // (the struct's comment), keeping pays from the second period on, or on the first when the caller wants `smod` anyway.
 extern "C" int mcf_snowrun_keep(mcf_snowrun* h, int64_t bytes) {
-    if (!h) return mcf::api_fail(MCF_ERR_ARG, "null snow run");
-    if (bytes < 0) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowrun_keep: bytes >= 0");
+    if (!h) return api_fail(MCF_ERR_ARG, "null snow run");
+    if (bytes < 0) return api_fail(MCF_ERR_ARG, "mcf_snowrun_keep: bytes >= 0");
     h->keep = bytes > 0;
     for (Block& k : h->blocks) {
         const int rc = mcf_snowplan_set_keep_budget(k.sp, bytes > 0 ? (int64_t)((double)bytes * (double)k.nr / (double)h->R) : 0);
@@ -424,33 +356,32 @@ extern "C" int mcf_snowrun_keep(mcf_snowrun* h, int64_t bytes) {
 
 extern "C" int32_t mcf_snowrun_days(const mcf_snowrun* h) { return h ? h->ndays : 0; }
 extern "C" int mcf_snowrun_stats(const mcf_snowrun* h, int64_t stats[4]) {
-    if (!h || !stats) return mcf::api_fail(MCF_ERR_ARG, "null argument");
+    if (!h || !stats) return api_fail(MCF_ERR_ARG, "null argument");
     stats[0] = h->st_tile_days; stats[1] = h->st_tile_days_left_out; stats[2] = h->st_chunks_kept; stats[3] = h->st_chunks_rerun;
     return MCF_OK;
 }
 
 extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod, int32_t* snowday, int32_t* nosnowday) {
-    if (!h) return mcf::api_fail(MCF_ERR_ARG, "null snow run");
+    if (!h) return api_fail(MCF_ERR_ARG, "null snow run");
     try {
         const int cd = h->chunk_days, ns = cd * 24;
         std::fill(h->snowday.begin(), h->snowday.end(), 0);
         std::fill(h->nosnowday.begin(), h->nosnowday.end(), 0);
         h->pass1_done = false;
-        double smean = 0, tmean = 0;
-        const int rc = run_workers(h, [&](int t, PhaseBarrier& bar, std::atomic<bool>& failed, auto& guarded, auto& fail_here) {
-            guarded([&] {
-                for (int b = t; b < h->nb && !failed; b += h->nt) {
+        const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
+            w.guarded([&] {
+                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                     Block& k = h->blocks[(size_t)b];
                     int rc2 = mcf_snowplan_reset(k.sp);
                     if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
-                    if (rc2) { fail_here(rc2); break; }
+                    if (rc2) { w.fail(rc2); break; }
                     std::fill(k.kept.begin(), k.kept.end(), 0);
                 }
             });
-            bar.wait();
+            w.wait();
             for (int ch = 0; ch < h->nchunks; ++ch) {
-                guarded([&] {
-                    for (int b = t; b < h->nb && !failed; b += h->nt) {
+                w.guarded([&] {
+                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                         Block& k = h->blocks[(size_t)b];
                         int rc2 = mcf_snowplan_checkpoint(k.sp, ch);      // pass 2 starts any chunk from here
                         // a chunk that could not stay in HBM is re-run by pass 2 if it holds a snow day: unless the caller wants the snow
@@ -458,13 +389,21 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                         int32_t room = 0;
                         if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
                         if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u));
-                        if (rc2) { fail_here(rc2); break; }
+                        if (rc2) { w.fail(rc2); break; }
                     }
                 });
-                snow_chunk(h, t, ch, bar, failed, guarded, fail_here, true, smod, &smean, &tmean);
-                // (under `guarded` like every phase body: an exception here — the vectors allocate — must neither leave the thread
-                // while the others are joinable nor skip the barrier below)
-                if (t == 0) guarded([&] {
+                snow_chunk(*h, w, ch, smod);
+                w.guarded([&] {                     // applycpp3 max / min of totalSWE
+                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
+                        Block& k = h->blocks[(size_t)b];
+                        k.mx.assign((size_t)ns, 0.0); k.cmx.assign((size_t)ns, 0.0); k.mn.assign((size_t)ns, 0.0); k.cmn.assign((size_t)ns, 0.0);
+                        int rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
+                        if (!rc2) rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
+                        if (rc2) { w.fail(rc2); break; }
+                    }
+                });
+                w.wait();
+                if (w.t == 0) w.guarded([&] {
                     // extremes over the blocks (max / min skip blocks whose step held no value), then the chunk's day classes
                     std::vector<double> mx((size_t)ns, -INFINITY), mn((size_t)ns, INFINITY);
                     for (const Block& k : h->blocks)
@@ -474,20 +413,20 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                         }
                     snowdays_of(mx.data(), mn.data(), cd, &h->snowday[(size_t)(ch * cd)], &h->nosnowday[(size_t)(ch * cd)]);
                 });
-                bar.wait();
-                guarded([&] {
+                w.wait();
+                w.guarded([&] {
                     bool any = false;
                     for (int d = 0; d < cd; ++d) any |= h->snowday[(size_t)(ch * cd + d)] != 0;
-                    for (int b = t; b < h->nb && !failed; b += h->nt) {
+                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                         Block& k = h->blocks[(size_t)b];
                         int rc2 = mcf_snowplan_meand_accumulate(k.sp, ch, &h->snowday[(size_t)(ch * cd)]);
                         int32_t kept = 0;
                         if (!rc2 && any && h->keep) rc2 = mcf_snowplan_keep_chunk(k.sp, ch, h->keep_reserve, &kept);
-                        if (rc2) { fail_here(rc2); break; }
+                        if (rc2) { w.fail(rc2); break; }
                         k.kept[(size_t)ch] = (char)kept;
                     }
                 });
-                bar.wait();
+                w.wait();
             }
         });
         if (rc) return rc;
@@ -499,18 +438,18 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
         if (nosnowday) memcpy(nosnowday, h->nosnowday.data(), (size_t)h->ndays * 4);
         return MCF_OK;
     } catch (const std::exception& e) {
-        return mcf::api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass1: ") + e.what());
+        return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass1: ") + e.what());
     }
 }
 
 extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, double mat, mcf_outputs* out) {
-    if (!h || !out) return mcf::api_fail(MCF_ERR_ARG, "null snow-run argument");
-    if (!h->pass1_done) return mcf::api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
+    if (!h || !out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
+    if (!h->pass1_done) return api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
     try {
         const int cd = h->chunk_days, ndays = h->ndays;
         const int64_t R = h->R, C = h->C, T = h->T, HS = R * C;
         for (int v = 0; v < MCF_NOUT; ++v)
-            if (h->opt.out[v] && !out->var[v]) return mcf::api_fail(MCF_ERR_ARG, "null output array for a requested variable");
+            if (h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
         // ---- day lists
         std::vector<int> sdays, ndays_;
         for (int d = 0; d < ndays; ++d) {
@@ -532,22 +471,22 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
         std::vector<double> hr, ser[10];
         mcf_snow_inputs sub{};
         if (!sdays.empty()) {
-            if (!micro) return mcf::api_fail(MCF_ERR_ARG, "snow run: the year has snow days, gridmicrosnow1's inputs are needed");
+            if (!micro) return api_fail(MCF_ERR_ARG, "snow run: the year has snow days, gridmicrosnow1's inputs are needed");
             if (micro->rows != R || micro->cols != C || micro->tsteps != T || (micro->array_forcing != 0) != h->af)
-                return mcf::api_fail(MCF_ERR_ARG, "snow run: gridmicrosnow's inputs must be the whole series on the whole raster, in the run's weather geometry");
+                return api_fail(MCF_ERR_ARG, "snow run: gridmicrosnow's inputs must be the whole series on the whole raster, in the run's weather geometry");
             const mcf_snow_climate& cl = micro->clim;
             const double* src[10] = {cl.temp, cl.relhum, cl.pres, cl.swdown, cl.difrad, cl.lwdown, cl.windspeed, cl.winddir, cl.precip, cl.umu};
             static const char* nm[10] = {"temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed", "winddir", "precip", "umu"};
             for (int f = 0; f < 10; ++f)
-                if (!src[f]) return mcf::api_fail(MCF_ERR_ARG, std::string("null input: gridmicrosnow1 weather$") + nm[f]);
+                if (!src[f]) return api_fail(MCF_ERR_ARG, std::string("null input: gridmicrosnow1 weather$") + nm[f]);
             const mcf_obstime& ob = micro->obstime;
-            if (!ob.year || !ob.month || !ob.day || !ob.hour) return mcf::api_fail(MCF_ERR_ARG, "null obstime");
+            if (!ob.year || !ob.month || !ob.day || !ob.hour) return api_fail(MCF_ERR_ARG, "null obstime");
             const mcf_snow_vegp& vg = micro->vegp;
             const mcf_snow_other& ot = micro->other;
             if (!vg.pai || !vg.hgt || !vg.leaft || !vg.clump || !vg.paia || !vg.leafd || !vg.leafden || !ot.slope || !ot.aspect ||
                 !ot.skyview || !ot.wsa || !ot.hor)
-                return mcf::api_fail(MCF_ERR_ARG, "null input: a gridmicrosnow1 raster");
-            if (outm[MCF_OUT_SOILM] && h->opt.out[MCF_OUT_SOILM] && !ot.Smax) return mcf::api_fail(MCF_ERR_ARG, "soilm requested but other$Smax is null");
+                return api_fail(MCF_ERR_ARG, "null input: a gridmicrosnow1 raster");
+            if (outm[MCF_OUT_SOILM] && h->opt.out[MCF_OUT_SOILM] && !ot.Smax) return api_fail(MCF_ERR_ARG, "soilm requested but other$Smax is null");
             sub = *micro;
             if (!h->af) {      // (array weather: the snow plan takes the whole series and the day map — nine arrays are not copied)
             yr.resize((size_t)TS); mo.resize((size_t)TS); dy.resize((size_t)TS); hr.resize((size_t)TS);
@@ -571,11 +510,10 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
         if (!h->af)
             for (int d : ndays_)
                 for (int hh = 0; hh < 24; ++hh) { const double v = h->grid.clim.tc[(int64_t)d * 24 + hh]; if (v > mxtc) mxtc = v; }
-        const double NA = na_real_host();
-        double smean = 0, tmean = 0;
-        const int rc = run_workers(h, [&](int t, PhaseBarrier& bar, std::atomic<bool>& failed, auto& guarded, auto& fail_here) {
-            guarded([&] {
-                for (int b = t; b < h->nb && !failed; b += h->nt) {
+        const double NA = mcf::na_real_host();
+        const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
+            w.guarded([&] {
+                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                     Block& k = h->blocks[(size_t)b];
                     int rc2 = MCF_OK;
                     if (!sdays.empty()) {
@@ -583,14 +521,14 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
                         if (h->nb > 1) {
                             const mcf_snow_vegp& vg = micro->vegp;
                             const mcf_snow_other& ot = micro->other;
-                            gather_rows(k.m_pai, vg.pai, R, C, k.r0, k.nr); gather_rows(k.m_hgt, vg.hgt, R, C, k.r0, k.nr);
-                            gather_rows(k.m_leaft, vg.leaft, R, C, k.r0, k.nr); gather_rows(k.m_clump, vg.clump, R, C, k.r0, k.nr);
-                            gather_rows(k.m_paia, vg.paia, R, C, k.r0, k.nr); gather_rows(k.m_leafd, vg.leafd, R, C, k.r0, k.nr);
-                            gather_rows(k.m_leafden, vg.leafden, R, C, k.r0, k.nr);
-                            gather_rows(k.m_slope, ot.slope, R, C, k.r0, k.nr); gather_rows(k.m_aspect, ot.aspect, R, C, k.r0, k.nr);
-                            gather_rows(k.m_svf, ot.skyview, R, C, k.r0, k.nr);
-                            gather_rows(k.m_wsa, ot.wsa, R, C, k.r0, k.nr, 8); gather_rows(k.m_hor, ot.hor, R, C, k.r0, k.nr, 24);
-                            if (ot.Smax) gather_rows(k.m_smax, ot.Smax, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_pai, vg.pai, R, C, k.r0, k.nr); mcf::gather_rows(k.m_hgt, vg.hgt, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_leaft, vg.leaft, R, C, k.r0, k.nr); mcf::gather_rows(k.m_clump, vg.clump, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_paia, vg.paia, R, C, k.r0, k.nr); mcf::gather_rows(k.m_leafd, vg.leafd, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_leafden, vg.leafden, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_slope, ot.slope, R, C, k.r0, k.nr); mcf::gather_rows(k.m_aspect, ot.aspect, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_svf, ot.skyview, R, C, k.r0, k.nr);
+                            mcf::gather_rows(k.m_wsa, ot.wsa, R, C, k.r0, k.nr, 8); mcf::gather_rows(k.m_hor, ot.hor, R, C, k.r0, k.nr, 24);
+                            if (ot.Smax) mcf::gather_rows(k.m_smax, ot.Smax, R, C, k.r0, k.nr);
                             bs.rows = k.nr;
                             bs.vegp.pai = k.m_pai.data(); bs.vegp.hgt = k.m_hgt.data(); bs.vegp.leaft = k.m_leaft.data();
                             bs.vegp.clump = k.m_clump.data(); bs.vegp.paia = k.m_paia.data(); bs.vegp.leafd = k.m_leafd.data();
@@ -604,10 +542,10 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
                     if (!rc2 && !ndays_.empty())         // (array weather: per cell, cpp:2467-2471, over the no-snow days)
                         rc2 = h->af ? mcf_plan_set_mxtc_days(k.plan, &k.gsub, h->nosnowday.data(), ndays) : mcf_plan_set_mxtc(k.plan, mxtc);
                     if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, 31u);         // (pass 2's re-runs feed the snow microclimate)
-                    if (rc2) { fail_here(rc2); break; }
+                    if (rc2) { w.fail(rc2); break; }
                 }
             });
-            bar.wait();
+            w.wait();
             // the merged days of a ring slot to the caller: the block's rows in place, through the row pitch
             auto fetch_days = [&](Block& k, int slot, int d0, int nd) -> int {
                 for (int v = 0; v < MCF_NOUT; ++v) {
@@ -680,37 +618,37 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
                 bool has_snow = false, kept_all = true;
                 for (int d = 0; d < cd; ++d) has_snow |= h->snowday[(size_t)(d0 + d)] != 0;
                 for (const Block& k : h->blocks) kept_all = kept_all && k.kept[(size_t)ch];
-                if (t == 0 && has_snow) ++(kept_all ? h->st_chunks_kept : h->st_chunks_rerun);
+                if (w.t == 0 && has_snow) ++(kept_all ? h->st_chunks_kept : h->st_chunks_rerun);
                 if (has_snow && !kept_all) {          // collective: the blocks' surfaces couple through their halos
-                    guarded([&] {
-                        for (int b = t; b < h->nb && !failed; b += h->nt) {
+                    w.guarded([&] {
+                        for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                             const int rc2 = mcf_snowplan_restore(h->blocks[(size_t)b].sp, ch);
-                            if (rc2) { fail_here(rc2); break; }
+                            if (rc2) { w.fail(rc2); break; }
                         }
                     });
-                    bar.wait();
-                    snow_chunk(h, t, ch, bar, failed, guarded, fail_here, false, nullptr, &smean, &tmean);
+                    w.wait();
+                    snow_chunk(*h, w, ch, nullptr);
                 }
-                guarded([&] {
-                    for (int b = t; b < h->nb && !failed; b += h->nt) {
+                w.guarded([&] {
+                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                         Block& k = h->blocks[(size_t)b];
                         int rc2 = solver_days(k, slot, ch, d0, nd, has_snow);
                         if (!rc2 && has_snow) rc2 = mcf_snowplan_microsnow(k.sp, k.plan, ch, slot, &h->nosnowday[(size_t)d0]);
                         if (!rc2 && nd > 0) rc2 = fetch_days(k, slot, d0, nd);
-                        if (rc2) { fail_here(rc2); break; }
+                        if (rc2) { w.fail(rc2); break; }
                     }
                 });
-                bar.wait();
+                w.wait();
             }
             // days past the last whole chunk: the solver's alone
-            guarded([&] {
-                for (int b = t; b < h->nb && !failed; b += h->nt) {
+            w.guarded([&] {
+                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
                     Block& k = h->blocks[(size_t)b];
-                    for (int d0 = h->nchunks * cd; d0 < ndays && !failed; d0 += cd) {
+                    for (int d0 = h->nchunks * cd; d0 < ndays && !w.failed(); d0 += cd) {
                         const int nd = std::min(cd, ndays - d0);
                         int rc2 = solver_days(k, 0, -1, d0, nd, false);
                         if (!rc2) rc2 = fetch_days(k, 0, d0, nd);
-                        if (rc2) { fail_here(rc2); break; }
+                        if (rc2) { w.fail(rc2); break; }
                     }
                     // steps past the last whole day stay NA (src/microclimfCpp.cpp:2116)
                     for (int v = 0; v < MCF_NOUT; ++v)
@@ -722,7 +660,7 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
         });
         return rc;
     } catch (const std::exception& e) {
-        return mcf::api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass2: ") + e.what());
+        return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass2: ") + e.what());
     }
 }
 
@@ -736,16 +674,64 @@ static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt
     return mcf_snowrun_pass2(h, in->micro, in->mat, out);
 }
 extern "C" int mcf_runmicrosnow1(const mcf_microsnow_in* in, const mcf_options* opt, mcf_outputs* out, const mcf_snowdriver_out* smod) {
-    if (in && in->grid && in->grid->array_forcing) return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1 takes data.frame (vector) weather; array weather: mcf_runmicrosnow2");
+    if (in && in->grid && in->grid->array_forcing) return api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1 takes data.frame (vector) weather; array weather: mcf_runmicrosnow2");
     return runmicrosnow1_impl(in, opt, nullptr, out, smod);
 }
 // `.snowmodel2`'s loop + `.runmicrosnow2` (R/internal.R:2950-3008, 3661-3745): the same run with array weather
 extern "C" int mcf_runmicrosnow2(const mcf_microsnow_in* in, const mcf_options* opt, mcf_outputs* out, const mcf_snowdriver_out* smod) {
-    if (in && in->grid && !in->grid->array_forcing) return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow2 takes array weather; data.frame weather: mcf_runmicrosnow1");
+    if (in && in->grid && !in->grid->array_forcing) return api_fail(MCF_ERR_ARG, "mcf_runmicrosnow2 takes array weather; data.frame weather: mcf_runmicrosnow1");
     return runmicrosnow1_impl(in, opt, nullptr, out, smod);
 }
 extern "C" int mcf_runmicrosnow1_multi(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* multi, mcf_outputs* out,
                                        const mcf_snowdriver_out* smod) {
-    if (!multi) return mcf::api_fail(MCF_ERR_ARG, "null argument");
+    if (!multi) return api_fail(MCF_ERR_ARG, "null argument");
     return runmicrosnow1_impl(in, opt, multi, out, smod);
+}
+
+// ---- the snow model alone: `.snowmodel1` / `.snowmodel2`'s chunk loop (mcf_snowmodel1 / 2: one plan on `device`, mu = NULL)
+// or over row blocks of ONE raster held by this process (include/mcf.h mcf_snowmodel1_multi: block b on devices[b % n_devices];
+// EVERY block's plan stays resident, the chunk loop couples the blocks at every chunk)
+static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device) {
+    if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
+    try {
+        SnowBlocks sb;
+        sb.R = in->base.rows; sb.C = in->base.cols;
+        int rc;
+        if (!mu) sb.devs.push_back(device);                        // (mcf_snowplan_create checks it)
+        else if ((rc = mcf::device_list(mu, 0, &sb.devs))) return rc;
+        sb.cut(mu ? mu->n_blocks : 1);
+        rc = mcf::run_workers(sb.nt, [&](Worker& w) {
+            w.guarded([&] {
+                for (int b = w.t; b < sb.nb && !w.failed(); b += sb.nt)
+                    if (const int rc2 = block_snowplan(sb, b, sb.devs[(size_t)w.t], *in)) { w.fail(rc2); break; }
+            });
+        });
+        if (rc) return rc;
+        const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
+        rc = mcf::run_workers(sb.nt, [&](Worker& w) {
+            for (int ch = 0; ch < nchunks; ++ch) snow_chunk(sb, w, ch, out);
+        });
+        if (!rc && !mu && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
+        return rc;
+    } catch (const std::exception& e) {
+        return api_fail(MCF_ERR_NOMEM, std::string("snow driver: ") + e.what());
+    }
+}
+extern "C" int mcf_snowmodel1(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, int32_t device) {
+    if (in && in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel1 takes data.frame (vector) climate; array weather: mcf_snowmodel2");
+    return snowmodel(in, out, nullptr, device);
+}
+extern "C" int mcf_snowmodel2(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, int32_t device) {
+    if (in && !in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel2 takes array weather; data.frame climate: mcf_snowmodel1");
+    return snowmodel(in, out, nullptr, device);
+}
+extern "C" int mcf_snowmodel1_multi(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu) {
+    if (!in || !out || !mu) return api_fail(MCF_ERR_ARG, "null snow driver argument");
+    const mcf_snow_inputs& base = in->base;
+    if (base.rows <= 0 || base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, "snow driver needs the raster and its dtm");
+    const mcf_snow_vegp& vg = base.vegp;
+    const mcf_snow_other& ot = base.other;
+    if (!vg.pai || !vg.hgt || !vg.leaft || !vg.clump || !ot.isnowdc || !ot.isnowdg || !ot.isnowac || !ot.isnowag)
+        return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
+    return snowmodel(in, out, mu, 0);
 }

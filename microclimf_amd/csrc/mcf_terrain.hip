@@ -20,15 +20,11 @@
 
 #include <algorithm>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../include/mcf.h"
+#include "mcf_rowblocks.hpp"
 #include "mcf_terrain.h"
-
-namespace mcf {
-int api_fail(int code, const std::string& msg);   // mcf_api.hip
-}
 
 namespace {
 
@@ -408,10 +404,7 @@ extern "C" int mcf_precompute_terrain(const mcf_terrain_in* in, const mcf_terrai
         snprintf(b, sizeof b, "terrain block needs %lld halo rows (or all rows up to the raster edge)", (long long)need);
         return mcf::api_fail(MCF_ERR_ARG, b);
     }
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
-        return mcf::api_fail(MCF_ERR_NO_DEVICE, "no HIP device available (libmcfhip has no CPU fallback)");
-    if (device < 0 || device >= nd) return mcf::api_fail(MCF_ERR_ARG, "device ordinal out of range");
+    if (const int rc = mcf::check_device(device)) return rc;
     T_TRY(hipSetDevice(device));
 
     const int64_t N = in->rows * in->cols, NB = (in->halo_north + in->rows + in->halo_south) * in->cols;
@@ -450,34 +443,21 @@ extern "C" int mcf_precompute_terrain_multi(const mcf_terrain_in* in, const mcf_
     if (in->rows <= 0 || in->cols <= 0 || !(in->res > 0)) return mcf::api_fail(MCF_ERR_ARG, "bad terrain geometry");
     if (in->halo_north != 0 || in->halo_south != 0 || (in->rows_total > 0 && (in->row0 != 0 || in->rows_total != in->rows)))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_precompute_terrain_multi takes the whole raster (no halos, no placement)");
-    int nd = 0;
-    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0)
-        return mcf::api_fail(MCF_ERR_NO_DEVICE, "no HIP device available (libmcfhip has no CPU fallback)");
     std::vector<int> devs;
-    if (mu->n_devices <= 0) for (int d = 0; d < nd; ++d) devs.push_back(d);
-    else {
-        if (!mu->devices) return mcf::api_fail(MCF_ERR_ARG, "n_devices > 0 with a null device list");
-        for (int i = 0; i < mu->n_devices; ++i) {
-            if (mu->devices[i] < 0 || mu->devices[i] >= nd) return mcf::api_fail(MCF_ERR_ARG, "device ordinal out of range");
-            devs.push_back(mu->devices[i]);
-        }
-    }
+    if (const int rc = mcf::device_list(mu, 0, &devs)) return rc;
     const int64_t R = in->rows, C = in->cols;
     const int nb = (int)std::min<int64_t>(mu->n_blocks > 0 ? mu->n_blocks : (int)devs.size(), R);
+    const int nt = (int)std::min<size_t>(devs.size(), (size_t)nb);
     const int s = in->agg > 0 ? in->agg : 10;
     const int64_t need = out->wsa ? 100 + 2 * s + s / 2 : ((out->hor || out->svfa) ? 100 : 1);     // as mcf_precompute_terrain asks
-    std::vector<int> rcs(devs.size(), MCF_OK);
-    std::vector<std::string> errs(devs.size());
-    std::vector<std::thread> threads;
-    for (size_t t = 0; t < devs.size(); ++t) {
-        threads.emplace_back([&, t] {
+    return mcf::run_workers(nt, [&](mcf::Worker& w) {
+        w.guarded([&] {
             std::vector<double> ext, part[5];
-            for (int b = (int)t; b < nb; b += (int)devs.size()) {
+            for (int b = w.t; b < nb && !w.failed(); b += nt) {
                 const int64_t r0 = R * b / nb, r1 = R * (b + 1) / nb, nr = r1 - r0;
                 if (nr <= 0) continue;
                 const int64_t hn = std::min(need, r0), hs = std::min(need, R - r1), RB = hn + nr + hs;
-                ext.resize((size_t)(RB * C));
-                for (int64_t c = 0; c < C; ++c) memcpy(&ext[(size_t)(RB * c)], in->dtm + (r0 - hn) + R * c, (size_t)RB * 8);
+                mcf::gather_rows(ext, in->dtm, R, C, r0 - hn, RB);
                 mcf_terrain_in bi = *in;
                 bi.rows = nr; bi.halo_north = (int32_t)hn; bi.halo_south = (int32_t)hs; bi.dtm = ext.data();
                 bi.row0 = r0; bi.rows_total = R;
@@ -489,17 +469,11 @@ extern "C" int mcf_precompute_terrain_multi(const mcf_terrain_in* in, const mcf_
                     if (dst[k]) part[k].resize((size_t)(nr * C * layers[k]));
                     *bop[k] = dst[k] ? part[k].data() : nullptr;
                 }
-                const int rc = mcf_precompute_terrain(&bi, &bo, devs[t]);
-                if (rc != MCF_OK) { rcs[t] = rc; errs[t] = mcf_last_error(); return; }
-                for (int k = 0; k < 5; ++k)
-                    if (dst[k])
-                        for (int64_t lc = 0; lc < C * layers[k]; ++lc)      // layer-column lc of the block -> the same one of the raster
-                            memcpy(dst[k] + r0 + R * lc, &part[k][(size_t)(nr * lc)], (size_t)nr * 8);
+                const int rc = mcf_precompute_terrain(&bi, &bo, devs[(size_t)w.t]);
+                if (rc != MCF_OK) { w.fail(rc); return; }
+                for (int k = 0; k < 5; ++k)      // layer-column lc of the block -> the same one of the raster
+                    if (dst[k]) mcf::scatter_rows(dst[k], part[k].data(), R, C, r0, nr, layers[k]);
             }
         });
-    }
-    for (auto& th : threads) th.join();
-    for (size_t t = 0; t < devs.size(); ++t)
-        if (rcs[t] != MCF_OK) return mcf::api_fail(rcs[t], errs[t]);
-    return MCF_OK;
+    });
 }

@@ -129,6 +129,10 @@ def test_row_blocks_and_host_threads(oracle):
     for devices, nb in (([0], 2), ([0, 0], 2)):                               # blocks > devices; two host threads on one device
         multi, smod_m = S.runmicrosnow1(a, snow, micro, MAT, devices=devices, n_blocks=nb, want_smod=True)
         _close(multi, one, 1e-9, f"{nb} blocks on {devices}")
+        smod_b = S.snowmodel1_chunks(sw["obstime"], sw["climdata"], sw["pointm"], sw["vegp"], sw["other"], sw["snowenv"], dtm, 1.0,
+                                     0.02, devices=devices, n_blocks=nb)
+        for k in smod_m:                                                      # the same row blocks, the same chunk loop
+            assert np.array_equal(smod_m[k], smod_b[k], equal_nan=True), (k, nb, devices)
     smod_1 = S.snowmodel1_chunks(sw["obstime"], sw["climdata"], sw["pointm"], sw["vegp"], sw["other"], sw["snowenv"], dtm, 1.0, 0.02)
     for k in smod_m:
         w = smod_1[k]
