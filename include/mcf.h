@@ -50,9 +50,10 @@
 extern "C" {
 #endif
 
-#define MCF_ABI_VERSION 6   /* 2: mcf_grid_inputs grew the coarse-forcing fields; 3: tiled output ring (mcf_plan_ring_layout);
+#define MCF_ABI_VERSION 7   /* 2: mcf_grid_inputs grew the coarse-forcing fields; 3: tiled output ring (mcf_plan_ring_layout);
                              * 4: mcf_nc_spec grew format / deflate_level (zero = the behaviour of version 3); 5: mcf_runmicrosnow1 / mcf_snowrun_*;
-                             * 6: mcf_snowdriver_in grew af_wsa_s (the former `reserved`) / af_wind at its end — read only with array weather */
+                             * 6: mcf_snowdriver_in grew af_wsa_s (the former `reserved`) / af_wind at its end — read only with array weather;
+                             * 7: below ground streamed through day chunks (mcf_plan_create_streamed, mcf_plan_below_prepare) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -273,8 +274,25 @@ int mcf_plan_set_mxtc(mcf_plan *plan, double mxtc);
  * version: mcf_plan_run_days_at accepts a run of days INSIDE the days a slot's forcing was uploaded for, with array forcing. */
 int mcf_plan_set_mxtc_days(mcf_plan *plan, const mcf_grid_inputs *in, const int32_t *dayflag, int32_t ndays);
 /* reqhgt<0: after every day has been solved into slot 0, smooth the stored
- * ground-temperature series into Tz (Tbelowgroundv, cpp:1474-1539). */
+ * ground-temperature series into Tz (Tbelowgroundv, cpp:1474-1539).  Not for a streamed plan (MCF_ERR_STATE). */
 int mcf_plan_belowground(mcf_plan *plan);
+/* Below ground streamed through day chunks.  For reqhgt >= 0 mcf_plan_create_streamed is mcf_plan_create.  For reqhgt < 0 it
+ * keeps the requested ring (tiled, as for reqhgt >= 0: mcf_plan_ring_layout) and allocates nothing of size cells x steps: the
+ * chunk's ground temperature (one more ring slot variable) and O(cells x days) of per-cell state — the damping-depth sum, and
+ * with complete = 1 the hourly sum, the daily means and the series' last 47 hours.  A slot may hold tsteps / 24 + 1 days: the
+ * chunk that ends on the last whole day also leaves the tsteps % 24 steps behind it (Tz only) in its slot, behind its days.
+ * mcf_plan_below_prepare computes that state: complete = 0 a damping-depth pre-pass over the soil-moisture series, complete = 1
+ * a first sweep of the solver over every day (chunks of ring_days through slot 0).  Array forcing: it streams the forcing of
+ * `in` through slot 0 (upload the chunks' forcing again afterwards); `in` may be NULL otherwise.  Then mcf_plan_run_days runs
+ * chunks in day order from day 0 (a chunk starting at day 0 begins a new pass) and each leaves the final Tz — the bits of the
+ * whole-series plan's mcf_plan_belowground — in its slot for mcf_plan_fetch*, mcf_plan_fetch_cells, mcf_plan_fetch_packed and
+ * mcf_nc_write_plan.  Running days before the prepare, out of order or with a gap is MCF_ERR_STATE; the refusals of below-ground
+ * plans (a tile mask, a cell subset, a day offset inside the slot) hold as for mcf_plan_create.  mcf_plan_bytes reports the
+ * device bytes either plan holds.  The one-shot entries take this route for reqhgt < 0 when the whole-series plan does not fit
+ * in free HBM (MCF_BELOW_STREAM=1 forces it, =0 forbids it). */
+int mcf_plan_create_streamed(const mcf_grid_inputs *in, const mcf_options *opt,
+                             int32_t ring_days, int32_t ring_slots, mcf_plan **plan);
+int mcf_plan_below_prepare(mcf_plan *plan, const mcf_grid_inputs *in);
 int mcf_plan_sync(mcf_plan *plan);
 
 /* Copy `nsteps` time steps of variable `var` from ring slot `slot` (starting at

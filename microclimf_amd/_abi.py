@@ -197,9 +197,10 @@ EXPORTS = (
     "mcf_flowacc", "mcf_topidx",
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
     "mcf_snowrun_pass1", "mcf_snowrun_pass2", "mcf_snowplan_run_chunk_pitched", "mcf_snowplan_chunk_af",
+    "mcf_plan_create_streamed", "mcf_plan_below_prepare",
 )
 
-ABI_VERSION = 6     # include/mcf.h MCF_ABI_VERSION this mirror was written against
+ABI_VERSION = 7     # include/mcf.h MCF_ABI_VERSION this mirror was written against
 _lib = None
 
 
@@ -340,6 +341,10 @@ def load() -> C.CDLL:
         lib.mcf_snowplan_microsnow.argtypes = [P, P, C.c_int32, C.c_int32, c_int32_p]
     lib.mcf_plan_belowground.restype = C.c_int
     lib.mcf_plan_belowground.argtypes = [P]
+    lib.mcf_plan_create_streamed.restype = C.c_int
+    lib.mcf_plan_create_streamed.argtypes = [GI, OP, C.c_int32, C.c_int32, C.POINTER(P)]
+    lib.mcf_plan_below_prepare.restype = C.c_int
+    lib.mcf_plan_below_prepare.argtypes = [P, GI]
     lib.mcf_plan_sync.restype = C.c_int
     lib.mcf_plan_sync.argtypes = [P]
     lib.mcf_plan_fetch.restype = C.c_int

@@ -175,14 +175,17 @@ class Plan:
 
     def __init__(self, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp,
                  tfact, complete, mat, out, *, array_forcing=False, ring_days=1, ring_slots=1,
-                 device=0, cells_per_block=0, dfsel=None, coarse=None):
+                 device=0, cells_per_block=0, dfsel=None, coarse=None, stream_below=False):
+        """stream_below: reqhgt < 0 through day chunks (include/mcf.h mcf_plan_create_streamed) — below_prepare() first, then
+        run_days in day order from day 0, each chunk's final Tz in its slot; for reqhgt >= 0 the same plan as without it."""
         self._lib = _abi.load()
         self._m: Marshalled = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
                                       Sminp, Smaxp, tfact, complete, mat, out, array_forcing or coarse is not None, device,
                                       0, cells_per_block, dfsel, coarse)
         self._p = C.c_void_p()
-        _abi.check(self._lib.mcf_plan_create(C.byref(self._m.inputs), C.byref(self._m.options),
-                                             int(ring_days), int(ring_slots), C.byref(self._p)))
+        create = self._lib.mcf_plan_create_streamed if stream_below else self._lib.mcf_plan_create
+        _abi.check(create(C.byref(self._m.inputs), C.byref(self._m.options), int(ring_days), int(ring_slots), C.byref(self._p)))
+        self.stream_below = bool(stream_below)
         self.rows, self.cols, self.tsteps = self._m.rows, self._m.cols, self._m.tsteps
         self.ndays = self.tsteps // 24
         self.array_forcing = bool(array_forcing) or coarse is not None
@@ -256,6 +259,11 @@ class Plan:
 
     def belowground(self):
         _abi.check(self._lib.mcf_plan_belowground(self._p))
+
+    def below_prepare(self):
+        """Streamed below-ground plan: the per-cell state of the whole series (damping-depth pre-pass, or with complete = 1 the
+        solver's first sweep).  Array forcing streams the forcing through slot 0: upload the chunks' forcing again afterwards."""
+        _abi.check(self._lib.mcf_plan_below_prepare(self._p, C.byref(self._m.inputs)))
 
     def sync(self):
         _abi.check(self._lib.mcf_plan_sync(self._p))

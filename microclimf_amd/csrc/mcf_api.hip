@@ -135,6 +135,14 @@ struct mcf_plan {
     // reqhgt < 0
     double *d_tgser = nullptr, *d_ddsum = nullptr, *d_scratch = nullptr;
     const double *d_Tgp = nullptr, *d_Tbp = nullptr;
+    // reqhgt < 0 streamed through day chunks (mcf_plan_create_streamed): the tiled ring, the chunk's Tg ring and per-cell state
+    // (mcf_kernels.h BelowStreamArgs); array forcing with complete = 0: the point model's Tg / Tbp of each slot's days
+    bool bg_stream = false;
+    bool below_ready = false;            // mcf_plan_below_prepare has run
+    int below_next = 0;                  // the day the next chunk has to start on (or 0: a new pass)
+    double *d_tgring = nullptr, *d_hsum = nullptr, *d_dmean = nullptr, *d_ybuf = nullptr, *d_wrap = nullptr, *d_prev = nullptr;
+    double *d_Tgp_slots = nullptr, *d_Tbp_slots = nullptr;      // [slots][ring_days * 24][N]
+    int64_t tg_tile_stride = 0;
     // timing
     bool ktiming = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
@@ -458,8 +466,8 @@ void mcf_plan_destroy(mcf_plan* p) {
     delete p;
 }
 
-int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots,
-                    mcf_plan** out) {
+static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots, bool streamed,
+                       mcf_plan** out) {
     if (!out) return fail(MCF_ERR_ARG, "null plan pointer");
     *out = nullptr;
     int rc = check_inputs(in, opt);
@@ -479,6 +487,7 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
     p->af = in->array_forcing != 0;
     p->coarse = in->array_forcing == 2;
     p->bg = opt->reqhgt < 0.0;
+    p->bg_stream = p->bg && streamed;
     if (p->coarse) {
         if (in->coarse_rows < 1 || in->coarse_cols < 1 || !in->coarse_rowpos || !in->coarse_colpos || !in->coarse_relhum ||
             !in->coarse_winddir)
@@ -526,9 +535,11 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
     const int64_t N = p->N, T = p->tsteps;
     if (ring_slots < 1) ring_slots = 1;
     if (ring_days < 1) ring_days = 1;
-    if (ring_days > std::max(p->ndays, 1)) ring_days = std::max(p->ndays, 1);
+    // (streamed below ground: a slot may hold one day more, for the steps behind the last whole day)
+    const int max_days = p->bg_stream ? (int)std::max<int64_t>((in->tsteps + 23) / 24, 1) : std::max(p->ndays, 1);
+    if (ring_days > max_days) ring_days = max_days;
     // reqhgt < 0 smooths the whole series (incl. steps past the last whole day, which read as 0)
-    if (p->bg) { ring_slots = 1; ring_days = (int)std::max<int64_t>((in->tsteps + 23) / 24, 1); }
+    if (p->bg && !p->bg_stream) { ring_slots = 1; ring_days = (int)std::max<int64_t>((in->tsteps + 23) / 24, 1); }
     // array forcing re-lays a slot's series with one launch row per step (gridDim.y <= 65535): 2730 whole days at most
     if (in->array_forcing == 1 && ring_days > 2730) ring_days = 2730;
     p->ring_days = ring_days; p->ring_slots = ring_slots;
@@ -775,7 +786,7 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
     // ---- output ring
     p->nvars = 0;
     for (int v = 0; v < MCF_NOUT; ++v) p->var_slot[v] = opt->out[v] ? p->nvars++ : -1;
-    p->tiled = !p->bg;
+    p->tiled = !p->bg || p->bg_stream;
     p->ntiles = (N + p->cpb - 1) / p->cpb;
     if (p->tiled) {
         const int64_t blk = mcf::ring_block_doubles(p->cpb);
@@ -789,8 +800,40 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
     if ((rc = dalloc(p, &tmp, (int64_t)ring_slots * p->slot_elems * 8))) return rc;
     p->d_ring = (double*)tmp;
 
+    // ---- below ground streamed through day chunks: O(cells x days) of state, no [N][tsteps] buffer
+    if (p->bg_stream && opt->out[MCF_OUT_TZ]) {
+        const int64_t blk = mcf::ring_block_doubles(p->cpb), nd = std::max(p->ndays, 1);
+        p->tg_tile_stride = (int64_t)ring_days * blk;
+        if ((rc = dalloc(p, &tmp, p->ntiles * p->tg_tile_stride * 8))) return rc;
+        p->d_tgring = (double*)tmp;
+        if ((rc = dalloc(p, &tmp, N * 8))) return rc;
+        p->d_ddsum = (double*)tmp;
+        if (opt->complete) {
+            if ((rc = dalloc(p, &tmp, N * 8))) return rc;
+            p->d_hsum = (double*)tmp;
+            if ((rc = dalloc(p, &tmp, N * nd * 8))) return rc;
+            p->d_dmean = (double*)tmp;
+            if ((rc = dalloc(p, &tmp, N * nd * 8))) return rc;
+            p->d_ybuf = (double*)tmp;
+            if ((rc = dalloc(p, &tmp, N * mcf::kBelowWin * 8))) return rc;
+            p->d_wrap = (double*)tmp;
+            if ((rc = dalloc(p, &tmp, N * mcf::kBelowWin * 8))) return rc;
+            p->d_prev = (double*)tmp;
+        } else if (p->af) {
+            // per cell-step: each slot's days, uploaded with its forcing (mcf_plan_upload_forcing_days)
+            const int64_t n = (int64_t)ring_slots * ring_days * 24 * N;
+            if ((rc = dalloc(p, &tmp, n * 8))) return rc;
+            p->d_Tgp_slots = (double*)tmp;
+            if ((rc = dalloc(p, &tmp, n * 8))) return rc;
+            p->d_Tbp_slots = (double*)tmp;
+            if (!in->pointm.Tg || !in->pointm.Tbp) return fail(MCF_ERR_ARG, "missing input array: pointm$Tg / pointm$Tbp");
+        } else {
+            if ((rc = upload(p, in->pointm.Tg, T, &p->d_Tgp, "pointm$Tg", false))) return rc;
+            if ((rc = upload(p, in->pointm.Tbp, T, &p->d_Tbp, "pointm$Tbp", false))) return rc;
+        }
+    }
     // ---- below-ground series
-    if (p->bg) {
+    if (p->bg && !p->bg_stream) {
         if ((rc = dalloc(p, &tmp, N * std::max<int64_t>(T, 1) * 8))) return rc;
         p->d_tgser = (double*)tmp;
         // steps past the last whole day read as 0 in the reference (std::vector<double> Tg(tsteps))
@@ -810,6 +853,15 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
     guard.p = nullptr;
     *out = p;
     return MCF_OK;
+}
+
+int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots,
+                    mcf_plan** out) {
+    return plan_create(in, opt, ring_days, ring_slots, false, out);
+}
+int mcf_plan_create_streamed(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots,
+                             mcf_plan** out) {
+    return plan_create(in, opt, ring_days, ring_slots, true, out);
 }
 
 }  // extern "C"
@@ -895,6 +947,13 @@ int mcf_plan_upload_forcing_days(mcf_plan* p, const mcf_grid_inputs* in, int32_t
         mcf::launch_tile_series(p->d_force_stage, (int64_t)ndays * 24, v, p->stream);
         HIP_TRY(hipGetLastError());
     }
+    if (p->d_Tgp_slots) {
+        // streamed below ground, complete = 0: the point model's Tg / Tbp of these days, [step][N] as the caller holds them
+        if (!in->pointm.Tg || !in->pointm.Tbp) return fail(MCF_ERR_ARG, "missing input array: pointm$Tg / pointm$Tbp");
+        const int64_t off = (int64_t)slot * p->ring_days * 24 * N, src = p->pitch * p->cols * (int64_t)day0 * 24;
+        HIP_TRY(copy_in(p, p->d_Tgp_slots + off, in->pointm.Tg + src, p->cols * (int64_t)ndays * 24));
+        HIP_TRY(copy_in(p, p->d_Tbp_slots + off, in->pointm.Tbp + src, p->cols * (int64_t)ndays * 24));
+    }
     p->force_day0[slot] = day0;
     p->force_ndays[slot] = ndays;
     return MCF_OK;
@@ -915,7 +974,8 @@ namespace {
 int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0, mcf::SolveArgs& a, bool& fast, bool& soil_daily) {
     if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
     if (day0 < 0 || ndays < 1 || day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
-    if (!p->bg && (slot_day0 < 0 || slot_day0 + ndays > p->ring_days)) return fail(MCF_ERR_ARG, "more days than the ring slot holds");
+    if ((!p->bg || p->bg_stream) && (slot_day0 < 0 || slot_day0 + ndays > p->ring_days))
+        return fail(MCF_ERR_ARG, "more days than the ring slot holds");
     if (slot_day0 != 0 && p->bg) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
     HIP_TRY(hipSetDevice(p->device));
     int rc = ensure_cells(p);
@@ -949,6 +1009,12 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
         a.out_sel |= (uint64_t)(p->var_slot[v] < 0 ? 15 : p->var_slot[v]) << (4 * v);
     a.slot_step0 = p->bg ? (int64_t)day0 * 24 : 0;
     a.tgser = p->d_tgser; a.ddsum = p->d_ddsum;
+    if (p->bg_stream) {
+        // Tg into the chunk's Tg ring, Tz itself is made from it by k_below_chunk; the damping-depth sum only in sweep 1
+        a.out_sel |= (uint64_t)15 << (4 * MCF_OUT_TZ);
+        a.tg_ring = p->d_tgring; a.tg_tile_stride = p->tg_tile_stride;
+        a.ddsum = nullptr;
+    }
     a.day0 = day0; a.ndays = ndays; a.total_days = p->ndays;
     {
         // pass 2 yields Tz (+ tleaf, relhum for reqhgt > 0) and the long-wave fluxes; requests for
@@ -971,7 +1037,137 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
     if (p->coarse) soil_daily = p->coarse_lds;      // (coarse array forcing: the same launch flag selects the LDS-staged taps)
     return MCF_OK;
 }
+
+// ---- below ground streamed through day chunks (DESIGN.md "Below ground in day chunks") ----------------------------------
+// the state of a streamed plan as k_below_* see it; the chunk fields are the caller's
+mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
+    mcf::BelowStreamArgs b{};
+    b.N = p->N; b.tsteps = (int)p->tsteps; b.ndays = p->ndays; b.complete = p->opt.complete; b.hiy = p->hiy;
+    b.reqhgt = p->opt.reqhgt; b.mat = p->opt.mat;
+    b.hgt = p->d_veg[0];
+    b.tg.base = p->d_tgring; b.tg.N = p->N; b.tg.cpb = p->cpb;
+    b.tg.tile_stride = p->tg_tile_stride; b.tg.day_stride = mcf::ring_block_doubles(p->cpb);
+    if (p->var_slot[MCF_OUT_TZ] >= 0) b.tz = ring_view(p, slot, MCF_OUT_TZ);
+    b.ddsum = p->d_ddsum; b.hsum = p->d_hsum; b.dmean = p->d_dmean; b.ybuf = p->d_ybuf; b.wrap = p->d_wrap; b.prev = p->d_prev;
+    b.Tgp = p->d_Tgp; b.Tbp = p->d_Tbp;
+    b.per_cell_pointm = p->af ? 1 : 0;
+    return b;
+}
+
+// days [day0, day0 + ndays) of a streamed below-ground plan into `slot`: the solver (Tg into the Tg ring, the other outputs into
+// the slot), then Tz made from Tg and the per-cell state.  Chunks run in day order from day 0; the chunk that ends on the last
+// whole day also writes the tsteps % 24 steps behind it (the slot needs a day more for them).
+int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0) {
+    const bool tz = p->var_slot[MCF_OUT_TZ] >= 0;
+    if (slot_day0 != 0) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
+    if (tz && !p->below_ready)
+        return fail(MCF_ERR_STATE, "streamed below-ground plan: call mcf_plan_below_prepare before running days");
+    if (tz && day0 != 0 && day0 != p->below_next)
+        return fail(MCF_ERR_STATE, "streamed below-ground plan: chunks run in day order from day 0 without gaps (expected day " +
+                                   std::to_string(p->below_next) + " or 0, got " + std::to_string(day0) + ")");
+    mcf::SolveArgs a{};
+    bool fast = false, soil_daily = false;
+    int rc = solve_args(p, day0, ndays, slot, 0, a, fast, soil_daily);
+    if (rc) return rc;
+    const bool tail = day0 + ndays == p->ndays && p->tsteps > (int64_t)p->ndays * 24;
+    if (tz && tail && ndays + 1 > p->ring_days)
+        return fail(MCF_ERR_ARG, "streamed below-ground plan: the chunk that ends on the last whole day needs one day more in its "
+                                 "slot, for the steps behind that day");
+    auto launch = [&]() {
+        mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
+        ++p->slow_launches;
+        if (!tz) return;
+        mcf::BelowStreamArgs b = below_args(p, slot);
+        b.day0 = day0; b.ndays_chunk = ndays; b.tail = tail ? 1 : 0;
+        if (p->d_Tgp_slots) {      // the slot's point-model series start at the slot's first uploaded day
+            const int64_t off = ((int64_t)slot * p->ring_days * 24 + (int64_t)(day0 - p->force_day0[slot]) * 24) * p->N;
+            b.Tgp = p->d_Tgp_slots + off; b.Tbp = p->d_Tbp_slots + off;
+        }
+        mcf::launch_below_chunk(b, p->stream);
+    };
+    if (p->ktiming) {
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, p->stream));
+        launch();
+        HIP_TRY(hipEventRecord(e1, p->stream));
+        p->kev.emplace_back(e0, e1);
+    } else {
+        launch();
+    }
+    HIP_TRY(hipGetLastError());
+    p->below_next = day0 + ndays;
+    return MCF_OK;
+}
 }  // namespace
+
+int mcf_plan_below_prepare(mcf_plan* p, const mcf_grid_inputs* in) {
+    if (!p) return fail(MCF_ERR_ARG, "null plan");
+    if (!p->bg_stream)
+        return fail(MCF_ERR_STATE, "mcf_plan_below_prepare needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
+    HIP_TRY(hipSetDevice(p->device));
+    p->below_ready = false;
+    p->below_next = 0;
+    if (p->var_slot[MCF_OUT_TZ] < 0) { p->below_ready = true; return MCF_OK; }      // cpp:2307 `&& out[0]`
+    const bool upload_days = p->af && !p->coarse;
+    if (upload_days && !in) return fail(MCF_ERR_ARG, "array forcing: mcf_plan_below_prepare streams the forcing and needs the inputs");
+    int rc = ensure_cells(p);
+    if (rc) return rc;
+    const int64_t N = p->N;
+    HIP_TRY(hipMemsetAsync(p->d_ddsum, 0, (size_t)N * 8, p->stream));
+    const bool complete = p->opt.complete != 0;
+    if (complete) {
+        HIP_TRY(hipMemsetAsync(p->d_hsum, 0, (size_t)N * 8, p->stream));
+        HIP_TRY(hipMemsetAsync(p->d_wrap, 0, (size_t)(N * mcf::kBelowWin) * 8, p->stream));
+    }
+    if (!complete && !p->af) {
+        // the damping-depth pre-pass over the whole series from the time table
+        mcf::BelowDDArgs d{};
+        d.N = N; d.cellc = p->d_cellc; d.ntiles_total = p->ntiles; d.cpb = p->cpb; d.daylayer = p->d_daylayer; d.tt = p->d_tt;
+        d.day0 = 0; d.ndays = p->ndays; d.ddsum = p->d_ddsum;
+        mcf::launch_below_dd(d, p->stream);
+        HIP_TRY(hipGetLastError());
+    } else {
+        // chunk by chunk through slot 0: the pre-pass on the uploaded forcing (complete = 0), or sweep 1 — the solver with the
+        // damping-depth sum on and its Tg folded into the per-cell state (complete = 1)
+        const int chunk = std::max(1, std::min(p->ring_days, std::max(p->ndays, 1)));
+        for (int d0 = 0; d0 < p->ndays; d0 += chunk) {
+            const int nd = std::min(chunk, p->ndays - d0);
+            if (upload_days && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
+            if (!complete) {
+                mcf::BelowDDArgs d{};
+                d.N = N; d.cellc = p->d_cellc; d.ntiles_total = p->ntiles; d.cpb = p->cpb; d.daylayer = p->d_daylayer;
+                d.af_base = p->d_force; d.af_tile_stride = p->force_tile_stride; d.af_day_stride = p->force_day_stride;
+                d.day0 = d0; d.ndays = nd; d.ddsum = p->d_ddsum;
+                mcf::launch_below_dd(d, p->stream);
+            } else {
+                mcf::SolveArgs a{};
+                bool fast = false, soil_daily = false;
+                if ((rc = solve_args(p, d0, nd, 0, 0, a, fast, soil_daily))) return rc;
+                a.out_sel = ~(uint64_t)0;       // nothing into the ring
+                a.ddsum = p->d_ddsum;
+                mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
+                mcf::BelowStreamArgs b = below_args(p, 0);
+                b.day0 = d0; b.ndays_chunk = nd;
+                mcf::launch_below_acc(b, p->stream);
+            }
+            HIP_TRY(hipGetLastError());
+        }
+        if (complete) {
+            mcf::BelowStreamArgs b = below_args(p, 0);
+            mcf::launch_below_finish(b, p->stream);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if (upload_days) {      // slot 0's forcing now holds the last chunk of the pass: the caller uploads again
+        p->force_day0[0] = -1;
+        p->force_ndays[0] = 0;
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->below_ready = true;
+    return MCF_OK;
+}
 
 int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0, const uint8_t* skip_tile,
                              int64_t n_skip_tile) {
@@ -979,6 +1175,7 @@ int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t s
     if (skip_tile && (p->bg || p->af)) return fail(MCF_ERR_ARG, "a tile mask needs vector forcing and reqhgt >= 0");
     if (skip_tile && n_skip_tile != (p->ntiles > 0 ? p->ntiles : (p->N + p->cpb - 1) / p->cpb))
         return fail(MCF_ERR_ARG, "the tile mask's length is not the plan's number of tiles");
+    if (p->bg_stream) return run_below_chunk(p, day0, ndays, slot, slot_day0);
     mcf::SolveArgs a{};
     bool fast = false, soil_daily = false;
     int rc = solve_args(p, day0, ndays, slot, slot_day0, a, fast, soil_daily);
@@ -1203,6 +1400,9 @@ int mcf_plan_dispatch_stats(mcf_plan* p, mcf_dispatch_stats* st) {
 int mcf_plan_belowground(mcf_plan* p) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
     if (!p->bg) return fail(MCF_ERR_STATE, "reqhgt >= 0: nothing to smooth");
+    if (p->bg_stream)
+        return fail(MCF_ERR_STATE, "mcf_plan_belowground: a streamed plan leaves the final Tz in each chunk's slot "
+                                   "(mcf_plan_below_prepare, then mcf_plan_run_days in day order)");
     if (p->var_slot[MCF_OUT_TZ] < 0) return MCF_OK;                      // cpp:2307 `&& out[0]`
     HIP_TRY(hipSetDevice(p->device));
     mcf::BelowArgs b{};
@@ -1753,7 +1953,23 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     const int ndays = (int)(T / 24);
     int nvars = 0;
     for (int v = 0; v < MCF_NOUT; ++v) nvars += opt->out[v] ? 1 : 0;
-    const bool bg = opt->reqhgt < 0.0;
+    // reqhgt < 0: the whole-series plan ([N][tsteps] Tg plus a linear output ring of every step), or — when that does not fit in
+    // free HBM, or MCF_BELOW_STREAM=1 — the plan streamed through day chunks; the same bits either way.  MCF_BELOW_STREAM=0: the
+    // whole-series plan always.
+    bool stream_bg = false;
+    if (opt->reqhgt < 0.0 && ndays > 0) {
+        const char* env = getenv("MCF_BELOW_STREAM");
+        if (env && env[0] == '1') stream_bg = true;
+        else if (!(env && env[0] == '0')) {
+            size_t fr = 0, tot = 0;
+            HIP_TRY(hipMemGetInfo(&fr, &tot));
+            const double whole = (double)N * 8 * ((double)T * (1 + std::max(nvars, 1)) + 2.0 * ndays) +
+                                 (in->array_forcing == 1 ? (opt->complete ? 16.0 : 18.0) * N * T * 8 : 0.0);    // forcing ring, Tg / Tbp
+            stream_bg = whole > 0.8 * (double)fr / std::max(sharers, 1);
+        }
+    }
+    const bool bg = opt->reqhgt < 0.0 && !stream_bg;
+    const bool tail = stream_bg && T > (int64_t)ndays * 24;      // the steps behind the last whole day: one day more per slot
     // ---- chunk size from free HBM
     int chunk = opt->days_per_chunk;
     if (bg) {
@@ -1763,6 +1979,10 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
         HIP_TRY(hipMemGetInfo(&fr, &tot));
         double per_day = (double)N * 24 * 8 * (nvars + (in->array_forcing ? 15 : 0));
         double budget = 0.6 * (double)fr / std::max(sharers, 1) - (double)N * 8 * 200;
+        if (stream_bg) {      // the chunk's Tg ring (and, array forcing with complete = 0, the point model's Tg / Tbp), the per-cell state
+            per_day += (double)N * 24 * 8 * (1 + (in->array_forcing == 1 && !opt->complete ? 2 : 0));
+            budget -= (double)N * 8 * (2.0 * ndays + 2 * mcf::kBelowWin + 2) + (tail ? per_day : 0.0);
+        }
         chunk = (int)std::max(1.0, std::min((double)std::max(ndays, 1), budget / std::max(per_day, 1.0)));
         chunk = std::min(chunk, 64);
     }
@@ -1771,10 +1991,11 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now(), t_solve = 0, t_fetch = 0;
     mcf_plan* p = nullptr;
-    rc = mcf_plan_create(in, opt, chunk, 1, &p);
+    rc = stream_bg ? mcf_plan_create_streamed(in, opt, chunk + (tail ? 1 : 0), 1, &p) : mcf_plan_create(in, opt, chunk, 1, &p);
     if (rc) return rc;
     struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
+    if (stream_bg && (rc = mcf_plan_below_prepare(p, in))) return rc;
     double t_create = now() - t0;
     for (int d0 = 0; d0 < ndays; d0 += chunk) {
         int nd = std::min(chunk, ndays - d0);
@@ -1791,8 +2012,8 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
         if (timing) t_fetch += now() - ta;
     }
     if (timing)
-        fprintf(stderr, "[mcf] one-shot: chunk %d days, plan create %.3f s, solve %.3f s, fetch %.3f s\n", chunk,
-                t_create, t_solve, t_fetch);
+        fprintf(stderr, "[mcf] one-shot: chunk %d days%s, plan create %.3f s, solve %.3f s, fetch %.3f s\n", chunk,
+                stream_bg ? " (below ground streamed)" : "", t_create, t_solve, t_fetch);
     if (bg && ndays > 0) {
         for (int v = 0; v < MCF_NOUT; ++v)
             if (opt->out[v] && v != MCF_OUT_TZ)
@@ -1809,6 +2030,13 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
         // Tbelowgroundv runs over all tsteps (cpp:2314-2319)
         if ((rc = mcf_plan_belowground(p))) return rc;
         if ((rc = mcf_plan_fetch_pitched(p, 0, MCF_OUT_TZ, 0, T, out->var[MCF_OUT_TZ], pitch))) return rc;
+    }
+    if (tail && opt->out[MCF_OUT_TZ]) {
+        // ... whose steps behind the last whole day the last chunk left in its slot, behind that chunk's days
+        const int last = (ndays - 1) / chunk * chunk, nd = ndays - last;
+        if ((rc = mcf_plan_fetch_pitched(p, 0, MCF_OUT_TZ, (int64_t)nd * 24, T - (int64_t)ndays * 24,
+                                         out->var[MCF_OUT_TZ] + HS * (int64_t)ndays * 24, pitch)))
+            return rc;
     }
     return mcf_plan_sync(p);
 }

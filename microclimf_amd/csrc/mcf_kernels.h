@@ -145,6 +145,12 @@ struct SolveArgs {
     int32_t* fix_list;      // [fix_cap]
     int32_t fix_cap;
     Globals g;
+    // reqhgt < 0, streamed plan (launch_solve_bg_tiled): the other outputs go to the TILED ring as for reqhgt >= 0 and the
+    // ground temperature Tg of day d of the launch to the block at tg_ring + tile * tg_tile_stride + d * ring_block_doubles,
+    // lane order (ring_pos); 0 where the cell is not solved.  ddsum: added to as above, or null (not summed).  (Last: the
+    // other instantiations read the fields above at the offsets they always had.)
+    double* tg_ring;
+    int64_t tg_tile_stride;
 };
 
 struct BelowArgs {
@@ -158,6 +164,58 @@ struct BelowArgs {
     double* scratch;             // [N][2*ndays]
     double* tz;                  // [N][tsteps]
 };
+
+// ---- below ground, streamed through day chunks (mcf_plan_create_streamed; DESIGN.md "Below ground in day chunks") ----------
+// Tbelowgroundv (cpp:1474-1539) of k_belowground, made from per-cell state of O(days) instead of the [N][tsteps] series.
+// Per-cell state, every buffer [rows][N] (cell fastest):
+//   ddsum [1]      sum of the damping depth DD over every solved step (the pre-pass or sweep 1), in k_solve's order
+//   hsum  [1]      complete: Tg summed over the steps in step order (meanT of n >= tsteps), tail zeros included
+//   dmean [ndays]  complete: the days' means (24-sums / 24); k_below_finish turns them into the circular n/24-day means y
+//   wrap  [47]     complete: Tg of the series' last 47 steps (step tsteps - 47 + j; 0 past the last whole day)
+//   prev  [47]     complete, sweep 2: Tg of the 47 steps in front of the chunk being transformed
+constexpr int kBelowWin = 47;
+struct BelowStreamArgs {
+    int64_t N;
+    int32_t tsteps, ndays, complete, hiy;
+    double reqhgt, mat;
+    const double* hgt;           // [N] (the NA test of k_belowground)
+    RingView tg;                 // the chunk's Tg: step 0 = the chunk's first step
+    RingView tz;                 // the slot's Tz view (written), step 0 = the chunk's first step
+    int32_t day0, ndays_chunk;   // the chunk: first day, whole days
+    int32_t tail;                // 1: the chunk ends on the last whole day and the slot takes the tsteps % 24 steps behind it
+    double* ddsum;
+    double* hsum;
+    double* dmean;               // [ndays][N]: daily means, after k_below_finish the circular means y
+    double* ybuf;                // [ndays][N] scratch of k_below_finish
+    double* wrap;                // [47][N]
+    double* prev;                // [47][N]
+    // complete == 0: the point model's Tg / Tbp — [tsteps] (vector forcing, step index absolute) or the chunk's [steps][N]
+    // (array forcing, step index relative to the chunk)
+    const double *Tgp, *Tbp;
+    int32_t per_cell_pointm;
+};
+// complete = 0: ddsum += DD over days [day0, day0 + ndays_chunk) from the soil moisture alone (soil_spread, soil_ksoil,
+// soil_damping: the functions pass 1 and 2 use), in k_solve's order.  Vector forcing reads the time table, array forcing the
+// slot's tiled forcing ring (the chunk's days).
+struct BelowDDArgs {
+    int64_t N;
+    const double* cellc;       // tile-major constant table
+    int64_t ntiles_total;
+    int32_t cpb;
+    const int32_t* daylayer;   // or null
+    const double* tt;          // vector forcing: [ndays][TF_COUNT][24]
+    const double* af_base;     // array forcing: the chunk's first day in the slot's forcing ring; else null
+    int64_t af_tile_stride, af_day_stride;
+    int32_t day0, ndays;
+    double* ddsum;
+};
+void launch_below_dd(const BelowDDArgs& a, hipStream_t s);
+// sweep 1 (complete = 1): fold the chunk's Tg into hsum, dmean and wrap
+void launch_below_acc(const BelowStreamArgs& a, hipStream_t s);
+// after the last chunk of sweep 1 / the pre-pass: tail zeros into hsum and wrap, dmean -> y for the cells of 48 < n < tsteps
+void launch_below_finish(const BelowStreamArgs& a, hipStream_t s);
+// sweep 2 / the day-local transform: the chunk's Tz into the slot; then (complete) prev <- the chunk's last 47 steps
+void launch_below_chunk(const BelowStreamArgs& a, hipStream_t s);
 
 struct BioclimArgs {
     int64_t N;
@@ -239,6 +297,9 @@ void launch_mxtc(const double* tc, int64_t N, int nsteps, double* mx, hipStream_
 // soil_daily: every day of the launch carries kSoilDaily (vector forcing): the per cell-day soil state is computed once per
 // tile and day and shared through LDS
 void launch_solve(const SolveArgs& a, int cells_per_block, bool af, bool bg, bool fast, bool soil_daily, hipStream_t s);
+// reqhgt < 0 of a streamed plan: the tiled-ring instantiation (SolveArgs tg_ring); the reference-form clamps, no shared soil state,
+// exactly the arithmetic of launch_solve's bg instantiation
+void launch_solve_bg_tiled(const SolveArgs& a, int cells_per_block, bool af, hipStream_t s);
 // out[t] = 1 if every valid cell of tile t (cpb consecutive cells) is FL_REGULAR in all layers
 void launch_tile_regular(const double* cellc, int64_t N, int layers, int cpb, uint8_t* out, hipStream_t s);
 // A launch over a SUBSET of the cells (mcf_plan_run_days_cells): the wanted cells gathered into dense tiles of their own.

@@ -462,7 +462,9 @@ __global__ __launch_bounds__(256) void k_mxtc_coarse(const double* __restrict__ 
 // ------------------------------------------------------------------------------------
 // The solver.  Workgroup = one tile of CPB consecutive cells x 24 hours, one lane per (cell, hour).
 //   AF   0 vector forcing, 1 array forcing (runmicro2Cpp geometry), 2 coarse array forcing
-//   BG   reqhgt < 0: store the ground temperature series and the damping-depth sum
+//   BG   reqhgt < 0: store the ground temperature series and the damping-depth sum — 1: into the linear [N][tsteps] series
+//        (the whole-series plan), 2: Tg into the chunk's TILED Tg ring, the other outputs into the tiled output ring (the
+//        streamed plan, k_below_*); the same arithmetic either way
 //
 // Output ring.  reqhgt >= 0 writes the TILED ring: the values one workgroup produces for one variable on one day —
 // CPB cells x 24 hours — form one block of ring_block_doubles(CPB) doubles in the workgroup's own lane order
@@ -484,7 +486,7 @@ static_assert(solve_threads(21) == 512 && solve_threads(32) == 768, "ring_block_
 //   F   fast clamps (mcf_device.hpp `cap`): only for tiles / days the host has classified REGULAR; a workgroup in which a
 //       canary trips appends its tile to a.fix_list and k_solve_fix redoes the tile's days of this launch with F = false
 //   SSREQ  per cell-day soil state shared through LDS (mcf_device.hpp SoilDay): only for launches whose days are all kSoilDaily
-template <int CPB, int AF, bool BG, bool F, bool SSREQ>
+template <int CPB, int AF, int BG, bool F, bool SSREQ>
 __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t tile, const int day0, const int ndays, const int rot) {
     constexpr int NT = solve_threads(CPB);
     static_assert(NT == RING_BLOCK(CPB), "tile-day block = one value per lane");
@@ -735,7 +737,9 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
     enter_layer(day0);
     // the tile's first block of this launch in the tiled ring (uniform: SGPRs); a day's ten stores are
     // [block base + variable slab * block] + pos
-    double* ring_day = BG ? nullptr : a.out_base + tile * a.out_tile_stride + (int64_t)a.slot_day0 * a.out_day_stride;
+    double* ring_day = BG == 1 ? nullptr : a.out_base + tile * a.out_tile_stride + (int64_t)a.slot_day0 * a.out_day_stride;
+    // BG 2: the tile's Tg block of the day; null when Tz was not requested (no Tg ring)
+    double* tg_day = (BG == 2 && a.tg_ring) ? a.tg_ring + tile * a.tg_tile_stride : nullptr;
     for (int dl = 0; dl < ndays; ++dl, ++run) {
         const int dabs = day0 + dl;
         // the tile's cell constants are restaged whenever the day's vegetation layer changes — workgroup-uniform and rare
@@ -755,11 +759,11 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
         uint64_t osel = a.out_sel;
         asm volatile("" : "+s"(osel));
         double* lin = nullptr;                 // linear ring (reqhgt < 0): the lane's element of slab 0
-        if (BG) lin = a.out_base + (c + N * (a.slot_step0 + kl));
+        if (BG == 1) lin = a.out_base + (c + N * (a.slot_step0 + kl));
         auto put = [&](int v, double val) {
             const unsigned sel = (unsigned)(osel >> (4 * v)) & 15u;
             if (sel == 15u) return;
-            if (BG) { if (in_grid) lin[(int64_t)sel * a.out_stride] = val; }
+            if (BG == 1) { if (in_grid) lin[(int64_t)sel * a.out_stride] = val; }
             else {
                 // SGPR base + the lane's 32-bit byte offset (global_store ... v_off, v_data, s[base]): no vector arithmetic per
                 // store.  The empty asm keeps the zero-extension of the offset in the store's own basic block, where
@@ -949,8 +953,11 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
             if (AF) derive_time_af_pass2(tv);
             if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
             else pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
-            if (BG) {
+            if (BG == 1) {
                 a.tgser[c + N * ((int64_t)dabs * 24 + hr)] = p2.Tg;
+                s_dd[hr * CPB + cl] = p2.DD;
+            } else if (BG == 2) {
+                *(double*)((char*)tg_day + posb) = p2.Tg;
                 s_dd[hr * CPB + cl] = p2.DD;
             } else {
                 const bool pos_h = g.reqhgt > 0.0;
@@ -960,8 +967,9 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
                 put(7, p2.lwdn);                      // cpp:2298
                 put(9, p2.lwup);                      // cpp:2299
             }
-        } else if (!BG || in_grid) {
+        } else if (BG != 1 || in_grid) {
             if (!BG) put(0, NA);
+            if (BG == 2 && tg_day) *(double*)((char*)tg_day + posb) = 0.0;      // the whole series' zero fill (k_belowground reads it)
             put(1, NA);
             put(2, NA);
             put(7, NA);
@@ -969,19 +977,25 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
         }
         if (BG) {
             // reqhgt < 0 never writes tleaf/relhum/Rlw* (cpp:2272): they stay NA
-            if (valid) {
+            if (valid && (BG == 1 || a.need_pass2)) {
                 put(1, NA);
                 put(2, NA);
                 put(7, NA);
                 put(9, NA);
             }
-            __syncthreads();
-            if (valid && hr == 0) {
-                double s = 0.0;
-                for (int hh = 0; hh < 24; ++hh) s += s_dd[hh * CPB + cl];
-                a.ddsum[c] += s;                                             // cpp:2309-2312
+            if (BG == 1 || a.ddsum) {       // (BG 2: workgroup-uniform)
+                __syncthreads();
+                if (valid && hr == 0) {
+                    double s = 0.0;
+                    for (int hh = 0; hh < 24; ++hh) s += s_dd[hh * CPB + cl];
+                    a.ddsum[c] += s;                                         // cpp:2309-2312
+                }
+                __syncthreads();
             }
-            __syncthreads();
+        }
+        if (BG == 2) {
+            ring_day += a.out_day_stride;
+            if (tg_day) tg_day += NT;
         }
         if (!BG) ring_day += a.out_day_stride;
     }
@@ -1010,7 +1024,7 @@ __device__ __forceinline__ int64_t tile_position(int64_t ntiles) {
 
 // array forcing keeps ~17 more doubles live per lane (forcing values instead of an LDS table):
 // it is built for 3 waves/SIMD (168 VGPRs, no scratch) and run with 32-cell workgroups
-template <int CPB, int AF, bool BG, bool F, bool SSREQ>
+template <int CPB, int AF, int BG, bool F, bool SSREQ>
 __global__ __launch_bounds__(solve_threads(CPB), AF ? MCF_AF_WAVES : MCF_WAVES_PER_EU) void k_solve(SolveArgs a) {
     // every other resident workgroup shifts its wave-to-hour assignment by six hours
     const int rot = (int)((blockIdx.x >> 8) & 1);
@@ -1228,6 +1242,222 @@ __global__ __launch_bounds__(64) void k_belowground(BelowArgs a) {
     // rat = 0/0, so every blend that uses Tzd is NaN; only the `mat` branch has a defined value.
     for (int i = nd * 24; i < m; ++i)
         z[N * i] = (blend_year && !(nb < a.hiy)) ? a.mat : __longlong_as_double(0x7FF8000000000000LL);
+}
+
+// ------------------------------------------------------------------------------------
+// Below ground in day chunks (mcf_kernels.h BelowStreamArgs; DESIGN.md "Below ground in day chunks"): k_belowground's
+// Tbelowgroundv from per-cell state of O(days).  Every sum is k_belowground's, term for term and in its order, so the
+// streamed plan's Tz has the whole-series plan's bits.  One lane per cell (per cell-day in k_below_chunk), cells along the
+// lanes: the per-cell state rows [rows][N] are read and written in whole lines.
+
+// complete = 0: the damping-depth sum of days [day0, day0 + ndays) without the solver — soilm, ksoil and DD of pass 1 / 2's
+// reference-form path (soil_spread<false>, soil_ksoil with the table exp, soil_damping), each day's 24 values summed in hour
+// order and added to the running sum in day order, for the days and cells the solver's `valid` lanes cover (cpp:2309-2312)
+__global__ __launch_bounds__(256) void k_below_dd(BelowDDArgs a) {
+    __shared__ double s_exptab[256];
+    __shared__ __attribute__((aligned(16))) double s_logtab[512];
+    const int tid = threadIdx.x;
+    s_exptab[tid] = kExp2Tab[tid];
+    for (int i = tid; i < 512; i += 256) s_logtab[i] = kLogTab[i];
+    __syncthreads();
+    MathK MK;
+    MK.set();
+    MK.tables(s_exptab, s_logtab);       // k_solve's exp: the table route
+    const int64_t c = (int64_t)blockIdx.x * 256 + tid;
+    if (c >= a.N) return;
+    const int cpb = a.cpb, blk = ring_block_doubles(cpb);
+    const int64_t tile = c / cpb;
+    const int cell = (int)(c - tile * cpb);
+    const int64_t IMG = tile_image_doubles_dev(cpb);
+    double acc = a.ddsum[c];
+    for (int dl = 0; dl < a.ndays; ++dl) {
+        const int d = a.day0 + dl;
+        const int layer = a.daylayer ? a.daylayer[d] : 0;
+        if (layer < 0) continue;                      // no vegetation layer: the solver's lanes are not valid
+        const double* img = a.cellc + ((int64_t)layer * a.ntiles_total + tile) * IMG + cell;
+        auto C = [&](int f) { return img[(int64_t)f * cpb]; };
+        if (!((int)C(CF_FLAGS) & FL_VALID)) continue;
+        const double* fday = a.af_base ? a.af_base + tile * a.af_tile_stride + (int64_t)dl * a.af_day_stride + (int64_t)TF_SOILMP * blk
+                                       : nullptr;
+        const double* tday = a.af_base ? nullptr : a.tt + ((int64_t)d * TF_COUNT + TF_SOILMP) * 24;
+        double s = 0.0;
+        for (int h = 0; h < 24; ++h) {
+            const double smp = fday ? fday[ring_pos(cpb, cell, h)] : tday[h];
+            Canary cn;
+            const double soilm = soil_spread<false>(smp, C(CF_SMIN), C(CF_INVRGE), C(CF_ETA), C(CF_RGE), cn);
+            const double rho = C(CF_RHO);
+            const double ksoil = soil_ksoil(soilm, rho, C(CF_C1), C(CF_C1MC4), fexp(soil_ksoil_arg(soilm, C(CF_C3)), MK));
+            double DD, rdd;
+            soil_damping(soilm, ksoil, rho, C(CF_CSA), DD, rdd);
+            s += DD;
+        }
+        acc += s;
+    }
+    a.ddsum[c] = acc;
+}
+
+// w[j] = the series' value kBelowWin - j steps before the end of what has been folded in; `L` more steps, value(k) of k < L
+template <class V>
+__device__ __forceinline__ void below_shift(double* w, int64_t c, int64_t N, int L, V&& value) {
+    for (int j = 0; j < kBelowWin; ++j) {
+        const int k = L - kBelowWin + j;
+        w[c + N * j] = k >= 0 ? value(k) : w[c + N * (j + L)];     // (ascending j: reads ahead of the writes)
+    }
+}
+
+// sweep 1 (complete = 1): the chunk's Tg into the hourly sum (step order), the daily means and the last 47 steps
+__global__ __launch_bounds__(256) void k_below_acc(BelowStreamArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
+    if (c >= N) return;
+    double hs = a.hsum[c];
+    for (int dl = 0; dl < a.ndays_chunk; ++dl) {
+        double s = 0.0;
+        for (int j = 0; j < 24; ++j) {
+            const double x = a.tg.at(c, dl * 24 + j);
+            hs = hs + x;                                                     // cpp:1489 (k_belowground's meanT)
+            s += x;                                                          // cpp:607-610
+        }
+        a.dmean[c + N * (a.day0 + dl)] = s / 24.0;
+    }
+    a.hsum[c] = hs;
+    below_shift(a.wrap, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, k); });
+}
+
+// after sweep 1 (complete = 1): the steps past the last whole day (Tg 0 there) into hsum and wrap; the circular n/24-day means
+// y (cpp:611-617) of the cells that take the daily path
+__global__ __launch_bounds__(256) void k_below_finish(BelowStreamArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
+    if (c >= N) return;
+    const int m = a.tsteps, nd = a.ndays, t = m - nd * 24;
+    double hs = a.hsum[c];
+    for (int k = 0; k < t; ++k) hs = hs + 0.0;
+    a.hsum[c] = hs;
+    if (t > 0) below_shift(a.wrap, c, N, t, [](int) { return 0.0; });
+    if (isnan(a.hgt[c])) return;
+    const double meanD = a.ddsum[c] / (double)m;                           // cpp:2313
+    const double nb = -118.35 * a.reqhgt / meanD;
+    const int n = (int)round(nb);
+    if (!(n < m && n > 48)) return;
+    const int n2 = n / 24;
+    const double* d = a.dmean + c;
+    for (int i = 0; i < nd; ++i) {
+        double s = 0.0;
+        for (int j = 0; j < n2; ++j) s += d[N * ((i - j + nd) % nd)];
+        a.ybuf[c + N * i] = s / n2;
+    }
+}
+
+// Tz of the chunk's days (blockIdx.y < ndays_chunk) and, with a.tail, of the steps behind the last whole day
+// (blockIdx.y == ndays_chunk) into the slot; one lane per cell-day, k_belowground's expressions
+__global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
+    if (c >= N) return;
+    const int dl = blockIdx.y;
+    const int m = a.tsteps, nd = a.ndays, L = a.ndays_chunk * 24;
+    const int hours = dl < a.ndays_chunk ? 24 : m - nd * 24;
+    const int k0 = dl * 24;                         // the day's first step in the chunk
+    const int64_t cs = (int64_t)a.day0 * 24;        // the chunk's first step in the series
+    double* const zb = const_cast<double*>(a.tz.base);
+    auto put = [&](int k, double v) { zb[a.tz.index(c, k)] = v; };
+    if (isnan(a.hgt[c])) {
+        for (int h = 0; h < hours; ++h) put(k0 + h, na_real());
+        return;
+    }
+    // Tg at step k of the chunk: k < 0 the steps in front of it (prev; in front of the series' start: its end, wrap),
+    // k >= L past the last whole day (0, as in the whole series' zero fill)
+    auto x = [&](int64_t k) -> double {
+        if (k >= L) return 0.0;
+        if (k >= 0) return a.tg.at(c, k);
+        const int64_t ka = cs + k;
+        if (ka >= 0) return a.prev[c + N * (k + kBelowWin)];
+        return a.wrap[c + N * (ka + kBelowWin)];
+    };
+    const double meanD = a.ddsum[c] / (double)m;                           // cpp:2313
+    const double nb = -118.35 * a.reqhgt / meanD;
+    const int n = (int)round(nb);
+    if (a.complete) {
+        if (n < m) {
+            if (n <= 48) {                                                   // cpp:600-602
+                for (int h = 0; h < hours; ++h) {
+                    const int i = k0 + h;
+                    double s = 0.0;
+                    for (int j = 0; j < n; ++j) s += x(i - j);
+                    put(i, s / n);
+                }
+            } else {                                                         // cpp:618-625
+                const double* y = a.ybuf + c;
+                for (int h = 0; h < hours; ++h) {
+                    const int64_t i = cs + k0 + h;
+                    double s = 0.0;
+                    for (int j = 0; j < 24; ++j) {
+                        int q = (int)((i - j + m) % m);
+                        s += (q < nd * 24) ? y[N * (q / 24)] : 0.0;
+                    }
+                    put(k0 + h, s / 24);
+                }
+            }
+        } else {                                                             // cpp:1487-1492
+            double meanT = a.hsum[c] / m;
+            for (int h = 0; h < hours; ++h) put(k0 + h, meanT);
+        }
+        return;
+    }
+    // incomplete time sequence, cpp:1495-1536
+    const bool pc = a.per_cell_pointm != 0;
+    auto ser = [&](const double* p, int64_t i) { return pc ? p[c + N * (i - cs)] : p[i]; };      // i: step of the series
+    const bool blend_day = (nb > 1.0 && nb <= 24.0);
+    const bool blend_year = nb > 24.0;
+    if (dl == a.ndays_chunk) {       // past the last whole day: see k_belowground
+        for (int h = 0; h < hours; ++h)
+            put(k0 + h, (!blend_day && !blend_year) ? 0.0
+                        : (blend_year && !(nb < a.hiy)) ? a.mat : __longlong_as_double(0x7FF8000000000000LL));
+        return;
+    }
+    if (!blend_day && !blend_year) {
+        for (int h = 0; h < 24; ++h) put(k0 + h, x(k0 + h));
+        return;
+    }
+    const int64_t i0 = cs + k0;
+    double gmx = x(k0), gmn = gmx, gsum = 0.0;
+    double pmx = ser(a.Tgp, i0), pmn = pmx, psum = 0.0, bsum = 0.0;
+    for (int j = 0; j < 24; ++j) {
+        double gv = x(k0 + j), pv = ser(a.Tgp, i0 + j);
+        if (j > 0) {
+            gmx = fmax(gmx, gv); gmn = fmin(gmn, gv);
+            pmx = fmax(pmx, pv); pmn = fmin(pmn, pv);
+        }
+        gsum += gv; psum += pv;
+        bsum += ser(a.Tbp, i0 + j);
+    }
+    double gme = gsum / 24, pme = psum / 24, Tbpd = bsum / 24;
+    double rat = (gmx - gmn) / (pmx - pmn);
+    double dif = gme - pme;
+    for (int j = 0; j < 24; ++j) {
+        const int64_t i = i0 + j;
+        double z = x(k0 + j);
+        double Tzd = rat * (ser(a.Tbp, i) - Tbpd) + Tbpd + dif;
+        if (blend_day) {
+            double w1 = 1.0 / nb, w2 = nb / 24.0;
+            double wgt = w1 / (w1 + w2);
+            z = wgt * x(k0 + j) + (1 - wgt) * Tzd;
+        }
+        if (blend_year) {
+            if (nb < a.hiy) {
+                double w1 = 24.0 / nb, w2 = nb / a.hiy;
+                double wgt = w1 / (w1 + w2);
+                z = wgt * Tzd + (1 - wgt) * a.mat;
+            } else {
+                z = a.mat;
+            }
+        }
+        put(k0 + j, z);
+    }
+}
+// behind k_below_chunk (complete = 1): prev <- the 47 steps in front of the next chunk
+__global__ __launch_bounds__(256) void k_below_carry(BelowStreamArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
+    if (c >= N) return;
+    below_shift(a.prev, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, k); });
 }
 
 // ------------------------------------------------------------------------------------
@@ -1645,6 +1875,50 @@ void launch_belowground(const BelowArgs& a, hipStream_t s) {
 }
 
 static dim3 solve_grid(int64_t ntiles) { return dim3((unsigned)(8 * ((ntiles + 7) / 8))); }     // tile_position()
+void launch_below_dd(const BelowDDArgs& a, hipStream_t s) {
+    if (a.N <= 0 || a.ndays <= 0) return;
+    hipLaunchKernelGGL(k_below_dd, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
+}
+void launch_below_acc(const BelowStreamArgs& a, hipStream_t s) {
+    if (a.N <= 0 || a.ndays_chunk <= 0) return;
+    hipLaunchKernelGGL(k_below_acc, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
+}
+void launch_below_finish(const BelowStreamArgs& a, hipStream_t s) {
+    if (a.N <= 0) return;
+    hipLaunchKernelGGL(k_below_finish, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
+}
+void launch_below_chunk(const BelowStreamArgs& a, hipStream_t s) {
+    const int days = a.ndays_chunk + (a.tail ? 1 : 0);
+    if (a.N <= 0 || days <= 0) return;
+    hipLaunchKernelGGL(k_below_chunk, dim3((unsigned)((a.N + 255) / 256), (unsigned)days), dim3(256), 0, s, a);
+    if (a.complete && a.ndays_chunk > 0)
+        hipLaunchKernelGGL(k_below_carry, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
+}
+template <int CPB>
+static void launch_solve_bgt_cpb(SolveArgs a, bool af, hipStream_t s) {
+    a.ntiles_launch = (a.N + CPB - 1) / CPB;
+    a.tile_list = nullptr;
+    const dim3 grid = solve_grid(a.ntiles_launch), block(solve_threads(CPB));
+    if (af) {
+        if constexpr (CPB != 42) hipLaunchKernelGGL((k_solve<CPB, 1, 2, false, false>), grid, block, 0, s, a);
+    } else {
+        hipLaunchKernelGGL((k_solve<CPB, 0, 2, false, false>), grid, block, 0, s, a);
+    }
+}
+void launch_solve_bg_tiled(const SolveArgs& a, int cells_per_block, bool af, hipStream_t s) {
+    if (a.N <= 0 || a.ndays <= 0) return;
+    if (a.crows > 0) {
+        SolveArgs b = a;
+        b.ntiles_launch = (b.N + 31) / 32;
+        b.tile_list = nullptr;
+        hipLaunchKernelGGL((k_solve<32, 2, 2, false, false>), solve_grid(b.ntiles_launch), dim3(solve_threads(32)), 0, s, b);
+        return;
+    }
+    if (cells_per_block == 32) launch_solve_bgt_cpb<32>(a, af, s);
+    else if (cells_per_block == 21) launch_solve_bgt_cpb<21>(a, af, s);
+    else if (cells_per_block == 42) launch_solve_bgt_cpb<42>(a, af, s);
+    else launch_solve_bgt_cpb<16>(a, af, s);
+}
 template <int CPB>
 static void launch_solve_cpb(SolveArgs a, bool af, bool bg, bool fast, bool ss, hipStream_t s) {
     if (a.ntiles_launch <= 0) {                      // no list: every tile of the raster
