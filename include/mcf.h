@@ -39,7 +39,7 @@
  * reference, and therefore usable without a device: the one-point time-series model
  * (mcf_bigleaf, mcf_soilm, mcf_pointmprocess, mcf_weatherhgt) and the file side of
  * the writetonc sink (mcf_nc_create, mcf_nc_write_host, mcf_nc_close), and the
- * flow-accumulation sweep behind soilc$twi (mcf_flowacc, mcf_topidx).
+ * flow-accumulation sweep behind soilc$twi (mcf_flowacc, mcf_topidx; on the device: mcf_flowacc_device, mcf_topidx_device).
  */
 #ifndef MCF_H
 #define MCF_H
@@ -50,10 +50,11 @@
 extern "C" {
 #endif
 
-#define MCF_ABI_VERSION 7   /* 2: mcf_grid_inputs grew the coarse-forcing fields; 3: tiled output ring (mcf_plan_ring_layout);
+#define MCF_ABI_VERSION 8   /* 2: mcf_grid_inputs grew the coarse-forcing fields; 3: tiled output ring (mcf_plan_ring_layout);
                              * 4: mcf_nc_spec grew format / deflate_level (zero = the behaviour of version 3); 5: mcf_runmicrosnow1 / mcf_snowrun_*;
                              * 6: mcf_snowdriver_in grew af_wsa_s (the former `reserved`) / af_wind at its end — read only with array weather;
-                             * 7: below ground streamed through day chunks (mcf_plan_create_streamed, mcf_plan_below_prepare) */
+                             * 7: below ground streamed through day chunks (mcf_plan_create_streamed, mcf_plan_below_prepare);
+                             * 8: plans and one-shot solves that take the dtm (mcf_dtm_spec), flow accumulation / wetness index on the device */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -489,6 +490,31 @@ int mcf_precompute_terrain(const mcf_terrain_in *in, const mcf_terrain_out *out,
  * block per device (more blocks than devices are time-sliced).  The values are those of the single-device call. */
 int mcf_precompute_terrain_multi(const mcf_terrain_in *in, const mcf_terrain_out *out, const mcf_multi *multi);
 
+/* ---- plans and one-shot solves that take the dtm --------------------------------------------------------------------------
+ * What the solver needs that is a function of the elevation raster alone, built on the device straight into the plan's own
+ * buffers: each of in->soilc.{slope, aspect, hor, svfa, wsa, twi} may be NULL and is then derived from `dtm` (no host copy in
+ * either direction); one that is given is uploaded as by mcf_plan_create.  The derived values are those of the host route, bit
+ * for bit: mcf_precompute_terrain with zref = opt->zref (slope and aspect NaN where the dtm is NA) and mcf_topidx_device.  With
+ * `hor` given and `svfa` not, svfa comes from the given hor (R/internal.R:1146-1149).  The terrain planes need square cells
+ * (xres == yres) and, for a row block of a larger raster (rows_total > rows), the halo rows mcf_precompute_terrain asks for;
+ * flow accumulation does not tile: a row block must bring its twi.  Nothing of the dtm or of the scratch stays allocated:
+ * mcf_plan_bytes equals that of the plan created from host arrays.
+ * mcf_runmicro_dtm is mcf_runmicro1 .. 4 (by in->array_forcing / in->veg_layers) on such a plan.  With `multi` (NULL: one
+ * device, opt->device) the raster — the whole one: no halos, no placement — goes in row blocks over the listed devices as by
+ * mcf_runmicro1_multi: twi is derived once for the whole raster on the first device, every block derives its terrain from its
+ * dtm rows plus halos on its own device.  Same bits as the single-device call. */
+typedef struct mcf_dtm_spec {
+    const double *dtm;                 /* [(halo_north + rows + halo_south), cols] column-major, NaN = NA */
+    int32_t halo_north, halo_south;    /* as mcf_terrain_in */
+    int64_t row0, rows_total;          /* 0, 0: the block is the whole raster */
+    double xres, yres;
+    int32_t agg, reserved0;            /* .windsheltera's s, 0 -> 10 */
+} mcf_dtm_spec;
+int mcf_plan_create_dtm(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_dtm_spec *dtm,
+                        int32_t ring_days, int32_t ring_slots, mcf_plan **plan);
+int mcf_runmicro_dtm(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_dtm_spec *dtm,
+                     const mcf_multi *multi /* NULL: one device */, mcf_outputs *out);
+
 /* ---- snow branch ----------------------------------------------------------------------
  *   mcf_gridmodelsnow1/2()  replace  _microclimf_gridmodelsnow1 / _microclimf_gridmodelsnow2
  *                           src/RcppExports.cpp:483-514  (R stubs R/RcppExports.R:108-114,
@@ -898,6 +924,12 @@ int mcf_man(int64_t n, const double *x, int32_t window, double *out);
  * `dtm`, `fa`, `twi`: [rows, cols] column-major; NaN = NA. */
 int mcf_flowacc(int64_t rows, int64_t cols, const double *dtm, double *fa);
 int mcf_topidx(int64_t rows, int64_t cols, const double *dtm, double xres, double yres, double *twi);
+/* The same on the device (mcf_hydro.hip; host pointers in and out): the elevation-ordered sweep restated as a subtree count
+ * over the forest of the edges that run forward in the order, found by pointer doubling with integer atomics — `fa` equals
+ * mcf_flowacc's exactly, ties and plateaus included, and is bit-reproducible; `twi` equals mcf_topidx's up to the last bits of
+ * atan / tan (the median of the slopes is the exact order statistic).  At most 2^31 - 1 cells. */
+int mcf_flowacc_device(int64_t rows, int64_t cols, const double *dtm, double *fa, int32_t device);
+int mcf_topidx_device(int64_t rows, int64_t cols, const double *dtm, double xres, double yres, double *twi, int32_t device);
 
 /* Diagnostics: evaluate one of the solver's lean device elementary functions
  * elementwise on host arrays (kind 0 exp, 1 log, 2 x/y, 3 sqrt, 4 1/x, 5 satvap

@@ -84,6 +84,13 @@ class TerrainOut(C.Structure):
                 ("svfa", c_double_p), ("wsa", c_double_p)]
 
 
+class DtmSpec(C.Structure):
+    """include/mcf.h mcf_dtm_spec: the elevation block a plan derives its missing terrain planes / wetness index from."""
+    _fields_ = [("dtm", c_double_p), ("halo_north", C.c_int32), ("halo_south", C.c_int32),
+                ("row0", C.c_int64), ("rows_total", C.c_int64), ("xres", C.c_double), ("yres", C.c_double),
+                ("agg", C.c_int32), ("reserved0", C.c_int32)]
+
+
 NBIO = 19
 
 
@@ -198,9 +205,10 @@ EXPORTS = (
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
     "mcf_snowrun_pass1", "mcf_snowrun_pass2", "mcf_snowplan_run_chunk_pitched", "mcf_snowplan_chunk_af",
     "mcf_plan_create_streamed", "mcf_plan_below_prepare",
+    "mcf_flowacc_device", "mcf_topidx_device", "mcf_plan_create_dtm", "mcf_runmicro_dtm",
 )
 
-ABI_VERSION = 7     # include/mcf.h MCF_ABI_VERSION this mirror was written against
+ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
 _lib = None
 
 
@@ -415,6 +423,14 @@ def load() -> C.CDLL:
     lib.mcf_flowacc.argtypes = [C.c_int64, C.c_int64, c_double_p, c_double_p]
     lib.mcf_topidx.restype = C.c_int
     lib.mcf_topidx.argtypes = [C.c_int64, C.c_int64, c_double_p, C.c_double, C.c_double, c_double_p]
+    lib.mcf_flowacc_device.restype = C.c_int
+    lib.mcf_flowacc_device.argtypes = [C.c_int64, C.c_int64, c_double_p, c_double_p, C.c_int32]
+    lib.mcf_topidx_device.restype = C.c_int
+    lib.mcf_topidx_device.argtypes = [C.c_int64, C.c_int64, c_double_p, C.c_double, C.c_double, c_double_p, C.c_int32]
+    lib.mcf_plan_create_dtm.restype = C.c_int
+    lib.mcf_plan_create_dtm.argtypes = [GI, OP, C.POINTER(DtmSpec), C.c_int32, C.c_int32, C.POINTER(P)]
+    lib.mcf_runmicro_dtm.restype = C.c_int
+    lib.mcf_runmicro_dtm.argtypes = [GI, OP, C.POINTER(DtmSpec), C.POINTER(Multi), C.POINTER(Outputs)]
     lib.mcf_nc_create.restype = C.c_int
     lib.mcf_nc_create.argtypes = [C.c_char_p, C.POINTER(NcSpec), C.POINTER(C.c_void_p)]
     lib.mcf_nc_write_host.restype = C.c_int

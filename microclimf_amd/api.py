@@ -23,13 +23,47 @@ from . import _abi
 from .marshal import Marshalled, alloc_outputs, marshal
 
 
+DTM_DERIVED = ("slope", "aspect", "hor", "svfa", "wsa", "twi")      # soilc entries a plan can derive from the dtm
+
+
+def dtm_spec(dtm: Mapping, rows: int, cols: int):
+    """include/mcf.h mcf_dtm_spec from `dtm` = {z, res[, halo_north, halo_south, row0, rows_total, agg]}: `z` is the block's
+    elevations [(halo_north + rows + halo_south), cols] (NaN = NA), `res` one number or (xres, yres).  -> (spec, the array
+    that backs its pointer)"""
+    z = np.asfortranarray(np.asarray(dtm["z"], dtype=np.float64))
+    hn, hs = int(dtm.get("halo_north", 0)), int(dtm.get("halo_south", 0))
+    if z.shape != (hn + rows + hs, cols):
+        raise ValueError(f"dtm$z: expected shape {(hn + rows + hs, cols)}, got {z.shape}")
+    res = dtm["res"]
+    xres, yres = (res, res) if np.isscalar(res) else res
+    sp = _abi.DtmSpec()
+    sp.dtm = z.ctypes.data_as(_abi.c_double_p)
+    sp.halo_north, sp.halo_south = hn, hs
+    sp.row0, sp.rows_total = int(dtm.get("row0", 0)), int(dtm.get("rows_total", 0))
+    sp.xres, sp.yres, sp.agg = float(xres), float(yres), int(dtm.get("agg", 0))
+    return sp, z
+
+
 def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
          Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel=None, coarse=None,
-         devices=None, n_blocks=0):
+         devices=None, n_blocks=0, dtm=None):
     lib = _abi.load()
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp,
-                tfact, complete, mat, out, array_forcing, device, days_per_chunk, cells_per_block, dfsel, coarse)
+                tfact, complete, mat, out, array_forcing, device, days_per_chunk, cells_per_block, dfsel, coarse,
+                soilc_optional=DTM_DERIVED if dtm is not None else ())
     outs, arrays = alloc_outputs(m)
+    if dtm is not None:
+        # missing terrain planes / wetness index derived on the device (include/mcf.h mcf_runmicro_dtm); the entry dispatches on
+        # the inputs as mcf_runmicro1 .. 4 do
+        sp, _z = dtm_spec(dtm, m.rows, m.cols)
+        mu = None
+        if devices is not None or n_blocks:
+            mu = _abi.Multi()
+            devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
+            mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
+        _abi.check(lib.mcf_runmicro_dtm(C.byref(m.inputs), C.byref(m.options), C.byref(sp), None if mu is None else C.byref(mu),
+                                        C.byref(outs)))
+        return arrays
     if devices is not None or n_blocks:
         # one process, several devices (include/mcf.h mcf_runmicro1_multi): row blocks dealt to the listed devices
         mu = _abi.Multi()
@@ -44,24 +78,26 @@ def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt,
 def runmicro1Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
                  reqhgt: float, zref: float, lat: float, lon: float, Sminp: float, Smaxp: float,
                  tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
     """Grid microclimate model, hourly, static vegetation, data.frame (vector) climate.
 
     Drop-in for the reference's runmicro1Cpp (src/microclimfCpp.cpp:2052-2337).  `devices` (a list of HIP ordinals, [] =
-    all visible) / `n_blocks`: the raster in row blocks over several devices from this one process, same bits."""
+    all visible) / `n_blocks`: the raster in row blocks over several devices from this one process, same bits.
+    `dtm` = {z, res[, halo_north, halo_south, row0, rows_total, agg]}: entries of `soilc` among slope, aspect, hor, svfa, wsa,
+    twi that are missing are derived from the elevations on the device, straight into the plan (include/mcf.h mcf_dtm_spec)."""
     return _run("mcf_runmicro1", False, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
-                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks)
+                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm)
 
 
 def runmicro2Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
                  reqhgt: float, zref: float, lats, lons, Sminp: float, Smaxp: float, tfact: float,
                  complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
     """Grid microclimate model, hourly, static vegetation, array climate inputs.
 
     Drop-in for the reference's runmicro2Cpp (src/microclimfCpp.cpp:2340-2621); `devices` / `n_blocks` as runmicro1Cpp."""
     return _run("mcf_runmicro2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
-                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks)
+                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm)
 
 
 def coarse_positions(n_fine: int, n_coarse: int):
@@ -93,24 +129,24 @@ def runmicro2Cpp_coarse(obstime: Mapping, climdata: Mapping, pointm: Mapping, ve
 def runmicro3Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
                  soilc: Mapping, reqhgt: float, zref: float, lat: float, lon: float, Sminp: float,
                  Smaxp: float, tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
     """Hourly, changing vegetation, data.frame climate: drop-in for the reference's runmicro3Cpp
     (src/microclimfCpp.cpp:2624-2924).  `dfsel` has columns lyr, st, ed (0-based step ranges of
     each vegetation layer, R/internal.R:1391-1399); vegp entries are [rows, cols, layers].  `devices` / `n_blocks`: as runmicro1Cpp."""
     return _run("mcf_runmicro3", False, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
                 Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel,
-                devices=devices, n_blocks=n_blocks)
+                devices=devices, n_blocks=n_blocks, dtm=dtm)
 
 
 def runmicro4Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
                  soilc: Mapping, reqhgt: float, zref: float, lats, lons, Sminp: float, Smaxp: float,
                  tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
     """Hourly, changing vegetation, array climate: drop-in for the reference's runmicro4Cpp
     (src/microclimfCpp.cpp:2926-3226).  `devices` / `n_blocks`: as runmicro1Cpp."""
     return _run("mcf_runmicro4", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
                 Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel,
-                devices=devices, n_blocks=n_blocks)
+                devices=devices, n_blocks=n_blocks, dtm=dtm)
 
 
 BIOCLIM_DFSEL = {"lyr": np.arange(1, 15), "st": np.arange(14) * 24, "ed": np.arange(14) * 24 + 23}   # cpp:3634-3646
@@ -175,16 +211,26 @@ class Plan:
 
     def __init__(self, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp,
                  tfact, complete, mat, out, *, array_forcing=False, ring_days=1, ring_slots=1,
-                 device=0, cells_per_block=0, dfsel=None, coarse=None, stream_below=False):
-        """stream_below: reqhgt < 0 through day chunks (include/mcf.h mcf_plan_create_streamed) — below_prepare() first, then
+                 device=0, cells_per_block=0, dfsel=None, coarse=None, stream_below=False, dtm=None):
+        """dtm: {z, res[, halo_north, halo_south, row0, rows_total, agg]} — entries of `soilc` among slope, aspect, hor, svfa, wsa,
+        twi that are missing are derived from it on the device (include/mcf.h mcf_plan_create_dtm).
+        stream_below: reqhgt < 0 through day chunks (include/mcf.h mcf_plan_create_streamed) — below_prepare() first, then
         run_days in day order from day 0, each chunk's final Tz in its slot; for reqhgt >= 0 the same plan as without it."""
         self._lib = _abi.load()
         self._m: Marshalled = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
                                       Sminp, Smaxp, tfact, complete, mat, out, array_forcing or coarse is not None, device,
-                                      0, cells_per_block, dfsel, coarse)
+                                      0, cells_per_block, dfsel, coarse,
+                                      soilc_optional=DTM_DERIVED if dtm is not None else ())
         self._p = C.c_void_p()
-        create = self._lib.mcf_plan_create_streamed if stream_below else self._lib.mcf_plan_create
-        _abi.check(create(C.byref(self._m.inputs), C.byref(self._m.options), int(ring_days), int(ring_slots), C.byref(self._p)))
+        if dtm is not None:
+            if stream_below:
+                raise ValueError("streamed below-ground plans have no dtm form")
+            sp, _z = dtm_spec(dtm, self._m.rows, self._m.cols)
+            _abi.check(self._lib.mcf_plan_create_dtm(C.byref(self._m.inputs), C.byref(self._m.options), C.byref(sp), int(ring_days),
+                                                     int(ring_slots), C.byref(self._p)))
+        else:
+            create = self._lib.mcf_plan_create_streamed if stream_below else self._lib.mcf_plan_create
+            _abi.check(create(C.byref(self._m.inputs), C.byref(self._m.options), int(ring_days), int(ring_slots), C.byref(self._p)))
         self.stream_below = bool(stream_below)
         self.rows, self.cols, self.tsteps = self._m.rows, self._m.cols, self._m.tsteps
         self.ndays = self.tsteps // 24

@@ -19,6 +19,8 @@
 
 #include "../../include/mcf.h"
 #include "mcf_kernels.h"
+#include "mcf_hydro.h"
+#include "mcf_terrain.h"
 #include "mcf_hostpipe.hpp"
 #include "mcf_ncfile.hpp"
 #include "mcf_nc4file.hpp"
@@ -279,6 +281,90 @@ const char* kRawNames[15] = {"tc", "es", "ea", "tdew", "pk", "swdown", "difrad",
                              "pointm$soilm", "pointm$G", "pointm$umu", "pointm$kp", "pointm$muGp",
                              "pointm$dtrp"};
 
+// ---- plans that take the dtm (include/mcf.h mcf_dtm_spec) ---------------------------------------------------------------
+struct DtmNeeds {
+    bool slope, aspect, hor, svfa, wsa, twi;
+    bool terrain() const { return slope || aspect || hor || wsa || svfa; }
+    bool any() const { return terrain() || twi; }
+};
+DtmNeeds dtm_needs(const mcf_grid_inputs* in) {
+    const mcf_soilc& s = in->soilc;
+    return DtmNeeds{!s.slope, !s.aspect, !s.hor, !s.svfa, !s.wsa, !s.twi};
+}
+// halo rows the missing planes' stencils reach (mcf_precompute_terrain's rule; svfa from a given hor needs none)
+int64_t dtm_halo_need(const DtmNeeds& nd, int s) {
+    return nd.wsa ? 100 + 2 * s + s / 2 : (nd.hor ? 100 : (nd.slope || nd.aspect) ? 1 : 0);
+}
+
+int check_dtm(const mcf_grid_inputs* in, const mcf_dtm_spec* dtm) {
+    if (!dtm->dtm) return fail(MCF_ERR_ARG, "mcf_dtm_spec: null dtm");
+    if (dtm->halo_north < 0 || dtm->halo_south < 0 || !(dtm->xres > 0) || !(dtm->yres > 0))
+        return fail(MCF_ERR_ARG, "mcf_dtm_spec: bad geometry or resolution");
+    const int64_t rows_total = dtm->rows_total > 0 ? dtm->rows_total : in->rows;
+    const int64_t row0 = dtm->rows_total > 0 ? dtm->row0 : 0;
+    if (row0 < 0 || row0 + in->rows > rows_total) return fail(MCF_ERR_ARG, "block outside the raster");
+    const DtmNeeds nd = dtm_needs(in);
+    if ((nd.slope || nd.aspect || nd.hor || nd.wsa) && dtm->xres != dtm->yres)
+        return fail(MCF_ERR_ARG, "terrain planes from the dtm need square cells (xres == yres), as the reference's .horizon does");
+    if (nd.twi && (rows_total > in->rows || dtm->halo_north || dtm->halo_south))
+        return fail(MCF_ERR_ARG, "flow accumulation does not tile: a row block of a larger raster must bring its twi");
+    const int s = dtm->agg > 0 ? dtm->agg : 10;
+    const int64_t need = dtm_halo_need(nd, s);
+    if (dtm->halo_north < std::min(need, row0) || dtm->halo_south < std::min(need, rows_total - row0 - in->rows)) {
+        char b[200];
+        snprintf(b, sizeof b, "terrain block needs %lld halo rows (or all rows up to the raster edge)", (long long)need);
+        return fail(MCF_ERR_ARG, b);
+    }
+    return MCF_OK;
+}
+
+// The missing planes, on the device, into the plan's buffers.  The dtm block and every scratch buffer are released on return.
+int derive_from_dtm(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* dtm) {
+    const DtmNeeds nd = dtm_needs(in);
+    if (!nd.any()) return MCF_OK;
+    const double t_enter = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+    HIP_TRY(hipStreamSynchronize(p->stream));           // the given planes are in place (svfa may read hor)
+    const int64_t N = p->N;
+    if (nd.svfa && !nd.hor) {                           // R/internal.R:1146-1149
+        if (const int rc = mcf::svf_from_hor_device(p->d_hor, N, (double*)p->d_soil[12])) return rc;
+        if (!(nd.slope || nd.aspect || nd.wsa || nd.twi)) return MCF_OK;
+    }
+    const int64_t RB = (int64_t)dtm->halo_north + p->rows + dtm->halo_south, NB = RB * p->cols;
+    const bool timing = getenv("MCF_TIMING") != nullptr;
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t0 = now();
+    double t1 = t0, t2 = t0;
+    double* d_dtm = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_dtm, (size_t)NB * 8));
+    struct Free { double* q; ~Free() { (void)hipFree(q); } } free_dtm{d_dtm};
+    HIP_TRY(hipMemcpy(d_dtm, dtm->dtm, (size_t)NB * 8, hipMemcpyHostToDevice));
+    t1 = t2 = now();
+    if (nd.slope || nd.aspect || nd.hor || nd.wsa) {
+        mcf::TerrainDev t;
+        memset(&t, 0, sizeof t);
+        t.rows = p->rows; t.cols = p->cols; t.halo_north = dtm->halo_north; t.halo_south = dtm->halo_south;
+        t.row0 = dtm->row0; t.rows_total = dtm->rows_total;
+        t.d_dtm = d_dtm; t.res = dtm->xres; t.zref = p->opt.zref; t.agg = dtm->agg; t.aspect_na = 0.0;     // R/internal.R:1132-1136
+        if (nd.slope) t.d_slope = (double*)p->d_soil[9];
+        if (nd.aspect) t.d_aspect = (double*)p->d_soil[10];
+        if (nd.hor) t.d_hor = (double*)p->d_hor;
+        if (nd.hor && nd.svfa) t.d_svfa = (double*)p->d_soil[12];
+        if (nd.wsa) t.d_wsa = (double*)p->d_wsa;
+        if (const int rc = mcf::terrain_device(t)) return rc;
+        // `slope[is.na(dtm)] <- NA` of the host marshaller
+        if (nd.slope || nd.aspect)
+            if (const int rc = mcf::mask_na_device(d_dtm, p->rows, p->cols, dtm->halo_north, dtm->halo_south, t.d_slope, t.d_aspect))
+                return rc;
+        t2 = now();
+    }
+    if (nd.twi)
+        if (const int rc = mcf::topidx_device(d_dtm, p->rows, p->cols, dtm->xres, dtm->yres, (double*)p->d_soil[11], nullptr)) return rc;
+    if (timing)
+        fprintf(stderr, "[mcf] planes from the dtm: given planes in place %.3f s, dtm upload %.3f s, terrain %.3f s, wetness index %.3f s\n",
+                t0 - t_enter, t1 - t0, t2 - t1, now() - t2);
+    return MCF_OK;
+}
+
 int ensure_cells(mcf_plan* p) {
     if (p->cells_ready) return MCF_OK;
   for (int l = 0; l < p->layers; ++l) {
@@ -467,11 +553,12 @@ void mcf_plan_destroy(mcf_plan* p) {
 }
 
 static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots, bool streamed,
-                       mcf_plan** out) {
+                       mcf_plan** out, const mcf_dtm_spec* dtm = nullptr) {
     if (!out) return fail(MCF_ERR_ARG, "null plan pointer");
     *out = nullptr;
     int rc = check_inputs(in, opt);
     if (rc) return rc;
+    if (dtm && (rc = check_dtm(in, dtm))) return rc;
     rc = ensure_device(opt->device);
     if (rc) return rc;
     mcf_plan* p = new mcf_plan();
@@ -555,10 +642,19 @@ static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_
                               in->soilc.aspect, in->soilc.twi, in->soilc.svfa};
     const char* soiln[13] = {"Smin", "Smax", "gref", "soilb", "Psie", "Vq", "Vm", "Mc", "rho", "slope",
                              "aspect", "twi", "svfa"};
+    // with a dtm, a terrain plane or the wetness index that is not given gets its buffer here and its values below
+    auto plane = [&](const double* host, int64_t n, const double** dev, const char* name) -> int {
+        if (host || !dtm) return upload(p, host, n, dev, name);
+        void* d = nullptr;
+        if (const int rca = dalloc(p, &d, n * 8)) return rca;
+        *dev = (const double*)d;
+        return MCF_OK;
+    };
     for (int i = 0; i < 13; ++i)
-        if ((rc = upload(p, soil[i], N, &p->d_soil[i], soiln[i]))) return rc;
-    if ((rc = upload(p, in->soilc.wsa, N * 8, &p->d_wsa, "wsa"))) return rc;
-    if ((rc = upload(p, in->soilc.hor, N * 24, &p->d_hor, "hor"))) return rc;
+        if ((rc = i >= 9 ? plane(soil[i], N, &p->d_soil[i], soiln[i]) : upload(p, soil[i], N, &p->d_soil[i], soiln[i]))) return rc;
+    if ((rc = plane(in->soilc.wsa, N * 8, &p->d_wsa, "wsa"))) return rc;
+    if ((rc = plane(in->soilc.hor, N * 24, &p->d_hor, "hor"))) return rc;
+    if (dtm && (rc = derive_from_dtm(p, in, dtm))) return rc;
     if (p->af) {
         if ((rc = upload(p, in->lats, N, &p->d_lats, "lats"))) return rc;
         if ((rc = upload(p, in->lons, N, &p->d_lons, "lons"))) return rc;
@@ -862,6 +958,11 @@ int mcf_plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t r
 int mcf_plan_create_streamed(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots,
                              mcf_plan** out) {
     return plan_create(in, opt, ring_days, ring_slots, true, out);
+}
+int mcf_plan_create_dtm(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_dtm_spec* dtm, int32_t ring_days,
+                        int32_t ring_slots, mcf_plan** out) {
+    if (!dtm) return fail(MCF_ERR_ARG, "null mcf_dtm_spec");
+    return plan_create(in, opt, ring_days, ring_slots, false, out, dtm);
 }
 
 }  // extern "C"
@@ -1937,7 +2038,7 @@ int64_t mcf_plan_bytes(const mcf_plan* p) { return p ? p->bytes : 0; }
 // sharers: host threads that solve their blocks on this device at the same time (one-process multi-device route with a device
 // listed more than once): each sizes its ring from its share of the free HBM
 static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out, int want_af,
-                       const double* twi_mean = nullptr, int sharers = 1) {
+                       const double* twi_mean = nullptr, int sharers = 1, const mcf_dtm_spec* dtm = nullptr) {
     int rc = check_inputs(in, opt);
     if (rc) return rc;
     if (!out) return fail(MCF_ERR_ARG, "null outputs");
@@ -1991,7 +2092,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now(), t_solve = 0, t_fetch = 0;
     mcf_plan* p = nullptr;
-    rc = stream_bg ? mcf_plan_create_streamed(in, opt, chunk + (tail ? 1 : 0), 1, &p) : mcf_plan_create(in, opt, chunk, 1, &p);
+    rc = plan_create(in, opt, stream_bg ? chunk + (tail ? 1 : 0) : chunk, 1, stream_bg, &p, dtm);
     if (rc) return rc;
     struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
@@ -2081,13 +2182,18 @@ extern "C++" {
 // block_fn(sub, o, r0, twi_mean, sharers): one row block — `sub` is the caller's inputs narrowed to the block's rows (same arrays, offset,
 // read through the row pitch), `o` the options with the block's device, r0 the block's first row
 template <class F>
-static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_multi* mu, F&& block_fn) {
-    int rc = check_inputs(in, opt);
+static int for_row_blocks(const mcf_grid_inputs* in_caller, const mcf_options* opt, const mcf_multi* mu, F&& block_fn,
+                          const mcf_dtm_spec* dtm = nullptr) {
+    int rc = check_inputs(in_caller, opt);
     if (rc) return rc;
     if (!mu) return fail(MCF_ERR_ARG, "null argument");
     // what row_blocks and the whole-raster twi mean read, before any plan has validated the inputs
-    if (!in->vegp.hgt) return fail(MCF_ERR_ARG, "missing input array: vegp$hgt");
-    if (!in->soilc.twi) return fail(MCF_ERR_ARG, "missing input array: twi");
+    if (!in_caller->vegp.hgt) return fail(MCF_ERR_ARG, "missing input array: vegp$hgt");
+    const bool derive_twi = dtm && !in_caller->soilc.twi;
+    if (!in_caller->soilc.twi && !derive_twi) return fail(MCF_ERR_ARG, "missing input array: twi");
+    mcf_grid_inputs in_twi = *in_caller;       // (with a derived twi: the caller's inputs with the derived plane in place)
+    const mcf_grid_inputs* in = &in_twi;
+    std::vector<double> twi_host;              // the derived plane, laid out with the caller's row pitch: the blocks' plans upload their rows
     std::vector<int> devs;
     if ((rc = mcf::device_list(mu, 0, &devs))) return rc;
     mcf::RestoreDevice restore_dev;          // (the twi reduction below runs on the first device)
@@ -2103,8 +2209,21 @@ static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, con
         HIP_TRY(hipMalloc((void**)&d_twi, (size_t)N * 8));
         struct G { double *&a, *&b; ~G() { (void)hipFree(a); (void)hipFree(b); } } g{d_twi, d_ws};
         HIP_TRY(hipMalloc((void**)&d_ws, (size_t)mcf::twi_scratch_doubles() * 8));
-        HIP_TRY(hipMemcpy2D(d_twi, (size_t)in->rows * 8, in->soilc.twi, (size_t)pitch * 8, (size_t)in->rows * 8, (size_t)in->cols,
-                            hipMemcpyHostToDevice));
+        if (derive_twi) {
+            // the wetness index of the whole raster, once, on the first device (flow accumulation does not tile)
+            double* d_dtm = nullptr;
+            HIP_TRY(hipMalloc((void**)&d_dtm, (size_t)N * 8));
+            struct Free { double* q; ~Free() { (void)hipFree(q); } } free_dtm{d_dtm};
+            HIP_TRY(hipMemcpy(d_dtm, dtm->dtm, (size_t)N * 8, hipMemcpyHostToDevice));
+            if ((rc = mcf::topidx_device(d_dtm, in->rows, in->cols, dtm->xres, dtm->yres, d_twi, nullptr))) return rc;
+            twi_host.resize((size_t)(pitch * in->cols));
+            HIP_TRY(hipMemcpy2D(twi_host.data(), (size_t)pitch * 8, d_twi, (size_t)in->rows * 8, (size_t)in->rows * 8, (size_t)in->cols,
+                                hipMemcpyDeviceToHost));
+            in_twi.soilc.twi = twi_host.data();
+        } else {
+            HIP_TRY(hipMemcpy2D(d_twi, (size_t)in->rows * 8, in->soilc.twi, (size_t)pitch * 8, (size_t)in->rows * 8, (size_t)in->cols,
+                                hipMemcpyHostToDevice));
+        }
         mcf::launch_twi_partial(d_twi, N, opt->tfact, d_ws, nullptr);
         double h2[2];
         HIP_TRY(hipMemcpy(h2, d_ws, 16, hipMemcpyDeviceToHost));
@@ -2129,13 +2248,30 @@ static int for_row_blocks(const mcf_grid_inputs* in, const mcf_options* opt, con
 }
 
 }  // extern "C++"
-static int run_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out, int want_af) {
+// dtm: null, or the WHOLE raster's (no halos, no placement) — a block then derives its missing terrain planes from its dtm
+// rows plus the halo rows their stencils reach, gathered out of the caller's array as mcf_precompute_terrain_multi does
+static int run_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out, int want_af,
+                     const mcf_dtm_spec* dtm = nullptr) {
     if (!out) return fail(MCF_ERR_ARG, "null argument");
+    if (dtm && in) {
+        if (dtm->halo_north || dtm->halo_south || (dtm->rows_total > 0 && (dtm->row0 != 0 || dtm->rows_total != in->rows)))
+            return fail(MCF_ERR_ARG, "mcf_runmicro_dtm over several devices takes the whole raster (no halos, no placement)");
+        if (in->rows <= 0 || in->cols <= 0) return fail(MCF_ERR_ARG, "rows/cols must be positive");
+        if (const int rc = check_dtm(in, dtm)) return rc;
+    }
     return for_row_blocks(in, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int sharers) {
         mcf_outputs so = *out;
         for (int v = 0; v < MCF_NOUT; ++v) if (so.var[v]) so.var[v] += r0;
-        return run_oneshot(&sub, &o, &so, want_af, twi_mean, sharers);
-    });
+        if (!dtm) return run_oneshot(&sub, &o, &so, want_af, twi_mean, sharers);
+        const int64_t R = in->rows, nr = sub.rows;
+        const int64_t need = dtm_halo_need(dtm_needs(&sub), dtm->agg > 0 ? dtm->agg : 10);
+        const int64_t hn = std::min(need, r0), hs = std::min(need, R - r0 - nr);
+        std::vector<double> ext;
+        mcf::gather_rows(ext, dtm->dtm, R, in->cols, r0 - hn, hn + nr + hs);
+        mcf_dtm_spec bd = *dtm;
+        bd.dtm = ext.data(); bd.halo_north = (int32_t)hn; bd.halo_south = (int32_t)hs; bd.row0 = r0; bd.rows_total = R;
+        return run_oneshot(&sub, &o, &so, want_af, twi_mean, sharers, &bd);
+    }, dtm);
 }
 // the fused bioclim sink over row blocks: a block's nineteen [rows, cols] matrices go into its rows of the caller's
 static int run_bioclim_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const mcf_multi* mu,
@@ -2165,6 +2301,15 @@ int mcf_runbioclim4_multi(const mcf_grid_inputs* in, const mcf_options* opt, con
 
 int mcf_runmicro1(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {
     return run_oneshot(in, opt, out, 0);
+}
+int mcf_runmicro_dtm(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_dtm_spec* dtm, const mcf_multi* multi, mcf_outputs* out) {
+    if (!in || !dtm) return fail(MCF_ERR_ARG, "null inputs / mcf_dtm_spec");
+    const int want_af = in->array_forcing != 0;
+    if (multi) {
+        if (!dtm->dtm) return fail(MCF_ERR_ARG, "mcf_dtm_spec: null dtm");
+        return run_multi(in, opt, multi, out, want_af, dtm);
+    }
+    return run_oneshot(in, opt, out, want_af, nullptr, 1, dtm);
 }
 int mcf_runmicro1_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_multi* multi, mcf_outputs* out) {
     return run_multi(in, opt, multi, out, 0);

@@ -282,9 +282,11 @@ def runpointmodel(weather: Mapping, reqhgt: float, dtm: Mapping, vegp: Mapping, 
 # ---- runmicro ---------------------------------------------------------------------------------------------------
 def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None,
                         out: Sequence = (1,) * 10, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None,
-                        device: int = 0) -> dict:
+                        device: int = 0, from_dtm: bool = False) -> dict:
     """Everything `.runmodel1Cpp` / `.runmodel3Cpp` do before calling the solver (R/internal.R:1067-1166 / 1347-1456):
-    returns the keyword arguments of runmicro1Cpp, plus `dfsel` when the vegetation varies in time."""
+    returns the keyword arguments of runmicro1Cpp, plus `dfsel` when the vegetation varies in time.  `from_dtm`: those of
+    slr, apr, hor, twi, wsa, svf that are not given are left out of `soilc` and `dtm` = {z, res} is returned with the
+    arguments instead: the solver's plan derives them on the device (api.runmicro1Cpp, `dtm`)."""
     res = dtm["res"]
     xres, yres = (res, res) if np.isscalar(res) else res
     if xres != yres:
@@ -329,19 +331,22 @@ def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc
           "Vq": sl["Vq"], "Vm": sl["Vm"], "Mc": sl["Mc"], "rho": sl["rho"]}
     na = np.isnan(z)
     need = [k for k, v in (("slope", slr), ("aspect", apr), ("hor", hor), ("svfa", svf), ("wsa", wsa)) if v is None]
-    ter = terrain.precompute_terrain(z, xres, micropoint["zref"], what=tuple(need), device=device) if need else {}
+    ter = terrain.precompute_terrain(z, xres, micropoint["zref"], what=tuple(need), device=device) if need and not from_dtm else {}
     for k, given in (("slope", slr), ("aspect", apr)):
+        if given is None and from_dtm:
+            continue
         a = np.array(ter[k] if given is None else given, dtype=np.float64, copy=True)
         a[np.isnan(a)] = 0.0
         a[na] = np.nan
         sc[k] = a
-    t = np.array(terrain.topidx(z, (xres, yres)) if twi is None else twi, dtype=np.float64, copy=True)
-    t[np.isnan(t)] = 1.0
-    t[na] = np.nan
-    sc["twi"] = t
-    sc["hor"] = ter["hor"] if hor is None else np.asarray(hor, dtype=np.float64)
-    sc["svfa"] = ter["svfa"] if svf is None else np.asarray(svf, dtype=np.float64)
-    sc["wsa"] = ter["wsa"] if wsa is None else np.asarray(wsa, dtype=np.float64)
+    if not (twi is None and from_dtm):
+        t = np.array(terrain.topidx(z, (xres, yres)) if twi is None else twi, dtype=np.float64, copy=True)
+        t[np.isnan(t)] = 1.0
+        t[na] = np.nan
+        sc["twi"] = t
+    for k, given in (("hor", hor), ("svfa", svf), ("wsa", wsa)):
+        if not (given is None and from_dtm):
+            sc[k] = ter[k] if given is None else np.asarray(given, dtype=np.float64)
     out = [int(bool(v)) for v in out]
     if reqhgt == 0:
         out = [a * b for a, b in zip((1, 0, 0, 1, 0, 1, 1, 1, 1, 1), out)]
@@ -353,16 +358,20 @@ def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc
                 mat=float(micropoint["matemp"]), out=out)
     if dfsel is not None:
         args["dfsel"] = dfsel
+    if from_dtm:
+        args["dtm"] = {"z": z, "res": (xres, yres)}
     return args
 
 
 def runmicro(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None,
              tfact: float = 1.5, out: Sequence = (1,) * 10, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None,
-             device: int = 0) -> dict:
+             device: int = 0, from_dtm: bool = False) -> dict:
     """`runmicro(micropoint, reqhgt, vegp, soilc, dtm, ...)` for data.frame weather without snow: time-invariant
-    vegetation goes to runmicro1Cpp, layered vegetation to runmicro3Cpp (R/internal.R:3332-3346)."""
+    vegetation goes to runmicro1Cpp, layered vegetation to runmicro3Cpp (R/internal.R:3332-3346).  `from_dtm`: every one of
+    slr, apr, hor, twi, wsa, svf that is not given is derived on the device inside the solver's plan instead of on the host
+    first (opt-in: the wetness index then differs from the host's in the last bits of atan / tan)."""
     a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, slr=slr, apr=apr, hor=hor, twi=twi,
-                            wsa=wsa, svf=svf, device=device)
+                            wsa=wsa, svf=svf, device=device, from_dtm=from_dtm)
     a["tfact"] = float(tfact)
     dfsel = a.pop("dfsel", None)
     if dfsel is None:

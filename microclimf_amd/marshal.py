@@ -56,8 +56,8 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             Smaxp: float, tfact: float, complete: bool, mat: float,
             out: Sequence, array_forcing: bool, device: int = 0,
             days_per_chunk: int = 0, cells_per_block: int = 0, dfsel: Mapping | None = None,
-            coarse: Mapping | None = None) -> Marshalled:
-    """`coarse` = {"rowpos": [rows], "colpos": [cols]} switches to coarse array forcing (mcf.h, array_forcing == 2):
+            coarse: Mapping | None = None, soilc_optional: Sequence = ()) -> Marshalled:
+    """`soilc_optional`: fields of soilc that may be missing (a NULL pointer: the plan derives them from the dtm).  `coarse` = {"rowpos": [rows], "colpos": [cols]} switches to coarse array forcing (mcf.h, array_forcing == 2):
     climdata = {temp, relhum, pres, swdown, difrad, lwdown, windspeed, winddir} and pointm are then
     [coarse_rows, coarse_cols, tsteps] arrays."""
     m = Marshalled()
@@ -135,6 +135,9 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
         gi.lyr_ed = m._i32(dfsel["ed"], L, "dfsel$ed")
     for f in _abi.SOILC_FIELDS:
         shape = (R, Cc, 8) if f == "wsa" else (R, Cc, 24) if f == "hor" else (R, Cc)
+        if f in soilc_optional and soilc.get(f) is None:
+            setattr(gi.soilc, f, None)
+            continue
         setattr(gi.soilc, f, m._f64(soilc[f], shape, f"soilc${f}"))
     if array_forcing:
         gi.lats = m._f64(lat, (R, Cc), "lats")

@@ -134,21 +134,25 @@ def precompute_terrain_tiled(block, res, zref, rank, world, row0, rows_total, *,
                    rows_total=rows_total, what=what, device=device)
 
 
-def flowaccCpp(dm) -> np.ndarray:
-    """Drop-in for flowaccCpp (src/microclimfCpp.cpp:5368-5408): flow accumulation of an elevation matrix (host)."""
+def flowaccCpp(dm, device=None) -> np.ndarray:
+    """Drop-in for flowaccCpp (src/microclimfCpp.cpp:5368-5408): flow accumulation of an elevation matrix.  `device`: None
+    keeps the host sweep; a HIP ordinal runs the pointer-doubling kernels there (include/mcf.h mcf_flowacc_device): the same
+    values, exactly."""
     lib = _abi.load()
     z = np.asfortranarray(np.asarray(dm, dtype=np.float64))
     fa = np.empty(z.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_flowacc(z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), fa.ctypes.data_as(_abi.c_double_p)))
+    args = (z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), fa.ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_flowacc(*args) if device is None else lib.mcf_flowacc_device(*args, int(device)))
     return fa
 
 
-def topidx(dtm, res) -> np.ndarray:
-    """`.topidx(dtm)` (R/internal.R:861-874): the topographic wetness index the solver takes as soilc$twi (host)."""
+def topidx(dtm, res, device=None) -> np.ndarray:
+    """`.topidx(dtm)` (R/internal.R:861-874): the topographic wetness index the solver takes as soilc$twi.  `device`: None
+    keeps the host code; a HIP ordinal computes it there (mcf_topidx_device): equal up to the last bits of atan / tan."""
     lib = _abi.load()
     z = np.asfortranarray(np.asarray(dtm, dtype=np.float64))
     xres, yres = (res, res) if np.isscalar(res) else res
     twi = np.empty(z.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_topidx(z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), float(xres), float(yres),
-                              twi.ctypes.data_as(_abi.c_double_p)))
+    args = (z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), float(xres), float(yres), twi.ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_topidx(*args) if device is None else lib.mcf_topidx_device(*args, int(device)))
     return twi

@@ -766,6 +766,49 @@ SEXP mcfhip_writetonc(SEXP mout, SEXP fileout, SEXP east, SEXP north, SEXP hours
     return R_NilValue;
 }
 
+/* The terrain planes and the wetness index `.runmodel1Cpp` .. `.runmodel4Cpp` build in R when slr / apr / hor / twi / wsa / svf
+ * are missing (R/internal.R:1124-1154), from the elevation matrix on the device: mcf_precompute_terrain (zref = the wind-shelter
+ * height, s = .windsheltera's aggregation) and mcf_topidx_device.  dtm: [rows, cols] matrix, NA = no data; res: c(xres, yres)
+ * (the terrain planes need xres == yres).  -> list(slope, aspect, hor, svf, wsa, twi); slope / aspect hold 0 where terra gives
+ * NA, as the callers set them.  NOT run in the build image (no R there): syntax- and type-checked only. */
+SEXP mcfhip_terrain_twi(SEXP dtm, SEXP res, SEXP zref, SEXP s) {
+    int np = 0;
+    g_keep = NULL; g_nkeep = 0;
+    SEXP dim = getAttrib(dtm, R_DimSymbol);
+    if (TYPEOF(dim) != INTSXP || LENGTH(dim) != 2) Rf_error("mcfhip: dtm must be a matrix");
+    const int rows = INTEGER(dim)[0], cols = INTEGER(dim)[1];
+    const double *r = dbl(res, &np);
+    const double xres = r[0], yres = XLENGTH(res) > 1 ? r[1] : r[0];
+    if (xres != yres) Rf_error("mcfhip: the horizon / wind-shelter pre-compute needs square cells");
+    mcf_terrain_in tin;
+    memset(&tin, 0, sizeof tin);
+    tin.rows = rows; tin.cols = cols; tin.dtm = dbl(dtm, &np);
+    tin.res = xres; tin.zref = asReal(zref); tin.agg = asInteger(s);
+    static const char *nm[6] = {"slope", "aspect", "hor", "svf", "wsa", "twi"};
+    const int layers[6] = {1, 1, 24, 1, 8, 1};
+    SEXP ans = PROTECT(allocVector(VECSXP, 6)); ++np;
+    SEXP nms = PROTECT(allocVector(STRSXP, 6)); ++np;
+    double *ptr[6];
+    for (int k = 0; k < 6; ++k) {
+        SEXP a = PROTECT(allocVector(REALSXP, (R_xlen_t)rows * cols * layers[k])); ++np;
+        SEXP d = PROTECT(allocVector(INTSXP, layers[k] > 1 ? 3 : 2)); ++np;
+        INTEGER(d)[0] = rows; INTEGER(d)[1] = cols;
+        if (layers[k] > 1) INTEGER(d)[2] = layers[k];
+        setAttrib(a, R_DimSymbol, d);
+        SET_VECTOR_ELT(ans, k, a);
+        SET_STRING_ELT(nms, k, mkChar(nm[k]));
+        ptr[k] = REAL(a);
+    }
+    setAttrib(ans, R_NamesSymbol, nms);
+    mcf_terrain_out tout;
+    tout.slope = ptr[0]; tout.aspect = ptr[1]; tout.hor = ptr[2]; tout.svfa = ptr[3]; tout.wsa = ptr[4];
+    int rc = mcf_precompute_terrain(&tin, &tout, 0);
+    if (rc == MCF_OK) rc = mcf_topidx_device(rows, cols, tin.dtm, xres, yres, ptr[5], 0);
+    if (rc != MCF_OK) raise_last(rc, np);
+    UNPROTECT(np);
+    return ans;
+}
+
 static const R_CallMethodDef CallEntries[] = {
     {"mcfhip_runmicro1", (DL_FUNC)&mcfhip_runmicro1, 15},
     {"mcfhip_runmicro2", (DL_FUNC)&mcfhip_runmicro2, 15},
@@ -785,6 +828,7 @@ static const R_CallMethodDef CallEntries[] = {
     {"mcfhip_snowrun_pass1", (DL_FUNC)&mcfhip_snowrun_pass1, 1},
     {"mcfhip_snowrun_pass2", (DL_FUNC)&mcfhip_snowrun_pass2, 6},
     {"mcfhip_writetonc", (DL_FUNC)&mcfhip_writetonc, 9},
+    {"mcfhip_terrain_twi", (DL_FUNC)&mcfhip_terrain_twi, 4},
     {NULL, NULL, 0}};
 
 void R_init_mcfhip_glue(DllInfo *dll) {

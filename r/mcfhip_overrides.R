@@ -81,6 +81,40 @@ mcfhip_enable <- function(glue = "r/mcfhip_glue.so", devices = NULL, blocks = NU
     invisible(.Call("mcfhip_writetonc", mout, fileout, est, nth, hours, wkt, reqhgt, vars, fmt))
   }
   utils::assignInNamespace("writetonc", wnc, ns = "microclimf")
+  # `.runmodel1Cpp` .. `.runmodel4Cpp` (R/internal.R:1065, 1172, 1345, 1461) build slope, aspect, twi, hor, svf and wsa in R when
+  # their slr / apr / twi / hor / svf / wsa arguments are missing: terra::terrain, the flow-accumulation sweep, 24 horizon
+  # passes, the wind-shelter smoothing.  options(mcfhip.from_dtm = TRUE) (opt-in: the wetness index then differs from R's in the
+  # last bits of atan / tan): the missing ones are filled from ONE device call first (mcfhip_terrain_twi) on the elevations as
+  # the function itself cleans them, and the function then finds nothing left to derive.  No line of its preparation is
+  # restated.  NOT run in the build image (no R there).
+  ns <- asNamespace("microclimf")
+  fill_from_dtm <- function(ref, array_weather) function(...) {
+    a <- as.list(match.call(ref, sys.call()))[-1]
+    a <- lapply(a, eval, envir = parent.frame())
+    gone <- function(x) is.null(x) || class(x)[1] == "logical"
+    six <- c("slr", "apr", "hor", "twi", "wsa", "svf")
+    if (isTRUE(getOption("mcfhip.from_dtm", FALSE)) && any(vapply(a[six], gone, NA))) {
+      up <- get(".unpack", envir = ns)(a$dtm, a$vegp, a$soilc)
+      d <- get(".cleanvars", envir = ns)(up$vegp, up$soilc, up$dtm)$dtm
+      zref <- if (array_weather) a[[1]][[which(!vapply(a[[1]], is.null, NA))[1]]]$zref else a[[1]]$zref
+      zm <- get(".is", envir = ns)(d)
+      rs <- terra::res(d)
+      agg <- if (rs[1] <= 100) 10L else 1L                         # R/internal.R:1150-1151
+      t <- .Call("mcfhip_terrain_twi", zm, rs, zref, agg)
+      as_r <- function(m) get(".rast", envir = ns)(m, d)
+      if (gone(a$slr)) a$slr <- as_r(t$slope)
+      if (gone(a$apr)) a$apr <- as_r(t$aspect)
+      if (gone(a$twi)) a$twi <- as_r(t$twi)
+      if (gone(a$svf) && gone(a$hor)) a$svf <- as_r(t$svf)        # (with a hor of the caller's, svf stays the function's to derive from it)
+      if (gone(a$hor)) a$hor <- t$hor
+      if (gone(a$wsa)) a$wsa <- t$wsa
+    }
+    do.call(ref, a)
+  }
+  for (k in 1:4) local({
+    nm <- paste0(".runmodel", k, "Cpp")
+    utils::assignInNamespace(nm, fill_from_dtm(get(nm, envir = ns), k %% 2 == 0), ns = "microclimf")
+  })
   utils::assignInNamespace("runmicro1Cpp", rm1, ns = "microclimf")
   utils::assignInNamespace("runmicro2Cpp", rm2, ns = "microclimf")
   utils::assignInNamespace("runmicro3Cpp", rm3, ns = "microclimf")
