@@ -54,7 +54,9 @@ extern "C" {
                              * 4: mcf_nc_spec grew format / deflate_level (zero = the behaviour of version 3); 5: mcf_runmicrosnow1 / mcf_snowrun_*;
                              * 6: mcf_snowdriver_in grew af_wsa_s (the former `reserved`) / af_wind at its end — read only with array weather;
                              * 7: below ground streamed through day chunks (mcf_plan_create_streamed, mcf_plan_below_prepare);
-                             * 8: plans and one-shot solves that take the dtm (mcf_dtm_spec), flow accumulation / wetness index on the device */
+                             * 8: plans and one-shot solves that take the dtm (mcf_dtm_spec), flow accumulation / wetness index on the device
+                             *    (added since, functions only: mcf_plan_below_set_days, mcf_below_days_range, mcf_runmicrosnow1_below,
+                             *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -294,6 +296,23 @@ int mcf_plan_belowground(mcf_plan *plan);
 int mcf_plan_create_streamed(const mcf_grid_inputs *in, const mcf_options *opt,
                              int32_t ring_days, int32_t ring_slots, mcf_plan **plan);
 int mcf_plan_below_prepare(mcf_plan *plan, const mcf_grid_inputs *in);
+/* A streamed below-ground plan over a subset of its days (vector forcing), before mcf_plan_below_prepare: `days` = n whole days
+ * of the plan's series, strictly ascending.  From then on the series Tbelowgroundv sees is those days joined end to end
+ * (24 n steps, no steps behind the last day): the damping-depth mean, the hourly sum, the daily means and the 47-step windows
+ * run over the subset in its order, across the gaps of the calendar, while forcing, vegetation layer and the point model's
+ * Tg / Tbp are read at each day's own place — the bits of a whole-series plan made from inputs subset to those days (whose
+ * maximum air temperature mcf_plan_set_mxtc supplies).  mcf_plan_below_prepare sweeps the subset's days only.
+ * mcf_plan_run_days(day0, ndays, slot) then runs the subset's days inside the calendar range [day0, day0 + ndays), each at its
+ * own place day - day0 of the slot (the other days of the slot are not touched); the ranges have to take the subset in order
+ * from its first day without leaving one out ("day order", MCF_ERR_STATE), and a range that holds none of its days does
+ * nothing.  MCF_ERR_STATE after the prepare, on a plan that is not streamed below ground or has array forcing; MCF_ERR_ARG for
+ * a list that is empty, unsorted, repeats a day or leaves the series. */
+int mcf_plan_below_set_days(mcf_plan *plan, const int32_t *days, int32_t n);
+/* The host bookkeeping of the above, no device needed: checks `days` (as mcf_plan_below_set_days does, against a series of
+ * total_days whole days) and gives the subset positions [*pos0, *pos0 + *npos) whose days lie in the calendar range
+ * [day0, day0 + ndays); *npos = 0: none. */
+int mcf_below_days_range(const int32_t *days, int32_t n, int32_t total_days, int32_t day0, int32_t ndays, int32_t *pos0,
+                         int32_t *npos);
 int mcf_plan_sync(mcf_plan *plan);
 
 /* Copy `nsteps` time steps of variable `var` from ring slot `slot` (starting at
@@ -794,8 +813,7 @@ int mcf_snowplan_microsnow(mcf_snowplan *plan, mcf_plan *solver, int32_t chunk, 
  *           smod$umu, `.sortl2` vegetation, bare-ground terrain (slope, aspect, skyview, wsa, hor), lat, lon, zref, Smax.
  *           May be NULL only if the year has no snow day.
  *   mat     micropoint$matemp
- * `opt`: reqhgt >= 0 (below ground the reference smooths whole series: use mcf_runmicro1 + mcf_gridmicrosnow1 on host
- * arrays), out[] as for mcf_runmicro1; with reqhgt == 0 gridmicrosnow1 is given the reference's fixed mask (:3616-3619).
+ * `opt`: reqhgt >= 0 (reqhgt < 0: the `_below` entries further down), out[] as for mcf_runmicro1; with reqhgt == 0 gridmicrosnow1 is given the reference's fixed mask (:3616-3619).
  * `out`: [rows, cols, tsteps] per requested variable; `smod` (optional, members may be NULL): `.snowmodel1`'s returned arrays.
  * Days that are in neither class (max totalSWE <= 0 and min != 0: a melted pack's negative rounding residue) are NA in
  * `out` — the reference's merge indexes past its arrays there (:3650-3655).  Steps past the last whole 5-day chunk are
@@ -830,6 +848,20 @@ typedef struct mcf_snowrun mcf_snowrun;
 /* `in->micro` and `in->mat` are not read here; multi = NULL: one block on opt->device.  The caller's arrays must stay valid
  * until mcf_snowrun_destroy. */
 int mcf_snowrun_create(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi, mcf_snowrun **run);
+/* Below ground (reqhgt < 0, data.frame weather; MCF_ERR_ARG otherwise): mcf_runmicrosnow1 / mcf_runmicrosnow1_multi /
+ * mcf_snowrun_create with the same arguments.  `.runmicrosnow1` gives the grid solver the NO-SNOW days' subset series, so
+ * Tbelowgroundv's running means (cpp:1474-1539) see those days joined end to end: each block's solver plan is a streamed
+ * below-ground plan over them (mcf_plan_create_streamed, mcf_plan_below_set_days) — O(cells x days) of state, no whole-series
+ * buffer, and with complete = 1 one more solver sweep over the no-snow days between the passes.  Pass 2 solves EVERY cell of a
+ * chunk's no-snow days (a cell's ground temperature under today's snow feeds its means on later days: mcf_snowrun_stats
+ * reports no tile-day left out), makes the chunk's Tz, and then the snow-day model (gridmicrosnow1 with `out[c(1, 4)]`,
+ * R/internal.R:3621-3624: Tz and soilm; every snow-covered cell-step is below the snow surface, cpp:5029-5051) merges into the
+ * same slot.  On a day of both classes the other requested outputs keep the solver's values, on a snow-only day they are NA.
+ * Steps behind the last whole day are NA.  A handle runs one period: a second mcf_snowrun_pass2 is MCF_ERR_STATE. */
+int mcf_runmicrosnow1_below(const mcf_microsnow_in *in, const mcf_options *opt, mcf_outputs *out, const mcf_snowdriver_out *smod);
+int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi, mcf_outputs *out,
+                                  const mcf_snowdriver_out *smod);
+int mcf_snowrun_create_below(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi, mcf_snowrun **run);
 void mcf_snowrun_destroy(mcf_snowrun *run);
 int32_t mcf_snowrun_days(const mcf_snowrun *run);     /* tsteps / 24 */
 /* What pass 2 was spared (diagnostics; tests assert which path ran): stats[0] tile-days of the solver's days that are snow days as

@@ -204,7 +204,8 @@ EXPORTS = (
     "mcf_flowacc", "mcf_topidx",
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
     "mcf_snowrun_pass1", "mcf_snowrun_pass2", "mcf_snowplan_run_chunk_pitched", "mcf_snowplan_chunk_af",
-    "mcf_plan_create_streamed", "mcf_plan_below_prepare",
+    "mcf_plan_create_streamed", "mcf_plan_below_prepare", "mcf_plan_below_set_days", "mcf_below_days_range",
+    "mcf_runmicrosnow1_below", "mcf_runmicrosnow1_below_multi", "mcf_snowrun_create_below",
     "mcf_flowacc_device", "mcf_topidx_device", "mcf_plan_create_dtm", "mcf_runmicro_dtm",
 )
 
@@ -353,6 +354,11 @@ def load() -> C.CDLL:
     lib.mcf_plan_create_streamed.argtypes = [GI, OP, C.c_int32, C.c_int32, C.POINTER(P)]
     lib.mcf_plan_below_prepare.restype = C.c_int
     lib.mcf_plan_below_prepare.argtypes = [P, GI]
+    if hasattr(lib, "mcf_plan_below_set_days"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_plan_below_set_days.restype = C.c_int
+        lib.mcf_plan_below_set_days.argtypes = [P, c_int32_p, C.c_int32]
+        lib.mcf_below_days_range.restype = C.c_int
+        lib.mcf_below_days_range.argtypes = [c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]
     lib.mcf_plan_sync.restype = C.c_int
     lib.mcf_plan_sync.argtypes = [P]
     lib.mcf_plan_fetch.restype = C.c_int
@@ -485,6 +491,13 @@ def load() -> C.CDLL:
         lib.mcf_runmicrosnow1_multi.argtypes = [MI, OP, C.POINTER(Multi), OU, SO]
         lib.mcf_snowrun_create.restype = C.c_int
         lib.mcf_snowrun_create.argtypes = [MI, OP, C.POINTER(Multi), C.POINTER(P)]
+        if hasattr(lib, "mcf_snowrun_create_below"):
+            lib.mcf_runmicrosnow1_below.restype = C.c_int
+            lib.mcf_runmicrosnow1_below.argtypes = [MI, OP, OU, SO]
+            lib.mcf_runmicrosnow1_below_multi.restype = C.c_int
+            lib.mcf_runmicrosnow1_below_multi.argtypes = [MI, OP, C.POINTER(Multi), OU, SO]
+            lib.mcf_snowrun_create_below.restype = C.c_int
+            lib.mcf_snowrun_create_below.argtypes = [MI, OP, C.POINTER(Multi), C.POINTER(P)]
         lib.mcf_snowrun_destroy.restype = None
         lib.mcf_snowrun_destroy.argtypes = [P]
         lib.mcf_snowrun_stats.restype = C.c_int

@@ -311,6 +311,13 @@ class Plan:
         solver's first sweep).  Array forcing streams the forcing through slot 0: upload the chunks' forcing again afterwards."""
         _abi.check(self._lib.mcf_plan_below_prepare(self._p, C.byref(self._m.inputs)))
 
+    def below_set_days(self, days):
+        """Streamed below-ground plan, before below_prepare(): the series Tbelowgroundv sees is the listed whole days (strictly
+        ascending) joined end to end (include/mcf.h mcf_plan_below_set_days).  run_days(day0, ndays, slot) then runs the
+        subset's days inside that calendar range, each at its own place day - day0 of the slot."""
+        d = np.ascontiguousarray(np.asarray(days).astype(np.int32))
+        _abi.check(self._lib.mcf_plan_below_set_days(self._p, d.ctypes.data_as(_abi.c_int32_p), int(d.size)))
+
     def sync(self):
         _abi.check(self._lib.mcf_plan_sync(self._p))
 
@@ -376,6 +383,16 @@ class Plan:
         ms, n = C.c_double(), C.c_int64()
         _abi.check(self._lib.mcf_plan_kernel_stats(self._p, C.byref(ms), C.byref(n)))
         return ms.value, n.value
+
+
+def below_days_range(days, total_days: int, day0: int, ndays: int):
+    """(pos0, npos): the positions of the day subset `days` that lie in the calendar range [day0, day0 + ndays) of a series of
+    `total_days` whole days (include/mcf.h mcf_below_days_range; the list is checked as Plan.below_set_days checks it)."""
+    d = np.ascontiguousarray(np.asarray(days).astype(np.int32))
+    pos0, npos = C.c_int32(), C.c_int32()
+    _abi.check(_abi.load().mcf_below_days_range(d.ctypes.data_as(_abi.c_int32_p), int(d.size), int(total_days), int(day0), int(ndays),
+                                                C.byref(pos0), C.byref(npos)))
+    return pos0.value, npos.value
 
 
 def runbioclim3Cpp(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, mat, out,

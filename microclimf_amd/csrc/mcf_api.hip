@@ -142,6 +142,10 @@ struct mcf_plan {
     bool bg_stream = false;
     bool below_ready = false;            // mcf_plan_below_prepare has run
     int below_next = 0;                  // the day the next chunk has to start on (or 0: a new pass)
+    // mcf_plan_below_set_days: the calendar day of each subset position (empty: every day), and its copy on the device;
+    // below_next then counts subset positions
+    std::vector<int32_t> below_days;
+    int32_t* d_below_days = nullptr;
     double *d_tgring = nullptr, *d_hsum = nullptr, *d_dmean = nullptr, *d_ybuf = nullptr, *d_wrap = nullptr, *d_prev = nullptr;
     double *d_Tgp_slots = nullptr, *d_Tbp_slots = nullptr;      // [slots][ring_days * 24][N]
     int64_t tg_tile_stride = 0;
@@ -1077,7 +1081,7 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
     if (day0 < 0 || ndays < 1 || day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
     if ((!p->bg || p->bg_stream) && (slot_day0 < 0 || slot_day0 + ndays > p->ring_days))
         return fail(MCF_ERR_ARG, "more days than the ring slot holds");
-    if (slot_day0 != 0 && p->bg) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
+    if (slot_day0 != 0 && p->bg && !p->bg_stream) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
     HIP_TRY(hipSetDevice(p->device));
     int rc = ensure_cells(p);
     if (rc) return rc;
@@ -1143,7 +1147,12 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
 // the state of a streamed plan as k_below_* see it; the chunk fields are the caller's
 mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
     mcf::BelowStreamArgs b{};
-    b.N = p->N; b.tsteps = (int)p->tsteps; b.ndays = p->ndays; b.complete = p->opt.complete; b.hiy = p->hiy;
+    b.N = p->N; b.tsteps = (int)p->tsteps; b.ndays = p->ndays;
+    if (!p->below_days.empty()) {       // a day subset: the series is its days joined, whole days only
+        b.ndays = (int)p->below_days.size(); b.tsteps = 24 * b.ndays;
+        b.days = p->d_below_days;
+    }
+    b.complete = p->opt.complete; b.hiy = p->hiy;
     b.reqhgt = p->opt.reqhgt; b.mat = p->opt.mat;
     b.hgt = p->d_veg[0];
     b.tg.base = p->d_tgring; b.tg.N = p->N; b.tg.cpb = p->cpb;
@@ -1155,31 +1164,77 @@ mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
     return b;
 }
 
+// the part of a streamed below-ground plan's series that calendar days [day0, day0 + ndays) hold: positions [pos0, pos0 + npos)
+// of the series Tbelowgroundv sees, and their calendar days as runs (first day, days) of consecutive days.  Without a day
+// subset that is the range itself.
+struct BelowRange {
+    int pos0 = 0, npos = 0;
+    std::vector<std::pair<int, int>> runs;
+};
+void below_range(const mcf_plan* p, int32_t day0, int32_t ndays, BelowRange& r) {
+    r = BelowRange{};
+    if (p->below_days.empty()) {
+        r.pos0 = day0; r.npos = ndays;
+        r.runs.emplace_back(day0, ndays);
+        return;
+    }
+    mcf_below_days_range(p->below_days.data(), (int32_t)p->below_days.size(), p->ndays, day0, ndays, &r.pos0, &r.npos);
+    for (int q = r.pos0; q < r.pos0 + r.npos; ++q) {
+        const int d = p->below_days[(size_t)q];
+        if (!r.runs.empty() && r.runs.back().first + r.runs.back().second == d) ++r.runs.back().second;
+        else r.runs.emplace_back(d, 1);
+    }
+}
+
+// the solver's launches for the runs of `r`, each at its days' own place (day - day0) of `slot` and of the Tg ring
+int below_solve_args(mcf_plan* p, const BelowRange& r, int32_t day0, int32_t slot, std::vector<mcf::SolveArgs>& as) {
+    for (const auto& run : r.runs) {
+        mcf::SolveArgs a{};
+        bool fast = false, soil_daily = false;
+        int rc = solve_args(p, run.first, run.second, slot, run.first - day0, a, fast, soil_daily);
+        if (rc) return rc;
+        if (a.tg_ring) a.tg_ring += (int64_t)(run.first - day0) * mcf::ring_block_doubles(p->cpb);
+        as.push_back(a);
+    }
+    return MCF_OK;
+}
+
 // days [day0, day0 + ndays) of a streamed below-ground plan into `slot`: the solver (Tg into the Tg ring, the other outputs into
 // the slot), then Tz made from Tg and the per-cell state.  Chunks run in day order from day 0; the chunk that ends on the last
-// whole day also writes the tsteps % 24 steps behind it (the slot needs a day more for them).
+// whole day also writes the tsteps % 24 steps behind it (the slot needs a day more for them).  With a day subset
+// (mcf_plan_below_set_days) the subset's days inside the range are run, each at its own place day - day0 of the slot, in
+// subset order from the subset's first day; a range that holds none of them does nothing.
 int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0) {
     const bool tz = p->var_slot[MCF_OUT_TZ] >= 0;
     if (slot_day0 != 0) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
     if (tz && !p->below_ready)
         return fail(MCF_ERR_STATE, "streamed below-ground plan: call mcf_plan_below_prepare before running days");
-    if (tz && day0 != 0 && day0 != p->below_next)
-        return fail(MCF_ERR_STATE, "streamed below-ground plan: chunks run in day order from day 0 without gaps (expected day " +
-                                   std::to_string(p->below_next) + " or 0, got " + std::to_string(day0) + ")");
-    mcf::SolveArgs a{};
-    bool fast = false, soil_daily = false;
-    int rc = solve_args(p, day0, ndays, slot, 0, a, fast, soil_daily);
+    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
+    if (day0 < 0 || ndays < 1 || day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
+    if (ndays > p->ring_days) return fail(MCF_ERR_ARG, "more days than the ring slot holds");
+    const bool sub = !p->below_days.empty();
+    BelowRange r;
+    below_range(p, day0, ndays, r);
+    if (tz && r.pos0 != 0 && r.pos0 != p->below_next && r.npos > 0)
+        return fail(MCF_ERR_STATE, std::string("streamed below-ground plan: chunks run in day order from day 0 without gaps (expected ") +
+                                   (sub ? "subset position " : "day ") + std::to_string(p->below_next) + " or 0, got " +
+                                   std::to_string(r.pos0) + ")");
+    if (r.npos == 0) return MCF_OK;
+    std::vector<mcf::SolveArgs> as;
+    int rc = below_solve_args(p, r, day0, slot, as);
     if (rc) return rc;
-    const bool tail = day0 + ndays == p->ndays && p->tsteps > (int64_t)p->ndays * 24;
+    const bool tail = !sub && day0 + ndays == p->ndays && p->tsteps > (int64_t)p->ndays * 24;
     if (tz && tail && ndays + 1 > p->ring_days)
         return fail(MCF_ERR_ARG, "streamed below-ground plan: the chunk that ends on the last whole day needs one day more in its "
                                  "slot, for the steps behind that day");
     auto launch = [&]() {
-        mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
-        ++p->slow_launches;
+        for (const mcf::SolveArgs& a : as) {
+            mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
+            ++p->slow_launches;
+        }
         if (!tz) return;
         mcf::BelowStreamArgs b = below_args(p, slot);
-        b.day0 = day0; b.ndays_chunk = ndays; b.tail = tail ? 1 : 0;
+        b.day0 = r.pos0; b.ndays_chunk = r.npos; b.cal0 = day0; b.tail = tail ? 1 : 0;
         if (p->d_Tgp_slots) {      // the slot's point-model series start at the slot's first uploaded day
             const int64_t off = ((int64_t)slot * p->ring_days * 24 + (int64_t)(day0 - p->force_day0[slot]) * 24) * p->N;
             b.Tgp = p->d_Tgp_slots + off; b.Tbp = p->d_Tbp_slots + off;
@@ -1198,10 +1253,50 @@ int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int3
         launch();
     }
     HIP_TRY(hipGetLastError());
-    p->below_next = day0 + ndays;
+    p->below_next = r.pos0 + r.npos;
     return MCF_OK;
 }
 }  // namespace
+
+int mcf_below_days_range(const int32_t* days, int32_t n, int32_t total_days, int32_t day0, int32_t ndays, int32_t* pos0,
+                         int32_t* npos) {
+    if (n < 1) return fail(MCF_ERR_ARG, "day subset: no days");
+    if (!days || !pos0 || !npos) return fail(MCF_ERR_ARG, "null argument");
+    for (int32_t q = 0; q < n; ++q) {
+        if (days[q] < 0 || days[q] >= total_days)
+            return fail(MCF_ERR_ARG, "day subset: day " + std::to_string(days[q]) + " is out of range (the series has " +
+                                     std::to_string(total_days) + " whole days)");
+        if (q > 0 && days[q] <= days[q - 1])
+            return fail(MCF_ERR_ARG, "day subset: the days have to be strictly ascending (position " + std::to_string(q) + ")");
+    }
+    if (day0 < 0 || ndays < 0 || (int64_t)day0 + ndays > total_days) return fail(MCF_ERR_ARG, "day range out of bounds");
+    const int32_t* lo = std::lower_bound(days, days + n, day0);
+    const int32_t* hi = std::lower_bound(lo, days + n, day0 + ndays);
+    *pos0 = (int32_t)(lo - days);
+    *npos = (int32_t)(hi - lo);
+    return MCF_OK;
+}
+
+int mcf_plan_below_set_days(mcf_plan* p, const int32_t* days, int32_t n) {
+    if (!p) return fail(MCF_ERR_ARG, "null plan");
+    if (!p->bg_stream)
+        return fail(MCF_ERR_STATE, "mcf_plan_below_set_days needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
+    if (p->af) return fail(MCF_ERR_STATE, "mcf_plan_below_set_days: a day subset needs vector forcing");
+    if (p->below_ready) return fail(MCF_ERR_STATE, "mcf_plan_below_set_days comes before mcf_plan_below_prepare");
+    int32_t pos0, npos;
+    int rc = mcf_below_days_range(days, n, p->ndays, 0, 0, &pos0, &npos);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    if (!p->d_below_days) {
+        void* q;
+        if ((rc = dalloc(p, &q, (int64_t)std::max(p->ndays, 1) * 4))) return rc;
+        p->d_below_days = (int32_t*)q;
+    }
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->below_days.assign(days, days + n);
+    HIP_TRY(hipMemcpy(p->d_below_days, p->below_days.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    return MCF_OK;
+}
 
 int mcf_plan_below_prepare(mcf_plan* p, const mcf_grid_inputs* in) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
@@ -1223,11 +1318,15 @@ int mcf_plan_below_prepare(mcf_plan* p, const mcf_grid_inputs* in) {
         HIP_TRY(hipMemsetAsync(p->d_wrap, 0, (size_t)(N * mcf::kBelowWin) * 8, p->stream));
     }
     if (!complete && !p->af) {
-        // the damping-depth pre-pass over the whole series from the time table
-        mcf::BelowDDArgs d{};
-        d.N = N; d.cellc = p->d_cellc; d.ntiles_total = p->ntiles; d.cpb = p->cpb; d.daylayer = p->d_daylayer; d.tt = p->d_tt;
-        d.day0 = 0; d.ndays = p->ndays; d.ddsum = p->d_ddsum;
-        mcf::launch_below_dd(d, p->stream);
+        // the damping-depth pre-pass over the whole series (a day subset: its runs of days, in order) from the time table
+        BelowRange whole;
+        below_range(p, 0, p->ndays, whole);
+        for (const auto& run : whole.runs) {
+            mcf::BelowDDArgs d{};
+            d.N = N; d.cellc = p->d_cellc; d.ntiles_total = p->ntiles; d.cpb = p->cpb; d.daylayer = p->d_daylayer; d.tt = p->d_tt;
+            d.day0 = run.first; d.ndays = run.second; d.ddsum = p->d_ddsum;
+            mcf::launch_below_dd(d, p->stream);
+        }
         HIP_TRY(hipGetLastError());
     } else {
         // chunk by chunk through slot 0: the pre-pass on the uploaded forcing (complete = 0), or sweep 1 — the solver with the
@@ -1243,14 +1342,18 @@ int mcf_plan_below_prepare(mcf_plan* p, const mcf_grid_inputs* in) {
                 d.day0 = d0; d.ndays = nd; d.ddsum = p->d_ddsum;
                 mcf::launch_below_dd(d, p->stream);
             } else {
-                mcf::SolveArgs a{};
-                bool fast = false, soil_daily = false;
-                if ((rc = solve_args(p, d0, nd, 0, 0, a, fast, soil_daily))) return rc;
-                a.out_sel = ~(uint64_t)0;       // nothing into the ring
-                a.ddsum = p->d_ddsum;
-                mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
+                BelowRange r;
+                below_range(p, d0, nd, r);
+                if (r.npos == 0) continue;      // none of the subset's days
+                std::vector<mcf::SolveArgs> as;
+                if ((rc = below_solve_args(p, r, d0, 0, as))) return rc;
+                for (mcf::SolveArgs& a : as) {
+                    a.out_sel = ~(uint64_t)0;       // nothing into the ring
+                    a.ddsum = p->d_ddsum;
+                    mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
+                }
                 mcf::BelowStreamArgs b = below_args(p, 0);
-                b.day0 = d0; b.ndays_chunk = nd;
+                b.day0 = r.pos0; b.ndays_chunk = r.npos; b.cal0 = d0;
                 mcf::launch_below_acc(b, p->stream);
             }
             HIP_TRY(hipGetLastError());

@@ -193,7 +193,19 @@ struct BelowStreamArgs {
     // (array forcing, step index relative to the chunk)
     const double *Tgp, *Tbp;
     int32_t per_cell_pointm;
+    // a day subset (mcf_plan_below_set_days): days[q] = the calendar day of subset position q, or null — every day, q itself.
+    // With it the series Tbelowgroundv sees is the subset's days joined: tsteps = 24 x ndays, ndays = the subset's length,
+    // day0 / ndays_chunk count subset positions, and position q's 24 steps lie at day days[q] - cal0 of the tg / tz views
+    // (cal0: the calendar day at the views' day 0); the point model's series are read at the calendar day's own steps.
+    const int32_t* days;
+    int32_t cal0;
 };
+// step k of the chunk, in the order of the series Tbelowgroundv sees -> step of the chunk's tg / tz views
+__host__ __device__ inline int below_view_step(const BelowStreamArgs& a, int k) {
+    if (!a.days) return k;
+    const int q = k / 24;
+    return (a.days[a.day0 + q] - a.cal0) * 24 + (k - 24 * q);
+}
 // complete = 0: ddsum += DD over days [day0, day0 + ndays_chunk) from the soil moisture alone (soil_spread, soil_ksoil,
 // soil_damping: the functions pass 1 and 2 use), in k_solve's order.  Vector forcing reads the time table, array forcing the
 // slot's tiled forcing ring (the chunk's days).

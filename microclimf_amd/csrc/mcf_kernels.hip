@@ -1313,14 +1313,14 @@ __global__ __launch_bounds__(256) void k_below_acc(BelowStreamArgs a) {
     for (int dl = 0; dl < a.ndays_chunk; ++dl) {
         double s = 0.0;
         for (int j = 0; j < 24; ++j) {
-            const double x = a.tg.at(c, dl * 24 + j);
+            const double x = a.tg.at(c, below_view_step(a, dl * 24 + j));
             hs = hs + x;                                                     // cpp:1489 (k_belowground's meanT)
             s += x;                                                          // cpp:607-610
         }
         a.dmean[c + N * (a.day0 + dl)] = s / 24.0;
     }
     a.hsum[c] = hs;
-    below_shift(a.wrap, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, k); });
+    below_shift(a.wrap, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, below_view_step(a, k)); });
 }
 
 // after sweep 1 (complete = 1): the steps past the last whole day (Tg 0 there) into hsum and wrap; the circular n/24-day means
@@ -1358,7 +1358,7 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
     const int k0 = dl * 24;                         // the day's first step in the chunk
     const int64_t cs = (int64_t)a.day0 * 24;        // the chunk's first step in the series
     double* const zb = const_cast<double*>(a.tz.base);
-    auto put = [&](int k, double v) { zb[a.tz.index(c, k)] = v; };
+    auto put = [&](int k, double v) { zb[a.tz.index(c, below_view_step(a, k))] = v; };
     if (isnan(a.hgt[c])) {
         for (int h = 0; h < hours; ++h) put(k0 + h, na_real());
         return;
@@ -1367,7 +1367,7 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
     // k >= L past the last whole day (0, as in the whole series' zero fill)
     auto x = [&](int64_t k) -> double {
         if (k >= L) return 0.0;
-        if (k >= 0) return a.tg.at(c, k);
+        if (k >= 0) return a.tg.at(c, below_view_step(a, (int)k));
         const int64_t ka = cs + k;
         if (ka >= 0) return a.prev[c + N * (k + kBelowWin)];
         return a.wrap[c + N * (ka + kBelowWin)];
@@ -1417,7 +1417,8 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
         for (int h = 0; h < 24; ++h) put(k0 + h, x(k0 + h));
         return;
     }
-    const int64_t i0 = cs + k0;
+    // the point model's series at the day's own place (a day subset: its calendar day)
+    const int64_t i0 = a.days ? (int64_t)a.days[a.day0 + dl] * 24 : cs + k0;
     double gmx = x(k0), gmn = gmx, gsum = 0.0;
     double pmx = ser(a.Tgp, i0), pmn = pmx, psum = 0.0, bsum = 0.0;
     for (int j = 0; j < 24; ++j) {
@@ -1457,7 +1458,7 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
 __global__ __launch_bounds__(256) void k_below_carry(BelowStreamArgs a) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
     if (c >= N) return;
-    below_shift(a.prev, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, k); });
+    below_shift(a.prev, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, below_view_step(a, k)); });
 }
 
 // ------------------------------------------------------------------------------------

@@ -728,13 +728,24 @@ __global__ __launch_bounds__(256, AF ? 3 : MCF_MICRORING_WAVES) void k_microsnow
 //     well: its value stays) holds a sentinel and is not stored.
 constexpr int kRtCells = 63, kRtWaves = MCF_MICRORING_WAVES == 3 ? 6 : 8;      // two workgroups per CU (56 KB of LDS each): 4 or 3 waves per SIMD
 constexpr unsigned long long kTailEmpty = 0x7FF8A5A5DEAD0001ULL;      // (a NaN payload no arithmetic produces)
-__global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsnow_tiles(MicroRingArgs q, const MicroStep* __restrict__ tb,
-                                                                                       const int32_t* __restrict__ tb_daymap,
-                                                                                       const int32_t* __restrict__ tb_nosnow) {
+// BELOW: reqhgt < 0 with gridmicrosnow1's `out[c(1, 4)]` (the below-ground snow run) — every snow-covered cell-step is below the
+// snow surface (reqhgt - groundsnowdepth < 0, cpp:5029-5051), so the lane needs meanD, the day's mean ground-snow temperature,
+// sTg, sdepg, swe, Smax and nothing else: no direction planes, no site table, no step table, no sTc / sden, and only Tz and soilm
+// ever carry a value — they alone go through s_tail; the other held variables are NA on a snow-only day, stored straight.  The
+// values are the generic instantiation's: the same micro_below on the same operands.  LDS: 2 + 6 + 4 KB instead of 10 + 16 + 30 + 4.
+// the row of the cell table a BELOW workgroup keeps
+template <bool BELOW>
+__device__ __forceinline__ constexpr int mc_row(int f) {
+    return !BELOW ? f : f == MC_HGT ? 0 : f == MC_MEAND ? 1 : f == MC_SMAX ? 2 : 3;
+}
+template <bool BELOW>
+__global__ __launch_bounds__(64 * kRtWaves, BELOW ? 8 : MCF_MICRORING_WAVES) void k_microsnow_tiles(MicroRingArgs q, const MicroStep* __restrict__ tb,
+                                                                                                   const int32_t* __restrict__ tb_daymap,
+                                                                                                   const int32_t* __restrict__ tb_nosnow) {
     snow::snow_tables_init();
-    __shared__ double s_mc[MC_COUNT][64];
-    __shared__ double s_hw[32][64];                   // 24 horizon + 8 wind-shelter planes of the workgroup's cells
-    __shared__ double s_tail[MCF_NOUT * 3 * 8 * 16];   // [held variable][tile][hour group][15 values + padding]
+    __shared__ double s_mc[BELOW ? 4 : MC_COUNT][64];
+    __shared__ double s_hw[BELOW ? 1 : 32][BELOW ? 1 : 64];   // 24 horizon + 8 wind-shelter planes of the workgroup's cells
+    __shared__ double s_tail[(BELOW ? 2 : MCF_NOUT) * 3 * 8 * 16];   // [held variable][tile][hour group][15 values + padding]
     constexpr int kTzdDays = 8;
     __shared__ double s_tzd[kTzdDays][64];            // the days' mean ground-snow temperatures (chunks of up to eight days)
     const MicroArgs& a = q.m;
@@ -746,7 +757,14 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
     {
         const int64_t cc = c0 + lane < N ? c0 + lane : N - 1;             // idle lanes read the last cell and write nothing
         // ---- once per workgroup: the cell table (a part by each of the first three waves) and the 32 direction planes
-        if (wv == 0) {
+        if constexpr (BELOW) {
+            if (wv == 0) {
+                s_mc[mc_row<true>(MC_HGT)][lane] = a.hgt[cc];
+            } else if (wv == 2) {
+                s_mc[mc_row<true>(MC_MEAND)][lane] = a.meanD[cc];
+                s_mc[mc_row<true>(MC_SMAX)][lane] = a.Smax ? a.Smax[cc] : 0.0;
+            }
+        } else if (wv == 0) {
             const double hgt = a.hgt[cc], pai = a.pai[cc], leafd = a.leafd[cc];
             s_mc[MC_HGT][lane] = hgt; s_mc[MC_PAI][lane] = pai; s_mc[MC_LEAFD][lane] = leafd;
             s_mc[MC_IHGT][lane] = gdiv(1.0, hgt); s_mc[MC_ILEAFD][lane] = gdiv(1.0, leafd); s_mc[MC_IPAI][lane] = gdiv(1.0, pai);
@@ -800,7 +818,8 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
     uint32_t rofs = (uint32_t)(tl * (int)q.ring.tile_stride + cl) * 8u;            // (a tile's days x variables x 512 doubles: < 2^29)
     const int tofs = tl * 128 + (cl - 16);
     uint32_t lofs = (uint32_t)lane * 8u;
-    const int nheld = __builtin_popcount(q.held);
+    // the variables that go through s_tail: every held one, or (BELOW) Tz and soilm
+    const int nheld = BELOW ? (int)((q.held & 1u) + ((q.held >> 3) & 1u)) : __builtin_popcount(q.held);
     for (int day = 0; day < q.ndays; ++day) {
         const int sub = tb_daymap[day];               // uniform: scalar loads
         if (sub < 0) continue;
@@ -817,9 +836,9 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
                 for (int h = 0; h < 24; ++h) sumd += tg[cc + N * h];
                 Tzd = sumd / 24.0;
             }
-            s_mc[MC_TZD][lane] = Tzd;
+            s_mc[mc_row<BELOW>(MC_TZD)][lane] = Tzd;
         }
-        const double* const tzd_row = q.ndays <= kTzdDays ? &s_tzd[day][0] : &s_mc[MC_TZD][0];
+        const double* const tzd_row = q.ndays <= kTzdDays ? &s_tzd[day][0] : &s_mc[mc_row<BELOW>(MC_TZD)][0];
         for (int e = tid; e < nheld * 384; e += 64 * kRtWaves) reinterpret_cast<unsigned long long*>(s_tail)[e] = kTailEmpty;
         __syncthreads();
         // the workgroup's first tile's block of this day (uniform)
@@ -838,11 +857,15 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
                     if (direct) {
                         asm("" : "+v"(rofs));       // (keeps the offset's zero-extension in the store's own block: mcf_kernels.hip `put`)
                         *(double*)((char*)(dayblk + (rank * vs + (64 * hg + 16 * hm))) + rofs) = v;
-                    } else {
+                    } else if (!BELOW) {
                         s_tail[(rank * 384 + hg * 16 + 5 * hm) + tofs] = v;
+                    } else if (i == 0 || i == 3) {
+                        s_tail[((i == 0 ? 0 : (int)(held & 1u)) * 384 + hg * 16 + 5 * hm) + tofs] = v;
+                    } else {      // (NA on a snow-only day: the fourth line's place, where the flush puts a staged value)
+                        dayblk[(int64_t)tl * q.ring.tile_stride + rank * vs + 64 * hg + 48 + 5 * hm + (cl - 16)] = v;
                     }
                 };
-                auto MC = [&](int f) { return s_mc[f][li]; };
+                auto MC = [&](int f) { return s_mc[mc_row<BELOW>(f)][li]; };
                 const double hgt = MC(MC_HGT);
                 if (isnan(hgt)) {            // cpp:4988-4989
                     if (!keep) {
@@ -873,6 +896,12 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
                     if ((selm >> i) & 1u) put(i, val);
                     else if (!keep) put(i, NA);
                 };
+                if constexpr (BELOW) {
+                    const double b = micro_below(reqhgts, MC(MC_MEAND), sTg, tzd_row[li], a.mat, a.hiy);
+#pragma unroll
+                    for (int i = 0; i < MCF_NOUT; ++i) emit(i, i == 0 ? b : MC(MC_SMAX));      // (sel holds Tz and soilm only)
+                    continue;
+                }
                 double Tz, tleaf, rh;
                 if (reqhgts >= 0.0) {
                     const MicroStep& r = tb[f];
@@ -907,7 +936,9 @@ __global__ __launch_bounds__(64 * kRtWaves, MCF_MICRORING_WAVES) void k_microsno
         for (int e = tid; e < nheld * 384; e += 64 * kRtWaves) {
             const unsigned long long bits = reinterpret_cast<const unsigned long long*>(s_tail)[e];
             if (bits == kTailEmpty) continue;
-            const int slot = e & 15, g = (e >> 4) & 7, rt = e >> 7, rank = rt / 3, t3 = rt - 3 * rank;
+            const int slot = e & 15, g = (e >> 4) & 7, rt = e >> 7, trank = rt / 3, t3 = rt - 3 * trank;
+            // the staged variable's place among the held ones (BELOW: Tz first if held, then soilm)
+            const int rank = !BELOW ? trank : (trank == 0 && (q.held & 1u)) ? 0 : __builtin_popcount(q.held & 7u);
             dayblk[(int64_t)t3 * q.ring.tile_stride + rank * q.vstride + 64 * g + 48 + slot] = __longlong_as_double((long long)bits);
         }
     }
@@ -2652,9 +2683,17 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
         q.m.windspeed = sp->d_micro[6] - back; q.m.precip = sp->d_micro[7] - back; q.m.umu = sp->d_micro[8] - back;
         hipLaunchKernelGGL(k_microsnow_ring<true>, dim3((unsigned)((N + 63) / 64), (unsigned)nd), dim3(256), 0, nullptr, q, (const void*)q.m.dates,
                            q.daymap, q.nosnow);
-    } else if (q.ring.cpb == 21 && !old_shape)
-        hipLaunchKernelGGL(k_microsnow_tiles, dim3((unsigned)((N + kRtCells - 1) / kRtCells)), dim3(64 * kRtWaves), 0, nullptr, q,
-                           (const MicroStep*)q.m.mstep, q.daymap, q.nosnow);
+    } else if (q.ring.cpb == 21 && !old_shape) {
+        // below ground with `out[c(1, 4)]`: the instantiation that reads nothing of the site, the radiation or the canopy
+        // (MCF_MICROSNOW_GENERIC: the generic one, for A/B runs — the values are the same)
+        const bool lean = q.m.reqhgt < 0 && !(q.sel & q.held & ~9u) && !getenv("MCF_MICROSNOW_GENERIC");
+        if (lean)
+            hipLaunchKernelGGL(k_microsnow_tiles<true>, dim3((unsigned)((N + kRtCells - 1) / kRtCells)), dim3(64 * kRtWaves), 0, nullptr, q,
+                               (const MicroStep*)q.m.mstep, q.daymap, q.nosnow);
+        else
+            hipLaunchKernelGGL(k_microsnow_tiles<false>, dim3((unsigned)((N + kRtCells - 1) / kRtCells)), dim3(64 * kRtWaves), 0, nullptr, q,
+                               (const MicroStep*)q.m.mstep, q.daymap, q.nosnow);
+    }
     else
         hipLaunchKernelGGL(k_microsnow_ring<false>, dim3((unsigned)((N + 63) / 64), (unsigned)nd), dim3(256), 0, nullptr, q, q.m.mstep,
                            q.daymap, q.nosnow);

@@ -17,6 +17,13 @@
 //   pass 2   per chunk: restore + re-run the snow chunk unless its series were kept; the solver on the chunk's no-snow days at
 //            their own place in the ring slot; k_microsnow_ring over it; the slot's merged days to the caller's arrays
 //
+// Below ground (the `_below` entries, reqhgt < 0): the block's solver plan is a streamed below-ground plan over the no-snow days
+// (mcf_plan_create_streamed, mcf_plan_below_set_days) — Tbelowgroundv's running means see those days joined end to end, as the
+// reference's solver does on the subset `.runmicrosnow1` hands it.  Between the passes the plan is prepared (complete = 1: one
+// more sweep of the solver over the no-snow days); pass 2 runs each chunk's no-snow days for EVERY cell (a cell's ground
+// temperature under today's snow feeds its means on later days: no tile or cell is left out), the chunk's Tz is made and the
+// 47-step window carried, and only then the snow-day kernel merges its Tz and soilm into the same slot.
+//
 // Row blocks: the raster is cut into contiguous row blocks, block b on devices[b % n_devices], one host thread per device
 // (mcf_rowblocks.hpp's worker pool): per chunk the blocks' snow surfaces meet in one whole-raster host array, the two raster-wide
 // means and the per-step extremes of totalSWE are combined in block order.  One block = the single-device sequence, bit for bit.
@@ -215,6 +222,7 @@ struct mcf_snowrun : SnowBlocks {
     std::vector<int32_t> snowday, nosnowday;   // [ndays]
     bool pass1_done = false;
     bool af = false;                           // array weather: `.snowmodel2` + `.runmicrosnow2` (mcf_runmicrosnow2)
+    bool below = false;                        // the `_below` entries: reqhgt < 0, a streamed solver plan over the no-snow days
     int64_t keep_reserve = (int64_t)8 << 30;
     // A run is one simulated period on fresh plans: the device memory a kept chunk needs would have to be ALLOCATED for it (5 GB per
     // chunk of a 1024 x 1024 raster: 0.1 s, measured 3 s of a 6 s call) where re-running the chunk in pass 2 takes 3.5 ms — chunks are
@@ -239,7 +247,7 @@ void snowdays_of(const double* mx, const double* mn, int nd, int32_t* snow, int3
     }
 }
 
-int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu) {
+int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool below) {
     if (!in || !opt || !in->grid || !in->snow) return mcf::api_fail(MCF_ERR_ARG, "null snow-run argument");
     const mcf_grid_inputs& g = *in->grid;
     const mcf_snow_inputs& sb = in->snow->base;
@@ -261,9 +269,14 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
     // single-layer — either way.
     if (g.veg_layers > 1 && (!g.lyr_st || !g.lyr_ed))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: layered vegetation needs lyr_st / lyr_ed (whole-series steps)");
-    if (opt->reqhgt < 0)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: reqhgt < 0 needs the whole series at once (Tbelowgroundv); use mcf_runmicro1 + "
-                                          "mcf_gridmicrosnow1 on host arrays");
+    if (opt->reqhgt < 0 && !below)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: reqhgt < 0 takes the below-ground entries (mcf_runmicrosnow1_below, "
+                                          "mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below), which stream Tbelowgroundv over the "
+                                          "no-snow days");
+    if (below && !(opt->reqhgt < 0))
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1_below: the below-ground entries need reqhgt < 0 (reqhgt >= 0: mcf_runmicrosnow1)");
+    if (below && g.array_forcing)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1_below: array weather below ground is not supported (data.frame weather only)");
     if (g.rows <= 0 || g.cols <= 0 || g.tsteps < 24) return mcf::api_fail(MCF_ERR_ARG, "bad dimensions");
     if (sb.rows != g.rows || sb.cols != g.cols || sb.tsteps != g.tsteps)
         return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: the solver's and the snow model's inputs differ in shape");
@@ -279,12 +292,13 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
 
 }  // namespace
 
-extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_snowrun** out) {
+static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool below, mcf_snowrun** out) {
     try {
         if (!out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
-        int rc = check_create(in, opt, mu);
+        int rc = check_create(in, opt, mu, below);
         if (rc) return rc;
         mcf_snowrun* h = new mcf_snowrun();
+        h->below = below;
         struct Guard { mcf_snowrun* p; ~Guard() { delete p; } } guard{h};
         if ((rc = mcf::device_list(mu, opt->device, &h->devs))) return rc;
         h->grid = *in->grid; h->opt = *opt; h->snow = *in->snow;
@@ -311,7 +325,8 @@ extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options*
                     k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
                     mcf_options o = h->opt;
                     o.device = k.device;
-                    rc2 = mcf_plan_create(&k.gsub, &o, h->chunk_days, 2, &k.plan);
+                    rc2 = below ? mcf_plan_create_streamed(&k.gsub, &o, h->chunk_days, 2, &k.plan)
+                                : mcf_plan_create(&k.gsub, &o, h->chunk_days, 2, &k.plan);
                     if (rc2) { w.fail(rc2); break; }
                     if (h->nb > 1 && (rc2 = mcf_plan_twi_partial(k.plan, &k.twi_s, &k.twi_n))) { w.fail(rc2); break; }
                     k.kept.assign((size_t)h->nchunks, 0);
@@ -335,6 +350,13 @@ extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options*
     } catch (const std::exception& e) {
         return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_create: ") + e.what());
     }
+}
+
+extern "C" int mcf_snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_snowrun** out) {
+    return snowrun_create(in, opt, mu, false, out);
+}
+extern "C" int mcf_snowrun_create_below(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_snowrun** out) {
+    return snowrun_create(in, opt, mu, true, out);
 }
 
 extern "C" void mcf_snowrun_destroy(mcf_snowrun* h) { delete h; }
@@ -465,6 +487,9 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
             static const int32_t ground[MCF_NOUT] = {1, 0, 0, 1, 0, 1, 1, 1, 1, 1};
             memcpy(outm, ground, sizeof outm);
         }
+        if (h->below)       // `out[c(1, 4)]`: Tz and soilm only
+            for (int v = 0; v < MCF_NOUT; ++v) outm[v] = outm[v] && (v == MCF_OUT_TZ || v == MCF_OUT_SOILM);
+        const std::vector<int32_t> below_days(ndays_.begin(), ndays_.end());
         // ---- the snow-day subset of the whole-series inputs (subsetpointmodel(micropoint, days = snowdays), R/internal.R:3599)
         const int64_t TS = (int64_t)sdays.size() * 24;
         std::vector<int32_t> yr, mo, dy;
@@ -539,8 +564,12 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
                         }
                         rc2 = mcf_snowplan_micro_setup(k.sp, &bs, sub_of_day.data(), (int32_t)sub_of_day.size(), h->opt.reqhgt, mat, outm, 0);
                     }
+                    // below ground: the series Tbelowgroundv sees is the no-snow days joined ...
+                    if (!rc2 && h->below && !ndays_.empty()) rc2 = mcf_plan_below_set_days(k.plan, below_days.data(), (int32_t)below_days.size());
                     if (!rc2 && !ndays_.empty())         // (array weather: per cell, cpp:2467-2471, over the no-snow days)
                         rc2 = h->af ? mcf_plan_set_mxtc_days(k.plan, &k.gsub, h->nosnowday.data(), ndays) : mcf_plan_set_mxtc(k.plan, mxtc);
+                    // ... and its per-cell state comes from a pass over them (complete = 1: the solver's first sweep)
+                    if (!rc2 && h->below && !ndays_.empty()) rc2 = mcf_plan_below_prepare(k.plan, nullptr);
                     if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, 31u);         // (pass 2's re-runs feed the snow microclimate)
                     if (rc2) { w.fail(rc2); break; }
                 }
@@ -569,6 +598,24 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
             std::vector<uint8_t> skip;
             auto solver_days = [&](Block& k, int slot, int ch, int d0, int nd, bool has_snow) -> int {
                 int q = 0;
+                if (h->below) {
+                    // the chunk's no-snow days in one call, each at its own place in the slot, EVERY cell: a cell's ground temperature
+                    // under today's snow feeds its running means on later days, so nothing is left out (and a chunk without a
+                    // no-snow day does not touch the plan's carried window)
+                    int n_no = 0, n_both = 0;
+                    for (int d = 0; d < nd; ++d) {
+                        n_no += h->nosnowday[(size_t)(d0 + d)] != 0;
+                        n_both += h->nosnowday[(size_t)(d0 + d)] && h->snowday[(size_t)(d0 + d)];
+                    }
+                    if (!n_no) return MCF_OK;
+                    if (has_snow && n_both) {
+                        mcf_ring_layout lay;
+                        const int rc3 = mcf_plan_ring_layout(k.plan, &lay);
+                        if (rc3) return rc3;
+                        h->st_tile_days += (lay.cells + lay.cells_per_tile - 1) / lay.cells_per_tile * n_both;
+                    }
+                    return mcf_plan_run_days_at(k.plan, d0, nd, slot, 0);
+                }
                 if (h->af) {      // array weather: the chunk's forcing into the slot once (all its days: the runs address them by day)
                     bool any = false;
                     for (int d = 0; d < nd; ++d) any |= h->nosnowday[(size_t)(d0 + d)] != 0;
@@ -665,9 +712,9 @@ extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, d
 }
 
 static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out,
-                              const mcf_snowdriver_out* smod) {
+                              const mcf_snowdriver_out* smod, bool below = false) {
     mcf_snowrun* h = nullptr;
-    int rc = mcf_snowrun_create(in, opt, mu, &h);
+    int rc = snowrun_create(in, opt, mu, below, &h);
     if (rc) return rc;
     struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
     if ((rc = mcf_snowrun_pass1(h, smod, nullptr, nullptr))) return rc;
@@ -686,6 +733,16 @@ extern "C" int mcf_runmicrosnow1_multi(const mcf_microsnow_in* in, const mcf_opt
                                        const mcf_snowdriver_out* smod) {
     if (!multi) return api_fail(MCF_ERR_ARG, "null argument");
     return runmicrosnow1_impl(in, opt, multi, out, smod);
+}
+
+// reqhgt < 0: the same run with a streamed below-ground solver plan over the no-snow days (data.frame weather)
+extern "C" int mcf_runmicrosnow1_below(const mcf_microsnow_in* in, const mcf_options* opt, mcf_outputs* out, const mcf_snowdriver_out* smod) {
+    return runmicrosnow1_impl(in, opt, nullptr, out, smod, true);
+}
+extern "C" int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* multi, mcf_outputs* out,
+                                             const mcf_snowdriver_out* smod) {
+    if (!multi) return api_fail(MCF_ERR_ARG, "null argument");
+    return runmicrosnow1_impl(in, opt, multi, out, smod, true);
 }
 
 // ---- the snow model alone: `.snowmodel1` / `.snowmodel2`'s chunk loop (mcf_snowmodel1 / 2: one plan on `device`, mu = NULL)

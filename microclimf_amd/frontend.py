@@ -523,7 +523,7 @@ def sortl(vegp, sdep):
 
 def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, *,
                  snowenv: str = "Taiga", method: str = "fast", snowinitd=0.0, snowinita=0.0, zref: float = 2.0,
-                 windhgt: float | None = None, stfact: float = 0.01, device: int = 0) -> dict:
+                 windhgt: float | None = None, stfact: float = 0.01, device: int = 0, inputs_only: bool = False) -> dict:
     """`runsnowmodel(weather, micropoint, vegp, soilc, dtm, ...)` for data.frame weather (R/Cppwrappers.R:717-735);
     `weather` is always the complete hourly series.  A complete micropoint runs `.snowmodel1` (R/internal.R:2498-2619)
     at the point model's reference height: weather height adjustment, the snow point model (host C++), `.sortl`, the
@@ -531,7 +531,9 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
     hand-over).  A subset micropoint runs, at `zref` / `windhgt`, either that and its subset (`method = "slow"`) or
     `.snowmodelq1` (:2627-2776, `method = "fast"`, the reference's default): the point model over every hour, the grid
     model on the selected days only, the pack carried between them by the point model's balance.
-    Returns Tc, Tg, groundsnowdepth, totalSWE, snowden, umu."""
+    Returns Tc, Tg, groundsnowdepth, totalSWE, snowden, umu.
+    `inputs_only` (complete micropoint): everything up to the chunk loop, not the loop — the `snow` mapping of
+    snow.SnowRun / snow.runmicrosnow1 plus `umu`, what `runmicro_snow(..., one_call=True)` takes as `snow_inputs`."""
     from . import snow as S
     if method not in ("fast", "slow"):
         raise ValueError('method is "fast" or "slow"')
@@ -579,6 +581,11 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
         out["umu"] = pmod["umu"][ai]
         return out
     other = {"zref": zref, "lat": lat, "lon": long, "isnowdc": sdep, "isnowac": sage, "isnowdg": sdep * 0.5, "isnowag": sage}
+    if inputs_only:
+        if subset:
+            raise ValueError("inputs_only: the one-call snow run takes a complete micropoint")
+        return {"obstime": hour_int, "climdata": clim, "pointm": pointm, "vegp": vg, "other": other, "snowenv": snowenv, "dtm": z,
+                "res": xres, "tfact": stfact, "umu": pmod["umu"]}
     out = S.snowmodel1_chunks(hour_int, clim, pointm, vg, other, snowenv, z, xres, stfact, device=device)
     out["umu"] = pmod["umu"]
     if subset:                                                         # method = "slow": the full model, then its subset
@@ -766,14 +773,20 @@ def sortl2(vegp, sdep, reqhgt, pai_a=None):
     return out
 
 
-def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, smod: Mapping, *,
+def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, smod: Mapping | None, *,
                   pai_a=None, tfact: float = 1.5, out: Sequence = (1,) * 10, device: int = 0,
-                  _solve=None, _microsnow=None, _terrain=None) -> dict:
+                  _solve=None, _microsnow=None, _terrain=None, one_call: bool = False, snow_inputs: Mapping | None = None) -> dict:
     """`runmicro(..., snow = TRUE, snowmod = smod)` for data.frame weather = `.runmicrosnow1` (R/internal.R:3581-3659):
     days with no snow anywhere go through the ordinary solver, days with snow through gridmicrosnow1 (which keeps the
     ordinary solver's values on snow-free cell-steps of days that have both), and the two are merged by day.
-    `_solve` / `_microsnow` / `_terrain` let the tests put their checkers behind the same orchestration."""
+    `_solve` / `_microsnow` / `_terrain` let the tests put their checkers behind the same orchestration.
+    `one_call` (default False: the host orchestration below, the comparison leg): the device-resident run instead
+    (snow.SnowRun, include/mcf.h mcf_snowrun_*) for reqhgt >= 0 and, through its below-ground entries, reqhgt < 0 alike — the
+    snow model's chunk loop runs inside it, so it takes `snow_inputs` = runsnowmodel(..., inputs_only=True) in place of `smod`
+    (a complete micropoint)."""
     from . import snow as S
+    if one_call:
+        return _runmicro_snow_one_call(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, pai_a, tfact, out, device, _terrain)
     solve = runmicro if _solve is None else _solve
     microsnow = S.gridmicrosnow1 if _microsnow is None else _microsnow
     veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
@@ -825,6 +838,45 @@ def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapp
     smods = subsetsnowmodel(sm, ai + 1)
     mouts = microsnow(reqhgt, mps["obstime"], w, smods, micro, vg, other, float(micropoint["matemp"]), outm)
     return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
+
+
+def _runmicro_snow_one_call(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, pai_a, tfact, out, device, _terrain):
+    """runmicro_snow's `one_call` route: the staged snow run — pass 1 gives the day classes that `.sortl2` weights the
+    vegetation layers with, pass 2 takes gridmicrosnow1's inputs for the WHOLE series"""
+    from . import snow as S
+    if snow_inputs is None:
+        raise ValueError("one_call: snow_inputs = runsnowmodel(weather, micropoint, vegp, soilc, dtm, inputs_only=True) is needed")
+    if len(micropoint["subs"]) != micropoint["ntme"]:
+        raise ValueError("one_call: the one-call snow run takes a complete micropoint")
+    a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device)
+    a["tfact"] = float(tfact)
+    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    snow = {k: v for k, v in snow_inputs.items() if k != "umu"}
+    # `complete` matters below ground only (Tbelowgroundv): the reference solves the no-snow SUBSET, an incomplete series unless
+    # every day is a no-snow day (prepare_grid_inputs: complete = len(subs) == ntme) — known after pass 1
+    for complete in ((False, True) if reqhgt < 0 else (a["complete"],)):
+        a["complete"] = complete
+        with S.SnowRun(a, snow, device=device, below=reqhgt < 0) as run:
+            sd, nd = run.pass1()
+            if reqhgt < 0 and not complete and nd.all():
+                continue
+            snowdays = np.flatnonzero(sd) + 1
+            if not snowdays.size:
+                return run.pass2(None, float(micropoint["matemp"]))
+            sdept = np.zeros(micropoint["ntme"])
+            sdept[np.asarray(subsetpointmodel(micropoint, days=snowdays)["subs"]) - 1] = 1
+            vg = sortl2(veg, sdept, reqhgt, pai_a)
+            res = dtm["res"]
+            xres = res if np.isscalar(res) else res[0]
+            ter = (terrain.precompute_terrain(z, xres, micropoint["zref"], device=device) if _terrain is None
+                   else _terrain(z, xres, micropoint["zref"]))
+            other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
+                     "lat": float(micropoint["lat"]), "lon": float(micropoint["long"]), "zref": float(micropoint["zref"]),
+                     "Smax": soilinit(soil)["Smax"]}
+            w = dict(micropoint["weather"])
+            w["umu"] = np.asarray(snow_inputs["umu"])
+            return run.pass2({"obstime": micropoint["obstime"], "climdata": w, "vegp": vg, "other": other},
+                             float(micropoint["matemp"]))
 
 
 

@@ -932,9 +932,12 @@ class SnowRun:
     grid   the fifteen arguments of runmicro1Cpp for the WHOLE series (mapping with the names of api.runmicro1Cpp's parameters)
     snow   {"obstime", "climdata", "pointm", "vegp", "other", "snowenv", "dtm", "res", "tfact"[, "chunk_steps"]} as for
            `SnowPlan` / snowmodel1_chunks
-    devices / n_blocks: row blocks over several devices from this one process (None: one block on `device`)."""
+    devices / n_blocks: row blocks over several devices from this one process (None: one block on `device`).
+    below  reqhgt < 0 (include/mcf.h mcf_snowrun_create_below): the solver streams Tbelowgroundv over the no-snow days, the
+           snow-day model gives Tz and soilm; data.frame weather, one period per handle.  False: reqhgt < 0 is refused."""
 
-    def __init__(self, grid: Mapping, snow: Mapping, *, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0):
+    def __init__(self, grid: Mapping, snow: Mapping, *, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0,
+                 below: bool = False):
         self._marshal_only(grid, snow, device, cells_per_block)
         mu = None
         if devices is not None or n_blocks:
@@ -942,7 +945,8 @@ class SnowRun:
             self._devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
             mu.n_devices, mu.devices, mu.n_blocks = int(self._devs.size), self._devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
         self._p = C.c_void_p()
-        _abi.check(self._lib.mcf_snowrun_create(C.byref(self._in), C.byref(self._gm.options), C.byref(mu) if mu is not None else None,
+        create = self._lib.mcf_snowrun_create_below if below else self._lib.mcf_snowrun_create
+        _abi.check(create(C.byref(self._in), C.byref(self._gm.options), C.byref(mu) if mu is not None else None,
                                                 C.byref(self._p)))
         self.days = int(self._lib.mcf_snowrun_days(self._p))
 
@@ -1036,9 +1040,9 @@ class SnowRun:
 
 
 def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, *, device: int = 0, devices=None, n_blocks: int = 0,
-                  want_smod: bool = False, cells_per_block: int = 0):
+                  want_smod: bool = False, cells_per_block: int = 0, below: bool = False):
     """mcf_runmicrosnow1 / mcf_runmicrosnow1_multi: the whole snow run as ONE library call (arguments as `SnowRun`, `micro` as
-    `SnowRun.pass2`) -> the merged outputs[, smod]"""
+    `SnowRun.pass2`) -> the merged outputs[, smod].  below: reqhgt < 0 through mcf_runmicrosnow1_below / _below_multi."""
     from .marshal import alloc_outputs
     with SnowRun.__new__(SnowRun) as run:
         run._p = None
@@ -1062,9 +1066,10 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
             mu = _abi.Multi()
             devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
             mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-            _abi.check(lib.mcf_runmicrosnow1_multi(C.byref(run._in), C.byref(run._gm.options), C.byref(mu), C.byref(outs), sop))
+            fn = lib.mcf_runmicrosnow1_below_multi if below else lib.mcf_runmicrosnow1_multi
+            _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(mu), C.byref(outs), sop))
         else:
-            fn = lib.mcf_runmicrosnow2 if run.array_weather else lib.mcf_runmicrosnow1
+            fn = lib.mcf_runmicrosnow1_below if below else lib.mcf_runmicrosnow2 if run.array_weather else lib.mcf_runmicrosnow1
             _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(outs), sop))
     return (arrays, smod) if want_smod else arrays
 

@@ -632,6 +632,10 @@ SEXP mcfhip_snowrun_create(SEXP grid, SEXP snow) {
 #undef S
     g_keep = NULL;
     b->in.grid = &b->grid; b->in.snow = &b->snow; b->in.micro = NULL; b->in.mat = 0.0;
+    /* reqhgt < 0 (data.frame weather): the below-ground entry — a streamed solver plan over the no-snow days (include/mcf.h
+     * mcf_snowrun_create_below); array weather below ground is refused there.  NOT EXERCISED: no R here. */
+    int (*create)(const mcf_microsnow_in *, const mcf_options *, const mcf_multi *, mcf_snowrun **) =
+        b->opt.reqhgt < 0 ? mcf_snowrun_create_below : mcf_snowrun_create;
     SEXP dv = GetOption1(install("mcfhip.devices"));
     int rc;
     if (dv != R_NilValue && LENGTH(dv) > 0) {
@@ -641,9 +645,9 @@ SEXP mcfhip_snowrun_create(SEXP grid, SEXP snow) {
         mu.n_devices = LENGTH(dvi);
         mu.devices = INTEGER(dvi);
         mu.n_blocks = nbo == R_NilValue ? 0 : asInteger(nbo);
-        rc = mcf_snowrun_create(&b->in, &b->opt, &mu, &b->run);
+        rc = create(&b->in, &b->opt, &mu, &b->run);
     } else {
-        rc = mcf_snowrun_create(&b->in, &b->opt, NULL, &b->run);
+        rc = create(&b->in, &b->opt, NULL, &b->run);
     }
     if (rc != MCF_OK) raise_last(rc, np);      /* (the finalizer frees the box) */
     SEXP kg = GetOption1(install("mcfhip.keep_gb"));     /* mcfhip_enable(keep_gb = ...): pass 1's chunks stay in HBM for pass 2 */

@@ -135,6 +135,9 @@ mcfhip_enable <- function(glue = "r/mcfhip_glue.so", devices = NULL, blocks = NU
 #                  marshalling (recorded at runmicro1Cpp), the run's first pass -> snow days / no-snow days, gridmicrosnow1's
 #                  inputs through `.prepsnowinputs1` (every day handed over, the true snow-day steps for `.sortl2`), second pass.
 #                  Anything else (arrays from the reference's runsnowmodel, reqhgt < 0) goes to the reference's function.
+#                  (reqhgt < 0: mcfhip_snowrun_create would take the below-ground entry, include/mcf.h mcf_snowrun_create_below,
+#                  but the arguments recorded here are those of the COMPLETE micropoint — complete = TRUE, Tbp = 0,
+#                  R/internal.R:1096 — where the reference solves the no-snow subset as an incomplete series.)
 # NOT run in the build image (no R there): tests/test_r_glue_syntax_cpu.py checks the .Call names and arities only.
 mcfhip_snow_resident <- function() {
   ns <- asNamespace("microclimf")
