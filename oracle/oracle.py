@@ -20,14 +20,49 @@ LIB_PATH = _DIR / "libmcf_oracle.so"
 _lib = None
 
 
+NOISE_VARIANTS = ("fma", "ulp", "ulpfma")                          # further correct fp64 evaluations (oracle/Makefile)
+SLIP_VARIANTS = ("exp32", "log32", "pow32", "sqrt32", "exp46")     # one precision mistake each: CPU tests only
+_variants = {}
+
+
+def variant_path(name: str) -> Path:
+    return _DIR / f"libmcf_oracle_{name}.so"
+
+
 def build(force: bool = False) -> Path:
+    """The default library and, next to it, the perturbed builds of oracle/variants/ (tests/parity_bars.py)."""
     srcs = [_DIR / "oracle_unit.c", _DIR / "mcf_oracle.c", _DIR / "mcf_oracle.h", _DIR / "pointmodel.c",
             _DIR / "pointmodel.h", _DIR / "snow_oracle.c", _DIR / "snow_oracle.h", _DIR / "Makefile", _DIR.parent / "include" / "mcf.h"]
     srcs = [s for s in srcs if s.exists()]
-    if force or not LIB_PATH.exists() or any(s.stat().st_mtime > LIB_PATH.stat().st_mtime for s in srcs):
-        subprocess.run(["make", "-C", str(_DIR), "-B", "libmcf_oracle.so"], check=True,
-                       capture_output=True)
+    vsrcs = srcs + sorted((_DIR / "variants").glob("*.h"))
+
+    def stale(lib, deps):
+        return force or not lib.exists() or any(s.stat().st_mtime > lib.stat().st_mtime for s in deps)
+
+    targets = [LIB_PATH.name] if stale(LIB_PATH, srcs) else []
+    targets += [variant_path(v).name for v in NOISE_VARIANTS + SLIP_VARIANTS if stale(variant_path(v), vsrcs)]
+    if targets:
+        r = subprocess.run(["make", "-C", str(_DIR), "-B", "-j8"] + targets, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("oracle build failed:\n" + r.stdout[-2000:] + r.stderr[-4000:])
     return LIB_PATH
+
+
+def load_variant(name: str) -> C.CDLL:
+    """A perturbed build of the oracle, for the `lib=` of run_grid / run_snowmodel / run_microsnow.  Raises where this
+    host cannot execute it (the fma builds on a CPU without fused multiply-add): asked of the library's own probe, which
+    runs no floating-point code, not found out by an illegal instruction."""
+    if name not in NOISE_VARIANTS + SLIP_VARIANTS:
+        raise ValueError(f"no oracle variant {name!r}")
+    if name not in _variants:
+        build()
+        lib = C.CDLL(str(variant_path(name)))
+        lib.orc_variant_probe.restype = C.c_int
+        lib.orc_variant_probe.argtypes = []
+        if lib.orc_variant_probe() != 1:
+            raise RuntimeError(f"oracle variant {name!r} needs fused multiply-add, which this CPU does not have")
+        _variants[name] = lib
+    return _variants[name]
 
 
 class Solmodel(C.Structure):

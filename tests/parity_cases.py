@@ -210,3 +210,32 @@ def build(name):
     if mut is not None:
         a = mut(a)
     return a, af
+
+
+def draw(i):
+    """seeded random configuration i of tests/test_random_configs_gpu.py: (rows, cols, steps, synthetic.workload kwargs,
+    solver geometry)"""
+    rng = np.random.default_rng(7000 + i)
+    rows, cols = (int(rng.integers(1, 40)), int(rng.integers(1, 40)))
+    if i % 7 == 0:
+        rows = 1
+    if i % 11 == 0:
+        cols = 1
+    days = int(rng.integers(1, 5))
+    tail = int(rng.choice([0, 0, 5, 23]))
+    reqhgt = float(rng.choice([0.02, 0.05, 0.4, 1.0, 1.9, 0.0, -0.03, -0.2]))
+    af = bool(rng.random() < 0.35)
+    out = [bool(b) for b in rng.random(10) < 0.6]
+    if not any(out):
+        out[0] = True
+    kw = dict(reqhgt=reqhgt, start_doy=int(rng.integers(1, 360)), variety=bool(rng.random() < 0.7),
+              cold=float(rng.choice([0.0, 0.0, 12.0])), hgt_range=(0.05, float(rng.choice([0.3, 1.5, 3.0]))),
+              lat=float(rng.choice([-35.0, 5.0, 50.0, 68.0])), lon=float(rng.choice([-5.0, 100.0])),
+              na_frac=float(rng.choice([0.0, 0.02, 0.3])), out=out, array_forcing=af,
+              complete=bool(rng.random() < 0.5) if reqhgt < 0 else True, seed=int(rng.integers(1, 1 << 30)))
+    if kw["hgt_range"][1] > 1.9:
+        kw["zref"] = 3.5                      # the model needs the reference height above the canopy
+    extra = dict(cells_per_block=int(rng.choice([0, 16, 21, 32, 42])), days_per_chunk=int(rng.choice([0, 1, 2])))
+    if reqhgt < 0:
+        extra["days_per_chunk"] = 0          # the below-ground smoother needs the whole series in one slot
+    return rows, cols, days * 24 + tail, kw, extra

@@ -71,7 +71,8 @@ def model_args(sw):
 
 
 def assert_close(got, want, tol, what=""):
-    """NaN pattern identical, finite values within tol * (1 + |x|)."""
+    """NaN pattern identical, finite values within tol * (1 + |x|); `tol` is the variable's bar of tests/parity_bars.py
+    wherever the oracle solves the same inputs, and always spelled out: there is no default."""
     assert got.shape == want.shape, what
     assert np.array_equal(np.isnan(got), np.isnan(want)), f"{what}: NaN pattern differs"
     fin = np.isfinite(want)

@@ -7,6 +7,7 @@ import pytest
 from microclimf_amd import synthetic
 from microclimf_amd.api import Plan, runmicro2Cpp, runmicro2Cpp_coarse
 from oracle import coarse_oracle as CO
+import parity_bars
 from test_parity_gpu import compare
 
 pytestmark = pytest.mark.gpu
@@ -27,8 +28,8 @@ def test_coarse_forcing_matches_expand_then_solve(oracle, rows, cols, cr, cc, re
     a, rp, cp = synthetic.coarse_workload(rows, cols, 72, cr, cc, reqhgt=reqhgt, variety=True, start_doy=170, na_frac=0.03)
     got = runmicro2Cpp_coarse(*[a[k] for k in ARGS], rowpos=rp, colpos=cp)
     b = expanded(a, rp, cp)
-    want = oracle.run_grid(**b, array_forcing=True)
-    compare(got, want)
+    want, bars = parity_bars.grid(oracle, b, True)
+    compare(got, want, bars)
     # and the device's own array-forcing path given the expanded arrays
     full = runmicro2Cpp(*[b[k] for k in ARGS])
     for k in want:
@@ -41,12 +42,13 @@ def test_identity_grid_equals_plain_array_forcing_bitwise_inputs(oracle):
     assert np.array_equal(rp, np.arange(24.0)) and np.array_equal(cp, np.arange(16.0))
     b = expanded(a, rp, cp)
     assert np.array_equal(b["climdata"]["tc"], a["climdata"]["temp"])
-    compare(runmicro2Cpp_coarse(*[a[k] for k in ARGS]), oracle.run_grid(**b, array_forcing=True))
+    want, bars = parity_bars.grid(oracle, b, True)
+    compare(runmicro2Cpp_coarse(*[a[k] for k in ARGS]), want, bars)
 
 
 def test_plan_keeps_the_coarse_series_resident_and_needs_no_uploads(oracle):
     a, rp, cp = synthetic.coarse_workload(40, 30, 120, 3, 3, variety=True, start_doy=200)
-    want = oracle.run_grid(**expanded(a, rp, cp), array_forcing=True)
+    want, bars = parity_bars.grid(oracle, expanded(a, rp, cp), True)
     with Plan(**a, ring_days=2, ring_slots=2, coarse={"rowpos": rp, "colpos": cp}) as p:
         slot = 0
         for d0 in (0, 2, 4):
@@ -56,8 +58,7 @@ def test_plan_keeps_the_coarse_series_resident_and_needs_no_uploads(oracle):
             for k in ("Tz", "relhum", "Rswup"):
                 got = p.fetch(slot, k, 0, nd * 24)
                 w = want[k][:, :, d0 * 24:(d0 + nd) * 24]
-                assert np.array_equal(np.isnan(got), np.isnan(w))
-                assert np.nanmax(np.abs(got - w) / (1 + np.abs(w))) < 1e-6, k
+                compare({k: got}, {k: w}, bars)
             slot ^= 1
 
 
@@ -88,7 +89,8 @@ def test_random_coarse_configurations(oracle, i):
         rp = np.clip(rp * 0.3 + 0.2 * (cr - 1), 0, cr - 1)
         cp = np.clip(cp * 0.5, 0, cc - 1)
     got = runmicro2Cpp_coarse(*[a[k] for k in ARGS], rowpos=rp, colpos=cp, days_per_chunk=int(rng.choice([0, 1])) if reqhgt >= 0 else 0)
-    compare(got, oracle.run_grid(**expanded(a, rp, cp), array_forcing=True))
+    want, bars = parity_bars.grid(oracle, expanded(a, rp, cp), True)
+    compare(got, want, bars)
 
 
 @pytest.mark.parametrize("altcorrect", [1, 2])
@@ -107,7 +109,8 @@ def test_altitude_correction_is_fused_too(oracle, altcorrect, rows, cols, cr, cc
     clim, pm = CO.expand(a["climdata"], a["pointm"], rp, cp, altcorrect, zc, z)
     b = dict(a)
     b.update(climdata=clim, pointm=pm)
-    compare(got, oracle.run_grid(**b, array_forcing=True))
+    want, bars = parity_bars.grid(oracle, b, True)
+    compare(got, want, bars)
     plain = runmicro2Cpp_coarse(*[a[k] for k in ARGS], rowpos=rp, colpos=cp)
     assert np.nanmax(np.abs(got["Tz"] - plain["Tz"])) > 0.3                  # the correction does something
 
@@ -121,7 +124,8 @@ def test_row_positions_that_are_not_monotone_take_the_per_lane_taps(oracle, kind
     a, rp, cp = synthetic.coarse_workload(64, 24, 48, 4, 3, reqhgt=0.05, variety=True, start_doy=170, na_frac=0.02)
     rp = rp[::-1].copy() if kind == "flipped" else np.where(np.arange(64) % 2 == 0, rp, rp[::-1])
     got = runmicro2Cpp_coarse(*[a[k] for k in ARGS], rowpos=rp, colpos=cp)
-    compare(got, oracle.run_grid(**expanded(a, rp, cp), array_forcing=True))
+    want, bars = parity_bars.grid(oracle, expanded(a, rp, cp), True)
+    compare(got, want, bars)
     monkeypatch.setenv("MCF_NO_COARSE_LDS", "1")
     ref = runmicro2Cpp_coarse(*[a[k] for k in ARGS], rowpos=rp, colpos=cp)
     for k in got:

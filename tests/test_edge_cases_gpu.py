@@ -5,6 +5,7 @@ import pytest
 
 from microclimf_amd import McfError, synthetic
 from microclimf_amd.api import Plan, runmicro1Cpp, runmicro2Cpp
+import parity_bars
 from test_parity_gpu import compare
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +16,8 @@ def test_tiny_rasters(oracle, rows, cols):
     """fewer cells than one workgroup tile, single row / single column rasters"""
     a = synthetic.workload(rows, cols, 48, reqhgt=0.05, variety=True, start_doy=170, )
     a["vegp"]["hgt"] = np.where(np.isnan(a["vegp"]["hgt"]), 0.5, a["vegp"]["hgt"])
-    compare(runmicro1Cpp(**a), oracle.run_grid(**a))
+    want, bars = parity_bars.grid(oracle, a)
+    compare(runmicro1Cpp(**a), want, bars)
 
 
 def test_less_than_one_day_is_all_na(oracle):
@@ -42,7 +44,8 @@ def test_all_cells_na(oracle):
     a["vegp"]["hgt"][:] = np.nan
     got = runmicro1Cpp(**a)
     assert all(np.isnan(v).all() for v in got.values())
-    compare(got, oracle.run_grid(**a))
+    want, bars = parity_bars.grid(oracle, a)
+    compare(got, want, bars)
 
 
 def test_bare_ground_only(oracle):
@@ -52,15 +55,16 @@ def test_bare_ground_only(oracle):
         a["vegp"][k][:] = 0.0
     with np.errstate(invalid="ignore"):
         a["vegp"]["leafden"] = a["vegp"]["pai"] / a["vegp"]["hgt"]      # 0/0 = NaN as in the marshaller
-    want = oracle.run_grid(**a)
+    want, bars = parity_bars.grid(oracle, a)
     assert np.isfinite(want["Tz"]).all()
-    compare(runmicro1Cpp(**a), want)
+    compare(runmicro1Cpp(**a), want, bars)
 
 
 def test_nan_wind_shelter_is_one(oracle):
     a = synthetic.workload(8, 6, 48, reqhgt=0.05, start_doy=170)
     a["soilc"]["wsa"][2, 3, :] = np.nan                                   # cpp:1193
-    compare(runmicro1Cpp(**a), oracle.run_grid(**a))
+    want, bars = parity_bars.grid(oracle, a)
+    compare(runmicro1Cpp(**a), want, bars)
 
 
 def test_errors_are_reported_not_crashed():
@@ -99,4 +103,5 @@ def test_array_forcing_plan_needs_uploaded_days():
 def test_output_subsets_skip_unneeded_work(oracle, reqhgt, out):
     a = synthetic.workload(14, 6, 72, reqhgt=reqhgt, variety=True, start_doy=170, out=out)
     a["vegp"]["hgt"][1, 1] = np.nan
-    compare(runmicro1Cpp(**a), oracle.run_grid(**a))
+    want, bars = parity_bars.grid(oracle, a)
+    compare(runmicro1Cpp(**a), want, bars)

@@ -8,6 +8,7 @@ import pytest
 import vignette_fixture as V
 from bundled import load
 from microclimf_amd import frontend as F
+import parity_bars
 from test_parity_gpu import compare
 
 pytestmark = pytest.mark.gpu
@@ -20,8 +21,8 @@ def test_bundled_year_through_runmicro(oracle, tmp_path):
     assert a["vegp"]["pai"].shape == (50, 50, 12) and list(a["dfsel"]["lyr"]) == list(range(1, 13))
     assert a["dfsel"]["st"][0] == 0 and a["dfsel"]["ed"][-1] == 8759 and a["complete"]
     got = F.runmicro(mp, 0.05, vegp, soilc, dtm)
-    want = oracle.run_grid(**a)
-    compare(got, want)
+    want, bars = parity_bars.grid(oracle, a)
+    compare(got, want, bars)
     tz, na = got["Tz"], np.isnan(F.cleanvars(vegp, soilc, dtm["z"])[2])
     assert tz.shape == (50, 50, 8760) and np.array_equal(np.isnan(tz[:, :, 4000]), na)
     # a year on the Lizard peninsula: air 5 cm above the ground between -5 and 65 degC (sunlit, sheltered slopes), warmer than the weather station on summer
@@ -50,7 +51,8 @@ def test_bundled_month_other_heights(oracle, reqhgt, static):
     got = F.runmicro(mp, reqhgt, vegp, soilc, dtm)
     dfsel = a.get("dfsel")
     assert (dfsel is None) == static
-    compare(got, oracle.run_grid(**a))
+    want, bars = parity_bars.grid(oracle, a)
+    compare(got, want, bars)
     assert list(got) == (["Tz", "tleaf", "relhum", "soilm", "windspeed", "Rdirdown", "Rdifdown", "Rlwdown", "Rswup", "Rlwup"]
                          if reqhgt > 0 else ["Tz", "soilm", "Rdirdown", "Rdifdown", "Rlwdown", "Rswup", "Rlwup"]
                          if reqhgt == 0 else ["Tz", "soilm"])
@@ -91,7 +93,8 @@ def test_array_weather_chain_on_the_bundled_site(oracle, layered):
     clim, pm = CO.expand(a["climdata"], a["pointm"], api.coarse_positions(50, cr), api.coarse_positions(50, cc))
     b = dict(a)
     b.update(climdata=clim, pointm=pm)
-    compare(got, oracle.run_grid(**b, array_forcing=True))
+    want, bars = parity_bars.grid(oracle, b, True)
+    compare(got, want, bars)
 
 
 def test_runsnowmodel_on_the_bundled_site_made_colder(oracle):

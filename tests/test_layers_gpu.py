@@ -4,6 +4,7 @@ import pytest
 
 from microclimf_amd import McfError, synthetic
 from microclimf_amd.api import runmicro3Cpp, runmicro4Cpp
+import parity_bars
 from test_parity_gpu import compare, with_na
 
 pytestmark = pytest.mark.gpu
@@ -13,27 +14,27 @@ pytestmark = pytest.mark.gpu
 def test_runmicro3_matches_oracle(oracle, layers, chunk):
     a = with_na(synthetic.workload(19, 7, 24 * 7, reqhgt=0.05, variety=True, start_doy=150))
     a = synthetic.layered(a, layers, cover_days=6)       # last day not covered by any layer
-    want = oracle.run_grid(**a)
+    want, bars = parity_bars.grid(oracle, a)
     got = runmicro3Cpp(a.pop("dfsel"), **a, days_per_chunk=chunk)
     assert np.isnan(got["Tz"][:, :, 144:]).all()
-    compare(got, want)
+    compare(got, want, bars)
 
 
 def test_runmicro3_below_ground(oracle):
     a = with_na(synthetic.workload(17, 5, 24 * 6, reqhgt=-0.1, variety=True, start_doy=120,
                                    out=[1, 0, 0, 1, 0, 0, 0, 0, 0, 0]))
     a = synthetic.layered(a, 3)
-    want = oracle.run_grid(**a)
-    compare(runmicro3Cpp(a.pop("dfsel"), **a), want)
+    want, bars = parity_bars.grid(oracle, a)
+    compare(runmicro3Cpp(a.pop("dfsel"), **a), want, bars)
 
 
 def test_runmicro4_matches_oracle(oracle):
     a = with_na(synthetic.workload(18, 6, 96, reqhgt=0.05, variety=True, start_doy=170, array_forcing=True))
     a = synthetic.layered(a, 2)
-    want = oracle.run_grid(**a, array_forcing=True)
+    want, bars = parity_bars.grid(oracle, a, True)
     dfsel = a.pop("dfsel")
     a["lats"], a["lons"] = a.pop("lat"), a.pop("lon")
-    compare(runmicro4Cpp(dfsel, **a), want)
+    compare(runmicro4Cpp(dfsel, **a), want, bars)
 
 
 def test_too_many_layers_is_the_reference_error():

@@ -1,7 +1,9 @@
 """GPU parity of the snow branch: mcf_gridmodelsnow1/2 and mcf_gridmicrosnow1/2
 through the C ABI against oracle/snow_oracle.c on the same seeded inputs.  Acceptance bar of
-BASELINE.json's north_star: 1e-4 degC / 1e-4 relative; asserted here: TOL * (1 + |x|) with
-TOL = 1e-6 for the snowpack recurrence (errors compound over the series) and for the microclimate."""
+BASELINE.json's north_star: 1e-4 degC / 1e-4 relative; asserted here: bar * (1 + |x|) with the bar of each case and
+variable derived from the oracle's own rounding sensitivity (tests/parity_bars.py; 1e-12 .. 1e-11 here) wherever the oracle
+solves the same inputs, and TOL = 1e-6 for the chunk-loop orchestration, whose hand-over gate is discontinuous in rounding
+(DESIGN section 8)."""
 import ctypes as C
 
 import numpy as np
@@ -9,6 +11,7 @@ import pytest
 
 from microclimf_amd import _abi, synthetic
 from microclimf_amd.snow import gridmicrosnow1, gridmicrosnow2, gridmodelsnow1, gridmodelsnow2, marshal_snow
+import parity_bars
 from snow_cases import MICRO_HEIGHTS, SNOW_CASES, assert_close, build_snow, microsnow_state, model_args
 
 pytestmark = pytest.mark.gpu
@@ -24,11 +27,11 @@ def run_model(sw, af):
 @pytest.mark.parametrize("name", sorted(SNOW_CASES))
 def test_snowmodel_matches_oracle(oracle, name):
     sw, af = build_snow(name)
-    want = oracle.run_snowmodel(**model_args(sw), array_forcing=af)
+    want, bars = parity_bars.snowmodel(oracle, model_args(sw), af, key=("snowmodel", name))
     got = run_model(sw, af)
     assert list(got) == ["Tc", "Tg", "sdepc", "sdepg", "sden", "agec", "ageg", "meltc", "meltg"]   # cpp:4413-4421
     for k in ("Tc", "Tg", "sdepc", "sdepg", "sden", "meltc", "meltg"):
-        assert_close(got[k], want[k], TOL, f"{name}:{k}")
+        assert_close(got[k], want[k], bars[k], f"{name}:{k}")
     for k in ("agec", "ageg"):                  # integer hours: exact
         assert np.array_equal(got[k], want[k], equal_nan=True), k
     na = np.isnan(sw["vegp"]["hgt"])
@@ -68,11 +71,15 @@ def test_snowmodel_chunks_chain_like_the_r_driver(oracle):
             oth["isnowag"] = np.nan_to_num(first["ageg"])
         return first, fn(cut(48, 96, oth))
 
-    g1, g2 = chain(lambda d: run_model(d, False))
-    o1, o2 = chain(lambda d: oracle.run_snowmodel(**d))
-    for k in ("Tc", "Tg", "sdepc", "sdepg", "sden"):
-        assert_close(g1[k], o1[k], TOL, k)
-        assert_close(g2[k], o2[k], TOL, k)
+    def both(pair):
+        return {f"{n}:{k}": v for n, res in zip("12", pair) for k, v in res.items()}
+
+    got = both(chain(lambda d: run_model(d, False)))
+    # the bars are those of the chained pair: each noise variant of the oracle hands its own depths and ages over
+    want, bars, _ = parity_bars.bars_for(oracle, lambda lib: both(chain(lambda d: oracle.run_snowmodel(**d, lib=lib))))
+    for n in "12":
+        for k in ("Tc", "Tg", "sdepc", "sdepg", "sden"):
+            assert_close(got[f"{n}:{k}"], want[f"{n}:{k}"], bars[f"{n}:{k}"], f"{n}:{k}")
 
 
 @pytest.mark.parametrize("reqhgt", MICRO_HEIGHTS)
@@ -84,13 +91,13 @@ def test_microsnow_matches_oracle(oracle, name, reqhgt):
     snowm, micro = microsnow_state(sw, smod)
     out = [1] * 10
     args = (reqhgt, sw["obstime"], sw["climdata"], snowm, micro, sw["vegp"], sw["other"], 3.0, out)
-    want = oracle.run_microsnow(*args, array_forcing=af)
+    want, bars = parity_bars.microsnow(oracle, args, af)
     got = (gridmicrosnow2 if af else gridmicrosnow1)(*args)
     assert list(got) == list(want)
     with np.errstate(invalid="ignore"):
         covered = snowm["totalSWE"] > 0
     for k in want:
-        assert_close(got[k], want[k], TOL, f"{name}:{reqhgt}:{k}")
+        assert_close(got[k], want[k], bars[k], f"{name}:{reqhgt}:{k}")
         assert np.array_equal(got[k][~covered], micro[k][~covered]), k     # snow-free steps untouched, bit for bit
 
 
@@ -100,10 +107,11 @@ def test_microsnow_out_mask(oracle):
     snowm, micro = synthetic.microsnow_inputs(sw, smod)
     out = [1, 0, 1, 0, 0, 1, 0, 0, 0, 1]
     args = (0.05, sw["obstime"], sw["climdata"], snowm, micro, sw["vegp"], sw["other"], 3.0, out)
-    got, want = gridmicrosnow1(*args), oracle.run_microsnow(*args)
+    got = gridmicrosnow1(*args)
+    want, bars = parity_bars.microsnow(oracle, args)
     assert list(got) == ["Tz", "relhum", "Rdirdown", "Rlwup"]
     for k in want:
-        assert_close(got[k], want[k], TOL, k)
+        assert_close(got[k], want[k], bars[k], k)
 
 
 def _driver_case(rows, cols, tsteps, **kw):
