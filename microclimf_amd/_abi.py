@@ -63,6 +63,15 @@ class Multi(C.Structure):
     _fields_ = [("n_devices", C.c_int32), ("devices", c_int32_p), ("n_blocks", C.c_int32)]
 
 
+def multi(devices, n_blocks):
+    """-> (mcf_multi, the int32 array its `devices` points into: keep it for as long as the struct is used) for `devices` (a list
+    of HIP ordinals, [] = all visible) / `n_blocks` row blocks, or None when neither is given: the single-device entry."""
+    if devices is None and not n_blocks:
+        return None
+    devs = (C.c_int32 * (0 if devices is None else len(devices)))(*(() if devices is None else devices))
+    return Multi(len(devs), C.cast(devs, c_int32_p), int(n_blocks)), devs
+
+
 class Options(C.Structure):
     _fields_ = [("reqhgt", C.c_double), ("zref", C.c_double),
                 ("Sminp", C.c_double), ("Smaxp", C.c_double),

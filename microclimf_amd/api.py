@@ -52,24 +52,17 @@ def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt,
                 tfact, complete, mat, out, array_forcing, device, days_per_chunk, cells_per_block, dfsel, coarse,
                 soilc_optional=DTM_DERIVED if dtm is not None else ())
     outs, arrays = alloc_outputs(m)
+    mu = _abi.multi(devices, n_blocks)
     if dtm is not None:
         # missing terrain planes / wetness index derived on the device (include/mcf.h mcf_runmicro_dtm); the entry dispatches on
         # the inputs as mcf_runmicro1 .. 4 do
         sp, _z = dtm_spec(dtm, m.rows, m.cols)
-        mu = None
-        if devices is not None or n_blocks:
-            mu = _abi.Multi()
-            devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-            mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-        _abi.check(lib.mcf_runmicro_dtm(C.byref(m.inputs), C.byref(m.options), C.byref(sp), None if mu is None else C.byref(mu),
+        _abi.check(lib.mcf_runmicro_dtm(C.byref(m.inputs), C.byref(m.options), C.byref(sp), C.byref(mu[0]) if mu else None,
                                         C.byref(outs)))
         return arrays
-    if devices is not None or n_blocks:
+    if mu:
         # one process, several devices (include/mcf.h mcf_runmicro1_multi): row blocks dealt to the listed devices
-        mu = _abi.Multi()
-        devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-        mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-        _abi.check(getattr(lib, fn_name + "_multi")(C.byref(m.inputs), C.byref(m.options), C.byref(mu), C.byref(outs)))
+        _abi.check(getattr(lib, fn_name + "_multi")(C.byref(m.inputs), C.byref(m.options), C.byref(mu[0]), C.byref(outs)))
         return arrays
     _abi.check(getattr(lib, fn_name)(C.byref(m.inputs), C.byref(m.options), C.byref(outs)))
     return arrays
@@ -178,12 +171,10 @@ def _bioclim(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, req
             bo.bio[v] = a.ctypes.data_as(_abi.c_double_p)
         else:
             bo.bio[v] = None
-    if devices is not None or n_blocks:
+    mu = _abi.multi(devices, n_blocks)
+    if mu:
         # one process, several devices (include/mcf.h mcf_runbioclim1_multi): row blocks dealt to the listed devices, same bits
-        mu = _abi.Multi()
-        devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-        mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-        _abi.check(getattr(lib, fn_name + "_multi")(C.byref(m.inputs), C.byref(m.options), C.byref(sel), C.byref(mu), C.byref(bo)))
+        _abi.check(getattr(lib, fn_name + "_multi")(C.byref(m.inputs), C.byref(m.options), C.byref(sel), C.byref(mu[0]), C.byref(bo)))
     else:
         _abi.check(getattr(lib, fn_name)(C.byref(m.inputs), C.byref(m.options), C.byref(sel), C.byref(bo)))
     return res

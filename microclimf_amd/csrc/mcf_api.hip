@@ -21,10 +21,10 @@
 #include "mcf_kernels.h"
 #include "mcf_hydro.h"
 #include "mcf_terrain.h"
-#include "mcf_hostpipe.hpp"
 #include "mcf_ncfile.hpp"
 #include "mcf_nc4file.hpp"
 #include "mcf_rowblocks.hpp"
+#include "mcf_hiphost.hpp"
 
 namespace {
 
@@ -34,17 +34,6 @@ int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            char b_[512];                                                                    \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                     __FILE__, __LINE__);                                                    \
-            return fail(e_ == hipErrorOutOfMemory ? MCF_ERR_NOMEM : MCF_ERR_HIP, b_);        \
-        }                                                                                    \
-    } while (0)
 
 }  // namespace
 
@@ -73,8 +62,7 @@ struct mcf_plan {
     mcf::Globals g{};
     int hiy = 8760;
     double lat = 0, lon = 0;
-    std::vector<void*> allocs;
-    int64_t bytes = 0;
+    mcf::DevOwner dev;          // every device buffer of the plan; dev.bytes is what mcf_plan_bytes reports
     // static inputs
     const double* d_veg[10] = {};
     const double* d_soil[13] = {};
@@ -158,57 +146,41 @@ struct mcf_plan {
     // packed sink staging
     int32_t* d_pack = nullptr;
     int64_t pack_elems = 0;
-    // device -> pageable host copies of large results (mcf_hostpipe.hpp)
-    mcf::HostPipe* pipe = nullptr;
-    hipEvent_t ev_pipe = nullptr;
-    bool pipe_failed = false;
+    // device -> pageable host copies of results (mcf_hiphost.hpp)
+    mcf::ToHost tohost;
 };
 
 namespace {
 
-// lazily sets up the pinned ring + host copy threads of a plan; false: unavailable (callers fall back to hipMemcpy)
-bool ensure_pipe(mcf_plan* p) {
-    if (p->pipe) return true;
-    if (p->pipe_failed) return false;
-    p->pipe = new mcf::HostPipe();
-    if (!p->pipe->init() || hipEventCreateWithFlags(&p->ev_pipe, hipEventDisableTiming) != hipSuccess) {
-        delete p->pipe;
-        p->pipe = nullptr;
-        p->pipe_failed = true;
-        return false;
-    }
-    return true;
-}
-
-int dalloc(mcf_plan* p, void** ptr, int64_t nbytes) {
-    if (nbytes <= 0) nbytes = 8;
-    hipError_t e = hipMalloc(ptr, (size_t)nbytes);
-    if (e != hipSuccess) {
-        char b[256];
-        snprintf(b, sizeof b, "hipMalloc(%lld bytes) failed: %s", (long long)nbytes, hipGetErrorString(e));
-        return fail(MCF_ERR_NOMEM, b);
-    }
-    p->allocs.push_back(*ptr);
-    p->bytes += nbytes;
-    return MCF_OK;
-}
+int dalloc(mcf_plan* p, void** ptr, int64_t nbytes) { return p->dev.alloc(ptr, nbytes); }
 
 // a buffer that grows: the old one is released first.  A buffer that has to grow gets a quarter more than is asked for — the
 // sets of cells of successive calls differ by little, and a release + allocation of a gigabyte costs 50 ms
 int dregrow(mcf_plan* p, void** ptr, int64_t* cap, int64_t nbytes) {
     if (*ptr && *cap >= nbytes) return MCF_OK;
-    if (*ptr) nbytes += nbytes / 4;
     if (*ptr) {
-        for (size_t i = 0; i < p->allocs.size(); ++i)
-            if (p->allocs[i] == *ptr) { p->allocs.erase(p->allocs.begin() + (long)i); break; }
-        (void)hipFree(*ptr);
-        p->bytes -= *cap;
+        nbytes += nbytes / 4;
+        p->dev.release(*ptr);
         *ptr = nullptr;
         *cap = 0;
     }
     const int rc = dalloc(p, ptr, nbytes);
     if (!rc) *cap = std::max<int64_t>(nbytes, 8);
     return rc;
+}
+
+// fn() between two events on the plan's stream when kernel timing is on (mcf_plan_kernel_stats adds the pairs up)
+template <class F>
+int timed(mcf_plan* p, F&& fn) {
+    if (!p->ktiming) { fn(); return MCF_OK; }
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, p->stream));
+    fn();
+    HIP_TRY(hipEventRecord(e1, p->stream));
+    p->kev.emplace_back(e0, e1);
+    return MCF_OK;
 }
 
 // variable `var` (requested) of ring slot `slot` as its consumers address it
@@ -224,6 +196,16 @@ mcf::RingView ring_view(const mcf_plan* p, int slot, int var) {
         v.cpb = 0;
     }
     return v;
+}
+
+// steps [step0, step0 + nsteps) of variable `var` in ring slot `slot`: a slot of the plan, a requested variable (kAnyVar: the
+// caller checks its variables itself), a range inside the slot
+constexpr int kAnyVar = -1;
+int check_slot_range(const mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps) {
+    if (slot < 0 || slot >= p->ring_slots || (var != kAnyVar && (var < 0 || var >= MCF_NOUT))) return fail(MCF_ERR_ARG, "bad slot/var");
+    if (var != kAnyVar && p->var_slot[var] < 0) return fail(MCF_ERR_ARG, "variable was not requested in out[]");
+    if (step0 < 0 || nsteps < 0 || step0 + nsteps > (int64_t)p->ring_days * 24) return fail(MCF_ERR_ARG, "step range out of slot");
+    return MCF_OK;
 }
 
 // host [rows x ncols] with leading dimension p->pitch -> dense device memory (and the other way): plain copies for dense hosts
@@ -338,9 +320,9 @@ int derive_from_dtm(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* 
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t0 = now();
     double t1 = t0, t2 = t0;
+    mcf::DevOwner tmp;
     double* d_dtm = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_dtm, (size_t)NB * 8));
-    struct Free { double* q; ~Free() { (void)hipFree(q); } } free_dtm{d_dtm};
+    if (const int rc = tmp.alloc((void**)&d_dtm, NB * 8)) return rc;
     HIP_TRY(hipMemcpy(d_dtm, dtm->dtm, (size_t)NB * 8, hipMemcpyHostToDevice));
     t1 = t2 = now();
     if (nd.slope || nd.aspect || nd.hor || nd.wsa) {
@@ -547,9 +529,7 @@ void mcf_plan_destroy(mcf_plan* p) {
     if (p->ev_prep) hipEventDestroy(p->ev_prep);
     if (p->ev_cells_done) hipEventDestroy(p->ev_cells_done);
     for (auto& e : p->kev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (void* a : p->allocs) hipFree(a);
-    delete p->pipe;
-    if (p->ev_pipe) hipEventDestroy(p->ev_pipe);
+    p->dev.release_all();
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
@@ -773,15 +753,13 @@ static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_
             cwd[(size_t)k] = d;
         }
     }
-    std::vector<void*> temps;   // freed after setup
+    mcf::DevOwner temps;   // freed after setup
     auto up_tmp = [&](const void* host, int64_t nbytes, void** dev) -> int {
         if (nbytes <= 0) nbytes = 8;
-        HIP_TRY(hipMalloc(dev, (size_t)nbytes));
-        temps.push_back(*dev);
+        if (const int rca = temps.alloc(dev, nbytes)) return rca;
         if (host) HIP_TRY(hipMemcpyAsync(*dev, host, (size_t)nbytes, hipMemcpyHostToDevice, p->stream));
         return MCF_OK;
     };
-    struct TmpGuard { std::vector<void*>& t; ~TmpGuard() { for (void* q : t) hipFree(q); } } tguard{temps};
     void *dy = nullptr, *dm = nullptr, *dd = nullptr, *dh = nullptr, *dw = nullptr;
     if (T > 0) {
         if ((rc = up_tmp(in->obstime.year, T * 4, &dy))) return rc;
@@ -1076,15 +1054,19 @@ namespace {
 // the launch description of days [day0, day0 + ndays) into `slot` from its day `slot_day0` on — everything but the tile list —,
 // and which instantiation the days allow: `fast` (the min / max clamps: every day regular), `soil_daily` (the per cell-day soil
 // state shared through LDS)
-int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0, mcf::SolveArgs& a, bool& fast, bool& soil_daily) {
+int check_days(const mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0) {
     if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
     if (day0 < 0 || ndays < 1 || day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
     if ((!p->bg || p->bg_stream) && (slot_day0 < 0 || slot_day0 + ndays > p->ring_days))
         return fail(MCF_ERR_ARG, "more days than the ring slot holds");
     if (slot_day0 != 0 && p->bg && !p->bg_stream) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = ensure_cells(p);
+    return MCF_OK;
+}
+int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t slot_day0, mcf::SolveArgs& a, bool& fast, bool& soil_daily) {
+    int rc = check_days(p, day0, ndays, slot, slot_day0);
     if (rc) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    if ((rc = ensure_cells(p))) return rc;
     a = mcf::SolveArgs{};
     a.N = p->N;
     a.cellc = p->d_cellc; a.ntiles_total = p->ntiles; a.tt = p->d_tt;
@@ -1141,6 +1123,40 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
         if (!p->day_soil_daily[(size_t)d]) soil_daily = false;
     if (p->coarse) soil_daily = p->coarse_lds;      // (coarse array forcing: the same launch flag selects the LDS-staged taps)
     return MCF_OK;
+}
+
+// The tiles of a launch by class.  A null list with a count: tiles 0 .. n - 1; no list and no count at all: every tile of the
+// raster.
+struct SolveTiles {
+    const int32_t* fast_list = nullptr;
+    int64_t n_fast = 0;
+    const int32_t* slow_list = nullptr;
+    int64_t n_slow = 0;
+    bool whole_raster() const { return !fast_list && !slow_list && n_fast == 0 && n_slow == 0; }
+};
+
+// The k_solve launches of `t` on the plan's stream: with `fast`, the fix-up count cleared, then the fast part through the
+// min / max clamps and the slow part through the reference form; without it (an irregular day, or no fast class at all) one
+// reference-form launch of the first part, or of the whole raster.  An empty part launches nothing.
+void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, const SolveTiles& t) {
+    if (!fast) {
+        if (!t.whole_raster() && t.n_fast == 0) return;
+        a.tile_list = t.fast_list; a.ntiles_launch = t.n_fast;
+        mcf::launch_solve(a, p->cpb, p->af, p->bg, false, soil_daily, p->stream);
+        ++p->slow_launches;
+        return;
+    }
+    (void)hipMemsetAsync(p->d_fix_count, 0, 4, p->stream);
+    if (t.n_fast > 0) {
+        a.tile_list = t.fast_list; a.ntiles_launch = t.n_fast;
+        mcf::launch_solve(a, p->cpb, p->af, false, true, soil_daily, p->stream);
+        ++p->fast_launches;
+    }
+    if (t.n_slow > 0) {
+        a.tile_list = t.slow_list; a.ntiles_launch = t.n_slow;
+        mcf::launch_solve(a, p->cpb, p->af, false, false, soil_daily, p->stream);
+        ++p->slow_launches;
+    }
 }
 
 // ---- below ground streamed through day chunks (DESIGN.md "Below ground in day chunks") ----------------------------------
@@ -1209,9 +1225,10 @@ int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int3
     if (slot_day0 != 0) return fail(MCF_ERR_ARG, "a day offset inside the slot needs reqhgt >= 0");
     if (tz && !p->below_ready)
         return fail(MCF_ERR_STATE, "streamed below-ground plan: call mcf_plan_below_prepare before running days");
-    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
-    if (day0 < 0 || ndays < 1 || day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
-    if (ndays > p->ring_days) return fail(MCF_ERR_ARG, "more days than the ring slot holds");
+    // (the whole range, once, before the day-order check: solve_args sees the range's runs of days only, and none of them when
+    // the range holds no day of a subset)
+    int rc = check_days(p, day0, ndays, slot, 0);
+    if (rc) return rc;
     const bool sub = !p->below_days.empty();
     BelowRange r;
     below_range(p, day0, ndays, r);
@@ -1221,13 +1238,12 @@ int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int3
                                    std::to_string(r.pos0) + ")");
     if (r.npos == 0) return MCF_OK;
     std::vector<mcf::SolveArgs> as;
-    int rc = below_solve_args(p, r, day0, slot, as);
-    if (rc) return rc;
+    if ((rc = below_solve_args(p, r, day0, slot, as))) return rc;
     const bool tail = !sub && day0 + ndays == p->ndays && p->tsteps > (int64_t)p->ndays * 24;
     if (tz && tail && ndays + 1 > p->ring_days)
         return fail(MCF_ERR_ARG, "streamed below-ground plan: the chunk that ends on the last whole day needs one day more in its "
                                  "slot, for the steps behind that day");
-    auto launch = [&]() {
+    rc = timed(p, [&] {
         for (const mcf::SolveArgs& a : as) {
             mcf::launch_solve_bg_tiled(a, p->cpb, p->af, p->stream);
             ++p->slow_launches;
@@ -1240,18 +1256,8 @@ int run_below_chunk(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int3
             b.Tgp = p->d_Tgp_slots + off; b.Tbp = p->d_Tbp_slots + off;
         }
         mcf::launch_below_chunk(b, p->stream);
-    };
-    if (p->ktiming) {
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, p->stream));
-        launch();
-        HIP_TRY(hipEventRecord(e1, p->stream));
-        p->kev.emplace_back(e0, e1);
-    } else {
-        launch();
-    }
+    });
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     p->below_next = r.pos0 + r.npos;
     return MCF_OK;
@@ -1415,49 +1421,11 @@ int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t s
         if (!l.empty()) HIP_TRY(hipMemcpyAsync(p->d_tiles_sub, l.data(), l.size() * 4, hipMemcpyHostToDevice, p->stream));
         sub_fast = p->d_tiles_sub; sub_slow = p->d_tiles_sub + n_sub_fast;
     }
-    auto launch = [&]() {
-        if (skip_tile) {
-            if (fast) (void)hipMemsetAsync(p->d_fix_count, 0, 4, p->stream);
-            if (n_sub_fast) {
-                a.tile_list = sub_fast; a.ntiles_launch = n_sub_fast;
-                if (fast) { mcf::launch_solve(a, p->cpb, p->af, false, true, soil_daily, p->stream); ++p->fast_launches; }
-                else { mcf::launch_solve(a, p->cpb, p->af, p->bg, false, soil_daily, p->stream); ++p->slow_launches; }
-            }
-            if (n_sub_slow) {
-                a.tile_list = sub_slow; a.ntiles_launch = n_sub_slow;
-                mcf::launch_solve(a, p->cpb, p->af, false, false, soil_daily, p->stream);
-                ++p->slow_launches;
-            }
-        } else if (fast) {
-            (void)hipMemsetAsync(p->d_fix_count, 0, 4, p->stream);
-            a.tile_list = p->n_slow > 0 ? p->d_tiles_fast : nullptr;
-            a.ntiles_launch = p->n_fast;
-            mcf::launch_solve(a, p->cpb, p->af, false, true, soil_daily, p->stream);
-            ++p->fast_launches;
-            if (p->n_slow > 0) {
-                ++p->slow_launches;
-                a.tile_list = p->d_tiles_slow;
-                a.ntiles_launch = p->n_slow;
-                mcf::launch_solve(a, p->cpb, p->af, false, false, soil_daily, p->stream);
-            }
-        } else {
-            a.tile_list = nullptr;
-            a.ntiles_launch = 0;
-            ++p->slow_launches;
-            mcf::launch_solve(a, p->cpb, p->af, p->bg, false, soil_daily, p->stream);
-        }
-    };
-    if (p->ktiming) {
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, p->stream));
-        launch();
-        HIP_TRY(hipEventRecord(e1, p->stream));
-        p->kev.emplace_back(e0, e1);
-    } else {
-        launch();
-    }
+    SolveTiles tiles;      // (an irregular day: the whole raster, or the mask's one list, in the reference form)
+    if (skip_tile) tiles = SolveTiles{sub_fast, n_sub_fast, sub_slow, n_sub_slow};
+    // with no irregular tile the plan's fast launch needs no list (identity)
+    else if (fast) tiles = SolveTiles{p->n_slow > 0 ? p->d_tiles_fast : nullptr, p->n_fast, p->d_tiles_slow, p->n_slow};
+    if ((rc = timed(p, [&] { dispatch_solve(p, a, fast, soil_daily, tiles); }))) return rc;
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -1551,23 +1519,9 @@ int mcf_plan_run_days_cells(mcf_plan* p, int32_t day0, int32_t ndays, int32_t sl
     for (int d = 0; d < ndays; d += pass_days) {
         const int nd = std::min(pass_days, ndays - d);
         a.day0 = day0 + d; a.ndays = nd;
-        if (fast) {
-            (void)hipMemsetAsync(p->d_fix_count, 0, 4, p->stream);
-            if (nt_fast > 0) {
-                a.tile_list = nullptr; a.ntiles_launch = nt_fast;
-                mcf::launch_solve(a, cpb, false, false, true, soil_daily, p->stream);
-                ++p->fast_launches;
-            }
-            if (nt_slow > 0) {
-                a.tile_list = p->d_cells_slow; a.ntiles_launch = nt_slow;
-                mcf::launch_solve(a, cpb, false, false, false, soil_daily, p->stream);
-                ++p->slow_launches;
-            }
-        } else {
-            a.tile_list = nullptr; a.ntiles_launch = nt_sub;
-            mcf::launch_solve(a, cpb, false, false, false, soil_daily, p->stream);
-            ++p->slow_launches;
-        }
+        // (vector forcing above ground, as checked on entry: the plan's af and bg, which dispatch_solve passes on, are false;
+        // these launches are not timed for mcf_plan_kernel_stats)
+        dispatch_solve(p, a, fast, soil_daily, fast ? SolveTiles{nullptr, nt_fast, p->d_cells_slow, nt_slow} : SolveTiles{nullptr, nt_sub, nullptr, 0});
         HIP_TRY(hipGetLastError());
         mcf::launch_scatter_cells(p->d_celllist, nt_sub, p->d_subring, a.out_tile_stride, slot_base + (int64_t)d * p->ring_day_stride,
                                   p->ring_tile_stride, day_doubles, cpb, nd, p->stream);
@@ -1639,35 +1593,15 @@ int mcf_plan_fetch_pitched(mcf_plan* p, int32_t slot, int32_t var, int64_t step0
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
     if (row_pitch == 0) row_pitch = p->rows;
     if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
-    if (slot < 0 || slot >= p->ring_slots || var < 0 || var >= MCF_NOUT) return fail(MCF_ERR_ARG, "bad slot/var");
-    if (p->var_slot[var] < 0) return fail(MCF_ERR_ARG, "variable was not requested in out[]");
-    const int64_t cap_steps = (int64_t)p->ring_days * 24;
-    if (step0 < 0 || nsteps < 0 || step0 + nsteps > cap_steps) return fail(MCF_ERR_ARG, "step range out of slot");
+    if (const int rc = check_slot_range(p, slot, var, step0, nsteps)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     if (nsteps == 0) return MCF_OK;
     const mcf::RingView view = ring_view(p, slot, var);
-    // large results: pinned ring + host copy threads instead of hipMemcpy's single-threaded staging
-    static const bool no_pipe = getenv("MCF_NO_HOSTPIPE") != nullptr;
+    // (a block of a taller raster goes column by column into its place)
     auto to_host = [&](double* dst, const double* src, size_t bytes) -> int {
-        if (row_pitch != p->rows) {      // a block of a taller raster: column by column into its place
-            const size_t width = (size_t)p->rows * 8, height = bytes / width;
-            if (bytes >= ((size_t)64 << 20) && width <= mcf::HostPipe::kPiece && !no_pipe && ensure_pipe(p)) {
-                // contiguous DMA into the pinned ring, the scatter by the host copy threads (mcf_hostpipe.hpp)
-                HIP_TRY(hipEventRecord(p->ev_pipe, p->stream));
-                HIP_TRY(p->pipe->copy_pitched(dst, (size_t)row_pitch * 8, src, width, height, p->ev_pipe));
-                return MCF_OK;
-            }
-            HIP_TRY(hipMemcpy2DAsync(dst, (size_t)row_pitch * 8, src, width, width, height, hipMemcpyDeviceToHost, p->stream));
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            return MCF_OK;
-        }
-        if (bytes >= ((size_t)64 << 20) && !no_pipe && ensure_pipe(p)) {
-            HIP_TRY(hipEventRecord(p->ev_pipe, p->stream));
-            HIP_TRY(p->pipe->copy(dst, src, bytes, p->ev_pipe));
-            return MCF_OK;
-        }
-        HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
+        const size_t width = (size_t)p->rows * 8;
+        if (row_pitch != p->rows) HIP_TRY(p->tohost.pitched(dst, (size_t)row_pitch * 8, src, width, bytes / width, p->stream));
+        else HIP_TRY(p->tohost.dense(dst, src, bytes, p->stream));
         return MCF_OK;
     };
     if (!p->tiled) return to_host(host_dst, view.base + p->N * step0, (size_t)(p->N * nsteps) * 8);
@@ -1693,40 +1627,30 @@ int mcf_plan_fetch_pitched(mcf_plan* p, int32_t slot, int32_t var, int64_t step0
 int mcf_plan_fetch_cells(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps, const int64_t* cells,
                          int64_t ncells, double* host_dst) {
     if (!p || !host_dst || !cells) return fail(MCF_ERR_ARG, "null argument");
-    if (slot < 0 || slot >= p->ring_slots || var < 0 || var >= MCF_NOUT) return fail(MCF_ERR_ARG, "bad slot/var");
-    if (p->var_slot[var] < 0) return fail(MCF_ERR_ARG, "variable was not requested in out[]");
-    const int64_t cap_steps = (int64_t)p->ring_days * 24;
-    if (step0 < 0 || nsteps < 0 || step0 + nsteps > cap_steps) return fail(MCF_ERR_ARG, "step range out of slot");
+    if (const int rc = check_slot_range(p, slot, var, step0, nsteps)) return rc;
     if (ncells < 0) return fail(MCF_ERR_ARG, "negative cell count");
     for (int64_t i = 0; i < ncells; ++i)
         if (cells[i] < 0 || cells[i] >= p->N) return fail(MCF_ERR_ARG, "cell index outside the raster");
     if (ncells == 0 || nsteps == 0) return MCF_OK;
     HIP_TRY(hipSetDevice(p->device));
+    mcf::DevOwner tmp;
     int64_t* d_cells = nullptr;
     double* d_dst = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_cells, (size_t)ncells * 8));
-    hipError_t e = hipMalloc((void**)&d_dst, (size_t)(ncells * nsteps) * 8);
-    if (e != hipSuccess) { (void)hipFree(d_cells); return fail(MCF_ERR_NOMEM, "hipMalloc failed for the gather buffer"); }
-    e = hipMemcpyAsync(d_cells, cells, (size_t)ncells * 8, hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) {
-        mcf::launch_gather_cells(ring_view(p, slot, var), step0, nsteps, d_cells, ncells, d_dst, p->stream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(host_dst, d_dst, (size_t)(ncells * nsteps) * 8, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    (void)hipFree(d_cells);
-    (void)hipFree(d_dst);
-    if (e != hipSuccess) return fail(MCF_ERR_HIP, std::string("mcf_plan_fetch_cells: ") + hipGetErrorString(e));
+    int rc;
+    if ((rc = tmp.alloc((void**)&d_cells, ncells * 8))) return rc;
+    if ((rc = tmp.alloc((void**)&d_dst, ncells * nsteps * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(d_cells, cells, (size_t)ncells * 8, hipMemcpyHostToDevice, p->stream));
+    mcf::launch_gather_cells(ring_view(p, slot, var), step0, nsteps, d_cells, ncells, d_dst, p->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(host_dst, d_dst, (size_t)(ncells * nsteps) * 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
     return MCF_OK;
 }
 
 int mcf_plan_fetch_packed(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps, double scale,
                           int32_t* host_dst, float* kernel_ms) {
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
-    if (slot < 0 || slot >= p->ring_slots || var < 0 || var >= MCF_NOUT) return fail(MCF_ERR_ARG, "bad slot/var");
-    if (p->var_slot[var] < 0) return fail(MCF_ERR_ARG, "variable was not requested in out[]");
-    const int64_t cap_steps = (int64_t)p->ring_days * 24;
-    if (step0 < 0 || nsteps < 0 || step0 + nsteps > cap_steps) return fail(MCF_ERR_ARG, "step range out of slot");
+    if (const int rc = check_slot_range(p, slot, var, step0, nsteps)) return rc;
     if (nsteps > 65535) return fail(MCF_ERR_ARG, "at most 65535 steps per packed fetch");
     HIP_TRY(hipSetDevice(p->device));
     if (p->pack_elems < p->N * nsteps) {
@@ -1823,9 +1747,7 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
                       float* kernel_ms) {
     if (!nc || !p) return fail(MCF_ERR_ARG, "null argument");
     if (nc->f->rows != p->rows || nc->f->cols != p->cols) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: the file's grid is not the plan's");
-    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "bad slot");
-    const int64_t cap_steps = (int64_t)p->ring_days * 24;
-    if (slot_step0 < 0 || nsteps < 0 || slot_step0 + nsteps > cap_steps) return fail(MCF_ERR_ARG, "step range out of slot");
+    if (const int rc = check_slot_range(p, slot, kAnyVar, slot_step0, nsteps)) return rc;
     if (file_step0 < 0 || file_step0 + nsteps > nc->f->nsteps) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: step range outside the file");
     mcf::PackNcArgs a{};
     a.nv = nc->f->nvars; a.missval = mcf::NcFile::kMissval; a.rows = p->rows; a.cols = p->cols;
@@ -1850,7 +1772,6 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
         p->pack_elems = piece * (rb / 4);
     }
     a.dst = p->d_pack;
-    static const bool no_pipe = getenv("MCF_NO_HOSTPIPE") != nullptr;
     std::future<std::string> pending;            // the previous piece going to disk while this one is packed and copied
     float kms = 0;
     int rc = MCF_OK;
@@ -1867,15 +1788,7 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
         // stage[i & 1] was handed to the writer two pieces ago: that write has been joined (below) before piece i-1 began
         const size_t bytes = (size_t)(n * rb);
         uint8_t* st = nc->staging((int)(i & 1), bytes);
-        if (e == hipSuccess) {
-            if (bytes >= ((size_t)64 << 20) && !no_pipe && ensure_pipe(p)) {
-                e = hipEventRecord(p->ev_pipe, p->stream);
-                if (e == hipSuccess) e = p->pipe->copy(st, p->d_pack, bytes, p->ev_pipe);
-            } else {
-                e = hipMemcpyAsync(st, p->d_pack, bytes, hipMemcpyDeviceToHost, p->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-            }
-        }
+        if (e == hipSuccess) e = p->tohost.dense(st, p->d_pack, bytes, p->stream);
         if (e == hipSuccess && kernel_ms) {
             float ms = 0;
             e = hipEventElapsedTime(&ms, p->ev0, p->ev1);
@@ -1901,8 +1814,7 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
 
 int mcf_plan_slot_ptr(mcf_plan* p, int32_t slot, int32_t var, void** dev_ptr) {
     if (!p || !dev_ptr) return fail(MCF_ERR_ARG, "null argument");
-    if (slot < 0 || slot >= p->ring_slots || var < 0 || var >= MCF_NOUT || p->var_slot[var] < 0)
-        return fail(MCF_ERR_ARG, "bad slot/var");
+    if (const int rc = check_slot_range(p, slot, var, 0, 0)) return rc;
     *dev_ptr = const_cast<double*>(ring_view(p, slot, var).base);
     return MCF_OK;
 }
@@ -1978,13 +1890,13 @@ int mcf_selftest_math(int32_t kind, const double* x, const double* y, double* ou
     int rc = ensure_device(device);
     if (rc) return rc;
     double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    struct G { double *&a, *&b, *&c; ~G() { hipFree(a); hipFree(b); hipFree(c); } } g{dx, dy, dout};
-    size_t nb = (size_t)std::max<int64_t>(n, 1) * 8;
-    HIP_TRY(hipMalloc((void**)&dx, nb));
-    HIP_TRY(hipMalloc((void**)&dout, nb));
+    mcf::DevOwner tmp;
+    const int64_t nb = std::max<int64_t>(n, 1) * 8;
+    if ((rc = tmp.alloc((void**)&dx, nb))) return rc;
+    if ((rc = tmp.alloc((void**)&dout, nb))) return rc;
     HIP_TRY(hipMemcpy(dx, x, (size_t)n * 8, hipMemcpyHostToDevice));
     if (y) {
-        HIP_TRY(hipMalloc((void**)&dy, nb));
+        if ((rc = tmp.alloc((void**)&dy, nb))) return rc;
         HIP_TRY(hipMemcpy(dy, y, (size_t)n * 8, hipMemcpyHostToDevice));
     }
     mcf::launch_selftest_math(kind, dx, dy, dout, n, nullptr);
@@ -2134,7 +2046,7 @@ int mcf_runbioclim2(const mcf_grid_inputs* in, const mcf_options* opt, const mcf
 }
 
 int64_t mcf_plan_valid_cells(const mcf_plan* p) { return p ? p->valid_cells : 0; }
-int64_t mcf_plan_bytes(const mcf_plan* p) { return p ? p->bytes : 0; }
+int64_t mcf_plan_bytes(const mcf_plan* p) { return p ? p->dev.bytes : 0; }
 
 // ---- one-shot host-to-host solve ---------------------------------------------------------
 // twi_mean: null, or the raster-wide mean of log(twi)/tfact to install (a row block of a larger raster, run_multi)
@@ -2309,14 +2221,14 @@ static int for_row_blocks(const mcf_grid_inputs* in_caller, const mcf_options* o
         HIP_TRY(hipSetDevice(devs[0]));
         const int64_t N = in->rows * in->cols;
         double *d_twi = nullptr, *d_ws = nullptr;
-        HIP_TRY(hipMalloc((void**)&d_twi, (size_t)N * 8));
-        struct G { double *&a, *&b; ~G() { (void)hipFree(a); (void)hipFree(b); } } g{d_twi, d_ws};
-        HIP_TRY(hipMalloc((void**)&d_ws, (size_t)mcf::twi_scratch_doubles() * 8));
+        mcf::DevOwner tmp;
+        if ((rc = tmp.alloc((void**)&d_twi, N * 8))) return rc;
+        if ((rc = tmp.alloc((void**)&d_ws, (int64_t)mcf::twi_scratch_doubles() * 8))) return rc;
         if (derive_twi) {
             // the wetness index of the whole raster, once, on the first device (flow accumulation does not tile)
             double* d_dtm = nullptr;
-            HIP_TRY(hipMalloc((void**)&d_dtm, (size_t)N * 8));
-            struct Free { double* q; ~Free() { (void)hipFree(q); } } free_dtm{d_dtm};
+            mcf::DevOwner tmp_dtm;      // (released before the reduction below)
+            if ((rc = tmp_dtm.alloc((void**)&d_dtm, N * 8))) return rc;
             HIP_TRY(hipMemcpy(d_dtm, dtm->dtm, (size_t)N * 8, hipMemcpyHostToDevice));
             if ((rc = mcf::topidx_device(d_dtm, in->rows, in->cols, dtm->xres, dtm->yres, d_twi, nullptr))) return rc;
             twi_host.resize((size_t)(pitch * in->cols));

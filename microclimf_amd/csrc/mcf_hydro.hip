@@ -27,6 +27,7 @@
 #include "../../include/mcf.h"
 #include "mcf_hydro.h"
 #include "mcf_rowblocks.hpp"
+#include "mcf_hiphost.hpp"
 
 // the host code this restates is built without FMA contraction
 #pragma clang fp contract(off)
@@ -34,29 +35,6 @@
 namespace {
 
 typedef unsigned long long u64;
-
-#define H_TRY(expr)                                                                             \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            char b_[512];                                                                       \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),      \
-                     __FILE__, __LINE__);                                                       \
-            return mcf::api_fail(e_ == hipErrorOutOfMemory ? MCF_ERR_NOMEM : MCF_ERR_HIP, b_);  \
-        }                                                                                       \
-    } while (0)
-
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-    int alloc(void** out, int64_t bytes) {
-        if (bytes <= 0) bytes = 8;
-        hipError_t e = hipMalloc(out, (size_t)bytes);
-        if (e != hipSuccess) return mcf::api_fail(MCF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-        p.push_back(*out);
-        return MCF_OK;
-    }
-};
 
 constexpr double kNaInt = -2147483648.0;
 constexpr u64 kNaRealBits = 0x7FF00000000007A2ULL;       // R's NA_real_
@@ -256,7 +234,7 @@ inline unsigned grid_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 inline unsigned grid_reduce(int64_t n) { return (unsigned)std::min<int64_t>((n + 255) / 256, 4096); }
 
 // the device part of flowacc: d_fa from d_dtm, scratch from `db`
-int flowacc_launch(const double* d_dtm, int64_t R, int64_t C, double* d_fa, DevBufs& db, int* rounds_out) {
+int flowacc_launch(const double* d_dtm, int64_t R, int64_t C, double* d_fa, mcf::DevOwner& db, int* rounds_out) {
     const int64_t N = R * C;
     if (N >= ((int64_t)1 << 31)) return mcf::api_fail(MCF_ERR_ARG, "flow accumulation on the device: at most 2^31 - 1 cells");
     int rc;
@@ -274,30 +252,30 @@ int flowacc_launch(const double* d_dtm, int64_t R, int64_t C, double* d_fa, DevB
         if ((rc = db.alloc((void**)&d_jump[k], N * 4))) return rc;
         if ((rc = db.alloc((void**)&d_acc[k], N * 8))) return rc;
     }
-    H_TRY(hipMemsetAsync(d_left, 0, (size_t)max_rounds * 4, nullptr));
-    H_TRY(hipMemsetAsync(d_last, 0xFF, sizeof(LastCell), nullptr));
+    HIP_TRY(hipMemsetAsync(d_left, 0, (size_t)max_rounds * 4, nullptr));
+    HIP_TRY(hipMemsetAsync(d_last, 0xFF, sizeof(LastCell), nullptr));
     hipLaunchKernelGGL(k_zmin, dim3(grid_reduce(N)), dim3(256), 0, nullptr, d_dtm, N, d_last);
     hipLaunchKernelGGL(k_rmmin, dim3(grid_reduce(N)), dim3(256), 0, nullptr, d_dtm, R, C, d_last);
     hipLaunchKernelGGL(k_edges, dim3(grid_for(N)), dim3(256), 0, nullptr, d_dtm, R, C, d_last, d_recv, d_kind, d_jump[0], d_acc[0]);
-    H_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     int cur = 0, rounds = 0;
     for (;;) {
         if (rounds == max_rounds) return mcf::api_fail(MCF_ERR_HIP, "flow accumulation: the early edges do not form a forest");
-        H_TRY(hipMemcpyAsync(d_acc[cur ^ 1], d_acc[cur], (size_t)N * 8, hipMemcpyDeviceToDevice, nullptr));
+        HIP_TRY(hipMemcpyAsync(d_acc[cur ^ 1], d_acc[cur], (size_t)N * 8, hipMemcpyDeviceToDevice, nullptr));
         hipLaunchKernelGGL(k_double, dim3(grid_for(N)), dim3(256), 0, nullptr, d_jump[cur], d_jump[cur ^ 1], d_acc[cur], d_acc[cur ^ 1],
                            N, d_left + rounds);
-        H_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         int32_t left = 0;
-        H_TRY(hipMemcpy(&left, d_left + rounds, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&left, d_left + rounds, 4, hipMemcpyDeviceToHost));
         cur ^= 1;
         ++rounds;
         if (!left) break;
     }
     u64 *d_P = d_acc[cur], *d_late = d_acc[cur ^ 1];
-    H_TRY(hipMemsetAsync(d_late, 0, (size_t)N * 8, nullptr));
+    HIP_TRY(hipMemsetAsync(d_late, 0, (size_t)N * 8, nullptr));
     hipLaunchKernelGGL(k_late, dim3(grid_for(N)), dim3(256), 0, nullptr, d_recv, d_kind, d_P, d_late, N);
     hipLaunchKernelGGL(k_fa, dim3(grid_for(N)), dim3(256), 0, nullptr, d_dtm, d_kind, d_P, d_late, d_fa, N);
-    H_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (rounds_out) *rounds_out = rounds;
     return MCF_OK;
 }
@@ -312,10 +290,10 @@ namespace mcf {
 
 // All launches on the null stream; returns after the device has finished, its temporaries released.
 int flowacc_device(const double* d_dtm, int64_t rows, int64_t cols, double* d_fa) {
-    DevBufs db;
+    mcf::DevOwner db;
     int rounds = 0;
     if (const int rc = flowacc_launch(d_dtm, rows, cols, d_fa, db, &rounds)) return rc;
-    H_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     report_rounds(rows, cols, rounds);
     return MCF_OK;
 }
@@ -323,27 +301,24 @@ int flowacc_device(const double* d_dtm, int64_t rows, int64_t cols, double* d_fa
 int topidx_device(const double* d_dtm, int64_t rows, int64_t cols, double xres, double yres, double* d_twi, double* d_fa) {
     const int64_t N = rows * cols;
     int rc;
-    struct Own { void* p = nullptr; ~Own() { if (p) (void)hipFree(p); } } own_fa;
-    if (!d_fa) {
-        H_TRY(hipMalloc(&own_fa.p, (size_t)N * 8));
-        d_fa = (double*)own_fa.p;
-    }
+    mcf::DevOwner own_fa;
+    if (!d_fa && (rc = own_fa.alloc((void**)&d_fa, N * 8))) return rc;
     {
-        DevBufs db;                                  // the flow accumulation's scratch goes before the slopes' is taken
+        mcf::DevOwner db;                            // the flow accumulation's scratch goes before the slopes' is taken
         int rounds = 0;
         if ((rc = flowacc_launch(d_dtm, rows, cols, d_fa, db, &rounds))) return rc;
-        H_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipDeviceSynchronize());
         report_rounds(rows, cols, rounds);
     }
-    DevBufs db;
+    mcf::DevOwner db;
     double* d_B;
     u64* d_hist;                                     // [8][256] digit histograms, then [2] of k_below
     if ((rc = db.alloc((void**)&d_B, N * 8))) return rc;
     if ((rc = db.alloc((void**)&d_hist, (8 * 256 + 2) * 8))) return rc;
-    H_TRY(hipMemsetAsync(d_hist, 0, (8 * 256 + 2) * 8, nullptr));
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (8 * 256 + 2) * 8, nullptr));
     const double minslope = atan(0.02 / (0.5 * (xres + yres)));
     hipLaunchKernelGGL(k_horn, dim3(grid_for(N)), dim3(256), 0, nullptr, d_dtm, rows, cols, xres, yres, minslope, d_B);
-    H_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     // R's median of the non-NA slopes: the middle order statistic, or the mean of the two middle ones
     double med = nan("");
     u64 hist[256];
@@ -352,8 +327,8 @@ int topidx_device(const double* d_dtm, int64_t rows, int64_t cols, double xres, 
         const int shift = 56 - 8 * pass;
         u64* d_h = d_hist + 256 * pass;
         hipLaunchKernelGGL(k_hist, dim3(grid_reduce(N)), dim3(256), 0, nullptr, d_B, N, prefix, shift, d_h);
-        H_TRY(hipGetLastError());
-        H_TRY(hipMemcpy(hist, d_h, 256 * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(hist, d_h, 256 * 8, hipMemcpyDeviceToHost));
         if (pass == 0) {
             for (int b = 0; b < 256; ++b) n += hist[b];
             if (n == 0) break;
@@ -368,9 +343,9 @@ int topidx_device(const double* d_dtm, int64_t rows, int64_t cols, double xres, 
         if (n % 2 == 0) {
             u64* d_out = d_hist + 8 * 256;
             hipLaunchKernelGGL(k_below, dim3(grid_reduce(N)), dim3(256), 0, nullptr, d_B, N, prefix, d_out);
-            H_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             u64 out[2];
-            H_TRY(hipMemcpy(out, d_out, 16, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(out, d_out, 16, hipMemcpyDeviceToHost));
             // fewer than n / 2 slopes below the upper middle one: the lower middle one equals it
             if (out[0] == n / 2) {
                 double lo;
@@ -380,23 +355,23 @@ int topidx_device(const double* d_dtm, int64_t rows, int64_t cols, double xres, 
         }
     }
     hipLaunchKernelGGL(k_twi, dim3(grid_for(N)), dim3(256), 0, nullptr, d_dtm, d_fa, d_B, med, xres, yres, (u64*)d_twi, N);
-    H_TRY(hipGetLastError());
-    H_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 
 int mask_na_device(const double* d_dtm, int64_t rows, int64_t cols, int32_t halo_north, int32_t halo_south, double* d_a, double* d_b) {
     hipLaunchKernelGGL(k_mask_na, dim3(grid_for(rows * cols)), dim3(256), 0, nullptr, d_dtm, rows, cols,
                        (int64_t)halo_north + rows + halo_south, (int64_t)halo_north, (u64*)d_a, (u64*)d_b);
-    H_TRY(hipGetLastError());
-    H_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 
 int svf_from_hor_device(const double* d_hor, int64_t N, double* d_svfa) {
     hipLaunchKernelGGL(k_svf_from_hor, dim3(grid_for(N)), dim3(256), 0, nullptr, d_hor, N, d_svfa);
-    H_TRY(hipGetLastError());
-    H_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 
@@ -406,17 +381,17 @@ int svf_from_hor_device(const double* d_hor, int64_t N, double* d_svfa) {
 static int hydro_host(int64_t rows, int64_t cols, const double* dtm, double xres, double yres, double* res, int32_t device, bool twi) {
     if (const int rc = mcf::check_device(device)) return rc;
     mcf::RestoreDevice restore;
-    H_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const int64_t N = rows * cols;
-    DevBufs db;
+    mcf::DevOwner db;
     int rc;
     double *d_dtm, *d_res;
     if ((rc = db.alloc((void**)&d_dtm, N * 8))) return rc;
     if ((rc = db.alloc((void**)&d_res, N * 8))) return rc;
-    H_TRY(hipMemcpy(d_dtm, dtm, (size_t)N * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dtm, dtm, (size_t)N * 8, hipMemcpyHostToDevice));
     if ((rc = twi ? mcf::topidx_device(d_dtm, rows, cols, xres, yres, d_res, nullptr) : mcf::flowacc_device(d_dtm, rows, cols, d_res)))
         return rc;
-    H_TRY(hipMemcpy(res, d_res, (size_t)N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(res, d_res, (size_t)N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

@@ -20,8 +20,8 @@
 #include <vector>
 
 #include "../../include/mcf.h"
-#include "mcf_hostpipe.hpp"
 #include "mcf_rowblocks.hpp"
+#include "mcf_hiphost.hpp"
 #include "mcf_snow_device.hpp"
 
 // the ring kernel (lane per cell-hour, cell table in LDS, step record through scalar loads): 141 VGPRs without scratch at three
@@ -1133,17 +1133,6 @@ __global__ __launch_bounds__(256) void k_apply3_fin(const double* __restrict__ w
 }
 
 // ---- host side -------------------------------------------------------------------------------------
-#define S_TRY(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            char b_[512];                                                                    \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                     __FILE__, __LINE__);                                                    \
-            return mcf::api_fail(e_ == hipErrorOutOfMemory ? MCF_ERR_NOMEM : MCF_ERR_HIP, b_); \
-        }                                                                                    \
-    } while (0)
-
 struct Events {   // timing events released on every exit path
     std::vector<hipEvent_t> e;
     ~Events() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
@@ -1155,64 +1144,6 @@ struct Events {   // timing events released on every exit path
             e.push_back(x);
         }
         return hipSuccess;
-    }
-};
-
-struct Bufs {
-    std::vector<void*> p;
-    int64_t bytes = 0;
-    ~Bufs() { release_all(); }
-    void release_all() { for (void* q : p) (void)hipFree(q); p.clear(); bytes = 0; }
-    int alloc(void** out, int64_t n) {
-        if (n <= 0) n = 8;
-        hipError_t e = hipMalloc(out, (size_t)n);
-        if (e != hipSuccess)
-            return mcf::api_fail(MCF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-        p.push_back(*out);
-        bytes += n;
-        return MCF_OK;
-    }
-    // device copy of a host array of `n` elements of size `esz`
-    template <class T>
-    int up(const T** dev, const T* host, int64_t n, const char* what) {
-        if (!host) return mcf::api_fail(MCF_ERR_ARG, std::string("null input: ") + what);
-        void* d;
-        int rc = alloc(&d, n * (int64_t)sizeof(T));
-        if (rc) return rc;
-        hipError_t e = hipMemcpy(d, host, (size_t)n * sizeof(T), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return mcf::api_fail(MCF_ERR_HIP, std::string("upload failed: ") + what);
-        *dev = (const T*)d;
-        return MCF_OK;
-    }
-};
-// device -> caller-owned pageable memory; large results through the pinned ring + copy threads (mcf_hostpipe.hpp)
-struct Downloader {
-    mcf::HostPipe pipe;
-    bool tried = false, ok = false;
-    // rows of `width` bytes, contiguous on the device, `dpitch` bytes apart on the host (a row block's series)
-    hipError_t get_pitched(void* dst, size_t dpitch, const void* dev, size_t width, size_t height) {
-        static const bool no_pipe = getenv("MCF_NO_HOSTPIPE") != nullptr;
-        if (width * height >= ((size_t)64 << 20) && width <= mcf::HostPipe::kPiece && !no_pipe) {
-            if (!tried) { tried = true; ok = pipe.init(); }
-            if (ok) {
-                hipError_t e = hipDeviceSynchronize();      // the producers ran on the null stream
-                if (e != hipSuccess) return e;
-                return pipe.copy_pitched(dst, dpitch, dev, width, height, nullptr);
-            }
-        }
-        return hipMemcpy2D(dst, dpitch, dev, width, width, height, hipMemcpyDeviceToHost);
-    }
-    hipError_t get(void* dst, const void* dev, size_t bytes) {
-        static const bool no_pipe = getenv("MCF_NO_HOSTPIPE") != nullptr;
-        if (bytes >= ((size_t)64 << 20) && !no_pipe) {
-            if (!tried) { tried = true; ok = pipe.init(); }
-            if (ok) {
-                hipError_t e = hipDeviceSynchronize();      // the producers ran on the null stream
-                if (e != hipSuccess) return e;
-                return pipe.copy(dst, dev, bytes, nullptr);
-            }
-        }
-        return hipMemcpy(dst, dev, bytes, hipMemcpyDeviceToHost);
     }
 };
 
@@ -1257,7 +1188,7 @@ int common_checks(const mcf_snow_inputs* in) {
 }
 
 // fills the time-class device tables shared by both entry points
-int build_step_tables(Bufs& b, const mcf_snow_inputs* in, bool af, bool model, bool degrees, const StepRow** rows,
+int build_step_tables(mcf::DevOwner& b, const mcf_snow_inputs* in, bool af, bool model, bool degrees, const StepRow** rows,
                       const DateRow2** dates, const double** mxtc1) {
     const int T = (int)in->tsteps;
     int rc;
@@ -1321,7 +1252,7 @@ int run_snowmodel(const mcf_snow_inputs* in, mcf_snowmodel_out* out, int32_t dev
     double* host3[5] = {out->Tc, out->Tg, out->sdepc, out->sdepg, out->sden};
     for (double* p : host3) nout3 += p != nullptr;
     if ((rc = check_room((af ? 13 * NT : 0) * 8 + (int64_t)nout3 * NT * 8 + 60 * N * 8))) return rc;
-    Bufs b;
+    mcf::DevOwner b;
     ModelArgs a;
     memset(&a, 0, sizeof a);
     a.N = N; a.tsteps = T; a.zref = in->other.zref;
@@ -1368,24 +1299,24 @@ int run_snowmodel(const mcf_snow_inputs* in, mcf_snowmodel_out* out, int32_t dev
     const unsigned grid = (unsigned)((N + 255) / 256);
     Events evs;
     const bool timing = getenv("MCF_TIMING") != nullptr;
-    if (timing) { S_TRY(evs.make(2)); S_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
     if (af) hipLaunchKernelGGL(k_snowmodel<true>, dim3(grid), dim3(256), 0, nullptr, a, a.rows, a.dates);
     else hipLaunchKernelGGL(k_snowmodel<false>, dim3(grid), dim3(256), 0, nullptr, a, a.rows, a.dates);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (timing) {
-        S_TRY(hipEventRecord(evs.e[1], nullptr));
-        S_TRY(hipEventSynchronize(evs.e[1]));
+        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(evs.e[1]));
         float ms = 0;
-        S_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
         fprintf(stderr, "[mcf] k_snowmodel<%d>: %lld cells x %d steps in %.3f ms (%.3e cell-steps/s)\n", (int)af,
                 (long long)N, T, ms, (double)NT / (ms * 1e-3));
     }
-    Downloader dl;
+    mcf::ToHost dl;
     for (int v = 0; v < 5; ++v)
-        if (host3[v]) S_TRY(dl.get(host3[v], *dev3[v], (size_t)NT * 8));
+        if (host3[v]) HIP_TRY(dl.dense(host3[v], *dev3[v], (size_t)NT * 8));
     for (int v = 0; v < 4; ++v)
-        if (host2[v]) S_TRY(hipMemcpy(host2[v], *dev2[v], (size_t)N * 8, hipMemcpyDeviceToHost));
-    S_TRY(hipDeviceSynchronize());
+        if (host2[v]) HIP_TRY(hipMemcpy(host2[v], *dev2[v], (size_t)N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 
@@ -1406,7 +1337,7 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
     int nsel = 0;
     for (int v = 0; v < MCF_NOUT; ++v) nsel += outsel[v] != 0;
     if ((rc = check_room(((af ? 9 : 0) + 5 + nsel) * NT * 8 + 60 * N * 8))) return rc;
-    Bufs b;
+    mcf::DevOwner b;
     MicroArgs a;
     memset(&a, 0, sizeof a);
     a.N = N; a.tsteps = T; a.reqhgt = reqhgt; a.mat = mat; a.zref = in->other.zref;
@@ -1462,7 +1393,7 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
         for (int v = 0; v < MCF_NOUT; ++v) {
             if (!outsel[v]) continue;
             a.out[v] = outbuf + (int64_t)rank * NT;
-            S_TRY(hipMemcpyAsync(a.out[v], micro->var[v], (size_t)NT * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(a.out[v], micro->var[v], (size_t)NT * 8, hipMemcpyHostToDevice, nullptr));
             q.held |= 1u << v;
             ++rank;
         }
@@ -1490,8 +1421,8 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
         int32_t *d_map = nullptr, *d_one = nullptr;
         if ((rc = b.alloc((void**)&d_map, (int64_t)nch * 4))) return rc;
         if ((rc = b.alloc((void**)&d_one, (int64_t)nch * 4))) return rc;
-        S_TRY(hipMemcpy(d_map, ident.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
-        S_TRY(hipMemcpy(d_one, ones.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_map, ident.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_one, ones.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
         q.daymap = d_map; q.nosnow = d_one; q.ndays = nch;
         for (int d0 = 0; d0 < nch; d0 += 32768) {        // (cells, days): the grid's y extent is 16 bits
             a.day0 = d0;
@@ -1501,11 +1432,11 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
             else hipLaunchKernelGGL(k_microsnow_ring<false>, grid, dim3(256), 0, nullptr, q, a.mstep, q.daymap, q.nosnow);
         }
     }
-    S_TRY(hipGetLastError());
-    Downloader dl;
+    HIP_TRY(hipGetLastError());
+    mcf::ToHost dl;
     for (int v = 0; v < MCF_NOUT; ++v)
-        if (outsel[v]) S_TRY(dl.get(micro->var[v], a.out[v], (size_t)NT * 8));
-    S_TRY(hipDeviceSynchronize());
+        if (outsel[v]) HIP_TRY(dl.dense(micro->var[v], a.out[v], (size_t)NT * 8));
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 
@@ -1519,7 +1450,7 @@ struct mcf_snowplan {
     int64_t rows = 0, cols = 0, N = 0, row0 = 0, rows_total = 0;
     int T = 0, chunk = 120, nchunks = 1, ss = 10;
     double res = 1.0, tfact = 0.02, zref = 2.0;
-    Bufs b;
+    mcf::DevOwner b;
     ModelArgs a;
     const StepRow* rows_tab = nullptr;
     // array weather (`.snowmodel2`'s loop): the caller's thirteen [N][T] series — a chunk's slices go up as the loop reaches it —
@@ -1547,7 +1478,7 @@ struct mcf_snowplan {
     std::vector<double> mm_host;         // max[chunk], count[chunk], min[chunk], count[chunk]
     int32_t *d_ac = nullptr, *d_ag = nullptr;
     std::vector<double> wind;
-    Downloader dl;
+    mcf::ToHost dl;
     int prepared = -1;
     double t_terrain = 0, t_model = 0;   // ms, MCF_TIMING
     mcf::TerrainWork twork;              // terrain_device's scratch, kept across the chunks
@@ -1559,7 +1490,7 @@ struct mcf_snowplan {
     int32_t* d_sden_na = nullptr;        // the subset series' first snow density is NA (cpp:4716)
     int64_t sumD_steps = 0;
     bool micro_ready = false;
-    Bufs mb, mbs;                        // the micro set-up's buffers: per-call (series) and static (vegetation, terrain)
+    mcf::DevOwner mb, mbs;               // the micro set-up's buffers: per-call (series) and static (vegetation, terrain)
     bool micro_static = false;
     MicroArgs ma;
     // array weather: the caller's whole-series [N][T] arrays of gridmicrosnow2's weather (temp, relhum, pres, swdown, difrad, lwdown,
@@ -1589,7 +1520,7 @@ struct mcf_snowplan {
     std::vector<Kept> pool;              // released sets, reused by the next year's pass 1 (hipMalloc of 10 GB costs 0.25 s)
     int64_t keep_budget = -1;            // bytes of kept sets this plan may ALLOCATE in all (mcf_snowplan_set_keep_budget); -1: no limit of its own
     int64_t keep_allocated = 0;
-    Bufs kb;
+    mcf::DevOwner kb;
     ~mcf_snowplan() { twork.release(); }
 };
 
@@ -1656,7 +1587,7 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
     else sp->wind.assign(in->clim.windspeed, in->clim.windspeed + sp->T);
     const int64_t N = sp->N;
     const int T = sp->T;
-    Bufs& b = sp->b;
+    mcf::DevOwner& b = sp->b;
     ModelArgs& a = sp->a;
     memset(&a, 0, sizeof a);
     a.N = N; a.zref = sp->zref;
@@ -1728,8 +1659,8 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
     if ((rc = b.alloc((void**)&a.ageg, N * 8))) return rc;
     hipLaunchKernelGGL(k_add_snow, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, sp->d_dtm, sp->d_isnowdg, 1.0,
                        N, sp->d_dtms);   // int:2562
-    S_TRY(hipGetLastError());
-    S_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     guard.p = nullptr;
     *out = sp;
     return MCF_OK;
@@ -1742,22 +1673,22 @@ extern "C" void mcf_snowplan_destroy(mcf_snowplan* sp) {
 extern "C" int32_t mcf_snowplan_chunks(const mcf_snowplan* sp) { return sp ? sp->nchunks : 0; }
 extern "C" int mcf_snowplan_surface(mcf_snowplan* sp, double* host_own) {
     if (!sp || !host_own) return mcf::api_fail(MCF_ERR_ARG, "null argument");
-    S_TRY(hipSetDevice(sp->device));
-    S_TRY(hipMemcpy(host_own, sp->d_dtms, (size_t)sp->N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipMemcpy(host_own, sp->d_dtms, (size_t)sp->N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_handover(mcf_snowplan* sp, double* host_isnowdc) {
     if (!sp || !host_isnowdc) return mcf::api_fail(MCF_ERR_ARG, "null argument");
-    S_TRY(hipSetDevice(sp->device));
-    S_TRY(hipMemcpy(host_isnowdc, sp->d_isnowdc, (size_t)sp->N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipMemcpy(host_isnowdc, sp->d_isnowdc, (size_t)sp->N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_surface_partial(mcf_snowplan* sp, double* sum, double* count) {
     if (!sp || !sum || !count) return mcf::api_fail(MCF_ERR_ARG, "null argument");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     launch_sumcount(sp->d_dtms, sp->N, sp->d_sumws, sp->d_mean2);
     double h[2];
-    S_TRY(hipMemcpy(h, sp->d_mean2, 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, sp->d_mean2, 16, hipMemcpyDeviceToHost));
     *sum = h[0]; *count = h[1];
     return MCF_OK;
 }
@@ -1803,13 +1734,13 @@ extern "C" int mcf_snowplan_prepare_chunk(mcf_snowplan* sp, int32_t ch, const do
     if (!sp || !tpic_sum || !tpic_count) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
     if (hn < 0 || hs < 0 || (!ext && (hn || hs))) return mcf::api_fail(MCF_ERR_ARG, "bad halo");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const double* d_z = sp->d_dtms;
     if (ext) {
         const int64_t n = (hn + sp->rows + hs) * sp->cols;
         int rc;
         if ((rc = ext_room(sp, n))) return rc;
-        S_TRY(hipMemcpy(sp->d_ext, ext, (size_t)n * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(sp->d_ext, ext, (size_t)n * 8, hipMemcpyHostToDevice));
         d_z = sp->d_ext;
     }
     return prepare_chunk_on(sp, ch, d_z, hn, hs, surface_mean, tpic_sum, tpic_count);
@@ -1817,11 +1748,11 @@ extern "C" int mcf_snowplan_prepare_chunk(mcf_snowplan* sp, int32_t ch, const do
 extern "C" int mcf_snowplan_pack_halo(mcf_snowplan* sp, int32_t hn, double* d_north, int32_t hs, double* d_south) {
     if (!sp || hn < 0 || hs < 0 || hn > sp->rows || hs > sp->rows || (hn && !d_north) || (hs && !d_south))
         return mcf::api_fail(MCF_ERR_ARG, "bad mcf_snowplan_pack_halo argument");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const int64_t n = (int64_t)(hn + hs) * sp->cols;
     if (n > 0) hipLaunchKernelGGL(k_halo_pack, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sp->d_dtms, sp->rows, sp->cols, hn, hs, d_north, d_south);
-    S_TRY(hipGetLastError());
-    S_TRY(hipStreamSynchronize(nullptr));      // the pieces are the caller's to send from here on
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(nullptr));      // the pieces are the caller's to send from here on
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_prepare_chunk_dev(mcf_snowplan* sp, int32_t ch, const double* d_north, int32_t hn, const double* d_south,
@@ -1829,7 +1760,7 @@ extern "C" int mcf_snowplan_prepare_chunk_dev(mcf_snowplan* sp, int32_t ch, cons
     if (!sp || !tpic_sum || !tpic_count) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
     if (hn < 0 || hs < 0 || (hn && !d_north) || (hs && !d_south)) return mcf::api_fail(MCF_ERR_ARG, "bad halo");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const double* d_z = sp->d_dtms;
     if (hn || hs) {
         const int64_t n = (hn + sp->rows + hs) * sp->cols;
@@ -1837,7 +1768,7 @@ extern "C" int mcf_snowplan_prepare_chunk_dev(mcf_snowplan* sp, int32_t ch, cons
         if ((rc = ext_room(sp, n))) return rc;
         hipLaunchKernelGGL(k_ext_assemble, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nullptr, sp->d_ext, sp->d_dtms, d_north, d_south,
                            sp->rows, sp->cols, hn, hs);
-        S_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         d_z = sp->d_ext;
     }
     return prepare_chunk_on(sp, ch, d_z, hn, hs, surface_mean, tpic_sum, tpic_count);
@@ -1882,7 +1813,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
     }
     const bool timing = getenv("MCF_TIMING") != nullptr;
     Events evs;
-    if (timing) { S_TRY(evs.make(2)); S_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
     // terrain of dtm + snow (int:2566-2580)
     mcf::TerrainDev td;
     memset(&td, 0, sizeof td);
@@ -1898,11 +1829,11 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
     if (!always) {
         if (!sp->d_zdiff && (rc = sp->b.alloc((void**)&sp->d_zdiff, 4))) return rc;
         if (sp->d_zlast && sp->zlast_n == zn && sp->zlast_hn == hn && sp->zlast_hs == hs) {
-            S_TRY(hipMemsetAsync(sp->d_zdiff, 0, 4, nullptr));
+            HIP_TRY(hipMemsetAsync(sp->d_zdiff, 0, 4, nullptr));
             hipLaunchKernelGGL(k_surface_differs, dim3((unsigned)((zn + 255) / 256)), dim3(256), 0, nullptr, d_z, (const double*)sp->d_zlast, zn,
                                sp->d_zdiff);
             int32_t diff = 1;
-            S_TRY(hipMemcpy(&diff, sp->d_zdiff, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&diff, sp->d_zdiff, 4, hipMemcpyDeviceToHost));
             same = diff == 0;
         }
     }
@@ -1917,7 +1848,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
                 if ((rc = sp->b.alloc((void**)&sp->d_zlast, zn * 8))) return rc;
                 sp->zlast_cap = zn;
             }
-            S_TRY(hipMemcpyAsync(sp->d_zlast, d_z, (size_t)zn * 8, hipMemcpyDeviceToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_zlast, d_z, (size_t)zn * 8, hipMemcpyDeviceToDevice, nullptr));
             sp->zlast_n = zn; sp->zlast_hn = hn; sp->zlast_hs = hs;
         }
     }
@@ -1935,15 +1866,15 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
                            sp->tfact, sp->d_tpic);
     }
     launch_sumcount(sp->d_tpic, N, sp->d_sumws, sp->d_mean2);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     double h[2];
-    S_TRY(hipMemcpy(h, sp->d_mean2, 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, sp->d_mean2, 16, hipMemcpyDeviceToHost));
     *tpic_sum = h[0]; *tpic_count = h[1];
     if (timing) {
-        S_TRY(hipEventRecord(evs.e[1], nullptr));
-        S_TRY(hipEventSynchronize(evs.e[1]));
+        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(evs.e[1]));
         float ms = 0;
-        S_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
         sp->t_terrain += ms;
     }
     sp->prepared = ch;
@@ -1971,7 +1902,7 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     if (!sp || !out) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (row_pitch <= 0) row_pitch = sp->rows;
     if (ch != sp->prepared) return mcf::api_fail(MCF_ERR_STATE, "snow plan: run_chunk needs prepare_chunk of the same chunk first");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     sp->mm_chunk = -1;
     if ((size_t)ch < sp->kept.size() && sp->kept[(size_t)ch].Tc) {     // a set kept from an earlier run of this chunk is stale now
         sp->pool.push_back(sp->kept[(size_t)ch]);
@@ -1982,14 +1913,14 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     const unsigned gridN = (unsigned)((N + 255) / 256);
     const bool timing = getenv("MCF_TIMING") != nullptr;
     Events evs;
-    if (timing) { S_TRY(evs.make(2)); S_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
     ModelArgs a = sp->a;
     a.rows = sp->af ? nullptr : sp->rows_tab + k0;            // gridmodelsnow1 on the chunk (int:2587)
     a.dates = sp->af ? sp->dates_tab + k0 : nullptr;          // gridmodelsnow2 (int:2979)
     a.tsteps = ns;
     if (sp->af)                                               // the chunk's slices of the caller's series: [N][T], a step's raster contiguous
         for (int f = 0; f < 13; ++f)
-            S_TRY(hipMemcpyAsync(sp->d_series[f], sp->h_series[f] + (int64_t)k0 * N, (size_t)ns * N * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_series[f], sp->h_series[f] + (int64_t)k0 * N, (size_t)ns * N * 8, hipMemcpyHostToDevice, nullptr));
     // ... with the redistribution by the topographic position index and the hand-over fused in (ModelArgs)
     a.tpic = sp->d_tpic; a.tpimean = tpic_mean; a.dtm = sp->d_dtm;
     a.isnowdc_out = sp->d_isnowdc; a.dtms = sp->d_dtms; a.isnowac_out = sp->d_ac; a.isnowag_out = sp->d_ag;
@@ -2007,12 +1938,12 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     }
     if (sp->af) hipLaunchKernelGGL(k_snowmodel<true>, dim3(gridN), dim3(256), 0, nullptr, a, a.rows, a.dates);
     else hipLaunchKernelGGL(k_snowmodel<false>, dim3(gridN), dim3(256), 0, nullptr, a, a.rows, a.dates);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     if (timing) {
-        S_TRY(hipEventRecord(evs.e[1], nullptr));
-        S_TRY(hipEventSynchronize(evs.e[1]));
+        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(evs.e[1]));
         float ms = 0;
-        S_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
         sp->t_model += ms;
     }
     double* hostv[5] = {out->Tc, out->Tg, out->groundsnowdepth, out->totalSWE, out->snowden};
@@ -2020,8 +1951,8 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     const int64_t HS = row_pitch * sp->cols;        // host doubles per step
     for (int v = 0; v < 5; ++v) {
         if (!hostv[v]) continue;
-        if (row_pitch == sp->rows) S_TRY(sp->dl.get(hostv[v] + host_step0 * N, devv[v], (size_t)ns * N * 8));
-        else S_TRY(sp->dl.get_pitched(hostv[v] + host_step0 * HS, (size_t)row_pitch * 8, devv[v], (size_t)sp->rows * 8, (size_t)(sp->cols * ns)));
+        if (row_pitch == sp->rows) HIP_TRY(sp->dl.dense(hostv[v] + host_step0 * N, devv[v], (size_t)ns * N * 8));
+        else HIP_TRY(sp->dl.pitched(hostv[v] + host_step0 * HS, (size_t)row_pitch * 8, devv[v], (size_t)sp->rows * 8, (size_t)(sp->cols * ns)));
     }
     if (fill_tail && ch == sp->nchunks - 1) {   // steps that no chunk covers stay NA (R pre-fills its arrays, int:2554-2558)
         union { uint64_t u; double d; } na; na.u = kNaRealBits;
@@ -2038,7 +1969,7 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
 // applycpp3 over device-resident data: [N][tsteps] -> result / count [tsteps] on the host
 static int apply3_device(const double* d_a, int64_t N, int64_t tsteps, int fun, double* result, double* count) {
     int rc;
-    Bufs b;
+    mcf::DevOwner b;
     double *d_r, *d_c = nullptr;
     if ((rc = b.alloc((void**)&d_r, tsteps * 8))) return rc;
     if (count && (rc = b.alloc((void**)&d_c, tsteps * 8))) return rc;
@@ -2050,15 +1981,15 @@ static int apply3_device(const double* d_a, int64_t N, int64_t tsteps, int fun, 
     hipLaunchKernelGGL(k_apply3_part, dim3((unsigned)parts, (unsigned)tsteps), dim3(256), 0, nullptr, d_a, N, fun, parts, d_ws);
     hipLaunchKernelGGL(k_apply3_fin, dim3((unsigned)((tsteps + 255) / 256)), dim3(256), 0, nullptr, d_ws, tsteps, fun, parts, d_r,
                        d_c);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpy(result, d_r, (size_t)tsteps * 8, hipMemcpyDeviceToHost));
-    if (count) S_TRY(hipMemcpy(count, d_c, (size_t)tsteps * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(result, d_r, (size_t)tsteps * 8, hipMemcpyDeviceToHost));
+    if (count) HIP_TRY(hipMemcpy(count, d_c, (size_t)tsteps * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_apply3(mcf_snowplan* sp, int32_t chunk, int32_t fun, double* result, double* count) {
     if (!sp || !result || fun < 0 || fun > 3) return mcf::api_fail(MCF_ERR_ARG, "bad mcf_snowplan_apply3 argument");
     if (chunk < 0 || chunk >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const int ns = std::min(sp->chunk, sp->T - chunk * sp->chunk);
     // (sdepc holds totalSWE after the redistribution; the series are the ones of the chunk run last)
     if (!(sp->series_valid & 4u)) return mcf::api_fail(MCF_ERR_STATE, "snow plan: the chunk's totalSWE series was switched off (mcf_snowplan_set_series)");
@@ -2079,8 +2010,8 @@ extern "C" int mcf_snowplan_apply3(mcf_snowplan* sp, int32_t chunk, int32_t fun,
         hipLaunchKernelGGL(k_apply3_fin, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, (const double*)ws_max, (int64_t)ns, 2, parts, d_r, d_r + C);
         hipLaunchKernelGGL(k_apply3_fin, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, (const double*)ws_min, (int64_t)ns, 3, parts, d_r + 2 * C,
                            d_r + 3 * C);
-        S_TRY(hipGetLastError());
-        S_TRY(hipMemcpy(sp->mm_host.data(), d_r, (size_t)(4 * C) * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpy(sp->mm_host.data(), d_r, (size_t)(4 * C) * 8, hipMemcpyDeviceToHost));
         sp->mm_chunk = chunk;
     }
     const double* h = sp->mm_host.data() + (fun == 2 ? 0 : 2 * sp->chunk);
@@ -2096,7 +2027,7 @@ extern "C" int mcf_applycpp3(const double* a, int64_t rows, int64_t cols, int64_
     if ((rc = pick_device(device))) return rc;
     const int64_t N = rows * cols;
     if ((rc = check_room(N * tsteps * 8))) return rc;
-    Bufs b;
+    mcf::DevOwner b;
     const double* d_a;
     UP(d_a, a, N * tsteps);
     return apply3_device(d_a, N, tsteps, (int)fun, result, count);
@@ -2114,7 +2045,7 @@ extern "C" int mcf_tpicalc(int64_t rows, int64_t cols, const double* dtm, int32_
     if ((rc = pick_device(device))) return rc;
     const int64_t N = rows * cols;
     if ((rc = check_room(N * 24))) return rc;
-    Bufs b;
+    mcf::DevOwner b;
     const double* d_z;
     double *d_t, *d_ws, *d_m2, *d_cm = nullptr;
     UP(d_z, dtm, N);
@@ -2132,27 +2063,27 @@ extern "C" int mcf_tpicalc(int64_t rows, int64_t cols, const double* dtm, int32_
     } else {
         launch_sumcount(d_z, N, d_ws, d_m2);
         double h[2];
-        S_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
         hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, nullptr, d_z, g, (const double*)nullptr, h[0] / h[1], tfact, d_t);
     }
     launch_sumcount(d_t, N, d_ws, d_m2);
     hipLaunchKernelGGL(k_scale_by_mean, dim3(gridN), dim3(256), 0, nullptr, d_t, N, (const double*)d_m2);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpy(tpic, d_t, (size_t)N * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(tpic, d_t, (size_t)N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 
 // ---- the snow-day microclimate inside the chunk loop --------------------------------------------------------------------
 extern "C" int mcf_snowplan_reset(mcf_snowplan* sp) {
     if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const int64_t N = sp->N;
-    S_TRY(hipMemcpy(sp->d_isnowdc, sp->d_isnowdc0, (size_t)N * 8, hipMemcpyDeviceToDevice));
-    S_TRY(hipMemcpy(sp->d_ac, sp->d_ac0, (size_t)N * 4, hipMemcpyDeviceToDevice));
-    S_TRY(hipMemcpy(sp->d_ag, sp->d_ag0, (size_t)N * 4, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(sp->d_isnowdc, sp->d_isnowdc0, (size_t)N * 8, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(sp->d_ac, sp->d_ac0, (size_t)N * 4, hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(sp->d_ag, sp->d_ag0, (size_t)N * 4, hipMemcpyDeviceToDevice));
     hipLaunchKernelGGL(k_add_snow, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, sp->d_dtm, sp->d_isnowdg, 1.0, N,
                        sp->d_dtms);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     sp->prepared = -1;
     return MCF_OK;
 }
@@ -2192,18 +2123,18 @@ extern "C" int mcf_snowplan_fetch_cells(mcf_snowplan* sp, int32_t what, const in
     }
     for (int j = 0; j < n; ++j)
         if (cells[j] < 0 || cells[j] >= sp->N) return mcf::api_fail(MCF_ERR_ARG, "snow plan: cell index outside the block");
-    S_TRY(hipSetDevice(sp->device));
-    Bufs tmp;
+    HIP_TRY(hipSetDevice(sp->device));
+    mcf::DevOwner tmp;
     int rc;
     int64_t* d_cells;
     double* d_out;
     if ((rc = tmp.alloc((void**)&d_cells, (int64_t)n * 8))) return rc;
     if ((rc = tmp.alloc((void**)&d_out, (int64_t)n * depth * 8))) return rc;
-    S_TRY(hipMemcpy(d_cells, cells, (size_t)n * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_cells, cells, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_gather_planes, dim3((unsigned)((n * depth + 255) / 256)), dim3(256), 0, nullptr, src, isrc, sp->N,
                        (const int64_t*)d_cells, n, depth, d_out);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpy(out, d_out, (size_t)n * depth * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d_out, (size_t)n * depth * 8, hipMemcpyDeviceToHost));
     if (depth_out) *depth_out = depth;
     return MCF_OK;
 }
@@ -2217,7 +2148,7 @@ extern "C" int mcf_snowplan_keep_chunk(mcf_snowplan* sp, int32_t ch, int64_t res
     if (!sp || !kept) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
     *kept = 0;
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     if (sp->kept.size() < (size_t)sp->nchunks) sp->kept.resize((size_t)sp->nchunks);
     if (sp->kept[ch].Tc) { *kept = 1; return MCF_OK; }
     if (sp->series_valid != 31) return MCF_OK;      // (a chunk run with some series switched off cannot be kept)
@@ -2230,21 +2161,20 @@ extern "C" int mcf_snowplan_keep_chunk(mcf_snowplan* sp, int32_t ch, int64_t res
         fresh[0] = f.Tc; fresh[1] = f.Tg; fresh[2] = f.sdepc; fresh[3] = f.sdepg; fresh[4] = f.sden; fresh[5] = f.tzd;
     } else {
         size_t free_b = 0, total_b = 0;
-        S_TRY(hipMemGetInfo(&free_b, &total_b));
+        HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         if ((int64_t)free_b < 5 * one + small + std::max<int64_t>(reserve_bytes, 0)) return MCF_OK;
         if (sp->keep_budget >= 0 && sp->keep_allocated + 5 * one > sp->keep_budget) return MCF_OK;
         for (int v = 0; v < 6; ++v) {
             if (v == 5 && !small) break;
-            if (hipMalloc((void**)&fresh[v], (size_t)(v == 5 ? small : one)) != hipSuccess) {      // (another process took the room: not an error)
+            if (sp->kb.alloc((void**)&fresh[v], v == 5 ? small : one) != MCF_OK) {      // (another process took the room: not an error)
                 (void)hipGetLastError();
-                for (int u = 0; u < v; ++u) { (void)hipFree(fresh[u]); sp->kb.p.pop_back(); }
+                for (int u = 0; u < v; ++u) sp->kb.release(fresh[u]);
                 return MCF_OK;
             }
-            sp->kb.p.push_back(fresh[v]);
         }
         sp->keep_allocated += 5 * one;
     }
-    S_TRY(hipDeviceSynchronize());         // (the chunk's kernels are done before its buffers change hands)
+    HIP_TRY(hipDeviceSynchronize());         // (the chunk's kernels are done before its buffers change hands)
     ModelArgs& a = sp->a;
     mcf_snowplan::Kept k;
     k.Tc = a.Tc; k.Tg = a.Tg; k.sdepc = a.sdepc; k.sdepg = a.sdepg; k.sden = a.sden; k.tzd = a.tzd;
@@ -2265,9 +2195,9 @@ extern "C" int mcf_snowplan_can_keep(mcf_snowplan* sp, int64_t reserve_bytes, in
     if (!sp || !yes) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     *yes = 0;
     if (!sp->pool.empty()) { *yes = 1; return MCF_OK; }
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     size_t free_b = 0, total_b = 0;
-    S_TRY(hipMemGetInfo(&free_b, &total_b));
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     const int64_t one = (int64_t)sp->chunk * sp->N * 8;
     *yes = (int64_t)free_b >= 5 * one + std::max<int64_t>(reserve_bytes, 0) ? 1 : 0;
     if (sp->keep_budget >= 0 && sp->keep_allocated + 5 * one > sp->keep_budget) *yes = 0;
@@ -2280,8 +2210,8 @@ extern "C" int mcf_snowplan_set_keep_budget(mcf_snowplan* sp, int64_t bytes) {
 }
 extern "C" int mcf_snowplan_release_kept(mcf_snowplan* sp) {
     if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
-    S_TRY(hipSetDevice(sp->device));
-    S_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipDeviceSynchronize());
     // the sets go to a pool for the next year's pass 1 (allocating 10 GB takes a quarter of a second: a year's cache costs more
     // to allocate than it saves, so it is allocated once per plan); the plan's allocation lists still own every buffer
     for (auto& k : sp->kept)
@@ -2296,7 +2226,7 @@ extern "C" int mcf_snowplan_release_kept(mcf_snowplan* sp) {
 extern "C" int mcf_snowplan_checkpoint(mcf_snowplan* sp, int32_t ch) {
     if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
     if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const size_t N = (size_t)sp->N;
     if (sp->ckpt.size() < (size_t)sp->nchunks) sp->ckpt.resize((size_t)sp->nchunks, nullptr);
     if (!sp->ckpt[ch]) {
@@ -2304,42 +2234,42 @@ extern "C" int mcf_snowplan_checkpoint(mcf_snowplan* sp, int32_t ch) {
         if ((rc = sp->b.alloc((void**)&sp->ckpt[ch], (int64_t)N * 24))) return rc;
     }
     char* c = sp->ckpt[ch];
-    S_TRY(hipMemcpyAsync(c, sp->d_isnowdc, N * 8, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(c + N * 8, sp->d_dtms, N * 8, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(c + N * 16, sp->d_ac, N * 4, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(c + N * 20, sp->d_ag, N * 4, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(c, sp->d_isnowdc, N * 8, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(c + N * 8, sp->d_dtms, N * 8, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(c + N * 16, sp->d_ac, N * 4, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(c + N * 20, sp->d_ag, N * 4, hipMemcpyDeviceToDevice, nullptr));
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_restore(mcf_snowplan* sp, int32_t ch) {
     if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
     if (ch < 0 || (size_t)ch >= sp->ckpt.size() || !sp->ckpt[ch])
         return mcf::api_fail(MCF_ERR_STATE, "snow plan: no checkpoint of this chunk (mcf_snowplan_checkpoint in the first pass)");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const size_t N = (size_t)sp->N;
     const char* c = sp->ckpt[ch];
-    S_TRY(hipMemcpyAsync(sp->d_isnowdc, c, N * 8, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(sp->d_dtms, c + N * 8, N * 8, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(sp->d_ac, c + N * 16, N * 4, hipMemcpyDeviceToDevice, nullptr));
-    S_TRY(hipMemcpyAsync(sp->d_ag, c + N * 20, N * 4, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(sp->d_isnowdc, c, N * 8, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(sp->d_dtms, c + N * 8, N * 8, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(sp->d_ac, c + N * 16, N * 4, hipMemcpyDeviceToDevice, nullptr));
+    HIP_TRY(hipMemcpyAsync(sp->d_ag, c + N * 20, N * 4, hipMemcpyDeviceToDevice, nullptr));
     sp->prepared = -1;
     return MCF_OK;
 }
 extern "C" int mcf_snowplan_meand_accumulate(mcf_snowplan* sp, int32_t ch, const int32_t* snowday) {
     if (!sp || !snowday) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     const int ns = std::min(sp->chunk, sp->T - ch * sp->chunk), nd = ns / 24;
     int nsnow = 0;
     for (int d = 0; d < nd; ++d) nsnow += snowday[d] != 0;
     if (ch == 0 || sp->sumD_steps < 0) sp->sumD_steps = 0;
-    if (ch == 0) S_TRY(hipMemset(sp->d_sumD, 0, (size_t)sp->N * 8));
-    if (ch == 0) S_TRY(hipMemset(sp->d_sden_na, 0, (size_t)sp->N * 4));
+    if (ch == 0) HIP_TRY(hipMemset(sp->d_sumD, 0, (size_t)sp->N * 8));
+    if (ch == 0) HIP_TRY(hipMemset(sp->d_sden_na, 0, (size_t)sp->N * 4));
     if (nsnow == 0) return MCF_OK;
     if (!(sp->series_valid & 16u)) return mcf::api_fail(MCF_ERR_STATE, "snow plan: the chunk's snow density series was switched off (mcf_snowplan_set_series)");
-    S_TRY(hipMemcpy(sp->d_daymap, snowday, (size_t)nd * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sp->d_daymap, snowday, (size_t)nd * 4, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_meand_accumulate, dim3((unsigned)((sp->N + 255) / 256)), dim3(256), 0, nullptr, sp->a.sden, sp->a.hgt,
                        sp->N, nd, (const int32_t*)sp->d_daymap, sp->sumD_steps == 0 ? 1 : 0, sp->d_sumD, sp->d_sden_na);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     sp->sumD_steps += (int64_t)nsnow * 24;
     return MCF_OK;
 }
@@ -2357,7 +2287,7 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
     if (ndays * 24 > sp->T) return mcf::api_fail(MCF_ERR_ARG, "micro set-up: more days than the series");
     if (maf && sub->tsteps != sp->T) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: the whole series is expected");
     if (outsel[MCF_OUT_SOILM] && !sub->other.Smax) return mcf::api_fail(MCF_ERR_ARG, "soilm requested but other$Smax is null");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     sp->mb.release_all();
     sp->micro_ready = false;
     // reuse_static: vegetation, terrain and Smax are those of the previous set-up (a year's day list changes, the raster does
@@ -2378,7 +2308,7 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
     }
     sp->sub_of_day.assign(sub_of_day, sub_of_day + ndays);
     sp->micro_af = maf;
-    Bufs& b = sp->mb;
+    mcf::DevOwner& b = sp->mb;
     MicroArgs& a = sp->ma;
     memset(&a, 0, sizeof a);
     a.N = N; a.tsteps = T; a.reqhgt = reqhgt; a.mat = mat; a.zref = sub->other.zref;
@@ -2393,7 +2323,7 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
         a.hor = prev.hor; a.Smax = prev.Smax;
         if (outsel[MCF_OUT_SOILM] && !a.Smax) return mcf::api_fail(MCF_ERR_ARG, "micro set-up: soilm was not part of the static set-up being reused");
     } else {
-        Bufs& b = sp->mbs;       // (shadows the series' buffer set: these uploads outlive the next set-up)
+        mcf::DevOwner& b = sp->mbs;       // (shadows the series' buffer set: these uploads outlive the next set-up)
         UP(a.pai, sub->vegp.pai, N);
         UP(a.hgt, sub->vegp.hgt, N);
         UP(a.leaft, sub->vegp.leaft, N);
@@ -2434,7 +2364,7 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
         ds.obstime.year = yr.data(); ds.obstime.month = mo.data(); ds.obstime.day = dy.data(); ds.obstime.hour = hr.data();
         ds.clim.winddir = wd.data();
         if ((rc = build_step_tables(b, &ds, true, false, false, &a.rows, &a.dates, &a.mxtc1))) return rc;
-        S_TRY(hipDeviceSynchronize());      // (the table kernels have read the host vectors' uploads)
+        HIP_TRY(hipDeviceSynchronize());      // (the table kernels have read the host vectors' uploads)
         // the slabs a chunk's snow days are uploaded into, addressed with the subset series' step numbers (mcf_snowplan_microsnow
         // shifts the bases by the chunk's first subset day)
         const int64_t CN = (int64_t)sp->chunk * N;
@@ -2448,18 +2378,18 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
         if ((rc = b.alloc((void**)&a.hs0, N * (int64_t)std::max(nsub, 1) * 4))) return rc;
         int32_t* d_hs;
         if ((rc = b.alloc((void**)&d_hs, N * 4))) return rc;
-        S_TRY(hipMemset(a.mxtc, 0, (size_t)N * 8));
+        HIP_TRY(hipMemset(a.mxtc, 0, (size_t)N * 8));
         const int cd = sp->chunk / 24;
         for (int d = 0; d < ndays;) {
             if (sub_of_day[d] < 0) { ++d; continue; }
             int e = d;
             while (e < ndays && sub_of_day[e] >= 0 && e - d < cd) ++e;
             const int64_t off = (int64_t)d * 24 * N, n = (int64_t)(e - d) * 24 * N;
-            S_TRY(hipMemcpyAsync(sp->d_micro[0], hm[0] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
-            S_TRY(hipMemcpyAsync(sp->d_micro[1], hm[7] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_micro[0], hm[0] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_micro[1], hm[7] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
             hipLaunchKernelGGL(k_micro_scan, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, (const double*)sp->d_micro[0],
                                (const double*)sp->d_micro[1], N, sub_of_day[d], e - d, a.hgt, a.mxtc, d_hs, a.hs0);
-            S_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             d = e;
         }
     } else {
@@ -2490,10 +2420,10 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
     // meanDsnow of the first pass (mcf_snowplan_meand_accumulate over every chunk)
     hipLaunchKernelGGL(k_meand_finish, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, (const double*)sp->d_sumD,
                        (const int32_t*)sp->d_sden_na, a.hgt, N, (double)std::max<int64_t>(sp->sumD_steps, 1), sp->d_meanD);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     a.meanD = sp->d_meanD;
     memcpy(sp->outsel, outsel, sizeof sp->outsel);
-    S_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     sp->micro_ready = true;
     return MCF_OK;
 }
@@ -2530,7 +2460,7 @@ extern "C" int mcf_snowplan_covered_tiles(mcf_snowplan* sp, mcf_plan* plan, int3
     *n_covered = 0;
     memset(skip_tile, 0, (size_t)n_tiles);
     if (!all_sel) return MCF_OK;           // an output the snow microclimate does not produce stays the solver's everywhere
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     if (!sp->d_tflag || sp->tflag_cap < n_tiles) {
         if ((rc = sp->b.alloc((void**)&sp->d_tflag, n_tiles))) return rc;
         sp->tflag_cap = n_tiles;
@@ -2538,11 +2468,11 @@ extern "C" int mcf_snowplan_covered_tiles(mcf_snowplan* sp, mcf_plan* plan, int3
     const bool k = (size_t)ch < sp->kept.size() && sp->kept[ch].Tc;
     if (!k && !(sp->series_valid & 4u)) return mcf::api_fail(MCF_ERR_STATE, "snow plan: the chunk's totalSWE series was switched off (mcf_snowplan_set_series)");
     const double* swe = k ? sp->kept[ch].sdepc : sp->a.sdepc;
-    S_TRY(hipMemset(sp->d_tflag, 1, (size_t)n_tiles));
+    HIP_TRY(hipMemset(sp->d_tflag, 1, (size_t)n_tiles));
     hipLaunchKernelGGL(k_tiles_covered, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, swe, sp->ma.hgt, N, day * 24, ndays * 24, cpb,
                        sp->d_tflag);
-    S_TRY(hipGetLastError());
-    S_TRY(hipMemcpy(skip_tile, sp->d_tflag, (size_t)n_tiles, hipMemcpyDeviceToHost));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(skip_tile, sp->d_tflag, (size_t)n_tiles, hipMemcpyDeviceToHost));
     int64_t n = 0;
     for (int64_t t = 0; t < n_tiles; ++t) n += skip_tile[t] != 0;
     *n_covered = n;
@@ -2584,7 +2514,7 @@ extern "C" int mcf_snowplan_free_cells(mcf_snowplan* sp, mcf_plan* plan, int32_t
         if (has[v]) { any = true; all_sel = all_sel && sp->outsel[v] != 0; }
     if (!any) return mcf::api_fail(MCF_ERR_STATE, "the solver plan holds no output");
     if (N != sp->N || device != sp->device) return mcf::api_fail(MCF_ERR_ARG, "snow plan and solver plan differ in raster or device");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     if (!sp->d_need || sp->need_cap < N) {
         if ((rc = sp->b.alloc((void**)&sp->d_need, N + 16))) return rc;
         sp->need_cap = N;
@@ -2592,19 +2522,19 @@ extern "C" int mcf_snowplan_free_cells(mcf_snowplan* sp, mcf_plan* plan, int32_t
     *need_cell = sp->d_need;
     unsigned long long* d_count = (unsigned long long*)(sp->d_need + (N + 7) / 8 * 8);
     if (!all_sel) {                        // an output the snow microclimate does not produce stays the solver's everywhere
-        S_TRY(hipMemset(sp->d_need, 1, (size_t)N));
+        HIP_TRY(hipMemset(sp->d_need, 1, (size_t)N));
         *n_need = N;
         return MCF_OK;
     }
     const bool k = (size_t)ch < sp->kept.size() && sp->kept[ch].Tc;
     if (!k && !(sp->series_valid & 4u)) return mcf::api_fail(MCF_ERR_STATE, "snow plan: the chunk's totalSWE series was switched off (mcf_snowplan_set_series)");
     const double* swe = k ? sp->kept[ch].sdepc : sp->a.sdepc;
-    S_TRY(hipMemset(d_count, 0, 8));
+    HIP_TRY(hipMemset(d_count, 0, 8));
     hipLaunchKernelGGL(k_cells_free, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, swe, sp->ma.hgt, N, day * 24, ndays * 24,
                        sp->d_need, d_count);
-    S_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     unsigned long long n = 0;
-    S_TRY(hipMemcpy(&n, d_count, 8, hipMemcpyDeviceToHost));       // (also: the flags are complete)
+    HIP_TRY(hipMemcpy(&n, d_count, 8, hipMemcpyDeviceToHost));       // (also: the flags are complete)
     *n_need = (int64_t)n;
     return MCF_OK;
 }
@@ -2641,15 +2571,15 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
     const int ns = std::min(sp->chunk, sp->T - ch * sp->chunk), nd = ns / 24, day0 = ch * (sp->chunk / 24);
     if (nd > slot_days) return mcf::api_fail(MCF_ERR_ARG, "the ring slot holds fewer days than a snow chunk");
     if (day0 + nd > (int)sp->sub_of_day.size()) return mcf::api_fail(MCF_ERR_ARG, "chunk past the day map of the micro set-up");
-    S_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipSetDevice(sp->device));
     int any = 0;
     for (int d = 0; d < nd; ++d) any |= sp->sub_of_day[day0 + d] >= 0;
     if (!any) return MCF_OK;
     // (the snow kernels run on the null stream, which orders itself against the plan's non-blocking stream only through the
     // explicit waits here: the solver's launches of this chunk first, this kernel before the plan's next use of the slot)
-    S_TRY(hipStreamSynchronize(stream));
-    S_TRY(hipMemcpy(sp->d_daymap, sp->sub_of_day.data() + day0, (size_t)nd * 4, hipMemcpyHostToDevice));
-    S_TRY(hipMemcpy(sp->d_nosnow, nosnowday, (size_t)nd * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(stream));
+    HIP_TRY(hipMemcpy(sp->d_daymap, sp->sub_of_day.data() + day0, (size_t)nd * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sp->d_nosnow, nosnowday, (size_t)nd * 4, hipMemcpyHostToDevice));
     q.m = sp->ma;
     q.m.day0 = 0;
     {   // the chunk's snow series: where pass 1 left them if the chunk was kept, the plan's working buffers otherwise
@@ -2674,7 +2604,7 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
             if (sb < 0) continue;
             if (sub_first < 0) sub_first = sb;
             for (int f = 0; f < 9; ++f)
-                S_TRY(hipMemcpyAsync(sp->d_micro[f] + (int64_t)(sb - sub_first) * 24 * N, sp->h_micro[f] + (int64_t)(day0 + d) * 24 * N,
+                HIP_TRY(hipMemcpyAsync(sp->d_micro[f] + (int64_t)(sb - sub_first) * 24 * N, sp->h_micro[f] + (int64_t)(day0 + d) * 24 * N,
                                      (size_t)24 * N * 8, hipMemcpyHostToDevice, nullptr));
         }
         const int64_t back = (int64_t)sub_first * 24 * N;
@@ -2697,8 +2627,8 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
     else
         hipLaunchKernelGGL(k_microsnow_ring<false>, dim3((unsigned)((N + 63) / 64), (unsigned)nd), dim3(256), 0, nullptr, q, q.m.mstep,
                            q.daymap, q.nosnow);
-    S_TRY(hipGetLastError());
-    S_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
 

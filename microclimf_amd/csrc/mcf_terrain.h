@@ -20,6 +20,7 @@ struct TerrainDev {
 struct TerrainWork {
     void* p[3] = {nullptr, nullptr, nullptr};
     int64_t cap[3] = {0, 0, 0};
+    void release(int slot);
     void release();
 };
 // All launches on the null stream; returns after the device has finished.

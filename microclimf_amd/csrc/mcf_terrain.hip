@@ -24,6 +24,7 @@
 
 #include "../../include/mcf.h"
 #include "mcf_rowblocks.hpp"
+#include "mcf_hiphost.hpp"
 #include "mcf_terrain.h"
 
 namespace {
@@ -259,40 +260,18 @@ void fill_shifts(ShiftTable& t, int ndir) {
     }
 }
 
-#define T_TRY(expr)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            char b_[512];                                                                    \
-            snprintf(b_, sizeof b_, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),   \
-                     __FILE__, __LINE__);                                                    \
-            return mcf::api_fail(e_ == hipErrorOutOfMemory ? MCF_ERR_NOMEM : MCF_ERR_HIP, b_); \
-        }                                                                                    \
-    } while (0)
-
-struct DevBufs {
-    std::vector<void*> p;
-    ~DevBufs() { for (void* q : p) (void)hipFree(q); }
-    int alloc(void** out, int64_t bytes) {
-        if (bytes <= 0) bytes = 8;
-        hipError_t e = hipMalloc(out, (size_t)bytes);
-        if (e != hipSuccess) return mcf::api_fail(MCF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
-        p.push_back(*out);
-        return MCF_OK;
-    }
-};
-
 }  // namespace
 
 // Device-level entry: `t.d_dtm` and every output pointer are device memory.  Used by
 // mcf_precompute_terrain (host arrays) and by the snow driver's 5-day terrain refresh (mcf_snow.hip).
 namespace mcf {
+void TerrainWork::release(int i) {
+    if (p[i]) (void)hipFree(p[i]);
+    p[i] = nullptr;
+    cap[i] = 0;
+}
 void TerrainWork::release() {
-    for (int i = 0; i < 3; ++i) {
-        if (p[i]) (void)hipFree(p[i]);
-        p[i] = nullptr;
-        cap[i] = 0;
-    }
+    for (int i = 0; i < 3; ++i) release(i);
 }
 int terrain_device(const TerrainDev& t, TerrainWork* work) {
     const int64_t rows_total = t.rows_total > 0 ? t.rows_total : t.rows;
@@ -304,17 +283,14 @@ int terrain_device(const TerrainDev& t, TerrainWork* work) {
     g.RB = t.halo_north + t.rows + t.halo_south;
     g.row0 = row0; g.rows_total = rows_total;
     const int64_t N = g.rows * g.cols, NB = g.RB * g.cols;
-    DevBufs db;
+    mcf::DevOwner db;
     int rc;
     // scratch buffer `slot` of at least `bytes`: the caller's workspace if there is one, else released on return
     auto scratch = [&](int slot, void** out, int64_t bytes) -> int {
         if (!work) return db.alloc(out, bytes);
         if (work->cap[slot] < bytes) {
-            if (work->p[slot]) (void)hipFree(work->p[slot]);
-            work->p[slot] = nullptr;
-            work->cap[slot] = 0;
-            hipError_t e = hipMalloc(&work->p[slot], (size_t)bytes);
-            if (e != hipSuccess) return mcf::api_fail(MCF_ERR_NOMEM, std::string("hipMalloc failed: ") + hipGetErrorString(e));
+            work->release(slot);
+            if (const int rca = dev_malloc(&work->p[slot], bytes)) return rca;
             work->cap[slot] = bytes;
         }
         *out = work->p[slot];
@@ -344,7 +320,7 @@ int terrain_device(const TerrainDev& t, TerrainWork* work) {
         } else {
             hipLaunchKernelGGL(k_horizon, dim3(gridN), dim3(256), 0, nullptr, d_Z, g, t24, t.d_hor, t.d_svfa);
         }
-        T_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (want_wsa) {
         ShiftTable t16;
@@ -374,14 +350,14 @@ int terrain_device(const TerrainDev& t, TerrainWork* work) {
         hipLaunchKernelGGL(k_block_mean, dim3((unsigned)((16 * nI * nJ + 255) / 256)), dim3(256), 0, nullptr, d_W, g,
                            s, e0, ne, I0, nI, nJ, d_C);
         hipLaunchKernelGGL(k_resample_blend, dim3(gridN), dim3(256), 0, nullptr, d_C, g, s, I0, nI, nJ, NItot, t.d_wsa);
-        T_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (t.d_slope || t.d_aspect) {
         hipLaunchKernelGGL(k_slope_aspect, dim3(gridN), dim3(256), 0, nullptr, t.d_dtm, g, t.res, t.aspect_na,
                            t.d_slope, t.d_aspect);
-        T_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
-    T_TRY(hipDeviceSynchronize());   // temporaries are released on return
+    HIP_TRY(hipDeviceSynchronize());   // temporaries are released on return
     return MCF_OK;
 }
 }  // namespace mcf
@@ -405,14 +381,14 @@ extern "C" int mcf_precompute_terrain(const mcf_terrain_in* in, const mcf_terrai
         return mcf::api_fail(MCF_ERR_ARG, b);
     }
     if (const int rc = mcf::check_device(device)) return rc;
-    T_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
 
     const int64_t N = in->rows * in->cols, NB = (in->halo_north + in->rows + in->halo_south) * in->cols;
-    DevBufs db;
+    mcf::DevOwner db;
     int rc;
     double* d_dtm;
     if ((rc = db.alloc((void**)&d_dtm, NB * 8))) return rc;
-    T_TRY(hipMemcpy(d_dtm, in->dtm, (size_t)NB * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_dtm, in->dtm, (size_t)NB * 8, hipMemcpyHostToDevice));
     mcf::TerrainDev t;
     memset(&t, 0, sizeof t);
     t.rows = in->rows; t.cols = in->cols; t.halo_north = in->halo_north; t.halo_south = in->halo_south;
@@ -424,11 +400,11 @@ extern "C" int mcf_precompute_terrain(const mcf_terrain_in* in, const mcf_terrai
     if (out->svfa && (rc = db.alloc((void**)&t.d_svfa, N * 8))) return rc;
     if (out->wsa && (rc = db.alloc((void**)&t.d_wsa, N * 8 * 8))) return rc;
     if ((rc = mcf::terrain_device(t))) return rc;
-    if (out->slope) T_TRY(hipMemcpy(out->slope, t.d_slope, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (out->aspect) T_TRY(hipMemcpy(out->aspect, t.d_aspect, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (out->hor) T_TRY(hipMemcpy(out->hor, t.d_hor, (size_t)N * 24 * 8, hipMemcpyDeviceToHost));
-    if (out->svfa) T_TRY(hipMemcpy(out->svfa, t.d_svfa, (size_t)N * 8, hipMemcpyDeviceToHost));
-    if (out->wsa) T_TRY(hipMemcpy(out->wsa, t.d_wsa, (size_t)N * 8 * 8, hipMemcpyDeviceToHost));
+    if (out->slope) HIP_TRY(hipMemcpy(out->slope, t.d_slope, (size_t)N * 8, hipMemcpyDeviceToHost));
+    if (out->aspect) HIP_TRY(hipMemcpy(out->aspect, t.d_aspect, (size_t)N * 8, hipMemcpyDeviceToHost));
+    if (out->hor) HIP_TRY(hipMemcpy(out->hor, t.d_hor, (size_t)N * 24 * 8, hipMemcpyDeviceToHost));
+    if (out->svfa) HIP_TRY(hipMemcpy(out->svfa, t.d_svfa, (size_t)N * 8, hipMemcpyDeviceToHost));
+    if (out->wsa) HIP_TRY(hipMemcpy(out->wsa, t.d_wsa, (size_t)N * 8 * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

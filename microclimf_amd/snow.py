@@ -195,6 +195,23 @@ def gridmicrosnow2(reqhgt, obstime, climdata, snowm, micro, vegp, other, mat, ou
                   device)
 
 
+def _terrain_placeholders(other, R, Cc) -> dict:
+    """`other` with zero planes where it has no terrain: the snow drivers recompute the terrain on the device every chunk"""
+    oth = dict(other)
+    for k, shp in (("slope", (R, Cc)), ("aspect", (R, Cc)), ("skyview", (R, Cc)), ("wsa", (R, Cc, 8)), ("hor", (R, Cc, 24))):
+        oth.setdefault(k, np.zeros(shp))
+    return oth
+
+
+def _driver_out(R, Cc, T):
+    """-> (mcf_snowdriver_out, {name: the F-ordered [R, Cc, T] array it points to}) for the snow model's five series"""
+    out, arrays = _abi.SnowDriverOut(), {}
+    for f in _abi.SNOWDRIVER_OUT:
+        arrays[f] = np.empty((R, Cc, T), dtype=np.float64, order="F")
+        setattr(out, f, arrays[f].ctypes.data_as(_abi.c_double_p))
+    return out, arrays
+
+
 def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *,
                       chunk_steps: int = 120, device: int = 0, devices=None, n_blocks: int = 0) -> dict:
     """The chunk loop of the reference's `.snowmodel1` (R/internal.R:2553-2617) resident on the
@@ -207,26 +224,15 @@ def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
     this one process (include/mcf.h mcf_snowmodel1_multi); equal up to the summation order of the two raster-wide means."""
     lib = _abi.load()
     R, Cc = np.shape(vegp["pai"])
-    oth = dict(other)
-    for k, shp in (("slope", (R, Cc)), ("aspect", (R, Cc)), ("skyview", (R, Cc)), ("wsa", (R, Cc, 8)),
-                   ("hor", (R, Cc, 24))):
-        oth.setdefault(k, np.zeros(shp))          # recomputed on the device every chunk
-    m = marshal_snow(obstime, climdata, vegp, oth, False, pointm=pointm, snowenv=snowenv)
+    m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
     din = _abi.SnowDriverIn()
     din.base = m.inputs
     din.dtm = m.f64(dtm, (R, Cc), "dtm")
     din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
-    out = _abi.SnowDriverOut()
-    arrays = {}
-    for f in _abi.SNOWDRIVER_OUT:
-        a = np.empty((R, Cc, m.tsteps), dtype=np.float64, order="F")
-        arrays[f] = a
-        setattr(out, f, a.ctypes.data_as(_abi.c_double_p))
-    if devices is not None or n_blocks:
-        mu = _abi.Multi()
-        devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-        mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-        _abi.check(lib.mcf_snowmodel1_multi(C.byref(din), C.byref(out), C.byref(mu)))
+    out, arrays = _driver_out(R, Cc, m.tsteps)
+    mu = _abi.multi(devices, n_blocks)
+    if mu:
+        _abi.check(lib.mcf_snowmodel1_multi(C.byref(din), C.byref(out), C.byref(mu[0])))
     else:
         _abi.check(lib.mcf_snowmodel1(C.byref(din), C.byref(out), device))
     return arrays
@@ -235,10 +241,7 @@ def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
 def _driver_in_array(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact, af_wind, wsa_s, chunk_steps):
     """mcf_snowdriver_in for array weather at the raster's resolution (include/mcf.h mcf_snowmodel2)"""
     R, Cc = np.shape(vegp["pai"])
-    oth = dict(other)
-    for k, shp in (("slope", (R, Cc)), ("aspect", (R, Cc)), ("skyview", (R, Cc)), ("wsa", (R, Cc, 8)), ("hor", (R, Cc, 24))):
-        oth.setdefault(k, np.zeros(shp))          # recomputed on the device every chunk
-    m = marshal_snow(obstime, climdata, vegp, oth, True, pointm=pointm, snowenv=snowenv)
+    m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), True, pointm=pointm, snowenv=snowenv)
     din = _abi.SnowDriverIn()
     din.base = m.inputs
     din.dtm = m.f64(dtm, (R, Cc), "dtm")
@@ -257,13 +260,7 @@ def snowmodel2_device(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
     uploaded as the loop reaches them.  Returns `.snowmodel2`'s list minus umu (include/mcf.h mcf_snowmodel2)."""
     lib = _abi.load()
     m, din = _driver_in_array(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact, af_wind, wsa_s, chunk_steps)
-    R, Cc = m.rows, m.cols
-    out = _abi.SnowDriverOut()
-    arrays = {}
-    for f in _abi.SNOWDRIVER_OUT:
-        a = np.empty((R, Cc, m.tsteps), dtype=np.float64, order="F")
-        arrays[f] = a
-        setattr(out, f, a.ctypes.data_as(_abi.c_double_p))
+    out, arrays = _driver_out(m.rows, m.cols, m.tsteps)
     _abi.check(lib.mcf_snowmodel2(C.byref(din), C.byref(out), device))
     return arrays
 
@@ -636,11 +633,7 @@ class SnowPlan:
                  row0=0, rows_total=0, device=0, keep_results=True):
         self._lib = _abi.load()
         R, Cc = np.shape(vegp["pai"])
-        oth = dict(other)
-        for k, shp in (("slope", (R, Cc)), ("aspect", (R, Cc)), ("skyview", (R, Cc)), ("wsa", (R, Cc, 8)),
-                       ("hor", (R, Cc, 24))):
-            oth.setdefault(k, np.zeros(shp))
-        self._m = marshal_snow(obstime, climdata, vegp, oth, False, pointm=pointm, snowenv=snowenv)
+        self._m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
         din = _abi.SnowDriverIn()
         din.base = self._m.inputs
         din.dtm = self._m.f64(dtm, (R, Cc), "dtm")
@@ -651,15 +644,8 @@ class SnowPlan:
         self.device = int(device)
         self.chunks = int(self._lib.mcf_snowplan_chunks(self._p))
         self._chunk_steps = int(chunk_steps) if chunk_steps else 120
-        self._out = _abi.SnowDriverOut()
-        self.result = {}
-        for f in _abi.SNOWDRIVER_OUT:          # keep_results=False: the series stay on the device (no [rows, cols, tsteps] host arrays)
-            if keep_results:
-                a = np.empty((R, Cc, self.tsteps), dtype=np.float64, order="F")
-                self.result[f] = a
-                setattr(self._out, f, a.ctypes.data_as(_abi.c_double_p))
-            else:
-                setattr(self._out, f, None)
+        # keep_results=False: the series stay on the device (null pointers, no [rows, cols, tsteps] host arrays)
+        self._out, self.result = _driver_out(R, Cc, self.tsteps) if keep_results else (_abi.SnowDriverOut(), {})
 
     def close(self):
         if getattr(self, "_p", None) is not None and self._p.value:
@@ -934,23 +920,23 @@ class SnowRun:
            `SnowPlan` / snowmodel1_chunks
     devices / n_blocks: row blocks over several devices from this one process (None: one block on `device`).
     below  reqhgt < 0 (include/mcf.h mcf_snowrun_create_below): the solver streams Tbelowgroundv over the no-snow days, the
-           snow-day model gives Tz and soilm; data.frame weather, one period per handle.  False: reqhgt < 0 is refused."""
+           snow-day model gives Tz and soilm; data.frame weather, one period per handle.  False: reqhgt < 0 is refused.
+    handle False: the inputs are marshalled (`_in`, `_gm`, `_din`) and no library handle is made — for the entries that take them
+           in one call (runmicrosnow1); pass1 / pass2 need the handle."""
 
     def __init__(self, grid: Mapping, snow: Mapping, *, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0,
-                 below: bool = False):
-        self._marshal_only(grid, snow, device, cells_per_block)
-        mu = None
-        if devices is not None or n_blocks:
-            mu = _abi.Multi()
-            self._devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-            mu.n_devices, mu.devices, mu.n_blocks = int(self._devs.size), self._devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
+                 below: bool = False, handle: bool = True):
+        self._p = None
+        self._marshal(grid, snow, device, cells_per_block)
+        if not handle:
+            return
+        mu = _abi.multi(devices, n_blocks)
         self._p = C.c_void_p()
         create = self._lib.mcf_snowrun_create_below if below else self._lib.mcf_snowrun_create
-        _abi.check(create(C.byref(self._in), C.byref(self._gm.options), C.byref(mu) if mu is not None else None,
-                                                C.byref(self._p)))
+        _abi.check(create(C.byref(self._in), C.byref(self._gm.options), C.byref(mu[0]) if mu else None, C.byref(self._p)))
         self.days = int(self._lib.mcf_snowrun_days(self._p))
 
-    def _marshal_only(self, grid: Mapping, snow: Mapping, device: int, cells_per_block: int):
+    def _marshal(self, grid: Mapping, snow: Mapping, device: int, cells_per_block: int):
         from .marshal import alloc_outputs, marshal
         self._lib = _abi.load()
         g = grid
@@ -962,9 +948,7 @@ class SnowRun:
                            g.get("out", (1,) * 10), self.array_weather, device, 0, cells_per_block, g.get("dfsel"))
         self._alloc_outputs = lambda: alloc_outputs(self._gm)
         R, Cc = np.shape(snow["vegp"]["pai"])
-        oth = dict(snow["other"])
-        for k, shp in (("slope", (R, Cc)), ("aspect", (R, Cc)), ("skyview", (R, Cc)), ("wsa", (R, Cc, 8)), ("hor", (R, Cc, 24))):
-            oth.setdefault(k, np.zeros(shp))
+        oth = _terrain_placeholders(snow["other"], R, Cc)
         if self.array_weather:
             self._sm, self._din = _driver_in_array(snow["obstime"], snow["climdata"], snow["pointm"], snow["vegp"], oth,
                                                    snow.get("snowenv", "Alpine"), snow["dtm"], snow["res"], snow.get("tfact", 0.02),
@@ -1016,13 +1000,7 @@ class SnowRun:
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
         sd, nd = np.zeros(self.days, np.int32), np.zeros(self.days, np.int32)
-        so, smod = None, None
-        if want_smod:
-            so, smod = _abi.SnowDriverOut(), {}
-            for f in _abi.SNOWDRIVER_OUT:
-                a = np.empty((self.rows, self.cols, self.tsteps), dtype=np.float64, order="F")
-                smod[f] = a
-                setattr(so, f, a.ctypes.data_as(_abi.c_double_p))
+        so, smod = _driver_out(self.rows, self.cols, self.tsteps) if want_smod else (None, None)
         _abi.check(self._lib.mcf_snowrun_pass1(self._p, C.byref(so) if so is not None else None, sd.ctypes.data_as(_abi.c_int32_p),
                                                nd.ctypes.data_as(_abi.c_int32_p)))
         return (sd, nd, smod) if want_smod else (sd, nd)
@@ -1044,30 +1022,19 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
     """mcf_runmicrosnow1 / mcf_runmicrosnow1_multi: the whole snow run as ONE library call (arguments as `SnowRun`, `micro` as
     `SnowRun.pass2`) -> the merged outputs[, smod].  below: reqhgt < 0 through mcf_runmicrosnow1_below / _below_multi."""
     from .marshal import alloc_outputs
-    with SnowRun.__new__(SnowRun) as run:
-        run._p = None
-        SnowRun._marshal_only(run, grid, snow, device, cells_per_block)
-        mi = None
+    with SnowRun(grid, snow, device=device, cells_per_block=cells_per_block, handle=False) as run:
         if micro is not None:
             run._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], run.array_weather, micro=True)
             run._in.micro = C.pointer(run._mm.inputs)
         run._in.mat = float(mat)
         outs, arrays = alloc_outputs(run._gm)
-        so, smod = None, None
-        if want_smod:
-            so, smod = _abi.SnowDriverOut(), {}
-            for f in _abi.SNOWDRIVER_OUT:
-                a = np.empty((run.rows, run.cols, run.tsteps), dtype=np.float64, order="F")
-                smod[f] = a
-                setattr(so, f, a.ctypes.data_as(_abi.c_double_p))
+        so, smod = _driver_out(run.rows, run.cols, run.tsteps) if want_smod else (None, None)
         sop = C.byref(so) if so is not None else None
         lib = _abi.load()
-        if devices is not None or n_blocks:
-            mu = _abi.Multi()
-            devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-            mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
+        mu = _abi.multi(devices, n_blocks)
+        if mu:
             fn = lib.mcf_runmicrosnow1_below_multi if below else lib.mcf_runmicrosnow1_multi
-            _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(mu), C.byref(outs), sop))
+            _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]), C.byref(outs), sop))
         else:
             fn = lib.mcf_runmicrosnow1_below if below else lib.mcf_runmicrosnow2 if run.array_weather else lib.mcf_runmicrosnow1
             _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(outs), sop))

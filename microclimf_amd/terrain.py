@@ -46,11 +46,9 @@ def precompute_terrain(dtm, res: float, zref: float, *, agg: int = 10, halo_nort
             setattr(tout, k, a.ctypes.data_as(_abi.c_double_p))
         else:
             setattr(tout, k, None)
-    if devices is not None or n_blocks:
-        mu = _abi.Multi()
-        devs = np.ascontiguousarray([] if devices is None else list(devices), dtype=np.int32)
-        mu.n_devices, mu.devices, mu.n_blocks = int(devs.size), devs.ctypes.data_as(_abi.c_int32_p), int(n_blocks)
-        _abi.check(lib.mcf_precompute_terrain_multi(C.byref(tin), C.byref(tout), C.byref(mu)))
+    mu = _abi.multi(devices, n_blocks)
+    if mu:
+        _abi.check(lib.mcf_precompute_terrain_multi(C.byref(tin), C.byref(tout), C.byref(mu[0])))
     else:
         _abi.check(lib.mcf_precompute_terrain(C.byref(tin), C.byref(tout), device))
     return res_arrays

@@ -119,6 +119,49 @@ def test_soil_state_shared_per_day_or_per_lane_gives_the_same_bits(oracle):
     _same(whole, oracle.run_grid(**a))
 
 
+def test_masked_and_gathered_launches_count_their_tile_classes_like_the_plain_one():
+    """The launch counters of every entry that turns tile classes into k_solve launches.  7 x 10 cells in 21-cell tiles: four
+    tiles, the last one partial (7 cells); cell (3, 3) = 24 has an NA twi, so tile 1 alone is in the slow class; day 1 has a NaN
+    forcing step.  After each call, (fast_launches, slow_launches) must have grown by: the plain launch (1, 1); a masked launch
+    with one fast tile skipped (1, 1); with every fast tile skipped (0, 1) — an empty part launches nothing; the gathered
+    launch of three cells, one of them in the slow tile (1, 1); the plain launch of the irregular day (0, 1) — one
+    reference-form launch."""
+    import torch
+    a = synthetic.workload(7, 10, 48, reqhgt=0.05, start_doy=170)
+    a["soilc"]["twi"][3, 3] = np.nan
+    a["climdata"]["lwdown"] = a["climdata"]["lwdown"].copy()
+    a["climdata"]["lwdown"][30] = np.nan      # day 1
+    need = np.zeros((7, 10), bool)
+    need[2, 0] = need[4, 3] = need[6, 9] = True         # cells 2 (tile 0), 25 (tile 1, the slow one), 69 (tile 3, the partial one)
+    flags = torch.from_numpy(np.ascontiguousarray(need.reshape(-1, order="F"), dtype=np.uint8)).to("cuda:0")
+    seen = []
+    with Plan(**a, ring_days=2, ring_slots=2, cells_per_block=21) as p:
+        def step():
+            st = p.dispatch_stats()
+            seen.append((st["fast_launches"], st["slow_launches"]))
+        assert p.n_tiles == 4
+        p.run_days(0, 1, 0)
+        step()
+        st = p.dispatch_stats()
+        assert st["fast_tiles"] == 3 and st["slow_tiles"] == 1 and st["irregular_days"] == 1, st
+        want = {k: p.fetch(0, k, 0, 24).copy() for k in NAMES}
+        p.run_days_masked(0, 1, 1, 0, np.array([1, 0, 0, 0], np.uint8))
+        step()
+        p.run_days_masked(0, 1, 1, 0, np.array([1, 0, 1, 1], np.uint8))
+        step()
+        assert p.run_days_cells(0, 1, 1, 1, flags.data_ptr()) == 3
+        step()
+        got = {k: p.fetch(1, k, 24, 24) for k in NAMES}
+        p.run_days(1, 1, 0)
+        step()
+    grown = [(f1 - f0, s1 - s0) for (f0, s0), (f1, s1) in zip([(0, 0)] + seen[:-1], seen)]
+    print("launch counters (fast, slow) after each call:", seen, "increments:", grown)
+    assert grown == [(1, 1), (1, 1), (0, 1), (1, 1), (0, 1)], grown
+    for k in NAMES:         # the gathered cells have the plain launch's bits
+        assert np.array_equal(got[k][need].view(np.uint64), want[k][need].view(np.uint64)), k
+    assert np.isfinite(want["Tz"][need]).all()
+
+
 # ---- array forcing: no per-step table the host could classify; every lane checks its own forcing values ---------------
 def _solve_af(a, days, **kw):
     with Plan(**a, array_forcing=kw.pop("mode", True), ring_days=days, ring_slots=1, **kw) as p:

@@ -356,9 +356,7 @@ def test_array_weather_below_ground_is_refused():
     from microclimf_amd import _abi
     import ctypes as C
     sw, a, dtm, snow, micro = _case(-0.1, 0.0, 90, rows=10, cols=9, ndays=5)
-    with S.SnowRun.__new__(S.SnowRun) as run:
-        run._p = None
-        S.SnowRun._marshal_only(run, a, snow, 0, 0)
+    with S.SnowRun(a, snow, handle=False) as run:
         run._gm.inputs.array_forcing = 1          # (checked before any array is read)
         run._din.base.array_forcing = 1
         p = C.c_void_p()
