@@ -2247,17 +2247,14 @@ static int for_row_blocks(const mcf_grid_inputs* in_caller, const mcf_options* o
     const auto blocks = row_blocks(in, nb);
     const int nt = (int)std::min<size_t>(devs.size(), (size_t)nb);
     return mcf::run_workers(nt, [&](mcf::Worker& w) {
-        w.guarded([&] {
-            mcf_options o = *opt;
-            o.device = devs[(size_t)w.t];
-            int sharers = 0;
-            for (int d : devs) sharers += d == o.device;
-            for (int b = w.t; b < nb && !w.failed(); b += nt) {
-                const int64_t r0 = blocks[(size_t)b].first, nr = blocks[(size_t)b].second;
-                if (nr <= 0) continue;
-                const int rcb = block_fn(mcf::narrow_rows(*in, r0, nr, pitch), o, r0, &twi_mean, sharers);
-                if (rcb != MCF_OK) { w.fail(rcb); return; }
-            }
+        mcf_options o = *opt;
+        o.device = devs[(size_t)w.t];
+        int sharers = 0;
+        for (int d : devs) sharers += d == o.device;
+        mcf::for_blocks(w, nb, nt, [&](int b) -> int {
+            const int64_t r0 = blocks[(size_t)b].first, nr = blocks[(size_t)b].second;
+            if (nr <= 0) return MCF_OK;
+            return block_fn(mcf::narrow_rows(*in, r0, nr, pitch), o, r0, &twi_mean, sharers);
         });
     });
 }

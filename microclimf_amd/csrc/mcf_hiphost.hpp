@@ -68,18 +68,23 @@ struct DevOwner {
         p.clear();
         bytes = 0;
     }
-    // device copy of a host array of `n` elements
+    // `n` elements of T
     template <class T>
-    int up(const T** dev, const T* host, int64_t n, const char* what) {
+    int make(T** out, int64_t n) { return alloc((void**)out, n * (int64_t)sizeof(T)); }
+    // device copy of a host array of `n` elements: one the device goes on to write ...
+    template <class T>
+    int up_mut(T** dev, const T* host, int64_t n, const char* what) {
         if (!host) return api_fail(MCF_ERR_ARG, std::string("null input: ") + what);
-        void* d;
-        int rc = alloc(&d, n * (int64_t)sizeof(T));
-        if (rc) return rc;
+        T* d;
+        if (const int rc = make(&d, n)) return rc;
         hipError_t e = hipMemcpy(d, host, (size_t)n * sizeof(T), hipMemcpyHostToDevice);
         if (e != hipSuccess) return api_fail(MCF_ERR_HIP, std::string("upload failed: ") + what);
-        *dev = (const T*)d;
+        *dev = d;
         return MCF_OK;
     }
+    // ... and one it only reads
+    template <class T>
+    int up(const T** dev, const T* host, int64_t n, const char* what) { return up_mut(const_cast<T**>(dev), host, n, what); }
 };
 
 // Device -> caller-owned pageable memory.  Results of 64 MiB and more go through the pinned ring + copy threads of

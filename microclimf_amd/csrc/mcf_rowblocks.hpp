@@ -1,6 +1,7 @@
 // mcf_rowblocks.hpp — host only: what the entries that cut one raster into row blocks and drive them with one host thread
 // per device share (the solver and bioclim `_multi` entries in mcf_api.hip, mcf_precompute_terrain_multi, the snow model
-// and the snow run in mcf_snowrun.hip): the device list, the worker pool, row gather / scatter, the solver inputs' block view.
+// and the snow run in mcf_snowrun.hip): the device list, the worker pool and its per-block loop, row gather / scatter, the host copies
+// an input struct is re-pointed at, the solver inputs' block view.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 
 #include <atomic>
 #include <condition_variable>
+#include <deque>
 #include <exception>
 #include <mutex>
 #include <string>
@@ -96,6 +98,24 @@ struct Worker {
     }
 };
 
+// body(b) for worker w's blocks b = w.t, w.t + nt, ... < nb, under guarded(): the first non-zero return is recorded as the
+// worker's failure and ends its loop.  No barrier: the caller places those.
+template <class B>
+void for_blocks(Worker& w, int nb, int nt, B&& body) {
+    w.guarded([&] {
+        for (int b = w.t; b < nb && !w.failed(); b += nt)
+            if (const int rc = body(b)) { w.fail(rc); break; }
+    });
+}
+// What every block reported in the phase before is combined by worker 0 alone, between two barriers (partial sums added in
+// block order: a run is reproducible for a given number of blocks).
+template <class B>
+void reduce_on_first(Worker& w, B&& body) {
+    w.wait();
+    if (w.t == 0) w.guarded(body);
+    w.wait();
+}
+
 // fn(Worker&) on nt workers: worker 0 on the calling thread, the others on threads of their own.  Returns the error of the
 // lowest-numbered failing worker; the calling thread's current device is put back.
 template <class F>
@@ -127,6 +147,30 @@ template <class T>
 void scatter_rows(T* dst, const T* src, int64_t R, int64_t C, int64_t r0, int64_t nr, int64_t layers = 1) {
     for (int64_t lc = 0; lc < C * layers; ++lc) memcpy(dst + r0 + R * lc, src + nr * lc, (size_t)nr * sizeof(T));
 }
+
+// Host copies that an input struct is pointed at — a block's own rows of a raster, the selected days of a series — kept for as
+// long as the struct is used.
+struct HostCopies {
+    std::deque<std::vector<double>> f64;
+    std::deque<std::vector<int32_t>> i32;
+    std::vector<double>& fresh(const double*) { f64.emplace_back(); return f64.back(); }
+    std::vector<int32_t>& fresh(const int32_t*) { i32.emplace_back(); return i32.back(); }
+    template <class T>
+    const T* rows(const T* src, int64_t R, int64_t C, int64_t r0, int64_t nr, int64_t layers) {     // gather_rows
+        std::vector<T>& v = fresh(src);
+        gather_rows(v, src, R, C, r0, nr, layers);
+        return v.data();
+    }
+    // the rows of the selected days out of a whole-series hourly table: day d of `src` becomes day sub_of_day[d] (>= 0) of nsub
+    template <class T>
+    const T* days(const T* src, const int32_t* sub_of_day, int ndays, int nsub) {
+        std::vector<T>& v = fresh(src);
+        v.resize((size_t)nsub * 24);
+        for (int d = 0; d < ndays; ++d)
+            if (sub_of_day[d] >= 0) memcpy(&v[(size_t)sub_of_day[d] * 24], src + (size_t)d * 24, 24 * sizeof(T));
+        return v.data();
+    }
+};
 
 // The block view of the solver's inputs: rows r0 .. r0 + nr of the caller's arrays, read in place through the row pitch.  The
 // array-forcing series are offset only for array_forcing == 1 (coarse forcing keeps its own grid).

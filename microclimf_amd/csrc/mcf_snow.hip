@@ -544,7 +544,7 @@ static_assert((int)MC_HGT == (int)MQ_HGT && (int)MC_PAI == (int)MQ_PAI && (int)M
 // (k_microsnow_cell<true>) and the day's precipitation is staged in LDS, so that a lane finds its hour's clock by walking back
 // through at most 23 LDS values instead of re-reading the series.  The table argument then carries the date rows (DateRow2).
 // The one-shot entries mcf_gridmicrosnow1 / 2 run this kernel too, over a linear [steps][cells] view of their output arrays
-// (RingView with cpb = N: ring_pos(N, cell, hour) = hour N + cell) — the lane-per-(cell, day) kernel k_microsnow<AF> (197-201
+// (RingView with cpb == 0: ring_pos(N, cell, hour) = hour N + cell) — the lane-per-(cell, day) kernel k_microsnow<AF> (197-201
 // VGPRs, two waves per SIMD) is gone.
 template <bool AF>
 __global__ __launch_bounds__(256, AF ? 3 : MCF_MICRORING_WAVES) void k_microsnow_ring(MicroRingArgs q, const void* __restrict__ tbv,
@@ -1147,7 +1147,67 @@ struct Events {   // timing events released on every exit path
     }
 };
 
-#define UP(dst, src, n) do { if ((rc = b.up(&(dst), (src), (n), #src))) return rc; } while (0)
+// ---- the array groups of the snow entries, each listed ONCE: every upload, null check, row gather and copy walks these.
+// f(the caller's pointer — a reference: a block's copy of the inputs is re-pointed through it —, the kernel argument it
+// becomes, ..., the R-side name).  A listing's order is the order in which a null array is reported.
+// gridmodelsnow's rasters.  terrain: given to the one-shot entries, derived on the device per chunk by the snow plan.
+template <class In, class F>
+void each_model_raster(In& in, F&& f) {   // f(pointer, member, layers, terrain, name)
+    f(in.vegp.pai, &ModelArgs::pai, 1, false, "vegp$pai"); f(in.vegp.hgt, &ModelArgs::hgt, 1, false, "vegp$hgt");
+    f(in.vegp.leaft, &ModelArgs::leaft, 1, false, "vegp$leaft"); f(in.vegp.clump, &ModelArgs::clump, 1, false, "vegp$clump");
+    f(in.other.slope, &ModelArgs::slope, 1, true, "other$slope"); f(in.other.aspect, &ModelArgs::aspect, 1, true, "other$aspect");
+    f(in.other.skyview, &ModelArgs::skyview, 1, true, "other$skyview"); f(in.other.wsa, &ModelArgs::wsa, 8, true, "other$wsa");
+    f(in.other.hor, &ModelArgs::hor, 24, true, "other$hor"); f(in.other.isnowdc, &ModelArgs::isnowdc, 1, false, "other$isnowdc");
+    f(in.other.isnowdg, &ModelArgs::isnowdg, 1, false, "other$isnowdg"); f(in.other.isnowac, &ModelArgs::isnowac, 1, false, "other$isnowac");
+    f(in.other.isnowag, &ModelArgs::isnowag, 1, false, "other$isnowag");
+}
+// gridmicrosnow's static rasters.  required = false: Smax, read only where soilm is asked for.
+template <class In, class F>
+void each_micro_raster(In& in, F&& f) {   // f(pointer, member, layers, required, name)
+    f(in.vegp.pai, &MicroArgs::pai, 1, true, "vegp$pai"); f(in.vegp.hgt, &MicroArgs::hgt, 1, true, "vegp$hgt");
+    f(in.vegp.leaft, &MicroArgs::leaft, 1, true, "vegp$leaft"); f(in.vegp.clump, &MicroArgs::clump, 1, true, "vegp$clump");
+    f(in.vegp.paia, &MicroArgs::paia, 1, true, "vegp$paia"); f(in.vegp.leafd, &MicroArgs::leafd, 1, true, "vegp$leafd");
+    f(in.vegp.leafden, &MicroArgs::leafden, 1, true, "vegp$leafden"); f(in.other.slope, &MicroArgs::slope, 1, true, "other$slope");
+    f(in.other.aspect, &MicroArgs::aspect, 1, true, "other$aspect"); f(in.other.skyview, &MicroArgs::skyview, 1, true, "other$skyview");
+    f(in.other.wsa, &MicroArgs::wsa, 8, true, "other$wsa"); f(in.other.hor, &MicroArgs::hor, 24, true, "other$hor");
+    f(in.other.Smax, &MicroArgs::Smax, 1, false, "other$Smax");
+}
+// the time of every step
+template <class In, class F>
+void each_obstime(In& in, F&& f) {   // f(pointer, the step tables' argument, name)
+    f(in.obstime.year, &StepArgs::year, "obstime$year"); f(in.obstime.month, &StepArgs::month, "obstime$month");
+    f(in.obstime.day, &StepArgs::day, "obstime$day"); f(in.obstime.hour, &StepArgs::hour, "obstime$hour");
+}
+// the snow model's thirteen series: [T] with data.frame weather (they go into the step table), [N][T] with array weather
+template <class In, class F>
+void each_model_series(In& in, F&& f) {   // f(pointer, the step tables' argument, the model's, name)
+    using S = StepArgs; using M = ModelArgs;
+    f(in.clim.temp, &S::temp, &M::temp, "climdata$temp"); f(in.clim.relhum, &S::relhum, &M::relhum, "climdata$relhum");
+    f(in.clim.pres, &S::pres, &M::pres, "climdata$pres"); f(in.clim.swdown, &S::swdown, &M::swdown, "climdata$swdown");
+    f(in.clim.difrad, &S::difrad, &M::difrad, "climdata$difrad"); f(in.clim.lwdown, &S::lwdown, &M::lwdown, "climdata$lwdown");
+    f(in.clim.windspeed, &S::windspeed, &M::windspeed, "climdata$windspeed"); f(in.clim.precip, &S::precip, &M::precip, "climdata$precip");
+    f(in.pointm.Gp, &S::Gp, &M::Gp, "pointm$Gp"); f(in.pointm.Tc, &S::Tcp, &M::Tcp, "pointm$Tc");
+    f(in.pointm.RswabsG, &S::RswabsG, &M::RswabsG, "pointm$RswabsG"); f(in.pointm.RlwabsG, &S::RlwabsG, &M::RlwabsG, "pointm$RlwabsG");
+    f(in.pointm.umu, &S::umu, &M::umu, "pointm$umu");
+}
+// gridmicrosnow's nine series, [T] or [N][T], and the wind direction: [T] in either geometry, the step tables' alone (no member)
+constexpr int kMicroSeries = 9;
+template <class In, class F>
+void each_micro_series(In& in, F&& f) {   // f(pointer, member or null, name)
+    f(in.clim.temp, &MicroArgs::temp, "climdata$temp"); f(in.clim.relhum, &MicroArgs::relhum, "climdata$relhum");
+    f(in.clim.pres, &MicroArgs::pres, "climdata$pres"); f(in.clim.swdown, &MicroArgs::swdown, "climdata$swdown");
+    f(in.clim.difrad, &MicroArgs::difrad, "climdata$difrad"); f(in.clim.lwdown, &MicroArgs::lwdown, "climdata$lwdown");
+    f(in.clim.windspeed, &MicroArgs::windspeed, "climdata$windspeed"); f(in.clim.winddir, (const double* MicroArgs::*)nullptr, "climdata$winddir");
+    f(in.clim.precip, &MicroArgs::precip, "climdata$precip"); f(in.clim.umu, &MicroArgs::umu, "climdata$umu");
+}
+// the sites of array weather
+template <class A>
+int up_sites(mcf::DevOwner& b, A& a, const mcf_snow_inputs* in, int64_t N) {
+    if (const int rc = b.up(&a.lats, in->other.lats, N, "other$lats")) return rc;
+    return b.up(&a.lons, in->other.lons, N, "other$lons");
+}
+
+int hours_in_year(int y) { return (y % 4 == 0 && (y % 100 != 0 || y % 400 == 0)) ? 366 * 24 : 365 * 24; }   // cpp:4984
 
 int pick_device(int32_t device) {
     if (const int rc = mcf::check_device(device)) return rc;
@@ -1187,55 +1247,64 @@ int common_checks(const mcf_snow_inputs* in) {
     return MCF_OK;
 }
 
-// fills the time-class device tables shared by both entry points
-int build_step_tables(mcf::DevOwner& b, const mcf_snow_inputs* in, bool af, bool model, bool degrees, const StepRow** rows,
-                      const DateRow2** dates, const double** mxtc1) {
+// the time-class device tables of both entry points: step rows + the series' maximum temperature, or (array weather) date rows
+struct StepTables {
+    const StepRow* rows = nullptr;
+    const DateRow2* dates = nullptr;
+    const double* mxtc1 = nullptr;
+};
+int build_step_tables(mcf::DevOwner& b, const mcf_snow_inputs* in, bool af, bool model, bool degrees, StepTables* tabs) {
     const int T = (int)in->tsteps;
-    int rc;
+    int rc = MCF_OK;
     StepArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.tsteps = T;
-    UP(sa.year, in->obstime.year, T);
-    UP(sa.month, in->obstime.month, T);
-    UP(sa.day, in->obstime.day, T);
-    UP(sa.hour, in->obstime.hour, T);
-    UP(sa.winddir, in->clim.winddir, T);
+    each_obstime(*in, [&](auto* host, auto member, const char* name) { if (!rc) rc = b.up(&(sa.*member), host, T, name); });
+    if (!rc) rc = b.up(&sa.winddir, in->clim.winddir, T, "climdata$winddir");
+    if (rc) return rc;
     sa.lat = in->other.lat; sa.lon = in->other.lon;
     sa.degrees = degrees ? 1 : 0;
     const unsigned grid = (unsigned)((T + 255) / 256);
+    *tabs = StepTables();
     if (af) {
-        if ((rc = b.alloc((void**)&sa.dates, (int64_t)T * sizeof(DateRow2)))) return rc;
+        if ((rc = b.make(&sa.dates, T))) return rc;
         hipLaunchKernelGGL(k_snow_dates, dim3(grid), dim3(256), 0, nullptr, sa);
-        *dates = sa.dates;
-        *rows = nullptr;
-        *mxtc1 = nullptr;
+        tabs->dates = sa.dates;
     } else {
-        UP(sa.temp, in->clim.temp, T);
-        UP(sa.precip, in->clim.precip, T);
-        if (model) {
-            UP(sa.relhum, in->clim.relhum, T);
-            UP(sa.pres, in->clim.pres, T);
-            UP(sa.swdown, in->clim.swdown, T);
-            UP(sa.difrad, in->clim.difrad, T);
-            UP(sa.lwdown, in->clim.lwdown, T);
-            UP(sa.windspeed, in->clim.windspeed, T);
-            UP(sa.Gp, in->pointm.Gp, T);
-            UP(sa.Tcp, in->pointm.Tc, T);
-            UP(sa.RswabsG, in->pointm.RswabsG, T);
-            UP(sa.RlwabsG, in->pointm.RlwabsG, T);
-            UP(sa.umu, in->pointm.umu, T);
-        }
-        if ((rc = b.alloc((void**)&sa.rows, (int64_t)T * sizeof(StepRow)))) return rc;
-        if ((rc = b.alloc((void**)&sa.mxtc, 8))) return rc;
+        // what the albedo scan reads, then (the snow model) the rest of the listing
+        if ((rc = b.up(&sa.temp, in->clim.temp, T, "climdata$temp"))) return rc;
+        if ((rc = b.up(&sa.precip, in->clim.precip, T, "climdata$precip"))) return rc;
+        if (model)
+            each_model_series(*in, [&](auto* host, auto member, auto, const char* name) {
+                if (!rc && !(sa.*member)) rc = b.up(&(sa.*member), host, T, name);
+            });
+        if (rc) return rc;
+        if ((rc = b.make(&sa.rows, T))) return rc;
+        if ((rc = b.make(&sa.mxtc, 1))) return rc;
         hipLaunchKernelGGL(k_snow_steps, dim3(grid), dim3(256), 0, nullptr, sa);
         if (model && T / 24 > 0)
             hipLaunchKernelGGL(k_snow_days, dim3((unsigned)((T / 24 + 63) / 64)), dim3(64), 0, nullptr, sa.rows, T);
         hipLaunchKernelGGL(k_snow_alb, dim3(1), dim3(64), 0, nullptr, sa.rows, sa.precip, sa.temp, T, sa.mxtc);
-        *rows = sa.rows;
-        *dates = nullptr;
-        *mxtc1 = sa.mxtc;
+        tabs->rows = sa.rows;
+        tabs->mxtc1 = sa.mxtc;
     }
     if (hipGetLastError() != hipSuccess) return mcf::api_fail(MCF_ERR_HIP, "snow table kernels failed to launch");
+    return MCF_OK;
+}
+
+// data.frame weather: every step's weather-only terms and the ring kernel's step records, from the series and step rows in `a`
+int build_micro_steps(mcf::DevOwner& b, MicroArgs& a) {
+    const int T = a.tsteps;
+    int rc;
+    MicroMet* mm;
+    if ((rc = b.make(&mm, T))) return rc;
+    hipLaunchKernelGGL(k_micro_steps, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.temp, a.relhum, a.pres, a.mxtc1, T, mm);
+    a.mmet = mm;
+    MicroStep* ms;
+    if ((rc = b.make(&ms, T))) return rc;
+    hipLaunchKernelGGL(k_micro_pack, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.rows, a.mmet, a.temp, a.pres, a.windspeed,
+                       a.swdown, a.difrad, a.lwdown, a.umu, T, ms);
+    a.mstep = ms;
     return MCF_OK;
 }
 
@@ -1257,45 +1326,25 @@ int run_snowmodel(const mcf_snow_inputs* in, mcf_snowmodel_out* out, int32_t dev
     memset(&a, 0, sizeof a);
     a.N = N; a.tsteps = T; a.zref = in->other.zref;
     snow_density_params(in->snowenv, a.sdp);
-    UP(a.pai, in->vegp.pai, N);
-    UP(a.hgt, in->vegp.hgt, N);
-    UP(a.leaft, in->vegp.leaft, N);
-    UP(a.clump, in->vegp.clump, N);
-    UP(a.slope, in->other.slope, N);
-    UP(a.aspect, in->other.aspect, N);
-    UP(a.skyview, in->other.skyview, N);
-    UP(a.wsa, in->other.wsa, 8 * N);
-    UP(a.hor, in->other.hor, 24 * N);
-    UP(a.isnowdc, in->other.isnowdc, N);
-    UP(a.isnowdg, in->other.isnowdg, N);
-    UP(a.isnowac, in->other.isnowac, N);
-    UP(a.isnowag, in->other.isnowag, N);
-    const double* unused = nullptr;
-    if ((rc = build_step_tables(b, in, af, true, !af, &a.rows, &a.dates, &unused))) return rc;
+    each_model_raster(*in, [&](auto* host, auto member, int layers, bool, const char* name) {
+        if (!rc) rc = b.up(&(a.*member), host, layers * N, name);
+    });
+    if (rc) return rc;
+    StepTables tabs;
+    if ((rc = build_step_tables(b, in, af, true, !af, &tabs))) return rc;
+    a.rows = tabs.rows; a.dates = tabs.dates;
     if (af) {
-        UP(a.lats, in->other.lats, N);
-        UP(a.lons, in->other.lons, N);
-        UP(a.temp, in->clim.temp, NT);
-        UP(a.relhum, in->clim.relhum, NT);
-        UP(a.pres, in->clim.pres, NT);
-        UP(a.swdown, in->clim.swdown, NT);
-        UP(a.difrad, in->clim.difrad, NT);
-        UP(a.lwdown, in->clim.lwdown, NT);
-        UP(a.windspeed, in->clim.windspeed, NT);
-        UP(a.precip, in->clim.precip, NT);
-        UP(a.Gp, in->pointm.Gp, NT);
-        UP(a.Tcp, in->pointm.Tc, NT);
-        UP(a.RswabsG, in->pointm.RswabsG, NT);
-        UP(a.RlwabsG, in->pointm.RlwabsG, NT);
-        UP(a.umu, in->pointm.umu, NT);
+        if ((rc = up_sites(b, a, in, N))) return rc;
+        each_model_series(*in, [&](auto* host, auto, auto member, const char* name) { if (!rc) rc = b.up(&(a.*member), host, NT, name); });
+        if (rc) return rc;
     }
     double** dev3[5] = {&a.Tc, &a.Tg, &a.sdepc, &a.sdepg, &a.sden};
     for (int v = 0; v < 5; ++v)
-        if (host3[v] && (rc = b.alloc((void**)dev3[v], NT * 8))) return rc;
+        if (host3[v] && (rc = b.make(dev3[v], NT))) return rc;
     double* host2[4] = {out->agec, out->ageg, out->meltc, out->meltg};
     double** dev2[4] = {&a.agec, &a.ageg, &a.meltc, &a.meltg};
     for (int v = 0; v < 4; ++v)
-        if (host2[v] && (rc = b.alloc((void**)dev2[v], N * 8))) return rc;
+        if (host2[v] && (rc = b.make(dev2[v], N))) return rc;
     const unsigned grid = (unsigned)((N + 255) / 256);
     Events evs;
     const bool timing = getenv("MCF_TIMING") != nullptr;
@@ -1341,51 +1390,33 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
     MicroArgs a;
     memset(&a, 0, sizeof a);
     a.N = N; a.tsteps = T; a.reqhgt = reqhgt; a.mat = mat; a.zref = in->other.zref;
-    const int y0 = in->obstime.year[0];
-    a.hiy = (y0 % 4 == 0 && (y0 % 100 != 0 || y0 % 400 == 0)) ? 366 * 24 : 365 * 24;   // cpp:4984
-    UP(a.pai, in->vegp.pai, N);
-    UP(a.hgt, in->vegp.hgt, N);
-    UP(a.leaft, in->vegp.leaft, N);
-    UP(a.clump, in->vegp.clump, N);
-    UP(a.paia, in->vegp.paia, N);
-    UP(a.leafd, in->vegp.leafd, N);
-    UP(a.leafden, in->vegp.leafden, N);
-    UP(a.slope, in->other.slope, N);
-    UP(a.aspect, in->other.aspect, N);
-    UP(a.skyview, in->other.skyview, N);
-    UP(a.wsa, in->other.wsa, 8 * N);
-    UP(a.hor, in->other.hor, 24 * N);
-    if (outsel[MCF_OUT_SOILM]) UP(a.Smax, in->other.Smax, N);
-    if ((rc = build_step_tables(b, in, af, false, false, &a.rows, &a.dates, &a.mxtc1))) return rc;
+    a.hiy = hours_in_year(in->obstime.year[0]);
+    each_micro_raster(*in, [&](auto* host, auto member, int layers, bool required, const char* name) {
+        if (!rc && (required || outsel[MCF_OUT_SOILM])) rc = b.up(&(a.*member), host, layers * N, name);
+    });
+    if (rc) return rc;
+    StepTables tabs;
+    if ((rc = build_step_tables(b, in, af, false, false, &tabs))) return rc;
+    a.rows = tabs.rows; a.dates = tabs.dates; a.mxtc1 = tabs.mxtc1;
     const int64_t F = af ? NT : T;
+    if (af && (rc = up_sites(b, a, in, N))) return rc;
+    each_micro_series(*in, [&](auto* host, auto member, const char* name) { if (!rc && member) rc = b.up(&(a.*member), host, F, name); });
+    if (!rc) rc = b.up(&a.sTc, sm->Tc, NT, "snowm$Tc");
+    if (!rc) rc = b.up(&a.sTg, sm->Tg, NT, "snowm$Tg");
+    if (!rc) rc = b.up(&a.swe, sm->totalSWE, NT, "snowm$totalSWE");
+    if (!rc) rc = b.up(&a.sdepg, sm->groundsnowdepth, NT, "snowm$groundsnowdepth");
+    if (!rc) rc = b.up(&a.sden, sm->snowden, NT, "snowm$snowden");
+    if (rc) return rc;
+    if ((rc = b.make(&a.meanD, N))) return rc;
     if (af) {
-        UP(a.lats, in->other.lats, N);
-        UP(a.lons, in->other.lons, N);
-    }
-    UP(a.temp, in->clim.temp, F);
-    UP(a.relhum, in->clim.relhum, F);
-    UP(a.pres, in->clim.pres, F);
-    UP(a.swdown, in->clim.swdown, F);
-    UP(a.difrad, in->clim.difrad, F);
-    UP(a.lwdown, in->clim.lwdown, F);
-    UP(a.windspeed, in->clim.windspeed, F);
-    UP(a.precip, in->clim.precip, F);
-    UP(a.umu, in->clim.umu, F);
-    UP(a.sTc, sm->Tc, NT);
-    UP(a.sTg, sm->Tg, NT);
-    UP(a.swe, sm->totalSWE, NT);
-    UP(a.sdepg, sm->groundsnowdepth, NT);
-    UP(a.sden, sm->snowden, NT);
-    if ((rc = b.alloc((void**)&a.meanD, N * 8))) return rc;
-    if (af) {
-        if ((rc = b.alloc((void**)&a.mxtc, N * 8))) return rc;
-        if ((rc = b.alloc((void**)&a.hs0, N * (int64_t)nch * 4))) return rc;
+        if ((rc = b.make(&a.mxtc, N))) return rc;
+        if ((rc = b.make(&a.hs0, N * (int64_t)nch))) return rc;
     }
     // The requested outputs in ONE buffer, NT apart (in/out: each starts as the no-snow solver's field): the linear view the
     // (cell, hour) kernel of the chunk loop writes through (k_microsnow_ring: RingView cpb = 0) — every day a snow day, every
     // snow-free cell-step kept.
     double* outbuf = nullptr;
-    if ((rc = b.alloc((void**)&outbuf, (int64_t)std::max(nsel, 1) * NT * 8))) return rc;
+    if ((rc = b.make(&outbuf, (int64_t)std::max(nsel, 1) * NT))) return rc;
     MicroRingArgs q;
     memset(&q, 0, sizeof q);
     {
@@ -1402,25 +1433,15 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
         q.ring.N = N; q.ring.cpb = 0;
     }
     const unsigned gridN = (unsigned)((N + 255) / 256);
-    if (!af) {
-        MicroMet* mm;
-        if ((rc = b.alloc((void**)&mm, (int64_t)T * sizeof(MicroMet)))) return rc;
-        hipLaunchKernelGGL(k_micro_steps, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.temp, a.relhum, a.pres, a.mxtc1, T, mm);
-        a.mmet = mm;
-        MicroStep* ms;
-        if ((rc = b.alloc((void**)&ms, (int64_t)T * sizeof(MicroStep)))) return rc;
-        hipLaunchKernelGGL(k_micro_pack, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.rows, a.mmet, a.temp, a.pres, a.windspeed,
-                           a.swdown, a.difrad, a.lwdown, a.umu, T, ms);
-        a.mstep = ms;
-    }
+    if (!af && (rc = build_micro_steps(b, a))) return rc;
     if (af) hipLaunchKernelGGL(k_microsnow_cell<true>, dim3(gridN), dim3(256), 0, nullptr, a);
     else hipLaunchKernelGGL(k_microsnow_cell<false>, dim3(gridN), dim3(256), 0, nullptr, a);
     {
         std::vector<int32_t> ident((size_t)nch), ones((size_t)nch, 1);
         for (int d = 0; d < nch; ++d) ident[(size_t)d] = d;
         int32_t *d_map = nullptr, *d_one = nullptr;
-        if ((rc = b.alloc((void**)&d_map, (int64_t)nch * 4))) return rc;
-        if ((rc = b.alloc((void**)&d_one, (int64_t)nch * 4))) return rc;
+        if ((rc = b.make(&d_map, nch))) return rc;
+        if ((rc = b.make(&d_one, nch))) return rc;
         HIP_TRY(hipMemcpy(d_map, ident.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d_one, ones.data(), (size_t)nch * 4, hipMemcpyHostToDevice));
         q.daymap = d_map; q.nosnow = d_one; q.ndays = nch;
@@ -1456,7 +1477,7 @@ struct mcf_snowplan {
     // array weather (`.snowmodel2`'s loop): the caller's thirteen [N][T] series — a chunk's slices go up as the loop reaches it —
     // and the date rows of every step
     bool af = false;
-    const double* h_series[13] = {};      // temp, relhum, pres, swdown, difrad, lwdown, windspeed, precip, Gp, Tc, RswabsG, RlwabsG, umu
+    const double* h_series[13] = {};      // in the order of each_model_series
     double* d_series[13] = {};            // [N][chunk]
     const DateRow2* dates_tab = nullptr;
     const double *d_dtm = nullptr, *d_isnowdg = nullptr;
@@ -1483,8 +1504,8 @@ struct mcf_snowplan {
     double t_terrain = 0, t_model = 0;   // ms, MCF_TIMING
     mcf::TerrainWork twork;              // terrain_device's scratch, kept across the chunks
     // initial hand-over state, for mcf_snowplan_reset (the snow-day microclimate needs a second pass over the series)
-    double* d_isnowdc0 = nullptr;
-    int32_t *d_ac0 = nullptr, *d_ag0 = nullptr;
+    const double* d_isnowdc0 = nullptr;
+    const int32_t *d_ac0 = nullptr, *d_ag0 = nullptr;
     // gridmicrosnow1 inside the chunk loop (mcf_snowplan_micro_*)
     double *d_sumD = nullptr, *d_meanD = nullptr;
     int32_t* d_sden_na = nullptr;        // the subset series' first snow density is NA (cpp:4716)
@@ -1496,8 +1517,9 @@ struct mcf_snowplan {
     // array weather: the caller's whole-series [N][T] arrays of gridmicrosnow2's weather (temp, relhum, pres, swdown, difrad, lwdown,
     // windspeed, precip, umu) — a chunk's snow days go up when the chunk's microclimate runs — and their device slabs [N][chunk]
     bool micro_af = false;
-    const double* h_micro[9] = {};
-    double* d_micro[9] = {};
+    const double* h_micro[kMicroSeries] = {};
+    double* d_micro[kMicroSeries] = {};
+    const double* MicroArgs::* micro_arg[kMicroSeries] = {};      // the kernel argument each slab is
     int32_t outsel[MCF_NOUT] = {};
     std::vector<int32_t> sub_of_day;     // absolute day -> day of the snow-day subset series, or -1
     int32_t *d_daymap = nullptr, *d_nosnow = nullptr;     // [chunk days]
@@ -1564,11 +1586,9 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
         if (row0 != 0 || rows_total != in->rows) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: one block (the whole raster)");
         if (!din->af_wind) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: af_wind (the chunk wind series) is null");
         if (!in->other.lats || !in->other.lons || !in->clim.winddir) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: lats / lons / winddir");
-        const double* need[13] = {in->clim.temp, in->clim.relhum, in->clim.pres, in->clim.swdown, in->clim.difrad, in->clim.lwdown,
-                                  in->clim.windspeed, in->clim.precip, in->pointm.Gp, in->pointm.Tc, in->pointm.RswabsG,
-                                  in->pointm.RlwabsG, in->pointm.umu};
-        for (const double* q : need)
-            if (!q) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: a climate / point-model array is null");
+        bool given = true;
+        each_model_series(*in, [&](auto* host, auto, auto, const char*) { given = given && host; });
+        if (!given) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: a climate / point-model array is null");
     }
     if ((rc = pick_device(device))) return rc;
     mcf_snowplan* sp = new mcf_snowplan();
@@ -1592,71 +1612,57 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
     memset(&a, 0, sizeof a);
     a.N = N; a.zref = sp->zref;
     snow_density_params(in->snowenv, a.sdp);
-    UP(a.pai, in->vegp.pai, N);
-    UP(a.hgt, in->vegp.hgt, N);
-    UP(a.leaft, in->vegp.leaft, N);
-    UP(a.clump, in->vegp.clump, N);
-    UP(sp->d_dtm, din->dtm, N);
-    UP(sp->d_isnowdg, in->other.isnowdg, N);
-    { const double* t; UP(t, in->other.isnowdc, N); sp->d_isnowdc = const_cast<double*>(t); }
-    { const int32_t* t; UP(t, in->other.isnowac, N); sp->d_ac = const_cast<int32_t*>(t); }
-    { const int32_t* t; UP(t, in->other.isnowag, N); sp->d_ag = const_cast<int32_t*>(t); }
-    { const double* t; UP(t, in->other.isnowdc, N); sp->d_isnowdc0 = const_cast<double*>(t); }
-    { const int32_t* t; UP(t, in->other.isnowac, N); sp->d_ac0 = const_cast<int32_t*>(t); }
-    { const int32_t* t; UP(t, in->other.isnowag, N); sp->d_ag0 = const_cast<int32_t*>(t); }
-    if ((rc = b.alloc((void**)&sp->d_sumD, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_meanD, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_sden_na, N * 4))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_daymap, (sp->chunk / 24 + 1) * 4))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_nosnow, (sp->chunk / 24 + 1) * 4))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_dtms, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_slope, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_aspect, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_svf, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_wsa, 8 * N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_hor, 24 * N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_tpic, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_mean2, 16))) return rc;
-    if ((rc = b.alloc((void**)&sp->d_sumws, 2 * kSumParts * 8))) return rc;
+    // the rasters as the caller hands them over (the initial snow state among them: what mcf_snowplan_reset goes back to) ...
+    each_model_raster(*in, [&](auto* host, auto member, int, bool terrain, const char* name) {
+        if (!rc && !terrain) rc = b.up(&(a.*member), host, N, name);
+    });
+    if (!rc) rc = b.up(&sp->d_dtm, din->dtm, N, "dtm");
+    if (rc) return rc;
+    sp->d_isnowdg = a.isnowdg; sp->d_isnowdc0 = a.isnowdc; sp->d_ac0 = a.isnowac; sp->d_ag0 = a.isnowag;
+    // ... and the state's working copies, handed on from chunk to chunk
+    if ((rc = b.up_mut(&sp->d_isnowdc, in->other.isnowdc, N, "other$isnowdc"))) return rc;
+    if ((rc = b.up_mut(&sp->d_ac, in->other.isnowac, N, "other$isnowac"))) return rc;
+    if ((rc = b.up_mut(&sp->d_ag, in->other.isnowag, N, "other$isnowag"))) return rc;
+    a.isnowdc = sp->d_isnowdc; a.isnowac = sp->d_ac; a.isnowag = sp->d_ag;
+    double** const per_cell[] = {&sp->d_sumD, &sp->d_meanD, &sp->d_dtms, &sp->d_slope, &sp->d_aspect, &sp->d_svf, &sp->d_tpic, &a.agec, &a.ageg};
+    for (double** q : per_cell)
+        if ((rc = b.make(q, N))) return rc;
+    if ((rc = b.make(&sp->d_sden_na, N))) return rc;
+    if ((rc = b.make(&sp->d_daymap, sp->chunk / 24 + 1))) return rc;
+    if ((rc = b.make(&sp->d_nosnow, sp->chunk / 24 + 1))) return rc;
+    if ((rc = b.make(&sp->d_wsa, 8 * N))) return rc;
+    if ((rc = b.make(&sp->d_hor, 24 * N))) return rc;
+    if ((rc = b.make(&sp->d_mean2, 2))) return rc;
+    if ((rc = b.make(&sp->d_sumws, 2 * kSumParts))) return rc;
     a.slope = sp->d_slope; a.aspect = sp->d_aspect; a.skyview = sp->d_svf; a.wsa = sp->d_wsa; a.hor = sp->d_hor;
-    a.isnowdc = sp->d_isnowdc; a.isnowdg = sp->d_isnowdg; a.isnowac = sp->d_ac; a.isnowag = sp->d_ag;
     const int64_t CN = (int64_t)sp->chunk * N;
-    const double* mx_unused;
+    StepTables tabs;
     if (af) {
         // gridmodelsnow2 on each chunk: the date rows of every step; the cell's part of the sun position and its albedo clock
         // (restarted at the chunk's first step, as every gridmodelsnow2 call does) are the kernel's
-        const StepRow* rows_unused;
-        if ((rc = build_step_tables(b, in, true, true, false, &rows_unused, &sp->dates_tab, &mx_unused))) return rc;
-        UP(a.lats, in->other.lats, N);
-        UP(a.lons, in->other.lons, N);
-        const double* hs[13] = {in->clim.temp, in->clim.relhum, in->clim.pres, in->clim.swdown, in->clim.difrad, in->clim.lwdown,
-                                in->clim.windspeed, in->clim.precip, in->pointm.Gp, in->pointm.Tc, in->pointm.RswabsG,
-                                in->pointm.RlwabsG, in->pointm.umu};
-        for (int f = 0; f < 13; ++f) {
-            sp->h_series[f] = hs[f];
-            if ((rc = b.alloc((void**)&sp->d_series[f], CN * 8))) return rc;
-        }
-        a.temp = sp->d_series[0]; a.relhum = sp->d_series[1]; a.pres = sp->d_series[2]; a.swdown = sp->d_series[3];
-        a.difrad = sp->d_series[4]; a.lwdown = sp->d_series[5]; a.windspeed = sp->d_series[6]; a.precip = sp->d_series[7];
-        a.Gp = sp->d_series[8]; a.Tcp = sp->d_series[9]; a.RswabsG = sp->d_series[10]; a.RlwabsG = sp->d_series[11];
-        a.umu = sp->d_series[12];
+        if ((rc = build_step_tables(b, in, true, true, false, &tabs))) return rc;
+        sp->dates_tab = tabs.dates;
+        if ((rc = up_sites(b, a, in, N))) return rc;
+        int f = 0;
+        each_model_series(*in, [&](auto* host, auto, auto member, const char*) {
+            sp->h_series[f] = host;
+            if (!rc) rc = b.make(&sp->d_series[f], CN);
+            a.*member = sp->d_series[f++];
+        });
+        if (rc) return rc;
     } else {
-        const DateRow2* dates_unused;
-        if ((rc = build_step_tables(b, in, false, true, true, &sp->rows_tab, &dates_unused, &mx_unused))) return rc;
+        if ((rc = build_step_tables(b, in, false, true, true, &tabs))) return rc;
+        sp->rows_tab = tabs.rows;
         // albedo per chunk (overrides the whole-series scan of build_step_tables)
         const double* d_prec;
-        UP(d_prec, in->clim.precip, T);
+        if ((rc = b.up(&d_prec, in->clim.precip, T, "climdata$precip"))) return rc;
         hipLaunchKernelGGL(k_snow_alb_chunks, dim3((unsigned)((sp->nchunks + 63) / 64)), dim3(64), 0, nullptr,
                            const_cast<StepRow*>(sp->rows_tab), d_prec, T, sp->chunk, sp->nchunks);
     }
-    if ((rc = b.alloc((void**)&a.Tc, CN * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.Tg, CN * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.sdepc, CN * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.sdepg, CN * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.sden, CN * 8))) return rc;
-    if (!sp->af && (rc = b.alloc((void**)&a.tzd, (int64_t)std::max(sp->chunk / 24, 1) * N * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.agec, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&a.ageg, N * 8))) return rc;
+    double** const series[5] = {&a.Tc, &a.Tg, &a.sdepc, &a.sdepg, &a.sden};
+    for (double** q : series)
+        if ((rc = b.make(q, CN))) return rc;
+    if (!sp->af && (rc = b.make(&a.tzd, (int64_t)std::max(sp->chunk / 24, 1) * N))) return rc;
     hipLaunchKernelGGL(k_add_snow, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, sp->d_dtm, sp->d_isnowdg, 1.0,
                        N, sp->d_dtms);   // int:2562
     HIP_TRY(hipGetLastError());
@@ -1721,7 +1727,7 @@ __global__ void k_halo_pack(const double* __restrict__ own, int64_t rows, int64_
 static int ext_room(mcf_snowplan* sp, int64_t n) {
     if (sp->ext_cap < n) {
         int rc;
-        if ((rc = sp->b.alloc((void**)&sp->d_ext, n * 8))) return rc;
+        if ((rc = sp->b.make(&sp->d_ext, n))) return rc;
         sp->ext_cap = n;
     }
     return MCF_OK;
@@ -1777,6 +1783,42 @@ namespace mcf {
 // the halo rows a row block hands mcf_snowplan_prepare_chunk for a chunk of aggregation factor af: at least what
 // prepare_chunk_on below asks for (the terrain stencil's reach, whole af x af blocks of the tpi)
 int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af) { return 100 + 3 * (int64_t)sp->ss + 2 * (int64_t)af; }
+// What the row-block driver (mcf_snowrun.hip) does with the listings above.  The snow model's rasters, its terrain aside: given? ...
+bool model_rasters_given(const mcf_snow_inputs& in) {
+    bool given = true;
+    each_model_raster(in, [&](auto* host, auto, int, bool terrain, const char*) { given = given && (host || terrain); });
+    return given;
+}
+// ... and a block's view of them: no terrain; with `rows`, the block's own rows r0 .. r0 + nr of the R x C rasters
+void model_rasters_of_block(mcf_snowdriver_in& in, HostCopies* rows, int64_t R, int64_t C, int64_t r0, int64_t nr) {
+    each_model_raster(in.base, [&](auto& p, auto, int, bool terrain, const char*) {
+        if (terrain) p = nullptr;
+        else if (rows) p = rows->rows(p, R, C, r0, nr, 1);
+    });
+    if (rows) { in.dtm = rows->rows(in.dtm, R, C, r0, nr, 1); in.base.rows = nr; }
+}
+// the same for gridmicrosnow's static rasters (Smax may be missing) ...
+bool micro_rasters_given(const mcf_snow_inputs& in) {
+    bool given = true;
+    each_micro_raster(in, [&](auto* host, auto, int, bool required, const char*) { given = given && (host || !required); });
+    return given;
+}
+void micro_rasters_of_block(mcf_snow_inputs& in, HostCopies& rows, int64_t R, int64_t C, int64_t r0, int64_t nr) {
+    each_micro_raster(in, [&](auto& p, auto, int layers, bool, const char*) { if (p) p = rows.rows(p, R, C, r0, nr, layers); });
+    in.rows = nr;
+}
+// ... and its weather: the field name of the first series that is null (or nullptr) ...
+const char* micro_series_missing(const mcf_snow_inputs& in) {
+    const char* missing = nullptr;
+    each_micro_series(in, [&](auto* host, auto, const char* name) { if (!host && !missing) missing = strchr(name, '$') + 1; });
+    return missing;
+}
+// ... and `in`'s obstime and wind direction — with `series`, its nine [T] series too — cut down to the days of HostCopies::days
+void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, int ndays, int nsub, HostCopies& keep) {
+    each_obstime(in, [&](auto& p, auto, const char*) { p = keep.days(p, sub_of_day, ndays, nsub); });
+    each_micro_series(in, [&](auto& p, auto member, const char*) { if (series || !member) p = keep.days(p, sub_of_day, ndays, nsub); });
+    in.tsteps = (int64_t)nsub * 24;
+}
 // mcf_snowmodel1 / 2's MCF_TIMING line (tools/snow_rate.py reads it)
 void snowplan_print_timing(const mcf_snowplan* sp) {
     fprintf(stderr, "[mcf] snowmodel1: %d chunks of %d steps, %lld cells: terrain + tpi %.2f ms, gridmodelsnow + "
@@ -1827,7 +1869,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
     bool same = false;
     static const bool always = getenv("MCF_SNOW_TERRAIN_ALWAYS") != nullptr;
     if (!always) {
-        if (!sp->d_zdiff && (rc = sp->b.alloc((void**)&sp->d_zdiff, 4))) return rc;
+        if (!sp->d_zdiff && (rc = sp->b.make(&sp->d_zdiff, 1))) return rc;
         if (sp->d_zlast && sp->zlast_n == zn && sp->zlast_hn == hn && sp->zlast_hs == hs) {
             HIP_TRY(hipMemsetAsync(sp->d_zdiff, 0, 4, nullptr));
             hipLaunchKernelGGL(k_surface_differs, dim3((unsigned)((zn + 255) / 256)), dim3(256), 0, nullptr, d_z, (const double*)sp->d_zlast, zn,
@@ -1845,7 +1887,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
         ++sp->terrain_refreshed;
         if (!always) {
             if (sp->zlast_cap < zn) {
-                if ((rc = sp->b.alloc((void**)&sp->d_zlast, zn * 8))) return rc;
+                if ((rc = sp->b.make(&sp->d_zlast, zn))) return rc;
                 sp->zlast_cap = zn;
             }
             HIP_TRY(hipMemcpyAsync(sp->d_zlast, d_z, (size_t)zn * 8, hipMemcpyDeviceToDevice, nullptr));
@@ -1855,7 +1897,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
     // topographic positioning index (int:2589-2592, 2471-2485)
     if (coarse) {
         if (sp->cm_cap < g.nI * g.nJ) {
-            if ((rc = sp->b.alloc((void**)&sp->d_cm, g.nI * g.nJ * 8))) return rc;
+            if ((rc = sp->b.make(&sp->d_cm, g.nI * g.nJ))) return rc;
             sp->cm_cap = g.nI * g.nJ;
         }
         hipLaunchKernelGGL(k_tpi_coarse, dim3((unsigned)((g.nI * g.nJ + 255) / 256)), dim3(256), 0, nullptr, d_z, g, sp->d_cm);
@@ -1971,13 +2013,13 @@ static int apply3_device(const double* d_a, int64_t N, int64_t tsteps, int fun, 
     int rc;
     mcf::DevOwner b;
     double *d_r, *d_c = nullptr;
-    if ((rc = b.alloc((void**)&d_r, tsteps * 8))) return rc;
-    if (count && (rc = b.alloc((void**)&d_c, tsteps * 8))) return rc;
+    if ((rc = b.make(&d_r, tsteps))) return rc;
+    if (count && (rc = b.make(&d_c, tsteps))) return rc;
     // enough workgroups to keep the memory system busy whatever the ratio of cells to steps
     int parts = (int)std::min<int64_t>(64, std::max<int64_t>(1, N / 16384));
     if (tsteps * parts < 2048) parts = (int)std::min<int64_t>(64, std::max<int64_t>(parts, (2048 + tsteps - 1) / tsteps));
     double* d_ws;
-    if ((rc = b.alloc((void**)&d_ws, tsteps * parts * 16))) return rc;
+    if ((rc = b.make(&d_ws, tsteps * parts * 2))) return rc;
     hipLaunchKernelGGL(k_apply3_part, dim3((unsigned)parts, (unsigned)tsteps), dim3(256), 0, nullptr, d_a, N, fun, parts, d_ws);
     hipLaunchKernelGGL(k_apply3_fin, dim3((unsigned)((tsteps + 255) / 256)), dim3(256), 0, nullptr, d_ws, tsteps, fun, parts, d_r,
                        d_c);
@@ -2001,7 +2043,7 @@ extern "C" int mcf_snowplan_apply3(mcf_snowplan* sp, int32_t chunk, int32_t fun,
         const int pmax = 64;
         if (!sp->d_mm) {
             int rc;
-            if ((rc = sp->b.alloc((void**)&sp->d_mm, (2 * C * pmax * 2 + 4 * C) * 8))) return rc;
+            if ((rc = sp->b.make(&sp->d_mm, 2 * C * pmax * 2 + 4 * C))) return rc;
             sp->mm_host.assign((size_t)(4 * C), 0.0);
         }
         double *ws_max = sp->d_mm, *ws_min = sp->d_mm + C * pmax * 2, *d_r = sp->d_mm + 2 * C * pmax * 2;
@@ -2029,7 +2071,7 @@ extern "C" int mcf_applycpp3(const double* a, int64_t rows, int64_t cols, int64_
     if ((rc = check_room(N * tsteps * 8))) return rc;
     mcf::DevOwner b;
     const double* d_a;
-    UP(d_a, a, N * tsteps);
+    if ((rc = b.up(&d_a, a, N * tsteps, "a"))) return rc;
     return apply3_device(d_a, N, tsteps, (int)fun, result, count);
 }
 
@@ -2048,16 +2090,16 @@ extern "C" int mcf_tpicalc(int64_t rows, int64_t cols, const double* dtm, int32_
     mcf::DevOwner b;
     const double* d_z;
     double *d_t, *d_ws, *d_m2, *d_cm = nullptr;
-    UP(d_z, dtm, N);
-    if ((rc = b.alloc((void**)&d_t, N * 8))) return rc;
-    if ((rc = b.alloc((void**)&d_ws, 2 * kSumParts * 8))) return rc;
-    if ((rc = b.alloc((void**)&d_m2, 16))) return rc;
+    if ((rc = b.up(&d_z, dtm, N, "dtm"))) return rc;
+    if ((rc = b.make(&d_t, N))) return rc;
+    if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
+    if ((rc = b.make(&d_m2, 2))) return rc;
     TpiGeo g;
     g.rows = rows; g.cols = cols; g.RB = rows; g.hn = 0; g.row0 = 0; g.rows_total = rows; g.af = af;
     g.NItot = (rows + af - 1) / af; g.nJ = (cols + af - 1) / af; g.I0 = 0; g.nI = g.NItot;
     const unsigned gridN = (unsigned)((N + 255) / 256);
     if ((double)af < std::min(rows, cols) / 2.0) {
-        if ((rc = b.alloc((void**)&d_cm, g.nI * g.nJ * 8))) return rc;
+        if ((rc = b.make(&d_cm, g.nI * g.nJ))) return rc;
         hipLaunchKernelGGL(k_tpi_coarse, dim3((unsigned)((g.nI * g.nJ + 255) / 256)), dim3(256), 0, nullptr, d_z, g, d_cm);
         hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, nullptr, d_z, g, (const double*)d_cm, 0.0, tfact, d_t);
     } else {
@@ -2128,8 +2170,8 @@ extern "C" int mcf_snowplan_fetch_cells(mcf_snowplan* sp, int32_t what, const in
     int rc;
     int64_t* d_cells;
     double* d_out;
-    if ((rc = tmp.alloc((void**)&d_cells, (int64_t)n * 8))) return rc;
-    if ((rc = tmp.alloc((void**)&d_out, (int64_t)n * depth * 8))) return rc;
+    if ((rc = tmp.make(&d_cells, n))) return rc;
+    if ((rc = tmp.make(&d_out, (int64_t)n * depth))) return rc;
     HIP_TRY(hipMemcpy(d_cells, cells, (size_t)n * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_gather_planes, dim3((unsigned)((n * depth + 255) / 256)), dim3(256), 0, nullptr, src, isrc, sp->N,
                        (const int64_t*)d_cells, n, depth, d_out);
@@ -2231,7 +2273,7 @@ extern "C" int mcf_snowplan_checkpoint(mcf_snowplan* sp, int32_t ch) {
     if (sp->ckpt.size() < (size_t)sp->nchunks) sp->ckpt.resize((size_t)sp->nchunks, nullptr);
     if (!sp->ckpt[ch]) {
         int rc;
-        if ((rc = sp->b.alloc((void**)&sp->ckpt[ch], (int64_t)N * 24))) return rc;
+        if ((rc = sp->b.make(&sp->ckpt[ch], (int64_t)N * 24))) return rc;
     }
     char* c = sp->ckpt[ch];
     HIP_TRY(hipMemcpyAsync(c, sp->d_isnowdc, N * 8, hipMemcpyDeviceToDevice, nullptr));
@@ -2316,68 +2358,52 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
     if (maf)
         for (int d = 0; d < ndays; ++d)
             if (sub_of_day[d] == 0) { y0 = sub->obstime.year[(size_t)d * 24]; break; }
-    a.hiy = (y0 % 4 == 0 && (y0 % 100 != 0 || y0 % 400 == 0)) ? 366 * 24 : 365 * 24;   // cpp:4984
+    a.hiy = hours_in_year(y0);
     if (keep_static) {
-        a.pai = prev.pai; a.hgt = prev.hgt; a.leaft = prev.leaft; a.clump = prev.clump; a.paia = prev.paia; a.leafd = prev.leafd;
-        a.leafden = prev.leafden; a.slope = prev.slope; a.aspect = prev.aspect; a.skyview = prev.skyview; a.wsa = prev.wsa;
-        a.hor = prev.hor; a.Smax = prev.Smax;
+        each_micro_raster(*sub, [&](auto*, auto member, int, bool, const char*) { a.*member = prev.*member; });
         if (outsel[MCF_OUT_SOILM] && !a.Smax) return mcf::api_fail(MCF_ERR_ARG, "micro set-up: soilm was not part of the static set-up being reused");
     } else {
-        mcf::DevOwner& b = sp->mbs;       // (shadows the series' buffer set: these uploads outlive the next set-up)
-        UP(a.pai, sub->vegp.pai, N);
-        UP(a.hgt, sub->vegp.hgt, N);
-        UP(a.leaft, sub->vegp.leaft, N);
-        UP(a.clump, sub->vegp.clump, N);
-        UP(a.paia, sub->vegp.paia, N);
-        UP(a.leafd, sub->vegp.leafd, N);
-        UP(a.leafden, sub->vegp.leafden, N);
-        UP(a.slope, sub->other.slope, N);
-        UP(a.aspect, sub->other.aspect, N);
-        UP(a.skyview, sub->other.skyview, N);
-        UP(a.wsa, sub->other.wsa, 8 * N);
-        UP(a.hor, sub->other.hor, 24 * N);
-        if (sub->other.Smax) UP(a.Smax, sub->other.Smax, N);
+        // (into the static buffer set: these uploads outlive the next set-up)
+        each_micro_raster(*sub, [&](auto* host, auto member, int layers, bool required, const char* name) {
+            if (!rc && (required || host)) rc = sp->mbs.up(&(a.*member), host, layers * N, name);
+        });
+        if (rc) return rc;
         sp->micro_static = true;
     }
     if (maf) {
         if (T == 0) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: no snow day");
-        const double* hm[9] = {sub->clim.temp, sub->clim.relhum, sub->clim.pres, sub->clim.swdown, sub->clim.difrad, sub->clim.lwdown,
-                               sub->clim.windspeed, sub->clim.precip, sub->clim.umu};
-        for (const double* q : hm)
-            if (!q) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: a weather array is null");
+        bool given = true;
+        each_micro_series(*sub, [&](auto* host, auto member, const char*) { given = given && (host || !member); });
+        if (!given) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: a weather array is null");
         if (!sub->other.lats || !sub->other.lons || !sub->clim.winddir) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: lats / lons / winddir");
-        UP(a.lats, sub->other.lats, N);
-        UP(a.lons, sub->other.lons, N);
+        if ((rc = up_sites(b, a, sub, N))) return rc;
         // the subset series' date rows (obstime and wind direction of the snow days)
-        std::vector<int32_t> yr((size_t)T), mo((size_t)T), dy((size_t)T);
-        std::vector<double> hr((size_t)T), wd((size_t)T);
-        for (int d = 0; d < ndays; ++d) {
-            if (sub_of_day[d] < 0) continue;
-            for (int hh = 0; hh < 24; ++hh) {
-                const size_t q = (size_t)sub_of_day[d] * 24 + hh, w = (size_t)d * 24 + hh;
-                yr[q] = sub->obstime.year[w]; mo[q] = sub->obstime.month[w]; dy[q] = sub->obstime.day[w]; hr[q] = sub->obstime.hour[w];
-                wd[q] = sub->clim.winddir[w];
-            }
-        }
+        mcf::HostCopies rows;
         mcf_snow_inputs ds = *sub;
-        ds.tsteps = T;
-        ds.obstime.year = yr.data(); ds.obstime.month = mo.data(); ds.obstime.day = dy.data(); ds.obstime.hour = hr.data();
-        ds.clim.winddir = wd.data();
-        if ((rc = build_step_tables(b, &ds, true, false, false, &a.rows, &a.dates, &a.mxtc1))) return rc;
+        mcf::subset_days(ds, false, sub_of_day, ndays, nsub, rows);
+        StepTables tabs;
+        if ((rc = build_step_tables(b, &ds, true, false, false, &tabs))) return rc;
+        a.rows = tabs.rows; a.dates = tabs.dates; a.mxtc1 = tabs.mxtc1;
         HIP_TRY(hipDeviceSynchronize());      // (the table kernels have read the host vectors' uploads)
         // the slabs a chunk's snow days are uploaded into, addressed with the subset series' step numbers (mcf_snowplan_microsnow
         // shifts the bases by the chunk's first subset day)
         const int64_t CN = (int64_t)sp->chunk * N;
-        for (int f = 0; f < 9; ++f) {
-            sp->h_micro[f] = hm[f];
-            if ((rc = b.alloc((void**)&sp->d_micro[f], CN * 8))) return rc;
-        }
+        int f = 0;
+        each_micro_series(*sub, [&](auto* host, auto member, const char*) {
+            if (!member) return;
+            sp->h_micro[f] = host;
+            sp->micro_arg[f] = member;
+            if (!rc) rc = b.make(&sp->d_micro[f], CN);
+            ++f;
+        });
+        if (rc) return rc;
+        const double *h_temp = sub->clim.temp, *h_precip = sub->clim.precip;
         // mxtc and the albedo clock at every subset day's start: the series' temperature and precipitation streamed once, a run of
         // consecutive snow days at a time through the first two slabs
-        if ((rc = b.alloc((void**)&a.mxtc, N * 8))) return rc;
-        if ((rc = b.alloc((void**)&a.hs0, N * (int64_t)std::max(nsub, 1) * 4))) return rc;
+        if ((rc = b.make(&a.mxtc, N))) return rc;
+        if ((rc = b.make(&a.hs0, N * (int64_t)std::max(nsub, 1)))) return rc;
         int32_t* d_hs;
-        if ((rc = b.alloc((void**)&d_hs, N * 4))) return rc;
+        if ((rc = b.make(&d_hs, N))) return rc;
         HIP_TRY(hipMemset(a.mxtc, 0, (size_t)N * 8));
         const int cd = sp->chunk / 24;
         for (int d = 0; d < ndays;) {
@@ -2385,35 +2411,20 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
             int e = d;
             while (e < ndays && sub_of_day[e] >= 0 && e - d < cd) ++e;
             const int64_t off = (int64_t)d * 24 * N, n = (int64_t)(e - d) * 24 * N;
-            HIP_TRY(hipMemcpyAsync(sp->d_micro[0], hm[0] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(sp->d_micro[1], hm[7] + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_micro[0], h_temp + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            HIP_TRY(hipMemcpyAsync(sp->d_micro[1], h_precip + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
             hipLaunchKernelGGL(k_micro_scan, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, (const double*)sp->d_micro[0],
                                (const double*)sp->d_micro[1], N, sub_of_day[d], e - d, a.hgt, a.mxtc, d_hs, a.hs0);
             HIP_TRY(hipGetLastError());
             d = e;
         }
     } else {
-    if ((rc = build_step_tables(b, sub, false, false, false, &a.rows, &a.dates, &a.mxtc1))) return rc;
-    UP(a.temp, sub->clim.temp, T);
-    UP(a.relhum, sub->clim.relhum, T);
-    UP(a.pres, sub->clim.pres, T);
-    UP(a.swdown, sub->clim.swdown, T);
-    UP(a.difrad, sub->clim.difrad, T);
-    UP(a.lwdown, sub->clim.lwdown, T);
-    UP(a.windspeed, sub->clim.windspeed, T);
-    UP(a.precip, sub->clim.precip, T);
-    UP(a.umu, sub->clim.umu, T);
-    }
-    if (!maf) {
-        MicroMet* mm;
-        if ((rc = b.alloc((void**)&mm, (int64_t)T * sizeof(MicroMet)))) return rc;
-        hipLaunchKernelGGL(k_micro_steps, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.temp, a.relhum, a.pres, a.mxtc1, T, mm);
-        a.mmet = mm;
-        MicroStep* ms;
-        if ((rc = b.alloc((void**)&ms, (int64_t)T * sizeof(MicroStep)))) return rc;
-        hipLaunchKernelGGL(k_micro_pack, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, nullptr, a.rows, a.mmet, a.temp, a.pres, a.windspeed,
-                           a.swdown, a.difrad, a.lwdown, a.umu, T, ms);
-        a.mstep = ms;
+        StepTables tabs;
+        if ((rc = build_step_tables(b, sub, false, false, false, &tabs))) return rc;
+        a.rows = tabs.rows; a.dates = tabs.dates; a.mxtc1 = tabs.mxtc1;
+        each_micro_series(*sub, [&](auto* host, auto member, const char* name) { if (!rc && member) rc = b.up(&(a.*member), host, T, name); });
+        if (!rc) rc = build_micro_steps(b, a);
+        if (rc) return rc;
     }
     // the chunk's snow series, where mcf_snowplan_run_chunk leaves them (sdepc holds totalSWE after the redistribution)
     a.sTc = sp->a.Tc; a.sTg = sp->a.Tg; a.swe = sp->a.sdepc; a.sdepg = sp->a.sdepg; a.sden = sp->a.sden;
@@ -2462,7 +2473,7 @@ extern "C" int mcf_snowplan_covered_tiles(mcf_snowplan* sp, mcf_plan* plan, int3
     if (!all_sel) return MCF_OK;           // an output the snow microclimate does not produce stays the solver's everywhere
     HIP_TRY(hipSetDevice(sp->device));
     if (!sp->d_tflag || sp->tflag_cap < n_tiles) {
-        if ((rc = sp->b.alloc((void**)&sp->d_tflag, n_tiles))) return rc;
+        if ((rc = sp->b.make(&sp->d_tflag, n_tiles))) return rc;
         sp->tflag_cap = n_tiles;
     }
     const bool k = (size_t)ch < sp->kept.size() && sp->kept[ch].Tc;
@@ -2516,7 +2527,7 @@ extern "C" int mcf_snowplan_free_cells(mcf_snowplan* sp, mcf_plan* plan, int32_t
     if (N != sp->N || device != sp->device) return mcf::api_fail(MCF_ERR_ARG, "snow plan and solver plan differ in raster or device");
     HIP_TRY(hipSetDevice(sp->device));
     if (!sp->d_need || sp->need_cap < N) {
-        if ((rc = sp->b.alloc((void**)&sp->d_need, N + 16))) return rc;
+        if ((rc = sp->b.make(&sp->d_need, N + 16))) return rc;
         sp->need_cap = N;
     }
     *need_cell = sp->d_need;
@@ -2603,14 +2614,12 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
             const int sb = sp->sub_of_day[day0 + d];
             if (sb < 0) continue;
             if (sub_first < 0) sub_first = sb;
-            for (int f = 0; f < 9; ++f)
+            for (int f = 0; f < kMicroSeries; ++f)
                 HIP_TRY(hipMemcpyAsync(sp->d_micro[f] + (int64_t)(sb - sub_first) * 24 * N, sp->h_micro[f] + (int64_t)(day0 + d) * 24 * N,
                                      (size_t)24 * N * 8, hipMemcpyHostToDevice, nullptr));
         }
         const int64_t back = (int64_t)sub_first * 24 * N;
-        q.m.temp = sp->d_micro[0] - back; q.m.relhum = sp->d_micro[1] - back; q.m.pres = sp->d_micro[2] - back;
-        q.m.swdown = sp->d_micro[3] - back; q.m.difrad = sp->d_micro[4] - back; q.m.lwdown = sp->d_micro[5] - back;
-        q.m.windspeed = sp->d_micro[6] - back; q.m.precip = sp->d_micro[7] - back; q.m.umu = sp->d_micro[8] - back;
+        for (int f = 0; f < kMicroSeries; ++f) q.m.*sp->micro_arg[f] = sp->d_micro[f] - back;
         hipLaunchKernelGGL(k_microsnow_ring<true>, dim3((unsigned)((N + 63) / 64), (unsigned)nd), dim3(256), 0, nullptr, q, (const void*)q.m.dates,
                            q.daymap, q.nosnow);
     } else if (q.ring.cpb == 21 && !old_shape) {

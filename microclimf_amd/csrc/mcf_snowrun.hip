@@ -44,9 +44,16 @@
 #include "../../include/mcf.h"
 #include "mcf_rowblocks.hpp"
 
-namespace mcf {
-int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);   // mcf_snow.hip
+namespace mcf {   // mcf_snow.hip
+int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);
 void snowplan_print_timing(const mcf_snowplan* sp);
+// (over the listings of the snow entries' array groups, kept there next to the kernels' argument structs)
+bool model_rasters_given(const mcf_snow_inputs& in);
+void model_rasters_of_block(mcf_snowdriver_in& in, HostCopies* rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
+bool micro_rasters_given(const mcf_snow_inputs& in);
+void micro_rasters_of_block(mcf_snow_inputs& in, HostCopies& rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
+const char* micro_series_missing(const mcf_snow_inputs& in);
+void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, int ndays, int nsub, HostCopies& keep);
 }
 
 namespace {
@@ -57,9 +64,9 @@ using mcf::Worker;
 struct Block {
     int64_t r0 = 0, nr = 0;
     int device = 0;
-    // the block's rows of the snow model's rasters (the snow plan uploads from dense arrays)
-    std::vector<double> pai, hgt, leaft, clump, dc, dg, dtm, ext;
-    std::vector<int32_t> ac, ag;
+    // the block's rows of the snow model's rasters (the snow plan uploads from dense arrays) and, pass 2, of gridmicrosnow1's
+    mcf::HostCopies model_rows, micro_rows;
+    std::vector<double> ext;                   // its rows (+ halos) of the current chunk's snow surface
     mcf_snowplan* sp = nullptr;
     mcf_plan* plan = nullptr;
     double s = 0, n = 0, ts = 0, tn = 0, twi_s = 0;
@@ -67,8 +74,7 @@ struct Block {
     std::vector<double> mx, cmx, mn, cmn;      // applycpp3 of the chunk just run
     std::vector<char> kept;                    // per chunk: its series stayed on the device
     mcf_grid_inputs gsub{};                    // the block's view of the solver's inputs (array weather: a chunk's forcing is uploaded from it)
-    // pass 2: the block's rows of gridmicrosnow1's static rasters
-    std::vector<double> m_pai, m_hgt, m_leaft, m_clump, m_paia, m_leafd, m_leafden, m_slope, m_aspect, m_svf, m_wsa, m_hor, m_smax;
+    std::vector<uint8_t> skip;                 // pass 2: the tiles a run of days leaves out
 };
 
 // The raster in nb contiguous row blocks, block b (rows R*b/nb ..) on devs[b % nt] driven by worker b % nt, each with its snow
@@ -87,6 +93,9 @@ struct SnowBlocks {
         blocks.resize((size_t)nb);
         if (nb > 1) surface.assign((size_t)(R * C), 0.0);
     }
+    // body(Block&) -> status for the calling worker's blocks (mcf::for_blocks)
+    template <class B>
+    void each_block(Worker& w, B&& body) { mcf::for_blocks(w, nb, nt, [&](int b) { return body(blocks[(size_t)b]); }); }
     ~SnowBlocks() {
         mcf::RestoreDevice restore;
         for (Block& k : blocks) {
@@ -104,22 +113,7 @@ int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& s
     k.device = device;
     k.r0 = R * b / sb.nb; k.nr = R * (b + 1) / sb.nb - k.r0;
     mcf_snowdriver_in bi = snow;
-    if (sb.nb > 1) {
-        const mcf_snow_vegp& vg = snow.base.vegp;
-        const mcf_snow_other& ot = snow.base.other;
-        mcf::gather_rows(k.pai, vg.pai, R, C, k.r0, k.nr); mcf::gather_rows(k.hgt, vg.hgt, R, C, k.r0, k.nr);
-        mcf::gather_rows(k.leaft, vg.leaft, R, C, k.r0, k.nr); mcf::gather_rows(k.clump, vg.clump, R, C, k.r0, k.nr);
-        mcf::gather_rows(k.dc, ot.isnowdc, R, C, k.r0, k.nr); mcf::gather_rows(k.dg, ot.isnowdg, R, C, k.r0, k.nr);
-        mcf::gather_rows(k.ac, ot.isnowac, R, C, k.r0, k.nr); mcf::gather_rows(k.ag, ot.isnowag, R, C, k.r0, k.nr);
-        mcf::gather_rows(k.dtm, snow.dtm, R, C, k.r0, k.nr);
-        bi.base.rows = k.nr;
-        bi.base.vegp.pai = k.pai.data(); bi.base.vegp.hgt = k.hgt.data(); bi.base.vegp.leaft = k.leaft.data();
-        bi.base.vegp.clump = k.clump.data();
-        bi.base.other.isnowdc = k.dc.data(); bi.base.other.isnowdg = k.dg.data();
-        bi.base.other.isnowac = k.ac.data(); bi.base.other.isnowag = k.ag.data();
-        bi.dtm = k.dtm.data();
-    }
-    bi.base.other.slope = bi.base.other.aspect = bi.base.other.skyview = bi.base.other.wsa = bi.base.other.hor = nullptr;
+    mcf::model_rasters_of_block(bi, sb.nb > 1 ? &k.model_rows : nullptr, R, C, k.r0, k.nr);
     return mcf_snowplan_create(&bi, k.r0, R, k.device, &k.sp);
 }
 
@@ -135,7 +129,7 @@ int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& s
 // out (optional): the caller's whole-series snow arrays — a block's chunk goes straight into its rows through the row pitch; the
 // steps no chunk covers become NA behind the last chunk.
 void snow_chunk(SnowBlocks& sb, Worker& w, int ch, const mcf_snowdriver_out* out) {
-    const int nb = sb.nb, nt = sb.nt;
+    const int nb = sb.nb;
     const int64_t R = sb.R, C = sb.C;
     auto block_out = [&](const Block& k) {
         mcf_snowdriver_out bo{};
@@ -161,51 +155,35 @@ void snow_chunk(SnowBlocks& sb, Worker& w, int ch, const mcf_snowdriver_out* out
             if (rc) w.fail(rc);
         });
     } else {
-        w.guarded([&] {                                       // ---- phase 1: the surface
-            for (int b = w.t; b < nb && !w.failed(); b += nt) {
-                Block& k = sb.blocks[(size_t)b];
-                k.ext.resize((size_t)(k.nr * C));
-                int rc = mcf_snowplan_surface(k.sp, k.ext.data());
-                if (!rc) rc = mcf_snowplan_surface_partial(k.sp, &k.s, &k.n);
-                if (rc) { w.fail(rc); break; }
-                mcf::scatter_rows(sb.surface.data(), k.ext.data(), R, C, k.r0, k.nr);
-            }
+        sb.each_block(w, [&](Block& k) -> int {              // ---- phase 1: the surface
+            k.ext.resize((size_t)(k.nr * C));
+            int rc = mcf_snowplan_surface(k.sp, k.ext.data());
+            if (!rc) rc = mcf_snowplan_surface_partial(k.sp, &k.s, &k.n);
+            if (!rc) mcf::scatter_rows(sb.surface.data(), k.ext.data(), R, C, k.r0, k.nr);
+            return rc;
         });
-        w.wait();
-        if (w.t == 0 && !w.failed()) {
+        mcf::reduce_on_first(w, [&] {
             double s = 0, n = 0;
             for (const Block& k : sb.blocks) { s += k.s; n += k.n; }
             sb.smean = s / n;
-        }
-        w.wait();
-        w.guarded([&] {                                       // ---- phase 2: halos, terrain, tpi
-            for (int b = w.t; b < nb && !w.failed(); b += nt) {
-                Block& k = sb.blocks[(size_t)b];
-                int32_t af = 1;
-                int rc = mcf_snowplan_chunk_af(k.sp, ch, &af);
-                if (rc) { w.fail(rc); break; }
-                // what prepare_chunk asks for at most, or every row up to the raster edge
-                const int64_t want = mcf::snowplan_halo_rows(k.sp, af);
-                const int64_t hn = std::min(want, k.r0), hs = std::min(want, R - k.r0 - k.nr), RB = hn + k.nr + hs;
-                mcf::gather_rows(k.ext, sb.surface.data(), R, C, k.r0 - hn, RB);
-                rc = mcf_snowplan_prepare_chunk(k.sp, ch, (hn || hs) ? k.ext.data() : nullptr, (int32_t)hn, (int32_t)hs, sb.smean, &k.ts, &k.tn);
-                if (rc) { w.fail(rc); break; }
-            }
         });
-        w.wait();
-        if (w.t == 0 && !w.failed()) {
+        sb.each_block(w, [&](Block& k) -> int {              // ---- phase 2: halos, terrain, tpi
+            int32_t af = 1;
+            if (const int rc = mcf_snowplan_chunk_af(k.sp, ch, &af)) return rc;
+            // what prepare_chunk asks for at most, or every row up to the raster edge
+            const int64_t want = mcf::snowplan_halo_rows(k.sp, af);
+            const int64_t hn = std::min(want, k.r0), hs = std::min(want, R - k.r0 - k.nr), RB = hn + k.nr + hs;
+            mcf::gather_rows(k.ext, sb.surface.data(), R, C, k.r0 - hn, RB);
+            return mcf_snowplan_prepare_chunk(k.sp, ch, (hn || hs) ? k.ext.data() : nullptr, (int32_t)hn, (int32_t)hs, sb.smean, &k.ts, &k.tn);
+        });
+        mcf::reduce_on_first(w, [&] {
             double s = 0, n = 0;
             for (const Block& k : sb.blocks) { s += k.ts; n += k.tn; }
             sb.tmean = s / n;
-        }
-        w.wait();
-        w.guarded([&] {                                       // ---- phase 3: the chunk
-            for (int b = w.t; b < nb && !w.failed(); b += nt) {
-                Block& k = sb.blocks[(size_t)b];
-                const mcf_snowdriver_out bo = block_out(k);
-                const int rc = mcf_snowplan_run_chunk_pitched(k.sp, ch, sb.tmean, &bo, R);
-                if (rc) { w.fail(rc); break; }
-            }
+        });
+        sb.each_block(w, [&](Block& k) -> int {              // ---- phase 3: the chunk
+            const mcf_snowdriver_out bo = block_out(k);
+            return mcf_snowplan_run_chunk_pitched(k.sp, ch, sb.tmean, &bo, R);
         });
     }
     w.wait();
@@ -281,8 +259,7 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
     if (sb.rows != g.rows || sb.cols != g.cols || sb.tsteps != g.tsteps)
         return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: the solver's and the snow model's inputs differ in shape");
     if (g.row_pitch > 0 && g.row_pitch != g.rows) return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1 takes dense rasters");
-    if (!in->snow->dtm || !sb.vegp.pai || !sb.vegp.hgt || !sb.vegp.leaft || !sb.vegp.clump || !sb.other.isnowdc || !sb.other.isnowdg ||
-        !sb.other.isnowac || !sb.other.isnowag)
+    if (!in->snow->dtm || !mcf::model_rasters_given(sb))
         return mcf::api_fail(MCF_ERR_ARG, "null input: a snow-model raster");
     if (!g.clim.tc) return mcf::api_fail(MCF_ERR_ARG, "null input: climdata$temp");
     if (in->snow->chunk_steps != 0 && in->snow->chunk_steps % 24)
@@ -316,32 +293,27 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
         if (const char* e = getenv("MCF_SNOW_KEEP_RESERVE_GB")) h->keep_reserve = (int64_t)(atof(e) * 1073741824.0);
         h->keep = getenv("MCF_SNOWRUN_KEEP") != nullptr;
         rc = mcf::run_workers(h->nt, [&](Worker& w) {
-            w.guarded([&] {
-                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                    Block& k = h->blocks[(size_t)b];
-                    int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
-                    if (rc2) { w.fail(rc2); break; }
-                    // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
-                    k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
-                    mcf_options o = h->opt;
-                    o.device = k.device;
-                    rc2 = below ? mcf_plan_create_streamed(&k.gsub, &o, h->chunk_days, 2, &k.plan)
-                                : mcf_plan_create(&k.gsub, &o, h->chunk_days, 2, &k.plan);
-                    if (rc2) { w.fail(rc2); break; }
-                    if (h->nb > 1 && (rc2 = mcf_plan_twi_partial(k.plan, &k.twi_s, &k.twi_n))) { w.fail(rc2); break; }
-                    k.kept.assign((size_t)h->nchunks, 0);
-                }
+            mcf::for_blocks(w, h->nb, h->nt, [&](int b) -> int {
+                Block& k = h->blocks[(size_t)b];
+                int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
+                if (rc2) return rc2;
+                // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
+                k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
+                mcf_options o = h->opt;
+                o.device = k.device;
+                rc2 = below ? mcf_plan_create_streamed(&k.gsub, &o, h->chunk_days, 2, &k.plan)
+                            : mcf_plan_create(&k.gsub, &o, h->chunk_days, 2, &k.plan);
+                if (!rc2 && h->nb > 1) rc2 = mcf_plan_twi_partial(k.plan, &k.twi_s, &k.twi_n);
+                if (!rc2) k.kept.assign((size_t)h->nchunks, 0);
+                return rc2;
             });
             w.wait();
-            // the solver's one global reduction (src/microclimfCpp.cpp:993-1004): partial sums in block order
-            if (h->nb > 1) w.guarded([&] {
+            // the solver's one global reduction (src/microclimfCpp.cpp:993-1004): partial sums in block order, by every worker
+            if (h->nb > 1) {
                 double s = 0; int64_t n = 0;
                 for (const Block& k : h->blocks) { s += k.twi_s; n += k.twi_n; }
-                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                    const int rc2 = mcf_plan_set_twi_mean(h->blocks[(size_t)b].plan, s / (double)n);
-                    if (rc2) { w.fail(rc2); break; }
-                }
-            });
+                h->each_block(w, [&](Block& k) { return mcf_plan_set_twi_mean(k.plan, s / (double)n); });
+            }
         });
         if (rc) return rc;
         guard.p = nullptr;
@@ -391,41 +363,30 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
         std::fill(h->nosnowday.begin(), h->nosnowday.end(), 0);
         h->pass1_done = false;
         const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
-            w.guarded([&] {
-                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                    Block& k = h->blocks[(size_t)b];
-                    int rc2 = mcf_snowplan_reset(k.sp);
-                    if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
-                    if (rc2) { w.fail(rc2); break; }
-                    std::fill(k.kept.begin(), k.kept.end(), 0);
-                }
+            h->each_block(w, [&](Block& k) -> int {
+                int rc2 = mcf_snowplan_reset(k.sp);
+                if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
+                if (!rc2) std::fill(k.kept.begin(), k.kept.end(), 0);
+                return rc2;
             });
             w.wait();
             for (int ch = 0; ch < h->nchunks; ++ch) {
-                w.guarded([&] {
-                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                        Block& k = h->blocks[(size_t)b];
-                        int rc2 = mcf_snowplan_checkpoint(k.sp, ch);      // pass 2 starts any chunk from here
-                        // a chunk that could not stay in HBM is re-run by pass 2 if it holds a snow day: unless the caller wants the snow
-                        // series, pass 1 writes only what it reads itself of such a chunk (totalSWE, density: mcf_snowplan_set_series)
-                        int32_t room = 0;
-                        if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
-                        if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u));
-                        if (rc2) { w.fail(rc2); break; }
-                    }
+                h->each_block(w, [&](Block& k) -> int {
+                    int rc2 = mcf_snowplan_checkpoint(k.sp, ch);      // pass 2 starts any chunk from here
+                    // a chunk that could not stay in HBM is re-run by pass 2 if it holds a snow day: unless the caller wants the snow
+                    // series, pass 1 writes only what it reads itself of such a chunk (totalSWE, density: mcf_snowplan_set_series)
+                    int32_t room = 0;
+                    if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
+                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u));
+                    return rc2;
                 });
                 snow_chunk(*h, w, ch, smod);
-                w.guarded([&] {                     // applycpp3 max / min of totalSWE
-                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                        Block& k = h->blocks[(size_t)b];
-                        k.mx.assign((size_t)ns, 0.0); k.cmx.assign((size_t)ns, 0.0); k.mn.assign((size_t)ns, 0.0); k.cmn.assign((size_t)ns, 0.0);
-                        int rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
-                        if (!rc2) rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
-                        if (rc2) { w.fail(rc2); break; }
-                    }
+                h->each_block(w, [&](Block& k) -> int {              // applycpp3 max / min of totalSWE
+                    k.mx.assign((size_t)ns, 0.0); k.cmx.assign((size_t)ns, 0.0); k.mn.assign((size_t)ns, 0.0); k.cmn.assign((size_t)ns, 0.0);
+                    const int rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
+                    return rc2 ? rc2 : mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
                 });
-                w.wait();
-                if (w.t == 0) w.guarded([&] {
+                mcf::reduce_on_first(w, [&] {
                     // extremes over the blocks (max / min skip blocks whose step held no value), then the chunk's day classes
                     std::vector<double> mx((size_t)ns, -INFINITY), mn((size_t)ns, INFINITY);
                     for (const Block& k : h->blocks)
@@ -435,18 +396,14 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                         }
                     snowdays_of(mx.data(), mn.data(), cd, &h->snowday[(size_t)(ch * cd)], &h->nosnowday[(size_t)(ch * cd)]);
                 });
-                w.wait();
-                w.guarded([&] {
-                    bool any = false;
-                    for (int d = 0; d < cd; ++d) any |= h->snowday[(size_t)(ch * cd + d)] != 0;
-                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                        Block& k = h->blocks[(size_t)b];
-                        int rc2 = mcf_snowplan_meand_accumulate(k.sp, ch, &h->snowday[(size_t)(ch * cd)]);
-                        int32_t kept = 0;
-                        if (!rc2 && any && h->keep) rc2 = mcf_snowplan_keep_chunk(k.sp, ch, h->keep_reserve, &kept);
-                        if (rc2) { w.fail(rc2); break; }
-                        k.kept[(size_t)ch] = (char)kept;
-                    }
+                bool any = false;
+                for (int d = 0; d < cd; ++d) any |= h->snowday[(size_t)(ch * cd + d)] != 0;
+                h->each_block(w, [&](Block& k) -> int {
+                    int rc2 = mcf_snowplan_meand_accumulate(k.sp, ch, &h->snowday[(size_t)(ch * cd)]);
+                    int32_t kept = 0;
+                    if (!rc2 && any && h->keep) rc2 = mcf_snowplan_keep_chunk(k.sp, ch, h->keep_reserve, &kept);
+                    if (!rc2) k.kept[(size_t)ch] = (char)kept;
+                    return rc2;
                 });
                 w.wait();
             }
@@ -464,248 +421,241 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
     }
 }
 
+// ---- pass 2, step by step: what the steps of one mcf_snowrun_pass2 call share -----------------------------------
+namespace {
+struct Pass2 {
+    mcf_snowrun* h;
+    const mcf_snow_inputs* micro;
+    double mat;
+    mcf_outputs* out;
+    std::vector<int32_t> sdays, ndays_;         // the snow days, the no-snow days
+    std::vector<int32_t> sub_of_day;            // day -> its place among the snow days, or -1
+    int32_t outm[MCF_NOUT];                     // gridmicrosnow1's `out`
+    mcf_snow_inputs sub{};                      // gridmicrosnow1's inputs on the snow-day subset (array weather: the whole series)
+    mcf::HostCopies sub_series;
+    double mxtc = -INFINITY;                    // the solver's maximum air temperature over the no-snow days (data.frame weather)
+    bool no_skip = false, no_cells = false;
+    const double NA = mcf::na_real_host();
+};
+
+// the day lists and gridmicrosnow1's `out` (R/internal.R:3616-3622)
+void day_lists(Pass2& p) {
+    const mcf_snowrun* h = p.h;
+    for (int d = 0; d < h->ndays; ++d) {
+        if (h->snowday[(size_t)d]) p.sdays.push_back(d);
+        if (h->nosnowday[(size_t)d]) p.ndays_.push_back(d);
+    }
+    p.sub_of_day.assign(h->snowday.size(), -1);
+    for (size_t i = 0; i < p.sdays.size(); ++i) p.sub_of_day[(size_t)p.sdays[i]] = (int32_t)i;
+    for (int v = 0; v < MCF_NOUT; ++v) p.outm[v] = h->opt.out[v] ? 1 : 0;
+    if (h->opt.reqhgt == 0.0) {
+        static const int32_t ground[MCF_NOUT] = {1, 0, 0, 1, 0, 1, 1, 1, 1, 1};
+        memcpy(p.outm, ground, sizeof p.outm);
+    }
+    if (h->below)       // `out[c(1, 4)]`: Tz and soilm only
+        for (int v = 0; v < MCF_NOUT; ++v) p.outm[v] = p.outm[v] && (v == MCF_OUT_TZ || v == MCF_OUT_SOILM);
+}
+
+// `micro` checked, and the snow-day subset of its whole-series inputs (subsetpointmodel(micropoint, days = snowdays),
+// R/internal.R:3599); the solver's maximum air temperature over the NO-snow subset (src/microclimfCpp.cpp:2159-2168 on what
+// `.runmicronosnow` hands it, R/internal.R:3605)
+int snow_day_inputs(Pass2& p) {
+    const mcf_snowrun* h = p.h;
+    const mcf_snow_inputs* micro = p.micro;
+    if (!p.sdays.empty()) {
+        if (!micro) return api_fail(MCF_ERR_ARG, "snow run: the year has snow days, gridmicrosnow1's inputs are needed");
+        if (micro->rows != h->R || micro->cols != h->C || micro->tsteps != h->T || (micro->array_forcing != 0) != h->af)
+            return api_fail(MCF_ERR_ARG, "snow run: gridmicrosnow's inputs must be the whole series on the whole raster, in the run's weather geometry");
+        if (const char* missing = mcf::micro_series_missing(*micro))
+            return api_fail(MCF_ERR_ARG, std::string("null input: gridmicrosnow1 weather$") + missing);
+        const mcf_obstime& ob = micro->obstime;
+        if (!ob.year || !ob.month || !ob.day || !ob.hour) return api_fail(MCF_ERR_ARG, "null obstime");
+        if (!mcf::micro_rasters_given(*micro)) return api_fail(MCF_ERR_ARG, "null input: a gridmicrosnow1 raster");
+        if (p.outm[MCF_OUT_SOILM] && h->opt.out[MCF_OUT_SOILM] && !micro->other.Smax)
+            return api_fail(MCF_ERR_ARG, "soilm requested but other$Smax is null");
+        p.sub = *micro;
+        // (array weather: the snow plan takes the whole series and the day map — nine arrays are not copied)
+        if (!h->af) mcf::subset_days(p.sub, true, p.sub_of_day.data(), h->ndays, (int)p.sdays.size(), p.sub_series);
+    }
+    if (!h->af)
+        for (int d : p.ndays_)
+            for (int hh = 0; hh < 24; ++hh) { const double v = h->grid.clim.tc[(int64_t)d * 24 + hh]; if (v > p.mxtc) p.mxtc = v; }
+    return MCF_OK;
+}
+
+// a block's set-up between the passes: gridmicrosnow1's on its rows, the solver plan's for the no-snow days
+int block_setup(Pass2& p, Block& k) {
+    mcf_snowrun* h = p.h;
+    int rc = MCF_OK;
+    if (!p.sdays.empty()) {
+        mcf_snow_inputs bs = p.sub;
+        k.micro_rows = mcf::HostCopies();
+        if (h->nb > 1) mcf::micro_rasters_of_block(bs, k.micro_rows, h->R, h->C, k.r0, k.nr);
+        rc = mcf_snowplan_micro_setup(k.sp, &bs, p.sub_of_day.data(), (int32_t)p.sub_of_day.size(), h->opt.reqhgt, p.mat, p.outm, 0);
+    }
+    const bool solver = !p.ndays_.empty();
+    // below ground: the series Tbelowgroundv sees is the no-snow days joined ...
+    if (!rc && h->below && solver) rc = mcf_plan_below_set_days(k.plan, p.ndays_.data(), (int32_t)p.ndays_.size());
+    if (!rc && solver)                         // (array weather: per cell, cpp:2467-2471, over the no-snow days)
+        rc = h->af ? mcf_plan_set_mxtc_days(k.plan, &k.gsub, h->nosnowday.data(), h->ndays) : mcf_plan_set_mxtc(k.plan, p.mxtc);
+    // ... and its per-cell state comes from a pass over them (complete = 1: the solver's first sweep)
+    if (!rc && h->below && solver) rc = mcf_plan_below_prepare(k.plan, nullptr);
+    if (!rc) rc = mcf_snowplan_set_series(k.sp, 31u);         // (pass 2's re-runs feed the snow microclimate)
+    return rc;
+}
+
+// The solver on the no-snow days among d0 .. d0 + nd, each at its own place in the ring slot: one function per mode.
+// Below ground: the chunk's no-snow days in one call, EVERY cell — a cell's ground temperature under today's snow feeds its
+// running means on later days, so nothing is left out (and a chunk without a no-snow day does not touch the plan's carried window)
+int solver_days_below(Pass2& p, Block& k, int slot, int d0, int nd, bool has_snow) {
+    mcf_snowrun* h = p.h;
+    int n_both = 0;
+    for (int d = 0; d < nd; ++d) n_both += h->nosnowday[(size_t)(d0 + d)] && h->snowday[(size_t)(d0 + d)];
+    if (has_snow && n_both) {
+        mcf_ring_layout lay;
+        if (const int rc = mcf_plan_ring_layout(k.plan, &lay)) return rc;
+        h->st_tile_days += (lay.cells + lay.cells_per_tile - 1) / lay.cells_per_tile * n_both;
+    }
+    return mcf_plan_run_days_at(k.plan, d0, nd, slot, 0);
+}
+// Data.frame weather: the runs of consecutive no-snow days, a run ending where the days' class changes (on a day without snow
+// anywhere every cell is the solver's).  Where a run lies in a chunk with snow (ch >= 0), the tiles whose cells are all under snow
+// for the whole run are left out (include/mcf.h mcf_plan_run_days_masked): gridmicrosnow1 overwrites every one of their values
+int solver_days_vector(Pass2& p, Block& k, int slot, int ch, int d0, int nd, bool has_snow) {
+    mcf_snowrun* h = p.h;
+    for (int q = 0, e; q < nd; q = e) {
+        e = q + 1;
+        if (!h->nosnowday[(size_t)(d0 + q)]) continue;
+        const bool both = h->snowday[(size_t)(d0 + q)] != 0;
+        while (e < nd && h->nosnowday[(size_t)(d0 + e)] && (h->snowday[(size_t)(d0 + e)] != 0) == both) ++e;
+        int rc;
+        if (!(has_snow && both && !p.no_skip && ch >= 0)) {
+            if ((rc = mcf_plan_run_days_at(k.plan, d0 + q, e - q, slot, q))) return rc;
+            continue;
+        }
+        mcf_ring_layout lay;
+        if ((rc = mcf_plan_ring_layout(k.plan, &lay))) return rc;
+        const int64_t nt = (lay.cells + lay.cells_per_tile - 1) / lay.cells_per_tile;
+        const uint8_t* need = nullptr;
+        int64_t n_need = lay.cells;
+        if (!p.no_cells && (rc = mcf_snowplan_free_cells(k.sp, k.plan, ch, q, e - q, &need, &n_need))) return rc;
+        if (!p.no_cells && 16 * n_need <= lay.cells) {
+            // the few cells that are not under snow throughout, gathered into tiles of their own (scattered cells
+            // pay below ~ 8 % of the raster, profiles/r05_cells_rate.txt: their values reach the ring 8 bytes at a time)
+            rc = mcf_plan_run_days_cells(k.plan, d0 + q, e - q, slot, q, need, lay.cells, nullptr);
+            h->st_tile_days += nt * (e - q);
+            h->st_tile_days_left_out += (nt - (n_need + lay.cells_per_tile - 1) / lay.cells_per_tile) * (e - q);
+        } else {
+            int64_t ncov = 0;
+            k.skip.resize((size_t)nt);
+            if ((rc = mcf_snowplan_covered_tiles(k.sp, k.plan, ch, q, e - q, k.skip.data(), nt, &ncov))) return rc;
+            rc = mcf_plan_run_days_masked(k.plan, d0 + q, e - q, slot, q, ncov ? k.skip.data() : nullptr, ncov ? nt : 0);
+            h->st_tile_days += nt * (e - q);
+            h->st_tile_days_left_out += ncov * (e - q);
+        }
+        if (rc) return rc;
+    }
+    return MCF_OK;
+}
+// Array weather: the chunk's forcing into the slot once (all its days: the runs address them by day), then the same runs, whole
+int solver_days_array(Pass2& p, Block& k, int slot, int d0, int nd) {
+    const int rc = mcf_plan_upload_forcing_days(k.plan, &k.gsub, d0, nd, slot);
+    return rc ? rc : solver_days_vector(p, k, slot, -1, d0, nd, false);
+}
+int solver_days(Pass2& p, Block& k, int slot, int ch, int d0, int nd, bool has_snow) {
+    const mcf_snowrun* h = p.h;
+    bool any = false;
+    for (int d = 0; d < nd; ++d) any |= h->nosnowday[(size_t)(d0 + d)] != 0;
+    if (!any) return MCF_OK;
+    return h->below ? solver_days_below(p, k, slot, d0, nd, has_snow)
+           : h->af  ? solver_days_array(p, k, slot, d0, nd)
+                    : solver_days_vector(p, k, slot, ch, d0, nd, has_snow);
+}
+
+// the merged days of a ring slot to the caller: the block's rows in place, through the row pitch
+int fetch_days(Pass2& p, Block& k, int slot, int d0, int nd) {
+    const mcf_snowrun* h = p.h;
+    const int64_t R = h->R, C = h->C;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!h->opt.out[v]) continue;
+        double* dst = p.out->var[v] + k.r0 + R * C * (int64_t)d0 * 24;
+        if (const int rc = mcf_plan_fetch_pitched(k.plan, slot, v, 0, (int64_t)nd * 24, dst, R)) return rc;
+        // a day in NEITHER class (a melted pack's negative rounding residue: max <= 0 and min != 0) is no day of either
+        // model; the reference's merge indexes past its arrays there (R/internal.R:3650-3655) — NA here
+        for (int d = 0; d < nd; ++d)
+            if (!h->snowday[(size_t)(d0 + d)] && !h->nosnowday[(size_t)(d0 + d)])
+                for (int64_t lc = (int64_t)(d0 + d) * 24 * C; lc < (int64_t)(d0 + d + 1) * 24 * C; ++lc)
+                    for (int64_t r = 0; r < k.nr; ++r) p.out->var[v][k.r0 + r + R * lc] = p.NA;
+    }
+    return MCF_OK;
+}
+
+// per chunk: restore + re-run the snow chunk unless its series were kept; the solver on its no-snow days; the snow-day kernel
+// over the slot; the slot's merged days to the caller.  Collective: every worker walks every chunk.
+void chunk_loop(Pass2& p, Worker& w) {
+    mcf_snowrun* h = p.h;
+    const int cd = h->chunk_days;
+    int slot = 0;
+    for (int ch = 0; ch < h->nchunks; ++ch, slot ^= 1) {
+        const int d0 = ch * cd, nd = std::min(cd, h->ndays - d0);
+        bool has_snow = false, kept_all = true;
+        for (int d = 0; d < cd; ++d) has_snow |= h->snowday[(size_t)(d0 + d)] != 0;
+        for (const Block& k : h->blocks) kept_all = kept_all && k.kept[(size_t)ch];
+        if (w.t == 0 && has_snow) ++(kept_all ? h->st_chunks_kept : h->st_chunks_rerun);
+        if (has_snow && !kept_all) {          // collective: the blocks' surfaces couple through their halos
+            h->each_block(w, [&](Block& k) { return mcf_snowplan_restore(k.sp, ch); });
+            w.wait();
+            snow_chunk(*h, w, ch, nullptr);
+        }
+        h->each_block(w, [&](Block& k) -> int {
+            int rc = solver_days(p, k, slot, ch, d0, nd, has_snow);
+            if (!rc && has_snow) rc = mcf_snowplan_microsnow(k.sp, k.plan, ch, slot, &h->nosnowday[(size_t)d0]);
+            if (!rc && nd > 0) rc = fetch_days(p, k, slot, d0, nd);
+            return rc;
+        });
+        w.wait();
+    }
+}
+
+// days past the last whole chunk: the solver's alone; steps past the last whole day stay NA (src/microclimfCpp.cpp:2116)
+void tail_days(Pass2& p, Worker& w) {
+    mcf_snowrun* h = p.h;
+    const int cd = h->chunk_days;
+    const int64_t R = h->R, C = h->C;
+    h->each_block(w, [&](Block& k) -> int {
+        for (int d0 = h->nchunks * cd; d0 < h->ndays && !w.failed(); d0 += cd) {
+            const int nd = std::min(cd, h->ndays - d0);
+            int rc = solver_days(p, k, 0, -1, d0, nd, false);
+            if (!rc) rc = fetch_days(p, k, 0, d0, nd);
+            if (rc) return rc;
+        }
+        for (int v = 0; v < MCF_NOUT; ++v)
+            if (h->opt.out[v])
+                for (int64_t lc = (int64_t)h->ndays * 24 * C; lc < h->T * C; ++lc)
+                    for (int64_t r = 0; r < k.nr; ++r) p.out->var[v][k.r0 + r + R * lc] = p.NA;
+        return MCF_OK;
+    });
+}
+
+}  // namespace
+
 extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, double mat, mcf_outputs* out) {
     if (!h || !out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
     if (!h->pass1_done) return api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
     try {
-        const int cd = h->chunk_days, ndays = h->ndays;
-        const int64_t R = h->R, C = h->C, T = h->T, HS = R * C;
         for (int v = 0; v < MCF_NOUT; ++v)
             if (h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
-        // ---- day lists
-        std::vector<int> sdays, ndays_;
-        for (int d = 0; d < ndays; ++d) {
-            if (h->snowday[(size_t)d]) sdays.push_back(d);
-            if (h->nosnowday[(size_t)d]) ndays_.push_back(d);
-        }
-        std::vector<int32_t> sub_of_day(h->snowday.size(), -1);
-        for (size_t i = 0; i < sdays.size(); ++i) sub_of_day[(size_t)sdays[i]] = (int32_t)i;
-        // gridmicrosnow1's `out` (R/internal.R:3616-3622)
-        int32_t outm[MCF_NOUT];
-        for (int v = 0; v < MCF_NOUT; ++v) outm[v] = h->opt.out[v] ? 1 : 0;
-        if (h->opt.reqhgt == 0.0) {
-            static const int32_t ground[MCF_NOUT] = {1, 0, 0, 1, 0, 1, 1, 1, 1, 1};
-            memcpy(outm, ground, sizeof outm);
-        }
-        if (h->below)       // `out[c(1, 4)]`: Tz and soilm only
-            for (int v = 0; v < MCF_NOUT; ++v) outm[v] = outm[v] && (v == MCF_OUT_TZ || v == MCF_OUT_SOILM);
-        const std::vector<int32_t> below_days(ndays_.begin(), ndays_.end());
-        // ---- the snow-day subset of the whole-series inputs (subsetpointmodel(micropoint, days = snowdays), R/internal.R:3599)
-        const int64_t TS = (int64_t)sdays.size() * 24;
-        std::vector<int32_t> yr, mo, dy;
-        std::vector<double> hr, ser[10];
-        mcf_snow_inputs sub{};
-        if (!sdays.empty()) {
-            if (!micro) return api_fail(MCF_ERR_ARG, "snow run: the year has snow days, gridmicrosnow1's inputs are needed");
-            if (micro->rows != R || micro->cols != C || micro->tsteps != T || (micro->array_forcing != 0) != h->af)
-                return api_fail(MCF_ERR_ARG, "snow run: gridmicrosnow's inputs must be the whole series on the whole raster, in the run's weather geometry");
-            const mcf_snow_climate& cl = micro->clim;
-            const double* src[10] = {cl.temp, cl.relhum, cl.pres, cl.swdown, cl.difrad, cl.lwdown, cl.windspeed, cl.winddir, cl.precip, cl.umu};
-            static const char* nm[10] = {"temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed", "winddir", "precip", "umu"};
-            for (int f = 0; f < 10; ++f)
-                if (!src[f]) return api_fail(MCF_ERR_ARG, std::string("null input: gridmicrosnow1 weather$") + nm[f]);
-            const mcf_obstime& ob = micro->obstime;
-            if (!ob.year || !ob.month || !ob.day || !ob.hour) return api_fail(MCF_ERR_ARG, "null obstime");
-            const mcf_snow_vegp& vg = micro->vegp;
-            const mcf_snow_other& ot = micro->other;
-            if (!vg.pai || !vg.hgt || !vg.leaft || !vg.clump || !vg.paia || !vg.leafd || !vg.leafden || !ot.slope || !ot.aspect ||
-                !ot.skyview || !ot.wsa || !ot.hor)
-                return api_fail(MCF_ERR_ARG, "null input: a gridmicrosnow1 raster");
-            if (outm[MCF_OUT_SOILM] && h->opt.out[MCF_OUT_SOILM] && !ot.Smax) return api_fail(MCF_ERR_ARG, "soilm requested but other$Smax is null");
-            sub = *micro;
-            if (!h->af) {      // (array weather: the snow plan takes the whole series and the day map — nine arrays are not copied)
-            yr.resize((size_t)TS); mo.resize((size_t)TS); dy.resize((size_t)TS); hr.resize((size_t)TS);
-            for (auto& s : ser) s.resize((size_t)TS);
-            for (size_t i = 0; i < sdays.size(); ++i)
-                for (int hh = 0; hh < 24; ++hh) {
-                    const int64_t a = (int64_t)sdays[i] * 24 + hh, q = (int64_t)i * 24 + hh;
-                    yr[(size_t)q] = ob.year[a]; mo[(size_t)q] = ob.month[a]; dy[(size_t)q] = ob.day[a]; hr[(size_t)q] = ob.hour[a];
-                    for (int f = 0; f < 10; ++f) ser[f][(size_t)q] = src[f][a];
-                }
-            sub.tsteps = TS;
-            sub.obstime.year = yr.data(); sub.obstime.month = mo.data(); sub.obstime.day = dy.data(); sub.obstime.hour = hr.data();
-            sub.clim.temp = ser[0].data(); sub.clim.relhum = ser[1].data(); sub.clim.pres = ser[2].data(); sub.clim.swdown = ser[3].data();
-            sub.clim.difrad = ser[4].data(); sub.clim.lwdown = ser[5].data(); sub.clim.windspeed = ser[6].data();
-            sub.clim.winddir = ser[7].data(); sub.clim.precip = ser[8].data(); sub.clim.umu = ser[9].data();
-            }
-        }
-        // the solver's maximum air temperature over the NO-snow subset (src/microclimfCpp.cpp:2159-2168 on what `.runmicronosnow`
-        // hands it, R/internal.R:3605)
-        double mxtc = -INFINITY;
-        if (!h->af)
-            for (int d : ndays_)
-                for (int hh = 0; hh < 24; ++hh) { const double v = h->grid.clim.tc[(int64_t)d * 24 + hh]; if (v > mxtc) mxtc = v; }
-        const double NA = mcf::na_real_host();
-        const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
-            w.guarded([&] {
-                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                    Block& k = h->blocks[(size_t)b];
-                    int rc2 = MCF_OK;
-                    if (!sdays.empty()) {
-                        mcf_snow_inputs bs = sub;
-                        if (h->nb > 1) {
-                            const mcf_snow_vegp& vg = micro->vegp;
-                            const mcf_snow_other& ot = micro->other;
-                            mcf::gather_rows(k.m_pai, vg.pai, R, C, k.r0, k.nr); mcf::gather_rows(k.m_hgt, vg.hgt, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_leaft, vg.leaft, R, C, k.r0, k.nr); mcf::gather_rows(k.m_clump, vg.clump, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_paia, vg.paia, R, C, k.r0, k.nr); mcf::gather_rows(k.m_leafd, vg.leafd, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_leafden, vg.leafden, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_slope, ot.slope, R, C, k.r0, k.nr); mcf::gather_rows(k.m_aspect, ot.aspect, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_svf, ot.skyview, R, C, k.r0, k.nr);
-                            mcf::gather_rows(k.m_wsa, ot.wsa, R, C, k.r0, k.nr, 8); mcf::gather_rows(k.m_hor, ot.hor, R, C, k.r0, k.nr, 24);
-                            if (ot.Smax) mcf::gather_rows(k.m_smax, ot.Smax, R, C, k.r0, k.nr);
-                            bs.rows = k.nr;
-                            bs.vegp.pai = k.m_pai.data(); bs.vegp.hgt = k.m_hgt.data(); bs.vegp.leaft = k.m_leaft.data();
-                            bs.vegp.clump = k.m_clump.data(); bs.vegp.paia = k.m_paia.data(); bs.vegp.leafd = k.m_leafd.data();
-                            bs.vegp.leafden = k.m_leafden.data();
-                            bs.other.slope = k.m_slope.data(); bs.other.aspect = k.m_aspect.data(); bs.other.skyview = k.m_svf.data();
-                            bs.other.wsa = k.m_wsa.data(); bs.other.hor = k.m_hor.data();
-                            bs.other.Smax = ot.Smax ? k.m_smax.data() : nullptr;
-                        }
-                        rc2 = mcf_snowplan_micro_setup(k.sp, &bs, sub_of_day.data(), (int32_t)sub_of_day.size(), h->opt.reqhgt, mat, outm, 0);
-                    }
-                    // below ground: the series Tbelowgroundv sees is the no-snow days joined ...
-                    if (!rc2 && h->below && !ndays_.empty()) rc2 = mcf_plan_below_set_days(k.plan, below_days.data(), (int32_t)below_days.size());
-                    if (!rc2 && !ndays_.empty())         // (array weather: per cell, cpp:2467-2471, over the no-snow days)
-                        rc2 = h->af ? mcf_plan_set_mxtc_days(k.plan, &k.gsub, h->nosnowday.data(), ndays) : mcf_plan_set_mxtc(k.plan, mxtc);
-                    // ... and its per-cell state comes from a pass over them (complete = 1: the solver's first sweep)
-                    if (!rc2 && h->below && !ndays_.empty()) rc2 = mcf_plan_below_prepare(k.plan, nullptr);
-                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, 31u);         // (pass 2's re-runs feed the snow microclimate)
-                    if (rc2) { w.fail(rc2); break; }
-                }
-            });
+        Pass2 p{h, micro, mat, out};
+        p.no_skip = getenv("MCF_SNOW_NO_TILE_SKIP") != nullptr;
+        p.no_cells = getenv("MCF_SNOW_NO_CELL_GATHER") != nullptr;      // (A/B: tiles as the unit, as in round 4)
+        day_lists(p);
+        if (const int rc = snow_day_inputs(p)) return rc;
+        return mcf::run_workers(h->nt, [&](Worker& w) {
+            h->each_block(w, [&](Block& k) { return block_setup(p, k); });
             w.wait();
-            // the merged days of a ring slot to the caller: the block's rows in place, through the row pitch
-            auto fetch_days = [&](Block& k, int slot, int d0, int nd) -> int {
-                for (int v = 0; v < MCF_NOUT; ++v) {
-                    if (!h->opt.out[v]) continue;
-                    double* dst = out->var[v] + k.r0 + HS * (int64_t)d0 * 24;
-                    int rc2 = mcf_plan_fetch_pitched(k.plan, slot, v, 0, (int64_t)nd * 24, dst, R);
-                    if (rc2) return rc2;
-                    // a day in NEITHER class (a melted pack's negative rounding residue: max <= 0 and min != 0) is no day of either
-                    // model; the reference's merge indexes past its arrays there (R/internal.R:3650-3655) — NA here
-                    for (int d = 0; d < nd; ++d)
-                        if (!h->snowday[(size_t)(d0 + d)] && !h->nosnowday[(size_t)(d0 + d)])
-                            for (int64_t lc = (int64_t)(d0 + d) * 24 * C; lc < (int64_t)(d0 + d + 1) * 24 * C; ++lc)
-                                for (int64_t r = 0; r < k.nr; ++r) out->var[v][k.r0 + r + R * lc] = NA;
-                }
-                return MCF_OK;
-            };
-            // runs of consecutive no-snow days.  Where such a run lies in a chunk with snow, the tiles whose cells are all under snow
-            // for the whole run are left out (include/mcf.h mcf_plan_run_days_masked): gridmicrosnow1 overwrites every one of their values
-            const bool no_skip = getenv("MCF_SNOW_NO_TILE_SKIP") != nullptr;
-            const bool no_cells = getenv("MCF_SNOW_NO_CELL_GATHER") != nullptr;      // (A/B: tiles as the unit, as in round 4)
-            std::vector<uint8_t> skip;
-            auto solver_days = [&](Block& k, int slot, int ch, int d0, int nd, bool has_snow) -> int {
-                int q = 0;
-                if (h->below) {
-                    // the chunk's no-snow days in one call, each at its own place in the slot, EVERY cell: a cell's ground temperature
-                    // under today's snow feeds its running means on later days, so nothing is left out (and a chunk without a
-                    // no-snow day does not touch the plan's carried window)
-                    int n_no = 0, n_both = 0;
-                    for (int d = 0; d < nd; ++d) {
-                        n_no += h->nosnowday[(size_t)(d0 + d)] != 0;
-                        n_both += h->nosnowday[(size_t)(d0 + d)] && h->snowday[(size_t)(d0 + d)];
-                    }
-                    if (!n_no) return MCF_OK;
-                    if (has_snow && n_both) {
-                        mcf_ring_layout lay;
-                        const int rc3 = mcf_plan_ring_layout(k.plan, &lay);
-                        if (rc3) return rc3;
-                        h->st_tile_days += (lay.cells + lay.cells_per_tile - 1) / lay.cells_per_tile * n_both;
-                    }
-                    return mcf_plan_run_days_at(k.plan, d0, nd, slot, 0);
-                }
-                if (h->af) {      // array weather: the chunk's forcing into the slot once (all its days: the runs address them by day)
-                    bool any = false;
-                    for (int d = 0; d < nd; ++d) any |= h->nosnowday[(size_t)(d0 + d)] != 0;
-                    if (!any) return MCF_OK;
-                    const int rc3 = mcf_plan_upload_forcing_days(k.plan, &k.gsub, d0, nd, slot);
-                    if (rc3) return rc3;
-                }
-                while (q < nd) {
-                    if (!h->nosnowday[(size_t)(d0 + q)]) { ++q; continue; }
-                    // (a run ends where the days' class changes: on a day without snow anywhere every cell is the solver's)
-                    const bool both = h->snowday[(size_t)(d0 + q)] != 0;
-                    int e = q;
-                    while (e < nd && h->nosnowday[(size_t)(d0 + e)] && (h->snowday[(size_t)(d0 + e)] != 0) == both) ++e;
-                    int rc2;
-                    if (has_snow && both && !no_skip && ch >= 0 && !h->af) {
-                        mcf_ring_layout lay;
-                        if ((rc2 = mcf_plan_ring_layout(k.plan, &lay))) return rc2;
-                        const int64_t nt = (lay.cells + lay.cells_per_tile - 1) / lay.cells_per_tile;
-                        const uint8_t* need = nullptr;
-                        int64_t n_need = lay.cells;
-                        if (!no_cells && (rc2 = mcf_snowplan_free_cells(k.sp, k.plan, ch, q, e - q, &need, &n_need))) return rc2;
-                        if (!no_cells && 16 * n_need <= lay.cells) {
-                            // the few cells that are not under snow throughout, gathered into tiles of their own (scattered cells
-                            // pay below ~ 8 % of the raster, profiles/r05_cells_rate.txt: their values reach the ring 8 bytes at a time)
-                            rc2 = mcf_plan_run_days_cells(k.plan, d0 + q, e - q, slot, q, need, lay.cells, nullptr);
-                            h->st_tile_days += nt * (e - q);
-                            h->st_tile_days_left_out += (nt - (n_need + lay.cells_per_tile - 1) / lay.cells_per_tile) * (e - q);
-                        } else {
-                            int64_t ncov = 0;
-                            skip.resize((size_t)nt);
-                            if ((rc2 = mcf_snowplan_covered_tiles(k.sp, k.plan, ch, q, e - q, skip.data(), nt, &ncov))) return rc2;
-                            rc2 = mcf_plan_run_days_masked(k.plan, d0 + q, e - q, slot, q, ncov ? skip.data() : nullptr, ncov ? nt : 0);
-                            h->st_tile_days += nt * (e - q);
-                            h->st_tile_days_left_out += ncov * (e - q);
-                        }
-                    } else {
-                        rc2 = mcf_plan_run_days_at(k.plan, d0 + q, e - q, slot, q);
-                    }
-                    if (rc2) return rc2;
-                    q = e;
-                }
-                return MCF_OK;
-            };
-            int slot = 0;
-            for (int ch = 0; ch < h->nchunks; ++ch, slot ^= 1) {
-                const int d0 = ch * cd, nd = std::min(cd, ndays - d0);
-                bool has_snow = false, kept_all = true;
-                for (int d = 0; d < cd; ++d) has_snow |= h->snowday[(size_t)(d0 + d)] != 0;
-                for (const Block& k : h->blocks) kept_all = kept_all && k.kept[(size_t)ch];
-                if (w.t == 0 && has_snow) ++(kept_all ? h->st_chunks_kept : h->st_chunks_rerun);
-                if (has_snow && !kept_all) {          // collective: the blocks' surfaces couple through their halos
-                    w.guarded([&] {
-                        for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                            const int rc2 = mcf_snowplan_restore(h->blocks[(size_t)b].sp, ch);
-                            if (rc2) { w.fail(rc2); break; }
-                        }
-                    });
-                    w.wait();
-                    snow_chunk(*h, w, ch, nullptr);
-                }
-                w.guarded([&] {
-                    for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                        Block& k = h->blocks[(size_t)b];
-                        int rc2 = solver_days(k, slot, ch, d0, nd, has_snow);
-                        if (!rc2 && has_snow) rc2 = mcf_snowplan_microsnow(k.sp, k.plan, ch, slot, &h->nosnowday[(size_t)d0]);
-                        if (!rc2 && nd > 0) rc2 = fetch_days(k, slot, d0, nd);
-                        if (rc2) { w.fail(rc2); break; }
-                    }
-                });
-                w.wait();
-            }
-            // days past the last whole chunk: the solver's alone
-            w.guarded([&] {
-                for (int b = w.t; b < h->nb && !w.failed(); b += h->nt) {
-                    Block& k = h->blocks[(size_t)b];
-                    for (int d0 = h->nchunks * cd; d0 < ndays && !w.failed(); d0 += cd) {
-                        const int nd = std::min(cd, ndays - d0);
-                        int rc2 = solver_days(k, 0, -1, d0, nd, false);
-                        if (!rc2) rc2 = fetch_days(k, 0, d0, nd);
-                        if (rc2) { w.fail(rc2); break; }
-                    }
-                    // steps past the last whole day stay NA (src/microclimfCpp.cpp:2116)
-                    for (int v = 0; v < MCF_NOUT; ++v)
-                        if (h->opt.out[v])
-                            for (int64_t lc = (int64_t)ndays * 24 * C; lc < T * C; ++lc)
-                                for (int64_t r = 0; r < k.nr; ++r) out->var[v][k.r0 + r + R * lc] = NA;
-                }
-            });
+            chunk_loop(p, w);
+            tail_days(p, w);
         });
-        return rc;
     } catch (const std::exception& e) {
         return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass2: ") + e.what());
     }
@@ -758,10 +708,7 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
         else if ((rc = mcf::device_list(mu, 0, &sb.devs))) return rc;
         sb.cut(mu ? mu->n_blocks : 1);
         rc = mcf::run_workers(sb.nt, [&](Worker& w) {
-            w.guarded([&] {
-                for (int b = w.t; b < sb.nb && !w.failed(); b += sb.nt)
-                    if (const int rc2 = block_snowplan(sb, b, sb.devs[(size_t)w.t], *in)) { w.fail(rc2); break; }
-            });
+            mcf::for_blocks(w, sb.nb, sb.nt, [&](int b) { return block_snowplan(sb, b, sb.devs[(size_t)w.t], *in); });
         });
         if (rc) return rc;
         const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
@@ -786,9 +733,7 @@ extern "C" int mcf_snowmodel1_multi(const mcf_snowdriver_in* in, mcf_snowdriver_
     if (!in || !out || !mu) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     const mcf_snow_inputs& base = in->base;
     if (base.rows <= 0 || base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, "snow driver needs the raster and its dtm");
-    const mcf_snow_vegp& vg = base.vegp;
-    const mcf_snow_other& ot = base.other;
-    if (!vg.pai || !vg.hgt || !vg.leaft || !vg.clump || !ot.isnowdc || !ot.isnowdg || !ot.isnowac || !ot.isnowag)
+    if (!mcf::model_rasters_given(base))
         return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
     return snowmodel(in, out, mu, 0);
 }

@@ -427,29 +427,27 @@ extern "C" int mcf_precompute_terrain_multi(const mcf_terrain_in* in, const mcf_
     const int s = in->agg > 0 ? in->agg : 10;
     const int64_t need = out->wsa ? 100 + 2 * s + s / 2 : ((out->hor || out->svfa) ? 100 : 1);     // as mcf_precompute_terrain asks
     return mcf::run_workers(nt, [&](mcf::Worker& w) {
-        w.guarded([&] {
-            std::vector<double> ext, part[5];
-            for (int b = w.t; b < nb && !w.failed(); b += nt) {
-                const int64_t r0 = R * b / nb, r1 = R * (b + 1) / nb, nr = r1 - r0;
-                if (nr <= 0) continue;
-                const int64_t hn = std::min(need, r0), hs = std::min(need, R - r1), RB = hn + nr + hs;
-                mcf::gather_rows(ext, in->dtm, R, C, r0 - hn, RB);
-                mcf_terrain_in bi = *in;
-                bi.rows = nr; bi.halo_north = (int32_t)hn; bi.halo_south = (int32_t)hs; bi.dtm = ext.data();
-                bi.row0 = r0; bi.rows_total = R;
-                double* const dst[5] = {out->slope, out->aspect, out->hor, out->svfa, out->wsa};
-                const int layers[5] = {1, 1, 24, 1, 8};
-                mcf_terrain_out bo;
-                double** const bop[5] = {&bo.slope, &bo.aspect, &bo.hor, &bo.svfa, &bo.wsa};
-                for (int k = 0; k < 5; ++k) {
-                    if (dst[k]) part[k].resize((size_t)(nr * C * layers[k]));
-                    *bop[k] = dst[k] ? part[k].data() : nullptr;
-                }
-                const int rc = mcf_precompute_terrain(&bi, &bo, devs[(size_t)w.t]);
-                if (rc != MCF_OK) { w.fail(rc); return; }
-                for (int k = 0; k < 5; ++k)      // layer-column lc of the block -> the same one of the raster
-                    if (dst[k]) mcf::scatter_rows(dst[k], part[k].data(), R, C, r0, nr, layers[k]);
+        std::vector<double> ext, part[5];
+        mcf::for_blocks(w, nb, nt, [&](int b) -> int {
+            const int64_t r0 = R * b / nb, r1 = R * (b + 1) / nb, nr = r1 - r0;
+            if (nr <= 0) return MCF_OK;
+            const int64_t hn = std::min(need, r0), hs = std::min(need, R - r1), RB = hn + nr + hs;
+            mcf::gather_rows(ext, in->dtm, R, C, r0 - hn, RB);
+            mcf_terrain_in bi = *in;
+            bi.rows = nr; bi.halo_north = (int32_t)hn; bi.halo_south = (int32_t)hs; bi.dtm = ext.data();
+            bi.row0 = r0; bi.rows_total = R;
+            double* const dst[5] = {out->slope, out->aspect, out->hor, out->svfa, out->wsa};
+            const int layers[5] = {1, 1, 24, 1, 8};
+            mcf_terrain_out bo;
+            double** const bop[5] = {&bo.slope, &bo.aspect, &bo.hor, &bo.svfa, &bo.wsa};
+            for (int k = 0; k < 5; ++k) {
+                if (dst[k]) part[k].resize((size_t)(nr * C * layers[k]));
+                *bop[k] = dst[k] ? part[k].data() : nullptr;
             }
+            if (const int rc = mcf_precompute_terrain(&bi, &bo, devs[(size_t)w.t])) return rc;
+            for (int k = 0; k < 5; ++k)      // layer-column lc of the block -> the same one of the raster
+                if (dst[k]) mcf::scatter_rows(dst[k], part[k].data(), R, C, r0, nr, layers[k]);
+            return MCF_OK;
         });
     });
 }
