@@ -37,7 +37,7 @@
  * There is no CPU fallback: every solver / kernel entry point fails with
  * MCF_ERR_NO_DEVICE when no HIP device is usable.  Host-side by nature, as in the
  * reference, and therefore usable without a device: the one-point time-series model
- * (mcf_bigleaf, mcf_soilm, mcf_pointmprocess, mcf_weatherhgt) and the file side of
+ * (mcf_bigleaf, mcf_soilm, mcf_pointmprocess, mcf_weatherhgt; their `_batch` forms for many points are device entries) and the file side of
  * the writetonc sink (mcf_nc_create, mcf_nc_write_host, mcf_nc_close), and the
  * flow-accumulation sweep behind soilc$twi (mcf_flowacc, mcf_topidx; on the device: mcf_flowacc_device, mcf_topidx_device).
  */
@@ -893,9 +893,11 @@ int mcf_applycpp3(const double *a, int64_t rows, int64_t cols, int64_t tsteps, i
  *   mcf_bigleaf()        BigLeafCpp      src/microclimfCpp.cpp:710-881   (_microclimf_BigLeafCpp)
  *   mcf_pointmprocess()  pointmprocess   src/microclimfCpp.cpp:5265-5323 (_microclimf_pointmprocess)
  *   mcf_weatherhgt()     weatherhgtCpp   src/microclimfCpp.cpp:884-929   (_microclimf_weatherhgtCpp)
- * as `runpointmodel` chains them (R/Cppwrappers.R:119-138).  They run on the HOST, as in the reference: one
- * point, iterated over the whole series with running means — nothing to parallelise and not part of the GPU hot
- * path (which has no CPU implementation).  vegp / groundp are read positionally as the reference does:
+ * as `runpointmodel` chains them (R/Cppwrappers.R:119-138).  They run on the HOST, as in the reference: ONE
+ * point is a serial job (an energy balance iterated over the whole series, coupled through running means) and is
+ * not part of the grid solver's hot path.  MANY points are not serial: the points of `runpointmodela` are
+ * independent, and inside one BigLeaf iteration every hour reads only its own state of the iteration before; the
+ * `_batch` entries below run them on the device, one lane per (point, hour).  vegp / groundp are read positionally as the reference does:
  * vegp = (h, pai, x, clump, lref, ltra, leafd, em, gsmax, q50), groundp = (gref, slope, aspect, em, rho, Vm, Vq,
  * Mc, b, psi_e, Smax, Smin).  One guard the reference lacks: its circular means index outside their arrays when
  * the window is longer than the series; mcf_bigleaf rejects yearG for 2..89 days and series under 6 steps. */
@@ -918,6 +920,37 @@ int mcf_pointmprocess(int64_t n, const double *windspeed, const double *tc, cons
                       double *DDp, double *T0p, double *dtrp);
 int mcf_weatherhgt(int64_t n, const mcf_obstime *obstime, const mcf_point_weather *weather, double zin, double uzin,
                    double zout, double lat, double lon, double *temp, double *relhum, double *windspeed);
+/* ---- the same three operators for P points at once, on the device (mcf_pointbatch.hip) ----
+ *   mcf_bigleaf_batch()        BigLeafCpp      src/microclimfCpp.cpp:710-881   per point
+ *   mcf_weatherhgt_batch()     weatherhgtCpp   src/microclimfCpp.cpp:884-929   per point
+ *   mcf_pointmprocess_batch()  pointmprocess   src/microclimfCpp.cpp:5265-5323 per point
+ * Semantics are those of the single-point entries, per point and without cross-talk: a point converges on its own
+ * (`iters[p]`, `err[p]`; it is frozen after the ground-flux update of the iteration in which its largest temperature
+ * change drops to `tol`, the others go on up to `maxiter`), and its results are bit-identical whatever batch it is in
+ * and however the batch is cut into blocks.  Series are [P][n], a point's series contiguous; `obstime` [n] is shared;
+ * vegp [P][10], groundp [P][12], lat / lon [P].  The batch entries take WHOLE DAYS only (n % 24 == 0); the other
+ * refusals are mcf_bigleaf's (null arguments, P < 1, n < 6, yearG with 2..89 days) and are returned before the device
+ * is touched; then MCF_ERR_NO_DEVICE without a HIP device.  About 30 series of 8 n bytes per point live on the device:
+ * points are processed in blocks sized from the free memory, or of `points_per_block` points (0 = from free memory).
+ * mcf_weatherhgt_batch runs mcf_weatherhgt's fixed canopy and ground through the batched BigLeaf (the annual term on
+ * for one day or >= 90 days, as there). */
+typedef struct mcf_bigleaf_batch_out { /* caller-allocated; series [P][n], a point's series contiguous */
+    double *Tc, *Tg, *H, *G, *psih, *psim, *phih, *OL, *uf, *RabsG, *albedo;
+    double *err;    /* [P] */
+    int32_t *iters; /* [P] */
+} mcf_bigleaf_batch_out;
+int mcf_bigleaf_batch(int64_t P, int64_t n, const mcf_obstime *obstime, const mcf_point_weather *weather,
+                      const double *vegp, const double *groundp, const double *soilm, const double *lat,
+                      const double *lon, double dTmx, double zref, int32_t maxiter, double bwgt, double tol,
+                      int32_t yearG, int64_t points_per_block, int32_t device, mcf_bigleaf_batch_out *out);
+int mcf_weatherhgt_batch(int64_t P, int64_t n, const mcf_obstime *obstime, const mcf_point_weather *weather, double zin,
+                         double uzin, double zout, const double *lat, const double *lon, int64_t points_per_block,
+                         int32_t device, double *temp, double *relhum, double *windspeed);
+int mcf_pointmprocess_batch(int64_t P, int64_t n, const double *windspeed, const double *tc, const double *rh,
+                            const double *pk, const double *uf, const double *soilm, const double *RabsG, double zref,
+                            const double *h, const double *pai, const double *rho, const double *Vm, const double *Vq,
+                            const double *Mc, int32_t device, double *umu, double *kp, double *muGp, double *DDp,
+                            double *T0p, double *dtrp);
 /* _microclimf_pointmodelsnow (src/microclimfCpp.cpp:4000-4169; called by `.snowmodel1`, R/internal.R:2536): the snow
  * branch's point model.  vegp = (pai, hgt, ltra, clump), other = (slope, aspect, lat, lon, zref, initial depth,
  * initial age); snowenv: MCF_SNOWENV_*; the reference's defaults are tol = 0.5, maxiter = 100.  Outputs: [n] each,

@@ -155,6 +155,11 @@ class BigLeafOut(C.Structure):
     _fields_ = [(k, c_double_p) for k in BIGLEAF_FIELDS] + [("err", C.c_double), ("iters", C.c_int32)]
 
 
+class BigLeafBatchOut(C.Structure):
+    """include/mcf.h mcf_bigleaf_batch_out: series [P][n], err / iters [P]"""
+    _fields_ = [(k, c_double_p) for k in BIGLEAF_FIELDS] + [("err", c_double_p), ("iters", c_int32_p)]
+
+
 class NcSpec(C.Structure):
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("nsteps", C.c_int64), ("east", c_double_p),
                 ("north", c_double_p), ("time_hours", c_double_p), ("crs_wkt", C.c_char_p), ("reqhgt", C.c_double),
@@ -208,6 +213,7 @@ EXPORTS = (
     "mcf_snowplan_create", "mcf_snowplan_destroy", "mcf_snowplan_chunks", "mcf_snowplan_surface", "mcf_snowplan_handover", "mcf_snowplan_apply3",
     "mcf_snowplan_surface_partial", "mcf_snowplan_prepare_chunk", "mcf_snowplan_run_chunk", "mcf_snowplan_pack_halo",
     "mcf_snowplan_prepare_chunk_dev",
+    "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch",
     "mcf_bigleaf", "mcf_soilm", "mcf_pointmprocess", "mcf_weatherhgt", "mcf_man", "mcf_pointmodelsnow", "mcf_canintfrac", "mcf_meltmu", "mcf_meltmu2", "mcf_tpicalc",
     "mcf_nc_create", "mcf_nc_write_host", "mcf_nc_write_plan", "mcf_nc_close",
     "mcf_flowacc", "mcf_topidx",
@@ -429,6 +435,15 @@ def load() -> C.CDLL:
     lib.mcf_pointmprocess.argtypes = [C.c_int64] + [c_double_p] * 7 + [C.c_double] * 7 + [c_double_p] * 6
     lib.mcf_weatherhgt.restype = C.c_int
     lib.mcf_weatherhgt.argtypes = [C.c_int64, OT, PW] + [C.c_double] * 5 + [c_double_p] * 3
+    lib.mcf_bigleaf_batch.restype = C.c_int
+    lib.mcf_bigleaf_batch.argtypes = ([C.c_int64, C.c_int64, OT, PW] + [c_double_p] * 5 + [C.c_double, C.c_double, C.c_int32,
+                                      C.c_double, C.c_double, C.c_int32, C.c_int64, C.c_int32, C.POINTER(BigLeafBatchOut)])
+    lib.mcf_weatherhgt_batch.restype = C.c_int
+    lib.mcf_weatherhgt_batch.argtypes = ([C.c_int64, C.c_int64, OT, PW] + [C.c_double] * 3 + [c_double_p] * 2 +
+                                         [C.c_int64, C.c_int32] + [c_double_p] * 3)
+    lib.mcf_pointmprocess_batch.restype = C.c_int
+    lib.mcf_pointmprocess_batch.argtypes = ([C.c_int64, C.c_int64] + [c_double_p] * 7 + [C.c_double] + [c_double_p] * 6 +
+                                            [C.c_int32] + [c_double_p] * 6)
     lib.mcf_pointmodelsnow.restype = C.c_int
     lib.mcf_pointmodelsnow.argtypes = [C.c_int64, C.POINTER(Obstime), C.POINTER(PointWeather), c_double_p, c_double_p,
                                        C.c_int32, C.c_double, C.c_double, C.POINTER(PointSnowOut)]

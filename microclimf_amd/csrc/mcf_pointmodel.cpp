@@ -950,3 +950,89 @@ extern "C" int mcf_meltmu2(int64_t cells, int64_t n, const double* mu, const dou
     }
     return MCF_OK;
 }
+
+// =====================================================================================================================
+// The host half of the batched point model (mcf_pointbatch.hip, mcf_pointbatch.h): the per-point and per-date constants of
+// BigLeafCpp, computed HERE, with the functions and the evaluation order mcf_bigleaf uses, so that the kernels start from the
+// bits the host model computes and only the (point, hour) work differs by the device's libm.
+// =====================================================================================================================
+#include "mcf_pointbatch.h"
+
+namespace mcf {
+
+void bl_point_consts(const double* vegp, const double* groundp, double lat, double lon, double zref, double* c) {
+    const double h = vegp[0], pai = vegp[1], vegx = vegp[2], clump = vegp[3], lref = vegp[4], ltra = vegp[5], leafd = vegp[6],
+                 em = vegp[7], gsmax = vegp[8];
+    const double gref = groundp[0], slope = groundp[1], aspect = groundp[2], groundem = groundp[3], rho = groundp[4],
+                 Vm = groundp[5], Vq = groundp[6], Mc = groundp[7], soilb = groundp[8], psie = groundp[9],
+                 Smax = groundp[10], Smin = groundp[11];
+    c[BC_PAI] = pai; c[BC_X] = vegx; c[BC_CLUMP] = clump; c[BC_LREF] = lref; c[BC_EM] = em; c[BC_GSMAX] = gsmax;
+    c[BC_GREF] = gref; c[BC_GROUNDEM] = groundem; c[BC_SMAX] = Smax; c[BC_SMIN] = Smin; c[BC_SOILB] = soilb; c[BC_PSIE] = psie;
+    const double latr = lat * kPi / 180.0;                                        // sun_position
+    c[BC_LON] = lon; c[BC_SINLAT] = sin(latr); c[BC_COSLAT] = cos(latr);
+    c[BC_SLOPE] = slope; c[BC_COSSL] = cos(slope * kToRad); c[BC_SINSL] = sin(slope * kToRad); c[BC_ASPECT] = aspect;
+    // shortwave_absorbed, pai > 0 (the table is not read for pai == 0)
+    double pait = pai;
+    if (clump > 0.0) pait = pai / (1 - clump);
+    const Dif p = two_stream_dif(pait, vegx, lref, ltra, gref);
+    const double trd = clump * clump;
+    double amx = gref;
+    if (amx < lref) amx = lref;
+    double albd = gref * (trd * trd) + (1.0 - trd * trd) * (p.p1 + p.p2);
+    if (albd > amx) albd = amx;
+    if (albd < 0.01) albd = 0.01;
+    c[BC_PAITSW] = pait; c[BC_A] = p.a; c[BC_GMA] = p.gma; c[BC_OM] = p.om; c[BC_J] = p.J; c[BC_DEL] = p.del; c[BC_U1] = p.u1;
+    c[BC_HH] = p.h; c[BC_D1] = p.D1; c[BC_D2] = p.D2; c[BC_S1] = p.S1; c[BC_EMH] = exp(-p.h * pait); c[BC_EPH] = exp(p.h * pait);
+    c[BC_TRDSW] = trd; c[BC_AMX] = amx; c[BC_ALBD] = albd;
+    c[BC_GRDD] = trd + (1.0 - trd) * (p.p3 * exp(-p.h * pait) + p.p4 * exp(p.h * pait));
+    // mcf_bigleaf
+    const double paitb = pai / (1 - clump);
+    c[BC_TRD] = (1 - clump * clump) * exp(-paitb) + clump * clump;
+    const double d = zeroplane(h, pai);
+    const double Be = sqrt(0.003 + (0.2 * pai) / 2);
+    c[BC_D] = d; c[BC_HMD] = h - d; c[BC_HDE] = (h - d) * exp(-kKa / Be);
+    c[BC_BELIM] = 0.4 / sqrt(0.003 + (0.2 * pai) / 2);
+    c[BC_ZREFD] = zref - d; c[BC_LEAFDD] = 0.71 * leafd; c[BC_OMC] = 0.5 * (lref + ltra);
+    c[BC_SHADEC] = (1.0 - exp(-pai)) / pai;
+    const Stomp st = stom_params(h, lat, vegx);
+    c[BC_RSMX] = st.Rsmx; c[BC_PSIW0] = st.psiw0; c[BC_KK] = st.kk; c[BC_RAT] = st.rat;
+    c[BC_MUDEN] = exp(-st.kk * st.psiw0) - 1.0;
+    // ground_flux
+    const double frs = Vm + Vq;
+    c[BC_C1] = (0.57 + 1.73 * Vq + 0.93 * Vm) / (1.0 - 0.74 * Vq - 0.49 * Vm) - 2.8 * frs * (1.0 - frs);
+    c[BC_C3] = 1.0 + 2.6 * pow(Mc, -0.5);
+    c[BC_C4] = 0.03 + 0.7 * frs * frs;
+    c[BC_MU1] = 2400.0 * rho / 2.64; c[BC_MU2] = 1.06 * rho; c[BC_RHO] = rho;
+}
+
+void bl_time_consts(int64_t n, const int32_t* year, const int32_t* month, const int32_t* day, const double* hour, double* out) {
+    for (int64_t i = 0; i < n; ++i) {                                             // sun_position's date terms
+        const int jd = julday(year[i], month[i], day[i]);
+        const double m = 6.24004077 + 0.01720197 * (jd - 2451545.0);
+        const double dec = (kPi * 23.5 / 180) * cos(2 * kPi * ((jd - 159.5) / 365.25));
+        double* t = out + i * TC_COUNT;
+        t[TC_HOUR] = hour[i];
+        t[TC_EOT] = -7.659 * sin(m) + 9.863 * sin(2 * m + 3.5932);
+        t[TC_SINDEC] = sin(dec);
+        t[TC_COSDEC] = cos(dec);
+    }
+}
+
+void pmp_point_consts(double zref, double h, double pai, double rho, double Vm, double Vq, double Mc, double* c) {
+    const double dp = zeroplane(h, pai);
+    const double zmp = roughlength(h, pai, dp, 0);
+    const double frs = Vm + Vq;
+    c[PC_LOGZ] = log((zref - dp) / zmp);
+    c[PC_C1] = (0.57 + 1.73 * Vq + 0.93 * Vm) / (1.0 - 0.74 * Vq - 0.49 * Vm) - 2.8 * frs * (1.0 - frs);
+    c[PC_C3] = 1.0 + 2.6 * pow(Mc, -0.5);
+    c[PC_C4] = 0.03 + 0.7 * frs * frs;
+    c[PC_RHO] = rho;
+}
+
+double wh_zeroplane() { return zeroplane(0.12, 1); }
+double wh_hde() {
+    const double d = zeroplane(0.12, 1);
+    return (0.12 - d) * exp(-kKa / sqrt(0.003 + (0.2 * 1) / 2));
+}
+
+}  // namespace mcf

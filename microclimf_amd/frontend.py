@@ -401,11 +401,13 @@ def block_reduce(a, crows: int, ccols: int, how: str = "mean"):
 
 def runpointmodela(climarray: Mapping, obstime: Mapping, reqhgt: float, dtm: Mapping, vegp: Mapping, soilc: Mapping, *,
                    lats, lons, matemp: float | None = None, zref: float = 2.0, windhgt: float = 2.0, soilm=None,
-                   dTmx: float = 25.0, maxiter: int = 20, yearG: bool = True) -> list:
+                   dTmx: float = 25.0, maxiter: int = 20, yearG: bool = True, device: int | None = None) -> list:
     """`runpointmodela(climarrayr, tme, reqhgt, dtm, vegp, soilc, ...)` (R/Cppwrappers.R:208-263): the point model once
     per cell of the coarse climate grid.  `climarray[k]`: [crows, ccols, T]; `lats`, `lons`: [crows, ccols] (the reference
     takes them from the climate raster's CRS).  Returns the row-major list of micropoints (None where the cell has no
-    data), as the reference's `pointo`."""
+    data), as the reference's `pointo`.  `device` = None: one cell at a time on the host, as the reference does; an int:
+    the cells with data as ONE batch on that device (weatherhgt_batch, BigLeafBatch, pointmprocess_batch; whole days
+    only), with the soil moisture model and `.soilbelowT` per cell on the host as before."""
     cr, cc, T = np.shape(climarray["temp"])
     mxhgt = float(np.nanmax(np.asarray(vegp["hgt"], dtype=np.float64)))
     wdir = np.array([getmode(np.asarray(climarray["winddir"])[:, :, k]) for k in range(T)])
@@ -415,6 +417,7 @@ def runpointmodela(climarray: Mapping, obstime: Mapping, reqhgt: float, dtm: Map
     gr = float(np.nanmean(np.asarray(soilc["groundr"], dtype=np.float64)))
     P = SOILPARAMETERS
     out = []
+    batch = []                                    # device: (list position, weather, vegp_p, groundp_p, soilm, lat, long)
     for i in range(cr):
         for j in range(cc):
             if np.isnan(climarray["temp"][i, j, 0]) or np.isnan(vc["hgt"][i, j, 0]):
@@ -428,11 +431,76 @@ def runpointmodela(climarray: Mapping, obstime: Mapping, reqhgt: float, dtm: Map
             sn = int(st[i, j]) - 1                                                                       # .togp
             groundp_p = np.array([gr, 0.0, 180.0, 0.97, P["rho"][sn], P["Vm"][sn], P["Vq"][sn], P["Mc"][sn], P["b"][sn],
                                   P["psi_e"][sn], P["Smax"][sn], P["Smin"][sn], P["Smin"][sn], P["Smin"][sn], P["Smin"][sn]])
+            if device is not None:
+                batch.append((len(out), w, vegp_p, groundp_p, None if soilm is None else np.asarray(soilm)[i, j, :],
+                              float(lats[i, j]), float(lons[i, j])))
+                out.append(None)
+                continue
             out.append(runpointmodel(w, reqhgt, dtm, vegp, soilc, zref=zref, windhgt=windhgt,
                                      soilm=None if soilm is None else np.asarray(soilm)[i, j, :], matemp=matemp, dTmx=dTmx,
                                      maxiter=maxiter, yearG=yearG, lat=float(lats[i, j]), long=float(lons[i, j]),
                                      vegp_p=vegp_p, groundp_p=groundp_p, soiltype=soiltype, mxhgt=mxhgt))
+    if batch:
+        for (pos, *_), m in zip(batch, _runpointmodel_batch(batch, obstime, reqhgt, zref=zref, windhgt=windhgt,
+                                                            matemp=matemp, dTmx=dTmx, maxiter=maxiter, yearG=yearG,
+                                                            soiltype=soiltype, mxhgt=mxhgt, device=int(device))):
+            out[pos] = m
     return out
+
+
+def _runpointmodel_batch(batch, obstime, reqhgt, *, zref, windhgt, matemp, dTmx, maxiter, yearG, soiltype, mxhgt,
+                         device) -> list:
+    """`runpointmodel` for the cells of `runpointmodela` as one batch on the device: the same steps in the same order,
+    the three point-model operators through their `_batch` entries."""
+    obst = {k: np.asarray(obstime[k]) for k in ("year", "month", "day", "hour")}
+    ws = [{k: np.array(b[1][k], dtype=np.float64, copy=True) for k in WEATHER if k in b[1]} for b in batch]
+    n = len(ws[0]["temp"])
+    lat = np.array([b[5] for b in batch])
+    lon = np.array([b[6] for b in batch])
+    windhgt = zref if windhgt is None else windhgt
+    mat = [float(np.mean(w["temp"])) if matemp is None else matemp for w in ws]
+    if zref != windhgt:
+        for w in ws:
+            w["windspeed"] = w["windspeed"] * np.log(67.8 * zref - 5.42) / np.log(67.8 * windhgt - 5.42)
+    if n < 8760:
+        yearG = False
+    cols = ("temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed")
+    zout = mxhgt if mxhgt > 2 else 2.0
+    if zout > zref:
+        w2 = pointmodel.weatherhgt_batch(obst, {k: np.stack([w[k] for w in ws]) for k in cols}, zref, zout, zout, lat, lon,
+                                         device=device)
+        for p, w in enumerate(ws):
+            if not np.isnan(np.mean(w2["temp"][p])):
+                for k in ("temp", "relhum", "windspeed"):
+                    w[k] = w2[k][p].copy()
+        zref = zout
+    sms = []
+    for b, w in zip(batch, ws):
+        w["windspeed"] = np.maximum(w["windspeed"], 0.5)
+        sm = b[4]
+        if sm is None:
+            ii = int(soiltype) - 1
+            p = SOILPARAMSP
+            sd = pointmodel.soilmCpp(w, p["rmu"][ii], p["mult"][ii], p["pwr"][ii], p["Smax"][ii], p["Smin"][ii], p["Ksat"][ii],
+                                     p["a"][ii])
+            sm = spline_fmm(sd, n)
+        sms.append(np.asarray(sm, dtype=np.float64))
+    W = {k: np.stack([w[k] for w in ws]) for k in cols}
+    SM = np.stack(sms)
+    vp = np.stack([b[2] for b in batch])
+    gp = np.stack([b[3] for b in batch])
+    bl = pointmodel.BigLeafBatch(obst, W, vp, gp, SM, lat, lon, dTmx, zref, maxiter, 0.5, 0.5, yearG, device=device)
+    pp = pointmodel.pointmprocess_batch({"windspeed": W["windspeed"], "tc": W["temp"], "rh": W["relhum"], "pk": W["pres"],
+                                         "uf": bl["uf"], "soilm": SM, "RabsG": bl["RabsG"]},
+                                        zref, vp[:, 0], vp[:, 1], gp[:, 4], gp[:, 5], gp[:, 6], gp[:, 7], device=device)
+    res = []
+    for p, w in enumerate(ws):
+        dfo = {k: pp[k][p].copy() for k in pp}
+        dfo.update(G=bl["G"][p].copy(), soilm=sms[p], Tg=bl["Tg"][p].copy(), Tc=bl["Tc"][p].copy())
+        Tbz = soilbelowT(dfo, reqhgt) if reqhgt < 0 else None
+        res.append({"weather": w, "obstime": obst, "dfo": dfo, "Tbz": Tbz, "lat": float(lat[p]), "long": float(lon[p]),
+                    "zref": zref, "subs": np.arange(1, n + 1), "ntme": n, "matemp": mat[p], "bigleaf_err": float(bl["err"][p])})
+    return res
 
 
 def prepare_grid_inputs_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: float, vegp: Mapping, soilc: Mapping,

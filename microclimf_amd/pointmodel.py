@@ -3,7 +3,9 @@
 `runpointmodel` strings them together into the grid solver's `pointm` (R/Cppwrappers.R:119-138).
 
 They are O(tsteps) serial series for one point and run on the host inside libmcfhip (mcf_pointmodel.cpp), as
-they run on the host in the reference; the grid solver itself has no CPU path.
+they run on the host in the reference; the grid solver itself has no CPU path.  `BigLeafBatch`, `weatherhgt_batch` and
+`pointmprocess_batch` run the same operators for many points at once on the device (mcf_pointbatch.hip): arrays with a
+leading point axis in, the single-point wrappers' keys with a leading point axis out.
 """
 from __future__ import annotations
 
@@ -112,6 +114,101 @@ def weatherhgtCpp(obstime, climdata, zin, uzin, zout, lat, lon) -> dict:
     out = {k: np.array(v, dtype=np.float64, copy=True) for k, v in climdata.items()}
     out.update(res)
     return out
+
+
+# ---- many points at once, on the device (include/mcf.h: the `_batch` entries) ---------------------------------------------
+def _mat(a, shape, name):
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if v.shape != shape:
+        raise ValueError(f"{name}: expected shape {shape}, got {v.shape}")
+    return v
+
+
+def _weather_batch(climdata: Mapping, P: int, n: int):
+    w = _abi.PointWeather()
+    keep = []
+    for f in _abi.POINT_WEATHER_FIELDS:
+        if f == "precip":
+            setattr(w, f, None)
+            continue
+        v = _mat(climdata[f], (P, n), f"climdata${f}")
+        keep.append(v)
+        setattr(w, f, v.ctypes.data_as(_abi.c_double_p))
+    return w, keep
+
+
+def BigLeafBatch(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, zref=2.0, maxiter=100, bwgt=0.5, tol=0.5,
+                 yearG=True, *, device: int = 0, points_per_block: int = 0) -> dict:
+    """BigLeafCpp for P points on device `device` (mcf_bigleaf_batch).  `climdata[k]` and `soilm`: [P, n]; `obstime`:
+    shared, [n]; `vegp`: [P, >= 9]; `groundp`: [P, >= 12]; `lat`, `lon`: [P].  Whole days only (n % 24 == 0).  Returns
+    BigLeafCpp's keys: the eleven series [P, n], `err` [P] and `iters` [P], each point's own."""
+    lib = _abi.load()
+    sm = np.ascontiguousarray(np.asarray(soilm, dtype=np.float64))
+    if sm.ndim != 2:
+        raise ValueError("soilm: expected [P, n]")
+    P, n = sm.shape
+    t, k1 = _obstime(obstime, n)
+    w, k2 = _weather_batch(climdata, P, n)
+    vp = np.asarray(vegp, dtype=np.float64)
+    gp = np.asarray(groundp, dtype=np.float64)
+    if vp.ndim != 2 or gp.ndim != 2 or vp.shape[0] != P or gp.shape[0] != P or vp.shape[1] < 9 or gp.shape[1] < 12:
+        raise ValueError("vegp needs [P, >= 9] and groundp [P, >= 12] entries")
+    vp10 = np.zeros((P, 10))
+    vp10[:, :min(vp.shape[1], 10)] = vp[:, :10]
+    gp12 = np.ascontiguousarray(gp[:, :12])
+    la, lo = _vec(lat, P, "lat"), _vec(lon, P, "lon")
+    out = _abi.BigLeafBatchOut()
+    res = {}
+    for f in _abi.BIGLEAF_FIELDS:
+        res[f] = np.zeros((P, n))
+        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
+    res["err"] = np.zeros(P)
+    res["iters"] = np.zeros(P, dtype=np.int32)
+    out.err = res["err"].ctypes.data_as(_abi.c_double_p)
+    out.iters = res["iters"].ctypes.data_as(_abi.c_int32_p)
+    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    _abi.check(lib.mcf_bigleaf_batch(P, n, C.byref(t), C.byref(w), d(vp10), d(gp12), d(sm), d(la), d(lo), float(dTmx),
+                                     float(zref), int(maxiter), float(bwgt), float(tol), 1 if yearG else 0,
+                                     int(points_per_block), int(device), C.byref(out)))
+    return res
+
+
+def weatherhgt_batch(obstime, climdata, zin, uzin, zout, lat, lon, *, device: int = 0, points_per_block: int = 0) -> dict:
+    """weatherhgtCpp for P points on the device (mcf_weatherhgt_batch): a copy of `climdata` ([P, n] each) with temp,
+    relhum and windspeed moved from zin / uzin to zout."""
+    lib = _abi.load()
+    tc = np.asarray(climdata["temp"], dtype=np.float64)
+    if tc.ndim != 2:
+        raise ValueError("climdata$temp: expected [P, n]")
+    P, n = tc.shape
+    t, k1 = _obstime(obstime, n)
+    w, k2 = _weather_batch(climdata, P, n)
+    la, lo = _vec(lat, P, "lat"), _vec(lon, P, "lon")
+    res = {k: np.zeros((P, n)) for k in ("temp", "relhum", "windspeed")}
+    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    _abi.check(lib.mcf_weatherhgt_batch(P, n, C.byref(t), C.byref(w), float(zin), float(uzin), float(zout), d(la), d(lo),
+                                        int(points_per_block), int(device), *[d(res[k]) for k in ("temp", "relhum", "windspeed")]))
+    out = {k: np.array(v, dtype=np.float64, copy=True) for k, v in climdata.items()}
+    out.update(res)
+    return out
+
+
+def pointmprocess_batch(pointvars, zref, h, pai, rho, Vm, Vq, Mc, *, device: int = 0) -> dict:
+    """pointmprocess for P points on the device (mcf_pointmprocess_batch); `pointvars` has windspeed, tc, rh, pk, uf,
+    soilm, RabsG as [P, n]; h, pai, rho, Vm, Vq, Mc: [P]."""
+    lib = _abi.load()
+    tc = np.asarray(pointvars["tc"], dtype=np.float64)
+    if tc.ndim != 2:
+        raise ValueError("pointvars$tc: expected [P, n]")
+    P, n = tc.shape
+    ins = [_mat(pointvars[k], (P, n), k) for k in ("windspeed", "tc", "rh", "pk", "uf", "soilm", "RabsG")]
+    par = [_vec(v, P, k) for k, v in (("h", h), ("pai", pai), ("rho", rho), ("Vm", Vm), ("Vq", Vq), ("Mc", Mc))]
+    keys = ("umu", "kp", "muGp", "DDp", "T0p", "dtrp")
+    res = {k: np.zeros((P, n)) for k in keys}
+    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    _abi.check(lib.mcf_pointmprocess_batch(P, n, *[d(v) for v in ins], float(zref), *[d(v) for v in par], int(device),
+                                           *[d(res[k]) for k in keys]))
+    return res
 
 
 def pointmodelsnow(obstime, climdata, vegp, other, snowenv, tol: float = 0.5, maxiter: float = 100) -> dict:
