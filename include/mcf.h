@@ -963,6 +963,29 @@ typedef struct mcf_pointsnow_out {
 } mcf_pointsnow_out;
 int mcf_pointmodelsnow(int64_t n, const mcf_obstime *obstime, const mcf_point_weather *weather, const double *vegp,
                        const double *other, int32_t snowenv, double tol, double maxiter, mcf_pointsnow_out *out);
+/* mcf_pointmodelsnow for P points at once, on the device (mcf_pointbatch.hip): what `runsnowmodel` runs once per cell of
+ * the climate grid with array weather.  Semantics are those of mcf_pointmodelsnow, per point and without cross-talk.
+ * Layout: series [P][n] (sdepc / sdepg [P][n + 1]), a point's series contiguous; `weather` [P][n] each, precip too;
+ * `obstime` [n] is shared; vegp [P][4], other [P][7], snowenv [P]; mxdif / iters [P], each point's own.
+ * Freeze rule: a pass is the sweep over the series and GFluxCppsnow on the new Tg; a point stops after the ground-flux
+ * update of the pass in which its mxdif <= tol, or when ++iter > maxiter (at most floor(maxiter) + 1 passes, as on the
+ * host); a stopped point is frozen while the others go on, and G is its flux after its last update.  The running maximum
+ * ignores NaN as fmax does.  A point's bits do not depend on the batch it is in, on `points_per_block` or on the run.
+ * Refusals, returned before the device is touched: null arguments or null output vectors, P < 1, n % 24 != 0 (WHOLE
+ * DAYS only, as for the other `_batch` entries), n < 24, n > 2^28, points_per_block < 0; then MCF_ERR_NO_DEVICE without
+ * a HIP device.  Memory: 36 series of 8 n bytes per point live on the device (rows padded to whole waves of 64 points;
+ * sized as 45 to leave room): points are processed in blocks sized from the free memory, or of `points_per_block`
+ * points (0 = from free memory); all points of a block are in flight in one launch. */
+typedef struct mcf_pointsnow_batch_out { /* caller-allocated; a point's series contiguous */
+    double *Tc, *Tg, *sdenc, *sdeng, *G, *RswabsG, *RlwabsG, *tr, *umu, *sublmelt, *tempmelt, *rainmelt, *sstemp; /* [P][n] */
+    double *sdepc, *sdepg; /* [P][n+1] */
+    double *mxdif;         /* [P] */
+    int32_t *iters;        /* [P] */
+} mcf_pointsnow_batch_out;
+int mcf_pointmodelsnow_batch(int64_t P, int64_t n, const mcf_obstime *obstime,
+                             const mcf_point_weather *weather /* [P][n], precip too */, const double *vegp /* [P][4] */,
+                             const double *other /* [P][7] */, const int32_t *snowenv /* [P] */, double tol, double maxiter,
+                             int64_t points_per_block, int32_t device, mcf_pointsnow_batch_out *out);
 /* ---- fast snow method for subset runs (R/internal.R:2627-2776 `.snowmodelq1`): its three kernels of arithmetic ----
  * mcf_canintfrac replaces _microclimf_canintfrac (src/microclimfCpp.cpp:5417-5450): frac = canopysnowintCpp(hgt, pai,
  *   uf, prec, tc, Li) / prec per cell, 0.5 everywhere when prec is not > 0, NaN where hgt is NA.  Host code.

@@ -171,8 +171,17 @@ POINTSNOW_FIELDS = ("Tc", "Tg", "sdepc", "sdepg", "sdenc", "sdeng", "G", "Rswabs
                     "tempmelt", "rainmelt", "sstemp")
 
 
+# mcf_pointsnow_batch_out lists the [n + 1] depths after the [n] series
+POINTSNOW_BATCH_FIELDS = tuple(k for k in POINTSNOW_FIELDS if k not in ("sdepc", "sdepg")) + ("sdepc", "sdepg")
+
+
 class PointSnowOut(C.Structure):
     _fields_ = [(k, c_double_p) for k in POINTSNOW_FIELDS] + [("mxdif", C.c_double), ("iters", C.c_int32)]
+
+
+class PointSnowBatchOut(C.Structure):
+    """include/mcf.h mcf_pointsnow_batch_out: series [P][n] (sdepc / sdepg [P][n + 1]), mxdif / iters [P]"""
+    _fields_ = ([(k, c_double_p) for k in POINTSNOW_BATCH_FIELDS] + [("mxdif", c_double_p), ("iters", c_int32_p)])
 
 
 class SnowDriverIn(C.Structure):
@@ -213,7 +222,7 @@ EXPORTS = (
     "mcf_snowplan_create", "mcf_snowplan_destroy", "mcf_snowplan_chunks", "mcf_snowplan_surface", "mcf_snowplan_handover", "mcf_snowplan_apply3",
     "mcf_snowplan_surface_partial", "mcf_snowplan_prepare_chunk", "mcf_snowplan_run_chunk", "mcf_snowplan_pack_halo",
     "mcf_snowplan_prepare_chunk_dev",
-    "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch",
+    "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch", "mcf_pointmodelsnow_batch",
     "mcf_bigleaf", "mcf_soilm", "mcf_pointmprocess", "mcf_weatherhgt", "mcf_man", "mcf_pointmodelsnow", "mcf_canintfrac", "mcf_meltmu", "mcf_meltmu2", "mcf_tpicalc",
     "mcf_nc_create", "mcf_nc_write_host", "mcf_nc_write_plan", "mcf_nc_close",
     "mcf_flowacc", "mcf_topidx",
@@ -447,6 +456,9 @@ def load() -> C.CDLL:
     lib.mcf_pointmodelsnow.restype = C.c_int
     lib.mcf_pointmodelsnow.argtypes = [C.c_int64, C.POINTER(Obstime), C.POINTER(PointWeather), c_double_p, c_double_p,
                                        C.c_int32, C.c_double, C.c_double, C.POINTER(PointSnowOut)]
+    lib.mcf_pointmodelsnow_batch.restype = C.c_int
+    lib.mcf_pointmodelsnow_batch.argtypes = [C.c_int64, C.c_int64, OT, PW, c_double_p, c_double_p, c_int32_p, C.c_double,
+                                             C.c_double, C.c_int64, C.c_int32, C.POINTER(PointSnowBatchOut)]
     lib.mcf_man.restype = C.c_int
     lib.mcf_man.argtypes = [C.c_int64, c_double_p, C.c_int32, c_double_p]
     lib.mcf_flowacc.restype = C.c_int

@@ -26,10 +26,21 @@ enum BlConst : int {
 enum BlTime : int { TC_HOUR = 0, TC_EOT, TC_SINDEC, TC_COSDEC, TC_COUNT };
 // per point of mcf_pointmprocess_batch
 enum PmpConst : int { PC_LOGZ = 0, PC_C1, PC_C3, PC_C4, PC_RHO, PC_COUNT };
+// per point of mcf_pointmodelsnow_batch, [PS_COUNT] doubles: what pointmodelsnow derives from vegp, other and snowenv alone
+// (cpp:4000-4169): the site for the sun, the canopy without snow, the pack's start, snowdenp's row, the density of the whole
+// run (the reference never updates it) and GFluxCppsnow's 6-hour mean of the constant Gmu that follows from it
+enum PsConst : int {
+    PS_SINLAT = 0, PS_COSLAT, PS_LON, PS_SLOPE, PS_COSSL, PS_SINSL, PS_ASPECT,
+    PS_PAI, PS_HGT, PS_LTRA, PS_CLUMP, PS_ZREF, PS_ISNOWD, PS_ISNOWA,
+    PS_DENA, PS_DENB, PS_DENC, PS_DEND, PS_SDEN0, PS_GMUD,
+    PS_COUNT
+};
 
 void bl_point_consts(const double* vegp, const double* groundp, double lat, double lon, double zref, double* out);
 void bl_time_consts(int64_t n, const int32_t* year, const int32_t* month, const int32_t* day, const double* hour, double* out);
 void pmp_point_consts(double zref, double h, double pai, double rho, double Vm, double Vq, double Mc, double* out);
+void ps_point_consts(const double* vegp, const double* other, int32_t snowenv, double* out);
+void ps_albedo(const double* prec, int64_t n, double* alb);   // snowalbCpp: a serial hour counter, host work
 double wh_zeroplane();   // zeroplane(0.12, 1) of weatherhgtCpp's fixed canopy
 double wh_hde();         // ... and its (h - d) exp(-ka / Be)
 

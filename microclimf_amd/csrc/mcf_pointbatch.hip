@@ -1,5 +1,5 @@
-// mcf_pointbatch.hip — the big-leaf point model for MANY points at once (gfx950): mcf_bigleaf_batch, mcf_weatherhgt_batch,
-// mcf_pointmprocess_batch (include/mcf.h).  One point of BigLeafCpp is a serial job; P points of `runpointmodela` are not:
+// mcf_pointbatch.hip — the point models for MANY points at once (gfx950): mcf_bigleaf_batch, mcf_weatherhgt_batch,
+// mcf_pointmprocess_batch and, further down with its own introduction, mcf_pointmodelsnow_batch (include/mcf.h).  One point of BigLeafCpp is a serial job; P points of `runpointmodela` are not:
 // the points are independent, and inside one iteration every hour reads only its own state of the iteration before
 // (mcf_pointmodel.cpp, the loop of mcf_bigleaf).  What couples hours is GFluxCpp: daily means, a 6-hour circular trailing
 // mean, the day's min / max on iteration 0, and with yearG a 91-day circular mean of daily values and one sum over the
@@ -65,9 +65,9 @@ __device__ __forceinline__ double cpair(double tc) { return 2e-05 * p2(tc) + 0.0
 
 struct Sun { double zend, zenr, azid; };
 // sun_position with the date terms (eot, sin / cos of the declination) and sin / cos of the latitude from the host
-__device__ Sun sun_position(const double* __restrict__ c, const double* __restrict__ t) {
-    const double sd = t[mcf::TC_SINDEC], cd = t[mcf::TC_COSDEC], sl = c[mcf::BC_SINLAT], cl = c[mcf::BC_COSLAT];
-    const double st = t[mcf::TC_HOUR] + (4.0 * c[mcf::BC_LON] + t[mcf::TC_EOT]) / 60.0;
+__device__ Sun sun_position(double sl, double cl, double lon, const double* __restrict__ t) {
+    const double sd = t[mcf::TC_SINDEC], cd = t[mcf::TC_COSDEC];
+    const double st = t[mcf::TC_HOUR] + (4.0 * lon + t[mcf::TC_EOT]) / 60.0;
     const double tt = 0.261799 * (st - 12);
     const double ct = cos(tt), stt = sin(tt);
     const double coh = sd * sl + cd * cl * ct;
@@ -83,11 +83,12 @@ __device__ Sun sun_position(const double* __restrict__ c, const double* __restri
     if (cazi < 0) azi = sazi < 0 ? 180 - azi : 540 - azi;
     return {z, z * kToRad, azi};
 }
-__device__ double solar_index(const double* __restrict__ c, double zend, double azid) {
+// slope, its cosine and sine, aspect: s[0..3] (BC_SLOPE.. / PS_SLOPE.. of the point's table)
+__device__ double solar_index(const double* __restrict__ s, double zend, double azid) {
     double si;
     if (zend > 90.0) si = 0;
-    else if (c[mcf::BC_SLOPE] == 0.0) si = cos(zend * kToRad);
-    else si = cos(zend * kToRad) * c[mcf::BC_COSSL] + sin(zend * kToRad) * c[mcf::BC_SINSL] * cos((azid - c[mcf::BC_ASPECT]) * kToRad);
+    else if (s[0] == 0.0) si = cos(zend * kToRad);
+    else si = cos(zend * kToRad) * s[1] + sin(zend * kToRad) * s[2] * cos((azid - s[3]) * kToRad);
     return si < 0.0 ? 0.0 : si;
 }
 struct Ext { double k, kd, Kc; };
@@ -104,11 +105,31 @@ __device__ Ext canopy_k(double zenr, double x, double si) {
     if (si == 0) { e.kd = 1.0; e.Kc = 600.0; }
     return e;
 }
+// the diffuse two-stream coefficients the direct ones need: from the host's table (big leaf: they depend on the point
+// only) or from two_stream_dif below (snow: the canopy above the pack changes with every step)
+struct Dif { double om, a, gma, J, del, h, u1, S1, D1, D2, p3, p4; };
+__device__ Dif two_stream_dif(double pait, double x, double lref, double ltra, double gref) {
+    Dif p;
+    p.om = lref + ltra; p.a = 1.0 - p.om; p.del = lref - ltra; p.J = 1.0 / 3.0;
+    if (x != 1.0) {
+        double mla = 9.65 * pow(3.0 + x, -1.65);
+        if (mla > kPi / 2.0) mla = kPi / 2.0;
+        p.J = cos(mla) * cos(mla);
+    }
+    p.gma = 0.5 * (p.om + p.J * p.del);
+    p.h = sqrt(p.a * p.a + 2.0 * p.a * p.gma);
+    p.S1 = exp(-p.h * pait);
+    p.u1 = p.a + p.gma * (1.0 - 1.0 / gref);
+    const double u2 = p.a + p.gma * (1.0 - gref);
+    p.D1 = (p.a + p.gma + p.h) * (p.u1 - p.h) * 1.0 / p.S1 - (p.a + p.gma - p.h) * (p.u1 + p.h) * p.S1;
+    p.D2 = (u2 + p.h) * 1.0 / p.S1 - (u2 - p.h) * p.S1;
+    p.p3 = (1.0 / (p.D2 * p.S1)) * (u2 + p.h);
+    p.p4 = (-p.S1 / p.D2) * (u2 - p.h);
+    return p;
+}
 struct Dir { double sig, p5, p6, p7, p8, p9, p10; };
-__device__ Dir two_stream_dir(const double* __restrict__ c, double kd) {
-    const double pait = c[mcf::BC_PAITSW], a = c[mcf::BC_A], gma = c[mcf::BC_GMA], om = c[mcf::BC_OM], J = c[mcf::BC_J],
-                 del = c[mcf::BC_DEL], u1 = c[mcf::BC_U1], h = c[mcf::BC_HH], D1 = c[mcf::BC_D1], D2 = c[mcf::BC_D2],
-                 S1 = c[mcf::BC_S1], gref = c[mcf::BC_GREF];
+__device__ Dir two_stream_dir(double pait, const Dif& f, double gref, double kd) {
+    const double a = f.a, gma = f.gma, om = f.om, J = f.J, del = f.del, u1 = f.u1, h = f.h, D1 = f.D1, D2 = f.D2, S1 = f.S1;
     Dir p;
     const double sig = kd * kd + gma * gma - p2(a + gma);
     const double ss = 0.5 * (om + J * del / kd) * kd;
@@ -255,7 +276,7 @@ __global__ __launch_bounds__(kStepBlock) void k_bl_setup(BlDev D) {
     const double* __restrict__ smrow = D.soilm + (int64_t)p * D.n;
     const double Rsw = D.Rsw[q], Rdif = D.Rdif[q], tc = D.tc[q], sm = smrow[i];
     const double pai = c[mcf::BC_PAI], gref = c[mcf::BC_GREF], lref = c[mcf::BC_LREF], x = c[mcf::BC_X];
-    Sun sp = sun_position(c, t);
+    Sun sp = sun_position(c[mcf::BC_SINLAT], c[mcf::BC_COSLAT], c[mcf::BC_LON], t);
     // canopy conductance of the iteration body: canopy_k(zenr, x, cos zenr) with the UNCLAMPED zenith, then canopy_cond
     const Ext kb = canopy_k(sp.zenr, x, cos(sp.zenr));
     D.gC[q] = canopy_cond(c, Rsw, Rdif, kb.k, sm);
@@ -266,11 +287,13 @@ __global__ __launch_bounds__(kStepBlock) void k_bl_setup(BlDev D) {
         if (Rsw > 0.0) {
             const double pait = c[mcf::BC_PAITSW], clump = c[mcf::BC_CLUMP], trd = c[mcf::BC_TRDSW], amx = c[mcf::BC_AMX],
                          emh = c[mcf::BC_EMH], eph = c[mcf::BC_EPH];
-            const double si = solar_index(c, sp.zend, sp.azid);
+            const double si = solar_index(c + mcf::BC_SLOPE, sp.zend, sp.azid);
             if (sp.zenr > kPi / 2.0) sp.zenr = kPi / 2.0;
             const double cosz = cos(sp.zenr);
             const Ext kp = canopy_k(sp.zenr, x, si);
-            const Dir d = two_stream_dir(c, kp.kd);
+            const Dif f{c[mcf::BC_OM], c[mcf::BC_A], c[mcf::BC_GMA], c[mcf::BC_J], c[mcf::BC_DEL], c[mcf::BC_HH], c[mcf::BC_U1],
+                        c[mcf::BC_S1], c[mcf::BC_D1], c[mcf::BC_D2], 0.0, 0.0};
+            const Dir d = two_stream_dir(pait, f, gref, kp.kd);
             double Rbeam = (Rsw - Rdif) / cosz;
             if (Rbeam > 1352.0) Rbeam = 1352.0;
             double trb = pow(clump, kp.Kc);
@@ -296,7 +319,7 @@ __global__ __launch_bounds__(kStepBlock) void k_bl_setup(BlDev D) {
     } else {
         alb = gref;
         if (Rsw > 0) {
-            const double si = solar_index(c, sp.zend, sp.azid);
+            const double si = solar_index(c + mcf::BC_SLOPE, sp.zend, sp.azid);
             if (sp.zenr > kPi / 2.0) sp.zenr = kPi / 2.0;
             const double dirr = (Rsw - Rdif) / cos(sp.zenr);
             radG = (1 - gref) * (Rdif + si * dirr);
@@ -617,6 +640,312 @@ __global__ __launch_bounds__(kGroup) void k_pointmprocess(PmpDev D) {
     D.dtrp[q] = mx - mn;
 }
 
+// =====================================================================================================================
+// pointmodelsnow (cpp:4000-4169) for many points: mcf_pointmodelsnow_batch.  Unlike BigLeafCpp, the hours of a pass are NOT
+// independent: the pack (two depths, two ages) is carried from step to step and feeds back into the canopy above it (pai and
+// hgt shrink with the ground pack; the two-stream solution, the roughness and the turbulent conductance follow).  Points are
+// independent, and much of a step does not depend on the pack.  So: one lane per point marching through time, and
+// everything else one lane per (point, hour) or (point, day).
+//
+//   k_ps_transpose    between the caller's [P][n] and the tables' [n][points]: the sweep's 64 lanes then touch whole lines
+//   k_ps_setup        once, per (point, hour): what a step needs that does not depend on the pack (ea, tdew, cpair, phair, the
+//                     sun, the capped beam, RswabsC and RabsC, canopy_k, exp(tc / 2.59), the rain melt), the initial state
+//   k_ps_sweep        per pass, per point, serial over the steps, the pack in registers; ONE wave per workgroup, so that the
+//                     waves of a batch spread over the CUs and each has a SIMD to itself (the kernel is a chain of dependent
+//                     fp64 operations and nothing runs beside it)
+//   k_ps_gflux        per pass, per (point, day): GFluxCppsnow — the day's mean, the 6-hour circular trailing mean of T - Td
+//                     (it wraps round the series end), times Gmud 1.1171; the host's order of summation
+//   k_ps_finish       per pass: convergence PER POINT, counts the points that go on
+//
+// The density of the pack never changes during a run: the reference keeps sdenc[i] at its initial value, and so does
+// mcf_pointmodelsnow.  Gmu is then one number per point and comes, with its 6-hour mean, from the host (PS_GMUD).  The albedo
+// is a serial hour counter with an integer division: host work too (mcf::ps_albedo), uploaded.
+// =====================================================================================================================
+struct PsDev {
+    int64_t n, nd, ps;             // steps, days, the tables' row length (points of a block rounded up to whole waves)
+    int pb;                        // points in this block
+    // tables [n][ps], the point fastest.  inputs (ea arrives as relhum):
+    double *tc, *ea, *pk, *u2, *prec, *Rsw, *Rdif, *Rlw, *alb;
+    // hoisted by k_ps_setup
+    double *tdew, *cp, *ph, *RabsC, *RswabsC, *cosz, *Rbeam, *kd, *Kc, *erhos, *mRc;
+    // state of the relaxation
+    double *Tc, *Tg, *te, *psim, *psih, *G;
+    // results of the last pass
+    double *RswabsG, *RlwabsG, *tr, *umu, *mSc, *mMc, *Tcp;
+    double *sdepc, *sdepg;         // [n + 1][ps]
+    const double* consts;          // [pb][PS_COUNT]
+    const double* tconst;          // [n][TC_COUNT]
+    double* mxd;                   // [ps] the pass's max |dT|
+    double* mxdif;                 // [ps] ... of the point's last pass
+    int* active;                   // [ps]
+    int* iters;                    // [ps]
+    int* going;                    // points that go on after this pass
+    double tol, maxiter;
+};
+
+// dst[c * ldd + r] = src[r * lds + c] for r < rows, c < cols
+__global__ __launch_bounds__(256) void k_ps_transpose(const double* __restrict__ src, int64_t rows, int64_t cols, int64_t lds,
+                                                      double* __restrict__ dst, int64_t ldd) {
+    __shared__ double tile[32][33];
+    const int64_t tx = (cols + 31) / 32;
+    const int64_t by = (int64_t)blockIdx.x / tx, bx = (int64_t)blockIdx.x - by * tx;
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+    for (int k = ly; k < 32; k += 8) {
+        const int64_t r = by * 32 + k, c = bx * 32 + lx;
+        if (r < rows && c < cols) tile[k][lx] = src[r * lds + c];
+    }
+    __syncthreads();
+    for (int k = ly; k < 32; k += 8) {
+        const int64_t c = bx * 32 + k, r = by * 32 + lx;
+        if (r < rows && c < cols) dst[c * ldd + r] = tile[lx][k];
+    }
+}
+
+__global__ __launch_bounds__(kStepBlock) void k_ps_setup(PsDev D) {
+    const int64_t q = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    if (q >= D.n * D.ps) return;
+    const int64_t i = q / D.ps;
+    const int p = (int)(q - i * D.ps);
+    if (p >= D.pb) return;
+    const double* __restrict__ c = D.consts + (int64_t)p * mcf::PS_COUNT;
+    const double* __restrict__ t = D.tconst + i * mcf::TC_COUNT;
+    const double tc = D.tc[q], pk = D.pk[q], Rsw = D.Rsw[q], Rdif = D.Rdif[q], alb = D.alb[q], prec = D.prec[q];
+    const double ea = satvap(tc) * D.ea[q] / 100.0;
+    D.ea[q] = ea;
+    D.tdew[q] = dewpoint(ea);
+    D.cp[q] = cpair(tc);
+    D.ph[q] = phair(tc, pk);
+    // snow_radiation without the pack: the canopy's own absorption, the beam, the extinction of a spherical canopy
+    const double RlwabsC = 0.97 * D.Rlw[q];
+    double RabsC = RlwabsC, RswabsC = 0.0, cosz = 0.0, Rbeam = 0.0, kd = 0.0, Kc = 0.0;
+    if (Rsw > 0.0) {
+        const Sun sp = sun_position(c[mcf::PS_SINLAT], c[mcf::PS_COSLAT], c[mcf::PS_LON], t);
+        double si = solar_index(c + mcf::PS_SLOPE, sp.zend, sp.azid);
+        if (si < 0.0) si = 0.0;
+        cosz = cos(sp.zenr);
+        Rbeam = (Rsw - Rdif) / cosz;
+        if (Rbeam > 1352.2) Rbeam = 1352.2;
+        RswabsC = (1.0 - alb) * (Rdif + Rbeam * cosz);
+        RabsC = RswabsC + RlwabsC;
+        const Ext kp = canopy_k(sp.zenr, 1.0, si);
+        kd = kp.kd; Kc = kp.Kc;
+    }
+    D.RabsC[q] = RabsC; D.RswabsC[q] = RswabsC; D.cosz[q] = cosz; D.Rbeam[q] = Rbeam; D.kd[q] = kd; D.Kc[q] = Kc;
+    D.erhos[q] = exp(tc / 2.59);
+    D.mRc[q] = tc > 0.0 ? 0.0125 * tc * prec / 1000 : 0.0;
+    // mcf_pointmodelsnow before its loop
+    D.Tc[q] = tc; D.Tg[q] = tc; D.te[q] = tc; D.psim[q] = 0.0; D.psih[q] = 0.0;
+}
+
+__device__ __forceinline__ double zeroplane(double h, double pai) {
+    if (pai < 0.001) pai = 0.001;
+    return (1.0 - (1.0 - exp(-sqrt(7.5 * pai))) / sqrt(7.5 * pai)) * h;
+}
+// roughlength(h, pai, d, psi_h) of the host: roughlength() above with its two factors formed here
+__device__ __forceinline__ double roughlength_canopy(double h, double pai, double d, double psi_h) {
+    const double Be = sqrt(0.003 + (0.2 * pai) / 2);
+    return roughlength(h - d, (h - d) * exp(-kKa / Be), psi_h);
+}
+__device__ __forceinline__ double latent_molar(double t) {
+    return t < 0.0 ? 51078.69 - 4.338 * t - 0.06367 * t * t : 45068.7 - 42.8428 * t;
+}
+__device__ __forceinline__ double clamp01(double v) { return v > 1.0 ? 1.0 : v < 0.0 ? 0.0 : v; }
+// canopysnowintCpp with exp(tc / 2.59) from the set-up
+__device__ double canopy_snow_interception(double hgt, double pai, double uf, double prec, double erhos, double Li) {
+    if (hgt < 0.001) hgt = 0.001;
+    if (pai < 0.001) pai = 0.001;
+    const double Be = sqrt(0.003 + (0.2 * pai) / 2.0), uh = uf / Be;
+    const double Lc = 1.0 / (0.25 * (pai / hgt)), Lm = 2.0 * p3(Be) * Lc, k1 = Be / Lm;
+    double uzm = (uh / (hgt * k1)) * (1 - exp(-k1 * hgt));
+    if (uzm < uf) uzm = uf;
+    const double rhos = 67.92 + 51.25 * erhos;
+    const double Lstr = 6.2 * (0.26 + 46 / rhos) * pai;
+    const double kc = 1.0 / (2.0 * cos(atan(uzm / 0.8)));
+    const double Cp = 1.0 - exp(-kc * pai);
+    const double cis = (Lstr - Li) * (1.0 - exp(-(Cp / Lstr) * prec)) * 0.678;
+    return cis > prec ? prec : cis;
+}
+__device__ __forceinline__ double snow_density(double a, double b, double c, double d, double depth, double age_hours) {
+    return ((a - b) * (1.0 - exp(-c * depth / 100.0 - d * age_hours / 24.0)) + b) * 1000.0;
+}
+
+// a pass of mcf_pointmodelsnow's loop for one point per lane: snow_step (with snow_radiation) and the stability update
+__global__ __launch_bounds__(64) void k_ps_sweep(PsDev D) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= D.pb || !D.active[p]) return;                     // a frozen point does no work
+    const double* __restrict__ c = D.consts + (int64_t)p * mcf::PS_COUNT;
+    const double pai0 = c[mcf::PS_PAI], hgt0 = c[mcf::PS_HGT], ltra0 = c[mcf::PS_LTRA], clump = c[mcf::PS_CLUMP],
+                 zref = c[mcf::PS_ZREF], da = c[mcf::PS_DENA], db = c[mcf::PS_DENB], dc = c[mcf::PS_DENC], dd = c[mcf::PS_DEND],
+                 sden = c[mcf::PS_SDEN0];
+    const double cld = clump * clump;
+    double sdepc = c[mcf::PS_ISNOWD], sdepg = c[mcf::PS_ISNOWD] * 0.5, agec = c[mcf::PS_ISNOWA], ageg = c[mcf::PS_ISNOWA];
+    D.sdepc[p] = sdepc;
+    D.sdepg[p] = sdepg;
+    double mxdif = 0.0;
+    int64_t q = p;
+    for (int64_t i = 0; i < D.n; ++i, q += D.ps) {
+        const double tc = D.tc[q], ea = D.ea[q], pk = D.pk[q], u2 = D.u2[q], prec = D.prec[q], Rsw = D.Rsw[q], Rdif = D.Rdif[q],
+                     Rlw = D.Rlw[q], alb = D.alb[q], te = D.te[q], G = D.G[q], Tco = D.Tc[q], Tgo = D.Tg[q], psim0 = D.psim[q],
+                     psih0 = D.psih[q];
+        // ---- snow_step: the canopy above the pack
+        const double pai = hgt0 > sdepg ? pai0 * (hgt0 - sdepg) / hgt0 : 0.0;
+        double hgt = hgt0 - sdepg;
+        if (hgt < 0.0) hgt = 0.0;
+        const double zi = (sdepg > 0.0 && hgt > 0.0) ? ((sdepc - sdepg) * sden) / (hgt * 1000.0) : 0.0;
+        double ltra = ltra0 * exp(-10.1 * zi);
+        // ---- snow_radiation: what depends on the pack
+        const double RlwabsC = 0.97 * Rlw, pait = pai / (1.0 - clump);
+        double RlwabsG = RlwabsC;
+        const double tr = (1.0 - cld) * exp(-pait) + cld;
+        if (hgt > 0.0) RlwabsG = 0.97 * (tr * Rlw + (1.0 - tr) * 0.97 * kSb * radem(Tco));
+        const double RabsC = D.RabsC[q];
+        double RswabsG = 0.0;
+        if (Rsw > 0.0) {
+            RswabsG = D.RswabsC[q];
+            if (hgt > 0.0) {
+                const double cosz = D.cosz[q], Rbeam = D.Rbeam[q], kd = D.kd[q];
+                if (alb + ltra > 0.999) ltra = 0.999 - alb;
+                const Dif f = two_stream_dif(pait, 1.0, alb, ltra, alb);
+                const Dir r = two_stream_dir(pait, f, alb, kd);
+                const double clb = pow(clump, D.Kc[q]);
+                const double emh = f.S1, eph = exp(f.h * pait), ekd = exp(-kd * pait);
+                const double Rddm = clamp01((1.0 - cld) * (f.p3 * emh + f.p4 * eph) + cld);
+                const double Rdbm = clamp01((1.0 - clb) * ((r.p8 / r.sig) * ekd + r.p9 * emh + r.p10 * eph));
+                const double Rbgm = clamp01((1.0 - clb) * ekd + clb);
+                RswabsG = (1.0 - alb) * (Rdbm * Rbeam * cosz) + Rddm * Rdif + (1.0 - alb) * (Rbgm * Rbeam * 0.5);
+            }
+        }
+        // ---- roughness, friction velocity, conductance, the two temperatures
+        double d = 0.0, zmr = 0.005;
+        if (hgt > 0.0) { d = zeroplane(hgt, pai); zmr = roughlength_canopy(hgt, pai, d, psih0); }
+        const double zm = zmr < 0.0009 ? 0.0009 : zmr;
+        const double uf = (kKa * u2) / (log((zref - d) / zm) + psim0);
+        const double ph = D.ph[q];
+        double gHa = (kKa * ph * uf) / (log((zref - d) / ((0.2 * zm + d) - d)) + psih0);     // g_turb, gmin = 0.03
+        if (gHa < 0.03) gHa = 0.03;
+        double Tc = penman(RabsC, gHa, gHa, tc, te, pk, ea, 0.97, G, 1.0);
+        double Tg = penman(RswabsG + RlwabsG, gHa, gHa, tc, te, pk, ea, 0.97, G, 1.0);
+        const double tdew = D.tdew[q];
+        if (Tc < tdew) Tc = tdew;
+        if (Tg < tdew) Tg = tdew;
+        // ---- the whole pack: sublimation, temperature melt, rain melt; then the ground pack
+        double la = latent_molar(Tc);
+        const double mSc = ((la * (gHa / pk) * (satvap(Tc) - ea)) / (la / 0.018015)) * 3.6;
+        const double Tcp = Tc;
+        double mMc = 0.0;
+        if (Tc > 0.0) {
+            mMc = ((583.3 * Tc * (sdepc * (sden / 1000))) / 334000.0) * 3.6;
+            if (sdepc > 0.0) Tc = 0.0;
+        }
+        const double mRc = D.mRc[q];
+        la = latent_molar(Tg);
+        double mu = exp(-pai);
+        if (mu > 1.0) mu = 1.0;
+        const double mSg = ((la * (gHa / pk) * (satvap(Tg) - ea) * mu) / (la / 0.018015)) * 3.6;
+        double mMg = 0.0;
+        if (Tg > 0.0) {
+            mMg = ((583.3 * Tg * (sdepg * (sden / 1000.0))) / 334000.0) * 3.6;
+            if (sdepg > 0.0) Tg = 0.0;
+        }
+        double Li = 0.0;
+        if (sdepc > 0.0) {
+            double wg = sdepg / sdepc;
+            wg = wg < 0.0 ? 0.0 : wg > 1.0 ? 1.0 : wg;
+            Li = (sdepc - sdepg) * (wg * sden + (1.0 - wg) * sden);
+        }
+        if (Li < 0.0) Li = 0.0;
+        double cis = canopy_snow_interception(hgt, pai, uf, prec, D.erhos[q], Li);
+        if (cis > prec) cis = prec;
+        const double mRg = tc > 0.0 ? 0.0125 * tc * (prec - cis) / 1000.0 : 0.0;
+        const double snowc = tc > 2.0 ? 0.0 : prec, snowg = tc > 2.0 ? 0.0 : prec - cis;
+        const double swec = snowc / 1000.0 - mSc - mMc - mRc, sweg = snowg / 1000.0 - mSg - mMg - mRg;
+        agec = agec + 1.0;
+        ageg = ageg + 1.0;
+        const double denc = snow_density(da, db, dc, dd, sdepc, agec), deng = snow_density(da, db, dc, dd, sdepg, ageg);
+        sdepc = sdepc + (swec * 1000.0) / denc;
+        sdepg = sdepg + (sweg * 1000.0) / deng;
+        if (sdepc < 0.0) { sdepc = 0.0; agec = 0.0; }
+        if (sdepg < 0.0) { sdepg = 0.0; ageg = 0.0; }
+        D.sdepc[q + D.ps] = sdepc;
+        D.sdepg[q + D.ps] = sdepg;
+        // ---- mcf_pointmodelsnow's loop body after snow_step: relaxation, then the stability of the surface layer
+        const double Tcn = 0.5 * Tco + 0.5 * Tc, Tgn = 0.5 * Tgo + 0.5 * Tg;
+        mxdif = fmax(mxdif, fmax(fabs(Tcn - Tco), fabs(Tgn - Tgo)));          // fmax: a NaN never becomes the maximum
+        const double cp = D.cp[q];
+        double H = cp * gHa * (Tcn - tc);
+        double zm2 = hgt > 0.0 ? zmr : roughlength_canopy(hgt, pai, zeroplane(hgt, pai), psih0);
+        if (zm2 < 0.001) zm2 = 0.001;
+        if (fabs(H) < 0.1) H = 0.1;
+        const double LL = (ph * cp * p3(uf) * (tc + 273.15)) / (-kKa * 9.81 * H);
+        double psim = psi_m(zm2 / LL) - psi_m((zref - d) / LL);
+        double psih = psi_h((0.2 * zm2) / LL) - psi_h((zref - d) / LL);
+        const double Belim = 0.4 / sqrt(0.003 + (0.2 * pai) / 2.0);
+        const double ln1 = log((zref - d) / zm2), ln2 = log((zref - d) / (0.2 * zm2));
+        if (psim < -0.9 * ln1) psim = -0.9 * ln1;
+        if (psih < -0.9 * ln2) psih = -0.9 * ln2;
+        if (psim > 0.9 * ln1) psim = 0.9 * ln1;
+        if (psih > 0.9 * ln2) psih = 0.9 * ln2;
+        if (psih > 0.9 * Belim) psih = 0.9 * Belim;
+        D.Tc[q] = Tcn; D.Tg[q] = Tgn; D.psim[q] = psim; D.psih[q] = psih; D.te[q] = (Tcn + tc) / 2.0;
+        D.RswabsG[q] = RswabsG; D.RlwabsG[q] = RlwabsG; D.tr[q] = tr;
+        D.umu[q] = uf / ((0.4 * u2) / ln1);
+        D.mSc[q] = mSc; D.mMc[q] = mMc; D.Tcp[q] = Tcp;
+    }
+    D.mxd[p] = mxdif;
+}
+
+// GFluxCppsnow on series `Ts` (the air temperature before the first pass, Tg after each): a lane = one day of one point; the
+// last five hours of the day before (circular) come with their own daily mean
+__global__ __launch_bounds__(kStepBlock) void k_ps_gflux(PsDev D, const double* __restrict__ Ts, int all) {
+    const int64_t q = (int64_t)blockIdx.x * kStepBlock + threadIdx.x;
+    if (q >= D.nd * D.ps) return;
+    const int64_t day = q / D.ps;
+    const int p = (int)(q - day * D.ps);
+    if (p >= D.pb || !(all || D.active[p])) return;
+    const int64_t before = day == 0 ? D.nd - 1 : day - 1;
+    const double* __restrict__ a = Ts + before * 24 * D.ps + p;
+    const double* __restrict__ b = Ts + day * 24 * D.ps + p;
+    double v[29], sa = 0.0, sb = 0.0;
+#pragma unroll
+    for (int j = 0; j < 24; ++j) {
+        const double x = a[j * D.ps];
+        sa += x;
+        if (j >= 19) v[j - 19] = x;
+    }
+#pragma unroll
+    for (int j = 0; j < 24; ++j) {
+        v[5 + j] = b[j * D.ps];
+        sb += v[5 + j];
+    }
+    sa /= 24;
+    sb /= 24;
+#pragma unroll
+    for (int j = 0; j < 29; ++j) v[j] = v[j] - (j < 5 ? sa : sb);
+    const double gmud = D.consts[(int64_t)p * mcf::PS_COUNT + mcf::PS_GMUD];
+    double* __restrict__ G = D.G + day * 24 * D.ps + p;
+#pragma unroll
+    for (int h = 0; h < 24; ++h) {
+        double sum = 0.0;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) sum += v[5 + h - j];
+        G[h * D.ps] = (sum / 6) * gmud * 1.1171;
+    }
+}
+
+// the end of a pass, per point: `tst = mxdif; if (++iter > maxiter) tst = 0; while (tst > tol)`
+__global__ __launch_bounds__(256) void k_ps_finish(PsDev D) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= D.pb || !D.active[p]) return;
+    const double mx = D.mxd[p];
+    const int it = D.iters[p] + 1;
+    D.iters[p] = it;
+    D.mxdif[p] = mx;
+    double tst = mx;
+    if ((double)it > D.maxiter) tst = 0;
+    if (tst > D.tol) atomicAdd(D.going, 1);
+    else D.active[p] = 0;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------
 bool weather_ok(const mcf_point_weather* w) {
     return w && w->temp && w->relhum && w->pres && w->swdown && w->difrad && w->lwdown && w->windspeed;
@@ -772,6 +1101,138 @@ int run_bigleaf(const BlJob& J) {
     return MCF_OK;
 }
 
+// ---- mcf_pointmodelsnow_batch: the host side ---------------------------------------------------------------------------
+constexpr int kPsTables = 35;      // tables of a block, the two [n + 1] depths last; with the staging buffer 36 series
+
+struct PsJob {
+    int64_t P, n;
+    const mcf_obstime* t;
+    const mcf_point_weather* w;
+    const double *vegp, *other;        // [P][4] / [P][7]
+    const int32_t* snowenv;            // [P]
+    double tol, maxiter;
+    int64_t ppb;
+    int device;
+    mcf_pointsnow_batch_out* out;
+};
+
+int ps_transpose(const double* src, int64_t rows, int64_t cols, int64_t lds, double* dst, int64_t ldd) {
+    const int64_t tiles = ((rows + 31) / 32) * ((cols + 31) / 32);
+    hipLaunchKernelGGL(k_ps_transpose, dim3((unsigned)tiles), dim3(256), 0, 0, src, rows, cols, lds, dst, ldd);
+    HIP_TRY(hipGetLastError());
+    return MCF_OK;
+}
+
+int run_pointsnow(const PsJob& J) {
+    if (const int rc = mcf::check_device(J.device)) return rc;
+    mcf::RestoreDevice restore;
+    HIP_TRY(hipSetDevice(J.device));
+    const int64_t n = J.n, nd = n / 24;
+    int64_t PB;
+    if (const int rc = block_points(J.P, n, 45, J.ppb, &PB)) return rc;
+    const int64_t PS = (PB + 63) / 64 * 64;                  // whole waves: the sweep's lanes read whole lines
+    if ((n + 1) * PS >= ((int64_t)1 << 32))                  // one lane per table element must fit a launch
+        return mcf::api_fail(MCF_ERR_NOMEM, "mcf_pointmodelsnow_batch: points_per_block x n does not fit one launch");
+    mcf::DevOwner own;
+    int rc;
+    double* tab[kPsTables];
+    for (int k = 0; k < kPsTables; ++k)
+        if ((rc = own.make(&tab[k], (k >= kPsTables - 2 ? n + 1 : n) * PS))) return rc;
+    double *stage, *dconst, *dtconst, *dmxd, *dmxdif;
+    int *dactive, *diters, *dgoing;
+    if ((rc = own.make(&stage, PB * (n + 1))) || (rc = own.make(&dconst, PB * mcf::PS_COUNT)) ||
+        (rc = own.make(&dtconst, n * mcf::TC_COUNT)) || (rc = own.make(&dmxd, PS)) || (rc = own.make(&dmxdif, PS)) ||
+        (rc = own.make(&dactive, PS)) || (rc = own.make(&diters, PS)) || (rc = own.make(&dgoing, (int64_t)1)))
+        return rc;
+    {
+        std::vector<double> tcv((size_t)n * mcf::TC_COUNT);
+        mcf::bl_time_consts(n, J.t->year, J.t->month, J.t->day, J.t->hour, tcv.data());
+        HIP_TRY(hipMemcpy(dtconst, tcv.data(), tcv.size() * 8, hipMemcpyHostToDevice));
+    }
+    PsDev D;
+    D.n = n; D.nd = nd; D.ps = PS;
+    double** slot[kPsTables] = {&D.tc, &D.ea, &D.pk, &D.u2, &D.prec, &D.Rsw, &D.Rdif, &D.Rlw, &D.alb,
+                                &D.tdew, &D.cp, &D.ph, &D.RabsC, &D.RswabsC, &D.cosz, &D.Rbeam, &D.kd, &D.Kc, &D.erhos, &D.mRc,
+                                &D.Tc, &D.Tg, &D.te, &D.psim, &D.psih, &D.G,
+                                &D.RswabsG, &D.RlwabsG, &D.tr, &D.umu, &D.mSc, &D.mMc, &D.Tcp, &D.sdepc, &D.sdepg};
+    for (int k = 0; k < kPsTables; ++k) *slot[k] = tab[k];
+    D.consts = dconst; D.tconst = dtconst; D.mxd = dmxd; D.mxdif = dmxdif; D.active = dactive; D.iters = diters; D.going = dgoing;
+    D.tol = J.tol; D.maxiter = J.maxiter;
+
+    const double* cols[8] = {J.w->temp, J.w->relhum, J.w->pres, J.w->windspeed, J.w->precip, J.w->swdown, J.w->difrad, J.w->lwdown};
+    double* const ins[8] = {D.tc, D.ea, D.pk, D.u2, D.prec, D.Rsw, D.Rdif, D.Rlw};
+    std::vector<double> hconst((size_t)PB * mcf::PS_COUNT), halb((size_t)(PB * n)), hden;
+    std::vector<int> hactive((size_t)PS);
+    const bool enter = 100.0 > J.tol;                         // the host's `tst = 100.0; while (tst > tol)`
+    mcf_pointsnow_batch_out* o = J.out;
+
+    for (int64_t p0 = 0; p0 < J.P; p0 += PB) {
+        const int64_t pb = std::min(PB, J.P - p0);
+        const size_t bytes = (size_t)(pb * n) * 8;
+        D.pb = (int)pb;
+        for (int k = 0; k < 8; ++k) {
+            HIP_TRY(hipMemcpy(stage, cols[k] + p0 * n, bytes, hipMemcpyHostToDevice));
+            if ((rc = ps_transpose(stage, pb, n, n, ins[k], PS))) return rc;
+        }
+        for (int64_t p = 0; p < pb; ++p) {
+            const int64_t g = p0 + p;
+            mcf::ps_point_consts(J.vegp + g * 4, J.other + g * 7, J.snowenv[g], hconst.data() + p * mcf::PS_COUNT);
+            mcf::ps_albedo(J.w->precip + g * n, n, halb.data() + p * n);
+        }
+        HIP_TRY(hipMemcpy(stage, halb.data(), bytes, hipMemcpyHostToDevice));
+        if ((rc = ps_transpose(stage, pb, n, n, D.alb, PS))) return rc;
+        for (int64_t p = 0; p < PS; ++p) hactive[(size_t)p] = p < pb ? 1 : 0;
+        HIP_TRY(hipMemcpy(dconst, hconst.data(), (size_t)pb * mcf::PS_COUNT * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(dactive, hactive.data(), (size_t)PS * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(diters, 0, (size_t)PS * 4));
+        HIP_TRY(hipMemset(dmxdif, 0, (size_t)PS * 8));
+        HIP_TRY(hipMemset(dmxd, 0, (size_t)PS * 8));
+
+        const unsigned gstep = (unsigned)((n * PS + kStepBlock - 1) / kStepBlock);
+        const unsigned gday = (unsigned)((nd * PS + kStepBlock - 1) / kStepBlock);
+        const unsigned gwave = (unsigned)((pb + 63) / 64), gpoint = (unsigned)((pb + 255) / 256);
+        hipLaunchKernelGGL(k_ps_setup, dim3(gstep), dim3(kStepBlock), 0, 0, D);
+        hipLaunchKernelGGL(k_ps_gflux, dim3(gday), dim3(kStepBlock), 0, 0, D, (const double*)D.tc, 1);
+        HIP_TRY(hipGetLastError());
+        if (!enter) {                                          // no pass: the host leaves these vectors as the caller gave them
+            double* untouched[10] = {D.RswabsG, D.RlwabsG, D.tr, D.umu, D.mSc, D.mMc, D.Tcp, D.mRc, D.sdepc, D.sdepg};
+            for (int k = 0; k < 10; ++k) HIP_TRY(hipMemset(untouched[k], 0, (size_t)((k >= 8 ? n + 1 : n) * PS) * 8));
+        }
+        while (enter) {
+            HIP_TRY(hipMemsetAsync(dgoing, 0, 4, 0));
+            hipLaunchKernelGGL(k_ps_sweep, dim3(gwave), dim3(64), 0, 0, D);
+            hipLaunchKernelGGL(k_ps_gflux, dim3(gday), dim3(kStepBlock), 0, 0, D, (const double*)D.Tg, 0);
+            hipLaunchKernelGGL(k_ps_finish, dim3(gpoint), dim3(256), 0, 0, D);
+            HIP_TRY(hipGetLastError());
+            int going = 0;                                    // the one small copy of a pass; it also reports a fault
+            HIP_TRY(hipMemcpy(&going, dgoing, 4, hipMemcpyDeviceToHost));
+            if (going == 0) break;
+        }
+        double* host[11] = {o->Tc, o->Tg, o->G, o->RswabsG, o->RlwabsG, o->tr, o->umu, o->sublmelt, o->tempmelt, o->rainmelt,
+                            o->sstemp};
+        double* dev[11] = {D.Tc, D.Tg, D.G, D.RswabsG, D.RlwabsG, D.tr, D.umu, D.mSc, D.mMc, D.mRc, D.Tcp};
+        for (int k = 0; k < 11; ++k) {
+            if ((rc = ps_transpose(dev[k], n, pb, PS, stage, n))) return rc;
+            HIP_TRY(hipMemcpy(host[k] + p0 * n, stage, bytes, hipMemcpyDeviceToHost));
+        }
+        double* hostd[2] = {o->sdepc, o->sdepg};
+        double* devd[2] = {D.sdepc, D.sdepg};
+        for (int k = 0; k < 2; ++k) {
+            if ((rc = ps_transpose(devd[k], n + 1, pb, PS, stage, n + 1))) return rc;
+            HIP_TRY(hipMemcpy(hostd[k] + p0 * (n + 1), stage, (size_t)(pb * (n + 1)) * 8, hipMemcpyDeviceToHost));
+        }
+        for (int64_t p = 0; p < pb; ++p) {                     // the density of the whole run
+            const double den = hconst[(size_t)(p * mcf::PS_COUNT + mcf::PS_SDEN0)];
+            std::fill_n(o->sdenc + (p0 + p) * n, n, den);
+            std::fill_n(o->sdeng + (p0 + p) * n, n, den);
+        }
+        HIP_TRY(hipMemcpy(o->mxdif + p0, dmxdif, (size_t)pb * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(o->iters + p0, diters, (size_t)pb * 4, hipMemcpyDeviceToHost));
+    }
+    return MCF_OK;
+}
+
+
 }  // namespace
 
 extern "C" int mcf_bigleaf_batch(int64_t P, int64_t n, const mcf_obstime* obstime, const mcf_point_weather* weather,
@@ -854,4 +1315,26 @@ extern "C" int mcf_pointmprocess_batch(int64_t P, int64_t n, const double* winds
         for (int k = 0; k < 6; ++k) HIP_TRY(hipMemcpy(outs[k] + p0 * n, buf[7 + k], bytes, hipMemcpyDeviceToHost));
     }
     return MCF_OK;
+}
+
+extern "C" int mcf_pointmodelsnow_batch(int64_t P, int64_t n, const mcf_obstime* obstime, const mcf_point_weather* weather,
+                                        const double* vegp, const double* other, const int32_t* snowenv, double tol,
+                                        double maxiter, int64_t points_per_block, int32_t device, mcf_pointsnow_batch_out* o) {
+    const char* who = "mcf_pointmodelsnow_batch";
+    if (!obstime_ok(obstime)) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": null obstime");
+    if (!weather_ok(weather) || !weather->precip) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": null weather column");
+    if (!vegp || !other || !snowenv || !o) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": null argument");
+    const void* outs[] = {o->Tc, o->Tg, o->sdenc, o->sdeng, o->G, o->RswabsG, o->RlwabsG, o->tr, o->umu, o->sublmelt, o->tempmelt,
+                          o->rainmelt, o->sstemp, o->sdepc, o->sdepg, o->mxdif, o->iters};
+    for (const void* q : outs)
+        if (!q) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": null output vector");
+    if (P < 1) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": P < 1: the batch needs at least one point");
+    if (n % 24 != 0) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": n % 24 != 0: the batch entries take whole days only");
+    if (n < 24) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": n < 24: the daily mean of GFluxCppsnow needs one day");
+    if (n > (1 << 28) || P > ((int64_t)1 << 40) / n) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": series too long");
+    if (points_per_block < 0) return mcf::api_fail(MCF_ERR_ARG, std::string(who) + ": points_per_block < 0");
+    PsJob J{};
+    J.P = P; J.n = n; J.t = obstime; J.w = weather; J.vegp = vegp; J.other = other; J.snowenv = snowenv; J.tol = tol;
+    J.maxiter = maxiter; J.ppb = points_per_block; J.device = device; J.out = o;
+    return run_pointsnow(J);
 }

@@ -678,7 +678,7 @@ double snow_density(const SnowDen& p, double depth, double age_hours) {
     return ((p.a - p.b) * (1.0 - exp(-p.c * depth / 100.0 - p.d * age_hours / 24.0)) + p.b) * 1000.0;
 }
 // the age clock counts HOURS since snowfall; `hs / 24` is an integer division in the reference (whole days)
-void snow_albedo(const double* prec, size_t n, Vec& alb) {
+void snow_albedo(const double* prec, size_t n, double* alb) {
     int hs = 0;
     for (size_t i = 0; i < n; ++i) {
         if (i > 0) hs = prec[i] > 0 ? 0 : hs + 1;
@@ -839,7 +839,7 @@ extern "C" int mcf_pointmodelsnow(int64_t n64, const mcf_obstime* t, const mcf_p
     for (size_t i = 0; i < n; ++i) ea[i] = satvap(w->temp[i]) * w->relhum[i] / 100.0;
     const double slope = other[0], aspect = other[1], lat = other[2], lon = other[3], zref = other[4], isnowd = other[5],
                  isnowa = other[6];
-    snow_albedo(w->precip, n, salb);
+    snow_albedo(w->precip, n, salb.data());
     const SnowDen sd = snow_density_params(snowenv);
     for (size_t i = 0; i < n; ++i) {
         o->sdenc[i] = o->sdeng[i] = snow_density(sd, isnowd, 0.0);
@@ -1028,6 +1028,28 @@ void pmp_point_consts(double zref, double h, double pai, double rho, double Vm, 
     c[PC_C4] = 0.03 + 0.7 * frs * frs;
     c[PC_RHO] = rho;
 }
+
+// mcf_pointmodelsnow's per-point values, as it computes them before and inside its loops
+void ps_point_consts(const double* vegp, const double* other, int32_t snowenv, double* c) {
+    const double slope = other[0], aspect = other[1], lat = other[2], lon = other[3], zref = other[4], isnowd = other[5],
+                 isnowa = other[6];
+    const double latr = lat * kPi / 180.0;                                        // sun_position
+    c[PS_SINLAT] = sin(latr); c[PS_COSLAT] = cos(latr); c[PS_LON] = lon;
+    c[PS_SLOPE] = slope; c[PS_COSSL] = cos(slope * kToRad); c[PS_SINSL] = sin(slope * kToRad); c[PS_ASPECT] = aspect;
+    c[PS_PAI] = vegp[0]; c[PS_HGT] = vegp[1]; c[PS_LTRA] = vegp[2]; c[PS_CLUMP] = vegp[3];
+    c[PS_ZREF] = zref; c[PS_ISNOWD] = isnowd; c[PS_ISNOWA] = (double)(int)isnowa;
+    const SnowDen sd = snow_density_params(snowenv);
+    c[PS_DENA] = sd.a; c[PS_DENB] = sd.b; c[PS_DENC] = sd.c; c[PS_DEND] = sd.d;
+    const double den = snow_density(sd, isnowd, 0.0);
+    c[PS_SDEN0] = den;
+    // snow_ground_flux with one density for every hour: Gmu is one number and its 6-hour mean is summed as there
+    const double k = 0.0442 * exp(5.181 * den / 1000), kap = k / (den * 2090);
+    const double gmu = sqrt(2.0) * (k / sqrt(2.0 * kap / kOmdy)) * 0.5;
+    double sum = 0.0;
+    for (int j = 0; j < 6; ++j) sum += gmu;
+    c[PS_GMUD] = sum / 6;
+}
+void ps_albedo(const double* prec, int64_t n, double* alb) { snow_albedo(prec, (size_t)n, alb); }
 
 double wh_zeroplane() { return zeroplane(0.12, 1); }
 double wh_hde() {

@@ -664,10 +664,11 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
 def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, vegp: Mapping, soilc: Mapping, dtm: Mapping, *,
                   dtmc, lats_c, lons_c, lats, lons, altcorrect: int = 0, snowenv: str = "Taiga", method: str = "fast",
                   snowinitd: float = 0.0, snowinita: float = 0.0, zref: float = 2.0, windhgt: float | None = None,
-                  stfact: float = 0.01, device: int = 0) -> dict:
+                  stfact: float = 0.01, device: int = 0, point_device: int | None = None) -> dict:
     """`runsnowmodel(climarrayr, micropointa, vegp, soilc, dtm, dtmc, tme, altcorrect, ...)` for array weather
-    (R/Cppwrappers.R:735-757 -> `.snowmodel2`, R/internal.R:2777-3013): the snow point model (host C++) once per cell of
-    the climate grid, then `snow.snowmodel2_chunks`.  `climarray[k]`: [crows, ccols, T]; `dtmc`, `lats_c`, `lons_c`:
+    (R/Cppwrappers.R:735-757 -> `.snowmodel2`, R/internal.R:2777-3013): the snow point model once per cell of
+    the climate grid (`point_device=None`: host C++, a cell at a time; an int: every cell as one batch on that device,
+    whole days only), then `snow.snowmodel2_chunks`.  `climarray[k]`: [crows, ccols, T]; `dtmc`, `lats_c`, `lons_c`:
     [crows, ccols] of the climate grid; `lats`, `lons`: [rows, cols] of the fine raster.  A subset micropoint list with
     `method = "slow"` runs the whole series and subsets it (here `umu` too along time; the reference indexes the array as
     a vector there); `method = "fast"` runs `.snowmodelq2` (R/internal.R:3017-3283) = `snow.snowmodelq2_days`.  As in the reference every climate cell needs
@@ -700,19 +701,7 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     if zref != windhgt:
         clim_c["windspeed"] *= np.log(67.8 * zref - 5.42) / np.log(67.8 * windhgt - 5.42)
     clim_c["winddir"] = wdir
-    pn = {"Gp": "G", "Tc": "Tc", "RswabsG": "RswabsG", "RlwabsG": "RlwabsG", "umu": "umu", "tr": "tr", "sdepc": "sdepc"}
-    if fast:                                                          # `.snowmodelq2`: depth after the step, the melt terms
-        pn.update({k: k for k in ("sublmelt", "tempmelt", "rainmelt", "sstemp", "sdenc", "sdeng")})
-    pointm_c = {k: np.empty((cr, cc, T), order="F") for k in pn}
-    for i in range(cr):
-        for j in range(cc):
-            w = {k: clim_c[k][i, j, :] for k in clim_c if k != "winddir"}
-            w["winddir"] = wdir
-            vegpp = [float(np.mean(vc[k][i, j, :])) for k in ("pai", "hgt", "leaft", "clump")]          # `.tovp`
-            pmod = pointmodel.pointmodelsnow(ob, w, vegpp, [0.0, 0.0, float(lats_c[i, j]), float(lons_c[i, j]), zref, snowinitd,
-                                                            snowinita], snowenv, maxiter=10)
-            for k, v in pn.items():
-                pointm_c[k][i, j, :] = pmod[v][1:T + 1] if fast and k == "sdepc" else pmod[v][:T]
+    pointm_c = snow_pointm_cells(ob, clim_c, vc, lats_c, lons_c, zref, snowinitd, snowinita, snowenv, fast, point_device)
     res = dtm["res"]
     xres = res if np.isscalar(res) else res[0]
     rowpos, colpos = api.coarse_positions(R, cr), api.coarse_positions(Cc, cc)
@@ -742,6 +731,34 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
         i = np.asarray(last["subs"], dtype=np.int64) - 1
         out = {k: v[:, :, i] for k, v in out.items()}
     return out
+
+
+def snow_pointm_cells(ob: Mapping, clim_c: Mapping, vc: Mapping, lats_c, lons_c, zref: float, snowinitd: float,
+                      snowinita: float, snowenv: str, fast: bool, point_device: int | None = None) -> dict:
+    """The point stage of `.snowmodel2` / `.snowmodelq2`: pointmodelsnow (maxiter = 10) for every cell of the climate grid
+    -> `pointm_c`, [crows, ccols, T] each.  `point_device=None`: the host entry, one cell at a time; an int: all cells as one
+    batch on that device (pointmodel.pointmodelsnow_batch).  `fast` adds the melt terms and takes the depth AFTER the step."""
+    cr, cc, T = np.shape(clim_c["temp"])
+    pn = {"Gp": "G", "Tc": "Tc", "RswabsG": "RswabsG", "RlwabsG": "RlwabsG", "umu": "umu", "tr": "tr", "sdepc": "sdepc"}
+    if fast:                                                          # `.snowmodelq2`: depth after the step, the melt terms
+        pn.update({k: k for k in ("sublmelt", "tempmelt", "rainmelt", "sstemp", "sdenc", "sdeng")})
+    pointm_c = {k: np.empty((cr, cc, T), order="F") for k in pn}
+    cells = [(i, j) for i in range(cr) for j in range(cc)]
+    vegpp = [[float(np.mean(vc[k][i, j, :])) for k in ("pai", "hgt", "leaft", "clump")] for i, j in cells]           # `.tovp`
+    other = [[0.0, 0.0, float(lats_c[i, j]), float(lons_c[i, j]), zref, snowinitd, snowinita] for i, j in cells]
+    cols = [k for k in clim_c if k != "winddir"]
+    if point_device is None:
+        pmods = [pointmodel.pointmodelsnow(ob, {**{k: clim_c[k][i, j, :] for k in cols}, "winddir": clim_c["winddir"]}, vegpp[p],
+                                           other[p], snowenv, maxiter=10) for p, (i, j) in enumerate(cells)]
+        take = lambda v, p: pmods[p][v]                                                  # noqa: E731
+    else:
+        batch = pointmodel.pointmodelsnow_batch(ob, {k: np.reshape(clim_c[k], (cr * cc, T)) for k in cols}, vegpp, other,
+                                                snowenv, maxiter=10, device=int(point_device))
+        take = lambda v, p: batch[v][p]                                                  # noqa: E731
+    for p, (i, j) in enumerate(cells):
+        for k, v in pn.items():
+            pointm_c[k][i, j, :] = take(v, p)[1:T + 1] if fast and k == "sdepc" else take(v, p)[:T]
+    return pointm_c
 
 
 # ---- snow: runmicro(snow = TRUE) -> .runmicrosnow1 ----------------------------------------------------------------

@@ -3,8 +3,8 @@
 `runpointmodel` strings them together into the grid solver's `pointm` (R/Cppwrappers.R:119-138).
 
 They are O(tsteps) serial series for one point and run on the host inside libmcfhip (mcf_pointmodel.cpp), as
-they run on the host in the reference; the grid solver itself has no CPU path.  `BigLeafBatch`, `weatherhgt_batch` and
-`pointmprocess_batch` run the same operators for many points at once on the device (mcf_pointbatch.hip): arrays with a
+they run on the host in the reference; the grid solver itself has no CPU path.  `BigLeafBatch`, `weatherhgt_batch`,
+`pointmprocess_batch` and `pointmodelsnow_batch` run the same operators for many points at once on the device (mcf_pointbatch.hip): arrays with a
 leading point axis in, the single-point wrappers' keys with a leading point axis out.
 """
 from __future__ import annotations
@@ -124,11 +124,11 @@ def _mat(a, shape, name):
     return v
 
 
-def _weather_batch(climdata: Mapping, P: int, n: int):
+def _weather_batch(climdata: Mapping, P: int, n: int, need_precip: bool = False):
     w = _abi.PointWeather()
     keep = []
     for f in _abi.POINT_WEATHER_FIELDS:
-        if f == "precip":
+        if f == "precip" and not need_precip:
             setattr(w, f, None)
             continue
         v = _mat(climdata[f], (P, n), f"climdata${f}")
@@ -231,6 +231,42 @@ def pointmodelsnow(obstime, climdata, vegp, other, snowenv, tol: float = 0.5, ma
                                       ot.ctypes.data_as(_abi.c_double_p), env, float(tol), float(maxiter), C.byref(out)))
     res["mxdif"] = out.mxdif
     res["iters"] = out.iters
+    return res
+
+
+def pointmodelsnow_batch(obstime, climdata, vegp, other, snowenv, tol: float = 0.5, maxiter: float = 100, *, device: int = 0,
+                         points_per_block: int = 0) -> dict:
+    """pointmodelsnow for P points on device `device` (mcf_pointmodelsnow_batch).  `climdata[k]`: [P, n], precip too;
+    `obstime`: shared, [n]; `vegp`: [P, 4]; `other`: [P, 7]; `snowenv`: one name for every point or P names.  Whole days
+    only (n % 24 == 0).  Returns pointmodelsnow's keys: thirteen series [P, n], sdepc / sdepg [P, n + 1], `mxdif` [P] and
+    `iters` [P], each point's own."""
+    lib = _abi.load()
+    tc = np.asarray(climdata["temp"], dtype=np.float64)
+    if tc.ndim != 2:
+        raise ValueError("climdata$temp: expected [P, n]")
+    P, n = tc.shape
+    t, k1 = _obstime(obstime, n)
+    w, k2 = _weather_batch(climdata, P, n, need_precip=True)
+    vp = np.ascontiguousarray(np.asarray(vegp, dtype=np.float64))
+    ot = np.ascontiguousarray(np.asarray(other, dtype=np.float64))
+    if vp.shape != (P, 4) or ot.shape != (P, 7):
+        raise ValueError("vegp needs [P, 4] and other [P, 7] entries")
+    names = [snowenv] * P if isinstance(snowenv, str) else list(snowenv)
+    if len(names) != P:
+        raise ValueError("snowenv: one name or P names")
+    env = np.array([lib.mcf_snowenv_from_name(str(s).encode()) for s in names], dtype=np.int32)
+    out = _abi.PointSnowBatchOut()
+    res = {}
+    for f in _abi.POINTSNOW_FIELDS:
+        res[f] = np.zeros((P, n + 1 if f in ("sdepc", "sdepg") else n))
+        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
+    res["mxdif"] = np.zeros(P)
+    res["iters"] = np.zeros(P, dtype=np.int32)
+    out.mxdif = res["mxdif"].ctypes.data_as(_abi.c_double_p)
+    out.iters = res["iters"].ctypes.data_as(_abi.c_int32_p)
+    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    _abi.check(lib.mcf_pointmodelsnow_batch(P, n, C.byref(t), C.byref(w), d(vp), d(ot), env.ctypes.data_as(_abi.c_int32_p),
+                                            float(tol), float(maxiter), int(points_per_block), int(device), C.byref(out)))
     return res
 
 
