@@ -1019,6 +1019,52 @@ int mcf_topidx(int64_t rows, int64_t cols, const double *dtm, double xres, doubl
 int mcf_flowacc_device(int64_t rows, int64_t cols, const double *dtm, double *fa, int32_t device);
 int mcf_topidx_device(int64_t rows, int64_t cols, const double *dtm, double xres, double yres, double *twi, int32_t device);
 
+/* ---- leaf and ground reflectance from albedo (vegp$leafr, vegp$leaft, soilc$gref) -------------
+ * The reference's exported leafrfromalb() (R/dataprep.R:1000-1050) inverts the diffuse two-stream albedo per cell by
+ * bisection.  mcf_find_lref / mcf_find_gref replace _microclimf_find_lref / _microclimf_find_gref
+ * (src/microclimfCpp.cpp:5675-5724, with leafrcpp :5594-5626, solve_lref :5629-5648, solve_gref :5652-5672), mcf_fill_na
+ * replaces _microclimf_fill_naCpp (:5727-5777).  Rasters are [rows, cols] column-major, NaN = NA; a result cell is NA
+ * (R's NA_real_) where any of its four inputs is, and in find_gref where the 100 steps find no root.  Brackets 0.0001..0.6665
+ * (lref) and 0.0001..0.9999 (gref), tolerance 1e-6 on the albedo residual; a step whose f_lower * f_mid < 0 is false moves
+ * `lower`, a NaN product included.  mcf_fill_na: every NA cell inside the mask (mask not NA) takes the value of the source
+ * the reference's breadth-first search reaches it from first (4 neighbours, sources queued column-major, neighbours tried as
+ * row - 1, row + 1, col - 1, col + 1); cells where the mask is NA keep what `m` holds, unreachable cells stay NA.  `out` may
+ * be `m`.  Host code; `ltrr` must be finite. */
+int mcf_find_lref(int64_t rows, int64_t cols, const double *pai, const double *gref, const double *x, const double *albin,
+                  double ltrr, double *lref_out);
+int mcf_find_gref(int64_t rows, int64_t cols, const double *lref, const double *pai, const double *x, const double *albin,
+                  double ltrr, double *gref_out);
+int mcf_fill_na(int64_t rows, int64_t cols, const double *m, const double *mask, double *out);
+/* The same on the device (mcf_vegprep.hip; host pointers in and out), from the same arithmetic (mcf_vegprep.h): bit for bit
+ * the host entries' values unless exp / pow / cos of the two math libraries differ by enough to flip one root test; the fill
+ * is exact.  At most 2^31 - 1 cells. */
+int mcf_find_lref_device(int64_t rows, int64_t cols, const double *pai, const double *gref, const double *x,
+                         const double *albin, double ltrr, double *lref_out, int32_t device);
+int mcf_find_gref_device(int64_t rows, int64_t cols, const double *lref, const double *pai, const double *x,
+                         const double *albin, double ltrr, double *gref_out, int32_t device);
+int mcf_fill_na_device(int64_t rows, int64_t cols, const double *m, const double *mask, double *out, int32_t device);
+/* The whole loop of leafrfromalb() (R/dataprep.R:1007-1049): tst = exp(-mean(pai)) < 0.5 solves lref first, lref starts at
+ * 0.25 + 0.5 alb and gref at 0.15 (NA where x is), both solves are filled inside the mask x, the update is half old and half
+ * new, and the loop ends when max(mean|gref - gref2|, mean|lref - lref2|) <= 0.001 or after 50 passes.  leaft = ltrr * leafr.
+ * On the device the rasters go up once and the three results come down once.  A pai without a single value is refused
+ * (R stops there with a missing value). */
+typedef struct {
+    double *leafr, *leaft, *gref; /* [rows, cols] each, caller-owned */
+    int32_t iterations;           /* passes done */
+    int32_t lref_first;           /* 1: the tst < 0.5 branch was taken */
+    double mxdif_gref, mxdif_leaf;/* the two mean absolute differences of the last pass */
+} mcf_leafr_out;
+int mcf_leafrfromalb(int64_t rows, int64_t cols, const double *pai, const double *x, const double *alb, double ltrr,
+                     mcf_leafr_out *out);
+int mcf_leafrfromalb_device(int64_t rows, int64_t cols, const double *pai, const double *x, const double *alb, double ltrr,
+                            mcf_leafr_out *out, int32_t device);
+/* Diagnostics of the above, used by tests.  kind 0 / 1: leafrcpp(a = lref, b = pai, c = gref, d = x, e = albin, ltrr)
+ * elementwise as the host unit / the device unit evaluates it, out[rows * cols].  kind 2: mcf_leafrfromalb_device(a = pai,
+ * b = x, c = alb) with `block` (64, 128 or 256) threads per workgroup in the per-cell and fill kernels; out[3 rows cols + 4]:
+ * leafr, leaft, gref, then iterations, mxdif_gref, mxdif_leaf, lref_first. */
+int mcf_selftest_vegprep(int32_t kind, int64_t rows, int64_t cols, const double *a, const double *b, const double *c,
+                         const double *d, const double *e, double ltrr, double *out, int32_t block, int32_t device);
+
 /* Diagnostics: evaluate one of the solver's lean device elementary functions
  * elementwise on host arrays (kind 0 exp, 1 log, 2 x/y, 3 sqrt, 4 1/x, 5 satvap
  * (cpp:480-490), 6 x^y); used by tests to bound their error against libm. */

@@ -198,6 +198,13 @@ class MicrosnowIn(C.Structure):
     _fields_ = [("grid", C.POINTER(GridInputs)), ("snow", C.POINTER(SnowDriverIn)), ("micro", C.POINTER(SnowInputs)),
                 ("mat", C.c_double)]
 
+
+class LeafrOut(C.Structure):
+    """include/mcf.h mcf_leafr_out"""
+    _fields_ = [("leafr", c_double_p), ("leaft", c_double_p), ("gref", c_double_p), ("iterations", C.c_int32),
+                ("lref_first", C.c_int32), ("mxdif_gref", C.c_double), ("mxdif_leaf", C.c_double)]
+
+
 _PKG_DIR = Path(__file__).resolve().parent
 LIB_PATH = _PKG_DIR / "csrc" / "libmcfhip.so"
 
@@ -231,6 +238,8 @@ EXPORTS = (
     "mcf_plan_create_streamed", "mcf_plan_below_prepare", "mcf_plan_below_set_days", "mcf_below_days_range",
     "mcf_runmicrosnow1_below", "mcf_runmicrosnow1_below_multi", "mcf_snowrun_create_below",
     "mcf_flowacc_device", "mcf_topidx_device", "mcf_plan_create_dtm", "mcf_runmicro_dtm",
+    "mcf_find_lref", "mcf_find_gref", "mcf_fill_na", "mcf_find_lref_device", "mcf_find_gref_device", "mcf_fill_na_device",
+    "mcf_leafrfromalb", "mcf_leafrfromalb_device", "mcf_selftest_vegprep",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -469,6 +478,16 @@ def load() -> C.CDLL:
     lib.mcf_flowacc_device.argtypes = [C.c_int64, C.c_int64, c_double_p, c_double_p, C.c_int32]
     lib.mcf_topidx_device.restype = C.c_int
     lib.mcf_topidx_device.argtypes = [C.c_int64, C.c_int64, c_double_p, C.c_double, C.c_double, c_double_p, C.c_int32]
+    solve = [C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, c_double_p, C.c_double, c_double_p]
+    fill = [C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p]
+    loop = [C.c_int64, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_double, C.POINTER(LeafrOut)]
+    for name, args in (("mcf_find_lref", solve), ("mcf_find_gref", solve), ("mcf_fill_na", fill), ("mcf_leafrfromalb", loop)):
+        for fn, extra in ((getattr(lib, name), []), (getattr(lib, name + "_device"), [C.c_int32])):
+            fn.restype = C.c_int
+            fn.argtypes = args + extra
+    lib.mcf_selftest_vegprep.restype = C.c_int
+    lib.mcf_selftest_vegprep.argtypes = ([C.c_int32, C.c_int64, C.c_int64] + [c_double_p] * 5 + [C.c_double, c_double_p, C.c_int32,
+                                                                                                C.c_int32])
     lib.mcf_plan_create_dtm.restype = C.c_int
     lib.mcf_plan_create_dtm.argtypes = [GI, OP, C.POINTER(DtmSpec), C.c_int32, C.c_int32, C.POINTER(P)]
     lib.mcf_runmicro_dtm.restype = C.c_int

@@ -10,6 +10,7 @@ between the user's rasters and the solver call is restated with numpy on top of 
     soilmCpp, BigLeafCpp, pointmprocess, manCpp     libmcfhip, host C++ (pointmodel.py)
     terra::terrain, .horizon, .windsheltera         mcf_precompute_terrain (device kernels, terrain.py)
     .topidx / flowaccCpp                            mcf_topidx (host C++)
+    leafrfromalb, find_lref, find_gref, fill_naCpp  mcf_leafrfromalb_device (device kernels, vegprep.py)
     runmicro1Cpp / runmicro3Cpp                     mcf_runmicro1 / mcf_runmicro3 (the hot path)
     .sortvegp, .soilinit, .foliageden, .satvap ...  numpy, below, citing the R lines they follow
 
@@ -25,6 +26,7 @@ from typing import Mapping, Sequence
 import numpy as np
 
 from . import api, pointmodel, terrain
+from .vegprep import fill_na, find_gref, find_lref, leafrfromalb      # noqa: F401  (leafrfromalb(), R/dataprep.R:1000-1050)
 from .soil_tables import SOILPARAMETERS, SOILPARAMSP
 from .rformulas import dewpoint_R as _dewpoint, satvap_R as _satvap   # .satvap / .dewpoint, R/internal.R:501-521
 

@@ -813,6 +813,63 @@ SEXP mcfhip_terrain_twi(SEXP dtm, SEXP res, SEXP zref, SEXP s) {
     return ans;
 }
 
+/* find_lref / find_gref / fill_naCpp of leafrfromalb() (R/dataprep.R:1018-1027; reference src/microclimfCpp.cpp:5675-5777) on the
+ * device, with the reference's argument lists: matrices [rows, cols], NA = no data.  -> a matrix of the first argument's shape.
+ * NOT run in the build image (no R there): syntax- and type-checked only. */
+static void matrix_dims(SEXP m, int *rows, int *cols) {
+    SEXP dim = getAttrib(m, R_DimSymbol);
+    if (TYPEOF(dim) != INTSXP || LENGTH(dim) != 2) Rf_error("mcfhip: a matrix is expected");
+    *rows = INTEGER(dim)[0]; *cols = INTEGER(dim)[1];
+}
+static void same_dims(SEXP m, int rows, int cols) {
+    int r, c;
+    matrix_dims(m, &r, &c);
+    if (r != rows || c != cols) Rf_error("mcfhip: the matrices differ in shape");
+}
+static SEXP new_matrix(int rows, int cols, int *np) {
+    SEXP a = PROTECT(allocVector(REALSXP, (R_xlen_t)rows * cols)); ++*np;
+    SEXP d = PROTECT(allocVector(INTSXP, 2)); ++*np;
+    INTEGER(d)[0] = rows; INTEGER(d)[1] = cols;
+    setAttrib(a, R_DimSymbol, d);
+    return a;
+}
+SEXP mcfhip_find_lref(SEXP pai, SEXP gref, SEXP x, SEXP albin, SEXP ltrr) {
+    int np = 0, rows, cols;
+    g_keep = NULL; g_nkeep = 0;
+    matrix_dims(pai, &rows, &cols);
+    same_dims(gref, rows, cols); same_dims(x, rows, cols); same_dims(albin, rows, cols);
+    const double *p = dbl(pai, &np), *g = dbl(gref, &np), *xx = dbl(x, &np), *al = dbl(albin, &np);
+    SEXP ans = new_matrix(rows, cols, &np);
+    const int rc = mcf_find_lref_device(rows, cols, p, g, xx, al, asReal(ltrr), REAL(ans), 0);
+    if (rc != MCF_OK) raise_last(rc, np);
+    UNPROTECT(np);
+    return ans;
+}
+SEXP mcfhip_find_gref(SEXP lref, SEXP pai, SEXP x, SEXP albin, SEXP ltrr) {
+    int np = 0, rows, cols;
+    g_keep = NULL; g_nkeep = 0;
+    matrix_dims(pai, &rows, &cols);
+    same_dims(lref, rows, cols); same_dims(x, rows, cols); same_dims(albin, rows, cols);
+    const double *l = dbl(lref, &np), *p = dbl(pai, &np), *xx = dbl(x, &np), *al = dbl(albin, &np);
+    SEXP ans = new_matrix(rows, cols, &np);
+    const int rc = mcf_find_gref_device(rows, cols, l, p, xx, al, asReal(ltrr), REAL(ans), 0);
+    if (rc != MCF_OK) raise_last(rc, np);
+    UNPROTECT(np);
+    return ans;
+}
+SEXP mcfhip_fill_na(SEXP m, SEXP mask) {
+    int np = 0, rows, cols;
+    g_keep = NULL; g_nkeep = 0;
+    matrix_dims(m, &rows, &cols);
+    same_dims(mask, rows, cols);
+    const double *mm = dbl(m, &np), *mk = dbl(mask, &np);
+    SEXP ans = new_matrix(rows, cols, &np);
+    const int rc = mcf_fill_na_device(rows, cols, mm, mk, REAL(ans), 0);
+    if (rc != MCF_OK) raise_last(rc, np);
+    UNPROTECT(np);
+    return ans;
+}
+
 static const R_CallMethodDef CallEntries[] = {
     {"mcfhip_runmicro1", (DL_FUNC)&mcfhip_runmicro1, 15},
     {"mcfhip_runmicro2", (DL_FUNC)&mcfhip_runmicro2, 15},
@@ -833,6 +890,9 @@ static const R_CallMethodDef CallEntries[] = {
     {"mcfhip_snowrun_pass2", (DL_FUNC)&mcfhip_snowrun_pass2, 6},
     {"mcfhip_writetonc", (DL_FUNC)&mcfhip_writetonc, 9},
     {"mcfhip_terrain_twi", (DL_FUNC)&mcfhip_terrain_twi, 4},
+    {"mcfhip_find_lref", (DL_FUNC)&mcfhip_find_lref, 5},
+    {"mcfhip_find_gref", (DL_FUNC)&mcfhip_find_gref, 5},
+    {"mcfhip_fill_na", (DL_FUNC)&mcfhip_fill_na, 2},
     {NULL, NULL, 0}};
 
 void R_init_mcfhip_glue(DllInfo *dll) {

@@ -115,6 +115,13 @@ mcfhip_enable <- function(glue = "r/mcfhip_glue.so", devices = NULL, blocks = NU
     nm <- paste0(".runmodel", k, "Cpp")
     utils::assignInNamespace(nm, fill_from_dtm(get(nm, envir = ns), k %% 2 == 0), ns = "microclimf")
   })
+  # leaf and ground reflectance from albedo (R/RcppExports.R find_lref, find_gref, fill_naCpp; called at R/dataprep.R:1018-1027):
+  # leafrfromalb() itself stays as it is, its two per-cell solves and its nearest fill run on the device
+  for (nm in c("find_lref", "find_gref")) local({
+    sym <- paste0("mcfhip_", nm)
+    utils::assignInNamespace(nm, function(a, b, x, albin, ltrr) .Call(sym, a, b, x, albin, ltrr), ns = "microclimf")
+  })
+  utils::assignInNamespace("fill_naCpp", function(m, mask) .Call("mcfhip_fill_na", m, mask), ns = "microclimf")
   utils::assignInNamespace("runmicro1Cpp", rm1, ns = "microclimf")
   utils::assignInNamespace("runmicro2Cpp", rm2, ns = "microclimf")
   utils::assignInNamespace("runmicro3Cpp", rm3, ns = "microclimf")
