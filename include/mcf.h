@@ -407,6 +407,52 @@ int mcf_plan_ring_layout(mcf_plan *plan, mcf_ring_layout *layout);
 /* Host-side index helper (no device needed); -1 when (cell, step) is outside the slot. */
 int64_t mcf_ring_index(const mcf_ring_layout *layout, int64_t cell, int64_t step);
 
+/* ---- staged model outputs: the solver's own intermediates ----------------------------------------------------------------
+ * What the reference's staged workflow (twostream / wind / soiltemp, src/microclimfCpp.cpp:1545-2046, cited as cpp:LINE)
+ * shows of a run: thirteen fp64 diagnostics per cell-step.  They are the COMPILED path's values — the very ones that
+ * produce the ten outputs of the same run (one solar position per time step, runmicro1Cpp's soil moisture clamp) — not the
+ * R-mode re-derivation, which takes the solar position per cell and clamps soil moisture differently.  NA cells, steps
+ * outside every vegetation layer of a layered run and (one-shot entries) steps beyond the last whole day hold NA_real_,
+ * like the ten outputs. */
+enum mcf_diag {
+    MCF_DIAG_SI = 0,       /* "si"      solar index after the horizon test                      cpp:2218-2223            */
+    MCF_DIAG_RADGSW = 1,   /* "radGsw"  short wave absorbed by the ground                       cpp:1131 (bare: 1148)    */
+    MCF_DIAG_RADGLW = 2,   /* "radGlw"  long wave absorbed by the ground                        cpp:1165-1175            */
+    MCF_DIAG_RADCSW = 3,   /* "radCsw"  short wave absorbed by the canopy                       cpp:1136 (bare: 1149)    */
+    MCF_DIAG_RADCLW = 4,   /* "radClw"  long wave absorbed by the canopy (bare: radGlw)         cpp:1170 / 1174          */
+    MCF_DIAG_RADLSW = 5,   /* "radLsw"  short wave absorbed by a leaf at reqhgt                 cpp:1151-1162            */
+    MCF_DIAG_RADLPAR = 6,  /* "radLpar" PAR absorbed by a leaf at reqhgt; both exactly 0 at night and for pai == 0       */
+    MCF_DIAG_LWOUT = 7,    /* "lwout"   0.97 sb (tc + 273.15)^4                                 cpp:1166                 */
+    MCF_DIAG_UF = 8,       /* "uf"      friction velocity                                       cpp:1189-1196            */
+    MCF_DIAG_GHA = 9,      /* "gHa"     convective conductance                                  cpp:1217                 */
+    MCF_DIAG_T0 = 10,      /* "T0"      ground surface temperature (Tg of soiltemp_hrCpp)       cpp:1277-1296            */
+    MCF_DIAG_G = 11,       /* "G"       ground heat flux after its +-0.6 Rmx clamp              cpp:1290                 */
+    MCF_DIAG_KDDG = 12,    /* "kDDg"    damping depth                                           cpp:1249-1260            */
+    MCF_NDIAG = 13
+};
+/* Switches a plan's diagnostics on: sel[d] != 0 selects diagnostic d.  Call it after the create and before the first run
+ * (MCF_ERR_STATE afterwards, or when called twice); it allocates a second device ring beside the output ring (MCF_ERR_NOMEM
+ * like that one).  From then on mcf_plan_run_days / mcf_plan_run_days_at fill both rings; the ten outputs keep their bits.
+ * For plans with vector forcing (static or layered vegetation) and reqhgt >= 0.  MCF_ERR_ARG with a message for array and
+ * coarse forcing, reqhgt < 0, streamed plans and an empty selection; on a diagnostics plan mcf_plan_run_days_masked with a
+ * mask and mcf_plan_run_days_cells return MCF_ERR_ARG, and the snow run's and the `_multi` entries' plans never enable it. */
+int mcf_plan_diag_enable(mcf_plan *plan, const int32_t sel[MCF_NDIAG]);
+/* steps [step0, step0 + nsteps) of a selected diagnostic in ring slot `slot` as [rows, cols, nsteps], like mcf_plan_fetch */
+int mcf_plan_diag_fetch(mcf_plan *plan, int32_t slot, int32_t dvar, int64_t step0, int64_t nsteps, double *host_dst);
+/* Device address of a selected diagnostic of a ring slot and the diagnostics ring's layout: the output ring's geometry
+ * (always tiled; its own day stride — one block per SELECTED diagnostic), to be read with mcf_ring_index. */
+int mcf_plan_diag_slot_ptr(mcf_plan *plan, int32_t slot, int32_t dvar, void **dev_ptr);
+int mcf_plan_diag_ring_layout(mcf_plan *plan, mcf_ring_layout *layout);
+/* One-shot, host to host: mcf_runmicro1 / mcf_runmicro3 with the selected diagnostics beside the requested outputs, in day
+ * chunks through the device.  diag_out->var[d]: caller-allocated [rows, cols, tsteps] for every selected d.  reqhgt >= 0. */
+typedef struct mcf_diag_outputs {
+    double *var[MCF_NDIAG];
+} mcf_diag_outputs;
+int mcf_runmicro1_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
+                       mcf_diag_outputs *diag_out);
+int mcf_runmicro3_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
+                       mcf_diag_outputs *diag_out);
+
 /* HIP-event timing on the plan's stream: start records an event, stop records
  * another, synchronises and returns the elapsed milliseconds between them. */
 int mcf_plan_timer_start(mcf_plan *plan);

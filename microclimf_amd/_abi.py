@@ -12,6 +12,9 @@ import os
 from pathlib import Path
 
 NOUT = 10
+NDIAG = 13
+# include/mcf.h mcf_diag: the staged model's diagnostics, in the enum's order
+DIAG_NAMES = ("si", "radGsw", "radGlw", "radCsw", "radClw", "radLsw", "radLpar", "lwout", "uf", "gHa", "T0", "G", "kDDg")
 OUT_NAMES = ("Tz", "tleaf", "relhum", "soilm", "windspeed", "Rdirdown",
              "Rdifdown", "Rlwdown", "Rswup", "Rlwup")
 
@@ -115,6 +118,11 @@ class BioclimOut(C.Structure):
 
 class Outputs(C.Structure):
     _fields_ = [("var", c_double_p * NOUT)]
+
+
+class DiagOutputs(C.Structure):
+    """include/mcf.h mcf_diag_outputs"""
+    _fields_ = [("var", c_double_p * NDIAG)]
 
 
 # ---- snow branch (include/mcf.h "snow branch") ----
@@ -240,6 +248,8 @@ EXPORTS = (
     "mcf_flowacc_device", "mcf_topidx_device", "mcf_plan_create_dtm", "mcf_runmicro_dtm",
     "mcf_find_lref", "mcf_find_gref", "mcf_fill_na", "mcf_find_lref_device", "mcf_find_gref_device", "mcf_fill_na_device",
     "mcf_leafrfromalb", "mcf_leafrfromalb_device", "mcf_selftest_vegprep",
+    "mcf_plan_diag_enable", "mcf_plan_diag_fetch", "mcf_plan_diag_slot_ptr", "mcf_plan_diag_ring_layout",
+    "mcf_runmicro1_diag", "mcf_runmicro3_diag",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -394,6 +404,19 @@ def load() -> C.CDLL:
         lib.mcf_below_days_range.argtypes = [c_int32_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]
     lib.mcf_plan_sync.restype = C.c_int
     lib.mcf_plan_sync.argtypes = [P]
+    if hasattr(lib, "mcf_plan_diag_enable"):
+        DSEL = C.POINTER(C.c_int32 * NDIAG)
+        lib.mcf_plan_diag_enable.restype = C.c_int
+        lib.mcf_plan_diag_enable.argtypes = [P, DSEL]
+        lib.mcf_plan_diag_fetch.restype = C.c_int
+        lib.mcf_plan_diag_fetch.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p]
+        lib.mcf_plan_diag_slot_ptr.restype = C.c_int
+        lib.mcf_plan_diag_slot_ptr.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        lib.mcf_plan_diag_ring_layout.restype = C.c_int
+        lib.mcf_plan_diag_ring_layout.argtypes = [P, C.POINTER(RingLayout)]
+        for fn in (lib.mcf_runmicro1_diag, lib.mcf_runmicro3_diag):
+            fn.restype = C.c_int
+            fn.argtypes = [GI, OP, DSEL, OU, C.POINTER(DiagOutputs)]
     lib.mcf_plan_fetch.restype = C.c_int
     lib.mcf_plan_fetch.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p]
     lib.mcf_plan_fetch_cells.restype = C.c_int

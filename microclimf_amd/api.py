@@ -44,15 +44,41 @@ def dtm_spec(dtm: Mapping, rows: int, cols: int):
     return sp, z
 
 
+def diag_selection(names):
+    """(int32[13] selection, the selected names in include/mcf.h mcf_diag order) from diagnostic names or indices;
+    "all": every one"""
+    if isinstance(names, str):
+        names = _abi.DIAG_NAMES if names == "all" else (names,)
+    idx = sorted({_abi.DIAG_NAMES.index(n) if isinstance(n, str) else int(n) for n in names})
+    if not idx or idx[0] < 0 or idx[-1] >= _abi.NDIAG:
+        raise ValueError(f"diagnostics: a non-empty selection of {_abi.DIAG_NAMES}")
+    sel = (C.c_int32 * _abi.NDIAG)(*[1 if v in idx else 0 for v in range(_abi.NDIAG)])
+    return sel, [_abi.DIAG_NAMES[v] for v in idx]
+
+
 def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
          Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel=None, coarse=None,
-         devices=None, n_blocks=0, dtm=None):
+         devices=None, n_blocks=0, dtm=None, diag=None):
     lib = _abi.load()
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp,
                 tfact, complete, mat, out, array_forcing, device, days_per_chunk, cells_per_block, dfsel, coarse,
                 soilc_optional=DTM_DERIVED if dtm is not None else ())
     outs, arrays = alloc_outputs(m)
     mu = _abi.multi(devices, n_blocks)
+    if diag is not None:
+        # the staged model's diagnostics beside the outputs (include/mcf.h mcf_runmicro1_diag): one device, no dtm form
+        if mu or dtm is not None:
+            raise ValueError("diag= is not available with devices= / n_blocks= / dtm=")
+        sel, names = diag_selection(diag)
+        dout = _abi.DiagOutputs()
+        darr = {}
+        for n in names:
+            darr[n] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+            dout.var[_abi.DIAG_NAMES.index(n)] = darr[n].ctypes.data_as(_abi.c_double_p)
+        _abi.check(getattr(lib, fn_name + "_diag")(C.byref(m.inputs), C.byref(m.options), C.byref(sel), C.byref(outs),
+                                                   C.byref(dout)))
+        arrays["diag"] = darr
+        return arrays
     if dtm is not None:
         # missing terrain planes / wetness index derived on the device (include/mcf.h mcf_runmicro_dtm); the entry dispatches on
         # the inputs as mcf_runmicro1 .. 4 do
@@ -71,15 +97,19 @@ def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt,
 def runmicro1Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
                  reqhgt: float, zref: float, lat: float, lon: float, Sminp: float, Smaxp: float,
                  tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None,
+                 diag=None) -> dict:
     """Grid microclimate model, hourly, static vegetation, data.frame (vector) climate.
 
     Drop-in for the reference's runmicro1Cpp (src/microclimfCpp.cpp:2052-2337).  `devices` (a list of HIP ordinals, [] =
     all visible) / `n_blocks`: the raster in row blocks over several devices from this one process, same bits.
     `dtm` = {z, res[, halo_north, halo_south, row0, rows_total, agg]}: entries of `soilc` among slope, aspect, hor, svfa, wsa,
-    twi that are missing are derived from the elevations on the device, straight into the plan (include/mcf.h mcf_dtm_spec)."""
+    twi that are missing are derived from the elevations on the device, straight into the plan (include/mcf.h mcf_dtm_spec).
+    `diag` (names of include/mcf.h mcf_diag, or "all"; reqhgt >= 0): the staged model's diagnostics of the same run, returned
+    as a dict under the key "diag"; the default None returns exactly the ten-variable dict."""
     return _run("mcf_runmicro1", False, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
-                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm)
+                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm,
+                diag=diag)
 
 
 def runmicro2Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
@@ -122,13 +152,15 @@ def runmicro2Cpp_coarse(obstime: Mapping, climdata: Mapping, pointm: Mapping, ve
 def runmicro3Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
                  soilc: Mapping, reqhgt: float, zref: float, lat: float, lon: float, Sminp: float,
                  Smaxp: float, tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None,
+                 diag=None) -> dict:
     """Hourly, changing vegetation, data.frame climate: drop-in for the reference's runmicro3Cpp
     (src/microclimfCpp.cpp:2624-2924).  `dfsel` has columns lyr, st, ed (0-based step ranges of
-    each vegetation layer, R/internal.R:1391-1399); vegp entries are [rows, cols, layers].  `devices` / `n_blocks`: as runmicro1Cpp."""
+    each vegetation layer, R/internal.R:1391-1399); vegp entries are [rows, cols, layers].  `devices` / `n_blocks`: as runmicro1Cpp;
+    `diag`: as runmicro1Cpp."""
     return _run("mcf_runmicro3", False, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
                 Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel,
-                devices=devices, n_blocks=n_blocks, dtm=dtm)
+                devices=devices, n_blocks=n_blocks, dtm=dtm, diag=diag)
 
 
 def runmicro4Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
@@ -311,6 +343,33 @@ class Plan:
 
     def sync(self):
         _abi.check(self._lib.mcf_plan_sync(self._p))
+
+    def diag_enable(self, names="all"):
+        """Before the first run: the staged model's diagnostics (names of include/mcf.h mcf_diag, or "all") go to a second
+        device ring beside the outputs, filled by run_days / run_days_at; the ten outputs keep their bits.  Vector forcing and
+        reqhgt >= 0 (include/mcf.h mcf_plan_diag_enable).  -> the selected names"""
+        sel, picked = diag_selection(names)
+        _abi.check(self._lib.mcf_plan_diag_enable(self._p, C.byref(sel)))
+        return picked
+
+    def fetch_diag(self, slot: int, dvar, step0: int, nsteps: int) -> np.ndarray:
+        """fetch() for a selected diagnostic (a name or an index of include/mcf.h mcf_diag)"""
+        v = _abi.DIAG_NAMES.index(dvar) if isinstance(dvar, str) else int(dvar)
+        a = np.empty((self.rows, self.cols, nsteps), dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_diag_fetch(self._p, slot, v, step0, nsteps, a.ctypes.data_as(_abi.c_double_p)))
+        return a
+
+    def diag_ring_layout(self) -> dict:
+        """How a selected diagnostic of a ring slot is addressed on the device (include/mcf.h mcf_plan_diag_ring_layout)."""
+        lay = _abi.RingLayout()
+        _abi.check(self._lib.mcf_plan_diag_ring_layout(self._p, C.byref(lay)))
+        return {n: int(getattr(lay, n)) for n, _ in lay._fields_}
+
+    def diag_slot_ptr(self, slot: int, dvar) -> int:
+        v = _abi.DIAG_NAMES.index(dvar) if isinstance(dvar, str) else int(dvar)
+        q = C.c_void_p()
+        _abi.check(self._lib.mcf_plan_diag_slot_ptr(self._p, slot, v, C.byref(q)))
+        return int(q.value or 0)
 
     def fetch(self, slot: int, var, step0: int, nsteps: int) -> np.ndarray:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)

@@ -122,6 +122,12 @@ struct mcf_plan {
     int64_t stage_elems = 0;
     int var_slot[MCF_NOUT];     // index among enabled vars or -1
     int nvars = 0;
+    // diagnostics (mcf_plan_diag_enable; null: off): a second tiled ring, [slots][tile][day][selected diagnostic][block]
+    double* d_dring = nullptr;
+    int dg_slab1[MCF_NDIAG] = {};   // 1 + slab among the selected diagnostics, 0: not selected
+    int ndiag = 0;
+    int64_t dg_tile_stride = 0, dg_day_stride = 0, dg_slot_elems = 0;
+    bool has_run = false;           // a solver launch has been described (mcf_plan_diag_enable comes before)
     // reqhgt < 0
     double *d_tgser = nullptr, *d_ddsum = nullptr, *d_scratch = nullptr;
     const double *d_Tgp = nullptr, *d_Tbp = nullptr;
@@ -196,6 +202,22 @@ mcf::RingView ring_view(const mcf_plan* p, int slot, int var) {
         v.cpb = 0;
     }
     return v;
+}
+
+// selected diagnostic `dvar` of ring slot `slot` (the diagnostics ring is always tiled)
+mcf::RingView diag_view(const mcf_plan* p, int slot, int dvar) {
+    mcf::RingView v{};
+    v.N = p->N;
+    v.base = p->d_dring + (int64_t)slot * p->dg_slot_elems + (int64_t)(p->dg_slab1[dvar] - 1) * mcf::ring_block_doubles(p->cpb);
+    v.tile_stride = p->dg_tile_stride; v.day_stride = p->dg_day_stride; v.cpb = p->cpb;
+    return v;
+}
+int check_diag_range(const mcf_plan* p, int32_t slot, int32_t dvar, int64_t step0, int64_t nsteps) {
+    if (!p->d_dring) return fail(MCF_ERR_STATE, "the plan has no diagnostics ring: mcf_plan_diag_enable first");
+    if (slot < 0 || slot >= p->ring_slots || dvar < 0 || dvar >= MCF_NDIAG) return fail(MCF_ERR_ARG, "bad slot/diagnostic");
+    if (!p->dg_slab1[dvar]) return fail(MCF_ERR_ARG, "diagnostic was not selected in mcf_plan_diag_enable");
+    if (step0 < 0 || nsteps < 0 || step0 + nsteps > (int64_t)p->ring_days * 24) return fail(MCF_ERR_ARG, "step range out of slot");
+    return MCF_OK;
 }
 
 // steps [step0, step0 + nsteps) of variable `var` in ring slot `slot`: a slot of the plan, a requested variable (kAnyVar: the
@@ -1115,6 +1137,12 @@ int solve_args(mcf_plan* p, int32_t day0, int32_t ndays, int32_t slot, int32_t s
     }
     a.g = p->g;
     a.fix_count = p->d_fix_count; a.fix_list = p->d_fix_list; a.fix_cap = p->fix_cap;
+    if (p->d_dring) {
+        // (the diagnostics ring itself: dispatch_solve)  T0, G and kDDg are pass 2's first values (the requested outputs are written as without them: a variable that is not
+        // requested is not stored, and what pass 2 stores for a requested one is what the NA branch stores when it is all NA)
+        if (p->dg_slab1[MCF_DIAG_T0] || p->dg_slab1[MCF_DIAG_G] || p->dg_slab1[MCF_DIAG_KDDG]) a.need_pass2 = 1;
+    }
+    p->has_run = true;
     fast = p->fast_enabled && p->n_fast > 0;
     for (int d = day0; fast && !p->af && d < day0 + ndays; ++d)     // array forcing: every lane checks its own forcing values
         if (p->day_irregular[(size_t)d]) fast = false;
@@ -1138,23 +1166,34 @@ struct SolveTiles {
 // The k_solve launches of `t` on the plan's stream: with `fast`, the fix-up count cleared, then the fast part through the
 // min / max clamps and the slow part through the reference form; without it (an irregular day, or no fast class at all) one
 // reference-form launch of the first part, or of the whole raster.  An empty part launches nothing.
-void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, const SolveTiles& t) {
+// A diagnostics plan (mcf_plan_diag_enable) sends the same launches, with the same choices, through k_solve_diag: the slot's
+// place in the diagnostics ring rides along.
+void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, const SolveTiles& t, int slot) {
+    auto launch = [&](bool bg, bool f) {
+        if (!p->d_dring) { mcf::launch_solve(a, p->cpb, p->af, bg, f, soil_daily, p->stream); return; }
+        mcf::DiagSolveArgs d{};
+        static_cast<mcf::SolveArgs&>(d) = a;
+        d.dg_base = p->d_dring + (int64_t)slot * p->dg_slot_elems;
+        d.dg_tile_stride = p->dg_tile_stride; d.dg_day_stride = p->dg_day_stride;
+        for (int v = 0; v < MCF_NDIAG; ++v) d.dg_sel |= (uint64_t)(p->dg_slab1[v] ? p->dg_slab1[v] - 1 : 15) << (4 * v);
+        mcf::launch_solve_diag(d, p->cpb, f, soil_daily, p->stream);
+    };
     if (!fast) {
         if (!t.whole_raster() && t.n_fast == 0) return;
         a.tile_list = t.fast_list; a.ntiles_launch = t.n_fast;
-        mcf::launch_solve(a, p->cpb, p->af, p->bg, false, soil_daily, p->stream);
+        launch(p->bg, false);
         ++p->slow_launches;
         return;
     }
     (void)hipMemsetAsync(p->d_fix_count, 0, 4, p->stream);
     if (t.n_fast > 0) {
         a.tile_list = t.fast_list; a.ntiles_launch = t.n_fast;
-        mcf::launch_solve(a, p->cpb, p->af, false, true, soil_daily, p->stream);
+        launch(false, true);
         ++p->fast_launches;
     }
     if (t.n_slow > 0) {
         a.tile_list = t.slow_list; a.ntiles_launch = t.n_slow;
-        mcf::launch_solve(a, p->cpb, p->af, false, false, soil_daily, p->stream);
+        launch(false, false);
         ++p->slow_launches;
     }
 }
@@ -1383,6 +1422,7 @@ int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t s
                              int64_t n_skip_tile) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
     if (skip_tile && (p->bg || p->af)) return fail(MCF_ERR_ARG, "a tile mask needs vector forcing and reqhgt >= 0");
+    if (skip_tile && p->d_dring) return fail(MCF_ERR_ARG, "a tile mask on a diagnostics plan is not supported");
     if (skip_tile && n_skip_tile != (p->ntiles > 0 ? p->ntiles : (p->N + p->cpb - 1) / p->cpb))
         return fail(MCF_ERR_ARG, "the tile mask's length is not the plan's number of tiles");
     if (p->bg_stream) return run_below_chunk(p, day0, ndays, slot, slot_day0);
@@ -1425,7 +1465,7 @@ int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t s
     if (skip_tile) tiles = SolveTiles{sub_fast, n_sub_fast, sub_slow, n_sub_slow};
     // with no irregular tile the plan's fast launch needs no list (identity)
     else if (fast) tiles = SolveTiles{p->n_slow > 0 ? p->d_tiles_fast : nullptr, p->n_fast, p->d_tiles_slow, p->n_slow};
-    if ((rc = timed(p, [&] { dispatch_solve(p, a, fast, soil_daily, tiles); }))) return rc;
+    if ((rc = timed(p, [&] { dispatch_solve(p, a, fast, soil_daily, tiles, slot); }))) return rc;
     HIP_TRY(hipGetLastError());
     return MCF_OK;
 }
@@ -1434,6 +1474,7 @@ int mcf_plan_run_days_cells(mcf_plan* p, int32_t day0, int32_t ndays, int32_t sl
                             int64_t n_cells, int64_t* n_gathered) {
     if (!p || !need_cell) return fail(MCF_ERR_ARG, "null argument");
     if (p->bg || p->af || !p->tiled) return fail(MCF_ERR_ARG, "a cell subset needs vector forcing and reqhgt >= 0");
+    if (p->d_dring) return fail(MCF_ERR_ARG, "a cell subset on a diagnostics plan is not supported");
     if (n_cells != p->N) return fail(MCF_ERR_ARG, "the cell flags' length is not the plan's number of cells");
     mcf::SolveArgs a{};
     bool fast = false, soil_daily = false;
@@ -1521,7 +1562,7 @@ int mcf_plan_run_days_cells(mcf_plan* p, int32_t day0, int32_t ndays, int32_t sl
         a.day0 = day0 + d; a.ndays = nd;
         // (vector forcing above ground, as checked on entry: the plan's af and bg, which dispatch_solve passes on, are false;
         // these launches are not timed for mcf_plan_kernel_stats)
-        dispatch_solve(p, a, fast, soil_daily, fast ? SolveTiles{nullptr, nt_fast, p->d_cells_slow, nt_slow} : SolveTiles{nullptr, nt_sub, nullptr, 0});
+        dispatch_solve(p, a, fast, soil_daily, fast ? SolveTiles{nullptr, nt_fast, p->d_cells_slow, nt_slow} : SolveTiles{nullptr, nt_sub, nullptr, 0}, slot);
         HIP_TRY(hipGetLastError());
         mcf::launch_scatter_cells(p->d_celllist, nt_sub, p->d_subring, a.out_tile_stride, slot_base + (int64_t)d * p->ring_day_stride,
                                   p->ring_tile_stride, day_doubles, cpb, nd, p->stream);
@@ -1589,14 +1630,31 @@ int mcf_plan_fetch(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_
     return mcf_plan_fetch_pitched(p, slot, var, step0, nsteps, host_dst, 0);
 }
 
+// steps [step0, step0 + nsteps) of `view` (a variable of the output ring, a diagnostic of the diagnostics ring) to the host
+static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch);
+
 int mcf_plan_fetch_pitched(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
     if (row_pitch == 0) row_pitch = p->rows;
     if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
     if (const int rc = check_slot_range(p, slot, var, step0, nsteps)) return rc;
+    return fetch_view(p, ring_view(p, slot, var), p->tiled, step0, nsteps, host_dst, row_pitch);
+}
+
+static int diag_fetch_pitched(mcf_plan* p, int32_t slot, int32_t dvar, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
+    if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
+    if (row_pitch == 0) row_pitch = p->rows;
+    if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
+    if (const int rc = check_diag_range(p, slot, dvar, step0, nsteps)) return rc;
+    return fetch_view(p, diag_view(p, slot, dvar), true, step0, nsteps, host_dst, row_pitch);
+}
+int mcf_plan_diag_fetch(mcf_plan* p, int32_t slot, int32_t dvar, int64_t step0, int64_t nsteps, double* host_dst) {
+    return diag_fetch_pitched(p, slot, dvar, step0, nsteps, host_dst, 0);
+}
+
+static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
     HIP_TRY(hipSetDevice(p->device));
     if (nsteps == 0) return MCF_OK;
-    const mcf::RingView view = ring_view(p, slot, var);
     // (a block of a taller raster goes column by column into its place)
     auto to_host = [&](double* dst, const double* src, size_t bytes) -> int {
         const size_t width = (size_t)p->rows * 8;
@@ -1604,7 +1662,7 @@ int mcf_plan_fetch_pitched(mcf_plan* p, int32_t slot, int32_t var, int64_t step0
         else HIP_TRY(p->tohost.dense(dst, src, bytes, p->stream));
         return MCF_OK;
     };
-    if (!p->tiled) return to_host(host_dst, view.base + p->N * step0, (size_t)(p->N * nsteps) * 8);
+    if (!tiled) return to_host(host_dst, view.base + p->N * step0, (size_t)(p->N * nsteps) * 8);
     // tiled ring: the reference's [rows, cols, steps] layout is made on the device (k_untile), in pieces of <= 1 GB
     const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(nsteps, ((int64_t)1 << 27) / std::max<int64_t>(p->N, 1)));
     if (p->stage_elems < piece * p->N) {
@@ -1834,6 +1892,50 @@ int mcf_plan_ring_layout(mcf_plan* p, mcf_ring_layout* out) {
     return MCF_OK;
 }
 
+int mcf_plan_diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
+    if (!p || !sel) return fail(MCF_ERR_ARG, "null argument");
+    if (p->af) return fail(MCF_ERR_ARG, p->coarse ? "diagnostics are not available with coarse array forcing"
+                                                  : "diagnostics are not available with array forcing");
+    if (p->bg || p->opt.reqhgt < 0.0) return fail(MCF_ERR_ARG, "diagnostics need reqhgt >= 0");
+    if (p->bg_stream) return fail(MCF_ERR_ARG, "diagnostics are not available on a streamed plan");
+    if (p->d_dring) return fail(MCF_ERR_STATE, "diagnostics are already enabled on this plan");
+    if (p->has_run) return fail(MCF_ERR_STATE, "mcf_plan_diag_enable comes before the plan's first run");
+    int n = 0;
+    for (int v = 0; v < MCF_NDIAG; ++v) n += sel[v] ? 1 : 0;
+    if (n == 0) return fail(MCF_ERR_ARG, "no diagnostic selected");
+    HIP_TRY(hipSetDevice(p->device));
+    const int64_t blk = mcf::ring_block_doubles(p->cpb);
+    const int64_t day_stride = (int64_t)n * blk, tile_stride = (int64_t)p->ring_days * day_stride, slot_elems = p->ntiles * tile_stride;
+    void* q = nullptr;
+    if (const int rc = dalloc(p, &q, (int64_t)p->ring_slots * slot_elems * 8)) return rc;
+    p->d_dring = (double*)q;
+    p->dg_day_stride = day_stride; p->dg_tile_stride = tile_stride; p->dg_slot_elems = slot_elems;
+    p->ndiag = 0;
+    for (int v = 0; v < MCF_NDIAG; ++v) p->dg_slab1[v] = sel[v] ? ++p->ndiag : 0;
+    return MCF_OK;
+}
+
+int mcf_plan_diag_slot_ptr(mcf_plan* p, int32_t slot, int32_t dvar, void** dev_ptr) {
+    if (!p || !dev_ptr) return fail(MCF_ERR_ARG, "null argument");
+    if (const int rc = check_diag_range(p, slot, dvar, 0, 0)) return rc;
+    *dev_ptr = const_cast<double*>(diag_view(p, slot, dvar).base);
+    return MCF_OK;
+}
+
+int mcf_plan_diag_ring_layout(mcf_plan* p, mcf_ring_layout* out) {
+    if (!p || !out) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->d_dring) return fail(MCF_ERR_STATE, "the plan has no diagnostics ring: mcf_plan_diag_enable first");
+    memset(out, 0, sizeof *out);
+    out->tiled = 1;
+    out->cells = p->N;
+    out->slot_days = p->ring_days;
+    out->cells_per_tile = p->cpb;
+    out->block_doubles = mcf::ring_block_doubles(p->cpb);
+    out->tile_stride = p->dg_tile_stride;
+    out->day_stride = p->dg_day_stride;
+    return MCF_OK;
+}
+
 int64_t mcf_ring_index(const mcf_ring_layout* l, int64_t cell, int64_t step) {
     if (!l || cell < 0 || cell >= l->cells || step < 0 || step >= (int64_t)l->slot_days * 24) return -1;
     mcf::RingView v{nullptr, l->cells, l->tile_stride, l->day_stride, l->tiled ? l->cells_per_tile : 0};
@@ -2052,11 +2154,22 @@ int64_t mcf_plan_bytes(const mcf_plan* p) { return p ? p->dev.bytes : 0; }
 // twi_mean: null, or the raster-wide mean of log(twi)/tfact to install (a row block of a larger raster, run_multi)
 // sharers: host threads that solve their blocks on this device at the same time (one-process multi-device route with a device
 // listed more than once): each sizes its ring from its share of the free HBM
+// dsel / dout: the diagnostics to fetch beside the outputs (mcf_runmicro1_diag), or null
 static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out, int want_af,
-                       const double* twi_mean = nullptr, int sharers = 1, const mcf_dtm_spec* dtm = nullptr) {
+                       const double* twi_mean = nullptr, int sharers = 1, const mcf_dtm_spec* dtm = nullptr,
+                       const int32_t* dsel = nullptr, mcf_diag_outputs* dout = nullptr) {
     int rc = check_inputs(in, opt);
     if (rc) return rc;
     if (!out) return fail(MCF_ERR_ARG, "null outputs");
+    int ndiag = 0;
+    if (dsel) {
+        if (opt->reqhgt < 0.0) return fail(MCF_ERR_ARG, "diagnostics need reqhgt >= 0");
+        for (int v = 0; v < MCF_NDIAG; ++v) {
+            if (dsel[v] && !dout->var[v]) return fail(MCF_ERR_ARG, "selected diagnostic has a null buffer");
+            ndiag += dsel[v] ? 1 : 0;
+        }
+        if (ndiag == 0) return fail(MCF_ERR_ARG, "no diagnostic selected");
+    }
     if ((in->array_forcing != 0) != (want_af != 0))
         return fail(MCF_ERR_ARG, want_af ? "mcf_runmicro2 needs array_forcing = 1" : "mcf_runmicro1 needs array_forcing = 0");
     for (int v = 0; v < MCF_NOUT; ++v)
@@ -2093,7 +2206,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     } else if (chunk <= 0) {
         size_t fr = 0, tot = 0;
         HIP_TRY(hipMemGetInfo(&fr, &tot));
-        double per_day = (double)N * 24 * 8 * (nvars + (in->array_forcing ? 15 : 0));
+        double per_day = (double)N * 24 * 8 * (nvars + ndiag + (in->array_forcing ? 15 : 0));
         double budget = 0.6 * (double)fr / std::max(sharers, 1) - (double)N * 8 * 200;
         if (stream_bg) {      // the chunk's Tg ring (and, array forcing with complete = 0, the point model's Tg / Tbp), the per-cell state
             per_day += (double)N * 24 * 8 * (1 + (in->array_forcing == 1 && !opt->complete ? 2 : 0));
@@ -2112,6 +2225,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if (stream_bg && (rc = mcf_plan_below_prepare(p, in))) return rc;
+    if (dsel && (rc = mcf_plan_diag_enable(p, dsel))) return rc;
     double t_create = now() - t0;
     for (int d0 = 0; d0 < ndays; d0 += chunk) {
         int nd = std::min(chunk, ndays - d0);
@@ -2123,6 +2237,10 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
             for (int v = 0; v < MCF_NOUT; ++v)
                 if (opt->out[v])
                     if ((rc = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, out->var[v] + HS * (int64_t)d0 * 24, pitch)))
+                        return rc;
+            for (int v = 0; dsel && v < MCF_NDIAG; ++v)
+                if (dsel[v])
+                    if ((rc = diag_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, dout->var[v] + HS * (int64_t)d0 * 24, pitch)))
                         return rc;
         }
         if (timing) t_fetch += now() - ta;
@@ -2142,6 +2260,11 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
             for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
                 for (int64_t j = 0; j < in->cols; ++j)
                     for (int64_t i = 0; i < in->rows; ++i) out->var[v][i + pitch * j + HS * k] = na;
+    for (int v = 0; dsel && v < MCF_NDIAG; ++v)
+        if (dsel[v])
+            for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
+                for (int64_t j = 0; j < in->cols; ++j)
+                    for (int64_t i = 0; i < in->rows; ++i) dout->var[v][i + pitch * j + HS * k] = na;
     if (bg && opt->out[MCF_OUT_TZ] && T > 0) {
         // Tbelowgroundv runs over all tsteps (cpp:2314-2319)
         if ((rc = mcf_plan_belowground(p))) return rc;
@@ -2331,6 +2454,19 @@ int mcf_runmicro2_multi(const mcf_grid_inputs* in, const mcf_options* opt, const
 }
 int mcf_runmicro2(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {
     return run_oneshot(in, opt, out, 1);
+}
+int mcf_runmicro1_diag(const mcf_grid_inputs* in, const mcf_options* opt, const int32_t sel[MCF_NDIAG], mcf_outputs* out,
+                       mcf_diag_outputs* diag_out) {
+    if (!sel || !diag_out) return fail(MCF_ERR_ARG, "null argument");
+    if (in && in->array_forcing != 0) return fail(MCF_ERR_ARG, "diagnostics are not available with array forcing");
+    return run_oneshot(in, opt, out, 0, nullptr, 1, nullptr, sel, diag_out);
+}
+int mcf_runmicro3_diag(const mcf_grid_inputs* in, const mcf_options* opt, const int32_t sel[MCF_NDIAG], mcf_outputs* out,
+                       mcf_diag_outputs* diag_out) {
+    if (!sel || !diag_out) return fail(MCF_ERR_ARG, "null argument");
+    if (in && in->veg_layers < 1) return fail(MCF_ERR_ARG, "mcf_runmicro3_diag needs veg_layers >= 1 and dfsel");
+    if (in && in->array_forcing != 0) return fail(MCF_ERR_ARG, "diagnostics are not available with array forcing");
+    return run_oneshot(in, opt, out, 0, nullptr, 1, nullptr, sel, diag_out);
 }
 int mcf_runmicro3(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {
     if (in && in->veg_layers < 1) return fail(MCF_ERR_ARG, "mcf_runmicro3 needs veg_layers >= 1 and dfsel");

@@ -1161,13 +1161,44 @@ struct SoilLds {
     __device__ __forceinline__ double operator()(int f) const { return p[f * CPB]; }
 };
 
+// ---- diagnostics sink (include/mcf.h `mcf_diag`) ------------------------------------------------------------------------
+// The staged model's intermediates — absorbed radiation, wind, the ground's heat flux — are values pass 1 and pass 2 hold
+// anyway.  Both passes take a sink `dg(which, value)`; the shipped instantiations pass NoDiag, whose `on = false` removes
+// every statement that only serves the sink, and k_solve_diag passes DiagRing, which stores the selected values into the
+// diagnostics ring as soon as they exist (pass 1's before the day's barrier: nothing more is carried across it).
+// The numbering is mcf.h's.
+enum Diag : int {
+    DG_SI = 0, DG_RADGSW, DG_RADGLW, DG_RADCSW, DG_RADCLW, DG_RADLSW, DG_RADLPAR, DG_LWOUT, DG_UF, DG_GHA, DG_T0, DG_G, DG_KDDG,
+    DG_COUNT
+};
+struct NoDiag {
+    static constexpr bool on = false;
+    __device__ __forceinline__ void operator()(int, double) const {}
+};
+// one tile-day of the diagnostics ring, laid out like the output ring's: [selected diagnostic][block], the lane's value at its
+// constant position; `day` is wave-uniform
+template <int NT>
+struct DiagRing {
+    static constexpr bool on = true;
+    char* day;
+    uint64_t sel;        // 4 bits per diagnostic: its slab among the selected ones, 15 = not selected
+    uint32_t posb;
+    __device__ __forceinline__ void operator()(int v, double val) const {
+        const unsigned s = (unsigned)(sel >> (4 * v)) & 15u;
+        if (s == 15u) return;
+        uint32_t pb = posb;
+        asm("" : "+v"(pb));      // (see k_solve `put`)
+        *(double*)(day + ((size_t)s * (NT * 8)) + pb) = val;
+    }
+};
+
 // ---------------------------------------------------------------------------------
 // PASS 1 (cpp:2214-2262): terrain-adjusted solar index, soil moisture spread,
 // two-stream radiation, wind, G = 0 soil surface temperature.
 // ---------------------------------------------------------------------------------
-template <bool F, bool SS, class CL, class TM, class SL>
+template <bool F, bool SS, class CL, class TM, class SL, class DG = NoDiag>
 __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, const Globals& g, int flags, double dTmx,
-                                      Carry& cy, Pass1Out& o, const MathK& K, Canary& cn) {
+                                      Carry& cy, Pass1Out& o, const MathK& K, Canary& cn, const DG& dg = NoDiag()) {
     // ---- section A operands: soil moisture spread + branch selectors
     double t_idx = T(TF_IDX), rsw = T(TF_RSW), rdif = T(TF_RDIF);
     pin(t_idx, rsw, rdif);
@@ -1187,6 +1218,17 @@ __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, con
     cy.soilm = soilm;
     // --- short wave, cpp:1086-1163 --------------------------------------------------
     double radGsw = 0.0, radCsw = 0.0, Rbdown = 0.0, Rddown = 0.0, Rdup = 0.0, X = 0.0;
+    if constexpr (DG::on) {
+        // the solar index of a step WITHOUT sun (the reference's driver makes it for every step, cpp:2218-2223; the block below
+        // needs it by day only and hands its own value to the sink): the same expression on the same operands
+        if (!(rsw > 0.0)) {
+            double si = T(TF_CZ) * C(CF_CS) + T(TF_SZ) * (C(CF_SSCA) * T(TF_CAZ) + C(CF_SSSA) * T(TF_SAZ));
+            if (!g.shadowmask && T(TF_ZEND) > 90.0) si = 0.0;
+            flr<F>(si, 0.0, cn);
+            if (C.hor(idx & 31) > T(TF_TANSA)) si = 0.0;
+            dg(DG_SI, si);
+        }
+    }
     if (rsw > 0.0) {
         // ---- section B operands: solar index, horizon, canopy extinction
         double cz = T(TF_CZ), t_sz = T(TF_SZ), t_caz = T(TF_CAZ), t_saz = T(TF_SAZ), t_tansa = T(TF_TANSA),
@@ -1199,6 +1241,7 @@ __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, con
         if (!g.shadowmask && t_zend > 90.0) si = 0.0;
         flr<F>(si, 0.0, cn);
         if (c_hor > t_tansa) si = 0.0;
+        if constexpr (DG::on) dg(DG_SI, si);
         if (flags & FL_PAI) {
             // ---- section C operands: extinction + direct-beam two-stream coefficients
             double t_tan2c = T(TF_TAN2C), t_cosc = T(TF_COSC);
@@ -1303,6 +1346,15 @@ __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, con
     cy.Rbdown = Rbdown;
     cy.X = X;
     o.Rdup = Rdup;
+    if constexpr (DG::on) {
+        dg(DG_RADGSW, radGsw);
+        dg(DG_RADCSW, radCsw);
+        // absorbed by a leaf at reqhgt, cpp:1151-1162: exactly 0 at night and for pai == 0 (pass 2 fuses the same products
+        // into the leaf's energy balance)
+        const bool lit = rsw > 0.0 && (flags & FL_PAI);
+        dg(DG_RADLSW, lit ? C(CF_HOM) * X : 0.0);
+        dg(DG_RADLPAR, lit ? C(CF_HOMP) * X : 0.0);
+    }
     // ---- section E operands: long wave, wind, G = 0 soil surface temperature
     double c_tsv = C(CF_TSV), c_omtrdif = C(CF_OMTRDIF), ws = C.wsa((idx >> 5) & 7), c_ufc = C(CF_UFC),
            c_uzfac = C(CF_UZFAC), c_ghafac = C(CF_GHAFAC);
@@ -1313,6 +1365,17 @@ __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, con
         t_wfac, t_lapk, t_es, t_ea, t_ghr, t_de, tc, tdew);
     // --- long wave absorbed by the ground, cpp:1165-1175 -----------------------------
     const double radGlw = 0.97 * (c_tsv * t_rlw + c_omtrdif * t_rem);
+    if constexpr (DG::on) {
+        // radGlw is a product the compiler contracts into the sum radabs below (fma): a second use of that product would keep
+        // it from doing so and the ten outputs would lose their bits.  The sink therefore multiplies an opaque copy of the
+        // bracket — the product rounded once, which is what the reference stores.
+        double lwsum = c_tsv * t_rlw + c_omtrdif * t_rem;
+        asm volatile("" : "+v"(lwsum));
+        const double radGlw_d = 0.97 * lwsum;
+        dg(DG_RADGLW, radGlw_d);
+        dg(DG_RADCLW, (flags & FL_PAI) ? 0.97 * C(CF_SVFA) * t_rlw : radGlw_d);    // cpp:1170 / 1174
+        dg(DG_LWOUT, t_rem);                                                        // cpp:1166
+    }
     // --- wind, cpp:1189-1218 ------------------------------------------------------------
     if (isnan(ws)) ws = 1.0;
     flr<F>(ws, 0.05, cn);
@@ -1324,6 +1387,10 @@ __device__ __forceinline__ void pass1(const CL& C, const TM& T, const SL& S, con
     flr<F>(gHa, 0.0001, cn);
     cy.uf = uf;
     o.uz = uz;
+    if constexpr (DG::on) {
+        dg(DG_UF, uf);
+        dg(DG_GHA, gHa);
+    }
     // --- soil surface temperature with G = 0, cpp:1262-1275 ------------------------------
     const double radabs = radGsw + radGlw;
     double surfwet = fexp(matric * t_wfac, K);
@@ -1395,10 +1462,10 @@ struct Pass2Out {
 // temperature and the Lagrangian profile of a below-canopy cell) is still to come and the register file is past its
 // fullest — where the array-forcing kernel starts loading the next day's forcing (solve_tile).
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
-template <bool F, bool SS, class CL, class TM, class SL, class HK = NoHook>
+template <bool F, bool SS, class CL, class TM, class SL, class HK = NoHook, class DG = NoDiag>
 __device__ __forceinline__ void pass2(const CL& C, const TM& T, const SL& S, const Globals& g, int flags, double dTmx,
                                       const Carry& cy, double dtr, double Rmx, bool above_ground,
-                                      Pass2Out& o, const MathK& K, Canary& cn, HK&& midway = NoHook()) {
+                                      Pass2Out& o, const MathK& K, Canary& cn, HK&& midway = NoHook(), const DG& dg = NoDiag()) {
     const double soilm = cy.soilm;
     // ---- section A operands: soil conductivity, ground heat flux, ground temperature
     double t_gfac = T(TF_GFAC), tc = T(TF_TC), tdew = T(TF_TDEW), ea = T(TF_EA);
@@ -1424,6 +1491,11 @@ __device__ __forceinline__ void pass2(const CL& C, const TM& T, const SL& S, con
     const double Tg = pm_temperature_r<F, F && !TM::in_registers>(cy.num0 - G, cy.rden, dTmx, tc, tdew, cn);
     o.Tg = Tg;
     o.DD = DD;
+    if constexpr (DG::on) {
+        dg(DG_T0, Tg);
+        dg(DG_G, G);
+        dg(DG_KDDG, DD);
+    }
     if (!above_ground) return;
     // ---- section B operands: TVaboveground up to the canopy temperature
     // (with the time values in registers, the three constants used last are read where they are used: one LDS latency

@@ -152,6 +152,16 @@ struct SolveArgs {
     double* tg_ring;
     int64_t tg_tile_stride;
 };
+// A launch of a diagnostics plan (mcf_plan_diag_enable; k_solve_diag): the same description plus a second tiled ring with the
+// output ring's geometry — the block of (tile, day d of the slot, slab s) at
+//   dg_base + tile * dg_tile_stride + d * dg_day_stride + s * ring_block_doubles;
+// dg_sel packs, 4 bits per diagnostic (mcf_diag), its slab (15 = not selected).  A type of its own: k_solve's argument block
+// stays what it was.
+struct DiagSolveArgs : SolveArgs {
+    double* dg_base;
+    int64_t dg_tile_stride, dg_day_stride;
+    uint64_t dg_sel;
+};
 
 struct BelowArgs {
     int64_t N;
@@ -309,6 +319,9 @@ void launch_mxtc(const double* tc, int64_t N, int nsteps, double* mx, hipStream_
 // soil_daily: every day of the launch carries kSoilDaily (vector forcing): the per cell-day soil state is computed once per
 // tile and day and shared through LDS
 void launch_solve(const SolveArgs& a, int cells_per_block, bool af, bool bg, bool fast, bool soil_daily, hipStream_t s);
+// the same launch of a diagnostics plan (vector forcing, reqhgt >= 0): both rings are filled; `fast` / `soil_daily` as above,
+// chosen by the caller exactly as for a plain launch of the same days, so that the ten outputs keep their bits
+void launch_solve_diag(const DiagSolveArgs& a, int cells_per_block, bool fast, bool soil_daily, hipStream_t s);
 // reqhgt < 0 of a streamed plan: the tiled-ring instantiation (SolveArgs tg_ring); the reference-form clamps, no shared soil state,
 // exactly the arithmetic of launch_solve's bg instantiation
 void launch_solve_bg_tiled(const SolveArgs& a, int cells_per_block, bool af, hipStream_t s);

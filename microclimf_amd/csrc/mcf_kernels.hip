@@ -486,8 +486,18 @@ static_assert(solve_threads(21) == 512 && solve_threads(32) == 768, "ring_block_
 //   F   fast clamps (mcf_device.hpp `cap`): only for tiles / days the host has classified REGULAR; a workgroup in which a
 //       canary trips appends its tile to a.fix_list and k_solve_fix redoes the tile's days of this launch with F = false
 //   SSREQ  per cell-day soil state shared through LDS (mcf_device.hpp SoilDay): only for launches whose days are all kSoilDaily
-template <int CPB, int AF, int BG, bool F, bool SSREQ>
-__device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t tile, const int day0, const int ndays, const int rot) {
+// the sink of one tile-day of a diagnostics launch (mcf_device.hpp DiagRing); the selector is made opaque where it is used, like
+// the outputs' (see `put`)
+template <int NT>
+__device__ __forceinline__ DiagRing<NT> diag_sink(const DiagSolveArgs& a, double* day, uint32_t posb) {
+    uint64_t dsel = a.dg_sel;
+    asm volatile("" : "+s"(dsel));
+    return DiagRing<NT>{(char*)day, dsel, posb};
+}
+//   DIAG   the staged model's diagnostics (mcf_device.hpp DiagRing) go to a second ring beside the outputs: k_solve_diag only
+template <int CPB, int AF, int BG, bool F, bool SSREQ, bool DIAG = false, class ARGS = SolveArgs>
+__device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, const int day0, const int ndays, const int rot) {
+    static_assert(!DIAG || (AF == 0 && BG == 0), "diagnostics: vector forcing, reqhgt >= 0");
     constexpr int NT = solve_threads(CPB);
     static_assert(NT == RING_BLOCK(CPB), "tile-day block = one value per lane");
     // the tile's LDS image: [CF_COUNT cell fields + 24 horizon + 8 wind-shelter rows][CPB], as it lies in the table
@@ -740,6 +750,9 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
     double* ring_day = BG == 1 ? nullptr : a.out_base + tile * a.out_tile_stride + (int64_t)a.slot_day0 * a.out_day_stride;
     // BG 2: the tile's Tg block of the day; null when Tz was not requested (no Tg ring)
     double* tg_day = (BG == 2 && a.tg_ring) ? a.tg_ring + tile * a.tg_tile_stride : nullptr;
+    // DIAG: the tile's first block of this launch in the diagnostics ring (uniform), addressed like ring_day
+    double* dg_day = nullptr;
+    if constexpr (DIAG) dg_day = a.dg_base + tile * a.dg_tile_stride + (int64_t)a.slot_day0 * a.dg_day_stride;
     for (int dl = 0; dl < ndays; ++dl, ++run) {
         const int dabs = day0 + dl;
         // the tile's cell constants are restaged whenever the day's vegetation layer changes — workgroup-uniform and rare
@@ -873,8 +886,17 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
 
         Carry cy;
         Pass1Out p1;
+        if constexpr (DIAG) {
+            // NA cells, cells past the raster's end, padding lanes, days outside every vegetation layer: whole blocks of NA
+            if (!valid) {
+                const DiagRing<NT> DR = diag_sink<NT>(a, dg_day, posb);
+#pragma unroll
+                for (int v = 0; v < DG_COUNT; ++v) DR(v, NA);
+            }
+        }
         if (valid) {
             if (AF) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn);
+            else if constexpr (DIAG) pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn, diag_sink<NT>(a, dg_day, posb));
             else pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn);
             if (!PRE) {
                 // every hour lane folds its values into the cell's slots (the 21-cell lane map combines a wave's three hours
@@ -952,6 +974,7 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
             Pass2Out p2{};
             if (AF) derive_time_af_pass2(tv);
             if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
+            else if constexpr (DIAG) pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn, NoHook(), diag_sink<NT>(a, dg_day, posb));
             else pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
             if (BG == 1) {
                 a.tgser[c + N * ((int64_t)dabs * 24 + hr)] = p2.Tg;
@@ -997,6 +1020,7 @@ __device__ __forceinline__ void solve_tile(const SolveArgs& a, const int64_t til
             ring_day += a.out_day_stride;
             if (tg_day) tg_day += NT;
         }
+        if constexpr (DIAG) dg_day += a.dg_day_stride;
         if (!BG) ring_day += a.out_day_stride;
     }
     if (F) {
@@ -1056,6 +1080,32 @@ __global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 :
     for (int i = blockIdx.x; i < n; i += gridDim.x) {
         __syncthreads();
         solve_tile<CPB, AF, false, false, false>(a, (int64_t)a.fix_list[i], a.day0, a.ndays, 0);
+    }
+}
+
+// The staged model's diagnostics (include/mcf.h mcf_diag; vector forcing, reqhgt >= 0): k_solve with the sink of
+// mcf_device.hpp switched on — the same solve_tile, so the ten outputs keep their bits, and the same choice of F / SS / fix-up
+// list as a plain launch of the same days.  Kernels of their own (not a template argument of k_solve: its instantiations keep
+// their symbols and their code) with the fix-up kernel's launch bounds: the sink's extra live values do not fit the 128
+// registers of four waves per SIMD, and an 8-wave workgroup needs only two.
+template <int CPB, bool F, bool SSREQ>
+__global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 : solve_threads(CPB) <= 768 ? 3 : MCF_WAVES_PER_EU) void k_solve_diag(DiagSolveArgs a) {
+    const int rot = (int)((blockIdx.x >> 8) & 1);
+    const int64_t pos = tile_position(a.ntiles_launch);
+    if (pos < 0) return;
+    const int64_t tile = a.tile_list ? (int64_t)a.tile_list[pos] : pos;
+    solve_tile<CPB, 0, 0, F, SSREQ, true>(a, tile, a.day0, a.ndays, rot);
+}
+template <int CPB>
+__global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 : solve_threads(CPB) <= 768 ? 3 : MCF_WAVES_PER_EU) void k_solve_fix_diag(DiagSolveArgs a) {
+    const int n = *a.fix_count;
+    if (n <= 0) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.fix_count + 1, n);
+    const bool all = n > a.fix_cap;
+    const int64_t cnt = all ? (a.N + CPB - 1) / CPB : n;
+    for (int64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
+        __syncthreads();
+        solve_tile<CPB, 0, 0, false, false, true>(a, all ? i : (int64_t)a.fix_list[i], a.day0, a.ndays, 0);
     }
 }
 
@@ -1948,6 +1998,31 @@ static void launch_solve_cpb(SolveArgs a, bool af, bool bg, bool fast, bool ss, 
         if (ss) hipLaunchKernelGGL((k_solve<CPB, 0, false, false, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((k_solve<CPB, 0, false, false, false>), grid, block, 0, s, a);
     }
+}
+// a diagnostics plan's launch: the choice of instantiation launch_solve_cpb makes for vector forcing and reqhgt >= 0
+template <int CPB>
+static void launch_solve_diag_cpb(DiagSolveArgs a, bool fast, bool ss, hipStream_t s) {
+    if (a.ntiles_launch <= 0) {
+        a.ntiles_launch = (a.N + CPB - 1) / CPB;
+        a.tile_list = nullptr;
+    }
+    const dim3 grid = solve_grid(a.ntiles_launch), block(solve_threads(CPB));
+    ss = ss && 2 * CPB <= 64;
+    if (fast) {
+        if (ss) hipLaunchKernelGGL((k_solve_diag<CPB, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_solve_diag<CPB, true, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((k_solve_fix_diag<CPB>), dim3(512), block, 0, s, a);
+    } else {
+        if (ss) hipLaunchKernelGGL((k_solve_diag<CPB, false, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_solve_diag<CPB, false, false>), grid, block, 0, s, a);
+    }
+}
+void launch_solve_diag(const DiagSolveArgs& a, int cells_per_block, bool fast, bool soil_daily, hipStream_t s) {
+    if (a.N <= 0 || a.ndays <= 0 || !a.dg_base) return;
+    if (cells_per_block == 32) launch_solve_diag_cpb<32>(a, fast, soil_daily, s);
+    else if (cells_per_block == 21) launch_solve_diag_cpb<21>(a, fast, soil_daily, s);
+    else if (cells_per_block == 42) launch_solve_diag_cpb<42>(a, fast, soil_daily, s);
+    else launch_solve_diag_cpb<16>(a, fast, soil_daily, s);
 }
 void launch_cells_class(const uint8_t* need, const uint8_t* tile_regular, int64_t N, int cpb, uint8_t* cls, int32_t* blockcnt,
                         hipStream_t s) {

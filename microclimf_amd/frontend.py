@@ -381,6 +381,119 @@ def runmicro(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
     return api.runmicro3Cpp(dfsel, **a, device=device)
 
 
+# ---- the staged workflow: modelin -> soilmdistribute -> twostream -> wind -> soiltemp -> aboveground / belowground ------------
+# The reference's R-mode stages (R/Rimplementation.R:70-342) let a user look inside a run.  Here every stage reads the
+# COMPILED path's own intermediates — the solver's diagnostics ring (include/mcf.h mcf_diag): the values that produce the ten
+# outputs of the same run, with one solar position per time step and runmicro1Cpp's soil-moisture clamp, not the R mode's
+# per-cell solar position and its clamp.  One diagnostics solve per (reqhgt, pai_a, tfact) serves all stages; it is made when
+# the first stage needs device values and kept in `micro`.
+STAGE_FIELDS = {1: ("soilm",),
+                2: ("radGsw", "radGlw", "radCsw", "radClw", "radLsw", "radLpar", "lwout", "Rbdown", "Rddown", "Rdup", "si"),
+                3: ("uf", "uz", "gHa"),
+                4: ("Tg", "T0", "G", "kDDg")}
+_STAGE_OUTPUT = {"soilm": "soilm", "Rbdown": "Rdirdown", "Rddown": "Rdifdown", "Rdup": "Rswup", "uz": "windspeed"}   # from the ten outputs
+
+
+def modelin(micropoint, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, slr=None, apr=None, hor=None, twi=None, wsa=None,
+            svf=None, device: int = 0) -> dict:
+    """`modelin(micropoint, vegp, soilc, dtm)` for data.frame weather (R/Rimplementation.R:70-77): the prepared grid inputs
+    (prepare_grid_inputs: cleaned vegetation and soil, the terrain planes, the wetness index), `progress = 0` and `tme`."""
+    if not isinstance(micropoint, Mapping):
+        raise NotImplementedError("modelin: a list of micropoints (array weather, `.modelina` and its altcorrect) is not "
+                                  "supported — the solver's diagnostics exist for data.frame weather only")
+    inputs = prepare_grid_inputs(micropoint, 0.05, vegp, soilc, dtm, slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf,
+                                 device=device)
+    return {"inputs": inputs, "progress": 0, "tme": micropoint["obstime"], "device": device,
+            "_src": (micropoint, vegp, soilc, dtm), "_runs": {}}
+
+
+def _stage_key(reqhgt, pai_a, tfact):
+    return (max(float(reqhgt), 0.0), None if pai_a is None else np.asarray(pai_a, dtype=np.float64).tobytes(), float(tfact))
+
+
+def _stage_run(micro: dict, reqhgt, pai_a, tfact) -> dict:
+    """the diagnostics solve of (reqhgt, pai_a, tfact): the ten outputs and, under "diag", the thirteen diagnostics.  The ground
+    sees neither reqhgt nor the foliage above it, so a below-ground height is served by the solve at reqhgt = 0."""
+    key = _stage_key(reqhgt, pai_a, tfact)
+    if key not in micro["_runs"]:
+        micropoint, vegp, soilc, dtm = micro["_src"]
+        sc = micro["inputs"]["soilc"]      # the terrain planes made by modelin are handed back: nothing is derived twice
+        a = prepare_grid_inputs(micropoint, key[0], vegp, soilc, dtm, pai_a=pai_a, slr=sc["slope"], apr=sc["aspect"],
+                                hor=sc["hor"], twi=sc["twi"], wsa=sc["wsa"], svf=sc["svfa"], device=micro["device"])
+        a["tfact"] = float(tfact)
+        dfsel = a.pop("dfsel", None)
+        if dfsel is None:
+            res = api.runmicro1Cpp(**a, device=micro["device"], diag="all")
+        else:
+            res = api.runmicro3Cpp(dfsel, **a, device=micro["device"], diag="all")
+        micro["_runs"][key] = res
+    micro["_last"] = key
+    return micro["_runs"][key]
+
+
+def _stage(micro: dict, level: int, reqhgt, pai_a, tfact) -> dict:
+    res = _stage_run(micro, reqhgt, pai_a, tfact)
+    for lv in range(1, level + 1):
+        for name in STAGE_FIELDS[lv]:
+            if name in _STAGE_OUTPUT:
+                if _STAGE_OUTPUT[name] in res:       # (windspeed is not an output at reqhgt = 0, as in the reference)
+                    micro[name] = res[_STAGE_OUTPUT[name]]
+            else:
+                micro[name] = res["diag"]["T0" if name == "Tg" else name]
+    micro["progress"] = max(micro["progress"], level)
+    return micro
+
+
+def soilmdistribute(micro: dict, reqhgt: float = 0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """adds `soilm`, the soil moisture spread by the wetness index (R/Rimplementation.R:97-118); progress 1"""
+    return _stage(micro, 1, reqhgt, pai_a, tfact)
+
+
+def twostream(micro: dict, reqhgt: float = 0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """adds radGsw, radGlw, radCsw, radClw, radLsw, radLpar, lwout, Rbdown, Rddown, Rdup and si (R/Rimplementation.R:136-176,
+    twostreamgrid); progress 2.  Runs soilmdistribute if it has not run."""
+    return _stage(micro, 2, reqhgt, pai_a, tfact)
+
+
+def wind(micro: dict, reqhgt: float = 0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """adds uf, gHa and (reqhgt > 0) uz (R/Rimplementation.R:202-218, windgrid); progress 3"""
+    return _stage(micro, 3, reqhgt, pai_a, tfact)
+
+
+def soiltemp(micro: dict, reqhgt: float = 0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """adds the ground surface temperature (`Tg`, under the reference's list name `T0` too), the ground heat flux `G` and the
+    damping depth `kDDg` (R/Rimplementation.R:242-256, soiltempgrid); progress 4"""
+    return _stage(micro, 4, reqhgt, pai_a, tfact)
+
+
+def aboveground(micro: dict, reqhgt: float = 0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """the reference's eleven arrays (R/Rimplementation.R:291-303, abovegrid): runmicro's ten — those the height has — plus `T0`,
+    all from the one diagnostics solve of (reqhgt, pai_a, tfact)"""
+    if reqhgt < 0:
+        raise ValueError("aboveground needs reqhgt >= 0: see belowground")
+    if micro["progress"] < 4 or micro.get("_last") != _stage_key(reqhgt, pai_a, tfact):
+        soiltemp(micro, reqhgt, pai_a, tfact)
+    res = _stage_run(micro, reqhgt, pai_a, tfact)
+    out = {k: v for k, v in res.items() if k != "diag"}
+    out["T0"] = res["diag"]["T0"]
+    return out
+
+
+def belowground(micro: dict, reqhgt: float = -0.05, pai_a=None, tfact: float = 1.5) -> dict:
+    """Tz, T0 and soilm (R/Rimplementation.R:331-342, belowgrid): Tz and soilm from the below-ground solve of runmicro, T0 from
+    the kept diagnostics solve (the ground's temperature does not depend on reqhgt)"""
+    if reqhgt >= 0:
+        raise ValueError("belowground needs reqhgt < 0: see aboveground")
+    if micro["progress"] < 4 or micro.get("_last") != _stage_key(reqhgt, pai_a, tfact):
+        soiltemp(micro, reqhgt, pai_a, tfact)
+    micropoint, vegp, soilc, dtm = micro["_src"]
+    sc = micro["inputs"]["soilc"]
+    below = runmicro(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, tfact=tfact, out=(1, 0, 0, 1, 0, 0, 0, 0, 0, 0),
+                     slr=sc["slope"], apr=sc["aspect"], hor=sc["hor"], twi=sc["twi"], wsa=sc["wsa"], svf=sc["svfa"],
+                     device=micro["device"])
+    return {"Tz": below["Tz"], "T0": _stage_run(micro, reqhgt, pai_a, tfact)["diag"]["T0"], "soilm": below["soilm"]}
+
+
 # ---- array weather: runpointmodela() and runmicro() -> .runmodel2Cpp / .runmodel4Cpp ------------------------------
 def block_reduce(a, crows: int, ccols: int, how: str = "mean"):
     """A fine raster [rows, cols(, layers)] summarised per coarse cell (the fine cells whose centres fall in it):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Machine digitisation of the reference's published result figures (vignettes/images/*.png) into a committed fixture.
 
-    python tools/digitize_vignette.py            # writes tests/golden/vignette_points.json   (build container only)
+    python tools/digitize_vignette.py                 # writes tests/golden/vignette_points.json       (build container only)
+    python tools/digitize_vignette.py --stage-maps    # writes tests/golden/vignette_stage_maps.json   (the staged section's maps)
 
 The reference holds no numeric outputs of its grid model — its tests assert intervals only — but its
 vignette prints base-R line plots of model output on the bundled example data.  Those PNGs are the only results of the
@@ -35,6 +36,7 @@ from PIL import Image
 ROOT = Path(__file__).resolve().parents[1]
 IMAGES = Path("/root/reference/vignettes/images")
 OUT = ROOT / "tests" / "golden" / "vignette_points.json"
+STAGE_OUT = ROOT / "tests" / "golden" / "vignette_stage_maps.json"
 
 HOURS_2017 = {"Jan 2017": 0, "Apr 2017": 24 * 90, "Jul 2017": 24 * 181, "Oct 2017": 24 * 273, "Jan 2018": 24 * 365}
 
@@ -216,6 +218,19 @@ MAPS = {
 }
 
 
+# The staged section's maps (running-microclimf.Rmd:340-352: `twostream(micro)`, radGsw and radGlw at 10:00 on 20 June), a
+# fixture of their own (STAGE_OUT) written by a separate invocation: vignette_points.json is not touched.  This figure's legend
+# ticks are 3 px strokes starting at the bar's edge (`legend_tick`: the strip beyond the bar a stroke must cover), and its
+# short-wave legend skips one palette step (`colour_tol`: what the tool already allows for short legends).
+STAGE_MAPS = {
+    "image3": dict(rmd="340-352", nrow=50, ncol=50, legend_tick=(1, 4), colour_tol=16, panels=[
+        dict(what="radGsw at 10:00 on 20 June (twostream, monthly-tmax subset)", xticks=XT50, yticks=XT50,
+             legend=[100, 200, 300, 400, 500, 600, 700]),
+        dict(what="radGlw at 10:00 on 20 June (twostream, monthly-tmax subset)", xticks=XT50, yticks=XT50,
+             legend=[250, 300, 350, 400])]),
+}
+
+
 def _runs2d(mask, axis, min_len):
     """black strokes: [(fixed index, start, stop)] of runs of at least min_len along `axis`"""
     out = []
@@ -264,7 +279,8 @@ def digitize_map(name, spec):
         # legend: ticks to the right of the bar
         bt, bb, bl, br = bar
         dk = colour_mask(img, "black")
-        strip = dk[:, br + 2:br + 5].all(axis=1)
+        t0, t1 = spec.get("legend_tick", (2, 5))
+        strip = dk[:, br + t0:br + t1].all(axis=1)
         strip[:max(bt - 2, 0)] = False
         strip[bb + 3:] = False
         lpix = [0.5 * (a + b - 1) for a, b in runs(strip, 1)]
@@ -308,7 +324,7 @@ def digitize_map(name, spec):
                 worst = max(worst, int(d[k]))
                 idx[r, c] = k
         # (a legend shorter than the palette skips colours: a cell may then sit one palette step from the nearest legend row)
-        assert worst <= (6 if len(ramp) >= 300 else 16), f"{name}: a cell colour is {worst} away from every legend colour"
+        assert worst <= spec.get("colour_tol", 6 if len(ramp) >= 300 else 16), f"{name}: a cell colour is {worst} away from every legend colour"
         panels.append({
             "what": ps["what"], "frame_px": {"top": top, "bottom": bot, "left": left, "right": right},
             "legend_px": {"top": bt, "bottom": bb, "left": bl, "right": br}, "extent_by_axes": [round(v, 3) for v in extent],
@@ -323,9 +339,30 @@ def digitize_map(name, spec):
     return {"source": f"vignettes/images/{name}.png", "rmd_lines": spec["rmd"], "panels": panels}
 
 
+ABOUT_MAPS = ("maps: terra::plot rasters; `classes` = [lo, hi] of every legend colour in data units (value = per_px * "
+              "pixel row + at_px0 on the legend), `cells` = [row][col] class index of the raster cell drawn there (row 0 "
+              "= northernmost), -1 = NA; a cell's value is known to the width of its class")
+
+
+def report_map(name, fig):
+    for k, p in enumerate(fig["panels"]):
+        w = np.median([b - a for a, b in p["classes"]])
+        print(f"{name} map {k}: legend {p['legend']['min']:.5g} .. {p['legend']['max']:.5g}, {len(p['classes'])} colour classes of "
+              f"{w:.3g}, fit residual {p['legend']['fit_resid_px']:.2f} px, {sum(v < 0 for r in p['cells'] for v in r)} NA cells")
+
+
 def main():
     if not IMAGES.exists():
         raise SystemExit("the reference's vignette images are not here: this script runs in the build container only")
+    if sys.argv[1:] == ["--stage-maps"]:
+        out = {"_about": "written by tools/digitize_vignette.py --stage-maps from the reference's published figures", "_about_maps": ABOUT_MAPS,
+               "maps": {}}
+        for name, spec in STAGE_MAPS.items():
+            out["maps"][name] = digitize_map(name, spec)
+            report_map(name, out["maps"][name])
+        STAGE_OUT.write_text(json.dumps(out, separators=(",", ":")))
+        print("wrote", STAGE_OUT, STAGE_OUT.stat().st_size, "bytes")
+        return
     only = sys.argv[1:]
     out = {"_about": "written by tools/digitize_vignette.py from the reference's published figures; columns = [x pixel, [first row, "
                      "last row, ...]] = the runs of pixels of the curve's colour in that pixel column (rows count downwards); "
@@ -340,18 +377,13 @@ def main():
             print(f"{name} panel {k}: frame {p['frame_px']}, 1 px = {p['px']['x']:.4g} ({p['x']['is']}) x {p['px']['y']:.4g} "
                   f"({p['y']['is']}); fit residual {p['x']['fit_resid_px']:.2f} / {p['y']['fit_resid_px']:.2f} px; "
                   + ", ".join(f"{c}: {len(v['columns'])} columns" for c, v in p["curves"].items()))
-    out["_about_maps"] = ("maps: terra::plot rasters; `classes` = [lo, hi] of every legend colour in data units (value = per_px * "
-                          "pixel row + at_px0 on the legend), `cells` = [row][col] class index of the raster cell drawn there (row 0 "
-                          "= northernmost), -1 = NA; a cell's value is known to the width of its class")
+    out["_about_maps"] = ABOUT_MAPS
     out["maps"] = {}
     for name, spec in MAPS.items():
         if only and name not in only:
             continue
         out["maps"][name] = digitize_map(name, spec)
-        for k, p in enumerate(out["maps"][name]["panels"]):
-            w = np.median([b - a for a, b in p["classes"]])
-            print(f"{name} map {k}: legend {p['legend']['min']:.5g} .. {p['legend']['max']:.5g}, {len(p['classes'])} colour classes of "
-                  f"{w:.3g}, fit residual {p['legend']['fit_resid_px']:.2f} px, {sum(v < 0 for r in p['cells'] for v in r)} NA cells")
+        report_map(name, out["maps"][name])
     if not only:
         OUT.write_text(json.dumps(out, separators=(",", ":")))
         print("wrote", OUT, OUT.stat().st_size, "bytes")
