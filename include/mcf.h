@@ -1047,7 +1047,39 @@ int mcf_meltmu(int64_t cells, const double *skyview, int64_t n, const double *st
  * with the cell index fastest (an R array [rows, cols, n]); 0.5 where the denominator is 0.  Host code. */
 int mcf_meltmu2(int64_t cells, int64_t n, const double *mu, const double *stemp, const double *tc, double *out);
 int mcf_tpicalc(int64_t rows, int64_t cols, const double *dtm, int32_t af, double tfact, double *tpic, int32_t device);
-/* manCpp (src/microclimfCpp.cpp:597-627): circular trailing mean, via daily means for windows beyond 48 steps. */
+/* mcf_snowmodelq1: the day loop of `.snowmodelq1` (R/internal.R:2690-2776) resident on the device — what
+ * runsnowmodel(method = "fast") runs for a subset point model (R/Cppwrappers.R:717-735).  Once per call the terrain of the
+ * bare dtm (:2690-2706: slope / aspect with NA -> 0 / 180 and masked by the dtm, hor x24, sky view, wsa with s = 10 if
+ * res <= 100 else 1), the step table of the n selected hours (each day's gridmodelsnow1 call restarts the albedo clock) and
+ * intfrac = canintfrac(hgt, pai, 2, mean(snow_all[snow_all > 0]), mean(selected temp), 0) with isnowdg = (1 - intfrac)
+ * isnowdc (:2708-2716).  Per selected day: the pack moved over the gap `sbtn = (ped + 1):(subs[first] - 1)` (R's `a:b`: two
+ * consecutive selected days give the two hours ped + 1, ped) by the point model's balance, its temperature melt scaled per
+ * cell by meltmu (:2724-2741; the gap's sums and means formed by the host left to right), gridmodelsnow1 on the day's 24
+ * hours (:2742), `.tpicalc(af, min(dim), dtm, tfact)` with af = round(10 sqrt(mean wind of the day) / res) — of the BARE dtm:
+ * the ground depth the reference stacks on it is still zero when read (:2750-2753) —, the redistribution of the ground
+ * layer's change and the hand-over of step 24's depths (:2744-2771).  Snow ages are not handed on (every day starts from
+ * isnowac / isnowag).  Nothing per cell crosses PCIe but the inputs, once, and the wanted series, each day's while the next
+ * day computes.  `out`: `.snowmodelq1`'s list minus umu, [rows,cols,n] each, NULL = not wanted (neither finished nor
+ * downloaded); totalSWE = sdepc * sden, as the reference returns it.
+ * MCF_ERR_ARG before any device is touched: null arguments, n = 0 or not whole days, subs outside 1..n_all or not
+ * increasing, array_forcing != 0, a first selected day that is the first day of the series (subs[0] - 1 <= 1: the reference
+ * fails there, `sbtn` not found), a day whose aggregation factor rounds to 0.  One device, one block: a raster that does not
+ * fit is MCF_ERR_NOMEM (the position index and the terrain stencil couple row blocks; no `_multi` form).
+ * mcf_canintfrac_device / mcf_meltmu_device: mcf_canintfrac / mcf_meltmu through the two kernels the call above uses
+ * (upload, one launch, download). */
+typedef struct mcf_snowfast_in {
+    mcf_snowdriver_in drv;  /* drv.base: obstime / clim / pointm of the n = base.tsteps SELECTED hours (vector forcing, whole days),
+                               vegp = .sortl's means (leaft NA -> 0.01 done by the caller), other.{lat, lon, zref, isnowdc, isnowac, isnowag};
+                               other.{isnowdg, slope, aspect, skyview, wsa, hor} ignored; drv.dtm, drv.res, drv.tfact; chunk_steps, af_* ignored */
+    int64_t n_all;          /* length of the complete hourly series */
+    const int64_t *subs;    /* [n] 1-based positions of the selected hours in it */
+    const double *sublmelt, *tempmelt, *rainmelt, *sstemp, *sdenc, *sdeng;   /* [n_all] pointmodelsnow over the whole series */
+    const double *temp_all, *snow_all;                                        /* [n_all] air temperature; precip where temp <= 2, else 0 */
+} mcf_snowfast_in;
+int mcf_snowmodelq1(const mcf_snowfast_in *in, mcf_snowdriver_out *out, int32_t device);
+int mcf_canintfrac_device(int64_t cells, const double *hgt, const double *pai, double uf, double prec, double tc, double Li, double *frac, int32_t device);
+int mcf_meltmu_device(int64_t cells, const double *skyview, int64_t n, const double *stemp, const double *tc, double *mu, int32_t device);
+/* manCpp(src/microclimfCpp.cpp:597-627): circular trailing mean, via daily means for windows beyond 48 steps. */
 int mcf_man(int64_t n, const double *x, int32_t window, double *out);
 
 /* ---- topographic wetness index (soilc$twi) ------------------------------------------------

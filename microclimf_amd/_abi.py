@@ -200,6 +200,14 @@ class SnowDriverIn(C.Structure):
 SNOWDRIVER_OUT = ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden")
 SnowDriverOut = _ptr_struct("SnowDriverOut", SNOWDRIVER_OUT)
 
+SNOWFAST_SERIES = ("sublmelt", "tempmelt", "rainmelt", "sstemp", "sdenc", "sdeng", "temp_all", "snow_all")
+
+
+class SnowFastIn(C.Structure):
+    """include/mcf.h mcf_snowfast_in"""
+    _fields_ = ([("drv", SnowDriverIn), ("n_all", C.c_int64), ("subs", C.POINTER(C.c_int64))]
+                + [(k, c_double_p) for k in SNOWFAST_SERIES])
+
 
 class MicrosnowIn(C.Structure):
     """include/mcf.h mcf_microsnow_in"""
@@ -239,6 +247,7 @@ EXPORTS = (
     "mcf_snowplan_prepare_chunk_dev",
     "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch", "mcf_pointmodelsnow_batch",
     "mcf_bigleaf", "mcf_soilm", "mcf_pointmprocess", "mcf_weatherhgt", "mcf_man", "mcf_pointmodelsnow", "mcf_canintfrac", "mcf_meltmu", "mcf_meltmu2", "mcf_tpicalc",
+    "mcf_snowmodelq1", "mcf_canintfrac_device", "mcf_meltmu_device",
     "mcf_nc_create", "mcf_nc_write_host", "mcf_nc_write_plan", "mcf_nc_close",
     "mcf_flowacc", "mcf_topidx",
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
@@ -557,6 +566,14 @@ def load() -> C.CDLL:
     lib.mcf_snowmodel2.argtypes = [C.POINTER(SnowDriverIn), C.POINTER(SnowDriverOut), C.c_int32]
     lib.mcf_snowmodel1_multi.restype = C.c_int
     lib.mcf_snowmodel1_multi.argtypes = [C.POINTER(SnowDriverIn), C.POINTER(SnowDriverOut), C.POINTER(Multi)]
+    if hasattr(lib, "mcf_snowmodelq1"):       # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_snowmodelq1.restype = C.c_int
+        lib.mcf_snowmodelq1.argtypes = [C.POINTER(SnowFastIn), C.POINTER(SnowDriverOut), C.c_int32]
+        lib.mcf_canintfrac_device.restype = C.c_int
+        lib.mcf_canintfrac_device.argtypes = [C.c_int64, c_double_p, c_double_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                              c_double_p, C.c_int32]
+        lib.mcf_meltmu_device.restype = C.c_int
+        lib.mcf_meltmu_device.argtypes = [C.c_int64, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int32]
     if hasattr(lib, "mcf_runmicrosnow1"):     # (absent from an older library named by MCF_LIB for an A/B run)
         MI, SO = C.POINTER(MicrosnowIn), C.POINTER(SnowDriverOut)
         lib.mcf_runmicrosnow1.restype = C.c_int

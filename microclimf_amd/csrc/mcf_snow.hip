@@ -16,6 +16,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -996,9 +997,9 @@ __global__ void k_sumcount_fin(const double* __restrict__ ws, double* __restrict
     out2[0] = s; out2[1] = n;
 }
 // ws: 2 * kSumParts doubles of scratch
-void launch_sumcount(const double* x, int64_t N, double* ws, double* out2) {
-    hipLaunchKernelGGL(k_sumcount_part, dim3(kSumParts), dim3(256), 0, nullptr, x, N, ws);
-    hipLaunchKernelGGL(k_sumcount_fin, dim3(1), dim3(64), 0, nullptr, ws, out2);
+void launch_sumcount(const double* x, int64_t N, double* ws, double* out2, hipStream_t stream = nullptr) {
+    hipLaunchKernelGGL(k_sumcount_part, dim3(kSumParts), dim3(256), 0, stream, x, N, ws);
+    hipLaunchKernelGGL(k_sumcount_fin, dim3(1), dim3(64), 0, stream, ws, out2);
 }
 // .tpicalc (int:2471-2485) on a row block of the raster.  `z` is the block's surface (dtm + ground snow) with
 // `hn` halo rows above: row b of z is global row row0 - hn + b; RB rows in all.
@@ -2080,6 +2081,29 @@ __global__ __launch_bounds__(256) void k_scale_by_mean(double* __restrict__ x, i
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < N) x[i] /= sumcount[0] / sumcount[1];
 }
+namespace {
+// `.tpicalc(af, min(rows, cols), z, tfact)` of a whole raster held on the device, into d_t: the chunk loop's kernels with one
+// block.  af < min(dim) / 2: block means (d_cm: tpi_coarse_cells doubles) resampled; else the raster mean `zmean` =
+// mean(z, na.rm = TRUE) in their place.  d_ws: 2 * kSumParts doubles, d_m2: 2.  Launches only, all on `stream`.
+bool tpi_is_coarse(int64_t rows, int64_t cols, int af) { return (double)af < std::min(rows, cols) / 2.0; }
+int64_t tpi_coarse_cells(int64_t rows, int64_t cols, int af) { return ((rows + af - 1) / af) * ((cols + af - 1) / af); }
+void tpi_raster(const double* d_z, int64_t rows, int64_t cols, int af, double tfact, double zmean, double* d_t, double* d_ws, double* d_m2,
+                double* d_cm, hipStream_t stream) {
+    const int64_t N = rows * cols;
+    TpiGeo g;
+    g.rows = rows; g.cols = cols; g.RB = rows; g.hn = 0; g.row0 = 0; g.rows_total = rows; g.af = af;
+    g.NItot = (rows + af - 1) / af; g.nJ = (cols + af - 1) / af; g.I0 = 0; g.nI = g.NItot;
+    const unsigned gridN = (unsigned)((N + 255) / 256);
+    if (tpi_is_coarse(rows, cols, af)) {
+        hipLaunchKernelGGL(k_tpi_coarse, dim3((unsigned)((g.nI * g.nJ + 255) / 256)), dim3(256), 0, stream, d_z, g, d_cm);
+        hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, stream, d_z, g, (const double*)d_cm, 0.0, tfact, d_t);
+    } else {
+        hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, stream, d_z, g, (const double*)nullptr, zmean, tfact, d_t);
+    }
+    launch_sumcount(d_t, N, d_ws, d_m2, stream);
+    hipLaunchKernelGGL(k_scale_by_mean, dim3(gridN), dim3(256), 0, stream, d_t, N, (const double*)d_m2);
+}
+}  // namespace
 extern "C" int mcf_tpicalc(int64_t rows, int64_t cols, const double* dtm, int32_t af, double tfact, double* tpic, int32_t device) {
     if (!dtm || !tpic || rows <= 0 || cols <= 0) return mcf::api_fail(MCF_ERR_ARG, "mcf_tpicalc: null argument or empty raster");
     if (af < 1) return mcf::api_fail(MCF_ERR_ARG, "mcf_tpicalc: aggregation factor below 1 (terra::aggregate fails)");
@@ -2094,24 +2118,434 @@ extern "C" int mcf_tpicalc(int64_t rows, int64_t cols, const double* dtm, int32_
     if ((rc = b.make(&d_t, N))) return rc;
     if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
     if ((rc = b.make(&d_m2, 2))) return rc;
-    TpiGeo g;
-    g.rows = rows; g.cols = cols; g.RB = rows; g.hn = 0; g.row0 = 0; g.rows_total = rows; g.af = af;
-    g.NItot = (rows + af - 1) / af; g.nJ = (cols + af - 1) / af; g.I0 = 0; g.nI = g.NItot;
-    const unsigned gridN = (unsigned)((N + 255) / 256);
-    if ((double)af < std::min(rows, cols) / 2.0) {
-        if ((rc = b.make(&d_cm, g.nI * g.nJ))) return rc;
-        hipLaunchKernelGGL(k_tpi_coarse, dim3((unsigned)((g.nI * g.nJ + 255) / 256)), dim3(256), 0, nullptr, d_z, g, d_cm);
-        hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, nullptr, d_z, g, (const double*)d_cm, 0.0, tfact, d_t);
+    double zmean = 0.0;
+    if (tpi_is_coarse(rows, cols, af)) {
+        if ((rc = b.make(&d_cm, tpi_coarse_cells(rows, cols, af)))) return rc;
     } else {
         launch_sumcount(d_z, N, d_ws, d_m2);
         double h[2];
         HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
-        hipLaunchKernelGGL(k_tpi_fine, dim3(gridN), dim3(256), 0, nullptr, d_z, g, (const double*)nullptr, h[0] / h[1], tfact, d_t);
+        zmean = h[0] / h[1];
     }
-    launch_sumcount(d_t, N, d_ws, d_m2);
-    hipLaunchKernelGGL(k_scale_by_mean, dim3(gridN), dim3(256), 0, nullptr, d_t, N, (const double*)d_m2);
+    tpi_raster(d_z, rows, cols, af, tfact, zmean, d_t, d_ws, d_m2, d_cm, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(tpic, d_t, (size_t)N * 8, hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+
+// ---- `.snowmodelq1`, the fast snow method of a subset run (R/internal.R "int:" 2627-2776), as one device-resident call -------
+namespace {
+// canintfrac (cpp:5417-5450): the canopy's share of a snowfall of `prec` mm, one lane per cell.  sint: canopysnowintCpp's
+// Sh (0.26 + 46 / rhos) of the one air temperature, formed by the host.  With dg: isnowdg = (1 - intfrac) isnowdc (int:2716).
+struct CanIntArgs {
+    int64_t N;
+    const double *hgt, *pai;
+    double uf, prec, sint, Li;
+    double* frac;
+    const double* dc;
+    double* dg;
+};
+__global__ __launch_bounds__(256) void k_canintfrac(CanIntArgs a) {
+    snow::snow_tables_init();
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const double h = a.hgt[c];
+    double f = 0.5;                                            // no snowfall in the series (prec 0 or NaN)
+    if (isnan(h)) f = na_real();
+    else if (a.prec > 0.0) f = canopy_snow_interception(h, a.pai[c], a.uf, a.prec, a.sint, a.Li) / a.prec;
+    a.frac[c] = f;
+    if (a.dg) a.dg[c] = (1 - f) * a.dc[c];
+}
+double canopy_sint(double tc) { return 6.2 * (0.26 + 46 / (67.92 + 51.25 * exp(tc / 2.59))); }   // cpp:3728-3729
+
+// The pack between two selected days (int:2724-2741): meltmu (cpp:5454-5492) over the gap's hours and the point model's balance
+// scaled by it, one lane per cell.  The gap's two series are the same for every lane: `st` / `tc` are the device copies of the
+// WHOLE series as `__restrict__` kernel arguments (see k_snowmodel's head), hour k of the gap is element start + step k of them
+// (step = -1: R's `a:b` counting down), so a step's pair comes through scalar loads and nothing is staged per day.  No FMA
+// contraction: the sums are the host entry's (mcf_meltmu) bit for bit, and a pack that melts to +-0 does so on both sides.
+// dc == null: meltmu alone (mcf_meltmu_device); mu: null or where the multiplier goes.
+struct GapArgs {
+    int64_t N, start, len;
+    int32_t step;
+    double dhp;                                  // sum of the gap's positive sstemp
+    double subrain, tempmelt, fall, kc, kg;      // sum(sublmelt) + sum(rainmelt), sum(tempmelt), sum(snow / 1000), 1000 / mean(sdenc), 1000 / mean(sdeng)
+    const double *skyview, *pai, *intfrac;
+    double *dc, *dg, *mu;
+};
+__global__ __launch_bounds__(256) void k_gap_balance(GapArgs a, const double* __restrict__ st, const double* __restrict__ tc) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const double sv = a.skyview[c];
+    double mu = 1.0;                                           // a frozen gap: 1 everywhere, NA cells included (cpp:5484-5490)
+    if (a.dhp > 0.0) {
+        if (isnan(sv)) {
+            mu = na_real();
+        } else {
+            double dhm = 0.0;
+            for (int64_t k = 0; k < a.len; ++k) {
+                const int64_t i = a.start + (int64_t)a.step * k;
+                const double t = tc[i];
+                const double s2 = (st[i] - t) * sv + t;
+                if (s2 > 0.0) dhm += s2;
+            }
+            mu = dhm / a.dhp;
+        }
+    }
+    if (a.mu) a.mu[c] = mu;
+    if (!a.dc) return;
+    const double melt = a.subrain + mu * a.tempmelt;
+    const double balancec = a.fall - melt;
+    const double balanceg = (1 - a.intfrac[c]) * a.fall - exp(-a.pai[c]) * melt;
+    double dc = a.dc[c] + balancec * a.kc, dg = a.dg[c] + balanceg * a.kg;
+    if (dc < 0) dc = 0;                                        // `x[x < 0] <- 0`: NA stays NA
+    if (dg < 0) dg = 0;
+    a.dc[c] = dc; a.dg[c] = dg;
+}
+
+// A selected day's redistribution and hand-over (int:2744-2771; the operations and their order: oracle/snowfast_oracle.py
+// 131-149), one lane per cell over the day's 24 steps of gridmodelsnow1's raw depths.  In place: the pack depth's slab takes
+// totalSWE, the ground depth's the redistributed ground depth — each only if it is wanted (null: not stored); step 23's depths
+// are the next day's isnowdc / isnowdg.  No FMA contraction, as above.
+struct DayRedistArgs {
+    int64_t N;
+    const double *tpi, *sdepc, *sdepg, *sden;    // raw [N][24]
+    double *swe, *gd;                            // [N][24] or null (may be sdepc / sdepg)
+    double *dc, *dg;                             // [N] in: the depths the day started from; out: the next day's
+};
+__global__ __launch_bounds__(256) void k_day_redistribute(DayRedistArgs a) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const double tpi = a.tpi[c], c0 = a.dc[c], g0 = a.dg[c];
+    double sdc = c0, sdg = g0;
+    for (int k = 0; k < 24; ++k) {
+        const int64_t o = c + a.N * k;
+        const double dsnow = a.sdepc[o] - c0, dsnowg = a.sdepg[o] - g0;
+        const double dsnowg2 = dsnowg * tpi;
+        sdc = (dsnow - dsnowg) + dsnowg2 + c0;
+        sdg = dsnowg2 + g0;
+        if (sdc < 0) sdc = 0;
+        if (sdg < 0) sdg = 0;
+        if (a.swe) a.swe[o] = sdc * a.sden[o];
+        if (a.gd) a.gd[o] = sdg;
+    }
+    a.dc[c] = sdc; a.dg[c] = sdg;
+}
+
+struct Streams {   // streams released on every exit path
+    std::vector<hipStream_t> s;
+    ~Streams() { for (hipStream_t x : s) (void)hipStreamDestroy(x); }
+    hipError_t make(hipStream_t* out) {
+        hipError_t r = hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+        if (r == hipSuccess) s.push_back(*out);
+        return r;
+    }
+};
+
+// the gap in front of selected day `day`: R's `(ped + 1):(subs[24 day] - 1)` as (0-based start, step, length)
+struct Gap { int64_t start, len; int32_t step; };
+Gap gap_of_day(const int64_t* subs, int64_t day) {
+    const int64_t ped = day ? subs[24 * day - 1] : 0, a = ped + 1, b = subs[24 * day] - 1;
+    Gap g;
+    g.start = a - 1; g.step = a <= b ? 1 : -1; g.len = (a <= b ? b - a : a - b) + 1;
+    return g;
+}
+// af of a selected day (int:2748-2749): round(10 sqrt(mean wind) / res), half to even
+double day_af(const double* wind24, double res) {
+    double s = 0.0;
+    for (int k = 0; k < 24; ++k) s += wind24[k];
+    return nearbyint(10 * sqrt(s / 24) / res);
+}
+
+constexpr int kTpiCache = 8;    // position indices kept per call, one per distinct af (a [rows, cols] raster each)
+
+int snowmodelq1_checks(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out) {
+    if (!fi || !out) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: null argument");
+    const mcf_snow_inputs* in = &fi->drv.base;
+    if (in->tsteps <= 0 || in->tsteps % 24)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: the fast snow method works on whole selected days (tsteps = 24 x days, at least one)");
+    if (const int rc = common_checks(in)) return rc;
+    if (in->array_forcing != 0)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: array_forcing must be 0 (vector forcing; `.snowmodelq2` is not on the device)");
+    const char* missing = nullptr;
+    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+    each_model_series(*in, [&](auto* host, auto, auto, const char* name) { need(host, name); });
+    need(in->clim.winddir, "climdata$winddir");
+    each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) {
+        if (!terrain && strcmp(name, "other$isnowdg")) need(host, name);          // (isnowdg is formed here, int:2716)
+    });
+    need(fi->drv.dtm, "dtm"); need(fi->subs, "subs");
+    need(fi->sublmelt, "sublmelt"); need(fi->tempmelt, "tempmelt"); need(fi->rainmelt, "rainmelt"); need(fi->sstemp, "sstemp");
+    need(fi->sdenc, "sdenc"); need(fi->sdeng, "sdeng"); need(fi->temp_all, "temp_all"); need(fi->snow_all, "snow_all");
+    if (missing) return mcf::api_fail(MCF_ERR_ARG, std::string("mcf_snowmodelq1: null input: ") + missing);
+    if (!(fi->drv.res > 0)) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: res must be > 0");
+    const int64_t n = in->tsteps;
+    char m[240];
+    for (int64_t k = 0; k < n; ++k) {
+        if (fi->subs[k] < 1 || fi->subs[k] > fi->n_all) {
+            snprintf(m, sizeof m, "mcf_snowmodelq1: subs[%lld] = %lld is outside 1..n_all = %lld", (long long)k, (long long)fi->subs[k],
+                     (long long)fi->n_all);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+        if (k && fi->subs[k] <= fi->subs[k - 1]) {
+            snprintf(m, sizeof m, "mcf_snowmodelq1: subs is not increasing at position %lld", (long long)k);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    }
+    if (fi->subs[0] - 1 <= 1)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: the fast snow method cannot start on the first day of the series (the reference "
+                                          "fails there: `sbtn` not found)");
+    for (int64_t d = 0; d < n / 24; ++d)
+        if (!(day_af(in->clim.windspeed + 24 * d, fi->drv.res) >= 1.0)) {
+            snprintf(m, sizeof m, "mcf_snowmodelq1: aggregation factor round(10*sqrt(mean wind)/res) of selected day %lld is 0 "
+                     "(terra::aggregate fails)", (long long)d);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    return MCF_OK;
+}
+
+int snowmodelq1(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out, int32_t device) {
+    int rc;
+    if ((rc = snowmodelq1_checks(fi, out))) return rc;      // nothing above needs a device
+    const mcf_snow_inputs* in = &fi->drv.base;
+    if ((rc = pick_device(device))) return rc;
+    const int64_t rows = in->rows, cols = in->cols, N = rows * cols, n_all = fi->n_all;
+    const int T = (int)in->tsteps, D = T / 24;
+    const int64_t DN = 24 * N;
+    // which series leave the call; what the day's kernels must write for them and for the hand-over
+    double* const hostv[5] = {out->Tc, out->Tg, out->groundsnowdepth, out->totalSWE, out->snowden};
+    const bool want_den = out->snowden || out->totalSWE;
+    const int nsets = std::min(2, D);
+    const int nser = 2 + (out->Tc != nullptr) + (out->Tg != nullptr) + want_den;
+    // every day's aggregation factor; the distinct ones, in the order they are met, share the cache's slots
+    std::vector<int> af((size_t)D);
+    std::vector<int> distinct;
+    int64_t cm_cells = 1;
+    for (int d = 0; d < D; ++d) {
+        af[(size_t)d] = (int)std::min(day_af(in->clim.windspeed + 24 * d, fi->drv.res), 1e9);
+        if (std::find(distinct.begin(), distinct.end(), af[(size_t)d]) == distinct.end()) distinct.push_back(af[(size_t)d]);
+        if (tpi_is_coarse(rows, cols, af[(size_t)d])) cm_cells = std::max(cm_cells, tpi_coarse_cells(rows, cols, af[(size_t)d]));
+    }
+    const int nslots = (int)std::min<size_t>(kTpiCache, distinct.size());
+    if ((rc = check_room((64 + nslots + (int64_t)nsets * nser * 24) * N * 8 + (2 * n_all + cm_cells) * 8))) return rc;
+    const bool timing = getenv("MCF_TIMING") != nullptr;
+    mcf::DevOwner b;
+    ModelArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = N; a.tsteps = 24; a.zref = in->other.zref;
+    snow_density_params(in->snowenv, a.sdp);
+    // once per call: vegetation, ages, the dtm, the depths' working copies, the whole series' surface and air temperatures
+    each_model_raster(*in, [&](auto* host, auto member, int, bool terrain, const char* name) {
+        if (!rc && !terrain && strcmp(name, "other$isnowdc") && strcmp(name, "other$isnowdg")) rc = b.up(&(a.*member), host, N, name);
+    });
+    if (rc) return rc;
+    const double *d_dtm, *d_st, *d_ta;
+    double *d_dc, *d_dg, *d_intfrac, *d_slope, *d_aspect, *d_svf, *d_wsa, *d_hor, *d_ws, *d_m2, *d_cm;
+    if ((rc = b.up(&d_dtm, fi->drv.dtm, N, "dtm"))) return rc;
+    if ((rc = b.up_mut(&d_dc, in->other.isnowdc, N, "other$isnowdc"))) return rc;
+    if ((rc = b.up(&d_st, fi->sstemp, n_all, "sstemp"))) return rc;
+    if ((rc = b.up(&d_ta, fi->temp_all, n_all, "temp_all"))) return rc;
+    double** const per_cell[] = {&d_dg, &d_intfrac, &d_slope, &d_aspect, &d_svf};
+    for (double** q : per_cell)
+        if ((rc = b.make(q, N))) return rc;
+    if ((rc = b.make(&d_wsa, 8 * N))) return rc;
+    if ((rc = b.make(&d_hor, 24 * N))) return rc;
+    if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
+    if ((rc = b.make(&d_m2, 2))) return rc;
+    if ((rc = b.make(&d_cm, cm_cells))) return rc;
+    a.isnowdc = d_dc; a.isnowdg = d_dg;
+    a.slope = d_slope; a.aspect = d_aspect; a.skyview = d_svf; a.wsa = d_wsa; a.hor = d_hor;
+    const unsigned gridN = (unsigned)((N + 255) / 256);
+    Events evs;
+    if (timing) { HIP_TRY(evs.make(2 + 5 * D)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    // terrain of the bare dtm (int:2690-2706): it does not change between the days
+    {
+        mcf::TerrainDev td;
+        memset(&td, 0, sizeof td);
+        td.rows = rows; td.cols = cols; td.row0 = 0; td.rows_total = rows;
+        td.d_dtm = d_dtm; td.res = fi->drv.res; td.zref = in->other.zref; td.agg = fi->drv.res <= 100 ? 10 : 1; td.aspect_na = 180.0;
+        td.d_slope = d_slope; td.d_aspect = d_aspect; td.d_hor = d_hor; td.d_svfa = d_svf; td.d_wsa = d_wsa;
+        if ((rc = mcf::terrain_device(td))) return rc;
+        hipLaunchKernelGGL(k_mask2, dim3(gridN), dim3(256), 0, nullptr, d_dtm, N, d_slope, d_aspect);
+    }
+    if (timing) HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+    // the step table of all selected hours; every day's gridmodelsnow1 call restarts the albedo clock (snowalbCpp on its slice)
+    StepTables tabs;
+    if ((rc = build_step_tables(b, in, false, true, true, &tabs))) return rc;
+    {
+        const double* d_prec;
+        if ((rc = b.up(&d_prec, in->clim.precip, T, "climdata$precip"))) return rc;
+        hipLaunchKernelGGL(k_snow_alb_chunks, dim3((unsigned)((D + 63) / 64)), dim3(64), 0, nullptr, const_cast<StepRow*>(tabs.rows), d_prec, T, 24, D);
+    }
+    // intfrac of a typical snowfall and the ground layer's share of the initial depth (int:2708-2716)
+    {
+        double ssum = 0.0, tsum = 0.0;
+        int64_t scount = 0;
+        for (int64_t k = 0; k < n_all; ++k)
+            if (fi->snow_all[k] > 0) { ssum += fi->snow_all[k]; ++scount; }
+        for (int k = 0; k < T; ++k) tsum += in->clim.temp[k];
+        CanIntArgs ca;
+        ca.N = N; ca.hgt = a.hgt; ca.pai = a.pai; ca.uf = 2.0; ca.prec = scount ? ssum / (double)scount : NAN;
+        ca.sint = canopy_sint(tsum / T); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = d_dc; ca.dg = d_dg;
+        hipLaunchKernelGGL(k_canintfrac, dim3(gridN), dim3(256), 0, nullptr, ca);
+    }
+    // mean(dtm, na.rm = TRUE): `.tpicalc`'s raster-mean branch
+    double zmean = 0.0;
+    {
+        launch_sumcount(d_dtm, N, d_ws, d_m2);
+        double h[2];
+        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        zmean = h[0] / h[1];
+    }
+    // the day's series, twice: day d + 1 computes into one set while day d's leaves the other
+    struct Set { double *Tc = nullptr, *Tg = nullptr, *sdepc = nullptr, *sdepg = nullptr, *sden = nullptr; } sets[2];
+    for (int s = 0; s < nsets; ++s) {
+        if (out->Tc && (rc = b.make(&sets[s].Tc, DN))) return rc;
+        if (out->Tg && (rc = b.make(&sets[s].Tg, DN))) return rc;
+        if ((rc = b.make(&sets[s].sdepc, DN))) return rc;
+        if ((rc = b.make(&sets[s].sdepg, DN))) return rc;
+        if (want_den && (rc = b.make(&sets[s].sden, DN))) return rc;
+    }
+    // `.tpicalc` of the bare dtm (the depth the reference stacks on it is still zero when read, int:2753) per distinct af
+    struct Slot { int af = 0; double* tpi = nullptr; } slots[kTpiCache];
+    for (int s = 0; s < nslots; ++s)
+        if ((rc = b.make(&slots[s].tpi, N))) return rc;
+    int next_slot = 0, tpi_computed = 0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    Streams streams;
+    hipStream_t cs, ds;                       // the days' kernels; the stream the downloads are ordered on (idle: the host waits for a set's day itself)
+    HIP_TRY(streams.make(&cs));
+    HIP_TRY(streams.make(&ds));
+    Events done;
+    HIP_TRY(done.make(2));
+    mcf::ToHost dl;
+    double t_download = 0.0;
+    auto download = [&](int d) -> hipError_t {                 // day d's wanted series, from the set it was computed into
+        hipError_t e = hipEventSynchronize(done.e[(size_t)(d & 1)]);
+        const auto t0 = std::chrono::steady_clock::now();
+        const Set& s = sets[d % nsets];
+        double* const devv[5] = {s.Tc, s.Tg, s.sdepg, s.sdepc, s.sden};
+        for (int v = 0; v < 5 && e == hipSuccess; ++v)
+            if (hostv[v]) e = dl.dense(hostv[v] + (int64_t)d * DN, devv[v], (size_t)DN * 8, ds);
+        t_download += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return e;
+    };
+    for (int d = 0; d < D; ++d) {
+        hipEvent_t* te = timing ? &evs.e[(size_t)(2 + 5 * d)] : nullptr;
+        if (te) HIP_TRY(hipEventRecord(te[0], cs));
+        // the gap's scalars, in plain left-to-right order over R's `sbtn`
+        const Gap g = gap_of_day(fi->subs, d);
+        GapArgs ga;
+        memset(&ga, 0, sizeof ga);
+        {
+            double sub = 0.0, rain = 0.0, tm = 0.0, fall = 0.0, sc = 0.0, sg = 0.0, dhp = 0.0;
+            for (int64_t k = 0; k < g.len; ++k) {
+                const int64_t i = g.start + g.step * k;
+                sub += fi->sublmelt[i]; rain += fi->rainmelt[i]; tm += fi->tempmelt[i]; fall += fi->snow_all[i] / 1000;
+                sc += fi->sdenc[i]; sg += fi->sdeng[i];
+                if (fi->sstemp[i] > 0.0) dhp += fi->sstemp[i];
+            }
+            ga.N = N; ga.start = g.start; ga.len = g.len; ga.step = g.step;
+            ga.dhp = dhp; ga.subrain = sub + rain; ga.tempmelt = tm; ga.fall = fall;
+            ga.kc = 1000 / (sc / (double)g.len); ga.kg = 1000 / (sg / (double)g.len);
+            ga.skyview = d_svf; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.dc = d_dc; ga.dg = d_dg; ga.mu = nullptr;
+        }
+        hipLaunchKernelGGL(k_gap_balance, dim3(gridN), dim3(256), 0, cs, ga, d_st, d_ta);
+        if (te) HIP_TRY(hipEventRecord(te[1], cs));
+        // gridmodelsnow1 on the day's 24 rows, from the depths just formed and the caller's ages (they are not handed on)
+        const Set& s = sets[d % nsets];
+        a.rows = tabs.rows + 24 * d;
+        a.Tc = s.Tc; a.Tg = s.Tg; a.sdepc = s.sdepc; a.sdepg = s.sdepg; a.sden = s.sden;
+        hipLaunchKernelGGL(k_snowmodel<false>, dim3(gridN), dim3(256), 0, cs, a, a.rows, a.dates);
+        if (te) HIP_TRY(hipEventRecord(te[2], cs));
+        // the day's position index: kept per af; beyond the cache's slots the oldest is computed over
+        const double* d_tpi = nullptr;
+        for (int q = 0; q < nslots; ++q)
+            if (slots[q].af == af[(size_t)d]) d_tpi = slots[q].tpi;
+        if (!d_tpi) {
+            Slot& sl = slots[next_slot];
+            next_slot = (next_slot + 1) % nslots;
+            sl.af = af[(size_t)d];
+            tpi_raster(d_dtm, rows, cols, sl.af, fi->drv.tfact, zmean, sl.tpi, d_ws, d_m2, d_cm, cs);
+            d_tpi = sl.tpi;
+            ++tpi_computed;
+        }
+        if (te) HIP_TRY(hipEventRecord(te[3], cs));
+        DayRedistArgs ra;
+        ra.N = N; ra.tpi = d_tpi; ra.sdepc = s.sdepc; ra.sdepg = s.sdepg; ra.sden = s.sden;
+        ra.swe = out->totalSWE ? s.sdepc : nullptr; ra.gd = out->groundsnowdepth ? s.sdepg : nullptr;
+        ra.dc = d_dc; ra.dg = d_dg;
+        hipLaunchKernelGGL(k_day_redistribute, dim3(gridN), dim3(256), 0, cs, ra);
+        if (te) HIP_TRY(hipEventRecord(te[4], cs));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(done.e[(size_t)(d & 1)], cs));
+        // the day before leaves while this one computes (with one set there is one day)
+        if (d > 0) HIP_TRY(download(d - 1));
+    }
+    HIP_TRY(download(D - 1));
+    HIP_TRY(hipDeviceSynchronize());
+    if (timing) {
+        float ms = 0;
+        double t[4] = {0, 0, 0, 0};
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        const double t_terrain = ms;
+        for (int d = 0; d < D; ++d)
+            for (int q = 0; q < 4; ++q) {
+                HIP_TRY(hipEventElapsedTime(&ms, evs.e[(size_t)(2 + 5 * d + q)], evs.e[(size_t)(2 + 5 * d + q + 1)]));
+                t[q] += ms;
+            }
+        fprintf(stderr, "[mcf] snowmodelq1: %d days, %lld cells: terrain %.2f ms, gap balance %.2f ms, gridmodelsnow %.2f ms, tpi %.2f ms "
+                "(%d of %d days computed), redistribute %.2f ms, downloads %.2f ms of host time\n", D, (long long)N, t_terrain, t[0], t[1],
+                t[2], tpi_computed, D, t[3], t_download * 1e3);
+    }
+    return MCF_OK;
+}
+}  // namespace
+
+extern "C" int mcf_snowmodelq1(const mcf_snowfast_in* in, mcf_snowdriver_out* out, int32_t device) { return snowmodelq1(in, out, device); }
+
+extern "C" int mcf_canintfrac_device(int64_t cells, const double* hgt, const double* pai, double uf, double prec, double tc, double Li,
+                                     double* frac, int32_t device) {
+    if (cells <= 0 || !hgt || !pai || !frac) return mcf::api_fail(MCF_ERR_ARG, "mcf_canintfrac_device: null argument or no cells");
+    int rc;
+    if ((rc = pick_device(device))) return rc;
+    if ((rc = check_room(cells * 24))) return rc;
+    mcf::DevOwner b;
+    CanIntArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = cells; a.uf = uf; a.prec = prec; a.sint = canopy_sint(tc); a.Li = Li;
+    if ((rc = b.up(&a.hgt, hgt, cells, "hgt"))) return rc;
+    if ((rc = b.up(&a.pai, pai, cells, "pai"))) return rc;
+    if ((rc = b.make(&a.frac, cells))) return rc;
+    hipLaunchKernelGGL(k_canintfrac, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(frac, a.frac, (size_t)cells * 8, hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+extern "C" int mcf_meltmu_device(int64_t cells, const double* skyview, int64_t n, const double* stemp, const double* tc, double* mu,
+                                 int32_t device) {
+    if (cells <= 0 || n < 0 || !skyview || !mu || (n > 0 && (!stemp || !tc)))
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu_device: null argument or no cells");
+    int rc;
+    if ((rc = pick_device(device))) return rc;
+    if ((rc = check_room((2 * cells + 2 * n) * 8))) return rc;
+    mcf::DevOwner b;
+    GapArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = cells; a.start = 0; a.len = n; a.step = 1;
+    for (int64_t k = 0; k < n; ++k)
+        if (stemp[k] > 0.0) a.dhp += stemp[k];
+    const double zero = 0.0;
+    const double *d_st, *d_ta;
+    if ((rc = b.up(&a.skyview, skyview, cells, "skyview"))) return rc;
+    if ((rc = b.up(&d_st, n ? stemp : &zero, std::max<int64_t>(n, 1), "stemp"))) return rc;
+    if ((rc = b.up(&d_ta, n ? tc : &zero, std::max<int64_t>(n, 1), "tc"))) return rc;
+    if ((rc = b.make(&a.mu, cells))) return rc;
+    hipLaunchKernelGGL(k_gap_balance, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, a, d_st, d_ta);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(mu, a.mu, (size_t)cells * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

@@ -358,6 +358,29 @@ __device__ __forceinline__ double snow_density(const double* sdp, double depth, 
     return ((sdp[0] - sdp[1]) * (1.0 - gexp(-sdp[2] * depth * (1.0 / 100.0) - sdp[3] * age_h * (1.0 / 24.0))) + sdp[1]) * 1000.0;
 }
 
+// canopysnowintCpp (cpp:3713-3739): the snowfall of `prec` mm a canopy already carrying Li holds back; sint = Sh (0.26 + 46 /
+// rhos), the step's maximum load per branch area (MetT::sint).  One copy for pack_step and k_canintfrac (`canintfrac`).
+__device__ __forceinline__ double canopy_snow_interception(double hgt, double pai, double uf, double prec, double sint, double Li) {
+    double h = hgt, p = pai;
+    if (h < 0.001) h = 0.001;
+    if (p < 0.001) p = 0.001;
+    const double Be = gsqrt(0.003 + (0.2 * p) * 0.5);
+    const double uh = gdiv(uf, Be);
+    const double Lc = gdiv(h, 0.25 * p);                       // 1 / (0.25 * (p / h))
+    const double Lm = 2.0 * (Be * Be * Be) * Lc;
+    const double k1 = gdiv(Be, Lm);
+    double uzm = gdiv(uh, h * k1) * (1 - gexp(-k1 * h));
+    if (uzm < uf) uzm = uf;
+    const double Lstr = sint * p;
+    const double tz = uzm * (1.0 / 0.8);
+    const double kc = 0.5 * gsqrt(1.0 + tz * tz);              // 1 / (2 cos(atan(t))) = sqrt(1 + t^2) / 2
+    const double Cp = 1.0 - gexp(-kc * p);
+    const double I1 = (Lstr - Li) * (1.0 - gexp(-gdiv(Cp, Lstr) * prec));
+    double cis = I1 * 0.678;
+    if (cis > prec) cis = prec;
+    return cis;
+}
+
 // The body of the k loop of gridmodelsnow1/2 for a step that passed `snowtest` (cpp:4340-4396).
 __device__ __forceinline__ void pack_step(const MetT& m, const DayT& dy, const SunT& sun, const CellV& c, double ha,
                                           double ws, const double* sdp, double zref, Pack& s, PackOut& o) {
@@ -481,25 +504,7 @@ __device__ __forceinline__ void pack_step(const MetT& m, const DayT& dy, const S
     // whole model (three exponentials, two square roots, five divisions) is skipped on dry steps — unless a NaN is on its
     // way through Li or uf, which the reference would pass on to the ground pack.
     double cis = 0.0;
-    if (!(m.prec == 0.0 && Li == Li && uf == uf)) {
-        double h = hgt, p = pai;
-        if (h < 0.001) h = 0.001;
-        if (p < 0.001) p = 0.001;
-        const double Be = gsqrt(0.003 + (0.2 * p) * 0.5);
-        const double uh = gdiv(uf, Be);
-        const double Lc = gdiv(h, 0.25 * p);                       // 1 / (0.25 * (p / h))
-        const double Lm = 2.0 * (Be * Be * Be) * Lc;
-        const double k1 = gdiv(Be, Lm);
-        double uzm = gdiv(uh, h * k1) * (1 - gexp(-k1 * h));
-        if (uzm < uf) uzm = uf;
-        const double Lstr = m.sint * p;
-        const double tz = uzm * (1.0 / 0.8);
-        const double kc = 0.5 * gsqrt(1.0 + tz * tz);              // 1 / (2 cos(atan(t))) = sqrt(1 + t^2) / 2
-        const double Cp = 1.0 - gexp(-kc * p);
-        const double I1 = (Lstr - Li) * (1.0 - gexp(-gdiv(Cp, Lstr) * m.prec));
-        cis = I1 * 0.678;
-        if (cis > m.prec) cis = m.prec;
-    }
+    if (!(m.prec == 0.0 && Li == Li && uf == uf)) cis = canopy_snow_interception(hgt, pai, uf, m.prec, m.sint, Li);
     double mRg = 0.0;
     if (m.tc > 0.0) mRg = 0.0125 * m.tc * (m.prec - cis) * 0.001;
     // mass balance, density, age (cpp:3941-3965)

@@ -706,7 +706,8 @@ def sortl(vegp, sdep):
 
 def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, *,
                  snowenv: str = "Taiga", method: str = "fast", snowinitd=0.0, snowinita=0.0, zref: float = 2.0,
-                 windhgt: float | None = None, stfact: float = 0.01, device: int = 0, inputs_only: bool = False) -> dict:
+                 windhgt: float | None = None, stfact: float = 0.01, device: int = 0, inputs_only: bool = False,
+                 one_call: bool = False) -> dict:
     """`runsnowmodel(weather, micropoint, vegp, soilc, dtm, ...)` for data.frame weather (R/Cppwrappers.R:717-735);
     `weather` is always the complete hourly series.  A complete micropoint runs `.snowmodel1` (R/internal.R:2498-2619)
     at the point model's reference height: weather height adjustment, the snow point model (host C++), `.sortl`, the
@@ -716,10 +717,15 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
     model on the selected days only, the pack carried between them by the point model's balance.
     Returns Tc, Tg, groundsnowdepth, totalSWE, snowden, umu.
     `inputs_only` (complete micropoint): everything up to the chunk loop, not the loop — the `snow` mapping of
-    snow.SnowRun / snow.runmicrosnow1 plus `umu`, what `runmicro_snow(..., one_call=True)` takes as `snow_inputs`."""
+    snow.SnowRun / snow.runmicrosnow1 plus `umu`, what `runmicro_snow(..., one_call=True)` takes as `snow_inputs`.
+    `one_call` (subset micropoint, `method = "fast"`): the day loop of `.snowmodelq1` as one device-resident call
+    (snow.snowmodelq1) instead of the host loop over the selected days (snow.snowmodelq1_days)."""
     from . import snow as S
     if method not in ("fast", "slow"):
         raise ValueError('method is "fast" or "slow"')
+    if one_call and (method != "fast" or len(micropoint["subs"]) == micropoint["ntme"]):
+        raise ValueError('one_call: the device-resident day loop is the fast method of a subset micropoint (method = "fast", '
+                         "subsetpointmodel's output)")
     vegp = cleanvegp(vegp)
     w = {k: np.array(weather[k], dtype=np.float64, copy=True) for k in WEATHER if k in weather}
     tme = weather["obstime"]
@@ -758,9 +764,9 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
         ai = subs - 1
         vg["leaft"] = np.where(np.isnan(vg["leaft"]), 0.01, vg["leaft"])
         other = {"zref": zref, "lat": lat, "lon": long, "isnowdc": snowinitd * z, "isnowac": sage, "isnowag": sage}
-        out = S.snowmodelq1_days(_rows(hour_int, ai), _rows(clim, ai), _rows(pointm, ai), pmod, w["temp"],
-                                 np.where(w["temp"] > 2, 0.0, w["precip"]), subs, vg, other, snowenv, z, xres, stfact,
-                                 device=device)
+        days = S.snowmodelq1 if one_call else S.snowmodelq1_days
+        out = days(_rows(hour_int, ai), _rows(clim, ai), _rows(pointm, ai), pmod, w["temp"],
+                   np.where(w["temp"] > 2, 0.0, w["precip"]), subs, vg, other, snowenv, z, xres, stfact, device=device)
         out["umu"] = pmod["umu"][ai]
         return out
     other = {"zref": zref, "lat": lat, "lon": long, "isnowdc": sdep, "isnowac": sage, "isnowdg": sdep * 0.5, "isnowag": sage}

@@ -265,22 +265,24 @@ def snowmodel2_device(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
     return arrays
 
 
-def canintfrac(hgt, pai, uf: float, prec: float, tc: float, Li: float = 0.0) -> np.ndarray:
-    """`canintfrac` (src/microclimfCpp.cpp:5417-5450): the canopy's share of a snowfall of `prec` mm per cell (host code)"""
+def canintfrac(hgt, pai, uf: float, prec: float, tc: float, Li: float = 0.0, *, device: int | None = None) -> np.ndarray:
+    """`canintfrac` (src/microclimfCpp.cpp:5417-5450): the canopy's share of a snowfall of `prec` mm per cell.  Host code;
+    `device`: that device's kernel instead (include/mcf.h mcf_canintfrac_device)"""
     lib = _abi.load()
     h = np.asfortranarray(np.asarray(hgt, dtype=np.float64))
     p = np.asfortranarray(np.asarray(pai, dtype=np.float64))
     if h.shape != p.shape:
         raise ValueError("hgt and pai differ in shape")
     out = np.empty(h.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_canintfrac(C.c_int64(h.size), h.ctypes.data_as(_abi.c_double_p), p.ctypes.data_as(_abi.c_double_p),
-                                  C.c_double(uf), C.c_double(prec), C.c_double(tc), C.c_double(Li),
-                                  out.ctypes.data_as(_abi.c_double_p)))
+    args = (C.c_int64(h.size), h.ctypes.data_as(_abi.c_double_p), p.ctypes.data_as(_abi.c_double_p), C.c_double(uf), C.c_double(prec),
+            C.c_double(tc), C.c_double(Li), out.ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_canintfrac(*args) if device is None else lib.mcf_canintfrac_device(*args, C.c_int32(device)))
     return out
 
 
-def meltmu(skyview, stemp, tc) -> np.ndarray:
-    """`meltmu` (src/microclimfCpp.cpp:5454-5492): per-cell multiplier of the point model's temperature melt (host code)"""
+def meltmu(skyview, stemp, tc, *, device: int | None = None) -> np.ndarray:
+    """`meltmu` (src/microclimfCpp.cpp:5454-5492): per-cell multiplier of the point model's temperature melt.  Host code;
+    `device`: that device's kernel instead (include/mcf.h mcf_meltmu_device)"""
     lib = _abi.load()
     sv = np.asfortranarray(np.asarray(skyview, dtype=np.float64))
     st = np.ascontiguousarray(stemp, dtype=np.float64)
@@ -288,9 +290,9 @@ def meltmu(skyview, stemp, tc) -> np.ndarray:
     if st.shape != ta.shape or st.ndim != 1:
         raise ValueError("stemp and tc must be vectors of one length")
     out = np.empty(sv.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_meltmu(C.c_int64(sv.size), sv.ctypes.data_as(_abi.c_double_p), C.c_int64(st.size),
-                              st.ctypes.data_as(_abi.c_double_p), ta.ctypes.data_as(_abi.c_double_p),
-                              out.ctypes.data_as(_abi.c_double_p)))
+    args = (C.c_int64(sv.size), sv.ctypes.data_as(_abi.c_double_p), C.c_int64(st.size), st.ctypes.data_as(_abi.c_double_p),
+            ta.ctypes.data_as(_abi.c_double_p), out.ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_meltmu(*args) if device is None else lib.mcf_meltmu_device(*args, C.c_int32(device)))
     return out
 
 
@@ -380,6 +382,56 @@ def snowmodelq1_days(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, 
             isnowdc, isnowdg = sdc[:, :, 23].copy(), sdg[:, :, 23].copy()
         swe = out["sdepc"] * out["snowden"]
     return {"Tc": out["Tc"], "Tg": out["Tg"], "groundsnowdepth": out["sdepg"], "totalSWE": swe, "snowden": out["snowden"]}
+
+
+def marshal_snowfast(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact):
+    """-> (the marshalling that keeps the arrays alive, mcf_snowfast_in) for `snowmodelq1`'s arguments"""
+    R, Cc = np.shape(vegp["pai"])
+    oth = _terrain_placeholders(other, R, Cc)
+    oth.setdefault("isnowdg", np.zeros((R, Cc)))
+    m = marshal_snow(obstime, climdata, vegp, oth, False, pointm=pointm, snowenv=snowenv)
+    o = m.inputs.other                                          # ignored by the entry (isnowdg is formed on the device)
+    o.slope = o.aspect = o.skyview = o.wsa = o.hor = o.isnowdg = None
+    fin = _abi.SnowFastIn()
+    fin.drv.base = m.inputs
+    fin.drv.dtm = m.f64(dtm, (R, Cc), "dtm")
+    fin.drv.res, fin.drv.tfact = float(res), float(tfact)
+    n_all = len(np.asarray(temp_all))
+    sub = np.ascontiguousarray(subs, dtype=np.int64)
+    if sub.size != m.tsteps:
+        raise ValueError("subs must name every selected hour")
+    m._keep.append(sub)
+    fin.n_all, fin.subs = n_all, sub.ctypes.data_as(C.POINTER(C.c_int64))
+    whole = dict(pmod, temp_all=temp_all, snow_all=snow_all)
+    for k in _abi.SNOWFAST_SERIES:
+        v = np.ascontiguousarray(whole[k], dtype=np.float64)
+        if v.ndim != 1 or v.size < n_all:
+            raise ValueError(f"{k}: expected the whole series ({n_all} hours), got shape {v.shape}")
+        m._keep.append(v)
+        setattr(fin, k, v.ctypes.data_as(_abi.c_double_p))
+    return m, fin
+
+
+def snowmodelq1(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact=0.02, *,
+                device: int = 0, series: Sequence[str] | None = None) -> dict:
+    """`snowmodelq1_days` as ONE device-resident call (include/mcf.h mcf_snowmodelq1): the same arguments, the same list.  The
+    terrain, the step table and `intfrac` are made once on the device, each selected day's gap balance, grid model, position
+    index and redistribution run there, and only the wanted series come back, a day's while the next day computes.
+    `series`: the names to return (default all five: Tc, Tg, groundsnowdepth, totalSWE, snowden); the others are neither
+    finished nor downloaded.  What the library refuses (a first selected day that is the series' first day, broken days,
+    `subs` out of range) raises _abi.McfError with its message."""
+    lib = _abi.load()
+    m, fin = marshal_snowfast(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact)
+    names = _abi.SNOWDRIVER_OUT if series is None else tuple(series)
+    if not names or any(k not in _abi.SNOWDRIVER_OUT for k in names):
+        raise ValueError(f"series: names out of {_abi.SNOWDRIVER_OUT}")
+    out, arrays = _abi.SnowDriverOut(), {}
+    for k in _abi.SNOWDRIVER_OUT:
+        if k in names:
+            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_snowmodelq1(C.byref(fin), C.byref(out), device))
+    return arrays
 
 
 def _fine_snow_inputs(clim_c, pointm_c, sl, z, zc, rowpos, colpos, altcorrect, wu_c, wv_c, winddir):
