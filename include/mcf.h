@@ -56,7 +56,8 @@ extern "C" {
                              * 7: below ground streamed through day chunks (mcf_plan_create_streamed, mcf_plan_below_prepare);
                              * 8: plans and one-shot solves that take the dtm (mcf_dtm_spec), flow accumulation / wetness index on the device
                              *    (added since, functions only: mcf_plan_below_set_days, mcf_below_days_range, mcf_runmicrosnow1_below,
-                             *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below) */
+                             *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below, mcf_snowmodelq1, mcf_canintfrac_device,
+                             *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -1079,6 +1080,55 @@ typedef struct mcf_snowfast_in {
 int mcf_snowmodelq1(const mcf_snowfast_in *in, mcf_snowdriver_out *out, int32_t device);
 int mcf_canintfrac_device(int64_t cells, const double *hgt, const double *pai, double uf, double prec, double tc, double Li, double *frac, int32_t device);
 int mcf_meltmu_device(int64_t cells, const double *skyview, int64_t n, const double *stemp, const double *tc, double *mu, int32_t device);
+/* mcf_snowmodelq2: the day loop of `.snowmodelq2` (R/internal.R:3219-3286), the fast snow method for ARRAY weather, resident on
+ * the device with the coarse climate and point-model arrays left coarse.  Coarse arrays are R arrays [coarse_rows, coarse_cols,
+ * hours] (column-major: one hour's coarse cells are contiguous); coarse_rowpos / coarse_colpos as in mcf_grid_inputs.  Every
+ * resampling is the bilinear tap (1 - wx) a00 + wx a01, the same for the lower pair, (1 - wy) top + wy bot, without FMA
+ * contraction: a tap has the bits of the host's resampling, so thresholds (`stemp > 0`, the clamps at 0) fall on the same side.
+ * Once per call: the terrain of the bare dtm, the date table, the dtm's mean and the position-index cache as in
+ * mcf_snowmodelq1; intfrac = canintfrac(hgt, pai, 2, msnow, mtemp, 0) with msnow the mean of the positive entries of coarse
+ * `snow` and mtemp = mean(cca(tc), na.rm = TRUE) formed as (sum over the non-hole cells of the tap of the per-coarse-cell time
+ * sums) / (count x n_all) by the device's deterministic reduction — the reference adds the [rows, cols, n_all] array left to
+ * right; the two differ by rounding only, and mtemp feeds canopysnowintCpp's storage term alone.
+ * Per selected day: the pack moved over the gap by the resampled point-model balance, its temperature melt scaled per cell by
+ * meltmu2 of the resampled sstemp / tc (:3229-3244; the six gap sums per coarse cell formed by the host left to right, the
+ * taps and the balance in one kernel); no adjustment, only the clamps, on a first day with subs[0] - 1 <= 1 (accepted here);
+ * the day's thirteen series on the raster from the coarse arrays (:3112-3164: `.cca` masked by the dtm, pressure and wind
+ * unmasked, altcorrect 0 / 1 / 2, relhum capped at 100); gridmodelsnow2; `.tpicalc` with af = round(10 sqrt(mean af_wind) /
+ * res); redistribution and hand-over as in mcf_snowmodelq1; all outputs NA on the dtm's holes (`.cleansmod`).
+ * MCF_ERR_ARG before any device is touched: null arguments (named), n = 0 or not whole days, subs outside 1..n_all or not
+ * increasing, coarse_rows / coarse_cols < 1, null positions or one outside the coarse grid, altcorrect outside 0..2 or > 0
+ * without coarse_dtm, a day whose
+ * aggregation factor rounds to 0, 24 x coarse cells x 8 B >= 2^32.  One device, one block: MCF_ERR_NOMEM if the raster does
+ * not fit (the day's thirteen series are 13 x 24 x 8 B per cell).
+ * mcf_meltmu2_device: the gap kernel alone — mu [rows, cols] from skyview, the dtm (its holes mask the taps) and coarse
+ * sstemp / tc [crows, ccols, n] (upload, one launch, download). */
+typedef struct mcf_snowfast2_in {
+    mcf_snowdriver_in drv;  /* drv.base: rows, cols, tsteps = n SELECTED hours (whole days), snowenv, obstime [n], clim.winddir [n] = the
+                               one direction per hour the model takes (atan2 of the wind components' spatial means), vegp = .sortl's
+                               means (leaft NA -> 0.01 done by the caller), other.{lats, lons, zref, isnowdc, isnowac, isnowag}; the
+                               other members of clim / pointm / other are ignored.  drv.dtm, drv.res, drv.tfact; drv.af_wind [n] =
+                               sqrt(wuv^2 + wvv^2) of the components' spatial means; chunk_steps, af_wsa_s ignored */
+    int64_t coarse_rows, coarse_cols;
+    const double *coarse_rowpos, *coarse_colpos;   /* [rows], [cols] */
+    int32_t altcorrect;                             /* 0, 1 (fixed lapse rate), 2 (moist adiabatic) */
+    int32_t reserved;
+    const double *coarse_dtm;                       /* [crows, ccols], NA read as 0; needed when altcorrect > 0 */
+    /* the selected hours, [crows, ccols, n].  windu / windv: windspeed x cos / sin of the coarse direction, formed by the caller */
+    const double *temp, *relhum, *pres, *swdown, *difrad, *lwdown, *precip, *windu, *windv;
+    const double *Gp, *Tc, *RswabsG, *RlwabsG, *umu;   /* the snow point model per climate cell */
+    int64_t n_all;          /* length of the complete hourly series */
+    const int64_t *subs;    /* [n] 1-based positions of the selected hours in it */
+    const double *sublmelt, *tempmelt, *rainmelt, *snow, *sstemp, *tc, *sdenc, *sdeng;   /* the whole series, [crows, ccols, n_all] */
+} mcf_snowfast2_in;
+typedef struct mcf_snowfast2_out {
+    mcf_snowdriver_out smod;   /* as mcf_snowmodelq1 */
+    double *umu;               /* [rows,cols,n] pointm$umu on the raster, the list's sixth element; NULL = not wanted */
+} mcf_snowfast2_out;
+int mcf_snowmodelq2(const mcf_snowfast2_in *in, mcf_snowfast2_out *out, int32_t device);
+int mcf_meltmu2_device(int64_t rows, int64_t cols, const double *skyview, const double *dtm, int64_t crows, int64_t ccols,
+                       const double *rowpos, const double *colpos, int64_t n, const double *sstemp_c, const double *tc_c,
+                       double *mu_out, int32_t device);
 /* manCpp(src/microclimfCpp.cpp:597-627): circular trailing mean, via daily means for windows beyond 48 steps. */
 int mcf_man(int64_t n, const double *x, int32_t window, double *out);
 

@@ -209,6 +209,24 @@ class SnowFastIn(C.Structure):
                 + [(k, c_double_p) for k in SNOWFAST_SERIES])
 
 
+SNOWFAST2_SELECTED = ("temp", "relhum", "pres", "swdown", "difrad", "lwdown", "precip", "windu", "windv",
+                      "Gp", "Tc", "RswabsG", "RlwabsG", "umu")
+SNOWFAST2_SERIES = ("sublmelt", "tempmelt", "rainmelt", "snow", "sstemp", "tc", "sdenc", "sdeng")
+
+
+class SnowFast2In(C.Structure):
+    """include/mcf.h mcf_snowfast2_in"""
+    _fields_ = ([("drv", SnowDriverIn), ("coarse_rows", C.c_int64), ("coarse_cols", C.c_int64), ("coarse_rowpos", c_double_p),
+                 ("coarse_colpos", c_double_p), ("altcorrect", C.c_int32), ("reserved", C.c_int32), ("coarse_dtm", c_double_p)]
+                + [(k, c_double_p) for k in SNOWFAST2_SELECTED]
+                + [("n_all", C.c_int64), ("subs", C.POINTER(C.c_int64))]
+                + [(k, c_double_p) for k in SNOWFAST2_SERIES])
+
+
+SNOWFAST2_OUT = SNOWDRIVER_OUT + ("umu",)
+SnowFast2Out = _ptr_struct("SnowFast2Out", SNOWFAST2_OUT)      # mcf_snowfast2_out: mcf_snowdriver_out, then umu
+
+
 class MicrosnowIn(C.Structure):
     """include/mcf.h mcf_microsnow_in"""
     _fields_ = [("grid", C.POINTER(GridInputs)), ("snow", C.POINTER(SnowDriverIn)), ("micro", C.POINTER(SnowInputs)),
@@ -247,7 +265,7 @@ EXPORTS = (
     "mcf_snowplan_prepare_chunk_dev",
     "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch", "mcf_pointmodelsnow_batch",
     "mcf_bigleaf", "mcf_soilm", "mcf_pointmprocess", "mcf_weatherhgt", "mcf_man", "mcf_pointmodelsnow", "mcf_canintfrac", "mcf_meltmu", "mcf_meltmu2", "mcf_tpicalc",
-    "mcf_snowmodelq1", "mcf_canintfrac_device", "mcf_meltmu_device",
+    "mcf_snowmodelq1", "mcf_canintfrac_device", "mcf_meltmu_device", "mcf_snowmodelq2", "mcf_meltmu2_device",
     "mcf_nc_create", "mcf_nc_write_host", "mcf_nc_write_plan", "mcf_nc_close",
     "mcf_flowacc", "mcf_topidx",
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
@@ -574,6 +592,12 @@ def load() -> C.CDLL:
                                               c_double_p, C.c_int32]
         lib.mcf_meltmu_device.restype = C.c_int
         lib.mcf_meltmu_device.argtypes = [C.c_int64, c_double_p, C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int32]
+    if hasattr(lib, "mcf_snowmodelq2"):       # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_snowmodelq2.restype = C.c_int
+        lib.mcf_snowmodelq2.argtypes = [C.POINTER(SnowFast2In), C.POINTER(SnowFast2Out), C.c_int32]
+        lib.mcf_meltmu2_device.restype = C.c_int
+        lib.mcf_meltmu2_device.argtypes = [C.c_int64, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p, c_double_p,
+                                           C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int32]
     if hasattr(lib, "mcf_runmicrosnow1"):     # (absent from an older library named by MCF_LIB for an A/B run)
         MI, SO = C.POINTER(MicrosnowIn), C.POINTER(SnowDriverOut)
         lib.mcf_runmicrosnow1.restype = C.c_int

@@ -2267,7 +2267,7 @@ int snowmodelq1_checks(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out)
         return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: the fast snow method works on whole selected days (tsteps = 24 x days, at least one)");
     if (const int rc = common_checks(in)) return rc;
     if (in->array_forcing != 0)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: array_forcing must be 0 (vector forcing; `.snowmodelq2` is not on the device)");
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: array_forcing must be 0 (vector forcing; array weather is mcf_snowmodelq2)");
     const char* missing = nullptr;
     auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
     each_model_series(*in, [&](auto* host, auto, auto, const char* name) { need(host, name); });
@@ -2546,6 +2546,546 @@ extern "C" int mcf_meltmu_device(int64_t cells, const double* skyview, int64_t n
     hipLaunchKernelGGL(k_gap_balance, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, nullptr, a, d_st, d_ta);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(mu, a.mu, (size_t)cells * 8, hipMemcpyDeviceToHost));
+    return MCF_OK;
+}
+
+// ---- `.snowmodelq2`, the fast snow method with array weather (R/internal.R "int:" 3017-3283), as one device-resident call -----
+namespace {
+// Bilinear tap into one hour of a coarse field [crows, ccols] (an R array: one hour's coarse cells are contiguous): the
+// operations of rformulas.upsample_coarse in their order, no FMA contraction — a tap has the host's bits.  (CoarseTap::mix
+// contracts; the solver's taps stay as they are.)  `p`: the field at one hour, uniform over the wave; the four neighbours are
+// 32-bit byte offsets from it (one hour's coarse cells x 8 B < 2^32: checked by the host).
+struct SnowTap {
+    uint32_t o00, o01, o10, o11;
+    double wx, wy;
+    __device__ __forceinline__ SnowTap(double rowpos, double colpos, int crows, int ccols) {
+        const double fr = floor(rowpos), fc = floor(colpos);
+        const int r0 = (int)fr, c0 = (int)fc;
+        const int r1 = r0 + 1 < crows ? r0 + 1 : r0, c1 = c0 + 1 < ccols ? c0 + 1 : c0;
+        wy = rowpos - fr;
+        wx = colpos - fc;
+        o00 = 8u * (uint32_t)(r0 + crows * c0); o01 = 8u * (uint32_t)(r0 + crows * c1);
+        o10 = 8u * (uint32_t)(r1 + crows * c0); o11 = 8u * (uint32_t)(r1 + crows * c1);
+    }
+    __device__ __forceinline__ double operator()(const double* __restrict__ p) const {
+#pragma clang fp contract(off)
+        const char* q = reinterpret_cast<const char*>(p);
+        const double v00 = *reinterpret_cast<const double*>(q + o00), v01 = *reinterpret_cast<const double*>(q + o01),
+                     v10 = *reinterpret_cast<const double*>(q + o10), v11 = *reinterpret_cast<const double*>(q + o11);
+        const double top = (1.0 - wx) * v00 + wx * v01;
+        const double bot = (1.0 - wx) * v10 + wx * v11;
+        return (1.0 - wy) * top + wy * bot;
+    }
+};
+// where a raster cell (column-major index c) lies in the coarse grid
+struct CoarseGeo {
+    int32_t rows, crows, ccols, pad;
+    const double *rowpos, *colpos;      // [rows], [cols]
+    __device__ __forceinline__ SnowTap tap(int64_t c) const {
+        const uint32_t j = (uint32_t)c / (uint32_t)rows, i = (uint32_t)c - j * (uint32_t)rows;
+        return SnowTap(rowpos[i], colpos[j], crows, ccols);
+    }
+};
+
+// The pack between two selected days with array weather (int:3229-3244): meltmu2 (cpp:5495-5527) of the resampled snow-surface
+// and air temperatures over the gap's hours fused with the resampled balance, one lane per cell.  `st` / `tc`: coarse sstemp /
+// tc of the WHOLE series, [hour][coarse cell]; gap hour k is hour start + step k (step = -1: R's `a:b` counting down).  Per
+// hour a lane taps both fields: eight loads, whose addresses the lanes of a workgroup (a stretch of one raster column, or of
+// few) share among a handful of coarse cells — they go straight through the cache, nothing is staged.  A hole of the dtm reads
+// NA taps (`.cca`'s mask): no term, 0.5.  sums: the six gap sums per coarse cell, [6][coarse cells] in the order sublmelt,
+// rainmelt, tempmelt, snow, sdenc, sdeng, tapped here (`.resamplemelt`); the balance in the operand order of
+// oracle/snowfast_oracle.py:239-251.  adjust = 0 (a first day with subs[0] - 1 <= 1): only the clamps.  dc == null: mu alone.
+struct Gap2Args {
+    int64_t N, start, len;
+    int32_t step, adjust;
+    CoarseGeo geo;
+    const double *skyview, *dtm, *pai, *intfrac, *sums;
+    double *dc, *dg, *mu;
+};
+__global__ __launch_bounds__(256) void k_gap_balance2(Gap2Args a, const double* __restrict__ st, const double* __restrict__ tc) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    double mu = 0.5;
+    if (a.adjust) {
+        const double sv = a.skyview[c];
+        if (isnan(sv)) {
+            mu = na_real();
+        } else if (!isnan(a.dtm[c])) {
+            double dhp = 0.0, dhm = 0.0;
+            const double* ps = st + a.start * CC;
+            const double* pt = tc + a.start * CC;
+            const int64_t inc = (int64_t)a.step * CC;
+#pragma unroll 4
+            for (int64_t k = 0; k < a.len; ++k) {
+                const double s = tap(ps), t = tap(pt);
+                if (s > 0.0) dhp += s;
+                const double s2 = (s - t) * sv + t;
+                if (s2 > 0.0) dhm += s2;
+                ps += inc; pt += inc;
+            }
+            if (dhp > 0.0) mu = dhm / dhp;
+        }
+    }
+    if (a.mu) a.mu[c] = mu;
+    if (!a.dc) return;
+    double dc = a.dc[c], dg = a.dg[c];
+    if (a.adjust) {
+        const double sub = tap(a.sums), rain = tap(a.sums + CC), tm = tap(a.sums + 2 * CC), snowsum = tap(a.sums + 3 * CC);
+        const double len = (double)a.len;
+        const double melt = sub + rain + mu * tm;
+        const double balancec = snowsum / 1000 - melt;
+        const double balanceg = (1 - a.intfrac[c]) * snowsum / 1000 - exp(-a.pai[c]) * melt;
+        const double sdec = tap(a.sums + 4 * CC) / len, sdeg = tap(a.sums + 5 * CC) / len;
+        dc = dc + balancec * (1000 / sdec);
+        dg = dg + balanceg * (1000 / sdeg);
+    }
+    if (dc < 0) dc = 0;                                        // `x[x < 0] <- 0`: NA stays NA
+    if (dg < 0) dg = 0;
+    a.dc[c] = dc; a.dg[c] = dg;
+}
+
+// `.satvap` and `.lapserate` (int:501-511, 545-550) in the operand order of rformulas.satvap_R / lapserate_R
+__device__ __forceinline__ double snow_satvap_r(double tc) {
+#pragma clang fp contract(off)
+    return tc < 0.0 ? 0.61078 * exp(21.875 * tc / (tc + 265.5)) : 0.61078 * exp(17.27 * tc / (tc + 237.3));
+}
+__device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double pk) {
+#pragma clang fp contract(off)
+    const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
+    return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
+}
+// A selected day's thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py _fine_snow_inputs), [24][N] as
+// k_snowmodel<true> reads them, one lane per cell.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
+// are not masked.  altcorrect > 0: `pres` holds the coarse pressure already taken to sea level (the host divides by the
+// coarse cell's factor), the cell's own factor brings it back up; the temperature moves by elevd x lapse rate, relative
+// humidity keeps the vapour pressure of the uncorrected field; capped at 100.  `umu` is the day's slab of the output set when
+// the caller wants pointm$umu, so what the model reads is what leaves.
+struct FineArgs {
+    int64_t N, hour0;                  // hour0: the day's first hour in the coarse arrays of the selected hours
+    int32_t altcorrect, pad;
+    CoarseGeo geo;
+    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
+    const double *temp, *relhum, *pres, *swdown, *difrad, *lwdown, *precip, *windu, *windv, *Gp, *Tc, *RswabsG, *RlwabsG, *umu;
+    double *o_temp, *o_relhum, *o_pres, *o_swdown, *o_difrad, *o_lwdown, *o_windspeed, *o_precip, *o_Gp, *o_Tc, *o_RswabsG, *o_RlwabsG,
+        *o_umu;
+};
+__global__ __launch_bounds__(256) void k_fine_day(FineArgs a) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    const double z = a.dtm[c], NA = na_real();
+    const bool hole = isnan(z);
+    double up = 1.0, elevd = 0.0;
+    if (a.altcorrect) {
+        up = pow((293 - 0.0065 * z) / 293, 5.26);
+        elevd = tap(a.zc) - z;
+    }
+    for (int k = 0; k < 24; ++k) {
+        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
+        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
+        double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
+        if (a.altcorrect) {
+            const double ea = snow_satvap_r(temp) * relhum / 100;
+            pres = pres * up;
+            const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
+            temp = lr * elevd + temp;
+            relhum = (ea / snow_satvap_r(temp)) * 100;
+        }
+        if (relhum > 100) relhum = 100.0;
+        const double wu = tap(a.windu + h), wv = tap(a.windv + h);
+        a.o_temp[o] = temp; a.o_relhum[o] = relhum; a.o_pres[o] = pres;
+        a.o_windspeed[o] = sqrt(wu * wu + wv * wv);
+        a.o_swdown[o] = cca(a.swdown); a.o_difrad[o] = cca(a.difrad); a.o_lwdown[o] = cca(a.lwdown); a.o_precip[o] = cca(a.precip);
+        a.o_Gp[o] = cca(a.Gp); a.o_Tc[o] = cca(a.Tc); a.o_RswabsG[o] = cca(a.RswabsG); a.o_RlwabsG[o] = cca(a.RlwabsG);
+        a.o_umu[o] = cca(a.umu);
+    }
+}
+// one coarse plane on the raster, NA on the dtm's holes (mean(cca(tc), na.rm = TRUE) is the mean of this of tc's time sums)
+__global__ __launch_bounds__(256) void k_tap_plane(CoarseGeo geo, int64_t N, const double* __restrict__ dtm, const double* __restrict__ plane,
+                                                   double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const double v = geo.tap(c)(plane);
+    out[c] = isnan(dtm[c]) ? na_real() : v;
+}
+// `.cleansmod`: NA on the dtm's holes in the day's series that leave, [24][N] each (null: not wanted)
+struct CleanArgs {
+    int64_t N;
+    const double* dtm;
+    double* v[5];
+};
+__global__ __launch_bounds__(256) void k_clean_day(CleanArgs a) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N || !isnan(a.dtm[c])) return;
+    const double NA = na_real();
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (a.v[q])
+            for (int k = 0; k < 24; ++k) a.v[q][c + a.N * k] = NA;
+}
+
+// the coarse arrays of the selected hours, in the order k_fine_day's arguments list them
+template <class In, class F>
+void each_coarse_selected(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
+    using A = FineArgs;
+    f(in.temp, &A::temp, "temp"); f(in.relhum, &A::relhum, "relhum"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
+    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.precip, &A::precip, "precip");
+    f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv"); f(in.Gp, &A::Gp, "pointm$Gp"); f(in.Tc, &A::Tc, "pointm$Tc");
+    f(in.RswabsG, &A::RswabsG, "pointm$RswabsG"); f(in.RlwabsG, &A::RlwabsG, "pointm$RlwabsG"); f(in.umu, &A::umu, "pointm$umu");
+}
+
+// every position inside the coarse grid: a tap reads cells floor(pos) and floor(pos) + 1 (or floor(pos) at the far edge)
+bool positions_inside(const double* pos, int64_t n, int64_t ncoarse) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(pos[i] >= 0.0 && pos[i] <= (double)(ncoarse - 1))) return false;
+    return true;
+}
+
+int snowmodelq2_checks(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out) {
+    if (!fi || !out) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: null argument");
+    const mcf_snow_inputs* in = &fi->drv.base;
+    if (in->tsteps <= 0 || in->tsteps % 24)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: the fast snow method works on whole selected days (tsteps = 24 x days, at least one)");
+    if (const int rc = common_checks(in)) return rc;
+    if (fi->coarse_rows < 1 || fi->coarse_cols < 1)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse_rows and coarse_cols must be at least 1");
+    if (fi->altcorrect < 0 || fi->altcorrect > 2) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: altcorrect must be 0, 1 or 2");
+    if (fi->altcorrect > 0 && !fi->coarse_dtm)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
+    const char* missing = nullptr;
+    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+    need(fi->coarse_rowpos, "coarse_rowpos"); need(fi->coarse_colpos, "coarse_colpos");
+    each_coarse_selected(*fi, [&](auto* host, auto, const char* name) { need(host, name); });
+    need(in->clim.winddir, "climdata$winddir");
+    each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) {
+        if (!terrain && strcmp(name, "other$isnowdg")) need(host, name);          // (isnowdg is formed here)
+    });
+    need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
+    need(fi->drv.dtm, "dtm"); need(fi->drv.af_wind, "af_wind"); need(fi->subs, "subs");
+    need(fi->sublmelt, "sublmelt"); need(fi->tempmelt, "tempmelt"); need(fi->rainmelt, "rainmelt"); need(fi->snow, "snow");
+    need(fi->sstemp, "sstemp"); need(fi->tc, "tc"); need(fi->sdenc, "sdenc"); need(fi->sdeng, "sdeng");
+    if (missing) return mcf::api_fail(MCF_ERR_ARG, std::string("mcf_snowmodelq2: null input: ") + missing);
+    if (!(fi->drv.res > 0)) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: res must be > 0");
+    if (!positions_inside(fi->coarse_rowpos, in->rows, fi->coarse_rows) || !positions_inside(fi->coarse_colpos, in->cols, fi->coarse_cols))
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
+    // (a tap is a uniform base + a 32-bit byte offset; the bound of the solver's coarse forcing, which addresses a day at once)
+    if ((double)fi->coarse_rows * (double)fi->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    const int64_t n = in->tsteps;
+    char m[240];
+    for (int64_t k = 0; k < n; ++k) {
+        if (fi->subs[k] < 1 || fi->subs[k] > fi->n_all) {
+            snprintf(m, sizeof m, "mcf_snowmodelq2: subs[%lld] = %lld is outside 1..n_all = %lld", (long long)k, (long long)fi->subs[k],
+                     (long long)fi->n_all);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+        if (k && fi->subs[k] <= fi->subs[k - 1]) {
+            snprintf(m, sizeof m, "mcf_snowmodelq2: subs is not increasing at position %lld", (long long)k);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    }
+    for (int64_t d = 0; d < n / 24; ++d)
+        if (!(day_af(fi->drv.af_wind + 24 * d, fi->drv.res) >= 1.0)) {
+            snprintf(m, sizeof m, "mcf_snowmodelq2: aggregation factor round(10*sqrt(mean af_wind)/res) of selected day %lld is 0 "
+                     "(terra::aggregate fails)", (long long)d);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    return MCF_OK;
+}
+
+int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_t device) {
+    int rc;
+    if ((rc = snowmodelq2_checks(fi, out))) return rc;      // nothing above needs a device
+    const mcf_snow_inputs* in = &fi->drv.base;
+    if ((rc = pick_device(device))) return rc;
+    const int64_t rows = in->rows, cols = in->cols, N = rows * cols, n_all = fi->n_all, CC = fi->coarse_rows * fi->coarse_cols;
+    const int T = (int)in->tsteps, D = T / 24;
+    const int64_t DN = 24 * N;
+    // which series leave the call (umu is one of the day's thirteen inputs: it leaves from the set when it is wanted)
+    double* const hostv[6] = {out->smod.Tc, out->smod.Tg, out->smod.groundsnowdepth, out->smod.totalSWE, out->smod.snowden, out->umu};
+    const bool want_den = out->smod.snowden || out->smod.totalSWE;
+    const int nsets = std::min(2, D);
+    const int nser = 2 + (out->smod.Tc != nullptr) + (out->smod.Tg != nullptr) + want_den + (out->umu != nullptr);
+    std::vector<int> af((size_t)D);
+    std::vector<int> distinct;
+    int64_t cm_cells = 1;
+    for (int d = 0; d < D; ++d) {
+        af[(size_t)d] = (int)std::min(day_af(fi->drv.af_wind + 24 * d, fi->drv.res), 1e9);
+        if (std::find(distinct.begin(), distinct.end(), af[(size_t)d]) == distinct.end()) distinct.push_back(af[(size_t)d]);
+        if (tpi_is_coarse(rows, cols, af[(size_t)d])) cm_cells = std::max(cm_cells, tpi_coarse_cells(rows, cols, af[(size_t)d]));
+    }
+    const int nslots = (int)std::min<size_t>(kTpiCache, distinct.size());
+    if ((rc = check_room((66 + nslots + 13 * 24 + (int64_t)nsets * nser * 24) * N * 8 + ((14 * (int64_t)T + 2 * n_all + 6 * D + 2) * CC + cm_cells) * 8)))
+        return rc;
+    const bool timing = getenv("MCF_TIMING") != nullptr;
+    mcf::DevOwner b;
+    ModelArgs a;
+    memset(&a, 0, sizeof a);
+    a.N = N; a.tsteps = 24; a.zref = in->other.zref;
+    snow_density_params(in->snowenv, a.sdp);
+    each_model_raster(*in, [&](auto* host, auto member, int, bool terrain, const char* name) {
+        if (!rc && !terrain && strcmp(name, "other$isnowdc") && strcmp(name, "other$isnowdg")) rc = b.up(&(a.*member), host, N, name);
+    });
+    if (rc) return rc;
+    if ((rc = up_sites(b, a, in, N))) return rc;
+    CoarseGeo geo;
+    memset(&geo, 0, sizeof geo);
+    geo.rows = (int32_t)rows; geo.crows = (int32_t)fi->coarse_rows; geo.ccols = (int32_t)fi->coarse_cols;
+    if ((rc = b.up(&geo.rowpos, fi->coarse_rowpos, rows, "coarse_rowpos"))) return rc;
+    if ((rc = b.up(&geo.colpos, fi->coarse_colpos, cols, "coarse_colpos"))) return rc;
+    // resident for the call: the coarse arrays of the selected hours, coarse sstemp / tc of the whole series
+    FineArgs fa;
+    memset(&fa, 0, sizeof fa);
+    fa.N = N; fa.altcorrect = fi->altcorrect; fa.geo = geo;
+    std::vector<double> zc, psl;
+    if (fi->altcorrect) {                                      // pressure to sea level on the coarse grid (int:3127-3129)
+        zc.resize((size_t)CC);
+        std::vector<double> down((size_t)CC);
+        for (int64_t q = 0; q < CC; ++q) {
+            zc[(size_t)q] = std::isnan(fi->coarse_dtm[q]) ? 0.0 : fi->coarse_dtm[q];
+            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
+        }
+        psl.resize((size_t)(CC * T));
+        for (int64_t k = 0; k < T; ++k)
+            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = fi->pres[k * CC + q] / down[(size_t)q];
+        if ((rc = b.up(&fa.zc, zc.data(), CC, "coarse_dtm"))) return rc;
+    }
+    each_coarse_selected(*fi, [&](auto* host, auto member, const char* name) {
+        if (!rc) rc = b.up(&(fa.*member), fi->altcorrect && !strcmp(name, "pres") ? psl.data() : host, CC * T, name);
+    });
+    if (rc) return rc;
+    const double *d_dtm, *d_st, *d_ta;
+    double *d_dc, *d_dg, *d_intfrac, *d_slope, *d_aspect, *d_svf, *d_wsa, *d_hor, *d_ws, *d_m2, *d_cm, *d_sums, *d_tsum;
+    if ((rc = b.up(&d_dtm, fi->drv.dtm, N, "dtm"))) return rc;
+    if ((rc = b.up_mut(&d_dc, in->other.isnowdc, N, "other$isnowdc"))) return rc;
+    if ((rc = b.up(&d_st, fi->sstemp, n_all * CC, "sstemp"))) return rc;
+    if ((rc = b.up(&d_ta, fi->tc, n_all * CC, "tc"))) return rc;
+    double** const per_cell[] = {&d_dg, &d_intfrac, &d_slope, &d_aspect, &d_svf};
+    for (double** q : per_cell)
+        if ((rc = b.make(q, N))) return rc;
+    if ((rc = b.make(&d_wsa, 8 * N))) return rc;
+    if ((rc = b.make(&d_hor, 24 * N))) return rc;
+    if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
+    if ((rc = b.make(&d_m2, 2))) return rc;
+    if ((rc = b.make(&d_cm, cm_cells))) return rc;
+    if ((rc = b.make(&d_sums, 6 * CC * D))) return rc;
+    if ((rc = b.make(&d_tsum, CC))) return rc;
+    fa.dtm = d_dtm;
+    // the day's thirteen series on the raster (umu: in the output sets when it leaves)
+    double** const fine[] = {&fa.o_temp, &fa.o_relhum, &fa.o_pres, &fa.o_swdown, &fa.o_difrad, &fa.o_lwdown, &fa.o_windspeed, &fa.o_precip,
+                             &fa.o_Gp, &fa.o_Tc, &fa.o_RswabsG, &fa.o_RlwabsG};
+    for (double** q : fine)
+        if ((rc = b.make(q, DN))) return rc;
+    if (!out->umu && (rc = b.make(&fa.o_umu, DN))) return rc;
+    a.temp = fa.o_temp; a.relhum = fa.o_relhum; a.pres = fa.o_pres; a.swdown = fa.o_swdown; a.difrad = fa.o_difrad; a.lwdown = fa.o_lwdown;
+    a.windspeed = fa.o_windspeed; a.precip = fa.o_precip; a.Gp = fa.o_Gp; a.Tcp = fa.o_Tc; a.RswabsG = fa.o_RswabsG; a.RlwabsG = fa.o_RlwabsG;
+    a.isnowdc = d_dc; a.isnowdg = d_dg;
+    a.slope = d_slope; a.aspect = d_aspect; a.skyview = d_svf; a.wsa = d_wsa; a.hor = d_hor;
+    const unsigned gridN = (unsigned)((N + 255) / 256);
+    Events evs;
+    if (timing) { HIP_TRY(evs.make(2 + 6 * D)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    // terrain of the bare dtm (int:3171-3190), as `.snowmodelq1` makes it
+    {
+        mcf::TerrainDev td;
+        memset(&td, 0, sizeof td);
+        td.rows = rows; td.cols = cols; td.row0 = 0; td.rows_total = rows;
+        td.d_dtm = d_dtm; td.res = fi->drv.res; td.zref = in->other.zref; td.agg = fi->drv.res <= 100 ? 10 : 1; td.aspect_na = 180.0;
+        td.d_slope = d_slope; td.d_aspect = d_aspect; td.d_hor = d_hor; td.d_svfa = d_svf; td.d_wsa = d_wsa;
+        if ((rc = mcf::terrain_device(td))) return rc;
+        hipLaunchKernelGGL(k_mask2, dim3(gridN), dim3(256), 0, nullptr, d_dtm, N, d_slope, d_aspect);
+    }
+    if (timing) HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+    // the date table of all selected hours (array weather: a day's gridmodelsnow2 launch starts its own albedo clock)
+    StepTables tabs;
+    if ((rc = build_step_tables(b, in, true, true, false, &tabs))) return rc;
+    // intfrac of a typical snowfall and the ground layer's share of the initial depth (int:3192-3200)
+    {
+        double ssum = 0.0;
+        int64_t scount = 0;
+        for (int64_t k = 0; k < n_all * CC; ++k)
+            if (fi->snow[k] > 0) { ssum += fi->snow[k]; ++scount; }
+        std::vector<double> tsum((size_t)CC, 0.0);               // per coarse cell: tc added over the series, left to right
+        for (int64_t k = 0; k < n_all; ++k)
+            for (int64_t q = 0; q < CC; ++q) tsum[(size_t)q] += fi->tc[k * CC + q];
+        HIP_TRY(hipMemcpy(d_tsum, tsum.data(), (size_t)CC * 8, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_tap_plane, dim3(gridN), dim3(256), 0, nullptr, geo, N, d_dtm, (const double*)d_tsum, fa.o_temp);
+        launch_sumcount(fa.o_temp, N, d_ws, d_m2);
+        double h[2];
+        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        CanIntArgs ca;
+        ca.N = N; ca.hgt = a.hgt; ca.pai = a.pai; ca.uf = 2.0; ca.prec = scount ? ssum / (double)scount : NAN;
+        ca.sint = canopy_sint(h[0] / (h[1] * (double)n_all)); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = d_dc; ca.dg = d_dg;
+        hipLaunchKernelGGL(k_canintfrac, dim3(gridN), dim3(256), 0, nullptr, ca);
+    }
+    // every gap's six sums per coarse cell, in plain left-to-right order over R's `sbtn` (`.resamplemelt` taps them)
+    {
+        std::vector<double> sums((size_t)(6 * CC * D), 0.0);
+        const double* const gapv[6] = {fi->sublmelt, fi->rainmelt, fi->tempmelt, fi->snow, fi->sdenc, fi->sdeng};
+        for (int d = 0; d < D; ++d) {
+            if (!(fi->subs[24 * d] - 1 > 1)) continue;
+            const Gap g = gap_of_day(fi->subs, d);
+            for (int v = 0; v < 6; ++v)
+                for (int64_t k = 0; k < g.len; ++k) {
+                    const double* src = gapv[v] + (g.start + g.step * k) * CC;
+                    double* dst = &sums[(size_t)((6 * d + v) * CC)];
+                    for (int64_t q = 0; q < CC; ++q) dst[q] += src[q];
+                }
+        }
+        HIP_TRY(hipMemcpy(d_sums, sums.data(), sums.size() * 8, hipMemcpyHostToDevice));
+    }
+    // mean(dtm, na.rm = TRUE): `.tpicalc`'s raster-mean branch
+    double zmean = 0.0;
+    {
+        launch_sumcount(d_dtm, N, d_ws, d_m2);
+        double h[2];
+        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        zmean = h[0] / h[1];
+    }
+    // the day's series, twice: day d + 1 computes into one set while day d's leaves the other
+    struct Set { double *Tc = nullptr, *Tg = nullptr, *sdepc = nullptr, *sdepg = nullptr, *sden = nullptr, *umu = nullptr; } sets[2];
+    for (int s = 0; s < nsets; ++s) {
+        if (out->smod.Tc && (rc = b.make(&sets[s].Tc, DN))) return rc;
+        if (out->smod.Tg && (rc = b.make(&sets[s].Tg, DN))) return rc;
+        if ((rc = b.make(&sets[s].sdepc, DN))) return rc;
+        if ((rc = b.make(&sets[s].sdepg, DN))) return rc;
+        if (want_den && (rc = b.make(&sets[s].sden, DN))) return rc;
+        if (out->umu && (rc = b.make(&sets[s].umu, DN))) return rc;
+    }
+    struct Slot { int af = 0; double* tpi = nullptr; } slots[kTpiCache];
+    for (int s = 0; s < nslots; ++s)
+        if ((rc = b.make(&slots[s].tpi, N))) return rc;
+    int next_slot = 0, tpi_computed = 0;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    Streams streams;
+    hipStream_t cs, ds;                       // the days' kernels; the stream the downloads are ordered on
+    HIP_TRY(streams.make(&cs));
+    HIP_TRY(streams.make(&ds));
+    Events done;
+    HIP_TRY(done.make(2));
+    mcf::ToHost dl;
+    double t_download = 0.0;
+    auto download = [&](int d) -> hipError_t {                 // day d's wanted series, from the set it was computed into
+        hipError_t e = hipEventSynchronize(done.e[(size_t)(d & 1)]);
+        const auto t0 = std::chrono::steady_clock::now();
+        const Set& s = sets[d % nsets];
+        double* const devv[6] = {s.Tc, s.Tg, s.sdepg, s.sdepc, s.sden, s.umu};
+        for (int v = 0; v < 6 && e == hipSuccess; ++v)
+            if (hostv[v]) e = dl.dense(hostv[v] + (int64_t)d * DN, devv[v], (size_t)DN * 8, ds);
+        t_download += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return e;
+    };
+    for (int d = 0; d < D; ++d) {
+        hipEvent_t* te = timing ? &evs.e[(size_t)(2 + 6 * d)] : nullptr;
+        if (te) HIP_TRY(hipEventRecord(te[0], cs));
+        const Gap g = gap_of_day(fi->subs, d);
+        Gap2Args ga;
+        memset(&ga, 0, sizeof ga);
+        ga.N = N; ga.geo = geo; ga.adjust = fi->subs[24 * d] - 1 > 1;
+        ga.skyview = d_svf; ga.dtm = d_dtm; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.sums = d_sums + 6 * CC * d; ga.dc = d_dc; ga.dg = d_dg;
+        if (ga.adjust) { ga.start = g.start; ga.len = g.len; ga.step = g.step; }
+        hipLaunchKernelGGL(k_gap_balance2, dim3(gridN), dim3(256), 0, cs, ga, d_st, d_ta);
+        if (te) HIP_TRY(hipEventRecord(te[1], cs));
+        // the day's weather and point model on the raster
+        const Set& s = sets[d % nsets];
+        fa.hour0 = 24 * (int64_t)d;
+        if (out->umu) fa.o_umu = s.umu;
+        hipLaunchKernelGGL(k_fine_day, dim3(gridN), dim3(256), 0, cs, fa);
+        if (te) HIP_TRY(hipEventRecord(te[2], cs));
+        // gridmodelsnow2 on the day's 24 hours, from the depths just formed and the caller's ages (they are not handed on)
+        a.dates = tabs.dates + 24 * d;
+        a.umu = fa.o_umu;
+        a.Tc = s.Tc; a.Tg = s.Tg; a.sdepc = s.sdepc; a.sdepg = s.sdepg; a.sden = s.sden;
+        hipLaunchKernelGGL(k_snowmodel<true>, dim3(gridN), dim3(256), 0, cs, a, a.rows, a.dates);
+        if (te) HIP_TRY(hipEventRecord(te[3], cs));
+        // the day's position index: kept per af; beyond the cache's slots the oldest is computed over
+        const double* d_tpi = nullptr;
+        for (int q = 0; q < nslots; ++q)
+            if (slots[q].af == af[(size_t)d]) d_tpi = slots[q].tpi;
+        if (!d_tpi) {
+            Slot& sl = slots[next_slot];
+            next_slot = (next_slot + 1) % nslots;
+            sl.af = af[(size_t)d];
+            tpi_raster(d_dtm, rows, cols, sl.af, fi->drv.tfact, zmean, sl.tpi, d_ws, d_m2, d_cm, cs);
+            d_tpi = sl.tpi;
+            ++tpi_computed;
+        }
+        if (te) HIP_TRY(hipEventRecord(te[4], cs));
+        DayRedistArgs ra;
+        ra.N = N; ra.tpi = d_tpi; ra.sdepc = s.sdepc; ra.sdepg = s.sdepg; ra.sden = s.sden;
+        ra.swe = out->smod.totalSWE ? s.sdepc : nullptr; ra.gd = out->smod.groundsnowdepth ? s.sdepg : nullptr;
+        ra.dc = d_dc; ra.dg = d_dg;
+        hipLaunchKernelGGL(k_day_redistribute, dim3(gridN), dim3(256), 0, cs, ra);
+        CleanArgs cl;
+        cl.N = N; cl.dtm = d_dtm;
+        cl.v[0] = s.Tc; cl.v[1] = s.Tg; cl.v[2] = out->smod.groundsnowdepth ? s.sdepg : nullptr;
+        cl.v[3] = out->smod.totalSWE ? s.sdepc : nullptr; cl.v[4] = out->smod.snowden ? s.sden : nullptr;
+        hipLaunchKernelGGL(k_clean_day, dim3(gridN), dim3(256), 0, cs, cl);
+        if (te) HIP_TRY(hipEventRecord(te[5], cs));
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(done.e[(size_t)(d & 1)], cs));
+        // the day before leaves while this one computes (with one set there is one day)
+        if (d > 0) HIP_TRY(download(d - 1));
+    }
+    HIP_TRY(download(D - 1));
+    HIP_TRY(hipDeviceSynchronize());
+    if (timing) {
+        float ms = 0;
+        double t[5] = {0, 0, 0, 0, 0};
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        const double t_terrain = ms;
+        for (int d = 0; d < D; ++d)
+            for (int q = 0; q < 5; ++q) {
+                HIP_TRY(hipEventElapsedTime(&ms, evs.e[(size_t)(2 + 6 * d + q)], evs.e[(size_t)(2 + 6 * d + q + 1)]));
+                t[q] += ms;
+            }
+        fprintf(stderr, "[mcf] snowmodelq2: %d days, %lld cells, %lld coarse cells: terrain %.2f ms, gap balance %.2f ms, "
+                "fine day %.2f ms, gridmodelsnow %.2f ms, tpi %.2f ms (%d of %d days computed), redistribute %.2f ms, downloads "
+                "%.2f ms of host time\n", D, (long long)N, (long long)CC, t_terrain, t[0], t[1], t[2], t[3], tpi_computed, D, t[4],
+                t_download * 1e3);
+    }
+    return MCF_OK;
+}
+}  // namespace
+
+extern "C" int mcf_snowmodelq2(const mcf_snowfast2_in* in, mcf_snowfast2_out* out, int32_t device) { return snowmodelq2(in, out, device); }
+
+extern "C" int mcf_meltmu2_device(int64_t rows, int64_t cols, const double* skyview, const double* dtm, int64_t crows, int64_t ccols,
+                                  const double* rowpos, const double* colpos, int64_t n, const double* sstemp_c, const double* tc_c,
+                                  double* mu_out, int32_t device) {
+    if (rows <= 0 || cols <= 0 || crows < 1 || ccols < 1 || n < 0 || !skyview || !dtm || !rowpos || !colpos || !mu_out ||
+        (n > 0 && (!sstemp_c || !tc_c)))
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: null argument, empty raster or empty coarse grid");
+    if (rows * cols >= ((int64_t)1 << 29) || (double)crows * (double)ccols * 24.0 * 8.0 >= 4294967296.0)
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: raster or coarse grid too large");
+    if (!positions_inside(rowpos, rows, crows) || !positions_inside(colpos, cols, ccols))
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: rowpos / colpos must lie in 0..crows - 1 / 0..ccols - 1");
+    int rc;
+    if ((rc = pick_device(device))) return rc;
+    const int64_t N = rows * cols, CC = crows * ccols;
+    if ((rc = check_room((3 * N + rows + cols + 2 * n * CC) * 8))) return rc;
+    mcf::DevOwner b;
+    Gap2Args a;
+    memset(&a, 0, sizeof a);
+    a.N = N; a.start = 0; a.len = n; a.step = 1; a.adjust = 1;
+    a.geo.rows = (int32_t)rows; a.geo.crows = (int32_t)crows; a.geo.ccols = (int32_t)ccols;
+    const double zero = 0.0;
+    const double *d_st, *d_ta;
+    if ((rc = b.up(&a.geo.rowpos, rowpos, rows, "rowpos"))) return rc;
+    if ((rc = b.up(&a.geo.colpos, colpos, cols, "colpos"))) return rc;
+    if ((rc = b.up(&a.skyview, skyview, N, "skyview"))) return rc;
+    if ((rc = b.up(&a.dtm, dtm, N, "dtm"))) return rc;
+    if ((rc = b.up(&d_st, n ? sstemp_c : &zero, std::max<int64_t>(n * CC, 1), "sstemp"))) return rc;
+    if ((rc = b.up(&d_ta, n ? tc_c : &zero, std::max<int64_t>(n * CC, 1), "tc"))) return rc;
+    if ((rc = b.make(&a.mu, N))) return rc;
+    hipLaunchKernelGGL(k_gap_balance2, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, a, d_st, d_ta);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(mu_out, a.mu, (size_t)N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

@@ -785,7 +785,7 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
 def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, vegp: Mapping, soilc: Mapping, dtm: Mapping, *,
                   dtmc, lats_c, lons_c, lats, lons, altcorrect: int = 0, snowenv: str = "Taiga", method: str = "fast",
                   snowinitd: float = 0.0, snowinita: float = 0.0, zref: float = 2.0, windhgt: float | None = None,
-                  stfact: float = 0.01, device: int = 0, point_device: int | None = None) -> dict:
+                  stfact: float = 0.01, device: int = 0, point_device: int | None = None, one_call: bool = False) -> dict:
     """`runsnowmodel(climarrayr, micropointa, vegp, soilc, dtm, dtmc, tme, altcorrect, ...)` for array weather
     (R/Cppwrappers.R:735-757 -> `.snowmodel2`, R/internal.R:2777-3013): the snow point model once per cell of
     the climate grid (`point_device=None`: host C++, a cell at a time; an int: every cell as one batch on that device,
@@ -793,9 +793,10 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     [crows, ccols] of the climate grid; `lats`, `lons`: [rows, cols] of the fine raster.  A subset micropoint list with
     `method = "slow"` runs the whole series and subsets it (here `umu` too along time; the reference indexes the array as
     a vector there); `method = "fast"` runs `.snowmodelq2` (R/internal.R:3017-3283) = `snow.snowmodelq2_days`.  As in the reference every climate cell needs
-    data, and vegetation taller than `zref` fails (`.snowmodel2` stops at R/internal.R:2838, `climdfr` not found)."""
+    data, and vegetation taller than `zref` fails (`.snowmodel2` stops at R/internal.R:2838, `climdfr` not found).
+    `one_call` (subset micropoints, `method = "fast"`): the day loop as one device-resident call with the coarse arrays left
+    coarse (`snow.snowmodelq2`) instead of the host day loop; the default is unchanged."""
     from . import snow as S
-    vegp = cleanvegp(vegp)
     if any(m is None for m in micropointa):
         raise ValueError("every coarse cell needs a micropoint")
     last = micropointa[-1]                                            # the reference's loop keeps the last one's subs
@@ -803,6 +804,10 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     if method not in ("fast", "slow"):
         raise ValueError('method is "fast" or "slow"')
     fast = subset and method == "fast"
+    if one_call and not fast:
+        raise ValueError('one_call: the device-resident day loop is the fast method of subset micropoints (method = "fast", '
+                         "subsetpointmodel's output for every climate cell)")
+    vegp = cleanvegp(vegp)
     if subset:
         zref = float(zref)
         windhgt = zref if windhgt is None else float(windhgt)
@@ -838,8 +843,9 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
         vg = sortl(vegp, np.max(pm_s["sdepc"], axis=(0, 1)))
         other = {"zref": zref, "lats": np.asarray(lats, dtype=np.float64), "lons": np.asarray(lons, dtype=np.float64),
                  "isnowdc": z * 0 + snowinitd, "isnowac": z * 0 + snowinita, "isnowag": z * 0 + snowinita}
-        return S.snowmodelq2_days(sel(ob), sel(clim_c), pm_s, pm2_c, subs, vg, other, snowenv, z, np.asarray(dtmc, dtype=np.float64),
-                                  xres, stfact, rowpos=rowpos, colpos=colpos, altcorrect=altcorrect, device=device)
+        days = S.snowmodelq2 if one_call else S.snowmodelq2_days
+        return days(sel(ob), sel(clim_c), pm_s, pm2_c, subs, vg, other, snowenv, z, np.asarray(dtmc, dtype=np.float64),
+                    xres, stfact, rowpos=rowpos, colpos=colpos, altcorrect=altcorrect, device=device)
     vg = sortl(vegp, np.max(pointm_c["sdepc"], axis=(0, 1)))
     sdep = z * 0 + snowinitd
     sage = z * 0 + snowinita

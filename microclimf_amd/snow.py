@@ -554,6 +554,102 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
     return res_
 
 
+def marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect=0):
+    """-> (the marshalling that keeps the arrays alive, mcf_snowfast2_in) for `snowmodelq2`'s arguments: the coarse arrays
+    stay coarse; the wind components, the one direction per hour and `af_wind` are formed here as `snowmodelq2_days` forms them"""
+    z = np.asarray(dtm, dtype=np.float64)
+    R, Cc = z.shape
+    cr, cc, n = np.shape(clim_c["temp"])
+    m = SnowMarshalled()
+    m.rows, m.cols, m.tsteps = R, Cc, n
+    sub = np.ascontiguousarray(subs, dtype=np.int64)
+    if sub.size != n or len(np.asarray(obstime["year"])) != n:
+        raise ValueError("subs and obstime must name every selected hour")
+    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
+    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
+    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
+    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
+    fin = _abi.SnowFast2In()
+    si = fin.drv.base
+    si.rows, si.cols, si.tsteps, si.array_forcing = R, Cc, n, 1
+    si.snowenv = _abi.SNOWENV.get(snowenv, 0)
+    si.obstime.year = m.i32(obstime["year"], (n,), "obstime$year")
+    si.obstime.month = m.i32(obstime["month"], (n,), "obstime$month")
+    si.obstime.day = m.i32(obstime["day"], (n,), "obstime$day")
+    si.obstime.hour = m.f64(obstime["hour"], (n,), "obstime$hour")
+    si.clim.winddir = m.f64((np.arctan2(wvv, wuv) * 180 / np.pi) % 360, (n,), "winddir")
+    for f in ("pai", "hgt", "leaft", "clump"):
+        v = np.asarray(vegp[f], dtype=np.float64)
+        setattr(si.vegp, f, m.f64(np.where(np.isnan(v), 0.01, v) if f == "leaft" else v, (R, Cc), f"vegp${f}"))
+    o = si.other
+    o.zref = float(other["zref"])
+    o.lat = o.lon = float("nan")
+    o.lats = m.f64(_get(other, "lats", "lat"), (R, Cc), "other$lats")
+    o.lons = m.f64(_get(other, "lons", "lon"), (R, Cc), "other$lons")
+    o.isnowdc = m.f64(other["isnowdc"], (R, Cc), "other$isnowdc")
+    o.isnowac = m.i32(other["isnowac"], (R, Cc), "other$isnowac")
+    o.isnowag = m.i32(other["isnowag"], (R, Cc), "other$isnowag")
+    fin.drv.dtm = m.f64(z, (R, Cc), "dtm")
+    fin.drv.res, fin.drv.tfact = float(res), float(tfact)
+    fin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (n,), "af_wind")
+    fin.coarse_rows, fin.coarse_cols, fin.altcorrect = cr, cc, int(altcorrect)
+    fin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
+    fin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
+    fin.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
+    selected = dict(clim_c, windu=wu_c, windv=wv_c, **{k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu")})
+    for k in _abi.SNOWFAST2_SELECTED:
+        setattr(fin, k, m.f64(selected[k], (cr, cc, n), k))
+    n_all = np.shape(pm2_c["tc"])[2]
+    m._keep.append(sub)
+    fin.n_all, fin.subs = n_all, sub.ctypes.data_as(C.POINTER(C.c_int64))
+    for k in _abi.SNOWFAST2_SERIES:
+        setattr(fin, k, m.f64(pm2_c[k], (cr, cc, n_all), k))
+    return m, fin
+
+
+def snowmodelq2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact=0.02, *, rowpos, colpos,
+                altcorrect: int = 0, device: int = 0, series: Sequence[str] | None = None) -> dict:
+    """`snowmodelq2_days` as ONE device-resident call (include/mcf.h mcf_snowmodelq2): the same arguments, the same six-entry
+    list.  The coarse arrays are uploaded once and stay coarse; the terrain, the date table and `intfrac` are made once on the
+    device, each selected day's gap balance (meltmu2 of the resampled temperatures fused with the resampled balance), the day's
+    thirteen series on the raster, the grid model, the position index and the redistribution run there, and only the wanted
+    series come back, a day's while the next day computes.  `series`: the names to return (default all six: Tc, Tg,
+    groundsnowdepth, totalSWE, snowden, umu); the others are neither finished nor downloaded.  What the library refuses raises
+    _abi.McfError with its message."""
+    lib = _abi.load()
+    m, fin = marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos,
+                               altcorrect)
+    names = _abi.SNOWFAST2_OUT if series is None else tuple(series)
+    if not names or any(k not in _abi.SNOWFAST2_OUT for k in names):
+        raise ValueError(f"series: names out of {_abi.SNOWFAST2_OUT}")
+    out, arrays = _abi.SnowFast2Out(), {}
+    for k in _abi.SNOWFAST2_OUT:
+        if k in names:
+            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_snowmodelq2(C.byref(fin), C.byref(out), device))
+    return arrays
+
+
+def meltmu2_coarse(skyview, dtm, sstemp_c, tc_c, rowpos, colpos, device: int = 0) -> np.ndarray:
+    """`meltmu2` of coarse snow-surface and air temperatures [crows, ccols, n] resampled to the raster inside the kernel
+    (include/mcf.h mcf_meltmu2_device): what `snowmodelq2` runs per gap; the dtm's holes mask the resampled series"""
+    lib = _abi.load()
+    sv = np.asfortranarray(np.asarray(skyview, dtype=np.float64))
+    z = np.asfortranarray(np.asarray(dtm, dtype=np.float64))
+    st = np.asfortranarray(np.asarray(sstemp_c, dtype=np.float64))
+    ta = np.asfortranarray(np.asarray(tc_c, dtype=np.float64))
+    rp, cp = np.ascontiguousarray(rowpos, dtype=np.float64), np.ascontiguousarray(colpos, dtype=np.float64)
+    if st.shape != ta.shape or st.ndim != 3 or sv.shape != z.shape or rp.shape != (z.shape[0],) or cp.shape != (z.shape[1],):
+        raise ValueError("sstemp_c and tc_c must be [crows, ccols, n], skyview and dtm one raster with a position per row and column")
+    out = np.empty(z.shape, dtype=np.float64, order="F")
+    p = lambda a: a.ctypes.data_as(_abi.c_double_p)                                      # noqa: E731
+    _abi.check(lib.mcf_meltmu2_device(C.c_int64(z.shape[0]), C.c_int64(z.shape[1]), p(sv), p(z), C.c_int64(st.shape[0]),
+                                      C.c_int64(st.shape[1]), p(rp), p(cp), C.c_int64(st.shape[2]), p(st), p(ta), p(out),
+                                      C.c_int32(device)))
+    return out
+
+
 def snowmodel2_chunks(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact=0.02, *, rowpos, colpos,
                       altcorrect: int = 0, agg: int = 10, chunk_steps: int = 120, device: int = 0) -> dict:
     """The second half of the reference's `.snowmodel2` (R/internal.R:2862-3013): coarse climate and snow point-model
