@@ -57,7 +57,8 @@ extern "C" {
                              * 8: plans and one-shot solves that take the dtm (mcf_dtm_spec), flow accumulation / wetness index on the device
                              *    (added since, functions only: mcf_plan_below_set_days, mcf_below_days_range, mcf_runmicrosnow1_below,
                              *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below, mcf_snowmodelq1, mcf_canintfrac_device,
-                             *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device) */
+                             *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device, mcf_plan_summary_*, mcf_runmicro_summary,
+                             *    mcf_runmicro_summary_multi) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -518,6 +519,74 @@ int mcf_runbioclim3_multi(const mcf_grid_inputs *in, const mcf_options *opt, con
                           mcf_bioclim_out *out);
 int mcf_runbioclim4_multi(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_bioclim_sel *sel, const mcf_multi *multi,
                           mcf_bioclim_out *out);
+
+/* ---- period summaries --------------------------------------------------------------------------------------------------
+ * Per-cell statistics of the solver's outputs over caller-defined periods (what users of the reference do with
+ * apply(mout$Tz, c(1, 2), mean) and with monthly mean / minimum / maximum maps), accumulated on the device from each ring
+ * chunk as it is produced: nothing of size cells x steps exists on either side.  For reqhgt >= 0 (the tiled ring).
+ *
+ * `summary`, defined here once.  A summary is
+ *   - a table period_of_day[days of the plan], values 0 .. nperiods - 1, or -1 for a day that is not counted (periods need not
+ *     be contiguous: "all Januaries" is a period);
+ *   - a selection var[] of output variables, each one the plan was created with;
+ *   - a selection stat[] of the six statistics below; HOURS_ABOVE takes one threshold per variable.
+ * Per (cell, period, variable), over the counted days in ascending day order, v the value of a step:
+ *   sum       s = s + v from s = 0, step by step in time order, in fp64, never reassociated;  MEAN = s / (24 days)
+ *   MIN, MAX  the strict comparisons v < mn, v > mx in time order, from the period's first counted value
+ *   MEAN_DAILY_MAX / _MIN  the day's maximum / minimum formed the same way over its 24 hours, added day by day from 0, then
+ *             divided by `days`
+ *   HOURS_ABOVE  the number of steps with v > threshold[var], as a double
+ *   NA rule   if any value of the (cell, period, variable) is NaN — NA cells, days outside every vegetation layer — every
+ *             statistic of it is NA_real_ (R's bit pattern), as is every statistic of a period without a counted day.
+ * The result is a function of the ring's values alone: it does not depend on ring days, chunking, slot placement or tile size. */
+enum mcf_stat {
+    MCF_STAT_MEAN = 0,
+    MCF_STAT_MIN = 1,
+    MCF_STAT_MAX = 2,
+    MCF_STAT_MEAN_DAILY_MAX = 3,
+    MCF_STAT_MEAN_DAILY_MIN = 4,
+    MCF_STAT_HOURS_ABOVE = 5,
+    MCF_NSTAT = 6
+};
+typedef struct mcf_summary_spec {
+    int32_t nperiods;
+    const int32_t *period_of_day;  /* [tsteps / 24] */
+    int32_t var[MCF_NOUT];         /* != 0: summarised                             */
+    int32_t stat[MCF_NSTAT];       /* != 0: kept                                   */
+    double threshold[MCF_NOUT];    /* HOURS_ABOVE; read for selected variables only */
+} mcf_summary_spec;
+/* Switches the sink on: allocates the state, nvars x nperiods x rows x cells x 8 bytes (rows: the sum's, and one per selected
+ * statistic other than MEAN), MCF_ERR_NOMEM when it does not fit.  MCF_ERR_ARG with a message: reqhgt < 0 or a streamed plan, a
+ * selected variable that was not requested at plan creation, an empty selection of variables or statistics, nperiods < 1, a
+ * table entry outside -1 .. nperiods - 1, a NaN threshold of a selected variable with HOURS_ABOVE selected.  MCF_ERR_STATE when
+ * called twice.  May be enabled on a diagnostics plan (it reads the ten outputs only). */
+int mcf_plan_summary_enable(mcf_plan *plan, const mcf_summary_spec *spec);
+/* Folds days [slot_day0, slot_day0 + ndays) of ring slot `slot` as calendar days [day0, day0 + ndays), on the plan's stream
+ * behind the run that filled them (however it filled them: plain, masked or cell-subset runs).  Days arrive in ascending
+ * order, each at most once: a day at or before one that has been folded is MCF_ERR_STATE, as is a call before the enable. */
+int mcf_plan_summary_accumulate(mcf_plan *plan, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays);
+/* One statistic of one variable as [rows, cols, nperiods], column-major (both selected in the enable: MCF_ERR_ARG otherwise). */
+int mcf_plan_summary_fetch(mcf_plan *plan, int32_t var, int32_t stat, double *host_dst);
+/* days[nperiods]: the counted days folded so far into each period */
+int mcf_plan_summary_days(mcf_plan *plan, int32_t *days);
+/* Back to the state of the enable: nothing folded, any day may come next. */
+int mcf_plan_summary_reset(mcf_plan *plan);
+/* One call, host to host: the solver in day chunks through a ring of `chunk_days` days (0: sized from a byte budget of 14 GB,
+ * MCF_SUMMARY_RING_GB overrides), each chunk folded as it is produced — vector forcing, array forcing (each chunk's forcing
+ * uploaded before its run) and coarse array forcing, with or without dfsel, as `in` says.  The plan is created with
+ * out = spec->var (`opt->out` is ignored); opt->reqhgt >= 0.  val[v][s]: caller-allocated [rows, cols, nperiods] for every
+ * selected pair (a null one is MCF_ERR_ARG); days: [nperiods] or NULL. */
+typedef struct mcf_summary_out {
+    double *val[MCF_NOUT][MCF_NSTAT];
+    int32_t *days;
+} mcf_summary_out;
+int mcf_runmicro_summary(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_summary_spec *spec, int32_t chunk_days,
+                         mcf_summary_out *out);
+/* The same over row blocks on several devices from one process (vector forcing; mcf_multi as for mcf_runmicro1_multi: the
+ * whole-raster twi mean installed in every block, inputs read and results written in place through the row pitch): bit for
+ * bit the single-device arrays. */
+int mcf_runmicro_summary_multi(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_summary_spec *spec, int32_t chunk_days,
+                               const mcf_multi *multi, mcf_summary_out *out);
 
 /* ---- terrain pre-compute (the solver's terrain inputs, built on the device) ------
  * Restates the R-side arithmetic of the reference's marshaller (R/internal.R):

@@ -120,6 +120,22 @@ class Outputs(C.Structure):
     _fields_ = [("var", c_double_p * NOUT)]
 
 
+NSTAT = 6
+# include/mcf.h mcf_stat: the statistics of a period summary, in the enum's order
+STAT_NAMES = ("mean", "min", "max", "mean_daily_max", "mean_daily_min", "hours_above")
+
+
+class SummarySpec(C.Structure):
+    """include/mcf.h mcf_summary_spec"""
+    _fields_ = [("nperiods", C.c_int32), ("period_of_day", c_int32_p), ("var", C.c_int32 * NOUT), ("stat", C.c_int32 * NSTAT),
+                ("threshold", C.c_double * NOUT)]
+
+
+class SummaryOut(C.Structure):
+    """include/mcf.h mcf_summary_out"""
+    _fields_ = [("val", (c_double_p * NSTAT) * NOUT), ("days", c_int32_p)]
+
+
 class DiagOutputs(C.Structure):
     """include/mcf.h mcf_diag_outputs"""
     _fields_ = [("var", c_double_p * NDIAG)]
@@ -277,6 +293,8 @@ EXPORTS = (
     "mcf_leafrfromalb", "mcf_leafrfromalb_device", "mcf_selftest_vegprep",
     "mcf_plan_diag_enable", "mcf_plan_diag_fetch", "mcf_plan_diag_slot_ptr", "mcf_plan_diag_ring_layout",
     "mcf_runmicro1_diag", "mcf_runmicro3_diag",
+    "mcf_plan_summary_enable", "mcf_plan_summary_accumulate", "mcf_plan_summary_fetch", "mcf_plan_summary_days",
+    "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -444,6 +462,22 @@ def load() -> C.CDLL:
         for fn in (lib.mcf_runmicro1_diag, lib.mcf_runmicro3_diag):
             fn.restype = C.c_int
             fn.argtypes = [GI, OP, DSEL, OU, C.POINTER(DiagOutputs)]
+    if hasattr(lib, "mcf_plan_summary_enable"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        SS, SO_ = C.POINTER(SummarySpec), C.POINTER(SummaryOut)
+        lib.mcf_plan_summary_enable.restype = C.c_int
+        lib.mcf_plan_summary_enable.argtypes = [P, SS]
+        lib.mcf_plan_summary_accumulate.restype = C.c_int
+        lib.mcf_plan_summary_accumulate.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        lib.mcf_plan_summary_fetch.restype = C.c_int
+        lib.mcf_plan_summary_fetch.argtypes = [P, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_plan_summary_days.restype = C.c_int
+        lib.mcf_plan_summary_days.argtypes = [P, c_int32_p]
+        lib.mcf_plan_summary_reset.restype = C.c_int
+        lib.mcf_plan_summary_reset.argtypes = [P]
+        lib.mcf_runmicro_summary.restype = C.c_int
+        lib.mcf_runmicro_summary.argtypes = [GI, OP, SS, C.c_int32, SO_]
+        lib.mcf_runmicro_summary_multi.restype = C.c_int
+        lib.mcf_runmicro_summary_multi.argtypes = [GI, OP, SS, C.c_int32, C.POINTER(Multi), SO_]
     lib.mcf_plan_fetch.restype = C.c_int
     lib.mcf_plan_fetch.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p]
     lib.mcf_plan_fetch_cells.restype = C.c_int

@@ -56,6 +56,91 @@ def diag_selection(names):
     return sel, [_abi.DIAG_NAMES[v] for v in idx]
 
 
+def summary_spec(periods, vars, stats, thresholds=None):
+    """include/mcf.h mcf_summary_spec from `periods` (one integer per day, -1 = not counted), output names or indices, names
+    of _abi.STAT_NAMES or indices, and `thresholds` for hours_above: one number for every selected variable or {variable:
+    number}.  -> (spec, the selected variables' indices, the selected statistics' indices, the array its table points into)"""
+    pod = np.ascontiguousarray(np.asarray(periods).astype(np.int32)).ravel()
+    vi = sorted({_abi.OUT_NAMES.index(v) if isinstance(v, str) else int(v) for v in ((vars,) if isinstance(vars, str) else vars)})
+    si = sorted({_abi.STAT_NAMES.index(s) if isinstance(s, str) else int(s) for s in ((stats,) if isinstance(stats, str) else stats)})
+    if any(v < 0 or v >= _abi.NOUT for v in vi) or any(s < 0 or s >= _abi.NSTAT for s in si):
+        raise ValueError(f"summary: variables of {_abi.OUT_NAMES}, statistics of {_abi.STAT_NAMES}")
+    sp = _abi.SummarySpec()
+    sp.nperiods = int(pod.max()) + 1 if pod.size and pod.max() >= 0 else 1
+    sp.period_of_day = pod.ctypes.data_as(_abi.c_int32_p)
+    for v in vi:
+        sp.var[v] = 1
+        if isinstance(thresholds, Mapping):
+            t = thresholds.get(_abi.OUT_NAMES[v], thresholds.get(v, float("nan")))
+        else:
+            t = float("nan") if thresholds is None else thresholds
+        sp.threshold[v] = float(t)
+    for s in si:
+        sp.stat[s] = 1
+    return sp, vi, si, pod
+
+
+def _summary_result(vi, si, arrays, days):
+    res = {_abi.OUT_NAMES[v]: {_abi.STAT_NAMES[s]: arrays[v, s] for s in si} for v in vi}
+    res["days"] = days
+    return res
+
+
+def runmicro_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, reqhgt: float,
+                     zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, periods,
+                     vars=("Tz",), stats=("mean", "min", "max"), thresholds=None, nperiods: int | None = None,
+                     chunk_days: int = 0, array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None,
+                     device: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
+    """Per-cell statistics of the solver's outputs over periods of days, accumulated on the device chunk by chunk (include/mcf.h
+    "period summaries", mcf_runmicro_summary): the argument lists of runmicro1Cpp .. 4Cpp (`array_forcing`, `dfsel`, and
+    `coarse` as for runmicro2Cpp_coarse's marshalling) without `out` — the selection `vars` is what the solver computes.
+    `periods`: one integer per whole day (-1: not counted); `nperiods` (default: the largest + 1) allows trailing periods
+    without a day.  `devices` / `n_blocks`: row blocks over several devices (vector forcing), same bits.  `dtm`: missing
+    terrain planes derived on the device — that route runs the plan API from here (Plan(dtm=...)), one device.
+    -> {variable: {statistic: [rows, cols, nperiods]}, "days": counted days per period}"""
+    sp, vi, si, _pod = summary_spec(periods, vars, stats, thresholds)
+    if nperiods is not None:
+        sp.nperiods = int(nperiods)
+    out = [1 if v in vi else 0 for v in range(_abi.NOUT)]
+    af = bool(array_forcing) or coarse is not None
+    if dtm is not None:
+        if devices is not None or n_blocks:
+            raise ValueError("dtm= is not available with devices= / n_blocks=")
+        T = len(np.asarray(obstime["year"]))
+        nd = T // 24
+        ring = max(1, min(nd, int(chunk_days) if chunk_days else 8))
+        with Plan(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out,
+                  array_forcing=af, ring_days=ring, device=device, cells_per_block=cells_per_block, dfsel=dfsel, coarse=coarse,
+                  dtm=dtm) as p:
+            p.summary_enable(_pod, vi, si, thresholds, nperiods=sp.nperiods)
+            for d0 in range(0, nd, ring):
+                n = min(ring, nd - d0)
+                if af:
+                    p.upload_forcing_days(d0, n, 0)
+                p.run_days(d0, n, 0)
+                p.summary_accumulate(0, 0, d0, n)
+            arrays = {(v, s): p.fetch_summary(v, s) for v in vi for s in si}
+            return _summary_result(vi, si, arrays, p.summary_days())
+    lib = _abi.load()
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out, af,
+                device, 0, cells_per_block, dfsel, coarse)
+    so = _abi.SummaryOut()
+    arrays = {}
+    for v in vi:
+        for s in si:
+            arrays[v, s] = np.empty((m.rows, m.cols, max(int(sp.nperiods), 0)), dtype=np.float64, order="F")
+            so.val[v][s] = arrays[v, s].ctypes.data_as(_abi.c_double_p)
+    days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
+    so.days = days.ctypes.data_as(_abi.c_int32_p)
+    mu = _abi.multi(devices, n_blocks)
+    if mu:
+        _abi.check(lib.mcf_runmicro_summary_multi(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(mu[0]),
+                                                  C.byref(so)))
+    else:
+        _abi.check(lib.mcf_runmicro_summary(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(so)))
+    return _summary_result(vi, si, arrays, days[:max(int(sp.nperiods), 0)])
+
+
 def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
          Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel=None, coarse=None,
          devices=None, n_blocks=0, dtm=None, diag=None):
@@ -370,6 +455,42 @@ class Plan:
         q = C.c_void_p()
         _abi.check(self._lib.mcf_plan_diag_slot_ptr(self._p, slot, v, C.byref(q)))
         return int(q.value or 0)
+
+    def summary_enable(self, periods, vars=("Tz",), stats=("mean", "min", "max"), thresholds=None, *, nperiods=None):
+        """Period summaries of the plan's outputs, accumulated on the device (include/mcf.h mcf_plan_summary_enable):
+        `periods` one integer per day of the plan (-1: not counted), `vars` among the plan's outputs, `stats` of
+        _abi.STAT_NAMES, `thresholds` for hours_above (a number or {variable: number}).  -> (variables, statistics) selected"""
+        sp, vi, si, _pod = summary_spec(periods, vars, stats, thresholds)
+        if nperiods is not None:
+            sp.nperiods = int(nperiods)
+        if _pod.size != self.ndays:
+            raise ValueError(f"periods: one entry per day of the plan ({self.ndays}), got {_pod.size}")
+        _abi.check(self._lib.mcf_plan_summary_enable(self._p, C.byref(sp)))
+        self._summary_nperiods = int(sp.nperiods)
+        return [_abi.OUT_NAMES[v] for v in vi], [_abi.STAT_NAMES[s] for s in si]
+
+    def summary_accumulate(self, slot: int, slot_day0: int, day0: int, ndays: int):
+        """Fold days [slot_day0, slot_day0 + ndays) of the slot as calendar days [day0, day0 + ndays), behind the run that
+        filled them; days in ascending order, each at most once (include/mcf.h mcf_plan_summary_accumulate)."""
+        _abi.check(self._lib.mcf_plan_summary_accumulate(self._p, slot, slot_day0, day0, ndays))
+
+    def fetch_summary(self, var, stat) -> np.ndarray:
+        """[rows, cols, nperiods] of one selected statistic of one selected variable (names or indices)"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        s = _abi.STAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
+        a = np.empty((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)), dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_summary_fetch(self._p, v, s, a.ctypes.data_as(_abi.c_double_p)))
+        return a
+
+    def summary_days(self) -> np.ndarray:
+        """counted days folded so far into each period"""
+        d = np.zeros(getattr(self, "_summary_nperiods", 1), dtype=np.int32)
+        _abi.check(self._lib.mcf_plan_summary_days(self._p, d.ctypes.data_as(_abi.c_int32_p)))
+        return d
+
+    def summary_reset(self):
+        """Back to the state of summary_enable: nothing folded."""
+        _abi.check(self._lib.mcf_plan_summary_reset(self._p))
 
     def fetch(self, slot: int, var, step0: int, nsteps: int) -> np.ndarray:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)

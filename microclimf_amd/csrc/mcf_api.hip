@@ -128,6 +128,17 @@ struct mcf_plan {
     int ndiag = 0;
     int64_t dg_tile_stride = 0, dg_day_stride = 0, dg_slot_elems = 0;
     bool has_run = false;           // a solver launch has been described (mcf_plan_diag_enable comes before)
+    // period summaries (mcf_plan_summary_enable; null state: off): the state [selected var][period][state row][N]
+    // (mcf_kernels.h SummaryAccArgs), the day tables on the device, one statistic plane on its way to the host
+    double *d_sum_state = nullptr, *d_sum_plane = nullptr;
+    int32_t *d_sum_pod = nullptr, *d_sum_prev = nullptr, *d_sum_next = nullptr, *d_sum_days = nullptr;
+    int sum_nperiods = 0, sum_nrows = 0, sum_nsel = 0;
+    int sum_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
+    int sum_row[MCF_NSTAT] = {};    // state row of a statistic, -1: not selected
+    double sum_thr[MCF_NOUT] = {};
+    uint32_t sum_init_codes = 0;
+    std::vector<int32_t> sum_pod, sum_days;
+    int sum_next_day = 0;           // the first day that may still be folded
     // reqhgt < 0
     double *d_tgser = nullptr, *d_ddsum = nullptr, *d_scratch = nullptr;
     const double *d_Tgp = nullptr, *d_Tbp = nullptr;
@@ -2147,6 +2158,224 @@ int mcf_runbioclim2(const mcf_grid_inputs* in, const mcf_options* opt, const mcf
     return run_bioclim(in, opt, sel, out, 1);
 }
 
+// ---- period summaries (include/mcf.h "period summaries"; kernels: mcf_summary.hip) -----------------------------------------
+// everything of a summary that can be judged without a device; `requested`: the plan's var_slot (null: any variable)
+static int check_summary_spec(const mcf_summary_spec* s, int64_t ndays, const int* requested) {
+    if (!s) return fail(MCF_ERR_ARG, "null mcf_summary_spec");
+    if (s->nperiods < 1) return fail(MCF_ERR_ARG, "summary: nperiods must be at least 1");
+    if (ndays > 0 && !s->period_of_day) return fail(MCF_ERR_ARG, "summary: null period_of_day");
+    for (int64_t d = 0; d < ndays; ++d)
+        if (s->period_of_day[d] < -1 || s->period_of_day[d] >= s->nperiods)
+            return fail(MCF_ERR_ARG, "summary: period_of_day[" + std::to_string(d) + "] = " + std::to_string(s->period_of_day[d]) +
+                                         " is outside -1 .. nperiods - 1");
+    int nv = 0, ns = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nv += s->var[v] ? 1 : 0;
+    for (int k = 0; k < MCF_NSTAT; ++k) ns += s->stat[k] ? 1 : 0;
+    if (nv == 0) return fail(MCF_ERR_ARG, "summary: no variable selected");
+    if (ns == 0) return fail(MCF_ERR_ARG, "summary: no statistic selected");
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!s->var[v]) continue;
+        if (requested && requested[v] < 0) return fail(MCF_ERR_ARG, "summary: a selected variable was not requested in out[] at plan creation");
+        if (s->stat[MCF_STAT_HOURS_ABOVE] && std::isnan(s->threshold[v]))
+            return fail(MCF_ERR_ARG, "summary: HOURS_ABOVE needs a threshold for every selected variable (NaN given)");
+    }
+    return MCF_OK;
+}
+static int check_room(int64_t need, const char* what) {
+    size_t fr = 0, tot = 0;
+    if (hipMemGetInfo(&fr, &tot) != hipSuccess) return MCF_OK;
+    if ((double)need > 0.95 * (double)fr) {
+        char m[200];
+        snprintf(m, sizeof m, "%s needs %.2f GB of device memory, %.2f GB free", what, need / 1e9, fr / 1e9);
+        return fail(MCF_ERR_NOMEM, m);
+    }
+    return MCF_OK;
+}
+
+int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
+    if (!p || !spec) return fail(MCF_ERR_ARG, "null argument");
+    if (p->bg_stream) return fail(MCF_ERR_ARG, "period summaries are not available on a streamed plan");
+    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
+    if (p->d_sum_state) return fail(MCF_ERR_STATE, "period summaries are already enabled on this plan");
+    int rc = check_summary_spec(spec, p->ndays, p->var_slot);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    // state rows: the sum's (it carries the NA rule), then one per selected statistic that needs one
+    int nrows = 1, row[MCF_NSTAT];
+    uint32_t codes = 0;
+    for (int k = 0; k < MCF_NSTAT; ++k) {
+        row[k] = !spec->stat[k] ? -1 : k == MCF_STAT_MEAN ? 0 : nrows++;
+        if (row[k] > 0 && k == MCF_STAT_MIN) codes |= 1u << (4 * row[k]);
+        if (row[k] > 0 && k == MCF_STAT_MAX) codes |= 2u << (4 * row[k]);
+    }
+    int nsel = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nsel += spec->var[v] ? 1 : 0;
+    const int64_t nd = std::max(p->ndays, 1), np = spec->nperiods;
+    const int64_t state_bytes = (int64_t)nsel * np * nrows * p->N * 8, plane_bytes = np * p->N * 8;
+    if ((rc = check_room(state_bytes + plane_bytes + (3 * nd + np) * 4, "the summary state"))) return rc;
+    // the previous / next day of each day's period
+    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)p->ndays), last((size_t)np, -1);
+    for (int d = 0; d < p->ndays; ++d) {
+        const int per = pod[(size_t)d] = spec->period_of_day[d];
+        if (per < 0) continue;
+        prev[(size_t)d] = last[(size_t)per];
+        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
+        last[(size_t)per] = d;
+    }
+    void* q = nullptr;
+    int32_t** tabs[3] = {&p->d_sum_pod, &p->d_sum_prev, &p->d_sum_next};
+    const std::vector<int32_t>* host[3] = {&pod, &prev, &next};
+    for (int i = 0; i < 3; ++i) {
+        if ((rc = dalloc(p, &q, nd * 4))) return rc;
+        HIP_TRY(hipMemcpy(q, host[i]->data(), (size_t)nd * 4, hipMemcpyHostToDevice));
+        *tabs[i] = (int32_t*)q;
+    }
+    if ((rc = dalloc(p, &q, np * 4))) return rc;
+    p->d_sum_days = (int32_t*)q;
+    if ((rc = dalloc(p, &q, plane_bytes))) return rc;
+    p->d_sum_plane = (double*)q;
+    if ((rc = dalloc(p, &q, state_bytes))) return rc;
+    p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_nsel = nsel; p->sum_init_codes = codes;
+    for (int k = 0; k < MCF_NSTAT; ++k) p->sum_row[k] = row[k];
+    int place = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        p->sum_sel1[v] = spec->var[v] ? ++place : 0;
+        p->sum_thr[v] = spec->var[v] && spec->stat[MCF_STAT_HOURS_ABOVE] ? spec->threshold[v] : 0.0;
+    }
+    p->sum_pod = std::move(pod);
+    p->d_sum_state = (double*)q;
+    return mcf_plan_summary_reset(p);
+}
+
+int mcf_plan_summary_reset(mcf_plan* p) {
+    if (!p) return fail(MCF_ERR_ARG, "null plan");
+    if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
+    HIP_TRY(hipSetDevice(p->device));
+    mcf::launch_summary_init(p->d_sum_state, (int64_t)p->sum_nsel * p->sum_nperiods * p->sum_nrows * p->N, p->N, p->sum_nrows,
+                             p->sum_init_codes, p->stream);
+    HIP_TRY(hipGetLastError());
+    p->sum_days.assign((size_t)p->sum_nperiods, 0);
+    p->sum_next_day = 0;
+    return MCF_OK;
+}
+
+int mcf_plan_summary_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays) {
+    if (!p) return fail(MCF_ERR_ARG, "null plan");
+    if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
+    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
+    if (day0 < 0 || ndays < 1 || (int64_t)day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
+    if (slot_day0 < 0 || (int64_t)slot_day0 + ndays > p->ring_days) return fail(MCF_ERR_ARG, "more days than the ring slot holds");
+    if (day0 < p->sum_next_day)
+        return fail(MCF_ERR_STATE, "summary: days arrive in ascending order, each at most once (day " + std::to_string(day0) +
+                                       " after day " + std::to_string(p->sum_next_day - 1) + ")");
+    HIP_TRY(hipSetDevice(p->device));
+    mcf::SummaryAccArgs a{};
+    a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
+    a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
+    a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
+    a.nsel = p->sum_nsel;
+    for (int v = 0; v < MCF_NOUT; ++v)
+        if (p->sum_sel1[v]) {
+            a.slab[p->sum_sel1[v] - 1] = p->var_slot[v];
+            a.threshold[p->sum_sel1[v] - 1] = p->sum_thr[v];
+        }
+    a.nperiods = p->sum_nperiods; a.nrows = p->sum_nrows;
+    for (int k = 0; k < MCF_NSTAT; ++k) a.row[k] = p->sum_row[k];
+    a.period_of_day = p->d_sum_pod; a.prev_same = p->d_sum_prev; a.next_same = p->d_sum_next;
+    a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
+    a.state = p->d_sum_state;
+    mcf::launch_summary_acc(a, p->stream);
+    HIP_TRY(hipGetLastError());
+    for (int d = day0; d < day0 + ndays; ++d)
+        if (p->sum_pod[(size_t)d] >= 0) p->sum_days[(size_t)p->sum_pod[(size_t)d]] += 1;
+    p->sum_next_day = day0 + ndays;
+    return MCF_OK;
+}
+
+// one statistic plane [rows, cols, nperiods] into the caller's array (row_pitch > rows: a row block's rows of taller planes)
+static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch) {
+    if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
+    if (var < 0 || var >= MCF_NOUT || stat < 0 || stat >= MCF_NSTAT) return fail(MCF_ERR_ARG, "bad variable / statistic");
+    if (!p->sum_sel1[var]) return fail(MCF_ERR_ARG, "variable was not selected in mcf_plan_summary_enable");
+    if (p->sum_row[stat] < 0) return fail(MCF_ERR_ARG, "statistic was not selected in mcf_plan_summary_enable");
+    if (row_pitch == 0) row_pitch = p->rows;
+    if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemcpyAsync(p->d_sum_days, p->sum_days.data(), (size_t)p->sum_nperiods * 4, hipMemcpyHostToDevice, p->stream));
+    mcf::SummaryFinArgs f{};
+    f.state = p->d_sum_state + (int64_t)(p->sum_sel1[var] - 1) * p->sum_nperiods * p->sum_nrows * p->N;
+    f.N = p->N; f.nperiods = p->sum_nperiods; f.nrows = p->sum_nrows;
+    f.stat = stat; f.row = p->sum_row[stat];
+    f.days = p->d_sum_days; f.out = p->d_sum_plane;
+    mcf::launch_summary_fin(f, p->stream);
+    HIP_TRY(hipGetLastError());
+    const size_t width = (size_t)p->rows * 8, bytes = (size_t)(p->N * p->sum_nperiods) * 8;
+    if (row_pitch != p->rows) HIP_TRY(p->tohost.pitched(host_dst, (size_t)row_pitch * 8, p->d_sum_plane, width, bytes / width, p->stream));
+    else HIP_TRY(p->tohost.dense(host_dst, p->d_sum_plane, bytes, p->stream));
+    return MCF_OK;
+}
+int mcf_plan_summary_fetch(mcf_plan* p, int32_t var, int32_t stat, double* host_dst) {
+    return summary_fetch_pitched(p, var, stat, host_dst, 0);
+}
+
+int mcf_plan_summary_days(mcf_plan* p, int32_t* days) {
+    if (!p || !days) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
+    for (int k = 0; k < p->sum_nperiods; ++k) days[k] = p->sum_days[(size_t)k];
+    return MCF_OK;
+}
+
+// twi_mean / out_pitch: a row block of a taller raster (mcf_runmicro_summary_multi), as for run_bioclim
+static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_summary_spec* spec, int32_t chunk_days,
+                       mcf_summary_out* out, const double* twi_mean = nullptr, int64_t out_pitch = 0) {
+    if (!spec || !out) return fail(MCF_ERR_ARG, "null summary argument");
+    int rc = check_inputs(in, opt_in);
+    if (rc) return rc;
+    if (opt_in->reqhgt < 0.0) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
+    if (chunk_days < 0) return fail(MCF_ERR_ARG, "summary: negative chunk_days");
+    const int ndays = (int)(in->tsteps / 24);
+    if ((rc = check_summary_spec(spec, ndays, nullptr))) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v)
+        for (int k = 0; k < MCF_NSTAT; ++k)
+            if (spec->var[v] && spec->stat[k] && !out->val[v][k]) return fail(MCF_ERR_ARG, "summary: a selected (variable, statistic) has a null buffer");
+    mcf_options opt = *opt_in;
+    int nsel = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nsel += (opt.out[v] = spec->var[v] ? 1 : 0);
+    if ((rc = ensure_device(opt.device))) return rc;
+    const int64_t N = in->rows * in->cols;
+    int chunk = chunk_days;
+    if (chunk == 0) {
+        // the ring (and, array forcing, its forcing ring) from a byte budget, as run_bioclim sizes its ring
+        const int cpb = opt.cells_per_block ? opt.cells_per_block : 21;
+        const double day_bytes = 8.0 * (nsel + (in->array_forcing == 1 ? 15 : 0)) * (double)((N + cpb - 1) / cpb) * (double)mcf::ring_block_doubles(cpb);
+        const char* e = getenv("MCF_SUMMARY_RING_GB");
+        const double budget = (e && atof(e) > 0.0 ? atof(e) : 14.0) * 1e9;
+        chunk = (int)std::max(1.0, floor(budget / day_bytes));
+    }
+    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
+    mcf_plan* p = nullptr;
+    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
+    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
+    if ((rc = mcf_plan_summary_enable(p, spec))) return rc;
+    for (int d0 = 0; d0 < ndays; d0 += chunk) {
+        const int nd = std::min(chunk, ndays - d0);
+        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
+        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+        if ((rc = mcf_plan_summary_accumulate(p, 0, 0, d0, nd))) return rc;
+    }
+    for (int v = 0; v < MCF_NOUT; ++v)
+        for (int k = 0; k < MCF_NSTAT; ++k)
+            if (spec->var[v] && spec->stat[k] && (rc = summary_fetch_pitched(p, v, k, out->val[v][k], out_pitch))) return rc;
+    if (out->days && (rc = mcf_plan_summary_days(p, out->days))) return rc;
+    return mcf_plan_sync(p);
+}
+int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_summary_spec* spec, int32_t chunk_days,
+                         mcf_summary_out* out) {
+    return run_summary(in, opt, spec, chunk_days, out);
+}
+
 int64_t mcf_plan_valid_cells(const mcf_plan* p) { return p ? p->valid_cells : 0; }
 int64_t mcf_plan_bytes(const mcf_plan* p) { return p ? p->dev.bytes : 0; }
 
@@ -2432,6 +2661,25 @@ int mcf_runbioclim3_multi(const mcf_grid_inputs* in, const mcf_options* opt, con
 }
 int mcf_runbioclim4_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const mcf_multi* mu, mcf_bioclim_out* out) {
     return run_bioclim_multi(in, opt, sel, mu, out, 1, 1);
+}
+
+// period summaries over row blocks: a block's [rows, cols, nperiods] planes go into its rows of the caller's
+int mcf_runmicro_summary_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_summary_spec* spec, int32_t chunk_days,
+                               const mcf_multi* mu, mcf_summary_out* out) {
+    if (!out || !spec || !in || !opt) return fail(MCF_ERR_ARG, "null summary argument");
+    if (in->array_forcing != 0) return fail(MCF_ERR_ARG, "mcf_runmicro_summary_multi takes vector forcing (array_forcing = 0)");
+    if (opt->reqhgt < 0.0) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
+    if (chunk_days < 0) return fail(MCF_ERR_ARG, "summary: negative chunk_days");
+    if (const int rc = check_summary_spec(spec, in->tsteps / 24, nullptr)) return rc;
+    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
+    return for_row_blocks(in, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int) {
+        mcf_summary_out so = *out;
+        for (int v = 0; v < MCF_NOUT; ++v)
+            for (int k = 0; k < MCF_NSTAT; ++k)
+                if (so.val[v][k]) so.val[v][k] += r0;
+        if (r0 != 0) so.days = nullptr;      // (the same for every block: the first one reports them)
+        return run_summary(&sub, &o, spec, chunk_days, &so, twi_mean, pitch);
+    });
 }
 
 int mcf_runmicro1(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {

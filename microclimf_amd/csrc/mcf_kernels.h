@@ -280,6 +280,39 @@ struct BioFinArgs {
 };
 void launch_bioclim_fin(const BioFinArgs& a, hipStream_t s);
 void launch_fill(double* p, int64_t n, double v, hipStream_t s);
+// ---- period summaries (mcf_summary.hip; include/mcf.h "period summaries") ------------------------------------
+// State [selected var][period][state row][N]: row 0 the running sum (R's NA_real_ once a NaN has been met: it carries the NA
+// rule from call to call), then one row per selected statistic that needs one (row[stat], -1: none; row[MCF_STAT_MEAN] = 0).
+struct SummaryAccArgs {
+    const double* ring;          // the slot: block of (tile, day of the slot, slab) at tile * tile_stride + day * day_stride + slab * var_stride
+    int64_t tile_stride, day_stride, var_stride;
+    int64_t N, ntiles;
+    int32_t cpb;                 // 16, 21, 32 or 42
+    int32_t nsel;                // selected variables (the grid's y)
+    int32_t slab[10];            // ring slab of each selected variable
+    double threshold[10];        // HOURS_ABOVE: v > threshold
+    int32_t nperiods, nrows;
+    int32_t row[6];
+    // [days of the plan]: the period of each day (-1: not counted) and the previous / next day of the same period (-1 / the
+    // plan's day count: none) — the days of one period are folded together, in ascending order
+    const int32_t *period_of_day, *prev_same, *next_same;
+    int32_t day0, ndays;         // calendar days of the call ...
+    int32_t slot_day0;           // ... and where the first of them lies in the slot
+    double* state;
+};
+void launch_summary_acc(const SummaryAccArgs& a, hipStream_t s);
+struct SummaryFinArgs {
+    const double* state;         // the variable's [period][state row][N]
+    int64_t N;
+    int32_t nperiods, nrows;
+    int32_t stat, row;           // the statistic and its state row
+    const int32_t* days;         // [nperiods] counted days
+    double* out;                 // [nperiods][N]
+};
+void launch_summary_fin(const SummaryFinArgs& a, hipStream_t s);
+// init_codes: 4 bits per state row — 0: 0.0, 1: +inf, 2: -inf
+void launch_summary_init(double* state, int64_t total, int64_t N, int nrows, uint32_t init_codes, hipStream_t s);
+int summary_tiles_per_group(int cpb);
 // dst[ci + ncells*k] = src(cells[ci], step0 + k), k < nsteps
 void launch_gather_cells(const RingView& src, int64_t step0, int64_t nsteps, const int64_t* cells, int64_t ncells, double* dst,
                          hipStream_t s);

@@ -381,6 +381,85 @@ def runmicro(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
     return api.runmicro3Cpp(dfsel, **a, device=device)
 
 
+# ---- period summaries: monthly (yearly, daily, ...) maps straight from the device ------------------------------------------------
+def summary_periods(obstime: Mapping, by="month"):
+    """The period of every whole day of an hourly `obstime` (taken from the first of the day's 24 rows) for
+    include/mcf.h's period summaries -> (int32 table [days], labels [nperiods]).  `by`: "all" (one period), "year", "month"
+    (year-month, in order of appearance), "monthofyear" (all Januaries together, ...: the months present, ascending), "day",
+    or an explicit array with one integer per day (-1: not counted)."""
+    year, month, day = (np.asarray(obstime[k]).astype(np.int64) for k in ("year", "month", "day"))
+    nd = len(year) // 24
+    y, m, d = year[:nd * 24:24], month[:nd * 24:24], day[:nd * 24:24]
+    if not isinstance(by, str):
+        tab = np.asarray(by).astype(np.int32).ravel()
+        if tab.size != nd:
+            raise ValueError(f"periods: one entry per whole day ({nd}), got {tab.size}")
+        if tab.size and tab.min() < -1:
+            raise ValueError("periods: entries are period indices >= 0, or -1 for a day that is not counted")
+        return tab, list(range(int(tab.max()) + 1 if tab.size and tab.max() >= 0 else 1))
+    if by == "all":
+        return np.zeros(nd, dtype=np.int32), ["all"]
+    if by == "monthofyear":
+        months = sorted(set(m.tolist()))
+        return np.array([months.index(v) for v in m.tolist()], dtype=np.int32), months
+    keys = {"year": lambda i: (int(y[i]),), "month": lambda i: (int(y[i]), int(m[i])),
+            "day": lambda i: (int(y[i]), int(m[i]), int(d[i]))}
+    if by not in keys:
+        raise ValueError('periods: "all", "year", "month", "monthofyear", "day" or one integer per day')
+    seen, tab = {}, np.empty(nd, dtype=np.int32)
+    for i in range(nd):
+        tab[i] = seen.setdefault(keys[by](i), len(seen))
+    fmt = {"year": "{:04d}", "month": "{:04d}-{:02d}", "day": "{:04d}-{:02d}-{:02d}"}[by]
+    return tab, ([k[0] for k in seen] if by == "year" else [fmt.format(*k) for k in seen])
+
+
+def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
+                     vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None, pai_a=None,
+                     tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
+                     from_dtm: bool = False, crows: int | None = None, ccols: int | None = None, lats=None, lons=None,
+                     altcorrect: int = 0, dtmc=None, chunk_days: int = 0, devices=None, n_blocks: int = 0) -> dict:
+    """`runmicro()` reduced over time on the device: per-cell statistics (`stats`, names of api._abi.STAT_NAMES) of the outputs
+    `vars` over `periods` (see summary_periods) instead of the [rows, cols, steps] arrays — what apply(mout$Tz, c(1, 2), mean)
+    and monthly mean / minimum / maximum maps need, without cells x steps values ever leaving the solver's ring.  A micropoint
+    (data.frame weather) or, with `crows`, `ccols`, `lats`, `lons`, the list of micropoints of runpointmodela (array weather,
+    as runmicro_array).  reqhgt == 0 masks the variables as runmicro does; reqhgt < 0 is not available.
+    -> {variable: {statistic: [rows, cols, nperiods]}, "periods": labels, "days": counted days per period}"""
+    if reqhgt < 0:
+        raise ValueError("period summaries need reqhgt >= 0")
+    names = (vars,) if isinstance(vars, str) else tuple(vars)
+    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    if sum(out) != len(set(names)):
+        raise ValueError(f"vars: names of {api._abi.OUT_NAMES}")
+    ter = dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf)
+    array = not isinstance(micropoint, Mapping)
+    if array:
+        if crows is None or ccols is None or lats is None or lons is None:
+            raise ValueError("a list of micropoints (array weather) needs crows, ccols, lats and lons")
+        if from_dtm:
+            raise ValueError("from_dtm is not available with array weather")
+        a = prepare_grid_inputs_array(micropoint, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, pai_a=pai_a, out=out,
+                                      device=device, **ter)
+        R, Cc = a["vegp"]["hgt"].shape[:2]
+        coarse = {"rowpos": api.coarse_positions(R, crows), "colpos": api.coarse_positions(Cc, ccols)}
+        if altcorrect:
+            coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=cleanvars(vegp, soilc, dtm["z"])[2])
+        extra = dict(array_forcing=True, coarse=coarse)
+    else:
+        a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device, from_dtm=from_dtm, **ter)
+        extra = dict(devices=devices, n_blocks=n_blocks)
+        if from_dtm:
+            extra["dtm"] = a.pop("dtm")
+    a["tfact"] = float(tfact)
+    kept = [n for n, o in zip(api._abi.OUT_NAMES, a.pop("out")) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
+    if not kept:
+        raise ValueError("none of the selected variables exists at this reqhgt")
+    tab, labels = summary_periods(a["obstime"], periods)
+    res = api.runmicro_summary(**a, periods=tab, nperiods=len(labels), vars=kept, stats=stats, thresholds=thresholds,
+                               chunk_days=chunk_days, device=device, **extra)
+    res["periods"] = labels
+    return res
+
+
 # ---- the staged workflow: modelin -> soilmdistribute -> twostream -> wind -> soiltemp -> aboveground / belowground ------------
 # The reference's R-mode stages (R/Rimplementation.R:70-342) let a user look inside a run.  Here every stage reads the
 # COMPILED path's own intermediates — the solver's diagnostics ring (include/mcf.h mcf_diag): the values that produce the ten
