@@ -55,7 +55,7 @@ def canintfrac(hgt, pai, uf, prec, tc, Li):
 
 
 def meltmu(skyview, stemp, tc):
-    """cpp:5454-5492"""
+    """cpp:5454-5492; every cell sums its hours in the source's order (the loop is over the hours, all cells abreast)"""
     skyview = np.asarray(skyview, dtype=np.float64)
     stemp = np.asarray(stemp, dtype=np.float64)
     tc = np.asarray(tc, dtype=np.float64)
@@ -65,16 +65,12 @@ def meltmu(skyview, stemp, tc):
             dhp += v
     mu = np.ones(skyview.shape)
     if dhp > 0.0:
-        for idx in np.ndindex(skyview.shape):
-            if np.isnan(skyview[idx]):
-                mu[idx] = np.nan
-                continue
-            dhm = 0.0
+        dhm = np.zeros(skyview.shape)
+        with np.errstate(invalid="ignore"):
             for k in range(stemp.size):
-                s2 = (stemp[k] - tc[k]) * skyview[idx] + tc[k]
-                if s2 > 0.0:
-                    dhm += s2
-            mu[idx] = dhm / dhp
+                s2 = (stemp[k] - tc[k]) * skyview + tc[k]
+                dhm = np.where(s2 > 0.0, dhm + s2, dhm)
+        mu = np.where(np.isnan(skyview), np.nan, dhm / dhp)
     return mu
 
 
@@ -82,18 +78,30 @@ def _colon(a, b):
     return (np.arange(a, b + 1) if a <= b else np.arange(a, b - 1, -1)) - 1
 
 
-def snowmodelq1_days(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact=0.02):
+def _terrain(dtm, res, zref, terrain):
+    """R/internal.R:2690-2706 for `other`; `terrain`: slope, aspect, hor, skyview, wsa to use instead (tests/snowfast_cases.py)"""
+    nanmask = np.isnan(dtm)
+    if terrain is None:
+        slope, aspect = TO.slope_aspect(dtm, res, aspect_na=180.0)
+        hor = TO.horizons24(dtm, res)
+        skyview, wsa = TO.skyview(hor), TO.windsheltera(dtm, zref, 10 if res <= 100 else 1, res)
+    else:
+        slope, aspect, hor, skyview, wsa = (np.asarray(terrain[k], dtype=np.float64) for k in ("slope", "aspect", "hor", "skyview", "wsa"))
+        R, Cc = dtm.shape
+        assert slope.shape == aspect.shape == skyview.shape == (R, Cc) and hor.shape == (R, Cc, 24) and wsa.shape == (R, Cc, 8)
+    return dict(slope=np.where(nanmask, np.nan, slope), aspect=np.where(nanmask, np.nan, aspect), hor=hor, skyview=skyview, wsa=wsa)
+
+
+def snowmodelq1_days(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact=0.02, *,
+                     lib=None, terrain=None):
+    """`lib`: the oracle build that runs gridmodelsnow1 (oracle.load_variant; None: the default); `terrain`: see _terrain"""
     dtm = np.asarray(dtm, dtype=np.float64)
     R, Cc = dtm.shape
     subs = np.asarray(subs, dtype=np.int64)
     n = subs.size
     zref = float(other["zref"])
-    nanmask = np.isnan(dtm)
-    slope, aspect = TO.slope_aspect(dtm, res, aspect_na=180.0)
-    hor = TO.horizons24(dtm, res)
     oth = dict(other)
-    oth.update(slope=np.where(nanmask, np.nan, slope), aspect=np.where(nanmask, np.nan, aspect), hor=hor, skyview=TO.skyview(hor),
-               wsa=TO.windsheltera(dtm, zref, 10 if res <= 100 else 1, res))
+    oth.update(_terrain(dtm, res, zref, terrain))
     snow_all = np.asarray(snow_all, dtype=np.float64)
     temp_all = np.asarray(temp_all, dtype=np.float64)
     pos = snow_all[snow_all > 0]
@@ -127,7 +135,7 @@ def snowmodelq1_days(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, 
             oth["isnowdc"], oth["isnowdg"] = isnowdc, isnowdg
             smod = O.run_snowmodel({k: np.asarray(v)[s] for k, v in obstime.items()},
                                    {k: np.asarray(v)[s] for k, v in climdata.items()},
-                                   {k: np.asarray(v)[s] for k, v in pointm.items()}, vegp, oth, snowenv)
+                                   {k: np.asarray(v)[s] for k, v in pointm.items()}, vegp, oth, snowenv, lib=lib)
             dsnow = smod["sdepc"] - isnowdc[:, :, None]
             dsnowg = smod["sdepg"] - isnowdg[:, :, None]
             dsnowc = dsnow - dsnowg
@@ -151,29 +159,24 @@ def snowmodelq1_days(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, 
 
 
 def meltmu2(mu, stemp, tc):
-    """cpp:5495-5527"""
+    """cpp:5495-5527 (hours in the source's order, all cells abreast: see meltmu)"""
     mu = np.asarray(mu, dtype=np.float64)
     stemp = np.asarray(stemp, dtype=np.float64)
     tc = np.asarray(tc, dtype=np.float64)
-    out = np.empty(mu.shape)
-    for i, j in np.ndindex(mu.shape):
-        if np.isnan(mu[i, j]):
-            out[i, j] = np.nan
-            continue
-        dhp = dhm = 0.0
+    dhp, dhm = np.zeros(mu.shape), np.zeros(mu.shape)
+    with np.errstate(invalid="ignore", divide="ignore"):
         for k in range(stemp.shape[2]):
-            if stemp[i, j, k] > 0.0:
-                dhp += stemp[i, j, k]
-            s2 = (stemp[i, j, k] - tc[i, j, k]) * mu[i, j] + tc[i, j, k]
-            if s2 > 0.0:
-                dhm += s2
-        out[i, j] = dhm / dhp if dhp > 0.0 else 0.5
-    return out
+            st, ta = stemp[:, :, k], tc[:, :, k]
+            dhp = np.where(st > 0.0, dhp + st, dhp)
+            s2 = (st - ta) * mu + ta
+            dhm = np.where(s2 > 0.0, dhm + s2, dhm)
+        out = np.where(dhp > 0.0, dhm / dhp, 0.5)
+    return np.where(np.isnan(mu), np.nan, out)
 
 
 def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos,
-                     altcorrect=0):
-    """`.snowmodelq2`, R/internal.R:3108-3283 (arguments as microclimf_amd.snow.snowmodelq2_days)"""
+                     altcorrect=0, *, lib=None, terrain=None):
+    """`.snowmodelq2`, R/internal.R:3108-3283 (arguments as microclimf_amd.snow.snowmodelq2_days; `lib`, `terrain` as for q1)"""
     from . import coarse_oracle as CO
     dtm = np.asarray(dtm, dtype=np.float64)
     R, Cc = dtm.shape
@@ -213,11 +216,8 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
     sstemp_f, tc_f = cca(pm2_c["sstemp"]), cca(pm2_c["tc"])
     vg = dict(vegp)
     vg["leaft"] = np.where(np.isnan(vg["leaft"]), 0.01, vg["leaft"])
-    slope, aspect = TO.slope_aspect(dtm, res, aspect_na=180.0)
-    hor = TO.horizons24(dtm, res)
     oth = dict(other)
-    oth.update(slope=np.where(nanmask, np.nan, slope), aspect=np.where(nanmask, np.nan, aspect), hor=hor, skyview=TO.skyview(hor),
-               wsa=TO.windsheltera(dtm, zref, 10 if res <= 100 else 1, res))
+    oth.update(_terrain(dtm, res, zref, terrain))
     snow_c = np.asarray(pm2_c["snow"], dtype=np.float64)
     pos = snow_c[snow_c > 0]
     msnow = pos.mean() if pos.size else np.nan
@@ -252,7 +252,7 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
             oth["isnowdc"], oth["isnowdg"] = isnowdc, isnowdg
             c1 = {k: (np.asarray(v)[s] if k == "winddir" else np.asfortranarray(v[:, :, s])) for k, v in clim.items()}
             p1 = {k: np.asfortranarray(v[:, :, s]) for k, v in pointm.items()}
-            smod = O.run_snowmodel({k: np.asarray(v)[s] for k, v in obstime.items()}, c1, p1, vg, oth, snowenv, array_forcing=True)
+            smod = O.run_snowmodel({k: np.asarray(v)[s] for k, v in obstime.items()}, c1, p1, vg, oth, snowenv, array_forcing=True, lib=lib)
             dsnow = smod["sdepc"] - isnowdc[:, :, None]
             dsnowg = smod["sdepg"] - isnowdg[:, :, None]
             dsnowc = dsnow - dsnowg

@@ -139,7 +139,8 @@ def slips_for(O, run, want):
 def case_sets(O, sets=("cases", "random", "snowmodel", "microsnow")):
     """The workloads whose bars are certified on the CPU (tests/test_parity_bars_cpu.py) and recorded
     (tools/parity_margins.py): yields (set, label, run, inputs) with run(lib) -> {variable: array}; `inputs` is what the
-    device entry needs to solve the same thing."""
+    device entry needs to solve the same thing.  `snowfast1` / `snowfast2` (the oracle chains of tests/snowfast_cases.py, on
+    terrain_oracle's terrain; certified by tests/test_snowfast_bars_cpu.py) are not in the default tuple."""
     from microclimf_amd import synthetic
     import parity_cases as PC
     import snow_cases as SC
@@ -170,3 +171,9 @@ def case_sets(O, sets=("cases", "random", "snowmodel", "microsnow")):
                     yield ("microsnow", f"{name}@{h:g}",
                            (lambda lib, args=args, af=af: O.run_microsnow(*args, array_forcing=af, lib=lib)),
                            dict(kind="microsnow", args=args, af=af))
+    for kind, n in (("snowfast1", "q1"), ("snowfast2", "q2")):
+        if kind in sets:
+            import snowfast_cases as FC
+            for i in range(len(FC.Q1_CASES if n == "q1" else FC.Q2_CASES)):
+                c = (FC.q1_case if n == "q1" else FC.q2_case)(i)
+                yield (kind, f"case{i}", FC.run(O, c), dict(kind=kind, index=i, case=c))

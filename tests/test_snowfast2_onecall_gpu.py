@@ -2,16 +2,17 @@
 the gap kernel alone against the host entry and the oracle, the call against the oracle's restatement of `.snowmodelq2`'s day
 loop and against the host day loop it replaces, `umu` against the host's resampling bit for bit, and what the call returns
 when asked for less, asked twice, or asked after a refusal."""
-import functools
-
 import numpy as np
 import pytest
 
-from bundled import load
 from microclimf_amd import _abi, api
 from microclimf_amd import frontend as F
 from microclimf_amd import snow as S
+from microclimf_amd import terrain
 from microclimf_amd.rformulas import upsample_coarse
+import parity_bars
+import snowfast_cases as FC
+from snowfast_cases import Q2_CASES as CASES, q2_case as _case
 
 pytestmark = pytest.mark.gpu
 
@@ -49,110 +50,6 @@ def test_meltmu2_from_coarse_series_on_the_device(n):
 
 
 # ---- the call against the oracle chain ------------------------------------------------------------------------------
-CASES = [
-    dict(days=[2, 3, 49], window=(0, 23, 0, 37), grid=(2, 3), altcorrect=0),       # gaps of 24 h, of 2 h counting down, of 1 080 h
-    dict(days=[4, 6, 7, 12], window=(0, 50, 0, 50), grid=(2, 3), altcorrect=2),
-    dict(days=[10, 40], window=(12, 13, 0, 50), grid=(1, 2), altcorrect=1, snowenv="Prairie", cold=-14.0),   # one row: `.tpicalc`'s raster mean
-    dict(days=[3, 20, 44], window=(5, 28, 10, 47), grid=(3, 1), altcorrect=2, snowenv="Alpine", snowinitd=0.002, snowinita=30.0,
-         stfact=0.03, hole=True),
-    dict(days=[1, 2, 8, 35], window=(20, 50, 0, 19), grid=(2, 3), altcorrect=0, snowenv="Tundra", zref=3.0, windhgt=2.0),   # the series' first day
-    dict(days=[5, 20], window=(10, 30, 5, 30), grid=(1, 2), altcorrect=0, cold=5.0, bare=True),          # no snowfall at all: msnow is NaN
-    dict(days=[5, 6, 20], window=(10, 30, 5, 30), grid=(2, 3), altcorrect=1, cold=-30.0),                # every gap frozen: mu = 0.5
-]
-
-
-def _crop(vegp, soilc, dtm, r0, r1, c0, c1):
-    cut = lambda a: np.array(np.asarray(a)[r0:r1, c0:c1])                # noqa: E731
-    return {k: cut(v) for k, v in vegp.items()}, {k: cut(v) for k, v in soilc.items()}, dict(dtm, z=cut(dtm["z"]))
-
-
-@functools.lru_cache(maxsize=None)
-def _case(i):
-    """the product's inputs of CASES[i], the day loop's arguments as the oracle chain forms them (built as the `fast` case of
-    tests/test_snowfast_gpu.py::test_array_weather_snow_model_matches_the_oracle_chain builds `want`), and the oracle's result"""
-    from oracle import oracle as O
-    from oracle import replay_reference_tests as RT
-    from oracle import snowfast_oracle as SF
-    O.load()
-    case = CASES[i]
-    weather, vegp, soilc, dtm = load(50 * 24)
-    vegp, soilc, dtm = _crop(vegp, soilc, dtm, *case["window"])
-    if case.get("hole"):
-        dtm["z"][5:8, 6:9] = np.nan
-    (cr, cc), T = case["grid"], 50 * 24
-    z = np.asarray(dtm["z"])
-    R, Cc = z.shape
-    rng = np.random.default_rng(9 + i)
-    climarray = {}
-    for k in F.WEATHER:
-        base = np.broadcast_to(weather[k][None, None, :], (cr, cc, T)).copy()
-        if k == "temp":
-            base += case.get("cold", -9.0) + rng.uniform(-1.5, 1.5, (cr, cc, 1))
-        elif k in ("swdown", "difrad", "windspeed", "precip"):
-            base *= rng.uniform(0.9, 1.1, (cr, cc, 1))
-        elif k == "winddir":
-            base = (base + rng.integers(-1, 2, (cr, cc, T)) * 10.0) % 360
-        climarray[k] = np.asfortranarray(base)
-    climarray["difrad"] = np.minimum(climarray["difrad"], climarray["swdown"])
-    clat = dtm["lat"] + 1e-4 * np.arange(cr)[:, None] + 0 * np.arange(cc)[None, :]
-    clon = dtm["long"] + 1e-4 * np.arange(cc)[None, :] + 0 * np.arange(cr)[:, None]
-    lats = dtm["lat"] + 9e-6 * np.arange(R)[::-1, None] + 0 * np.arange(Cc)[None, :]
-    lons = dtm["long"] + 1.4e-5 * np.arange(Cc)[None, :] + 0 * np.arange(R)[:, None]
-    dtmc = np.nanmean(z) + 40.0 + 5.0 * np.arange(cr * cc).reshape(cr, cc)
-    env, sd0, sa0 = case.get("snowenv", "Taiga"), case.get("snowinitd", 0.0), case.get("snowinita", 0.0)
-    zref, windhgt, stfact = case.get("zref", 2.0), case.get("windhgt", case.get("zref", 2.0)), case.get("stfact", 0.01)
-    days = np.asarray(case["days"])
-    subs = (np.repeat((days - 1) * 24, 24) + np.tile(np.arange(24), days.size) + 1).astype(np.int64)
-    mpa = [{"subs": subs, "ntme": T, "zref": zref}] * (cr * cc)         # what runsnowmodela reads of subsetpointmodel's output
-    kw = dict(dtmc=dtmc, lats_c=clat, lons_c=clon, lats=lats, lons=lons, altcorrect=case["altcorrect"], snowenv=env, snowinitd=sd0,
-              snowinita=sa0, zref=zref, windhgt=windhgt, stfact=stfact)
-    # the same through the oracle
-    vg = F.cleanvegp(vegp)
-    assert np.nanmax(vg["hgt"]) <= zref
-    obst = {k: np.asarray(v) for k, v in weather["obstime"].items()}
-    wdir = np.array([F.getmode(climarray["winddir"][:, :, k]) for k in range(T)])
-    vc = {k: F.block_reduce(vg[k], cr, cc) for k in ("pai", "hgt", "leaft", "clump")}
-    clim_c = {k: np.array(climarray[k], copy=True) for k in F.WEATHER if k != "winddir"}
-    if zref != windhgt:
-        clim_c["windspeed"] *= np.log(67.8 * zref - 5.42) / np.log(67.8 * windhgt - 5.42)
-    clim_c["winddir"] = wdir
-    names = {"Gp": "G", "Tc": "Tc", "RswabsG": "RswabsG", "RlwabsG": "RlwabsG", "umu": "umu", "tr": "tr", "sdepc": "sdepc"}
-    names.update({k: k for k in ("sublmelt", "tempmelt", "rainmelt", "sstemp", "sdenc", "sdeng")})
-    pointm_c = {k: np.empty((cr, cc, T)) for k in names}
-    for a in range(cr):
-        for b in range(cc):
-            w = {k: np.ascontiguousarray(clim_c[k][a, b, :]) for k in clim_c if k != "winddir"}
-            pm = RT.pointmodelsnow(obst, w, np.array([np.mean(vc[k][a, b, :]) for k in ("pai", "hgt", "leaft", "clump")]),
-                                   np.array([0, 0, clat[a, b], clon[a, b], zref, sd0, sa0]), env, maxiter=10)
-            for k, v in names.items():
-                pointm_c[k][a, b, :] = pm[v][1:T + 1] if k == "sdepc" else pm[v][:T]
-    other = {"zref": zref, "lats": lats, "lons": lons, "isnowdc": z * 0 + sd0, "isnowac": z * 0 + sa0, "isnowag": z * 0 + sa0}
-    ai = subs - 1
-    sel = lambda d: {k: (np.asarray(v)[ai] if np.ndim(v) == 1 else np.asfortranarray(np.asarray(v)[:, :, ai])) for k, v in d.items()}   # noqa: E731
-    pm2 = {k: pointm_c[k] for k in ("sublmelt", "tempmelt", "rainmelt", "sstemp", "sdenc", "sdeng")}
-    pm2["tc"] = clim_c["temp"]
-    pm2["snow"] = np.where(clim_c["temp"] > 2, 0.0, clim_c["precip"])
-    pm_s = sel({k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu", "tr", "sdepc")})
-    rowpos, colpos = api.coarse_positions(R, cr), api.coarse_positions(Cc, cc)
-    args = (sel(obst), sel(clim_c), pm_s, pm2, subs, F.sortl(vg, np.max(pm_s["sdepc"], axis=(0, 1))), other, env, z, dtmc, dtm["res"],
-            stfact)
-    pos = dict(rowpos=rowpos, colpos=colpos, altcorrect=case["altcorrect"])
-    want = SF.snowmodelq2_days(*args, rowpos, colpos, altcorrect=case["altcorrect"])
-    for v in want.values():
-        v.flags.writeable = False
-    # the gaps' multipliers on the reference side: does a gap thaw somewhere (mu neither 0.5 nor NA)?
-    hole = np.isnan(z)[:, :, None]
-    cca = lambda a: np.where(hole, np.nan, upsample_coarse(a, rowpos, colpos))               # noqa: E731
-    thaws = False
-    for d in range(days.size):
-        if subs[24 * d] - 1 > 1:
-            sbtn = SF._colon((subs[24 * d - 1] if d else 0) + 1, int(subs[24 * d]) - 1)
-            st = cca(pm2["sstemp"][:, :, sbtn])
-            thaws = thaws or bool(np.any(np.nansum(np.where(st > 0, st, 0.0), axis=2) > 0))
-    return dict(product=(climarray, weather["obstime"], mpa, vegp, soilc, dtm, kw), args=args, pos=pos, want=want, thaws=thaws,
-                umu_c=pm_s["umu"], hole=np.isnan(z))
-
-
 def _worst(got, want):
     """the bar of tests/test_snowfast_gpu.py: identical NaN and inf masks, every finite value within 1e-6 scaled; -> the
     largest scaled difference and where"""
@@ -213,6 +110,35 @@ def test_one_call_matches_the_host_day_loop(oracle, i):
     err, where = _worst(got, ref)
     print(f"case {i}: largest scaled |one call - day loop| = {err:.3e} at {where}")
     assert err < 1e-6, f"largest scaled difference between the one call and the host day loop: {err:.3e} at {where}"
+
+
+# ---- the call and the host day loop against the oracle chain under derived bars ----------------------------------------
+@pytest.mark.parametrize("i", FC.SMALL)
+def test_one_call_and_day_loop_within_the_derived_bars_of_the_oracle_chain(oracle, i):
+    """The 1e-6 of the product-level tests above cannot see a single-precision exp, log or sqrt in the snow day kernels, the
+    gap balance or the redistribution (tests/test_snowfast_bars_cpu.py); the bars of parity_bars.py can.  They are floor-level
+    (2^-40), while 1e-10 on the terrain moves Tg by 4e-9 and no oracle variant models numpy terrain: so the device's own
+    terrain is first held to terrain_oracle (the bound of test_terrain_gpu.py) and then handed to the oracle chain, which
+    takes the terrain out of the snow kernels' account without widening anything.  The host day loop runs the same device
+    kernels on the same terrain and owes the same bars."""
+    c = _case(i)
+    z, res, zref, want_t = FC.oracle_terrain(c)
+    dev_t = terrain.snow_terrain(z, res, zref, device=0)
+    assert list(dev_t) == list(want_t)
+    for k, w in want_t.items():
+        assert dev_t[k].shape == w.shape and np.array_equal(np.isnan(dev_t[k]), np.isnan(w)), k
+        print(f"q2 case {i} terrain {k:8s} largest |device - oracle| {np.nanmax(np.abs(dev_t[k] - w), initial=0.0):.3e}")
+    for k, w in want_t.items():
+        np.testing.assert_allclose(dev_t[k], w, rtol=0, atol=1e-10, err_msg=k)
+    want, bars, noise = parity_bars.bars_for(oracle, FC.run(oracle, c, terrain=dev_t), ("snowfast2-device-terrain", i))
+    assert max(bars.values()) < parity_bars.CAP                         # admissible (snowfast_cases.py)
+    got = {"one call": S.snowmodelq2(*c["args"], **c["pos"]), "day loop": S.snowmodelq2_days(*c["args"], **c["pos"])}
+    for name, g in got.items():
+        assert list(g) == list(want)
+        for k in want:
+            print(f"q2 case {i} {name} {k:15s} distance {parity_bars.distance(g[k], want[k]):.3e}  bar {bars[k]:.3e}  N {noise[k]:.2e}")
+    for name, g in got.items():
+        parity_bars.compare(g, want, bars)
 
 
 # ---- outputs and state ----------------------------------------------------------------------------------------------

@@ -1,15 +1,16 @@
 """The fast snow method as one device-resident call (mcf_snowmodelq1; `runsnowmodel(..., one_call=True)`): its two kernel
 entries against the host entries and the oracle, the call against the oracle's restatement of `.snowmodelq1`'s day loop and
 against the host day loop it replaces, and what it returns when asked for less or asked twice."""
-import functools
-
 import numpy as np
 import pytest
 
-from bundled import load
 from microclimf_amd import _abi
 from microclimf_amd import frontend as F
 from microclimf_amd import snow as S
+from microclimf_amd import terrain
+import parity_bars
+import snowfast_cases as FC
+from snowfast_cases import Q1_CASES as CASES, q1_case as _case
 
 pytestmark = pytest.mark.gpu
 
@@ -60,66 +61,6 @@ def test_meltmu_on_the_device(n):
 
 
 # ---- the call against the oracle chain ------------------------------------------------------------------------------
-CASES = [
-    dict(days=[2, 3, 49], window=(0, 23, 0, 37)),           # gaps of 24 h, of 2 h counting down, of 1 080 h
-    dict(days=[4, 11, 12, 30, 47], window=(0, 50, 0, 50)),
-    dict(days=[10, 40], window=(12, 13, 0, 50), snowenv="Prairie", cold=-14.0),          # one row: `.tpicalc`'s raster mean
-    dict(days=[3, 20, 44], window=(5, 28, 10, 47), snowenv="Alpine", snowinitd=0.002, snowinita=30.0, stfact=0.03, hole=True),
-    dict(days=[6, 7, 8, 35], window=(20, 50, 0, 19), snowenv="Tundra", zref=3.0, windhgt=2.0),
-    dict(days=[5, 20], window=(10, 30, 5, 30), cold=5.0, bare=True),                     # no snowfall at all: msnow is NaN
-    dict(days=[5, 6, 20], window=(10, 30, 5, 30), cold=-30.0),                           # every gap frozen: mu = 1
-]
-
-
-def _crop(vegp, soilc, dtm, r0, r1, c0, c1):
-    cut = lambda a: np.array(np.asarray(a)[r0:r1, c0:c1])                # noqa: E731
-    return {k: cut(v) for k, v in vegp.items()}, {k: cut(v) for k, v in soilc.items()}, dict(dtm, z=cut(dtm["z"]))
-
-
-@functools.lru_cache(maxsize=None)
-def _case(i):
-    """the product's inputs of CASES[i], the day loop's arguments as the oracle chain forms them (built as
-    tests/test_snowfast_gpu.py::test_fast_method_matches_the_oracle_chain builds `want`), and the oracle's result"""
-    from oracle import oracle as O
-    from oracle import replay_reference_tests as RT
-    from oracle import snowfast_oracle as SF
-    O.load()
-    case = CASES[i]
-    weather, vegp, soilc, dtm = load(50 * 24)
-    vegp, soilc, dtm = _crop(vegp, soilc, dtm, *case["window"])
-    if case.get("hole"):
-        dtm["z"][5:8, 6:9] = np.nan
-    weather = dict(weather, temp=weather["temp"] + case.get("cold", -9.0))
-    env, sd0, sa0 = case.get("snowenv", "Taiga"), case.get("snowinitd", 0.0), case.get("snowinita", 0.0)
-    zref, windhgt, stfact = case.get("zref", 2.0), case.get("windhgt", case.get("zref", 2.0)), case.get("stfact", 0.01)
-    mp = F.subsetpointmodel(F.runpointmodel(weather, 0.05, dtm, vegp, soilc), days=case["days"])
-    kw = dict(snowenv=env, snowinitd=sd0, snowinita=sa0, zref=zref, windhgt=windhgt, stfact=stfact)
-    z = np.asarray(dtm["z"])
-    vg = F.cleanvegp(vegp)
-    vp = F.sortvegp_point(vg)
-    obst = {k: np.asarray(v) for k, v in weather["obstime"].items()}
-    w = {k: np.array(weather[k], dtype=np.float64) for k in F.WEATHER}
-    if zref != windhgt:
-        w["windspeed"] = w["windspeed"] * np.log(67.8 * zref - 5.42) / np.log(67.8 * windhgt - 5.42)
-    assert np.nanmax(vg["hgt"]) <= zref
-    sdep, sage = z * 0 + sd0, z * 0 + sa0
-    pm = RT.pointmodelsnow(obst, w, np.array([vp[1], vp[0], vp[5], vp[3]]),
-                           np.array([0, 0, mp["lat"], mp["long"], zref, np.nanmean(sdep), np.nanmean(sage)]), env, maxiter=20)
-    T = len(w["temp"])
-    ai = np.asarray(mp["subs"]) - 1
-    pointm = {"Gp": pm["G"], "Tc": pm["Tc"], "RswabsG": pm["RswabsG"], "RlwabsG": pm["RlwabsG"], "umu": pm["umu"], "tr": pm["tr"]}
-    vs = F.sortl(vg, pm["sdepc"][:T])
-    vs["leaft"] = np.where(np.isnan(vs["leaft"]), 0.01, vs["leaft"])
-    other = {"zref": zref, "lat": mp["lat"], "lon": mp["long"], "isnowdc": sd0 * z, "isnowac": sage, "isnowag": sage}
-    rows = lambda d: {k: np.asarray(v)[ai] for k, v in d.items()}      # noqa: E731
-    args = (rows(obst), rows(w), rows(pointm), pm, w["temp"], np.where(w["temp"] > 2, 0.0, w["precip"]), mp["subs"], vs, other, env, z,
-            dtm["res"], stfact)
-    want = SF.snowmodelq1_days(*args)
-    for v in want.values():
-        v.flags.writeable = False
-    return dict(product=(weather, mp, vegp, soilc, dtm, kw), args=args, want=want, umu=pm["umu"][ai])
-
-
 def _worst(got, want):
     """the bar of tests/test_snowfast_gpu.py: identical NaN and inf masks, every finite value within 1e-6 scaled; -> the
     largest scaled difference and where"""
@@ -165,6 +106,35 @@ def test_one_call_matches_the_host_day_loop(oracle, i):
     err, where = _worst(got, ref)
     print(f"case {i}: largest scaled |one call - day loop| = {err:.3e} at {where}")
     assert err < 1e-6, f"largest scaled difference between the one call and the host day loop: {err:.3e} at {where}"
+
+
+# ---- the call and the host day loop against the oracle chain under derived bars ----------------------------------------
+@pytest.mark.parametrize("i", FC.SMALL)
+def test_one_call_and_day_loop_within_the_derived_bars_of_the_oracle_chain(oracle, i):
+    """The 1e-6 of the product-level tests above cannot see a single-precision exp, log or sqrt in the snow day kernels, the
+    gap balance or the redistribution (tests/test_snowfast_bars_cpu.py); the bars of parity_bars.py can.  They are floor-level
+    (2^-40), while 1e-10 on the terrain moves Tg by 4e-9 and no oracle variant models numpy terrain: so the device's own
+    terrain is first held to terrain_oracle (the bound of test_terrain_gpu.py) and then handed to the oracle chain, which
+    takes the terrain out of the snow kernels' account without widening anything.  The host day loop runs the same device
+    kernels on the same terrain and owes the same bars."""
+    c = _case(i)
+    z, res, zref, want_t = FC.oracle_terrain(c)
+    dev_t = terrain.snow_terrain(z, res, zref, device=0)
+    assert list(dev_t) == list(want_t)
+    for k, w in want_t.items():
+        assert dev_t[k].shape == w.shape and np.array_equal(np.isnan(dev_t[k]), np.isnan(w)), k
+        print(f"q1 case {i} terrain {k:8s} largest |device - oracle| {np.nanmax(np.abs(dev_t[k] - w), initial=0.0):.3e}")
+    for k, w in want_t.items():
+        np.testing.assert_allclose(dev_t[k], w, rtol=0, atol=1e-10, err_msg=k)
+    want, bars, noise = parity_bars.bars_for(oracle, FC.run(oracle, c, terrain=dev_t), ("snowfast1-device-terrain", i))
+    assert max(bars.values()) < parity_bars.CAP                         # admissible (snowfast_cases.py)
+    got = {"one call": S.snowmodelq1(*c["args"]), "day loop": S.snowmodelq1_days(*c["args"])}
+    for name, g in got.items():
+        assert list(g) == list(want)
+        for k in want:
+            print(f"q1 case {i} {name} {k:15s} distance {parity_bars.distance(g[k], want[k]):.3e}  bar {bars[k]:.3e}  N {noise[k]:.2e}")
+    for name, g in got.items():
+        parity_bars.compare(g, want, bars)
 
 
 # ---- outputs and state ----------------------------------------------------------------------------------------------

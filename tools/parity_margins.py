@@ -2,7 +2,8 @@
 """Margins of the GPU-against-oracle parity bars (tests/parity_bars.py), case by case.
 
 For every workload of tests/parity_cases.py (the hand-written cases and the 96 random draws) and tests/snow_cases.py (snow
-model; snow microclimate at MICRO_HEIGHTS) one line, or with --per-variable one line per variable:
+model; snow microclimate at MICRO_HEIGHTS), and with --sets snowfast1,snowfast2 of tests/snowfast_cases.py (the oracle chains of
+the fast snow method's one-call entries), one line, or with --per-variable one line per variable:
 
     N        spread of the oracle's noise variants (fma, ulp, ulpfma): how far apart two correct evaluations lie
     bar      min(1e-6, max(2^-40, 16 N)): what the GPU tests assert
@@ -14,8 +15,13 @@ The per-case line gives the variable with the largest bar (N, bar), each slip's 
 largest (what the power condition of tests/test_parity_bars_cpu.py is about; "-": the slip does not touch the case), and
 with --gpu the variable with the largest d / bar.
 
+The snowfast sets run on terrain_oracle's terrain without --gpu.  With --gpu the oracle chain is handed the device's terrain
+(terrain.snow_terrain; no variant models numpy terrain: DESIGN section 2, "Tolerance"), so N, bar and S are those of that
+terrain, and each case gives two lines: `caseN` the one device-resident call, `caseN/days` the host day loop.
+
     python tools/parity_margins.py > profiles/parity_bars_cpu.txt             (no GPU needed)
     python tools/parity_margins.py --gpu > profiles/parity_margins_gpu.txt
+    python tools/parity_margins.py --sets snowfast1,snowfast2 [--gpu] [--per-variable]       (appended to the same files)
 """
 from __future__ import annotations
 
@@ -39,11 +45,30 @@ def hip(inp):
             return runmicro2Cpp(**a, **inp["extra"])
         return runmicro1Cpp(**a, **inp["extra"])
     from microclimf_amd import snow as S
+    if inp["kind"] in ("snowfast1", "snowfast2"):
+        c, days = inp["case"], "_days" if inp.get("days") else ""
+        if inp["kind"] == "snowfast1":
+            return getattr(S, "snowmodelq1" + days)(*c["args"])
+        return getattr(S, "snowmodelq2" + days)(*c["args"], **c["pos"])
     if inp["kind"] == "snowmodel":
         sw = inp["sw"]
         return (S.gridmodelsnow2 if inp["af"] else S.gridmodelsnow1)(sw["obstime"], sw["climdata"], sw["pointm"], sw["vegp"],
                                                                       sw["other"], sw["snowenv"])
     return (S.gridmicrosnow2 if inp["af"] else S.gridmicrosnow1)(*inp["args"])
+
+
+def workloads(sets, gpu):
+    """PB.case_sets; with --gpu a snowfast case runs on the device's terrain and yields the one call and the day loop"""
+    for kind, label, run, inp in PB.case_sets(O, sets):
+        if gpu and kind in ("snowfast1", "snowfast2"):
+            import snowfast_cases as FC
+            from microclimf_amd.terrain import snow_terrain
+            z, res, zref, _ = FC.oracle_terrain(inp["case"])
+            run = FC.run(O, inp["case"], terrain=snow_terrain(z, res, zref, device=0))
+            yield kind, label, run, inp
+            yield kind, label + "/days", run, dict(inp, days=True)
+        else:
+            yield kind, label, run, inp
 
 
 def fmt(x):
@@ -64,9 +89,13 @@ def main():
         print("# set case variables largest-bar-variable N bar " + " ".join(f"S_{s}/bar" for s in slips)
               + (" largest-d/bar-variable d bar d/bar" if args.gpu else ""))
     summary = {}
-    for kind, label, run, inp in PB.case_sets(O, tuple(args.sets.split(","))):
-        want, bars, noise = PB.bars_for(O, run)
-        S = PB.slips_for(O, run, want)
+    slipped = {}
+    for kind, label, run, inp in workloads(tuple(args.sets.split(",")), args.gpu):
+        want, bars, noise = PB.bars_for(O, run, (kind, label.split("/")[0]))
+        if (kind, label.split("/")[0]) not in slipped:
+            slipped.clear()                                    # the day loop's line shares the call's variant runs
+            slipped[kind, label.split("/")[0]] = PB.slips_for(O, run, want)
+        S = slipped[kind, label.split("/")[0]]
         got = hip(inp) if args.gpu else None
         s = summary.setdefault(kind, dict(cases=0, pairs=0, floor=0, cap=0, maxbar=0.0, maxbar_at="", minpower=float("inf"),
                                           minpower_at="", maxratio=0.0, maxratio_at="", over=0, exp46=[float("inf"), 0.0]))
