@@ -519,6 +519,12 @@ int mcf_runbioclim3_multi(const mcf_grid_inputs *in, const mcf_options *opt, con
                           mcf_bioclim_out *out);
 int mcf_runbioclim4_multi(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_bioclim_sel *sel, const mcf_multi *multi,
                           mcf_bioclim_out *out);
+/* How the calling thread's last bioclim call ran: the number of solver chunk launches of the streamed sink (vector forcing
+ * and coarse array forcing, array_forcing == 2, above ground with ascending quarter lists: the solver runs in day chunks and
+ * nothing of size cells x steps is allocated), summed over the row blocks of a `_multi` call; 0: the whole-series route
+ * (fine array forcing, reqhgt < 0, MCF_BIOCLIM_WHOLE set) or no call yet.  The matrices are the same bits either way: a
+ * read-only observation, like mcf_plan_kernel_stats. */
+int mcf_bioclim_last_chunks(void);
 
 /* ---- period summaries --------------------------------------------------------------------------------------------------
  * Per-cell statistics of the solver's outputs over caller-defined periods (what users of the reference do with

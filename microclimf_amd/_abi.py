@@ -295,6 +295,7 @@ EXPORTS = (
     "mcf_runmicro1_diag", "mcf_runmicro3_diag",
     "mcf_plan_summary_enable", "mcf_plan_summary_accumulate", "mcf_plan_summary_fetch", "mcf_plan_summary_days",
     "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
+    "mcf_bioclim_last_chunks",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -518,6 +519,8 @@ def load() -> C.CDLL:
     for fn in (lib.mcf_runbioclim1_multi, lib.mcf_runbioclim2_multi, lib.mcf_runbioclim3_multi, lib.mcf_runbioclim4_multi):
         fn.restype = C.c_int
         fn.argtypes = [GI, OP, C.POINTER(BioclimSel), C.POINTER(Multi), C.POINTER(BioclimOut)]
+    lib.mcf_bioclim_last_chunks.restype = C.c_int
+    lib.mcf_bioclim_last_chunks.argtypes = []
     lib.mcf_snowenv_from_name.restype = C.c_int32
     lib.mcf_snowenv_from_name.argtypes = [C.c_char_p]
     SI = C.POINTER(SnowInputs)

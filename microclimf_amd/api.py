@@ -263,10 +263,10 @@ BIOCLIM_DFSEL = {"lyr": np.arange(1, 15), "st": np.arange(14) * 24, "ed": np.ara
 
 
 def _bioclim(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp,
-             Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, layered=False, devices=None, n_blocks=0):
+             Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, layered=False, devices=None, n_blocks=0, coarse=None):
     lib = _abi.load()
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, True, mat,
-                [1] * 10, array_forcing, device, dfsel=BIOCLIM_DFSEL if layered else None)
+                [1] * 10, array_forcing, device, dfsel=BIOCLIM_DFSEL if layered else None, coarse=coarse)
     sel = _abi.BioclimSel()
     keep = []
     for name, q in (("wet", wetq), ("dry", dryq), ("hot", hotq), ("col", colq)):
@@ -311,6 +311,47 @@ def runbioclim2Cpp(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, l
     """Drop-in for the reference's runbioclim2Cpp (src/microclimfCpp.cpp:3590-3616), array climate."""
     return _bioclim("mcf_runbioclim2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
                     Sminp, Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, devices=devices, n_blocks=n_blocks)
+
+
+def _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm):
+    R, Cc = np.shape(vegp["hgt"])[:2]
+    cr, cc = np.shape(climdata["temp"])[:2]
+    coarse = {"rowpos": coarse_positions(R, cr) if rowpos is None else rowpos,
+              "colpos": coarse_positions(Cc, cc) if colpos is None else colpos}
+    if altcorrect:
+        if dtmc is None or dtm is None:
+            raise ValueError("altcorrect needs dtmc (the climate cells' elevations) and dtm (the raster's)")
+        coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=dtm)
+    return coarse
+
+
+def runbioclim2Cpp_coarse(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons, Sminp, Smaxp, tfact, mat, out,
+                          wetq, dryq, hotq, colq, air, *, rowpos=None, colpos=None, altcorrect: int = 0, dtmc=None, dtm=None,
+                          device: int = 0, devices=None, n_blocks: int = 0) -> dict:
+    """`.runbioclim2`'s solver call with the resampling fused into the solver (array_forcing == 2): `climdata` and `pointm`
+    as COARSE arrays [coarse_rows, coarse_cols, tsteps], as for runmicro2Cpp_coarse (`rowpos` / `colpos`, `altcorrect` with
+    `dtmc` / `dtm`: see there).  Above ground the sink is streamed: the solver runs in day chunks and nothing of size
+    cells x steps exists on the device (`bioclim_last_chunks`).  `devices` / `n_blocks`: row blocks, same bits."""
+    coarse = _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm)
+    return _bioclim("mcf_runbioclim2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
+                    Sminp, Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, devices=devices, n_blocks=n_blocks,
+                    coarse=coarse)
+
+
+def runbioclim4Cpp_coarse(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons, Sminp, Smaxp, tfact, mat, out,
+                          wetq, dryq, hotq, colq, air, *, rowpos=None, colpos=None, altcorrect: int = 0, dtmc=None, dtm=None,
+                          device: int = 0, devices=None, n_blocks: int = 0) -> dict:
+    """runbioclim2Cpp_coarse with the fourteen one-day vegetation layers of runbioclim4Cpp (`.runbioclim4`)."""
+    coarse = _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm)
+    return _bioclim("mcf_runbioclim4", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
+                    Sminp, Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, True, devices=devices, n_blocks=n_blocks,
+                    coarse=coarse)
+
+
+def bioclim_last_chunks() -> int:
+    """Solver chunk launches of this thread's last runbioclim*Cpp call (include/mcf.h mcf_bioclim_last_chunks): > 0 — the
+    streamed sink ran; 0 — the whole-series one.  The matrices do not tell."""
+    return int(_abi.load().mcf_bioclim_last_chunks())
 
 
 class Plan:

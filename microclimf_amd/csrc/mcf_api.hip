@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdlib>
 #include <future>
@@ -2035,10 +2036,13 @@ static int bioclim_download(mcf_plan* p, const mcf_grid_inputs* in, const mcf_bi
         }
     return mcf_plan_sync(p);
 }
+// solver chunk launches of this thread's last bioclim call (mcf_bioclim_last_chunks); 0: the whole-series route
+static thread_local int g_bioclim_chunks = 0;
 // twi_mean / out_pitch: a row block of a taller raster (the bioclim `_multi` entries): the raster-wide twi mean to install, and
 // the rows of the caller's [rows_total, cols] matrices the block's rows are written into in place
 static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_in, const mcf_bioclim_sel* sel,
                        mcf_bioclim_out* out, int want_af, int layered = 0, const double* twi_mean = nullptr, int64_t out_pitch = 0) {
+    g_bioclim_chunks = 0;
     if (!sel || !out || !in_caller) return fail(MCF_ERR_ARG, "null bioclim argument");
     // runbioclim3Cpp / 4Cpp (cpp:3620-3658 / 3660-3700): vegetation arrays [rows, cols, >= 14] and a fixed dfsel of
     // fourteen one-day layers — the twelve monthly days, the hottest and the coldest day; later steps (the quarter
@@ -2071,18 +2075,20 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
     opt.out[MCF_OUT_SOILM] = 1;
     if ((rc = ensure_device(opt.device))) return rc;
     const int ndays = (int)(T / 24);
-    // Streamed (round 5; vector forcing above ground, quarter lists in ascending order — what runbioclim passes): the solver
-    // runs in day chunks into a ring of a few GB and k_bioclim_acc folds each chunk into 29 doubles of running state per cell;
+    // Streamed (round 5; vector or coarse array forcing above ground, quarter lists in ascending order — what runbioclim passes):
+    // the solver runs in day chunks into a ring of a few GB and k_bioclim_acc folds each chunk into 29 doubles of running state per cell;
     // nothing of size cells x steps is allocated (the whole-series form below needs 2 x 8 B x cells x steps: 167 GB for a 4096^2
     // raster, most of the call's time).  Same accumulation order, same operands: the matrices are bit for bit the whole-series
-    // form's (MCF_BIOCLIM_WHOLE=1 selects that one: the A/B of tests/test_bioclim_gpu.py).
-    bool streamed = !in->array_forcing && !(opt.reqhgt < 0.0) && getenv("MCF_BIOCLIM_WHOLE") == nullptr;
+    // form's (MCF_BIOCLIM_WHOLE=1 selects that one: the A/B of tests/test_bioclim_gpu.py, tests/test_bioclim_coarse_gpu.py).
+    // Fine array forcing stays whole-series: its inputs are cells x steps by themselves.  Coarse array forcing keeps its series
+    // resident on the coarse grid, so nothing but the ring and the running state scales with the raster.
+    bool streamed = in->array_forcing != 1 && !(opt.reqhgt < 0.0) && getenv("MCF_BIOCLIM_WHOLE") == nullptr;
     for (int i = 0; streamed && i < 4; ++i)
         for (int j = 1; j < nq[i]; ++j)
             if (q[i][j] < q[i][j - 1]) streamed = false;
     int chunk_days = ndays;
     if (streamed) {
-        const int cpb = opt.cells_per_block ? opt.cells_per_block : 21;
+        const int cpb = in->array_forcing == 2 ? 32 : opt.cells_per_block ? opt.cells_per_block : 21;     // mcf_plan_create's tiles
         const double day_bytes = 2.0 * 8.0 * (double)((N + cpb - 1) / cpb) * (double)mcf::ring_block_doubles(cpb);
         const char* e = getenv("MCF_BIOCLIM_RING_GB");
         const double budget = (e && atof(e) > 0.0 ? atof(e) : 14.0) * 1e9;     // (4096^2: 0.80 s with 14 GB = two-day chunks, 0.85 s with 8, 2.3 s with 27 — the allocation; profiles/r05_sink_rates.txt)
@@ -2107,6 +2113,7 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
         for (int d0 = 0; d0 < ndays; d0 += p->ring_days) {
             const int nd = std::min(p->ring_days, ndays - d0);
             if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+            ++g_bioclim_chunks;
             acc.day0 = d0; acc.ndays = nd;
             for (int i = 0; i < 4; ++i) {
                 acc.qlo[i] = (int32_t)(std::lower_bound(q[i], q[i] + nq[i], d0 * 24) - q[i]);
@@ -2118,6 +2125,13 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
         mcf::BioFinArgs fin{};
         fin.N = N; fin.tsteps = (int)T; fin.state = acc.state;
         fin.cellc = p->d_cellc; fin.ntiles_total = p->ntiles; fin.cpb = p->cpb; fin.daylayer = p->d_daylayer; fin.tt = p->d_tt;
+        if (p->coarse) {
+            // no per-day table: the second pass taps the resident coarse soil moisture series as the solver does (mcf_kernels.h)
+            fin.cforce = p->d_force;
+            fin.cstride = (int64_t)p->crows * p->ccols * std::max<int64_t>(p->tsteps, 1);
+            fin.crows = p->crows; fin.ccols = p->ccols;
+            fin.crowpos = p->d_crowpos; fin.ccolpos = p->d_ccolpos; fin.rows = (int32_t)p->rows;
+        }
         if ((rc = dalloc(p, &tmp, (int64_t)MCF_NBIO * N * 8))) return rc;
         fin.bio = (double*)tmp;
         mcf::launch_bioclim_fin(fin, p->stream);
@@ -2157,6 +2171,7 @@ int mcf_runbioclim4(const mcf_grid_inputs* in, const mcf_options* opt, const mcf
 int mcf_runbioclim2(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, mcf_bioclim_out* out) {
     return run_bioclim(in, opt, sel, out, 1);
 }
+int mcf_bioclim_last_chunks(void) { return g_bioclim_chunks; }
 
 // ---- period summaries (include/mcf.h "period summaries"; kernels: mcf_summary.hip) -----------------------------------------
 // everything of a summary that can be judged without a device; `requested`: the plan's var_slot (null: any variable)
@@ -2644,11 +2659,16 @@ static int run_bioclim_multi(const mcf_grid_inputs* in, const mcf_options* opt, 
     const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
     mcf_grid_inputs in_l = *in;
     if (layered) { in_l.veg_layers = 14; in_l.lyr_st = kBioSt; in_l.lyr_ed = kBioEd; }     // as run_bioclim: the fixed dfsel
-    return for_row_blocks(&in_l, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int) {
+    std::atomic<int> chunks{0};               // the blocks run on worker threads: their counts, summed for the caller's thread
+    const int rc = for_row_blocks(&in_l, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int) {
         mcf_bioclim_out bo = *out;
         for (int v = 0; v < MCF_NBIO; ++v) if (bo.bio[v]) bo.bio[v] += r0;
-        return run_bioclim(&sub, &o, sel, &bo, want_af, layered, twi_mean, pitch);
+        const int rcb = run_bioclim(&sub, &o, sel, &bo, want_af, layered, twi_mean, pitch);
+        chunks += g_bioclim_chunks;
+        return rcb;
     });
+    g_bioclim_chunks = chunks;
+    return rc;
 }
 int mcf_runbioclim1_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const mcf_multi* mu, mcf_bioclim_out* out) {
     return run_bioclim_multi(in, opt, sel, mu, out, 0, 0);

@@ -918,6 +918,13 @@ struct CoarseTap {
     // columns once per tile-day and along the rows per lane, and must give the bits of this per-lane form
     static __device__ __forceinline__ double mix(double a, double b, double w) { return fma(w, b, (1.0 - w) * a); }
 };
+// The resident coarse series of a plan, [15][crows*ccols][tsteps] (mcf_plan_create): series f at hour `hour` of day `day`.
+// Wave-uniform operands give a scalar address; a lane's four neighbours then lie at CoarseTap's 32-bit byte offsets from it
+// (a day of one series is 24 x cells x 8 B < 2^32: mcf_plan_create refuses larger coarse grids).
+__device__ __forceinline__ const double* coarse_day_field(const double* base, int64_t stride, int crows, int ccols, int f, int day,
+                                                          int hour = 0) {
+    return base + (int64_t)f * stride + (int64_t)crows * ccols * ((int64_t)day * 24 + hour);
+}
 // `.satvap` and `.dewpoint` of the R side (R/internal.R:501-521), which `.runmodel2Cpp` applies to the resampled
 // temperature and humidity (R/internal.R:1230-1232); NOT satvapCpp / dewpointCpp (other ice threshold, other constants).
 __device__ __forceinline__ double satvap_r(double tc, const MathK& K) {

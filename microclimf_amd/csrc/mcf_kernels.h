@@ -276,7 +276,14 @@ struct BioFinArgs {
     int64_t ntiles_total;
     int32_t cpb;
     const int32_t* daylayer;   // or null
-    const double* tt;          // time table [day][TF_COUNT][24]
+    const double* tt;          // time table [day][TF_COUNT][24]; null with coarse array forcing
+    // coarse array forcing (cforce != null) has no such table: the point model's soil moisture of a cell at a step is the
+    // bilinear tap of the resident coarse series, taken as the solver's lanes take it (CoarseTap, coarse_day_field)
+    const double* cforce;      // the resident series [15][crows*ccols][tsteps]
+    int64_t cstride;           // doubles from one of the fifteen to the next
+    int32_t crows, ccols;
+    const double *crowpos, *ccolpos;   // [rows], [cols]
+    int32_t rows;
 };
 void launch_bioclim_fin(const BioFinArgs& a, hipStream_t s);
 void launch_fill(double* p, int64_t n, double v, hipStream_t s);

@@ -1676,6 +1676,11 @@ void launch_bioclim_acc(const BioAccArgs& a, hipStream_t s) {
     if (a.N <= 0) return;
     hipLaunchKernelGGL(k_bioclim_acc, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
 }
+// COARSE (coarse array forcing): the second pass has no per-day table to read the point model's soil moisture from — every step's
+// value is the cell's bilinear tap of the resident coarse series, as k_solve's lanes take it (per lane or staged in LDS: the
+// same bits, CoarseTap::mix).  The step's field is a scalar address, the cell's four neighbours four 32-bit byte offsets made
+// once; the loop over the steps holds no per-lane address arithmetic.
+template <bool COARSE>
 __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t N = a.N;
@@ -1714,6 +1719,8 @@ __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
         double smin = 0.0, invrge = 0.0, eta = 0.0, rge = 0.0;
         bool valid = false;
         Canary cn;
+        const uint32_t rows = COARSE ? (uint32_t)a.rows : 1u, col = cc / rows;
+        const CoarseTap tap(COARSE ? a.crowpos[cc - col * rows] : 0.0, COARSE ? a.ccolpos[col] : 0.0, a.crows, a.ccols);
         for (int d = 0; d < T / 24; ++d) {
             const int l = a.daylayer ? a.daylayer[d] : 0;
             if (l != layer) {
@@ -1724,9 +1731,12 @@ __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
                     valid = ((int)img[CF_FLAGS * a.cpb] & FL_VALID) != 0;
                 }
             }
-            const double* sp = a.tt + ((int64_t)d * TF_COUNT + TF_SOILMP) * 24;
+            const double* sp = COARSE ? nullptr : a.tt + ((int64_t)d * TF_COUNT + TF_SOILMP) * 24;
             for (int h = 0; h < 24; ++h) {
-                const double v = (l >= 0 && valid) ? soil_spread<false>(sp[h], smin, invrge, eta, rge, cn) : NA;
+                double smp;
+                if constexpr (COARSE) smp = tap(coarse_day_field(a.cforce, a.cstride, a.crows, a.ccols, TF_SOILMP, d, h));
+                else smp = sp[h];
+                const double v = (l >= 0 && valid) ? soil_spread<false>(smp, smin, invrge, eta, rge, cn) : NA;
                 const double dlt = v - mean;
                 ss += dlt * dlt;
             }
@@ -1743,7 +1753,8 @@ __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
 }
 void launch_bioclim_fin(const BioFinArgs& a, hipStream_t s) {
     if (a.N <= 0) return;
-    hipLaunchKernelGGL(k_bioclim_fin, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
+    if (a.cforce) hipLaunchKernelGGL(k_bioclim_fin<true>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_bioclim_fin<false>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------

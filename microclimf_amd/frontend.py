@@ -21,6 +21,7 @@ SpatRaster carries besides values is passed as `dtm = {"z": array, "res": xres |
 """
 from __future__ import annotations
 
+import warnings
 from typing import Mapping, Sequence
 
 import numpy as np
@@ -1299,6 +1300,39 @@ def _quarter(values, months, how):
     return sm
 
 
+def bioclim_quarters(precip, temp, months):
+    """(wq, dq, hq, cq), 1-based months: the centre months of the wettest, driest, hottest and coldest quarter
+    (R/internal.R:1796-1801 / 1911-1916; `precip`, `temp`: one value per step)"""
+    pq = _quarter(precip, months, np.nanmean)
+    tq = _quarter(temp, months, np.nansum)
+    return int(np.argmax(pq)) + 1, int(np.argmin(pq)) + 1, int(np.argmax(tq)) + 1, int(np.argmin(tq)) + 1
+
+
+def _bioclim_vegp14(veg, seld, n, vegpisannual, reqhgt, pai_a, mp) -> dict:
+    """`.sortvegp2` (R/internal.R:2100-2130): the vegetation layer of each of the fourteen modelled days"""
+    seld = seld % 365 if vegpisannual else seld
+    nd = 365 if vegpisannual else int(round(n / 24))
+    v14 = {}
+    for k in VEG_KEYS:
+        arr = as3d(veg[k])
+        dmx = arr.shape[2]
+        if dmx == 1:
+            v14[k] = np.repeat(arr, 14, axis=2)
+        else:
+            sidx = layer_index(dmx, nd)
+            sidx = np.concatenate([sidx, sidx[-1:]])
+            v14[k] = arr[:, :, sidx[np.clip(seld, 1, len(sidx)) - 1] - 1]      # (seld = 0 would drop the day in R)
+    pa = None if pai_a is None else intr(pai_a, mp["ntme"], mp["subs"])
+    v14["leafden"], v14["paia"] = foliageden(reqhgt, v14["hgt"], v14["pai"], pa)
+    return v14
+
+
+def _getselq(mon2, iq):
+    """`.getselq(iq, tme) - 1` (R/internal.R:1764-1774): the steps of the modelled series in the quarter around month iq"""
+    imn, imx = (12 if iq == 1 else iq - 1), (1 if iq == 12 else iq + 1)
+    return np.sort(np.concatenate([np.nonzero(mon2 == m)[0] for m in (imn, iq, imx)]))
+
+
 def runbioclim(climdata: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, temp: str = "air",
                zref: float = 2.0, windhgt: float | None = None, soilm=None, pai_a=None, tfact: float = 1.5,
                out: Sequence = (1,) * 19, vegpisannual: bool = True, device: int = 0, _bioclim=None, _terrain=None) -> dict:
@@ -1308,9 +1342,7 @@ def runbioclim(climdata: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
     ob_all = {k: np.asarray(climdata["obstime"][k]) for k in ("year", "month", "day", "hour")}
     mon_all = ob_all["month"].astype(int)
     t_all, p_all = np.asarray(climdata["temp"], dtype=np.float64), np.asarray(climdata["precip"], dtype=np.float64)
-    pq = _quarter(p_all, mon_all, np.nanmean)
-    tq = _quarter(t_all, mon_all, np.nansum)
-    wq, dq, hq, cq = int(np.argmax(pq)) + 1, int(np.argmin(pq)) + 1, int(np.argmax(tq)) + 1, int(np.argmin(tq)) + 1
+    wq, dq, hq, cq = bioclim_quarters(p_all, t_all, mon_all)
     sel = biosel(ob_all, t_all)
     w2 = {k: np.asarray(climdata[k])[sel["selh"]] for k in WEATHER}
     w2["obstime"] = {k: v[sel["selh"]] for k, v in ob_all.items()}
@@ -1323,34 +1355,82 @@ def runbioclim(climdata: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
         ter_kw = dict(slr=t["slope"], apr=t["aspect"], hor=t["hor"], svf=t["svfa"], wsa=t["wsa"])
     static = {k: as3d(v)[:, :, 0] for k, v in veg.items()} if layered else vegp
     a = prepare_grid_inputs(mp, reqhgt, static, soilc, dtm, pai_a=None if layered else pai_a, device=device, **ter_kw)
-    if layered:                                                                 # .sortvegp2
-        n = len(t_all)
-        seld = sel["seld"] % 365 if vegpisannual else sel["seld"]
-        nd = 365 if vegpisannual else int(round(n / 24))
-        v14 = {}
-        for k in VEG_KEYS:
-            arr = as3d(veg[k])
-            dmx = arr.shape[2]
-            if dmx == 1:
-                v14[k] = np.repeat(arr, 14, axis=2)
-            else:
-                sidx = layer_index(dmx, nd)
-                sidx = np.concatenate([sidx, sidx[-1:]])
-                v14[k] = arr[:, :, sidx[np.clip(seld, 1, len(sidx)) - 1] - 1]      # (seld = 0 would drop the day in R)
-        pa = None if pai_a is None else intr(pai_a, mp["ntme"], mp["subs"])
-        v14["leafden"], v14["paia"] = foliageden(reqhgt, v14["hgt"], v14["pai"], pa)
-        a["vegp"] = v14
+    if layered:
+        a["vegp"] = _bioclim_vegp14(veg, sel["seld"], len(t_all), vegpisannual, reqhgt, pai_a, mp)
     mon2 = np.asarray(w2["obstime"]["month"]).astype(int)
-
-    def selq(iq):                                                               # .getselq(iq, tme) - 1
-        imn, imx = (12 if iq == 1 else iq - 1), (1 if iq == 12 else iq + 1)
-        return np.sort(np.concatenate([np.nonzero(mon2 == m)[0] for m in (imn, iq, imx)]))
     args = {k: a[k] for k in ("obstime", "climdata", "pointm", "vegp", "soilc", "reqhgt", "zref", "lat", "lon", "Sminp", "Smaxp")}
-    kw = dict(tfact=float(tfact), mat=a["mat"], out=[int(bool(v)) for v in out], wetq=selq(wq), dryq=selq(dq), hotq=selq(hq),
-              colq=selq(cq), air=(temp == "air"))
+    kw = dict(tfact=float(tfact), mat=a["mat"], out=[int(bool(v)) for v in out], wetq=_getselq(mon2, wq), dryq=_getselq(mon2, dq),
+              hotq=_getselq(mon2, hq), colq=_getselq(mon2, cq), air=(temp == "air"))
     if _bioclim is not None:
         return _bioclim(layered, args, kw)
     fn = api.runbioclim3Cpp if layered else api.runbioclim1Cpp
+    res = fn(**args, **kw, device=device)
+    na = np.isnan(z)
+    for v in res.values():
+        v[na] = np.nan                                                          # mask(bior, dtm)
+    return res
+
+
+def bioclima_selection(climarray: Mapping, obstime: Mapping) -> dict:
+    """What `.runbioclim2` / `.runbioclim4` decide from the weather alone (R/internal.R:1909-1916, 1749-1755): the four
+    quarters from the spatial means of precipitation and temperature per step (`apply(..., 3, mean, na.rm = TRUE)`), and
+    `biosel` on the spatial-mean temperature.  Returns {wq, dq, hq, cq (1-based months), seld, selh}."""
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)                           # a step without data anywhere: NaN, as in R
+        prech = np.nanmean(np.asarray(climarray["precip"], dtype=np.float64), axis=(0, 1))
+        tc = np.nanmean(np.asarray(climarray["temp"], dtype=np.float64), axis=(0, 1))
+    wq, dq, hq, cq = bioclim_quarters(prech, tc, np.asarray(obstime["month"]).astype(int))
+    sel = biosel(obstime, tc)
+    return dict(wq=wq, dq=dq, hq=hq, cq=cq, seld=sel["seld"], selh=sel["selh"])
+
+
+def runbioclima(climarray: Mapping, obstime: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, lats, lons,
+                clats, clons, dtmc=None, altcorrect: int = 0, temp: str = "air", zref: float = 2.0, windhgt: float | None = None,
+                soilm=None, pai_a=None, tfact: float = 1.5, out: Sequence = (1,) * 19, vegpisannual: bool = True,
+                device: int = 0, point_device: int | None = None, _bioclim=None, _terrain=None) -> dict:
+    """`runbioclim()` for array weather (R/Cppwrappers.R:628-651 -> `.runbioclim2` / `.runbioclim4`, R/internal.R:1896-2081 /
+    2200-2388): `climarray[k]` [crows, ccols, T] for the weather variables, `obstime` = {year, month, day, hour}.  The
+    fourteen days `biosel` picks from the spatial-mean temperature are cut out of every array, the point model runs once per
+    climate cell on them (`.biomicropoint`; `point_device`: as one batch on that device), and the solver interpolates the
+    coarse climate and point-model arrays itself while the nineteen variables are reduced from its day chunks
+    (runbioclim2Cpp_coarse / 4Cpp_coarse).  `lats`, `lons`: [rows, cols] of the raster; `clats`, `clons`: [crows, ccols] of
+    the climate grid; `altcorrect` 1 / 2 with `dtmc` [crows, ccols]: as runmicro_array.  Returns {bio1.. : [rows, cols]}."""
+    if reqhgt < 0:
+        raise ValueError("coarse array forcing below ground needs the per-cell point-model series: not mirrored")
+    if altcorrect and dtmc is None:
+        raise ValueError("altcorrect needs dtmc, the elevations of the climate cells")
+    ob_all = {k: np.asarray(obstime[k]) for k in ("year", "month", "day", "hour")}
+    s = bioclima_selection(climarray, ob_all)
+    cut = {k: np.asfortranarray(np.asarray(climarray[k], dtype=np.float64)[:, :, s["selh"]]) for k in WEATHER}
+    ob2 = {k: v[s["selh"]] for k, v in ob_all.items()}
+    cr, cc, n_all = np.shape(climarray["temp"])
+    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    mpa = runpointmodela(cut, ob2, reqhgt, dtm, vegp, soilc, lats=clats, lons=clons, zref=zref,
+                         windhgt=zref if windhgt is None else windhgt, soilm=soilm, yearG=False, device=point_device)
+    if any(m is None for m in mpa):
+        raise ValueError("every coarse cell needs a micropoint")
+    layered = vegpdmx(veg) > 1
+    ter_kw = {}
+    if _terrain is not None:
+        t = _terrain(z, dtm["res"] if np.isscalar(dtm["res"]) else dtm["res"][0], mpa[0]["zref"])
+        ter_kw = dict(slr=t["slope"], apr=t["aspect"], hor=t["hor"], svf=t["svfa"], wsa=t["wsa"])
+    static = {k: as3d(v)[:, :, 0] for k, v in veg.items()} if layered else vegp
+    a = prepare_grid_inputs_array(mpa, cr, cc, reqhgt, static, soilc, dtm, lats=lats, lons=lons,
+                                  pai_a=None if layered else pai_a, device=device, **ter_kw)
+    if layered:
+        a["vegp"] = _bioclim_vegp14(veg, s["seld"], n_all, vegpisannual, reqhgt, pai_a, mpa[0])
+    mon2 = ob2["month"].astype(int)
+    args = {k: a[k] for k in ("obstime", "climdata", "pointm", "vegp", "soilc", "reqhgt", "zref", "Sminp", "Smaxp")}
+    args.update(lats=a["lat"], lons=a["lon"])
+    R, Cc = z.shape
+    kw = dict(tfact=float(tfact), mat=a["mat"], out=[int(bool(v)) for v in out], wetq=_getselq(mon2, s["wq"]),
+              dryq=_getselq(mon2, s["dq"]), hotq=_getselq(mon2, s["hq"]), colq=_getselq(mon2, s["cq"]), air=(temp == "air"),
+              rowpos=api.coarse_positions(R, cr), colpos=api.coarse_positions(Cc, cc))
+    if altcorrect:
+        kw.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=z)
+    if _bioclim is not None:
+        return _bioclim(layered, args, kw)
+    fn = api.runbioclim4Cpp_coarse if layered else api.runbioclim2Cpp_coarse
     res = fn(**args, **kw, device=device)
     na = np.isnan(z)
     for v in res.values():
