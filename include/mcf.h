@@ -58,7 +58,7 @@ extern "C" {
                              *    (added since, functions only: mcf_plan_below_set_days, mcf_below_days_range, mcf_runmicrosnow1_below,
                              *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below, mcf_snowmodelq1, mcf_canintfrac_device,
                              *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device, mcf_plan_summary_*, mcf_runmicro_summary,
-                             *    mcf_runmicro_summary_multi) */
+                             *    mcf_runmicro_summary_multi, mcf_snowmodel2_coarse, mcf_snow_expand_coarse_device) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -1204,6 +1204,38 @@ int mcf_snowmodelq2(const mcf_snowfast2_in *in, mcf_snowfast2_out *out, int32_t 
 int mcf_meltmu2_device(int64_t rows, int64_t cols, const double *skyview, const double *dtm, int64_t crows, int64_t ccols,
                        const double *rowpos, const double *colpos, int64_t n, const double *sstemp_c, const double *tc_c,
                        double *mu_out, int32_t device);
+/* mcf_snowmodel2_coarse: the chunk loop of `.snowmodel2` (the slow snow method for ARRAY weather, R/internal.R:2862-3013) with the
+ * coarse climate and point-model arrays left coarse on the device — mcf_snowmodel2's loop, its thirteen uploads per chunk replaced
+ * by one kernel that expands the chunk's hours from the resident coarse arrays (14 x coarse cells x T x 8 B, uploaded once) into
+ * the buffers the snow kernel reads: `.cca` masked by the dtm, pressure and wind components unmasked, altcorrect 0 / 1 / 2 (the
+ * host takes the coarse pressure to sea level), relhum capped at 100 — the arithmetic and the bits of mcf_snowmodelq2's day
+ * expansion.  Terrain refresh, position index (af_wind, floor of 2), af_wsa_s, `1:n5days` truncation with at least one chunk,
+ * other$isnowdg never updated: as mcf_snowmodel2.  out->umu: pointm$umu on the raster for ALL T steps (the steps behind the last
+ * whole chunk too, where the other five stay NA); every series is NA on the dtm's holes.  One device, one block: MCF_ERR_NOMEM if
+ * the chunk's series (18 x chunk_steps x 8 B per cell) do not fit.
+ * mcf_snow_expand_coarse_device: the expansion kernel alone (upload, one launch, download) for steps step0 .. step0 + nsteps - 1;
+ * fine[k]: [rows, cols, nsteps] in the order temp, relhum, pres, swdown, difrad, lwdown, windspeed, precip, Gp, Tc, RswabsG,
+ * RlwabsG, umu (what mcf_snowmodel2 takes as clim / pointm).  It reads drv.base.{rows, cols, tsteps}, drv.dtm, the positions, the
+ * coarse arrays, coarse_dtm and altcorrect only.
+ * MCF_ERR_ARG before any device is touched, the message naming the entry and the input: a null argument, coarse_rows /
+ * coarse_cols < 1, a position outside the coarse grid, altcorrect outside 0..2 or > 0 without coarse_dtm, 24 x coarse cells x
+ * 8 B >= 2^32, chunk_steps not whole days, drv.base.array_forcing == 0; for the expansion step0 < 0, nsteps < 1 or step0 +
+ * nsteps > T. */
+typedef struct mcf_snowcoarse_in {
+    mcf_snowdriver_in drv;  /* drv.base: rows, cols, tsteps = T, array_forcing != 0, snowenv, obstime [T], clim.winddir [T] (one
+                               direction per hour), vegp, other.{lats, lons, zref, isnowdc, isnowdg, isnowac, isnowag}; drv.dtm,
+                               res, tfact, chunk_steps, af_wsa_s, af_wind [T]; the other members of clim / pointm are ignored */
+    int64_t coarse_rows, coarse_cols;
+    const double *coarse_rowpos, *coarse_colpos;   /* [rows], [cols] */
+    int32_t altcorrect;                             /* 0, 1 (fixed lapse rate), 2 (moist adiabatic) */
+    int32_t reserved;
+    const double *coarse_dtm;                       /* [crows, ccols], NA read as 0; needed when altcorrect > 0 */
+    /* [crows, ccols, T].  windu / windv: windspeed x cos / sin of the coarse direction, formed by the caller */
+    const double *temp, *relhum, *pres, *swdown, *difrad, *lwdown, *precip, *windu, *windv;
+    const double *Gp, *Tc, *RswabsG, *RlwabsG, *umu;   /* the snow point model per climate cell */
+} mcf_snowcoarse_in;
+int mcf_snowmodel2_coarse(const mcf_snowcoarse_in *in, mcf_snowfast2_out *out, int32_t device);
+int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in *in, int64_t step0, int64_t nsteps, double *const fine[13], int32_t device);
 /* manCpp(src/microclimfCpp.cpp:597-627): circular trailing mean, via daily means for windows beyond 48 steps. */
 int mcf_man(int64_t n, const double *x, int32_t window, double *out);
 

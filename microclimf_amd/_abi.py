@@ -239,6 +239,16 @@ class SnowFast2In(C.Structure):
                 + [(k, c_double_p) for k in SNOWFAST2_SERIES])
 
 
+class SnowCoarseIn(C.Structure):
+    """include/mcf.h mcf_snowcoarse_in"""
+    _fields_ = ([("drv", SnowDriverIn), ("coarse_rows", C.c_int64), ("coarse_cols", C.c_int64), ("coarse_rowpos", c_double_p),
+                 ("coarse_colpos", c_double_p), ("altcorrect", C.c_int32), ("reserved", C.c_int32), ("coarse_dtm", c_double_p)]
+                + [(k, c_double_p) for k in SNOWFAST2_SELECTED])
+
+
+# the thirteen series of the snow model on the raster, in the order mcf_snow_expand_coarse_device returns them
+SNOW_FINE_SERIES = ("temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed", "precip", "Gp", "Tc", "RswabsG", "RlwabsG", "umu")
+
 SNOWFAST2_OUT = SNOWDRIVER_OUT + ("umu",)
 SnowFast2Out = _ptr_struct("SnowFast2Out", SNOWFAST2_OUT)      # mcf_snowfast2_out: mcf_snowdriver_out, then umu
 
@@ -282,6 +292,7 @@ EXPORTS = (
     "mcf_bigleaf_batch", "mcf_weatherhgt_batch", "mcf_pointmprocess_batch", "mcf_pointmodelsnow_batch",
     "mcf_bigleaf", "mcf_soilm", "mcf_pointmprocess", "mcf_weatherhgt", "mcf_man", "mcf_pointmodelsnow", "mcf_canintfrac", "mcf_meltmu", "mcf_meltmu2", "mcf_tpicalc",
     "mcf_snowmodelq1", "mcf_canintfrac_device", "mcf_meltmu_device", "mcf_snowmodelq2", "mcf_meltmu2_device",
+    "mcf_snowmodel2_coarse", "mcf_snow_expand_coarse_device",
     "mcf_nc_create", "mcf_nc_write_host", "mcf_nc_write_plan", "mcf_nc_close",
     "mcf_flowacc", "mcf_topidx",
     "mcf_runmicrosnow1", "mcf_runmicrosnow2", "mcf_runmicrosnow1_multi", "mcf_snowrun_create", "mcf_snowrun_destroy", "mcf_snowrun_days", "mcf_snowrun_stats", "mcf_snowrun_keep",
@@ -635,6 +646,11 @@ def load() -> C.CDLL:
         lib.mcf_meltmu2_device.restype = C.c_int
         lib.mcf_meltmu2_device.argtypes = [C.c_int64, C.c_int64, c_double_p, c_double_p, C.c_int64, C.c_int64, c_double_p, c_double_p,
                                            C.c_int64, c_double_p, c_double_p, c_double_p, C.c_int32]
+    if hasattr(lib, "mcf_snowmodel2_coarse"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_snowmodel2_coarse.restype = C.c_int
+        lib.mcf_snowmodel2_coarse.argtypes = [C.POINTER(SnowCoarseIn), C.POINTER(SnowFast2Out), C.c_int32]
+        lib.mcf_snow_expand_coarse_device.restype = C.c_int
+        lib.mcf_snow_expand_coarse_device.argtypes = [C.POINTER(SnowCoarseIn), C.c_int64, C.c_int64, C.POINTER(c_double_p), C.c_int32]
     if hasattr(lib, "mcf_runmicrosnow1"):     # (absent from an older library named by MCF_LIB for an A/B run)
         MI, SO = C.POINTER(MicrosnowIn), C.POINTER(SnowDriverOut)
         lib.mcf_runmicrosnow1.restype = C.c_int

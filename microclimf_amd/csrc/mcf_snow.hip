@@ -1467,6 +1467,12 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
 }  // namespace
 
 // ---- .snowmodel1's chunk loop as a stepwise, device-resident plan (one per rank's row block) ---------------
+// coarse array weather (mcf_snowmodel2_coarse, behind mcf_meltmu2_device): the resident coarse arrays and the chunk expansion
+struct SnowCoarseState;
+static void coarse_release(SnowCoarseState* cs);
+static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns);
+static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last);
+static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns);
 struct mcf_snowplan {
     int device = 0;
     int64_t rows = 0, cols = 0, N = 0, row0 = 0, rows_total = 0;
@@ -1480,6 +1486,9 @@ struct mcf_snowplan {
     bool af = false;
     const double* h_series[13] = {};      // in the order of each_model_series
     double* d_series[13] = {};            // [N][chunk]
+    // coarse array weather: the fourteen coarse arrays stay on the device, a chunk's thirteen series are expanded from them
+    // into d_series by one kernel (no h_series)
+    SnowCoarseState* coarse = nullptr;
     const DateRow2* dates_tab = nullptr;
     const double *d_dtm = nullptr, *d_isnowdg = nullptr;
     double *d_isnowdc = nullptr, *d_dtms = nullptr, *d_slope = nullptr, *d_aspect = nullptr, *d_svf = nullptr,
@@ -1502,7 +1511,7 @@ struct mcf_snowplan {
     std::vector<double> wind;
     mcf::ToHost dl;
     int prepared = -1;
-    double t_terrain = 0, t_model = 0;   // ms, MCF_TIMING
+    double t_terrain = 0, t_model = 0, t_fine = 0;   // ms, MCF_TIMING (t_fine: the chunk expansion of coarse array weather)
     mcf::TerrainWork twork;              // terrain_device's scratch, kept across the chunks
     // initial hand-over state, for mcf_snowplan_reset (the snow-day microclimate needs a second pass over the series)
     const double* d_isnowdc0 = nullptr;
@@ -1544,7 +1553,7 @@ struct mcf_snowplan {
     int64_t keep_budget = -1;            // bytes of kept sets this plan may ALLOCATE in all (mcf_snowplan_set_keep_budget); -1: no limit of its own
     int64_t keep_allocated = 0;
     mcf::DevOwner kb;
-    ~mcf_snowplan() { twork.release(); }
+    ~mcf_snowplan() { twork.release(); coarse_release(coarse); }
 };
 
 namespace {
@@ -1572,15 +1581,18 @@ extern "C" int mcf_snowplan_chunk_af(const mcf_snowplan* sp, int32_t chunk, int3
     *af = a;
     return rc;
 }
-extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, int64_t rows_total, int32_t device,
-                                   mcf_snowplan** out) {
+// `co`: coarse array weather (mcf_snowmodel2_coarse, which has checked its arguments) — din is &co->drv, the thirteen fine series
+// of din->base are not read; umu_out: where pointm$umu goes (null: not wanted)
+static int coarse_attach(mcf_snowplan* sp, const mcf_snowcoarse_in* co, double* umu_out);
+static int snowplan_create(const mcf_snowdriver_in* din, int64_t row0, int64_t rows_total, int32_t device, const mcf_snowcoarse_in* co,
+                           double* umu_out, mcf_snowplan** out) {
     int rc;
     if (!din || !out) return mcf::api_fail(MCF_ERR_ARG, "null snow driver argument");
     const mcf_snow_inputs* in = &din->base;
     if ((rc = common_checks(in))) return rc;
     const bool af = in->array_forcing != 0;
     if (!din->dtm || !(din->res > 0)) return mcf::api_fail(MCF_ERR_ARG, "snow driver needs dtm and res > 0");
-    if (!in->clim.windspeed) return mcf::api_fail(MCF_ERR_ARG, "null input: windspeed");
+    if (!co && !in->clim.windspeed) return mcf::api_fail(MCF_ERR_ARG, "null input: windspeed");
     if (rows_total <= 0) { rows_total = in->rows; row0 = 0; }
     if (row0 < 0 || row0 + in->rows > rows_total) return mcf::api_fail(MCF_ERR_ARG, "block outside the raster");
     if (af) {
@@ -1589,9 +1601,13 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
         if (!in->other.lats || !in->other.lons || !in->clim.winddir) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: lats / lons / winddir");
         bool given = true;
         each_model_series(*in, [&](auto* host, auto, auto, const char*) { given = given && host; });
-        if (!given) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: a climate / point-model array is null");
+        if (!given && !co) return mcf::api_fail(MCF_ERR_ARG, "snow driver, array weather: a climate / point-model array is null");
     }
     if ((rc = pick_device(device))) return rc;
+    if (co) {                                        // the chunk's series, the plan's rasters, the resident coarse arrays
+        const int64_t chunk = din->chunk_steps > 0 ? din->chunk_steps : 120, N = in->rows * in->cols;
+        if ((rc = check_room((18 * chunk + 60) * N * 8 + 14 * co->coarse_rows * co->coarse_cols * in->tsteps * 8))) return rc;
+    }
     mcf_snowplan* sp = new mcf_snowplan();
     struct Guard { mcf_snowplan* p; ~Guard() { delete p; } } guard{sp};
     sp->device = device;
@@ -1618,6 +1634,7 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
         if (!rc && !terrain) rc = b.up(&(a.*member), host, N, name);
     });
     if (!rc) rc = b.up(&sp->d_dtm, din->dtm, N, "dtm");
+    if (!rc && co) rc = coarse_attach(sp, co, umu_out);
     if (rc) return rc;
     sp->d_isnowdg = a.isnowdg; sp->d_isnowdc0 = a.isnowdc; sp->d_ac0 = a.isnowac; sp->d_ag0 = a.isnowag;
     // ... and the state's working copies, handed on from chunk to chunk
@@ -1671,6 +1688,15 @@ extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, i
     guard.p = nullptr;
     *out = sp;
     return MCF_OK;
+}
+extern "C" int mcf_snowplan_create(const mcf_snowdriver_in* din, int64_t row0, int64_t rows_total, int32_t device,
+                                   mcf_snowplan** out) {
+    return snowplan_create(din, row0, rows_total, device, nullptr, nullptr, out);
+}
+namespace mcf {   // mcf_snowrun.hip: the plan of mcf_snowmodel2_coarse
+int snowplan_create_coarse(const mcf_snowcoarse_in* co, double* umu_out, int32_t device, mcf_snowplan** out) {
+    return snowplan_create(&co->drv, 0, 0, device, co, umu_out, out);
+}
 }
 extern "C" void mcf_snowplan_destroy(mcf_snowplan* sp) {
     if (!sp) return;
@@ -1822,6 +1848,14 @@ void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, in
 }
 // mcf_snowmodel1 / 2's MCF_TIMING line (tools/snow_rate.py reads it)
 void snowplan_print_timing(const mcf_snowplan* sp) {
+    if (sp->coarse) {
+        const double bytes = 13.0 * 8.0 * (double)sp->N * (double)sp->chunk;
+        fprintf(stderr, "[mcf] snowmodel2_coarse: %d chunks of %d steps, %lld cells: terrain + tpi %.2f ms, chunk expansion %.3f ms per "
+                "chunk (%.1f GB/s written), gridmodelsnow + redistribute %.3f ms per chunk\n", sp->nchunks, sp->chunk, (long long)sp->N,
+                sp->t_terrain, sp->t_fine / sp->nchunks, sp->t_fine > 0 ? bytes * sp->nchunks / (sp->t_fine * 1e6) : 0.0,
+                sp->t_model / sp->nchunks);
+        return;
+    }
     fprintf(stderr, "[mcf] snowmodel1: %d chunks of %d steps, %lld cells: terrain + tpi %.2f ms, gridmodelsnow + "
             "redistribute %.2f ms\n", sp->nchunks, sp->chunk, (long long)sp->N, sp->t_terrain, sp->t_model);
 }
@@ -1961,7 +1995,10 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     a.rows = sp->af ? nullptr : sp->rows_tab + k0;            // gridmodelsnow1 on the chunk (int:2587)
     a.dates = sp->af ? sp->dates_tab + k0 : nullptr;          // gridmodelsnow2 (int:2979)
     a.tsteps = ns;
-    if (sp->af)                                               // the chunk's slices of the caller's series: [N][T], a step's raster contiguous
+    if (sp->coarse) {                                         // the chunk's hours expanded from the resident coarse arrays
+        if (const int rc = coarse_fill_chunk(sp, k0, ns)) return rc;
+        if (timing) HIP_TRY(hipEventRecord(evs.e[0], nullptr));
+    } else if (sp->af)                                        // the chunk's slices of the caller's series: [N][T], a step's raster contiguous
         for (int f = 0; f < 13; ++f)
             HIP_TRY(hipMemcpyAsync(sp->d_series[f], sp->h_series[f] + (int64_t)k0 * N, (size_t)ns * N * 8, hipMemcpyHostToDevice, nullptr));
     // ... with the redistribution by the topographic position index and the hand-over fused in (ModelArgs)
@@ -1981,6 +2018,7 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     }
     if (sp->af) hipLaunchKernelGGL(k_snowmodel<true>, dim3(gridN), dim3(256), 0, nullptr, a, a.rows, a.dates);
     else hipLaunchKernelGGL(k_snowmodel<false>, dim3(gridN), dim3(256), 0, nullptr, a, a.rows, a.dates);
+    if (sp->coarse) coarse_clean_chunk(sp, a.Tc, a.Tg, a.sdepg, a.sdepc, a.sden, ns);      // `.cleansmod` (the hand-over state is written already)
     HIP_TRY(hipGetLastError());
     if (timing) {
         HIP_TRY(hipEventRecord(evs.e[1], nullptr));
@@ -2005,6 +2043,8 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
                 for (int64_t lc = (int64_t)covered * sp->cols; lc < (int64_t)sp->T * sp->cols; ++lc)
                     for (int64_t r = 0; r < sp->rows; ++r) h[r + row_pitch * lc] = na.d;
     }
+    if (sp->coarse)                                           // pointm$umu leaves from the chunk's slab; behind the last chunk it alone is expanded
+        if (const int rc = coarse_umu_out(sp, k0, ns, fill_tail && ch == sp->nchunks - 1)) return rc;
     sp->prepared = -1;
     return MCF_OK;
 }
@@ -3087,6 +3127,238 @@ extern "C" int mcf_meltmu2_device(int64_t rows, int64_t cols, const double* skyv
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(mu_out, a.mu, (size_t)N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
+}
+
+// ---- `.snowmodel2`, the slow snow method with array weather, with the coarse arrays left coarse (mcf_snowmodel2_coarse) ---------
+namespace {
+// A chunk's thirteen series on the raster from the coarse arrays: k_fine_day's arithmetic, expression for expression, for the
+// hours a.hour0 .. a.hour0 + ns - 1 into [ns][N].  Lanes run along the cells (a wave stores 512 contiguous bytes per series
+// and hour), blockIdx.y over groups of kFineHours hours: a lane forms its tap, its pressure factor and elevd once and walks
+// its group.  Five hours: the 120-hour chunk of the bundled 50 x 50 raster is 10 x 24 = 240 workgroups on 256 CUs where one
+// lane per cell would be 10, the lane's set-up (two position loads, one pow with altcorrect) is spread over 5 x 14 taps, and
+// a chunk of whole days (24, 48, 120 hours; 24 is no multiple of 5) ends in a partial group, so the partial path is the
+// everyday one.  g0: the first group of this launch (the grid's y extent is 16 bits).
+constexpr int kFineHours = 5;
+__global__ __launch_bounds__(256) void k_fine_chunk(FineArgs a, int ns, int g0) {
+#pragma clang fp contract(off)
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    const double z = a.dtm[c], NA = na_real();
+    const bool hole = isnan(z);
+    double up = 1.0, elevd = 0.0;
+    if (a.altcorrect) {
+        up = pow((293 - 0.0065 * z) / 293, 5.26);
+        elevd = tap(a.zc) - z;
+    }
+    for (int k = kb; k < ke; ++k) {
+        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
+        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
+        double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
+        if (a.altcorrect) {
+            const double ea = snow_satvap_r(temp) * relhum / 100;
+            pres = pres * up;
+            const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
+            temp = lr * elevd + temp;
+            relhum = (ea / snow_satvap_r(temp)) * 100;
+        }
+        if (relhum > 100) relhum = 100.0;
+        const double wu = tap(a.windu + h), wv = tap(a.windv + h);
+        a.o_temp[o] = temp; a.o_relhum[o] = relhum; a.o_pres[o] = pres;
+        a.o_windspeed[o] = sqrt(wu * wu + wv * wv);
+        a.o_swdown[o] = cca(a.swdown); a.o_difrad[o] = cca(a.difrad); a.o_lwdown[o] = cca(a.lwdown); a.o_precip[o] = cca(a.precip);
+        a.o_Gp[o] = cca(a.Gp); a.o_Tc[o] = cca(a.Tc); a.o_RswabsG[o] = cca(a.RswabsG); a.o_RlwabsG[o] = cca(a.RlwabsG);
+        a.o_umu[o] = cca(a.umu);
+    }
+}
+// `.cca` of one coarse field for the hours hour0 .. hour0 + ns - 1, [ns][N]: the same lane map (pointm$umu behind the last chunk)
+__global__ __launch_bounds__(256) void k_fine_field(CoarseGeo geo, int64_t N, int64_t hour0, int ns, const double* __restrict__ dtm,
+                                                    const double* __restrict__ field, double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const int kb = (int)blockIdx.y * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    const SnowTap tap = geo.tap(c);
+    const int64_t CC = (int64_t)geo.crows * geo.ccols;
+    const bool hole = isnan(dtm[c]);
+    for (int k = kb; k < ke; ++k) {
+        const double v = tap(field + (hour0 + k) * CC);
+        out[c + N * k] = hole ? na_real() : v;
+    }
+}
+// `.cleansmod` on a chunk: NA on the dtm's holes in the series that leave, [ns][N] each (null: not written); holes are few, a
+// lane walks its cell's steps
+__global__ __launch_bounds__(256) void k_clean_chunk(CleanArgs a, int ns) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N || !isnan(a.dtm[c])) return;
+    const double NA = na_real();
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (a.v[q])
+            for (int k = 0; k < ns; ++k) a.v[q][c + a.N * k] = NA;
+}
+void launch_fine_chunk(const FineArgs& fa, int ns) {
+    const int groups = (ns + kFineHours - 1) / kFineHours;
+    for (int g0 = 0; g0 < groups; g0 += 32768)
+        hipLaunchKernelGGL(k_fine_chunk, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, nullptr,
+                           fa, ns, g0);
+}
+
+// what both entries refuse before a device is touched; model: mcf_snowmodel2_coarse (the expansion reads geometry, dtm, coarse arrays)
+int snowcoarse_checks(const mcf_snowcoarse_in* ci, const void* out, bool model, const char* entry) {
+    const std::string e = std::string(entry) + ": ";
+    auto fail = [&](const std::string& m) { return mcf::api_fail(MCF_ERR_ARG, e + m); };
+    if (!ci) return fail("null argument: in");
+    if (!out) return fail(model ? "null argument: out" : "null argument: fine");
+    const mcf_snow_inputs* in = &ci->drv.base;
+    if (in->array_forcing == 0) return fail("drv.base.array_forcing must not be 0 (array weather; data.frame weather: mcf_snowmodel1)");
+    if (in->rows <= 0 || in->cols <= 0 || in->tsteps <= 0 || in->tsteps > (1 << 30) || in->rows * in->cols >= ((int64_t)1 << 29))
+        return fail("rows, cols, tsteps out of range (at least 1; at most 2^29 - 1 cells, 2^30 steps)");
+    if (ci->coarse_rows < 1 || ci->coarse_cols < 1) return fail("coarse_rows and coarse_cols must be at least 1");
+    if (ci->altcorrect < 0 || ci->altcorrect > 2) return fail("altcorrect must be 0, 1 or 2");
+    if (ci->altcorrect > 0 && !ci->coarse_dtm) return fail("altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
+    const char* missing = nullptr;
+    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+    need(ci->coarse_rowpos, "coarse_rowpos"); need(ci->coarse_colpos, "coarse_colpos");
+    each_coarse_selected(*ci, [&](auto* host, auto, const char* name) { need(host, name); });
+    need(ci->drv.dtm, "dtm");
+    if (model) {
+        each_obstime(*in, [&](auto* host, auto, const char* name) { need(host, name); });
+        need(in->clim.winddir, "climdata$winddir");
+        each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) { if (!terrain) need(host, name); });
+        need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
+        need(ci->drv.af_wind, "af_wind");
+    }
+    if (missing) return fail(std::string("null input: ") + missing);
+    if (model && !(ci->drv.res > 0)) return fail("res must be > 0");
+    if (!positions_inside(ci->coarse_rowpos, in->rows, ci->coarse_rows) || !positions_inside(ci->coarse_colpos, in->cols, ci->coarse_cols))
+        return fail("coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
+    // (mcf_snowmodelq2's bound: a tap is a uniform base + a 32-bit byte offset)
+    if ((double)ci->coarse_rows * (double)ci->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
+        return fail("coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    if (model && (ci->drv.chunk_steps < 0 || ci->drv.chunk_steps % 24)) return fail("chunk_steps must be whole days (0: 120)");
+    return MCF_OK;
+}
+
+// geometry, dtm and the coarse arrays of hours h0 .. h0 + nh - 1 on the device (pressure taken to sea level by the host when
+// altcorrect > 0, int:2871-2873, as mcf_snowmodelq2 does); d_dtm: the raster's dtm if the caller has it there already
+int coarse_upload(mcf::DevOwner& b, const mcf_snowcoarse_in* ci, int64_t h0, int64_t nh, const double* d_dtm, FineArgs* fa) {
+    const mcf_snow_inputs* in = &ci->drv.base;
+    const int64_t N = in->rows * in->cols, CC = ci->coarse_rows * ci->coarse_cols;
+    int rc = MCF_OK;
+    memset(fa, 0, sizeof *fa);
+    fa->N = N; fa->altcorrect = ci->altcorrect;
+    fa->geo.rows = (int32_t)in->rows; fa->geo.crows = (int32_t)ci->coarse_rows; fa->geo.ccols = (int32_t)ci->coarse_cols;
+    if ((rc = b.up(&fa->geo.rowpos, ci->coarse_rowpos, in->rows, "coarse_rowpos"))) return rc;
+    if ((rc = b.up(&fa->geo.colpos, ci->coarse_colpos, in->cols, "coarse_colpos"))) return rc;
+    if (d_dtm) fa->dtm = d_dtm;
+    else if ((rc = b.up(&fa->dtm, ci->drv.dtm, N, "dtm"))) return rc;
+    std::vector<double> psl;
+    if (ci->altcorrect) {
+        std::vector<double> zc((size_t)CC), down((size_t)CC);
+        for (int64_t q = 0; q < CC; ++q) {
+            zc[(size_t)q] = std::isnan(ci->coarse_dtm[q]) ? 0.0 : ci->coarse_dtm[q];
+            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
+        }
+        psl.resize((size_t)(CC * nh));
+        for (int64_t k = 0; k < nh; ++k)
+            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = ci->pres[(h0 + k) * CC + q] / down[(size_t)q];
+        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
+    }
+    each_coarse_selected(*ci, [&](auto* host, auto member, const char* name) {
+        if (!rc) rc = b.up(&(fa->*member), ci->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
+    });
+    return rc;
+}
+// the kernel's outputs in the order of each_model_series
+void fine_outputs(FineArgs& fa, double* const d[13]) {
+    fa.o_temp = d[0]; fa.o_relhum = d[1]; fa.o_pres = d[2]; fa.o_swdown = d[3]; fa.o_difrad = d[4]; fa.o_lwdown = d[5];
+    fa.o_windspeed = d[6]; fa.o_precip = d[7]; fa.o_Gp = d[8]; fa.o_Tc = d[9]; fa.o_RswabsG = d[10]; fa.o_RlwabsG = d[11]; fa.o_umu = d[12];
+}
+}  // namespace
+
+struct SnowCoarseState {
+    FineArgs fa;                         // the resident coarse arrays of the whole series (hour 0 = step 0), the plan's dtm
+    double* h_umu = nullptr;             // [rows, cols, T] of the caller, or null
+};
+static void coarse_release(SnowCoarseState* cs) { delete cs; }
+static int coarse_attach(mcf_snowplan* sp, const mcf_snowcoarse_in* co, double* umu_out) {
+    sp->coarse = new SnowCoarseState();
+    sp->coarse->h_umu = umu_out;
+    return coarse_upload(sp->b, co, 0, sp->T, sp->d_dtm, &sp->coarse->fa);
+}
+static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns) {
+    FineArgs fa = sp->coarse->fa;
+    fa.hour0 = k0;
+    fine_outputs(fa, sp->d_series);
+    const bool timing = getenv("MCF_TIMING") != nullptr;
+    Events evs;
+    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    launch_fine_chunk(fa, ns);
+    HIP_TRY(hipGetLastError());
+    if (timing) {
+        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(evs.e[1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        sp->t_fine += ms;
+    }
+    return MCF_OK;
+}
+static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns) {
+    CleanArgs cl;
+    cl.N = sp->N; cl.dtm = sp->d_dtm;
+    cl.v[0] = Tc; cl.v[1] = Tg; cl.v[2] = sdepg; cl.v[3] = sdepc; cl.v[4] = sden;
+    hipLaunchKernelGGL(k_clean_chunk, dim3((unsigned)((sp->N + 255) / 256)), dim3(256), 0, nullptr, cl, ns);
+}
+static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last) {
+    SnowCoarseState* cs = sp->coarse;
+    if (!cs->h_umu) return MCF_OK;
+    const int64_t N = sp->N;
+    HIP_TRY(sp->dl.dense(cs->h_umu + (int64_t)k0 * N, sp->d_series[12], (size_t)ns * N * 8));
+    if (!last) return MCF_OK;
+    // the steps behind the last whole chunk (fewer than a chunk): umu alone, through the chunk's slab
+    for (int t0 = k0 + ns; t0 < sp->T; t0 += sp->chunk) {
+        const int nt = std::min(sp->chunk, sp->T - t0);
+        hipLaunchKernelGGL(k_fine_field, dim3((unsigned)((N + 255) / 256), (unsigned)((nt + kFineHours - 1) / kFineHours)), dim3(256), 0,
+                           nullptr, cs->fa.geo, N, (int64_t)t0, nt, cs->fa.dtm, cs->fa.umu, sp->d_series[12]);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(sp->dl.dense(cs->h_umu + (int64_t)t0 * N, sp->d_series[12], (size_t)nt * N * 8));
+    }
+    return MCF_OK;
+}
+
+extern "C" int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[13],
+                                             int32_t device) {
+    const char* entry = "mcf_snow_expand_coarse_device";
+    int rc;
+    if ((rc = snowcoarse_checks(in, fine, false, entry))) return rc;
+    for (int f = 0; f < 13; ++f)
+        if (!fine[f]) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[" + std::to_string(f) + "]");
+    if (step0 < 0 || nsteps < 1 || step0 > in->drv.base.tsteps - nsteps)
+        return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": step0 >= 0, nsteps >= 1 and step0 + nsteps <= tsteps are needed");
+    if ((rc = pick_device(device))) return rc;
+    const int64_t N = in->drv.base.rows * in->drv.base.cols, CC = in->coarse_rows * in->coarse_cols;
+    if ((rc = check_room((13 * nsteps + 1) * N * 8 + 14 * CC * nsteps * 8))) return rc;
+    mcf::DevOwner b;
+    FineArgs fa;
+    if ((rc = coarse_upload(b, in, step0, nsteps, nullptr, &fa))) return rc;
+    double* d[13];
+    for (int f = 0; f < 13; ++f)
+        if ((rc = b.make(&d[f], N * nsteps))) return rc;
+    fine_outputs(fa, d);
+    launch_fine_chunk(fa, (int)nsteps);
+    HIP_TRY(hipGetLastError());
+    mcf::ToHost dl;
+    for (int f = 0; f < 13; ++f) HIP_TRY(dl.dense(fine[f], d[f], (size_t)(N * nsteps) * 8));
+    HIP_TRY(hipDeviceSynchronize());
+    return MCF_OK;
+}
+namespace mcf {   // mcf_snowrun.hip
+int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out) {
+    return snowcoarse_checks(in, out, true, "mcf_snowmodel2_coarse");
+}
 }
 
 // ---- the snow-day microclimate inside the chunk loop --------------------------------------------------------------------

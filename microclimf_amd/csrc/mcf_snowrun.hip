@@ -47,6 +47,8 @@
 namespace mcf {   // mcf_snow.hip
 int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);
 void snowplan_print_timing(const mcf_snowplan* sp);
+int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out);
+int snowplan_create_coarse(const mcf_snowcoarse_in* co, double* umu_out, int32_t device, mcf_snowplan** out);
 // (over the listings of the snow entries' array groups, kept there next to the kernels' argument structs)
 bool model_rasters_given(const mcf_snow_inputs& in);
 void model_rasters_of_block(mcf_snowdriver_in& in, HostCopies* rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
@@ -728,6 +730,30 @@ extern "C" int mcf_snowmodel1(const mcf_snowdriver_in* in, mcf_snowdriver_out* o
 extern "C" int mcf_snowmodel2(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, int32_t device) {
     if (in && !in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel2 takes array weather; data.frame climate: mcf_snowmodel1");
     return snowmodel(in, out, nullptr, device);
+}
+// `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
+// (mcf_snow.hip, k_fine_chunk) and hands pointm$umu out of the chunk's slab
+extern "C" int mcf_snowmodel2_coarse(const mcf_snowcoarse_in* in, mcf_snowfast2_out* out, int32_t device) {
+    if (const int rc = mcf::snowcoarse_model_checks(in, out)) return rc;      // nothing above needs a device
+    try {
+        SnowBlocks sb;
+        sb.R = in->drv.base.rows; sb.C = in->drv.base.cols;
+        sb.devs.push_back(device);
+        sb.cut(1);
+        sb.blocks[0].device = device; sb.blocks[0].r0 = 0; sb.blocks[0].nr = sb.R;
+        int rc = mcf::run_workers(1, [&](Worker& w) {
+            mcf::for_blocks(w, 1, 1, [&](int) { return mcf::snowplan_create_coarse(in, out->umu, device, &sb.blocks[0].sp); });
+        });
+        if (rc) return rc;
+        const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
+        rc = mcf::run_workers(1, [&](Worker& w) {
+            for (int ch = 0; ch < nchunks; ++ch) snow_chunk(sb, w, ch, &out->smod);
+        });
+        if (!rc && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
+        return rc;
+    } catch (const std::exception& e) {
+        return api_fail(MCF_ERR_NOMEM, std::string("snow driver: ") + e.what());
+    }
 }
 extern "C" int mcf_snowmodel1_multi(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu) {
     if (!in || !out || !mu) return api_fail(MCF_ERR_ARG, "null snow driver argument");

@@ -865,7 +865,8 @@ def runsnowmodel(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Ma
 def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, vegp: Mapping, soilc: Mapping, dtm: Mapping, *,
                   dtmc, lats_c, lons_c, lats, lons, altcorrect: int = 0, snowenv: str = "Taiga", method: str = "fast",
                   snowinitd: float = 0.0, snowinita: float = 0.0, zref: float = 2.0, windhgt: float | None = None,
-                  stfact: float = 0.01, device: int = 0, point_device: int | None = None, one_call: bool = False) -> dict:
+                  stfact: float = 0.01, device: int = 0, point_device: int | None = None, one_call: bool = False,
+                  device_loop: bool = False) -> dict:
     """`runsnowmodel(climarrayr, micropointa, vegp, soilc, dtm, dtmc, tme, altcorrect, ...)` for array weather
     (R/Cppwrappers.R:735-757 -> `.snowmodel2`, R/internal.R:2777-3013): the snow point model once per cell of
     the climate grid (`point_device=None`: host C++, a cell at a time; an int: every cell as one batch on that device,
@@ -875,7 +876,9 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     a vector there); `method = "fast"` runs `.snowmodelq2` (R/internal.R:3017-3283) = `snow.snowmodelq2_days`.  As in the reference every climate cell needs
     data, and vegetation taller than `zref` fails (`.snowmodel2` stops at R/internal.R:2838, `climdfr` not found).
     `one_call` (subset micropoints, `method = "fast"`): the day loop as one device-resident call with the coarse arrays left
-    coarse (`snow.snowmodelq2`) instead of the host day loop; the default is unchanged."""
+    coarse (`snow.snowmodelq2`) instead of the host day loop; the default is unchanged.
+    `device_loop` (`method = "slow"`, or micropoints of the complete series): the chunk loop as one device-resident call with
+    the coarse arrays left coarse (`snow.snowmodel2_coarse`) instead of `snow.snowmodel2_chunks`; the default is unchanged."""
     from . import snow as S
     if any(m is None for m in micropointa):
         raise ValueError("every coarse cell needs a micropoint")
@@ -887,6 +890,9 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     if one_call and not fast:
         raise ValueError('one_call: the device-resident day loop is the fast method of subset micropoints (method = "fast", '
                          "subsetpointmodel's output for every climate cell)")
+    if device_loop and fast:
+        raise ValueError('device_loop: the device-resident chunk loop is the slow method (method = "slow", or micropoints of the '
+                         "complete series); the fast method's device-resident day loop is one_call=True")
     vegp = cleanvegp(vegp)
     if subset:
         zref = float(zref)
@@ -931,9 +937,10 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     sage = z * 0 + snowinita
     other = {"zref": zref, "lats": np.asarray(lats, dtype=np.float64), "lons": np.asarray(lons, dtype=np.float64),
              "isnowdc": sdep, "isnowac": sage, "isnowdg": sdep * 0.5, "isnowag": sage}
-    out = S.snowmodel2_chunks(ob, clim_c, pointm_c, vg, other, snowenv, z, np.asarray(dtmc, dtype=np.float64), xres, stfact,
-                              rowpos=rowpos, colpos=colpos, altcorrect=altcorrect,
-                              agg=10 if xres <= 100 and min(cr, cc) >= 10 else 1, device=device)
+    loop = S.snowmodel2_coarse if device_loop else S.snowmodel2_chunks
+    out = loop(ob, clim_c, pointm_c, vg, other, snowenv, z, np.asarray(dtmc, dtype=np.float64), xres, stfact,
+               rowpos=rowpos, colpos=colpos, altcorrect=altcorrect,
+               agg=10 if xres <= 100 and min(cr, cc) >= 10 else 1, device=device)
     if subset:
         i = np.asarray(last["subs"], dtype=np.int64) - 1
         out = {k: v[:, :, i] for k, v in out.items()}

@@ -659,7 +659,7 @@ def snowmodel2_chunks(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc
     swdown, difrad, lwdown, precip, windspeed [crows, ccols, T] and winddir [T] (degrees, the same in every cell as `.todf`
     makes it); `pointm_c`: Gp, Tc, RswabsG, RlwabsG, umu, tr; `vegp`: `.sortl`'s means; `other`: zref, lats, lons, isnowdc,
     isnowdg, isnowac, isnowag.  Reference behaviours kept: `other$isnowdg` is never updated, the aggregation factor of the
-    position index is at least 2, `1:n5days` truncates."""
+    position index is at least 2, `1:n5days` truncates.  The device-resident form of this loop is `snowmodel2_coarse`."""
     from . import terrain as T
     from .rformulas import upsample_coarse
     z = np.asarray(dtm, dtype=np.float64)
@@ -710,7 +710,103 @@ def snowmodel2_chunks(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc
     return out
 
 
-APPLY_FUNS = {"mean": 0, "sum": 1, "max": 2, "min": 3}
+def marshal_snowcoarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect=0, agg=10,
+                       chunk_steps=120):
+    """-> (the marshalling that keeps the arrays alive, mcf_snowcoarse_in, the one wind direction per step) for
+    `snowmodel2_coarse`'s arguments: the coarse arrays stay coarse; the wind components, the direction and `af_wind` are formed
+    here exactly as `snowmodel2_chunks` forms them.  `obstime` / `vegp` / `other` None: only what the expansion reads"""
+    z = np.asarray(dtm, dtype=np.float64)
+    R, Cc = z.shape
+    cr, cc, T = np.shape(clim_c["temp"])
+    m = SnowMarshalled()
+    m.rows, m.cols, m.tsteps = R, Cc, T
+    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
+    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
+    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
+    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
+    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
+    cin = _abi.SnowCoarseIn()
+    si = cin.drv.base
+    si.rows, si.cols, si.tsteps, si.array_forcing = R, Cc, T, 1
+    cin.drv.dtm = m.f64(z, (R, Cc), "dtm")
+    cin.coarse_rows, cin.coarse_cols, cin.altcorrect = cr, cc, int(altcorrect)
+    cin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
+    cin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
+    cin.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
+    arrays = dict(clim_c, windu=wu_c, windv=wv_c, **{k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu")})
+    for k in _abi.SNOWFAST2_SELECTED:
+        setattr(cin, k, m.f64(arrays[k], (cr, cc, T), k))
+    if obstime is None:
+        return m, cin, winddir
+    if len(np.asarray(obstime["year"])) != T:
+        raise ValueError("obstime must name every step of the coarse arrays")
+    si.snowenv = _abi.SNOWENV.get(snowenv, 0)
+    si.obstime.year = m.i32(obstime["year"], (T,), "obstime$year")
+    si.obstime.month = m.i32(obstime["month"], (T,), "obstime$month")
+    si.obstime.day = m.i32(obstime["day"], (T,), "obstime$day")
+    si.obstime.hour = m.f64(obstime["hour"], (T,), "obstime$hour")
+    si.clim.winddir = m.f64(winddir, (T,), "winddir")
+    for f in ("pai", "hgt", "leaft", "clump"):
+        v = np.asarray(vegp[f], dtype=np.float64)
+        setattr(si.vegp, f, m.f64(np.where(np.isnan(v), 0.001, v) if f == "leaft" else v, (R, Cc), f"vegp${f}"))
+    o = si.other
+    o.zref = float(other["zref"])
+    o.lat = o.lon = float("nan")
+    o.lats = m.f64(_get(other, "lats", "lat"), (R, Cc), "other$lats")
+    o.lons = m.f64(_get(other, "lons", "lon"), (R, Cc), "other$lons")
+    o.isnowdc = m.f64(other["isnowdc"], (R, Cc), "other$isnowdc")
+    o.isnowdg = m.f64(other["isnowdg"], (R, Cc), "other$isnowdg")
+    o.isnowac = m.i32(other["isnowac"], (R, Cc), "other$isnowac")
+    o.isnowag = m.i32(other["isnowag"], (R, Cc), "other$isnowag")
+    cin.drv.res, cin.drv.tfact, cin.drv.chunk_steps = float(res), float(tfact), int(chunk_steps)
+    cin.drv.af_wsa_s = int(agg)
+    cin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (T,), "af_wind")
+    return m, cin, winddir
+
+
+def snowmodel2_coarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact=0.02, *, rowpos, colpos,
+                      altcorrect: int = 0, agg: int = 10, chunk_steps: int = 120, series: Sequence[str] | None = None,
+                      device: int = 0) -> dict:
+    """`snowmodel2_chunks` as ONE device-resident call (include/mcf.h mcf_snowmodel2_coarse): the same arguments, the same
+    six-entry list.  The fourteen coarse arrays are uploaded once and stay coarse; per chunk one kernel expands the chunk's
+    thirteen series on the raster into the buffers the snow kernel reads, and the chunk loop of `snowmodel2_device` (terrain
+    refresh, gridmodelsnow2, position index, redistribution, hand-over) runs on them; only the wanted series come back.
+    `series`: the names to return (default all six: Tc, Tg, groundsnowdepth, totalSWE, snowden, umu), as for `snowmodelq2`.
+    Unlike the host loop a series shorter than one chunk runs as one short chunk (the library's `1:n5days`).  What the library
+    refuses raises _abi.McfError with its message."""
+    lib = _abi.load()
+    m, cin, _ = marshal_snowcoarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect, agg,
+                                   chunk_steps)
+    names = _abi.SNOWFAST2_OUT if series is None else tuple(series)
+    if not names or any(k not in _abi.SNOWFAST2_OUT for k in names):
+        raise ValueError(f"series: names out of {_abi.SNOWFAST2_OUT}")
+    out, arrays = _abi.SnowFast2Out(), {}
+    for k in _abi.SNOWFAST2_OUT:
+        if k in names:
+            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    _abi.check(lib.mcf_snowmodel2_coarse(C.byref(cin), C.byref(out), device))
+    return arrays
+
+
+def expand_coarse(clim_c, pointm_c, dtm, dtmc, *, rowpos, colpos, altcorrect: int = 0, step0: int = 0, nsteps: int | None = None,
+                  device: int = 0):
+    """Steps step0 .. step0 + nsteps - 1 (default: to the end) of the coarse climate and snow point-model arrays on the fine
+    raster by the chunk kernel of `snowmodel2_coarse` alone (include/mcf.h mcf_snow_expand_coarse_device): -> (clim, pointm)
+    as `_fine_snow_inputs` returns them (without `tr`), [rows, cols, nsteps] each and `winddir` [nsteps] — what
+    `snowmodel2_device` takes"""
+    lib = _abi.load()
+    m, cin, winddir = marshal_snowcoarse(None, clim_c, pointm_c, None, None, None, dtm, dtmc, 1.0, 0.0, rowpos, colpos, altcorrect)
+    n = m.tsteps - step0 if nsteps is None else int(nsteps)
+    fine = {k: np.empty((m.rows, m.cols, max(n, 0)), dtype=np.float64, order="F") for k in _abi.SNOW_FINE_SERIES}
+    ptrs = (_abi.c_double_p * 13)(*[fine[k].ctypes.data_as(_abi.c_double_p) for k in _abi.SNOW_FINE_SERIES])
+    _abi.check(lib.mcf_snow_expand_coarse_device(C.byref(cin), C.c_int64(step0), C.c_int64(n), ptrs, device))
+    clim = {k: fine[k] for k in _abi.SNOW_FINE_SERIES[:8]}
+    clim["winddir"] = winddir[step0:step0 + n]
+    return clim, {k: fine[k] for k in _abi.SNOW_FINE_SERIES[8:]}
+
+
+APPLY_FUNS ={"mean": 0, "sum": 1, "max": 2, "min": 3}
 
 
 def applycpp3(a, fun_name: str, *, device: int = 0, with_count: bool = False):
