@@ -17,6 +17,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -2300,6 +2301,204 @@ double day_af(const double* wind24, double res) {
 
 constexpr int kTpiCache = 8;    // position indices kept per call, one per distinct af (a [rows, cols] raster each)
 
+// What both fast methods refuse about `subs` and the days' aggregation factors.  wind / windname: the series of the selected
+// hours the factor is formed from; first_day: the refusal of a first selected day that is the series' first (null: the method
+// runs it).
+int subs_af_checks(const char* entry, const int64_t* subs, int64_t n, int64_t n_all, const char* first_day, const double* wind,
+                   const char* windname, double res) {
+    char m[240];
+    for (int64_t k = 0; k < n; ++k) {
+        if (subs[k] < 1 || subs[k] > n_all) {
+            snprintf(m, sizeof m, "%s: subs[%lld] = %lld is outside 1..n_all = %lld", entry, (long long)k, (long long)subs[k], (long long)n_all);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+        if (k && subs[k] <= subs[k - 1]) {
+            snprintf(m, sizeof m, "%s: subs is not increasing at position %lld", entry, (long long)k);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    }
+    if (first_day && subs[0] - 1 <= 1) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": " + first_day);
+    for (int64_t d = 0; d < n / 24; ++d)
+        if (!(day_af(wind + 24 * d, res) >= 1.0)) {
+            snprintf(m, sizeof m, "%s: aggregation factor round(10*sqrt(mean %s)/res) of selected day %lld is 0 (terra::aggregate fails)",
+                     entry, windname, (long long)d);
+            return mcf::api_fail(MCF_ERR_ARG, m);
+        }
+    return MCF_OK;
+}
+
+// ---- the day loop of the fast methods ------------------------------------------------------------------------------------------
+// What a selected day computes into, [N][24] each (null: not wanted; umu: array weather only).  There are two sets: day d + 1
+// computes into one while day d's wanted series leave the other.
+struct DaySet { double *Tc = nullptr, *Tg = nullptr, *sdepc = nullptr, *sdepg = nullptr, *sden = nullptr, *umu = nullptr; };
+// One of a method's own steps of a selected day: launches only, on the stream handed to it.  name: its sum in the MCF_TIMING line.
+struct DayStage {
+    const char* name;
+    std::function<void(int day, const DaySet& set, hipStream_t stream)> launch;
+};
+// Everything `.snowmodelq1` and `.snowmodelq2` do alike.  The constructor plans on the host; prepare() puts the dtm and the
+// pack depth on the device and makes what no day changes; run() is the loop over the selected days:
+//     the method's stages | the day's position index | k_day_redistribute | the method's stages behind it
+// on one stream, day d - 1's wanted series leaving meanwhile.  What differs between the methods is a stage or a value handed in.
+struct DayLoop {
+    int64_t rows, cols, N, cm_cells = 1;
+    int D, nsets, nser, nslots;                  // selected days; output sets; series per set; position indices kept
+    std::vector<int> af;                         // per day: round(10 sqrt(mean wind) / res)
+    const mcf_snowdriver_in& drv;
+    double* hostv[6];                            // the caller's Tc, Tg, groundsnowdepth, totalSWE, snowden, umu (null: not wanted)
+    bool want_den, timing;
+    const double* d_dtm = nullptr;
+    double *d_dc = nullptr, *d_dg = nullptr;     // the pack and ground depths a day starts from, handed on by k_day_redistribute
+    double *d_slope = nullptr, *d_aspect = nullptr, *d_svf = nullptr, *d_wsa = nullptr, *d_hor = nullptr;
+    double *d_ws = nullptr, *d_m2 = nullptr, *d_cm = nullptr;   // launch_sumcount's and tpi_raster's scratch
+    double zmean = 0.0;                          // mean(dtm, na.rm = TRUE): `.tpicalc`'s raster-mean branch
+    Events tev;                                  // around the terrain
+
+    // wind: the series of the selected hours the aggregation factors are formed from
+    DayLoop(const mcf_snowdriver_in& drv_, const double* wind, const mcf_snowdriver_out& sm, double* umu)
+        : rows(drv_.base.rows), cols(drv_.base.cols), N(rows * cols), D((int)(drv_.base.tsteps / 24)), nsets(std::min(2, D)), af((size_t)D),
+          drv(drv_), hostv{sm.Tc, sm.Tg, sm.groundsnowdepth, sm.totalSWE, sm.snowden, umu}, want_den(sm.snowden || sm.totalSWE),
+          timing(getenv("MCF_TIMING") != nullptr) {
+        nser = 2 + (sm.Tc != nullptr) + (sm.Tg != nullptr) + want_den + (umu != nullptr);
+        // the distinct factors, in the order they are met, share the cache's slots
+        std::vector<int> distinct;
+        for (int d = 0; d < D; ++d) {
+            af[(size_t)d] = (int)std::min(day_af(wind + 24 * d, drv.res), 1e9);
+            if (std::find(distinct.begin(), distinct.end(), af[(size_t)d]) == distinct.end()) distinct.push_back(af[(size_t)d]);
+            if (tpi_is_coarse(rows, cols, af[(size_t)d])) cm_cells = std::max(cm_cells, tpi_coarse_cells(rows, cols, af[(size_t)d]));
+        }
+        nslots = (int)std::min<size_t>(kTpiCache, distinct.size());
+    }
+
+    // dtm and isnowdc up, the terrain of the bare dtm (int:2690-2706, 3171-3190: it does not change between the days) and its mean
+    int prepare(mcf::DevOwner& b, ModelArgs& a) {
+        int rc;
+        if ((rc = b.up(&d_dtm, drv.dtm, N, "dtm"))) return rc;
+        if ((rc = b.up_mut(&d_dc, drv.base.other.isnowdc, N, "other$isnowdc"))) return rc;
+        double** const per_cell[] = {&d_dg, &d_slope, &d_aspect, &d_svf};
+        for (double** q : per_cell)
+            if ((rc = b.make(q, N))) return rc;
+        if ((rc = b.make(&d_wsa, 8 * N))) return rc;
+        if ((rc = b.make(&d_hor, 24 * N))) return rc;
+        if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
+        if ((rc = b.make(&d_m2, 2))) return rc;
+        if ((rc = b.make(&d_cm, cm_cells))) return rc;
+        a.isnowdc = d_dc; a.isnowdg = d_dg;
+        a.slope = d_slope; a.aspect = d_aspect; a.skyview = d_svf; a.wsa = d_wsa; a.hor = d_hor;
+        if (timing) { HIP_TRY(tev.make(2)); HIP_TRY(hipEventRecord(tev.e[0], nullptr)); }
+        mcf::TerrainDev td;
+        memset(&td, 0, sizeof td);
+        td.rows = rows; td.cols = cols; td.row0 = 0; td.rows_total = rows;
+        td.d_dtm = d_dtm; td.res = drv.res; td.zref = drv.base.other.zref; td.agg = drv.res <= 100 ? 10 : 1; td.aspect_na = 180.0;
+        td.d_slope = d_slope; td.d_aspect = d_aspect; td.d_hor = d_hor; td.d_svfa = d_svf; td.d_wsa = d_wsa;
+        if ((rc = mcf::terrain_device(td))) return rc;
+        hipLaunchKernelGGL(k_mask2, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, d_dtm, N, d_slope, d_aspect);
+        if (timing) HIP_TRY(hipEventRecord(tev.e[1], nullptr));
+        launch_sumcount(d_dtm, N, d_ws, d_m2);
+        double h[2];
+        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        zmean = h[0] / h[1];
+        return MCF_OK;
+    }
+
+    // The selected days.  stages: in front of the day's position index, each timed under its name; behind: after the
+    // redistribution, timed with it.  entry, sizes: the head of the MCF_TIMING line ("<entry>: D days, N cells<sizes>").
+    int run(mcf::DevOwner& b, const char* entry, const std::string& sizes, const std::vector<DayStage>& stages,
+            const std::vector<DayStage>& behind) {
+        int rc;
+        const int64_t DN = 24 * N;
+        DaySet sets[2];
+        for (int s = 0; s < nsets; ++s) {
+            if (hostv[0] && (rc = b.make(&sets[s].Tc, DN))) return rc;
+            if (hostv[1] && (rc = b.make(&sets[s].Tg, DN))) return rc;
+            if ((rc = b.make(&sets[s].sdepc, DN))) return rc;
+            if ((rc = b.make(&sets[s].sdepg, DN))) return rc;
+            if (want_den && (rc = b.make(&sets[s].sden, DN))) return rc;
+            if (hostv[5] && (rc = b.make(&sets[s].umu, DN))) return rc;
+        }
+        // `.tpicalc` of the bare dtm (the depth the reference stacks on it is still zero when read, int:2753) per distinct af
+        struct Slot { int af = 0; double* tpi = nullptr; } slots[kTpiCache];
+        for (int s = 0; s < nslots; ++s)
+            if ((rc = b.make(&slots[s].tpi, N))) return rc;
+        int next_slot = 0, tpi_computed = 0;
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipDeviceSynchronize());
+        Streams streams;
+        hipStream_t cs, ds;                       // the days' kernels; the stream the downloads are ordered on (idle: the host waits for a set's day itself)
+        HIP_TRY(streams.make(&cs));
+        HIP_TRY(streams.make(&ds));
+        Events done;
+        HIP_TRY(done.make(2));
+        mcf::ToHost dl;
+        double t_download = 0.0;
+        auto download = [&](int d) -> hipError_t {                 // day d's wanted series, from the set it was computed into
+            hipError_t e = hipEventSynchronize(done.e[(size_t)(d & 1)]);
+            const auto t0 = std::chrono::steady_clock::now();
+            const DaySet& s = sets[d % nsets];
+            double* const devv[6] = {s.Tc, s.Tg, s.sdepg, s.sdepc, s.sden, s.umu};
+            for (int v = 0; v < 6 && e == hipSuccess; ++v)
+                if (hostv[v]) e = dl.dense(hostv[v] + (int64_t)d * DN, devv[v], (size_t)DN * 8, ds);
+            t_download += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            return e;
+        };
+        // a day's timing events: one in front of each stage, of the position index and of the redistribution, one behind
+        const int S = (int)stages.size(), E = S + 3;
+        Events evs;
+        if (timing) HIP_TRY(evs.make(E * D));
+        const unsigned gridN = (unsigned)((N + 255) / 256);
+        for (int d = 0; d < D; ++d) {
+            hipEvent_t* te = timing ? &evs.e[(size_t)(E * d)] : nullptr;
+            const DaySet& s = sets[d % nsets];
+            for (int q = 0; q < S; ++q) {
+                if (te) HIP_TRY(hipEventRecord(te[q], cs));
+                stages[(size_t)q].launch(d, s, cs);
+            }
+            if (te) HIP_TRY(hipEventRecord(te[S], cs));
+            // the day's position index: kept per af; beyond the cache's slots the oldest is computed over
+            const double* d_tpi = nullptr;
+            for (int q = 0; q < nslots; ++q)
+                if (slots[q].af == af[(size_t)d]) d_tpi = slots[q].tpi;
+            if (!d_tpi) {
+                Slot& sl = slots[next_slot];
+                next_slot = (next_slot + 1) % nslots;
+                sl.af = af[(size_t)d];
+                tpi_raster(d_dtm, rows, cols, sl.af, drv.tfact, zmean, sl.tpi, d_ws, d_m2, d_cm, cs);
+                d_tpi = sl.tpi;
+                ++tpi_computed;
+            }
+            if (te) HIP_TRY(hipEventRecord(te[S + 1], cs));
+            DayRedistArgs ra;
+            ra.N = N; ra.tpi = d_tpi; ra.sdepc = s.sdepc; ra.sdepg = s.sdepg; ra.sden = s.sden;
+            ra.swe = hostv[3] ? s.sdepc : nullptr; ra.gd = hostv[2] ? s.sdepg : nullptr;
+            ra.dc = d_dc; ra.dg = d_dg;
+            hipLaunchKernelGGL(k_day_redistribute, dim3(gridN), dim3(256), 0, cs, ra);
+            for (const DayStage& st : behind) st.launch(d, s, cs);
+            if (te) HIP_TRY(hipEventRecord(te[S + 2], cs));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipEventRecord(done.e[(size_t)(d & 1)], cs));
+            // the day before leaves while this one computes (with one set there is one day)
+            if (d > 0) HIP_TRY(download(d - 1));
+        }
+        HIP_TRY(download(D - 1));
+        HIP_TRY(hipDeviceSynchronize());
+        if (timing) {
+            float ms = 0;
+            std::vector<double> t((size_t)(S + 2), 0.0);
+            for (int d = 0; d < D; ++d)
+                for (int q = 0; q < S + 2; ++q) {
+                    HIP_TRY(hipEventElapsedTime(&ms, evs.e[(size_t)(E * d + q)], evs.e[(size_t)(E * d + q + 1)]));
+                    t[(size_t)q] += ms;
+                }
+            HIP_TRY(hipEventElapsedTime(&ms, tev.e[0], tev.e[1]));
+            fprintf(stderr, "[mcf] %s: %d days, %lld cells%s: terrain %.2f ms, ", entry, D, (long long)N, sizes.c_str(), ms);
+            for (int q = 0; q < S; ++q) fprintf(stderr, "%s %.2f ms, ", stages[(size_t)q].name, t[(size_t)q]);
+            fprintf(stderr, "tpi %.2f ms (%d of %d days computed), redistribute %.2f ms, downloads %.2f ms of host time\n", t[(size_t)S],
+                    tpi_computed, D, t[(size_t)S + 1], t_download * 1e3);
+        }
+        return MCF_OK;
+    }
+};
+
 int snowmodelq1_checks(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out) {
     if (!fi || !out) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: null argument");
     const mcf_snow_inputs* in = &fi->drv.base;
@@ -2320,29 +2519,9 @@ int snowmodelq1_checks(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out)
     need(fi->sdenc, "sdenc"); need(fi->sdeng, "sdeng"); need(fi->temp_all, "temp_all"); need(fi->snow_all, "snow_all");
     if (missing) return mcf::api_fail(MCF_ERR_ARG, std::string("mcf_snowmodelq1: null input: ") + missing);
     if (!(fi->drv.res > 0)) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: res must be > 0");
-    const int64_t n = in->tsteps;
-    char m[240];
-    for (int64_t k = 0; k < n; ++k) {
-        if (fi->subs[k] < 1 || fi->subs[k] > fi->n_all) {
-            snprintf(m, sizeof m, "mcf_snowmodelq1: subs[%lld] = %lld is outside 1..n_all = %lld", (long long)k, (long long)fi->subs[k],
-                     (long long)fi->n_all);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-        if (k && fi->subs[k] <= fi->subs[k - 1]) {
-            snprintf(m, sizeof m, "mcf_snowmodelq1: subs is not increasing at position %lld", (long long)k);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-    }
-    if (fi->subs[0] - 1 <= 1)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq1: the fast snow method cannot start on the first day of the series (the reference "
-                                          "fails there: `sbtn` not found)");
-    for (int64_t d = 0; d < n / 24; ++d)
-        if (!(day_af(in->clim.windspeed + 24 * d, fi->drv.res) >= 1.0)) {
-            snprintf(m, sizeof m, "mcf_snowmodelq1: aggregation factor round(10*sqrt(mean wind)/res) of selected day %lld is 0 "
-                     "(terra::aggregate fails)", (long long)d);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-    return MCF_OK;
+    return subs_af_checks("mcf_snowmodelq1", fi->subs, in->tsteps, fi->n_all,
+                          "the fast snow method cannot start on the first day of the series (the reference fails there: `sbtn` not found)",
+                          in->clim.windspeed, "wind", fi->drv.res);
 }
 
 int snowmodelq1(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out, int32_t device) {
@@ -2350,26 +2529,10 @@ int snowmodelq1(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out, int32_
     if ((rc = snowmodelq1_checks(fi, out))) return rc;      // nothing above needs a device
     const mcf_snow_inputs* in = &fi->drv.base;
     if ((rc = pick_device(device))) return rc;
-    const int64_t rows = in->rows, cols = in->cols, N = rows * cols, n_all = fi->n_all;
-    const int T = (int)in->tsteps, D = T / 24;
-    const int64_t DN = 24 * N;
-    // which series leave the call; what the day's kernels must write for them and for the hand-over
-    double* const hostv[5] = {out->Tc, out->Tg, out->groundsnowdepth, out->totalSWE, out->snowden};
-    const bool want_den = out->snowden || out->totalSWE;
-    const int nsets = std::min(2, D);
-    const int nser = 2 + (out->Tc != nullptr) + (out->Tg != nullptr) + want_den;
-    // every day's aggregation factor; the distinct ones, in the order they are met, share the cache's slots
-    std::vector<int> af((size_t)D);
-    std::vector<int> distinct;
-    int64_t cm_cells = 1;
-    for (int d = 0; d < D; ++d) {
-        af[(size_t)d] = (int)std::min(day_af(in->clim.windspeed + 24 * d, fi->drv.res), 1e9);
-        if (std::find(distinct.begin(), distinct.end(), af[(size_t)d]) == distinct.end()) distinct.push_back(af[(size_t)d]);
-        if (tpi_is_coarse(rows, cols, af[(size_t)d])) cm_cells = std::max(cm_cells, tpi_coarse_cells(rows, cols, af[(size_t)d]));
-    }
-    const int nslots = (int)std::min<size_t>(kTpiCache, distinct.size());
-    if ((rc = check_room((64 + nslots + (int64_t)nsets * nser * 24) * N * 8 + (2 * n_all + cm_cells) * 8))) return rc;
-    const bool timing = getenv("MCF_TIMING") != nullptr;
+    const int64_t N = in->rows * in->cols, n_all = fi->n_all;
+    const int T = (int)in->tsteps;
+    DayLoop L(fi->drv, in->clim.windspeed, *out, nullptr);
+    if ((rc = check_room((64 + L.nslots + (int64_t)L.nsets * L.nser * 24) * N * 8 + (2 * n_all + L.cm_cells) * 8))) return rc;
     mcf::DevOwner b;
     ModelArgs a;
     memset(&a, 0, sizeof a);
@@ -2380,43 +2543,21 @@ int snowmodelq1(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out, int32_
         if (!rc && !terrain && strcmp(name, "other$isnowdc") && strcmp(name, "other$isnowdg")) rc = b.up(&(a.*member), host, N, name);
     });
     if (rc) return rc;
-    const double *d_dtm, *d_st, *d_ta;
-    double *d_dc, *d_dg, *d_intfrac, *d_slope, *d_aspect, *d_svf, *d_wsa, *d_hor, *d_ws, *d_m2, *d_cm;
-    if ((rc = b.up(&d_dtm, fi->drv.dtm, N, "dtm"))) return rc;
-    if ((rc = b.up_mut(&d_dc, in->other.isnowdc, N, "other$isnowdc"))) return rc;
+    if ((rc = L.prepare(b, a))) return rc;
+    const double *d_st, *d_ta;
+    double* d_intfrac;
     if ((rc = b.up(&d_st, fi->sstemp, n_all, "sstemp"))) return rc;
     if ((rc = b.up(&d_ta, fi->temp_all, n_all, "temp_all"))) return rc;
-    double** const per_cell[] = {&d_dg, &d_intfrac, &d_slope, &d_aspect, &d_svf};
-    for (double** q : per_cell)
-        if ((rc = b.make(q, N))) return rc;
-    if ((rc = b.make(&d_wsa, 8 * N))) return rc;
-    if ((rc = b.make(&d_hor, 24 * N))) return rc;
-    if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
-    if ((rc = b.make(&d_m2, 2))) return rc;
-    if ((rc = b.make(&d_cm, cm_cells))) return rc;
-    a.isnowdc = d_dc; a.isnowdg = d_dg;
-    a.slope = d_slope; a.aspect = d_aspect; a.skyview = d_svf; a.wsa = d_wsa; a.hor = d_hor;
+    if ((rc = b.make(&d_intfrac, N))) return rc;
     const unsigned gridN = (unsigned)((N + 255) / 256);
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2 + 5 * D)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
-    // terrain of the bare dtm (int:2690-2706): it does not change between the days
-    {
-        mcf::TerrainDev td;
-        memset(&td, 0, sizeof td);
-        td.rows = rows; td.cols = cols; td.row0 = 0; td.rows_total = rows;
-        td.d_dtm = d_dtm; td.res = fi->drv.res; td.zref = in->other.zref; td.agg = fi->drv.res <= 100 ? 10 : 1; td.aspect_na = 180.0;
-        td.d_slope = d_slope; td.d_aspect = d_aspect; td.d_hor = d_hor; td.d_svfa = d_svf; td.d_wsa = d_wsa;
-        if ((rc = mcf::terrain_device(td))) return rc;
-        hipLaunchKernelGGL(k_mask2, dim3(gridN), dim3(256), 0, nullptr, d_dtm, N, d_slope, d_aspect);
-    }
-    if (timing) HIP_TRY(hipEventRecord(evs.e[1], nullptr));
     // the step table of all selected hours; every day's gridmodelsnow1 call restarts the albedo clock (snowalbCpp on its slice)
     StepTables tabs;
     if ((rc = build_step_tables(b, in, false, true, true, &tabs))) return rc;
     {
         const double* d_prec;
         if ((rc = b.up(&d_prec, in->clim.precip, T, "climdata$precip"))) return rc;
-        hipLaunchKernelGGL(k_snow_alb_chunks, dim3((unsigned)((D + 63) / 64)), dim3(64), 0, nullptr, const_cast<StepRow*>(tabs.rows), d_prec, T, 24, D);
+        hipLaunchKernelGGL(k_snow_alb_chunks, dim3((unsigned)((L.D + 63) / 64)), dim3(64), 0, nullptr, const_cast<StepRow*>(tabs.rows), d_prec, T, 24,
+                           L.D);
     }
     // intfrac of a typical snowfall and the ground layer's share of the initial depth (int:2708-2716)
     {
@@ -2427,120 +2568,34 @@ int snowmodelq1(const mcf_snowfast_in* fi, const mcf_snowdriver_out* out, int32_
         for (int k = 0; k < T; ++k) tsum += in->clim.temp[k];
         CanIntArgs ca;
         ca.N = N; ca.hgt = a.hgt; ca.pai = a.pai; ca.uf = 2.0; ca.prec = scount ? ssum / (double)scount : NAN;
-        ca.sint = canopy_sint(tsum / T); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = d_dc; ca.dg = d_dg;
+        ca.sint = canopy_sint(tsum / T); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = L.d_dc; ca.dg = L.d_dg;
         hipLaunchKernelGGL(k_canintfrac, dim3(gridN), dim3(256), 0, nullptr, ca);
     }
-    // mean(dtm, na.rm = TRUE): `.tpicalc`'s raster-mean branch
-    double zmean = 0.0;
-    {
-        launch_sumcount(d_dtm, N, d_ws, d_m2);
-        double h[2];
-        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
-        zmean = h[0] / h[1];
-    }
-    // the day's series, twice: day d + 1 computes into one set while day d's leaves the other
-    struct Set { double *Tc = nullptr, *Tg = nullptr, *sdepc = nullptr, *sdepg = nullptr, *sden = nullptr; } sets[2];
-    for (int s = 0; s < nsets; ++s) {
-        if (out->Tc && (rc = b.make(&sets[s].Tc, DN))) return rc;
-        if (out->Tg && (rc = b.make(&sets[s].Tg, DN))) return rc;
-        if ((rc = b.make(&sets[s].sdepc, DN))) return rc;
-        if ((rc = b.make(&sets[s].sdepg, DN))) return rc;
-        if (want_den && (rc = b.make(&sets[s].sden, DN))) return rc;
-    }
-    // `.tpicalc` of the bare dtm (the depth the reference stacks on it is still zero when read, int:2753) per distinct af
-    struct Slot { int af = 0; double* tpi = nullptr; } slots[kTpiCache];
-    for (int s = 0; s < nslots; ++s)
-        if ((rc = b.make(&slots[s].tpi, N))) return rc;
-    int next_slot = 0, tpi_computed = 0;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    Streams streams;
-    hipStream_t cs, ds;                       // the days' kernels; the stream the downloads are ordered on (idle: the host waits for a set's day itself)
-    HIP_TRY(streams.make(&cs));
-    HIP_TRY(streams.make(&ds));
-    Events done;
-    HIP_TRY(done.make(2));
-    mcf::ToHost dl;
-    double t_download = 0.0;
-    auto download = [&](int d) -> hipError_t {                 // day d's wanted series, from the set it was computed into
-        hipError_t e = hipEventSynchronize(done.e[(size_t)(d & 1)]);
-        const auto t0 = std::chrono::steady_clock::now();
-        const Set& s = sets[d % nsets];
-        double* const devv[5] = {s.Tc, s.Tg, s.sdepg, s.sdepc, s.sden};
-        for (int v = 0; v < 5 && e == hipSuccess; ++v)
-            if (hostv[v]) e = dl.dense(hostv[v] + (int64_t)d * DN, devv[v], (size_t)DN * 8, ds);
-        t_download += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return e;
-    };
-    for (int d = 0; d < D; ++d) {
-        hipEvent_t* te = timing ? &evs.e[(size_t)(2 + 5 * d)] : nullptr;
-        if (te) HIP_TRY(hipEventRecord(te[0], cs));
+    auto gap_balance = [&](int d, const DaySet&, hipStream_t cs) {
         // the gap's scalars, in plain left-to-right order over R's `sbtn`
         const Gap g = gap_of_day(fi->subs, d);
+        double sub = 0.0, rain = 0.0, tm = 0.0, fall = 0.0, sc = 0.0, sg = 0.0, dhp = 0.0;
+        for (int64_t k = 0; k < g.len; ++k) {
+            const int64_t i = g.start + g.step * k;
+            sub += fi->sublmelt[i]; rain += fi->rainmelt[i]; tm += fi->tempmelt[i]; fall += fi->snow_all[i] / 1000;
+            sc += fi->sdenc[i]; sg += fi->sdeng[i];
+            if (fi->sstemp[i] > 0.0) dhp += fi->sstemp[i];
+        }
         GapArgs ga;
         memset(&ga, 0, sizeof ga);
-        {
-            double sub = 0.0, rain = 0.0, tm = 0.0, fall = 0.0, sc = 0.0, sg = 0.0, dhp = 0.0;
-            for (int64_t k = 0; k < g.len; ++k) {
-                const int64_t i = g.start + g.step * k;
-                sub += fi->sublmelt[i]; rain += fi->rainmelt[i]; tm += fi->tempmelt[i]; fall += fi->snow_all[i] / 1000;
-                sc += fi->sdenc[i]; sg += fi->sdeng[i];
-                if (fi->sstemp[i] > 0.0) dhp += fi->sstemp[i];
-            }
-            ga.N = N; ga.start = g.start; ga.len = g.len; ga.step = g.step;
-            ga.dhp = dhp; ga.subrain = sub + rain; ga.tempmelt = tm; ga.fall = fall;
-            ga.kc = 1000 / (sc / (double)g.len); ga.kg = 1000 / (sg / (double)g.len);
-            ga.skyview = d_svf; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.dc = d_dc; ga.dg = d_dg; ga.mu = nullptr;
-        }
+        ga.N = N; ga.start = g.start; ga.len = g.len; ga.step = g.step;
+        ga.dhp = dhp; ga.subrain = sub + rain; ga.tempmelt = tm; ga.fall = fall;
+        ga.kc = 1000 / (sc / (double)g.len); ga.kg = 1000 / (sg / (double)g.len);
+        ga.skyview = L.d_svf; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.dc = L.d_dc; ga.dg = L.d_dg; ga.mu = nullptr;
         hipLaunchKernelGGL(k_gap_balance, dim3(gridN), dim3(256), 0, cs, ga, d_st, d_ta);
-        if (te) HIP_TRY(hipEventRecord(te[1], cs));
-        // gridmodelsnow1 on the day's 24 rows, from the depths just formed and the caller's ages (they are not handed on)
-        const Set& s = sets[d % nsets];
+    };
+    // gridmodelsnow1 on the day's 24 rows, from the depths just formed and the caller's ages (they are not handed on)
+    auto model = [&](int d, const DaySet& s, hipStream_t cs) {
         a.rows = tabs.rows + 24 * d;
         a.Tc = s.Tc; a.Tg = s.Tg; a.sdepc = s.sdepc; a.sdepg = s.sdepg; a.sden = s.sden;
         hipLaunchKernelGGL(k_snowmodel<false>, dim3(gridN), dim3(256), 0, cs, a, a.rows, a.dates);
-        if (te) HIP_TRY(hipEventRecord(te[2], cs));
-        // the day's position index: kept per af; beyond the cache's slots the oldest is computed over
-        const double* d_tpi = nullptr;
-        for (int q = 0; q < nslots; ++q)
-            if (slots[q].af == af[(size_t)d]) d_tpi = slots[q].tpi;
-        if (!d_tpi) {
-            Slot& sl = slots[next_slot];
-            next_slot = (next_slot + 1) % nslots;
-            sl.af = af[(size_t)d];
-            tpi_raster(d_dtm, rows, cols, sl.af, fi->drv.tfact, zmean, sl.tpi, d_ws, d_m2, d_cm, cs);
-            d_tpi = sl.tpi;
-            ++tpi_computed;
-        }
-        if (te) HIP_TRY(hipEventRecord(te[3], cs));
-        DayRedistArgs ra;
-        ra.N = N; ra.tpi = d_tpi; ra.sdepc = s.sdepc; ra.sdepg = s.sdepg; ra.sden = s.sden;
-        ra.swe = out->totalSWE ? s.sdepc : nullptr; ra.gd = out->groundsnowdepth ? s.sdepg : nullptr;
-        ra.dc = d_dc; ra.dg = d_dg;
-        hipLaunchKernelGGL(k_day_redistribute, dim3(gridN), dim3(256), 0, cs, ra);
-        if (te) HIP_TRY(hipEventRecord(te[4], cs));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(done.e[(size_t)(d & 1)], cs));
-        // the day before leaves while this one computes (with one set there is one day)
-        if (d > 0) HIP_TRY(download(d - 1));
-    }
-    HIP_TRY(download(D - 1));
-    HIP_TRY(hipDeviceSynchronize());
-    if (timing) {
-        float ms = 0;
-        double t[4] = {0, 0, 0, 0};
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        const double t_terrain = ms;
-        for (int d = 0; d < D; ++d)
-            for (int q = 0; q < 4; ++q) {
-                HIP_TRY(hipEventElapsedTime(&ms, evs.e[(size_t)(2 + 5 * d + q)], evs.e[(size_t)(2 + 5 * d + q + 1)]));
-                t[q] += ms;
-            }
-        fprintf(stderr, "[mcf] snowmodelq1: %d days, %lld cells: terrain %.2f ms, gap balance %.2f ms, gridmodelsnow %.2f ms, tpi %.2f ms "
-                "(%d of %d days computed), redistribute %.2f ms, downloads %.2f ms of host time\n", D, (long long)N, t_terrain, t[0], t[1],
-                t[2], tpi_computed, D, t[3], t_download * 1e3);
-    }
-    return MCF_OK;
+    };
+    return L.run(b, "snowmodelq1", "", {{"gap balance", gap_balance}, {"gridmodelsnow", model}}, {});
 }
 }  // namespace
 
@@ -2697,8 +2752,8 @@ __device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double 
     const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
     return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
 }
-// A selected day's thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py _fine_snow_inputs), [24][N] as
-// k_snowmodel<true> reads them, one lane per cell.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
+// A selected day's (or a chunk's) thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py
+// _fine_snow_inputs), [hours][N] as k_snowmodel<true> reads them.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
 // are not masked.  altcorrect > 0: `pres` holds the coarse pressure already taken to sea level (the host divides by the
 // coarse cell's factor), the cell's own factor brings it back up; the temperature moves by elevd x lapse rate, relative
 // humidity keeps the vapour pressure of the uncorrected field; capped at 100.  `umu` is the day's slab of the output set when
@@ -2712,10 +2767,9 @@ struct FineArgs {
     double *o_temp, *o_relhum, *o_pres, *o_swdown, *o_difrad, *o_lwdown, *o_windspeed, *o_precip, *o_Gp, *o_Tc, *o_RswabsG, *o_RlwabsG,
         *o_umu;
 };
-__global__ __launch_bounds__(256) void k_fine_day(FineArgs a) {
+// hours kb .. ke - 1 of cell c's thirteen series into [.][N]: the arithmetic, whose bits tests rely on
+__device__ __forceinline__ void fine_cell_hours(const FineArgs& a, int64_t c, int kb, int ke) {
 #pragma clang fp contract(off)
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N) return;
     const SnowTap tap = a.geo.tap(c);
     const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
     const double z = a.dtm[c], NA = na_real();
@@ -2725,7 +2779,7 @@ __global__ __launch_bounds__(256) void k_fine_day(FineArgs a) {
         up = pow((293 - 0.0065 * z) / 293, 5.26);
         elevd = tap(a.zc) - z;
     }
-    for (int k = 0; k < 24; ++k) {
+    for (int k = kb; k < ke; ++k) {
         const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
         auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
         double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
@@ -2745,6 +2799,26 @@ __global__ __launch_bounds__(256) void k_fine_day(FineArgs a) {
         a.o_umu[o] = cca(a.umu);
     }
 }
+// The thirteen series of the hours a.hour0 .. a.hour0 + ns - 1 into [ns][N]: a selected day of the fast method (ns = 24) or a
+// chunk of the slow one.  Lanes run along the cells (a wave stores 512 contiguous bytes per series and hour), blockIdx.y over
+// groups of kFineHours hours: a lane forms its tap, its pressure factor and elevd once and walks its group.  Five hours: the
+// 120-hour chunk of the bundled 50 x 50 raster is 10 x 24 = 240 workgroups on 256 CUs where one lane per cell would be 10, the
+// lane's set-up (two position loads, one pow with altcorrect) is spread over 5 x 14 taps, and a chunk of whole days (24, 48, 120
+// hours; 24 is no multiple of 5) ends in a partial group, so the partial path is the everyday one.  g0: the first group of
+// this launch (the grid's y extent is 16 bits).
+constexpr int kFineHours = 5;
+__global__ __launch_bounds__(256) void k_fine_chunk(FineArgs a, int ns, int g0) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    fine_cell_hours(a, c, kb, ke);
+}
+void launch_fine_chunk(const FineArgs& fa, int ns, hipStream_t stream) {
+    const int groups = (ns + kFineHours - 1) / kFineHours;
+    for (int g0 = 0; g0 < groups; g0 += 32768)
+        hipLaunchKernelGGL(k_fine_chunk, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, stream,
+                           fa, ns, g0);
+}
 // one coarse plane on the raster, NA on the dtm's holes (mean(cca(tc), na.rm = TRUE) is the mean of this of tc's time sums)
 __global__ __launch_bounds__(256) void k_tap_plane(CoarseGeo geo, int64_t N, const double* __restrict__ dtm, const double* __restrict__ plane,
                                                    double* __restrict__ out) {
@@ -2753,23 +2827,24 @@ __global__ __launch_bounds__(256) void k_tap_plane(CoarseGeo geo, int64_t N, con
     const double v = geo.tap(c)(plane);
     out[c] = isnan(dtm[c]) ? na_real() : v;
 }
-// `.cleansmod`: NA on the dtm's holes in the day's series that leave, [24][N] each (null: not wanted)
+// `.cleansmod`: NA on the dtm's holes in the series that leave, [ns][N] each (null: not written); holes are few, a lane walks
+// its cell's steps
 struct CleanArgs {
     int64_t N;
     const double* dtm;
     double* v[5];
 };
-__global__ __launch_bounds__(256) void k_clean_day(CleanArgs a) {
+__global__ __launch_bounds__(256) void k_clean_chunk(CleanArgs a, int ns) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.N || !isnan(a.dtm[c])) return;
     const double NA = na_real();
 #pragma unroll
     for (int q = 0; q < 5; ++q)
         if (a.v[q])
-            for (int k = 0; k < 24; ++k) a.v[q][c + a.N * k] = NA;
+            for (int k = 0; k < ns; ++k) a.v[q][c + a.N * k] = NA;
 }
 
-// the coarse arrays of the selected hours, in the order k_fine_day's arguments list them
+// the coarse arrays of the selected hours, in the order k_fine_chunk's arguments list them
 template <class In, class F>
 void each_coarse_selected(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
     using A = FineArgs;
@@ -2784,6 +2859,39 @@ bool positions_inside(const double* pos, int64_t n, int64_t ncoarse) {
     for (int64_t i = 0; i < n; ++i)
         if (!(pos[i] >= 0.0 && pos[i] <= (double)(ncoarse - 1))) return false;
     return true;
+}
+
+// geometry, dtm and the coarse arrays of hours h0 .. h0 + nh - 1 on the device (pressure taken to sea level on the coarse grid by
+// the host when altcorrect > 0, int:2871-2873, 3127-3129); d_dtm: the raster's dtm if the caller has it there already.
+// In: mcf_snowfast2_in or mcf_snowcoarse_in
+template <class In>
+int coarse_upload(mcf::DevOwner& b, const In* ci, int64_t h0, int64_t nh, const double* d_dtm, FineArgs* fa) {
+    const mcf_snow_inputs* in = &ci->drv.base;
+    const int64_t N = in->rows * in->cols, CC = ci->coarse_rows * ci->coarse_cols;
+    int rc = MCF_OK;
+    memset(fa, 0, sizeof *fa);
+    fa->N = N; fa->altcorrect = ci->altcorrect;
+    fa->geo.rows = (int32_t)in->rows; fa->geo.crows = (int32_t)ci->coarse_rows; fa->geo.ccols = (int32_t)ci->coarse_cols;
+    if ((rc = b.up(&fa->geo.rowpos, ci->coarse_rowpos, in->rows, "coarse_rowpos"))) return rc;
+    if ((rc = b.up(&fa->geo.colpos, ci->coarse_colpos, in->cols, "coarse_colpos"))) return rc;
+    if (d_dtm) fa->dtm = d_dtm;
+    else if ((rc = b.up(&fa->dtm, ci->drv.dtm, N, "dtm"))) return rc;
+    std::vector<double> psl;
+    if (ci->altcorrect) {
+        std::vector<double> zc((size_t)CC), down((size_t)CC);
+        for (int64_t q = 0; q < CC; ++q) {
+            zc[(size_t)q] = std::isnan(ci->coarse_dtm[q]) ? 0.0 : ci->coarse_dtm[q];
+            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
+        }
+        psl.resize((size_t)(CC * nh));
+        for (int64_t k = 0; k < nh; ++k)
+            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = ci->pres[(h0 + k) * CC + q] / down[(size_t)q];
+        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
+    }
+    each_coarse_selected(*ci, [&](auto* host, auto member, const char* name) {
+        if (!rc) rc = b.up(&(fa->*member), ci->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
+    });
+    return rc;
 }
 
 int snowmodelq2_checks(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out) {
@@ -2816,26 +2924,7 @@ int snowmodelq2_checks(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out)
     // (a tap is a uniform base + a 32-bit byte offset; the bound of the solver's coarse forcing, which addresses a day at once)
     if ((double)fi->coarse_rows * (double)fi->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
         return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
-    const int64_t n = in->tsteps;
-    char m[240];
-    for (int64_t k = 0; k < n; ++k) {
-        if (fi->subs[k] < 1 || fi->subs[k] > fi->n_all) {
-            snprintf(m, sizeof m, "mcf_snowmodelq2: subs[%lld] = %lld is outside 1..n_all = %lld", (long long)k, (long long)fi->subs[k],
-                     (long long)fi->n_all);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-        if (k && fi->subs[k] <= fi->subs[k - 1]) {
-            snprintf(m, sizeof m, "mcf_snowmodelq2: subs is not increasing at position %lld", (long long)k);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-    }
-    for (int64_t d = 0; d < n / 24; ++d)
-        if (!(day_af(fi->drv.af_wind + 24 * d, fi->drv.res) >= 1.0)) {
-            snprintf(m, sizeof m, "mcf_snowmodelq2: aggregation factor round(10*sqrt(mean af_wind)/res) of selected day %lld is 0 "
-                     "(terra::aggregate fails)", (long long)d);
-            return mcf::api_fail(MCF_ERR_ARG, m);
-        }
-    return MCF_OK;
+    return subs_af_checks("mcf_snowmodelq2", fi->subs, in->tsteps, fi->n_all, nullptr, fi->drv.af_wind, "af_wind", fi->drv.res);
 }
 
 int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_t device) {
@@ -2843,26 +2932,15 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
     if ((rc = snowmodelq2_checks(fi, out))) return rc;      // nothing above needs a device
     const mcf_snow_inputs* in = &fi->drv.base;
     if ((rc = pick_device(device))) return rc;
-    const int64_t rows = in->rows, cols = in->cols, N = rows * cols, n_all = fi->n_all, CC = fi->coarse_rows * fi->coarse_cols;
-    const int T = (int)in->tsteps, D = T / 24;
+    const int64_t N = in->rows * in->cols, n_all = fi->n_all, CC = fi->coarse_rows * fi->coarse_cols;
+    const int T = (int)in->tsteps;
     const int64_t DN = 24 * N;
-    // which series leave the call (umu is one of the day's thirteen inputs: it leaves from the set when it is wanted)
-    double* const hostv[6] = {out->smod.Tc, out->smod.Tg, out->smod.groundsnowdepth, out->smod.totalSWE, out->smod.snowden, out->umu};
-    const bool want_den = out->smod.snowden || out->smod.totalSWE;
-    const int nsets = std::min(2, D);
-    const int nser = 2 + (out->smod.Tc != nullptr) + (out->smod.Tg != nullptr) + want_den + (out->umu != nullptr);
-    std::vector<int> af((size_t)D);
-    std::vector<int> distinct;
-    int64_t cm_cells = 1;
-    for (int d = 0; d < D; ++d) {
-        af[(size_t)d] = (int)std::min(day_af(fi->drv.af_wind + 24 * d, fi->drv.res), 1e9);
-        if (std::find(distinct.begin(), distinct.end(), af[(size_t)d]) == distinct.end()) distinct.push_back(af[(size_t)d]);
-        if (tpi_is_coarse(rows, cols, af[(size_t)d])) cm_cells = std::max(cm_cells, tpi_coarse_cells(rows, cols, af[(size_t)d]));
-    }
-    const int nslots = (int)std::min<size_t>(kTpiCache, distinct.size());
-    if ((rc = check_room((66 + nslots + 13 * 24 + (int64_t)nsets * nser * 24) * N * 8 + ((14 * (int64_t)T + 2 * n_all + 6 * D + 2) * CC + cm_cells) * 8)))
+    // (umu is one of the day's thirteen inputs: it leaves from the set when it is wanted)
+    DayLoop L(fi->drv, fi->drv.af_wind, out->smod, out->umu);
+    const int D = L.D;
+    if ((rc = check_room((66 + L.nslots + 13 * 24 + (int64_t)L.nsets * L.nser * 24) * N * 8 +
+                         ((14 * (int64_t)T + 2 * n_all + 6 * D + 2) * CC + L.cm_cells) * 8)))
         return rc;
-    const bool timing = getenv("MCF_TIMING") != nullptr;
     mcf::DevOwner b;
     ModelArgs a;
     memset(&a, 0, sizeof a);
@@ -2873,49 +2951,17 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
     });
     if (rc) return rc;
     if ((rc = up_sites(b, a, in, N))) return rc;
-    CoarseGeo geo;
-    memset(&geo, 0, sizeof geo);
-    geo.rows = (int32_t)rows; geo.crows = (int32_t)fi->coarse_rows; geo.ccols = (int32_t)fi->coarse_cols;
-    if ((rc = b.up(&geo.rowpos, fi->coarse_rowpos, rows, "coarse_rowpos"))) return rc;
-    if ((rc = b.up(&geo.colpos, fi->coarse_colpos, cols, "coarse_colpos"))) return rc;
+    if ((rc = L.prepare(b, a))) return rc;
     // resident for the call: the coarse arrays of the selected hours, coarse sstemp / tc of the whole series
     FineArgs fa;
-    memset(&fa, 0, sizeof fa);
-    fa.N = N; fa.altcorrect = fi->altcorrect; fa.geo = geo;
-    std::vector<double> zc, psl;
-    if (fi->altcorrect) {                                      // pressure to sea level on the coarse grid (int:3127-3129)
-        zc.resize((size_t)CC);
-        std::vector<double> down((size_t)CC);
-        for (int64_t q = 0; q < CC; ++q) {
-            zc[(size_t)q] = std::isnan(fi->coarse_dtm[q]) ? 0.0 : fi->coarse_dtm[q];
-            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
-        }
-        psl.resize((size_t)(CC * T));
-        for (int64_t k = 0; k < T; ++k)
-            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = fi->pres[k * CC + q] / down[(size_t)q];
-        if ((rc = b.up(&fa.zc, zc.data(), CC, "coarse_dtm"))) return rc;
-    }
-    each_coarse_selected(*fi, [&](auto* host, auto member, const char* name) {
-        if (!rc) rc = b.up(&(fa.*member), fi->altcorrect && !strcmp(name, "pres") ? psl.data() : host, CC * T, name);
-    });
-    if (rc) return rc;
-    const double *d_dtm, *d_st, *d_ta;
-    double *d_dc, *d_dg, *d_intfrac, *d_slope, *d_aspect, *d_svf, *d_wsa, *d_hor, *d_ws, *d_m2, *d_cm, *d_sums, *d_tsum;
-    if ((rc = b.up(&d_dtm, fi->drv.dtm, N, "dtm"))) return rc;
-    if ((rc = b.up_mut(&d_dc, in->other.isnowdc, N, "other$isnowdc"))) return rc;
+    if ((rc = coarse_upload(b, fi, 0, T, L.d_dtm, &fa))) return rc;
+    const double *d_st, *d_ta;
+    double *d_intfrac, *d_sums, *d_tsum;
     if ((rc = b.up(&d_st, fi->sstemp, n_all * CC, "sstemp"))) return rc;
     if ((rc = b.up(&d_ta, fi->tc, n_all * CC, "tc"))) return rc;
-    double** const per_cell[] = {&d_dg, &d_intfrac, &d_slope, &d_aspect, &d_svf};
-    for (double** q : per_cell)
-        if ((rc = b.make(q, N))) return rc;
-    if ((rc = b.make(&d_wsa, 8 * N))) return rc;
-    if ((rc = b.make(&d_hor, 24 * N))) return rc;
-    if ((rc = b.make(&d_ws, 2 * kSumParts))) return rc;
-    if ((rc = b.make(&d_m2, 2))) return rc;
-    if ((rc = b.make(&d_cm, cm_cells))) return rc;
+    if ((rc = b.make(&d_intfrac, N))) return rc;
     if ((rc = b.make(&d_sums, 6 * CC * D))) return rc;
     if ((rc = b.make(&d_tsum, CC))) return rc;
-    fa.dtm = d_dtm;
     // the day's thirteen series on the raster (umu: in the output sets when it leaves)
     double** const fine[] = {&fa.o_temp, &fa.o_relhum, &fa.o_pres, &fa.o_swdown, &fa.o_difrad, &fa.o_lwdown, &fa.o_windspeed, &fa.o_precip,
                              &fa.o_Gp, &fa.o_Tc, &fa.o_RswabsG, &fa.o_RlwabsG};
@@ -2924,22 +2970,7 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
     if (!out->umu && (rc = b.make(&fa.o_umu, DN))) return rc;
     a.temp = fa.o_temp; a.relhum = fa.o_relhum; a.pres = fa.o_pres; a.swdown = fa.o_swdown; a.difrad = fa.o_difrad; a.lwdown = fa.o_lwdown;
     a.windspeed = fa.o_windspeed; a.precip = fa.o_precip; a.Gp = fa.o_Gp; a.Tcp = fa.o_Tc; a.RswabsG = fa.o_RswabsG; a.RlwabsG = fa.o_RlwabsG;
-    a.isnowdc = d_dc; a.isnowdg = d_dg;
-    a.slope = d_slope; a.aspect = d_aspect; a.skyview = d_svf; a.wsa = d_wsa; a.hor = d_hor;
     const unsigned gridN = (unsigned)((N + 255) / 256);
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2 + 6 * D)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
-    // terrain of the bare dtm (int:3171-3190), as `.snowmodelq1` makes it
-    {
-        mcf::TerrainDev td;
-        memset(&td, 0, sizeof td);
-        td.rows = rows; td.cols = cols; td.row0 = 0; td.rows_total = rows;
-        td.d_dtm = d_dtm; td.res = fi->drv.res; td.zref = in->other.zref; td.agg = fi->drv.res <= 100 ? 10 : 1; td.aspect_na = 180.0;
-        td.d_slope = d_slope; td.d_aspect = d_aspect; td.d_hor = d_hor; td.d_svfa = d_svf; td.d_wsa = d_wsa;
-        if ((rc = mcf::terrain_device(td))) return rc;
-        hipLaunchKernelGGL(k_mask2, dim3(gridN), dim3(256), 0, nullptr, d_dtm, N, d_slope, d_aspect);
-    }
-    if (timing) HIP_TRY(hipEventRecord(evs.e[1], nullptr));
     // the date table of all selected hours (array weather: a day's gridmodelsnow2 launch starts its own albedo clock)
     StepTables tabs;
     if ((rc = build_step_tables(b, in, true, true, false, &tabs))) return rc;
@@ -2953,13 +2984,13 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
         for (int64_t k = 0; k < n_all; ++k)
             for (int64_t q = 0; q < CC; ++q) tsum[(size_t)q] += fi->tc[k * CC + q];
         HIP_TRY(hipMemcpy(d_tsum, tsum.data(), (size_t)CC * 8, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_tap_plane, dim3(gridN), dim3(256), 0, nullptr, geo, N, d_dtm, (const double*)d_tsum, fa.o_temp);
-        launch_sumcount(fa.o_temp, N, d_ws, d_m2);
+        hipLaunchKernelGGL(k_tap_plane, dim3(gridN), dim3(256), 0, nullptr, fa.geo, N, L.d_dtm, (const double*)d_tsum, fa.o_temp);
+        launch_sumcount(fa.o_temp, N, L.d_ws, L.d_m2);
         double h[2];
-        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h, L.d_m2, 16, hipMemcpyDeviceToHost));
         CanIntArgs ca;
         ca.N = N; ca.hgt = a.hgt; ca.pai = a.pai; ca.uf = 2.0; ca.prec = scount ? ssum / (double)scount : NAN;
-        ca.sint = canopy_sint(h[0] / (h[1] * (double)n_all)); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = d_dc; ca.dg = d_dg;
+        ca.sint = canopy_sint(h[0] / (h[1] * (double)n_all)); ca.Li = 0.0; ca.frac = d_intfrac; ca.dc = L.d_dc; ca.dg = L.d_dg;
         hipLaunchKernelGGL(k_canintfrac, dim3(gridN), dim3(256), 0, nullptr, ca);
     }
     // every gap's six sums per coarse cell, in plain left-to-right order over R's `sbtn` (`.resamplemelt` taps them)
@@ -2978,118 +3009,38 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
         }
         HIP_TRY(hipMemcpy(d_sums, sums.data(), sums.size() * 8, hipMemcpyHostToDevice));
     }
-    // mean(dtm, na.rm = TRUE): `.tpicalc`'s raster-mean branch
-    double zmean = 0.0;
-    {
-        launch_sumcount(d_dtm, N, d_ws, d_m2);
-        double h[2];
-        HIP_TRY(hipMemcpy(h, d_m2, 16, hipMemcpyDeviceToHost));
-        zmean = h[0] / h[1];
-    }
-    // the day's series, twice: day d + 1 computes into one set while day d's leaves the other
-    struct Set { double *Tc = nullptr, *Tg = nullptr, *sdepc = nullptr, *sdepg = nullptr, *sden = nullptr, *umu = nullptr; } sets[2];
-    for (int s = 0; s < nsets; ++s) {
-        if (out->smod.Tc && (rc = b.make(&sets[s].Tc, DN))) return rc;
-        if (out->smod.Tg && (rc = b.make(&sets[s].Tg, DN))) return rc;
-        if ((rc = b.make(&sets[s].sdepc, DN))) return rc;
-        if ((rc = b.make(&sets[s].sdepg, DN))) return rc;
-        if (want_den && (rc = b.make(&sets[s].sden, DN))) return rc;
-        if (out->umu && (rc = b.make(&sets[s].umu, DN))) return rc;
-    }
-    struct Slot { int af = 0; double* tpi = nullptr; } slots[kTpiCache];
-    for (int s = 0; s < nslots; ++s)
-        if ((rc = b.make(&slots[s].tpi, N))) return rc;
-    int next_slot = 0, tpi_computed = 0;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    Streams streams;
-    hipStream_t cs, ds;                       // the days' kernels; the stream the downloads are ordered on
-    HIP_TRY(streams.make(&cs));
-    HIP_TRY(streams.make(&ds));
-    Events done;
-    HIP_TRY(done.make(2));
-    mcf::ToHost dl;
-    double t_download = 0.0;
-    auto download = [&](int d) -> hipError_t {                 // day d's wanted series, from the set it was computed into
-        hipError_t e = hipEventSynchronize(done.e[(size_t)(d & 1)]);
-        const auto t0 = std::chrono::steady_clock::now();
-        const Set& s = sets[d % nsets];
-        double* const devv[6] = {s.Tc, s.Tg, s.sdepg, s.sdepc, s.sden, s.umu};
-        for (int v = 0; v < 6 && e == hipSuccess; ++v)
-            if (hostv[v]) e = dl.dense(hostv[v] + (int64_t)d * DN, devv[v], (size_t)DN * 8, ds);
-        t_download += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        return e;
-    };
-    for (int d = 0; d < D; ++d) {
-        hipEvent_t* te = timing ? &evs.e[(size_t)(2 + 6 * d)] : nullptr;
-        if (te) HIP_TRY(hipEventRecord(te[0], cs));
+    auto gap_balance = [&](int d, const DaySet&, hipStream_t cs) {
         const Gap g = gap_of_day(fi->subs, d);
         Gap2Args ga;
         memset(&ga, 0, sizeof ga);
-        ga.N = N; ga.geo = geo; ga.adjust = fi->subs[24 * d] - 1 > 1;
-        ga.skyview = d_svf; ga.dtm = d_dtm; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.sums = d_sums + 6 * CC * d; ga.dc = d_dc; ga.dg = d_dg;
+        ga.N = N; ga.geo = fa.geo; ga.adjust = fi->subs[24 * d] - 1 > 1;
+        ga.skyview = L.d_svf; ga.dtm = L.d_dtm; ga.pai = a.pai; ga.intfrac = d_intfrac; ga.sums = d_sums + 6 * CC * d;
+        ga.dc = L.d_dc; ga.dg = L.d_dg;
         if (ga.adjust) { ga.start = g.start; ga.len = g.len; ga.step = g.step; }
         hipLaunchKernelGGL(k_gap_balance2, dim3(gridN), dim3(256), 0, cs, ga, d_st, d_ta);
-        if (te) HIP_TRY(hipEventRecord(te[1], cs));
-        // the day's weather and point model on the raster
-        const Set& s = sets[d % nsets];
+    };
+    // the day's weather and point model on the raster
+    auto fine_day = [&](int d, const DaySet& s, hipStream_t cs) {
         fa.hour0 = 24 * (int64_t)d;
         if (out->umu) fa.o_umu = s.umu;
-        hipLaunchKernelGGL(k_fine_day, dim3(gridN), dim3(256), 0, cs, fa);
-        if (te) HIP_TRY(hipEventRecord(te[2], cs));
-        // gridmodelsnow2 on the day's 24 hours, from the depths just formed and the caller's ages (they are not handed on)
+        launch_fine_chunk(fa, 24, cs);
+    };
+    // gridmodelsnow2 on the day's 24 hours, from the depths just formed and the caller's ages (they are not handed on)
+    auto model = [&](int d, const DaySet& s, hipStream_t cs) {
         a.dates = tabs.dates + 24 * d;
         a.umu = fa.o_umu;
         a.Tc = s.Tc; a.Tg = s.Tg; a.sdepc = s.sdepc; a.sdepg = s.sdepg; a.sden = s.sden;
         hipLaunchKernelGGL(k_snowmodel<true>, dim3(gridN), dim3(256), 0, cs, a, a.rows, a.dates);
-        if (te) HIP_TRY(hipEventRecord(te[3], cs));
-        // the day's position index: kept per af; beyond the cache's slots the oldest is computed over
-        const double* d_tpi = nullptr;
-        for (int q = 0; q < nslots; ++q)
-            if (slots[q].af == af[(size_t)d]) d_tpi = slots[q].tpi;
-        if (!d_tpi) {
-            Slot& sl = slots[next_slot];
-            next_slot = (next_slot + 1) % nslots;
-            sl.af = af[(size_t)d];
-            tpi_raster(d_dtm, rows, cols, sl.af, fi->drv.tfact, zmean, sl.tpi, d_ws, d_m2, d_cm, cs);
-            d_tpi = sl.tpi;
-            ++tpi_computed;
-        }
-        if (te) HIP_TRY(hipEventRecord(te[4], cs));
-        DayRedistArgs ra;
-        ra.N = N; ra.tpi = d_tpi; ra.sdepc = s.sdepc; ra.sdepg = s.sdepg; ra.sden = s.sden;
-        ra.swe = out->smod.totalSWE ? s.sdepc : nullptr; ra.gd = out->smod.groundsnowdepth ? s.sdepg : nullptr;
-        ra.dc = d_dc; ra.dg = d_dg;
-        hipLaunchKernelGGL(k_day_redistribute, dim3(gridN), dim3(256), 0, cs, ra);
+    };
+    auto cleansmod = [&](int, const DaySet& s, hipStream_t cs) {
         CleanArgs cl;
-        cl.N = N; cl.dtm = d_dtm;
+        cl.N = N; cl.dtm = L.d_dtm;
         cl.v[0] = s.Tc; cl.v[1] = s.Tg; cl.v[2] = out->smod.groundsnowdepth ? s.sdepg : nullptr;
         cl.v[3] = out->smod.totalSWE ? s.sdepc : nullptr; cl.v[4] = out->smod.snowden ? s.sden : nullptr;
-        hipLaunchKernelGGL(k_clean_day, dim3(gridN), dim3(256), 0, cs, cl);
-        if (te) HIP_TRY(hipEventRecord(te[5], cs));
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(done.e[(size_t)(d & 1)], cs));
-        // the day before leaves while this one computes (with one set there is one day)
-        if (d > 0) HIP_TRY(download(d - 1));
-    }
-    HIP_TRY(download(D - 1));
-    HIP_TRY(hipDeviceSynchronize());
-    if (timing) {
-        float ms = 0;
-        double t[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        const double t_terrain = ms;
-        for (int d = 0; d < D; ++d)
-            for (int q = 0; q < 5; ++q) {
-                HIP_TRY(hipEventElapsedTime(&ms, evs.e[(size_t)(2 + 6 * d + q)], evs.e[(size_t)(2 + 6 * d + q + 1)]));
-                t[q] += ms;
-            }
-        fprintf(stderr, "[mcf] snowmodelq2: %d days, %lld cells, %lld coarse cells: terrain %.2f ms, gap balance %.2f ms, "
-                "fine day %.2f ms, gridmodelsnow %.2f ms, tpi %.2f ms (%d of %d days computed), redistribute %.2f ms, downloads "
-                "%.2f ms of host time\n", D, (long long)N, (long long)CC, t_terrain, t[0], t[1], t[2], t[3], tpi_computed, D, t[4],
-                t_download * 1e3);
-    }
-    return MCF_OK;
+        hipLaunchKernelGGL(k_clean_chunk, dim3(gridN), dim3(256), 0, cs, cl, 24);
+    };
+    return L.run(b, "snowmodelq2", ", " + std::to_string(CC) + " coarse cells",
+                 {{"gap balance", gap_balance}, {"fine day", fine_day}, {"gridmodelsnow", model}}, {{".cleansmod", cleansmod}});
 }
 }  // namespace
 
@@ -3131,49 +3082,7 @@ extern "C" int mcf_meltmu2_device(int64_t rows, int64_t cols, const double* skyv
 
 // ---- `.snowmodel2`, the slow snow method with array weather, with the coarse arrays left coarse (mcf_snowmodel2_coarse) ---------
 namespace {
-// A chunk's thirteen series on the raster from the coarse arrays: k_fine_day's arithmetic, expression for expression, for the
-// hours a.hour0 .. a.hour0 + ns - 1 into [ns][N].  Lanes run along the cells (a wave stores 512 contiguous bytes per series
-// and hour), blockIdx.y over groups of kFineHours hours: a lane forms its tap, its pressure factor and elevd once and walks
-// its group.  Five hours: the 120-hour chunk of the bundled 50 x 50 raster is 10 x 24 = 240 workgroups on 256 CUs where one
-// lane per cell would be 10, the lane's set-up (two position loads, one pow with altcorrect) is spread over 5 x 14 taps, and
-// a chunk of whole days (24, 48, 120 hours; 24 is no multiple of 5) ends in a partial group, so the partial path is the
-// everyday one.  g0: the first group of this launch (the grid's y extent is 16 bits).
-constexpr int kFineHours = 5;
-__global__ __launch_bounds__(256) void k_fine_chunk(FineArgs a, int ns, int g0) {
-#pragma clang fp contract(off)
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N) return;
-    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
-    const SnowTap tap = a.geo.tap(c);
-    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
-    const double z = a.dtm[c], NA = na_real();
-    const bool hole = isnan(z);
-    double up = 1.0, elevd = 0.0;
-    if (a.altcorrect) {
-        up = pow((293 - 0.0065 * z) / 293, 5.26);
-        elevd = tap(a.zc) - z;
-    }
-    for (int k = kb; k < ke; ++k) {
-        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
-        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
-        double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
-        if (a.altcorrect) {
-            const double ea = snow_satvap_r(temp) * relhum / 100;
-            pres = pres * up;
-            const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
-            temp = lr * elevd + temp;
-            relhum = (ea / snow_satvap_r(temp)) * 100;
-        }
-        if (relhum > 100) relhum = 100.0;
-        const double wu = tap(a.windu + h), wv = tap(a.windv + h);
-        a.o_temp[o] = temp; a.o_relhum[o] = relhum; a.o_pres[o] = pres;
-        a.o_windspeed[o] = sqrt(wu * wu + wv * wv);
-        a.o_swdown[o] = cca(a.swdown); a.o_difrad[o] = cca(a.difrad); a.o_lwdown[o] = cca(a.lwdown); a.o_precip[o] = cca(a.precip);
-        a.o_Gp[o] = cca(a.Gp); a.o_Tc[o] = cca(a.Tc); a.o_RswabsG[o] = cca(a.RswabsG); a.o_RlwabsG[o] = cca(a.RlwabsG);
-        a.o_umu[o] = cca(a.umu);
-    }
-}
-// `.cca` of one coarse field for the hours hour0 .. hour0 + ns - 1, [ns][N]: the same lane map (pointm$umu behind the last chunk)
+// `.cca` of one coarse field for the hours hour0 .. hour0 + ns - 1, [ns][N]: k_fine_chunk's lane map (pointm$umu behind the last chunk)
 __global__ __launch_bounds__(256) void k_fine_field(CoarseGeo geo, int64_t N, int64_t hour0, int ns, const double* __restrict__ dtm,
                                                     const double* __restrict__ field, double* __restrict__ out) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3186,23 +3095,6 @@ __global__ __launch_bounds__(256) void k_fine_field(CoarseGeo geo, int64_t N, in
         const double v = tap(field + (hour0 + k) * CC);
         out[c + N * k] = hole ? na_real() : v;
     }
-}
-// `.cleansmod` on a chunk: NA on the dtm's holes in the series that leave, [ns][N] each (null: not written); holes are few, a
-// lane walks its cell's steps
-__global__ __launch_bounds__(256) void k_clean_chunk(CleanArgs a, int ns) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N || !isnan(a.dtm[c])) return;
-    const double NA = na_real();
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-        if (a.v[q])
-            for (int k = 0; k < ns; ++k) a.v[q][c + a.N * k] = NA;
-}
-void launch_fine_chunk(const FineArgs& fa, int ns) {
-    const int groups = (ns + kFineHours - 1) / kFineHours;
-    for (int g0 = 0; g0 < groups; g0 += 32768)
-        hipLaunchKernelGGL(k_fine_chunk, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, nullptr,
-                           fa, ns, g0);
 }
 
 // what both entries refuse before a device is touched; model: mcf_snowmodel2_coarse (the expansion reads geometry, dtm, coarse arrays)
@@ -3241,36 +3133,6 @@ int snowcoarse_checks(const mcf_snowcoarse_in* ci, const void* out, bool model, 
     return MCF_OK;
 }
 
-// geometry, dtm and the coarse arrays of hours h0 .. h0 + nh - 1 on the device (pressure taken to sea level by the host when
-// altcorrect > 0, int:2871-2873, as mcf_snowmodelq2 does); d_dtm: the raster's dtm if the caller has it there already
-int coarse_upload(mcf::DevOwner& b, const mcf_snowcoarse_in* ci, int64_t h0, int64_t nh, const double* d_dtm, FineArgs* fa) {
-    const mcf_snow_inputs* in = &ci->drv.base;
-    const int64_t N = in->rows * in->cols, CC = ci->coarse_rows * ci->coarse_cols;
-    int rc = MCF_OK;
-    memset(fa, 0, sizeof *fa);
-    fa->N = N; fa->altcorrect = ci->altcorrect;
-    fa->geo.rows = (int32_t)in->rows; fa->geo.crows = (int32_t)ci->coarse_rows; fa->geo.ccols = (int32_t)ci->coarse_cols;
-    if ((rc = b.up(&fa->geo.rowpos, ci->coarse_rowpos, in->rows, "coarse_rowpos"))) return rc;
-    if ((rc = b.up(&fa->geo.colpos, ci->coarse_colpos, in->cols, "coarse_colpos"))) return rc;
-    if (d_dtm) fa->dtm = d_dtm;
-    else if ((rc = b.up(&fa->dtm, ci->drv.dtm, N, "dtm"))) return rc;
-    std::vector<double> psl;
-    if (ci->altcorrect) {
-        std::vector<double> zc((size_t)CC), down((size_t)CC);
-        for (int64_t q = 0; q < CC; ++q) {
-            zc[(size_t)q] = std::isnan(ci->coarse_dtm[q]) ? 0.0 : ci->coarse_dtm[q];
-            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
-        }
-        psl.resize((size_t)(CC * nh));
-        for (int64_t k = 0; k < nh; ++k)
-            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = ci->pres[(h0 + k) * CC + q] / down[(size_t)q];
-        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
-    }
-    each_coarse_selected(*ci, [&](auto* host, auto member, const char* name) {
-        if (!rc) rc = b.up(&(fa->*member), ci->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
-    });
-    return rc;
-}
 // the kernel's outputs in the order of each_model_series
 void fine_outputs(FineArgs& fa, double* const d[13]) {
     fa.o_temp = d[0]; fa.o_relhum = d[1]; fa.o_pres = d[2]; fa.o_swdown = d[3]; fa.o_difrad = d[4]; fa.o_lwdown = d[5];
@@ -3295,7 +3157,7 @@ static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns) {
     const bool timing = getenv("MCF_TIMING") != nullptr;
     Events evs;
     if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
-    launch_fine_chunk(fa, ns);
+    launch_fine_chunk(fa, ns, nullptr);
     HIP_TRY(hipGetLastError());
     if (timing) {
         HIP_TRY(hipEventRecord(evs.e[1], nullptr));
@@ -3348,7 +3210,7 @@ extern "C" int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in* in, int64_
     for (int f = 0; f < 13; ++f)
         if ((rc = b.make(&d[f], N * nsteps))) return rc;
     fine_outputs(fa, d);
-    launch_fine_chunk(fa, (int)nsteps);
+    launch_fine_chunk(fa, (int)nsteps, nullptr);
     HIP_TRY(hipGetLastError());
     mcf::ToHost dl;
     for (int f = 0; f < 13; ++f) HIP_TRY(dl.dense(fine[f], d[f], (size_t)(N * nsteps) * 8));

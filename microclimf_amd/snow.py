@@ -412,6 +412,20 @@ def marshal_snowfast(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, 
     return m, fin
 
 
+def _wanted_series(m: SnowMarshalled, series, every: tuple, out) -> dict:
+    """The series a one-call entry returns (`series` None: `every` one): an array [rows, cols, tsteps] each, its pointer in
+    the entry's out struct; the others stay null, so the library neither finishes nor downloads them"""
+    names = every if series is None else tuple(series)
+    if not names or any(k not in every for k in names):
+        raise ValueError(f"series: names out of {every}")
+    arrays = {}
+    for k in every:
+        if k in names:
+            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    return arrays
+
+
 def snowmodelq1(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact=0.02, *,
                 device: int = 0, series: Sequence[str] | None = None) -> dict:
     """`snowmodelq1_days` as ONE device-resident call (include/mcf.h mcf_snowmodelq1): the same arguments, the same list.  The
@@ -422,14 +436,8 @@ def snowmodelq1(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp,
     `subs` out of range) raises _abi.McfError with its message."""
     lib = _abi.load()
     m, fin = marshal_snowfast(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact)
-    names = _abi.SNOWDRIVER_OUT if series is None else tuple(series)
-    if not names or any(k not in _abi.SNOWDRIVER_OUT for k in names):
-        raise ValueError(f"series: names out of {_abi.SNOWDRIVER_OUT}")
-    out, arrays = _abi.SnowDriverOut(), {}
-    for k in _abi.SNOWDRIVER_OUT:
-        if k in names:
-            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    out = _abi.SnowDriverOut()
+    arrays = _wanted_series(m, series, _abi.SNOWDRIVER_OUT, out)
     _abi.check(lib.mcf_snowmodelq1(C.byref(fin), C.byref(out), device))
     return arrays
 
@@ -554,51 +562,71 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
     return res_
 
 
-def marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect=0):
-    """-> (the marshalling that keeps the arrays alive, mcf_snowfast2_in) for `snowmodelq2`'s arguments: the coarse arrays
-    stay coarse; the wind components, the one direction per hour and `af_wind` are formed here as `snowmodelq2_days` forms them"""
+def _marshal_coarse(cin, clim_c, pointm_c, dtm, dtmc, rowpos, colpos, altcorrect):
+    """What the array-weather entries' input structs (mcf_snowfast2_in, mcf_snowcoarse_in) share, formed as the host loops form
+    it: sizes, dtm, the coarse grid's geometry and dtm, the fourteen coarse arrays with the wind as components, and from the
+    components' spatial means the one direction per step and `af_wind` -> (the marshalling, the direction per step)"""
     z = np.asarray(dtm, dtype=np.float64)
     R, Cc = z.shape
     cr, cc, n = np.shape(clim_c["temp"])
     m = SnowMarshalled()
     m.rows, m.cols, m.tsteps = R, Cc, n
-    sub = np.ascontiguousarray(subs, dtype=np.int64)
-    if sub.size != n or len(np.asarray(obstime["year"])) != n:
-        raise ValueError("subs and obstime must name every selected hour")
     wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
     wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
     wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
     wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
-    fin = _abi.SnowFast2In()
-    si = fin.drv.base
+    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
+    si = cin.drv.base
     si.rows, si.cols, si.tsteps, si.array_forcing = R, Cc, n, 1
+    cin.drv.dtm = m.f64(z, (R, Cc), "dtm")
+    cin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (n,), "af_wind")
+    cin.coarse_rows, cin.coarse_cols, cin.altcorrect = cr, cc, int(altcorrect)
+    cin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
+    cin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
+    cin.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
+    arrays = dict(clim_c, windu=wu_c, windv=wv_c, **{k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu")})
+    for k in _abi.SNOWFAST2_SELECTED:
+        setattr(cin, k, m.f64(arrays[k], (cr, cc, n), k))
+    return m, winddir
+
+
+def _marshal_model(m: SnowMarshalled, si, obstime, winddir, vegp, other, snowenv, leaft_fill: float, isnowdg: bool):
+    """The point model's side of an array-weather entry's mcf_snow_inputs: snowenv, obstime, the direction per step, `.sortl`'s
+    vegetation (`leaft` NA -> leaft_fill: `.snowmodelq2` and `.snowmodel2` differ in it) and `other` (isnowdg: whether the entry
+    reads it)"""
+    R, Cc, n = m.rows, m.cols, m.tsteps
     si.snowenv = _abi.SNOWENV.get(snowenv, 0)
     si.obstime.year = m.i32(obstime["year"], (n,), "obstime$year")
     si.obstime.month = m.i32(obstime["month"], (n,), "obstime$month")
     si.obstime.day = m.i32(obstime["day"], (n,), "obstime$day")
     si.obstime.hour = m.f64(obstime["hour"], (n,), "obstime$hour")
-    si.clim.winddir = m.f64((np.arctan2(wvv, wuv) * 180 / np.pi) % 360, (n,), "winddir")
+    si.clim.winddir = m.f64(winddir, (n,), "winddir")
     for f in ("pai", "hgt", "leaft", "clump"):
         v = np.asarray(vegp[f], dtype=np.float64)
-        setattr(si.vegp, f, m.f64(np.where(np.isnan(v), 0.01, v) if f == "leaft" else v, (R, Cc), f"vegp${f}"))
+        setattr(si.vegp, f, m.f64(np.where(np.isnan(v), leaft_fill, v) if f == "leaft" else v, (R, Cc), f"vegp${f}"))
     o = si.other
     o.zref = float(other["zref"])
     o.lat = o.lon = float("nan")
     o.lats = m.f64(_get(other, "lats", "lat"), (R, Cc), "other$lats")
     o.lons = m.f64(_get(other, "lons", "lon"), (R, Cc), "other$lons")
     o.isnowdc = m.f64(other["isnowdc"], (R, Cc), "other$isnowdc")
+    if isnowdg:
+        o.isnowdg = m.f64(other["isnowdg"], (R, Cc), "other$isnowdg")
     o.isnowac = m.i32(other["isnowac"], (R, Cc), "other$isnowac")
     o.isnowag = m.i32(other["isnowag"], (R, Cc), "other$isnowag")
-    fin.drv.dtm = m.f64(z, (R, Cc), "dtm")
+
+
+def marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect=0):
+    """-> (the marshalling that keeps the arrays alive, mcf_snowfast2_in) for `snowmodelq2`'s arguments: the coarse arrays
+    stay coarse; the wind components, the one direction per hour and `af_wind` are formed here as `snowmodelq2_days` forms them"""
+    cr, cc, n = np.shape(clim_c["temp"])
+    sub = np.ascontiguousarray(subs, dtype=np.int64)
+    if sub.size != n or len(np.asarray(obstime["year"])) != n:
+        raise ValueError("subs and obstime must name every selected hour")
+    fin = _abi.SnowFast2In()
+    m, winddir = _marshal_coarse(fin, clim_c, pointm_c, dtm, dtmc, rowpos, colpos, altcorrect)
+    _marshal_model(m, fin.drv.base, obstime, winddir, vegp, other, snowenv, 0.01, False)
     fin.drv.res, fin.drv.tfact = float(res), float(tfact)
-    fin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (n,), "af_wind")
-    fin.coarse_rows, fin.coarse_cols, fin.altcorrect = cr, cc, int(altcorrect)
-    fin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
-    fin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
-    fin.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
-    selected = dict(clim_c, windu=wu_c, windv=wv_c, **{k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu")})
-    for k in _abi.SNOWFAST2_SELECTED:
-        setattr(fin, k, m.f64(selected[k], (cr, cc, n), k))
     n_all = np.shape(pm2_c["tc"])[2]
     m._keep.append(sub)
     fin.n_all, fin.subs = n_all, sub.ctypes.data_as(C.POINTER(C.c_int64))
@@ -619,14 +647,8 @@ def snowmodelq2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dt
     lib = _abi.load()
     m, fin = marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos,
                                altcorrect)
-    names = _abi.SNOWFAST2_OUT if series is None else tuple(series)
-    if not names or any(k not in _abi.SNOWFAST2_OUT for k in names):
-        raise ValueError(f"series: names out of {_abi.SNOWFAST2_OUT}")
-    out, arrays = _abi.SnowFast2Out(), {}
-    for k in _abi.SNOWFAST2_OUT:
-        if k in names:
-            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    out = _abi.SnowFast2Out()
+    arrays = _wanted_series(m, series, _abi.SNOWFAST2_OUT, out)
     _abi.check(lib.mcf_snowmodelq2(C.byref(fin), C.byref(out), device))
     return arrays
 
@@ -715,52 +737,15 @@ def marshal_snowcoarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtm
     """-> (the marshalling that keeps the arrays alive, mcf_snowcoarse_in, the one wind direction per step) for
     `snowmodel2_coarse`'s arguments: the coarse arrays stay coarse; the wind components, the direction and `af_wind` are formed
     here exactly as `snowmodel2_chunks` forms them.  `obstime` / `vegp` / `other` None: only what the expansion reads"""
-    z = np.asarray(dtm, dtype=np.float64)
-    R, Cc = z.shape
-    cr, cc, T = np.shape(clim_c["temp"])
-    m = SnowMarshalled()
-    m.rows, m.cols, m.tsteps = R, Cc, T
-    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
-    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
-    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
-    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
-    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
     cin = _abi.SnowCoarseIn()
-    si = cin.drv.base
-    si.rows, si.cols, si.tsteps, si.array_forcing = R, Cc, T, 1
-    cin.drv.dtm = m.f64(z, (R, Cc), "dtm")
-    cin.coarse_rows, cin.coarse_cols, cin.altcorrect = cr, cc, int(altcorrect)
-    cin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
-    cin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
-    cin.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
-    arrays = dict(clim_c, windu=wu_c, windv=wv_c, **{k: pointm_c[k] for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu")})
-    for k in _abi.SNOWFAST2_SELECTED:
-        setattr(cin, k, m.f64(arrays[k], (cr, cc, T), k))
+    m, winddir = _marshal_coarse(cin, clim_c, pointm_c, dtm, dtmc, rowpos, colpos, altcorrect)
     if obstime is None:
         return m, cin, winddir
-    if len(np.asarray(obstime["year"])) != T:
+    if len(np.asarray(obstime["year"])) != m.tsteps:
         raise ValueError("obstime must name every step of the coarse arrays")
-    si.snowenv = _abi.SNOWENV.get(snowenv, 0)
-    si.obstime.year = m.i32(obstime["year"], (T,), "obstime$year")
-    si.obstime.month = m.i32(obstime["month"], (T,), "obstime$month")
-    si.obstime.day = m.i32(obstime["day"], (T,), "obstime$day")
-    si.obstime.hour = m.f64(obstime["hour"], (T,), "obstime$hour")
-    si.clim.winddir = m.f64(winddir, (T,), "winddir")
-    for f in ("pai", "hgt", "leaft", "clump"):
-        v = np.asarray(vegp[f], dtype=np.float64)
-        setattr(si.vegp, f, m.f64(np.where(np.isnan(v), 0.001, v) if f == "leaft" else v, (R, Cc), f"vegp${f}"))
-    o = si.other
-    o.zref = float(other["zref"])
-    o.lat = o.lon = float("nan")
-    o.lats = m.f64(_get(other, "lats", "lat"), (R, Cc), "other$lats")
-    o.lons = m.f64(_get(other, "lons", "lon"), (R, Cc), "other$lons")
-    o.isnowdc = m.f64(other["isnowdc"], (R, Cc), "other$isnowdc")
-    o.isnowdg = m.f64(other["isnowdg"], (R, Cc), "other$isnowdg")
-    o.isnowac = m.i32(other["isnowac"], (R, Cc), "other$isnowac")
-    o.isnowag = m.i32(other["isnowag"], (R, Cc), "other$isnowag")
+    _marshal_model(m, cin.drv.base, obstime, winddir, vegp, other, snowenv, 0.001, True)
     cin.drv.res, cin.drv.tfact, cin.drv.chunk_steps = float(res), float(tfact), int(chunk_steps)
     cin.drv.af_wsa_s = int(agg)
-    cin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (T,), "af_wind")
     return m, cin, winddir
 
 
@@ -777,14 +762,8 @@ def snowmodel2_coarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc
     lib = _abi.load()
     m, cin, _ = marshal_snowcoarse(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos, altcorrect, agg,
                                    chunk_steps)
-    names = _abi.SNOWFAST2_OUT if series is None else tuple(series)
-    if not names or any(k not in _abi.SNOWFAST2_OUT for k in names):
-        raise ValueError(f"series: names out of {_abi.SNOWFAST2_OUT}")
-    out, arrays = _abi.SnowFast2Out(), {}
-    for k in _abi.SNOWFAST2_OUT:
-        if k in names:
-            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
+    out = _abi.SnowFast2Out()
+    arrays = _wanted_series(m, series, _abi.SNOWFAST2_OUT, out)
     _abi.check(lib.mcf_snowmodel2_coarse(C.byref(cin), C.byref(out), device))
     return arrays
 

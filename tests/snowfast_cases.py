@@ -42,14 +42,15 @@ def _crop(vegp, soilc, dtm, r0, r1, c0, c1):
 
 
 @functools.lru_cache(maxsize=None)
-def q1_case(i):
+def q1_case(i, days=None):
     """the product's inputs of Q1_CASES[i], the day loop's arguments as the oracle chain forms them (built as
-    tests/test_snowfast_gpu.py::test_fast_method_matches_the_oracle_chain builds `want`), and the oracle's result"""
+    tests/test_snowfast_gpu.py::test_fast_method_matches_the_oracle_chain builds `want`), and the oracle's result.
+    days (a tuple): the case with other selected days, for the day loop's arguments alone — the oracle chain is not run"""
     from oracle import oracle as O
     from oracle import replay_reference_tests as RT
     from oracle import snowfast_oracle as SF
     O.load()
-    case = Q1_CASES[i]
+    case = Q1_CASES[i] if days is None else dict(Q1_CASES[i], days=list(days))
     weather, vegp, soilc, dtm = load(50 * 24)
     vegp, soilc, dtm = _crop(vegp, soilc, dtm, *case["window"])
     if case.get("hole"):
@@ -79,7 +80,7 @@ def q1_case(i):
     rows = lambda d: {k: np.asarray(v)[ai] for k, v in d.items()}      # noqa: E731
     args = (rows(obst), rows(w), rows(pointm), pm, w["temp"], np.where(w["temp"] > 2, 0.0, w["precip"]), mp["subs"], vs, other, env, z,
             dtm["res"], stfact)
-    want = SF.snowmodelq1_days(*args)
+    want = SF.snowmodelq1_days(*args) if days is None else {}
     for v in want.values():
         v.flags.writeable = False
     return dict(kind="q1", product=(weather, mp, vegp, soilc, dtm, kw), args=args, want=want, umu=pm["umu"][ai])
@@ -99,14 +100,15 @@ Q2_CASES = [
 
 
 @functools.lru_cache(maxsize=None)
-def q2_case(i):
+def q2_case(i, days=None):
     """the product's inputs of Q2_CASES[i], the day loop's arguments as the oracle chain forms them (built as the `fast` case of
-    tests/test_snowfast_gpu.py::test_array_weather_snow_model_matches_the_oracle_chain builds `want`), and the oracle's result"""
+    tests/test_snowfast_gpu.py::test_array_weather_snow_model_matches_the_oracle_chain builds `want`), and the oracle's result.
+    days (a tuple): the case with other selected days, for the day loop's arguments alone — the oracle chain is not run"""
     from oracle import oracle as O
     from oracle import replay_reference_tests as RT
     from oracle import snowfast_oracle as SF
     O.load()
-    case = Q2_CASES[i]
+    case, run_oracle = (Q2_CASES[i], True) if days is None else (dict(Q2_CASES[i], days=list(days)), False)
     weather, vegp, soilc, dtm = load(50 * 24)
     vegp, soilc, dtm = _crop(vegp, soilc, dtm, *case["window"])
     if case.get("hole"):
@@ -169,7 +171,7 @@ def q2_case(i):
     args = (sel(obst), sel(clim_c), pm_s, pm2, subs, F.sortl(vg, np.max(pm_s["sdepc"], axis=(0, 1))), other, env, z, dtmc, dtm["res"],
             stfact)
     pos = dict(rowpos=rowpos, colpos=colpos, altcorrect=case["altcorrect"])
-    want = SF.snowmodelq2_days(*args, rowpos, colpos, altcorrect=case["altcorrect"])
+    want = SF.snowmodelq2_days(*args, rowpos, colpos, altcorrect=case["altcorrect"]) if run_oracle else {}
     for v in want.values():
         v.flags.writeable = False
     # the gaps' multipliers on the reference side: does a gap thaw somewhere (mu neither 0.5 nor NA)?
@@ -183,6 +185,40 @@ def q2_case(i):
             thaws = thaws or bool(np.any(np.nansum(np.where(st > 0, st, 0.0), axis=2) > 0))
     return dict(kind="q2", product=(climarray, weather["obstime"], mpa, vegp, soilc, dtm, kw), args=args, pos=pos, want=want, thaws=thaws,
                 umu_c=pm_s["umu"], hole=np.isnan(z))
+
+
+# ---- the day loop's branches that no case above takes ------------------------------------------------------------------
+# One selected day: one output set, one `done` event, only the trailing download.  Ten selected days whose aggregation factors
+# round(10 sqrt(mean wind) / res) are AF_DAYS: nine distinct ones against the eight position indices a call keeps, so the ninth
+# is computed over the oldest slot (af = 2's) and the tenth day needs af = 2 again.  Both on case 0's window (23 x 37: every
+# factor is below min(dim) / 2 = 11.5, `.tpicalc` aggregates, and a wrong slot is another position index).
+ONE_DAY = (3,)
+TEN_DAYS = (2, 3, 7, 11, 16, 22, 29, 37, 44, 49)
+AF_DAYS = [2, 3, 4, 5, 6, 7, 8, 9, 10, 2]
+
+
+def loop_args(kind, days):
+    """-> (S.snowmodelq1's / S.snowmodelq2's arguments, the keywords) of case 0 with `days` selected; with TEN_DAYS every
+    selected hour's wind speed is the day's (AF_DAYS res / 10)^2 (q2: in every coarse cell, the directions as they are)"""
+    c = q1_case(0, days) if kind == "q1" else q2_case(0, days)
+    args = list(c["args"])
+    if days == TEN_DAYS:
+        res = args[11] if kind == "q1" else args[10]
+        wind = np.repeat((np.asarray(AF_DAYS) * res / 10) ** 2, 24)
+        args[1] = dict(args[1], windspeed=wind if kind == "q1" else np.asfortranarray(np.broadcast_to(wind, args[1]["windspeed"].shape)))
+    return tuple(args), c.get("pos", {})
+
+
+def library_af(wind, res):
+    """the aggregation factor per day as the library forms it (day_af): the day's 24 values added left to right, / 24, sqrt,
+    x 10, / res, rounded half to even"""
+    out = []
+    for day in np.asarray(wind, dtype=np.float64).reshape(-1, 24):
+        s = 0.0
+        for v in day:
+            s += float(v)
+        out.append(int(np.rint(10 * np.sqrt(s / 24) / res)))
+    return out
 
 
 # ---- the oracle chain as a workload of parity_bars --------------------------------------------------------------------

@@ -112,6 +112,25 @@ def test_one_call_matches_the_host_day_loop(oracle, i):
     assert err < 1e-6, f"largest scaled difference between the one call and the host day loop: {err:.3e} at {where}"
 
 
+# ---- the day loop's branches that the cases above do not take -------------------------------------------------------------
+@pytest.mark.parametrize("days", [FC.ONE_DAY, FC.TEN_DAYS], ids=["one day", "cache eviction"])
+def test_one_selected_day_and_more_factors_than_cached_match_the_host_day_loop(oracle, days):
+    """One selected day: a single output set and `done` event, only the trailing download.  Ten days with the aggregation
+    factors 2 .. 10, 2 (tests/test_snowfast_onecall_cpu.py): the ninth distinct factor is computed over the oldest of the eight
+    kept position indices and the tenth day needs the evicted one again."""
+    args, pos = FC.loop_args("q2", days)
+    got, ref = S.snowmodelq2(*args, **pos), S.snowmodelq2_days(*args, **pos)
+    assert list(got) == list(ref) and got["Tc"].shape[2] == 24 * len(days)
+    err, where = _worst(got, ref)
+    print(f"{len(days)} days: largest scaled |one call - day loop| = {err:.3e} at {where}, deepest ground snow "
+          f"{np.nanmax(got['groundsnowdepth']):.4f} m")
+    assert err < 1e-6, f"largest scaled difference between the one call and the host day loop: {err:.3e} at {where}"
+    if days == FC.TEN_DAYS:
+        assert np.nanmax(got["groundsnowdepth"]) > 0.01                # the position index matters
+    only = S.snowmodelq2(*args, **pos, series=("totalSWE",))
+    assert list(only) == ["totalSWE"] and only["totalSWE"].tobytes() == got["totalSWE"].tobytes()
+
+
 # ---- the call and the host day loop against the oracle chain under derived bars ----------------------------------------
 @pytest.mark.parametrize("i", FC.SMALL)
 def test_one_call_and_day_loop_within_the_derived_bars_of_the_oracle_chain(oracle, i):

@@ -143,6 +143,23 @@ def test_an_aggregation_factor_of_zero_is_refused(lib):
     assert rc == MCF_ERR_ARG and "aggregation factor" in msg, (rc, msg)
 
 
+def test_the_eviction_inputs_walk_the_aggregation_factors_past_the_cache(oracle, lib):
+    """The ten-day inputs of the one-call GPU tests (snowfast_cases.loop_args) give, rounded as the library rounds, the factors
+    2 .. 10 and 2 again: nine distinct ones for eight slots — for mcf_snowmodelq1 from the selected hours' wind speed, for
+    mcf_snowmodelq2 from the `af_wind` that marshal_snowfast2 hands the library."""
+    import snowfast_cases as FC
+    want = [2, 3, 4, 5, 6, 7, 8, 9, 10, 2]
+    assert FC.AF_DAYS == want and len(set(want)) == 9 > 8
+    args, _ = FC.loop_args("q1", FC.TEN_DAYS)
+    assert FC.library_af(args[1]["windspeed"], args[11]) == want
+    assert max(want) < min(np.shape(args[10])) / 2                    # `.tpicalc` aggregates for every one of them
+    args, pos = FC.loop_args("q2", FC.TEN_DAYS)
+    m, fin = S.marshal_snowfast2(*args, **pos)
+    af_wind = np.ctypeslib.as_array(fin.drv.af_wind, shape=(m.tsteps,))
+    assert m.tsteps == 240 and FC.library_af(af_wind, args[10]) == want
+    assert max(want) < min(np.shape(args[8])) / 2
+
+
 def test_one_shot_kernel_entries_refuse_null_arguments(lib):
     x = np.ones(4)
     p = x.ctypes.data_as(_abi.c_double_p)
