@@ -964,21 +964,30 @@ __device__ __forceinline__ void derive_time_af_pass2(TimeVals& t) {
 }
 
 // ---- accessors ----------------------------------------------------------------
+// An operand in LDS is read as ONE 8-byte ds_read_b64.  Through plain pointers hipcc's machine-level load/store merging
+// pairs the reads of a batch into ds_read2_b64 (93 of them in the day loop of the 21-cell kernel), which occupies the
+// LDS array for 8 cycles per wave-instruction where two ds_read_b64 take 2 each.  The accessors therefore keep pointers
+// in the LDS address space (so the read stays a ds_read, no flat aperture) and read through a volatile one: the merging
+// pass leaves volatile accesses alone, and the compiler still counts lgkmcnt for them itself, so no wait is hand-written.
+// Every instantiation takes them: none gains scratch, the array / coarse kernels end 1-5 VGPRs lower.
+typedef const __attribute__((address_space(3))) double* LdsPtr;
+__device__ __forceinline__ LdsPtr lds_ptr(const double* p) { return (LdsPtr)p; }      // p: into a __shared__ array
+__device__ __forceinline__ double lds_operand(LdsPtr p, int i) { return ((const volatile __attribute__((address_space(3))) double*)p)[i]; }
 // Cell constants in LDS, laid out [field][cells_per_block]; `dirs` holds the 24
 // horizon + 8 wind-shelter values [dir][cells_per_block].
 // One pointer per lane: the tile's image is [CF_COUNT cell fields, then 24 horizon + 8 wind-shelter rows][cells_per_block].
 template <int CPB>
 struct CellLds {
-    const double* p;   // image + the lane's cell
-    __device__ __forceinline__ double operator()(int field) const { return p[field * CPB]; }
-    __device__ __forceinline__ double hor(int s) const { return p[(CF_COUNT + s) * CPB]; }
-    __device__ __forceinline__ double wsa(int w) const { return p[(CF_COUNT + 24 + w) * CPB]; }
+    LdsPtr p;   // image + the lane's cell
+    __device__ __forceinline__ double operator()(int field) const { return lds_operand(p, field * CPB); }
+    __device__ __forceinline__ double hor(int s) const { return lds_operand(p, (CF_COUNT + s) * CPB); }
+    __device__ __forceinline__ double wsa(int w) const { return lds_operand(p, (CF_COUNT + 24 + w) * CPB); }
 };
 // A day's time table in LDS, laid out [field][24].
 struct TimeLds {
     static constexpr bool in_registers = false;
-    const double* row;  // + hour
-    __device__ __forceinline__ double operator()(int field) const { return row[field * 24]; }
+    LdsPtr row;  // + hour
+    __device__ __forceinline__ double operator()(int field) const { return lds_operand(row, field * 24); }
 };
 struct TimeReg {
     static constexpr bool in_registers = true;      // array forcing: the passes are short of registers (see pass2, section B)
@@ -1139,7 +1148,7 @@ __device__ __forceinline__ void soil_day_produce(const double* cellc, double soi
     static_assert(2 * CPB <= 64, "two roles per cell must fit a wave");
     const int role = lane / CPB, cell = lane - role * CPB;
     if (role > 1) return;
-    auto C = [&](int f) { return cellc[f * CPB + cell]; };
+    auto C = [&](int f) { return lds_operand(lds_ptr(cellc), f * CPB + cell); };
     Canary cn;
     const double soilm = soil_spread<F>(soilmp, C(CF_SMIN), C(CF_INVRGE), C(CF_ETA), C(CF_RGE), cn);
     const double abspsie = C(CF_ABSPSIE), invsmax = C(CF_INVSMAX);
@@ -1164,8 +1173,8 @@ __device__ __forceinline__ void soil_day_produce(const double* cellc, double soi
 // a lane's view of its cell's entry; SS = false: never read (array forcing)
 template <int CPB>
 struct SoilLds {
-    const double* p;   // + cell
-    __device__ __forceinline__ double operator()(int f) const { return p[f * CPB]; }
+    LdsPtr p;   // + cell
+    __device__ __forceinline__ double operator()(int f) const { return lds_operand(p, f * CPB); }
 };
 
 // ---- diagnostics sink (include/mcf.h `mcf_diag`) ------------------------------------------------------------------------

@@ -585,7 +585,7 @@ __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, co
         double2* dst = reinterpret_cast<double2*>(s_tile);
         for (int q = tid; q < IMG / 2; q += NT) dst[q] = src[q];
     };
-    const CellLds<CPB> C{s_cell + cl};
+    const CellLds<CPB> C{lds_ptr(s_cell + cl)};
     int flags = 0;
     bool valid = false;
     // vegetation layer of a day (runmicro3Cpp/4Cpp `dfsel`, cpp:2760-2768)
@@ -880,9 +880,9 @@ __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, co
                 if (!(fabs(tv.v[TF_TC]) < 150.0 && fabs(tv.v[TF_TDEW]) < 150.0)) cn.trip();     // satvap_f's bounded exp
             }
         }
-        TimeLds TL{s_time + (AF ? 0 : (run % 3) * (TF_COUNT * 24)) + hr};
+        TimeLds TL{lds_ptr(s_time + (AF ? 0 : (run % 3) * (TF_COUNT * 24)) + hr)};
         TimeReg TR{&tv};
-        SoilLds<CPB> SL{s_soil + (SS ? (run % 3) * (SD_COUNT * CPB) + cl : 0)};
+        SoilLds<CPB> SL{lds_ptr(s_soil + (SS ? (run % 3) * (SD_COUNT * CPB) + cl : 0))};
 
         Carry cy;
         Pass1Out p1;
@@ -969,7 +969,8 @@ __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, co
             // day reductions with the reference's comparisons, cpp:2196-2198, 2256-2263.  `if (Rmx < rv) Rmx = rv` with a
             // finite start value ignores a NaN rv, exactly what v_max_f64 does (the accumulator is never NaN, rv is never a
             // signalling NaN: it was just computed): one VALU instruction instead of a compare and two 32-bit selects
-            const double tmx = s_ext[run % 3][0][cl], tmn = s_ext[run % 3][1][cl], Rmx = s_ext[run % 3][2][cl];
+            const LdsPtr ext = lds_ptr(&s_ext[run % 3][0][cl]);
+            const double tmx = lds_operand(ext, 0), tmn = lds_operand(ext, CPB), Rmx = lds_operand(ext, 2 * CPB);
             const double dtr = tmx - tmn;
             Pass2Out p2{};
             if (AF) derive_time_af_pass2(tv);
