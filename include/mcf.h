@@ -58,7 +58,8 @@ extern "C" {
                              *    (added since, functions only: mcf_plan_below_set_days, mcf_below_days_range, mcf_runmicrosnow1_below,
                              *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below, mcf_snowmodelq1, mcf_canintfrac_device,
                              *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device, mcf_plan_summary_*, mcf_runmicro_summary,
-                             *    mcf_runmicro_summary_multi, mcf_snowmodel2_coarse, mcf_snow_expand_coarse_device) */
+                             *    mcf_runmicro_summary_multi, mcf_snowmodel2_coarse, mcf_snow_expand_coarse_device, mcf_snowplan_summary_*,
+                             *    mcf_snowrun_summary_*, mcf_runmicrosnow_summary, mcf_snowmodel1_summary) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -999,6 +1000,72 @@ int mcf_snowrun_keep(mcf_snowrun *run, int64_t bytes);
 /* snowday / nosnowday: [mcf_snowrun_days] or NULL */
 int mcf_snowrun_pass1(mcf_snowrun *run, const mcf_snowdriver_out *smod, int32_t *snowday, int32_t *nosnowday);
 int mcf_snowrun_pass2(mcf_snowrun *run, const mcf_snow_inputs *micro, double mat, mcf_outputs *out);
+
+/* ---- period summaries of the snow run and of the snowpack, folded on the device -------------------------------
+ * The `summary` of "period summaries" above (same table, statistics, order of evaluation and NA rule) kept over
+ *   - the snow run's merged outputs: each block's solver plan carries a mcf_summary_spec, and pass 2 folds every merged ring
+ *     chunk behind the snow-day kernel (or behind the solver alone) with mcf_plan_summary_accumulate;
+ *   - the snowpack's five series (mcf_snowdriver_out's order: Tc, Tg, groundsnowdepth, totalSWE, snowden), folded from a
+ *     chunk's device series right after run_chunk — the values mcf_snowmodel1 copies to its host arrays, totalSWE after the
+ *     redistribution.  HOURS_ABOVE of totalSWE with threshold 0 is the snow-cover duration, MAX of totalSWE the peak snow
+ *     water equivalent.
+ * Nothing of size cells x steps crosses PCIe or exists on the host.  reqhgt >= 0 (a below-ground run is refused: its solver
+ * plan is a streamed plan). */
+typedef struct mcf_snowpack_summary_spec {
+    int32_t nperiods;
+    const int32_t *period_of_day;  /* [tsteps / 24]; a day past the last whole chunk must be -1 (no chunk covers it) */
+    int32_t series[5];             /* != 0: summarised (Tc, Tg, groundsnowdepth, totalSWE, snowden)  */
+    int32_t stat[MCF_NSTAT];       /* != 0: kept                                                      */
+    double threshold[5];           /* HOURS_ABOVE; read for selected series only                      */
+} mcf_snowpack_summary_spec;
+typedef struct mcf_snowpack_summary_out {
+    double *val[5][MCF_NSTAT];     /* [rows, cols, nperiods] for every selected pair */
+    int32_t *days;                 /* [nperiods] or NULL */
+} mcf_snowpack_summary_out;
+/* The snow plan's sink.  enable: allocates nsel x nperiods x state rows x cells x 8 bytes (MCF_ERR_NOMEM when it does not
+ * fit); MCF_ERR_ARG with a message for a null spec, nperiods < 1, a table entry outside -1 .. nperiods - 1, an empty selection,
+ * a NaN threshold of a selected series with HOURS_ABOVE selected, chunk_steps that are not whole days, a counted day past the
+ * last whole chunk; MCF_ERR_STATE when called twice.  accumulate(chunk): folds the series of the chunk run last (after
+ * run_chunk, before mcf_snowplan_keep_chunk hands the buffers over), on the stream the model wrote them on; chunks arrive in
+ * ascending order, each at most once, and every selected series must have been written (mcf_snowplan_set_series):
+ * MCF_ERR_STATE otherwise.  fetch: one statistic of one series as [rows, cols, nperiods], column-major, `row_pitch` rows per
+ * column on the host (0: dense).  reset: nothing folded, chunk 0 may come next. */
+int mcf_snowplan_summary_enable(mcf_snowplan *plan, const mcf_snowpack_summary_spec *spec);
+int mcf_snowplan_summary_accumulate(mcf_snowplan *plan, int32_t chunk);
+int mcf_snowplan_summary_fetch(mcf_snowplan *plan, int32_t series, int32_t stat, double *host_dst, int64_t row_pitch);
+int mcf_snowplan_summary_days(mcf_snowplan *plan, int32_t *days);
+int mcf_snowplan_summary_reset(mcf_snowplan *plan);
+/* The summary table of a snow run from the caller's: days in NEITHER class (no day of either model: NA for every cell in the
+ * run's arrays) are never counted, out[d] = -1 there and period_of_day[d] elsewhere.  Pure host function. */
+int mcf_snowrun_summary_table(const int32_t *period_of_day, const int32_t *snowday, const int32_t *nosnowday, int32_t ndays,
+                              int32_t *out);
+/* Switches the sinks of a run on, before mcf_snowrun_pass1 (MCF_ERR_STATE after it, or when called twice); either spec may be
+ * NULL, not both.  `micro` selects among the variables the run was created with.  With a summary enabled mcf_snowrun_pass2
+ * accepts out == NULL or null arrays: variables without a host array are folded only.  mcf_snowrun_pass1 starts the summaries
+ * over (a second year on one handle). */
+int mcf_snowrun_summary_enable(mcf_snowrun *run, const mcf_summary_spec *micro, const mcf_snowpack_summary_spec *pack);
+/* One plane [rows, cols, nperiods] of the whole raster, every block's rows in place; pack = 0: variable `var` of the merged
+ * outputs (after pass 2), pack != 0: series `var` of the snowpack (after pass 1).  MCF_ERR_STATE before that. */
+int mcf_snowrun_summary_fetch(mcf_snowrun *run, int32_t pack, int32_t var, int32_t stat, double *host_dst);
+int mcf_snowrun_summary_days(mcf_snowrun *run, int32_t pack, int32_t *days);
+/* One call: mcf_runmicrosnow1 / 2 / _multi (by `in`'s weather geometry and `multi`, which may be NULL) with the sinks on.
+ * micro / pack: the planes of the enabled specs (the struct of a NULL spec is not read); arrays (optional): host arrays for
+ * some or all requested variables, as mcf_runmicrosnow1's `out`; smod (optional) as there; snowday / nosnowday: [days] or NULL. */
+typedef struct mcf_snowrun_summary_out {
+    mcf_summary_out micro;
+    mcf_snowpack_summary_out pack;
+    mcf_outputs *arrays;
+    const mcf_snowdriver_out *smod;
+    int32_t *snowday, *nosnowday;
+} mcf_snowrun_summary_out;
+int mcf_runmicrosnow_summary(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi,
+                             const mcf_summary_spec *micro_spec, const mcf_snowpack_summary_spec *pack_spec,
+                             mcf_snowrun_summary_out *outs);
+/* The snow model alone with the snowpack sink and no series output: data.frame weather, mcf_snowmodel1's loop on device 0
+ * (multi == NULL) or mcf_snowmodel1_multi's over `multi`'s devices and row blocks (another single device: a mcf_multi that
+ * names it). */
+int mcf_snowmodel1_summary(const mcf_snowdriver_in *in, const mcf_snowpack_summary_spec *spec, const mcf_multi *multi,
+                           mcf_snowpack_summary_out *out);
 
 /* applycpp3 (src/microclimfCpp.cpp:5553-5588; `.runmicrosnow1/2` use it on totalSWE, R/internal.R:3592-3593):
  * reduction of a [rows,cols,tsteps] array over space, per time step, skipping NA.  fun: 0 mean, 1 sum,

@@ -136,6 +136,17 @@ class SummaryOut(C.Structure):
     _fields_ = [("val", (c_double_p * NSTAT) * NOUT), ("days", c_int32_p)]
 
 
+class SnowpackSummarySpec(C.Structure):
+    """include/mcf.h mcf_snowpack_summary_spec (series in SNOWDRIVER_OUT's order)"""
+    _fields_ = [("nperiods", C.c_int32), ("period_of_day", c_int32_p), ("series", C.c_int32 * 5), ("stat", C.c_int32 * NSTAT),
+                ("threshold", C.c_double * 5)]
+
+
+class SnowpackSummaryOut(C.Structure):
+    """include/mcf.h mcf_snowpack_summary_out"""
+    _fields_ = [("val", (c_double_p * NSTAT) * 5), ("days", c_int32_p)]
+
+
 class DiagOutputs(C.Structure):
     """include/mcf.h mcf_diag_outputs"""
     _fields_ = [("var", c_double_p * NDIAG)]
@@ -259,6 +270,12 @@ class MicrosnowIn(C.Structure):
                 ("mat", C.c_double)]
 
 
+class SnowrunSummaryOut(C.Structure):
+    """include/mcf.h mcf_snowrun_summary_out"""
+    _fields_ = [("micro", SummaryOut), ("pack", SnowpackSummaryOut), ("arrays", C.POINTER(Outputs)), ("smod", C.POINTER(SnowDriverOut)),
+                ("snowday", c_int32_p), ("nosnowday", c_int32_p)]
+
+
 class LeafrOut(C.Structure):
     """include/mcf.h mcf_leafr_out"""
     _fields_ = [("leafr", c_double_p), ("leaft", c_double_p), ("gref", c_double_p), ("iterations", C.c_int32),
@@ -307,6 +324,9 @@ EXPORTS = (
     "mcf_plan_summary_enable", "mcf_plan_summary_accumulate", "mcf_plan_summary_fetch", "mcf_plan_summary_days",
     "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
     "mcf_bioclim_last_chunks",
+    "mcf_snowplan_summary_enable", "mcf_snowplan_summary_accumulate", "mcf_snowplan_summary_fetch", "mcf_snowplan_summary_days",
+    "mcf_snowplan_summary_reset", "mcf_snowrun_summary_table", "mcf_snowrun_summary_enable", "mcf_snowrun_summary_fetch",
+    "mcf_snowrun_summary_days", "mcf_runmicrosnow_summary", "mcf_snowmodel1_summary",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -688,6 +708,30 @@ def load() -> C.CDLL:
         lib.mcf_snowplan_run_chunk_pitched.argtypes = [P, C.c_int32, C.c_double, SO, C.c_int64]
         lib.mcf_snowplan_chunk_af.restype = C.c_int
         lib.mcf_snowplan_chunk_af.argtypes = [P, C.c_int32, C.POINTER(C.c_int32)]
+    if hasattr(lib, "mcf_snowrun_summary_enable"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        SS, PS, PO = C.POINTER(SummarySpec), C.POINTER(SnowpackSummarySpec), C.POINTER(SnowpackSummaryOut)
+        lib.mcf_snowplan_summary_enable.restype = C.c_int
+        lib.mcf_snowplan_summary_enable.argtypes = [P, PS]
+        lib.mcf_snowplan_summary_accumulate.restype = C.c_int
+        lib.mcf_snowplan_summary_accumulate.argtypes = [P, C.c_int32]
+        lib.mcf_snowplan_summary_fetch.restype = C.c_int
+        lib.mcf_snowplan_summary_fetch.argtypes = [P, C.c_int32, C.c_int32, c_double_p, C.c_int64]
+        lib.mcf_snowplan_summary_days.restype = C.c_int
+        lib.mcf_snowplan_summary_days.argtypes = [P, c_int32_p]
+        lib.mcf_snowplan_summary_reset.restype = C.c_int
+        lib.mcf_snowplan_summary_reset.argtypes = [P]
+        lib.mcf_snowrun_summary_table.restype = C.c_int
+        lib.mcf_snowrun_summary_table.argtypes = [c_int32_p, c_int32_p, c_int32_p, C.c_int32, c_int32_p]
+        lib.mcf_snowrun_summary_enable.restype = C.c_int
+        lib.mcf_snowrun_summary_enable.argtypes = [P, SS, PS]
+        lib.mcf_snowrun_summary_fetch.restype = C.c_int
+        lib.mcf_snowrun_summary_fetch.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_snowrun_summary_days.restype = C.c_int
+        lib.mcf_snowrun_summary_days.argtypes = [P, C.c_int32, c_int32_p]
+        lib.mcf_runmicrosnow_summary.restype = C.c_int
+        lib.mcf_runmicrosnow_summary.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), SS, PS, C.POINTER(SnowrunSummaryOut)]
+        lib.mcf_snowmodel1_summary.restype = C.c_int
+        lib.mcf_snowmodel1_summary.argtypes = [C.POINTER(SnowDriverIn), PS, C.POINTER(Multi), PO]
     lib.mcf_precompute_terrain.restype = C.c_int
     lib.mcf_precompute_terrain.argtypes = [C.POINTER(TerrainIn), C.POINTER(TerrainOut), C.c_int32]
     lib.mcf_precompute_terrain_multi.restype = C.c_int

@@ -2341,6 +2341,43 @@ int mcf_plan_summary_days(mcf_plan* p, int32_t* days) {
     return MCF_OK;
 }
 
+}  // extern "C"
+namespace mcf {   // mcf_snowrun.hip: the snow run's summaries
+// a spec judged without a plan; out_mask: the variables a run was created with (null: any)
+int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask) {
+    int requested[MCF_NOUT];
+    for (int v = 0; v < MCF_NOUT; ++v) requested[v] = !out_mask || out_mask[v] ? 0 : -1;
+    return check_summary_spec(s, ndays, requested);
+}
+int plan_summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch) {
+    return summary_fetch_pitched(p, var, stat, host_dst, row_pitch);
+}
+// Another table for an enabled summary (a second year on one snow-run handle: the day classes, and with them the days that are
+// never counted, belong to the year), and the state of the enable: nothing folded.
+int plan_summary_retable(mcf_plan* p, const int32_t* period_of_day) {
+    if (!p || !period_of_day) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
+    const int64_t nd = std::max(p->ndays, 1);
+    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)p->ndays), last((size_t)p->sum_nperiods, -1);
+    for (int d = 0; d < p->ndays; ++d) {
+        const int per = pod[(size_t)d] = period_of_day[d];
+        if (per < -1 || per >= p->sum_nperiods) return fail(MCF_ERR_ARG, "summary: a table entry is outside -1 .. nperiods - 1");
+        if (per < 0) continue;
+        prev[(size_t)d] = last[(size_t)per];
+        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
+        last[(size_t)per] = d;
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));                     // (a fold of the year before may still read the tables)
+    HIP_TRY(hipMemcpy(p->d_sum_pod, pod.data(), (size_t)nd * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_sum_prev, prev.data(), (size_t)nd * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_sum_next, next.data(), (size_t)nd * 4, hipMemcpyHostToDevice));
+    p->sum_pod = std::move(pod);
+    return mcf_plan_summary_reset(p);
+}
+}  // namespace mcf
+extern "C" {
+
 // twi_mean / out_pitch: a row block of a taller raster (mcf_runmicro_summary_multi), as for run_bioclim
 static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_summary_spec* spec, int32_t chunk_days,
                        mcf_summary_out* out, const double* twi_mean = nullptr, int64_t out_pitch = 0) {

@@ -320,6 +320,20 @@ void launch_summary_fin(const SummaryFinArgs& a, hipStream_t s);
 // init_codes: 4 bits per state row — 0: 0.0, 1: +inf, 2: -inf
 void launch_summary_init(double* state, int64_t total, int64_t N, int nrows, uint32_t init_codes, hipStream_t s);
 int summary_tiles_per_group(int cpb);
+// The same fold over step-major planes (the snow plan's chunk series): value of (step k of the call, cell c) at
+// series[i][k * N + c], step 0 = hour 0 of calendar day `day0`.  State, tables and the meaning of `row` as in SummaryAccArgs.
+struct SummaryPlanesArgs {
+    const double* series[5];     // the selected series, in selection order
+    double threshold[5];
+    int64_t N;
+    int32_t nsel;                // selected series (the grid's y)
+    int32_t nperiods, nrows;
+    int32_t row[6];
+    const int32_t *period_of_day, *prev_same, *next_same;
+    int32_t day0, ndays;
+    double* state;
+};
+void launch_summary_planes(const SummaryPlanesArgs& a, hipStream_t s);
 // dst[ci + ncells*k] = src(cells[ci], step0 + k), k < nsteps
 void launch_gather_cells(const RingView& src, int64_t step0, int64_t nsteps, const int64_t* cells, int64_t ncells, double* dst,
                          hipStream_t s);

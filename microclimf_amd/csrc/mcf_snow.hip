@@ -1554,6 +1554,15 @@ struct mcf_snowplan {
     int64_t keep_budget = -1;            // bytes of kept sets this plan may ALLOCATE in all (mcf_snowplan_set_keep_budget); -1: no limit of its own
     int64_t keep_allocated = 0;
     mcf::DevOwner kb;
+    // period summaries of the five series (mcf_snowplan_summary_enable; null state: off): the state [selected series][period]
+    // [state row][N] of mcf_kernels.h SummaryPlanesArgs, the day tables on the device, one statistic plane on its way to the host
+    double *d_ps_state = nullptr, *d_ps_plane = nullptr;
+    int32_t *d_ps_pod = nullptr, *d_ps_prev = nullptr, *d_ps_next = nullptr, *d_ps_days = nullptr;
+    int ps_nperiods = 0, ps_nrows = 0, ps_nsel = 0, ps_next_chunk = 0;
+    uint32_t ps_init_codes = 0, ps_bits = 0;      // ps_bits: the selected series as a mcf_snowplan_set_series mask
+    int ps_row[MCF_NSTAT] = {}, ps_sel1[5] = {};  // ps_sel1: 1-based place of a series in the state, 0: not selected
+    double ps_thr[5] = {};
+    std::vector<int32_t> ps_pod, ps_days;
     ~mcf_snowplan() { twork.release(); coarse_release(coarse); }
 };
 
@@ -3746,6 +3755,170 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
                            q.daymap, q.nosnow);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
+    return MCF_OK;
+}
+
+// ---- period summaries of the five series (include/mcf.h "period summaries of the snow run and of the snowpack"; the kernels:
+// mcf_summary.hip k_summary_planes / _fin / _init) ---------------------------------------------------------------------------------
+namespace mcf {   // mcf_snowrun.hip judges a spec with it before a device is needed
+int snowpack_spec_check(const mcf_snowpack_summary_spec* s, int64_t tsteps, int64_t chunk_steps) {
+    if (!s) return api_fail(MCF_ERR_ARG, "null mcf_snowpack_summary_spec");
+    if (s->nperiods < 1) return api_fail(MCF_ERR_ARG, "snowpack summary: nperiods must be at least 1");
+    if (chunk_steps <= 0) chunk_steps = 120;
+    if (chunk_steps % 24) return api_fail(MCF_ERR_ARG, "snowpack summary: chunk_steps must be a multiple of 24");
+    const int64_t ndays = tsteps / 24, covered = std::max<int64_t>(1, tsteps / chunk_steps) * (chunk_steps / 24);
+    if (ndays > 0 && !s->period_of_day) return api_fail(MCF_ERR_ARG, "snowpack summary: null period_of_day");
+    for (int64_t d = 0; d < ndays; ++d) {
+        const int per = s->period_of_day[d];
+        if (per < -1 || per >= s->nperiods)
+            return api_fail(MCF_ERR_ARG, "snowpack summary: period_of_day[" + std::to_string(d) + "] = " + std::to_string(per) +
+                                             " is outside -1 .. nperiods - 1");
+        if (per >= 0 && d >= covered)
+            return api_fail(MCF_ERR_ARG, "snowpack summary: day " + std::to_string(d) + " is counted but lies past the last whole chunk "
+                                             "(no chunk covers it: its table entry must be -1)");
+    }
+    int nv = 0, ns = 0;
+    for (int v = 0; v < 5; ++v) nv += s->series[v] ? 1 : 0;
+    for (int k = 0; k < MCF_NSTAT; ++k) ns += s->stat[k] ? 1 : 0;
+    if (nv == 0) return api_fail(MCF_ERR_ARG, "snowpack summary: no series selected");
+    if (ns == 0) return api_fail(MCF_ERR_ARG, "snowpack summary: no statistic selected");
+    for (int v = 0; v < 5; ++v)
+        if (s->series[v] && s->stat[MCF_STAT_HOURS_ABOVE] && std::isnan(s->threshold[v]))
+            return api_fail(MCF_ERR_ARG, "snowpack summary: HOURS_ABOVE needs a threshold for every selected series (NaN given)");
+    return MCF_OK;
+}
+// the selected series as a mcf_snowplan_set_series mask (bit 2 is totalSWE, bit 3 the ground snow depth)
+uint32_t snowpack_series_bits(const mcf_snowpack_summary_spec* s) {
+    static const uint32_t bit[5] = {1u, 2u, 8u, 4u, 16u};
+    uint32_t m = 0;
+    for (int v = 0; v < 5; ++v) m |= s->series[v] ? bit[v] : 0u;
+    return m;
+}
+}  // namespace mcf
+
+extern "C" int mcf_snowplan_summary_reset(mcf_snowplan* sp) {
+    if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
+    if (!sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no summary: mcf_snowplan_summary_enable first");
+    HIP_TRY(hipSetDevice(sp->device));
+    mcf::launch_summary_init(sp->d_ps_state, (int64_t)sp->ps_nsel * sp->ps_nperiods * sp->ps_nrows * sp->N, sp->N, sp->ps_nrows,
+                             sp->ps_init_codes, nullptr);
+    HIP_TRY(hipGetLastError());
+    sp->ps_days.assign((size_t)sp->ps_nperiods, 0);
+    sp->ps_next_chunk = 0;
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_summary_enable(mcf_snowplan* sp, const mcf_snowpack_summary_spec* spec) {
+    if (!sp || !spec) return mcf::api_fail(MCF_ERR_ARG, "null argument");
+    if (sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "snowpack summaries are already enabled on this plan");
+    int rc = mcf::snowpack_spec_check(spec, sp->T, sp->chunk);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(sp->device));
+    // state rows as mcf_plan_summary_enable lays them out: the sum's (it carries the NA rule), then one per other statistic
+    int nrows = 1, row[MCF_NSTAT];
+    uint32_t codes = 0;
+    for (int k = 0; k < MCF_NSTAT; ++k) {
+        row[k] = !spec->stat[k] ? -1 : k == MCF_STAT_MEAN ? 0 : nrows++;
+        if (row[k] > 0 && k == MCF_STAT_MIN) codes |= 1u << (4 * row[k]);
+        if (row[k] > 0 && k == MCF_STAT_MAX) codes |= 2u << (4 * row[k]);
+    }
+    int nsel = 0;
+    for (int v = 0; v < 5; ++v) nsel += spec->series[v] ? 1 : 0;
+    const int ndays = sp->T / 24;
+    const int64_t nd = std::max(ndays, 1), np = spec->nperiods;
+    const int64_t state_bytes = (int64_t)nsel * np * nrows * sp->N * 8, plane_bytes = np * sp->N * 8;
+    if ((rc = check_room(state_bytes + plane_bytes + (3 * nd + np) * 4))) return rc;
+    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)ndays), last((size_t)np, -1);
+    for (int d = 0; d < ndays; ++d) {
+        const int per = pod[(size_t)d] = spec->period_of_day[d];
+        if (per < 0) continue;
+        prev[(size_t)d] = last[(size_t)per];
+        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
+        last[(size_t)per] = d;
+    }
+    int32_t** tabs[3] = {&sp->d_ps_pod, &sp->d_ps_prev, &sp->d_ps_next};
+    const std::vector<int32_t>* host[3] = {&pod, &prev, &next};
+    for (int i = 0; i < 3; ++i) {
+        if ((rc = sp->b.make(tabs[i], nd))) return rc;
+        HIP_TRY(hipMemcpy(*tabs[i], host[i]->data(), (size_t)nd * 4, hipMemcpyHostToDevice));
+    }
+    if ((rc = sp->b.make(&sp->d_ps_days, np))) return rc;
+    if ((rc = sp->b.make(&sp->d_ps_plane, np * sp->N))) return rc;
+    double* state;
+    if ((rc = sp->b.make(&state, (int64_t)nsel * np * nrows * sp->N))) return rc;
+    sp->ps_nperiods = (int)np; sp->ps_nrows = nrows; sp->ps_nsel = nsel; sp->ps_init_codes = codes;
+    for (int k = 0; k < MCF_NSTAT; ++k) sp->ps_row[k] = row[k];
+    int place = 0;
+    for (int v = 0; v < 5; ++v) {
+        sp->ps_sel1[v] = spec->series[v] ? ++place : 0;
+        sp->ps_thr[v] = spec->series[v] && spec->stat[MCF_STAT_HOURS_ABOVE] ? spec->threshold[v] : 0.0;
+    }
+    sp->ps_bits = mcf::snowpack_series_bits(spec);
+    sp->ps_pod = std::move(pod);
+    sp->d_ps_state = state;
+    return mcf_snowplan_summary_reset(sp);
+}
+
+extern "C" int mcf_snowplan_summary_accumulate(mcf_snowplan* sp, int32_t ch) {
+    if (!sp) return mcf::api_fail(MCF_ERR_ARG, "null snow plan");
+    if (!sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no summary: mcf_snowplan_summary_enable first");
+    if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "chunk out of range");
+    if (ch < sp->ps_next_chunk)
+        return mcf::api_fail(MCF_ERR_STATE, "snowpack summary: chunks arrive in ascending order, each at most once (chunk " + std::to_string(ch) +
+                                                " after chunk " + std::to_string(sp->ps_next_chunk - 1) + ")");
+    if ((sp->series_valid & sp->ps_bits) != sp->ps_bits)
+        return mcf::api_fail(MCF_ERR_STATE, "snowpack summary: a selected series of the chunk was switched off (mcf_snowplan_set_series)");
+    const int cd = sp->chunk / 24, day0 = ch * cd;
+    const int nd = std::min(sp->chunk, sp->T - ch * sp->chunk) / 24;       // (whole days of the chunk: a one-chunk series shorter than a chunk)
+    sp->ps_next_chunk = ch + 1;
+    if (nd < 1) return MCF_OK;
+    HIP_TRY(hipSetDevice(sp->device));
+    mcf::SummaryPlanesArgs a{};
+    const double* const dev[5] = {sp->a.Tc, sp->a.Tg, sp->a.sdepg, sp->a.sdepc, sp->a.sden};      // (sdepc: totalSWE after the redistribution)
+    for (int v = 0; v < 5; ++v)
+        if (sp->ps_sel1[v]) {
+            a.series[sp->ps_sel1[v] - 1] = dev[v];
+            a.threshold[sp->ps_sel1[v] - 1] = sp->ps_thr[v];
+        }
+    a.N = sp->N; a.nsel = sp->ps_nsel; a.nperiods = sp->ps_nperiods; a.nrows = sp->ps_nrows;
+    for (int k = 0; k < MCF_NSTAT; ++k) a.row[k] = sp->ps_row[k];
+    a.period_of_day = sp->d_ps_pod; a.prev_same = sp->d_ps_prev; a.next_same = sp->d_ps_next;
+    a.day0 = day0; a.ndays = nd;
+    a.state = sp->d_ps_state;
+    mcf::launch_summary_planes(a, nullptr);          // the null stream: behind k_snowmodel, which wrote the series on it
+    HIP_TRY(hipGetLastError());
+    for (int d = day0; d < day0 + nd; ++d)
+        if (sp->ps_pod[(size_t)d] >= 0) sp->ps_days[(size_t)sp->ps_pod[(size_t)d]] += 1;
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_summary_fetch(mcf_snowplan* sp, int32_t series, int32_t stat, double* host_dst, int64_t row_pitch) {
+    if (!sp || !host_dst) return mcf::api_fail(MCF_ERR_ARG, "null argument");
+    if (!sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no summary: mcf_snowplan_summary_enable first");
+    if (series < 0 || series >= 5 || stat < 0 || stat >= MCF_NSTAT) return mcf::api_fail(MCF_ERR_ARG, "bad series / statistic");
+    if (!sp->ps_sel1[series]) return mcf::api_fail(MCF_ERR_ARG, "series was not selected in mcf_snowplan_summary_enable");
+    if (sp->ps_row[stat] < 0) return mcf::api_fail(MCF_ERR_ARG, "statistic was not selected in mcf_snowplan_summary_enable");
+    if (row_pitch == 0) row_pitch = sp->rows;
+    if (row_pitch < sp->rows) return mcf::api_fail(MCF_ERR_ARG, "row_pitch smaller than rows");
+    HIP_TRY(hipSetDevice(sp->device));
+    HIP_TRY(hipMemcpy(sp->d_ps_days, sp->ps_days.data(), (size_t)sp->ps_nperiods * 4, hipMemcpyHostToDevice));
+    mcf::SummaryFinArgs f{};
+    f.state = sp->d_ps_state + (int64_t)(sp->ps_sel1[series] - 1) * sp->ps_nperiods * sp->ps_nrows * sp->N;
+    f.N = sp->N; f.nperiods = sp->ps_nperiods; f.nrows = sp->ps_nrows;
+    f.stat = stat; f.row = sp->ps_row[stat];
+    f.days = sp->d_ps_days; f.out = sp->d_ps_plane;
+    mcf::launch_summary_fin(f, nullptr);
+    HIP_TRY(hipGetLastError());
+    const size_t width = (size_t)sp->rows * 8, bytes = (size_t)(sp->N * sp->ps_nperiods) * 8;
+    if (row_pitch != sp->rows) HIP_TRY(sp->dl.pitched(host_dst, (size_t)row_pitch * 8, sp->d_ps_plane, width, bytes / width));
+    else HIP_TRY(sp->dl.dense(host_dst, sp->d_ps_plane, bytes));
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_summary_days(mcf_snowplan* sp, int32_t* days) {
+    if (!sp || !days) return mcf::api_fail(MCF_ERR_ARG, "null argument");
+    if (!sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no summary: mcf_snowplan_summary_enable first");
+    for (int k = 0; k < sp->ps_nperiods; ++k) days[k] = sp->ps_days[(size_t)k];
     return MCF_OK;
 }
 

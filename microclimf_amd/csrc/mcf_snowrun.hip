@@ -16,6 +16,8 @@
 //            `subsetpointmodel(micropoint, days = snowdays)` does in R), the solver's maximum temperature over the no-snow subset
 //   pass 2   per chunk: restore + re-run the snow chunk unless its series were kept; the solver on the chunk's no-snow days at
 //            their own place in the ring slot; k_microsnow_ring over it; the slot's merged days to the caller's arrays
+//   sinks    besides the host arrays: period summaries (mcf_snowrun_summary_enable) — the snowpack's series folded
+//            behind every chunk of pass 1, the merged days of every ring slot behind pass 2's snow-day kernel
 //
 // Below ground (the `_below` entries, reqhgt < 0): the block's solver plan is a streamed below-ground plan over the no-snow days
 // (mcf_plan_create_streamed, mcf_plan_below_set_days) — Tbelowgroundv's running means see those days joined end to end, as the
@@ -56,6 +58,14 @@ bool micro_rasters_given(const mcf_snow_inputs& in);
 void micro_rasters_of_block(mcf_snow_inputs& in, HostCopies& rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
 const char* micro_series_missing(const mcf_snow_inputs& in);
 void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, int ndays, int nsub, HostCopies& keep);
+// the summaries' specs judged without a device, and the selected series as a mcf_snowplan_set_series mask
+int snowpack_spec_check(const mcf_snowpack_summary_spec* s, int64_t tsteps, int64_t chunk_steps);
+uint32_t snowpack_series_bits(const mcf_snowpack_summary_spec* s);
+}
+namespace mcf {   // mcf_api.hip
+int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask);
+int plan_summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch);
+int plan_summary_retable(mcf_plan* p, const int32_t* period_of_day);
 }
 
 namespace {
@@ -77,6 +87,7 @@ struct Block {
     std::vector<char> kept;                    // per chunk: its series stayed on the device
     mcf_grid_inputs gsub{};                    // the block's view of the solver's inputs (array weather: a chunk's forcing is uploaded from it)
     std::vector<uint8_t> skip;                 // pass 2: the tiles a run of days leaves out
+    bool sum_on = false;                       // the solver plan's summary has been enabled (block_setup)
 };
 
 // The raster in nb contiguous row blocks, block b (rows R*b/nb ..) on devs[b % nt] driven by worker b % nt, each with its snow
@@ -210,6 +221,13 @@ struct mcf_snowrun : SnowBlocks {
     bool keep = false;
     // what pass 2 did not have to do (mcf_snowrun_stats)
     std::atomic<int64_t> st_tile_days{0}, st_tile_days_left_out{0}, st_chunks_kept{0}, st_chunks_rerun{0};
+    // period summaries (mcf_snowrun_summary_enable): the caller's specs with their tables copied, the table of the current year
+    // (the caller's with the days of neither class taken out)
+    bool sum_micro = false, sum_pack = false, pass1_ever = false, pass2_done = false;
+    mcf_summary_spec mspec{};
+    mcf_snowpack_summary_spec pspec{};
+    std::vector<int32_t> mtable, ptable, mtable_year;
+    uint32_t pack_bits = 0;
 };
 
 namespace {
@@ -364,9 +382,12 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
         std::fill(h->snowday.begin(), h->snowday.end(), 0);
         std::fill(h->nosnowday.begin(), h->nosnowday.end(), 0);
         h->pass1_done = false;
+        h->pass1_ever = true;
+        h->pass2_done = false;
         const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
             h->each_block(w, [&](Block& k) -> int {
                 int rc2 = mcf_snowplan_reset(k.sp);
+                if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_reset(k.sp);      // (a second year starts the summaries over)
                 if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
                 if (!rc2) std::fill(k.kept.begin(), k.kept.end(), 0);
                 return rc2;
@@ -379,14 +400,17 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                     // series, pass 1 writes only what it reads itself of such a chunk (totalSWE, density: mcf_snowplan_set_series)
                     int32_t room = 0;
                     if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
-                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u));
+                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u | h->pack_bits));
                     return rc2;
                 });
                 snow_chunk(*h, w, ch, smod);
                 h->each_block(w, [&](Block& k) -> int {              // applycpp3 max / min of totalSWE
                     k.mx.assign((size_t)ns, 0.0); k.cmx.assign((size_t)ns, 0.0); k.mn.assign((size_t)ns, 0.0); k.cmn.assign((size_t)ns, 0.0);
-                    const int rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
-                    return rc2 ? rc2 : mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
+                    int rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MAX, k.mx.data(), k.cmx.data());
+                    if (!rc2) rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
+                    // the snowpack's summaries: from the series where they lie, before keep_chunk hands the buffers over
+                    if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_accumulate(k.sp, ch);
+                    return rc2;
                 });
                 mcf::reduce_on_first(w, [&] {
                     // extremes over the blocks (max / min skip blocks whose step held no value), then the chunk's day classes
@@ -503,6 +527,17 @@ int block_setup(Pass2& p, Block& k) {
     // ... and its per-cell state comes from a pass over them (complete = 1: the solver's first sweep)
     if (!rc && h->below && solver) rc = mcf_plan_below_prepare(k.plan, nullptr);
     if (!rc) rc = mcf_snowplan_set_series(k.sp, 31u);         // (pass 2's re-runs feed the snow microclimate)
+    // the summaries of the merged outputs: the day classes are known, the plan has not run — enabled with this year's table
+    // (a later year on the handle: the table replaced, nothing folded)
+    if (!rc && h->sum_micro) {
+        if (k.sum_on) rc = mcf::plan_summary_retable(k.plan, h->mtable_year.data());
+        else {
+            mcf_summary_spec spec = h->mspec;
+            spec.period_of_day = h->mtable_year.data();
+            rc = mcf_plan_summary_enable(k.plan, &spec);
+            k.sum_on = !rc;
+        }
+    }
     return rc;
 }
 
@@ -579,7 +614,7 @@ int fetch_days(Pass2& p, Block& k, int slot, int d0, int nd) {
     const mcf_snowrun* h = p.h;
     const int64_t R = h->R, C = h->C;
     for (int v = 0; v < MCF_NOUT; ++v) {
-        if (!h->opt.out[v]) continue;
+        if (!h->opt.out[v] || !p.out || !p.out->var[v]) continue;      // (no host array: a variable that is only summarised)
         double* dst = p.out->var[v] + k.r0 + R * C * (int64_t)d0 * 24;
         if (const int rc = mcf_plan_fetch_pitched(k.plan, slot, v, 0, (int64_t)nd * 24, dst, R)) return rc;
         // a day in NEITHER class (a melted pack's negative rounding residue: max <= 0 and min != 0) is no day of either
@@ -612,6 +647,9 @@ void chunk_loop(Pass2& p, Worker& w) {
         h->each_block(w, [&](Block& k) -> int {
             int rc = solver_days(p, k, slot, ch, d0, nd, has_snow);
             if (!rc && has_snow) rc = mcf_snowplan_microsnow(k.sp, k.plan, ch, slot, &h->nosnowday[(size_t)d0]);
+            // the slot holds the merged days: folded on the plan's stream — behind the solver's launches on it, and behind the
+            // snow-day kernel, whose null stream mcf_snowplan_microsnow has synchronised the device on before it returned
+            if (!rc && nd > 0 && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, slot, 0, d0, nd);
             if (!rc && nd > 0) rc = fetch_days(p, k, slot, d0, nd);
             return rc;
         });
@@ -628,11 +666,14 @@ void tail_days(Pass2& p, Worker& w) {
         for (int d0 = h->nchunks * cd; d0 < h->ndays && !w.failed(); d0 += cd) {
             const int nd = std::min(cd, h->ndays - d0);
             int rc = solver_days(p, k, 0, -1, d0, nd, false);
+            if (!rc && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, 0, 0, d0, nd);
             if (!rc) rc = fetch_days(p, k, 0, d0, nd);
             if (rc) return rc;
         }
+        if (h->sum_micro)                          // (a summary-only run has no fetch that waits for the plan's stream)
+            if (const int rc = mcf_plan_sync(k.plan)) return rc;
         for (int v = 0; v < MCF_NOUT; ++v)
-            if (h->opt.out[v])
+            if (h->opt.out[v] && p.out && p.out->var[v])
                 for (int64_t lc = (int64_t)h->ndays * 24 * C; lc < h->T * C; ++lc)
                     for (int64_t r = 0; r < k.nr; ++r) p.out->var[v][k.r0 + r + R * lc] = p.NA;
         return MCF_OK;
@@ -642,25 +683,142 @@ void tail_days(Pass2& p, Worker& w) {
 }  // namespace
 
 extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, double mat, mcf_outputs* out) {
-    if (!h || !out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
+    if (!h || (!out && !h->sum_micro)) return api_fail(MCF_ERR_ARG, "null snow-run argument");
     if (!h->pass1_done) return api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
     try {
-        for (int v = 0; v < MCF_NOUT; ++v)
-            if (h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
+        for (int v = 0; v < MCF_NOUT; ++v)       // (with a summary enabled a variable may go without a host array: it is folded only)
+            if (!h->sum_micro && h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
         Pass2 p{h, micro, mat, out};
         p.no_skip = getenv("MCF_SNOW_NO_TILE_SKIP") != nullptr;
         p.no_cells = getenv("MCF_SNOW_NO_CELL_GATHER") != nullptr;      // (A/B: tiles as the unit, as in round 4)
         day_lists(p);
         if (const int rc = snow_day_inputs(p)) return rc;
-        return mcf::run_workers(h->nt, [&](Worker& w) {
+        if (h->sum_micro) {
+            h->mtable_year.assign((size_t)std::max(h->ndays, 1), -1);
+            if (const int rc = mcf_snowrun_summary_table(h->mtable.data(), h->snowday.data(), h->nosnowday.data(), h->ndays, h->mtable_year.data()))
+                return rc;
+        }
+        h->pass2_done = false;
+        const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
             h->each_block(w, [&](Block& k) { return block_setup(p, k); });
             w.wait();
             chunk_loop(p, w);
             tail_days(p, w);
         });
+        h->pass2_done = !rc;
+        return rc;
     } catch (const std::exception& e) {
         return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_pass2: ") + e.what());
     }
+}
+
+// ---- period summaries of the run (include/mcf.h "period summaries of the snow run and of the snowpack") --------
+extern "C" int mcf_snowrun_summary_table(const int32_t* period_of_day, const int32_t* snowday, const int32_t* nosnowday, int32_t ndays,
+                                         int32_t* out) {
+    if (ndays < 0 || (ndays > 0 && (!period_of_day || !snowday || !nosnowday || !out)))
+        return api_fail(MCF_ERR_ARG, "mcf_snowrun_summary_table: null argument");
+    // a day in neither class is no day of either model (fetch_days: NA for every cell): never counted
+    for (int d = 0; d < ndays; ++d) out[d] = snowday[d] || nosnowday[d] ? period_of_day[d] : -1;
+    return MCF_OK;
+}
+
+static const char* const kSummaryBelow =
+    "period summaries of the snow run need reqhgt >= 0 (a below-ground run's solver plan is a streamed plan, which takes no summary)";
+
+// what can be judged of the two specs from the arguments alone
+static int check_summary_specs(const mcf_summary_spec* micro, const mcf_snowpack_summary_spec* pack, const mcf_options& opt, int64_t tsteps,
+                               int64_t chunk_steps) {
+    if (!micro && !pack) return api_fail(MCF_ERR_ARG, "snow-run summaries: null spec (one of the two is needed)");
+    if (opt.reqhgt < 0) return api_fail(MCF_ERR_ARG, kSummaryBelow);
+    if (micro)
+        if (const int rc = mcf::summary_spec_check(micro, tsteps / 24, opt.out)) return rc;
+    return pack ? mcf::snowpack_spec_check(pack, tsteps, chunk_steps) : MCF_OK;
+}
+
+extern "C" int mcf_snowrun_summary_enable(mcf_snowrun* h, const mcf_summary_spec* micro, const mcf_snowpack_summary_spec* pack) {
+    if (!h) return api_fail(MCF_ERR_ARG, "null snow run");
+    if (h->below) return api_fail(MCF_ERR_ARG, kSummaryBelow);
+    if (const int rc = check_summary_specs(micro, pack, h->opt, h->T, h->snow.chunk_steps)) return rc;
+    if (h->sum_micro || h->sum_pack) return api_fail(MCF_ERR_STATE, "snow-run summaries are already enabled on this run");
+    if (h->pass1_ever) return api_fail(MCF_ERR_STATE, "snow-run summaries are enabled before mcf_snowrun_pass1");
+    try {
+        if (pack) {
+            h->pspec = *pack;
+            h->ptable.assign(pack->period_of_day, pack->period_of_day + h->ndays);
+            h->pspec.period_of_day = h->ptable.data();
+            mcf::RestoreDevice restore;
+            for (Block& k : h->blocks)
+                if (const int rc = mcf_snowplan_summary_enable(k.sp, &h->pspec)) return rc;
+            h->pack_bits = mcf::snowpack_series_bits(pack);
+            h->sum_pack = true;
+        }
+        if (micro) {      // (the plans' own enable waits for the day classes: block_setup)
+            h->mspec = *micro;
+            h->mtable.assign(micro->period_of_day, micro->period_of_day + h->ndays);
+            h->mspec.period_of_day = h->mtable.data();
+            h->sum_micro = true;
+        }
+        return MCF_OK;
+    } catch (const std::exception& e) {
+        return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_summary_enable: ") + e.what());
+    }
+}
+
+extern "C" int mcf_snowrun_summary_fetch(mcf_snowrun* h, int32_t pack, int32_t var, int32_t stat, double* host_dst) {
+    if (!h || !host_dst) return api_fail(MCF_ERR_ARG, "null argument");
+    if (!(pack ? h->sum_pack : h->sum_micro)) return api_fail(MCF_ERR_STATE, "snow run: this summary was not enabled (mcf_snowrun_summary_enable)");
+    if (pack ? !h->pass1_done : !h->pass2_done)
+        return api_fail(MCF_ERR_STATE, pack ? "snow run: the snowpack's summaries are there after mcf_snowrun_pass1"
+                                            : "snow run: the summaries of the outputs are there after mcf_snowrun_pass2");
+    mcf::RestoreDevice restore;
+    for (Block& k : h->blocks) {      // a block's rows in place, through the row pitch
+        const int rc = pack ? mcf_snowplan_summary_fetch(k.sp, var, stat, host_dst + k.r0, h->R)
+                            : mcf::plan_summary_fetch_pitched(k.plan, var, stat, host_dst + k.r0, h->R);
+        if (rc) return rc;
+    }
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowrun_summary_days(mcf_snowrun* h, int32_t pack, int32_t* days) {
+    if (!h || !days) return api_fail(MCF_ERR_ARG, "null argument");
+    if (!(pack ? h->sum_pack : h->sum_micro)) return api_fail(MCF_ERR_STATE, "snow run: this summary was not enabled (mcf_snowrun_summary_enable)");
+    if (pack ? !h->pass1_done : !h->pass2_done) return api_fail(MCF_ERR_STATE, "snow run: no summary before the pass that folds it");
+    return pack ? mcf_snowplan_summary_days(h->blocks[0].sp, days) : mcf_plan_summary_days(h->blocks[0].plan, days);
+}
+
+extern "C" int mcf_runmicrosnow_summary(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu,
+                                        const mcf_summary_spec* micro_spec, const mcf_snowpack_summary_spec* pack_spec,
+                                        mcf_snowrun_summary_out* outs) {
+    if (!outs) return api_fail(MCF_ERR_ARG, "null snow-run argument");
+    if (!micro_spec && !pack_spec) return api_fail(MCF_ERR_ARG, "snow-run summaries: null spec (one of the two is needed)");
+    if (opt && opt->reqhgt < 0) return api_fail(MCF_ERR_ARG, kSummaryBelow);
+    int rc = check_create(in, opt, mu, false);
+    if (rc) return rc;
+    if ((rc = check_summary_specs(micro_spec, pack_spec, *opt, in->grid->tsteps, in->snow->chunk_steps))) return rc;
+    for (int k = 0; k < MCF_NSTAT; ++k) {
+        for (int v = 0; micro_spec && v < MCF_NOUT; ++v)
+            if (micro_spec->var[v] && micro_spec->stat[k] && !outs->micro.val[v][k])
+                return api_fail(MCF_ERR_ARG, "summary: a selected (variable, statistic) has a null buffer");
+        for (int v = 0; pack_spec && v < 5; ++v)
+            if (pack_spec->series[v] && pack_spec->stat[k] && !outs->pack.val[v][k])
+                return api_fail(MCF_ERR_ARG, "snowpack summary: a selected (series, statistic) has a null buffer");
+    }
+    mcf_snowrun* h = nullptr;
+    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
+    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
+    if ((rc = mcf_snowrun_summary_enable(h, micro_spec, pack_spec))) return rc;
+    if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
+    // (a run for the snowpack's summaries alone ends behind pass 1, unless the caller asks for the arrays)
+    if ((micro_spec || outs->arrays) && (rc = mcf_snowrun_pass2(h, in->micro, in->mat, outs->arrays))) return rc;
+    for (int k = 0; k < MCF_NSTAT; ++k) {
+        for (int v = 0; micro_spec && v < MCF_NOUT; ++v)
+            if (micro_spec->var[v] && micro_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 0, v, k, outs->micro.val[v][k]))) return rc;
+        for (int v = 0; pack_spec && v < 5; ++v)
+            if (pack_spec->series[v] && pack_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 1, v, k, outs->pack.val[v][k]))) return rc;
+    }
+    if (micro_spec && outs->micro.days && (rc = mcf_snowrun_summary_days(h, 0, outs->micro.days))) return rc;
+    if (pack_spec && outs->pack.days && (rc = mcf_snowrun_summary_days(h, 1, outs->pack.days))) return rc;
+    return MCF_OK;
 }
 
 static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out,
@@ -700,7 +858,9 @@ extern "C" int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in* in, const m
 // ---- the snow model alone: `.snowmodel1` / `.snowmodel2`'s chunk loop (mcf_snowmodel1 / 2: one plan on `device`, mu = NULL)
 // or over row blocks of ONE raster held by this process (include/mcf.h mcf_snowmodel1_multi: block b on devices[b % n_devices];
 // EVERY block's plan stays resident, the chunk loop couples the blocks at every chunk)
-static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device) {
+// spec / sout: the snowpack's period summaries (mcf_snowmodel1_summary, which has checked them), folded behind every chunk
+static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device,
+                     const mcf_snowpack_summary_spec* spec = nullptr, mcf_snowpack_summary_out* sout = nullptr) {
     if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     try {
         SnowBlocks sb;
@@ -715,8 +875,24 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
         if (rc) return rc;
         const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
         rc = mcf::run_workers(sb.nt, [&](Worker& w) {
-            for (int ch = 0; ch < nchunks; ++ch) snow_chunk(sb, w, ch, out);
+            if (spec) {
+                sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_enable(k.sp, spec); });
+                w.wait();
+            }
+            for (int ch = 0; ch < nchunks; ++ch) {
+                snow_chunk(sb, w, ch, out);
+                if (spec) sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_accumulate(k.sp, ch); });
+            }
+            if (spec)      // every block's rows of the planes in place, through the row pitch
+                sb.each_block(w, [&](Block& k) -> int {
+                    for (int v = 0; v < 5; ++v)
+                        for (int q = 0; q < MCF_NSTAT; ++q)
+                            if (spec->series[v] && spec->stat[q])
+                                if (const int rc2 = mcf_snowplan_summary_fetch(k.sp, v, q, sout->val[v][q] + k.r0, sb.R)) return rc2;
+                    return MCF_OK;
+                });
         });
+        if (!rc && spec && sout->days) rc = mcf_snowplan_summary_days(sb.blocks[0].sp, sout->days);
         if (!rc && !mu && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
         return rc;
     } catch (const std::exception& e) {
@@ -730,6 +906,21 @@ extern "C" int mcf_snowmodel1(const mcf_snowdriver_in* in, mcf_snowdriver_out* o
 extern "C" int mcf_snowmodel2(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, int32_t device) {
     if (in && !in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel2 takes array weather; data.frame climate: mcf_snowmodel1");
     return snowmodel(in, out, nullptr, device);
+}
+// mcf_snowmodel1 / _multi with the snowpack's period summaries as the only sink: no series leaves the device
+extern "C" int mcf_snowmodel1_summary(const mcf_snowdriver_in* in, const mcf_snowpack_summary_spec* spec, const mcf_multi* mu,
+                                      mcf_snowpack_summary_out* out) {
+    if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
+    if (in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel1_summary takes data.frame (vector) climate");
+    if (const int rc = mcf::snowpack_spec_check(spec, in->base.tsteps, in->chunk_steps)) return rc;
+    for (int v = 0; v < 5; ++v)
+        for (int q = 0; q < MCF_NSTAT; ++q)
+            if (spec->series[v] && spec->stat[q] && !out->val[v][q])
+                return api_fail(MCF_ERR_ARG, "snowpack summary: a selected (series, statistic) has a null buffer");
+    if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, "snow driver needs the raster and its dtm");
+    if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
+    mcf_snowdriver_out none{};
+    return snowmodel(in, &none, mu, 0, spec, out);
 }
 // `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
 // (mcf_snow.hip, k_fine_chunk) and hands pointm$umu out of the chunk's slab

@@ -7,6 +7,9 @@
 //                 and one lane per cell walks its 24 places (ring_pos) in hour order, folding them into registers.  The
 //                 next day's loads are in flight while the lanes fold.  The days of one period are taken together, in
 //                 ascending order, so a period's state is read once and written once per call however its days lie.
+// k_summary_planes  the same fold over step-major planes [step][cell] (the snow plan's chunk series): one lane
+//                 per cell along the cells, one selected series per blockIdx.y; a day's 24 values are 24 independent loads,
+//                 each a contiguous 512-byte run per wave, in flight together; no LDS, nothing shared between lanes.
 // k_summary_fin   state -> one statistic plane [N][nperiods]: the divide, the NA rule, the count as a double.
 // k_summary_init  the state before the first day: sums and counts 0, minimum +inf, maximum -inf (with the strict
 //                 comparisons that is the same as starting from the period's first value).
@@ -132,6 +135,60 @@ __global__ __launch_bounds__(kSumLanes) void k_summary_acc(SummaryAccArgs a) {
     }
 }
 
+__global__ __launch_bounds__(kSumLanes) void k_summary_planes(SummaryPlanesArgs a) {
+    const int k = (int)blockIdx.y;
+    const int64_t c = (int64_t)blockIdx.x * kSumLanes + threadIdx.x;
+    if (c >= a.N) return;                                         // (no barrier below: the last group's spare lanes leave)
+    const double* src = nullptr;
+    double thr = 0.0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)                                   // (constant indices: the argument block stays in scalar registers)
+        if (i == k) { src = a.series[i]; thr = a.threshold[i]; }
+    src += c;
+    double* st = a.state + (int64_t)k * a.nperiods * a.nrows * a.N;
+    const int end = a.day0 + a.ndays;
+
+    for (int d = a.day0; d < end; ++d) {
+        const int per = a.period_of_day[d];
+        if (per < 0 || a.prev_same[d] >= a.day0) continue;        // not counted, or its period has been folded already
+        double* sp = st + (int64_t)per * a.nrows * a.N + c;
+        double s = sp[0], mn = 0.0, mx = 0.0, dxs = 0.0, dns = 0.0, cnt = 0.0;
+        bool bad = is_na_bits(s);
+        if (a.row[MCF_STAT_MIN] >= 0) mn = sp[a.row[MCF_STAT_MIN] * a.N];
+        if (a.row[MCF_STAT_MAX] >= 0) mx = sp[a.row[MCF_STAT_MAX] * a.N];
+        if (a.row[MCF_STAT_MEAN_DAILY_MAX] >= 0) dxs = sp[a.row[MCF_STAT_MEAN_DAILY_MAX] * a.N];
+        if (a.row[MCF_STAT_MEAN_DAILY_MIN] >= 0) dns = sp[a.row[MCF_STAT_MEAN_DAILY_MIN] * a.N];
+        if (a.row[MCF_STAT_HOURS_ABOVE] >= 0) cnt = sp[a.row[MCF_STAT_HOURS_ABOVE] * a.N];
+        for (int e = d; e < end; e = a.next_same[e]) {            // the period's days inside the call, ascending
+            const double* day = src + (int64_t)(e - a.day0) * 24 * a.N;
+            double v[24];
+#pragma unroll
+            for (int h = 0; h < 24; ++h) v[h] = day[(int64_t)h * a.N];
+            double dmx = v[0], dmn = v[0];
+#pragma unroll
+            for (int h = 0; h < 24; ++h) {
+                bad |= v[h] != v[h];
+                s = s + v[h];
+                if (v[h] < mn) mn = v[h];
+                if (v[h] > mx) mx = v[h];
+                if (h > 0) {
+                    if (v[h] > dmx) dmx = v[h];
+                    if (v[h] < dmn) dmn = v[h];
+                }
+                if (v[h] > thr) cnt = cnt + 1.0;
+            }
+            dxs = dxs + dmx;
+            dns = dns + dmn;
+        }
+        sp[0] = bad ? na_value() : s;                             // the sum row carries the NA rule between calls
+        if (a.row[MCF_STAT_MIN] >= 0) sp[a.row[MCF_STAT_MIN] * a.N] = mn;
+        if (a.row[MCF_STAT_MAX] >= 0) sp[a.row[MCF_STAT_MAX] * a.N] = mx;
+        if (a.row[MCF_STAT_MEAN_DAILY_MAX] >= 0) sp[a.row[MCF_STAT_MEAN_DAILY_MAX] * a.N] = dxs;
+        if (a.row[MCF_STAT_MEAN_DAILY_MIN] >= 0) sp[a.row[MCF_STAT_MEAN_DAILY_MIN] * a.N] = dns;
+        if (a.row[MCF_STAT_HOURS_ABOVE] >= 0) sp[a.row[MCF_STAT_HOURS_ABOVE] * a.N] = cnt;
+    }
+}
+
 __global__ __launch_bounds__(256) void k_summary_fin(SummaryFinArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.N * a.nperiods) return;
@@ -176,6 +233,11 @@ void launch_summary_acc(const SummaryAccArgs& a, hipStream_t s) {
         case 42: launch_acc<42>(a, s); break;
         default: break;      // (the linear ring is refused by the host)
     }
+}
+
+void launch_summary_planes(const SummaryPlanesArgs& a, hipStream_t s) {
+    if (a.N <= 0 || a.nsel <= 0 || a.ndays <= 0) return;
+    hipLaunchKernelGGL(k_summary_planes, dim3((unsigned)((a.N + kSumLanes - 1) / kSumLanes), (unsigned)a.nsel), dim3(kSumLanes), 0, s, a);
 }
 
 void launch_summary_fin(const SummaryFinArgs& a, hipStream_t s) {

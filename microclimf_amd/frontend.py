@@ -1159,23 +1159,118 @@ def _runmicro_snow_one_call(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, p
             sd, nd = run.pass1()
             if reqhgt < 0 and not complete and nd.all():
                 continue
-            snowdays = np.flatnonzero(sd) + 1
-            if not snowdays.size:
-                return run.pass2(None, float(micropoint["matemp"]))
-            sdept = np.zeros(micropoint["ntme"])
-            sdept[np.asarray(subsetpointmodel(micropoint, days=snowdays)["subs"]) - 1] = 1
-            vg = sortl2(veg, sdept, reqhgt, pai_a)
-            res = dtm["res"]
-            xres = res if np.isscalar(res) else res[0]
-            ter = (terrain.precompute_terrain(z, xres, micropoint["zref"], device=device) if _terrain is None
-                   else _terrain(z, xres, micropoint["zref"]))
-            other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
-                     "lat": float(micropoint["lat"]), "lon": float(micropoint["long"]), "zref": float(micropoint["zref"]),
-                     "Smax": soilinit(soil)["Smax"]}
-            w = dict(micropoint["weather"])
-            w["umu"] = np.asarray(snow_inputs["umu"])
-            return run.pass2({"obstime": micropoint["obstime"], "climdata": w, "vegp": vg, "other": other},
+            return run.pass2(_one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain),
                              float(micropoint["matemp"]))
+
+
+def _one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain):
+    """gridmicrosnow1's inputs for the WHOLE series once pass 1 has given the snow days `sd` (one flag per day): `.sortl2`
+    vegetation weighted by them, bare-ground terrain, Smax, the weather with the snow model's umu; None for a year without a
+    snow day"""
+    snowdays = np.flatnonzero(sd) + 1
+    if not snowdays.size:
+        return None
+    sdept = np.zeros(micropoint["ntme"])
+    sdept[np.asarray(subsetpointmodel(micropoint, days=snowdays)["subs"]) - 1] = 1
+    vg = sortl2(veg, sdept, reqhgt, pai_a)
+    res = dtm["res"]
+    xres = res if np.isscalar(res) else res[0]
+    ter = (terrain.precompute_terrain(z, xres, micropoint["zref"], device=device) if _terrain is None
+           else _terrain(z, xres, micropoint["zref"]))
+    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
+             "lat": float(micropoint["lat"]), "lon": float(micropoint["long"]), "zref": float(micropoint["zref"]),
+             "Smax": soilinit(soil)["Smax"]}
+    w = dict(micropoint["weather"])
+    w["umu"] = np.asarray(snow_inputs["umu"])
+    return {"obstime": micropoint["obstime"], "climdata": w, "vegp": vg, "other": other}
+
+
+def _names(sel, every, what):
+    names = (sel,) if isinstance(sel, str) else tuple(sel)
+    if any(n not in every for n in names) or len(set(names)) != len(names):
+        raise ValueError(f"{what}: distinct names of {tuple(every)}")
+    return names
+
+
+def _pack_table(tab, tsteps: int, chunk_steps: int):
+    """the summary table for the snow model's series: the days past the last whole chunk belong to no chunk (NA in the series)"""
+    tab = np.array(tab, dtype=np.int32, copy=True)
+    tab[max(1, tsteps // chunk_steps) * (chunk_steps // 24):] = -1
+    return tab
+
+
+def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, snow_inputs: Mapping, *,
+                          periods="month", vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None,
+                          snow_vars: Sequence = (), snow_stats: Sequence = ("mean", "max", "hours_above"), snow_thresholds=None,
+                          pai_a=None, tfact: float = 1.5, device: int = 0, devices=None, n_blocks: int = 0, _terrain=None) -> dict:
+    """`runmicro(..., snow = TRUE)` reduced over time on the device: runmicro_snow(..., one_call=True) with the period summaries
+    of include/mcf.h as its only sink — per-cell statistics `stats` of the merged outputs `vars` and, with `snow_vars` (names
+    of Tc, Tg, groundsnowdepth, totalSWE, snowden), `snow_stats` of the snow model's series, over `periods` (summary_periods).
+    No [rows, cols, steps] array is made on either side.  Days that are neither snow nor no-snow days are never counted (they
+    are NA in runmicro_snow's arrays); the snow series' days past the last whole 5-day chunk neither.  `snow_thresholds`
+    defaults to 0 (hours_above of totalSWE: the snow-cover duration).  reqhgt == 0 masks the variables as runmicro does;
+    reqhgt < 0 is not available.  `devices` / `n_blocks`: row blocks over several devices.
+    -> {variable: {statistic: [rows, cols, nperiods]}, "snow": {series: {statistic: ...}, "days"}, "periods": labels, "days":
+    counted days per period, "snowdays", "nosnowdays": one flag per day}"""
+    from . import snow as S
+    if reqhgt < 0:
+        raise ValueError("period summaries of the snow run need reqhgt >= 0")
+    names = _names(vars, api._abi.OUT_NAMES, "vars")
+    snames = _names(snow_vars, api._abi.SNOWDRIVER_OUT, "snow_vars")
+    if not names and not snames:
+        raise ValueError("nothing selected: vars and snow_vars are both empty")
+    if snow_inputs is None:
+        raise ValueError("snow_inputs = runsnowmodel(weather, micropoint, vegp, soilc, dtm, inputs_only=True) is needed")
+    if len(micropoint["subs"]) != micropoint["ntme"]:
+        raise ValueError("the one-call snow run takes a complete micropoint")
+    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device)
+    a["tfact"] = float(tfact)
+    kept = [n for n, o in zip(api._abi.OUT_NAMES, a["out"]) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
+    if names and not kept:
+        raise ValueError("none of the selected variables exists at this reqhgt")
+    if not kept:                                                       # (the snowpack's summaries alone: the run still needs an output)
+        a["out"] = [1] + [0] * 9
+    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    snow = {k: v for k, v in snow_inputs.items() if k != "umu"}
+    tab, labels = summary_periods(a["obstime"], periods)
+    summary = dict(periods=tab, nperiods=len(labels), vars=kept, stats=stats, thresholds=thresholds) if kept else None
+    pack = None
+    if snames:
+        pack = dict(periods=_pack_table(tab, len(a["obstime"]["year"]), int(snow.get("chunk_steps", 120))), nperiods=len(labels),
+                    vars=snames, stats=snow_stats, thresholds=0.0 if snow_thresholds is None else snow_thresholds)
+    with S.SnowRun(a, snow, device=device, devices=devices, n_blocks=n_blocks) as run:
+        run.summary_enable(summary, pack)
+        sd, nd = run.pass1()
+        if summary is not None:
+            run.pass2(_one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain),
+                      float(micropoint["matemp"]), want_arrays=False)
+        res = run.fetch_summary()
+    res.setdefault("days", None)
+    res.update(periods=labels, snowdays=sd, nosnowdays=nd)
+    return res
+
+
+def runsnowmodel_summary(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
+                         vars: Sequence = ("totalSWE",), stats: Sequence = ("mean", "max", "hours_above"), thresholds=None,
+                         snowenv: str = "Taiga", snowinitd=0.0, snowinita=0.0, stfact: float = 0.01, devices=None, n_blocks: int = 0) -> dict:
+    """`runsnowmodel()` (the slow method, data.frame weather, a complete micropoint) reduced over time on the device: per-cell
+    statistics of the snow model's series `vars` over `periods` (summary_periods) instead of the five [rows, cols, steps]
+    arrays.  hours_above of totalSWE with the default threshold 0 is the snow-cover duration, max of totalSWE the peak snow
+    water equivalent.  The days past the last whole 5-day chunk (NA in runsnowmodel's arrays) are not counted.
+    -> {series: {statistic: [rows, cols, nperiods]}, "periods": labels, "days": counted days per period}"""
+    from . import snow as S
+    names = _names(vars, api._abi.SNOWDRIVER_OUT, "vars")
+    if not names:
+        raise ValueError("vars: nothing selected")
+    si = runsnowmodel(weather, micropoint, vegp, soilc, dtm, snowenv=snowenv, method="slow", snowinitd=snowinitd, snowinita=snowinita,
+                      stfact=stfact, inputs_only=True)
+    tab, labels = summary_periods(si["obstime"], periods)
+    res = S.snowmodel1_summary(si["obstime"], si["climdata"], si["pointm"], si["vegp"], si["other"], si["snowenv"], si["dtm"], si["res"],
+                               si["tfact"], periods=_pack_table(tab, len(si["obstime"]["year"]), 120), nperiods=len(labels), vars=names,
+                               stats=stats, thresholds=0.0 if thresholds is None else thresholds, devices=devices, n_blocks=n_blocks)
+    res["periods"] = labels
+    return res
 
 
 

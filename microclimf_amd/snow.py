@@ -238,6 +238,82 @@ def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
     return arrays
 
 
+def snowpack_summary_spec(periods, vars=("totalSWE",), stats=("mean", "min", "max"), thresholds=None, nperiods: int | None = None):
+    """include/mcf.h mcf_snowpack_summary_spec from `periods` (one integer per day, -1 = not counted; a day past the last whole
+    chunk must be -1), series names of _abi.SNOWDRIVER_OUT or indices, statistics of _abi.STAT_NAMES or indices, and
+    `thresholds` for hours_above: one number for every selected series or {series: number} (totalSWE with 0: the snow-cover
+    duration).  -> (spec, the selected series' indices, the selected statistics' indices, the array its table points into)"""
+    pod = np.ascontiguousarray(np.asarray(periods).astype(np.int32)).ravel()
+    names = _abi.SNOWDRIVER_OUT
+    vi = sorted({names.index(v) if isinstance(v, str) else int(v) for v in ((vars,) if isinstance(vars, str) else vars)})
+    si = sorted({_abi.STAT_NAMES.index(k) if isinstance(k, str) else int(k) for k in ((stats,) if isinstance(stats, str) else stats)})
+    if any(v < 0 or v >= 5 for v in vi) or any(k < 0 or k >= _abi.NSTAT for k in si):
+        raise ValueError(f"snowpack summary: series of {names}, statistics of {_abi.STAT_NAMES}")
+    sp = _abi.SnowpackSummarySpec()
+    sp.nperiods = int(nperiods) if nperiods is not None else int(pod.max()) + 1 if pod.size and pod.max() >= 0 else 1
+    sp.period_of_day = pod.ctypes.data_as(_abi.c_int32_p)
+    for v in vi:
+        sp.series[v] = 1
+        if isinstance(thresholds, Mapping):
+            t = thresholds.get(names[v], thresholds.get(v, float("nan")))
+        else:
+            t = float("nan") if thresholds is None else thresholds
+        sp.threshold[v] = float(t)
+    for k in si:
+        sp.stat[k] = 1
+    return sp, vi, si, pod
+
+
+def _micro_summary_spec(summary: Mapping):
+    from .api import summary_spec
+    sp, vi, si, pod = summary_spec(summary["periods"], summary.get("vars", ("Tz",)), summary.get("stats", ("mean", "min", "max")),
+                                   summary.get("thresholds"))
+    if summary.get("nperiods") is not None:
+        sp.nperiods = int(summary["nperiods"])
+    return sp, vi, si, pod
+
+
+def _pack_summary_spec(summary: Mapping):
+    return snowpack_summary_spec(summary["periods"], summary.get("vars", ("totalSWE",)), summary.get("stats", ("mean", "min", "max")),
+                                 summary.get("thresholds"), summary.get("nperiods"))
+
+
+def _planes(R, Cc, sp, vi, si):
+    return {(v, k): np.empty((R, Cc, max(int(sp.nperiods), 0)), dtype=np.float64, order="F") for v in vi for k in si}
+
+
+def _summary_dict(names, vi, si, planes, days):
+    res = {names[v]: {_abi.STAT_NAMES[k]: planes[v, k] for k in si} for v in vi}
+    res["days"] = days
+    return res
+
+
+def snowmodel1_summary(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *, periods, vars=("totalSWE",),
+                       stats=("mean", "min", "max"), thresholds=None, nperiods: int | None = None, chunk_steps: int = 120,
+                       devices=None, n_blocks: int = 0) -> dict:
+    """snowmodel1_chunks with the period summaries of the five series as its only sink (include/mcf.h mcf_snowmodel1_summary):
+    no [rows, cols, steps] array exists on either side.  `periods`: one integer per whole day, -1 for a day that is not counted
+    and for every day past the last whole chunk.  hours_above of totalSWE with threshold 0 is the snow-cover duration, max of
+    totalSWE the peak snow water equivalent.  -> {series: {statistic: [rows, cols, nperiods]}, "days": counted days per period}"""
+    lib = _abi.load()
+    R, Cc = np.shape(vegp["pai"])
+    m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
+    din = _abi.SnowDriverIn()
+    din.base = m.inputs
+    din.dtm = m.f64(dtm, (R, Cc), "dtm")
+    din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
+    sp, vi, si, _pod = snowpack_summary_spec(periods, vars, stats, thresholds, nperiods)
+    planes = _planes(R, Cc, sp, vi, si)
+    so = _abi.SnowpackSummaryOut()
+    for (v, k), a in planes.items():
+        so.val[v][k] = a.ctypes.data_as(_abi.c_double_p)
+    days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
+    so.days = days.ctypes.data_as(_abi.c_int32_p)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_snowmodel1_summary(C.byref(din), C.byref(sp), C.byref(mu[0]) if mu else None, C.byref(so)))
+    return _summary_dict(_abi.SNOWDRIVER_OUT, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+
+
 def _driver_in_array(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact, af_wind, wsa_s, chunk_steps):
     """mcf_snowdriver_in for array weather at the raster's resolution (include/mcf.h mcf_snowmodel2)"""
     R, Cc = np.shape(vegp["pai"])
@@ -946,6 +1022,29 @@ class SnowPlan:
     def run_chunk(self, chunk: int, tpic_mean: float):
         _abi.check(self._lib.mcf_snowplan_run_chunk(self._p, int(chunk), float(tpic_mean), C.byref(self._out)))
 
+    # ---- period summaries of the five series (include/mcf.h mcf_snowplan_summary_*) --------------------------------------
+    def summary_enable(self, periods, vars=("totalSWE",), stats=("mean", "min", "max"), thresholds=None, nperiods: int | None = None):
+        """arguments as snowpack_summary_spec; the state is allocated here"""
+        self._psum = snowpack_summary_spec(periods, vars, stats, thresholds, nperiods)
+        _abi.check(self._lib.mcf_snowplan_summary_enable(self._p, C.byref(self._psum[0])))
+
+    def summary_accumulate(self, chunk: int):
+        """folds the series of the chunk run last (after run_chunk, before keep_chunk): ascending chunks, each once"""
+        _abi.check(self._lib.mcf_snowplan_summary_accumulate(self._p, int(chunk)))
+
+    def summary_reset(self):
+        _abi.check(self._lib.mcf_snowplan_summary_reset(self._p))
+
+    def fetch_summary(self) -> dict:
+        """-> {series: {statistic: [rows, cols, nperiods]}, "days": counted days per period}"""
+        sp, vi, si, _pod = self._psum
+        planes = _planes(self.rows, self.cols, sp, vi, si)
+        for (v, k), a in planes.items():
+            _abi.check(self._lib.mcf_snowplan_summary_fetch(self._p, v, k, a.ctypes.data_as(_abi.c_double_p), 0))
+        days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
+        _abi.check(self._lib.mcf_snowplan_summary_days(self._p, days.ctypes.data_as(_abi.c_int32_p)))
+        return _summary_dict(_abi.SNOWDRIVER_OUT, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+
     # ---- the snow-day microclimate inside the chunk loop (include/mcf.h: two passes over the year) ------------------
     def reset(self):
         """Back to the series' start (hand-over depths, ages, snow surface): the second pass."""
@@ -1191,6 +1290,7 @@ class SnowRun:
         self._in.mat = 0.0
         self.rows, self.cols, self.tsteps = R, Cc, self._sm.tsteps
         self._mm = None
+        self._msum = self._psum = None      # (spec, variables, statistics, table) of the enabled summaries
 
     def keep(self, gigabytes: float):
         """Keep pass 1's snow chunks in device memory for pass 2, up to this much (include/mcf.h mcf_snowrun_keep; 0: off).
@@ -1220,6 +1320,36 @@ class SnowRun:
     def __exit__(self, *exc):
         self.close()
 
+    def summary_enable(self, summary: Mapping | None = None, pack_summary: Mapping | None = None):
+        """Period summaries folded on the device (include/mcf.h mcf_snowrun_summary_enable), before pass1.  Each a mapping with
+        "periods" (one integer per day, -1: not counted) and optionally "vars", "stats", "thresholds", "nperiods": `summary` over
+        the merged outputs (vars: output names the run was created with; days of neither class are never counted), `pack_summary`
+        over the snow model's five series (vars: names of _abi.SNOWDRIVER_OUT; days past the last whole chunk must be -1)."""
+        ms = _micro_summary_spec(summary) if summary is not None else None
+        ps = _pack_summary_spec(pack_summary) if pack_summary is not None else None
+        _abi.check(self._lib.mcf_snowrun_summary_enable(self._p, C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None))
+        self._msum, self._psum = ms, ps
+
+    def fetch_summary(self) -> dict:
+        """-> {variable: {statistic: [rows, cols, nperiods]}, "days": ...} of the outputs' summaries (after pass2) and, under
+        "snow", {series: {statistic: plane}, "days": ...} of the snowpack's (after pass1)"""
+        res = {}
+        for pack, spec, names in ((0, self._msum, _abi.OUT_NAMES), (1, self._psum, _abi.SNOWDRIVER_OUT)):
+            if spec is None:
+                continue
+            sp, vi, si, _pod = spec
+            planes = _planes(self.rows, self.cols, sp, vi, si)
+            for (v, k), a in planes.items():
+                _abi.check(self._lib.mcf_snowrun_summary_fetch(self._p, pack, v, k, a.ctypes.data_as(_abi.c_double_p)))
+            days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
+            _abi.check(self._lib.mcf_snowrun_summary_days(self._p, pack, days.ctypes.data_as(_abi.c_int32_p)))
+            d = _summary_dict(names, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+            if pack:
+                res["snow"] = d
+            else:
+                res.update(d)
+        return res
+
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
         sd, nd = np.zeros(self.days, np.int32), np.zeros(self.days, np.int32)
@@ -1228,28 +1358,40 @@ class SnowRun:
                                                nd.ctypes.data_as(_abi.c_int32_p)))
         return (sd, nd, smod) if want_smod else (sd, nd)
 
-    def pass2(self, micro: Mapping | None, mat: float) -> dict:
+    def pass2(self, micro: Mapping | None, mat: float, want_arrays: bool = True):
         """micro = {"obstime", "climdata" (with umu), "vegp" (`.sortl2`), "other" (bare-ground terrain, lat, lon, zref, Smax)} for
-        the WHOLE series, or None when the year has no snow day -> the ten merged outputs"""
+        the WHOLE series, or None when the year has no snow day -> the ten merged outputs.  want_arrays False (with a summary
+        enabled): the merged days are folded only, no [rows, cols, steps] array is allocated or filled -> None"""
         mi = None
         if micro is not None:
             self._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], self.array_weather, micro=True)
             mi = C.byref(self._mm.inputs)
+        if not want_arrays:
+            _abi.check(self._lib.mcf_snowrun_pass2(self._p, mi, float(mat), None))
+            return None
         outs, arrays = self._alloc_outputs()
         _abi.check(self._lib.mcf_snowrun_pass2(self._p, mi, float(mat), C.byref(outs)))
         return arrays
 
 
 def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, *, device: int = 0, devices=None, n_blocks: int = 0,
-                  want_smod: bool = False, cells_per_block: int = 0, below: bool = False):
+                  want_smod: bool = False, cells_per_block: int = 0, below: bool = False, summary: Mapping | None = None,
+                  pack_summary: Mapping | None = None, want_arrays: bool = True):
     """mcf_runmicrosnow1 / mcf_runmicrosnow1_multi: the whole snow run as ONE library call (arguments as `SnowRun`, `micro` as
-    `SnowRun.pass2`) -> the merged outputs[, smod].  below: reqhgt < 0 through mcf_runmicrosnow1_below / _below_multi."""
+    `SnowRun.pass2`) -> the merged outputs[, smod].  below: reqhgt < 0 through mcf_runmicrosnow1_below / _below_multi.
+    summary / pack_summary (mappings as for SnowRun.summary_enable): the run through mcf_runmicrosnow_summary, either weather
+    geometry -> {"out": the merged outputs, or None with want_arrays False (nothing of size cells x steps is moved), "summary":
+    as SnowRun.fetch_summary, "snowdays", "nosnowdays"[, "smod"]}"""
     from .marshal import alloc_outputs
     with SnowRun(grid, snow, device=device, cells_per_block=cells_per_block, handle=False) as run:
         if micro is not None:
             run._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], run.array_weather, micro=True)
             run._in.micro = C.pointer(run._mm.inputs)
         run._in.mat = float(mat)
+        if summary is not None or pack_summary is not None:
+            if below:
+                raise ValueError("period summaries of the snow run need reqhgt >= 0")
+            return _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, devices, n_blocks)
         outs, arrays = alloc_outputs(run._gm)
         so, smod = _driver_out(run.rows, run.cols, run.tsteps) if want_smod else (None, None)
         sop = C.byref(so) if so is not None else None
@@ -1262,6 +1404,43 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
             fn = lib.mcf_runmicrosnow1_below if below else lib.mcf_runmicrosnow2 if run.array_weather else lib.mcf_runmicrosnow1
             _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(outs), sop))
     return (arrays, smod) if want_smod else arrays
+
+
+def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, devices, n_blocks) -> dict:
+    from .marshal import alloc_outputs
+    lib = _abi.load()
+    ms = _micro_summary_spec(summary) if summary is not None else None
+    ps = _pack_summary_spec(pack_summary) if pack_summary is not None else None
+    so = _abi.SnowrunSummaryOut()
+    res, keep = {"out": None, "summary": {}}, []
+    for spec, names, dst, key in ((ms, _abi.OUT_NAMES, so.micro, None), (ps, _abi.SNOWDRIVER_OUT, so.pack, "snow")):
+        if spec is None:
+            continue
+        sp, vi, si, _pod = spec
+        planes = _planes(run.rows, run.cols, sp, vi, si)
+        for (v, k), a in planes.items():
+            dst.val[v][k] = a.ctypes.data_as(_abi.c_double_p)
+        days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
+        dst.days = days.ctypes.data_as(_abi.c_int32_p)
+        d = _summary_dict(names, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+        if key:
+            res["summary"][key] = d
+        else:
+            res["summary"].update(d)
+    if want_arrays:
+        outs, res["out"] = alloc_outputs(run._gm)
+        so.arrays = C.pointer(outs)
+    if want_smod:
+        sm, res["smod"] = _driver_out(run.rows, run.cols, run.tsteps)
+        so.smod = C.pointer(sm)
+    nd = run.tsteps // 24
+    res["snowdays"], res["nosnowdays"] = np.zeros(nd, np.int32), np.zeros(nd, np.int32)
+    so.snowday = res["snowdays"].ctypes.data_as(_abi.c_int32_p)
+    so.nosnowday = res["nosnowdays"].ctypes.data_as(_abi.c_int32_p)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_runmicrosnow_summary(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
+                                            C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
+    return res
 
 
 def runmicrosnow2(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, **kw):
