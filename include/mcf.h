@@ -59,7 +59,9 @@ extern "C" {
                              *    mcf_runmicrosnow1_below_multi, mcf_snowrun_create_below, mcf_snowmodelq1, mcf_canintfrac_device,
                              *    mcf_meltmu_device, mcf_snowmodelq2, mcf_meltmu2_device, mcf_plan_summary_*, mcf_runmicro_summary,
                              *    mcf_runmicro_summary_multi, mcf_snowmodel2_coarse, mcf_snow_expand_coarse_device, mcf_snowplan_summary_*,
-                             *    mcf_snowrun_summary_*, mcf_runmicrosnow_summary, mcf_snowmodel1_summary) */
+                             *    mcf_snowrun_summary_*, mcf_runmicrosnow_summary, mcf_snowmodel1_summary,
+                             *    mcf_microsnow_expand_coarse_device, mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse,
+                             *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -277,8 +279,18 @@ int mcf_plan_run_days_cells(mcf_plan *plan, int32_t day0, int32_t ndays, int32_t
 int mcf_plan_set_mxtc(mcf_plan *plan, double mxtc);
 /* Array forcing (at the raster's resolution): the same per CELL (src/microclimfCpp.cpp:2467-2471) over the days with
  * dayflag[d] != 0 — the temperature series of `in` streamed once more, a run of flagged days at a time.  Also since this
- * version: mcf_plan_run_days_at accepts a run of days INSIDE the days a slot's forcing was uploaded for, with array forcing. */
+ * version: mcf_plan_run_days_at accepts a run of days INSIDE the days a slot's forcing was uploaded for, with array forcing.
+ * A plan with COARSE array forcing (array_forcing == 2) folds the flagged days of its resident series (`in` is not read, may be
+ * NULL): the interpolated, altitude-corrected temperature of the plan's create-time maximum, started from -273.15 — a maximum is
+ * order-free, so bit for bit the cap of a coarse plan created on the host-subset coarse arrays. */
 int mcf_plan_set_mxtc_days(mcf_plan *plan, const mcf_grid_inputs *in, const int32_t *dayflag, int32_t ndays);
+/* Layered vegetation (veg_layers > 1): replace the day -> layer map the plan made from lyr_st / lyr_ed; layer_of_day[d] in
+ * 0 .. veg_layers - 1, or -1 for a day no layer covers; ndays = tsteps / 24.  For callers that solve a SUBSET of the days and deal
+ * the subset to layers themselves (`.runmodel3Cpp` on `.runmicronosnow`'s day subset renumbers the layers it uses,
+ * R/internal.R:1391-1399, so a layer that serves no day of the subset shifts the ones behind it). */
+int mcf_plan_set_day_layers(mcf_plan *plan, const int32_t *layer_of_day, int32_t ndays);   /* layer_of_day NULL: the plan's own table again */
+/* Array forcing (fine or coarse): the per-cell temperature cap's maximum air temperature as the plan holds it now, [rows, cols]. */
+int mcf_plan_fetch_mxtc(mcf_plan *plan, double *host_dst);
 /* reqhgt<0: after every day has been solved into slot 0, smooth the stored
  * ground-temperature series into Tz (Tbelowgroundv, cpp:1474-1539).  Not for a streamed plan (MCF_ERR_STATE). */
 int mcf_plan_belowground(mcf_plan *plan);
@@ -987,6 +999,12 @@ int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in *in, const mcf_options 
 int mcf_snowrun_create_below(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi, mcf_snowrun **run);
 void mcf_snowrun_destroy(mcf_snowrun *run);
 int32_t mcf_snowrun_days(const mcf_snowrun *run);     /* tsteps / 24 */
+/* Between mcf_snowrun_pass1 and mcf_snowrun_pass2, layered vegetation: the solver plans' day -> layer map (mcf_plan_set_day_layers).
+ * The run solves the no-snow days with the layer the WHOLE-series table gives them; a caller that wants `.runmodel3Cpp`'s dealing of
+ * the no-snow SUBSET passes that here, in whole-series days and rows of the whole series' arrays (the two differ when a layer keeps
+ * steps of the subset without being any of its days' mode: `.sortvegp` cuts the arrays by steps, the table has a row per day mode).
+ * MCF_ERR_STATE outside the two passes.  The map holds for this period: the next mcf_snowrun_pass1 puts the plans' own table back. */
+int mcf_snowrun_set_day_layers(mcf_snowrun *run, const int32_t *layer_of_day, int32_t ndays);
 /* What pass 2 was spared (diagnostics; tests assert which path ran): stats[0] tile-days of the solver's days that are snow days as
  * well, [1] of them left out (tiles wholly under snow, mcf_plan_run_days_masked; or, where few cells are not under snow, all tiles
  * but the ones those cells fill, mcf_plan_run_days_cells), [2] snow chunks whose series had stayed in HBM,
@@ -1303,6 +1321,63 @@ typedef struct mcf_snowcoarse_in {
 } mcf_snowcoarse_in;
 int mcf_snowmodel2_coarse(const mcf_snowcoarse_in *in, mcf_snowfast2_out *out, int32_t device);
 int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in *in, int64_t step0, int64_t nsteps, double *const fine[13], int32_t device);
+/* The snow-day microclimate's weather from coarse arrays: `.prepsnowinputs2` (R/internal.R:3445-3579) on the device.  Its nine
+ * series are NOT `.snowmodel2`'s: temperature and pressure are resampled unmasked, the vapour pressure is resampled (the caller
+ * forms `ea` = satvap(temp) x relhum / 100 on the climate grid, as it forms windu / windv), with altcorrect 1 / 2 the temperature
+ * moves by elevd x lapse rate (5 / 1000, or the moist adiabatic one of the resampled temp / ea / pres), relative humidity is
+ * ea / satvap(temp) x 100 kept within 20 .. 100 in every altitude mode, swdown / difrad / lwdown / precip / umu are `.cca`
+ * (NA on the dtm's holes), the wind speed comes from the resampled components.  `pres` is the coarse pressure as the climate
+ * data have it; with altcorrect > 0 the library takes it to sea level on the coarse grid and back up by the cell's own factor.
+ * mcf_microsnow_expand_coarse_device: the expansion kernel alone (upload, one launch, download) for steps step0 .. step0 +
+ * nsteps - 1; fine[k]: [rows, cols, nsteps] in the order temp, relhum, pres, swdown, difrad, lwdown, windspeed, precip, umu (what
+ * mcf_gridmicrosnow2 takes as clim); a NULL fine[k] is a series that is not wanted (the kernel's series mask), at least one is
+ * needed.  MCF_ERR_ARG before any device is touched, the message starting with the entry's name: a null argument, coarse_rows /
+ * coarse_cols < 1, a position outside the coarse grid, altcorrect outside 0..2 or > 0 without coarse_dtm, 24 x coarse cells x
+ * 8 B >= 2^32, step0 < 0, nsteps < 1 or step0 + nsteps > tsteps. */
+typedef struct mcf_microcoarse_in {
+    int64_t rows, cols, tsteps;
+    const double *dtm;                              /* [rows, cols], NaN = NA */
+    int64_t coarse_rows, coarse_cols;
+    const double *coarse_rowpos, *coarse_colpos;   /* [rows], [cols] */
+    int32_t altcorrect;                             /* 0, 1 (fixed lapse rate), 2 (moist adiabatic) */
+    int32_t reserved;
+    const double *coarse_dtm;                       /* [crows, ccols], NA read as 0; needed when altcorrect > 0 */
+    /* [crows, ccols, tsteps].  windu / windv: windspeed x cos / sin of the coarse CELL's own direction */
+    const double *temp, *ea, *pres, *swdown, *difrad, *lwdown, *windu, *windv, *precip, *umu;
+} mcf_microcoarse_in;
+int mcf_microsnow_expand_coarse_device(const mcf_microcoarse_in *in, int64_t step0, int64_t nsteps, double *const fine[9], int32_t device);
+/* mcf_runmicrosnow2_coarse: the array-weather snow run (mcf_runmicrosnow2) with every coarse array left coarse — `.snowmodel2`'s
+ * loop as mcf_snowmodel2_coarse runs it, the solver on a coarse plan (grid->array_forcing == 2: the whole coarse series resident,
+ * mcf_plan_upload_forcing_days a no-op), and gridmicrosnow2 on slabs the kernel above fills per run of consecutive snow days.
+ * Nothing of size cells x steps goes up; the ten outputs (and smod, if asked for) come down.
+ *   grid    runmicro2Cpp's coarse arguments (array_forcing = 2)
+ *   snow    as for mcf_snowmodel2_coarse
+ *   micro   the ten coarse arrays of the microclimate's weather; its own set (the two preparations differ in wind direction and
+ *           in the reference-height scaling), resident beside the snow model's: 10 x coarse cells x T x 8 B
+ *   micro_static  gridmicrosnow2's other inputs for the WHOLE series as mcf_runmicrosnow2's `micro`, the nine weather arrays
+ *           null: obstime [T], clim.winddir [T], `.sortl2` vegetation, bare-ground terrain, lats / lons, zref, Smax.  May be
+ *           NULL only if the period has no snow day
+ *   mat     as mcf_runmicrosnow2
+ * Pass 2 re-runs a snow chunk from its checkpoint (the expansion runs again inside it), solves the chunk's no-snow days whole
+ * (mcf_snowrun_stats reports nothing left out; the per-cell temperature cap is taken over the no-snow days by
+ * mcf_plan_set_mxtc_days, bit for bit that of a coarse plan made on the host-subset arrays) and runs the snow-day kernel over
+ * the slot.  smod->umu: all T steps, the series NA on the dtm's holes, as mcf_snowmodel2_coarse.  One block on one device.
+ * mcf_snowrun_create_coarse: the staged form; mcf_snowrun_pass1 / _pass2 (its `micro` = micro_static) / _destroy work on the
+ * handle.  multi: NULL, or one block on one device; umu_out: where pass 1 hands pointm$umu [rows, cols, T], or NULL.
+ * MCF_ERR_ARG before a device is touched, the message starting with the entry's name: a null argument (named); the three groups
+ * disagreeing in rows / cols / T, coarse rows / cols, positions or altcorrect; grid->array_forcing != 2; reqhgt < 0; more than
+ * one block or device; what mcf_snowmodel2_coarse and the expansion entry refuse of their groups.  MCF_ERR_NOMEM if a chunk's
+ * series and the nine slabs do not fit. */
+typedef struct mcf_microsnow_coarse_in {
+    const mcf_grid_inputs *grid;
+    const mcf_snowcoarse_in *snow;
+    const mcf_microcoarse_in *micro;
+    const mcf_snow_inputs *micro_static;
+    double mat;
+} mcf_microsnow_coarse_in;
+int mcf_runmicrosnow2_coarse(const mcf_microsnow_coarse_in *in, const mcf_options *opt, mcf_outputs *out, const mcf_snowfast2_out *smod);
+int mcf_snowrun_create_coarse(const mcf_microsnow_coarse_in *in, const mcf_options *opt, const mcf_multi *multi, double *umu_out,
+                              mcf_snowrun **run);
 /* manCpp(src/microclimfCpp.cpp:597-627): circular trailing mean, via daily means for windows beyond 48 steps. */
 int mcf_man(int64_t n, const double *x, int32_t window, double *out);
 

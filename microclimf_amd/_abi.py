@@ -270,6 +270,25 @@ class MicrosnowIn(C.Structure):
                 ("mat", C.c_double)]
 
 
+# the ten coarse arrays of the snow-day microclimate's weather (mcf_microcoarse_in), and its nine series on the raster in the order
+# mcf_microsnow_expand_coarse_device returns them
+MICRO_COARSE = ("temp", "ea", "pres", "swdown", "difrad", "lwdown", "windu", "windv", "precip", "umu")
+MICRO_FINE_SERIES = ("temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed", "precip", "umu")
+
+
+class MicroCoarseIn(C.Structure):
+    """include/mcf.h mcf_microcoarse_in"""
+    _fields_ = ([("rows", C.c_int64), ("cols", C.c_int64), ("tsteps", C.c_int64), ("dtm", c_double_p), ("coarse_rows", C.c_int64),
+                 ("coarse_cols", C.c_int64), ("coarse_rowpos", c_double_p), ("coarse_colpos", c_double_p), ("altcorrect", C.c_int32),
+                 ("reserved", C.c_int32), ("coarse_dtm", c_double_p)] + [(k, c_double_p) for k in MICRO_COARSE])
+
+
+class MicrosnowCoarseIn(C.Structure):
+    """include/mcf.h mcf_microsnow_coarse_in"""
+    _fields_ = [("grid", C.POINTER(GridInputs)), ("snow", C.POINTER(SnowCoarseIn)), ("micro", C.POINTER(MicroCoarseIn)),
+                ("micro_static", C.POINTER(SnowInputs)), ("mat", C.c_double)]
+
+
 class SnowrunSummaryOut(C.Structure):
     """include/mcf.h mcf_snowrun_summary_out"""
     _fields_ = [("micro", SummaryOut), ("pack", SnowpackSummaryOut), ("arrays", C.POINTER(Outputs)), ("smod", C.POINTER(SnowDriverOut)),
@@ -327,6 +346,8 @@ EXPORTS = (
     "mcf_snowplan_summary_enable", "mcf_snowplan_summary_accumulate", "mcf_snowplan_summary_fetch", "mcf_snowplan_summary_days",
     "mcf_snowplan_summary_reset", "mcf_snowrun_summary_table", "mcf_snowrun_summary_enable", "mcf_snowrun_summary_fetch",
     "mcf_snowrun_summary_days", "mcf_runmicrosnow_summary", "mcf_snowmodel1_summary",
+    "mcf_microsnow_expand_coarse_device", "mcf_runmicrosnow2_coarse", "mcf_snowrun_create_coarse",
+    "mcf_plan_set_day_layers", "mcf_snowrun_set_day_layers", "mcf_plan_fetch_mxtc",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -732,6 +753,19 @@ def load() -> C.CDLL:
         lib.mcf_runmicrosnow_summary.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), SS, PS, C.POINTER(SnowrunSummaryOut)]
         lib.mcf_snowmodel1_summary.restype = C.c_int
         lib.mcf_snowmodel1_summary.argtypes = [C.POINTER(SnowDriverIn), PS, C.POINTER(Multi), PO]
+    if hasattr(lib, "mcf_runmicrosnow2_coarse"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        MC = C.POINTER(MicrosnowCoarseIn)
+        lib.mcf_microsnow_expand_coarse_device.restype = C.c_int
+        lib.mcf_microsnow_expand_coarse_device.argtypes = [C.POINTER(MicroCoarseIn), C.c_int64, C.c_int64, C.POINTER(c_double_p), C.c_int32]
+        lib.mcf_runmicrosnow2_coarse.restype = C.c_int
+        lib.mcf_runmicrosnow2_coarse.argtypes = [MC, OP, OU, C.POINTER(SnowFast2Out)]
+        lib.mcf_snowrun_create_coarse.restype = C.c_int
+        lib.mcf_snowrun_create_coarse.argtypes = [MC, OP, C.POINTER(Multi), c_double_p, C.POINTER(P)]
+        lib.mcf_plan_fetch_mxtc.restype = C.c_int
+        lib.mcf_plan_fetch_mxtc.argtypes = [P, c_double_p]
+        for fn in (lib.mcf_plan_set_day_layers, lib.mcf_snowrun_set_day_layers):
+            fn.restype = C.c_int
+            fn.argtypes = [P, c_int32_p, C.c_int32]
     lib.mcf_precompute_terrain.restype = C.c_int
     lib.mcf_precompute_terrain.argtypes = [C.POINTER(TerrainIn), C.POINTER(TerrainOut), C.c_int32]
     lib.mcf_precompute_terrain_multi.restype = C.c_int

@@ -452,6 +452,26 @@ class Plan:
         """Replace the series' maximum air temperature (the snow branch solves a subset of the days)."""
         _abi.check(self._lib.mcf_plan_set_mxtc(self._p, float(mxtc)))
 
+    def set_mxtc_days(self, dayflag):
+        """array forcing: the per-cell temperature cap over the days with dayflag != 0 (include/mcf.h mcf_plan_set_mxtc_days); a
+        coarse plan folds its resident series, a fine one streams its temperature array again"""
+        flags = np.ascontiguousarray(dayflag, dtype=np.int32)
+        _abi.check(self._lib.mcf_plan_set_mxtc_days(self._p, C.byref(self._m.inputs), flags.ctypes.data_as(_abi.c_int32_p), int(flags.size)))
+
+    def set_day_layers(self, layer_of_day=None):
+        """layered vegetation: the day -> layer map (include/mcf.h mcf_plan_set_day_layers); None: the plan's own table again"""
+        if layer_of_day is None:
+            _abi.check(self._lib.mcf_plan_set_day_layers(self._p, None, self.ndays))
+            return
+        lod = np.ascontiguousarray(layer_of_day, dtype=np.int32)
+        _abi.check(self._lib.mcf_plan_set_day_layers(self._p, lod.ctypes.data_as(_abi.c_int32_p), int(lod.size)))
+
+    def fetch_mxtc(self) -> np.ndarray:
+        """array forcing: the per-cell maximum air temperature the plan holds now, [rows, cols]"""
+        a = np.empty((self.rows, self.cols), dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_fetch_mxtc(self._p, a.ctypes.data_as(_abi.c_double_p)))
+        return a
+
     def belowground(self):
         _abi.check(self._lib.mcf_plan_belowground(self._p))
 

@@ -59,6 +59,7 @@ struct mcf_plan {
     int cpb = 16;
     int layers = 1;
     int32_t* d_daylayer = nullptr;
+    std::vector<int32_t> daylayer0;      // the day -> layer map of lyr_st / lyr_ed (mcf_plan_set_day_layers(NULL) goes back to it)
     mcf_options opt{};
     mcf::Globals g{};
     int hiy = 8760;
@@ -756,6 +757,7 @@ static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_
         }
         if ((rc = dalloc(p, &tmp, (int64_t)dl.size() * 4))) return rc;
         p->d_daylayer = (int32_t*)tmp;
+        p->daylayer0 = dl;
         HIP_TRY(hipMemcpyAsync(p->d_daylayer, dl.data(), dl.size() * 4, hipMemcpyHostToDevice, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
@@ -1008,9 +1010,24 @@ int mcf_plan_set_mxtc(mcf_plan* p, double mxtc) {
 // runmicro2Cpp computes when `.runmicronosnow` hands it the no-snow-day SUBSET (R/internal.R:3689); streamed through the plan's
 // forcing stage, a run of consecutive flagged days at a time
 int mcf_plan_set_mxtc_days(mcf_plan* p, const mcf_grid_inputs* in, const int32_t* dayflag, int32_t ndays) {
-    if (!p || !in || !dayflag) return fail(MCF_ERR_ARG, "null argument");
-    if (!p->af || p->coarse) return fail(MCF_ERR_STATE, "mcf_plan_set_mxtc_days: a plan with (fine) array forcing");
+    if (!p || !dayflag || (!in && !p->coarse)) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->af) return fail(MCF_ERR_STATE, "mcf_plan_set_mxtc_days: a plan with array forcing");
     if (ndays < 0 || ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
+    if (p->coarse) {
+        // coarse forcing: the flagged days of the resident series, folded by the day-flagged form of the create-time kernel
+        HIP_TRY(hipSetDevice(p->device));
+        if (ndays == 0) { mcf::launch_fill(p->d_mxtc, p->N, -273.15, p->stream); return MCF_OK; }
+        void* tmp = nullptr;
+        if (const int rc = dalloc(p, &tmp, (int64_t)ndays * 4)) return rc;
+        struct Release { mcf_plan* p; void* q; ~Release() { p->dev.release(q); } } release{p, tmp};      // on every exit path
+        HIP_TRY(hipMemcpyAsync(tmp, dayflag, (size_t)ndays * 4, hipMemcpyHostToDevice, p->stream));
+        const int64_t slab = (int64_t)p->crows * p->ccols * std::max<int64_t>(p->tsteps, 1);
+        mcf::launch_mxtc_coarse_days(p->d_force, slab, p->crows, p->ccols, (const int32_t*)tmp, ndays, p->d_crowpos, p->d_ccolpos,
+                                     p->rows, p->N, p->altcorrect, p->d_elevd, p->d_pkfac, p->d_mxtc, p->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(p->stream));      // (the caller's flags have been read, the kernel has read its copy)
+        return MCF_OK;
+    }
     if (!in->clim.tc) return fail(MCF_ERR_ARG, "missing forcing array: tc");
     HIP_TRY(hipSetDevice(p->device));
     mcf::launch_fill(p->d_mxtc, p->N, -273.15, p->stream);
@@ -1023,6 +1040,33 @@ int mcf_plan_set_mxtc_days(mcf_plan* p, const mcf_grid_inputs* in, const int32_t
         HIP_TRY(hipGetLastError());
         d = e;
     }
+    return MCF_OK;
+}
+
+// layered vegetation: the day -> layer map replaced (mcf_snowrun_set_day_layers: a snow run's solver sees the no-snow days only, and
+// a caller that mirrors how `.runmodel3Cpp` deals a day SUBSET to layers knows the subset after pass 1)
+int mcf_plan_set_day_layers(mcf_plan* p, const int32_t* layer_of_day, int32_t ndays) {
+    if (!p) return fail(MCF_ERR_ARG, "null argument");
+    if (p->layers <= 1 || !p->d_daylayer) return fail(MCF_ERR_STATE, "mcf_plan_set_day_layers: the plan's vegetation has one layer");
+    if (ndays != p->ndays) return fail(MCF_ERR_ARG, "mcf_plan_set_day_layers: one entry per day of the plan");
+    if (!layer_of_day) layer_of_day = p->daylayer0.data();      // null: the table made from lyr_st / lyr_ed again
+    for (int d = 0; d < ndays; ++d)
+        if (layer_of_day[d] < -1 || layer_of_day[d] >= p->layers)
+            return fail(MCF_ERR_ARG, "mcf_plan_set_day_layers: layer_of_day[" + std::to_string(d) + "] is no layer of the plan (-1: none)");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipMemcpy(p->d_daylayer, layer_of_day, (size_t)ndays * 4, hipMemcpyHostToDevice));
+    return MCF_OK;
+}
+
+// array forcing: the per-cell maximum air temperature the plan holds now, [rows, cols] (diagnostics; tests compare the day-flagged
+// form with a plan created on the subset series)
+int mcf_plan_fetch_mxtc(mcf_plan* p, double* host_dst) {
+    if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->af || !p->d_mxtc) return fail(MCF_ERR_STATE, "mcf_plan_fetch_mxtc: a plan with array forcing");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    HIP_TRY(hipMemcpy(host_dst, p->d_mxtc, (size_t)p->N * 8, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 

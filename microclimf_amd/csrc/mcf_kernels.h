@@ -346,6 +346,10 @@ void launch_tile_series(const double* src, int64_t nsteps, const RingView& dst, 
 void launch_mxtc_coarse(const double* force, int64_t stride, int crows, int ccols, int tsteps, const double* rowpos,
                         const double* colpos, int64_t rows, int64_t N, int altcorrect, const double* elevd,
                         const double* pkfac, double* mx, hipStream_t s);
+// the same maximum over the days with dayflag[d] != 0 only (device array [ndays]), started from -273.15
+void launch_mxtc_coarse_days(const double* force, int64_t stride, int crows, int ccols, const int32_t* dayflag, int ndays,
+                             const double* rowpos, const double* colpos, int64_t rows, int64_t N, int altcorrect,
+                             const double* elevd, const double* pkfac, double* mx, hipStream_t s);
 struct PackNcArgs {
     RingView src[10];        // each variable's slot view
     int64_t step0;           // first step (of the slot) of this launch

@@ -1903,6 +1903,43 @@ void launch_mxtc_coarse(const double* force, int64_t stride, int crows, int ccol
     hipLaunchKernelGGL(k_mxtc_coarse, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, force, stride, crows, ccols, tsteps,
                        rowpos, colpos, rows, N, altcorrect, elevd, pkfac, mx);
 }
+// k_mxtc_coarse over the flagged days only (the snow run's no-snow days, cpp:2467-2471 on the subset `.runmicronosnow` hands the
+// solver): the per-step expression is k_mxtc_coarse's, a maximum is order-free — the cap of a coarse plan created on the
+// host-subset arrays, bit for bit.  The flags are uniform: no lane diverges on them.
+__global__ __launch_bounds__(256) void k_mxtc_coarse_days(const double* __restrict__ force, int64_t stride, int crows, int ccols,
+                                                          const int32_t* __restrict__ dayflag, int ndays,
+                                                          const double* __restrict__ rowpos, const double* __restrict__ colpos,
+                                                          int64_t rows, int64_t N, int altcorrect, const double* __restrict__ elevd,
+                                                          const double* __restrict__ pkfac, double* __restrict__ mx) {
+    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const CoarseTap tap(rowpos[c % rows], colpos[c / rows], crows, ccols);
+    const int64_t cN = (int64_t)crows * ccols;
+    MathK MK;
+    MK.set();
+    const double ed = altcorrect ? elevd[c] : 0.0, pf = altcorrect ? pkfac[c] : 1.0;
+    double m = -273.15;
+    for (int d = 0; d < ndays; ++d) {
+        if (!dayflag[d]) continue;
+        for (int k = d * 24; k < d * 24 + 24; ++k) {
+            const double* q = force + cN * k;
+            double v = tap(q + (int64_t)TF_TC * stride);
+            if (altcorrect == 1) v += 0.005 * ed;
+            if (altcorrect == 2) {
+                const double ea = satvap_r(v, MK) * tap(q + (int64_t)TF_ES * stride) / 100.0;
+                v += lapserate_r(v, ea, tap(q + (int64_t)TF_PK * stride) * pf) * ed;
+            }
+            if (v > m) m = v;
+        }
+    }
+    mx[c] = m;
+}
+void launch_mxtc_coarse_days(const double* force, int64_t stride, int crows, int ccols, const int32_t* dayflag, int ndays,
+                             const double* rowpos, const double* colpos, int64_t rows, int64_t N, int altcorrect,
+                             const double* elevd, const double* pkfac, double* mx, hipStream_t s) {
+    hipLaunchKernelGGL(k_mxtc_coarse_days, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, force, stride, crows, ccols, dayflag,
+                       ndays, rowpos, colpos, rows, N, altcorrect, elevd, pkfac, mx);
+}
 void launch_gather_cells(const RingView& src, int64_t step0, int64_t nsteps, const int64_t* cells, int64_t ncells, double* dst,
                          hipStream_t s) {
     const int64_t n = ncells * nsteps;

@@ -1474,6 +1474,10 @@ static void coarse_release(SnowCoarseState* cs);
 static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns);
 static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last);
 static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns);
+// the snow-day microclimate's own resident coarse set (mcf_runmicrosnow2_coarse, behind mcf_microsnow_expand_coarse_device)
+struct MicroCoarseState;
+static void micro_coarse_release(MicroCoarseState* ms);
+static int micro_coarse_fill(mcf_snowplan* sp, int64_t hour0, int ns, int64_t slab_off, uint32_t mask, double* precip_into);
 struct mcf_snowplan {
     int device = 0;
     int64_t rows = 0, cols = 0, N = 0, row0 = 0, rows_total = 0;
@@ -1531,6 +1535,11 @@ struct mcf_snowplan {
     const double* h_micro[kMicroSeries] = {};
     double* d_micro[kMicroSeries] = {};
     const double* MicroArgs::* micro_arg[kMicroSeries] = {};      // the kernel argument each slab is
+    // coarse array weather: the ten coarse arrays of the microclimate's weather stay on the device (no h_micro), a chunk's snow
+    // days are expanded from them into d_micro by one kernel per run of consecutive snow days
+    MicroCoarseState* mcoarse = nullptr;
+    double t_micro_fine = 0;             // ms, MCF_TIMING: that expansion, pass 2's launches
+    int n_micro_fine = 0;
     int32_t outsel[MCF_NOUT] = {};
     std::vector<int32_t> sub_of_day;     // absolute day -> day of the snow-day subset series, or -1
     int32_t *d_daymap = nullptr, *d_nosnow = nullptr;     // [chunk days]
@@ -1563,7 +1572,7 @@ struct mcf_snowplan {
     int ps_row[MCF_NSTAT] = {}, ps_sel1[5] = {};  // ps_sel1: 1-based place of a series in the state, 0: not selected
     double ps_thr[5] = {};
     std::vector<int32_t> ps_pod, ps_days;
-    ~mcf_snowplan() { twork.release(); coarse_release(coarse); }
+    ~mcf_snowplan() { twork.release(); coarse_release(coarse); micro_coarse_release(mcoarse); }
 };
 
 namespace {
@@ -1864,6 +1873,10 @@ void snowplan_print_timing(const mcf_snowplan* sp) {
                 "chunk (%.1f GB/s written), gridmodelsnow + redistribute %.3f ms per chunk\n", sp->nchunks, sp->chunk, (long long)sp->N,
                 sp->t_terrain, sp->t_fine / sp->nchunks, sp->t_fine > 0 ? bytes * sp->nchunks / (sp->t_fine * 1e6) : 0.0,
                 sp->t_model / sp->nchunks);
+        if (sp->mcoarse && sp->n_micro_fine > 0)      // written bytes from shapes: 9 x 8 B x N x snow steps
+            fprintf(stderr, "[mcf] microsnow coarse expansion: %d snow steps, %.3f ms in all, %.3f ms per %d steps (%.1f GB/s written)\n",
+                    sp->n_micro_fine, sp->t_micro_fine, sp->t_micro_fine * sp->chunk / sp->n_micro_fine, sp->chunk,
+                    9.0 * 8.0 * (double)sp->N * sp->n_micro_fine / (sp->t_micro_fine * 1e6));
         return;
     }
     fprintf(stderr, "[mcf] snowmodel1: %d chunks of %d steps, %lld cells: terrain + tpi %.2f ms, gridmodelsnow + "
@@ -3226,7 +3239,228 @@ extern "C" int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in* in, int64_
     HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
+
+// ---- gridmicrosnow2's nine series from coarse arrays (`.prepsnowinputs2`, int:3445-3579; snow.py _fine_micro_inputs) -------------
+namespace {
+// The snow-day microclimate's weather is not the snow model's: vapour pressure is resampled (the host forms it on the climate
+// grid), temperature and pressure are NOT masked by the dtm, relative humidity comes from the resampled vapour pressure in every
+// altitude mode and is kept within 20 .. 100.  o[]: the nine series in the order of each_micro_series, [hours][N] as
+// k_microsnow_ring<true> reads them; mask bit f: series f is written (the set-up's scan reads temp and precip alone).
+struct MicroFineArgs {
+    int64_t N, hour0;                  // hour0: the first hour in the resident coarse arrays
+    int32_t altcorrect;
+    uint32_t mask;
+    CoarseGeo geo;
+    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
+    const double *temp, *ea, *pres, *swdown, *difrad, *lwdown, *windu, *windv, *precip, *umu;   // pres: at sea level when altcorrect > 0
+    double* o[kMicroSeries];
+};
+enum { MF_TEMP = 0, MF_RELHUM, MF_PRES, MF_SWDOWN, MF_DIFRAD, MF_LWDOWN, MF_WINDSPEED, MF_PRECIP, MF_UMU };
+constexpr uint32_t kMicroAll = (1u << kMicroSeries) - 1;
+// hours kb .. ke - 1 of cell c: the host's operations in the host's order, no contraction (the mask is uniform: no lane diverges)
+__device__ __forceinline__ void micro_cell_hours(const MicroFineArgs& a, int64_t c, int kb, int ke) {
+#pragma clang fp contract(off)
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    const double z = a.dtm[c], NA = na_real();
+    const bool hole = isnan(z);
+    const uint32_t m = a.mask;
+    const bool want_t = (m & (1u << MF_TEMP | 1u << MF_RELHUM)) != 0;
+    const bool want_ea = (m >> MF_RELHUM & 1u) || (want_t && a.altcorrect == 2);
+    const bool want_p = (m >> MF_PRES & 1u) || (want_t && a.altcorrect == 2);
+    double up = 1.0, elevd = 0.0;
+    if (a.altcorrect) {
+        up = pow((293 - 0.0065 * z) / 293, 5.26);
+        elevd = tap(a.zc) - z;
+    }
+    for (int k = kb; k < ke; ++k) {
+        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
+        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
+        double ea = 0.0, pres = 0.0;
+        if (want_ea) ea = tap(a.ea + h);
+        if (want_p) {
+            pres = tap(a.pres + h);
+            if (a.altcorrect) pres = pres * up;
+        }
+        if (want_t) {
+            double temp = tap(a.temp + h);
+            if (a.altcorrect) {
+                const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
+                temp = lr * elevd + temp;
+            }
+            if (m >> MF_TEMP & 1u) a.o[MF_TEMP][o] = temp;
+            if (m >> MF_RELHUM & 1u) {
+                double relhum = (ea / snow_satvap_r(temp)) * 100;
+                if (relhum < 20.0) relhum = 20.0;              // np.clip: NaN stays NaN
+                if (relhum > 100.0) relhum = 100.0;
+                a.o[MF_RELHUM][o] = relhum;
+            }
+        }
+        if (m >> MF_PRES & 1u) a.o[MF_PRES][o] = pres;
+        if (m >> MF_SWDOWN & 1u) a.o[MF_SWDOWN][o] = cca(a.swdown);
+        if (m >> MF_DIFRAD & 1u) a.o[MF_DIFRAD][o] = cca(a.difrad);
+        if (m >> MF_LWDOWN & 1u) a.o[MF_LWDOWN][o] = cca(a.lwdown);
+        if (m >> MF_WINDSPEED & 1u) {
+            const double wu = tap(a.windu + h), wv = tap(a.windv + h);
+            a.o[MF_WINDSPEED][o] = sqrt(wu * wu + wv * wv);
+        }
+        if (m >> MF_PRECIP & 1u) a.o[MF_PRECIP][o] = cca(a.precip);
+        if (m >> MF_UMU & 1u) a.o[MF_UMU][o] = cca(a.umu);
+    }
+}
+// k_fine_chunk's lane map: lanes along the cells, blockIdx.y over groups of kFineHours hours, g0 the launch's first group
+__global__ __launch_bounds__(256) void k_micro_fine(MicroFineArgs a, int ns, int g0) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    micro_cell_hours(a, c, kb, ke);
+}
+void launch_micro_fine(const MicroFineArgs& fa, int ns, hipStream_t stream) {
+    const int groups = (ns + kFineHours - 1) / kFineHours;
+    for (int g0 = 0; g0 < groups; g0 += 32768)
+        hipLaunchKernelGGL(k_micro_fine, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, stream,
+                           fa, ns, g0);
+}
+// the ten coarse arrays in the order of the kernel's arguments
+template <class In, class F>
+void each_micro_coarse(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
+    using A = MicroFineArgs;
+    f(in.temp, &A::temp, "temp"); f(in.ea, &A::ea, "ea"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
+    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv");
+    f(in.precip, &A::precip, "precip"); f(in.umu, &A::umu, "umu");
+}
+// what the entries that take a mcf_microcoarse_in refuse before a device is touched
+int microcoarse_checks(const mcf_microcoarse_in* mi, const char* entry) {
+    const std::string e = std::string(entry) + ": ";
+    auto fail = [&](const std::string& m) { return mcf::api_fail(MCF_ERR_ARG, e + m); };
+    if (!mi) return fail("null argument: micro");
+    if (mi->rows <= 0 || mi->cols <= 0 || mi->tsteps <= 0 || mi->tsteps > (1 << 30) || mi->rows * mi->cols >= ((int64_t)1 << 29))
+        return fail("micro: rows, cols, tsteps out of range (at least 1; at most 2^29 - 1 cells, 2^30 steps)");
+    if (mi->coarse_rows < 1 || mi->coarse_cols < 1) return fail("micro: coarse_rows and coarse_cols must be at least 1");
+    if (mi->altcorrect < 0 || mi->altcorrect > 2) return fail("micro: altcorrect must be 0, 1 or 2");
+    if (mi->altcorrect > 0 && !mi->coarse_dtm) return fail("micro: altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
+    const char* missing = nullptr;
+    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+    need(mi->coarse_rowpos, "coarse_rowpos"); need(mi->coarse_colpos, "coarse_colpos");
+    each_micro_coarse(*mi, [&](auto* host, auto, const char* name) { need(host, name); });
+    need(mi->dtm, "dtm");
+    if (missing) return fail(std::string("null input: micro ") + missing);
+    if (!positions_inside(mi->coarse_rowpos, mi->rows, mi->coarse_rows) || !positions_inside(mi->coarse_colpos, mi->cols, mi->coarse_cols))
+        return fail("micro: coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
+    if ((double)mi->coarse_rows * (double)mi->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
+        return fail("micro: coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    return MCF_OK;
+}
+// geometry, dtm and the ten coarse arrays of hours h0 .. h0 + nh - 1 on the device; the pressure is taken to sea level on the coarse
+// grid here when altcorrect > 0, as coarse_upload does; d_dtm: the raster's dtm if the caller has it there already
+int micro_coarse_upload(mcf::DevOwner& b, const mcf_microcoarse_in* mi, int64_t h0, int64_t nh, const double* d_dtm, MicroFineArgs* fa) {
+    const int64_t N = mi->rows * mi->cols, CC = mi->coarse_rows * mi->coarse_cols;
+    int rc = MCF_OK;
+    memset(fa, 0, sizeof *fa);
+    fa->N = N; fa->altcorrect = mi->altcorrect; fa->mask = kMicroAll;
+    fa->geo.rows = (int32_t)mi->rows; fa->geo.crows = (int32_t)mi->coarse_rows; fa->geo.ccols = (int32_t)mi->coarse_cols;
+    if ((rc = b.up(&fa->geo.rowpos, mi->coarse_rowpos, mi->rows, "coarse_rowpos"))) return rc;
+    if ((rc = b.up(&fa->geo.colpos, mi->coarse_colpos, mi->cols, "coarse_colpos"))) return rc;
+    if (d_dtm) fa->dtm = d_dtm;
+    else if ((rc = b.up(&fa->dtm, mi->dtm, N, "dtm"))) return rc;
+    std::vector<double> psl;
+    if (mi->altcorrect) {
+        std::vector<double> zc((size_t)CC), down((size_t)CC);
+        for (int64_t q = 0; q < CC; ++q) {
+            zc[(size_t)q] = std::isnan(mi->coarse_dtm[q]) ? 0.0 : mi->coarse_dtm[q];
+            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
+        }
+        psl.resize((size_t)(CC * nh));
+        for (int64_t k = 0; k < nh; ++k)
+            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = mi->pres[(h0 + k) * CC + q] / down[(size_t)q];
+        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
+    }
+    each_micro_coarse(*mi, [&](auto* host, auto member, const char* name) {
+        if (!rc) rc = b.up(&(fa->*member), mi->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
+    });
+    return rc;
+}
+}  // namespace
+
+// the snow plan's own resident coarse set of the snow-day microclimate (ten arrays of the whole series; not the snow model's)
+struct MicroCoarseState {
+    MicroFineArgs fa;
+};
+static void micro_coarse_release(MicroCoarseState* ms) { delete ms; }
+// hours hour0 .. hour0 + ns - 1 of the series in `mask` into the plan's slabs from step slab_off on; precip_into: where the
+// precipitation goes instead of its own slab (the set-up's scan streams temp and precip through the first two slabs)
+static int micro_coarse_fill(mcf_snowplan* sp, int64_t hour0, int ns, int64_t slab_off, uint32_t mask, double* precip_into) {
+    MicroFineArgs fa = sp->mcoarse->fa;
+    fa.hour0 = hour0; fa.mask = mask;
+    for (int f = 0; f < kMicroSeries; ++f) fa.o[f] = sp->d_micro[f] + slab_off * sp->N;
+    if (precip_into) fa.o[MF_PRECIP] = precip_into;
+    const bool timing = getenv("MCF_TIMING") != nullptr && mask == kMicroAll;
+    Events evs;
+    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    launch_micro_fine(fa, ns, nullptr);
+    HIP_TRY(hipGetLastError());
+    if (timing) {
+        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
+        HIP_TRY(hipEventSynchronize(evs.e[1]));
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+        sp->t_micro_fine += ms;
+        sp->n_micro_fine += ns;
+    }
+    return MCF_OK;
+}
+
+extern "C" int mcf_microsnow_expand_coarse_device(const mcf_microcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[9],
+                                                  int32_t device) {
+    const char* entry = "mcf_microsnow_expand_coarse_device";
+    int rc;
+    if (!in) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: in");
+    if (!fine) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine");
+    if ((rc = microcoarse_checks(in, entry))) return rc;
+    uint32_t mask = 0;                   // a null fine[f]: series f is not wanted
+    for (int f = 0; f < kMicroSeries; ++f) mask |= fine[f] ? 1u << f : 0u;
+    if (!mask) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[] (every series is null)");
+    if (step0 < 0 || nsteps < 1 || step0 > in->tsteps - nsteps)
+        return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": step0 >= 0, nsteps >= 1 and step0 + nsteps <= tsteps are needed");
+    if ((rc = pick_device(device))) return rc;
+    const int64_t N = in->rows * in->cols, CC = in->coarse_rows * in->coarse_cols;
+    if ((rc = check_room((9 * nsteps + 1) * N * 8 + 10 * CC * nsteps * 8))) return rc;
+    mcf::DevOwner b;
+    MicroFineArgs fa;
+    if ((rc = micro_coarse_upload(b, in, step0, nsteps, nullptr, &fa))) return rc;
+    fa.mask = mask;
+    for (int f = 0; f < kMicroSeries; ++f)
+        if (fine[f] && (rc = b.make(&fa.o[f], N * nsteps))) return rc;
+    launch_micro_fine(fa, (int)nsteps, nullptr);
+    HIP_TRY(hipGetLastError());
+    mcf::ToHost dl;
+    for (int f = 0; f < kMicroSeries; ++f)
+        if (fine[f]) HIP_TRY(dl.dense(fine[f], fa.o[f], (size_t)(N * nsteps) * 8));
+    HIP_TRY(hipDeviceSynchronize());
+    return MCF_OK;
+}
 namespace mcf {   // mcf_snowrun.hip
+int microcoarse_arg_checks(const mcf_microcoarse_in* in, const char* entry) { return microcoarse_checks(in, entry); }
+int snowcoarse_run_checks(const mcf_snowcoarse_in* in, const char* entry) {
+    static const int dummy = 0;
+    return snowcoarse_checks(in, &dummy, true, entry);
+}
+// the micro group's coarse set onto the plan (once, before mcf_snowplan_micro_setup, whose `sub` then carries no weather arrays)
+int snowplan_micro_attach_coarse(mcf_snowplan* sp, const mcf_microcoarse_in* mi) {
+    if (!sp || !mi) return api_fail(MCF_ERR_ARG, "null argument");
+    if (sp->mcoarse) return api_fail(MCF_ERR_STATE, "snow plan: the microclimate's coarse arrays are attached already");
+    if (!sp->af || mi->rows != sp->rows || mi->cols != sp->cols || mi->tsteps != sp->T)
+        return api_fail(MCF_ERR_ARG, "snow plan: the microclimate's coarse arrays are not of the plan's raster and series (array weather)");
+    HIP_TRY(hipSetDevice(sp->device));
+    if (const int rc = check_room((int64_t)kMicroSeries * sp->chunk * sp->N * 8 + 10 * mi->coarse_rows * mi->coarse_cols * mi->tsteps * 8))
+        return rc;
+    sp->mcoarse = new MicroCoarseState();
+    return micro_coarse_upload(sp->b, mi, 0, sp->T, sp->d_dtm, &sp->mcoarse->fa);
+}
+// where a coarse plan's run_chunk hands pointm$umu to (null: nowhere — pass 2's re-runs of a chunk)
+void snowplan_coarse_umu_out(mcf_snowplan* sp, double* umu_out) {
+    if (sp && sp->coarse) sp->coarse->h_umu = umu_out;
+}
 int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out) {
     return snowcoarse_checks(in, out, true, "mcf_snowmodel2_coarse");
 }
@@ -3491,7 +3725,8 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
         if (T == 0) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: no snow day");
         bool given = true;
         each_micro_series(*sub, [&](auto* host, auto member, const char*) { given = given && (host || !member); });
-        if (!given) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: a weather array is null");
+        // (a plan with the microclimate's coarse arrays attached expands the series itself: `sub` carries none)
+        if (!given && !sp->mcoarse) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: a weather array is null");
         if (!sub->other.lats || !sub->other.lons || !sub->clim.winddir) return mcf::api_fail(MCF_ERR_ARG, "micro set-up, array weather: lats / lons / winddir");
         if ((rc = up_sites(b, a, sub, N))) return rc;
         // the subset series' date rows (obstime and wind direction of the snow days)
@@ -3528,8 +3763,12 @@ extern "C" int mcf_snowplan_micro_setup(mcf_snowplan* sp, const mcf_snow_inputs*
             int e = d;
             while (e < ndays && sub_of_day[e] >= 0 && e - d < cd) ++e;
             const int64_t off = (int64_t)d * 24 * N, n = (int64_t)(e - d) * 24 * N;
-            HIP_TRY(hipMemcpyAsync(sp->d_micro[0], h_temp + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
-            HIP_TRY(hipMemcpyAsync(sp->d_micro[1], h_precip + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            if (sp->mcoarse) {          // the run's temp and precip expanded from the resident coarse arrays
+                if ((rc = micro_coarse_fill(sp, (int64_t)d * 24, (e - d) * 24, 0, 1u << MF_TEMP | 1u << MF_PRECIP, sp->d_micro[1]))) return rc;
+            } else {
+                HIP_TRY(hipMemcpyAsync(sp->d_micro[0], h_temp + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+                HIP_TRY(hipMemcpyAsync(sp->d_micro[1], h_precip + off, (size_t)n * 8, hipMemcpyHostToDevice, nullptr));
+            }
             hipLaunchKernelGGL(k_micro_scan, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, nullptr, (const double*)sp->d_micro[0],
                                (const double*)sp->d_micro[1], N, sub_of_day[d], e - d, a.hgt, a.mxtc, d_hs, a.hs0);
             HIP_TRY(hipGetLastError());
@@ -3727,13 +3966,27 @@ extern "C" int mcf_snowplan_microsnow(mcf_snowplan* sp, mcf_plan* plan, int32_t 
         // array weather: the chunk's snow days of the nine series into the slabs; the kernel addresses a series with the subset's
         // step number, so the bases are shifted back by the chunk's first subset day
         int sub_first = -1;
-        for (int d = 0; d < nd; ++d) {
-            const int sb = sp->sub_of_day[day0 + d];
-            if (sb < 0) continue;
-            if (sub_first < 0) sub_first = sb;
-            for (int f = 0; f < kMicroSeries; ++f)
-                HIP_TRY(hipMemcpyAsync(sp->d_micro[f] + (int64_t)(sb - sub_first) * 24 * N, sp->h_micro[f] + (int64_t)(day0 + d) * 24 * N,
-                                     (size_t)24 * N * 8, hipMemcpyHostToDevice, nullptr));
+        if (sp->mcoarse) {
+            // coarse array weather: one expansion launch per run of consecutive snow days (their subset numbers are consecutive
+            // too); the slab offset (sub - sub_first) x 24 x N stays inside chunk x N
+            for (int d = 0; d < nd;) {
+                const int sb = sp->sub_of_day[day0 + d];
+                if (sb < 0) { ++d; continue; }
+                if (sub_first < 0) sub_first = sb;
+                int e = d + 1;
+                while (e < nd && sp->sub_of_day[day0 + e] >= 0) ++e;
+                if ((rc = micro_coarse_fill(sp, (int64_t)(day0 + d) * 24, (e - d) * 24, (int64_t)(sb - sub_first) * 24, kMicroAll, nullptr))) return rc;
+                d = e;
+            }
+        } else {
+            for (int d = 0; d < nd; ++d) {
+                const int sb = sp->sub_of_day[day0 + d];
+                if (sb < 0) continue;
+                if (sub_first < 0) sub_first = sb;
+                for (int f = 0; f < kMicroSeries; ++f)
+                    HIP_TRY(hipMemcpyAsync(sp->d_micro[f] + (int64_t)(sb - sub_first) * 24 * N, sp->h_micro[f] + (int64_t)(day0 + d) * 24 * N,
+                                         (size_t)24 * N * 8, hipMemcpyHostToDevice, nullptr));
+            }
         }
         const int64_t back = (int64_t)sub_first * 24 * N;
         for (int f = 0; f < kMicroSeries; ++f) q.m.*sp->micro_arg[f] = sp->d_micro[f] - back;

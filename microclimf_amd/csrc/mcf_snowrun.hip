@@ -30,6 +30,11 @@
 // (mcf_rowblocks.hpp's worker pool): per chunk the blocks' snow surfaces meet in one whole-raster host array, the two raster-wide
 // means and the per-step extremes of totalSWE are combined in block order.  One block = the single-device sequence, bit for bit.
 // The snow model's own entries (mcf_snowmodel1 / 2, mcf_snowmodel1_multi, at the end) run the same chunk loop (snow_chunk).
+//
+// Array weather with the coarse arrays left coarse (mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse): one block
+// whose snow plan expands a chunk's thirteen series (k_fine_chunk) and a run of snow days' nine microclimate series (k_micro_fine)
+// from resident coarse arrays, and whose solver plan interpolates its own (array_forcing == 2) — the same two passes, nothing of
+// size cells x steps uploaded; the solver's temperature cap over the no-snow days from the resident series (mcf_plan_set_mxtc_days).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -51,6 +56,12 @@ int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);
 void snowplan_print_timing(const mcf_snowplan* sp);
 int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out);
 int snowplan_create_coarse(const mcf_snowcoarse_in* co, double* umu_out, int32_t device, mcf_snowplan** out);
+// the coarse snow run: its groups' own checks under the entry's name, the microclimate's coarse set onto a plan, and where a
+// coarse plan's chunks hand pointm$umu to
+int snowcoarse_run_checks(const mcf_snowcoarse_in* in, const char* entry);
+int microcoarse_arg_checks(const mcf_microcoarse_in* in, const char* entry);
+int snowplan_micro_attach_coarse(mcf_snowplan* sp, const mcf_microcoarse_in* mi);
+void snowplan_coarse_umu_out(mcf_snowplan* sp, double* umu_out);
 // (over the listings of the snow entries' array groups, kept there next to the kernels' argument structs)
 bool model_rasters_given(const mcf_snow_inputs& in);
 void model_rasters_of_block(mcf_snowdriver_in& in, HostCopies* rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
@@ -214,6 +225,11 @@ struct mcf_snowrun : SnowBlocks {
     bool pass1_done = false;
     bool af = false;                           // array weather: `.snowmodel2` + `.runmicrosnow2` (mcf_runmicrosnow2)
     bool below = false;                        // the `_below` entries: reqhgt < 0, a streamed solver plan over the no-snow days
+    // mcf_runmicrosnow2_coarse: array weather with the coarse arrays left coarse — the snow plan expands its chunks and the
+    // microclimate's snow days itself, the solver plan interpolates (array_forcing == 2); umu_out: pass 1's pointm$umu, or null
+    bool coarse = false;
+    double* umu_out = nullptr;
+    bool layers_set = false;                   // mcf_snowrun_set_day_layers since the last pass 1 (which restores the plans' own table)
     int64_t keep_reserve = (int64_t)8 << 30;
     // A run is one simulated period on fresh plans: the device memory a kept chunk needs would have to be ALLOCATED for it (5 GB per
     // chunk of a 1024 x 1024 raster: 0.1 s, measured 3 s of a 6 s call) where re-running the chunk in pass 2 takes 3.5 ms — chunks are
@@ -255,16 +271,21 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
     if ((g.array_forcing != 0) != (sb.array_forcing != 0))
         return mcf::api_fail(MCF_ERR_ARG, "snow run: the solver's and the snow model's weather differ in geometry (data.frame / array)");
     if (g.array_forcing == 2)
-        return mcf::api_fail(MCF_ERR_ARG, "snow run: coarse array forcing is not supported here (resample to the raster first, as `.snowmodel2` does)");
+        return mcf::api_fail(MCF_ERR_ARG, "snow run: coarse array forcing is not taken here (mcf_runmicrosnow2_coarse / mcf_snowrun_create_coarse "
+                                          "keep the coarse arrays coarse; or resample to the raster first, as `.snowmodel2` does)");
     if (g.array_forcing && mu && (mu->n_blocks > 1 || mu->n_devices > 1))
         return mcf::api_fail(MCF_ERR_ARG, "snow run, array weather: one block on one device");
     // Time-varying vegetation (round 5).  `.runmicronosnow` sends a layered `vegp` to `.runmodel3Cpp` on the no-snow-day SUBSET
     // (R/internal.R:3333-3342), which deals the subset's days to layers by `.sortvegp(vegp, "C", n, subs)` — the layer a step has
     // in the WHOLE series (round(seq(0.50001, dmx + 0.5, length.out = n))[subs], the day's mode, R/internal.R:252-270) — and
-    // renumbers the layers it uses (:1391-1399).  A no-snow day therefore runs with the layer the whole-series table gives it:
-    // the solver plan takes the caller's whole-series layer table (lyr_st / lyr_ed in whole-series steps, as mcf_runmicro3) and
-    // the days run at their own place in it.  The snow model's and gridmicrosnow1's rasters are `.sortl` / `.sortl2` means —
-    // single-layer — either way.
+    // renumbers the layers it uses (:1391-1399).  Here a no-snow day runs with the layer the whole-series table gives it: the
+    // solver plan takes the caller's whole-series layer table (lyr_st / lyr_ed in whole-series steps, as mcf_runmicro3) and the
+    // days run at their own place in it.  That is the reference's dealing as long as the subset's two lists of layers agree —
+    // `.sortvegp` cuts the arrays to the layers some STEP of the subset has, the table has a row per layer that is some DAY's mode,
+    // and the solver walks the cut arrays by row: a layer that keeps a few steps of the subset without being a day's mode puts
+    // every later row one layer early.  A caller that wants that dealing passes it between the passes
+    // (mcf_snowrun_set_day_layers; frontend.subset_day_layers forms it).  The snow model's and gridmicrosnow1's rasters are
+    // `.sortl` / `.sortl2` means — single-layer — either way.
     if (g.veg_layers > 1 && (!g.lyr_st || !g.lyr_ed))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_runmicrosnow1: layered vegetation needs lyr_st / lyr_ed (whole-series steps)");
     if (opt->reqhgt < 0 && !below)
@@ -287,18 +308,55 @@ int check_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_m
     return MCF_OK;
 }
 
+// the coarse run's arguments, each refusal before a device is touched and under the entry's name
+int check_create_coarse(const mcf_microsnow_coarse_in* in, const mcf_options* opt, const mcf_multi* mu, const char* entry) {
+    const std::string e = std::string(entry) + ": ";
+    auto fail = [&](const std::string& m) { return mcf::api_fail(MCF_ERR_ARG, e + m); };
+    if (!in) return fail("null argument: in");
+    if (!opt) return fail("null argument: opt");
+    if (!in->grid) return fail("null argument: in->grid");
+    if (!in->snow) return fail("null argument: in->snow");
+    if (!in->micro) return fail("null argument: in->micro");
+    const mcf_grid_inputs& g = *in->grid;
+    const mcf_snowcoarse_in& s = *in->snow;
+    const mcf_microcoarse_in& m = *in->micro;
+    if (g.array_forcing != 2) return fail("grid->array_forcing must be 2 (coarse array forcing; arrays at the raster's resolution: mcf_runmicrosnow2)");
+    if (opt->reqhgt < 0) return fail("reqhgt < 0 is not supported with coarse array weather");
+    if (mu && (mu->n_blocks > 1 || mu->n_devices > 1)) return fail("one block on one device");
+    int rc;
+    if ((rc = mcf::snowcoarse_run_checks(in->snow, entry))) return rc;
+    if ((rc = mcf::microcoarse_arg_checks(in->micro, entry))) return rc;
+    const mcf_snow_inputs& sb = s.drv.base;
+    if (g.rows != sb.rows || g.cols != sb.cols || g.tsteps != sb.tsteps || m.rows != sb.rows || m.cols != sb.cols || m.tsteps != sb.tsteps)
+        return fail("grid, snow and micro differ in rows / cols / tsteps");
+    if (g.tsteps < 24) return fail("tsteps: at least one day");
+    if (g.coarse_rows != s.coarse_rows || g.coarse_cols != s.coarse_cols || m.coarse_rows != s.coarse_rows || m.coarse_cols != s.coarse_cols)
+        return fail("grid, snow and micro differ in coarse_rows / coarse_cols");
+    if (g.coarse_altcorrect != s.altcorrect || m.altcorrect != s.altcorrect) return fail("grid, snow and micro differ in altcorrect");
+    if (!g.coarse_rowpos || !g.coarse_colpos) return fail("null input: grid coarse_rowpos / coarse_colpos");
+    if (memcmp(g.coarse_rowpos, s.coarse_rowpos, (size_t)sb.rows * 8) || memcmp(m.coarse_rowpos, s.coarse_rowpos, (size_t)sb.rows * 8) ||
+        memcmp(g.coarse_colpos, s.coarse_colpos, (size_t)sb.cols * 8) || memcmp(m.coarse_colpos, s.coarse_colpos, (size_t)sb.cols * 8))
+        return fail("grid, snow and micro differ in coarse_rowpos / coarse_colpos");
+    if (g.row_pitch > 0 && g.row_pitch != g.rows) return fail("dense rasters are taken (row_pitch)");
+    if (g.veg_layers > 1 && (!g.lyr_st || !g.lyr_ed)) return fail("layered vegetation needs lyr_st / lyr_ed (whole-series steps)");
+    return MCF_OK;
+}
+
 }  // namespace
 
-static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool below, mcf_snowrun** out) {
+// co: the coarse run (mcf_snowrun_create_coarse, which has checked its arguments) — `in` is then null
+static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool below, mcf_snowrun** out,
+                          const mcf_microsnow_coarse_in* co = nullptr, double* umu_out = nullptr) {
     try {
         if (!out) return api_fail(MCF_ERR_ARG, "null snow-run argument");
-        int rc = check_create(in, opt, mu, below);
+        int rc = co ? MCF_OK : check_create(in, opt, mu, below);
         if (rc) return rc;
         mcf_snowrun* h = new mcf_snowrun();
         h->below = below;
+        h->coarse = co != nullptr; h->umu_out = umu_out;
         struct Guard { mcf_snowrun* p; ~Guard() { delete p; } } guard{h};
         if ((rc = mcf::device_list(mu, opt->device, &h->devs))) return rc;
-        h->grid = *in->grid; h->opt = *opt; h->snow = *in->snow;
+        h->grid = co ? *co->grid : *in->grid; h->opt = *opt; h->snow = co ? co->snow->drv : *in->snow;
         h->af = h->grid.array_forcing != 0;
         const int64_t R = h->R = h->grid.rows;
         h->C = h->grid.cols;
@@ -315,7 +373,14 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
         rc = mcf::run_workers(h->nt, [&](Worker& w) {
             mcf::for_blocks(w, h->nb, h->nt, [&](int b) -> int {
                 Block& k = h->blocks[(size_t)b];
-                int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
+                int rc2;
+                if (co) {          // one block: the snow plan expands its chunks, and the microclimate's snow days, from coarse arrays
+                    k.device = h->devs[(size_t)w.t]; k.r0 = 0; k.nr = R;
+                    rc2 = mcf::snowplan_create_coarse(co->snow, umu_out, k.device, &k.sp);
+                    if (!rc2) rc2 = mcf::snowplan_micro_attach_coarse(k.sp, co->micro);
+                } else {
+                    rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
+                }
                 if (rc2) return rc2;
                 // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
                 k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
@@ -369,6 +434,18 @@ extern "C" int mcf_snowrun_keep(mcf_snowrun* h, int64_t bytes) {
 }
 
 extern "C" int32_t mcf_snowrun_days(const mcf_snowrun* h) { return h ? h->ndays : 0; }
+// between the passes: every block's solver plan takes this day -> layer map (include/mcf.h)
+extern "C" int mcf_snowrun_set_day_layers(mcf_snowrun* h, const int32_t* layer_of_day, int32_t ndays) {
+    if (!h || !layer_of_day) return api_fail(MCF_ERR_ARG, "mcf_snowrun_set_day_layers: null argument");
+    if (ndays != h->ndays) return api_fail(MCF_ERR_ARG, "mcf_snowrun_set_day_layers: one entry per day of the run");
+    if (!h->pass1_done || h->pass2_done)
+        return api_fail(MCF_ERR_STATE, "mcf_snowrun_set_day_layers: between mcf_snowrun_pass1 (which gives the no-snow days) and mcf_snowrun_pass2");
+    mcf::RestoreDevice restore;
+    for (Block& k : h->blocks)
+        if (const int rc = mcf_plan_set_day_layers(k.plan, layer_of_day, ndays)) return rc;
+    h->layers_set = true;
+    return MCF_OK;
+}
 extern "C" int mcf_snowrun_stats(const mcf_snowrun* h, int64_t stats[4]) {
     if (!h || !stats) return api_fail(MCF_ERR_ARG, "null argument");
     stats[0] = h->st_tile_days; stats[1] = h->st_tile_days_left_out; stats[2] = h->st_chunks_kept; stats[3] = h->st_chunks_rerun;
@@ -387,6 +464,8 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
         const int rc = mcf::run_workers(h->nt, [&](Worker& w) {
             h->each_block(w, [&](Block& k) -> int {
                 int rc2 = mcf_snowplan_reset(k.sp);
+                if (!rc2 && h->layers_set) rc2 = mcf_plan_set_day_layers(k.plan, nullptr, h->ndays);      // (a period's map is its own)
+                if (h->coarse) mcf::snowplan_coarse_umu_out(k.sp, h->umu_out);      // (pass 1 hands pointm$umu out, pass 2's re-runs do not)
                 if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_reset(k.sp);      // (a second year starts the summaries over)
                 if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
                 if (!rc2) std::fill(k.kept.begin(), k.kept.end(), 0);
@@ -438,6 +517,7 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
         // steps past the last whole chunk: the snow model leaves them NA (R/internal.R:2554-2558), `.runmicrosnow1` turns NA
         // into 0 (:3586) — days without snow anywhere, solved by the grid solver
         for (int d = h->nchunks * cd; d < h->ndays; ++d) { h->snowday[(size_t)d] = 0; h->nosnowday[(size_t)d] = 1; }
+        h->layers_set = false;
         h->pass1_done = true;
         if (snowday) memcpy(snowday, h->snowday.data(), (size_t)h->ndays * 4);
         if (nosnowday) memcpy(nosnowday, h->nosnowday.data(), (size_t)h->ndays * 4);
@@ -492,7 +572,7 @@ int snow_day_inputs(Pass2& p) {
         if (!micro) return api_fail(MCF_ERR_ARG, "snow run: the year has snow days, gridmicrosnow1's inputs are needed");
         if (micro->rows != h->R || micro->cols != h->C || micro->tsteps != h->T || (micro->array_forcing != 0) != h->af)
             return api_fail(MCF_ERR_ARG, "snow run: gridmicrosnow's inputs must be the whole series on the whole raster, in the run's weather geometry");
-        if (const char* missing = mcf::micro_series_missing(*micro))
+        if (const char* missing = h->coarse ? nullptr : mcf::micro_series_missing(*micro))      // (a coarse run expands them itself)
             return api_fail(MCF_ERR_ARG, std::string("null input: gridmicrosnow1 weather$") + missing);
         const mcf_obstime& ob = micro->obstime;
         if (!ob.year || !ob.month || !ob.day || !ob.hour) return api_fail(MCF_ERR_ARG, "null obstime");
@@ -513,6 +593,7 @@ int snow_day_inputs(Pass2& p) {
 int block_setup(Pass2& p, Block& k) {
     mcf_snowrun* h = p.h;
     int rc = MCF_OK;
+    if (h->coarse) mcf::snowplan_coarse_umu_out(k.sp, nullptr);
     if (!p.sdays.empty()) {
         mcf_snow_inputs bs = p.sub;
         k.micro_rows = mcf::HostCopies();
@@ -843,6 +924,32 @@ extern "C" int mcf_runmicrosnow1_multi(const mcf_microsnow_in* in, const mcf_opt
                                        const mcf_snowdriver_out* smod) {
     if (!multi) return api_fail(MCF_ERR_ARG, "null argument");
     return runmicrosnow1_impl(in, opt, multi, out, smod);
+}
+
+// The array-weather run with every coarse array left coarse (include/mcf.h mcf_runmicrosnow2_coarse): the chunk loop of
+// mcf_snowmodel2_coarse, a coarse solver plan, and the microclimate's snow days expanded on the device (mcf_snow.hip k_micro_fine)
+extern "C" int mcf_snowrun_create_coarse(const mcf_microsnow_coarse_in* in, const mcf_options* opt, const mcf_multi* mu, double* umu_out,
+                                         mcf_snowrun** out) {
+    const char* entry = "mcf_snowrun_create_coarse";
+    if (!out) return api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: run");
+    if (const int rc = check_create_coarse(in, opt, mu, entry)) return rc;      // nothing above needs a device
+    return snowrun_create(nullptr, opt, mu, false, out, in, umu_out);
+}
+extern "C" int mcf_runmicrosnow2_coarse(const mcf_microsnow_coarse_in* in, const mcf_options* opt, mcf_outputs* out,
+                                        const mcf_snowfast2_out* smod) {
+    const char* entry = "mcf_runmicrosnow2_coarse";
+    if (!out) return api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: out");
+    if (const int rc = check_create_coarse(in, opt, nullptr, entry)) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v)
+        if (opt->out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: out->var[" + std::to_string(v) + "]");
+    mcf_snowrun* h = nullptr;
+    int rc = snowrun_create(nullptr, opt, nullptr, false, &h, in, smod ? smod->umu : nullptr);
+    if (rc) return rc;
+    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
+    if ((rc = mcf_snowrun_pass1(h, smod ? &smod->smod : nullptr, nullptr, nullptr))) return rc;
+    rc = mcf_snowrun_pass2(h, in->micro_static, in->mat, out);
+    if (!rc && getenv("MCF_TIMING")) mcf::snowplan_print_timing(h->blocks[0].sp);
+    return rc;
 }
 
 // reqhgt < 0: the same run with a streamed below-ground solver plan over the no-snow days (data.frame weather)

@@ -283,6 +283,56 @@ def runpointmodel(weather: Mapping, reqhgt: float, dtm: Mapping, vegp: Mapping, 
 
 
 # ---- runmicro ---------------------------------------------------------------------------------------------------
+def _dfsel(lsubs) -> dict:
+    """`.runmodel3Cpp`'s layer table (R/internal.R:1391-1399) from the layer of every step of the series it solves: the layers in
+    use renumbered 1, 2, ... in their order, each with the whole days its steps span (0-based steps st .. ed)"""
+    lyr = []
+    for v in lsubs:
+        if v not in lyr:
+            lyr.append(int(v))
+    st, ed = [], []
+    for v in lyr:
+        s = np.nonzero(lsubs == v)[0] + 1                                # 1-based positions
+        st.append(int(np.floor(s[0] / 24) * 24))
+        ed.append(int(np.floor(s[-1] / 24) * 24 - 1))
+    return {"lyr": np.arange(1, len(lyr) + 1), "st": np.array(st), "ed": np.array(ed)}
+
+
+def subset_day_layers(micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, days) -> np.ndarray | None:
+    """The vegetation layer (0-based row of the layered arrays) `.runmodel3Cpp` / `.runmodel4Cpp` solve each of the 1-based
+    `days` of a complete micropoint with when they are handed the day SUBSET, as `.runmicronosnow` does: one entry per day of the
+    whole series, -1 for the days that are not in the subset; None when the vegetation has a single layer.
+    Two things make this differ from the whole-series table.  `.sortvegp` cuts the layered arrays to `unique(s[subs])`, the
+    layers some STEP of the subset has, in their order; the layer table has one row per layer that is some DAY's mode
+    (`_dfsel`), and the solver walks the cut arrays by ROW of that table.  Row r therefore reads the r-th layer of
+    `unique(s[subs])`, which is the table's own layer only as long as the two lists agree: a layer that keeps a few steps of
+    the subset without being a day's mode puts every later row one layer early, a layer that loses all its steps does not.
+    The entries returned are rows of the WHOLE series' arrays (`unique(s)` of every step)."""
+    veg = cleanvars(vegp, soilc, dtm["z"])[0]
+    if as3d(veg["pai"]).shape[2] <= 1:
+        return None
+    sub = subsetpointmodel(micropoint, days=days)
+    n, subs = sub["ntme"], np.asarray(sub["subs"])
+    s = layer_index(vegpdmx(veg), n)
+
+    def unique(v):                                                        # first-appearance order, as sortvegp_grid
+        out = []
+        for x in v:
+            if x not in out:
+                out.append(int(x))
+        return out
+    first_sub, first_whole = unique(s[subs - 1]), unique(s)
+    t = _dfsel(sortvegp_grid(veg, n, subs)["lsubs"])
+    days = np.asarray(days, dtype=np.int64)
+    lod_sub = np.full(days.size, -1, dtype=np.int32)
+    for row, (st, ed) in enumerate(zip(t["st"], t["ed"])):
+        d0, nd = st // 24, (ed - st + 1) // 24
+        lod_sub[d0:min(d0 + nd, days.size)] = first_whole.index(first_sub[row])      # (the solver's day -> layer map: later rows win)
+    lod = np.full(micropoint["ntme"] // 24, -1, dtype=np.int32)
+    lod[days - 1] = lod_sub
+    return lod
+
+
 def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None,
                         out: Sequence = (1,) * 10, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None,
                         device: int = 0, from_dtm: bool = False) -> dict:
@@ -317,16 +367,7 @@ def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc
     layers = sv["pai"].shape[2]
     dfsel = None
     if layers > 1:                                                       # R/internal.R:1391-1399
-        lyr = []
-        for v in lsubs:
-            if v not in lyr:
-                lyr.append(int(v))
-        st, ed = [], []
-        for v in lyr:
-            s = np.nonzero(lsubs == v)[0] + 1                            # 1-based positions
-            st.append(int(np.floor(s[0] / 24) * 24))
-            ed.append(int(np.floor(s[-1] / 24) * 24 - 1))
-        dfsel = {"lyr": np.arange(1, len(lyr) + 1), "st": np.array(st), "ed": np.array(ed)}
+        dfsel = _dfsel(lsubs)
     else:
         sv = {k: v[:, :, 0] for k, v in sv.items()}
     sl = soilinit(soil)
@@ -866,7 +907,7 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
                   dtmc, lats_c, lons_c, lats, lons, altcorrect: int = 0, snowenv: str = "Taiga", method: str = "fast",
                   snowinitd: float = 0.0, snowinita: float = 0.0, zref: float = 2.0, windhgt: float | None = None,
                   stfact: float = 0.01, device: int = 0, point_device: int | None = None, one_call: bool = False,
-                  device_loop: bool = False) -> dict:
+                  device_loop: bool = False, inputs_only: bool = False) -> dict:
     """`runsnowmodel(climarrayr, micropointa, vegp, soilc, dtm, dtmc, tme, altcorrect, ...)` for array weather
     (R/Cppwrappers.R:735-757 -> `.snowmodel2`, R/internal.R:2777-3013): the snow point model once per cell of
     the climate grid (`point_device=None`: host C++, a cell at a time; an int: every cell as one batch on that device,
@@ -878,7 +919,9 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     `one_call` (subset micropoints, `method = "fast"`): the day loop as one device-resident call with the coarse arrays left
     coarse (`snow.snowmodelq2`) instead of the host day loop; the default is unchanged.
     `device_loop` (`method = "slow"`, or micropoints of the complete series): the chunk loop as one device-resident call with
-    the coarse arrays left coarse (`snow.snowmodel2_coarse`) instead of `snow.snowmodel2_chunks`; the default is unchanged."""
+    the coarse arrays left coarse (`snow.snowmodel2_coarse`) instead of `snow.snowmodel2_chunks`; the default is unchanged.
+    `inputs_only` (the slow method on micropoints of the complete series): everything up to the chunk loop, not the loop — the
+    arguments of `snow.snowmodel2_coarse` by name, what `runmicro_snow_array(..., one_call=True)` takes as `snow_inputs`."""
     from . import snow as S
     if any(m is None for m in micropointa):
         raise ValueError("every coarse cell needs a micropoint")
@@ -893,6 +936,8 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     if device_loop and fast:
         raise ValueError('device_loop: the device-resident chunk loop is the slow method (method = "slow", or micropoints of the '
                          "complete series); the fast method's device-resident day loop is one_call=True")
+    if inputs_only and subset:
+        raise ValueError("inputs_only: the one-call snow run takes micropoints of the complete series")
     vegp = cleanvegp(vegp)
     if subset:
         zref = float(zref)
@@ -937,10 +982,15 @@ def runsnowmodela(climarray: Mapping, obstime: Mapping, micropointa: Sequence, v
     sage = z * 0 + snowinita
     other = {"zref": zref, "lats": np.asarray(lats, dtype=np.float64), "lons": np.asarray(lons, dtype=np.float64),
              "isnowdc": sdep, "isnowac": sage, "isnowdg": sdep * 0.5, "isnowag": sage}
+    agg = 10 if xres <= 100 and min(cr, cc) >= 10 else 1
+    if inputs_only:
+        return {"obstime": ob, "clim_c": clim_c, "pointm_c": pointm_c, "vegp": vg, "other": other, "snowenv": snowenv, "dtm": z,
+                "dtmc": np.asarray(dtmc, dtype=np.float64), "res": xres, "tfact": stfact, "rowpos": rowpos, "colpos": colpos,
+                "altcorrect": int(altcorrect), "agg": agg}
     loop = S.snowmodel2_coarse if device_loop else S.snowmodel2_chunks
     out = loop(ob, clim_c, pointm_c, vg, other, snowenv, z, np.asarray(dtmc, dtype=np.float64), xres, stfact,
                rowpos=rowpos, colpos=colpos, altcorrect=altcorrect,
-               agg=10 if xres <= 100 and min(cr, cc) >= 10 else 1, device=device)
+               agg=agg, device=device)
     if subset:
         i = np.asarray(last["subs"], dtype=np.int64) - 1
         out = {k: v[:, :, i] for k, v in out.items()}
@@ -1275,18 +1325,28 @@ def runsnowmodel_summary(weather: Mapping, micropoint: Mapping, vegp: Mapping, s
 
 
 def runmicro_snow_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: float, vegp: Mapping, soilc: Mapping,
-                        dtm: Mapping, smod: Mapping, *, dtmc, lats, lons, altcorrect: int = 0, pai_a=None, tfact: float = 1.5,
-                        out: Sequence = (1,) * 10, device: int = 0, _solve=None, _microsnow=None, _terrain=None) -> dict:
+                        dtm: Mapping, smod: Mapping | None = None, *, dtmc, lats, lons, altcorrect: int = 0, pai_a=None,
+                        tfact: float = 1.5, out: Sequence = (1,) * 10, device: int = 0, one_call: bool = False, snow_inputs=None,
+                        want_smod: bool = False, _solve=None, _microsnow=None, _terrain=None) -> dict:
     """`runmicro(..., snow = TRUE, snowmod = smod)` for array weather = `.runmicrosnow2` with `.prepsnowinputs2`
     (R/internal.R:3661-3742, 3445-3579): as `runmicro_snow`, with the no-snow days through the coarse-array solver and
     the snow days through gridmicrosnow2 on climate resampled to the fine raster (host numpy, as the reference does it in
     R; relative humidity from resampled vapour pressure, kept within 20 .. 100 %).  Reference behaviour kept: `.sortl2`
     sees no snow-covered step here (`micropoints$subs` of a list is NULL), so the vegetation layers are weighted as
-    without snow."""
+    without snow.
+    `one_call`: the whole run as ONE device-resident call with every coarse array left coarse (snow.runmicrosnow2_coarse): the
+    snow model's chunk loop runs inside it, so it takes `snow_inputs` = runsnowmodela(..., method="slow", inputs_only=True) in
+    place of `smod`; the solver interpolates the coarse arrays of `prepare_grid_inputs_array`, the snow days' weather is
+    expanded on the device from the micropoints the host route reads.  `want_smod`: -> (outputs, the snow model's six series).
+    reqhgt >= 0.  The default route is unchanged."""
     from . import snow as S
-    from .rformulas import lapserate_R, satvap_R, upsample_coarse
     if any(m is None for m in micropointa):
         raise ValueError("every coarse cell needs a micropoint")
+    if one_call:
+        return _runmicro_snow_array_one_call(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, snow_inputs, dtmc, lats, lons,
+                                             altcorrect, pai_a, tfact, out, device, want_smod, _terrain)
+    if smod is None:
+        raise ValueError("smod (runsnowmodela's output) is needed; one_call=True takes snow_inputs instead")
     microsnow = S.gridmicrosnow2 if _microsnow is None else _microsnow
 
     def solve(mpa, **kw):
@@ -1321,26 +1381,9 @@ def runmicro_snow_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: f
             a[k // ccols, k % ccols, :] = get(m)
         return a
     rowpos, colpos = api.coarse_positions(rows, crows), api.coarse_positions(cols, ccols)
-    up = lambda a: upsample_coarse(a, rowpos, colpos)                                          # noqa: E731
-    cca = lambda a: np.where(hole[:, :, None], np.nan, up(a))                                  # noqa: E731
     wc = {k: grid(lambda m, k=k: m["weather"][k]) for k in WEATHER}
-    with np.errstate(invalid="ignore"):
-        ea = up(satvap_R(wc["temp"]) * (wc["relhum"] / 100))
-        temp = up(wc["temp"])
-        if altcorrect == 0:
-            pres = up(wc["pres"])
-        else:
-            zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0)
-            pres = up(wc["pres"] / (((293 - 0.0065 * zc[:, :, None]) / 293) ** 5.26)) * (((293 - 0.0065 * z[:, :, None]) / 293) ** 5.26)
-            elevd = (up(zc) - z)[:, :, None]
-            temp = (5 / 1000 if altcorrect == 1 else lapserate_R(temp, ea, pres)) * elevd + temp
-        relhum = np.clip((ea / satvap_R(temp)) * 100, 20.0, 100.0)
-        wd = wc["winddir"] * np.pi / 180
-        wu, wv = wc["windspeed"] * np.cos(wd), wc["windspeed"] * np.sin(wd)
-        w = {"temp": temp, "relhum": relhum, "pres": pres, "swdown": cca(wc["swdown"]), "difrad": cca(wc["difrad"]),
-             "lwdown": cca(wc["lwdown"]), "windspeed": np.sqrt(up(wu) ** 2 + up(wv) ** 2),
-             "winddir": (np.arctan2(np.nanmean(wv, axis=(0, 1)), np.nanmean(wu, axis=(0, 1))) * 180 / np.pi) % 360,
-             "precip": cca(wc["precip"]), "umu": cca(grid(lambda m: m["dfo"]["umu"]))}
+    zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0) if altcorrect else None
+    w = S._fine_micro_inputs(wc, grid(lambda m: m["dfo"]["umu"]), slice(None), z, zc, rowpos, colpos, altcorrect)
     last = micropointa[-1]
     vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
     res = dtm["res"]
@@ -1366,6 +1409,67 @@ def runmicro_snow_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: f
     smods = {k: np.asfortranarray(np.asarray(sm[k])[:, :, ai]) for k in ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden")}
     mouts = microsnow(reqhgt, mps[0]["obstime"], w, smods, micro, vg, other, float(np.mean([m["matemp"] for m in micropointa])), outm)
     return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
+
+
+def snow_array_groups(micropointa: Sequence, crows: int, ccols: int, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping,
+                      snow_inputs: Mapping, *, dtmc, lats, lons, altcorrect: int = 0, pai_a=None, tfact: float = 1.5,
+                      out: Sequence = (1,) * 10, device: int = 0, _terrain=None):
+    """-> (grid, snow, micro, mat): the three input groups of snow.runmicrosnow2_coarse / snow.SnowRun(micro_coarse=...) as
+    `runmicro_snow_array` forms them — the solver's from `prepare_grid_inputs_array`, the snow model's = `snow_inputs`, the
+    snow-day microclimate's coarse weather from the micropoints' own weather (each coarse cell's own wind direction) with
+    `.sortl2`'s vegetation and the bare-ground terrain"""
+    if reqhgt < 0:
+        raise ValueError("the one-call snow run with array weather needs reqhgt >= 0")
+    if snow_inputs is None or "clim_c" not in snow_inputs:
+        raise ValueError('one_call: snow_inputs = runsnowmodela(..., method="slow", inputs_only=True) is needed')
+    a = prepare_grid_inputs_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, pai_a=pai_a, out=out,
+                                  device=device)
+    a["tfact"] = float(tfact)
+    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    rows, cols = z.shape
+    coarse = {"rowpos": api.coarse_positions(rows, crows), "colpos": api.coarse_positions(cols, ccols)}
+    if altcorrect:
+        coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=z)
+    a["coarse"] = coarse
+    T = len(micropointa[0]["weather"]["temp"])
+
+    def grid(get):
+        g = np.empty((crows, ccols, T), order="F")
+        for k, m in enumerate(micropointa):
+            g[k // ccols, k % ccols, :] = get(m)
+        return g
+    last = micropointa[-1]
+    vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
+    res = dtm["res"]
+    xres = res if np.isscalar(res) else res[0]
+    zref = float(last["zref"])
+    ter = terrain.precompute_terrain(z, xres, zref, device=device) if _terrain is None else _terrain(z, xres, zref)
+    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
+             "lat": np.asarray(lats, dtype=np.float64), "lon": np.asarray(lons, dtype=np.float64), "zref": zref,
+             "Smax": soilinit(soil)["Smax"]}
+    micro = {"clim_c": {k: grid(lambda m, k=k: m["weather"][k]) for k in WEATHER}, "umu_c": grid(lambda m: m["dfo"]["umu"]),
+             "obstime": micropointa[0]["obstime"], "vegp": vg, "other": other}
+    return a, dict(snow_inputs), micro, float(np.mean([m["matemp"] for m in micropointa]))
+
+
+def _runmicro_snow_array_one_call(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, snow_inputs, dtmc, lats, lons, altcorrect,
+                                  pai_a, tfact, out, device, want_smod, _terrain):
+    from . import snow as S
+    g, sn, mi, mat = snow_array_groups(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, snow_inputs, dtmc=dtmc, lats=lats, lons=lons,
+                                       altcorrect=altcorrect, pai_a=pai_a, tfact=tfact, out=out, device=device, _terrain=_terrain)
+    if g.get("dfsel") is None:                                           # one vegetation layer: the library's one call
+        return S.runmicrosnow2_coarse(g, sn, mi, mat, want_smod=want_smod, device=device)
+    # time-varying vegetation: the staged form of the same run — pass 1 gives the no-snow days, which `.runmodel4Cpp` deals to
+    # layers as a SUBSET (subset_day_layers); the solver's day -> layer map is set to that before pass 2
+    with S.SnowRun(g, sn, device=device, micro_coarse=mi, want_umu=want_smod) as run:
+        res = run.pass1(want_smod=want_smod)
+        nd = np.flatnonzero(res[1]) + 1
+        if nd.size:
+            run.set_day_layers(subset_day_layers(micropointa[0], vegp, soilc, dtm, nd))
+        outs = run.pass2(mi, mat)
+        if not want_smod:
+            return outs
+        return outs, dict(res[2], umu=run.umu)
 
 
 # ---- runbioclim() -> .runbioclim1 / .runbioclim3 ------------------------------------------------------------------

@@ -51,9 +51,10 @@ def _get(d: Mapping, *names):
 
 
 def marshal_snow(obstime: Mapping, climdata: Mapping, vegp: Mapping, other: Mapping, array_forcing: bool,
-                 pointm: Mapping | None = None, snowenv: str = "Alpine", micro: bool = False) -> SnowMarshalled:
+                 pointm: Mapping | None = None, snowenv: str = "Alpine", micro: bool = False, weather: bool = True) -> SnowMarshalled:
     """Builds mcf_snow_inputs.  `pointm` (gridmodelsnow) and `micro` (gridmicrosnow: paia, leafd,
-    leafden, umu, Smax) select which optional members are filled."""
+    leafden, umu, Smax) select which optional members are filled.  `weather` False: of `climdata` only `winddir` is read,
+    the weather arrays stay null (the coarse snow run expands them on the device)."""
     m = SnowMarshalled()
     pai = np.asarray(vegp["pai"], dtype=np.float64)
     if pai.ndim != 2:
@@ -71,7 +72,7 @@ def marshal_snow(obstime: Mapping, climdata: Mapping, vegp: Mapping, other: Mapp
     si.obstime.hour = m.f64(obstime["hour"], (T,), "obstime$hour")
     fshape = (R, Cc, T) if array_forcing else (T,)
     for f in _abi.SNOW_CLIM_FIELDS:
-        if f == "umu" and not micro:
+        if (f == "umu" and not micro) or (not weather and f != "winddir"):
             setattr(si.clim, f, None)
             continue
         src = _get(climdata, *(("precip", "prec") if f == "precip" else (f,)))   # cpp:5083 reads "prec"
@@ -541,6 +542,104 @@ def _fine_snow_inputs(clim_c, pointm_c, sl, z, zc, rowpos, colpos, altcorrect, w
             "lwdown": cca(clim_c["lwdown"]), "precip": cca(clim_c["precip"]),
             "windspeed": np.sqrt(up(wu_c) ** 2 + up(wv_c) ** 2), "winddir": winddir[sl]}
     return clim, {k: cca(pointm_c[k]) for k in ("Gp", "Tc", "RswabsG", "RlwabsG", "umu", "tr")}
+
+
+MICRO_WEATHER = ("temp", "relhum", "pres", "swdown", "difrad", "lwdown", "windspeed", "winddir", "precip")
+
+
+def _fine_micro_inputs(clim_c, umu_c, sl, z, zc, rowpos, colpos, altcorrect):
+    """Steps `sl` of the coarse weather of the snow-day microclimate on the fine raster, as `.prepsnowinputs2` prepares it
+    (R/internal.R:3445-3579) — NOT `.snowmodel2`'s weather: temperature and pressure resampled unmasked, relative humidity from
+    the resampled vapour pressure and kept within 20 .. 100 % in every altitude mode, the wind from each coarse cell's own
+    direction, one direction per step from the components' means.  `clim_c[k]`: [crows, ccols, T] (winddir too), `umu_c` the
+    point model's umu, `zc` the coarse dtm with NA read as 0 (read with altcorrect > 0 only) -> gridmicrosnow2's `climdata`.
+    The host statement of what `expand_micro_coarse` computes on the device."""
+    from .rformulas import lapserate_R, satvap_R, upsample_coarse
+    hole = np.isnan(z)
+    up = lambda a: upsample_coarse(a, rowpos, colpos)                                          # noqa: E731
+    cca = lambda a: np.where(hole[:, :, None], np.nan, up(a))                                  # noqa: E731
+    wc = {k: np.asarray(clim_c[k])[:, :, sl] for k in MICRO_WEATHER}
+    with np.errstate(invalid="ignore"):
+        ea = up(satvap_R(wc["temp"]) * (wc["relhum"] / 100))
+        temp = up(wc["temp"])
+        if altcorrect == 0:
+            pres = up(wc["pres"])
+        else:
+            pres = up(wc["pres"] / (((293 - 0.0065 * zc[:, :, None]) / 293) ** 5.26)) * (((293 - 0.0065 * z[:, :, None]) / 293) ** 5.26)
+            elevd = (up(zc) - z)[:, :, None]
+            temp = (5 / 1000 if altcorrect == 1 else lapserate_R(temp, ea, pres)) * elevd + temp
+        relhum = np.clip((ea / satvap_R(temp)) * 100, 20.0, 100.0)
+        wd = wc["winddir"] * np.pi / 180
+        wu, wv = wc["windspeed"] * np.cos(wd), wc["windspeed"] * np.sin(wd)
+        return {"temp": temp, "relhum": relhum, "pres": pres, "swdown": cca(wc["swdown"]), "difrad": cca(wc["difrad"]),
+                "lwdown": cca(wc["lwdown"]), "windspeed": np.sqrt(up(wu) ** 2 + up(wv) ** 2),
+                "winddir": (np.arctan2(np.nanmean(wv, axis=(0, 1)), np.nanmean(wu, axis=(0, 1))) * 180 / np.pi) % 360,
+                "precip": cca(wc["precip"]), "umu": cca(np.asarray(umu_c)[:, :, sl])}
+
+
+def micro_coarse_arrays(clim_c, umu_c) -> dict:
+    """The ten coarse arrays mcf_microcoarse_in takes, formed on the climate grid with `_fine_micro_inputs`' own expressions:
+    the vapour pressure and the wind components of each coarse cell's own direction; the rest as given"""
+    from .rformulas import satvap_R
+    f = lambda k: np.asarray(clim_c[k], dtype=np.float64)                                    # noqa: E731
+    wd = f("winddir") * np.pi / 180
+    a = {k: f(k) for k in ("temp", "pres", "swdown", "difrad", "lwdown", "precip")}
+    a.update(ea=satvap_R(f("temp")) * (f("relhum") / 100), windu=f("windspeed") * np.cos(wd), windv=f("windspeed") * np.sin(wd),
+             umu=np.asarray(umu_c, dtype=np.float64))
+    return a
+
+
+def marshal_microcoarse(clim_c, umu_c, dtm, dtmc, rowpos, colpos, altcorrect=0):
+    """-> (the marshalling that keeps the arrays alive, mcf_microcoarse_in, the one wind direction per step [T]) for the coarse
+    weather of the snow-day microclimate (`_fine_micro_inputs`' arguments)"""
+    z = np.asarray(dtm, dtype=np.float64)
+    R, Cc = z.shape
+    arrays = micro_coarse_arrays(clim_c, umu_c)
+    cr, cc, n = arrays["temp"].shape
+    m = SnowMarshalled()
+    m.rows, m.cols, m.tsteps = R, Cc, n
+    mi = _abi.MicroCoarseIn()
+    mi.rows, mi.cols, mi.tsteps = R, Cc, n
+    mi.dtm = m.f64(z, (R, Cc), "dtm")
+    mi.coarse_rows, mi.coarse_cols, mi.altcorrect = cr, cc, int(altcorrect)
+    mi.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
+    mi.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
+    mi.coarse_dtm = m.f64(dtmc, (cr, cc), "dtmc") if dtmc is not None else None
+    for k in _abi.MICRO_COARSE:
+        setattr(mi, k, m.f64(arrays[k], (cr, cc, n), k))
+    with np.errstate(invalid="ignore"):
+        winddir = (np.arctan2(np.nanmean(arrays["windv"], axis=(0, 1)), np.nanmean(arrays["windu"], axis=(0, 1))) * 180 / np.pi) % 360
+    return m, mi, winddir
+
+
+def expand_micro_coarse(clim_c, umu_c, dtm, dtmc, *, rowpos, colpos, altcorrect: int = 0, step0: int = 0, nsteps: int | None = None,
+                        series: Sequence[str] | None = None, out: Mapping | None = None, device: int = 0) -> dict:
+    """Steps step0 .. step0 + nsteps - 1 (default: to the end) of the snow-day microclimate's coarse weather on the fine raster by
+    the expansion kernel alone (include/mcf.h mcf_microsnow_expand_coarse_device) -> gridmicrosnow2's `climdata` as
+    `_fine_micro_inputs` returns it: nine series [rows, cols, nsteps] and `winddir` [nsteps].  `series`: the names to expand (the
+    kernel's series mask; default all nine); `out`: arrays [rows, cols, nsteps] (Fortran order) to write into — the ones that are
+    not asked for are left as they are."""
+    lib = _abi.load()
+    m, mi, winddir = marshal_microcoarse(clim_c, umu_c, dtm, dtmc, rowpos, colpos, altcorrect)
+    n = m.tsteps - step0 if nsteps is None else int(nsteps)
+    names = _abi.MICRO_FINE_SERIES if series is None else tuple(series)
+    if not names or any(k not in _abi.MICRO_FINE_SERIES for k in names):
+        raise ValueError(f"series: names out of {_abi.MICRO_FINE_SERIES}")
+    shape = (m.rows, m.cols, max(n, 0))
+    fine = {}
+    for k in _abi.MICRO_FINE_SERIES:
+        if out is not None and k in out:
+            a = out[k]
+            if a.shape != shape or a.dtype != np.float64 or not a.flags.f_contiguous:
+                raise ValueError(f"out[{k!r}] must be a Fortran-ordered float64 array {shape}")
+            fine[k] = a
+        elif k in names:
+            fine[k] = np.empty(shape, dtype=np.float64, order="F")
+    ptrs = (_abi.c_double_p * 9)(*[fine[k].ctypes.data_as(_abi.c_double_p) if k in names else None for k in _abi.MICRO_FINE_SERIES])
+    _abi.check(lib.mcf_microsnow_expand_coarse_device(C.byref(mi), C.c_int64(step0), C.c_int64(n), ptrs, device))
+    clim = {k: fine[k] for k in _abi.MICRO_FINE_SERIES if k in fine}
+    clim["winddir"] = winddir[step0:step0 + n]
+    return clim
 
 
 def meltmu2(mu, stemp, tc) -> np.ndarray:
@@ -1244,16 +1343,33 @@ class SnowRun:
     below  reqhgt < 0 (include/mcf.h mcf_snowrun_create_below): the solver streams Tbelowgroundv over the no-snow days, the
            snow-day model gives Tz and soilm; data.frame weather, one period per handle.  False: reqhgt < 0 is refused.
     handle False: the inputs are marshalled (`_in`, `_gm`, `_din`) and no library handle is made — for the entries that take them
-           in one call (runmicrosnow1); pass1 / pass2 need the handle."""
+           in one call (runmicrosnow1); pass1 / pass2 need the handle.
+    micro_coarse  array weather with the coarse arrays left coarse (include/mcf.h mcf_snowrun_create_coarse): {"clim_c": the nine
+           coarse weather arrays of the snow-day microclimate [crows, ccols, T] (winddir per coarse cell), "umu_c"}.  `grid` is then
+           runmicro2Cpp_coarse's arguments by name with "coarse" = {"rowpos", "colpos"[, "altcorrect", "dtmc", "dtm"]}, `snow`
+           snowmodel2_coarse's by name (obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc, res, tfact, rowpos, colpos[,
+           altcorrect, agg, chunk_steps]); pass2's `micro` carries obstime, vegp and other only.  want_umu: pass 1 fills `self.umu`,
+           pointm$umu on the raster [rows, cols, tsteps] (the sixth series of `snowmodel2_coarse`)."""
 
     def __init__(self, grid: Mapping, snow: Mapping, *, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0,
-                 below: bool = False, handle: bool = True):
+                 below: bool = False, handle: bool = True, micro_coarse: Mapping | None = None, want_umu: bool = False):
         self._p = None
-        self._marshal(grid, snow, device, cells_per_block)
+        self.coarse = micro_coarse is not None
+        if self.coarse:
+            self._marshal_coarse(grid, snow, micro_coarse, device)
+        else:
+            self._marshal(grid, snow, device, cells_per_block)
         if not handle:
             return
         mu = _abi.multi(devices, n_blocks)
         self._p = C.c_void_p()
+        if self.coarse:
+            # (pointm$umu of every step leaves with pass 1: the coarse handle hands it out of the chunks' slabs)
+            self.umu = np.empty((self.rows, self.cols, self.tsteps), dtype=np.float64, order="F") if want_umu else None
+            _abi.check(self._lib.mcf_snowrun_create_coarse(C.byref(self._cin_all), C.byref(self._gm.options), C.byref(mu[0]) if mu else None,
+                                                           self.umu.ctypes.data_as(_abi.c_double_p) if want_umu else None, C.byref(self._p)))
+            self.days = int(self._lib.mcf_snowrun_days(self._p))
+            return
         create = self._lib.mcf_snowrun_create_below if below else self._lib.mcf_snowrun_create
         _abi.check(create(C.byref(self._in), C.byref(self._gm.options), C.byref(mu[0]) if mu else None, C.byref(self._p)))
         self.days = int(self._lib.mcf_snowrun_days(self._p))
@@ -1292,10 +1408,52 @@ class SnowRun:
         self._mm = None
         self._msum = self._psum = None      # (spec, variables, statistics, table) of the enabled summaries
 
+    def _marshal_coarse(self, grid: Mapping, snow: Mapping, micro_coarse: Mapping, device: int):
+        from .marshal import alloc_outputs, marshal
+        self._lib = _abi.load()
+        g = grid
+        if "coarse" not in g:
+            raise ValueError('the coarse snow run takes grid["coarse"] = {"rowpos", "colpos"[, "altcorrect", "dtmc", "dtm"]}')
+        self.array_weather = True
+        self._gm = marshal(g["obstime"], g["climdata"], g["pointm"], g["vegp"], g["soilc"], g["reqhgt"], g["zref"],
+                           g["lats"] if "lats" in g else g["lat"], g["lons"] if "lons" in g else g["lon"],
+                           g.get("Sminp", 0.0), g.get("Smaxp", 0.0), g["tfact"], g.get("complete", True), g.get("mat", 0.0),
+                           g.get("out", (1,) * 10), True, device, 0, 0, g.get("dfsel"), g["coarse"])
+        self._alloc_outputs = lambda: alloc_outputs(self._gm)
+        alt = int(snow.get("altcorrect", 0))
+        self._sm, self._cin, _ = marshal_snowcoarse(snow["obstime"], snow["clim_c"], snow["pointm_c"], snow["vegp"], snow["other"],
+                                                    snow.get("snowenv", "Alpine"), snow["dtm"], snow["dtmc"], snow["res"],
+                                                    snow.get("tfact", 0.02), snow["rowpos"], snow["colpos"], alt, snow.get("agg", 10),
+                                                    snow.get("chunk_steps", 120))
+        self._mcm, self._mci, self._mwinddir = marshal_microcoarse(micro_coarse["clim_c"], micro_coarse["umu_c"], snow["dtm"],
+                                                                   snow["dtmc"], snow["rowpos"], snow["colpos"], alt)
+        self._cin_all = _abi.MicrosnowCoarseIn()
+        self._cin_all.grid = C.pointer(self._gm.inputs)
+        self._cin_all.snow = C.pointer(self._cin)
+        self._cin_all.micro = C.pointer(self._mci)
+        self._cin_all.micro_static = None
+        self._cin_all.mat = 0.0
+        self.rows, self.cols, self.tsteps = self._sm.rows, self._sm.cols, self._sm.tsteps
+        self._mm = None
+        self._msum = self._psum = None
+
+    def _marshal_micro(self, micro: Mapping):
+        """gridmicrosnow's inputs for the whole series (the coarse run: no weather arrays, the direction per step its own)"""
+        if self.coarse:
+            return marshal_snow(micro["obstime"], {"winddir": micro.get("winddir", self._mwinddir)}, micro["vegp"], micro["other"], True,
+                                micro=True, weather=False)
+        return marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], self.array_weather, micro=True)
+
     def keep(self, gigabytes: float):
         """Keep pass 1's snow chunks in device memory for pass 2, up to this much (include/mcf.h mcf_snowrun_keep; 0: off).
         Pays from the handle's second period on — the sets are pooled — or when the snow series are fetched anyway."""
         _abi.check(self._lib.mcf_snowrun_keep(self._p, int(gigabytes * 2 ** 30)))
+
+    def set_day_layers(self, layer_of_day):
+        """Between pass1 and pass2, layered vegetation: the solver's day -> layer map (include/mcf.h mcf_snowrun_set_day_layers);
+        one 0-based layer per day of the whole series, -1: none"""
+        lod = np.ascontiguousarray(layer_of_day, dtype=np.int32)
+        _abi.check(self._lib.mcf_snowrun_set_day_layers(self._p, lod.ctypes.data_as(_abi.c_int32_p), int(lod.size)))
 
     def stats(self) -> dict:
         """What pass 2 was spared (include/mcf.h mcf_snowrun_stats)."""
@@ -1364,7 +1522,7 @@ class SnowRun:
         enabled): the merged days are folded only, no [rows, cols, steps] array is allocated or filled -> None"""
         mi = None
         if micro is not None:
-            self._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], self.array_weather, micro=True)
+            self._mm = self._marshal_micro(micro)
             mi = C.byref(self._mm.inputs)
         if not want_arrays:
             _abi.check(self._lib.mcf_snowrun_pass2(self._p, mi, float(mat), None))
@@ -1450,3 +1608,25 @@ def runmicrosnow2(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
     if "af_wind" not in snow:
         raise ValueError("runmicrosnow2: snow['af_wind'] (the chunk wind series of `.snowmodel2`) is missing")
     return runmicrosnow1(grid, snow, micro, mat, **kw)
+
+
+def runmicrosnow2_coarse(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, *, want_smod: bool = False, device: int = 0):
+    """mcf_runmicrosnow2_coarse: `.snowmodel2`'s loop + `.runmicrosnow2` as ONE library call with every coarse array left coarse.
+    `grid`, `snow` as for `SnowRun(..., micro_coarse=...)`; `micro` = {"clim_c", "umu_c"} (the snow-day microclimate's coarse
+    weather, `_fine_micro_inputs`' arguments) plus {"obstime", "vegp", "other"} as `SnowRun.pass2` takes them -> the merged
+    outputs[, smod: Tc, Tg, groundsnowdepth, totalSWE, snowden, umu as `snowmodel2_coarse` returns them]"""
+    if micro is None:
+        raise ValueError("runmicrosnow2_coarse: the microclimate's coarse weather (micro['clim_c'], micro['umu_c']) is needed")
+    with SnowRun(grid, snow, device=device, handle=False, micro_coarse=micro) as run:
+        if "obstime" in micro:
+            run._mm = run._marshal_micro(micro)
+            run._cin_all.micro_static = C.pointer(run._mm.inputs)
+        run._cin_all.mat = float(mat)
+        outs, arrays = run._alloc_outputs()
+        so, smod = None, None
+        if want_smod:
+            so = _abi.SnowFast2Out()
+            smod = _wanted_series(run._sm, None, _abi.SNOWFAST2_OUT, so)
+        _abi.check(run._lib.mcf_runmicrosnow2_coarse(C.byref(run._cin_all), C.byref(run._gm.options), C.byref(outs),
+                                                     C.byref(so) if so is not None else None))
+    return (arrays, smod) if want_smod else arrays
