@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <chrono>
 #include <functional>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -25,6 +26,7 @@
 #include "mcf_rowblocks.hpp"
 #include "mcf_hiphost.hpp"
 #include "mcf_snow_device.hpp"
+#include "mcf_snow_plan.hpp"
 
 // the ring kernel (lane per cell-hour, cell table in LDS, step record through scalar loads): 141 VGPRs without scratch at three
 // waves per SIMD, 128 + 44 B (eight spill stores and loads per hour) at four — measured 0.515 against 0.55 s per simulated year
@@ -1148,6 +1150,28 @@ struct Events {   // timing events released on every exit path
         return hipSuccess;
     }
 };
+// An MCF_TIMING span on the null stream: end() adds the device time since the last begin() to a counter of milliseconds and
+// waits for it.  MCF_TIMING unset (or `wanted` false): no event, no synchronise.
+struct TimedSpan {
+    Events evs;
+    const bool on;
+    explicit TimedSpan(bool wanted = true) : on(wanted && getenv("MCF_TIMING") != nullptr) {}
+    hipError_t begin() {
+        if (!on) return hipSuccess;
+        if (evs.e.empty())
+            if (const hipError_t r = evs.make(2)) return r;
+        return hipEventRecord(evs.e[0], nullptr);
+    }
+    hipError_t end(double* ms_sum) {
+        if (!on) return hipSuccess;
+        hipError_t r;
+        if ((r = hipEventRecord(evs.e[1], nullptr)) || (r = hipEventSynchronize(evs.e[1]))) return r;
+        float ms = 0;
+        r = hipEventElapsedTime(&ms, evs.e[0], evs.e[1]);
+        *ms_sum += ms;
+        return r;
+    }
+};
 
 // ---- the array groups of the snow entries, each listed ONCE: every upload, null check, row gather and copy walks these.
 // f(the caller's pointer — a reference: a block's copy of the inputs is re-pointed through it —, the kernel argument it
@@ -1348,20 +1372,16 @@ int run_snowmodel(const mcf_snow_inputs* in, mcf_snowmodel_out* out, int32_t dev
     for (int v = 0; v < 4; ++v)
         if (host2[v] && (rc = b.make(dev2[v], N))) return rc;
     const unsigned grid = (unsigned)((N + 255) / 256);
-    Events evs;
-    const bool timing = getenv("MCF_TIMING") != nullptr;
-    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    TimedSpan span;
+    double ms = 0;
+    HIP_TRY(span.begin());
     if (af) hipLaunchKernelGGL(k_snowmodel<true>, dim3(grid), dim3(256), 0, nullptr, a, a.rows, a.dates);
     else hipLaunchKernelGGL(k_snowmodel<false>, dim3(grid), dim3(256), 0, nullptr, a, a.rows, a.dates);
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(evs.e[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
+    HIP_TRY(span.end(&ms));
+    if (span.on)
         fprintf(stderr, "[mcf] k_snowmodel<%d>: %lld cells x %d steps in %.3f ms (%.3e cell-steps/s)\n", (int)af,
                 (long long)N, T, ms, (double)NT / (ms * 1e-3));
-    }
     mcf::ToHost dl;
     for (int v = 0; v < 5; ++v)
         if (host3[v]) HIP_TRY(dl.dense(host3[v], *dev3[v], (size_t)NT * 8));
@@ -1463,21 +1483,337 @@ int run_microsnow(const mcf_snow_inputs* in, const mcf_snowm* sm, double reqhgt,
     return MCF_OK;
 }
 
+// ---- coarse array weather left coarse (mcf_snowmodelq2, mcf_snowmodel2_coarse, mcf_runmicrosnow2_coarse): where a raster cell lies
+// in the coarse grid, the argument structs of the expansion, its kernels, the upload of the coarse arrays ---------------------------
+// Bilinear tap into one hour of a coarse field [crows, ccols] (an R array: one hour's coarse cells are contiguous): the
+// operations of rformulas.upsample_coarse in their order, no FMA contraction — a tap has the host's bits.  (CoarseTap::mix
+// contracts; the solver's taps stay as they are.)  `p`: the field at one hour, uniform over the wave; the four neighbours are
+// 32-bit byte offsets from it (one hour's coarse cells x 8 B < 2^32: checked by the host).
+struct SnowTap {
+    uint32_t o00, o01, o10, o11;
+    double wx, wy;
+    __device__ __forceinline__ SnowTap(double rowpos, double colpos, int crows, int ccols) {
+        const double fr = floor(rowpos), fc = floor(colpos);
+        const int r0 = (int)fr, c0 = (int)fc;
+        const int r1 = r0 + 1 < crows ? r0 + 1 : r0, c1 = c0 + 1 < ccols ? c0 + 1 : c0;
+        wy = rowpos - fr;
+        wx = colpos - fc;
+        o00 = 8u * (uint32_t)(r0 + crows * c0); o01 = 8u * (uint32_t)(r0 + crows * c1);
+        o10 = 8u * (uint32_t)(r1 + crows * c0); o11 = 8u * (uint32_t)(r1 + crows * c1);
+    }
+    __device__ __forceinline__ double operator()(const double* __restrict__ p) const {
+#pragma clang fp contract(off)
+        const char* q = reinterpret_cast<const char*>(p);
+        const double v00 = *reinterpret_cast<const double*>(q + o00), v01 = *reinterpret_cast<const double*>(q + o01),
+                     v10 = *reinterpret_cast<const double*>(q + o10), v11 = *reinterpret_cast<const double*>(q + o11);
+        const double top = (1.0 - wx) * v00 + wx * v01;
+        const double bot = (1.0 - wx) * v10 + wx * v11;
+        return (1.0 - wy) * top + wy * bot;
+    }
+};
+// where a raster cell (column-major index c) lies in the coarse grid
+struct CoarseGeo {
+    int32_t rows, crows, ccols, pad;
+    const double *rowpos, *colpos;      // [rows], [cols]
+    __device__ __forceinline__ SnowTap tap(int64_t c) const {
+        const uint32_t j = (uint32_t)c / (uint32_t)rows, i = (uint32_t)c - j * (uint32_t)rows;
+        return SnowTap(rowpos[i], colpos[j], crows, ccols);
+    }
+};
+
+// `.satvap` and `.lapserate` (int:501-511, 545-550) in the operand order of rformulas.satvap_R / lapserate_R
+__device__ __forceinline__ double snow_satvap_r(double tc) {
+#pragma clang fp contract(off)
+    return tc < 0.0 ? 0.61078 * exp(21.875 * tc / (tc + 265.5)) : 0.61078 * exp(17.27 * tc / (tc + 237.3));
+}
+__device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double pk) {
+#pragma clang fp contract(off)
+    const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
+    return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
+}
+// A selected day's (or a chunk's) thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py
+// _fine_snow_inputs), [hours][N] as k_snowmodel<true> reads them.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
+// are not masked.  altcorrect > 0: `pres` holds the coarse pressure already taken to sea level (the host divides by the
+// coarse cell's factor), the cell's own factor brings it back up; the temperature moves by elevd x lapse rate, relative
+// humidity keeps the vapour pressure of the uncorrected field; capped at 100.  `umu` is the day's slab of the output set when
+// the caller wants pointm$umu, so what the model reads is what leaves.
+struct FineArgs {
+    int64_t N, hour0;                  // hour0: the day's first hour in the coarse arrays of the selected hours
+    int32_t altcorrect, pad;
+    CoarseGeo geo;
+    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
+    const double *temp, *relhum, *pres, *swdown, *difrad, *lwdown, *precip, *windu, *windv, *Gp, *Tc, *RswabsG, *RlwabsG, *umu;
+    double *o_temp, *o_relhum, *o_pres, *o_swdown, *o_difrad, *o_lwdown, *o_windspeed, *o_precip, *o_Gp, *o_Tc, *o_RswabsG, *o_RlwabsG,
+        *o_umu;
+};
+// hours kb .. ke - 1 of cell c's thirteen series into [.][N]: the arithmetic, whose bits tests rely on
+__device__ __forceinline__ void coarse_cell_hours(const FineArgs& a, int64_t c, int kb, int ke) {
+#pragma clang fp contract(off)
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    const double z = a.dtm[c], NA = na_real();
+    const bool hole = isnan(z);
+    double up = 1.0, elevd = 0.0;
+    if (a.altcorrect) {
+        up = pow((293 - 0.0065 * z) / 293, 5.26);
+        elevd = tap(a.zc) - z;
+    }
+    for (int k = kb; k < ke; ++k) {
+        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
+        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
+        double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
+        if (a.altcorrect) {
+            const double ea = snow_satvap_r(temp) * relhum / 100;
+            pres = pres * up;
+            const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
+            temp = lr * elevd + temp;
+            relhum = (ea / snow_satvap_r(temp)) * 100;
+        }
+        if (relhum > 100) relhum = 100.0;
+        const double wu = tap(a.windu + h), wv = tap(a.windv + h);
+        a.o_temp[o] = temp; a.o_relhum[o] = relhum; a.o_pres[o] = pres;
+        a.o_windspeed[o] = sqrt(wu * wu + wv * wv);
+        a.o_swdown[o] = cca(a.swdown); a.o_difrad[o] = cca(a.difrad); a.o_lwdown[o] = cca(a.lwdown); a.o_precip[o] = cca(a.precip);
+        a.o_Gp[o] = cca(a.Gp); a.o_Tc[o] = cca(a.Tc); a.o_RswabsG[o] = cca(a.RswabsG); a.o_RlwabsG[o] = cca(a.RlwabsG);
+        a.o_umu[o] = cca(a.umu);
+    }
+}
+// The thirteen series of the hours a.hour0 .. a.hour0 + ns - 1 into [ns][N]: a selected day of the fast method (ns = 24) or a
+// chunk of the slow one.  Lanes run along the cells (a wave stores 512 contiguous bytes per series and hour), blockIdx.y over
+// groups of kFineHours hours: a lane forms its tap, its pressure factor and elevd once and walks its group.  Five hours: the
+// 120-hour chunk of the bundled 50 x 50 raster is 10 x 24 = 240 workgroups on 256 CUs where one lane per cell would be 10, the
+// lane's set-up (two position loads, one pow with altcorrect) is spread over 5 x 14 taps, and a chunk of whole days (24, 48, 120
+// hours; 24 is no multiple of 5) ends in a partial group, so the partial path is the everyday one.  g0: the first group of
+// this launch (the grid's y extent is 16 bits).
+constexpr int kFineHours = 5;
+// one coarse plane on the raster, NA on the dtm's holes (mean(cca(tc), na.rm = TRUE) is the mean of this of tc's time sums)
+__global__ __launch_bounds__(256) void k_tap_plane(CoarseGeo geo, int64_t N, const double* __restrict__ dtm, const double* __restrict__ plane,
+                                                   double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const double v = geo.tap(c)(plane);
+    out[c] = isnan(dtm[c]) ? na_real() : v;
+}
+// `.cleansmod`: NA on the dtm's holes in the series that leave, [ns][N] each (null: not written); holes are few, a lane walks
+// its cell's steps
+struct CleanArgs {
+    int64_t N;
+    const double* dtm;
+    double* v[5];
+};
+__global__ __launch_bounds__(256) void k_clean_chunk(CleanArgs a, int ns) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N || !isnan(a.dtm[c])) return;
+    const double NA = na_real();
+#pragma unroll
+    for (int q = 0; q < 5; ++q)
+        if (a.v[q])
+            for (int k = 0; k < ns; ++k) a.v[q][c + a.N * k] = NA;
+}
+
+// the coarse arrays of the selected hours, in the order FineArgs lists them
+template <class In, class F>
+void each_coarse_selected(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
+    using A = FineArgs;
+    f(in.temp, &A::temp, "temp"); f(in.relhum, &A::relhum, "relhum"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
+    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.precip, &A::precip, "precip");
+    f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv"); f(in.Gp, &A::Gp, "pointm$Gp"); f(in.Tc, &A::Tc, "pointm$Tc");
+    f(in.RswabsG, &A::RswabsG, "pointm$RswabsG"); f(in.RlwabsG, &A::RlwabsG, "pointm$RlwabsG"); f(in.umu, &A::umu, "pointm$umu");
+}
+
+// What every entry with a coarse grid has of it, whatever struct brings it (host only): the raster, the grid, where the raster's
+// rows and columns lie in it, the grid's dtm and the altitude mode
+struct CoarseGrid {
+    int64_t rows, cols, coarse_rows, coarse_cols;
+    const double *rowpos, *colpos, *coarse_dtm;
+    int32_t altcorrect;
+    int64_t cells() const { return rows * cols; }
+    int64_t coarse_cells() const { return coarse_rows * coarse_cols; }
+};
+template <class In>      // mcf_snowfast2_in, mcf_snowcoarse_in, mcf_microcoarse_in
+CoarseGrid coarse_grid(const In& ci, int64_t rows, int64_t cols) {
+    return {rows, cols, ci.coarse_rows, ci.coarse_cols, ci.coarse_rowpos, ci.coarse_colpos, ci.coarse_dtm, ci.altcorrect};
+}
+// every position inside the coarse grid: a tap reads cells floor(pos) and floor(pos) + 1 (or floor(pos) at the far edge)
+bool positions_inside(const double* pos, int64_t n, int64_t ncoarse) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(pos[i] >= 0.0 && pos[i] <= (double)(ncoarse - 1))) return false;
+    return true;
+}
+bool positions_inside(const CoarseGrid& g) {
+    return positions_inside(g.rowpos, g.rows, g.coarse_rows) && positions_inside(g.colpos, g.cols, g.coarse_cols);
+}
+// a tap is a uniform base + a 32-bit byte offset; the bound of the solver's coarse forcing, which addresses a day at once
+bool coarse_grid_too_large(const CoarseGrid& g) { return (double)g.coarse_rows * (double)g.coarse_cols * 24.0 * 8.0 >= 4294967296.0; }
+// What the entries refuse of a coarse grid before a device is touched, under the entry's name and its group's tag ("micro: " or
+// none): the grid's own conditions, then the caller's scan for null inputs (null_inputs() -> status: the order of its need()
+// calls decides which missing input is named, so it stays with the caller), then the two bounds that read the positions.
+template <class Scan>
+int coarse_grid_checks(const CoarseGrid& g, const char* entry, const char* tag, Scan&& null_inputs) {
+    auto fail = [&](const char* m) { return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": " + tag + m); };
+    if (g.coarse_rows < 1 || g.coarse_cols < 1) return fail("coarse_rows and coarse_cols must be at least 1");
+    if (g.altcorrect < 0 || g.altcorrect > 2) return fail("altcorrect must be 0, 1 or 2");
+    if (g.altcorrect > 0 && !g.coarse_dtm) return fail("altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
+    if (const int rc = null_inputs()) return rc;
+    if (!positions_inside(g)) return fail("coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
+    if (coarse_grid_too_large(g)) return fail("coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    return MCF_OK;
+}
+
+// Geometry, dtm and the coarse arrays of hours h0 .. h0 + nh - 1 on the device, into either argument struct (FineArgs, MicroFineArgs).
+// altcorrect > 0: the coarse dtm with NA read as 0, and the pressure taken to sea level on the coarse grid here (int:2871-2873,
+// 3127-3129).  dtm: the raster's on the host; d_dtm: on the device if the caller has it there already.  each(in, f): the list of
+// the struct's coarse arrays (each_coarse_selected, each_micro_coarse).
+template <class Args, class In, class Each>
+int coarse_upload(mcf::DevOwner& b, const CoarseGrid& g, const In* ci, Each&& each, const double* dtm, int64_t h0, int64_t nh,
+                  const double* d_dtm, Args* fa) {
+    const int64_t N = g.cells(), CC = g.coarse_cells();
+    int rc = MCF_OK;
+    memset(fa, 0, sizeof *fa);
+    fa->N = N; fa->altcorrect = g.altcorrect;
+    fa->geo.rows = (int32_t)g.rows; fa->geo.crows = (int32_t)g.coarse_rows; fa->geo.ccols = (int32_t)g.coarse_cols;
+    if ((rc = b.up(&fa->geo.rowpos, g.rowpos, g.rows, "coarse_rowpos"))) return rc;
+    if ((rc = b.up(&fa->geo.colpos, g.colpos, g.cols, "coarse_colpos"))) return rc;
+    if (d_dtm) fa->dtm = d_dtm;
+    else if ((rc = b.up(&fa->dtm, dtm, N, "dtm"))) return rc;
+    std::vector<double> psl;
+    if (g.altcorrect) {
+        std::vector<double> zc((size_t)CC), down((size_t)CC);
+        for (int64_t q = 0; q < CC; ++q) {
+            zc[(size_t)q] = std::isnan(g.coarse_dtm[q]) ? 0.0 : g.coarse_dtm[q];
+            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
+        }
+        psl.resize((size_t)(CC * nh));
+        for (int64_t k = 0; k < nh; ++k)
+            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = ci->pres[(h0 + k) * CC + q] / down[(size_t)q];
+        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
+    }
+    each(*ci, [&](auto* host, auto member, const char* name) {
+        if (!rc) rc = b.up(&(fa->*member), g.altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
+    });
+    return rc;
+}
+// (the lists as coarse_upload takes them)
+constexpr auto kSnowCoarseArrays = [](auto& in, auto&& f) { each_coarse_selected(in, f); };
+
+// `.cca` of one coarse field for the hours hour0 .. hour0 + ns - 1, [ns][N]: k_coarse_hours' lane map (pointm$umu behind the last chunk)
+__global__ __launch_bounds__(256) void k_fine_field(CoarseGeo geo, int64_t N, int64_t hour0, int ns, const double* __restrict__ dtm,
+                                                    const double* __restrict__ field, double* __restrict__ out) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= N) return;
+    const int kb = (int)blockIdx.y * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    const SnowTap tap = geo.tap(c);
+    const int64_t CC = (int64_t)geo.crows * geo.ccols;
+    const bool hole = isnan(dtm[c]);
+    for (int k = kb; k < ke; ++k) {
+        const double v = tap(field + (hour0 + k) * CC);
+        out[c + N * k] = hole ? na_real() : v;
+    }
+}
+
+// the kernel's outputs in the order of each_model_series
+void fine_outputs(FineArgs& fa, double* const d[13]) {
+    fa.o_temp = d[0]; fa.o_relhum = d[1]; fa.o_pres = d[2]; fa.o_swdown = d[3]; fa.o_difrad = d[4]; fa.o_lwdown = d[5];
+    fa.o_windspeed = d[6]; fa.o_precip = d[7]; fa.o_Gp = d[8]; fa.o_Tc = d[9]; fa.o_RswabsG = d[10]; fa.o_RlwabsG = d[11]; fa.o_umu = d[12];
+}
+
+// The snow-day microclimate's weather is not the snow model's: vapour pressure is resampled (the host forms it on the climate
+// grid), temperature and pressure are NOT masked by the dtm, relative humidity comes from the resampled vapour pressure in every
+// altitude mode and is kept within 20 .. 100.  o[]: the nine series in the order of each_micro_series, [hours][N] as
+// k_microsnow_ring<true> reads them; mask bit f: series f is written (the set-up's scan reads temp and precip alone).
+struct MicroFineArgs {
+    int64_t N, hour0;                  // hour0: the first hour in the resident coarse arrays
+    int32_t altcorrect;
+    uint32_t mask;
+    CoarseGeo geo;
+    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
+    const double *temp, *ea, *pres, *swdown, *difrad, *lwdown, *windu, *windv, *precip, *umu;   // pres: at sea level when altcorrect > 0
+    double* o[kMicroSeries];
+};
+enum { MF_TEMP = 0, MF_RELHUM, MF_PRES, MF_SWDOWN, MF_DIFRAD, MF_LWDOWN, MF_WINDSPEED, MF_PRECIP, MF_UMU };
+constexpr uint32_t kMicroAll = (1u << kMicroSeries) - 1;
+// hours kb .. ke - 1 of cell c: the host's operations in the host's order, no contraction (the mask is uniform: no lane diverges)
+__device__ __forceinline__ void coarse_cell_hours(const MicroFineArgs& a, int64_t c, int kb, int ke) {
+#pragma clang fp contract(off)
+    const SnowTap tap = a.geo.tap(c);
+    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
+    const double z = a.dtm[c], NA = na_real();
+    const bool hole = isnan(z);
+    const uint32_t m = a.mask;
+    const bool want_t = (m & (1u << MF_TEMP | 1u << MF_RELHUM)) != 0;
+    const bool want_ea = (m >> MF_RELHUM & 1u) || (want_t && a.altcorrect == 2);
+    const bool want_p = (m >> MF_PRES & 1u) || (want_t && a.altcorrect == 2);
+    double up = 1.0, elevd = 0.0;
+    if (a.altcorrect) {
+        up = pow((293 - 0.0065 * z) / 293, 5.26);
+        elevd = tap(a.zc) - z;
+    }
+    for (int k = kb; k < ke; ++k) {
+        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
+        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
+        double ea = 0.0, pres = 0.0;
+        if (want_ea) ea = tap(a.ea + h);
+        if (want_p) {
+            pres = tap(a.pres + h);
+            if (a.altcorrect) pres = pres * up;
+        }
+        if (want_t) {
+            double temp = tap(a.temp + h);
+            if (a.altcorrect) {
+                const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
+                temp = lr * elevd + temp;
+            }
+            if (m >> MF_TEMP & 1u) a.o[MF_TEMP][o] = temp;
+            if (m >> MF_RELHUM & 1u) {
+                double relhum = (ea / snow_satvap_r(temp)) * 100;
+                if (relhum < 20.0) relhum = 20.0;              // np.clip: NaN stays NaN
+                if (relhum > 100.0) relhum = 100.0;
+                a.o[MF_RELHUM][o] = relhum;
+            }
+        }
+        if (m >> MF_PRES & 1u) a.o[MF_PRES][o] = pres;
+        if (m >> MF_SWDOWN & 1u) a.o[MF_SWDOWN][o] = cca(a.swdown);
+        if (m >> MF_DIFRAD & 1u) a.o[MF_DIFRAD][o] = cca(a.difrad);
+        if (m >> MF_LWDOWN & 1u) a.o[MF_LWDOWN][o] = cca(a.lwdown);
+        if (m >> MF_WINDSPEED & 1u) {
+            const double wu = tap(a.windu + h), wv = tap(a.windv + h);
+            a.o[MF_WINDSPEED][o] = sqrt(wu * wu + wv * wv);
+        }
+        if (m >> MF_PRECIP & 1u) a.o[MF_PRECIP][o] = cca(a.precip);
+        if (m >> MF_UMU & 1u) a.o[MF_UMU][o] = cca(a.umu);
+    }
+}
+// The expansion kernel of either argument struct (FineArgs: the snow model's thirteen series, MicroFineArgs: the snow-day
+// microclimate's nine) around its coarse_cell_hours, and its launches: at most 32768 groups each
+template <class Args>
+__global__ __launch_bounds__(256) void k_coarse_hours(Args a, int ns, int g0) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.N) return;
+    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
+    coarse_cell_hours(a, c, kb, ke);
+}
+template <class Args>
+void launch_coarse_hours(const Args& fa, int ns, hipStream_t stream) {
+    const int groups = (ns + kFineHours - 1) / kFineHours;
+    for (int g0 = 0; g0 < groups; g0 += 32768)
+        hipLaunchKernelGGL(k_coarse_hours<Args>, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0,
+                           stream, fa, ns, g0);
+}
+// the ten coarse arrays in the order of the kernel's arguments
+template <class In, class F>
+void each_micro_coarse(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
+    using A = MicroFineArgs;
+    f(in.temp, &A::temp, "temp"); f(in.ea, &A::ea, "ea"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
+    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv");
+    f(in.precip, &A::precip, "precip"); f(in.umu, &A::umu, "umu");
+}
+constexpr auto kMicroCoarseArrays = [](auto& in, auto&& f) { each_micro_coarse(in, f); };
+
 // (the chunk loop lives in mcf_snowplan below)
 
 }  // namespace
 
 // ---- .snowmodel1's chunk loop as a stepwise, device-resident plan (one per rank's row block) ---------------
-// coarse array weather (mcf_snowmodel2_coarse, behind mcf_meltmu2_device): the resident coarse arrays and the chunk expansion
-struct SnowCoarseState;
-static void coarse_release(SnowCoarseState* cs);
-static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns);
-static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last);
-static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns);
-// the snow-day microclimate's own resident coarse set (mcf_runmicrosnow2_coarse, behind mcf_microsnow_expand_coarse_device)
-struct MicroCoarseState;
-static void micro_coarse_release(MicroCoarseState* ms);
-static int micro_coarse_fill(mcf_snowplan* sp, int64_t hour0, int ns, int64_t slab_off, uint32_t mask, double* precip_into);
 struct mcf_snowplan {
     int device = 0;
     int64_t rows = 0, cols = 0, N = 0, row0 = 0, rows_total = 0;
@@ -1492,8 +1828,10 @@ struct mcf_snowplan {
     const double* h_series[13] = {};      // in the order of each_model_series
     double* d_series[13] = {};            // [N][chunk]
     // coarse array weather: the fourteen coarse arrays stay on the device, a chunk's thirteen series are expanded from them
-    // into d_series by one kernel (no h_series)
-    SnowCoarseState* coarse = nullptr;
+    // into d_series by one kernel (no h_series).  coarse: the resident arrays of the whole series (hour 0 = step 0) and the plan's
+    // dtm (mcf_snowmodel2_coarse); h_umu: [rows, cols, T] of the caller, where a chunk's pointm$umu goes, or null
+    std::optional<FineArgs> coarse;
+    double* h_umu = nullptr;
     const DateRow2* dates_tab = nullptr;
     const double *d_dtm = nullptr, *d_isnowdg = nullptr;
     double *d_isnowdc = nullptr, *d_dtms = nullptr, *d_slope = nullptr, *d_aspect = nullptr, *d_svf = nullptr,
@@ -1536,8 +1874,9 @@ struct mcf_snowplan {
     double* d_micro[kMicroSeries] = {};
     const double* MicroArgs::* micro_arg[kMicroSeries] = {};      // the kernel argument each slab is
     // coarse array weather: the ten coarse arrays of the microclimate's weather stay on the device (no h_micro), a chunk's snow
-    // days are expanded from them into d_micro by one kernel per run of consecutive snow days
-    MicroCoarseState* mcoarse = nullptr;
+    // days are expanded from them into d_micro by one kernel per run of consecutive snow days (mcf_runmicrosnow2_coarse; the
+    // plan's own set, not the snow model's)
+    std::optional<MicroFineArgs> mcoarse;
     double t_micro_fine = 0;             // ms, MCF_TIMING: that expansion, pass 2's launches
     int n_micro_fine = 0;
     int32_t outsel[MCF_NOUT] = {};
@@ -1572,7 +1911,7 @@ struct mcf_snowplan {
     int ps_row[MCF_NSTAT] = {}, ps_sel1[5] = {};  // ps_sel1: 1-based place of a series in the state, 0: not selected
     double ps_thr[5] = {};
     std::vector<int32_t> ps_pod, ps_days;
-    ~mcf_snowplan() { twork.release(); coarse_release(coarse); micro_coarse_release(mcoarse); }
+    ~mcf_snowplan() { twork.release(); }
 };
 
 namespace {
@@ -1600,9 +1939,63 @@ extern "C" int mcf_snowplan_chunk_af(const mcf_snowplan* sp, int32_t chunk, int3
     *af = a;
     return rc;
 }
+// ---- the plan's coarse array weather: the snow model's resident arrays and a chunk's expansion, `.cleansmod` and pointm$umu behind
+// the chunk (mcf_snowmodel2_coarse), the snow-day microclimate's expansion (mcf_runmicrosnow2_coarse)
+static int coarse_attach(mcf_snowplan* sp, const mcf_snowcoarse_in* co, double* umu_out) {
+    sp->h_umu = umu_out;
+    sp->coarse.emplace();
+    return coarse_upload(sp->b, coarse_grid(*co, sp->rows, sp->cols), co, kSnowCoarseArrays, co->drv.dtm, 0, sp->T, sp->d_dtm, &*sp->coarse);
+}
+static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns) {
+    FineArgs fa = *sp->coarse;
+    fa.hour0 = k0;
+    fine_outputs(fa, sp->d_series);
+    TimedSpan span;
+    HIP_TRY(span.begin());
+    launch_coarse_hours(fa, ns, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(span.end(&sp->t_fine));
+    return MCF_OK;
+}
+static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns) {
+    CleanArgs cl;
+    cl.N = sp->N; cl.dtm = sp->d_dtm;
+    cl.v[0] = Tc; cl.v[1] = Tg; cl.v[2] = sdepg; cl.v[3] = sdepc; cl.v[4] = sden;
+    hipLaunchKernelGGL(k_clean_chunk, dim3((unsigned)((sp->N + 255) / 256)), dim3(256), 0, nullptr, cl, ns);
+}
+static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last) {
+    if (!sp->h_umu) return MCF_OK;
+    const FineArgs& fa = *sp->coarse;
+    const int64_t N = sp->N;
+    HIP_TRY(sp->dl.dense(sp->h_umu + (int64_t)k0 * N, sp->d_series[12], (size_t)ns * N * 8));
+    if (!last) return MCF_OK;
+    // the steps behind the last whole chunk (fewer than a chunk): umu alone, through the chunk's slab
+    for (int t0 = k0 + ns; t0 < sp->T; t0 += sp->chunk) {
+        const int nt = std::min(sp->chunk, sp->T - t0);
+        hipLaunchKernelGGL(k_fine_field, dim3((unsigned)((N + 255) / 256), (unsigned)((nt + kFineHours - 1) / kFineHours)), dim3(256), 0,
+                           nullptr, fa.geo, N, (int64_t)t0, nt, fa.dtm, fa.umu, sp->d_series[12]);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(sp->dl.dense(sp->h_umu + (int64_t)t0 * N, sp->d_series[12], (size_t)nt * N * 8));
+    }
+    return MCF_OK;
+}
+// hours hour0 .. hour0 + ns - 1 of the series in `mask` into the plan's slabs from step slab_off on; precip_into: where the
+// precipitation goes instead of its own slab (the set-up's scan streams temp and precip through the first two slabs)
+static int micro_coarse_fill(mcf_snowplan* sp, int64_t hour0, int ns, int64_t slab_off, uint32_t mask, double* precip_into) {
+    MicroFineArgs fa = *sp->mcoarse;
+    fa.hour0 = hour0; fa.mask = mask;
+    for (int f = 0; f < kMicroSeries; ++f) fa.o[f] = sp->d_micro[f] + slab_off * sp->N;
+    if (precip_into) fa.o[MF_PRECIP] = precip_into;
+    TimedSpan span(mask == kMicroAll);       // (pass 2's launches: the set-up's scan is not in the figure)
+    HIP_TRY(span.begin());
+    launch_coarse_hours(fa, ns, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(span.end(&sp->t_micro_fine));
+    if (span.on) sp->n_micro_fine += ns;
+    return MCF_OK;
+}
 // `co`: coarse array weather (mcf_snowmodel2_coarse, which has checked its arguments) — din is &co->drv, the thirteen fine series
 // of din->base are not read; umu_out: where pointm$umu goes (null: not wanted)
-static int coarse_attach(mcf_snowplan* sp, const mcf_snowcoarse_in* co, double* umu_out);
 static int snowplan_create(const mcf_snowdriver_in* din, int64_t row0, int64_t rows_total, int32_t device, const mcf_snowcoarse_in* co,
                            double* umu_out, mcf_snowplan** out) {
     int rc;
@@ -1911,9 +2304,8 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
                  ch, (long long)need_n, (long long)need_s);
         return mcf::api_fail(MCF_ERR_ARG, m);
     }
-    const bool timing = getenv("MCF_TIMING") != nullptr;
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    TimedSpan span;
+    HIP_TRY(span.begin());
     // terrain of dtm + snow (int:2566-2580)
     mcf::TerrainDev td;
     memset(&td, 0, sizeof td);
@@ -1970,13 +2362,7 @@ static int prepare_chunk_on(mcf_snowplan* sp, int32_t ch, const double* d_z, int
     double h[2];
     HIP_TRY(hipMemcpy(h, sp->d_mean2, 16, hipMemcpyDeviceToHost));
     *tpic_sum = h[0]; *tpic_count = h[1];
-    if (timing) {
-        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(evs.e[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        sp->t_terrain += ms;
-    }
+    HIP_TRY(span.end(&sp->t_terrain));
     sp->prepared = ch;
     return MCF_OK;
 }
@@ -2011,16 +2397,15 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     const int64_t N = sp->N;
     const int k0 = ch * sp->chunk, ns = std::min(sp->chunk, sp->T - k0);
     const unsigned gridN = (unsigned)((N + 255) / 256);
-    const bool timing = getenv("MCF_TIMING") != nullptr;
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
+    TimedSpan span;
+    HIP_TRY(span.begin());
     ModelArgs a = sp->a;
     a.rows = sp->af ? nullptr : sp->rows_tab + k0;            // gridmodelsnow1 on the chunk (int:2587)
     a.dates = sp->af ? sp->dates_tab + k0 : nullptr;          // gridmodelsnow2 (int:2979)
     a.tsteps = ns;
     if (sp->coarse) {                                         // the chunk's hours expanded from the resident coarse arrays
         if (const int rc = coarse_fill_chunk(sp, k0, ns)) return rc;
-        if (timing) HIP_TRY(hipEventRecord(evs.e[0], nullptr));
+        HIP_TRY(span.begin());                                // (the expansion has its own span: the model's starts behind it)
     } else if (sp->af)                                        // the chunk's slices of the caller's series: [N][T], a step's raster contiguous
         for (int f = 0; f < 13; ++f)
             HIP_TRY(hipMemcpyAsync(sp->d_series[f], sp->h_series[f] + (int64_t)k0 * N, (size_t)ns * N * 8, hipMemcpyHostToDevice, nullptr));
@@ -2043,13 +2428,7 @@ static int run_chunk_to(mcf_snowplan* sp, int32_t ch, double tpic_mean, const mc
     else hipLaunchKernelGGL(k_snowmodel<false>, dim3(gridN), dim3(256), 0, nullptr, a, a.rows, a.dates);
     if (sp->coarse) coarse_clean_chunk(sp, a.Tc, a.Tg, a.sdepg, a.sdepc, a.sden, ns);      // `.cleansmod` (the hand-over state is written already)
     HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(evs.e[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        sp->t_model += ms;
-    }
+    HIP_TRY(span.end(&sp->t_model));
     double* hostv[5] = {out->Tc, out->Tg, out->groundsnowdepth, out->totalSWE, out->snowden};
     double* devv[5] = {a.Tc, a.Tg, a.sdepg, a.sdepc, a.sden};
     const int64_t HS = row_pitch * sp->cols;        // host doubles per step
@@ -2668,42 +3047,6 @@ extern "C" int mcf_meltmu_device(int64_t cells, const double* skyview, int64_t n
 
 // ---- `.snowmodelq2`, the fast snow method with array weather (R/internal.R "int:" 3017-3283), as one device-resident call -----
 namespace {
-// Bilinear tap into one hour of a coarse field [crows, ccols] (an R array: one hour's coarse cells are contiguous): the
-// operations of rformulas.upsample_coarse in their order, no FMA contraction — a tap has the host's bits.  (CoarseTap::mix
-// contracts; the solver's taps stay as they are.)  `p`: the field at one hour, uniform over the wave; the four neighbours are
-// 32-bit byte offsets from it (one hour's coarse cells x 8 B < 2^32: checked by the host).
-struct SnowTap {
-    uint32_t o00, o01, o10, o11;
-    double wx, wy;
-    __device__ __forceinline__ SnowTap(double rowpos, double colpos, int crows, int ccols) {
-        const double fr = floor(rowpos), fc = floor(colpos);
-        const int r0 = (int)fr, c0 = (int)fc;
-        const int r1 = r0 + 1 < crows ? r0 + 1 : r0, c1 = c0 + 1 < ccols ? c0 + 1 : c0;
-        wy = rowpos - fr;
-        wx = colpos - fc;
-        o00 = 8u * (uint32_t)(r0 + crows * c0); o01 = 8u * (uint32_t)(r0 + crows * c1);
-        o10 = 8u * (uint32_t)(r1 + crows * c0); o11 = 8u * (uint32_t)(r1 + crows * c1);
-    }
-    __device__ __forceinline__ double operator()(const double* __restrict__ p) const {
-#pragma clang fp contract(off)
-        const char* q = reinterpret_cast<const char*>(p);
-        const double v00 = *reinterpret_cast<const double*>(q + o00), v01 = *reinterpret_cast<const double*>(q + o01),
-                     v10 = *reinterpret_cast<const double*>(q + o10), v11 = *reinterpret_cast<const double*>(q + o11);
-        const double top = (1.0 - wx) * v00 + wx * v01;
-        const double bot = (1.0 - wx) * v10 + wx * v11;
-        return (1.0 - wy) * top + wy * bot;
-    }
-};
-// where a raster cell (column-major index c) lies in the coarse grid
-struct CoarseGeo {
-    int32_t rows, crows, ccols, pad;
-    const double *rowpos, *colpos;      // [rows], [cols]
-    __device__ __forceinline__ SnowTap tap(int64_t c) const {
-        const uint32_t j = (uint32_t)c / (uint32_t)rows, i = (uint32_t)c - j * (uint32_t)rows;
-        return SnowTap(rowpos[i], colpos[j], crows, ccols);
-    }
-};
-
 // The pack between two selected days with array weather (int:3229-3244): meltmu2 (cpp:5495-5527) of the resampled snow-surface
 // and air temperatures over the gap's hours fused with the resampled balance, one lane per cell.  `st` / `tc`: coarse sstemp /
 // tc of the WHOLE series, [hour][coarse cell]; gap hour k is hour start + step k (step = -1: R's `a:b` counting down).  Per
@@ -2764,188 +3107,30 @@ __global__ __launch_bounds__(256) void k_gap_balance2(Gap2Args a, const double* 
     a.dc[c] = dc; a.dg[c] = dg;
 }
 
-// `.satvap` and `.lapserate` (int:501-511, 545-550) in the operand order of rformulas.satvap_R / lapserate_R
-__device__ __forceinline__ double snow_satvap_r(double tc) {
-#pragma clang fp contract(off)
-    return tc < 0.0 ? 0.61078 * exp(21.875 * tc / (tc + 265.5)) : 0.61078 * exp(17.27 * tc / (tc + 237.3));
-}
-__device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double pk) {
-#pragma clang fp contract(off)
-    const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
-    return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
-}
-// A selected day's (or a chunk's) thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py
-// _fine_snow_inputs), [hours][N] as k_snowmodel<true> reads them.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
-// are not masked.  altcorrect > 0: `pres` holds the coarse pressure already taken to sea level (the host divides by the
-// coarse cell's factor), the cell's own factor brings it back up; the temperature moves by elevd x lapse rate, relative
-// humidity keeps the vapour pressure of the uncorrected field; capped at 100.  `umu` is the day's slab of the output set when
-// the caller wants pointm$umu, so what the model reads is what leaves.
-struct FineArgs {
-    int64_t N, hour0;                  // hour0: the day's first hour in the coarse arrays of the selected hours
-    int32_t altcorrect, pad;
-    CoarseGeo geo;
-    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
-    const double *temp, *relhum, *pres, *swdown, *difrad, *lwdown, *precip, *windu, *windv, *Gp, *Tc, *RswabsG, *RlwabsG, *umu;
-    double *o_temp, *o_relhum, *o_pres, *o_swdown, *o_difrad, *o_lwdown, *o_windspeed, *o_precip, *o_Gp, *o_Tc, *o_RswabsG, *o_RlwabsG,
-        *o_umu;
-};
-// hours kb .. ke - 1 of cell c's thirteen series into [.][N]: the arithmetic, whose bits tests rely on
-__device__ __forceinline__ void fine_cell_hours(const FineArgs& a, int64_t c, int kb, int ke) {
-#pragma clang fp contract(off)
-    const SnowTap tap = a.geo.tap(c);
-    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
-    const double z = a.dtm[c], NA = na_real();
-    const bool hole = isnan(z);
-    double up = 1.0, elevd = 0.0;
-    if (a.altcorrect) {
-        up = pow((293 - 0.0065 * z) / 293, 5.26);
-        elevd = tap(a.zc) - z;
-    }
-    for (int k = kb; k < ke; ++k) {
-        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
-        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
-        double temp = cca(a.temp), relhum = cca(a.relhum), pres = tap(a.pres + h);
-        if (a.altcorrect) {
-            const double ea = snow_satvap_r(temp) * relhum / 100;
-            pres = pres * up;
-            const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
-            temp = lr * elevd + temp;
-            relhum = (ea / snow_satvap_r(temp)) * 100;
-        }
-        if (relhum > 100) relhum = 100.0;
-        const double wu = tap(a.windu + h), wv = tap(a.windv + h);
-        a.o_temp[o] = temp; a.o_relhum[o] = relhum; a.o_pres[o] = pres;
-        a.o_windspeed[o] = sqrt(wu * wu + wv * wv);
-        a.o_swdown[o] = cca(a.swdown); a.o_difrad[o] = cca(a.difrad); a.o_lwdown[o] = cca(a.lwdown); a.o_precip[o] = cca(a.precip);
-        a.o_Gp[o] = cca(a.Gp); a.o_Tc[o] = cca(a.Tc); a.o_RswabsG[o] = cca(a.RswabsG); a.o_RlwabsG[o] = cca(a.RlwabsG);
-        a.o_umu[o] = cca(a.umu);
-    }
-}
-// The thirteen series of the hours a.hour0 .. a.hour0 + ns - 1 into [ns][N]: a selected day of the fast method (ns = 24) or a
-// chunk of the slow one.  Lanes run along the cells (a wave stores 512 contiguous bytes per series and hour), blockIdx.y over
-// groups of kFineHours hours: a lane forms its tap, its pressure factor and elevd once and walks its group.  Five hours: the
-// 120-hour chunk of the bundled 50 x 50 raster is 10 x 24 = 240 workgroups on 256 CUs where one lane per cell would be 10, the
-// lane's set-up (two position loads, one pow with altcorrect) is spread over 5 x 14 taps, and a chunk of whole days (24, 48, 120
-// hours; 24 is no multiple of 5) ends in a partial group, so the partial path is the everyday one.  g0: the first group of
-// this launch (the grid's y extent is 16 bits).
-constexpr int kFineHours = 5;
-__global__ __launch_bounds__(256) void k_fine_chunk(FineArgs a, int ns, int g0) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N) return;
-    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
-    fine_cell_hours(a, c, kb, ke);
-}
-void launch_fine_chunk(const FineArgs& fa, int ns, hipStream_t stream) {
-    const int groups = (ns + kFineHours - 1) / kFineHours;
-    for (int g0 = 0; g0 < groups; g0 += 32768)
-        hipLaunchKernelGGL(k_fine_chunk, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, stream,
-                           fa, ns, g0);
-}
-// one coarse plane on the raster, NA on the dtm's holes (mean(cca(tc), na.rm = TRUE) is the mean of this of tc's time sums)
-__global__ __launch_bounds__(256) void k_tap_plane(CoarseGeo geo, int64_t N, const double* __restrict__ dtm, const double* __restrict__ plane,
-                                                   double* __restrict__ out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= N) return;
-    const double v = geo.tap(c)(plane);
-    out[c] = isnan(dtm[c]) ? na_real() : v;
-}
-// `.cleansmod`: NA on the dtm's holes in the series that leave, [ns][N] each (null: not written); holes are few, a lane walks
-// its cell's steps
-struct CleanArgs {
-    int64_t N;
-    const double* dtm;
-    double* v[5];
-};
-__global__ __launch_bounds__(256) void k_clean_chunk(CleanArgs a, int ns) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N || !isnan(a.dtm[c])) return;
-    const double NA = na_real();
-#pragma unroll
-    for (int q = 0; q < 5; ++q)
-        if (a.v[q])
-            for (int k = 0; k < ns; ++k) a.v[q][c + a.N * k] = NA;
-}
-
-// the coarse arrays of the selected hours, in the order k_fine_chunk's arguments list them
-template <class In, class F>
-void each_coarse_selected(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
-    using A = FineArgs;
-    f(in.temp, &A::temp, "temp"); f(in.relhum, &A::relhum, "relhum"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
-    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.precip, &A::precip, "precip");
-    f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv"); f(in.Gp, &A::Gp, "pointm$Gp"); f(in.Tc, &A::Tc, "pointm$Tc");
-    f(in.RswabsG, &A::RswabsG, "pointm$RswabsG"); f(in.RlwabsG, &A::RlwabsG, "pointm$RlwabsG"); f(in.umu, &A::umu, "pointm$umu");
-}
-
-// every position inside the coarse grid: a tap reads cells floor(pos) and floor(pos) + 1 (or floor(pos) at the far edge)
-bool positions_inside(const double* pos, int64_t n, int64_t ncoarse) {
-    for (int64_t i = 0; i < n; ++i)
-        if (!(pos[i] >= 0.0 && pos[i] <= (double)(ncoarse - 1))) return false;
-    return true;
-}
-
-// geometry, dtm and the coarse arrays of hours h0 .. h0 + nh - 1 on the device (pressure taken to sea level on the coarse grid by
-// the host when altcorrect > 0, int:2871-2873, 3127-3129); d_dtm: the raster's dtm if the caller has it there already.
-// In: mcf_snowfast2_in or mcf_snowcoarse_in
-template <class In>
-int coarse_upload(mcf::DevOwner& b, const In* ci, int64_t h0, int64_t nh, const double* d_dtm, FineArgs* fa) {
-    const mcf_snow_inputs* in = &ci->drv.base;
-    const int64_t N = in->rows * in->cols, CC = ci->coarse_rows * ci->coarse_cols;
-    int rc = MCF_OK;
-    memset(fa, 0, sizeof *fa);
-    fa->N = N; fa->altcorrect = ci->altcorrect;
-    fa->geo.rows = (int32_t)in->rows; fa->geo.crows = (int32_t)ci->coarse_rows; fa->geo.ccols = (int32_t)ci->coarse_cols;
-    if ((rc = b.up(&fa->geo.rowpos, ci->coarse_rowpos, in->rows, "coarse_rowpos"))) return rc;
-    if ((rc = b.up(&fa->geo.colpos, ci->coarse_colpos, in->cols, "coarse_colpos"))) return rc;
-    if (d_dtm) fa->dtm = d_dtm;
-    else if ((rc = b.up(&fa->dtm, ci->drv.dtm, N, "dtm"))) return rc;
-    std::vector<double> psl;
-    if (ci->altcorrect) {
-        std::vector<double> zc((size_t)CC), down((size_t)CC);
-        for (int64_t q = 0; q < CC; ++q) {
-            zc[(size_t)q] = std::isnan(ci->coarse_dtm[q]) ? 0.0 : ci->coarse_dtm[q];
-            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
-        }
-        psl.resize((size_t)(CC * nh));
-        for (int64_t k = 0; k < nh; ++k)
-            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = ci->pres[(h0 + k) * CC + q] / down[(size_t)q];
-        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
-    }
-    each_coarse_selected(*ci, [&](auto* host, auto member, const char* name) {
-        if (!rc) rc = b.up(&(fa->*member), ci->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
-    });
-    return rc;
-}
-
 int snowmodelq2_checks(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out) {
     if (!fi || !out) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: null argument");
     const mcf_snow_inputs* in = &fi->drv.base;
     if (in->tsteps <= 0 || in->tsteps % 24)
         return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: the fast snow method works on whole selected days (tsteps = 24 x days, at least one)");
     if (const int rc = common_checks(in)) return rc;
-    if (fi->coarse_rows < 1 || fi->coarse_cols < 1)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse_rows and coarse_cols must be at least 1");
-    if (fi->altcorrect < 0 || fi->altcorrect > 2) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: altcorrect must be 0, 1 or 2");
-    if (fi->altcorrect > 0 && !fi->coarse_dtm)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
-    const char* missing = nullptr;
-    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
-    need(fi->coarse_rowpos, "coarse_rowpos"); need(fi->coarse_colpos, "coarse_colpos");
-    each_coarse_selected(*fi, [&](auto* host, auto, const char* name) { need(host, name); });
-    need(in->clim.winddir, "climdata$winddir");
-    each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) {
-        if (!terrain && strcmp(name, "other$isnowdg")) need(host, name);          // (isnowdg is formed here)
+    const int rc = coarse_grid_checks(coarse_grid(*fi, in->rows, in->cols), "mcf_snowmodelq2", "", [&]() -> int {
+        const char* missing = nullptr;
+        auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+        need(fi->coarse_rowpos, "coarse_rowpos"); need(fi->coarse_colpos, "coarse_colpos");
+        each_coarse_selected(*fi, [&](auto* host, auto, const char* name) { need(host, name); });
+        need(in->clim.winddir, "climdata$winddir");
+        each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) {
+            if (!terrain && strcmp(name, "other$isnowdg")) need(host, name);          // (isnowdg is formed here)
+        });
+        need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
+        need(fi->drv.dtm, "dtm"); need(fi->drv.af_wind, "af_wind"); need(fi->subs, "subs");
+        need(fi->sublmelt, "sublmelt"); need(fi->tempmelt, "tempmelt"); need(fi->rainmelt, "rainmelt"); need(fi->snow, "snow");
+        need(fi->sstemp, "sstemp"); need(fi->tc, "tc"); need(fi->sdenc, "sdenc"); need(fi->sdeng, "sdeng");
+        if (missing) return mcf::api_fail(MCF_ERR_ARG, std::string("mcf_snowmodelq2: null input: ") + missing);
+        if (!(fi->drv.res > 0)) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: res must be > 0");
+        return MCF_OK;
     });
-    need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
-    need(fi->drv.dtm, "dtm"); need(fi->drv.af_wind, "af_wind"); need(fi->subs, "subs");
-    need(fi->sublmelt, "sublmelt"); need(fi->tempmelt, "tempmelt"); need(fi->rainmelt, "rainmelt"); need(fi->snow, "snow");
-    need(fi->sstemp, "sstemp"); need(fi->tc, "tc"); need(fi->sdenc, "sdenc"); need(fi->sdeng, "sdeng");
-    if (missing) return mcf::api_fail(MCF_ERR_ARG, std::string("mcf_snowmodelq2: null input: ") + missing);
-    if (!(fi->drv.res > 0)) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: res must be > 0");
-    if (!positions_inside(fi->coarse_rowpos, in->rows, fi->coarse_rows) || !positions_inside(fi->coarse_colpos, in->cols, fi->coarse_cols))
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
-    // (a tap is a uniform base + a 32-bit byte offset; the bound of the solver's coarse forcing, which addresses a day at once)
-    if ((double)fi->coarse_rows * (double)fi->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
-        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowmodelq2: coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    if (rc) return rc;
     return subs_af_checks("mcf_snowmodelq2", fi->subs, in->tsteps, fi->n_all, nullptr, fi->drv.af_wind, "af_wind", fi->drv.res);
 }
 
@@ -2976,7 +3161,7 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
     if ((rc = L.prepare(b, a))) return rc;
     // resident for the call: the coarse arrays of the selected hours, coarse sstemp / tc of the whole series
     FineArgs fa;
-    if ((rc = coarse_upload(b, fi, 0, T, L.d_dtm, &fa))) return rc;
+    if ((rc = coarse_upload(b, coarse_grid(*fi, in->rows, in->cols), fi, kSnowCoarseArrays, fi->drv.dtm, 0, T, L.d_dtm, &fa))) return rc;
     const double *d_st, *d_ta;
     double *d_intfrac, *d_sums, *d_tsum;
     if ((rc = b.up(&d_st, fi->sstemp, n_all * CC, "sstemp"))) return rc;
@@ -3045,7 +3230,7 @@ int snowmodelq2(const mcf_snowfast2_in* fi, const mcf_snowfast2_out* out, int32_
     auto fine_day = [&](int d, const DaySet& s, hipStream_t cs) {
         fa.hour0 = 24 * (int64_t)d;
         if (out->umu) fa.o_umu = s.umu;
-        launch_fine_chunk(fa, 24, cs);
+        launch_coarse_hours(fa, 24, cs);
     };
     // gridmodelsnow2 on the day's 24 hours, from the depths just formed and the caller's ages (they are not handed on)
     auto model = [&](int d, const DaySet& s, hipStream_t cs) {
@@ -3074,9 +3259,11 @@ extern "C" int mcf_meltmu2_device(int64_t rows, int64_t cols, const double* skyv
     if (rows <= 0 || cols <= 0 || crows < 1 || ccols < 1 || n < 0 || !skyview || !dtm || !rowpos || !colpos || !mu_out ||
         (n > 0 && (!sstemp_c || !tc_c)))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: null argument, empty raster or empty coarse grid");
-    if (rows * cols >= ((int64_t)1 << 29) || (double)crows * (double)ccols * 24.0 * 8.0 >= 4294967296.0)
+    // (this entry's own wording, older than coarse_grid_checks': the two bounds are the shared ones, the sentences stay)
+    const CoarseGrid g{rows, cols, crows, ccols, rowpos, colpos, nullptr, 0};
+    if (rows * cols >= ((int64_t)1 << 29) || coarse_grid_too_large(g))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: raster or coarse grid too large");
-    if (!positions_inside(rowpos, rows, crows) || !positions_inside(colpos, cols, ccols))
+    if (!positions_inside(g))
         return mcf::api_fail(MCF_ERR_ARG, "mcf_meltmu2_device: rowpos / colpos must lie in 0..crows - 1 / 0..ccols - 1");
     int rc;
     if ((rc = pick_device(device))) return rc;
@@ -3102,232 +3289,40 @@ extern "C" int mcf_meltmu2_device(int64_t rows, int64_t cols, const double* skyv
     return MCF_OK;
 }
 
-// ---- `.snowmodel2`, the slow snow method with array weather, with the coarse arrays left coarse (mcf_snowmodel2_coarse) ---------
-namespace {
-// `.cca` of one coarse field for the hours hour0 .. hour0 + ns - 1, [ns][N]: k_fine_chunk's lane map (pointm$umu behind the last chunk)
-__global__ __launch_bounds__(256) void k_fine_field(CoarseGeo geo, int64_t N, int64_t hour0, int ns, const double* __restrict__ dtm,
-                                                    const double* __restrict__ field, double* __restrict__ out) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= N) return;
-    const int kb = (int)blockIdx.y * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
-    const SnowTap tap = geo.tap(c);
-    const int64_t CC = (int64_t)geo.crows * geo.ccols;
-    const bool hole = isnan(dtm[c]);
-    for (int k = kb; k < ke; ++k) {
-        const double v = tap(field + (hour0 + k) * CC);
-        out[c + N * k] = hole ? na_real() : v;
-    }
-}
-
-// what both entries refuse before a device is touched; model: mcf_snowmodel2_coarse (the expansion reads geometry, dtm, coarse arrays)
-int snowcoarse_checks(const mcf_snowcoarse_in* ci, const void* out, bool model, const char* entry) {
+// ---- the coarse arrays left coarse behind the slow snow method (`.snowmodel2`, mcf_snowmodel2_coarse) and behind gridmicrosnow2's
+// nine series (`.prepsnowinputs2`, int:3445-3579; snow.py _fine_micro_inputs): what is refused, and the expansions alone ---------
+namespace mcf {   // mcf_snow_plan.hpp
+// What the entries that take a mcf_snowcoarse_in refuse before a device is touched; model: the snow model runs behind (the
+// expansion alone reads geometry, dtm and coarse arrays); null_out: the name of the entry's output argument if that is null
+int snowcoarse_checks(const mcf_snowcoarse_in* ci, bool model, const char* entry, const char* null_out) {
     const std::string e = std::string(entry) + ": ";
     auto fail = [&](const std::string& m) { return mcf::api_fail(MCF_ERR_ARG, e + m); };
     if (!ci) return fail("null argument: in");
-    if (!out) return fail(model ? "null argument: out" : "null argument: fine");
+    if (null_out) return fail(std::string("null argument: ") + null_out);
     const mcf_snow_inputs* in = &ci->drv.base;
     if (in->array_forcing == 0) return fail("drv.base.array_forcing must not be 0 (array weather; data.frame weather: mcf_snowmodel1)");
     if (in->rows <= 0 || in->cols <= 0 || in->tsteps <= 0 || in->tsteps > (1 << 30) || in->rows * in->cols >= ((int64_t)1 << 29))
         return fail("rows, cols, tsteps out of range (at least 1; at most 2^29 - 1 cells, 2^30 steps)");
-    if (ci->coarse_rows < 1 || ci->coarse_cols < 1) return fail("coarse_rows and coarse_cols must be at least 1");
-    if (ci->altcorrect < 0 || ci->altcorrect > 2) return fail("altcorrect must be 0, 1 or 2");
-    if (ci->altcorrect > 0 && !ci->coarse_dtm) return fail("altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
-    const char* missing = nullptr;
-    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
-    need(ci->coarse_rowpos, "coarse_rowpos"); need(ci->coarse_colpos, "coarse_colpos");
-    each_coarse_selected(*ci, [&](auto* host, auto, const char* name) { need(host, name); });
-    need(ci->drv.dtm, "dtm");
-    if (model) {
-        each_obstime(*in, [&](auto* host, auto, const char* name) { need(host, name); });
-        need(in->clim.winddir, "climdata$winddir");
-        each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) { if (!terrain) need(host, name); });
-        need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
-        need(ci->drv.af_wind, "af_wind");
-    }
-    if (missing) return fail(std::string("null input: ") + missing);
-    if (model && !(ci->drv.res > 0)) return fail("res must be > 0");
-    if (!positions_inside(ci->coarse_rowpos, in->rows, ci->coarse_rows) || !positions_inside(ci->coarse_colpos, in->cols, ci->coarse_cols))
-        return fail("coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
-    // (mcf_snowmodelq2's bound: a tap is a uniform base + a 32-bit byte offset)
-    if ((double)ci->coarse_rows * (double)ci->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
-        return fail("coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
+    const int rc = coarse_grid_checks(coarse_grid(*ci, in->rows, in->cols), entry, "", [&]() -> int {
+        const char* missing = nullptr;
+        auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+        need(ci->coarse_rowpos, "coarse_rowpos"); need(ci->coarse_colpos, "coarse_colpos");
+        each_coarse_selected(*ci, [&](auto* host, auto, const char* name) { need(host, name); });
+        need(ci->drv.dtm, "dtm");
+        if (model) {
+            each_obstime(*in, [&](auto* host, auto, const char* name) { need(host, name); });
+            need(in->clim.winddir, "climdata$winddir");
+            each_model_raster(*in, [&](auto* host, auto, int, bool terrain, const char* name) { if (!terrain) need(host, name); });
+            need(in->other.lats, "other$lats"); need(in->other.lons, "other$lons");
+            need(ci->drv.af_wind, "af_wind");
+        }
+        if (missing) return fail(std::string("null input: ") + missing);
+        if (model && !(ci->drv.res > 0)) return fail("res must be > 0");
+        return MCF_OK;
+    });
+    if (rc) return rc;
     if (model && (ci->drv.chunk_steps < 0 || ci->drv.chunk_steps % 24)) return fail("chunk_steps must be whole days (0: 120)");
     return MCF_OK;
-}
-
-// the kernel's outputs in the order of each_model_series
-void fine_outputs(FineArgs& fa, double* const d[13]) {
-    fa.o_temp = d[0]; fa.o_relhum = d[1]; fa.o_pres = d[2]; fa.o_swdown = d[3]; fa.o_difrad = d[4]; fa.o_lwdown = d[5];
-    fa.o_windspeed = d[6]; fa.o_precip = d[7]; fa.o_Gp = d[8]; fa.o_Tc = d[9]; fa.o_RswabsG = d[10]; fa.o_RlwabsG = d[11]; fa.o_umu = d[12];
-}
-}  // namespace
-
-struct SnowCoarseState {
-    FineArgs fa;                         // the resident coarse arrays of the whole series (hour 0 = step 0), the plan's dtm
-    double* h_umu = nullptr;             // [rows, cols, T] of the caller, or null
-};
-static void coarse_release(SnowCoarseState* cs) { delete cs; }
-static int coarse_attach(mcf_snowplan* sp, const mcf_snowcoarse_in* co, double* umu_out) {
-    sp->coarse = new SnowCoarseState();
-    sp->coarse->h_umu = umu_out;
-    return coarse_upload(sp->b, co, 0, sp->T, sp->d_dtm, &sp->coarse->fa);
-}
-static int coarse_fill_chunk(mcf_snowplan* sp, int k0, int ns) {
-    FineArgs fa = sp->coarse->fa;
-    fa.hour0 = k0;
-    fine_outputs(fa, sp->d_series);
-    const bool timing = getenv("MCF_TIMING") != nullptr;
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
-    launch_fine_chunk(fa, ns, nullptr);
-    HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(evs.e[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        sp->t_fine += ms;
-    }
-    return MCF_OK;
-}
-static void coarse_clean_chunk(mcf_snowplan* sp, double* Tc, double* Tg, double* sdepg, double* sdepc, double* sden, int ns) {
-    CleanArgs cl;
-    cl.N = sp->N; cl.dtm = sp->d_dtm;
-    cl.v[0] = Tc; cl.v[1] = Tg; cl.v[2] = sdepg; cl.v[3] = sdepc; cl.v[4] = sden;
-    hipLaunchKernelGGL(k_clean_chunk, dim3((unsigned)((sp->N + 255) / 256)), dim3(256), 0, nullptr, cl, ns);
-}
-static int coarse_umu_out(mcf_snowplan* sp, int k0, int ns, bool last) {
-    SnowCoarseState* cs = sp->coarse;
-    if (!cs->h_umu) return MCF_OK;
-    const int64_t N = sp->N;
-    HIP_TRY(sp->dl.dense(cs->h_umu + (int64_t)k0 * N, sp->d_series[12], (size_t)ns * N * 8));
-    if (!last) return MCF_OK;
-    // the steps behind the last whole chunk (fewer than a chunk): umu alone, through the chunk's slab
-    for (int t0 = k0 + ns; t0 < sp->T; t0 += sp->chunk) {
-        const int nt = std::min(sp->chunk, sp->T - t0);
-        hipLaunchKernelGGL(k_fine_field, dim3((unsigned)((N + 255) / 256), (unsigned)((nt + kFineHours - 1) / kFineHours)), dim3(256), 0,
-                           nullptr, cs->fa.geo, N, (int64_t)t0, nt, cs->fa.dtm, cs->fa.umu, sp->d_series[12]);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(sp->dl.dense(cs->h_umu + (int64_t)t0 * N, sp->d_series[12], (size_t)nt * N * 8));
-    }
-    return MCF_OK;
-}
-
-extern "C" int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[13],
-                                             int32_t device) {
-    const char* entry = "mcf_snow_expand_coarse_device";
-    int rc;
-    if ((rc = snowcoarse_checks(in, fine, false, entry))) return rc;
-    for (int f = 0; f < 13; ++f)
-        if (!fine[f]) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[" + std::to_string(f) + "]");
-    if (step0 < 0 || nsteps < 1 || step0 > in->drv.base.tsteps - nsteps)
-        return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": step0 >= 0, nsteps >= 1 and step0 + nsteps <= tsteps are needed");
-    if ((rc = pick_device(device))) return rc;
-    const int64_t N = in->drv.base.rows * in->drv.base.cols, CC = in->coarse_rows * in->coarse_cols;
-    if ((rc = check_room((13 * nsteps + 1) * N * 8 + 14 * CC * nsteps * 8))) return rc;
-    mcf::DevOwner b;
-    FineArgs fa;
-    if ((rc = coarse_upload(b, in, step0, nsteps, nullptr, &fa))) return rc;
-    double* d[13];
-    for (int f = 0; f < 13; ++f)
-        if ((rc = b.make(&d[f], N * nsteps))) return rc;
-    fine_outputs(fa, d);
-    launch_fine_chunk(fa, (int)nsteps, nullptr);
-    HIP_TRY(hipGetLastError());
-    mcf::ToHost dl;
-    for (int f = 0; f < 13; ++f) HIP_TRY(dl.dense(fine[f], d[f], (size_t)(N * nsteps) * 8));
-    HIP_TRY(hipDeviceSynchronize());
-    return MCF_OK;
-}
-
-// ---- gridmicrosnow2's nine series from coarse arrays (`.prepsnowinputs2`, int:3445-3579; snow.py _fine_micro_inputs) -------------
-namespace {
-// The snow-day microclimate's weather is not the snow model's: vapour pressure is resampled (the host forms it on the climate
-// grid), temperature and pressure are NOT masked by the dtm, relative humidity comes from the resampled vapour pressure in every
-// altitude mode and is kept within 20 .. 100.  o[]: the nine series in the order of each_micro_series, [hours][N] as
-// k_microsnow_ring<true> reads them; mask bit f: series f is written (the set-up's scan reads temp and precip alone).
-struct MicroFineArgs {
-    int64_t N, hour0;                  // hour0: the first hour in the resident coarse arrays
-    int32_t altcorrect;
-    uint32_t mask;
-    CoarseGeo geo;
-    const double *dtm, *zc;            // zc: coarse dtm with NA read as 0 (altcorrect > 0)
-    const double *temp, *ea, *pres, *swdown, *difrad, *lwdown, *windu, *windv, *precip, *umu;   // pres: at sea level when altcorrect > 0
-    double* o[kMicroSeries];
-};
-enum { MF_TEMP = 0, MF_RELHUM, MF_PRES, MF_SWDOWN, MF_DIFRAD, MF_LWDOWN, MF_WINDSPEED, MF_PRECIP, MF_UMU };
-constexpr uint32_t kMicroAll = (1u << kMicroSeries) - 1;
-// hours kb .. ke - 1 of cell c: the host's operations in the host's order, no contraction (the mask is uniform: no lane diverges)
-__device__ __forceinline__ void micro_cell_hours(const MicroFineArgs& a, int64_t c, int kb, int ke) {
-#pragma clang fp contract(off)
-    const SnowTap tap = a.geo.tap(c);
-    const int64_t CC = (int64_t)a.geo.crows * a.geo.ccols;
-    const double z = a.dtm[c], NA = na_real();
-    const bool hole = isnan(z);
-    const uint32_t m = a.mask;
-    const bool want_t = (m & (1u << MF_TEMP | 1u << MF_RELHUM)) != 0;
-    const bool want_ea = (m >> MF_RELHUM & 1u) || (want_t && a.altcorrect == 2);
-    const bool want_p = (m >> MF_PRES & 1u) || (want_t && a.altcorrect == 2);
-    double up = 1.0, elevd = 0.0;
-    if (a.altcorrect) {
-        up = pow((293 - 0.0065 * z) / 293, 5.26);
-        elevd = tap(a.zc) - z;
-    }
-    for (int k = kb; k < ke; ++k) {
-        const int64_t h = (a.hour0 + k) * CC, o = c + a.N * k;
-        auto cca = [&](const double* f) { const double v = tap(f + h); return hole ? NA : v; };
-        double ea = 0.0, pres = 0.0;
-        if (want_ea) ea = tap(a.ea + h);
-        if (want_p) {
-            pres = tap(a.pres + h);
-            if (a.altcorrect) pres = pres * up;
-        }
-        if (want_t) {
-            double temp = tap(a.temp + h);
-            if (a.altcorrect) {
-                const double lr = a.altcorrect == 1 ? 5.0 / 1000 : snow_lapserate_r(temp, ea, pres);
-                temp = lr * elevd + temp;
-            }
-            if (m >> MF_TEMP & 1u) a.o[MF_TEMP][o] = temp;
-            if (m >> MF_RELHUM & 1u) {
-                double relhum = (ea / snow_satvap_r(temp)) * 100;
-                if (relhum < 20.0) relhum = 20.0;              // np.clip: NaN stays NaN
-                if (relhum > 100.0) relhum = 100.0;
-                a.o[MF_RELHUM][o] = relhum;
-            }
-        }
-        if (m >> MF_PRES & 1u) a.o[MF_PRES][o] = pres;
-        if (m >> MF_SWDOWN & 1u) a.o[MF_SWDOWN][o] = cca(a.swdown);
-        if (m >> MF_DIFRAD & 1u) a.o[MF_DIFRAD][o] = cca(a.difrad);
-        if (m >> MF_LWDOWN & 1u) a.o[MF_LWDOWN][o] = cca(a.lwdown);
-        if (m >> MF_WINDSPEED & 1u) {
-            const double wu = tap(a.windu + h), wv = tap(a.windv + h);
-            a.o[MF_WINDSPEED][o] = sqrt(wu * wu + wv * wv);
-        }
-        if (m >> MF_PRECIP & 1u) a.o[MF_PRECIP][o] = cca(a.precip);
-        if (m >> MF_UMU & 1u) a.o[MF_UMU][o] = cca(a.umu);
-    }
-}
-// k_fine_chunk's lane map: lanes along the cells, blockIdx.y over groups of kFineHours hours, g0 the launch's first group
-__global__ __launch_bounds__(256) void k_micro_fine(MicroFineArgs a, int ns, int g0) {
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.N) return;
-    const int kb = (g0 + (int)blockIdx.y) * kFineHours, ke = kb + kFineHours < ns ? kb + kFineHours : ns;
-    micro_cell_hours(a, c, kb, ke);
-}
-void launch_micro_fine(const MicroFineArgs& fa, int ns, hipStream_t stream) {
-    const int groups = (ns + kFineHours - 1) / kFineHours;
-    for (int g0 = 0; g0 < groups; g0 += 32768)
-        hipLaunchKernelGGL(k_micro_fine, dim3((unsigned)((fa.N + 255) / 256), (unsigned)std::min(32768, groups - g0)), dim3(256), 0, stream,
-                           fa, ns, g0);
-}
-// the ten coarse arrays in the order of the kernel's arguments
-template <class In, class F>
-void each_micro_coarse(In& in, F&& f) {   // f(pointer, the kernel's argument, name)
-    using A = MicroFineArgs;
-    f(in.temp, &A::temp, "temp"); f(in.ea, &A::ea, "ea"); f(in.pres, &A::pres, "pres"); f(in.swdown, &A::swdown, "swdown");
-    f(in.difrad, &A::difrad, "difrad"); f(in.lwdown, &A::lwdown, "lwdown"); f(in.windu, &A::windu, "windu"); f(in.windv, &A::windv, "windv");
-    f(in.precip, &A::precip, "precip"); f(in.umu, &A::umu, "umu");
 }
 // what the entries that take a mcf_microcoarse_in refuse before a device is touched
 int microcoarse_checks(const mcf_microcoarse_in* mi, const char* entry) {
@@ -3336,115 +3331,77 @@ int microcoarse_checks(const mcf_microcoarse_in* mi, const char* entry) {
     if (!mi) return fail("null argument: micro");
     if (mi->rows <= 0 || mi->cols <= 0 || mi->tsteps <= 0 || mi->tsteps > (1 << 30) || mi->rows * mi->cols >= ((int64_t)1 << 29))
         return fail("micro: rows, cols, tsteps out of range (at least 1; at most 2^29 - 1 cells, 2^30 steps)");
-    if (mi->coarse_rows < 1 || mi->coarse_cols < 1) return fail("micro: coarse_rows and coarse_cols must be at least 1");
-    if (mi->altcorrect < 0 || mi->altcorrect > 2) return fail("micro: altcorrect must be 0, 1 or 2");
-    if (mi->altcorrect > 0 && !mi->coarse_dtm) return fail("micro: altcorrect > 0 needs coarse_dtm (null input: coarse_dtm)");
-    const char* missing = nullptr;
-    auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
-    need(mi->coarse_rowpos, "coarse_rowpos"); need(mi->coarse_colpos, "coarse_colpos");
-    each_micro_coarse(*mi, [&](auto* host, auto, const char* name) { need(host, name); });
-    need(mi->dtm, "dtm");
-    if (missing) return fail(std::string("null input: micro ") + missing);
-    if (!positions_inside(mi->coarse_rowpos, mi->rows, mi->coarse_rows) || !positions_inside(mi->coarse_colpos, mi->cols, mi->coarse_cols))
-        return fail("micro: coarse_rowpos / coarse_colpos must lie in 0..coarse_rows - 1 / 0..coarse_cols - 1");
-    if ((double)mi->coarse_rows * (double)mi->coarse_cols * 24.0 * 8.0 >= 4294967296.0)
-        return fail("micro: coarse grid too large (24 x coarse cells x 8 B must stay below 2^32)");
-    return MCF_OK;
-}
-// geometry, dtm and the ten coarse arrays of hours h0 .. h0 + nh - 1 on the device; the pressure is taken to sea level on the coarse
-// grid here when altcorrect > 0, as coarse_upload does; d_dtm: the raster's dtm if the caller has it there already
-int micro_coarse_upload(mcf::DevOwner& b, const mcf_microcoarse_in* mi, int64_t h0, int64_t nh, const double* d_dtm, MicroFineArgs* fa) {
-    const int64_t N = mi->rows * mi->cols, CC = mi->coarse_rows * mi->coarse_cols;
-    int rc = MCF_OK;
-    memset(fa, 0, sizeof *fa);
-    fa->N = N; fa->altcorrect = mi->altcorrect; fa->mask = kMicroAll;
-    fa->geo.rows = (int32_t)mi->rows; fa->geo.crows = (int32_t)mi->coarse_rows; fa->geo.ccols = (int32_t)mi->coarse_cols;
-    if ((rc = b.up(&fa->geo.rowpos, mi->coarse_rowpos, mi->rows, "coarse_rowpos"))) return rc;
-    if ((rc = b.up(&fa->geo.colpos, mi->coarse_colpos, mi->cols, "coarse_colpos"))) return rc;
-    if (d_dtm) fa->dtm = d_dtm;
-    else if ((rc = b.up(&fa->dtm, mi->dtm, N, "dtm"))) return rc;
-    std::vector<double> psl;
-    if (mi->altcorrect) {
-        std::vector<double> zc((size_t)CC), down((size_t)CC);
-        for (int64_t q = 0; q < CC; ++q) {
-            zc[(size_t)q] = std::isnan(mi->coarse_dtm[q]) ? 0.0 : mi->coarse_dtm[q];
-            down[(size_t)q] = pow((293 - 0.0065 * zc[(size_t)q]) / 293, 5.26);
-        }
-        psl.resize((size_t)(CC * nh));
-        for (int64_t k = 0; k < nh; ++k)
-            for (int64_t q = 0; q < CC; ++q) psl[(size_t)(k * CC + q)] = mi->pres[(h0 + k) * CC + q] / down[(size_t)q];
-        if ((rc = b.up(&fa->zc, zc.data(), CC, "coarse_dtm"))) return rc;
-    }
-    each_micro_coarse(*mi, [&](auto* host, auto member, const char* name) {
-        if (!rc) rc = b.up(&(fa->*member), mi->altcorrect && !strcmp(name, "pres") ? psl.data() : host + h0 * CC, CC * nh, name);
+    return coarse_grid_checks(coarse_grid(*mi, mi->rows, mi->cols), entry, "micro: ", [&]() -> int {
+        const char* missing = nullptr;
+        auto need = [&](const void* p, const char* name) { if (!p && !missing) missing = name; };
+        need(mi->coarse_rowpos, "coarse_rowpos"); need(mi->coarse_colpos, "coarse_colpos");
+        each_micro_coarse(*mi, [&](auto* host, auto, const char* name) { need(host, name); });
+        need(mi->dtm, "dtm");
+        return missing ? fail(std::string("null input: micro ") + missing) : (int)MCF_OK;
     });
-    return rc;
 }
-}  // namespace
+}  // namespace mcf
 
-// the snow plan's own resident coarse set of the snow-day microclimate (ten arrays of the whole series; not the snow model's)
-struct MicroCoarseState {
-    MicroFineArgs fa;
-};
-static void micro_coarse_release(MicroCoarseState* ms) { delete ms; }
-// hours hour0 .. hour0 + ns - 1 of the series in `mask` into the plan's slabs from step slab_off on; precip_into: where the
-// precipitation goes instead of its own slab (the set-up's scan streams temp and precip through the first two slabs)
-static int micro_coarse_fill(mcf_snowplan* sp, int64_t hour0, int ns, int64_t slab_off, uint32_t mask, double* precip_into) {
-    MicroFineArgs fa = sp->mcoarse->fa;
-    fa.hour0 = hour0; fa.mask = mask;
-    for (int f = 0; f < kMicroSeries; ++f) fa.o[f] = sp->d_micro[f] + slab_off * sp->N;
-    if (precip_into) fa.o[MF_PRECIP] = precip_into;
-    const bool timing = getenv("MCF_TIMING") != nullptr && mask == kMicroAll;
-    Events evs;
-    if (timing) { HIP_TRY(evs.make(2)); HIP_TRY(hipEventRecord(evs.e[0], nullptr)); }
-    launch_micro_fine(fa, ns, nullptr);
-    HIP_TRY(hipGetLastError());
-    if (timing) {
-        HIP_TRY(hipEventRecord(evs.e[1], nullptr));
-        HIP_TRY(hipEventSynchronize(evs.e[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, evs.e[0], evs.e[1]));
-        sp->t_micro_fine += ms;
-        sp->n_micro_fine += ns;
-    }
-    return MCF_OK;
-}
-
-extern "C" int mcf_microsnow_expand_coarse_device(const mcf_microcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[9],
-                                                  int32_t device) {
-    const char* entry = "mcf_microsnow_expand_coarse_device";
-    int rc;
-    if (!in) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: in");
-    if (!fine) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine");
-    if ((rc = microcoarse_checks(in, entry))) return rc;
-    uint32_t mask = 0;                   // a null fine[f]: series f is not wanted
-    for (int f = 0; f < kMicroSeries; ++f) mask |= fine[f] ? 1u << f : 0u;
-    if (!mask) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[] (every series is null)");
-    if (step0 < 0 || nsteps < 1 || step0 > in->tsteps - nsteps)
+namespace {
+using mcf::snowcoarse_checks;
+using mcf::microcoarse_checks;
+// The two entries that expand alone (tests and tools hold the kernels to the host's expansion through them): hours step0 ..
+// step0 + nsteps - 1 of the series in `mask` — of nseries, made from nseries + 1 coarse arrays — into the host arrays fine[].
+// outputs(fa, d): the device arrays d[] (null: not wanted) into the kernel's arguments.
+template <class Args, class In, class Each, class Outs>
+int expand_coarse_alone(const char* entry, const CoarseGrid& g, const In* in, Each&& each, const double* dtm, int64_t tsteps,
+                        int64_t step0, int64_t nsteps, int nseries, uint32_t mask, double* const fine[], Outs&& outputs, int32_t device) {
+    if (step0 < 0 || nsteps < 1 || step0 > tsteps - nsteps)
         return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": step0 >= 0, nsteps >= 1 and step0 + nsteps <= tsteps are needed");
+    int rc;
     if ((rc = pick_device(device))) return rc;
-    const int64_t N = in->rows * in->cols, CC = in->coarse_rows * in->coarse_cols;
-    if ((rc = check_room((9 * nsteps + 1) * N * 8 + 10 * CC * nsteps * 8))) return rc;
+    const int64_t N = g.cells(), CC = g.coarse_cells();
+    if ((rc = check_room((nseries * nsteps + 1) * N * 8 + (nseries + 1) * CC * nsteps * 8))) return rc;
     mcf::DevOwner b;
-    MicroFineArgs fa;
-    if ((rc = micro_coarse_upload(b, in, step0, nsteps, nullptr, &fa))) return rc;
-    fa.mask = mask;
-    for (int f = 0; f < kMicroSeries; ++f)
-        if (fine[f] && (rc = b.make(&fa.o[f], N * nsteps))) return rc;
-    launch_micro_fine(fa, (int)nsteps, nullptr);
+    Args fa;
+    if ((rc = coarse_upload(b, g, in, each, dtm, step0, nsteps, nullptr, &fa))) return rc;
+    double* d[13] = {};
+    for (int f = 0; f < nseries; ++f)
+        if ((mask >> f & 1u) && (rc = b.make(&d[f], N * nsteps))) return rc;
+    outputs(fa, d);
+    launch_coarse_hours(fa, (int)nsteps, nullptr);
     HIP_TRY(hipGetLastError());
     mcf::ToHost dl;
-    for (int f = 0; f < kMicroSeries; ++f)
-        if (fine[f]) HIP_TRY(dl.dense(fine[f], fa.o[f], (size_t)(N * nsteps) * 8));
+    for (int f = 0; f < nseries; ++f)
+        if (d[f]) HIP_TRY(dl.dense(fine[f], d[f], (size_t)(N * nsteps) * 8));
     HIP_TRY(hipDeviceSynchronize());
     return MCF_OK;
 }
-namespace mcf {   // mcf_snowrun.hip
-int microcoarse_arg_checks(const mcf_microcoarse_in* in, const char* entry) { return microcoarse_checks(in, entry); }
-int snowcoarse_run_checks(const mcf_snowcoarse_in* in, const char* entry) {
-    static const int dummy = 0;
-    return snowcoarse_checks(in, &dummy, true, entry);
+}  // namespace
+
+extern "C" int mcf_snow_expand_coarse_device(const mcf_snowcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[13],
+                                             int32_t device) {
+    const char* entry = "mcf_snow_expand_coarse_device";
+    if (const int rc = snowcoarse_checks(in, false, entry, fine ? nullptr : "fine")) return rc;
+    for (int f = 0; f < 13; ++f)
+        if (!fine[f]) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[" + std::to_string(f) + "]");
+    const mcf_snow_inputs& base = in->drv.base;
+    return expand_coarse_alone<FineArgs>(entry, coarse_grid(*in, base.rows, base.cols), in, kSnowCoarseArrays, in->drv.dtm, base.tsteps, step0,
+                                         nsteps, 13, (1u << 13) - 1, fine, [](FineArgs& fa, double* const d[]) { fine_outputs(fa, d); }, device);
 }
+extern "C" int mcf_microsnow_expand_coarse_device(const mcf_microcoarse_in* in, int64_t step0, int64_t nsteps, double* const fine[9],
+                                                  int32_t device) {
+    const char* entry = "mcf_microsnow_expand_coarse_device";
+    if (!in) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: in");
+    if (!fine) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine");
+    if (const int rc = microcoarse_checks(in, entry)) return rc;
+    uint32_t mask = 0;                   // a null fine[f]: series f is not wanted
+    for (int f = 0; f < kMicroSeries; ++f) mask |= fine[f] ? 1u << f : 0u;
+    if (!mask) return mcf::api_fail(MCF_ERR_ARG, std::string(entry) + ": null argument: fine[] (every series is null)");
+    auto outputs = [&](MicroFineArgs& fa, double* const d[]) {
+        fa.mask = mask;
+        for (int f = 0; f < kMicroSeries; ++f) fa.o[f] = d[f];
+    };
+    return expand_coarse_alone<MicroFineArgs>(entry, coarse_grid(*in, in->rows, in->cols), in, kMicroCoarseArrays, in->dtm, in->tsteps, step0,
+                                              nsteps, kMicroSeries, mask, fine, outputs, device);
+}
+
+namespace mcf {   // mcf_snow_plan.hpp
 // the micro group's coarse set onto the plan (once, before mcf_snowplan_micro_setup, whose `sub` then carries no weather arrays)
 int snowplan_micro_attach_coarse(mcf_snowplan* sp, const mcf_microcoarse_in* mi) {
     if (!sp || !mi) return api_fail(MCF_ERR_ARG, "null argument");
@@ -3454,17 +3411,14 @@ int snowplan_micro_attach_coarse(mcf_snowplan* sp, const mcf_microcoarse_in* mi)
     HIP_TRY(hipSetDevice(sp->device));
     if (const int rc = check_room((int64_t)kMicroSeries * sp->chunk * sp->N * 8 + 10 * mi->coarse_rows * mi->coarse_cols * mi->tsteps * 8))
         return rc;
-    sp->mcoarse = new MicroCoarseState();
-    return micro_coarse_upload(sp->b, mi, 0, sp->T, sp->d_dtm, &sp->mcoarse->fa);
+    sp->mcoarse.emplace();
+    return coarse_upload(sp->b, coarse_grid(*mi, mi->rows, mi->cols), mi, kMicroCoarseArrays, mi->dtm, 0, sp->T, sp->d_dtm, &*sp->mcoarse);
 }
 // where a coarse plan's run_chunk hands pointm$umu to (null: nowhere — pass 2's re-runs of a chunk)
 void snowplan_coarse_umu_out(mcf_snowplan* sp, double* umu_out) {
-    if (sp && sp->coarse) sp->coarse->h_umu = umu_out;
+    if (sp && sp->coarse) sp->h_umu = umu_out;
 }
-int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out) {
-    return snowcoarse_checks(in, out, true, "mcf_snowmodel2_coarse");
-}
-}
+}  // namespace mcf
 
 // ---- the snow-day microclimate inside the chunk loop --------------------------------------------------------------------
 extern "C" int mcf_snowplan_reset(mcf_snowplan* sp) {

@@ -32,8 +32,8 @@
 // The snow model's own entries (mcf_snowmodel1 / 2, mcf_snowmodel1_multi, at the end) run the same chunk loop (snow_chunk).
 //
 // Array weather with the coarse arrays left coarse (mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse): one block
-// whose snow plan expands a chunk's thirteen series (k_fine_chunk) and a run of snow days' nine microclimate series (k_micro_fine)
-// from resident coarse arrays, and whose solver plan interpolates its own (array_forcing == 2) — the same two passes, nothing of
+// whose snow plan expands a chunk's thirteen series and a run of snow days' nine microclimate series (k_coarse_hours over either
+// argument struct) from resident coarse arrays, and whose solver plan interpolates its own (array_forcing == 2) — the same two passes, nothing of
 // size cells x steps uploaded; the solver's temperature cap over the no-snow days from the resident series (mcf_plan_set_mxtc_days).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -50,29 +50,8 @@
 
 #include "../../include/mcf.h"
 #include "mcf_rowblocks.hpp"
+#include "mcf_snow_plan.hpp"
 
-namespace mcf {   // mcf_snow.hip
-int64_t snowplan_halo_rows(const mcf_snowplan* sp, int32_t af);
-void snowplan_print_timing(const mcf_snowplan* sp);
-int snowcoarse_model_checks(const mcf_snowcoarse_in* in, const mcf_snowfast2_out* out);
-int snowplan_create_coarse(const mcf_snowcoarse_in* co, double* umu_out, int32_t device, mcf_snowplan** out);
-// the coarse snow run: its groups' own checks under the entry's name, the microclimate's coarse set onto a plan, and where a
-// coarse plan's chunks hand pointm$umu to
-int snowcoarse_run_checks(const mcf_snowcoarse_in* in, const char* entry);
-int microcoarse_arg_checks(const mcf_microcoarse_in* in, const char* entry);
-int snowplan_micro_attach_coarse(mcf_snowplan* sp, const mcf_microcoarse_in* mi);
-void snowplan_coarse_umu_out(mcf_snowplan* sp, double* umu_out);
-// (over the listings of the snow entries' array groups, kept there next to the kernels' argument structs)
-bool model_rasters_given(const mcf_snow_inputs& in);
-void model_rasters_of_block(mcf_snowdriver_in& in, HostCopies* rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
-bool micro_rasters_given(const mcf_snow_inputs& in);
-void micro_rasters_of_block(mcf_snow_inputs& in, HostCopies& rows, int64_t R, int64_t C, int64_t r0, int64_t nr);
-const char* micro_series_missing(const mcf_snow_inputs& in);
-void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, int ndays, int nsub, HostCopies& keep);
-// the summaries' specs judged without a device, and the selected series as a mcf_snowplan_set_series mask
-int snowpack_spec_check(const mcf_snowpack_summary_spec* s, int64_t tsteps, int64_t chunk_steps);
-uint32_t snowpack_series_bits(const mcf_snowpack_summary_spec* s);
-}
 namespace mcf {   // mcf_api.hip
 int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask);
 int plan_summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch);
@@ -130,12 +109,15 @@ struct SnowBlocks {
     }
 };
 
-// block b's snow plan on `device`: one block reads the caller's arrays in place, more gather their rows
-int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& snow) {
+// block b's snow plan on `device`: one block reads the caller's arrays in place, more gather their rows.  co: coarse array
+// weather (one block; `snow` is co->drv) — the plan expands its chunks from the resident coarse arrays, pointm$umu goes to umu_out
+int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& snow, const mcf_snowcoarse_in* co = nullptr,
+                   double* umu_out = nullptr) {
     Block& k = sb.blocks[(size_t)b];
     const int64_t R = sb.R, C = sb.C;
     k.device = device;
     k.r0 = R * b / sb.nb; k.nr = R * (b + 1) / sb.nb - k.r0;
+    if (co) return mcf::snowplan_create_coarse(co, umu_out, device, &k.sp);
     mcf_snowdriver_in bi = snow;
     mcf::model_rasters_of_block(bi, sb.nb > 1 ? &k.model_rows : nullptr, R, C, k.r0, k.nr);
     return mcf_snowplan_create(&bi, k.r0, R, k.device, &k.sp);
@@ -324,8 +306,8 @@ int check_create_coarse(const mcf_microsnow_coarse_in* in, const mcf_options* op
     if (opt->reqhgt < 0) return fail("reqhgt < 0 is not supported with coarse array weather");
     if (mu && (mu->n_blocks > 1 || mu->n_devices > 1)) return fail("one block on one device");
     int rc;
-    if ((rc = mcf::snowcoarse_run_checks(in->snow, entry))) return rc;
-    if ((rc = mcf::microcoarse_arg_checks(in->micro, entry))) return rc;
+    if ((rc = mcf::snowcoarse_checks(in->snow, true, entry, nullptr))) return rc;
+    if ((rc = mcf::microcoarse_checks(in->micro, entry))) return rc;
     const mcf_snow_inputs& sb = s.drv.base;
     if (g.rows != sb.rows || g.cols != sb.cols || g.tsteps != sb.tsteps || m.rows != sb.rows || m.cols != sb.cols || m.tsteps != sb.tsteps)
         return fail("grid, snow and micro differ in rows / cols / tsteps");
@@ -373,14 +355,9 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
         rc = mcf::run_workers(h->nt, [&](Worker& w) {
             mcf::for_blocks(w, h->nb, h->nt, [&](int b) -> int {
                 Block& k = h->blocks[(size_t)b];
-                int rc2;
-                if (co) {          // one block: the snow plan expands its chunks, and the microclimate's snow days, from coarse arrays
-                    k.device = h->devs[(size_t)w.t]; k.r0 = 0; k.nr = R;
-                    rc2 = mcf::snowplan_create_coarse(co->snow, umu_out, k.device, &k.sp);
-                    if (!rc2) rc2 = mcf::snowplan_micro_attach_coarse(k.sp, co->micro);
-                } else {
-                    rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow);
-                }
+                // (the coarse run: one block, whose snow plan expands its chunks, and the microclimate's snow days, from coarse arrays)
+                int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow, co ? co->snow : nullptr, umu_out);
+                if (!rc2 && co) rc2 = mcf::snowplan_micro_attach_coarse(k.sp, co->micro);
                 if (rc2) return rc2;
                 // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
                 k.gsub = mcf::narrow_rows(h->grid, k.r0, k.nr, R);
@@ -927,7 +904,7 @@ extern "C" int mcf_runmicrosnow1_multi(const mcf_microsnow_in* in, const mcf_opt
 }
 
 // The array-weather run with every coarse array left coarse (include/mcf.h mcf_runmicrosnow2_coarse): the chunk loop of
-// mcf_snowmodel2_coarse, a coarse solver plan, and the microclimate's snow days expanded on the device (mcf_snow.hip k_micro_fine)
+// mcf_snowmodel2_coarse, a coarse solver plan, and the microclimate's snow days expanded on the device (mcf_snow.hip k_coarse_hours)
 extern "C" int mcf_snowrun_create_coarse(const mcf_microsnow_coarse_in* in, const mcf_options* opt, const mcf_multi* mu, double* umu_out,
                                          mcf_snowrun** out) {
     const char* entry = "mcf_snowrun_create_coarse";
@@ -966,8 +943,10 @@ extern "C" int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in* in, const m
 // or over row blocks of ONE raster held by this process (include/mcf.h mcf_snowmodel1_multi: block b on devices[b % n_devices];
 // EVERY block's plan stays resident, the chunk loop couples the blocks at every chunk)
 // spec / sout: the snowpack's period summaries (mcf_snowmodel1_summary, which has checked them), folded behind every chunk
+// co / umu_out: coarse array weather (mcf_snowmodel2_coarse, which has checked it; `in` is &co->drv) and where pointm$umu goes
 static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device,
-                     const mcf_snowpack_summary_spec* spec = nullptr, mcf_snowpack_summary_out* sout = nullptr) {
+                     const mcf_snowpack_summary_spec* spec = nullptr, mcf_snowpack_summary_out* sout = nullptr,
+                     const mcf_snowcoarse_in* co = nullptr, double* umu_out = nullptr) {
     if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     try {
         SnowBlocks sb;
@@ -977,7 +956,7 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
         else if ((rc = mcf::device_list(mu, 0, &sb.devs))) return rc;
         sb.cut(mu ? mu->n_blocks : 1);
         rc = mcf::run_workers(sb.nt, [&](Worker& w) {
-            mcf::for_blocks(w, sb.nb, sb.nt, [&](int b) { return block_snowplan(sb, b, sb.devs[(size_t)w.t], *in); });
+            mcf::for_blocks(w, sb.nb, sb.nt, [&](int b) { return block_snowplan(sb, b, sb.devs[(size_t)w.t], *in, co, umu_out); });
         });
         if (rc) return rc;
         const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
@@ -1030,28 +1009,10 @@ extern "C" int mcf_snowmodel1_summary(const mcf_snowdriver_in* in, const mcf_sno
     return snowmodel(in, &none, mu, 0, spec, out);
 }
 // `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
-// (mcf_snow.hip, k_fine_chunk) and hands pointm$umu out of the chunk's slab
+// (mcf_snow.hip, k_coarse_hours) and hands pointm$umu out of the chunk's slab
 extern "C" int mcf_snowmodel2_coarse(const mcf_snowcoarse_in* in, mcf_snowfast2_out* out, int32_t device) {
-    if (const int rc = mcf::snowcoarse_model_checks(in, out)) return rc;      // nothing above needs a device
-    try {
-        SnowBlocks sb;
-        sb.R = in->drv.base.rows; sb.C = in->drv.base.cols;
-        sb.devs.push_back(device);
-        sb.cut(1);
-        sb.blocks[0].device = device; sb.blocks[0].r0 = 0; sb.blocks[0].nr = sb.R;
-        int rc = mcf::run_workers(1, [&](Worker& w) {
-            mcf::for_blocks(w, 1, 1, [&](int) { return mcf::snowplan_create_coarse(in, out->umu, device, &sb.blocks[0].sp); });
-        });
-        if (rc) return rc;
-        const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
-        rc = mcf::run_workers(1, [&](Worker& w) {
-            for (int ch = 0; ch < nchunks; ++ch) snow_chunk(sb, w, ch, &out->smod);
-        });
-        if (!rc && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
-        return rc;
-    } catch (const std::exception& e) {
-        return api_fail(MCF_ERR_NOMEM, std::string("snow driver: ") + e.what());
-    }
+    if (const int rc = mcf::snowcoarse_checks(in, true, "mcf_snowmodel2_coarse", out ? nullptr : "out")) return rc;      // no device yet
+    return snowmodel(&in->drv, &out->smod, nullptr, device, nullptr, nullptr, in, out->umu);
 }
 extern "C" int mcf_snowmodel1_multi(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu) {
     if (!in || !out || !mu) return api_fail(MCF_ERR_ARG, "null snow driver argument");

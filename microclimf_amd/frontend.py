@@ -752,13 +752,7 @@ def prepare_grid_inputs_array(micropointa: Sequence, crows: int, ccols: int, req
     first = micropointa[0]
     base = prepare_grid_inputs(first, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, slr=slr, apr=apr, hor=hor, twi=twi,
                                wsa=wsa, svf=svf, device=device)
-    T = len(first["weather"]["temp"])
-
-    def grid(get):
-        a = np.empty((crows, ccols, T), order="F")
-        for k, m in enumerate(micropointa):
-            a[k // ccols, k % ccols, :] = get(m)
-        return a
+    grid = lambda get: _stack_micropoints(micropointa, crows, ccols, get)                      # noqa: E731
     clim = {k: grid(lambda m, k=k: m["weather"][k]) for k in ("temp", "relhum", "pres", "swdown", "difrad", "lwdown",
                                                                 "windspeed", "winddir")}
     pm = {"soilm": "soilm", "Gp": "G", "umu": "umu", "kp": "kp", "muGp": "muGp", "dtrp": "dtrp"}
@@ -1122,6 +1116,46 @@ def sortl2(vegp, sdep, reqhgt, pai_a=None):
     return out
 
 
+def _stack_micropoints(mps: Sequence, crows: int, ccols: int, get) -> np.ndarray:
+    """get(micropoint) -> [T] of every coarse cell (the micropoints run along the rows of the climate grid) as [crows, ccols, T]"""
+    a = np.empty((crows, ccols, len(mps[0]["weather"]["temp"])), order="F")
+    for k, m in enumerate(mps):
+        a[k // ccols, k % ccols, :] = get(m)
+    return a
+
+
+def _snow_day_other(z, dtm: Mapping, zref, lat, lon, soil: Mapping, device: int, _terrain) -> dict:
+    """gridmicrosnow's `other`: the bare-ground terrain of the dtm (`_terrain`: the tests' stand-in), the site(s), Smax"""
+    res = dtm["res"]
+    xres = res if np.isscalar(res) else res[0]
+    ter = terrain.precompute_terrain(z, xres, zref, device=device) if _terrain is None else _terrain(z, xres, zref)
+    return {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
+            "lat": lat, "lon": lon, "zref": float(zref), "Smax": soilinit(soil)["Smax"]}
+
+
+def _snow_day_template(moutn: Mapping, snowdays, nosnowdays, rows: int, cols: int) -> dict:
+    """the snow days' outputs as gridmicrosnow receives them: the solver's values on the days of both classes, NaN elsewhere"""
+    t1 = len(snowdays) * 24
+    s1 = np.arange(t1)[np.repeat(np.isin(snowdays, nosnowdays), 24)]
+    s2 = np.arange(len(nosnowdays) * 24)[np.repeat(np.isin(nosnowdays, snowdays), 24)]
+    micro = {}
+    for k, v in moutn.items():
+        a = np.full((rows, cols, t1), np.nan, order="F")
+        if len(s1):
+            a[:, :, s1] = np.asarray(v)[:, :, s2]
+        micro[k] = a
+    return micro
+
+
+def _snow_day_outm(out: Sequence, reqhgt: float) -> list:
+    """which of the ten outputs gridmicrosnow writes: the caller's selection above ground, a fixed set at and below it"""
+    if reqhgt == 0:
+        return [1 if i in (0, 3, 5, 6, 7, 8, 9) else 0 for i in range(10)]
+    if reqhgt < 0:
+        return [1 if i in (0, 3) else 0 for i in range(10)]
+    return [int(bool(v)) for v in out]
+
+
 def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, smod: Mapping | None, *,
                   pai_a=None, tfact: float = 1.5, out: Sequence = (1,) * 10, device: int = 0,
                   _solve=None, _microsnow=None, _terrain=None, one_call: bool = False, snow_inputs: Mapping | None = None) -> dict:
@@ -1163,29 +1197,10 @@ def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapp
     sdept = np.zeros(micropoint["ntme"])
     sdept[np.asarray(mps["subs"]) - 1] = 1
     vg = sortl2(veg, sdept, reqhgt, pai_a)
-    res = dtm["res"]
-    xres = res if np.isscalar(res) else res[0]
-    ter = (terrain.precompute_terrain(z, xres, micropoint["zref"], device=device) if _terrain is None
-           else _terrain(z, xres, micropoint["zref"]))
-    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
-             "lat": float(micropoint["lat"]), "lon": float(micropoint["long"]), "zref": float(micropoint["zref"]),
-             "Smax": soilinit(soil)["Smax"]}
-    t1 = len(snowdays) * 24
-    s1 = np.arange(t1)[np.repeat(np.isin(snowdays, nosnowdays), 24)]
-    s2 = np.arange(len(nosnowdays) * 24)[np.repeat(np.isin(nosnowdays, snowdays), 24)]
-    micro = {}
-    for k, v in moutn.items():
-        a = np.full((rows, cols, t1), np.nan, order="F")
-        if len(s1):
-            a[:, :, s1] = np.asarray(v)[:, :, s2]
-        micro[k] = a
-    outm = [int(bool(v)) for v in out]
-    if reqhgt == 0:
-        outm = [1 if i in (0, 3, 5, 6, 7, 8, 9) else 0 for i in range(10)]
-    elif reqhgt < 0:
-        outm = [1 if i in (0, 3) else 0 for i in range(10)]
+    other = _snow_day_other(z, dtm, micropoint["zref"], float(micropoint["lat"]), float(micropoint["long"]), soil, device, _terrain)
+    micro = _snow_day_template(moutn, snowdays, nosnowdays, rows, cols)
     smods = subsetsnowmodel(sm, ai + 1)
-    mouts = microsnow(reqhgt, mps["obstime"], w, smods, micro, vg, other, float(micropoint["matemp"]), outm)
+    mouts = microsnow(reqhgt, mps["obstime"], w, smods, micro, vg, other, float(micropoint["matemp"]), _snow_day_outm(out, reqhgt))
     return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
 
 
@@ -1223,13 +1238,7 @@ def _one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_
     sdept = np.zeros(micropoint["ntme"])
     sdept[np.asarray(subsetpointmodel(micropoint, days=snowdays)["subs"]) - 1] = 1
     vg = sortl2(veg, sdept, reqhgt, pai_a)
-    res = dtm["res"]
-    xres = res if np.isscalar(res) else res[0]
-    ter = (terrain.precompute_terrain(z, xres, micropoint["zref"], device=device) if _terrain is None
-           else _terrain(z, xres, micropoint["zref"]))
-    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
-             "lat": float(micropoint["lat"]), "lon": float(micropoint["long"]), "zref": float(micropoint["zref"]),
-             "Smax": soilinit(soil)["Smax"]}
+    other = _snow_day_other(z, dtm, micropoint["zref"], float(micropoint["lat"]), float(micropoint["long"]), soil, device, _terrain)
     w = dict(micropoint["weather"])
     w["umu"] = np.asarray(snow_inputs["umu"])
     return {"obstime": micropoint["obstime"], "climdata": w, "vegp": vg, "other": other}
@@ -1372,42 +1381,20 @@ def runmicro_snow_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: f
     if not len(snowdays):
         return moutn
     mps = [subsetpointmodel(m, days=snowdays) for m in micropointa]
-    h = len(snowdays) * 24
     ai = (np.repeat((snowdays - 1) * 24, 24) + np.tile(np.arange(24), snowdays.size)).astype(np.int64)
-
-    def grid(get):
-        a = np.empty((crows, ccols, h), order="F")
-        for k, m in enumerate(mps):
-            a[k // ccols, k % ccols, :] = get(m)
-        return a
     rowpos, colpos = api.coarse_positions(rows, crows), api.coarse_positions(cols, ccols)
-    wc = {k: grid(lambda m, k=k: m["weather"][k]) for k in WEATHER}
+    wc = {k: _stack_micropoints(mps, crows, ccols, lambda m, k=k: m["weather"][k]) for k in WEATHER}
     zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0) if altcorrect else None
-    w = S._fine_micro_inputs(wc, grid(lambda m: m["dfo"]["umu"]), slice(None), z, zc, rowpos, colpos, altcorrect)
+    w = S._fine_micro_inputs(wc, _stack_micropoints(mps, crows, ccols, lambda m: m["dfo"]["umu"]), slice(None), z, zc, rowpos, colpos,
+                             altcorrect)
     last = micropointa[-1]
     vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
-    res = dtm["res"]
-    xres = res if np.isscalar(res) else res[0]
-    zref = float(last["zref"])
-    ter = terrain.precompute_terrain(z, xres, zref, device=device) if _terrain is None else _terrain(z, xres, zref)
-    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
-             "lat": np.asarray(lats, dtype=np.float64), "lon": np.asarray(lons, dtype=np.float64), "zref": zref,
-             "Smax": soilinit(soil)["Smax"]}
-    s1 = np.arange(h)[np.repeat(np.isin(snowdays, nosnowdays), 24)]
-    s2 = np.arange(len(nosnowdays) * 24)[np.repeat(np.isin(nosnowdays, snowdays), 24)]
-    micro = {}
-    for k, v in moutn.items():
-        a = np.full((rows, cols, h), np.nan, order="F")
-        if len(s1):
-            a[:, :, s1] = np.asarray(v)[:, :, s2]
-        micro[k] = a
-    outm = [int(bool(v)) for v in out]
-    if reqhgt == 0:
-        outm = [1 if i in (0, 3, 5, 6, 7, 8, 9) else 0 for i in range(10)]
-    elif reqhgt < 0:
-        outm = [1 if i in (0, 3) else 0 for i in range(10)]
+    other = _snow_day_other(z, dtm, float(last["zref"]), np.asarray(lats, dtype=np.float64), np.asarray(lons, dtype=np.float64), soil,
+                            device, _terrain)
+    micro = _snow_day_template(moutn, snowdays, nosnowdays, rows, cols)
     smods = {k: np.asfortranarray(np.asarray(sm[k])[:, :, ai]) for k in ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden")}
-    mouts = microsnow(reqhgt, mps[0]["obstime"], w, smods, micro, vg, other, float(np.mean([m["matemp"] for m in micropointa])), outm)
+    mouts = microsnow(reqhgt, mps[0]["obstime"], w, smods, micro, vg, other, float(np.mean([m["matemp"] for m in micropointa])),
+                      _snow_day_outm(out, reqhgt))
     return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
 
 
@@ -1431,22 +1418,11 @@ def snow_array_groups(micropointa: Sequence, crows: int, ccols: int, reqhgt: flo
     if altcorrect:
         coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=z)
     a["coarse"] = coarse
-    T = len(micropointa[0]["weather"]["temp"])
-
-    def grid(get):
-        g = np.empty((crows, ccols, T), order="F")
-        for k, m in enumerate(micropointa):
-            g[k // ccols, k % ccols, :] = get(m)
-        return g
     last = micropointa[-1]
     vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
-    res = dtm["res"]
-    xres = res if np.isscalar(res) else res[0]
-    zref = float(last["zref"])
-    ter = terrain.precompute_terrain(z, xres, zref, device=device) if _terrain is None else _terrain(z, xres, zref)
-    other = {"slope": ter["slope"], "aspect": ter["aspect"], "hor": ter["hor"], "skyview": ter["svfa"], "wsa": ter["wsa"],
-             "lat": np.asarray(lats, dtype=np.float64), "lon": np.asarray(lons, dtype=np.float64), "zref": zref,
-             "Smax": soilinit(soil)["Smax"]}
+    other = _snow_day_other(z, dtm, float(last["zref"]), np.asarray(lats, dtype=np.float64), np.asarray(lons, dtype=np.float64), soil,
+                            device, _terrain)
+    grid = lambda get: _stack_micropoints(micropointa, crows, ccols, get)                      # noqa: E731
     micro = {"clim_c": {k: grid(lambda m, k=k: m["weather"][k]) for k in WEATHER}, "umu_c": grid(lambda m: m["dfo"]["umu"]),
              "obstime": micropointa[0]["obstime"], "vegp": vg, "other": other}
     return a, dict(snow_inputs), micro, float(np.mean([m["matemp"] for m in micropointa]))
