@@ -61,7 +61,9 @@ extern "C" {
                              *    mcf_runmicro_summary_multi, mcf_snowmodel2_coarse, mcf_snow_expand_coarse_device, mcf_snowplan_summary_*,
                              *    mcf_snowrun_summary_*, mcf_runmicrosnow_summary, mcf_snowmodel1_summary,
                              *    mcf_microsnow_expand_coarse_device, mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse,
-                             *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc) */
+                             *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc, mcf_plan_below_set_depths,
+                             *    mcf_plan_fetch_depth*, mcf_plan_summary_enable_below, mcf_plan_summary_fetch_depth, mcf_runmicro_depths,
+                             *    mcf_runmicro_depths_summary) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -328,6 +330,42 @@ int mcf_plan_below_set_days(mcf_plan *plan, const int32_t *days, int32_t n);
  * [day0, day0 + ndays); *npos = 0: none. */
 int mcf_below_days_range(const int32_t *days, int32_t n, int32_t total_days, int32_t day0, int32_t ndays, int32_t *pos0,
                          int32_t *npos);
+/* Below ground at several depths from one solve.  Below ground the solver's work does not depend on the depth (reqhgt2 =
+ * max(reqhgt, 1e-5); Tg, the damping depth and soilm read neither paia nor leafden); only the tail of Tbelowgroundv does: the
+ * window length n = round(-118.35 reqhgt / meanD), the circular n/24-day means and, complete = 0, the point model's Tbp.
+ * mcf_plan_below_set_depths hands a streamed below-ground plan that was created with Tz requested a list of depths, before
+ * mcf_plan_below_prepare: depths[d] < 0 in any order (a depth may repeat), 1 <= ndepths <= MCF_MAX_DEPTHS.  The list replaces
+ * opt.reqhgt for everything Tbelowgroundv does.  tbp: [ndepths][tsteps], the point model's soil temperature at each depth
+ * (pointm$Tbp of a run at that depth); read only with complete = 0, where NULL is MCF_ERR_ARG.  The prepare and
+ * mcf_plan_run_days keep their contracts (day order from day 0, the steps behind the last whole day); the damping-depth sum,
+ * the hourly sum, the daily means, the 47-step windows and the chunk's Tg are shared by all depths, and per depth there is one
+ * row of circular means (days x cells, complete = 1) and one Tz slab per ring slot.  Slab 0 is the slot's own Tz:
+ * mcf_plan_fetch*, mcf_plan_fetch_packed and mcf_nc_write_plan see depths[0] there.  Every depth's Tz has the bits of a
+ * single-depth run at that depth.
+ * MCF_ERR_STATE: a plan that is not streamed below ground (the whole-series plan of mcf_plan_create refuses depth lists and
+ * below-ground summaries alike), a plan without Tz, a call after the prepare or a second call, a plan with a day subset
+ * (mcf_plan_below_set_days; that call in turn refuses a plan with a depth list).  MCF_ERR_ARG: a null, empty or too long list, a
+ * depth >= 0 or NaN, a null tbp with complete = 0, array forcing (fine or coarse) together with complete = 0 — per-cell Tbp for
+ * several depths is not taken.  Every message starts with the entry's name. */
+#define MCF_MAX_DEPTHS 8
+int mcf_plan_below_set_depths(mcf_plan *plan, const double *depths, int32_t ndepths, const double *tbp);
+/* mcf_plan_fetch / mcf_plan_fetch_pitched for depth `depth` (0 .. ndepths - 1; a plan without a list has depth 0 alone) of a
+ * streamed below-ground plan's Tz. */
+int mcf_plan_fetch_depth(mcf_plan *plan, int32_t slot, int32_t depth, int64_t step0, int64_t nsteps, double *host_dst);
+int mcf_plan_fetch_depth_pitched(mcf_plan *plan, int32_t slot, int32_t depth, int64_t step0, int64_t nsteps, double *host_dst,
+                                 int64_t row_pitch);
+/* One call, host to host: a streamed plan at depths[0] (opt->reqhgt is ignored), the depths set, the prepare, the chunks in
+ * order.  opt->out is ignored: Tz at every depth and, where out->soilm is not NULL, soilm.  tz[d]: caller-allocated [rows, cols,
+ * tsteps] per depth, the steps behind the last whole day included (soilm's are NA there).  Chunks of opt->days_per_chunk days
+ * (0: sized from free device memory, the depth slabs counted).  Vector forcing with or without dfsel for complete 0 and 1;
+ * array and coarse array forcing for complete = 1.  The refusals of mcf_plan_below_set_depths that need no plan come before a
+ * device is needed; a series shorter than a day is MCF_ERR_ARG. */
+typedef struct mcf_depth_outputs {
+    double *tz[MCF_MAX_DEPTHS];
+    double *soilm;                 /* or NULL */
+} mcf_depth_outputs;
+int mcf_runmicro_depths(const mcf_grid_inputs *in, const mcf_options *opt, const double *depths, int32_t ndepths,
+                        const double *tbp, mcf_depth_outputs *out);
 int mcf_plan_sync(mcf_plan *plan);
 
 /* Copy `nsteps` time steps of variable `var` from ring slot `slot` (starting at
@@ -606,6 +644,27 @@ int mcf_runmicro_summary(const mcf_grid_inputs *in, const mcf_options *opt, cons
  * bit the single-device arrays. */
 int mcf_runmicro_summary_multi(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_summary_spec *spec, int32_t chunk_days,
                                const mcf_multi *multi, mcf_summary_out *out);
+/* Period summaries below ground: the sink on a streamed below-ground plan (mcf_plan_create_streamed, reqhgt < 0), with or
+ * without a depth list (without one: one depth, opt.reqhgt).  spec->var may select Tz and soilm (MCF_ERR_ARG otherwise); Tz is
+ * kept per depth.  The summary, its state rows, the NA rule and the day-order rule are the ones defined above;
+ * mcf_plan_summary_accumulate / _days / _reset work on such a plan as they do above ground (the fold reads each depth's slab of
+ * the slot, behind the mcf_plan_run_days that filled it; the steps behind the last whole day belong to no day).  With a depth
+ * list, mcf_plan_below_set_depths comes first.  mcf_plan_summary_enable itself keeps refusing streamed and below-ground plans,
+ * and the whole-series plan (mcf_plan_create, reqhgt < 0) is refused here as there (MCF_ERR_STATE). */
+int mcf_plan_summary_enable_below(mcf_plan *plan, const mcf_summary_spec *spec);
+/* mcf_plan_summary_fetch for one depth's Tz; with var = MCF_OUT_SOILM the depth must be 0. */
+int mcf_plan_summary_fetch_depth(mcf_plan *plan, int32_t depth, int32_t var, int32_t stat, double *host_dst);
+/* One call, host to host, as mcf_runmicro_depths runs it, each chunk folded as it is produced: nothing of size cells x steps
+ * exists on either side.  chunk_days = 0: sized from free device memory as mcf_runmicro_depths does.  tz[d][s] / soilm[s]:
+ * caller-allocated [rows, cols, nperiods] for every depth and selected statistic (a null one is MCF_ERR_ARG); days: [nperiods]
+ * or NULL. */
+typedef struct mcf_depth_summary_out {
+    double *tz[MCF_MAX_DEPTHS][MCF_NSTAT];
+    double *soilm[MCF_NSTAT];
+    int32_t *days;
+} mcf_depth_summary_out;
+int mcf_runmicro_depths_summary(const mcf_grid_inputs *in, const mcf_options *opt, const double *depths, int32_t ndepths,
+                                const double *tbp, const mcf_summary_spec *spec, int32_t chunk_days, mcf_depth_summary_out *out);
 
 /* ---- terrain pre-compute (the solver's terrain inputs, built on the device) ------
  * Restates the R-side arithmetic of the reference's marshaller (R/internal.R):

@@ -136,6 +136,19 @@ class SummaryOut(C.Structure):
     _fields_ = [("val", (c_double_p * NSTAT) * NOUT), ("days", c_int32_p)]
 
 
+MAX_DEPTHS = 8      # include/mcf.h MCF_MAX_DEPTHS
+
+
+class DepthOutputs(C.Structure):
+    """include/mcf.h mcf_depth_outputs"""
+    _fields_ = [("tz", c_double_p * MAX_DEPTHS), ("soilm", c_double_p)]
+
+
+class DepthSummaryOut(C.Structure):
+    """include/mcf.h mcf_depth_summary_out"""
+    _fields_ = [("tz", (c_double_p * NSTAT) * MAX_DEPTHS), ("soilm", c_double_p * NSTAT), ("days", c_int32_p)]
+
+
 class SnowpackSummarySpec(C.Structure):
     """include/mcf.h mcf_snowpack_summary_spec (series in SNOWDRIVER_OUT's order)"""
     _fields_ = [("nperiods", C.c_int32), ("period_of_day", c_int32_p), ("series", C.c_int32 * 5), ("stat", C.c_int32 * NSTAT),
@@ -342,6 +355,8 @@ EXPORTS = (
     "mcf_runmicro1_diag", "mcf_runmicro3_diag",
     "mcf_plan_summary_enable", "mcf_plan_summary_accumulate", "mcf_plan_summary_fetch", "mcf_plan_summary_days",
     "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
+    "mcf_plan_below_set_depths", "mcf_plan_fetch_depth", "mcf_plan_fetch_depth_pitched", "mcf_plan_summary_enable_below",
+    "mcf_plan_summary_fetch_depth", "mcf_runmicro_depths", "mcf_runmicro_depths_summary",
     "mcf_bioclim_last_chunks",
     "mcf_snowplan_summary_enable", "mcf_snowplan_summary_accumulate", "mcf_snowplan_summary_fetch", "mcf_snowplan_summary_days",
     "mcf_snowplan_summary_reset", "mcf_snowrun_summary_table", "mcf_snowrun_summary_enable", "mcf_snowrun_summary_fetch",
@@ -531,6 +546,23 @@ def load() -> C.CDLL:
         lib.mcf_runmicro_summary.argtypes = [GI, OP, SS, C.c_int32, SO_]
         lib.mcf_runmicro_summary_multi.restype = C.c_int
         lib.mcf_runmicro_summary_multi.argtypes = [GI, OP, SS, C.c_int32, C.POINTER(Multi), SO_]
+    if hasattr(lib, "mcf_plan_below_set_depths"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        SS = C.POINTER(SummarySpec)
+        lib.mcf_plan_below_set_depths.restype = C.c_int
+        lib.mcf_plan_below_set_depths.argtypes = [P, c_double_p, C.c_int32, c_double_p]
+        lib.mcf_plan_fetch_depth.restype = C.c_int
+        lib.mcf_plan_fetch_depth.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p]
+        lib.mcf_plan_fetch_depth_pitched.restype = C.c_int
+        lib.mcf_plan_fetch_depth_pitched.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p, C.c_int64]
+        lib.mcf_plan_summary_enable_below.restype = C.c_int
+        lib.mcf_plan_summary_enable_below.argtypes = [P, SS]
+        lib.mcf_plan_summary_fetch_depth.restype = C.c_int
+        lib.mcf_plan_summary_fetch_depth.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_runmicro_depths.restype = C.c_int
+        lib.mcf_runmicro_depths.argtypes = [GI, OP, c_double_p, C.c_int32, c_double_p, C.POINTER(DepthOutputs)]
+        lib.mcf_runmicro_depths_summary.restype = C.c_int
+        lib.mcf_runmicro_depths_summary.argtypes = [GI, OP, c_double_p, C.c_int32, c_double_p, SS, C.c_int32,
+                                                    C.POINTER(DepthSummaryOut)]
     lib.mcf_plan_fetch.restype = C.c_int
     lib.mcf_plan_fetch.argtypes = [P, C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_double_p]
     lib.mcf_plan_fetch_cells.restype = C.c_int

@@ -141,6 +141,93 @@ def runmicro_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp:
     return _summary_result(vi, si, arrays, days[:max(int(sp.nperiods), 0)])
 
 
+def _depth_list(depths, tbp, tsteps):
+    """(depths as float64, tbp as C-ordered [ndepths, tsteps] or None) for the C ABI"""
+    d = np.ascontiguousarray(np.atleast_1d(np.asarray(depths, dtype=np.float64))).ravel()
+    t = None
+    if tbp is not None:
+        t = np.ascontiguousarray(np.asarray(tbp, dtype=np.float64))
+        if t.shape != (d.size, tsteps):
+            raise ValueError(f"tbp: expected shape {(d.size, tsteps)} (one row of the point model's soil temperature per depth), got {t.shape}")
+    return d, t
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data_as(_abi.c_double_p)
+
+
+def runmicro_depths(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths, zref: float,
+                    lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, tbp=None, soilm: bool = True,
+                    array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                    days_per_chunk: int = 0, cells_per_block: int = 0) -> dict:
+    """Below ground at several depths from one solve (include/mcf.h mcf_runmicro_depths): the argument list of runmicro1Cpp with
+    `depths` (each < 0, any order, at most _abi.MAX_DEPTHS) in place of reqhgt and without `out`.  `tbp`: [ndepths, tsteps], the
+    point model's soil temperature at each depth (pointm$Tbp of a run at that depth), needed with complete = False.
+    `array_forcing` / `coarse` (complete = True only) and `dfsel` as for runmicro_summary.
+    -> {"Tz": [one [rows, cols, tsteps] array per depth], "soilm": [rows, cols, tsteps] (with soilm=True), "depths": depths}:
+    every array has the bits of runmicro1Cpp at that depth."""
+    lib = _abi.load()
+    af = bool(array_forcing) or coarse is not None
+    T = len(np.asarray(obstime["year"]))
+    d, t = _depth_list(depths, tbp, T)
+    reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0          # (the library judges the list)
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
+                [1, 0, 0, 1 if soilm else 0, 0, 0, 0, 0, 0, 0], af, device, days_per_chunk, cells_per_block, dfsel, coarse)
+    do = _abi.DepthOutputs()
+    tz = [np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F") for _ in range(min(d.size, _abi.MAX_DEPTHS))]
+    for i, a in enumerate(tz):
+        do.tz[i] = _ptr(a)
+    res = {"Tz": tz, "depths": d.copy()}
+    if soilm:
+        res["soilm"] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
+        do.soilm = _ptr(res["soilm"])
+    _abi.check(lib.mcf_runmicro_depths(C.byref(m.inputs), C.byref(m.options), _ptr(d), int(d.size), _ptr(t), C.byref(do)))
+    return res
+
+
+def runmicro_depths_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths,
+                            zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *,
+                            periods, tbp=None, vars=("Tz",), stats=("mean", "min", "max"), thresholds=None,
+                            nperiods: int | None = None, chunk_days: int = 0, array_forcing: bool = False,
+                            dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                            cells_per_block: int = 0) -> dict:
+    """Period summaries below ground at several depths (include/mcf.h mcf_runmicro_depths_summary): runmicro_depths with each
+    chunk folded on the device as it is produced.  `vars` among Tz and soilm; `periods`, `stats`, `thresholds`, `nperiods` as
+    for runmicro_summary.
+    -> {"Tz": [per depth {statistic: [rows, cols, nperiods]}], "soilm": {statistic: ...} (if selected), "days", "depths"}"""
+    lib = _abi.load()
+    sp, vi, si, _pod = summary_spec(periods, vars, stats, thresholds)
+    if nperiods is not None:
+        sp.nperiods = int(nperiods)
+    af = bool(array_forcing) or coarse is not None
+    T = len(np.asarray(obstime["year"]))
+    d, t = _depth_list(depths, tbp, T)
+    reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
+                [1, 0, 0, 1, 0, 0, 0, 0, 0, 0], af, device, 0, cells_per_block, dfsel, coarse)
+    so = _abi.DepthSummaryOut()
+    npd = max(int(sp.nperiods), 0)
+    plane = lambda: np.empty((m.rows, m.cols, npd), dtype=np.float64, order="F")
+    res = {"depths": d.copy()}
+    TZ, SM = _abi.OUT_NAMES.index("Tz"), _abi.OUT_NAMES.index("soilm")
+    if TZ in vi:
+        res["Tz"] = []
+        for i in range(min(d.size, _abi.MAX_DEPTHS)):
+            res["Tz"].append({_abi.STAT_NAMES[k]: plane() for k in si})
+            for k in si:
+                so.tz[i][k] = _ptr(res["Tz"][i][_abi.STAT_NAMES[k]])
+    if SM in vi:
+        res["soilm"] = {_abi.STAT_NAMES[k]: plane() for k in si}
+        for k in si:
+            so.soilm[k] = _ptr(res["soilm"][_abi.STAT_NAMES[k]])
+    days = np.zeros(max(npd, 1), dtype=np.int32)
+    so.days = days.ctypes.data_as(_abi.c_int32_p)
+    _abi.check(lib.mcf_runmicro_depths_summary(C.byref(m.inputs), C.byref(m.options), _ptr(d), int(d.size), _ptr(t), C.byref(sp),
+                                               int(chunk_days), C.byref(so)))
+    res["days"] = days[:npd]
+    return res
+
+
 def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
          Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel=None, coarse=None,
          devices=None, n_blocks=0, dtm=None, diag=None):
@@ -486,6 +573,41 @@ class Plan:
         subset's days inside that calendar range, each at its own place day - day0 of the slot."""
         d = np.ascontiguousarray(np.asarray(days).astype(np.int32))
         _abi.check(self._lib.mcf_plan_below_set_days(self._p, d.ctypes.data_as(_abi.c_int32_p), int(d.size)))
+
+    def below_set_depths(self, depths, tbp=None):
+        """Streamed below-ground plan with Tz, before below_prepare(): Tbelowgroundv at each of `depths` (< 0, any order, at most
+        _abi.MAX_DEPTHS) from the one solve (include/mcf.h mcf_plan_below_set_depths).  `tbp`: [ndepths, tsteps], the point
+        model's soil temperature per depth — needed with complete = False.  fetch() and the sinks see depths[0]."""
+        d, t = _depth_list(depths, tbp, self.tsteps)
+        _abi.check(self._lib.mcf_plan_below_set_depths(self._p, _ptr(d), int(d.size), _ptr(t)))
+        self.depths = d.copy()
+
+    def fetch_depth(self, slot: int, depth: int, step0: int, nsteps: int) -> np.ndarray:
+        """fetch() of Tz at depth index `depth` of the list (a plan without a list: 0)"""
+        a = np.empty((self.rows, self.cols, nsteps), dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_fetch_depth(self._p, slot, int(depth), step0, nsteps, a.ctypes.data_as(_abi.c_double_p)))
+        return a
+
+    def summary_enable_below(self, periods, vars=("Tz",), stats=("mean", "min", "max"), thresholds=None, *, nperiods=None):
+        """summary_enable() for a streamed below-ground plan, after below_set_depths() if there is a list (include/mcf.h
+        mcf_plan_summary_enable_below): `vars` among Tz and soilm, Tz kept per depth.  summary_accumulate / summary_days /
+        summary_reset work as above ground; fetch_summary_depth reads the planes."""
+        sp, vi, si, _pod = summary_spec(periods, vars, stats, thresholds)
+        if nperiods is not None:
+            sp.nperiods = int(nperiods)
+        if _pod.size != self.ndays:
+            raise ValueError(f"periods: one entry per day of the plan ({self.ndays}), got {_pod.size}")
+        _abi.check(self._lib.mcf_plan_summary_enable_below(self._p, C.byref(sp)))
+        self._summary_nperiods = int(sp.nperiods)
+        return [_abi.OUT_NAMES[v] for v in vi], [_abi.STAT_NAMES[s] for s in si]
+
+    def fetch_summary_depth(self, depth: int, var, stat) -> np.ndarray:
+        """fetch_summary() of Tz at depth index `depth`; soilm has depth 0 alone"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        s = _abi.STAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
+        a = np.empty((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)), dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_summary_fetch_depth(self._p, int(depth), v, s, a.ctypes.data_as(_abi.c_double_p)))
+        return a
 
     def sync(self):
         _abi.check(self._lib.mcf_plan_sync(self._p))

@@ -135,6 +135,10 @@ struct mcf_plan {
     double *d_sum_state = nullptr, *d_sum_plane = nullptr;
     int32_t *d_sum_pod = nullptr, *d_sum_prev = nullptr, *d_sum_next = nullptr, *d_sum_days = nullptr;
     int sum_nperiods = 0, sum_nrows = 0, sum_nsel = 0;
+    // mcf_plan_summary_enable_below: the state's first sum_nmain places are the ring's selected variables, the places behind
+    // them Tz at depths 1 .. D - 1 (sum_nmain = sum_nsel everywhere else)
+    int sum_nmain = 0;
+    bool sum_below = false;
     int sum_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
     int sum_row[MCF_NSTAT] = {};    // state row of a statistic, -1: not selected
     double sum_thr[MCF_NOUT] = {};
@@ -156,6 +160,12 @@ struct mcf_plan {
     double *d_tgring = nullptr, *d_hsum = nullptr, *d_dmean = nullptr, *d_ybuf = nullptr, *d_wrap = nullptr, *d_prev = nullptr;
     double *d_Tgp_slots = nullptr, *d_Tbp_slots = nullptr;      // [slots][ring_days * 24][N]
     int64_t tg_tile_stride = 0;
+    // mcf_plan_below_set_depths (empty: one depth, opt.reqhgt): the depths; beside the ring the Tz slabs of depths 1 .. D - 1,
+    // [depth][slot][tile][day][block] (the Tg ring's geometry per slot); their rows of circular means [depth][days][N]; with
+    // complete = 0 the point model's Tbp per depth [D][tsteps]
+    std::vector<double> depths;
+    double *d_tzx = nullptr, *d_ybufx = nullptr;
+    const double* d_Tbp_depths = nullptr;
     // timing
     bool ktiming = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> kev;
@@ -1255,6 +1265,16 @@ void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, 
 }
 
 // ---- below ground streamed through day chunks (DESIGN.md "Below ground in day chunks") ----------------------------------
+static_assert(mcf::kBelowMaxDepths == MCF_MAX_DEPTHS, "mcf_kernels.h and mcf.h agree on the depth count");
+// Tz at depth `depth` of ring slot `slot`: depth 0 is the slot's own variable, the others have a slab beside the ring
+mcf::RingView depth_view(const mcf_plan* p, int slot, int depth) {
+    if (depth == 0) return ring_view(p, slot, MCF_OUT_TZ);
+    mcf::RingView v{};
+    v.N = p->N; v.cpb = p->cpb;
+    v.tile_stride = p->tg_tile_stride; v.day_stride = mcf::ring_block_doubles(p->cpb);
+    v.base = p->d_tzx + ((int64_t)(depth - 1) * p->ring_slots + slot) * p->ntiles * p->tg_tile_stride;
+    return v;
+}
 // the state of a streamed plan as k_below_* see it; the chunk fields are the caller's
 mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
     mcf::BelowStreamArgs b{};
@@ -1272,6 +1292,16 @@ mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
     b.ddsum = p->d_ddsum; b.hsum = p->d_hsum; b.dmean = p->d_dmean; b.ybuf = p->d_ybuf; b.wrap = p->d_wrap; b.prev = p->d_prev;
     b.Tgp = p->d_Tgp; b.Tbp = p->d_Tbp;
     b.per_cell_pointm = p->af ? 1 : 0;
+    b.ndepths = std::max<int>(1, (int)p->depths.size());
+    b.depth[0] = p->opt.reqhgt;
+    for (size_t d = 0; d < p->depths.size(); ++d) b.depth[d] = p->depths[d];
+    b.reqhgt = b.depth[0];
+    if (p->d_tzx) {
+        b.tzx = depth_view(p, slot, 1);
+        b.tzx_stride = (int64_t)p->ring_slots * p->ntiles * p->tg_tile_stride;
+    }
+    b.ybufx = p->d_ybufx;
+    if (p->d_Tbp_depths) { b.Tbp = p->d_Tbp_depths; b.tbp_stride = p->tsteps; }
     return b;
 }
 
@@ -1384,6 +1414,7 @@ int mcf_plan_below_set_days(mcf_plan* p, const int32_t* days, int32_t n) {
         return fail(MCF_ERR_STATE, "mcf_plan_below_set_days needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
     if (p->af) return fail(MCF_ERR_STATE, "mcf_plan_below_set_days: a day subset needs vector forcing");
     if (p->below_ready) return fail(MCF_ERR_STATE, "mcf_plan_below_set_days comes before mcf_plan_below_prepare");
+    if (!p->depths.empty()) return fail(MCF_ERR_STATE, "mcf_plan_below_set_days: a day subset together with a depth list is not taken");
     int32_t pos0, npos;
     int rc = mcf_below_days_range(days, n, p->ndays, 0, 0, &pos0, &npos);
     if (rc) return rc;
@@ -1396,6 +1427,51 @@ int mcf_plan_below_set_days(mcf_plan* p, const int32_t* days, int32_t n) {
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->below_days.assign(days, days + n);
     HIP_TRY(hipMemcpy(p->d_below_days, p->below_days.data(), (size_t)n * 4, hipMemcpyHostToDevice));
+    return MCF_OK;
+}
+
+// what a depth list can be refused for without a plan or a device; `who`: the entry's name
+static int check_depths(const char* who, const double* depths, int32_t ndepths, const double* tbp, bool complete, bool af) {
+    const std::string w = std::string(who) + ": ";
+    if (!depths || ndepths < 1) return fail(MCF_ERR_ARG, w + "a null or empty depth list");
+    if (ndepths > MCF_MAX_DEPTHS)
+        return fail(MCF_ERR_ARG, w + std::to_string(ndepths) + " depths, at most MCF_MAX_DEPTHS = " + std::to_string(MCF_MAX_DEPTHS));
+    for (int d = 0; d < ndepths; ++d)
+        if (!(depths[d] < 0.0))
+            return fail(MCF_ERR_ARG, w + "depths[" + std::to_string(d) + "] is not below ground (every depth is < 0)");
+    if (af && !complete)
+        return fail(MCF_ERR_ARG, w + "array forcing with complete = 0 is not taken (per-cell Tbp for several depths)");
+    if (!complete && !tbp) return fail(MCF_ERR_ARG, w + "complete = 0 needs tbp, the point model's soil temperature at each depth");
+    return MCF_OK;
+}
+
+int mcf_plan_below_set_depths(mcf_plan* p, const double* depths, int32_t ndepths, const double* tbp) {
+    const char* who = "mcf_plan_below_set_depths";
+    const std::string w = std::string(who) + ": ";
+    if (!p) return fail(MCF_ERR_ARG, w + "null plan");
+    if (!p->bg_stream) return fail(MCF_ERR_STATE, w + "needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
+    if (p->below_ready) return fail(MCF_ERR_STATE, w + "comes before mcf_plan_below_prepare");
+    if (!p->below_days.empty()) return fail(MCF_ERR_STATE, w + "a depth list together with a day subset is not taken");
+    if (p->var_slot[MCF_OUT_TZ] < 0) return fail(MCF_ERR_STATE, w + "the plan was created without Tz");
+    if (!p->depths.empty()) return fail(MCF_ERR_STATE, w + "the plan has its depth list already");
+    if (p->d_sum_state) return fail(MCF_ERR_STATE, w + "comes before mcf_plan_summary_enable_below");
+    const bool complete = p->opt.complete != 0;
+    int rc = check_depths(who, depths, ndepths, tbp, complete, p->af);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    void* q = nullptr;
+    const int64_t extra = ndepths - 1, nd = std::max(p->ndays, 1);
+    if (extra > 0) {
+        if ((rc = dalloc(p, &q, extra * p->ring_slots * p->ntiles * p->tg_tile_stride * 8))) return rc;
+        p->d_tzx = (double*)q;
+        if (complete) {
+            if ((rc = dalloc(p, &q, extra * nd * p->N * 8))) return rc;
+            p->d_ybufx = (double*)q;
+        }
+    }
+    if (!complete && (rc = upload(p, tbp, (int64_t)ndepths * p->tsteps, &p->d_Tbp_depths, "tbp", false))) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->depths.assign(depths, depths + ndepths);
     return MCF_OK;
 }
 
@@ -1736,6 +1812,22 @@ static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_
         if (rc) return rc;
     }
     return MCF_OK;
+}
+
+int mcf_plan_fetch_depth_pitched(mcf_plan* p, int32_t slot, int32_t depth, int64_t step0, int64_t nsteps, double* host_dst,
+                                 int64_t row_pitch) {
+    if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->bg_stream || p->var_slot[MCF_OUT_TZ] < 0)
+        return fail(MCF_ERR_STATE, "mcf_plan_fetch_depth needs a streamed below-ground plan with Tz");
+    if (depth < 0 || depth >= std::max<int>(1, (int)p->depths.size()))
+        return fail(MCF_ERR_ARG, "mcf_plan_fetch_depth: depth " + std::to_string(depth) + " is outside the plan's list");
+    if (row_pitch == 0) row_pitch = p->rows;
+    if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
+    if (const int rc = check_slot_range(p, slot, MCF_OUT_TZ, step0, nsteps)) return rc;
+    return fetch_view(p, depth_view(p, slot, depth), true, step0, nsteps, host_dst, row_pitch);
+}
+int mcf_plan_fetch_depth(mcf_plan* p, int32_t slot, int32_t depth, int64_t step0, int64_t nsteps, double* host_dst) {
+    return mcf_plan_fetch_depth_pitched(p, slot, depth, step0, nsteps, host_dst, 0);
 }
 
 int mcf_plan_fetch_cells(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps, const int64_t* cells,
@@ -2251,13 +2343,10 @@ static int check_room(int64_t need, const char* what) {
     return MCF_OK;
 }
 
-int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
-    if (!p || !spec) return fail(MCF_ERR_ARG, "null argument");
-    if (p->bg_stream) return fail(MCF_ERR_ARG, "period summaries are not available on a streamed plan");
-    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
-    if (p->d_sum_state) return fail(MCF_ERR_STATE, "period summaries are already enabled on this plan");
-    int rc = check_summary_spec(spec, p->ndays, p->var_slot);
-    if (rc) return rc;
+// the sink switched on for a checked spec; extra_places: places of the state behind the selected variables' (Tz at depths
+// 1 .. D - 1 of a below-ground plan)
+static int summary_enable_checked(mcf_plan* p, const mcf_summary_spec* spec, int extra_places) {
+    int rc;
     HIP_TRY(hipSetDevice(p->device));
     // state rows: the sum's (it carries the NA rule), then one per selected statistic that needs one
     int nrows = 1, row[MCF_NSTAT];
@@ -2267,8 +2356,9 @@ int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
         if (row[k] > 0 && k == MCF_STAT_MIN) codes |= 1u << (4 * row[k]);
         if (row[k] > 0 && k == MCF_STAT_MAX) codes |= 2u << (4 * row[k]);
     }
-    int nsel = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) nsel += spec->var[v] ? 1 : 0;
+    int nmain = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nmain += spec->var[v] ? 1 : 0;
+    const int nsel = nmain + extra_places;
     const int64_t nd = std::max(p->ndays, 1), np = spec->nperiods;
     const int64_t state_bytes = (int64_t)nsel * np * nrows * p->N * 8, plane_bytes = np * p->N * 8;
     if ((rc = check_room(state_bytes + plane_bytes + (3 * nd + np) * 4, "the summary state"))) return rc;
@@ -2294,7 +2384,7 @@ int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
     if ((rc = dalloc(p, &q, plane_bytes))) return rc;
     p->d_sum_plane = (double*)q;
     if ((rc = dalloc(p, &q, state_bytes))) return rc;
-    p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_nsel = nsel; p->sum_init_codes = codes;
+    p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_nsel = nsel; p->sum_nmain = nmain; p->sum_init_codes = codes;
     for (int k = 0; k < MCF_NSTAT; ++k) p->sum_row[k] = row[k];
     int place = 0;
     for (int v = 0; v < MCF_NOUT; ++v) {
@@ -2304,6 +2394,39 @@ int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
     p->sum_pod = std::move(pod);
     p->d_sum_state = (double*)q;
     return mcf_plan_summary_reset(p);
+}
+
+int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
+    if (!p || !spec) return fail(MCF_ERR_ARG, "null argument");
+    if (p->bg_stream) return fail(MCF_ERR_ARG, "period summaries are not available on a streamed plan");
+    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
+    if (p->d_sum_state) return fail(MCF_ERR_STATE, "period summaries are already enabled on this plan");
+    int rc = check_summary_spec(spec, p->ndays, p->var_slot);
+    if (rc) return rc;
+    return summary_enable_checked(p, spec, 0);
+}
+
+// below ground only Tz and soilm exist (what .runmodel1Cpp keeps there)
+static int check_summary_below_vars(const char* who, const mcf_summary_spec* s) {
+    for (int v = 0; s && v < MCF_NOUT; ++v)
+        if (s->var[v] && v != MCF_OUT_TZ && v != MCF_OUT_SOILM)
+            return fail(MCF_ERR_ARG, std::string(who) + ": below ground Tz and soilm can be summarised, nothing else");
+    return MCF_OK;
+}
+
+int mcf_plan_summary_enable_below(mcf_plan* p, const mcf_summary_spec* spec) {
+    const char* who = "mcf_plan_summary_enable_below";
+    if (!p || !spec) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
+    if (!p->bg_stream || !p->tiled)
+        return fail(MCF_ERR_STATE, std::string(who) + " needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
+    if (p->d_sum_state) return fail(MCF_ERR_STATE, "period summaries are already enabled on this plan");
+    int rc = check_summary_below_vars(who, spec);
+    if (rc) return rc;
+    if ((rc = check_summary_spec(spec, p->ndays, p->var_slot))) return rc;
+    const int D = std::max<int>(1, (int)p->depths.size());
+    if ((rc = summary_enable_checked(p, spec, spec->var[MCF_OUT_TZ] ? D - 1 : 0))) return rc;
+    p->sum_below = true;
+    return MCF_OK;
 }
 
 int mcf_plan_summary_reset(mcf_plan* p) {
@@ -2332,7 +2455,7 @@ int mcf_plan_summary_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, in
     a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
     a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
     a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
-    a.nsel = p->sum_nsel;
+    a.nsel = p->sum_nmain;
     for (int v = 0; v < MCF_NOUT; ++v)
         if (p->sum_sel1[v]) {
             a.slab[p->sum_sel1[v] - 1] = p->var_slot[v];
@@ -2344,6 +2467,14 @@ int mcf_plan_summary_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, in
     a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
     a.state = p->d_sum_state;
     mcf::launch_summary_acc(a, p->stream);
+    // below ground: Tz at depths 1 .. D - 1, each one variable of its own slab beside the ring
+    for (int d = 1; d <= p->sum_nsel - p->sum_nmain; ++d) {
+        const mcf::RingView v = depth_view(p, slot, d);
+        a.ring = v.base; a.tile_stride = v.tile_stride; a.day_stride = v.day_stride; a.var_stride = 0;
+        a.nsel = 1; a.slab[0] = 0; a.threshold[0] = p->sum_thr[MCF_OUT_TZ];
+        a.state = p->d_sum_state + (int64_t)(p->sum_nmain + d - 1) * p->sum_nperiods * p->sum_nrows * p->N;
+        mcf::launch_summary_acc(a, p->stream);
+    }
     HIP_TRY(hipGetLastError());
     for (int d = day0; d < day0 + ndays; ++d)
         if (p->sum_pod[(size_t)d] >= 0) p->sum_days[(size_t)p->sum_pod[(size_t)d]] += 1;
@@ -2352,18 +2483,23 @@ int mcf_plan_summary_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, in
 }
 
 // one statistic plane [rows, cols, nperiods] into the caller's array (row_pitch > rows: a row block's rows of taller planes)
-static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch) {
+static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch, int32_t depth = 0) {
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
     if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
     if (var < 0 || var >= MCF_NOUT || stat < 0 || stat >= MCF_NSTAT) return fail(MCF_ERR_ARG, "bad variable / statistic");
     if (!p->sum_sel1[var]) return fail(MCF_ERR_ARG, "variable was not selected in mcf_plan_summary_enable");
     if (p->sum_row[stat] < 0) return fail(MCF_ERR_ARG, "statistic was not selected in mcf_plan_summary_enable");
+    // the place in the state: the variable's own, or (below ground) that of Tz at a depth behind the first
+    if (depth < 0 || depth > (var == MCF_OUT_TZ ? p->sum_nsel - p->sum_nmain : 0))
+        return fail(MCF_ERR_ARG, var == MCF_OUT_TZ ? "mcf_plan_summary_fetch_depth: depth " + std::to_string(depth) + " is outside the plan's list"
+                                                   : std::string("mcf_plan_summary_fetch_depth: only Tz is kept per depth (depth 0 for soilm)"));
+    const int place = depth == 0 ? p->sum_sel1[var] - 1 : p->sum_nmain + depth - 1;
     if (row_pitch == 0) row_pitch = p->rows;
     if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipMemcpyAsync(p->d_sum_days, p->sum_days.data(), (size_t)p->sum_nperiods * 4, hipMemcpyHostToDevice, p->stream));
     mcf::SummaryFinArgs f{};
-    f.state = p->d_sum_state + (int64_t)(p->sum_sel1[var] - 1) * p->sum_nperiods * p->sum_nrows * p->N;
+    f.state = p->d_sum_state + (int64_t)place * p->sum_nperiods * p->sum_nrows * p->N;
     f.N = p->N; f.nperiods = p->sum_nperiods; f.nrows = p->sum_nrows;
     f.stat = stat; f.row = p->sum_row[stat];
     f.days = p->d_sum_days; f.out = p->d_sum_plane;
@@ -2376,6 +2512,10 @@ static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double*
 }
 int mcf_plan_summary_fetch(mcf_plan* p, int32_t var, int32_t stat, double* host_dst) {
     return summary_fetch_pitched(p, var, stat, host_dst, 0);
+}
+int mcf_plan_summary_fetch_depth(mcf_plan* p, int32_t depth, int32_t var, int32_t stat, double* host_dst) {
+    if (p && !p->sum_below) return fail(MCF_ERR_STATE, "mcf_plan_summary_fetch_depth: the plan has no below-ground summary (mcf_plan_summary_enable_below)");
+    return summary_fetch_pitched(p, var, stat, host_dst, 0, depth);
 }
 
 int mcf_plan_summary_days(mcf_plan* p, int32_t* days) {
@@ -2470,6 +2610,111 @@ static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, con
 int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_summary_spec* spec, int32_t chunk_days,
                          mcf_summary_out* out) {
     return run_summary(in, opt, spec, chunk_days, out);
+}
+
+// ---- below ground at several depths from one solve (include/mcf.h mcf_runmicro_depths) ----------------------
+// The chunk of a streamed run from free device memory, as run_oneshot's streamed branch sizes it, with the D - 1 depth slabs
+// per day and their rows of circular means counted.
+static int depths_chunk_days(const mcf_grid_inputs* in, const mcf_options* opt, int nvars, int D, int ndays, bool tail, int* chunk) {
+    size_t fr = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    const int64_t N = in->rows * in->cols;
+    const double per_day = (double)N * 24 * 8 * (nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1));
+    const double budget = 0.6 * (double)fr - (double)N * 8 * 200 - (double)N * 8 * ((1.0 + D) * ndays + 2 * mcf::kBelowWin + 2) -
+                          (tail ? per_day : 0.0);
+    *chunk = std::min((int)std::max(1.0, std::min((double)std::max(ndays, 1), budget / std::max(per_day, 1.0))), 64);
+    return MCF_OK;
+}
+
+// both one-call entries: `out` (every step of every depth) or `spec` + `sout` (the period summaries)
+static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
+                      const double* tbp, mcf_depth_outputs* out, const mcf_summary_spec* spec, int32_t chunk_days,
+                      mcf_depth_summary_out* sout) {
+    const std::string w = std::string(who) + ": ";
+    if (!in || !opt_in || (!out && !sout) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
+    int rc = check_depths(who, depths, D, tbp, opt_in->complete != 0, in->array_forcing != 0);
+    if (rc) return rc;
+    mcf_options opt = *opt_in;
+    opt.reqhgt = depths[0];
+    if ((rc = check_inputs(in, &opt))) return rc;
+    const int64_t T = in->tsteps;
+    const int ndays = (int)(T / 24);
+    if (ndays < 1) return fail(MCF_ERR_ARG, w + "the series is shorter than a day");
+    if (chunk_days < 0) return fail(MCF_ERR_ARG, w + "negative chunk_days");
+    for (int v = 0; v < MCF_NOUT; ++v) opt.out[v] = 0;
+    if (out) {
+        for (int d = 0; d < D; ++d)
+            if (!out->tz[d]) return fail(MCF_ERR_ARG, w + "tz[" + std::to_string(d) + "] is a null buffer");
+        opt.out[MCF_OUT_TZ] = 1;
+        opt.out[MCF_OUT_SOILM] = out->soilm ? 1 : 0;
+    } else {
+        if ((rc = check_summary_below_vars(who, spec))) return rc;
+        if ((rc = check_summary_spec(spec, ndays, nullptr))) return rc;
+        for (int k = 0; k < MCF_NSTAT; ++k) {
+            if (!spec->stat[k]) continue;
+            for (int d = 0; spec->var[MCF_OUT_TZ] && d < D; ++d)
+                if (!sout->tz[d][k]) return fail(MCF_ERR_ARG, w + "a selected (depth, statistic) has a null buffer");
+            if (spec->var[MCF_OUT_SOILM] && !sout->soilm[k]) return fail(MCF_ERR_ARG, w + "a selected statistic of soilm has a null buffer");
+        }
+        // (the depth list lives on a plan with Tz; soilm alone is summarised beside it)
+        opt.out[MCF_OUT_TZ] = 1;
+        opt.out[MCF_OUT_SOILM] = spec->var[MCF_OUT_SOILM] ? 1 : 0;
+    }
+    if ((rc = ensure_device(opt.device))) return rc;
+    const int nvars = 1 + opt.out[MCF_OUT_SOILM];
+    const bool tail = T > (int64_t)ndays * 24;      // the steps behind the last whole day: one day more per slot
+    int chunk = out ? opt.days_per_chunk : chunk_days;
+    if (chunk <= 0 && (rc = depths_chunk_days(in, &opt, nvars, D, ndays, tail, &chunk))) return rc;
+    chunk = std::max(1, std::min(chunk, ndays));
+    mcf_plan* p = nullptr;
+    if ((rc = plan_create(in, &opt, chunk + (tail ? 1 : 0), 1, true, &p, nullptr))) return rc;
+    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
+    if ((rc = mcf_plan_below_prepare(p, in))) return rc;
+    if (sout && (rc = mcf_plan_summary_enable_below(p, spec))) return rc;
+    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows, HS = pitch * in->cols;
+    for (int d0 = 0; d0 < ndays; d0 += chunk) {
+        const int nd = std::min(chunk, ndays - d0);
+        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
+        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+        if (sout) {
+            if ((rc = mcf_plan_summary_accumulate(p, 0, 0, d0, nd))) return rc;
+            continue;
+        }
+        // ... the last chunk with the steps it left behind its days
+        const int64_t steps = (int64_t)nd * 24 + (d0 + nd == ndays ? T - (int64_t)ndays * 24 : 0);
+        for (int d = 0; d < D; ++d)
+            if ((rc = mcf_plan_fetch_depth_pitched(p, 0, d, 0, steps, out->tz[d] + HS * (int64_t)d0 * 24, pitch))) return rc;
+        if (out->soilm && (rc = mcf_plan_fetch_pitched(p, 0, MCF_OUT_SOILM, 0, (int64_t)nd * 24, out->soilm + HS * (int64_t)d0 * 24, pitch)))
+            return rc;
+    }
+    if (sout) {
+        for (int k = 0; k < MCF_NSTAT; ++k) {
+            if (!spec->stat[k]) continue;
+            for (int d = 0; spec->var[MCF_OUT_TZ] && d < D; ++d)
+                if ((rc = summary_fetch_pitched(p, MCF_OUT_TZ, k, sout->tz[d][k], 0, d))) return rc;
+            if (spec->var[MCF_OUT_SOILM] && (rc = summary_fetch_pitched(p, MCF_OUT_SOILM, k, sout->soilm[k], 0))) return rc;
+        }
+        if (sout->days && (rc = mcf_plan_summary_days(p, sout->days))) return rc;
+        return mcf_plan_sync(p);
+    }
+    if (out->soilm) {      // steps past the last whole day are never computed by the reference and stay NA (cpp:2116)
+        const double na = mcf::na_real_host();
+        for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
+            for (int64_t j = 0; j < in->cols; ++j)
+                for (int64_t i = 0; i < in->rows; ++i) out->soilm[i + pitch * j + HS * k] = na;
+    }
+    return mcf_plan_sync(p);
+}
+int mcf_runmicro_depths(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths, const double* tbp,
+                        mcf_depth_outputs* out) {
+    if (!out) return fail(MCF_ERR_ARG, "mcf_runmicro_depths: null argument");
+    return run_depths("mcf_runmicro_depths", in, opt, depths, ndepths, tbp, out, nullptr, 0, nullptr);
+}
+int mcf_runmicro_depths_summary(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths,
+                                const double* tbp, const mcf_summary_spec* spec, int32_t chunk_days, mcf_depth_summary_out* out) {
+    if (!out || !spec) return fail(MCF_ERR_ARG, "mcf_runmicro_depths_summary: null argument");
+    return run_depths("mcf_runmicro_depths_summary", in, opt, depths, ndepths, tbp, nullptr, spec, chunk_days, out);
 }
 
 int64_t mcf_plan_valid_cells(const mcf_plan* p) { return p ? p->valid_cells : 0; }

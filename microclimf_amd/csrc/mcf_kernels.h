@@ -184,6 +184,7 @@ struct BelowArgs {
 //   wrap  [47]     complete: Tg of the series' last 47 steps (step tsteps - 47 + j; 0 past the last whole day)
 //   prev  [47]     complete, sweep 2: Tg of the 47 steps in front of the chunk being transformed
 constexpr int kBelowWin = 47;
+constexpr int kBelowMaxDepths = 8;      // include/mcf.h MCF_MAX_DEPTHS
 struct BelowStreamArgs {
     int64_t N;
     int32_t tsteps, ndays, complete, hiy;
@@ -209,6 +210,17 @@ struct BelowStreamArgs {
     // (cal0: the calendar day at the views' day 0); the point model's series are read at the calendar day's own steps.
     const int32_t* days;
     int32_t cal0;
+    // the depths of the launch (mcf_plan_below_set_depths; without a list: one, reqhgt).  Everything above is shared by them;
+    // per depth d there is depth[d], a Tz slab (slab 0: tz; slab d > 0: the view tzx moved on by (d - 1) * tzx_stride — a
+    // buffer beside the ring, [depth][slot][tile][day][block]), a row of circular means (row 0: ybuf; row d > 0: ybufx +
+    // (d - 1) * ndays * N) and, complete == 0 with vector forcing, the point model's series Tbp + d * tbp_stride.  (Last:
+    // k_below_acc / k_below_carry read the fields above where they were.)
+    int32_t ndepths;
+    double depth[kBelowMaxDepths];
+    RingView tzx;
+    int64_t tzx_stride;
+    double* ybufx;
+    int64_t tbp_stride;
 };
 // step k of the chunk, in the order of the series Tbelowgroundv sees -> step of the chunk's tg / tz views
 __host__ __device__ inline int below_view_step(const BelowStreamArgs& a, int k) {

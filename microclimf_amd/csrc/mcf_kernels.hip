@@ -1374,8 +1374,18 @@ __global__ __launch_bounds__(256) void k_below_acc(BelowStreamArgs a) {
     below_shift(a.wrap, c, N, a.ndays_chunk * 24, [&](int k) { return a.tg.at(c, below_view_step(a, k)); });
 }
 
-// after sweep 1 (complete = 1): the steps past the last whole day (Tg 0 there) into hsum and wrap; the circular n/24-day means
-// y (cpp:611-617) of the cells that take the daily path
+// depth d of a launch (BelowStreamArgs): the place of (cell c, step k of the views) in its Tz slab — slab 0 is the slot's, the
+// others lie tzx_stride apart in a buffer of their own (tzx: depth 1's) —, and its row of circular means
+__device__ __forceinline__ double* below_tz(const BelowStreamArgs& a, int d, int64_t c, int k) {
+    if (d == 0) return const_cast<double*>(a.tz.base) + a.tz.index(c, k);
+    return const_cast<double*>(a.tzx.base) + (int64_t)(d - 1) * a.tzx_stride + a.tzx.index(c, k);
+}
+__device__ __forceinline__ double* below_y(const BelowStreamArgs& a, int d) {
+    return d == 0 ? a.ybuf : a.ybufx + (int64_t)(d - 1) * a.ndays * a.N;
+}
+
+// after sweep 1 (complete = 1): the steps past the last whole day (Tg 0 there) into hsum and wrap; per depth the circular
+// n/24-day means y (cpp:611-617) of the cells that take the daily path at that depth
 __global__ __launch_bounds__(256) void k_below_finish(BelowStreamArgs a) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
     if (c >= N) return;
@@ -1386,32 +1396,42 @@ __global__ __launch_bounds__(256) void k_below_finish(BelowStreamArgs a) {
     if (t > 0) below_shift(a.wrap, c, N, t, [](int) { return 0.0; });
     if (isnan(a.hgt[c])) return;
     const double meanD = a.ddsum[c] / (double)m;                           // cpp:2313
-    const double nb = -118.35 * a.reqhgt / meanD;
-    const int n = (int)round(nb);
-    if (!(n < m && n > 48)) return;
-    const int n2 = n / 24;
     const double* d = a.dmean + c;
-    for (int i = 0; i < nd; ++i) {
-        double s = 0.0;
-        for (int j = 0; j < n2; ++j) s += d[N * ((i - j + nd) % nd)];
-        a.ybuf[c + N * i] = s / n2;
+    for (int dp = 0; dp < a.ndepths; ++dp) {
+        const double nb = -118.35 * a.depth[dp] / meanD;
+        const int n = (int)round(nb);
+        if (!(n < m && n > 48)) continue;
+        const int n2 = n / 24;
+        double* y = below_y(a, dp) + c;
+        for (int i = 0; i < nd; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < n2; ++j) s += d[N * ((i - j + nd) % nd)];
+            y[N * i] = s / n2;
+        }
     }
 }
 
 // Tz of the chunk's days (blockIdx.y < ndays_chunk) and, with a.tail, of the steps behind the last whole day
-// (blockIdx.y == ndays_chunk) into the slot; one lane per cell-day, k_belowground's expressions
+// (blockIdx.y == ndays_chunk) into the slot, at every depth of the launch; one lane per cell-day, k_belowground's expressions.
+// What does not depend on the depth is read once and held in registers, every index a constant after unrolling:
+//   complete = 1  where some depth takes the hourly window, Tg of the 47 steps in front of the day and of the day's hours, as
+//                 a window v that slides along the day (v[j] = Tg j steps before the hour in hand); each hour serves all depths
+//   complete = 0  the day's 24 Tg values and the day statistics of Tg and of the point model's Tg
+// COMPLETE = a.complete != 0: one body, two instantiations, so that the incomplete form does not carry the window's registers.
+template <bool COMPLETE>
 __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
     const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x, N = a.N;
     if (c >= N) return;
     const int dl = blockIdx.y;
-    const int m = a.tsteps, nd = a.ndays, L = a.ndays_chunk * 24;
+    const int m = a.tsteps, nd = a.ndays, L = a.ndays_chunk * 24, D = a.ndepths;
     const int hours = dl < a.ndays_chunk ? 24 : m - nd * 24;
     const int k0 = dl * 24;                         // the day's first step in the chunk
     const int64_t cs = (int64_t)a.day0 * 24;        // the chunk's first step in the series
-    double* const zb = const_cast<double*>(a.tz.base);
-    auto put = [&](int k, double v) { zb[a.tz.index(c, below_view_step(a, k))] = v; };
+    const int v0 = below_view_step(a, k0);          // ... and in the views: the day's steps are one day of a slab
+    auto put = [&](int d, int h, double v) { *below_tz(a, d, c, v0 + h) = v; };
     if (isnan(a.hgt[c])) {
-        for (int h = 0; h < hours; ++h) put(k0 + h, na_real());
+        for (int d = 0; d < D; ++d)
+            for (int h = 0; h < hours; ++h) put(d, h, na_real());
         return;
     }
     // Tg at step k of the chunk: k < 0 the steps in front of it (prev; in front of the series' start: its end, wrap),
@@ -1424,19 +1444,39 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
         return a.wrap[c + N * (ka + kBelowWin)];
     };
     const double meanD = a.ddsum[c] / (double)m;                           // cpp:2313
-    const double nb = -118.35 * a.reqhgt / meanD;
-    const int n = (int)round(nb);
-    if (a.complete) {
-        if (n < m) {
-            if (n <= 48) {                                                   // cpp:600-602
-                for (int h = 0; h < hours; ++h) {
-                    const int i = k0 + h;
+    if (COMPLETE) {
+        bool window = false;
+        for (int d = 0; d < D; ++d) {
+            const int n = (int)round(-118.35 * a.depth[d] / meanD);
+            window = window || (n < m && n <= 48);
+        }
+        if (window) {                                                        // cpp:600-602
+            double v[kBelowWin + 1] = {};
+#pragma nounroll
+            for (int k = k0 - kBelowWin; k < k0 + hours; ++k) {
+#pragma unroll
+                for (int j = kBelowWin; j > 0; --j) v[j] = v[j - 1];
+                v[0] = x(k);
+                if (k < k0) continue;            // (still filling the window)
+#pragma nounroll
+                for (int d = 0; d < D; ++d) {
+                    const double nb = -118.35 * a.depth[d] / meanD;
+                    const int n = (int)round(nb);
+                    if (!(n < m && n <= 48)) continue;
                     double s = 0.0;
-                    for (int j = 0; j < n; ++j) s += x(i - j);
-                    put(i, s / n);
+#pragma unroll
+                    for (int j = 0; j <= kBelowWin; ++j)
+                        if (j < n) s += v[j];
+                    put(d, k - k0, s / n);
                 }
-            } else {                                                         // cpp:618-625
-                const double* y = a.ybuf + c;
+            }
+        }
+        for (int d = 0; d < D; ++d) {
+            const double nb = -118.35 * a.depth[d] / meanD;
+            const int n = (int)round(nb);
+            if (n < m) {
+                if (n <= 48) continue;                                       // (the window above)
+                const double* y = below_y(a, d) + c;                         // cpp:618-625
                 for (int h = 0; h < hours; ++h) {
                     const int64_t i = cs + k0 + h;
                     double s = 0.0;
@@ -1444,65 +1484,113 @@ __global__ __launch_bounds__(256) void k_below_chunk(BelowStreamArgs a) {
                         int q = (int)((i - j + m) % m);
                         s += (q < nd * 24) ? y[N * (q / 24)] : 0.0;
                     }
-                    put(k0 + h, s / 24);
+                    put(d, h, s / 24);
                 }
+            } else {                                                         // cpp:1487-1492
+                double meanT = a.hsum[c] / m;
+                for (int h = 0; h < hours; ++h) put(d, h, meanT);
             }
-        } else {                                                             // cpp:1487-1492
-            double meanT = a.hsum[c] / m;
-            for (int h = 0; h < hours; ++h) put(k0 + h, meanT);
         }
         return;
     }
     // incomplete time sequence, cpp:1495-1536
+    if (dl == a.ndays_chunk) {           // past the last whole day: see k_belowground
+        for (int d = 0; d < D; ++d) {
+            const double nb = -118.35 * a.depth[d] / meanD;
+            const bool blend_day = (nb > 1.0 && nb <= 24.0);
+            const bool blend_year = nb > 24.0;
+            for (int h = 0; h < hours; ++h)
+                put(d, h, (!blend_day && !blend_year) ? 0.0
+                          : (blend_year && !(nb < a.hiy)) ? a.mat : __longlong_as_double(0x7FF8000000000000LL));
+        }
+        return;
+    }
     const bool pc = a.per_cell_pointm != 0;
     auto ser = [&](const double* p, int64_t i) { return pc ? p[c + N * (i - cs)] : p[i]; };      // i: step of the series
-    const bool blend_day = (nb > 1.0 && nb <= 24.0);
-    const bool blend_year = nb > 24.0;
-    if (dl == a.ndays_chunk) {       // past the last whole day: see k_belowground
-        for (int h = 0; h < hours; ++h)
-            put(k0 + h, (!blend_day && !blend_year) ? 0.0
-                        : (blend_year && !(nb < a.hiy)) ? a.mat : __longlong_as_double(0x7FF8000000000000LL));
-        return;
-    }
-    if (!blend_day && !blend_year) {
-        for (int h = 0; h < 24; ++h) put(k0 + h, x(k0 + h));
-        return;
-    }
     // the point model's series at the day's own place (a day subset: its calendar day)
     const int64_t i0 = a.days ? (int64_t)a.days[a.day0 + dl] * 24 : cs + k0;
-    double gmx = x(k0), gmn = gmx, gsum = 0.0;
-    double pmx = ser(a.Tgp, i0), pmn = pmx, psum = 0.0, bsum = 0.0;
-    for (int j = 0; j < 24; ++j) {
-        double gv = x(k0 + j), pv = ser(a.Tgp, i0 + j);
-        if (j > 0) {
-            gmx = fmax(gmx, gv); gmn = fmin(gmn, gv);
-            pmx = fmax(pmx, pv); pmn = fmin(pmn, pv);
-        }
-        gsum += gv; psum += pv;
-        bsum += ser(a.Tbp, i0 + j);
-    }
-    double gme = gsum / 24, pme = psum / 24, Tbpd = bsum / 24;
-    double rat = (gmx - gmn) / (pmx - pmn);
-    double dif = gme - pme;
-    for (int j = 0; j < 24; ++j) {
-        const int64_t i = i0 + j;
-        double z = x(k0 + j);
-        double Tzd = rat * (ser(a.Tbp, i) - Tbpd) + Tbpd + dif;
-        if (blend_day) {
-            double w1 = 1.0 / nb, w2 = nb / 24.0;
-            double wgt = w1 / (w1 + w2);
-            z = wgt * x(k0 + j) + (1 - wgt) * Tzd;
-        }
-        if (blend_year) {
-            if (nb < a.hiy) {
-                double w1 = 24.0 / nb, w2 = nb / a.hiy;
-                double wgt = w1 / (w1 + w2);
-                z = wgt * Tzd + (1 - wgt) * a.mat;
-            } else {
-                z = a.mat;
+    // (g is walked four hours at a time, g[0 .. 3], and then turned by four places: the loops stay rolled and every index a
+    // constant; six turns bring it back)
+    double g[24] = {};
+    auto turn = [&](double t0, double t1, double t2, double t3) {
+#pragma unroll
+        for (int q = 0; q < 20; ++q) g[q] = g[q + 4];
+        g[20] = t0; g[21] = t1; g[22] = t2; g[23] = t3;
+    };
+#pragma nounroll
+    for (int j = 0; j < 24; j += 4) turn(x(k0 + j), x(k0 + j + 1), x(k0 + j + 2), x(k0 + j + 3));
+    // the day statistics no depth changes (of the cells where some depth blends)
+    bool blend = false;
+    for (int d = 0; d < D; ++d) blend = blend || -118.35 * a.depth[d] / meanD > 1.0;
+    double rat = 0.0, dif = 0.0;
+    if (blend) {
+        double gmx = g[0], gmn = gmx, gsum = 0.0;
+        double pmx = ser(a.Tgp, i0), pmn = pmx, psum = 0.0;
+#pragma nounroll
+        for (int jj = 0; jj < 24; jj += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = jj + u;
+                double gv = g[u], pv = ser(a.Tgp, i0 + j);
+                if (j > 0) {
+                    gmx = fmax(gmx, gv); gmn = fmin(gmn, gv);
+                    pmx = fmax(pmx, pv); pmn = fmin(pmn, pv);
+                }
+                gsum += gv; psum += pv;
             }
+            turn(g[0], g[1], g[2], g[3]);
         }
-        put(k0 + j, z);
+        double gme = gsum / 24, pme = psum / 24;
+        rat = (gmx - gmn) / (pmx - pmn);
+        dif = gme - pme;
+    }
+#pragma nounroll
+    for (int d = 0; d < D; ++d) {
+        const double nb = -118.35 * a.depth[d] / meanD;
+        const bool blend_day = (nb > 1.0 && nb <= 24.0);
+        const bool blend_year = nb > 24.0;
+        if (!blend_day && !blend_year) {
+#pragma nounroll
+            for (int hh = 0; hh < 24; hh += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) put(d, hh + u, g[u]);
+                turn(g[0], g[1], g[2], g[3]);
+            }
+            continue;
+        }
+        const double* Tbp = a.Tbp + (int64_t)d * a.tbp_stride;
+        double bsum = 0.0;
+        for (int j = 0; j < 24; ++j) bsum += ser(Tbp, i0 + j);
+        double Tbpd = bsum / 24;
+#pragma nounroll
+        for (int jj = 0; jj < 24; jj += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = jj + u;
+                const int64_t i = i0 + j;
+                const double gj = g[u];
+                double z = gj;
+                double Tzd = rat * (ser(Tbp, i) - Tbpd) + Tbpd + dif;
+                if (blend_day) {
+                    double w1 = 1.0 / nb, w2 = nb / 24.0;
+                    double wgt = w1 / (w1 + w2);
+                    // wgt * Tg + (1 - wgt) * Tzd as k_belowground's is contracted: the first product rounded, the second fused
+                    // into the sum (with Tg in a register the compiler would fuse the first instead)
+                    z = fma(1 - wgt, Tzd, wgt * gj);
+                }
+                if (blend_year) {
+                    if (nb < a.hiy) {
+                        double w1 = 24.0 / nb, w2 = nb / a.hiy;
+                        double wgt = w1 / (w1 + w2);
+                        z = wgt * Tzd + (1 - wgt) * a.mat;
+                    } else {
+                        z = a.mat;
+                    }
+                }
+                put(d, j, z);
+            }
+            turn(g[0], g[1], g[2], g[3]);
+        }
     }
 }
 // behind k_below_chunk (complete = 1): prev <- the 47 steps in front of the next chunk
@@ -1990,7 +2078,9 @@ void launch_below_finish(const BelowStreamArgs& a, hipStream_t s) {
 void launch_below_chunk(const BelowStreamArgs& a, hipStream_t s) {
     const int days = a.ndays_chunk + (a.tail ? 1 : 0);
     if (a.N <= 0 || days <= 0) return;
-    hipLaunchKernelGGL(k_below_chunk, dim3((unsigned)((a.N + 255) / 256), (unsigned)days), dim3(256), 0, s, a);
+    const dim3 grid((unsigned)((a.N + 255) / 256), (unsigned)days);
+    if (a.complete) hipLaunchKernelGGL(k_below_chunk<true>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_below_chunk<false>, grid, dim3(256), 0, s, a);
     if (a.complete && a.ndays_chunk > 0)
         hipLaunchKernelGGL(k_below_carry, dim3((unsigned)((a.N + 255) / 256)), dim3(256), 0, s, a);
 }

@@ -467,7 +467,7 @@ def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, d
     as runmicro_array).  reqhgt == 0 masks the variables as runmicro does; reqhgt < 0 is not available.
     -> {variable: {statistic: [rows, cols, nperiods]}, "periods": labels, "days": counted days per period}"""
     if reqhgt < 0:
-        raise ValueError("period summaries need reqhgt >= 0")
+        raise ValueError("period summaries need reqhgt >= 0 (below ground: runmicro_depths_summary)")
     names = (vars,) if isinstance(vars, str) else tuple(vars)
     out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
     if sum(out) != len(set(names)):
@@ -498,6 +498,52 @@ def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, d
     tab, labels = summary_periods(a["obstime"], periods)
     res = api.runmicro_summary(**a, periods=tab, nperiods=len(labels), vars=kept, stats=stats, thresholds=thresholds,
                                chunk_days=chunk_days, device=device, **extra)
+    res["periods"] = labels
+    return res
+
+
+# ---- below ground at several depths from one solve ---------------------------------------------------------------------------------
+def _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, ter, device):
+    """runmicro1Cpp's arguments at depths[0] with `depths` in place of reqhgt, and the point model's soil temperature at every
+    depth: below ground the solver's work does not depend on the depth, only the tail of Tbelowgroundv does"""
+    depths = [float(d) for d in np.atleast_1d(np.asarray(depths, dtype=np.float64))]
+    if not depths or not all(d < 0 for d in depths):
+        raise ValueError("depths: one or more heights below ground (each < 0)")
+    tbp = np.stack([soilbelowT(micropoint["dfo"], d) for d in depths])
+    a = prepare_grid_inputs(dict(micropoint, Tbz=tbp[0]), depths[0], vegp, soilc, dtm, pai_a=pai_a, out=(1, 0, 0, 1, 0, 0, 0, 0, 0, 0),
+                            device=device, **ter)
+    a["tfact"] = float(tfact)
+    a.pop("out")
+    a.pop("reqhgt")
+    return a, depths, tbp
+
+
+def runmicro_depths(micropoint: Mapping, depths, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None, tfact: float = 1.5,
+                    slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0, days_per_chunk: int = 0) -> dict:
+    """`runmicro()` at several depths below ground from ONE run of the solver (include/mcf.h mcf_runmicro_depths): a soil
+    temperature profile costs one run, not one per depth.  `depths`: each < 0, any order, at most api._abi.MAX_DEPTHS.  The
+    point model's soil temperature at each depth comes from `.soilbelowT` on the micropoint.
+    -> {"Tz": [one [rows, cols, steps] array per depth], "soilm": [rows, cols, steps], "depths": depths}, each array with
+    the bits of runmicro(micropoint, depth, ...) on a micropoint of that depth."""
+    a, depths, tbp = _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device)
+    return api.runmicro_depths(**a, depths=depths, tbp=tbp, device=device, days_per_chunk=days_per_chunk)
+
+
+def runmicro_depths_summary(micropoint: Mapping, depths, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
+                            vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None, pai_a=None,
+                            tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
+                            chunk_days: int = 0) -> dict:
+    """runmicro_depths reduced over time on the device, as runmicro_summary reduces runmicro: monthly (...) soil-temperature
+    maps at several depths without a cells x steps array anywhere.  `vars` among "Tz" and "soilm".
+    -> {"Tz": [per depth {statistic: [rows, cols, nperiods]}], "soilm": {statistic: ...} (if selected), "periods", "days",
+    "depths"}"""
+    names = (vars,) if isinstance(vars, str) else tuple(vars)
+    if not names or any(n not in ("Tz", "soilm") for n in names):
+        raise ValueError('vars: below ground "Tz" and "soilm" can be summarised')
+    a, depths, tbp = _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device)
+    tab, labels = summary_periods(a["obstime"], periods)
+    res = api.runmicro_depths_summary(**a, depths=depths, tbp=tbp, periods=tab, nperiods=len(labels), vars=names, stats=stats,
+                                      thresholds=thresholds, chunk_days=chunk_days, device=device)
     res["periods"] = labels
     return res
 
