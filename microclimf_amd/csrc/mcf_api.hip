@@ -85,7 +85,7 @@ struct mcf_plan {
     // mcf_plan_run_days_masked: the tile classes on the host, and the launch's own lists on the device
     std::vector<int32_t> h_tiles_fast, h_tiles_slow, h_tiles_sub;
     int32_t* d_tiles_sub = nullptr;
-    int64_t tiles_sub_cap = 0, masked_tiles_skipped = 0;
+    int64_t masked_tiles_skipped = 0;
     // mcf_plan_run_days_cells: the cells' classes, the per-256-cell counts / list offsets, the list of gathered cells, the
     // gathered tiles' images and their ring (grown as needed)
     uint8_t* d_cls = nullptr;
@@ -100,7 +100,7 @@ struct mcf_plan {
     hipEvent_t ev_prep = nullptr, ev_cells_done = nullptr;
     bool cells_inflight = false;
     int64_t cells_runs = 0, cells_gathered = 0;
-    int64_t n_fast = 0, n_slow = 0, tiles_cap = 0;
+    int64_t n_fast = 0, n_slow = 0;
     int32_t *d_fix_count = nullptr, *d_fix_list = nullptr;
     int fix_cap = 8192;
     int64_t fast_launches = 0, slow_launches = 0;
@@ -181,22 +181,12 @@ struct mcf_plan {
 
 namespace {
 
-int dalloc(mcf_plan* p, void** ptr, int64_t nbytes) { return p->dev.alloc(ptr, nbytes); }
+// a plan on its way to the caller, or a one-call entry's own: destroyed on every path that does not release() it
+struct PlanDestroy { void operator()(mcf_plan* p) const { mcf_plan_destroy(p); } };
+using PlanHolder = std::unique_ptr<mcf_plan, PlanDestroy>;
 
-// a buffer that grows: the old one is released first.  A buffer that has to grow gets a quarter more than is asked for — the
-// sets of cells of successive calls differ by little, and a release + allocation of a gigabyte costs 50 ms
-int dregrow(mcf_plan* p, void** ptr, int64_t* cap, int64_t nbytes) {
-    if (*ptr && *cap >= nbytes) return MCF_OK;
-    if (*ptr) {
-        nbytes += nbytes / 4;
-        p->dev.release(*ptr);
-        *ptr = nullptr;
-        *cap = 0;
-    }
-    const int rc = dalloc(p, ptr, nbytes);
-    if (!rc) *cap = std::max<int64_t>(nbytes, 8);
-    return rc;
-}
+// rows of the (taller) column-major raster the caller's arrays are blocks of
+int64_t host_pitch(const mcf_grid_inputs* in) { return in->row_pitch > 0 ? in->row_pitch : in->rows; }
 
 // fn() between two events on the plan's stream when kernel timing is on (mcf_plan_kernel_stats adds the pairs up)
 template <class F>
@@ -262,12 +252,25 @@ hipError_t copy_in(mcf_plan* p, void* dev, const double* host, int64_t ncols) {
 // `spatial`: n = rows x (cols x layers) values of a raster array (read with the plan's row pitch); else a plain vector
 int upload(mcf_plan* p, const double* host, int64_t n, const double** dev, const char* name, bool spatial = true) {
     if (!host) return fail(MCF_ERR_ARG, std::string("missing input array: ") + name);
-    void* d = nullptr;
-    int rc = dalloc(p, &d, n * 8);
-    if (rc) return rc;
+    double* d = nullptr;
+    if (const int rc = p->dev.make(&d, n)) return rc;
     if (spatial && p->pitch != p->rows) HIP_TRY(copy_in(p, d, host, n / p->rows));
     else HIP_TRY(hipMemcpyAsync(d, host, (size_t)n * 8, hipMemcpyHostToDevice, p->stream));
-    *dev = (const double*)d;
+    *dev = d;
+    return MCF_OK;
+}
+// with a dtm, a terrain plane or the wetness index that is not given gets its buffer here and its values in derive_from_dtm
+int upload_or_derive(mcf_plan* p, bool have_dtm, const double* host, int64_t n, const double** dev, const char* name) {
+    if (host || !have_dtm) return upload(p, host, n, dev, name);
+    return p->dev.make(dev, n);
+}
+// a set-up temporary of `own` with the host array's copy queued on the plan's stream (null host: the buffer alone)
+template <class T>
+int upload_temp(mcf_plan* p, mcf::DevOwner& own, const T* host, int64_t n, const T** dev) {
+    T* d = nullptr;
+    if (const int rc = own.make(&d, n)) return rc;
+    if (host) HIP_TRY(hipMemcpyAsync(d, host, (size_t)n * sizeof(T), hipMemcpyHostToDevice, p->stream));
+    *dev = d;
     return MCF_OK;
 }
 
@@ -398,30 +401,30 @@ int derive_from_dtm(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* 
 
 int ensure_cells(mcf_plan* p) {
     if (p->cells_ready) return MCF_OK;
-  for (int l = 0; l < p->layers; ++l) {
-    mcf::CellSetupArgs a{};
-    a.N = p->N;
-    const int64_t lo = (int64_t)l * p->N;      // layer l of the [rows,cols,layers] vegetation arrays
-    a.hgt = p->d_veg[0] + lo; a.pai = p->d_veg[1] + lo; a.x = p->d_veg[2] + lo; a.gsmax = p->d_veg[3] + lo;
-    a.leafr = p->d_veg[4] + lo; a.leaft = p->d_veg[5] + lo; a.clump = p->d_veg[6] + lo; a.leafd = p->d_veg[7] + lo;
-    a.paia = p->d_veg[8] + lo; a.leafden = p->d_veg[9] + lo;
-    a.hgt0 = p->d_veg[0];
-    a.Smin = p->d_soil[0]; a.Smax = p->d_soil[1]; a.gref = p->d_soil[2]; a.soilb = p->d_soil[3];
-    a.Psie = p->d_soil[4]; a.Vq = p->d_soil[5]; a.Vm = p->d_soil[6]; a.Mc = p->d_soil[7];
-    a.rho = p->d_soil[8]; a.slope = p->d_soil[9]; a.aspect = p->d_soil[10]; a.twi = p->d_soil[11];
-    a.svfa = p->d_soil[12];
-    a.hor = p->d_hor; a.wsa = p->d_wsa;
-    a.lats = p->d_lats; a.lons = p->d_lons; a.lat = p->lat; a.lon = p->lon;
-    a.crowpos = p->d_crowpos; a.ccolpos = p->d_ccolpos; a.rows = p->rows;
-    a.elevd = p->d_elevd; a.pkfac = p->d_pkfac;
-    a.tfact = p->opt.tfact;
-    a.twi_mean = p->twi_mean;
-    a.g = p->g;
-    a.cpb = p->cpb;
-    a.cellc = p->d_cellc + (int64_t)l * p->ntiles * mcf::tile_image_doubles(p->cpb);
-    mcf::launch_cell_setup(a, p->stream);
-    HIP_TRY(hipGetLastError());
-  }
+    for (int l = 0; l < p->layers; ++l) {
+        mcf::CellSetupArgs a{};
+        a.N = p->N;
+        const int64_t lo = (int64_t)l * p->N;      // layer l of the [rows,cols,layers] vegetation arrays
+        a.hgt = p->d_veg[0] + lo; a.pai = p->d_veg[1] + lo; a.x = p->d_veg[2] + lo; a.gsmax = p->d_veg[3] + lo;
+        a.leafr = p->d_veg[4] + lo; a.leaft = p->d_veg[5] + lo; a.clump = p->d_veg[6] + lo; a.leafd = p->d_veg[7] + lo;
+        a.paia = p->d_veg[8] + lo; a.leafden = p->d_veg[9] + lo;
+        a.hgt0 = p->d_veg[0];
+        a.Smin = p->d_soil[0]; a.Smax = p->d_soil[1]; a.gref = p->d_soil[2]; a.soilb = p->d_soil[3];
+        a.Psie = p->d_soil[4]; a.Vq = p->d_soil[5]; a.Vm = p->d_soil[6]; a.Mc = p->d_soil[7];
+        a.rho = p->d_soil[8]; a.slope = p->d_soil[9]; a.aspect = p->d_soil[10]; a.twi = p->d_soil[11];
+        a.svfa = p->d_soil[12];
+        a.hor = p->d_hor; a.wsa = p->d_wsa;
+        a.lats = p->d_lats; a.lons = p->d_lons; a.lat = p->lat; a.lon = p->lon;
+        a.crowpos = p->d_crowpos; a.ccolpos = p->d_ccolpos; a.rows = p->rows;
+        a.elevd = p->d_elevd; a.pkfac = p->d_pkfac;
+        a.tfact = p->opt.tfact;
+        a.twi_mean = p->twi_mean;
+        a.g = p->g;
+        a.cpb = p->cpb;
+        a.cellc = p->d_cellc + (int64_t)l * p->ntiles * mcf::tile_image_doubles(p->cpb);
+        mcf::launch_cell_setup(a, p->stream);
+        HIP_TRY(hipGetLastError());
+    }
     if (!p->af && p->day_irregular.empty() && p->ndays > 0) {
         // the per-day flags of the time table, once: kStepIrregular and kSoilDaily in TF_IDX (its last field)
         const int tfc = mcf::time_field_count();
@@ -440,29 +443,15 @@ int ensure_cells(mcf_plan* p) {
     }
     if (p->fast_enabled) {
         int rc;
-        const int64_t ntiles = (p->N + p->cpb - 1) / p->cpb;
-        if (p->tiles_cap < ntiles) {
-            void* q;
-            if ((rc = dalloc(p, &q, ntiles * 4))) return rc;
-            p->d_tiles_fast = (int32_t*)q;
-            if ((rc = dalloc(p, &q, ntiles * 4))) return rc;
-            p->d_tiles_slow = (int32_t*)q;
-            p->tiles_cap = ntiles;
-        }
+        const int64_t ntiles = p->ntiles;
+        if (!p->d_tiles_slow && ((rc = p->dev.make(&p->d_tiles_fast, ntiles)) || (rc = p->dev.make(&p->d_tiles_slow, ntiles)))) return rc;
         if (!p->d_fix_count) {
-            void* q;
-            if ((rc = dalloc(p, &q, 64))) return rc;
-            p->d_fix_count = (int32_t*)q;
+            if ((rc = p->dev.make(&p->d_fix_count, 16))) return rc;
             HIP_TRY(hipMemsetAsync(p->d_fix_count, 0, 64, p->stream));
-            if ((rc = dalloc(p, &q, (int64_t)p->fix_cap * 8))) return rc;
-            p->d_fix_list = (int32_t*)q;
+            if ((rc = p->dev.make(&p->d_fix_list, (int64_t)p->fix_cap * 2))) return rc;
         }
         // tile classes (the flags stay on the device for mcf_plan_run_days_cells)
-        if (!p->d_tile_regular) {
-            void* q;
-            if ((rc = dalloc(p, &q, ntiles))) return rc;
-            p->d_tile_regular = (uint8_t*)q;
-        }
+        if (!p->d_tile_regular && (rc = p->dev.make(&p->d_tile_regular, ntiles))) return rc;
         uint8_t* d_flag = p->d_tile_regular;
         mcf::launch_tile_regular(p->d_cellc, p->N, p->layers, p->cpb, d_flag, p->stream);
         HIP_TRY(hipGetLastError());
@@ -481,6 +470,454 @@ int ensure_cells(mcf_plan* p) {
         }
     }
     p->cells_ready = true;     // only now: a failed allocation or copy above leaves the plan to try again, not half set up
+    return MCF_OK;
+}
+
+// ---- plan set-up, step by step (plan_create is the list; the steps run in this order, and so do their refusals) -------------
+// What steps hand to later ones and what the copies and kernels queued on the stream read: plan_create holds it until its last synchronise.
+struct SetupScratch {
+    std::vector<double> cpk_sea;            // coarse pressure reduced to sea level (altitude correction), [crows*ccols][T]
+    std::vector<double> cwu, cwv, cwd;      // coarse wind components [crows*ccols][T] and the raster-mean direction per step
+    mcf::DevOwner temps;                    // device copies of obstime, winddir and the vector forcing; the mxtc slab
+    const int32_t *year = nullptr, *month = nullptr, *day = nullptr;
+    const double *hour = nullptr, *winddir = nullptr;
+};
+
+// coarse array forcing, what the host can judge; leaves: crows / ccols, altcorrect, coarse_lds
+int coarse_check(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt) {
+    if (!p->coarse) return MCF_OK;
+    if (in->coarse_rows < 1 || in->coarse_cols < 1 || !in->coarse_rowpos || !in->coarse_colpos || !in->coarse_relhum ||
+        !in->coarse_winddir)
+        return fail(MCF_ERR_ARG, "coarse array forcing needs coarse_rows/cols, coarse_rowpos/colpos, coarse_relhum and coarse_winddir");
+    // (the solver addresses a day of a coarse field with 32-bit byte offsets: 24 x cells x 8 B < 2^32)
+    if ((int64_t)in->coarse_rows * in->coarse_cols > 11000000) return fail(MCF_ERR_ARG, "coarse grid too large (more than 1.1e7 cells)");
+    if (p->bg && !opt->complete) return fail(MCF_ERR_ARG, "coarse array forcing: reqhgt < 0 needs complete = 1");
+    for (int64_t i = 0; i < in->rows; ++i)
+        if (!(in->coarse_rowpos[i] >= 0.0 && in->coarse_rowpos[i] <= in->coarse_rows - 1))
+            return fail(MCF_ERR_ARG, "coarse_rowpos must lie in [0, coarse_rows - 1]");
+    for (int64_t j = 0; j < in->cols; ++j)
+        if (!(in->coarse_colpos[j] >= 0.0 && in->coarse_colpos[j] <= in->coarse_cols - 1))
+            return fail(MCF_ERR_ARG, "coarse_colpos must lie in [0, coarse_cols - 1]");
+    p->crows = in->coarse_rows; p->ccols = in->coarse_cols;
+    p->altcorrect = in->coarse_altcorrect;
+    // the LDS-staged taps (k_solve, CLDS): a tile's 32 cells lie in at most two raster columns and, in each, reach at most
+    // four coarse rows (the rows of its first and last cell and one more)
+    p->coarse_lds = in->rows >= 32 && getenv("MCF_NO_COARSE_LDS") == nullptr;
+    // ... with row positions that do not decrease down a raster column: the kernel finds a tile's wrap into the next column
+    // where the position falls back, and the window test below looks at a window's two ends only.  A flipped or otherwise
+    // non-monotone coarse grid takes the per-lane taps, which make no such assumption.
+    for (int64_t i = 1; p->coarse_lds && i < in->rows; ++i)
+        if (in->coarse_rowpos[i] < in->coarse_rowpos[i - 1]) p->coarse_lds = false;
+    for (int64_t i = 0; p->coarse_lds && i < in->rows; ++i) {
+        const int64_t l = std::min<int64_t>(i + 31, in->rows - 1);
+        if (floor(in->coarse_rowpos[l]) - floor(in->coarse_rowpos[i]) + 2 > 4) p->coarse_lds = false;
+    }
+    if (p->altcorrect < 0 || p->altcorrect > 2) return fail(MCF_ERR_ARG, "coarse_altcorrect must be 0, 1 or 2");
+    if (p->altcorrect && (!in->coarse_dtm || !in->fine_dtm))
+        return fail(MCF_ERR_ARG, "altitude correction needs coarse_dtm and fine_dtm");
+    return MCF_OK;
+}
+
+// leaves: geometry and pitch, the plan's kind (af, coarse, bg, bg_stream), coarse_check's, cpb / ntiles, layers, opt, the ring's days and slots
+int plan_shape(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots, bool streamed) {
+    p->rows = in->rows; p->cols = in->cols; p->N = in->rows * in->cols; p->tsteps = in->tsteps;
+    p->pitch = host_pitch(in);
+    if (p->pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
+    p->ndays = (int)(in->tsteps / 24);                       // cpp:2116 truncation
+    p->af = in->array_forcing != 0;
+    p->coarse = in->array_forcing == 2;
+    p->bg = opt->reqhgt < 0.0;
+    p->bg_stream = p->bg && streamed;
+    if (const int rc = coarse_check(p, in, opt)) return rc;
+    // vector forcing: two 8-wave workgroups per CU (21 cells); array forcing: one 12-wave workgroup
+    p->cpb = opt->cells_per_block ? opt->cells_per_block : (in->array_forcing ? 32 : 21);
+    // coarse array forcing is built for 32-cell tiles only: tile classes, tile lists and the ring's blocks must agree
+    if (p->coarse) p->cpb = 32;
+    if (in->array_forcing && p->cpb == 42) p->cpb = 32;      // 42-cell tiles are built for vector forcing only (they would spill)
+    if (p->N >= ((int64_t)1 << 31)) return fail(MCF_ERR_ARG, "at most 2^31 - 1 cells per plan (row-tile larger rasters)");
+    p->ntiles = (p->N + p->cpb - 1) / p->cpb;
+    static const bool no_fast = getenv("MCF_NO_FAST_CLAMPS") != nullptr;     // A/B runs
+    p->fast_enabled = !no_fast && !(opt->reqhgt < 0.0);
+    p->layers = in->veg_layers > 1 ? in->veg_layers : 1;
+    p->opt = *opt;
+    p->lat = in->lat; p->lon = in->lon;
+    if (ring_slots < 1) ring_slots = 1;
+    if (ring_days < 1) ring_days = 1;
+    // (streamed below ground: a slot may hold one day more, for the steps behind the last whole day)
+    const int max_days = p->bg_stream ? (int)std::max<int64_t>((in->tsteps + 23) / 24, 1) : std::max(p->ndays, 1);
+    if (ring_days > max_days) ring_days = max_days;
+    // reqhgt < 0 smooths the whole series (incl. steps past the last whole day, which read as 0)
+    if (p->bg && !p->bg_stream) { ring_slots = 1; ring_days = (int)std::max<int64_t>((in->tsteps + 23) / 24, 1); }
+    // array forcing re-lays a slot's series with one launch row per step (gridDim.y <= 65535): 2730 whole days at most
+    if (in->array_forcing == 1 && ring_days > 2730) ring_days = 2730;
+    p->ring_days = ring_days; p->ring_slots = ring_slots;
+    return MCF_OK;
+}
+
+// leaves: d_veg, d_soil, d_wsa, d_hor (given, or derived from the dtm), d_lats / d_lons (array forcing), valid_cells
+int upload_static(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* dtm) {
+    int rc;
+    const int64_t N = p->N;
+    const double* veg[10] = {in->vegp.hgt, in->vegp.pai, in->vegp.x, in->vegp.gsmax, in->vegp.leafr,
+                             in->vegp.leaft, in->vegp.clump, in->vegp.leafd, in->vegp.paia, in->vegp.leafden};
+    const char* vegn[10] = {"hgt", "pai", "x", "gsmax", "leafr", "leaft", "clump", "leafd", "paia", "leafden"};
+    for (int i = 0; i < 10; ++i)
+        if ((rc = upload(p, veg[i], N * p->layers, &p->d_veg[i], vegn[i]))) return rc;
+    const double* soil[13] = {in->soilc.Smin, in->soilc.Smax, in->soilc.gref, in->soilc.soilb, in->soilc.Psie,
+                              in->soilc.Vq, in->soilc.Vm, in->soilc.Mc, in->soilc.rho, in->soilc.slope,
+                              in->soilc.aspect, in->soilc.twi, in->soilc.svfa};
+    const char* soiln[13] = {"Smin", "Smax", "gref", "soilb", "Psie", "Vq", "Vm", "Mc", "rho", "slope",
+                             "aspect", "twi", "svfa"};
+    for (int i = 0; i < 13; ++i)      // (slope, aspect, twi and svfa can come from the dtm)
+        if ((rc = upload_or_derive(p, dtm && i >= 9, soil[i], N, &p->d_soil[i], soiln[i]))) return rc;
+    if ((rc = upload_or_derive(p, dtm, in->soilc.wsa, N * 8, &p->d_wsa, "wsa"))) return rc;
+    if ((rc = upload_or_derive(p, dtm, in->soilc.hor, N * 24, &p->d_hor, "hor"))) return rc;
+    if (dtm && (rc = derive_from_dtm(p, in, dtm))) return rc;
+    if (p->af) {
+        if ((rc = upload(p, in->lats, N, &p->d_lats, "lats"))) return rc;
+        if ((rc = upload(p, in->lons, N, &p->d_lons, "lons"))) return rc;
+    }
+    p->valid_cells = 0;
+    for (int64_t j = 0; j < in->cols; ++j)
+        for (int64_t i = 0; i < in->rows; ++i) p->valid_cells += !std::isnan(in->vegp.hgt[i + p->pitch * j]);
+    return MCF_OK;
+}
+
+// coarse array forcing; leaves: d_crowpos / d_ccolpos, with altitude correction d_elevd / d_pkfac and s.cpk_sea
+int coarse_planes(mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    if (!p->coarse) return MCF_OK;
+    int rc;
+    const int64_t N = p->N;
+    if ((rc = upload(p, in->coarse_rowpos, in->rows, &p->d_crowpos, "coarse_rowpos", false))) return rc;
+    if ((rc = upload(p, in->coarse_colpos, in->cols, &p->d_ccolpos, "coarse_colpos", false))) return rc;
+    if (!p->altcorrect) return MCF_OK;
+    // R/internal.R:1236-1241: psl = pk / ((293 - 0.0065 zc) / 293)^5.26 on the coarse grid, back up with the
+    // fine elevation after resampling; elevd = resample(dtmc) - dtm
+    const int cr = p->crows, cc = p->ccols;
+    std::vector<double> zc((size_t)cr * cc), elevd((size_t)N), pkfac((size_t)N);
+    for (size_t q = 0; q < zc.size(); ++q) zc[q] = std::isnan(in->coarse_dtm[q]) ? 0.0 : in->coarse_dtm[q];
+    for (int64_t j = 0; j < in->cols; ++j) {
+        const double cp = in->coarse_colpos[j], fc = floor(cp), wx = cp - fc;
+        const int c0 = (int)fc, c1 = c0 + 1 < cc ? c0 + 1 : c0;
+        for (int64_t i = 0; i < in->rows; ++i) {
+            const double rp = in->coarse_rowpos[i], fr = floor(rp), wy = rp - fr;
+            const int r0 = (int)fr, r1 = r0 + 1 < cr ? r0 + 1 : r0;
+            const double top = (1.0 - wx) * zc[(size_t)(r0 + cr * c0)] + wx * zc[(size_t)(r0 + cr * c1)];
+            const double bot = (1.0 - wx) * zc[(size_t)(r1 + cr * c0)] + wx * zc[(size_t)(r1 + cr * c1)];
+            const double z = in->fine_dtm[i + p->pitch * j];
+            elevd[(size_t)(i + in->rows * j)] = ((1.0 - wy) * top + wy * bot) - z;
+            pkfac[(size_t)(i + in->rows * j)] = pow((293.0 - 0.0065 * z) / 293.0, 5.26);
+        }
+    }
+    if ((rc = upload(p, elevd.data(), N, &p->d_elevd, "elevd", false))) return rc;
+    if ((rc = upload(p, pkfac.data(), N, &p->d_pkfac, "pkfac", false))) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));      // elevd and pkfac have been read
+    if (in->tsteps > 0 && in->clim.pk) {
+        const int64_t cN = (int64_t)cr * cc;
+        s.cpk_sea.resize((size_t)(cN * in->tsteps));
+        for (int64_t k = 0; k < in->tsteps; ++k)
+            for (int64_t q = 0; q < cN; ++q)
+                s.cpk_sea[(size_t)(q + cN * k)] = in->clim.pk[q + cN * k] / pow((293.0 - 0.0065 * zc[(size_t)q]) / 293.0, 5.26);
+    }
+    return MCF_OK;
+}
+
+// leaves: the solver's globals g (dTmx: the time tables), hiy, and the one global reduction — the mean of log(twi)/tfact, cpp:993-1004
+int solver_constants(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt) {
+    p->g.reqhgt = opt->reqhgt;
+    p->g.reqhgt2 = opt->reqhgt < 0.00001 ? 0.00001 : opt->reqhgt;      // cpp:2246-2247
+    p->g.zref = opt->zref;
+    p->g.hf0p = mcf::hf_pow02(1 / 999.99);   // mincondCpp(leafabs, 999.99, ...) at cpp:1348
+    p->g.hf500p = mcf::hf_pow02(500.0);      // rs capped at 500 (gs <= 0.002), cpp:1321-1323
+    p->g.shadowmask = p->af ? 0 : 1;
+    p->g.dTmx = 0.0;
+    p->hiy = 365 * 24;
+    if (p->tsteps > 0 && in->obstime.year[0] % 4 == 0) p->hiy = 366 * 24;      // cpp:2171-2172
+    if (const int rc = p->dev.make(&p->d_twi2, (int64_t)mcf::twi_scratch_doubles())) return rc;
+    mcf::launch_twi_partial(p->d_soil[11], p->N, opt->tfact, p->d_twi2, p->stream);
+    double h2[2];
+    HIP_TRY(hipMemcpyAsync(h2, p->d_twi2, 16, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->twi_sum = h2[0];
+    p->twi_count = (int64_t)h2[1];
+    p->twi_mean = h2[0] / h2[1];
+    return MCF_OK;
+}
+
+// leaves: d_cellc zeroed (ensure_cells fills it before the first run), with layered vegetation d_daylayer / daylayer0
+int cell_images(mcf_plan* p, const mcf_grid_inputs* in) {
+    int rc;
+    // per-cell constants, tile-major (mcf_kernels.h CellSetupArgs); zeroed once: the cells past the raster's end in the last
+    // tile's image are read (not used) by the solver
+    const int64_t cellc_doubles = (int64_t)p->layers * p->ntiles * mcf::tile_image_doubles(p->cpb);
+    if ((rc = p->dev.make(&p->d_cellc, cellc_doubles))) return rc;
+    HIP_TRY(hipMemsetAsync(p->d_cellc, 0, (size_t)cellc_doubles * 8, p->stream));
+    if (p->layers <= 1) return MCF_OK;
+    // day -> layer map from dfsel (cpp:2629-2640, k = dy*24 + hr + st[lyr]); -1 = not covered
+    std::vector<int32_t> dl((size_t)std::max(p->ndays, 1), -1);
+    for (int l = 0; l < p->layers; ++l) {
+        int nd = (in->lyr_ed[l] - in->lyr_st[l] + 1) / 24, d0 = in->lyr_st[l] / 24;
+        for (int d = d0; d < d0 + nd && d < p->ndays; ++d) dl[d] = l;
+    }
+    if ((rc = p->dev.make(&p->d_daylayer, (int64_t)dl.size()))) return rc;
+    p->daylayer0 = dl;
+    HIP_TRY(hipMemcpyAsync(p->d_daylayer, dl.data(), dl.size() * 4, hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return MCF_OK;
+}
+
+// leaves: s.cwu / s.cwv, the wind components per coarse cell, and s.cwd, the raster-mean direction per step (R/internal.R:1255-1264)
+void coarse_wind(const mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    const int64_t T = p->tsteps, cN = (int64_t)p->crows * p->ccols;
+    s.cwu.resize((size_t)(cN * T)); s.cwv.resize((size_t)(cN * T)); s.cwd.resize((size_t)T);
+    for (int64_t k = 0; k < T; ++k) {
+        double su = 0, sv = 0;
+        int64_t nu = 0, nv = 0;
+        for (int64_t q = 0; q < cN; ++q) {
+            const double u2 = in->clim.windspeed[q + cN * k], wd = in->coarse_winddir[q + cN * k] * M_PI / 180.0;
+            const double u = u2 * cos(wd), v = u2 * sin(wd);
+            s.cwu[(size_t)(q + cN * k)] = u; s.cwv[(size_t)(q + cN * k)] = v;
+            if (!std::isnan(u)) { su += u; ++nu; }               // apply(wu, 3, mean, na.rm = TRUE)
+            if (!std::isnan(v)) { sv += v; ++nv; }
+        }
+        double d = fmod(atan2(sv / (double)nv, su / (double)nu) * 180.0 / M_PI, 360.0);
+        if (d < 0) d += 360.0;                                    // R's %% takes the sign of the divisor
+        s.cwd[(size_t)k] = d;
+    }
+}
+
+// the plan's forcing series are all there; leaves: the device copies of obstime and of the wind direction (coarse: coarse_wind's) in s
+int time_inputs(mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    const int64_t T = p->tsteps;
+    if (T <= 0) return MCF_OK;
+    const double* raw[15];
+    clim_ptrs(in, raw);
+    for (int f = 0; f < 15; ++f)
+        if (!raw[f] && !(p->coarse && f >= 1 && f <= 3))     // es, ea, tdew are derived in coarse mode
+            return fail(MCF_ERR_ARG, std::string("missing forcing array: ") + kRawNames[f]);
+    if (!p->coarse && !in->clim.winddir) return fail(MCF_ERR_ARG, "missing forcing array: winddir");
+    if (p->coarse) coarse_wind(p, in, s);
+    int rc;
+    if ((rc = upload_temp(p, s.temps, in->obstime.year, T, &s.year)) || (rc = upload_temp(p, s.temps, in->obstime.month, T, &s.month)) ||
+        (rc = upload_temp(p, s.temps, in->obstime.day, T, &s.day)) || (rc = upload_temp(p, s.temps, in->obstime.hour, T, &s.hour)))
+        return rc;
+    return upload_temp(p, s.temps, p->coarse ? s.cwd.data() : in->clim.winddir, T, &s.winddir);
+}
+
+// vector forcing; leaves: g.dTmx from the series' maximum air temperature, and d_tt, the table of every day's 24 steps
+int time_tables_vector(mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    int rc;
+    const int64_t T = p->tsteps;
+    double mxtc = -273.15;                                           // cpp:2159-2168
+    for (int64_t k = 0; k < T; ++k)
+        if (in->clim.tc[k] > mxtc) mxtc = in->clim.tc[k];
+    p->g.dTmx = -0.6273 * mxtc + 49.79;                              // cpp:1236
+    if ((rc = p->dev.make(&p->d_tt, (int64_t)std::max(p->ndays, 1) * mcf::time_field_count() * 24))) return rc;
+    if (p->ndays <= 0) return MCF_OK;
+    const double* raw[15];
+    clim_ptrs(in, raw);
+    mcf::TimeSetupArgs ta{};
+    ta.nsteps = p->ndays * 24;
+    ta.year = s.year; ta.month = s.month; ta.day = s.day; ta.hour = s.hour; ta.winddir = s.winddir;
+    for (int f = 0; f < 15; ++f)
+        if ((rc = upload_temp(p, s.temps, raw[f], T, &ta.raw[f]))) return rc;
+    ta.lat = in->lat; ta.lon = in->lon;
+    ta.tt = p->d_tt;
+    mcf::launch_time_setup(ta, p->stream);
+    HIP_TRY(hipGetLastError());
+    return MCF_OK;
+}
+// array forcing, fine and coarse; leaves: d_dt and d_windex filled from the dates, d_mxtc allocated
+int time_tables_array(mcf_plan* p, SetupScratch& s) {
+    int rc;
+    const int64_t T = p->tsteps;
+    if ((rc = p->dev.make(&p->d_dt, std::max<int64_t>(T, 1) * 4)) || (rc = p->dev.make(&p->d_windex, std::max<int64_t>(T, 1))) ||
+        (rc = p->dev.make(&p->d_mxtc, p->N)))
+        return rc;
+    if (T <= 0) return MCF_OK;
+    mcf::DateSetupArgs da{};
+    da.nsteps = (int)T;
+    da.year = s.year; da.month = s.month; da.day = s.day; da.hour = s.hour; da.winddir = s.winddir;
+    da.dt = p->d_dt; da.windex = p->d_windex;
+    mcf::launch_date_setup(da, p->stream);
+    HIP_TRY(hipGetLastError());
+    return MCF_OK;
+}
+// coarse array forcing; leaves: d_force, the 15 coarse slabs' whole series resident ([15][crows*ccols][T]), d_mxtc (k_mxtc_coarse)
+int time_tables_coarse(mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    int rc;
+    if ((rc = time_tables_array(p, s))) return rc;
+    const int64_t T = p->tsteps, cN = (int64_t)p->crows * p->ccols, slab = cN * std::max<int64_t>(T, 1);
+    if ((rc = p->dev.make(&p->d_force, 15 * slab))) return rc;
+    const double* src[15];
+    clim_ptrs(in, src);
+    src[1] = in->coarse_relhum;                    // slot TF_ES
+    src[2] = s.cwv.data();                         // slot TF_EA: v component
+    src[3] = nullptr;                              // slot TF_TDEW unused
+    if (p->altcorrect) src[4] = s.cpk_sea.data();  // slot TF_PK: sea-level pressure
+    src[8] = s.cwu.data();                         // slot TF_U2: u component
+    for (int f = 0; f < 15 && T > 0; ++f)
+        if (src[f]) HIP_TRY(hipMemcpyAsync(p->d_force + f * slab, src[f], (size_t)(cN * T * 8), hipMemcpyHostToDevice, p->stream));
+    if (T > 0) {
+        mcf::launch_mxtc_coarse(p->d_force, slab, p->crows, p->ccols, (int)T, p->d_crowpos, p->d_ccolpos, p->rows, p->N,
+                                p->altcorrect, p->d_elevd, p->d_pkfac, p->d_mxtc, p->stream);
+        HIP_TRY(hipGetLastError());
+    } else {
+        mcf::launch_fill(p->d_mxtc, p->N, -273.15, p->stream);
+    }
+    // the slabs are on the device before anything else is queued (their sources: s.cwu / s.cwv / s.cpk_sea, which plan_create
+    // holds until its own synchronise, and the caller's arrays)
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    p->force_day0.assign(p->ring_slots, 0);
+    p->force_ndays.assign(p->ring_slots, p->ndays);
+    return MCF_OK;
+}
+// fine array forcing; leaves: d_mxtc over the WHOLE series (cpp:2467-2471), the tiled forcing ring d_force (empty) and its staging slab
+int time_tables_fine(mcf_plan* p, const mcf_grid_inputs* in, SetupScratch& s) {
+    int rc;
+    if ((rc = time_tables_array(p, s))) return rc;
+    const int64_t T = p->tsteps, N = p->N;
+    mcf::launch_fill(p->d_mxtc, N, -273.15, p->stream);
+    const int64_t slab_steps = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(256LL << 20) / (N * 8)));
+    if (T > 0) {      // streamed in slabs
+        const double* dslab = nullptr;
+        if ((rc = upload_temp<double>(p, s.temps, nullptr, slab_steps * N, &dslab))) return rc;
+        for (int64_t k0 = 0; k0 < T; k0 += slab_steps) {
+            const int64_t ns = std::min(slab_steps, T - k0);
+            HIP_TRY(copy_in(p, const_cast<double*>(dslab), in->clim.tc + p->pitch * p->cols * k0, p->cols * ns));
+            mcf::launch_mxtc(dslab, N, (int)ns, p->d_mxtc, p->stream);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    // forcing ring, TILED like the output ring: [slots][tile][day][15 series][ring_block_doubles(cpb)] in the solver's lane
+    // order, so that a workgroup's 360 loads per day (15 series x 24 hours, each 8 B x N x hour apart in the caller's
+    // arrays) become whole lines of one contiguous 90 KB run; mcf_plan_upload_forcing_days re-lays each series on the
+    // device behind its host-to-device copy
+    p->force_day_stride = 15 * (int64_t)mcf::ring_block_doubles(p->cpb);
+    p->force_tile_stride = (int64_t)p->ring_days * p->force_day_stride;
+    p->force_slot_elems = p->ntiles * p->force_tile_stride;
+    if ((rc = p->dev.make(&p->d_force, (int64_t)p->ring_slots * p->force_slot_elems))) return rc;
+    if ((rc = p->dev.make(&p->d_force_stage, N * (int64_t)p->ring_days * 24))) return rc;     // one series of one slot, as uploaded
+    p->force_day0.assign(p->ring_slots, -1);
+    p->force_ndays.assign(p->ring_slots, 0);
+    return MCF_OK;
+}
+
+// leaves: var_slot / nvars, the ring's geometry — tiled, or linear for whole-series below ground — and d_ring
+int output_ring(mcf_plan* p, const mcf_options* opt) {
+    p->nvars = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) p->var_slot[v] = opt->out[v] ? p->nvars++ : -1;
+    p->tiled = !p->bg || p->bg_stream;
+    if (p->tiled) {
+        const int64_t blk = mcf::ring_block_doubles(p->cpb);
+        p->ring_var_stride = blk;
+        p->ring_day_stride = (int64_t)std::max(p->nvars, 1) * blk;
+        p->ring_tile_stride = (int64_t)p->ring_days * p->ring_day_stride;
+        p->slot_elems = p->ntiles * p->ring_tile_stride;
+    } else {
+        p->slot_elems = (int64_t)std::max(p->nvars, 1) * p->N * (int64_t)p->ring_days * 24;
+    }
+    return p->dev.make(&p->d_ring, (int64_t)p->ring_slots * p->slot_elems);
+}
+
+// below ground in day chunks: O(cells x days) of state, no [N][tsteps] buffer.  Leaves: the Tg ring, d_ddsum, the sweep's state or Tgp / Tbp
+int below_stream_state(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt) {
+    if (!(p->bg_stream && opt->out[MCF_OUT_TZ])) return MCF_OK;
+    int rc;
+    const int64_t N = p->N, nd = std::max(p->ndays, 1);
+    p->tg_tile_stride = (int64_t)p->ring_days * mcf::ring_block_doubles(p->cpb);
+    if ((rc = p->dev.make(&p->d_tgring, p->ntiles * p->tg_tile_stride)) || (rc = p->dev.make(&p->d_ddsum, N))) return rc;
+    if (opt->complete) {
+        if ((rc = p->dev.make(&p->d_hsum, N)) || (rc = p->dev.make(&p->d_dmean, N * nd)) || (rc = p->dev.make(&p->d_ybuf, N * nd)) ||
+            (rc = p->dev.make(&p->d_wrap, N * mcf::kBelowWin)))
+            return rc;
+        return p->dev.make(&p->d_prev, N * mcf::kBelowWin);
+    }
+    if (p->af) {
+        // per cell-step: each slot's days, uploaded with its forcing (mcf_plan_upload_forcing_days)
+        const int64_t n = (int64_t)p->ring_slots * p->ring_days * 24 * N;
+        if ((rc = p->dev.make(&p->d_Tgp_slots, n)) || (rc = p->dev.make(&p->d_Tbp_slots, n))) return rc;
+        if (!in->pointm.Tg || !in->pointm.Tbp) return fail(MCF_ERR_ARG, "missing input array: pointm$Tg / pointm$Tbp");
+        return MCF_OK;
+    }
+    if ((rc = upload(p, in->pointm.Tg, p->tsteps, &p->d_Tgp, "pointm$Tg", false))) return rc;
+    return upload(p, in->pointm.Tbp, p->tsteps, &p->d_Tbp, "pointm$Tbp", false);
+}
+// below ground over the whole series; leaves: d_tgser and d_ddsum zeroed, d_scratch, with complete = 0 the point model's Tg / Tbp
+int below_series_state(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt) {
+    if (!(p->bg && !p->bg_stream)) return MCF_OK;
+    int rc;
+    const int64_t N = p->N, T = p->tsteps;
+    if ((rc = p->dev.make(&p->d_tgser, N * std::max<int64_t>(T, 1)))) return rc;
+    // steps past the last whole day read as 0 in the reference (std::vector<double> Tg(tsteps))
+    mcf::launch_fill(p->d_tgser, N * T, 0.0, p->stream);
+    if ((rc = p->dev.make(&p->d_ddsum, N))) return rc;
+    mcf::launch_fill(p->d_ddsum, N, 0.0, p->stream);
+    if ((rc = p->dev.make(&p->d_scratch, N * 2 * (int64_t)std::max(p->ndays, 1)))) return rc;
+    if (opt->complete) return MCF_OK;
+    const int64_t n = p->af ? N * T : T;
+    if ((rc = upload(p, in->pointm.Tg, n, &p->d_Tgp, "pointm$Tg", p->af))) return rc;
+    return upload(p, in->pointm.Tbp, n, &p->d_Tbp, "pointm$Tbp", p->af);
+}
+
+// ---- what the one-call entries share (run_oneshot, run_summary, run_depths, run_bioclim) ------------------------------------
+// The day-chunk driver: days [0, ndays) through slot 0 of `p`, `chunk` at a time — the chunk's forcing uploaded (array
+// forcing; a coarse plan's series is resident and the upload returns at once), its days run, then sink(d0, nd).
+template <class Sink>
+int for_day_chunks(mcf_plan* p, const mcf_grid_inputs* in, int ndays, int chunk, Sink&& sink) {
+    for (int d0 = 0; d0 < ndays; d0 += chunk) {
+        const int nd = std::min(chunk, ndays - d0);
+        int rc;
+        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
+        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+        if ((rc = sink(d0, nd))) return rc;
+    }
+    return MCF_OK;
+}
+
+// Chunk size, ring-budget family (the sinks that keep nothing but a ring: bioclim, summaries): the days of a tiled ring of
+// `slabs` blocks per tile and day that fit the budget of environment variable `env` in GB (default 14), at least one.
+int ring_budget_days(const char* env, int slabs, int64_t N, int cpb) {
+    const double day_bytes = 8.0 * slabs * (double)((N + cpb - 1) / cpb) * (double)mcf::ring_block_doubles(cpb);
+    const char* e = getenv(env);
+    const double budget = (e && atof(e) > 0.0 ? atof(e) : 14.0) * 1e9;     // (4096^2 bioclim: 0.80 s with 14 GB = two-day chunks, 0.85 s with 8, 2.3 s with 27 — the allocation; profiles/r05_sink_rates.txt)
+    return (int)std::max(1.0, floor(budget / day_bytes));
+}
+
+// Chunk size, free-memory family (the entries whose chunks go to the host: run_oneshot, run_depths): the days of `slabs`
+// untiled [N][24] slabs that fit 0.6 of this caller's share of the free HBM, less 200 doubles per cell for the plan's planes,
+// less `state_doubles` per cell of below-ground state, less one day more in the slot for a tail; 1 .. 64, and no more than ndays.
+// (The amounts taken off are whole numbers of bytes: each subtraction is exact while the budget stays positive, so their
+// order is free, and a negative budget gives one day whatever its value.)
+int free_memory_chunk_days(int64_t N, int ndays, int sharers, int slabs, double state_doubles, bool tail, int* chunk) {
+    size_t fr = 0, tot = 0;
+    HIP_TRY(hipMemGetInfo(&fr, &tot));
+    const double per_day = (double)N * 24 * 8 * slabs;
+    const double budget = 0.6 * (double)fr / std::max(sharers, 1) - (double)N * 8 * 200 - (double)N * 8 * state_doubles -
+                          (tail ? per_day : 0.0);
+    *chunk = std::min((int)std::max(1.0, std::min((double)std::max(ndays, 1), budget / std::max(per_day, 1.0))), 64);
+    return MCF_OK;
+}
+// per-cell doubles of a streamed below-ground plan's state with D depths: dmean and a ybuf per depth, wrap, prev, the two sums
+double below_state_doubles(int D, int ndays) { return (1.0 + D) * ndays + 2 * mcf::kBelowWin + 2; }
+
+// steps past the last whole day of a caller's [rows, cols, tsteps] array: never computed by the reference, they stay NA (cpp:2116)
+void fill_tail_na(double* buf, const mcf_grid_inputs* in, int ndays) {
+    const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
+    const double na = mcf::na_real_host();
+    for (int64_t k = (int64_t)ndays * 24; k < in->tsteps; ++k)
+        for (int64_t j = 0; j < in->cols; ++j)
+            for (int64_t i = 0; i < in->rows; ++i) buf[i + pitch * j + HS * k] = na;
+}
+
+// the four quarter-index vectors of a bioclim call (wet, dry, hot, cold) as plan buffers, their copies queued on its stream
+int upload_quarters(mcf_plan* p, const int32_t* const q[4], const int32_t nq[4], const int32_t* dq[4]) {
+    for (int i = 0; i < 4; ++i) {
+        int32_t* d = nullptr;
+        if (const int rc = p->dev.make(&d, (int64_t)std::max(nq[i], 1))) return rc;
+        if (nq[i] > 0) HIP_TRY(hipMemcpyAsync(d, q[i], (size_t)nq[i] * 4, hipMemcpyHostToDevice, p->stream));
+        dq[i] = d;
+    }
     return MCF_OK;
 }
 
@@ -566,8 +1003,8 @@ int mcf_device_count(void) {
 }
 
 void mcf_plan_destroy(mcf_plan* p) {
-    if (p) mcf::print_variant_stats();
     if (!p) return;
+    mcf::print_variant_stats();
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
     if (p->prep) { hipStreamSynchronize(p->prep); hipStreamDestroy(p->prep); }
@@ -585,397 +1022,29 @@ static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_
                        mcf_plan** out, const mcf_dtm_spec* dtm = nullptr) {
     if (!out) return fail(MCF_ERR_ARG, "null plan pointer");
     *out = nullptr;
-    int rc = check_inputs(in, opt);
-    if (rc) return rc;
+    int rc;
+    if ((rc = check_inputs(in, opt))) return rc;
     if (dtm && (rc = check_dtm(in, dtm))) return rc;
-    rc = ensure_device(opt->device);
-    if (rc) return rc;
-    mcf_plan* p = new mcf_plan();
-    struct Guard { mcf_plan* p; ~Guard() { if (p) mcf_plan_destroy(p); } } guard{p};
+    if ((rc = ensure_device(opt->device))) return rc;
+    PlanHolder holder(new mcf_plan());
+    mcf_plan* p = holder.get();
     p->device = opt->device;
     HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&p->ev0));
     HIP_TRY(hipEventCreate(&p->ev1));
-    p->rows = in->rows; p->cols = in->cols; p->N = in->rows * in->cols; p->tsteps = in->tsteps;
-    p->pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
-    if (p->pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
-    p->ndays = (int)(in->tsteps / 24);                       // cpp:2116 truncation
-    p->af = in->array_forcing != 0;
-    p->coarse = in->array_forcing == 2;
-    p->bg = opt->reqhgt < 0.0;
-    p->bg_stream = p->bg && streamed;
-    if (p->coarse) {
-        if (in->coarse_rows < 1 || in->coarse_cols < 1 || !in->coarse_rowpos || !in->coarse_colpos || !in->coarse_relhum ||
-            !in->coarse_winddir)
-            return fail(MCF_ERR_ARG, "coarse array forcing needs coarse_rows/cols, coarse_rowpos/colpos, coarse_relhum and coarse_winddir");
-        // (the solver addresses a day of a coarse field with 32-bit byte offsets: 24 x cells x 8 B < 2^32)
-        if ((int64_t)in->coarse_rows * in->coarse_cols > 11000000) return fail(MCF_ERR_ARG, "coarse grid too large (more than 1.1e7 cells)");
-        if (p->bg && !opt->complete) return fail(MCF_ERR_ARG, "coarse array forcing: reqhgt < 0 needs complete = 1");
-        for (int64_t i = 0; i < in->rows; ++i)
-            if (!(in->coarse_rowpos[i] >= 0.0 && in->coarse_rowpos[i] <= in->coarse_rows - 1))
-                return fail(MCF_ERR_ARG, "coarse_rowpos must lie in [0, coarse_rows - 1]");
-        for (int64_t j = 0; j < in->cols; ++j)
-            if (!(in->coarse_colpos[j] >= 0.0 && in->coarse_colpos[j] <= in->coarse_cols - 1))
-                return fail(MCF_ERR_ARG, "coarse_colpos must lie in [0, coarse_cols - 1]");
-        p->crows = in->coarse_rows; p->ccols = in->coarse_cols;
-        p->altcorrect = in->coarse_altcorrect;
-        // the LDS-staged taps (k_solve, CLDS): a tile's 32 cells lie in at most two raster columns and, in each, reach at most
-        // four coarse rows (the rows of its first and last cell and one more)
-        p->coarse_lds = in->rows >= 32 && getenv("MCF_NO_COARSE_LDS") == nullptr;
-        // ... with row positions that do not decrease down a raster column: the kernel finds a tile's wrap into the next column
-        // where the position falls back, and the window test below looks at a window's two ends only.  A flipped or otherwise
-        // non-monotone coarse grid takes the per-lane taps, which make no such assumption.
-        for (int64_t i = 1; p->coarse_lds && i < in->rows; ++i)
-            if (in->coarse_rowpos[i] < in->coarse_rowpos[i - 1]) p->coarse_lds = false;
-        for (int64_t i = 0; p->coarse_lds && i < in->rows; ++i) {
-            const int64_t l = std::min<int64_t>(i + 31, in->rows - 1);
-            if (floor(in->coarse_rowpos[l]) - floor(in->coarse_rowpos[i]) + 2 > 4) p->coarse_lds = false;
-        }
-        if (p->altcorrect < 0 || p->altcorrect > 2) return fail(MCF_ERR_ARG, "coarse_altcorrect must be 0, 1 or 2");
-        if (p->altcorrect && (!in->coarse_dtm || !in->fine_dtm))
-            return fail(MCF_ERR_ARG, "altitude correction needs coarse_dtm and fine_dtm");
-    }
-    // vector forcing: two 8-wave workgroups per CU (21 cells); array forcing: one 12-wave workgroup
-    p->cpb = opt->cells_per_block ? opt->cells_per_block : (in->array_forcing ? 32 : 21);
-    // coarse array forcing is built for 32-cell tiles only: tile classes, tile lists and the ring's blocks must agree
-    if (p->coarse) p->cpb = 32;
-    if (in->array_forcing && p->cpb == 42) p->cpb = 32;      // 42-cell tiles are built for vector forcing only (they would spill)
-    if (p->N >= ((int64_t)1 << 31)) return fail(MCF_ERR_ARG, "at most 2^31 - 1 cells per plan (row-tile larger rasters)");
-    {
-        static const bool no_fast = getenv("MCF_NO_FAST_CLAMPS") != nullptr;     // A/B runs
-        p->fast_enabled = !no_fast && !(opt->reqhgt < 0.0);
-    }
-    p->layers = in->veg_layers > 1 ? in->veg_layers : 1;
-    p->opt = *opt;
-    p->lat = in->lat; p->lon = in->lon;
-    const int64_t N = p->N, T = p->tsteps;
-    if (ring_slots < 1) ring_slots = 1;
-    if (ring_days < 1) ring_days = 1;
-    // (streamed below ground: a slot may hold one day more, for the steps behind the last whole day)
-    const int max_days = p->bg_stream ? (int)std::max<int64_t>((in->tsteps + 23) / 24, 1) : std::max(p->ndays, 1);
-    if (ring_days > max_days) ring_days = max_days;
-    // reqhgt < 0 smooths the whole series (incl. steps past the last whole day, which read as 0)
-    if (p->bg && !p->bg_stream) { ring_slots = 1; ring_days = (int)std::max<int64_t>((in->tsteps + 23) / 24, 1); }
-    // array forcing re-lays a slot's series with one launch row per step (gridDim.y <= 65535): 2730 whole days at most
-    if (in->array_forcing == 1 && ring_days > 2730) ring_days = 2730;
-    p->ring_days = ring_days; p->ring_slots = ring_slots;
-
-    // ---- static rasters
-    const double* veg[10] = {in->vegp.hgt, in->vegp.pai, in->vegp.x, in->vegp.gsmax, in->vegp.leafr,
-                             in->vegp.leaft, in->vegp.clump, in->vegp.leafd, in->vegp.paia, in->vegp.leafden};
-    const char* vegn[10] = {"hgt", "pai", "x", "gsmax", "leafr", "leaft", "clump", "leafd", "paia", "leafden"};
-    for (int i = 0; i < 10; ++i)
-        if ((rc = upload(p, veg[i], N * p->layers, &p->d_veg[i], vegn[i]))) return rc;
-    const double* soil[13] = {in->soilc.Smin, in->soilc.Smax, in->soilc.gref, in->soilc.soilb, in->soilc.Psie,
-                              in->soilc.Vq, in->soilc.Vm, in->soilc.Mc, in->soilc.rho, in->soilc.slope,
-                              in->soilc.aspect, in->soilc.twi, in->soilc.svfa};
-    const char* soiln[13] = {"Smin", "Smax", "gref", "soilb", "Psie", "Vq", "Vm", "Mc", "rho", "slope",
-                             "aspect", "twi", "svfa"};
-    // with a dtm, a terrain plane or the wetness index that is not given gets its buffer here and its values below
-    auto plane = [&](const double* host, int64_t n, const double** dev, const char* name) -> int {
-        if (host || !dtm) return upload(p, host, n, dev, name);
-        void* d = nullptr;
-        if (const int rca = dalloc(p, &d, n * 8)) return rca;
-        *dev = (const double*)d;
-        return MCF_OK;
-    };
-    for (int i = 0; i < 13; ++i)
-        if ((rc = i >= 9 ? plane(soil[i], N, &p->d_soil[i], soiln[i]) : upload(p, soil[i], N, &p->d_soil[i], soiln[i]))) return rc;
-    if ((rc = plane(in->soilc.wsa, N * 8, &p->d_wsa, "wsa"))) return rc;
-    if ((rc = plane(in->soilc.hor, N * 24, &p->d_hor, "hor"))) return rc;
-    if (dtm && (rc = derive_from_dtm(p, in, dtm))) return rc;
-    if (p->af) {
-        if ((rc = upload(p, in->lats, N, &p->d_lats, "lats"))) return rc;
-        if ((rc = upload(p, in->lons, N, &p->d_lons, "lons"))) return rc;
-    }
-    std::vector<double> cpk_sea;     // coarse pressure reduced to sea level (altitude correction)
-    if (p->coarse) {
-        if ((rc = upload(p, in->coarse_rowpos, in->rows, &p->d_crowpos, "coarse_rowpos", false))) return rc;
-        if ((rc = upload(p, in->coarse_colpos, in->cols, &p->d_ccolpos, "coarse_colpos", false))) return rc;
-        if (p->altcorrect) {
-            // R/internal.R:1236-1241: psl = pk / ((293 - 0.0065 zc) / 293)^5.26 on the coarse grid, back up with the
-            // fine elevation after resampling; elevd = resample(dtmc) - dtm
-            const int cr = p->crows, cc = p->ccols;
-            std::vector<double> zc((size_t)cr * cc), elevd((size_t)N), pkfac((size_t)N);
-            for (size_t q = 0; q < zc.size(); ++q) zc[q] = std::isnan(in->coarse_dtm[q]) ? 0.0 : in->coarse_dtm[q];
-            for (int64_t j = 0; j < in->cols; ++j) {
-                const double cp = in->coarse_colpos[j], fc = floor(cp), wx = cp - fc;
-                const int c0 = (int)fc, c1 = c0 + 1 < cc ? c0 + 1 : c0;
-                for (int64_t i = 0; i < in->rows; ++i) {
-                    const double rp = in->coarse_rowpos[i], fr = floor(rp), wy = rp - fr;
-                    const int r0 = (int)fr, r1 = r0 + 1 < cr ? r0 + 1 : r0;
-                    const double top = (1.0 - wx) * zc[(size_t)(r0 + cr * c0)] + wx * zc[(size_t)(r0 + cr * c1)];
-                    const double bot = (1.0 - wx) * zc[(size_t)(r1 + cr * c0)] + wx * zc[(size_t)(r1 + cr * c1)];
-                    const double z = in->fine_dtm[i + p->pitch * j];
-                    elevd[(size_t)(i + in->rows * j)] = ((1.0 - wy) * top + wy * bot) - z;
-                    pkfac[(size_t)(i + in->rows * j)] = pow((293.0 - 0.0065 * z) / 293.0, 5.26);
-                }
-            }
-            if ((rc = upload(p, elevd.data(), N, &p->d_elevd, "elevd", false))) return rc;
-            if ((rc = upload(p, pkfac.data(), N, &p->d_pkfac, "pkfac", false))) return rc;
-            HIP_TRY(hipStreamSynchronize(p->stream));
-            if (in->tsteps > 0 && in->clim.pk) {
-                const int64_t cN = (int64_t)cr * cc;
-                cpk_sea.resize((size_t)(cN * in->tsteps));
-                for (int64_t k = 0; k < in->tsteps; ++k)
-                    for (int64_t q = 0; q < cN; ++q)
-                        cpk_sea[(size_t)(q + cN * k)] = in->clim.pk[q + cN * k] / pow((293.0 - 0.0065 * zc[(size_t)q]) / 293.0, 5.26);
-            }
-        }
-    }
-    int64_t nvalid = 0;
-    for (int64_t j = 0; j < in->cols; ++j)
-        for (int64_t i = 0; i < in->rows; ++i) nvalid += !std::isnan(in->vegp.hgt[i + p->pitch * j]);
-    p->valid_cells = nvalid;
-
-    // ---- solver constants
-    p->g.reqhgt = opt->reqhgt;
-    p->g.reqhgt2 = opt->reqhgt < 0.00001 ? 0.00001 : opt->reqhgt;      // cpp:2246-2247
-    p->g.zref = opt->zref;
-    p->g.hf0p = mcf::hf_pow02(1 / 999.99);   // mincondCpp(leafabs, 999.99, ...) at cpp:1348
-    p->g.hf500p = mcf::hf_pow02(500.0);      // rs capped at 500 (gs <= 0.002), cpp:1321-1323
-    p->g.shadowmask = p->af ? 0 : 1;
-    p->g.dTmx = 0.0;
-    p->hiy = 365 * 24;
-    if (T > 0 && in->obstime.year[0] % 4 == 0) p->hiy = 366 * 24;      // cpp:2171-2172
-
-    // ---- the one global reduction: mean of log(twi)/tfact, cpp:993-1004
-    void* tmp = nullptr;
-    if ((rc = dalloc(p, &tmp, (int64_t)mcf::twi_scratch_doubles() * 8))) return rc;
-    p->d_twi2 = (double*)tmp;
-    mcf::launch_twi_partial(p->d_soil[11], N, opt->tfact, p->d_twi2, p->stream);
-    double h2[2];
-    HIP_TRY(hipMemcpyAsync(h2, p->d_twi2, 16, hipMemcpyDeviceToHost, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    p->twi_sum = h2[0];
-    p->twi_count = (int64_t)h2[1];
-    p->twi_mean = h2[0] / h2[1];
-
-    // per-cell constants, tile-major (mcf_kernels.h CellSetupArgs); zeroed once: the cells past the raster's end in the last
-    // tile's image are read (not used) by the solver
-    p->ntiles = (N + p->cpb - 1) / p->cpb;
-    const int64_t cellc_bytes = (int64_t)p->layers * p->ntiles * mcf::tile_image_doubles(p->cpb) * 8;
-    if ((rc = dalloc(p, &tmp, cellc_bytes))) return rc;
-    p->d_cellc = (double*)tmp;
-    HIP_TRY(hipMemsetAsync(p->d_cellc, 0, (size_t)cellc_bytes, p->stream));
-    if (p->layers > 1) {
-        // day -> layer map from dfsel (cpp:2629-2640, k = dy*24 + hr + st[lyr]); -1 = not covered
-        std::vector<int32_t> dl((size_t)std::max(p->ndays, 1), -1);
-        for (int l = 0; l < p->layers; ++l) {
-            int nd = (in->lyr_ed[l] - in->lyr_st[l] + 1) / 24, d0 = in->lyr_st[l] / 24;
-            for (int d = d0; d < d0 + nd && d < p->ndays; ++d) dl[d] = l;
-        }
-        if ((rc = dalloc(p, &tmp, (int64_t)dl.size() * 4))) return rc;
-        p->d_daylayer = (int32_t*)tmp;
-        p->daylayer0 = dl;
-        HIP_TRY(hipMemcpyAsync(p->d_daylayer, dl.data(), dl.size() * 4, hipMemcpyHostToDevice, p->stream));
-        HIP_TRY(hipStreamSynchronize(p->stream));
-    }
-
-    // ---- time tables
-    const double* raw[15];
-    clim_ptrs(in, raw);
-    for (int f = 0; f < 15; ++f)
-        if (T > 0 && !raw[f] && !(p->coarse && f >= 1 && f <= 3))     // es, ea, tdew are derived in coarse mode
-            return fail(MCF_ERR_ARG, std::string("missing forcing array: ") + kRawNames[f]);
-    if (T > 0 && !p->coarse && !in->clim.winddir) return fail(MCF_ERR_ARG, "missing forcing array: winddir");
-    // coarse mode: wind components per coarse cell and the raster-mean direction per step (R/internal.R:1255-1264)
-    std::vector<double> cwu, cwv, cwd;
-    if (p->coarse && T > 0) {
-        const int64_t cN = (int64_t)p->crows * p->ccols;
-        cwu.resize((size_t)(cN * T)); cwv.resize((size_t)(cN * T)); cwd.resize((size_t)T);
-        for (int64_t k = 0; k < T; ++k) {
-            double su = 0, sv = 0;
-            int64_t nu = 0, nv = 0;
-            for (int64_t q = 0; q < cN; ++q) {
-                const double u2 = in->clim.windspeed[q + cN * k], wd = in->coarse_winddir[q + cN * k] * M_PI / 180.0;
-                const double u = u2 * cos(wd), v = u2 * sin(wd);
-                cwu[(size_t)(q + cN * k)] = u; cwv[(size_t)(q + cN * k)] = v;
-                if (!std::isnan(u)) { su += u; ++nu; }               // apply(wu, 3, mean, na.rm = TRUE)
-                if (!std::isnan(v)) { sv += v; ++nv; }
-            }
-            double d = fmod(atan2(sv / (double)nv, su / (double)nu) * 180.0 / M_PI, 360.0);
-            if (d < 0) d += 360.0;                                    // R's %% takes the sign of the divisor
-            cwd[(size_t)k] = d;
-        }
-    }
-    mcf::DevOwner temps;   // freed after setup
-    auto up_tmp = [&](const void* host, int64_t nbytes, void** dev) -> int {
-        if (nbytes <= 0) nbytes = 8;
-        if (const int rca = temps.alloc(dev, nbytes)) return rca;
-        if (host) HIP_TRY(hipMemcpyAsync(*dev, host, (size_t)nbytes, hipMemcpyHostToDevice, p->stream));
-        return MCF_OK;
-    };
-    void *dy = nullptr, *dm = nullptr, *dd = nullptr, *dh = nullptr, *dw = nullptr;
-    if (T > 0) {
-        if ((rc = up_tmp(in->obstime.year, T * 4, &dy))) return rc;
-        if ((rc = up_tmp(in->obstime.month, T * 4, &dm))) return rc;
-        if ((rc = up_tmp(in->obstime.day, T * 4, &dd))) return rc;
-        if ((rc = up_tmp(in->obstime.hour, T * 8, &dh))) return rc;
-        if ((rc = up_tmp(p->coarse ? cwd.data() : in->clim.winddir, T * 8, &dw))) return rc;
-    }
-    if (!p->af) {
-        double mxtc = -273.15;                                           // cpp:2159-2168
-        for (int64_t k = 0; k < T; ++k)
-            if (in->clim.tc[k] > mxtc) mxtc = in->clim.tc[k];
-        p->g.dTmx = -0.6273 * mxtc + 49.79;                              // cpp:1236
-        if ((rc = dalloc(p, &tmp, (int64_t)std::max(p->ndays, 1) * mcf::time_field_count() * 24 * 8))) return rc;
-        p->d_tt = (double*)tmp;
-        if (p->ndays > 0) {
-            mcf::TimeSetupArgs ta{};
-            ta.nsteps = p->ndays * 24;
-            ta.year = (const int32_t*)dy; ta.month = (const int32_t*)dm; ta.day = (const int32_t*)dd;
-            ta.hour = (const double*)dh; ta.winddir = (const double*)dw;
-            for (int f = 0; f < 15; ++f) {
-                void* q = nullptr;
-                if ((rc = up_tmp(raw[f], T * 8, &q))) return rc;
-                ta.raw[f] = (const double*)q;
-            }
-            ta.lat = in->lat; ta.lon = in->lon;
-            ta.tt = p->d_tt;
-            mcf::launch_time_setup(ta, p->stream);
-            HIP_TRY(hipGetLastError());
-        }
-    } else {
-        if ((rc = dalloc(p, &tmp, std::max<int64_t>(T, 1) * 4 * 8))) return rc;
-        p->d_dt = (double*)tmp;
-        if ((rc = dalloc(p, &tmp, std::max<int64_t>(T, 1) * 4))) return rc;
-        p->d_windex = (int32_t*)tmp;
-        if ((rc = dalloc(p, &tmp, N * 8))) return rc;
-        p->d_mxtc = (double*)tmp;
-        if (T > 0) {
-            mcf::DateSetupArgs da{};
-            da.nsteps = (int)T;
-            da.year = (const int32_t*)dy; da.month = (const int32_t*)dm; da.day = (const int32_t*)dd;
-            da.hour = (const double*)dh; da.winddir = (const double*)dw;
-            da.dt = p->d_dt; da.windex = p->d_windex;
-            mcf::launch_date_setup(da, p->stream);
-            HIP_TRY(hipGetLastError());
-        }
-        if (p->coarse) {
-            // the whole series of the 15 coarse slabs stays resident: [15][crows*ccols][T]
-            const int64_t cN = (int64_t)p->crows * p->ccols, slab = cN * std::max<int64_t>(T, 1);
-            if ((rc = dalloc(p, &tmp, 15 * slab * 8))) return rc;
-            p->d_force = (double*)tmp;
-            const double* src[15];
-            for (int f = 0; f < 15; ++f) src[f] = raw[f];
-            src[1] = in->coarse_relhum;                  // slot TF_ES
-            src[2] = cwv.data();                         // slot TF_EA: v component
-            src[3] = nullptr;                            // slot TF_TDEW unused
-            if (p->altcorrect) src[4] = cpk_sea.data();  // slot TF_PK: sea-level pressure
-            src[8] = cwu.data();                         // slot TF_U2: u component
-            for (int f = 0; f < 15 && T > 0; ++f)
-                if (src[f]) HIP_TRY(hipMemcpyAsync(p->d_force + f * slab, src[f], (size_t)(cN * T * 8), hipMemcpyHostToDevice, p->stream));
-            if (T > 0) {
-                mcf::launch_mxtc_coarse(p->d_force, slab, p->crows, p->ccols, (int)T, p->d_crowpos, p->d_ccolpos, p->rows, N,
-                                        p->altcorrect, p->d_elevd, p->d_pkfac, p->d_mxtc, p->stream);
-                HIP_TRY(hipGetLastError());
-            } else {
-                mcf::launch_fill(p->d_mxtc, N, -273.15, p->stream);
-            }
-            HIP_TRY(hipStreamSynchronize(p->stream));    // cwu / cwv are about to go out of scope
-            p->force_day0.assign(ring_slots, 0);
-            p->force_ndays.assign(ring_slots, p->ndays);
-        } else {
-        // per-cell max air temperature over the WHOLE series (cpp:2467-2471), streamed in slabs
-        mcf::launch_fill(p->d_mxtc, N, -273.15, p->stream);
-        int64_t slab_steps = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(256LL << 20) / (N * 8)));
-        void* dslab = nullptr;
-        if (T > 0) {
-            if ((rc = up_tmp(nullptr, slab_steps * N * 8, &dslab))) return rc;
-            for (int64_t k0 = 0; k0 < T; k0 += slab_steps) {
-                int64_t ns = std::min(slab_steps, T - k0);
-                HIP_TRY(copy_in(p, dslab, in->clim.tc + p->pitch * p->cols * k0, p->cols * ns));
-                mcf::launch_mxtc((const double*)dslab, N, (int)ns, p->d_mxtc, p->stream);
-            }
-            HIP_TRY(hipGetLastError());
-        }
-        // forcing ring, TILED like the output ring: [slots][tile][day][15 series][ring_block_doubles(cpb)] in the solver's lane
-        // order, so that a workgroup's 360 loads per day (15 series x 24 hours, each 8 B x N x hour apart in the caller's
-        // arrays) become whole lines of one contiguous 90 KB run; mcf_plan_upload_forcing_days re-lays each series on the
-        // device behind its host-to-device copy
-        p->ntiles = (N + p->cpb - 1) / p->cpb;
-        p->force_day_stride = 15 * (int64_t)mcf::ring_block_doubles(p->cpb);
-        p->force_tile_stride = (int64_t)ring_days * p->force_day_stride;
-        p->force_slot_elems = p->ntiles * p->force_tile_stride;
-        if ((rc = dalloc(p, &tmp, (int64_t)ring_slots * p->force_slot_elems * 8))) return rc;
-        p->d_force = (double*)tmp;
-        if ((rc = dalloc(p, &tmp, N * (int64_t)ring_days * 24 * 8))) return rc;     // one series of one slot, as uploaded
-        p->d_force_stage = (double*)tmp;
-        p->force_day0.assign(ring_slots, -1);
-        p->force_ndays.assign(ring_slots, 0);
-        }
-    }
-
-    // ---- output ring
-    p->nvars = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) p->var_slot[v] = opt->out[v] ? p->nvars++ : -1;
-    p->tiled = !p->bg || p->bg_stream;
-    p->ntiles = (N + p->cpb - 1) / p->cpb;
-    if (p->tiled) {
-        const int64_t blk = mcf::ring_block_doubles(p->cpb);
-        p->ring_var_stride = blk;
-        p->ring_day_stride = (int64_t)std::max(p->nvars, 1) * blk;
-        p->ring_tile_stride = (int64_t)ring_days * p->ring_day_stride;
-        p->slot_elems = p->ntiles * p->ring_tile_stride;
-    } else {
-        p->slot_elems = (int64_t)std::max(p->nvars, 1) * N * (int64_t)ring_days * 24;
-    }
-    if ((rc = dalloc(p, &tmp, (int64_t)ring_slots * p->slot_elems * 8))) return rc;
-    p->d_ring = (double*)tmp;
-
-    // ---- below ground streamed through day chunks: O(cells x days) of state, no [N][tsteps] buffer
-    if (p->bg_stream && opt->out[MCF_OUT_TZ]) {
-        const int64_t blk = mcf::ring_block_doubles(p->cpb), nd = std::max(p->ndays, 1);
-        p->tg_tile_stride = (int64_t)ring_days * blk;
-        if ((rc = dalloc(p, &tmp, p->ntiles * p->tg_tile_stride * 8))) return rc;
-        p->d_tgring = (double*)tmp;
-        if ((rc = dalloc(p, &tmp, N * 8))) return rc;
-        p->d_ddsum = (double*)tmp;
-        if (opt->complete) {
-            if ((rc = dalloc(p, &tmp, N * 8))) return rc;
-            p->d_hsum = (double*)tmp;
-            if ((rc = dalloc(p, &tmp, N * nd * 8))) return rc;
-            p->d_dmean = (double*)tmp;
-            if ((rc = dalloc(p, &tmp, N * nd * 8))) return rc;
-            p->d_ybuf = (double*)tmp;
-            if ((rc = dalloc(p, &tmp, N * mcf::kBelowWin * 8))) return rc;
-            p->d_wrap = (double*)tmp;
-            if ((rc = dalloc(p, &tmp, N * mcf::kBelowWin * 8))) return rc;
-            p->d_prev = (double*)tmp;
-        } else if (p->af) {
-            // per cell-step: each slot's days, uploaded with its forcing (mcf_plan_upload_forcing_days)
-            const int64_t n = (int64_t)ring_slots * ring_days * 24 * N;
-            if ((rc = dalloc(p, &tmp, n * 8))) return rc;
-            p->d_Tgp_slots = (double*)tmp;
-            if ((rc = dalloc(p, &tmp, n * 8))) return rc;
-            p->d_Tbp_slots = (double*)tmp;
-            if (!in->pointm.Tg || !in->pointm.Tbp) return fail(MCF_ERR_ARG, "missing input array: pointm$Tg / pointm$Tbp");
-        } else {
-            if ((rc = upload(p, in->pointm.Tg, T, &p->d_Tgp, "pointm$Tg", false))) return rc;
-            if ((rc = upload(p, in->pointm.Tbp, T, &p->d_Tbp, "pointm$Tbp", false))) return rc;
-        }
-    }
-    // ---- below-ground series
-    if (p->bg && !p->bg_stream) {
-        if ((rc = dalloc(p, &tmp, N * std::max<int64_t>(T, 1) * 8))) return rc;
-        p->d_tgser = (double*)tmp;
-        // steps past the last whole day read as 0 in the reference (std::vector<double> Tg(tsteps))
-        mcf::launch_fill(p->d_tgser, N * T, 0.0, p->stream);
-        if ((rc = dalloc(p, &tmp, N * 8))) return rc;
-        p->d_ddsum = (double*)tmp;
-        mcf::launch_fill(p->d_ddsum, N, 0.0, p->stream);
-        if ((rc = dalloc(p, &tmp, N * 2 * (int64_t)std::max(p->ndays, 1) * 8))) return rc;
-        p->d_scratch = (double*)tmp;
-        if (!opt->complete) {
-            int64_t n = p->af ? N * T : T;
-            if ((rc = upload(p, in->pointm.Tg, n, &p->d_Tgp, "pointm$Tg", p->af))) return rc;
-            if ((rc = upload(p, in->pointm.Tbp, n, &p->d_Tbp, "pointm$Tbp", p->af))) return rc;
-        }
-    }
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    guard.p = nullptr;
-    *out = p;
+    SetupScratch s;      // (after the holder: on a refusal it goes first, as the set-up temporaries always have)
+    if ((rc = plan_shape(p, in, opt, ring_days, ring_slots, streamed))) return rc;      // (with coarse_check)
+    if ((rc = upload_static(p, in, dtm))) return rc;
+    if ((rc = coarse_planes(p, in, s))) return rc;
+    if ((rc = solver_constants(p, in, opt))) return rc;
+    if ((rc = cell_images(p, in))) return rc;
+    if ((rc = time_inputs(p, in, s))) return rc;      // (with coarse_wind)
+    if ((rc = !p->af ? time_tables_vector(p, in, s) : p->coarse ? time_tables_coarse(p, in, s) : time_tables_fine(p, in, s))) return rc;
+    if ((rc = output_ring(p, opt))) return rc;
+    if ((rc = below_stream_state(p, in, opt))) return rc;
+    if ((rc = below_series_state(p, in, opt))) return rc;
+    HIP_TRY(hipStreamSynchronize(p->stream));      // every queued copy has read its source: s and the caller's arrays are free
+    *out = holder.release();
     return MCF_OK;
 }
 
@@ -1027,12 +1096,12 @@ int mcf_plan_set_mxtc_days(mcf_plan* p, const mcf_grid_inputs* in, const int32_t
         // coarse forcing: the flagged days of the resident series, folded by the day-flagged form of the create-time kernel
         HIP_TRY(hipSetDevice(p->device));
         if (ndays == 0) { mcf::launch_fill(p->d_mxtc, p->N, -273.15, p->stream); return MCF_OK; }
-        void* tmp = nullptr;
-        if (const int rc = dalloc(p, &tmp, (int64_t)ndays * 4)) return rc;
-        struct Release { mcf_plan* p; void* q; ~Release() { p->dev.release(q); } } release{p, tmp};      // on every exit path
-        HIP_TRY(hipMemcpyAsync(tmp, dayflag, (size_t)ndays * 4, hipMemcpyHostToDevice, p->stream));
+        int32_t* d_flag = nullptr;
+        if (const int rc = p->dev.make(&d_flag, ndays)) return rc;
+        struct Release { mcf_plan* p; int32_t* buf; ~Release() { p->dev.release(buf); } } release{p, d_flag};      // on every exit path
+        HIP_TRY(hipMemcpyAsync(d_flag, dayflag, (size_t)ndays * 4, hipMemcpyHostToDevice, p->stream));
         const int64_t slab = (int64_t)p->crows * p->ccols * std::max<int64_t>(p->tsteps, 1);
-        mcf::launch_mxtc_coarse_days(p->d_force, slab, p->crows, p->ccols, (const int32_t*)tmp, ndays, p->d_crowpos, p->d_ccolpos,
+        mcf::launch_mxtc_coarse_days(p->d_force, slab, p->crows, p->ccols, d_flag, ndays, p->d_crowpos, p->d_ccolpos,
                                      p->rows, p->N, p->altcorrect, p->d_elevd, p->d_pkfac, p->d_mxtc, p->stream);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(p->stream));      // (the caller's flags have been read, the kernel has read its copy)
@@ -1419,11 +1488,7 @@ int mcf_plan_below_set_days(mcf_plan* p, const int32_t* days, int32_t n) {
     int rc = mcf_below_days_range(days, n, p->ndays, 0, 0, &pos0, &npos);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    if (!p->d_below_days) {
-        void* q;
-        if ((rc = dalloc(p, &q, (int64_t)std::max(p->ndays, 1) * 4))) return rc;
-        p->d_below_days = (int32_t*)q;
-    }
+    if (!p->d_below_days && (rc = p->dev.make(&p->d_below_days, (int64_t)std::max(p->ndays, 1)))) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->below_days.assign(days, days + n);
     HIP_TRY(hipMemcpy(p->d_below_days, p->below_days.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -1459,15 +1524,10 @@ int mcf_plan_below_set_depths(mcf_plan* p, const double* depths, int32_t ndepths
     int rc = check_depths(who, depths, ndepths, tbp, complete, p->af);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    void* q = nullptr;
     const int64_t extra = ndepths - 1, nd = std::max(p->ndays, 1);
     if (extra > 0) {
-        if ((rc = dalloc(p, &q, extra * p->ring_slots * p->ntiles * p->tg_tile_stride * 8))) return rc;
-        p->d_tzx = (double*)q;
-        if (complete) {
-            if ((rc = dalloc(p, &q, extra * nd * p->N * 8))) return rc;
-            p->d_ybufx = (double*)q;
-        }
+        if ((rc = p->dev.make(&p->d_tzx, extra * p->ring_slots * p->ntiles * p->tg_tile_stride))) return rc;
+        if (complete && (rc = p->dev.make(&p->d_ybufx, extra * nd * p->N))) return rc;
     }
     if (!complete && (rc = upload(p, tbp, (int64_t)ndepths * p->tsteps, &p->d_Tbp_depths, "tbp", false))) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1568,12 +1628,7 @@ int mcf_plan_run_days_masked(mcf_plan* p, int32_t day0, int32_t ndays, int32_t s
     int64_t n_sub_fast = 0, n_sub_slow = 0;
     if (skip_tile) {
         const int64_t ntiles = p->ntiles;
-        if (p->tiles_sub_cap < ntiles) {
-            void* q;
-            if ((rc = dalloc(p, &q, ntiles * 4))) return rc;
-            p->d_tiles_sub = (int32_t*)q;
-            p->tiles_sub_cap = ntiles;
-        }
+        if (!p->d_tiles_sub && (rc = p->dev.make(&p->d_tiles_sub, ntiles))) return rc;
         // (the lists live in the plan: they go up on the plan's own stream, in order with the launches that read them, and an
         // earlier masked launch may still be reading the device copy or an earlier copy the host one)
         HIP_TRY(hipStreamSynchronize(p->stream));
@@ -1629,8 +1684,8 @@ int mcf_plan_run_days_cells(mcf_plan* p, int32_t day0, int32_t ndays, int32_t sl
     const double t0 = now();
     if (p->cells_inflight) { HIP_TRY(hipEventSynchronize(p->ev_cells_done)); p->cells_inflight = false; }
     const double t1 = now();
-    if ((rc = dregrow(p, (void**)&p->d_cls, &p->cls_cap, N))) return rc;
-    if ((rc = dregrow(p, (void**)&p->d_blockcnt, &p->blockcnt_cap, nb * 8))) return rc;
+    if ((rc = p->dev.regrow(&p->d_cls, &p->cls_cap, N))) return rc;
+    if ((rc = p->dev.regrow(&p->d_blockcnt, &p->blockcnt_cap, nb * 2))) return rc;
     // 1. the wanted cells by class, counted per 256 cells; the list offsets are the host's prefix sums of those counts
     mcf::launch_cells_class(need_cell, p->fast_enabled ? p->d_tile_regular : nullptr, N, cpb, p->d_cls, p->d_blockcnt, p->prep);
     HIP_TRY(hipGetLastError());
@@ -1657,15 +1712,15 @@ int mcf_plan_run_days_cells(mcf_plan* p, int32_t day0, int32_t ndays, int32_t sl
         }
     }
     // (buffers that grow are released first: hipFree waits for the device)
-    if ((rc = dregrow(p, (void**)&p->d_celllist, &p->celllist_cap, total * 4))) return rc;
-    if ((rc = dregrow(p, (void**)&p->d_subimg, &p->subimg_cap, (int64_t)p->layers * nt_sub * IMG * 8))) return rc;
+    if ((rc = p->dev.regrow(&p->d_celllist, &p->celllist_cap, total))) return rc;
+    if ((rc = p->dev.regrow(&p->d_subimg, &p->subimg_cap, (int64_t)p->layers * nt_sub * IMG))) return rc;
     const int64_t day_doubles = p->ring_day_stride;                  // variables x block
     const double budget_gb = getenv("MCF_CELLS_RING_GB") ? atof(getenv("MCF_CELLS_RING_GB")) : 0.0;
     const int64_t budget = budget_gb > 0.0 ? (int64_t)(budget_gb * 1e9)
                                            : std::max<int64_t>((int64_t)512 << 20, (int64_t)p->ring_slots * p->slot_elems);       // (bytes: an eighth of the ring)
     const int pass_days = (int)std::max<int64_t>(1, std::min<int64_t>(ndays, budget / (nt_sub * day_doubles * 8)));
-    if ((rc = dregrow(p, (void**)&p->d_subring, &p->subring_cap, nt_sub * pass_days * day_doubles * 8))) return rc;
-    if (nt_slow > 0 && fast && (rc = dregrow(p, (void**)&p->d_cells_slow, &p->cells_slow_cap, nt_slow * 4))) return rc;
+    if ((rc = p->dev.regrow(&p->d_subring, &p->subring_cap, nt_sub * pass_days * day_doubles))) return rc;
+    if (nt_slow > 0 && fast && (rc = p->dev.regrow(&p->d_cells_slow, &p->cells_slow_cap, nt_slow))) return rc;
     const double t3 = now();
     HIP_TRY(hipMemcpyAsync(p->d_blockcnt, cnt.data(), (size_t)nb * 8, hipMemcpyHostToDevice, p->prep));
     HIP_TRY(hipMemsetAsync(p->d_celllist, 0xFF, (size_t)total * 4, p->prep));         // -1: no cell (a class's last tile)
@@ -1762,8 +1817,34 @@ int mcf_plan_fetch(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_
     return mcf_plan_fetch_pitched(p, slot, var, step0, nsteps, host_dst, 0);
 }
 
+// `bytes` of dense [rows, ...] device memory into the caller's array (a block of a taller raster goes column by column into its place)
+static int to_host(mcf_plan* p, double* dst, const double* src, size_t bytes, int64_t row_pitch) {
+    const size_t width = (size_t)p->rows * 8;
+    if (row_pitch != p->rows) HIP_TRY(p->tohost.pitched(dst, (size_t)row_pitch * 8, src, width, bytes / width, p->stream));
+    else HIP_TRY(p->tohost.dense(dst, src, bytes, p->stream));
+    return MCF_OK;
+}
 // steps [step0, step0 + nsteps) of `view` (a variable of the output ring, a diagnostic of the diagnostics ring) to the host
-static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch);
+static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
+    HIP_TRY(hipSetDevice(p->device));
+    if (nsteps == 0) return MCF_OK;
+    if (!tiled) return to_host(p, host_dst, view.base + p->N * step0, (size_t)(p->N * nsteps) * 8, row_pitch);
+    // tiled ring: the reference's [rows, cols, steps] layout is made on the device (k_untile), in pieces of <= 1 GB
+    const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(nsteps, ((int64_t)1 << 27) / std::max<int64_t>(p->N, 1)));
+    if (p->stage_elems < piece * p->N) {
+        double* d = nullptr;
+        if (const int rc = p->dev.make(&d, piece * p->N)) return rc;      // an earlier (smaller) buffer is released with the plan
+        p->d_stage = d;
+        p->stage_elems = piece * p->N;
+    }
+    for (int64_t k0 = 0; k0 < nsteps; k0 += piece) {
+        const int64_t n = std::min(piece, nsteps - k0);
+        mcf::launch_untile(view, step0 + k0, n, p->d_stage, p->stream);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = to_host(p, host_dst + row_pitch * p->cols * k0, p->d_stage, (size_t)(p->N * n) * 8, row_pitch)) return rc;
+    }
+    return MCF_OK;
+}
 
 int mcf_plan_fetch_pitched(mcf_plan* p, int32_t slot, int32_t var, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
@@ -1782,36 +1863,6 @@ static int diag_fetch_pitched(mcf_plan* p, int32_t slot, int32_t dvar, int64_t s
 }
 int mcf_plan_diag_fetch(mcf_plan* p, int32_t slot, int32_t dvar, int64_t step0, int64_t nsteps, double* host_dst) {
     return diag_fetch_pitched(p, slot, dvar, step0, nsteps, host_dst, 0);
-}
-
-static int fetch_view(mcf_plan* p, const mcf::RingView& view, bool tiled, int64_t step0, int64_t nsteps, double* host_dst, int64_t row_pitch) {
-    HIP_TRY(hipSetDevice(p->device));
-    if (nsteps == 0) return MCF_OK;
-    // (a block of a taller raster goes column by column into its place)
-    auto to_host = [&](double* dst, const double* src, size_t bytes) -> int {
-        const size_t width = (size_t)p->rows * 8;
-        if (row_pitch != p->rows) HIP_TRY(p->tohost.pitched(dst, (size_t)row_pitch * 8, src, width, bytes / width, p->stream));
-        else HIP_TRY(p->tohost.dense(dst, src, bytes, p->stream));
-        return MCF_OK;
-    };
-    if (!tiled) return to_host(host_dst, view.base + p->N * step0, (size_t)(p->N * nsteps) * 8);
-    // tiled ring: the reference's [rows, cols, steps] layout is made on the device (k_untile), in pieces of <= 1 GB
-    const int64_t piece = std::max<int64_t>(1, std::min<int64_t>(nsteps, ((int64_t)1 << 27) / std::max<int64_t>(p->N, 1)));
-    if (p->stage_elems < piece * p->N) {
-        int rc;
-        void* q;
-        if ((rc = dalloc(p, &q, piece * p->N * 8))) return rc;      // an earlier (smaller) buffer is released with the plan
-        p->d_stage = (double*)q;
-        p->stage_elems = piece * p->N;
-    }
-    for (int64_t k0 = 0; k0 < nsteps; k0 += piece) {
-        const int64_t n = std::min(piece, nsteps - k0);
-        mcf::launch_untile(view, step0 + k0, n, p->d_stage, p->stream);
-        HIP_TRY(hipGetLastError());
-        int rc = to_host(host_dst + row_pitch * p->cols * k0, p->d_stage, (size_t)(p->N * n) * 8);
-        if (rc) return rc;
-    }
-    return MCF_OK;
 }
 
 int mcf_plan_fetch_depth_pitched(mcf_plan* p, int32_t slot, int32_t depth, int64_t step0, int64_t nsteps, double* host_dst,
@@ -1860,10 +1911,9 @@ int mcf_plan_fetch_packed(mcf_plan* p, int32_t slot, int32_t var, int64_t step0,
     if (nsteps > 65535) return fail(MCF_ERR_ARG, "at most 65535 steps per packed fetch");
     HIP_TRY(hipSetDevice(p->device));
     if (p->pack_elems < p->N * nsteps) {
-        int rc;
-        void* q;
-        if ((rc = dalloc(p, &q, p->N * nsteps * 4))) return rc;     // earlier (smaller) buffers are released with the plan
-        p->d_pack = (int32_t*)q;
+        int32_t* d = nullptr;
+        if (const int rc = p->dev.make(&d, p->N * nsteps)) return rc;     // earlier (smaller) buffers are released with the plan
+        p->d_pack = d;
         p->pack_elems = p->N * nsteps;
     }
     if (kernel_ms) HIP_TRY(hipEventRecord(p->ev0, p->stream));
@@ -1971,10 +2021,9 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
     int64_t piece = std::min<int64_t>(65535 / a.nv, std::max<int64_t>(1, ((int64_t)256 << 20) / rb));
     piece = std::min(piece, std::max<int64_t>(nsteps, 1));
     if (p->pack_elems < piece * (rb / 4)) {
-        int rc;
-        void* q;
-        if ((rc = dalloc(p, &q, piece * rb))) return rc;
-        p->d_pack = (int32_t*)q;
+        int32_t* d = nullptr;
+        if (const int rc = p->dev.make(&d, piece * (rb / 4))) return rc;
+        p->d_pack = d;
         p->pack_elems = piece * (rb / 4);
     }
     a.dst = p->d_pack;
@@ -2054,9 +2103,7 @@ int mcf_plan_diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
     HIP_TRY(hipSetDevice(p->device));
     const int64_t blk = mcf::ring_block_doubles(p->cpb);
     const int64_t day_stride = (int64_t)n * blk, tile_stride = (int64_t)p->ring_days * day_stride, slot_elems = p->ntiles * tile_stride;
-    void* q = nullptr;
-    if (const int rc = dalloc(p, &q, (int64_t)p->ring_slots * slot_elems * 8)) return rc;
-    p->d_dring = (double*)q;
+    if (const int rc = p->dev.make(&p->d_dring, (int64_t)p->ring_slots * slot_elems)) return rc;
     p->dg_day_stride = day_stride; p->dg_tile_stride = tile_stride; p->dg_slot_elems = slot_elems;
     p->ndiag = 0;
     for (int v = 0; v < MCF_NDIAG; ++v) p->dg_slab1[v] = sel[v] ? ++p->ndiag : 0;
@@ -2223,32 +2270,22 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
         for (int j = 1; j < nq[i]; ++j)
             if (q[i][j] < q[i][j - 1]) streamed = false;
     int chunk_days = ndays;
-    if (streamed) {
-        const int cpb = in->array_forcing == 2 ? 32 : opt.cells_per_block ? opt.cells_per_block : 21;     // mcf_plan_create's tiles
-        const double day_bytes = 2.0 * 8.0 * (double)((N + cpb - 1) / cpb) * (double)mcf::ring_block_doubles(cpb);
-        const char* e = getenv("MCF_BIOCLIM_RING_GB");
-        const double budget = (e && atof(e) > 0.0 ? atof(e) : 14.0) * 1e9;     // (4096^2: 0.80 s with 14 GB = two-day chunks, 0.85 s with 8, 2.3 s with 27 — the allocation; profiles/r05_sink_rates.txt)
-        chunk_days = (int)std::max(1.0, std::min((double)ndays, floor(budget / day_bytes)));
+    if (streamed) {      // the ring of the two variables, on mcf_plan_create's tiles
+        const int cpb = in->array_forcing == 2 ? 32 : opt.cells_per_block ? opt.cells_per_block : 21;
+        chunk_days = std::min(ndays, ring_budget_days("MCF_BIOCLIM_RING_GB", 2, N, cpb));
     }
     mcf_plan* p = nullptr;
     if ((rc = mcf_plan_create(in, &opt, chunk_days, 1, &p))) return rc;
-    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    PlanHolder holder(p);
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if (streamed && p->tiled) {
-        void* tmp = nullptr;
         mcf::BioAccArgs acc{};
         acc.N = N;
         acc.tz = ring_view(p, 0, tvar); acc.soilm = ring_view(p, 0, MCF_OUT_SOILM);
-        for (int i = 0; i < 4; ++i) {
-            if ((rc = dalloc(p, &tmp, (int64_t)std::max(nq[i], 1) * 4))) return rc;
-            if (nq[i] > 0) HIP_TRY(hipMemcpyAsync(tmp, q[i], (size_t)nq[i] * 4, hipMemcpyHostToDevice, p->stream));
-            acc.q[i] = (const int32_t*)tmp;
-        }
-        if ((rc = dalloc(p, &tmp, (int64_t)mcf::kBioStateRows * N * 8))) return rc;
-        acc.state = (double*)tmp;
-        for (int d0 = 0; d0 < ndays; d0 += p->ring_days) {
-            const int nd = std::min(p->ring_days, ndays - d0);
-            if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+        if ((rc = upload_quarters(p, q, nq, acc.q))) return rc;
+        if ((rc = p->dev.make(&acc.state, (int64_t)mcf::kBioStateRows * N))) return rc;
+        // (the streamed route takes vector or coarse forcing: the driver has no forcing to upload)
+        rc = for_day_chunks(p, in, ndays, p->ring_days, [&](int d0, int nd) -> int {
             ++g_bioclim_chunks;
             acc.day0 = d0; acc.ndays = nd;
             for (int i = 0; i < 4; ++i) {
@@ -2257,7 +2294,9 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
             }
             mcf::launch_bioclim_acc(acc, p->stream);
             HIP_TRY(hipGetLastError());
-        }
+            return MCF_OK;
+        });
+        if (rc) return rc;
         mcf::BioFinArgs fin{};
         fin.N = N; fin.tsteps = (int)T; fin.state = acc.state;
         fin.cellc = p->d_cellc; fin.ntiles_total = p->ntiles; fin.cpb = p->cpb; fin.daylayer = p->d_daylayer; fin.tt = p->d_tt;
@@ -2268,8 +2307,7 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
             fin.crows = p->crows; fin.ccols = p->ccols;
             fin.crowpos = p->d_crowpos; fin.ccolpos = p->d_ccolpos; fin.rows = (int32_t)p->rows;
         }
-        if ((rc = dalloc(p, &tmp, (int64_t)MCF_NBIO * N * 8))) return rc;
-        fin.bio = (double*)tmp;
+        if ((rc = p->dev.make(&fin.bio, (int64_t)MCF_NBIO * N))) return rc;
         mcf::launch_bioclim_fin(fin, p->stream);
         HIP_TRY(hipGetLastError());
         return bioclim_download(p, in, sel, out, fin.bio, out_pitch);
@@ -2278,19 +2316,14 @@ static int run_bioclim(const mcf_grid_inputs* in_caller, const mcf_options* opt_
     if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, 0, ndays, 0))) return rc;
     if ((rc = mcf_plan_run_days(p, 0, ndays, 0))) return rc;
     if (p->bg && (rc = mcf_plan_belowground(p))) return rc;
-    void* tmp = nullptr;
     mcf::BioclimArgs b{};
     b.N = N; b.tsteps = (int)T;
     b.tz = ring_view(p, 0, tvar); b.soilm = ring_view(p, 0, MCF_OUT_SOILM);
-    const int32_t** dq[4] = {&b.wetq, &b.dryq, &b.hotq, &b.colq};
+    const int32_t* dq[4];
+    if ((rc = upload_quarters(p, q, nq, dq))) return rc;
+    b.wetq = dq[0]; b.dryq = dq[1]; b.hotq = dq[2]; b.colq = dq[3];
     b.nwet = nq[0]; b.ndry = nq[1]; b.nhot = nq[2]; b.ncol = nq[3];
-    for (int i = 0; i < 4; ++i) {
-        if ((rc = dalloc(p, &tmp, (int64_t)std::max(nq[i], 1) * 4))) return rc;
-        if (nq[i] > 0) HIP_TRY(hipMemcpyAsync(tmp, q[i], (size_t)nq[i] * 4, hipMemcpyHostToDevice, p->stream));
-        *dq[i] = (const int32_t*)tmp;
-    }
-    if ((rc = dalloc(p, &tmp, (int64_t)MCF_NBIO * N * 8))) return rc;
-    b.bio = (double*)tmp;
+    if ((rc = p->dev.make(&b.bio, (int64_t)MCF_NBIO * N))) return rc;
     mcf::launch_bioclim(b, p->stream);
     HIP_TRY(hipGetLastError());
     return bioclim_download(p, in, sel, out, b.bio, out_pitch);
@@ -2371,19 +2404,16 @@ static int summary_enable_checked(mcf_plan* p, const mcf_summary_spec* spec, int
         if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
         last[(size_t)per] = d;
     }
-    void* q = nullptr;
     int32_t** tabs[3] = {&p->d_sum_pod, &p->d_sum_prev, &p->d_sum_next};
     const std::vector<int32_t>* host[3] = {&pod, &prev, &next};
     for (int i = 0; i < 3; ++i) {
-        if ((rc = dalloc(p, &q, nd * 4))) return rc;
-        HIP_TRY(hipMemcpy(q, host[i]->data(), (size_t)nd * 4, hipMemcpyHostToDevice));
-        *tabs[i] = (int32_t*)q;
+        if ((rc = p->dev.make(tabs[i], nd))) return rc;
+        HIP_TRY(hipMemcpy(*tabs[i], host[i]->data(), (size_t)nd * 4, hipMemcpyHostToDevice));
     }
-    if ((rc = dalloc(p, &q, np * 4))) return rc;
-    p->d_sum_days = (int32_t*)q;
-    if ((rc = dalloc(p, &q, plane_bytes))) return rc;
-    p->d_sum_plane = (double*)q;
-    if ((rc = dalloc(p, &q, state_bytes))) return rc;
+    if ((rc = p->dev.make(&p->d_sum_days, np))) return rc;
+    if ((rc = p->dev.make(&p->d_sum_plane, plane_bytes / 8))) return rc;
+    double* state = nullptr;      // (the plan gets it last: d_sum_state says that the summary is on)
+    if ((rc = p->dev.make(&state, state_bytes / 8))) return rc;
     p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_nsel = nsel; p->sum_nmain = nmain; p->sum_init_codes = codes;
     for (int k = 0; k < MCF_NSTAT; ++k) p->sum_row[k] = row[k];
     int place = 0;
@@ -2392,7 +2422,7 @@ static int summary_enable_checked(mcf_plan* p, const mcf_summary_spec* spec, int
         p->sum_thr[v] = spec->var[v] && spec->stat[MCF_STAT_HOURS_ABOVE] ? spec->threshold[v] : 0.0;
     }
     p->sum_pod = std::move(pod);
-    p->d_sum_state = (double*)q;
+    p->d_sum_state = state;
     return mcf_plan_summary_reset(p);
 }
 
@@ -2505,10 +2535,7 @@ static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double*
     f.days = p->d_sum_days; f.out = p->d_sum_plane;
     mcf::launch_summary_fin(f, p->stream);
     HIP_TRY(hipGetLastError());
-    const size_t width = (size_t)p->rows * 8, bytes = (size_t)(p->N * p->sum_nperiods) * 8;
-    if (row_pitch != p->rows) HIP_TRY(p->tohost.pitched(host_dst, (size_t)row_pitch * 8, p->d_sum_plane, width, bytes / width, p->stream));
-    else HIP_TRY(p->tohost.dense(host_dst, p->d_sum_plane, bytes, p->stream));
-    return MCF_OK;
+    return to_host(p, host_dst, p->d_sum_plane, (size_t)(p->N * p->sum_nperiods) * 8, row_pitch);
 }
 int mcf_plan_summary_fetch(mcf_plan* p, int32_t var, int32_t stat, double* host_dst) {
     return summary_fetch_pitched(p, var, stat, host_dst, 0);
@@ -2581,26 +2608,17 @@ static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, con
     if ((rc = ensure_device(opt.device))) return rc;
     const int64_t N = in->rows * in->cols;
     int chunk = chunk_days;
-    if (chunk == 0) {
-        // the ring (and, array forcing, its forcing ring) from a byte budget, as run_bioclim sizes its ring
-        const int cpb = opt.cells_per_block ? opt.cells_per_block : 21;
-        const double day_bytes = 8.0 * (nsel + (in->array_forcing == 1 ? 15 : 0)) * (double)((N + cpb - 1) / cpb) * (double)mcf::ring_block_doubles(cpb);
-        const char* e = getenv("MCF_SUMMARY_RING_GB");
-        const double budget = (e && atof(e) > 0.0 ? atof(e) : 14.0) * 1e9;
-        chunk = (int)std::max(1.0, floor(budget / day_bytes));
-    }
+    // the ring of the selected variables (and, fine array forcing, the forcing ring's 15 series) from the byte budget
+    if (chunk == 0)
+        chunk = ring_budget_days("MCF_SUMMARY_RING_GB", nsel + (in->array_forcing == 1 ? 15 : 0), N,
+                                 opt.cells_per_block ? opt.cells_per_block : 21);
     chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
     mcf_plan* p = nullptr;
     if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
-    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    PlanHolder holder(p);
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if ((rc = mcf_plan_summary_enable(p, spec))) return rc;
-    for (int d0 = 0; d0 < ndays; d0 += chunk) {
-        const int nd = std::min(chunk, ndays - d0);
-        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
-        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
-        if ((rc = mcf_plan_summary_accumulate(p, 0, 0, d0, nd))) return rc;
-    }
+    if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return mcf_plan_summary_accumulate(p, 0, 0, d0, nd); }))) return rc;
     for (int v = 0; v < MCF_NOUT; ++v)
         for (int k = 0; k < MCF_NSTAT; ++k)
             if (spec->var[v] && spec->stat[k] && (rc = summary_fetch_pitched(p, v, k, out->val[v][k], out_pitch))) return rc;
@@ -2613,19 +2631,6 @@ int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, cons
 }
 
 // ---- below ground at several depths from one solve (include/mcf.h mcf_runmicro_depths) ----------------------
-// The chunk of a streamed run from free device memory, as run_oneshot's streamed branch sizes it, with the D - 1 depth slabs
-// per day and their rows of circular means counted.
-static int depths_chunk_days(const mcf_grid_inputs* in, const mcf_options* opt, int nvars, int D, int ndays, bool tail, int* chunk) {
-    size_t fr = 0, tot = 0;
-    HIP_TRY(hipMemGetInfo(&fr, &tot));
-    const int64_t N = in->rows * in->cols;
-    const double per_day = (double)N * 24 * 8 * (nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1));
-    const double budget = 0.6 * (double)fr - (double)N * 8 * 200 - (double)N * 8 * ((1.0 + D) * ndays + 2 * mcf::kBelowWin + 2) -
-                          (tail ? per_day : 0.0);
-    *chunk = std::min((int)std::max(1.0, std::min((double)std::max(ndays, 1), budget / std::max(per_day, 1.0))), 64);
-    return MCF_OK;
-}
-
 // both one-call entries: `out` (every step of every depth) or `spec` + `sout` (the period summaries)
 static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
                       const double* tbp, mcf_depth_outputs* out, const mcf_summary_spec* spec, int32_t chunk_days,
@@ -2664,30 +2669,28 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     const int nvars = 1 + opt.out[MCF_OUT_SOILM];
     const bool tail = T > (int64_t)ndays * 24;      // the steps behind the last whole day: one day more per slot
     int chunk = out ? opt.days_per_chunk : chunk_days;
-    if (chunk <= 0 && (rc = depths_chunk_days(in, &opt, nvars, D, ndays, tail, &chunk))) return rc;
+    // (the solver's variables, the forcing ring, the chunk's Tg ring and the D - 1 depth slabs per day)
+    if (chunk <= 0 && (rc = free_memory_chunk_days(in->rows * in->cols, ndays, 1, nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1),
+                                                   below_state_doubles(D, ndays), tail, &chunk)))
+        return rc;
     chunk = std::max(1, std::min(chunk, ndays));
     mcf_plan* p = nullptr;
     if ((rc = plan_create(in, &opt, chunk + (tail ? 1 : 0), 1, true, &p, nullptr))) return rc;
-    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    PlanHolder holder(p);
     if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
     if ((rc = mcf_plan_below_prepare(p, in))) return rc;
     if (sout && (rc = mcf_plan_summary_enable_below(p, spec))) return rc;
-    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows, HS = pitch * in->cols;
-    for (int d0 = 0; d0 < ndays; d0 += chunk) {
-        const int nd = std::min(chunk, ndays - d0);
-        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
-        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
-        if (sout) {
-            if ((rc = mcf_plan_summary_accumulate(p, 0, 0, d0, nd))) return rc;
-            continue;
-        }
+    const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
+    rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
+        if (sout) return mcf_plan_summary_accumulate(p, 0, 0, d0, nd);
         // ... the last chunk with the steps it left behind its days
         const int64_t steps = (int64_t)nd * 24 + (d0 + nd == ndays ? T - (int64_t)ndays * 24 : 0);
         for (int d = 0; d < D; ++d)
-            if ((rc = mcf_plan_fetch_depth_pitched(p, 0, d, 0, steps, out->tz[d] + HS * (int64_t)d0 * 24, pitch))) return rc;
-        if (out->soilm && (rc = mcf_plan_fetch_pitched(p, 0, MCF_OUT_SOILM, 0, (int64_t)nd * 24, out->soilm + HS * (int64_t)d0 * 24, pitch)))
-            return rc;
-    }
+            if (const int rcf = mcf_plan_fetch_depth_pitched(p, 0, d, 0, steps, out->tz[d] + HS * (int64_t)d0 * 24, pitch)) return rcf;
+        if (!out->soilm) return MCF_OK;
+        return mcf_plan_fetch_pitched(p, 0, MCF_OUT_SOILM, 0, (int64_t)nd * 24, out->soilm + HS * (int64_t)d0 * 24, pitch);
+    });
+    if (rc) return rc;
     if (sout) {
         for (int k = 0; k < MCF_NSTAT; ++k) {
             if (!spec->stat[k]) continue;
@@ -2698,12 +2701,7 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
         if (sout->days && (rc = mcf_plan_summary_days(p, sout->days))) return rc;
         return mcf_plan_sync(p);
     }
-    if (out->soilm) {      // steps past the last whole day are never computed by the reference and stay NA (cpp:2116)
-        const double na = mcf::na_real_host();
-        for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
-            for (int64_t j = 0; j < in->cols; ++j)
-                for (int64_t i = 0; i < in->rows; ++i) out->soilm[i + pitch * j + HS * k] = na;
-    }
+    if (out->soilm) fill_tail_na(out->soilm, in, ndays);
     return mcf_plan_sync(p);
 }
 int mcf_runmicro_depths(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths, const double* tbp,
@@ -2744,11 +2742,10 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
         return fail(MCF_ERR_ARG, want_af ? "mcf_runmicro2 needs array_forcing = 1" : "mcf_runmicro1 needs array_forcing = 0");
     for (int v = 0; v < MCF_NOUT; ++v)
         if (opt->out[v] && !out->var[v]) return fail(MCF_ERR_ARG, "requested output has a null buffer");
-    rc = ensure_device(opt->device);
-    if (rc) return rc;
+    if ((rc = ensure_device(opt->device))) return rc;
     const int64_t N = in->rows * in->cols, T = in->tsteps;
     // host arrays may be row blocks of a taller raster (row_pitch): a time step of an output is then pitch x cols values on
-    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows, HS = pitch * in->cols;
+    const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
     const int ndays = (int)(T / 24);
     int nvars = 0;
     for (int v = 0; v < MCF_NOUT; ++v) nvars += opt->out[v] ? 1 : 0;
@@ -2774,47 +2771,40 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     if (bg) {
         chunk = std::max(ndays, 1);
     } else if (chunk <= 0) {
-        size_t fr = 0, tot = 0;
-        HIP_TRY(hipMemGetInfo(&fr, &tot));
-        double per_day = (double)N * 24 * 8 * (nvars + ndiag + (in->array_forcing ? 15 : 0));
-        double budget = 0.6 * (double)fr / std::max(sharers, 1) - (double)N * 8 * 200;
-        if (stream_bg) {      // the chunk's Tg ring (and, array forcing with complete = 0, the point model's Tg / Tbp), the per-cell state
-            per_day += (double)N * 24 * 8 * (1 + (in->array_forcing == 1 && !opt->complete ? 2 : 0));
-            budget -= (double)N * 8 * (2.0 * ndays + 2 * mcf::kBelowWin + 2) + (tail ? per_day : 0.0);
-        }
-        chunk = (int)std::max(1.0, std::min((double)std::max(ndays, 1), budget / std::max(per_day, 1.0)));
-        chunk = std::min(chunk, 64);
+        // the solver's variables and the forcing ring; streamed below ground the chunk's Tg ring (and, array forcing with
+        // complete = 0, the point model's Tg / Tbp) and the per-cell state of one depth
+        const int slabs = nvars + ndiag + (in->array_forcing ? 15 : 0) +
+                          (stream_bg ? 1 + (in->array_forcing == 1 && !opt->complete ? 2 : 0) : 0);
+        if ((rc = free_memory_chunk_days(N, ndays, sharers, slabs, stream_bg ? below_state_doubles(1, ndays) : 0.0, tail, &chunk)))
+            return rc;
     }
     chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
     const bool timing = getenv("MCF_TIMING") != nullptr;
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now(), t_solve = 0, t_fetch = 0;
     mcf_plan* p = nullptr;
-    rc = plan_create(in, opt, stream_bg ? chunk + (tail ? 1 : 0) : chunk, 1, stream_bg, &p, dtm);
-    if (rc) return rc;
-    struct Guard { mcf_plan* p; ~Guard() { mcf_plan_destroy(p); } } guard{p};
+    if ((rc = plan_create(in, opt, stream_bg ? chunk + (tail ? 1 : 0) : chunk, 1, stream_bg, &p, dtm))) return rc;
+    PlanHolder holder(p);
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if (stream_bg && (rc = mcf_plan_below_prepare(p, in))) return rc;
     if (dsel && (rc = mcf_plan_diag_enable(p, dsel))) return rc;
     double t_create = now() - t0;
-    for (int d0 = 0; d0 < ndays; d0 += chunk) {
-        int nd = std::min(chunk, ndays - d0);
-        if (in->array_forcing && (rc = mcf_plan_upload_forcing_days(p, in, d0, nd, 0))) return rc;
-        double ta = now();
-        if ((rc = mcf_plan_run_days(p, d0, nd, 0))) return rc;
+    // the timing split: the driver's half (a chunk's forcing upload and its days, synchronised) and the sink's half (its fetches)
+    double ta = now();
+    rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
         if (timing) { mcf_plan_sync(p); t_solve += now() - ta; ta = now(); }
-        if (!bg) {
-            for (int v = 0; v < MCF_NOUT; ++v)
-                if (opt->out[v])
-                    if ((rc = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, out->var[v] + HS * (int64_t)d0 * 24, pitch)))
-                        return rc;
-            for (int v = 0; dsel && v < MCF_NDIAG; ++v)
-                if (dsel[v])
-                    if ((rc = diag_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, dout->var[v] + HS * (int64_t)d0 * 24, pitch)))
-                        return rc;
-        }
-        if (timing) t_fetch += now() - ta;
-    }
+        for (int v = 0; !bg && v < MCF_NOUT; ++v)
+            if (opt->out[v])
+                if (const int rcf = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, out->var[v] + HS * (int64_t)d0 * 24, pitch))
+                    return rcf;
+        for (int v = 0; !bg && dsel && v < MCF_NDIAG; ++v)
+            if (dsel[v])
+                if (const int rcf = diag_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, dout->var[v] + HS * (int64_t)d0 * 24, pitch))
+                    return rcf;
+        if (timing) { t_fetch += now() - ta; ta = now(); }
+        return MCF_OK;
+    });
+    if (rc) return rc;
     if (timing)
         fprintf(stderr, "[mcf] one-shot: chunk %d days%s, plan create %.3f s, solve %.3f s, fetch %.3f s\n", chunk,
                 stream_bg ? " (below ground streamed)" : "", t_create, t_solve, t_fetch);
@@ -2823,18 +2813,10 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
             if (opt->out[v] && v != MCF_OUT_TZ)
                 if ((rc = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)ndays * 24, out->var[v], pitch))) return rc;
     }
-    // steps past the last whole day are never computed by the reference and stay NA (cpp:2116)
-    const double na = mcf::na_real_host();
     for (int v = 0; v < MCF_NOUT; ++v)
-        if (opt->out[v])
-            for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
-                for (int64_t j = 0; j < in->cols; ++j)
-                    for (int64_t i = 0; i < in->rows; ++i) out->var[v][i + pitch * j + HS * k] = na;
+        if (opt->out[v]) fill_tail_na(out->var[v], in, ndays);
     for (int v = 0; dsel && v < MCF_NDIAG; ++v)
-        if (dsel[v])
-            for (int64_t k = (int64_t)ndays * 24; k < T; ++k)
-                for (int64_t j = 0; j < in->cols; ++j)
-                    for (int64_t i = 0; i < in->rows; ++i) dout->var[v][i + pitch * j + HS * k] = na;
+        if (dsel[v]) fill_tail_na(dout->var[v], in, ndays);
     if (bg && opt->out[MCF_OUT_TZ] && T > 0) {
         // Tbelowgroundv runs over all tsteps (cpp:2314-2319)
         if ((rc = mcf_plan_belowground(p))) return rc;
@@ -2858,7 +2840,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
 // kernels a single-device plan uses, and installed in every block's plan: the result is bit for bit the single-device one.
 // Host arrays are not copied: a block reads and writes its rows in place through the row pitch.
 static std::vector<std::pair<int64_t, int64_t>> row_blocks(const mcf_grid_inputs* in, int nb) {
-    const int64_t R = in->rows, pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
+    const int64_t R = in->rows, pitch = host_pitch(in);
     const int64_t mult = R / 10 >= nb ? 10 : 1, ng = (R + mult - 1) / mult;
     std::vector<double> cum((size_t)ng + 1, 0.0);
     for (int64_t j = 0; j < in->cols; ++j)
@@ -2907,7 +2889,7 @@ static int for_row_blocks(const mcf_grid_inputs* in_caller, const mcf_options* o
     mcf::RestoreDevice restore_dev;          // (the twi reduction below runs on the first device)
     int nb = mu->n_blocks > 0 ? mu->n_blocks : (int)devs.size();
     nb = (int)std::min<int64_t>(nb, in->rows);
-    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
+    const int64_t pitch = host_pitch(in);
     // ---- the one global reduction, over the whole raster, on the first device (the kernels of mcf_plan_create)
     double twi_mean;
     {
@@ -2982,7 +2964,7 @@ static int run_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mc
 static int run_bioclim_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const mcf_multi* mu,
                              mcf_bioclim_out* out, int want_af, int layered) {
     if (!out || !sel || !in) return fail(MCF_ERR_ARG, "null bioclim argument");
-    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
+    const int64_t pitch = host_pitch(in);
     mcf_grid_inputs in_l = *in;
     if (layered) { in_l.veg_layers = 14; in_l.lyr_st = kBioSt; in_l.lyr_ed = kBioEd; }     // as run_bioclim: the fixed dfsel
     std::atomic<int> chunks{0};               // the blocks run on worker threads: their counts, summed for the caller's thread
@@ -3017,7 +2999,7 @@ int mcf_runmicro_summary_multi(const mcf_grid_inputs* in, const mcf_options* opt
     if (opt->reqhgt < 0.0) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, "summary: negative chunk_days");
     if (const int rc = check_summary_spec(spec, in->tsteps / 24, nullptr)) return rc;
-    const int64_t pitch = in->row_pitch > 0 ? in->row_pitch : in->rows;
+    const int64_t pitch = host_pitch(in);
     return for_row_blocks(in, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int) {
         mcf_summary_out so = *out;
         for (int v = 0; v < MCF_NOUT; ++v)

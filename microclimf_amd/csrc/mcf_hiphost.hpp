@@ -68,9 +68,20 @@ struct DevOwner {
         p.clear();
         bytes = 0;
     }
-    // `n` elements of T
+    // `n` elements of T (T may be const: a buffer its holder only reads)
     template <class T>
     int make(T** out, int64_t n) { return alloc((void**)out, n * (int64_t)sizeof(T)); }
+    // a buffer of `n` elements that grows (*cap: its bytes): the old one is released first.  A buffer that has to grow gets a quarter
+    // more than is asked for — successive calls ask for about the same, and a release + allocation of a gigabyte costs 50 ms
+    template <class T>
+    int regrow(T** buf, int64_t* cap, int64_t n) {
+        int64_t nbytes = n * (int64_t)sizeof(T);
+        if (*buf && *cap >= nbytes) return MCF_OK;
+        if (*buf) { nbytes += nbytes / 4; release((void*)*buf); *buf = nullptr; *cap = 0; }
+        const int rc = alloc((void**)buf, nbytes);
+        if (!rc) *cap = nbytes > 8 ? nbytes : 8;
+        return rc;
+    }
     // device copy of a host array of `n` elements: one the device goes on to write ...
     template <class T>
     int up_mut(T** dev, const T* host, int64_t n, const char* what) {
