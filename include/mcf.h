@@ -63,7 +63,7 @@ extern "C" {
                              *    mcf_microsnow_expand_coarse_device, mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse,
                              *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc, mcf_plan_below_set_depths,
                              *    mcf_plan_fetch_depth*, mcf_plan_summary_enable_below, mcf_plan_summary_fetch_depth, mcf_runmicro_depths,
-                             *    mcf_runmicro_depths_summary) */
+                             *    mcf_runmicro_depths_summary, mcf_plan_diag_enable_array, mcf_runmicro2_diag, mcf_runmicro4_diag) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -504,6 +504,17 @@ typedef struct mcf_diag_outputs {
 int mcf_runmicro1_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
                        mcf_diag_outputs *diag_out);
 int mcf_runmicro3_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
+                       mcf_diag_outputs *diag_out);
+/* Array weather (array_forcing 1: fine arrays; 2: coarse arrays interpolated in the solver, with or without altcorrect).
+ * mcf_plan_diag_enable_array is mcf_plan_diag_enable for such a plan: the same ring, layout, fetch, slot_ptr, ring_layout,
+ * pass-2 rule and state rules.  MCF_ERR_ARG on a vector-forcing plan (use mcf_plan_diag_enable), reqhgt < 0, streamed plans and
+ * an empty selection; MCF_ERR_STATE after the first run or on a second enable; tile masks and cell subsets are refused on the
+ * plan as above.  mcf_runmicro2_diag / mcf_runmicro4_diag: mcf_runmicro2 / mcf_runmicro4 (fine or coarse as `in` says) with the
+ * selected diagnostics beside the outputs, the forcing streamed in day chunks.  reqhgt >= 0. */
+int mcf_plan_diag_enable_array(mcf_plan *plan, const int32_t sel[MCF_NDIAG]);
+int mcf_runmicro2_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
+                       mcf_diag_outputs *diag_out);
+int mcf_runmicro4_diag(const mcf_grid_inputs *in, const mcf_options *opt, const int32_t sel[MCF_NDIAG], mcf_outputs *out,
                        mcf_diag_outputs *diag_out);
 
 /* HIP-event timing on the plan's stream: start records an event, stop records

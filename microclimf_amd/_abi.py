@@ -353,6 +353,7 @@ EXPORTS = (
     "mcf_leafrfromalb", "mcf_leafrfromalb_device", "mcf_selftest_vegprep",
     "mcf_plan_diag_enable", "mcf_plan_diag_fetch", "mcf_plan_diag_slot_ptr", "mcf_plan_diag_ring_layout",
     "mcf_runmicro1_diag", "mcf_runmicro3_diag",
+    "mcf_plan_diag_enable_array", "mcf_runmicro2_diag", "mcf_runmicro4_diag",
     "mcf_plan_summary_enable", "mcf_plan_summary_accumulate", "mcf_plan_summary_fetch", "mcf_plan_summary_days",
     "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
     "mcf_plan_below_set_depths", "mcf_plan_fetch_depth", "mcf_plan_fetch_depth_pitched", "mcf_plan_summary_enable_below",
@@ -530,6 +531,12 @@ def load() -> C.CDLL:
         for fn in (lib.mcf_runmicro1_diag, lib.mcf_runmicro3_diag):
             fn.restype = C.c_int
             fn.argtypes = [GI, OP, DSEL, OU, C.POINTER(DiagOutputs)]
+        if hasattr(lib, "mcf_plan_diag_enable_array"):      # (absent from an older library named by MCF_LIB for an A/B run)
+            lib.mcf_plan_diag_enable_array.restype = C.c_int
+            lib.mcf_plan_diag_enable_array.argtypes = [P, DSEL]
+            for fn in (lib.mcf_runmicro2_diag, lib.mcf_runmicro4_diag):
+                fn.restype = C.c_int
+                fn.argtypes = [GI, OP, DSEL, OU, C.POINTER(DiagOutputs)]
     if hasattr(lib, "mcf_plan_summary_enable"):     # (absent from an older library named by MCF_LIB for an A/B run)
         SS, SO_ = C.POINTER(SummarySpec), C.POINTER(SummaryOut)
         lib.mcf_plan_summary_enable.restype = C.c_int

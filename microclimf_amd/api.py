@@ -287,12 +287,15 @@ def runmicro1Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Map
 def runmicro2Cpp(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
                  reqhgt: float, zref: float, lats, lons, Sminp: float, Smaxp: float, tfact: float,
                  complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None,
+                 diag=None) -> dict:
     """Grid microclimate model, hourly, static vegetation, array climate inputs.
 
-    Drop-in for the reference's runmicro2Cpp (src/microclimfCpp.cpp:2340-2621); `devices` / `n_blocks` as runmicro1Cpp."""
+    Drop-in for the reference's runmicro2Cpp (src/microclimfCpp.cpp:2340-2621); `devices` / `n_blocks` as runmicro1Cpp;
+    `diag`: as runmicro1Cpp (include/mcf.h mcf_runmicro2_diag)."""
     return _run("mcf_runmicro2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
-                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm)
+                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, devices=devices, n_blocks=n_blocks, dtm=dtm,
+                diag=diag)
 
 
 def coarse_positions(n_fine: int, n_coarse: int):
@@ -305,12 +308,13 @@ def coarse_positions(n_fine: int, n_coarse: int):
 def runmicro2Cpp_coarse(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping,
                         reqhgt: float, zref: float, lats, lons, Sminp: float, Smaxp: float, tfact: float,
                         complete: bool, mat: float, out: Sequence, *, rowpos=None, colpos=None, altcorrect: int = 0,
-                        dtmc=None, dtm=None, device: int = 0, days_per_chunk: int = 0, devices=None, n_blocks: int = 0) -> dict:
+                        dtmc=None, dtm=None, device: int = 0, days_per_chunk: int = 0, devices=None, n_blocks: int = 0,
+                        diag=None) -> dict:
     """`.runmodel2Cpp` with the resampling fused into the solver (include/mcf.h, array_forcing == 2): `climdata` =
     {temp, relhum, pres, swdown, difrad, lwdown, windspeed, winddir} and `pointm` = {soilm, Gp, umu, kp, muGp, dtrp} as
     COARSE arrays [coarse_rows, coarse_cols, tsteps] — what `.cca(..., dtmc, dtmc)` gives before `resample` — instead of
     the full-resolution arrays runmicro2Cpp takes.  `rowpos` / `colpos`: see `coarse_positions` (default: the coarse
-    grid covers the raster's extent)."""
+    grid covers the raster's extent).  `diag`: as runmicro1Cpp — the diagnostics of the interpolated (and altitude-corrected) weather."""
     R, Cc = np.shape(vegp["hgt"])[:2]
     cr, cc = np.shape(climdata["temp"])[:2]
     coarse = {"rowpos": coarse_positions(R, cr) if rowpos is None else rowpos,
@@ -318,7 +322,8 @@ def runmicro2Cpp_coarse(obstime: Mapping, climdata: Mapping, pointm: Mapping, ve
     if altcorrect:                     # `.runmodel2Cpp`'s altcorrect 1 / 2 with the coarse (dtmc) and fine (dtm) elevations
         coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=dtm)
     return _run("mcf_runmicro2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
-                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, 0, None, coarse, devices=devices, n_blocks=n_blocks)
+                Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, 0, None, coarse, devices=devices, n_blocks=n_blocks,
+                diag=diag)
 
 
 def runmicro3Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
@@ -338,12 +343,13 @@ def runmicro3Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Ma
 def runmicro4Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
                  soilc: Mapping, reqhgt: float, zref: float, lats, lons, Sminp: float, Smaxp: float,
                  tfact: float, complete: bool, mat: float, out: Sequence, *, device: int = 0,
-                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None) -> dict:
+                 days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0, dtm: Mapping | None = None,
+                 diag=None) -> dict:
     """Hourly, changing vegetation, array climate: drop-in for the reference's runmicro4Cpp
-    (src/microclimfCpp.cpp:2926-3226).  `devices` / `n_blocks`: as runmicro1Cpp."""
+    (src/microclimfCpp.cpp:2926-3226).  `devices` / `n_blocks`: as runmicro1Cpp; `diag`: as runmicro1Cpp."""
     return _run("mcf_runmicro4", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
                 Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel,
-                devices=devices, n_blocks=n_blocks, dtm=dtm)
+                devices=devices, n_blocks=n_blocks, dtm=dtm, diag=diag)
 
 
 BIOCLIM_DFSEL = {"lyr": np.arange(1, 15), "st": np.arange(14) * 24, "ed": np.arange(14) * 24 + 23}   # cpp:3634-3646
@@ -618,6 +624,13 @@ class Plan:
         reqhgt >= 0 (include/mcf.h mcf_plan_diag_enable).  -> the selected names"""
         sel, picked = diag_selection(names)
         _abi.check(self._lib.mcf_plan_diag_enable(self._p, C.byref(sel)))
+        return picked
+
+    def diag_enable_array(self, names="all"):
+        """diag_enable() for an array-weather plan, fine or coarse (include/mcf.h mcf_plan_diag_enable_array): the same ring,
+        fetch_diag / diag_slot_ptr / diag_ring_layout read it.  -> the selected names"""
+        sel, picked = diag_selection(names)
+        _abi.check(self._lib.mcf_plan_diag_enable_array(self._p, C.byref(sel)))
         return picked
 
     def fetch_diag(self, slot: int, dvar, step0: int, nsteps: int) -> np.ndarray:

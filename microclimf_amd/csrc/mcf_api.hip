@@ -1301,8 +1301,8 @@ struct SolveTiles {
 // The k_solve launches of `t` on the plan's stream: with `fast`, the fix-up count cleared, then the fast part through the
 // min / max clamps and the slow part through the reference form; without it (an irregular day, or no fast class at all) one
 // reference-form launch of the first part, or of the whole raster.  An empty part launches nothing.
-// A diagnostics plan (mcf_plan_diag_enable) sends the same launches, with the same choices, through k_solve_diag: the slot's
-// place in the diagnostics ring rides along.
+// A diagnostics plan (mcf_plan_diag_enable, mcf_plan_diag_enable_array) sends the same launches, with the same choices, through
+// k_solve_diag / k_solve_diag_af: the slot's place in the diagnostics ring rides along.
 void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, const SolveTiles& t, int slot) {
     auto launch = [&](bool bg, bool f) {
         if (!p->d_dring) { mcf::launch_solve(a, p->cpb, p->af, bg, f, soil_daily, p->stream); return; }
@@ -1311,7 +1311,8 @@ void dispatch_solve(mcf_plan* p, mcf::SolveArgs& a, bool fast, bool soil_daily, 
         d.dg_base = p->d_dring + (int64_t)slot * p->dg_slot_elems;
         d.dg_tile_stride = p->dg_tile_stride; d.dg_day_stride = p->dg_day_stride;
         for (int v = 0; v < MCF_NDIAG; ++v) d.dg_sel |= (uint64_t)(p->dg_slab1[v] ? p->dg_slab1[v] - 1 : 15) << (4 * v);
-        mcf::launch_solve_diag(d, p->cpb, f, soil_daily, p->stream);
+        if (p->af) mcf::launch_solve_diag_af(d, p->cpb, f, soil_daily, p->stream);      // (coarse: the flag says "taps through LDS")
+        else mcf::launch_solve_diag(d, p->cpb, f, soil_daily, p->stream);
     };
     if (!fast) {
         if (!t.whole_raster() && t.n_fast == 0) return;
@@ -2089,14 +2090,12 @@ int mcf_plan_ring_layout(mcf_plan* p, mcf_ring_layout* out) {
     return MCF_OK;
 }
 
-int mcf_plan_diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
-    if (!p || !sel) return fail(MCF_ERR_ARG, "null argument");
-    if (p->af) return fail(MCF_ERR_ARG, p->coarse ? "diagnostics are not available with coarse array forcing"
-                                                  : "diagnostics are not available with array forcing");
+// the diagnostics ring of a plan whose kind of forcing the caller has checked: one set of rules for both entries
+static int diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG], const char* entry) {
     if (p->bg || p->opt.reqhgt < 0.0) return fail(MCF_ERR_ARG, "diagnostics need reqhgt >= 0");
     if (p->bg_stream) return fail(MCF_ERR_ARG, "diagnostics are not available on a streamed plan");
     if (p->d_dring) return fail(MCF_ERR_STATE, "diagnostics are already enabled on this plan");
-    if (p->has_run) return fail(MCF_ERR_STATE, "mcf_plan_diag_enable comes before the plan's first run");
+    if (p->has_run) return fail(MCF_ERR_STATE, std::string(entry) + " comes before the plan's first run");
     int n = 0;
     for (int v = 0; v < MCF_NDIAG; ++v) n += sel[v] ? 1 : 0;
     if (n == 0) return fail(MCF_ERR_ARG, "no diagnostic selected");
@@ -2108,6 +2107,20 @@ int mcf_plan_diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
     p->ndiag = 0;
     for (int v = 0; v < MCF_NDIAG; ++v) p->dg_slab1[v] = sel[v] ? ++p->ndiag : 0;
     return MCF_OK;
+}
+
+int mcf_plan_diag_enable(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
+    if (!p || !sel) return fail(MCF_ERR_ARG, "null argument");
+    if (p->af) return fail(MCF_ERR_ARG, p->coarse ? "diagnostics are not available with coarse array forcing"
+                                                  : "diagnostics are not available with array forcing");
+    return diag_enable(p, sel, "mcf_plan_diag_enable");
+}
+// array forcing, fine or coarse: the same ring filled by k_solve_diag_af (the entry above keeps its refusal, as
+// mcf_plan_summary_enable does beside mcf_plan_summary_enable_below)
+int mcf_plan_diag_enable_array(mcf_plan* p, const int32_t sel[MCF_NDIAG]) {
+    if (!p || !sel) return fail(MCF_ERR_ARG, "null argument");
+    if (!p->af) return fail(MCF_ERR_ARG, "mcf_plan_diag_enable_array needs an array-forcing plan: mcf_plan_diag_enable for vector forcing");
+    return diag_enable(p, sel, "mcf_plan_diag_enable_array");
 }
 
 int mcf_plan_diag_slot_ptr(mcf_plan* p, int32_t slot, int32_t dvar, void** dev_ptr) {
@@ -2787,7 +2800,7 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
     PlanHolder holder(p);
     if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if (stream_bg && (rc = mcf_plan_below_prepare(p, in))) return rc;
-    if (dsel && (rc = mcf_plan_diag_enable(p, dsel))) return rc;
+    if (dsel && (rc = want_af ? mcf_plan_diag_enable_array(p, dsel) : mcf_plan_diag_enable(p, dsel))) return rc;
     double t_create = now() - t0;
     // the timing split: the driver's half (a chunk's forcing upload and its days, synchronised) and the sink's half (its fetches)
     double ta = now();
@@ -3043,6 +3056,18 @@ int mcf_runmicro3_diag(const mcf_grid_inputs* in, const mcf_options* opt, const 
     if (in && in->veg_layers < 1) return fail(MCF_ERR_ARG, "mcf_runmicro3_diag needs veg_layers >= 1 and dfsel");
     if (in && in->array_forcing != 0) return fail(MCF_ERR_ARG, "diagnostics are not available with array forcing");
     return run_oneshot(in, opt, out, 0, nullptr, 1, nullptr, sel, diag_out);
+}
+// array weather, fine or coarse as `in` says (the entries above keep their refusals)
+int mcf_runmicro2_diag(const mcf_grid_inputs* in, const mcf_options* opt, const int32_t sel[MCF_NDIAG], mcf_outputs* out,
+                       mcf_diag_outputs* diag_out) {
+    if (!sel || !diag_out) return fail(MCF_ERR_ARG, "null argument");
+    return run_oneshot(in, opt, out, 1, nullptr, 1, nullptr, sel, diag_out);
+}
+int mcf_runmicro4_diag(const mcf_grid_inputs* in, const mcf_options* opt, const int32_t sel[MCF_NDIAG], mcf_outputs* out,
+                       mcf_diag_outputs* diag_out) {
+    if (!sel || !diag_out) return fail(MCF_ERR_ARG, "null argument");
+    if (in && in->veg_layers < 1) return fail(MCF_ERR_ARG, "mcf_runmicro4_diag needs veg_layers >= 1 and dfsel");
+    return run_oneshot(in, opt, out, 1, nullptr, 1, nullptr, sel, diag_out);
 }
 int mcf_runmicro3(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {
     if (in && in->veg_layers < 1) return fail(MCF_ERR_ARG, "mcf_runmicro3 needs veg_layers >= 1 and dfsel");

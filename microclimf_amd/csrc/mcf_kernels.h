@@ -392,6 +392,9 @@ void launch_solve(const SolveArgs& a, int cells_per_block, bool af, bool bg, boo
 // the same launch of a diagnostics plan (vector forcing, reqhgt >= 0): both rings are filled; `fast` / `soil_daily` as above,
 // chosen by the caller exactly as for a plain launch of the same days, so that the ten outputs keep their bits
 void launch_solve_diag(const DiagSolveArgs& a, int cells_per_block, bool fast, bool soil_daily, hipStream_t s);
+// the same for an array-forcing plan (mcf_plan_diag_enable_array; k_solve_diag_af): fine arrays with the plan's tile size, or — a.crows
+// > 0 — coarse arrays with 32-cell tiles, `coarse_lds` as launch_solve's flag says "taps through LDS"
+void launch_solve_diag_af(const DiagSolveArgs& a, int cells_per_block, bool fast, bool coarse_lds, hipStream_t s);
 // reqhgt < 0 of a streamed plan: the tiled-ring instantiation (SolveArgs tg_ring); the reference-form clamps, no shared soil state,
 // exactly the arithmetic of launch_solve's bg instantiation
 void launch_solve_bg_tiled(const SolveArgs& a, int cells_per_block, bool af, hipStream_t s);

@@ -494,10 +494,11 @@ __device__ __forceinline__ DiagRing<NT> diag_sink(const DiagSolveArgs& a, double
     asm volatile("" : "+s"(dsel));
     return DiagRing<NT>{(char*)day, dsel, posb};
 }
-//   DIAG   the staged model's diagnostics (mcf_device.hpp DiagRing) go to a second ring beside the outputs: k_solve_diag only
+//   DIAG   the staged model's diagnostics (mcf_device.hpp DiagRing) go to a second ring beside the outputs: k_solve_diag and
+//          k_solve_diag_af only
 template <int CPB, int AF, int BG, bool F, bool SSREQ, bool DIAG = false, class ARGS = SolveArgs>
 __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, const int day0, const int ndays, const int rot) {
-    static_assert(!DIAG || (AF == 0 && BG == 0), "diagnostics: vector forcing, reqhgt >= 0");
+    static_assert(!DIAG || BG == 0, "diagnostics: reqhgt >= 0");
     constexpr int NT = solve_threads(CPB);
     static_assert(NT == RING_BLOCK(CPB), "tile-day block = one value per lane");
     // the tile's LDS image: [CF_COUNT cell fields + 24 horizon + 8 wind-shelter rows][CPB], as it lies in the table
@@ -895,7 +896,8 @@ __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, co
             }
         }
         if (valid) {
-            if (AF) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn);
+            if constexpr (AF != 0 && DIAG) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn, diag_sink<NT>(a, dg_day, posb));
+            else if (AF) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn);
             else if constexpr (DIAG) pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn, diag_sink<NT>(a, dg_day, posb));
             else pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn);
             if (!PRE) {
@@ -974,7 +976,8 @@ __device__ __forceinline__ void solve_tile(const ARGS& a, const int64_t tile, co
             const double dtr = tmx - tmn;
             Pass2Out p2{};
             if (AF) derive_time_af_pass2(tv);
-            if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
+            if constexpr (AF != 0 && DIAG) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn, NoHook(), diag_sink<NT>(a, dg_day, posb));
+            else if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
             else if constexpr (DIAG) pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn, NoHook(), diag_sink<NT>(a, dg_day, posb));
             else pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
             if (BG == 1) {
@@ -1107,6 +1110,33 @@ __global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 :
     for (int64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
         __syncthreads();
         solve_tile<CPB, 0, 0, false, false, true>(a, all ? i : (int64_t)a.fix_list[i], a.day0, a.ndays, 0);
+    }
+}
+
+// The same for array forcing (AF 1: fine arrays from the tiled forcing ring; AF 2: coarse arrays interpolated here, SSREQ = the taps
+// staged in LDS): again kernels of their own, so that neither k_solve's nor k_solve_diag's instantiations change.  The sink stores
+// every diagnostic where pass 1 / pass 2 produce it, so nothing more than the store's operand is live; the bounds are the fix-up
+// kernel's — three waves per SIMD (168 VGPRs) where the workgroup has twelve waves and has to fit a CU, two below that.
+template <int CPB, int AF, bool F, bool SSREQ>
+__global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 : 3) void k_solve_diag_af(DiagSolveArgs a) {
+    static_assert(AF == 1 || AF == 2, "array forcing");
+    const int rot = (int)((blockIdx.x >> 8) & 1);
+    const int64_t pos = tile_position(a.ntiles_launch);
+    if (pos < 0) return;
+    const int64_t tile = a.tile_list ? (int64_t)a.tile_list[pos] : pos;
+    solve_tile<CPB, AF, 0, F, SSREQ, true>(a, tile, a.day0, a.ndays, rot);
+}
+template <int CPB, int AF>
+__global__ __launch_bounds__(solve_threads(CPB), solve_threads(CPB) <= 512 ? 2 : 3) void k_solve_fix_diag_af(DiagSolveArgs a) {
+    static_assert(AF == 1 || AF == 2, "array forcing");
+    const int n = *a.fix_count;
+    if (n <= 0) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.fix_count + 1, n);
+    const bool all = n > a.fix_cap;
+    const int64_t cnt = all ? (a.N + CPB - 1) / CPB : n;
+    for (int64_t i = blockIdx.x; i < cnt; i += gridDim.x) {
+        __syncthreads();
+        solve_tile<CPB, AF, 0, false, false, true>(a, all ? i : (int64_t)a.fix_list[i], a.day0, a.ndays, 0);
     }
 }
 
@@ -2155,6 +2185,40 @@ static void launch_solve_diag_cpb(DiagSolveArgs a, bool fast, bool ss, hipStream
         if (ss) hipLaunchKernelGGL((k_solve_diag<CPB, false, true>), grid, block, 0, s, a);
         else hipLaunchKernelGGL((k_solve_diag<CPB, false, false>), grid, block, 0, s, a);
     }
+}
+// array forcing: launch_solve_cpb's choices for af and reqhgt >= 0 (no 42-cell tiles), and launch_solve_coarse's
+template <int CPB>
+static void launch_solve_diag_af_cpb(DiagSolveArgs a, bool fast, hipStream_t s) {
+    if (a.ntiles_launch <= 0) {
+        a.ntiles_launch = (a.N + CPB - 1) / CPB;
+        a.tile_list = nullptr;
+    }
+    const dim3 grid = solve_grid(a.ntiles_launch), block(solve_threads(CPB));
+    if (fast) {
+        hipLaunchKernelGGL((k_solve_diag_af<CPB, 1, true, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((k_solve_fix_diag_af<CPB, 1>), dim3(512), block, 0, s, a);
+    } else hipLaunchKernelGGL((k_solve_diag_af<CPB, 1, false, false>), grid, block, 0, s, a);
+}
+static void launch_solve_diag_coarse(DiagSolveArgs a, bool fast, bool lds, hipStream_t s) {
+    constexpr int CPB = 32;
+    if (a.ntiles_launch <= 0) {
+        a.ntiles_launch = (a.N + CPB - 1) / CPB;
+        a.tile_list = nullptr;
+    }
+    const dim3 grid = solve_grid(a.ntiles_launch), block(solve_threads(CPB));
+    if (fast) {
+        if (lds) hipLaunchKernelGGL((k_solve_diag_af<CPB, 2, true, true>), grid, block, 0, s, a);
+        else hipLaunchKernelGGL((k_solve_diag_af<CPB, 2, true, false>), grid, block, 0, s, a);
+        hipLaunchKernelGGL((k_solve_fix_diag_af<CPB, 2>), dim3(512), block, 0, s, a);
+    } else hipLaunchKernelGGL((k_solve_diag_af<CPB, 2, false, false>), grid, block, 0, s, a);
+}
+void launch_solve_diag_af(const DiagSolveArgs& a, int cells_per_block, bool fast, bool coarse_lds, hipStream_t s) {
+    if (a.N <= 0 || a.ndays <= 0 || !a.dg_base) return;
+    if (a.crows > 0) { launch_solve_diag_coarse(a, fast, coarse_lds, s); return; }
+    if (cells_per_block == 32) launch_solve_diag_af_cpb<32>(a, fast, s);
+    else if (cells_per_block == 21) launch_solve_diag_af_cpb<21>(a, fast, s);
+    else if (cells_per_block == 42) return;       // (not an array-forcing geometry: launch_solve_cpb builds nothing for it either)
+    else launch_solve_diag_af_cpb<16>(a, fast, s);
 }
 void launch_solve_diag(const DiagSolveArgs& a, int cells_per_block, bool fast, bool soil_daily, hipStream_t s) {
     if (a.N <= 0 || a.ndays <= 0 || !a.dg_base) return;

@@ -566,12 +566,29 @@ def modelin(micropoint, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, slr=None
     """`modelin(micropoint, vegp, soilc, dtm)` for data.frame weather (R/Rimplementation.R:70-77): the prepared grid inputs
     (prepare_grid_inputs: cleaned vegetation and soil, the terrain planes, the wetness index), `progress = 0` and `tme`."""
     if not isinstance(micropoint, Mapping):
-        raise NotImplementedError("modelin: a list of micropoints (array weather, `.modelina` and its altcorrect) is not "
-                                  "supported — the solver's diagnostics exist for data.frame weather only")
+        raise NotImplementedError("modelin: a list of micropoints (array weather) needs the climate grid's shape and the "
+                                  "raster's lats / lons — see modelina")
     inputs = prepare_grid_inputs(micropoint, 0.05, vegp, soilc, dtm, slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf,
                                  device=device)
     return {"inputs": inputs, "progress": 0, "tme": micropoint["obstime"], "device": device,
             "_src": (micropoint, vegp, soilc, dtm), "_runs": {}}
+
+
+def modelina(micropointa: Sequence, crows: int, ccols: int, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, lats, lons, dtmc=None,
+             altcorrect: int = 0, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0) -> dict:
+    """`modelin(micropoint, vegp, soilc, dtm, dtmc, altcorrect)` for a list of micropoints from `runpointmodela` (array weather:
+    `.modelina`, R/internal.R:645): the prepared grid inputs with the climate and point-model variables left on the coarse grid
+    (prepare_grid_inputs_array), `progress = 0` and `tme`.  The stage functions work on the result as on modelin's; `altcorrect`
+    1 / 2 with `dtmc` [crows, ccols] as in runmicro_array.  Below ground is refused as runmicro_array refuses it."""
+    if isinstance(micropointa, Mapping):
+        raise ValueError("modelina takes the list of micropoints of runpointmodela: see modelin for data.frame weather")
+    if altcorrect and dtmc is None:
+        raise ValueError("altcorrect needs dtmc, the elevations of the climate cells")
+    inputs = prepare_grid_inputs_array(micropointa, crows, ccols, 0.05, vegp, soilc, dtm, lats=lats, lons=lons, slr=slr, apr=apr,
+                                       hor=hor, twi=twi, wsa=wsa, svf=svf, device=device)
+    return {"inputs": inputs, "progress": 0, "tme": micropointa[0]["obstime"], "device": device,
+            "_src": (micropointa, vegp, soilc, dtm), "_runs": {},
+            "_array": {"crows": int(crows), "ccols": int(ccols), "lats": lats, "lons": lons, "dtmc": dtmc, "altcorrect": int(altcorrect)}}
 
 
 def _stage_key(reqhgt, pai_a, tfact):
@@ -585,14 +602,18 @@ def _stage_run(micro: dict, reqhgt, pai_a, tfact) -> dict:
     if key not in micro["_runs"]:
         micropoint, vegp, soilc, dtm = micro["_src"]
         sc = micro["inputs"]["soilc"]      # the terrain planes made by modelin are handed back: nothing is derived twice
-        a = prepare_grid_inputs(micropoint, key[0], vegp, soilc, dtm, pai_a=pai_a, slr=sc["slope"], apr=sc["aspect"],
-                                hor=sc["hor"], twi=sc["twi"], wsa=sc["wsa"], svf=sc["svfa"], device=micro["device"])
-        a["tfact"] = float(tfact)
-        dfsel = a.pop("dfsel", None)
-        if dfsel is None:
-            res = api.runmicro1Cpp(**a, device=micro["device"], diag="all")
+        terrain = dict(slr=sc["slope"], apr=sc["aspect"], hor=sc["hor"], twi=sc["twi"], wsa=sc["wsa"], svf=sc["svfa"])
+        if "_array" in micro:              # modelina: the coarse one-shot with the diagnostics beside the outputs
+            res = _run_array(micropoint, reqhgt=key[0], vegp=vegp, soilc=soilc, dtm=dtm, tfact=tfact, pai_a=pai_a, **terrain,
+                             device=micro["device"], diag="all", **micro["_array"])
         else:
-            res = api.runmicro3Cpp(dfsel, **a, device=micro["device"], diag="all")
+            a = prepare_grid_inputs(micropoint, key[0], vegp, soilc, dtm, pai_a=pai_a, **terrain, device=micro["device"])
+            a["tfact"] = float(tfact)
+            dfsel = a.pop("dfsel", None)
+            if dfsel is None:
+                res = api.runmicro1Cpp(**a, device=micro["device"], diag="all")
+            else:
+                res = api.runmicro3Cpp(dfsel, **a, device=micro["device"], diag="all")
         micro["_runs"][key] = res
     micro["_last"] = key
     return micro["_runs"][key]
@@ -651,6 +672,8 @@ def belowground(micro: dict, reqhgt: float = -0.05, pai_a=None, tfact: float = 1
     the kept diagnostics solve (the ground's temperature does not depend on reqhgt)"""
     if reqhgt >= 0:
         raise ValueError("belowground needs reqhgt < 0: see aboveground")
+    if "_array" in micro:
+        raise ValueError(_ARRAY_BELOW)
     if micro["progress"] < 4 or micro.get("_last") != _stage_key(reqhgt, pai_a, tfact):
         soiltemp(micro, reqhgt, pai_a, tfact)
     micropoint, vegp, soilc, dtm = micro["_src"]
@@ -813,8 +836,18 @@ def runmicro_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: float,
                    *, lats, lons, tfact: float = 1.5, altcorrect: int = 0, dtmc=None, device: int = 0, **kw) -> dict:
     """`runmicro()` for a list of micropoints from `runpointmodela` (array weather, no snow).  `altcorrect` 1 / 2 with
     `dtmc` [crows, ccols], the elevations of the climate cells: the lapse-rate correction of R/internal.R:1233-1251."""
+    return _run_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, tfact=tfact, altcorrect=altcorrect,
+                      dtmc=dtmc, device=device, **kw)
+
+
+_ARRAY_BELOW = "coarse array forcing below ground needs the per-cell point-model series: not mirrored"
+
+
+def _run_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, *, lats, lons, tfact=1.5, altcorrect=0, dtmc=None, device=0,
+               diag=None, **kw) -> dict:
+    """runmicro_array, and — `diag` — the same solve with the staged model's diagnostics under "diag" (modelina's stages)"""
     if reqhgt < 0:
-        raise ValueError("coarse array forcing below ground needs the per-cell point-model series: not mirrored")
+        raise ValueError(_ARRAY_BELOW)
     a = prepare_grid_inputs_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, device=device, **kw)
     a["tfact"] = float(tfact)
     dfsel = a.pop("dfsel", None)
@@ -825,7 +858,7 @@ def runmicro_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: float,
     order = ("obstime", "climdata", "pointm", "vegp", "soilc", "reqhgt", "zref", "lat", "lon", "Sminp", "Smaxp", "tfact",
              "complete", "mat", "out")
     fn = "mcf_runmicro2" if dfsel is None else "mcf_runmicro4"
-    return api._run(fn, True, *[a[k] for k in order], device, 0, 0, dfsel, coarse)
+    return api._run(fn, True, *[a[k] for k in order], device, 0, 0, dfsel, coarse, diag=diag)
 
 
 # ---- snow: runsnowmodel() -> .snowmodel1 --------------------------------------------------------------------------

@@ -13,11 +13,13 @@ ROOT = Path(__file__).resolve().parents[1]
 SRC = ROOT / "microclimf_amd" / "csrc" / "mcf_kernels.hip"
 OUT = ROOT / "tools" / "variants"
 
-P1 = '''            if (AF) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn);
+P1 = '''            if constexpr (AF != 0 && DIAG) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn, diag_sink<NT>(a, dg_day, posb));
+            else if (AF) pass1<F, false>(C, TR, SL, g, flags, dTcap, cy, p1, MK, cn);
             else if constexpr (DIAG) pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn, diag_sink<NT>(a, dg_day, posb));
             else pass1<F, SS>(C, TL, SL, g, flags, dTcap, cy, p1, MK, cn);
 '''
-P2 = '''            if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
+P2 = '''            if constexpr (AF != 0 && DIAG) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn, NoHook(), diag_sink<NT>(a, dg_day, posb));
+            else if (AF) pass2<F, false>(C, TR, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
             else if constexpr (DIAG) pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn, NoHook(), diag_sink<NT>(a, dg_day, posb));
             else pass2<F, SS>(C, TL, SL, g, flags, dTcap, cy, dtr, Rmx, need_tv, p2, MK, cn);
 '''
