@@ -63,7 +63,8 @@ extern "C" {
                              *    mcf_microsnow_expand_coarse_device, mcf_runmicrosnow2_coarse, mcf_snowrun_create_coarse,
                              *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc, mcf_plan_below_set_depths,
                              *    mcf_plan_fetch_depth*, mcf_plan_summary_enable_below, mcf_plan_summary_fetch_depth, mcf_runmicro_depths,
-                             *    mcf_runmicro_depths_summary, mcf_plan_diag_enable_array, mcf_runmicro2_diag, mcf_runmicro4_diag) */
+                             *    mcf_runmicro_depths_summary, mcf_plan_diag_enable_array, mcf_runmicro2_diag, mcf_runmicro4_diag,
+                             *    mcf_foliageden, mcf_foliageden_device, mcf_plan_set_height, mcf_plan_fetch_foliage, mcf_runmicro_heights) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -1511,6 +1512,38 @@ int mcf_leafrfromalb_device(int64_t rows, int64_t cols, const double *pai, const
  * leafr, leaft, gref, then iterations, mxdif_gref, mxdif_leaf, lref_first. */
 int mcf_selftest_vegprep(int32_t kind, int64_t rows, int64_t cols, const double *a, const double *b, const double *c,
                          const double *d, const double *e, double ltrr, double *out, int32_t block, int32_t device);
+
+/* ---- height profiles from one plan ---------------------------------------------------------------------
+ * The foliage profile of `.foliageden` (R/internal.R:937-946) with the shape 1.5 and rate 1.5 / 7 every call site of the
+ * reference uses: for each of n values, x = ((hgt - z) / hgt) 10, leafden = (pai / hgt) (dgamma(x) / td) 10 and
+ * paia = pgamma(x) (pai / td), td = pgamma(10).  z >= hgt gives exact zeros, hgt = 0 gives paia 0 and leafden NaN (the
+ * reference's 0 / 0), a NaN hgt or pai propagates.  The gamma functions are the closed forms of shape 3/2 with a series near
+ * the canopy top (mcf_foliage.h): within 2^-40 relative of R's pgamma / dgamma.  mcf_foliageden is the host twin;
+ * mcf_foliageden_device is upload, one launch (k_foliage) and download. */
+int mcf_foliageden(int64_t n, const double *hgt, const double *pai, double z, double *leafden, double *paia);
+int mcf_foliageden_device(int64_t n, const double *hgt, const double *pai, double z, double *leafden, double *paia,
+                          int32_t device);
+/* Re-targets a plan to another height above ground: everything but vegp$paia, vegp$leafden and reqhgt itself stays resident.
+ * The plan's stream is synchronised, leafden and paia of every layer are derived on the device from the resident hgt and pai
+ * (k_foliage), reqhgt is replaced and the per-cell images and tile classes are rebuilt before the next run: the outputs are
+ * bit for bit those of a plan created at `reqhgt` with these two planes.  `paia`: NULL, or a host [rows, cols, layers]
+ * array, laid out as vegp$paia was at creation (row_pitch included), that takes the place of the derived plant area above
+ * (leafden is always derived, as in the reference).
+ * For a tiled plan created with reqhgt >= 0: vector, array or coarse array forcing, any number of vegetation layers, with or
+ * without period summaries (mcf_plan_summary_reset starts the next height's statistics).  MCF_ERR_ARG: a null plan, reqhgt <= 0
+ * or NaN (0: mcf_runmicro*; below ground: mcf_runmicro_depths); MCF_ERR_STATE: a below-ground plan, a plan with diagnostics
+ * enabled.  Every message starts with the entry's name. */
+int mcf_plan_set_height(mcf_plan *plan, double reqhgt, const double *paia);
+/* The two planes the plan holds now, [rows, cols, layers] each, dense (either may be NULL). */
+int mcf_plan_fetch_foliage(mcf_plan *plan, double *paia, double *leafden);
+/* One call for a profile: one plan and one ring; per height mcf_plan_set_height, the day-chunk driver of mcf_runmicro1 and the
+ * fetches.  heights: nheights values > 0; out: nheights caller-allocated mcf_outputs structs, opt->out selecting the variables
+ * of every height; paia: NULL, or nheights pointers each of which may be NULL (mcf_plan_set_height's `paia`).  in->vegp.paia and
+ * in->vegp.leafden are not read and may be NULL; opt->reqhgt is ignored.  Vector forcing (static or layered vegetation) and
+ * coarse array forcing (array_forcing = 2); no `_multi` form.  A null or empty list and a height <= 0 or NaN are refused
+ * before any device is touched (MCF_ERR_ARG, the message starting with the entry's name). */
+int mcf_runmicro_heights(const mcf_grid_inputs *in, const mcf_options *opt, const double *heights, int32_t nheights,
+                         const double *const *paia, mcf_outputs *out);
 
 /* Diagnostics: evaluate one of the solver's lean device elementary functions
  * elementwise on host arrays (kind 0 exp, 1 log, 2 x/y, 3 sqrt, 4 1/x, 5 satvap

@@ -364,6 +364,7 @@ EXPORTS = (
     "mcf_snowrun_summary_days", "mcf_runmicrosnow_summary", "mcf_snowmodel1_summary",
     "mcf_microsnow_expand_coarse_device", "mcf_runmicrosnow2_coarse", "mcf_snowrun_create_coarse",
     "mcf_plan_set_day_layers", "mcf_snowrun_set_day_layers", "mcf_plan_fetch_mxtc",
+    "mcf_foliageden", "mcf_foliageden_device", "mcf_plan_set_height", "mcf_plan_fetch_foliage", "mcf_runmicro_heights",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -805,6 +806,17 @@ def load() -> C.CDLL:
         for fn in (lib.mcf_plan_set_day_layers, lib.mcf_snowrun_set_day_layers):
             fn.restype = C.c_int
             fn.argtypes = [P, c_int32_p, C.c_int32]
+    if hasattr(lib, "mcf_plan_set_height"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_foliageden.restype = C.c_int
+        lib.mcf_foliageden.argtypes = [C.c_int64, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p]
+        lib.mcf_foliageden_device.restype = C.c_int
+        lib.mcf_foliageden_device.argtypes = [C.c_int64, c_double_p, c_double_p, C.c_double, c_double_p, c_double_p, C.c_int32]
+        lib.mcf_plan_set_height.restype = C.c_int
+        lib.mcf_plan_set_height.argtypes = [P, C.c_double, c_double_p]
+        lib.mcf_plan_fetch_foliage.restype = C.c_int
+        lib.mcf_plan_fetch_foliage.argtypes = [P, c_double_p, c_double_p]
+        lib.mcf_runmicro_heights.restype = C.c_int
+        lib.mcf_runmicro_heights.argtypes = [GI, OP, c_double_p, C.c_int32, C.POINTER(c_double_p), OU]
     lib.mcf_precompute_terrain.restype = C.c_int
     lib.mcf_precompute_terrain.argtypes = [C.POINTER(TerrainIn), C.POINTER(TerrainOut), C.c_int32]
     lib.mcf_precompute_terrain_multi.restype = C.c_int

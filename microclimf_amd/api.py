@@ -228,6 +228,64 @@ def runmicro_depths_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping
     return res
 
 
+def foliageden(hgt, pai, z: float, device: int | None = None):
+    """The foliage profile of `.foliageden` (R/internal.R:937-946; include/mcf.h mcf_foliageden) at height `z`, elementwise over
+    `hgt` and `pai` (any shape, the same): -> (leafden, paia).  device=None: the host twin; an ordinal: one kernel launch there.
+    Both come from one copy of the arithmetic (closed-form gamma functions of shape 3/2)."""
+    lib = _abi.load()
+    h = np.asfortranarray(np.asarray(hgt, dtype=np.float64))
+    p = np.asfortranarray(np.asarray(pai, dtype=np.float64))
+    if h.shape != p.shape:
+        raise ValueError(f"foliageden: hgt {h.shape} and pai {p.shape} differ in shape")
+    ld, pa = np.empty(h.shape, dtype=np.float64, order="F"), np.empty(h.shape, dtype=np.float64, order="F")
+    if device is None:
+        _abi.check(lib.mcf_foliageden(int(h.size), _ptr(h), _ptr(p), float(z), _ptr(ld), _ptr(pa)))
+    else:
+        _abi.check(lib.mcf_foliageden_device(int(h.size), _ptr(h), _ptr(p), float(z), _ptr(ld), _ptr(pa), int(device)))
+    return ld, pa
+
+
+def runmicro_heights(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, heights, zref: float,
+                     lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, out: Sequence = (1,) * 10, *,
+                     pai_a=None, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                     days_per_chunk: int = 0, cells_per_block: int = 0) -> dict:
+    """A height profile from one plan (include/mcf.h mcf_runmicro_heights): the argument list of runmicro1Cpp (`dfsel`:
+    runmicro3Cpp; `coarse`: runmicro2Cpp_coarse, lat / lon then the rasters) with `heights` (each > 0) in place of reqhgt.
+    vegp needs no paia / leafden: both are derived on the device per height; `pai_a`: None, or one entry per height, each None or
+    the plant area above that height [rows, cols(, layers)] to use instead of the derived one.
+    -> {"heights": heights, variable: [one [rows, cols, tsteps] array per height]}: the bits of a Plan moved through the heights."""
+    lib = _abi.load()
+    hs = np.ascontiguousarray(np.atleast_1d(np.asarray(heights, dtype=np.float64))).ravel()
+    m = marshal(obstime, climdata, pointm, vegp, soilc, float(hs[0]) if hs.size else 0.0, zref, lat, lon, Sminp, Smaxp, tfact,
+                complete, mat, out, coarse is not None, device, days_per_chunk, cells_per_block, dfsel, coarse,
+                vegp_optional=("paia", "leafden"))
+    L = max(int(m.inputs.veg_layers), 1)
+    outs = (_abi.Outputs * max(hs.size, 1))()
+    res = {"heights": hs.copy()}
+    for h in range(hs.size):
+        _o, arrays = alloc_outputs(m)
+        outs[h] = _o
+        for k, a in arrays.items():
+            res.setdefault(k, []).append(a)
+    pp, keep = None, []
+    if pai_a is not None:
+        if len(pai_a) != hs.size:
+            raise ValueError(f"pai_a: one entry per height ({hs.size}), each None or an array")
+        pp = (_abi.c_double_p * max(hs.size, 1))()
+        for h, a in enumerate(pai_a):
+            if a is None:
+                continue
+            a = np.asfortranarray(np.asarray(a, dtype=np.float64))
+            if a.ndim == 3 and a.shape[2] > L:
+                a = a[:, :, :L]                  # as marshal() reads layered vegetation: the first L layers, no copy
+            if a.size != m.rows * m.cols * L:
+                raise ValueError(f"pai_a[{h}]: expected {m.rows} x {m.cols} x {L} values, got shape {a.shape}")
+            keep.append(a)
+            pp[h] = _ptr(a)
+    _abi.check(lib.mcf_runmicro_heights(C.byref(m.inputs), C.byref(m.options), _ptr(hs) if hs.size else None, int(hs.size), pp, outs))
+    return res
+
+
 def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon,
          Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, cells_per_block, dfsel=None, coarse=None,
          devices=None, n_blocks=0, dtm=None, diag=None):
@@ -564,6 +622,28 @@ class Plan:
         a = np.empty((self.rows, self.cols), dtype=np.float64, order="F")
         _abi.check(self._lib.mcf_plan_fetch_mxtc(self._p, a.ctypes.data_as(_abi.c_double_p)))
         return a
+
+    def set_height(self, h: float, pai_a=None):
+        """Re-target the plan to height `h` > 0 above ground (include/mcf.h mcf_plan_set_height): leafden and paia of every layer
+        are derived on the device from the resident hgt and pai, everything else stays; the next run has the bits of a plan
+        created at `h` with those planes.  `pai_a`: the plant area above `h`, [rows, cols(, layers)], instead of the derived one."""
+        L = max(int(self._m.inputs.veg_layers), 1)
+        a = None
+        if pai_a is not None:
+            a = np.asfortranarray(np.asarray(pai_a, dtype=np.float64))
+            if a.ndim == 3 and a.shape[2] > L:
+                a = a[:, :, :L]
+            if a.size != self.rows * self.cols * L:
+                raise ValueError(f"pai_a: expected {self.rows} x {self.cols} x {L} values, got shape {a.shape}")
+        _abi.check(self._lib.mcf_plan_set_height(self._p, float(h), _ptr(a)))
+
+    def fetch_foliage(self):
+        """(paia, leafden) as the plan holds them now, [rows, cols] or [rows, cols, layers]"""
+        L = int(self._m.inputs.veg_layers)
+        shape = (self.rows, self.cols) if L < 1 else (self.rows, self.cols, L)
+        pa, ld = np.empty(shape, dtype=np.float64, order="F"), np.empty(shape, dtype=np.float64, order="F")
+        _abi.check(self._lib.mcf_plan_fetch_foliage(self._p, _ptr(pa), _ptr(ld)))
+        return pa, ld
 
     def belowground(self):
         _abi.check(self._lib.mcf_plan_belowground(self._p))

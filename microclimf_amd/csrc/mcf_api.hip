@@ -555,14 +555,16 @@ int plan_shape(mcf_plan* p, const mcf_grid_inputs* in, const mcf_options* opt, i
 }
 
 // leaves: d_veg, d_soil, d_wsa, d_hor (given, or derived from the dtm), d_lats / d_lons (array forcing), valid_cells
-int upload_static(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* dtm) {
+// foliage_later: paia and leafden get their buffers only; mcf_plan_set_height fills them before the first run (mcf_runmicro_heights)
+int upload_static(mcf_plan* p, const mcf_grid_inputs* in, const mcf_dtm_spec* dtm, bool foliage_later) {
     int rc;
     const int64_t N = p->N;
     const double* veg[10] = {in->vegp.hgt, in->vegp.pai, in->vegp.x, in->vegp.gsmax, in->vegp.leafr,
                              in->vegp.leaft, in->vegp.clump, in->vegp.leafd, in->vegp.paia, in->vegp.leafden};
     const char* vegn[10] = {"hgt", "pai", "x", "gsmax", "leafr", "leaft", "clump", "leafd", "paia", "leafden"};
     for (int i = 0; i < 10; ++i)
-        if ((rc = upload(p, veg[i], N * p->layers, &p->d_veg[i], vegn[i]))) return rc;
+        if ((rc = foliage_later && i >= 8 ? p->dev.make(&p->d_veg[i], N * p->layers) : upload(p, veg[i], N * p->layers, &p->d_veg[i], vegn[i])))
+            return rc;
     const double* soil[13] = {in->soilc.Smin, in->soilc.Smax, in->soilc.gref, in->soilc.soilb, in->soilc.Psie,
                               in->soilc.Vq, in->soilc.Vm, in->soilc.Mc, in->soilc.rho, in->soilc.slope,
                               in->soilc.aspect, in->soilc.twi, in->soilc.svfa};
@@ -1019,7 +1021,7 @@ void mcf_plan_destroy(mcf_plan* p) {
 }
 
 static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_t ring_days, int32_t ring_slots, bool streamed,
-                       mcf_plan** out, const mcf_dtm_spec* dtm = nullptr) {
+                       mcf_plan** out, const mcf_dtm_spec* dtm = nullptr, bool foliage_later = false) {
     if (!out) return fail(MCF_ERR_ARG, "null plan pointer");
     *out = nullptr;
     int rc;
@@ -1034,7 +1036,7 @@ static int plan_create(const mcf_grid_inputs* in, const mcf_options* opt, int32_
     HIP_TRY(hipEventCreate(&p->ev1));
     SetupScratch s;      // (after the holder: on a refusal it goes first, as the set-up temporaries always have)
     if ((rc = plan_shape(p, in, opt, ring_days, ring_slots, streamed))) return rc;      // (with coarse_check)
-    if ((rc = upload_static(p, in, dtm))) return rc;
+    if ((rc = upload_static(p, in, dtm, foliage_later))) return rc;
     if ((rc = coarse_planes(p, in, s))) return rc;
     if ((rc = solver_constants(p, in, opt))) return rc;
     if ((rc = cell_images(p, in))) return rc;
@@ -1160,6 +1162,51 @@ int mcf_plan_set_twi_mean(mcf_plan* p, double mean) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
     p->twi_mean = mean;
     p->cells_ready = false;
+    return MCF_OK;
+}
+
+// ---- height profiles from one plan (include/mcf.h mcf_plan_set_height) ----------------------------------------
+// what every entry that takes a height above ground refuses, before any device is touched
+static int check_height_above(const char* who, double h) {
+    if (h > 0.0) return MCF_OK;
+    const std::string w = std::string(who) + ": ";
+    if (h == 0.0) return fail(MCF_ERR_ARG, w + "a height must be > 0 (the ground surface, reqhgt = 0: mcf_runmicro1 .. mcf_runmicro4)");
+    if (h < 0.0) return fail(MCF_ERR_ARG, w + "a height must be > 0 (below ground: mcf_runmicro_depths)");
+    return fail(MCF_ERR_ARG, w + "a height must be > 0, got NaN");
+}
+
+int mcf_plan_set_height(mcf_plan* p, double reqhgt, const double* paia) {
+    if (!p) return fail(MCF_ERR_ARG, "mcf_plan_set_height: null plan");
+    if (const int rc = check_height_above("mcf_plan_set_height", reqhgt)) return rc;
+    if (p->bg || !p->tiled || p->opt.reqhgt < 0.0)
+        return fail(MCF_ERR_STATE, "mcf_plan_set_height: a below-ground plan (reqhgt < 0 at creation) cannot be moved above ground");
+    if (p->d_dring) return fail(MCF_ERR_STATE, "mcf_plan_set_height: the plan has diagnostics enabled");
+    HIP_TRY(hipSetDevice(p->device));
+    // every launch that reads the planes, the images or the tile lists of the height before has finished
+    if (p->cells_inflight) { HIP_TRY(hipEventSynchronize(p->ev_cells_done)); p->cells_inflight = false; }
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    const int64_t n = p->N * p->layers;
+    mcf::launch_foliage(p->d_veg[0], p->d_veg[1], reqhgt, n, const_cast<double*>(p->d_veg[9]), const_cast<double*>(p->d_veg[8]), p->stream);
+    HIP_TRY(hipGetLastError());
+    if (paia) {      // (stream order: behind the kernel's store; read with the plan's row pitch, as vegp$paia is)
+        HIP_TRY(copy_in(p, const_cast<double*>(p->d_veg[8]), paia, p->cols * p->layers));
+        HIP_TRY(hipStreamSynchronize(p->stream));      // the caller's array has been read
+    }
+    p->opt.reqhgt = reqhgt;
+    p->g.reqhgt = reqhgt;
+    p->g.reqhgt2 = reqhgt < 0.00001 ? 0.00001 : reqhgt;      // cpp:2246-2247, as solver_constants
+    p->cells_ready = false;                                  // ensure_cells: the per-layer images and the fast / slow tile lists
+    return MCF_OK;
+}
+
+int mcf_plan_fetch_foliage(mcf_plan* p, double* paia, double* leafden) {
+    if (!p) return fail(MCF_ERR_ARG, "mcf_plan_fetch_foliage: null plan");
+    if (!p->d_veg[8] || !p->d_veg[9]) return fail(MCF_ERR_STATE, "mcf_plan_fetch_foliage: the plan holds no vegetation planes");
+    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    const size_t bytes = (size_t)(p->N * p->layers) * 8;
+    if (paia) HIP_TRY(hipMemcpy(paia, p->d_veg[8], bytes, hipMemcpyDeviceToHost));
+    if (leafden) HIP_TRY(hipMemcpy(leafden, p->d_veg[9], bytes, hipMemcpyDeviceToHost));
     return MCF_OK;
 }
 
@@ -2841,6 +2888,51 @@ static int run_oneshot(const mcf_grid_inputs* in, const mcf_options* opt, mcf_ou
         if ((rc = mcf_plan_fetch_pitched(p, 0, MCF_OUT_TZ, (int64_t)nd * 24, T - (int64_t)ndays * 24,
                                          out->var[MCF_OUT_TZ] + HS * (int64_t)ndays * 24, pitch)))
             return rc;
+    }
+    return mcf_plan_sync(p);
+}
+
+// ---- a height profile from one plan (include/mcf.h mcf_runmicro_heights) ------------------------------------
+int mcf_runmicro_heights(const mcf_grid_inputs* in, const mcf_options* opt_in, const double* heights, int32_t nheights,
+                         const double* const* paia, mcf_outputs* out) {
+    const std::string w = "mcf_runmicro_heights: ";
+    if (!heights || nheights < 1) return fail(MCF_ERR_ARG, w + "a null or empty list of heights");
+    for (int h = 0; h < nheights; ++h)
+        if (const int rc = check_height_above("mcf_runmicro_heights", heights[h])) return rc;
+    if (!in || !opt_in || !out) return fail(MCF_ERR_ARG, w + "null argument");
+    mcf_options opt = *opt_in;
+    opt.reqhgt = heights[0];
+    int rc = check_inputs(in, &opt);
+    if (rc) return rc;
+    if (in->array_forcing == 1) return fail(MCF_ERR_ARG, w + "vector forcing or coarse array forcing (array_forcing = 0 or 2)");
+    int nvars = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        nvars += opt.out[v] ? 1 : 0;
+        for (int h = 0; opt.out[v] && h < nheights; ++h)
+            if (!out[h].var[v]) return fail(MCF_ERR_ARG, w + "a requested output of height " + std::to_string(h) + " has a null buffer");
+    }
+    if ((rc = ensure_device(opt.device))) return rc;
+    const int64_t N = in->rows * in->cols, pitch = host_pitch(in), HS = pitch * in->cols;
+    const int ndays = (int)(in->tsteps / 24);
+    int chunk = opt.days_per_chunk;
+    if (chunk <= 0 && (rc = free_memory_chunk_days(N, ndays, 1, nvars + (in->array_forcing ? 15 : 0), 0.0, false, &chunk))) return rc;
+    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
+    // one plan and one ring: everything but the two foliage planes and reqhgt itself is set up once
+    mcf_plan* p = nullptr;
+    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr, true))) return rc;
+    PlanHolder holder(p);
+    for (int h = 0; h < nheights; ++h) {
+        if ((rc = mcf_plan_set_height(p, heights[h], paia ? paia[h] : nullptr))) return rc;
+        rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
+            for (int v = 0; v < MCF_NOUT; ++v)
+                if (opt.out[v])
+                    if (const int rcf = mcf_plan_fetch_pitched(p, 0, v, 0, (int64_t)nd * 24, out[h].var[v] + HS * (int64_t)d0 * 24, pitch))
+                        return rcf;
+            return MCF_OK;
+        });
+        if (rc) return rc;
+        for (int v = 0; v < MCF_NOUT; ++v)
+            if (opt.out[v]) fill_tail_na(out[h].var[v], in, ndays);
     }
     return mcf_plan_sync(p);
 }

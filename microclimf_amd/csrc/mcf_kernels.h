@@ -417,6 +417,8 @@ void launch_scatter_cells(const int32_t* list, int64_t ntiles_sub, const double*
                           int64_t tile_stride, int64_t day_doubles, int cpb, int ndays, hipStream_t s);
 void launch_belowground(const BelowArgs& a, hipStream_t s);
 void launch_selftest_math(int kind, const double* x, const double* y, double* out, int64_t n, hipStream_t s);
+// mcf_foliage.hip: `.foliageden` of n = cells x layers values at height z (hgt, pai -> leafden, paia), one lane each
+void launch_foliage(const double* hgt, const double* pai, double z, int64_t n, double* leafden, double* paia, hipStream_t s);
 
 // a plan's ring slot as another translation unit's kernels address it (mcf_snow.hip writes the snow-day microclimate into it):
 // views of the requested variables (has[v] = 0: not requested), the plan's stream, its cell count and its device

@@ -12,6 +12,7 @@ between the user's rasters and the solver call is restated with numpy on top of 
     .topidx / flowaccCpp                            mcf_topidx (host C++)
     leafrfromalb, find_lref, find_gref, fill_naCpp  mcf_leafrfromalb_device (device kernels, vegprep.py)
     runmicro1Cpp / runmicro3Cpp                     mcf_runmicro1 / mcf_runmicro3 (the hot path)
+    a loop of runmicro over reqhgt (the vignette)   mcf_runmicro_heights: one plan, .foliageden per height on the device (k_foliage)
     .sortvegp, .soilinit, .foliageden, .satvap ...  numpy, below, citing the R lines they follow
 
 Rasters are numpy arrays `[rows, cols]` (or `[rows, cols, layers]`), row 0 = northern edge as in terra; what a
@@ -335,11 +336,12 @@ def subset_day_layers(micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: M
 
 def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None,
                         out: Sequence = (1,) * 10, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None,
-                        device: int = 0, from_dtm: bool = False) -> dict:
+                        device: int = 0, from_dtm: bool = False, foliage: bool = True) -> dict:
     """Everything `.runmodel1Cpp` / `.runmodel3Cpp` do before calling the solver (R/internal.R:1067-1166 / 1347-1456):
     returns the keyword arguments of runmicro1Cpp, plus `dfsel` when the vegetation varies in time.  `from_dtm`: those of
     slr, apr, hor, twi, wsa, svf that are not given are left out of `soilc` and `dtm` = {z, res} is returned with the
-    arguments instead: the solver's plan derives them on the device (api.runmicro1Cpp, `dtm`)."""
+    arguments instead: the solver's plan derives them on the device (api.runmicro1Cpp, `dtm`).  `foliage=False` leaves
+    vegp$leafden and vegp$paia out (no `.foliageden` on the host): the height-profile entries derive them on the device."""
     res = dtm["res"]
     xres, yres = (res, res) if np.isscalar(res) else res
     if xres != yres:
@@ -363,7 +365,8 @@ def prepare_grid_inputs(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc
         sv["pai"][sv["hgt"] == 0] = 0.0
     if pai_a is not None:
         pai_a = intr(pai_a, n, subs)
-    sv["leafden"], sv["paia"] = foliageden(reqhgt, sv["hgt"], sv["pai"], pai_a)
+    if foliage:
+        sv["leafden"], sv["paia"] = foliageden(reqhgt, sv["hgt"], sv["pai"], pai_a)
     layers = sv["pai"].shape[2]
     dfsel = None
     if layers > 1:                                                       # R/internal.R:1391-1399
@@ -545,6 +548,73 @@ def runmicro_depths_summary(micropoint: Mapping, depths, vegp: Mapping, soilc: M
     res = api.runmicro_depths_summary(**a, depths=depths, tbp=tbp, periods=tab, nperiods=len(labels), vars=names, stats=stats,
                                       thresholds=thresholds, chunk_days=chunk_days, device=device)
     res["periods"] = labels
+    return res
+
+
+# ---- height profiles from one plan ----------------------------------------------------------------------------------------------
+def _height_inputs(micropoint, heights, vegp, soilc, dtm, pai_a, tfact, ter, device, out=(1,) * 10):
+    """runmicro1Cpp's (runmicro3Cpp's) arguments without reqhgt and without the two foliage planes, the heights, and `pai_a` per
+    height dealt to the time steps as prepare_grid_inputs deals runmicro's"""
+    heights = [float(h) for h in np.atleast_1d(np.asarray(heights, dtype=np.float64))]
+    if not heights or not all(h > 0 for h in heights):
+        raise ValueError("heights: one or more heights above ground (each > 0; the ground surface: runmicro, below ground: "
+                         "runmicro_depths)")
+    if pai_a is not None and len(pai_a) != len(heights):
+        raise ValueError(f"pai_a: one entry per height ({len(heights)}), each None or the plant area above that height")
+    a = prepare_grid_inputs(micropoint, heights[0], vegp, soilc, dtm, out=out, device=device, foliage=False, **ter)
+    a["tfact"] = float(tfact)
+    a.pop("reqhgt")
+    if pai_a is not None:
+        n, subs = micropoint["ntme"], micropoint["subs"]
+        pai_a = [None if p is None else intr(p, n, subs) for p in pai_a]
+    return a, heights, pai_a
+
+
+def runmicro_heights(micropoint: Mapping, heights, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, pai_a=None, tfact: float = 1.5,
+                     out: Sequence = (1,) * 10, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
+                     days_per_chunk: int = 0) -> dict:
+    """`runmicro()` at several heights above ground from ONE plan (include/mcf.h mcf_runmicro_heights): the vignette's loop over
+    `reqhgt` without repeating the terrain pre-compute, the wetness index, the uploads, the plan and the ring per height.  A
+    height is still a full solve (the canopy's own absorbed radiation depends on the foliage above the height); what only
+    depends on the height — vegp$paia and vegp$leafden — is derived on the device.  `heights`: each > 0; `pai_a`: None, or one
+    entry per height, each None or the plant area above that height.
+    -> {"heights": heights, "Tz": [one [rows, cols, steps] array per height], ...: likewise for every requested variable}"""
+    a, heights, pai_a = _height_inputs(micropoint, heights, vegp, soilc, dtm, pai_a, tfact,
+                                       dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device, out)
+    return api.runmicro_heights(**a, heights=heights, pai_a=pai_a, device=device, days_per_chunk=days_per_chunk)
+
+
+def runmicro_heights_summary(micropoint: Mapping, heights, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
+                             vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None, pai_a=None,
+                             tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
+                             chunk_days: int = 0) -> dict:
+    """runmicro_heights reduced over time on the device, as runmicro_summary reduces runmicro: one plan with period summaries,
+    per height set_height, summary_reset, the accumulate loop and the fetches.
+    -> {"heights": heights, variable: [per height {statistic: [rows, cols, nperiods]}], "periods": labels, "days": counted days}"""
+    names = (vars,) if isinstance(vars, str) else tuple(vars)
+    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    if not names or sum(out) != len(set(names)):
+        raise ValueError(f"vars: names of {api._abi.OUT_NAMES}")
+    a, heights, pai_a = _height_inputs(micropoint, heights, vegp, soilc, dtm, pai_a, tfact,
+                                       dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device, out)
+    tab, labels = summary_periods(a["obstime"], periods)
+    # (a plan is created with both foliage planes in place: zeros, which set_height replaces before the first run)
+    a["vegp"] = dict(a["vegp"], paia=np.zeros_like(a["vegp"]["pai"]), leafden=np.zeros_like(a["vegp"]["pai"]))
+    nd = len(tab)
+    ring = max(1, min(nd, int(chunk_days) if chunk_days else 8))
+    res = {"heights": np.array(heights), "periods": labels}
+    with api.Plan(**a, reqhgt=heights[0], ring_days=ring, device=device) as p:
+        vi, si = p.summary_enable(tab, names, stats, thresholds, nperiods=len(labels))
+        for h, hgt in enumerate(heights):
+            p.set_height(hgt, None if pai_a is None else pai_a[h])
+            p.summary_reset()
+            for d0 in range(0, nd, ring):
+                n = min(ring, nd - d0)
+                p.run_days(d0, n, 0)
+                p.summary_accumulate(0, 0, d0, n)
+            for v in vi:
+                res.setdefault(v, []).append({s: p.fetch_summary(v, s) for s in si})
+            res["days"] = p.summary_days()
     return res
 
 

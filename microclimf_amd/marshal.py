@@ -56,8 +56,9 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             Smaxp: float, tfact: float, complete: bool, mat: float,
             out: Sequence, array_forcing: bool, device: int = 0,
             days_per_chunk: int = 0, cells_per_block: int = 0, dfsel: Mapping | None = None,
-            coarse: Mapping | None = None, soilc_optional: Sequence = ()) -> Marshalled:
-    """`soilc_optional`: fields of soilc that may be missing (a NULL pointer: the plan derives them from the dtm).  `coarse` = {"rowpos": [rows], "colpos": [cols]} switches to coarse array forcing (mcf.h, array_forcing == 2):
+            coarse: Mapping | None = None, soilc_optional: Sequence = (), vegp_optional: Sequence = ()) -> Marshalled:
+    """`soilc_optional`: fields of soilc that may be missing (a NULL pointer: the plan derives them from the dtm); `vegp_optional`:
+    likewise for vegp (paia, leafden: runmicro_heights derives them per height).  `coarse` = {"rowpos": [rows], "colpos": [cols]} switches to coarse array forcing (mcf.h, array_forcing == 2):
     climdata = {temp, relhum, pres, swdown, difrad, lwdown, windspeed, winddir} and pointm are then
     [coarse_rows, coarse_cols, tsteps] arrays."""
     m = Marshalled()
@@ -119,6 +120,9 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             src = np.full(fshape, float(src))
         setattr(gi.pointm, f, m._f64(src, fshape, f"pointm${f}"))
     for f in _abi.VEGP_FIELDS:
+        if f in vegp_optional and vegp.get(f) is None:
+            setattr(gi.vegp, f, None)
+            continue
         src = vegp[f]
         if dfsel is not None:
             src = np.asfortranarray(np.asarray(src, dtype=np.float64))

@@ -30,7 +30,9 @@ res = {}
 for name, vegp2, rq0, heights in (("image7", uniform(0.05, 0.005), 0.05, [0.01, 0.02, 0.05, 0.1, 0.2, 0.5, 1.0]),
                                   ("image8", uniform(3.0, 10.0), 10.0, list(10 ** (np.arange(-10, 11) / 10)))):
     mp = F.subsetpointmodel(F.runpointmodel(weather, rq0, dem, vegp2, soilc2), tstep="month", what="tmax")
-    temps = [float(F.runmicro(mp, h, vegp2, soilc2, dem)["Tz"][1, 1, 131]) for h in heights]
+    # one plan for the whole profile (frontend.runmicro_heights): the vignette's loop over reqhgt without its repeated set-up
+    prof = F.runmicro_heights(mp, heights, vegp2, soilc2, dem, out=(1, 0, 0, 0, 0, 0, 0, 0, 0, 0))
+    temps = [float(tz[1, 1, 131]) for tz in prof["Tz"]]
     res[name + "_h"] = np.array(heights)
     res[name + "_t"] = np.array(temps)
     print(name, "zref", mp["zref"], "entries", len(mp["weather"]["temp"]))
