@@ -588,6 +588,31 @@ int mcf_runbioclim4_multi(const mcf_grid_inputs *in, const mcf_options *opt, con
  * (fine array forcing, reqhgt < 0, MCF_BIOCLIM_WHOLE set) or no call yet.  The matrices are the same bits either way: a
  * read-only observation, like mcf_plan_kernel_stats. */
 int mcf_bioclim_last_chunks(void);
+/* Soil bioclim variables at several depths from ONE streamed below-ground solve: mcf_runmicro_depths' driver (a streamed plan,
+ * mcf_plan_below_set_depths, sweep 1, then the solver in day chunks) with each chunk folded on the device into 21 doubles of
+ * running state per cell and depth and 8 per cell for the soil moisture, which below ground does not depend on the depth.
+ * Nothing of size cells x steps exists on either side.  Every matrix has the bits of mcf_runbioclim1 / 3 / 2 (coarse) with
+ * opt->reqhgt = depths[d] — the whole-series route, one solve per depth.
+ *   opt      reqhgt, out and complete are ignored: the run is made at depths[0] with complete = 1, as runbioclim*Cpp pass it.
+ *   sel      air must be 1 (Tz; tleaf does not exist below ground); out[v] selects as in mcf_runbioclim1; the quarter lists
+ *            must be in ascending order (what runbioclim passes) — mcf_runbioclim1 keeps taking any order.
+ *   in       vector forcing with static vegetation, or with in->veg_layers > 1: vegetation arrays [rows, cols, >= 14] under
+ *            the fixed dfsel of mcf_runbioclim3 (steps past the 336th belong to no layer, as there); coarse array forcing
+ *            (array_forcing == 2).  Fine array forcing (array_forcing == 1) is refused: mcf_runbioclim2 serves it.
+ *            tsteps >= 336 in whole days.
+ *   depths   as mcf_plan_below_set_depths: each < 0, any order, a depth may repeat, 1 <= ndepths <= MCF_MAX_DEPTHS.
+ *   chunk_days  days per solver chunk; 0: sized from free device memory as mcf_runmicro_depths does.
+ *   out      temp[d][v]: bio1..bio11 at depths[d]; moist[v]: bio12..bio19, once.  A selected variable with a null buffer — at
+ *            any listed depth for bio1..bio11 — is MCF_ERR_ARG.  NA_real_ where the depth's first Tz is NA (bio1..bio11, each
+ *            depth by its own first value) and where depths[0]'s is (bio12..bio19).
+ * Every refusal that needs no plan comes before a device is touched; every message starts with the entry's name.
+ * mcf_bioclim_last_chunks reports this entry's chunk launches of sweep 2. */
+typedef struct mcf_bioclim_depths_out {
+    double *temp[MCF_MAX_DEPTHS][11]; /* bio1..bio11 per depth, each [rows, cols] or NULL */
+    double *moist[8];                 /* bio12..bio19, once: below ground soilm does not depend on the depth */
+} mcf_bioclim_depths_out;
+int mcf_runbioclim_depths(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_bioclim_sel *sel, const double *depths,
+                          int32_t ndepths, int32_t chunk_days, mcf_bioclim_depths_out *out);
 
 /* ---- period summaries --------------------------------------------------------------------------------------------------
  * Per-cell statistics of the solver's outputs over caller-defined periods (what users of the reference do with

@@ -144,6 +144,11 @@ class DepthOutputs(C.Structure):
     _fields_ = [("tz", c_double_p * MAX_DEPTHS), ("soilm", c_double_p)]
 
 
+class BioclimDepthsOut(C.Structure):
+    """include/mcf.h mcf_bioclim_depths_out"""
+    _fields_ = [("temp", (c_double_p * 11) * MAX_DEPTHS), ("moist", c_double_p * 8)]
+
+
 class DepthSummaryOut(C.Structure):
     """include/mcf.h mcf_depth_summary_out"""
     _fields_ = [("tz", (c_double_p * NSTAT) * MAX_DEPTHS), ("soilm", c_double_p * NSTAT), ("days", c_int32_p)]
@@ -358,7 +363,7 @@ EXPORTS = (
     "mcf_plan_summary_reset", "mcf_runmicro_summary", "mcf_runmicro_summary_multi",
     "mcf_plan_below_set_depths", "mcf_plan_fetch_depth", "mcf_plan_fetch_depth_pitched", "mcf_plan_summary_enable_below",
     "mcf_plan_summary_fetch_depth", "mcf_runmicro_depths", "mcf_runmicro_depths_summary",
-    "mcf_bioclim_last_chunks",
+    "mcf_bioclim_last_chunks", "mcf_runbioclim_depths",
     "mcf_snowplan_summary_enable", "mcf_snowplan_summary_accumulate", "mcf_snowplan_summary_fetch", "mcf_snowplan_summary_days",
     "mcf_snowplan_summary_reset", "mcf_snowrun_summary_table", "mcf_snowrun_summary_enable", "mcf_snowrun_summary_fetch",
     "mcf_snowrun_summary_days", "mcf_runmicrosnow_summary", "mcf_snowmodel1_summary",
@@ -613,6 +618,10 @@ def load() -> C.CDLL:
         fn.argtypes = [GI, OP, C.POINTER(BioclimSel), C.POINTER(Multi), C.POINTER(BioclimOut)]
     lib.mcf_bioclim_last_chunks.restype = C.c_int
     lib.mcf_bioclim_last_chunks.argtypes = []
+    if hasattr(lib, "mcf_runbioclim_depths"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        lib.mcf_runbioclim_depths.restype = C.c_int
+        lib.mcf_runbioclim_depths.argtypes = [GI, OP, C.POINTER(BioclimSel), c_double_p, C.c_int32, C.c_int32,
+                                              C.POINTER(BioclimDepthsOut)]
     lib.mcf_snowenv_from_name.restype = C.c_int32
     lib.mcf_snowenv_from_name.argtypes = [C.c_char_p]
     SI = C.POINTER(SnowInputs)

@@ -499,6 +499,54 @@ def runbioclim4Cpp_coarse(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, 
                     coarse=coarse)
 
 
+def runbioclim_depths(obstime, climdata, pointm, vegp, soilc, depths, zref, lat, lon, Sminp, Smaxp, tfact, mat, out,
+                      wetq, dryq, hotq, colq, air=True, *, layered: bool = False, array_forcing: bool = False, coarse: Mapping | None = None,
+                      device: int = 0, chunk_days: int = 0, cells_per_block: int = 0) -> dict:
+    """Soil bioclim variables at several depths from one streamed below-ground solve (include/mcf.h mcf_runbioclim_depths):
+    runbioclim1Cpp's argument list with `depths` (each < 0, any order, at most _abi.MAX_DEPTHS) in place of reqhgt.  `air`
+    must be true (Tz).  `layered`: vegetation arrays [rows, cols, >= 14] under runbioclim3Cpp's fixed fourteen one-day layers.
+    `coarse` as for runmicro_depths: `climdata` / `pointm` are coarse arrays and `lat` / `lon` the per-cell lats / lons
+    (`array_forcing` without `coarse`, fine arrays, is refused by the library: runbioclim2Cpp serves it).
+    `chunk_days`: days per solver chunk (0: sized from free device memory).  The quarter lists must be ascending.
+    -> {"depths": depths, "bio1" .. "bio11": [ndepths, rows, cols], "bio12" .. "bio19": [rows, cols]} for the selected
+    variables; slab d of a matrix has the bits of runbioclim1Cpp(reqhgt = depths[d])."""
+    lib = _abi.load()
+    d, _ = _depth_list(depths, None, 0)
+    reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0          # (the library judges the list)
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, True, mat,
+                [1] * 10, bool(array_forcing) or coarse is not None, device, 0, cells_per_block, BIOCLIM_DFSEL if layered else None, coarse)
+    sel = _abi.BioclimSel()
+    keep = []
+    for name, q in (("wet", wetq), ("dry", dryq), ("hot", hotq), ("col", colq)):
+        arr = np.ascontiguousarray(np.asarray(q).astype(np.int32))
+        keep.append(arr)
+        setattr(sel, name + "q", arr.ctypes.data_as(_abi.c_int32_p))
+        setattr(sel, "n" + name, arr.size)
+    sel.air = 1 if air else 0
+    out = list(out)
+    if len(out) != _abi.NBIO:
+        raise ValueError("out must have 19 entries")
+    nd = min(d.size, _abi.MAX_DEPTHS)
+    bo = _abi.BioclimDepthsOut()
+    res = {"depths": d.copy()}
+    for v in range(_abi.NBIO):
+        sel.out[v] = 1 if out[v] else 0
+        if not out[v]:
+            continue
+        if v < 11:
+            # (slab i is one Fortran-ordered [rows, cols] matrix)
+            a = np.empty((nd, m.cols, m.rows), dtype=np.float64).transpose(0, 2, 1)
+            for i in range(nd):
+                bo.temp[i][v] = a[i].ctypes.data_as(_abi.c_double_p)
+        else:
+            a = np.empty((m.rows, m.cols), dtype=np.float64, order="F")
+            bo.moist[v - 11] = a.ctypes.data_as(_abi.c_double_p)
+        res[f"bio{v + 1}"] = a
+    _abi.check(lib.mcf_runbioclim_depths(C.byref(m.inputs), C.byref(m.options), C.byref(sel), _ptr(d), int(d.size), int(chunk_days),
+                                         C.byref(bo)))
+    return res
+
+
 def bioclim_last_chunks() -> int:
     """Solver chunk launches of this thread's last runbioclim*Cpp call (include/mcf.h mcf_bioclim_last_chunks): > 0 — the
     streamed sink ran; 0 — the whole-series one.  The matrices do not tell."""

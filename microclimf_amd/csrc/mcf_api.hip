@@ -902,6 +902,8 @@ int free_memory_chunk_days(int64_t N, int ndays, int sharers, int slabs, double 
 }
 // per-cell doubles of a streamed below-ground plan's state with D depths: dmean and a ybuf per depth, wrap, prev, the two sums
 double below_state_doubles(int D, int ndays) { return (1.0 + D) * ndays + 2 * mcf::kBelowWin + 2; }
+// ... and of the bioclim sink on it: 21 temperature rows per depth and 8 moisture rows, then the matrices of the finish
+double bioclim_state_doubles(int D) { return (mcf::kBioTempRows + 11.0) * D + 2 * mcf::kBioMoistRows; }
 
 // steps past the last whole day of a caller's [rows, cols, tsteps] array: never computed by the reference, they stay NA (cpp:2116)
 void fill_tail_na(double* buf, const mcf_grid_inputs* in, int ndays) {
@@ -2691,15 +2693,116 @@ int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, cons
 }
 
 // ---- below ground at several depths from one solve (include/mcf.h mcf_runmicro_depths) ----------------------
-// both one-call entries: `out` (every step of every depth) or `spec` + `sout` (the period summaries)
+// the bioclim sink's arguments (mcf_runbioclim_depths)
+struct BioDepthsSink {
+    const mcf_bioclim_sel* sel;
+    mcf_bioclim_depths_out* out;
+};
+// what that sink can be refused for without a plan or a device
+static int check_bioclim_depths(const std::string& w, const mcf_grid_inputs* in, const BioDepthsSink* bio, int32_t D) {
+    const mcf_bioclim_sel* sel = bio->sel;
+    if (!sel || !bio->out) return fail(MCF_ERR_ARG, w + "null argument");
+    if (sel->air != 1) return fail(MCF_ERR_ARG, w + "air = 0 is not taken: tleaf does not exist below ground (air = 1: Tz)");
+    if (in->array_forcing == 1)
+        return fail(MCF_ERR_ARG, w + "fine array forcing is not taken (its inputs are cells x steps by themselves): mcf_runbioclim2 serves it");
+    const int64_t T = in->tsteps;
+    if (T < 336 || T % 24 != 0) return fail(MCF_ERR_ARG, w + "runbioclim needs >= 336 hourly steps in whole days");
+    const int32_t* q[4] = {sel->wetq, sel->dryq, sel->hotq, sel->colq};
+    const int32_t nq[4] = {sel->nwet, sel->ndry, sel->nhot, sel->ncol};
+    for (int i = 0; i < 4; ++i) {
+        if (nq[i] < 0 || (nq[i] > 0 && !q[i])) return fail(MCF_ERR_ARG, w + "bad quarter index vector");
+        for (int j = 0; j < nq[i]; ++j) {
+            if (q[i][j] < 0 || q[i][j] >= T) return fail(MCF_ERR_ARG, w + "quarter index outside the time series");
+            if (j > 0 && q[i][j] < q[i][j - 1])
+                return fail(MCF_ERR_ARG, w + "a quarter list that is not in ascending order is not taken by the streamed sink: "
+                                             "mcf_runbioclim1 (the whole-series form, one depth per call) takes any order");
+        }
+    }
+    for (int v = 0; v < MCF_NBIO; ++v) {
+        if (!sel->out[v]) continue;
+        if (v >= 11 && !bio->out->moist[v - 11])
+            return fail(MCF_ERR_ARG, w + "requested bioclim variable bio" + std::to_string(v + 1) + " has a null buffer");
+        for (int d = 0; v < 11 && d < D; ++d)
+            if (!bio->out->temp[d][v])
+                return fail(MCF_ERR_ARG, w + "requested bioclim variable bio" + std::to_string(v + 1) + " has a null buffer at depth " +
+                                             std::to_string(d));
+    }
+    return MCF_OK;
+}
+// the sink itself on a prepared plan: the accumulate launches' arguments and the state, [D][21][N] then [8][N]
+static int bioclim_depths_begin(mcf_plan* p, const mcf_bioclim_sel* sel, mcf::BioAccDepthsArgs& acc) {
+    if (!p->tiled) return fail(MCF_ERR_STATE, "bioclim: the streamed sink expects the tiled ring");
+    const int D = (int)p->depths.size();
+    const mcf::RingView sm = ring_view(p, 0, MCF_OUT_SOILM), tz = depth_view(p, 0, 0);
+    acc.soilm = sm.base; acc.tz0 = tz.base;
+    acc.ring_tile_stride = tz.tile_stride; acc.ring_day_stride = tz.day_stride;
+    if (D > 1) {
+        const mcf::RingView x = depth_view(p, 0, 1);
+        acc.tzx = x.base; acc.tzx_tile_stride = x.tile_stride; acc.tzx_day_stride = x.day_stride;
+        acc.tzx_stride = (int64_t)p->ring_slots * p->ntiles * p->tg_tile_stride;
+    }
+    acc.N = p->N; acc.ntiles = p->ntiles; acc.cpb = p->cpb; acc.ndepths = D;
+    const int32_t* q[4] = {sel->wetq, sel->dryq, sel->hotq, sel->colq};
+    const int32_t nq[4] = {sel->nwet, sel->ndry, sel->nhot, sel->ncol};
+    if (const int rc = upload_quarters(p, q, nq, acc.q)) return rc;
+    return p->dev.make(&acc.state, ((int64_t)mcf::kBioTempRows * D + mcf::kBioMoistRows) * p->N);
+}
+// days [d0, d0 + nd) of slot 0, behind the run that filled them, into the state
+static int bioclim_depths_fold(mcf_plan* p, const mcf_bioclim_sel* sel, mcf::BioAccDepthsArgs& acc, int d0, int nd) {
+    const int32_t* q[4] = {sel->wetq, sel->dryq, sel->hotq, sel->colq};
+    const int32_t nq[4] = {sel->nwet, sel->ndry, sel->nhot, sel->ncol};
+    acc.day0 = d0; acc.ndays = nd;
+    for (int i = 0; i < 4; ++i) {
+        acc.qlo[i] = (int32_t)(std::lower_bound(q[i], q[i] + nq[i], d0 * 24) - q[i]);
+        acc.qhi[i] = (int32_t)(std::lower_bound(q[i], q[i] + nq[i], (d0 + nd) * 24) - q[i]);
+    }
+    mcf::launch_bioclim_acc_depths(acc, p->stream);
+    HIP_TRY(hipGetLastError());
+    return MCF_OK;
+}
+// the two finishes, then a pitched download per (depth, variable)
+static int bioclim_depths_finish(mcf_plan* p, const mcf_grid_inputs* in, const BioDepthsSink* bio, const mcf::BioAccDepthsArgs& acc) {
+    const int64_t N = p->N;
+    const int D = acc.ndepths;
+    double* out = nullptr;      // [D][11][N], then [8][N]
+    int rc = p->dev.make(&out, (11 * (int64_t)D + mcf::kBioMoistRows) * N);
+    if (rc) return rc;
+    mcf::launch_bioclim_fin_temp(acc.state, N, D, out, p->stream);
+    mcf::BioFinArgs fin{};
+    fin.N = N; fin.tsteps = (int)p->tsteps; fin.state = acc.state + (int64_t)mcf::kBioTempRows * D * N; fin.bio = out + 11 * (int64_t)D * N;
+    fin.cellc = p->d_cellc; fin.ntiles_total = p->ntiles; fin.cpb = p->cpb; fin.daylayer = p->d_daylayer; fin.tt = p->d_tt;
+    if (p->coarse) {      // as run_bioclim: the second pass taps the resident coarse soil moisture series
+        fin.cforce = p->d_force;
+        fin.cstride = (int64_t)p->crows * p->ccols * std::max<int64_t>(p->tsteps, 1);
+        fin.crows = p->crows; fin.ccols = p->ccols;
+        fin.crowpos = p->d_crowpos; fin.ccolpos = p->d_ccolpos; fin.rows = (int32_t)p->rows;
+    }
+    mcf::launch_bioclim_fin_moist(fin, acc.state, p->stream);
+    HIP_TRY(hipGetLastError());
+    const int64_t pitch = host_pitch(in);
+    for (int v = 0; v < MCF_NBIO; ++v) {
+        if (!bio->sel->out[v]) continue;
+        if (v >= 11) {
+            if ((rc = to_host(p, bio->out->moist[v - 11], fin.bio + (int64_t)(v - 11) * N, (size_t)N * 8, pitch))) return rc;
+            continue;
+        }
+        for (int d = 0; d < D; ++d)
+            if ((rc = to_host(p, bio->out->temp[d][v], out + ((int64_t)d * 11 + v) * N, (size_t)N * 8, pitch))) return rc;
+    }
+    return mcf_plan_sync(p);
+}
+
+// the one-call entries: `out` (every step of every depth), `spec` + `sout` (the period summaries) or `bio` (the bioclim variables)
 static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
                       const double* tbp, mcf_depth_outputs* out, const mcf_summary_spec* spec, int32_t chunk_days,
-                      mcf_depth_summary_out* sout) {
+                      mcf_depth_summary_out* sout, const BioDepthsSink* bio = nullptr) {
     const std::string w = std::string(who) + ": ";
-    if (!in || !opt_in || (!out && !sout) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
-    int rc = check_depths(who, depths, D, tbp, opt_in->complete != 0, in->array_forcing != 0);
-    if (rc) return rc;
+    if (!in || !opt_in || (!out && !sout && !bio) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
     mcf_options opt = *opt_in;
+    if (bio) opt.complete = 1;                                          // cpp:3576: complete = true
+    int rc = check_depths(who, depths, D, tbp, opt.complete != 0, in->array_forcing != 0);
+    if (rc) return rc;
+    if (bio && (rc = check_bioclim_depths(w, in, bio, D))) return rc;
     opt.reqhgt = depths[0];
     if ((rc = check_inputs(in, &opt))) return rc;
     const int64_t T = in->tsteps;
@@ -2707,7 +2810,9 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     if (ndays < 1) return fail(MCF_ERR_ARG, w + "the series is shorter than a day");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, w + "negative chunk_days");
     for (int v = 0; v < MCF_NOUT; ++v) opt.out[v] = 0;
-    if (out) {
+    if (bio) {
+        opt.out[MCF_OUT_TZ] = opt.out[MCF_OUT_SOILM] = 1;               // cpp:3569-3575 with air = 1
+    } else if (out) {
         for (int d = 0; d < D; ++d)
             if (!out->tz[d]) return fail(MCF_ERR_ARG, w + "tz[" + std::to_string(d) + "] is a null buffer");
         opt.out[MCF_OUT_TZ] = 1;
@@ -2731,7 +2836,7 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     int chunk = out ? opt.days_per_chunk : chunk_days;
     // (the solver's variables, the forcing ring, the chunk's Tg ring and the D - 1 depth slabs per day)
     if (chunk <= 0 && (rc = free_memory_chunk_days(in->rows * in->cols, ndays, 1, nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1),
-                                                   below_state_doubles(D, ndays), tail, &chunk)))
+                                                   below_state_doubles(D, ndays) + (bio ? bioclim_state_doubles(D) : 0.0), tail, &chunk)))
         return rc;
     chunk = std::max(1, std::min(chunk, ndays));
     mcf_plan* p = nullptr;
@@ -2740,9 +2845,15 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
     if ((rc = mcf_plan_below_prepare(p, in))) return rc;
     if (sout && (rc = mcf_plan_summary_enable_below(p, spec))) return rc;
+    mcf::BioAccDepthsArgs acc{};
+    if (bio && (rc = bioclim_depths_begin(p, bio->sel, acc))) return rc;
     const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
     rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
         if (sout) return mcf_plan_summary_accumulate(p, 0, 0, d0, nd);
+        if (bio) {
+            ++g_bioclim_chunks;
+            return bioclim_depths_fold(p, bio->sel, acc, d0, nd);
+        }
         // ... the last chunk with the steps it left behind its days
         const int64_t steps = (int64_t)nd * 24 + (d0 + nd == ndays ? T - (int64_t)ndays * 24 : 0);
         for (int d = 0; d < D; ++d)
@@ -2751,6 +2862,7 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
         return mcf_plan_fetch_pitched(p, 0, MCF_OUT_SOILM, 0, (int64_t)nd * 24, out->soilm + HS * (int64_t)d0 * 24, pitch);
     });
     if (rc) return rc;
+    if (bio) return bioclim_depths_finish(p, in, bio, acc);
     if (sout) {
         for (int k = 0; k < MCF_NSTAT; ++k) {
             if (!spec->stat[k]) continue;
@@ -2773,6 +2885,23 @@ int mcf_runmicro_depths_summary(const mcf_grid_inputs* in, const mcf_options* op
                                 const double* tbp, const mcf_summary_spec* spec, int32_t chunk_days, mcf_depth_summary_out* out) {
     if (!out || !spec) return fail(MCF_ERR_ARG, "mcf_runmicro_depths_summary: null argument");
     return run_depths("mcf_runmicro_depths_summary", in, opt, depths, ndepths, tbp, nullptr, spec, chunk_days, out);
+}
+
+// the bioclim sink on that driver (include/mcf.h); layered vegetation as run_bioclim takes it
+int mcf_runbioclim_depths(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const double* depths,
+                          int32_t ndepths, int32_t chunk_days, mcf_bioclim_depths_out* out) {
+    const char* who = "mcf_runbioclim_depths";
+    g_bioclim_chunks = 0;
+    if (!in || !opt || !sel || !out) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
+    mcf_grid_inputs in_l = *in;
+    if (in->veg_layers > 1) {      // runbioclim3Cpp's fixed dfsel: fourteen one-day layers; later days belong to no layer
+        if (in->veg_layers < 14) return fail(MCF_ERR_ARG, std::string(who) + ": layered vegetation needs the fourteen layers of runbioclim3Cpp");
+        in_l.veg_layers = 14; in_l.lyr_st = kBioSt; in_l.lyr_ed = kBioEd;
+    }
+    const BioDepthsSink bio{sel, out};
+    const int rc = run_depths(who, &in_l, opt, depths, ndepths, nullptr, nullptr, nullptr, chunk_days, nullptr, &bio);
+    if (rc && g_err.compare(0, strlen(who), who) != 0) g_err = std::string(who) + ": " + g_err;      // (the shared checks' messages)
+    return rc;
 }
 
 int64_t mcf_plan_valid_cells(const mcf_plan* p) { return p ? p->valid_cells : 0; }

@@ -298,6 +298,33 @@ struct BioFinArgs {
     int32_t rows;
 };
 void launch_bioclim_fin(const BioFinArgs& a, hipStream_t s);
+// ---- the streamed sink below ground at several depths (mcf_bioclim.hip; include/mcf.h mcf_runbioclim_depths) ----
+// The 29 state rows split: rows 0..20 (kBioTempRows, the temperature rows above) once per depth, rows 21..28 (kBioMoistRows)
+// once — below ground soilm is the solver's own and no depth changes it.  State [ndepths][kBioTempRows][N], then
+// [kBioMoistRows][N]: bio12's sum, the maximum, the minimum, the sum over all steps, the four quarter sums.
+constexpr int kBioTempRows = 21, kBioMoistRows = 8;
+struct BioAccDepthsArgs {
+    // the slot's soilm and depth 0's Tz (the slot's own variables): block of (tile, day of the chunk) at tile * ring_tile_stride
+    // + day * ring_day_stride
+    const double *soilm, *tz0;
+    int64_t ring_tile_stride, ring_day_stride;
+    // depth 1's slab beside the ring (null with one depth), depth d's (d - 1) * tzx_stride behind it
+    const double* tzx;
+    int64_t tzx_stride, tzx_tile_stride, tzx_day_stride;
+    int64_t N, ntiles;
+    int32_t cpb, ndepths;      // 16, 21, 32 or 42
+    int32_t day0, ndays;       // the chunk, as in BioAccArgs; likewise q, qlo, qhi
+    const int32_t* q[4];
+    int32_t qlo[4], qhi[4];
+    double* state;
+};
+// k_bioclim_acc's folds, term for term, over every depth's Tz (the grid's y) and, in a launch of its own, over soilm
+void launch_bioclim_acc_depths(const BioAccDepthsArgs& a, hipStream_t s);
+// The finish in two parts.  Moisture (BioFinArgs: `state` = the moisture rows, `bio` = [8][N] for bio12..bio19; the variance's
+// second pass once, not per depth) with the NA rule read from `first`, depth 0's row 0.  Temperature: bio1..bio11 of every depth,
+// state [ndepths][kBioTempRows][N] -> bio [ndepths][11][N], each depth under its own NA rule (cpp:3505-3506).
+void launch_bioclim_fin_moist(const BioFinArgs& a, const double* first, hipStream_t s);
+void launch_bioclim_fin_temp(const double* state, int64_t N, int ndepths, double* bio, hipStream_t s);
 void launch_fill(double* p, int64_t n, double v, hipStream_t s);
 // ---- period summaries (mcf_summary.hip; include/mcf.h "period summaries") ------------------------------------
 // State [selected var][period][state row][N]: row 0 the running sum (R's NA_real_ once a NaN has been met: it carries the NA

@@ -1799,6 +1799,43 @@ void launch_bioclim_acc(const BioAccArgs& a, hipStream_t s) {
 // value is the cell's bilinear tap of the resident coarse series, as k_solve's lanes take it (per lane or staged in LDS: the
 // same bits, CoarseTap::mix).  The step's field is a scalar address, the cell's four neighbours four 32-bit byte offsets made
 // once; the loop over the steps holds no per-lane address arithmetic.
+// the variance's second pass (cpp:3391-3398) of cell c: the sum of squares about `mean` of the solver's soil moisture of every step,
+// made again (BioFinArgs)
+template <bool COARSE>
+__device__ __forceinline__ double bio_soilm_ss(const BioFinArgs& a, int64_t c, double mean) {
+    const double NA = na_real();
+    const int T = a.tsteps;
+    const uint32_t cc = (uint32_t)c, tile = cc / (uint32_t)a.cpb, cl = cc - tile * (uint32_t)a.cpb;
+    const int64_t IMG = tile_image_doubles_dev(a.cpb);
+    double ss = 0.0;
+    int layer = -2;
+    double smin = 0.0, invrge = 0.0, eta = 0.0, rge = 0.0;
+    bool valid = false;
+    Canary cn;
+    const uint32_t rows = COARSE ? (uint32_t)a.rows : 1u, col = cc / rows;
+    const CoarseTap tap(COARSE ? a.crowpos[cc - col * rows] : 0.0, COARSE ? a.ccolpos[col] : 0.0, a.crows, a.ccols);
+    for (int d = 0; d < T / 24; ++d) {
+        const int l = a.daylayer ? a.daylayer[d] : 0;
+        if (l != layer) {
+            layer = l;
+            if (l >= 0) {
+                const double* img = a.cellc + ((int64_t)l * a.ntiles_total + tile) * IMG + cl;
+                smin = img[CF_SMIN * a.cpb]; invrge = img[CF_INVRGE * a.cpb]; eta = img[CF_ETA * a.cpb]; rge = img[CF_RGE * a.cpb];
+                valid = ((int)img[CF_FLAGS * a.cpb] & FL_VALID) != 0;
+            }
+        }
+        const double* sp = COARSE ? nullptr : a.tt + ((int64_t)d * TF_COUNT + TF_SOILMP) * 24;
+        for (int h = 0; h < 24; ++h) {
+            double smp;
+            if constexpr (COARSE) smp = tap(coarse_day_field(a.cforce, a.cstride, a.crows, a.ccols, TF_SOILMP, d, h));
+            else smp = sp[h];
+            const double v = (l >= 0 && valid) ? soil_spread<false>(smp, smin, invrge, eta, rge, cn) : NA;
+            const double dlt = v - mean;
+            ss += dlt * dlt;
+        }
+    }
+    return ss;
+}
 template <bool COARSE>
 __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1830,36 +1867,7 @@ __global__ __launch_bounds__(64) void k_bioclim_fin(BioFinArgs a) {
     {
         const double me = S(21) / 288.0;
         const double mean = S(24) / T;
-        // second pass over the soil moisture series: the solver's value of every step, made again (BioFinArgs)
-        const uint32_t cc = (uint32_t)c, tile = cc / (uint32_t)a.cpb, cl = cc - tile * (uint32_t)a.cpb;
-        const int64_t IMG = tile_image_doubles_dev(a.cpb);
-        double ss = 0.0;
-        int layer = -2;
-        double smin = 0.0, invrge = 0.0, eta = 0.0, rge = 0.0;
-        bool valid = false;
-        Canary cn;
-        const uint32_t rows = COARSE ? (uint32_t)a.rows : 1u, col = cc / rows;
-        const CoarseTap tap(COARSE ? a.crowpos[cc - col * rows] : 0.0, COARSE ? a.ccolpos[col] : 0.0, a.crows, a.ccols);
-        for (int d = 0; d < T / 24; ++d) {
-            const int l = a.daylayer ? a.daylayer[d] : 0;
-            if (l != layer) {
-                layer = l;
-                if (l >= 0) {
-                    const double* img = a.cellc + ((int64_t)l * a.ntiles_total + tile) * IMG + cl;
-                    smin = img[CF_SMIN * a.cpb]; invrge = img[CF_INVRGE * a.cpb]; eta = img[CF_ETA * a.cpb]; rge = img[CF_RGE * a.cpb];
-                    valid = ((int)img[CF_FLAGS * a.cpb] & FL_VALID) != 0;
-                }
-            }
-            const double* sp = COARSE ? nullptr : a.tt + ((int64_t)d * TF_COUNT + TF_SOILMP) * 24;
-            for (int h = 0; h < 24; ++h) {
-                double smp;
-                if constexpr (COARSE) smp = tap(coarse_day_field(a.cforce, a.cstride, a.crows, a.ccols, TF_SOILMP, d, h));
-                else smp = sp[h];
-                const double v = (l >= 0 && valid) ? soil_spread<false>(smp, smin, invrge, eta, rge, cn) : NA;
-                const double dlt = v - mean;
-                ss += dlt * dlt;
-            }
-        }
+        const double ss = bio_soilm_ss<COARSE>(a, c, mean);
         const double sd = T <= 1 ? NA : sqrt(ss / (T - 1));
         bio[11] = me;
         bio[12] = S(22);
@@ -1874,6 +1882,36 @@ void launch_bioclim_fin(const BioFinArgs& a, hipStream_t s) {
     if (a.N <= 0) return;
     if (a.cforce) hipLaunchKernelGGL(k_bioclim_fin<true>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_bioclim_fin<false>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a);
+}
+// the moisture rows alone (mcf_kernels.h launch_bioclim_fin_moist): k_bioclim_fin's bio12..bio19, expression for expression
+template <bool COARSE>
+__global__ __launch_bounds__(64) void k_bioclim_fin_moist(BioFinArgs a, const double* __restrict__ first) {
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t N = a.N;
+    if (c >= N) return;
+    const double* st = a.state + c;
+    auto M = [&](int row) { return st[N * row]; };
+    double* out = a.bio + c;
+    const double NA = na_real();
+    if (isnan(first[c])) {
+        for (int b = 0; b < kBioMoistRows; ++b) out[N * b] = NA;
+        return;
+    }
+    const int T = a.tsteps;
+    const double me = M(0) / 288.0;
+    const double mean = M(3) / T;
+    const double ss = bio_soilm_ss<COARSE>(a, c, mean);
+    const double sd = T <= 1 ? NA : sqrt(ss / (T - 1));
+    out[0] = me;
+    out[N] = M(1);
+    out[N * 2] = M(2);
+    out[N * 3] = me / sd;                                               // cpp:3402 (sic: mean / sd)
+    for (int qi = 0; qi < 4; ++qi) out[N * (4 + qi)] = M(4 + qi) / 72.0;     // cpp:3325
+}
+void launch_bioclim_fin_moist(const BioFinArgs& a, const double* first, hipStream_t s) {
+    if (a.N <= 0) return;
+    if (a.cforce) hipLaunchKernelGGL(k_bioclim_fin_moist<true>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a, first);
+    else hipLaunchKernelGGL(k_bioclim_fin_moist<false>, dim3((unsigned)((a.N + 63) / 64)), dim3(64), 0, s, a, first);
 }
 
 // ------------------------------------------------------------------------------------

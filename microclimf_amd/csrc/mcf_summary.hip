@@ -18,41 +18,15 @@
 
 #include "../../include/mcf.h"
 #include "mcf_kernels.h"
+#include "mcf_tilestage.hpp"
 
 namespace mcf {
 namespace {
 
 constexpr unsigned long long kNaBits = 0x7FF00000000007A2ull;      // R's NA_real_
-constexpr int kSumLanes = 256;
 
 __device__ __forceinline__ double na_value() { return __longlong_as_double((long long)kNaBits); }
 __device__ __forceinline__ bool is_na_bits(double x) { return (unsigned long long)__double_as_longlong(x) == kNaBits; }
-
-// Geometry of a workgroup for `CPB` cells per tile: TPW tiles (<= 256 cells, one lane each), their blocks S doubles apart in
-// LDS.  The pad keeps the lanes of neighbouring tiles, which read the same place of their blocks, on different banks.
-template <int CPB>
-struct SumGeom {
-    static constexpr int B = RING_BLOCK(CPB);
-    static constexpr int TPW = kSumLanes / CPB;                                   // 16, 12, 8, 6
-    static constexpr int PAD = CPB == 16 ? 16 : CPB == 21 ? 22 : CPB == 42 ? 10 : 0;
-    static constexpr int S = B + PAD;
-    static constexpr int HALF = B / 2;                                            // 16-byte pieces per block
-    static constexpr int NLD = TPW * HALF / kSumLanes;                            // pieces per lane: 12 for every CPB
-    static_assert(TPW * HALF % kSumLanes == 0, "the blocks of a workgroup divide evenly over its lanes");
-    static_assert(S % 2 == 0, "blocks stay 16-byte aligned in LDS");
-};
-
-// the blocks of one day of the workgroup's tiles (`day` = the first tile's block) into registers: piece j * 256 + lane of the
-// tiles' pieces taken one after the other, so that a wave reads 1 KiB of one block at a time; tiles past the ring's last: none
-template <int CPB>
-__device__ __forceinline__ void load_day(double2 (&r)[SumGeom<CPB>::NLD], const double* day, int64_t tile_stride, int tid, int ntl) {
-    using G = SumGeom<CPB>;
-#pragma unroll
-    for (int j = 0; j < G::NLD; ++j) {
-        const int idx = j * kSumLanes + tid, t = idx / G::HALF, o = idx - t * G::HALF;
-        r[j] = t < ntl ? *reinterpret_cast<const double2*>(day + (int64_t)t * tile_stride + 2 * o) : double2{0.0, 0.0};
-    }
-}
 
 template <int CPB>
 __global__ __launch_bounds__(kSumLanes) void k_summary_acc(SummaryAccArgs a) {
@@ -94,11 +68,7 @@ __global__ __launch_bounds__(kSumLanes) void k_summary_acc(SummaryAccArgs a) {
         load_day<CPB>(r, src + (int64_t)(a.slot_day0 + d - a.day0) * a.day_stride, a.tile_stride, tid, ntl);
         for (int e = d;;) {
             __syncthreads();                                      // the day before has left the LDS
-#pragma unroll
-            for (int j = 0; j < G::NLD; ++j) {
-                const int idx = j * kSumLanes + tid, t = idx / G::HALF, o = idx - t * G::HALF;
-                if (t < ntl) *reinterpret_cast<double2*>(lds + t * G::S + 2 * o) = r[j];
-            }
+            store_day<CPB>(lds, r, tid, ntl);
             __syncthreads();
             const int nx = a.next_same[e];                        // the period's next day (>= the series' days: none)
             if (nx < end) load_day<CPB>(r, src + (int64_t)(a.slot_day0 + nx - a.day0) * a.day_stride, a.tile_stride, tid, ntl);

@@ -1702,6 +1702,40 @@ def runbioclim(climdata: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
     return res
 
 
+def runbioclim_depths(climdata: Mapping, depths, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, zref: float = 2.0,
+                      windhgt: float | None = None, soilm=None, pai_a=None, tfact: float = 1.5, out: Sequence = (1,) * 19,
+                      vegpisannual: bool = True, device: int = 0, chunk_days: int = 0, _bioclim=None, _terrain=None) -> dict:
+    """`runbioclim` for soil temperatures at several depths from ONE solve (api.runbioclim_depths, mcf_runbioclim_depths):
+    `runbioclim(climdata, reqhgt = depths[0], ..., temp = "air")` step by step — `biosel`, the quarters, the vegetation, and one
+    `runpointmodel` at depths[0]: of the point model's series only `Tbz` depends on the height, and the run is made with
+    complete = 1, which never reads it — with the library call replaced by the one that folds every depth.  `mask(bior, dtm)`
+    is applied to every matrix.  Returns {"depths", "bio1" .. "bio11": [ndepths, rows, cols], "bio12" .. "bio19": [rows, cols]}.
+    Array weather is not taken: `runbioclima` keeps its reqhgt < 0 refusal, because that route needs the per-cell point-model
+    series this mirror does not carry."""
+    d = np.atleast_1d(np.asarray(depths, dtype=np.float64)).ravel()
+    if d.size < 1 or not np.all(d < 0):
+        raise ValueError("runbioclim_depths: depths is a non-empty list of heights below ground (each < 0)")
+    got = {}
+
+    def capture(layered, args, kw):
+        got.update(layered=layered, args=args, kw=kw)
+        return {}
+
+    runbioclim(climdata, float(d[0]), vegp, soilc, dtm, temp="air", zref=zref, windhgt=windhgt, soilm=soilm, pai_a=pai_a,
+               tfact=tfact, out=out, vegpisannual=vegpisannual, device=device, _bioclim=capture, _terrain=_terrain)
+    layered, args, kw = got["layered"], dict(got["args"]), got["kw"]
+    args.pop("reqhgt")
+    args["depths"] = d
+    if _bioclim is not None:
+        return _bioclim(layered, args, kw)
+    res = api.runbioclim_depths(**args, **kw, layered=layered, device=device, chunk_days=chunk_days)
+    na = np.isnan(cleanvars(vegp, soilc, dtm["z"])[2])
+    for k, v in res.items():
+        if k != "depths":
+            v[..., na] = np.nan                                                 # mask(bior, dtm)
+    return res
+
+
 def bioclima_selection(climarray: Mapping, obstime: Mapping) -> dict:
     """What `.runbioclim2` / `.runbioclim4` decide from the weather alone (R/internal.R:1909-1916, 1749-1755): the four
     quarters from the spatial means of precipitation and temperature per step (`apply(..., 3, mean, na.rm = TRUE)`), and
