@@ -1576,6 +1576,25 @@ int mcf_runmicro_heights(const mcf_grid_inputs *in, const mcf_options *opt, cons
 int mcf_selftest_math(int32_t kind, const double *x, const double *y, double *out, int64_t n,
                       int32_t device);
 
+/* Diagnostics: the per-cell-step sun position and humidity helpers of array forcing, elementwise, one lane per element.
+ * `in` holds nin planes of n doubles, `out` nout planes of n doubles (plane f of element i at [f * n + i]); used by tests to
+ * hold each field against a high-precision evaluation of the reference's formulas.
+ *   kind 0, 1, 2: nin = 11: year, month, day, hour, winddir, lat, lon, tc, pk, rsw, rdif.
+ *   kind 0 (nout = 29): the solver's array-forcing step — the date row as the date set-up makes it, the cell constants
+ *     (sin / cos of the latitude and of B = 0.261799 * 4 lon / 60) as the cell set-up makes them, then derive_time_af and
+ *     derive_time_af_pass2.  Planes: 0 CZ, 1 SZ, 2 TANSA, 3 ZEND, 4 COSC, 5 TANC, 6 TAN2C, 7 INV2COSC, 8 SAZ, 9 CAZ, 10 sindex,
+ *     11 windex, 12 ksat, 13 DE, 14 GHRRAD, 15 REM, 16 LAPK, 17 WFAC, 18 RBEAM, 19 RB; after pass 2: 20 GHRRAD, 21 REM, 22 MUPM,
+ *     23 INVMUPM; the date row: 24 sin dec, 25 cos dec, 26 cos A, 27 sin A (A = 0.261799 * (hour + eot / 60 - 12)); 28 julday.
+ *   kind 1 (nout = 29): the literal device route of vector forcing (sol_date, sol_site, derive_time) on the same inputs, the
+ *     same planes; 26 holds the equation of time (minutes), 27 NaN.  Fields the route reads and this entry does not supply
+ *     (Gp, muGp, ...) are 1.
+ *   kind 2 (nout = 21): the snow kernels' sun (sun_cell + sun_at_cell) from the same date row: 0 zend, 1 cosz, 2 cz, 3 sz,
+ *     4 tansa, 5 kx, 6 kcos, 7 sa, 8 ca, 9 sindex; beside it the literal sol_site + sun_derive(degrees = 0): 10 .. 18 in the same
+ *     order, 19 tansa of sun_derive(degrees = 1), 20 the literal horizon sector.
+ *   kind 3 (nin = 3: tc, rh, pk; nout = 4): the R-side humidity helpers: 0 es = satvap_r(tc), 1 ea = es rh / 100,
+ *     2 dewpoint_r(ea, tc), 3 lapserate_r(tc, ea, pk), exp and log through the tables in LDS. */
+int mcf_selftest_step(int32_t kind, const double *in, int32_t nin, double *out, int32_t nout, int64_t n, int32_t device);
+
 /* Information. */
 int64_t mcf_plan_valid_cells(const mcf_plan *plan); /* cells with non-NA hgt */
 int64_t mcf_plan_bytes(const mcf_plan *plan);       /* device bytes held      */

@@ -835,7 +835,9 @@ __device__ __forceinline__ void derive_time_af(TimeVals& t, const DateRow& dr, d
     t.v[TF_TANSA] = fdiv(coh, sz);
     // zenith in degrees is only compared with 90 (cpp:88) and with pi/2 (the degrees call, cpp:1425)
     const bool up = coh >= 0.0;                    // zenith <= 90 degrees
-    const bool nearzen = coh > 0.99962422;         // zenith (deg) may be below pi/2 = 1.5708
+    // zenith (deg) may be below pi/2 = 1.5708.  The bit flips at coh = cos(pi/2 pi/180) = 0.999624216859...: the constant stays BELOW
+    // that (0.99962422 left a band 3.1e-9 wide in which ksat was set against the literal route; tests/test_step_gpu.py)
+    const bool nearzen = coh > 0.99962421;
     double zend = up ? 45.0 : 135.0;
     if (nearzen) zend = acos(coh) * (180 / kPi);
     t.v[TF_ZEND] = zend;
