@@ -1595,6 +1595,28 @@ int mcf_selftest_math(int32_t kind, const double *x, const double *y, double *ou
  *     2 dewpoint_r(ea, tc), 3 lapserate_r(tc, ea, pk), exp and log through the tables in LDS. */
 int mcf_selftest_step(int32_t kind, const double *in, int32_t nin, double *out, int32_t nout, int64_t n, int32_t device);
 
+/* Diagnostics: the device physics of the snow kernels (mcf_snow_device.hpp), elementwise, one lane per element; planes as in
+ * mcf_selftest_step.  Used by tests to hold each field against a high-precision evaluation of the reference's formulas.
+ *   kind 0 (nin = 2: x, y; nout = 12), guards and scalars: 0 gexp(x), 1 glog(x), 2 gsqrt(x), 3 gpow0(x, y), 4 svp(x),
+ *     5 dewpoint(x), 6 rad4(x), 7 latent_lt0(x), 8 clamp01(x), 9 snow_albedo((int)x) (0 <= x < 2^31, else of 0),
+ *     10 snow_satvap_r(x), 11 snow_lapserate_r(x, ea, y) with ea = snow_satvap_r(x) * 80 / 100 as the coarse expansion forms it.
+ *   kind 1 (nin = 8: pait, lref, ltra, gref, kd, kx, kcos, si; nout = 29), radiation: ts_dif(pait, lref, ltra, gref, 1 / gref):
+ *     0 om, 1 a, 2 gma, 3 del, 4 h, 5 S1, 6 iS1, 7 iD1, 8 iD2, 9 u1, 10 u2, 11 D1, 12 D2, 13 p1, 14 p2, 15 p3, 16 p4;
+ *     ts_dir(pait, that, gref, kd): 17 sig, 18 isig (both of the NEGATED determinant), 19 S2, 20 p5, 21 p6, 22 p7, 23 p8, 24 p9,
+ *     25 p10; cank1(kx, kcos, si): 26 k, 27 kd, 28 Kc.
+ *   kind 2 (nin = 32; nout = 23), canopy and profile.  In: 0 h, 1 pai, 2 d, 3 uf, 4 prec, 5 sint, 6 Li, 7 .. 10 sdp[0 .. 3],
+ *     11 depth, 12 age (hours), 13 x, 14 z, 15 leafden, 16 Flux, 17 Fluxz, 18 SH, 19 SG, 20 mxnear, 21 zm, 22 zref, 23 za, 24 T0,
+ *     25 tc, 26 ea, 27 slope, 28 aspect, 29 zend, 30 azid, 31 hc.  Out: 0 zeroplane(h, pai), 1 roughlen0(h, pai, d),
+ *     2 canopy_snow_interception(hc, pai, uf, prec, sint, Li), 3 snow_density(sdp, depth, age), 4 / 5 sin / cos of
+ *     sincos_0pi(x), 6 rh_canopy(uf, h, 1 / h, d, z), 7 rh_canopy(.., h), below_k(z, d, h, uf): 8 Kg, 9 Kh, 10 Kc, 11 iKc, 12 iKs,
+ *     13 tv_below(that, glog(pai), leafden, Flux, Fluxz, SH, SG, mxnear), tv_above_l(za, d, zm, log((za - d) / zm) + log 5,
+ *     log((zref - d) / zm) + log 5, T0, tc, ea): 14 Tz, 15 ez; site_derive(slope, aspect): 16 cS, 17 sS, 18 cA, 19 sA, 20 flat;
+ *     solar_index of sun_derive(zend, zend torad, azid) at that site: 21 shadowmask = 0, 22 shadowmask = 1.
+ *   kind 3 (nin = 5: tc, rh, pk, tci, mxtc; nout = 22), step weather.  met_derive(tc, rh, pk, tci): 0 ea, 1 te, 2 rem, 3 rcan,
+ *     4 la, 5 cp, 6 Da, 7 gR, 8 De, 9 tdew, 10 ph, 11 sint; micro_met(tc, rh, pk, mxtc): 12 es, 13 ea, 14 tdew, 15 De, 16 gHrad,
+ *     17 Rem, 18 la_pm, 19 lat0, 20 dTmx, 21 ipk. */
+int mcf_selftest_snow(int32_t kind, const double *in, int32_t nin, double *out, int32_t nout, int64_t n, int32_t device);
+
 /* Information. */
 int64_t mcf_plan_valid_cells(const mcf_plan *plan); /* cells with non-NA hgt */
 int64_t mcf_plan_bytes(const mcf_plan *plan);       /* device bytes held      */

@@ -370,7 +370,7 @@ EXPORTS = (
     "mcf_microsnow_expand_coarse_device", "mcf_runmicrosnow2_coarse", "mcf_snowrun_create_coarse",
     "mcf_plan_set_day_layers", "mcf_snowrun_set_day_layers", "mcf_plan_fetch_mxtc",
     "mcf_foliageden", "mcf_foliageden_device", "mcf_plan_set_height", "mcf_plan_fetch_foliage", "mcf_runmicro_heights",
-    "mcf_selftest_step",
+    "mcf_selftest_step", "mcf_selftest_snow",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -614,6 +614,9 @@ def load() -> C.CDLL:
     if hasattr(lib, "mcf_selftest_step"):     # (absent from an older library named by MCF_LIB for an A/B run)
         lib.mcf_selftest_step.restype = C.c_int
         lib.mcf_selftest_step.argtypes = [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_int64, C.c_int32]
+    if hasattr(lib, "mcf_selftest_snow"):
+        lib.mcf_selftest_snow.restype = C.c_int
+        lib.mcf_selftest_snow.argtypes = [C.c_int32, c_double_p, C.c_int32, c_double_p, C.c_int32, C.c_int64, C.c_int32]
     for fn in (lib.mcf_runbioclim1, lib.mcf_runbioclim2, lib.mcf_runbioclim3, lib.mcf_runbioclim4):
         fn.restype = C.c_int
         fn.argtypes = [GI, OP, C.POINTER(BioclimSel), C.POINTER(BioclimOut)]

@@ -1521,16 +1521,7 @@ struct CoarseGeo {
     }
 };
 
-// `.satvap` and `.lapserate` (int:501-511, 545-550) in the operand order of rformulas.satvap_R / lapserate_R
-__device__ __forceinline__ double snow_satvap_r(double tc) {
-#pragma clang fp contract(off)
-    return tc < 0.0 ? 0.61078 * exp(21.875 * tc / (tc + 265.5)) : 0.61078 * exp(17.27 * tc / (tc + 237.3));
-}
-__device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double pk) {
-#pragma clang fp contract(off)
-    const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
-    return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
-}
+// (`.satvap` and `.lapserate`, snow_satvap_r / snow_lapserate_r: mcf_snow_device.hpp, where mcf_selftest_snow.hip reaches them)
 // A selected day's (or a chunk's) thirteen series on the raster from the coarse arrays (int:3112-3164; snow.py
 // _fine_snow_inputs), [hours][N] as k_snowmodel<true> reads them.  `.cca`: bilinear, NA on the dtm's holes; pressure and the wind components
 // are not masked.  altcorrect > 0: `pres` holds the coarse pressure already taken to sea level (the host divides by the

@@ -64,11 +64,54 @@ __device__ __forceinline__ double gsqrt(double x) {     // sqrt(x) for ANY opera
     return ::sqrt(x);
 }
 __device__ __forceinline__ double gdiv(double a, double b) { return fdiv(a, b); }   // b finite, non-zero by construction (or NaN)
-// pow(b, e) for b >= 0 and e > 0 (clump^Kc): pow(0, e) = 0
+// pow(b, e) for b > 0.  exp(e log b) on the lean routines carries the rounding of e log b into the result |e ln b| times (1.1e-13
+// relative for clump^Kc at |e ln b| = 700, where the reference's pow has half an ulp: tests/test_snow_unit_gpu.py); here the
+// logarithm is made as a pair hi + lo good to about 2^-62: b = m 2^k with m in [sqrt(1/2), sqrt(2)), s = (m - 1) / (m + 1) as a pair,
+// log m = 2 s + 2 s^3 / 3 (as a pair) + 2 s^5 / 5 + ... (to s^25: |s| <= 0.172), k ln 2 from a two-part ln 2; then
+// e (hi + lo) = th + tl with the product's own rounding kept, and exp(th) (1 + tl).  No table, no libm call.
+__device__ __forceinline__ double gpow_pos(double b, double e) {
+#pragma clang fp contract(off)
+    int ki;
+    double m = __builtin_frexp(b, &ki);                        // [0.5, 1), denormals included
+    const bool low = m < 0.70710678118654752;
+    m = low ? 2.0 * m : m;
+    const double k = (double)(low ? ki - 1 : ki);
+    const double num = m - 1.0;                                 // exact
+    const double den = m + 1.0;
+    const double dv = den - m, dl = (m - (den - dv)) + (1.0 - dv);      // den + dl = m + 1 exactly
+    const double rc = frcp(den);
+    const double s = num * rc;
+    const double sl = (fma(-s, den, num) - s * dl) * rc;        // s + sl = num / (den + dl)
+    const double s2 = s * s, s2l = fma(s, s, -s2) + 2.0 * s * sl;
+    constexpr double kThirdHi = 1.0 / 3.0, kThirdLo = 1.850371707708594e-17;
+    const double c = s2 * kThirdHi, cl = fma(s2, kThirdHi, -c) + (s2 * kThirdLo + s2l * kThirdHi);
+    double R = 1.0 / 25.0;
+    R = fma(s2, R, 1.0 / 23.0); R = fma(s2, R, 1.0 / 21.0); R = fma(s2, R, 1.0 / 19.0); R = fma(s2, R, 1.0 / 17.0);
+    R = fma(s2, R, 1.0 / 15.0); R = fma(s2, R, 1.0 / 13.0); R = fma(s2, R, 1.0 / 11.0); R = fma(s2, R, 1.0 / 9.0);
+    R = fma(s2, R, 1.0 / 7.0); R = fma(s2, R, 1.0 / 5.0);
+    R = (s2 * s2) * R;                                          // s^4 / 5 + s^6 / 7 + ...
+    const double A = k * 6.93147180369123816490e-01;            // exact: ln2_hi carries 32 bits
+    const double B = 2.0 * s;
+    const double q = B * c;
+    const double small = fma(B, c, -q) + B * (cl + R);
+    double hi = A + B, v = hi - A;
+    const double e1 = (A - (hi - v)) + (B - v);
+    const double h1 = hi;
+    hi = h1 + q; v = hi - h1;
+    const double e2 = (h1 - (hi - v)) + (q - v);
+    const double lo = (e1 + e2) + (k * 1.90821492927058770002e-10 + (2.0 * sl + small));
+    const double h2 = hi + lo, l2 = lo - (h2 - hi);
+    const double th = e * h2, tl = fma(e, h2, -th) + e * l2;
+    const double r = gexp(th);
+    return r < 0x1.fffffffffffffp+1023 ? fma(r, tl, r) : r;       // (an overflowed exp stays +inf: inf * tl + inf is a NaN for tl <= 0; NaN stays NaN)
+}
+// pow(b, e) for b >= 0 and e > 0 (clump^Kc): pow(0, e) = 0.  kPrecise = false: the b > 0 route is exp(e log b) on the lean routines, whose
+// error is |e ln b| roundings — for a small fixed exponent only (the 0.2 of mincondCpp: |e ln b| < 3)
+template <bool kPrecise = true>
 __device__ __forceinline__ double gpow0(double b, double e) {
     // b = 0 is the common special case (clump = 0: every bare cell, and a wave that holds one ran the device's 220-instruction
     // pow for all its lanes): pow(0, e > 0) = 0.  Anything else outside b > 0 (NaNs, e <= 0) still goes to libm.
-    if (b > 0.0) return gexp(e * glog(b));
+    if (b > 0.0) return kPrecise ? gpow_pos(b, e) : gexp(e * glog(b));
     if (b == 0.0 && e > 0.0) return 0.0;
     // What is left is outside the model's domain (a negative or NaN clumping factor, a non-positive exponent).  Round 5: C's pow
     // semantics written out with the lean routines instead of the device libm's pow — 220 instructions and the registers of a
@@ -876,7 +919,7 @@ __device__ __forceinline__ MicroOut micro_above(const MicroIn& q, const MicroMet
             const double Rnet = leafabs - lwcan;
             // Hf = -1 / (1 + exp(2 - 1.09767 * rs^0.2672778)) with rs = 1 / 999.99: a constant of the model
             const double Hf = -0x1.1be70d7011323p-3;
-            double gmin = 0.0463 * gpow0(fabs(Hf * Rnet) * ileafd, 0.2);
+            double gmin = 0.0463 * gpow0<false>(fabs(Hf * Rnet) * ileafd, 0.2);
             if (gmin < 0.05) gmin = 0.05;
             if (gh < gmin) gh = gmin;
         }
@@ -934,6 +977,18 @@ __device__ __forceinline__ double micro_below(double reqhgt, double meanD, doubl
         }
     }
     return Tz;
+}
+
+// `.satvap` and `.lapserate` (int:501-511, 545-550) in the operand order of rformulas.satvap_R / lapserate_R: the altitude
+// correction of the coarse-array expansion (mcf_snow.hip k_fine_*)
+__device__ __forceinline__ double snow_satvap_r(double tc) {
+#pragma clang fp contract(off)
+    return tc < 0.0 ? 0.61078 * exp(21.875 * tc / (tc + 265.5)) : 0.61078 * exp(17.27 * tc / (tc + 237.3));
+}
+__device__ __forceinline__ double snow_lapserate_r(double tc, double ea, double pk) {
+#pragma clang fp contract(off)
+    const double rv = 0.622 * ea / (pk - ea), tk = tc + 273.15;
+    return 9.8076 * (1 + (2501000 * rv) / (287 * tk)) / (1003.5 + (0.622 * 6255001000000.0 * rv) / (287 * (tk * tk)));
 }
 
 }  // namespace snow

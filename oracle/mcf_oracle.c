@@ -199,6 +199,20 @@ static tsdir_t twostreamdir_params(double pait, double om, double a, double gma,
     return p;
 }
 
+/* the two above for tests/test_snow_unit_ref_cpu.py: out[14] = p1 .. p4, om, a, gma, J, del, h, u1, S1, D1, D2; out[7] = sig,
+ * p5 .. p10 */
+void orc_twostreamdif_params(double pait, double x, double lref, double ltra, double gref, double *out) {
+    const tsdif_t p = twostreamdif_params(pait, x, lref, ltra, gref);
+    const double v[14] = {p.p1, p.p2, p.p3, p.p4, p.om, p.a, p.gma, p.J, p.del, p.h, p.u1, p.S1, p.D1, p.D2};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+}
+void orc_twostreamdir_params(double pait, double om, double a, double gma, double J, double del, double h, double gref,
+                             double kd, double u1, double S1, double D1, double D2, double *out) {
+    const tsdir_t p = twostreamdir_params(pait, om, a, gma, J, del, h, gref, kd, u1, S1, D1, D2);
+    const double v[7] = {p.sig, p.p5, p.p6, p.p7, p.p8, p.p9, p.p10};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+}
+
 /* cpp:294-299 zeroplanedisCpp */
 double orc_zeroplanedis(double h, double pai) {
     if (pai < 0.001) pai = 0.001;
@@ -734,6 +748,19 @@ static double TVbelow(double zref, double z, double d, double h, double pai, dou
     }
     if (isnan(near)) near = 0;
     return near + farg;
+}
+
+/* TVabove, rhcanopy and TVbelow for tests/test_snow_unit_ref_cpu.py */
+void orc_tvabove(double reqhgt, double zref, double h, double d, double zm, double T0, double tc, double ea, double surfwet,
+                 double *out) {
+    const abovecan_t o = TVabove(reqhgt, zref, h, d, zm, T0, tc, ea, surfwet);
+    out[0] = o.Tz;
+    out[1] = o.ez;
+}
+double orc_rhcanopy(double uf, double h, double d, double z) { return rhcanopy(uf, h, d, z); }
+double orc_tvbelow(double zref, double z, double d, double h, double pai, double uf, double leafden, double Flux,
+                   double Fluxz, double SH, double SG, double mxnear) {
+    return TVbelow(zref, z, d, h, pai, uf, leafden, Flux, Fluxz, SH, SG, mxnear);
 }
 
 static double max4(double a, double b, double c, double d) {

@@ -20,6 +20,14 @@ orc_kstruct orc_cank(double zenr, double x, double si);
 double orc_zeroplanedis(double h, double pai);
 double orc_roughlength(double h, double pai, double d, double psi_h);
 double orc_satvap(double tc);
+void orc_twostreamdif_params(double pait, double x, double lref, double ltra, double gref, double *out);
+void orc_twostreamdir_params(double pait, double om, double a, double gma, double J, double del, double h, double gref,
+                             double kd, double u1, double S1, double D1, double D2, double *out);
+void orc_tvabove(double reqhgt, double zref, double h, double d, double zm, double T0, double tc, double ea, double surfwet,
+                 double *out);
+double orc_rhcanopy(double uf, double h, double d, double z);
+double orc_tvbelow(double zref, double z, double d, double h, double pai, double uf, double leafden, double Flux,
+                   double Fluxz, double SH, double SG, double mxnear);
 double orc_soild(double soilm, double Smin, double Smax, double tadd);
 void orc_soild_tadd(const double *twi, int64_t n_cells, int64_t rows, int64_t cols, double tfact,
                     double *tadd);

@@ -40,6 +40,9 @@ static double canopysnowint(double hgt, double pai, double uf, double prec, doub
     if (cis > prec) cis = prec;
     return cis;
 }
+double orc_canopysnowint(double hgt, double pai, double uf, double prec, double tc, double Li) {
+    return canopysnowint(hgt, pai, uf, prec, tc, Li);
+}
 
 /* cpp:3741-3749 snowdenp; the enum is include/mcf.h's MCF_SNOWENV_* */
 static void snowdenp(int snowenv, double sdp[4]) {

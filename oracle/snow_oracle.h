@@ -20,6 +20,7 @@ int orc_pointmodelsnow(int tsteps, const int *year, const int *month, const int 
                        const double *vegp, const double *other, int snowenv, double tol, double maxiter,
                        orc_pointsnow_out *o);
 void orc_snowalb(const double *prec, int tsteps, double *alb); /* snowalbCpp cpp:3752-3771 */
+double orc_canopysnowint(double hgt, double pai, double uf, double prec, double tc, double Li); /* cpp:3713-3739 */
 int orc_gridmodelsnow(const mcf_snow_inputs *in, mcf_snowmodel_out *out);
 int orc_gridmicrosnow(const mcf_snow_inputs *in, const mcf_snowm *sm, double reqhgt, double mat,
                       const int32_t *outsel, mcf_outputs *micro);
