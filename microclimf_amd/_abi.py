@@ -67,12 +67,13 @@ class Multi(C.Structure):
 
 
 def multi(devices, n_blocks):
-    """-> (mcf_multi, the int32 array its `devices` points into: keep it for as long as the struct is used) for `devices` (a list
-    of HIP ordinals, [] = all visible) / `n_blocks` row blocks, or None when neither is given: the single-device entry."""
+    """-> mcf_multi[1] (pass `C.byref(mu[0])`) for `devices` (a list of HIP ordinals, [] = all visible) / `n_blocks` row blocks,
+    or None when neither is given: the single-device entry.  The returned object holds the int32 list its `devices` points into
+    (ctypes keeps what a cast pointer was made from with the struct it is stored in)."""
     if devices is None and not n_blocks:
         return None
     devs = (C.c_int32 * (0 if devices is None else len(devices)))(*(() if devices is None else devices))
-    return Multi(len(devs), C.cast(devs, c_int32_p), int(n_blocks)), devs
+    return (Multi * 1)(Multi(len(devs), C.cast(devs, c_int32_p), int(n_blocks)))
 
 
 class Options(C.Structure):

@@ -20,7 +20,7 @@ from typing import Mapping, Sequence
 import numpy as np
 
 from . import _abi
-from .marshal import Marshalled, alloc_outputs, marshal
+from .marshal import Buffers, Marshalled, alloc_outputs, build_summary_spec, marshal, summary_sink
 
 
 DTM_DERIVED = ("slope", "aspect", "hor", "svfa", "wsa", "twi")      # soilc entries a plan can derive from the dtm
@@ -28,8 +28,8 @@ DTM_DERIVED = ("slope", "aspect", "hor", "svfa", "wsa", "twi")      # soilc entr
 
 def dtm_spec(dtm: Mapping, rows: int, cols: int):
     """include/mcf.h mcf_dtm_spec from `dtm` = {z, res[, halo_north, halo_south, row0, rows_total, agg]}: `z` is the block's
-    elevations [(halo_north + rows + halo_south), cols] (NaN = NA), `res` one number or (xres, yres).  -> (spec, the array
-    that backs its pointer)"""
+    elevations [(halo_north + rows + halo_south), cols] (NaN = NA), `res` one number or (xres, yres).  -> the spec (it holds
+    the array behind its pointer)"""
     z = np.asfortranarray(np.asarray(dtm["z"], dtype=np.float64))
     hn, hs = int(dtm.get("halo_north", 0)), int(dtm.get("halo_south", 0))
     if z.shape != (hn + rows + hs, cols):
@@ -37,11 +37,12 @@ def dtm_spec(dtm: Mapping, rows: int, cols: int):
     res = dtm["res"]
     xres, yres = (res, res) if np.isscalar(res) else res
     sp = _abi.DtmSpec()
-    sp.dtm = z.ctypes.data_as(_abi.c_double_p)
+    sp._owner = Buffers()
+    sp.dtm = sp._owner.ptr(z)
     sp.halo_north, sp.halo_south = hn, hs
     sp.row0, sp.rows_total = int(dtm.get("row0", 0)), int(dtm.get("rows_total", 0))
     sp.xres, sp.yres, sp.agg = float(xres), float(yres), int(dtm.get("agg", 0))
-    return sp, z
+    return sp
 
 
 def diag_selection(names):
@@ -59,31 +60,8 @@ def diag_selection(names):
 def summary_spec(periods, vars, stats, thresholds=None):
     """include/mcf.h mcf_summary_spec from `periods` (one integer per day, -1 = not counted), output names or indices, names
     of _abi.STAT_NAMES or indices, and `thresholds` for hours_above: one number for every selected variable or {variable:
-    number}.  -> (spec, the selected variables' indices, the selected statistics' indices, the array its table points into)"""
-    pod = np.ascontiguousarray(np.asarray(periods).astype(np.int32)).ravel()
-    vi = sorted({_abi.OUT_NAMES.index(v) if isinstance(v, str) else int(v) for v in ((vars,) if isinstance(vars, str) else vars)})
-    si = sorted({_abi.STAT_NAMES.index(s) if isinstance(s, str) else int(s) for s in ((stats,) if isinstance(stats, str) else stats)})
-    if any(v < 0 or v >= _abi.NOUT for v in vi) or any(s < 0 or s >= _abi.NSTAT for s in si):
-        raise ValueError(f"summary: variables of {_abi.OUT_NAMES}, statistics of {_abi.STAT_NAMES}")
-    sp = _abi.SummarySpec()
-    sp.nperiods = int(pod.max()) + 1 if pod.size and pod.max() >= 0 else 1
-    sp.period_of_day = pod.ctypes.data_as(_abi.c_int32_p)
-    for v in vi:
-        sp.var[v] = 1
-        if isinstance(thresholds, Mapping):
-            t = thresholds.get(_abi.OUT_NAMES[v], thresholds.get(v, float("nan")))
-        else:
-            t = float("nan") if thresholds is None else thresholds
-        sp.threshold[v] = float(t)
-    for s in si:
-        sp.stat[s] = 1
-    return sp, vi, si, pod
-
-
-def _summary_result(vi, si, arrays, days):
-    res = {_abi.OUT_NAMES[v]: {_abi.STAT_NAMES[s]: arrays[v, s] for s in si} for v in vi}
-    res["days"] = days
-    return res
+    number}.  -> (spec, the selected variables' indices, the selected statistics' indices, the period table the spec holds)"""
+    return build_summary_spec(_abi.SummarySpec, _abi.OUT_NAMES, "var", "summary: variables", periods, vars, stats, thresholds)
 
 
 def runmicro_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, reqhgt: float,
@@ -106,39 +84,28 @@ def runmicro_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp:
     if dtm is not None:
         if devices is not None or n_blocks:
             raise ValueError("dtm= is not available with devices= / n_blocks=")
-        T = len(np.asarray(obstime["year"]))
-        nd = T // 24
+        nd = len(np.asarray(obstime["year"])) // 24
         ring = max(1, min(nd, int(chunk_days) if chunk_days else 8))
         with Plan(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out,
                   array_forcing=af, ring_days=ring, device=device, cells_per_block=cells_per_block, dfsel=dfsel, coarse=coarse,
                   dtm=dtm) as p:
             p.summary_enable(_pod, vi, si, thresholds, nperiods=sp.nperiods)
-            for d0 in range(0, nd, ring):
-                n = min(ring, nd - d0)
-                if af:
-                    p.upload_forcing_days(d0, n, 0)
-                p.run_days(d0, n, 0)
-                p.summary_accumulate(0, 0, d0, n)
-            arrays = {(v, s): p.fetch_summary(v, s) for v in vi for s in si}
-            return _summary_result(vi, si, arrays, p.summary_days())
+            p.summarise_days(ring)
+            return summary_sink(Buffers(), p.rows, p.cols, (sp, vi, si, _pod), _abi.OUT_NAMES,
+                                plane=lambda v, s, ptr: _abi.check(p._lib.mcf_plan_summary_fetch(p._p, v, s, ptr)),
+                                days=lambda ptr: _abi.check(p._lib.mcf_plan_summary_days(p._p, ptr)))
     lib = _abi.load()
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out, af,
                 device, 0, cells_per_block, dfsel, coarse)
     so = _abi.SummaryOut()
-    arrays = {}
-    for v in vi:
-        for s in si:
-            arrays[v, s] = np.empty((m.rows, m.cols, max(int(sp.nperiods), 0)), dtype=np.float64, order="F")
-            so.val[v][s] = arrays[v, s].ctypes.data_as(_abi.c_double_p)
-    days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
-    so.days = days.ctypes.data_as(_abi.c_int32_p)
+    res = summary_sink(m, m.rows, m.cols, (sp, vi, si, _pod), _abi.OUT_NAMES, so)
     mu = _abi.multi(devices, n_blocks)
     if mu:
         _abi.check(lib.mcf_runmicro_summary_multi(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(mu[0]),
                                                   C.byref(so)))
     else:
         _abi.check(lib.mcf_runmicro_summary(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(so)))
-    return _summary_result(vi, si, arrays, days[:max(int(sp.nperiods), 0)])
+    return res
 
 
 def _depth_list(depths, tbp, tsteps):
@@ -150,10 +117,6 @@ def _depth_list(depths, tbp, tsteps):
         if t.shape != (d.size, tsteps):
             raise ValueError(f"tbp: expected shape {(d.size, tsteps)} (one row of the point model's soil temperature per depth), got {t.shape}")
     return d, t
-
-
-def _ptr(a):
-    return None if a is None else a.ctypes.data_as(_abi.c_double_p)
 
 
 def runmicro_depths(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths, zref: float,
@@ -174,14 +137,13 @@ def runmicro_depths(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: 
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
                 [1, 0, 0, 1 if soilm else 0, 0, 0, 0, 0, 0, 0], af, device, days_per_chunk, cells_per_block, dfsel, coarse)
     do = _abi.DepthOutputs()
-    tz = [np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F") for _ in range(min(d.size, _abi.MAX_DEPTHS))]
-    for i, a in enumerate(tz):
-        do.tz[i] = _ptr(a)
-    res = {"Tz": tz, "depths": d.copy()}
+    res = {"Tz": [], "depths": d.copy()}
+    for i in range(min(d.size, _abi.MAX_DEPTHS)):
+        a, do.tz[i] = m.out((m.rows, m.cols, m.tsteps))
+        res["Tz"].append(a)
     if soilm:
-        res["soilm"] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-        do.soilm = _ptr(res["soilm"])
-    _abi.check(lib.mcf_runmicro_depths(C.byref(m.inputs), C.byref(m.options), _ptr(d), int(d.size), _ptr(t), C.byref(do)))
+        res["soilm"], do.soilm = m.out((m.rows, m.cols, m.tsteps))
+    _abi.check(lib.mcf_runmicro_depths(C.byref(m.inputs), C.byref(m.options), m.ptr(d), int(d.size), m.ptr(t), C.byref(do)))
     return res
 
 
@@ -206,25 +168,19 @@ def runmicro_depths_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
                 [1, 0, 0, 1, 0, 0, 0, 0, 0, 0], af, device, 0, cells_per_block, dfsel, coarse)
     so = _abi.DepthSummaryOut()
-    npd = max(int(sp.nperiods), 0)
-    plane = lambda: np.empty((m.rows, m.cols, npd), dtype=np.float64, order="F")
     res = {"depths": d.copy()}
-    TZ, SM = _abi.OUT_NAMES.index("Tz"), _abi.OUT_NAMES.index("soilm")
-    if TZ in vi:
-        res["Tz"] = []
-        for i in range(min(d.size, _abi.MAX_DEPTHS)):
-            res["Tz"].append({_abi.STAT_NAMES[k]: plane() for k in si})
-            for k in si:
-                so.tz[i][k] = _ptr(res["Tz"][i][_abi.STAT_NAMES[k]])
-    if SM in vi:
-        res["soilm"] = {_abi.STAT_NAMES[k]: plane() for k in si}
-        for k in si:
-            so.soilm[k] = _ptr(res["soilm"][_abi.STAT_NAMES[k]])
-    days = np.zeros(max(npd, 1), dtype=np.int32)
-    so.days = days.ctypes.data_as(_abi.c_int32_p)
-    _abi.check(lib.mcf_runmicro_depths_summary(C.byref(m.inputs), C.byref(m.options), _ptr(d), int(d.size), _ptr(t), C.byref(sp),
+
+    def sink(name, row, **kw):
+        """the planes of one variable into one row [statistic] of the out struct"""
+        one = (sp, [_abi.OUT_NAMES.index(name)] if name else [], si, _pod)
+        return summary_sink(m, m.rows, m.cols, one, _abi.OUT_NAMES, plane=lambda v, k, ptr: row.__setitem__(k, ptr), **kw)
+    if _abi.OUT_NAMES.index("Tz") in vi:
+        res["Tz"] = [sink("Tz", so.tz[i])["Tz"] for i in range(min(d.size, _abi.MAX_DEPTHS))]
+    if _abi.OUT_NAMES.index("soilm") in vi:
+        res["soilm"] = sink("soilm", so.soilm)["soilm"]
+    res["days"] = sink(None, None, days=lambda ptr: setattr(so, "days", ptr))["days"]
+    _abi.check(lib.mcf_runmicro_depths_summary(C.byref(m.inputs), C.byref(m.options), m.ptr(d), int(d.size), m.ptr(t), C.byref(sp),
                                                int(chunk_days), C.byref(so)))
-    res["days"] = days[:npd]
     return res
 
 
@@ -237,11 +193,12 @@ def foliageden(hgt, pai, z: float, device: int | None = None):
     p = np.asfortranarray(np.asarray(pai, dtype=np.float64))
     if h.shape != p.shape:
         raise ValueError(f"foliageden: hgt {h.shape} and pai {p.shape} differ in shape")
-    ld, pa = np.empty(h.shape, dtype=np.float64, order="F"), np.empty(h.shape, dtype=np.float64, order="F")
+    b = Buffers()
+    (ld, ldp), (pa, pap) = b.out(h.shape), b.out(h.shape)
     if device is None:
-        _abi.check(lib.mcf_foliageden(int(h.size), _ptr(h), _ptr(p), float(z), _ptr(ld), _ptr(pa)))
+        _abi.check(lib.mcf_foliageden(int(h.size), b.ptr(h), b.ptr(p), float(z), ldp, pap))
     else:
-        _abi.check(lib.mcf_foliageden_device(int(h.size), _ptr(h), _ptr(p), float(z), _ptr(ld), _ptr(pa), int(device)))
+        _abi.check(lib.mcf_foliageden_device(int(h.size), b.ptr(h), b.ptr(p), float(z), ldp, pap, int(device)))
     return ld, pa
 
 
@@ -267,7 +224,7 @@ def runmicro_heights(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp:
         outs[h] = _o
         for k, a in arrays.items():
             res.setdefault(k, []).append(a)
-    pp, keep = None, []
+    pp = None
     if pai_a is not None:
         if len(pai_a) != hs.size:
             raise ValueError(f"pai_a: one entry per height ({hs.size}), each None or an array")
@@ -280,9 +237,8 @@ def runmicro_heights(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp:
                 a = a[:, :, :L]                  # as marshal() reads layered vegetation: the first L layers, no copy
             if a.size != m.rows * m.cols * L:
                 raise ValueError(f"pai_a[{h}]: expected {m.rows} x {m.cols} x {L} values, got shape {a.shape}")
-            keep.append(a)
-            pp[h] = _ptr(a)
-    _abi.check(lib.mcf_runmicro_heights(C.byref(m.inputs), C.byref(m.options), _ptr(hs) if hs.size else None, int(hs.size), pp, outs))
+            pp[h] = m.ptr(a)
+    _abi.check(lib.mcf_runmicro_heights(C.byref(m.inputs), C.byref(m.options), m.ptr(hs) if hs.size else None, int(hs.size), pp, outs))
     return res
 
 
@@ -303,8 +259,7 @@ def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt,
         dout = _abi.DiagOutputs()
         darr = {}
         for n in names:
-            darr[n] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            dout.var[_abi.DIAG_NAMES.index(n)] = darr[n].ctypes.data_as(_abi.c_double_p)
+            darr[n], dout.var[_abi.DIAG_NAMES.index(n)] = m.out((m.rows, m.cols, m.tsteps))
         _abi.check(getattr(lib, fn_name + "_diag")(C.byref(m.inputs), C.byref(m.options), C.byref(sel), C.byref(outs),
                                                    C.byref(dout)))
         arrays["diag"] = darr
@@ -312,7 +267,7 @@ def _run(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt,
     if dtm is not None:
         # missing terrain planes / wetness index derived on the device (include/mcf.h mcf_runmicro_dtm); the entry dispatches on
         # the inputs as mcf_runmicro1 .. 4 do
-        sp, _z = dtm_spec(dtm, m.rows, m.cols)
+        sp = dtm_spec(dtm, m.rows, m.cols)
         _abi.check(lib.mcf_runmicro_dtm(C.byref(m.inputs), C.byref(m.options), C.byref(sp), C.byref(mu[0]) if mu else None,
                                         C.byref(outs)))
         return arrays
@@ -373,12 +328,7 @@ def runmicro2Cpp_coarse(obstime: Mapping, climdata: Mapping, pointm: Mapping, ve
     COARSE arrays [coarse_rows, coarse_cols, tsteps] — what `.cca(..., dtmc, dtmc)` gives before `resample` — instead of
     the full-resolution arrays runmicro2Cpp takes.  `rowpos` / `colpos`: see `coarse_positions` (default: the coarse
     grid covers the raster's extent).  `diag`: as runmicro1Cpp — the diagnostics of the interpolated (and altitude-corrected) weather."""
-    R, Cc = np.shape(vegp["hgt"])[:2]
-    cr, cc = np.shape(climdata["temp"])[:2]
-    coarse = {"rowpos": coarse_positions(R, cr) if rowpos is None else rowpos,
-              "colpos": coarse_positions(Cc, cc) if colpos is None else colpos}
-    if altcorrect:                     # `.runmodel2Cpp`'s altcorrect 1 / 2 with the coarse (dtmc) and fine (dtm) elevations
-        coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=dtm)
+    coarse = _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm, refuse_missing=False)
     return _run("mcf_runmicro2", True, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, lons,
                 Sminp, Smaxp, tfact, complete, mat, out, device, days_per_chunk, 0, None, coarse, devices=devices, n_blocks=n_blocks,
                 diag=diag)
@@ -413,30 +363,32 @@ def runmicro4Cpp(dfsel: Mapping, obstime: Mapping, climdata: Mapping, pointm: Ma
 BIOCLIM_DFSEL = {"lyr": np.arange(1, 15), "st": np.arange(14) * 24, "ed": np.arange(14) * 24 + 23}   # cpp:3634-3646
 
 
+def _bioclim_sel(b: Buffers, wetq, dryq, hotq, colq, air, out):
+    """-> (mcf_bioclim_sel: the four quarters' step lists (held by `b`), `air`, the nineteen flags of `out`; `out` as a list)"""
+    sel = _abi.BioclimSel()
+    for name, q in (("wet", wetq), ("dry", dryq), ("hot", hotq), ("col", colq)):
+        setattr(sel, name + "q", b.i32_plain(q))
+        setattr(sel, "n" + name, np.size(q))
+    sel.air = 1 if air else 0
+    out = list(out)
+    if len(out) != _abi.NBIO:
+        raise ValueError("out must have 19 entries")
+    for v in range(_abi.NBIO):
+        sel.out[v] = 1 if out[v] else 0
+    return sel, out
+
+
 def _bioclim(fn_name, array_forcing, obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp,
              Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, layered=False, devices=None, n_blocks=0, coarse=None):
     lib = _abi.load()
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, True, mat,
                 [1] * 10, array_forcing, device, dfsel=BIOCLIM_DFSEL if layered else None, coarse=coarse)
-    sel = _abi.BioclimSel()
-    keep = []
-    for name, q in (("wet", wetq), ("dry", dryq), ("hot", hotq), ("col", colq)):
-        arr = np.ascontiguousarray(np.asarray(q).astype(np.int32))
-        keep.append(arr)
-        setattr(sel, name + "q", arr.ctypes.data_as(_abi.c_int32_p))
-        setattr(sel, "n" + name, arr.size)
-    sel.air = 1 if air else 0
-    out = list(out)
-    if len(out) != _abi.NBIO:
-        raise ValueError("out must have 19 entries")
+    sel, out = _bioclim_sel(m, wetq, dryq, hotq, colq, air, out)
     bo = _abi.BioclimOut()
     res = {}
     for v in range(_abi.NBIO):
-        sel.out[v] = 1 if out[v] else 0
         if out[v]:
-            a = np.empty((m.rows, m.cols), dtype=np.float64, order="F")
-            res[f"bio{v + 1}"] = a
-            bo.bio[v] = a.ctypes.data_as(_abi.c_double_p)
+            res[f"bio{v + 1}"], bo.bio[v] = m.out((m.rows, m.cols))
         else:
             bo.bio[v] = None
     mu = _abi.multi(devices, n_blocks)
@@ -464,13 +416,16 @@ def runbioclim2Cpp(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lats, l
                     Sminp, Smaxp, tfact, mat, out, wetq, dryq, hotq, colq, air, device, devices=devices, n_blocks=n_blocks)
 
 
-def _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm):
+def _coarse_spec(vegp, climdata, rowpos, colpos, altcorrect, dtmc, dtm, refuse_missing: bool = True):
+    """marshal()'s `coarse` mapping: the raster's positions on the climate grid (default: the grid covers the raster's extent)
+    and, with `altcorrect` 1 / 2 (`.runmodel2Cpp`'s), the coarse (dtmc) and fine (dtm) elevations.  `refuse_missing` False: absent
+    elevations are left to marshal()"""
     R, Cc = np.shape(vegp["hgt"])[:2]
     cr, cc = np.shape(climdata["temp"])[:2]
     coarse = {"rowpos": coarse_positions(R, cr) if rowpos is None else rowpos,
               "colpos": coarse_positions(Cc, cc) if colpos is None else colpos}
     if altcorrect:
-        if dtmc is None or dtm is None:
+        if refuse_missing and (dtmc is None or dtm is None):
             raise ValueError("altcorrect needs dtmc (the climate cells' elevations) and dtm (the raster's)")
         coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=dtm)
     return coarse
@@ -515,34 +470,22 @@ def runbioclim_depths(obstime, climdata, pointm, vegp, soilc, depths, zref, lat,
     reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0          # (the library judges the list)
     m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, True, mat,
                 [1] * 10, bool(array_forcing) or coarse is not None, device, 0, cells_per_block, BIOCLIM_DFSEL if layered else None, coarse)
-    sel = _abi.BioclimSel()
-    keep = []
-    for name, q in (("wet", wetq), ("dry", dryq), ("hot", hotq), ("col", colq)):
-        arr = np.ascontiguousarray(np.asarray(q).astype(np.int32))
-        keep.append(arr)
-        setattr(sel, name + "q", arr.ctypes.data_as(_abi.c_int32_p))
-        setattr(sel, "n" + name, arr.size)
-    sel.air = 1 if air else 0
-    out = list(out)
-    if len(out) != _abi.NBIO:
-        raise ValueError("out must have 19 entries")
+    sel, out = _bioclim_sel(m, wetq, dryq, hotq, colq, air, out)
     nd = min(d.size, _abi.MAX_DEPTHS)
     bo = _abi.BioclimDepthsOut()
     res = {"depths": d.copy()}
     for v in range(_abi.NBIO):
-        sel.out[v] = 1 if out[v] else 0
         if not out[v]:
             continue
         if v < 11:
             # (slab i is one Fortran-ordered [rows, cols] matrix)
             a = np.empty((nd, m.cols, m.rows), dtype=np.float64).transpose(0, 2, 1)
             for i in range(nd):
-                bo.temp[i][v] = a[i].ctypes.data_as(_abi.c_double_p)
+                bo.temp[i][v] = m.ptr(a[i])
         else:
-            a = np.empty((m.rows, m.cols), dtype=np.float64, order="F")
-            bo.moist[v - 11] = a.ctypes.data_as(_abi.c_double_p)
+            a, bo.moist[v - 11] = m.out((m.rows, m.cols))
         res[f"bio{v + 1}"] = a
-    _abi.check(lib.mcf_runbioclim_depths(C.byref(m.inputs), C.byref(m.options), C.byref(sel), _ptr(d), int(d.size), int(chunk_days),
+    _abi.check(lib.mcf_runbioclim_depths(C.byref(m.inputs), C.byref(m.options), C.byref(sel), m.ptr(d), int(d.size), int(chunk_days),
                                          C.byref(bo)))
     return res
 
@@ -573,7 +516,7 @@ class Plan:
         if dtm is not None:
             if stream_below:
                 raise ValueError("streamed below-ground plans have no dtm form")
-            sp, _z = dtm_spec(dtm, self._m.rows, self._m.cols)
+            sp = dtm_spec(dtm, self._m.rows, self._m.cols)
             _abi.check(self._lib.mcf_plan_create_dtm(C.byref(self._m.inputs), C.byref(self._m.options), C.byref(sp), int(ring_days),
                                                      int(ring_slots), C.byref(self._p)))
         else:
@@ -630,8 +573,7 @@ class Plan:
     def run_days_masked(self, day0: int, ndays: int, slot: int, slot_day0: int, skip_tile):
         """run_days_at leaving out the tiles with skip_tile[t] != 0 (include/mcf.h mcf_plan_run_days_masked)."""
         sk = np.ascontiguousarray(skip_tile, dtype=np.uint8)
-        _abi.check(self._lib.mcf_plan_run_days_masked(self._p, day0, ndays, slot, slot_day0, sk.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                      int(sk.size)))
+        _abi.check(self._lib.mcf_plan_run_days_masked(self._p, day0, ndays, slot, slot_day0, Buffers().ptr(sk), int(sk.size)))
 
     def run_days_cells(self, day0: int, ndays: int, slot: int, slot_day0: int, need_cell_dev: int) -> int:
         """run_days_at for the cells marked in `need_cell_dev` — the ADDRESS of one byte per cell in this device's memory, e.g.
@@ -655,7 +597,7 @@ class Plan:
         """array forcing: the per-cell temperature cap over the days with dayflag != 0 (include/mcf.h mcf_plan_set_mxtc_days); a
         coarse plan folds its resident series, a fine one streams its temperature array again"""
         flags = np.ascontiguousarray(dayflag, dtype=np.int32)
-        _abi.check(self._lib.mcf_plan_set_mxtc_days(self._p, C.byref(self._m.inputs), flags.ctypes.data_as(_abi.c_int32_p), int(flags.size)))
+        _abi.check(self._lib.mcf_plan_set_mxtc_days(self._p, C.byref(self._m.inputs), Buffers().ptr(flags), int(flags.size)))
 
     def set_day_layers(self, layer_of_day=None):
         """layered vegetation: the day -> layer map (include/mcf.h mcf_plan_set_day_layers); None: the plan's own table again"""
@@ -663,12 +605,12 @@ class Plan:
             _abi.check(self._lib.mcf_plan_set_day_layers(self._p, None, self.ndays))
             return
         lod = np.ascontiguousarray(layer_of_day, dtype=np.int32)
-        _abi.check(self._lib.mcf_plan_set_day_layers(self._p, lod.ctypes.data_as(_abi.c_int32_p), int(lod.size)))
+        _abi.check(self._lib.mcf_plan_set_day_layers(self._p, Buffers().ptr(lod), int(lod.size)))
 
     def fetch_mxtc(self) -> np.ndarray:
         """array forcing: the per-cell maximum air temperature the plan holds now, [rows, cols]"""
-        a = np.empty((self.rows, self.cols), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_fetch_mxtc(self._p, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols))
+        _abi.check(self._lib.mcf_plan_fetch_mxtc(self._p, ptr))
         return a
 
     def set_height(self, h: float, pai_a=None):
@@ -683,14 +625,14 @@ class Plan:
                 a = a[:, :, :L]
             if a.size != self.rows * self.cols * L:
                 raise ValueError(f"pai_a: expected {self.rows} x {self.cols} x {L} values, got shape {a.shape}")
-        _abi.check(self._lib.mcf_plan_set_height(self._p, float(h), _ptr(a)))
+        _abi.check(self._lib.mcf_plan_set_height(self._p, float(h), Buffers().ptr(a)))
 
     def fetch_foliage(self):
         """(paia, leafden) as the plan holds them now, [rows, cols] or [rows, cols, layers]"""
         L = int(self._m.inputs.veg_layers)
         shape = (self.rows, self.cols) if L < 1 else (self.rows, self.cols, L)
-        pa, ld = np.empty(shape, dtype=np.float64, order="F"), np.empty(shape, dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_fetch_foliage(self._p, _ptr(pa), _ptr(ld)))
+        (pa, pap), (ld, ldp) = Buffers().out(shape), Buffers().out(shape)
+        _abi.check(self._lib.mcf_plan_fetch_foliage(self._p, pap, ldp))
         return pa, ld
 
     def belowground(self):
@@ -705,21 +647,21 @@ class Plan:
         """Streamed below-ground plan, before below_prepare(): the series Tbelowgroundv sees is the listed whole days (strictly
         ascending) joined end to end (include/mcf.h mcf_plan_below_set_days).  run_days(day0, ndays, slot) then runs the
         subset's days inside that calendar range, each at its own place day - day0 of the slot."""
-        d = np.ascontiguousarray(np.asarray(days).astype(np.int32))
-        _abi.check(self._lib.mcf_plan_below_set_days(self._p, d.ctypes.data_as(_abi.c_int32_p), int(d.size)))
+        b = Buffers()
+        _abi.check(self._lib.mcf_plan_below_set_days(self._p, b.i32_plain(days), int(np.size(days))))
 
     def below_set_depths(self, depths, tbp=None):
         """Streamed below-ground plan with Tz, before below_prepare(): Tbelowgroundv at each of `depths` (< 0, any order, at most
         _abi.MAX_DEPTHS) from the one solve (include/mcf.h mcf_plan_below_set_depths).  `tbp`: [ndepths, tsteps], the point
         model's soil temperature per depth — needed with complete = False.  fetch() and the sinks see depths[0]."""
         d, t = _depth_list(depths, tbp, self.tsteps)
-        _abi.check(self._lib.mcf_plan_below_set_depths(self._p, _ptr(d), int(d.size), _ptr(t)))
+        _abi.check(self._lib.mcf_plan_below_set_depths(self._p, Buffers().ptr(d), int(d.size), Buffers().ptr(t)))
         self.depths = d.copy()
 
     def fetch_depth(self, slot: int, depth: int, step0: int, nsteps: int) -> np.ndarray:
         """fetch() of Tz at depth index `depth` of the list (a plan without a list: 0)"""
-        a = np.empty((self.rows, self.cols, nsteps), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_fetch_depth(self._p, slot, int(depth), step0, nsteps, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols, nsteps))
+        _abi.check(self._lib.mcf_plan_fetch_depth(self._p, slot, int(depth), step0, nsteps, ptr))
         return a
 
     def summary_enable_below(self, periods, vars=("Tz",), stats=("mean", "min", "max"), thresholds=None, *, nperiods=None):
@@ -739,8 +681,8 @@ class Plan:
         """fetch_summary() of Tz at depth index `depth`; soilm has depth 0 alone"""
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
         s = _abi.STAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
-        a = np.empty((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_summary_fetch_depth(self._p, int(depth), v, s, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)))
+        _abi.check(self._lib.mcf_plan_summary_fetch_depth(self._p, int(depth), v, s, ptr))
         return a
 
     def sync(self):
@@ -764,8 +706,8 @@ class Plan:
     def fetch_diag(self, slot: int, dvar, step0: int, nsteps: int) -> np.ndarray:
         """fetch() for a selected diagnostic (a name or an index of include/mcf.h mcf_diag)"""
         v = _abi.DIAG_NAMES.index(dvar) if isinstance(dvar, str) else int(dvar)
-        a = np.empty((self.rows, self.cols, nsteps), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_diag_fetch(self._p, slot, v, step0, nsteps, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols, nsteps))
+        _abi.check(self._lib.mcf_plan_diag_fetch(self._p, slot, v, step0, nsteps, ptr))
         return a
 
     def diag_ring_layout(self) -> dict:
@@ -798,18 +740,28 @@ class Plan:
         filled them; days in ascending order, each at most once (include/mcf.h mcf_plan_summary_accumulate)."""
         _abi.check(self._lib.mcf_plan_summary_accumulate(self._p, slot, slot_day0, day0, ndays))
 
+    def summarise_days(self, ring: int):
+        """The whole series through ring slot 0 in chunks of `ring` days, each run and then folded (array forcing: its forcing
+        uploaded first)."""
+        for d0 in range(0, self.ndays, ring):
+            n = min(ring, self.ndays - d0)
+            if self.array_forcing:
+                self.upload_forcing_days(d0, n, 0)
+            self.run_days(d0, n, 0)
+            self.summary_accumulate(0, 0, d0, n)
+
     def fetch_summary(self, var, stat) -> np.ndarray:
         """[rows, cols, nperiods] of one selected statistic of one selected variable (names or indices)"""
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
         s = _abi.STAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
-        a = np.empty((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_summary_fetch(self._p, v, s, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols, getattr(self, "_summary_nperiods", 1)))
+        _abi.check(self._lib.mcf_plan_summary_fetch(self._p, v, s, ptr))
         return a
 
     def summary_days(self) -> np.ndarray:
         """counted days folded so far into each period"""
-        d = np.zeros(getattr(self, "_summary_nperiods", 1), dtype=np.int32)
-        _abi.check(self._lib.mcf_plan_summary_days(self._p, d.ctypes.data_as(_abi.c_int32_p)))
+        d, ptr = Buffers().out(getattr(self, "_summary_nperiods", 1), np.int32, zero=True)
+        _abi.check(self._lib.mcf_plan_summary_days(self._p, ptr))
         return d
 
     def summary_reset(self):
@@ -818,19 +770,16 @@ class Plan:
 
     def fetch(self, slot: int, var, step0: int, nsteps: int) -> np.ndarray:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
-        a = np.empty((self.rows, self.cols, nsteps), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_fetch(self._p, slot, v, step0, nsteps,
-                                            a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols, nsteps))
+        _abi.check(self._lib.mcf_plan_fetch(self._p, slot, v, step0, nsteps, ptr))
         return a
 
     def fetch_cells(self, slot: int, var, step0: int, nsteps: int, cells) -> np.ndarray:
         """[len(cells), nsteps] values of `var` for the listed cells (0-based column-major indices i + rows*j)."""
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
         cells = np.ascontiguousarray(np.asarray(cells, dtype=np.int64))
-        a = np.empty((cells.size, nsteps), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_plan_fetch_cells(self._p, slot, v, step0, nsteps,
-                                                  cells.ctypes.data_as(C.POINTER(C.c_int64)), cells.size,
-                                                  a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((cells.size, nsteps))
+        _abi.check(self._lib.mcf_plan_fetch_cells(self._p, slot, v, step0, nsteps, Buffers().ptr(cells), cells.size, ptr))
         return a
 
     # writetonc's scale per variable (R/dataprep.R:1158-1167): x100 for temperatures, soil moisture, wind
@@ -844,11 +793,9 @@ class Plan:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
         if scale is None:
             scale = self.NC_SCALE[_abi.OUT_NAMES[v]]
-        a = np.empty((self.cols, self.rows, nsteps), dtype=np.int32, order="F")
+        a, ptr = Buffers().out((self.cols, self.rows, nsteps), np.int32)
         ms = C.c_float()
-        _abi.check(self._lib.mcf_plan_fetch_packed(self._p, slot, v, step0, nsteps, float(scale),
-                                                   a.ctypes.data_as(_abi.c_int32_p),
-                                                   C.byref(ms) if timing else None))
+        _abi.check(self._lib.mcf_plan_fetch_packed(self._p, slot, v, step0, nsteps, float(scale), ptr, C.byref(ms) if timing else None))
         return (a, ms.value) if timing else a
 
     def ring_layout(self) -> dict:
@@ -883,9 +830,8 @@ class Plan:
 def below_days_range(days, total_days: int, day0: int, ndays: int):
     """(pos0, npos): the positions of the day subset `days` that lie in the calendar range [day0, day0 + ndays) of a series of
     `total_days` whole days (include/mcf.h mcf_below_days_range; the list is checked as Plan.below_set_days checks it)."""
-    d = np.ascontiguousarray(np.asarray(days).astype(np.int32))
-    pos0, npos = C.c_int32(), C.c_int32()
-    _abi.check(_abi.load().mcf_below_days_range(d.ctypes.data_as(_abi.c_int32_p), int(d.size), int(total_days), int(day0), int(ndays),
+    b, pos0, npos = Buffers(), C.c_int32(), C.c_int32()
+    _abi.check(_abi.load().mcf_below_days_range(b.i32_plain(days), int(np.size(days)), int(total_days), int(day0), int(ndays),
                                                 C.byref(pos0), C.byref(npos)))
     return pos0.value, npos.value
 

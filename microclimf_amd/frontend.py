@@ -458,6 +458,16 @@ def summary_periods(obstime: Mapping, by="month"):
     return tab, ([k[0] for k in seen] if by == "year" else [fmt.format(*k) for k in seen])
 
 
+def _out_mask(vars, allow_none: bool = True):
+    """-> (the names, the solver's ten `out` flags) for output names (one name or several); a name that is no output is refused,
+    and with `allow_none` False an empty selection too"""
+    names = (vars,) if isinstance(vars, str) else tuple(vars)
+    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    if sum(out) != len(set(names)) or not (names or allow_none):
+        raise ValueError(f"vars: names of {api._abi.OUT_NAMES}")
+    return names, out
+
+
 def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
                      vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None, pai_a=None,
                      tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
@@ -471,10 +481,7 @@ def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, d
     -> {variable: {statistic: [rows, cols, nperiods]}, "periods": labels, "days": counted days per period}"""
     if reqhgt < 0:
         raise ValueError("period summaries need reqhgt >= 0 (below ground: runmicro_depths_summary)")
-    names = (vars,) if isinstance(vars, str) else tuple(vars)
-    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
-    if sum(out) != len(set(names)):
-        raise ValueError(f"vars: names of {api._abi.OUT_NAMES}")
+    names, out = _out_mask(vars)
     ter = dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf)
     array = not isinstance(micropoint, Mapping)
     if array:
@@ -484,10 +491,8 @@ def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, d
             raise ValueError("from_dtm is not available with array weather")
         a = prepare_grid_inputs_array(micropoint, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, pai_a=pai_a, out=out,
                                       device=device, **ter)
-        R, Cc = a["vegp"]["hgt"].shape[:2]
-        coarse = {"rowpos": api.coarse_positions(R, crows), "colpos": api.coarse_positions(Cc, ccols)}
-        if altcorrect:
-            coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=cleanvars(vegp, soilc, dtm["z"])[2])
+        coarse = api._coarse_spec(a["vegp"], a["climdata"], None, None, altcorrect, dtmc,
+                                  cleanvars(vegp, soilc, dtm["z"])[2] if altcorrect else None, refuse_missing=False)
         extra = dict(array_forcing=True, coarse=coarse)
     else:
         a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device, from_dtm=from_dtm, **ter)
@@ -591,10 +596,7 @@ def runmicro_heights_summary(micropoint: Mapping, heights, vegp: Mapping, soilc:
     """runmicro_heights reduced over time on the device, as runmicro_summary reduces runmicro: one plan with period summaries,
     per height set_height, summary_reset, the accumulate loop and the fetches.
     -> {"heights": heights, variable: [per height {statistic: [rows, cols, nperiods]}], "periods": labels, "days": counted days}"""
-    names = (vars,) if isinstance(vars, str) else tuple(vars)
-    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
-    if not names or sum(out) != len(set(names)):
-        raise ValueError(f"vars: names of {api._abi.OUT_NAMES}")
+    names, out = _out_mask(vars, allow_none=False)
     a, heights, pai_a = _height_inputs(micropoint, heights, vegp, soilc, dtm, pai_a, tfact,
                                        dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device, out)
     tab, labels = summary_periods(a["obstime"], periods)
@@ -608,10 +610,7 @@ def runmicro_heights_summary(micropoint: Mapping, heights, vegp: Mapping, soilc:
         for h, hgt in enumerate(heights):
             p.set_height(hgt, None if pai_a is None else pai_a[h])
             p.summary_reset()
-            for d0 in range(0, nd, ring):
-                n = min(ring, nd - d0)
-                p.run_days(d0, n, 0)
-                p.summary_accumulate(0, 0, d0, n)
+            p.summarise_days(ring)
             for v in vi:
                 res.setdefault(v, []).append({s: p.fetch_summary(v, s) for s in si})
             res["days"] = p.summary_days()
@@ -921,10 +920,8 @@ def _run_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, *, lats, lon
     a = prepare_grid_inputs_array(micropointa, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, device=device, **kw)
     a["tfact"] = float(tfact)
     dfsel = a.pop("dfsel", None)
-    R, Cc = a["vegp"]["hgt"].shape[:2]
-    coarse = {"rowpos": api.coarse_positions(R, crows), "colpos": api.coarse_positions(Cc, ccols)}
-    if altcorrect:
-        coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=cleanvars(vegp, soilc, dtm["z"])[2])
+    coarse = api._coarse_spec(a["vegp"], a["climdata"], None, None, altcorrect, dtmc,
+                              cleanvars(vegp, soilc, dtm["z"])[2] if altcorrect else None, refuse_missing=False)
     order = ("obstime", "climdata", "pointm", "vegp", "soilc", "reqhgt", "zref", "lat", "lon", "Sminp", "Smaxp", "tfact",
              "complete", "mat", "out")
     fn = "mcf_runmicro2" if dfsel is None else "mcf_runmicro4"
@@ -1305,6 +1302,33 @@ def _snow_day_outm(out: Sequence, reqhgt: float) -> list:
     return [int(bool(v)) for v in out]
 
 
+def _snow_host_route(smod: Mapping, z, reqhgt: float, pai_a, tfact: float, out: Sequence, device: int, solve_days, snow_days) -> dict:
+    """What `.runmicrosnow1` and `.runmicrosnow2` share (R/internal.R:3581-3659, 3661-3742): the day classes from the snow
+    model's totalSWE (NA -> 0, masked by the dtm `z`), the no-snow days through `solve_days(days, **runmicro's keywords)` (none:
+    `.createblanktemplate`, day 1 solved and blanked), the snow days through `snow_days(smod, snowdays, their hour indices, the
+    template gridmicrosnow writes over, its output selection)`, and the two merged by day"""
+    from . import snow as S
+    sm = dict(smod)
+    swe = np.array(sm["totalSWE"], dtype=np.float64, copy=True)
+    swe[np.isnan(swe)] = 0.0
+    swe[np.isnan(z)] = np.nan                                            # mask(totalSWE, dtm)
+    sm["totalSWE"] = swe
+    sd = S.snowdaysfun(S.applycpp3(swe, "max", device=device), S.applycpp3(swe, "min", device=device))
+    alldays = np.arange(1, len(sd["snowdays"]) + 1)
+    snowdays, nosnowdays = alldays[sd["snowdays"] == 1], alldays[sd["nosnowdays"] == 1]
+    rows, cols = z.shape
+    if len(nosnowdays):
+        moutn = solve_days(nosnowdays, pai_a=pai_a, tfact=tfact, out=out)
+    else:
+        moutn = {k: v * np.nan for k, v in solve_days([1], tfact=1.5, out=out).items()}
+    if not len(snowdays):
+        return moutn
+    ai = (np.repeat((snowdays - 1) * 24, 24) + np.tile(np.arange(24), snowdays.size)).astype(np.int64)
+    micro = _snow_day_template(moutn, snowdays, nosnowdays, rows, cols)
+    mouts = snow_days(sm, snowdays, ai, micro, _snow_day_outm(out, reqhgt))
+    return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
+
+
 def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, smod: Mapping | None, *,
                   pai_a=None, tfact: float = 1.5, out: Sequence = (1,) * 10, device: int = 0,
                   _solve=None, _microsnow=None, _terrain=None, one_call: bool = False, snow_inputs: Mapping | None = None) -> dict:
@@ -1322,35 +1346,20 @@ def runmicro_snow(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapp
     solve = runmicro if _solve is None else _solve
     microsnow = S.gridmicrosnow1 if _microsnow is None else _microsnow
     veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
-    sm = dict(smod)
-    swe = np.array(sm["totalSWE"], dtype=np.float64, copy=True)
-    swe[np.isnan(swe)] = 0.0
-    swe[np.isnan(z)] = np.nan                                            # mask(totalSWE, dtm)
-    sm["totalSWE"] = swe
-    sd = S.snowdaysfun(S.applycpp3(swe, "max", device=device), S.applycpp3(swe, "min", device=device))
-    alldays = np.arange(1, len(sd["snowdays"]) + 1)
-    snowdays, nosnowdays = alldays[sd["snowdays"] == 1], alldays[sd["nosnowdays"] == 1]
-    rows, cols = z.shape
-    if len(nosnowdays):
-        moutn = solve(subsetpointmodel(micropoint, days=nosnowdays), reqhgt, vegp, soilc, dtm, pai_a=pai_a, tfact=tfact,
-                      out=out, device=device)
-    else:                                                                # .createblanktemplate1
-        moutn = solve(subsetpointmodel(micropoint, days=[1]), reqhgt, vegp, soilc, dtm, tfact=1.5, out=out, device=device)
-        moutn = {k: v * np.nan for k, v in moutn.items()}
-    if not len(snowdays):
-        return moutn
-    mps = subsetpointmodel(micropoint, days=snowdays)
-    ai = (np.repeat((snowdays - 1) * 24, 24) + np.tile(np.arange(24), snowdays.size)).astype(np.int64)
-    w = dict(mps["weather"])
-    w["umu"] = np.asarray(sm["umu"])[ai]
-    sdept = np.zeros(micropoint["ntme"])
-    sdept[np.asarray(mps["subs"]) - 1] = 1
-    vg = sortl2(veg, sdept, reqhgt, pai_a)
-    other = _snow_day_other(z, dtm, micropoint["zref"], float(micropoint["lat"]), float(micropoint["long"]), soil, device, _terrain)
-    micro = _snow_day_template(moutn, snowdays, nosnowdays, rows, cols)
-    smods = subsetsnowmodel(sm, ai + 1)
-    mouts = microsnow(reqhgt, mps["obstime"], w, smods, micro, vg, other, float(micropoint["matemp"]), _snow_day_outm(out, reqhgt))
-    return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
+
+    def solve_days(days, **kw):
+        return solve(subsetpointmodel(micropoint, days=days), reqhgt, vegp, soilc, dtm, device=device, **kw)
+
+    def snow_days(sm, snowdays, ai, micro, outm):
+        mps = subsetpointmodel(micropoint, days=snowdays)
+        w = dict(mps["weather"])
+        w["umu"] = np.asarray(sm["umu"])[ai]
+        sdept = np.zeros(micropoint["ntme"])
+        sdept[np.asarray(mps["subs"]) - 1] = 1
+        vg = sortl2(veg, sdept, reqhgt, pai_a)
+        other = _snow_day_other(z, dtm, micropoint["zref"], float(micropoint["lat"]), float(micropoint["long"]), soil, device, _terrain)
+        return microsnow(reqhgt, mps["obstime"], w, subsetsnowmodel(sm, ai + 1), micro, vg, other, float(micropoint["matemp"]), outm)
+    return _snow_host_route(smod, z, reqhgt, pai_a, tfact, out, device, solve_days, snow_days)
 
 
 def _runmicro_snow_one_call(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, pai_a, tfact, out, device, _terrain):
@@ -1431,7 +1440,7 @@ def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soi
         raise ValueError("snow_inputs = runsnowmodel(weather, micropoint, vegp, soilc, dtm, inputs_only=True) is needed")
     if len(micropoint["subs"]) != micropoint["ntme"]:
         raise ValueError("the one-call snow run takes a complete micropoint")
-    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    out = _out_mask(names)[1]
     a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device)
     a["tfact"] = float(tfact)
     kept = [n for n, o in zip(api._abi.OUT_NAMES, a["out"]) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
@@ -1513,38 +1522,24 @@ def runmicro_snow_array(micropointa: Sequence, crows: int, ccols: int, reqhgt: f
         return runmicro_array(mpa, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, altcorrect=altcorrect, dtmc=dtmc,
                               device=device, **kw)
     veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
-    hole = np.isnan(z)
-    sm = dict(smod)
-    swe = np.array(sm["totalSWE"], dtype=np.float64, copy=True)
-    swe[np.isnan(swe)] = 0.0
-    swe[hole] = np.nan
-    sm["totalSWE"] = swe
-    sd = S.snowdaysfun(S.applycpp3(swe, "max", device=device), S.applycpp3(swe, "min", device=device))
-    alldays = np.arange(1, len(sd["snowdays"]) + 1)
-    snowdays, nosnowdays = alldays[sd["snowdays"] == 1], alldays[sd["nosnowdays"] == 1]
-    rows, cols = z.shape
-    if len(nosnowdays):
-        moutn = solve([subsetpointmodel(m, days=nosnowdays) for m in micropointa], pai_a=pai_a, tfact=tfact, out=out)
-    else:                                                                # .createblanktemplate2
-        moutn = {k: v * np.nan for k, v in solve([subsetpointmodel(m, days=[1]) for m in micropointa], tfact=1.5, out=out).items()}
-    if not len(snowdays):
-        return moutn
-    mps = [subsetpointmodel(m, days=snowdays) for m in micropointa]
-    ai = (np.repeat((snowdays - 1) * 24, 24) + np.tile(np.arange(24), snowdays.size)).astype(np.int64)
-    rowpos, colpos = api.coarse_positions(rows, crows), api.coarse_positions(cols, ccols)
-    wc = {k: _stack_micropoints(mps, crows, ccols, lambda m, k=k: m["weather"][k]) for k in WEATHER}
-    zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0) if altcorrect else None
-    w = S._fine_micro_inputs(wc, _stack_micropoints(mps, crows, ccols, lambda m: m["dfo"]["umu"]), slice(None), z, zc, rowpos, colpos,
-                             altcorrect)
-    last = micropointa[-1]
-    vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
-    other = _snow_day_other(z, dtm, float(last["zref"]), np.asarray(lats, dtype=np.float64), np.asarray(lons, dtype=np.float64), soil,
-                            device, _terrain)
-    micro = _snow_day_template(moutn, snowdays, nosnowdays, rows, cols)
-    smods = {k: np.asfortranarray(np.asarray(sm[k])[:, :, ai]) for k in ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden")}
-    mouts = microsnow(reqhgt, mps[0]["obstime"], w, smods, micro, vg, other, float(np.mean([m["matemp"] for m in micropointa])),
-                      _snow_day_outm(out, reqhgt))
-    return S.merge_snow_outputs(moutn, mouts, snowdays, nosnowdays, rows, cols)
+
+    def solve_days(days, **kw):
+        return solve([subsetpointmodel(m, days=days) for m in micropointa], **kw)
+
+    def snow_days(sm, snowdays, ai, micro, outm):
+        mps = [subsetpointmodel(m, days=snowdays) for m in micropointa]
+        rowpos, colpos = api.coarse_positions(z.shape[0], crows), api.coarse_positions(z.shape[1], ccols)
+        wc = {k: _stack_micropoints(mps, crows, ccols, lambda m, k=k: m["weather"][k]) for k in WEATHER}
+        zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0) if altcorrect else None
+        w = S._fine_micro_inputs(wc, _stack_micropoints(mps, crows, ccols, lambda m: m["dfo"]["umu"]), slice(None), z, zc, rowpos, colpos,
+                                 altcorrect)
+        last = micropointa[-1]
+        vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
+        other = _snow_day_other(z, dtm, float(last["zref"]), np.asarray(lats, dtype=np.float64), np.asarray(lons, dtype=np.float64), soil,
+                                device, _terrain)
+        smods = {k: np.asfortranarray(np.asarray(sm[k])[:, :, ai]) for k in ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden")}
+        return microsnow(reqhgt, mps[0]["obstime"], w, smods, micro, vg, other, float(np.mean([m["matemp"] for m in micropointa])), outm)
+    return _snow_host_route(smod, z, reqhgt, pai_a, tfact, out, device, solve_days, snow_days)
 
 
 def snow_array_groups(micropointa: Sequence, crows: int, ccols: int, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping,
@@ -1562,11 +1557,7 @@ def snow_array_groups(micropointa: Sequence, crows: int, ccols: int, reqhgt: flo
                                   device=device)
     a["tfact"] = float(tfact)
     veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
-    rows, cols = z.shape
-    coarse = {"rowpos": api.coarse_positions(rows, crows), "colpos": api.coarse_positions(cols, ccols)}
-    if altcorrect:
-        coarse.update(altcorrect=int(altcorrect), dtmc=dtmc, dtm=z)
-    a["coarse"] = coarse
+    a["coarse"] = api._coarse_spec(a["vegp"], a["climdata"], None, None, altcorrect, dtmc, z, refuse_missing=False)
     last = micropointa[-1]
     vg = sortl2(veg, np.zeros(last["ntme"]), reqhgt, pai_a)
     other = _snow_day_other(z, dtm, float(last["zref"]), np.asarray(lats, dtype=np.float64), np.asarray(lons, dtype=np.float64), soil,

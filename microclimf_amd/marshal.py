@@ -16,32 +16,78 @@ import numpy as np
 
 from . import _abi
 
+_POINTER = {np.dtype(np.float64): _abi.c_double_p, np.dtype(np.int32): _abi.c_int32_p, np.dtype(np.int64): C.POINTER(C.c_int64),
+            np.dtype(np.uint8): C.POINTER(C.c_uint8)}
 
-class Marshalled:
-    """GridInputs/Options plus the numpy arrays that back their pointers."""
+
+class Buffers:
+    """Owner of the numpy arrays behind the pointers it hands out: every such array lives as long as this object, so a pointer
+    is good for as long as its owner is referenced (a call's own owner: for the call; a marshalling's: with the marshalling)."""
 
     def __init__(self):
-        self.inputs = _abi.GridInputs()
-        self.options = _abi.Options()
         self._keep = []
-        self.rows = self.cols = self.tsteps = 0
 
-    def _f64(self, a, shape=None, name="?"):
+    def ptr(self, a):
+        """the pointer to an array as it lies in memory (None: a null pointer); the array is held from here on"""
+        if a is None:
+            return None
+        self._keep.append(a)
+        return a.ctypes.data_as(_POINTER[a.dtype])
+
+    def f64(self, a, shape=None, name="?"):
+        """column-major fp64 of `shape`; an array of another shape and the same size is read in Fortran order"""
         arr = np.asarray(a, dtype=np.float64)
         if shape is not None and tuple(arr.shape) != tuple(shape):
             if arr.size != int(np.prod(shape)):
                 raise ValueError(f"{name}: expected shape {tuple(shape)}, got {arr.shape}")
             arr = arr.reshape(shape, order="F")
-        arr = np.asfortranarray(arr)
-        self._keep.append(arr)
-        return arr.ctypes.data_as(_abi.c_double_p)
+        return self.ptr(np.asfortranarray(arr))
 
-    def _i32(self, a, n, name):
+    def i32_plain(self, a, n=None, name="?"):
+        """numpy's own conversion to int32 (integers arrive as integers: year, month, day, step ranges, day tables)"""
         arr = np.ascontiguousarray(np.asarray(a).astype(np.int32))
-        if arr.shape != (n,):
+        if n is not None and arr.shape != (n,):
             raise ValueError(f"{name}: expected length {n}")
-        self._keep.append(arr)
-        return arr.ctypes.data_as(_abi.c_int32_p)
+        return self.ptr(arr)
+
+    def i32_rcpp(self, a, shape, name):
+        """Rcpp's as<IntegerVector/IntegerMatrix>(): doubles truncated towards zero, NA cells NA_integer_ (INT_MIN)"""
+        v = np.trunc(np.asarray(a, dtype=np.float64))
+        arr = np.asfortranarray(np.where(np.isnan(v), float(np.iinfo(np.int32).min), v).astype(np.int32))
+        if tuple(arr.shape) != tuple(shape):
+            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {arr.shape}")
+        return self.ptr(arr)
+
+    def i64(self, a):
+        return self.ptr(np.ascontiguousarray(a, dtype=np.int64))
+
+    def out(self, shape, dtype=np.float64, zero=False):
+        """-> (a column-major array for the library to write into, its pointer)"""
+        a = (np.zeros if zero else np.empty)(shape, dtype=dtype, order="F")
+        return a, self.ptr(a)
+
+
+class Marshalled(Buffers):
+    """GridInputs/Options plus the numpy arrays that back their pointers."""
+
+    def __init__(self):
+        super().__init__()
+        self.inputs = _abi.GridInputs()
+        self.options = _abi.Options()
+        self.rows = self.cols = self.tsteps = 0
+
+    i32 = Buffers.i32_plain
+
+
+class SnowMarshalled(Buffers):
+    """mcf_snow_inputs plus the numpy arrays that back its pointers (and those of the structs built around it)."""
+
+    def __init__(self):
+        super().__init__()
+        self.inputs = _abi.SnowInputs()
+        self.rows = self.cols = self.tsteps = 0
+
+    i32 = Buffers.i32_rcpp
 
 
 def _get(d: Mapping, *names):
@@ -88,18 +134,18 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             raise ValueError("coarse climate arrays must be [coarse_rows, coarse_cols, tsteps]")
         cshape = t0.shape
         gi.coarse_rows, gi.coarse_cols = int(cshape[0]), int(cshape[1])
-        gi.coarse_rowpos = m._f64(coarse["rowpos"], (R,), "coarse$rowpos")
-        gi.coarse_colpos = m._f64(coarse["colpos"], (Cc,), "coarse$colpos")
-        gi.coarse_relhum = m._f64(climdata["relhum"], cshape, "climdata$relhum")
-        gi.coarse_winddir = m._f64(climdata["winddir"], cshape, "climdata$winddir")
+        gi.coarse_rowpos = m.f64(coarse["rowpos"], (R,), "coarse$rowpos")
+        gi.coarse_colpos = m.f64(coarse["colpos"], (Cc,), "coarse$colpos")
+        gi.coarse_relhum = m.f64(climdata["relhum"], cshape, "climdata$relhum")
+        gi.coarse_winddir = m.f64(climdata["winddir"], cshape, "climdata$winddir")
         gi.coarse_altcorrect = int(coarse.get("altcorrect", 0))
         if gi.coarse_altcorrect:
-            gi.coarse_dtm = m._f64(coarse["dtmc"], cshape[:2], "coarse$dtmc")
-            gi.fine_dtm = m._f64(coarse["dtm"], (R, Cc), "coarse$dtm")
-    gi.obstime.year = m._i32(obstime["year"], T, "obstime$year")
-    gi.obstime.month = m._i32(obstime["month"], T, "obstime$month")
-    gi.obstime.day = m._i32(obstime["day"], T, "obstime$day")
-    gi.obstime.hour = m._f64(obstime["hour"], (T,), "obstime$hour")
+            gi.coarse_dtm = m.f64(coarse["dtmc"], cshape[:2], "coarse$dtmc")
+            gi.fine_dtm = m.f64(coarse["dtm"], (R, Cc), "coarse$dtm")
+    gi.obstime.year = m.i32_plain(obstime["year"], T, "obstime$year")
+    gi.obstime.month = m.i32_plain(obstime["month"], T, "obstime$month")
+    gi.obstime.day = m.i32_plain(obstime["day"], T, "obstime$day")
+    gi.obstime.hour = m.f64(obstime["hour"], (T,), "obstime$hour")
     fshape = cshape if coarse is not None else (R, Cc, T) if array_forcing else (T,)
     # climdata: data.frame names (1Cpp) or list names (2Cpp)
     names = {"tc": ("temp", "tc"), "pk": ("pres", "pk")}
@@ -109,7 +155,7 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             continue
         src = _get(climdata, *names.get(f, (f,)))
         shape = (T,) if f == "winddir" else fshape
-        setattr(gi.clim, f, m._f64(src, shape, f"climdata${f}"))
+        setattr(gi.clim, f, m.f64(src, shape, f"climdata${f}"))
     need_tgp = (reqhgt < 0) and (not complete)
     for f in _abi.POINTM_FIELDS:
         if f in ("Tg", "Tbp") and not need_tgp:
@@ -118,7 +164,7 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
         src = _get(pointm, *(("G", "Gp") if f == "G" else (f,)))
         if f == "Tbp" and np.ndim(src) == 0:       # `pointm$Tbp <- 0` (R/internal.R:1096)
             src = np.full(fshape, float(src))
-        setattr(gi.pointm, f, m._f64(src, fshape, f"pointm${f}"))
+        setattr(gi.pointm, f, m.f64(src, fshape, f"pointm${f}"))
     for f in _abi.VEGP_FIELDS:
         if f in vegp_optional and vegp.get(f) is None:
             setattr(gi.vegp, f, None)
@@ -129,23 +175,23 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
             if src.ndim != 3 or src.shape[2] < L:
                 raise ValueError(f"vegp${f}: expected [rows, cols, >= {L} layers]")
             src = src[:, :, :L]            # a contiguous prefix in column-major order: no copy
-        setattr(gi.vegp, f, m._f64(src, (R, Cc) if dfsel is None else (R, Cc, L), f"vegp${f}"))
+        setattr(gi.vegp, f, m.f64(src, (R, Cc) if dfsel is None else (R, Cc, L), f"vegp${f}"))
     if dfsel is None:
         gi.veg_layers = 0
         gi.lyr_st = gi.lyr_ed = None
     else:
         gi.veg_layers = L
-        gi.lyr_st = m._i32(dfsel["st"], L, "dfsel$st")
-        gi.lyr_ed = m._i32(dfsel["ed"], L, "dfsel$ed")
+        gi.lyr_st = m.i32_plain(dfsel["st"], L, "dfsel$st")
+        gi.lyr_ed = m.i32_plain(dfsel["ed"], L, "dfsel$ed")
     for f in _abi.SOILC_FIELDS:
         shape = (R, Cc, 8) if f == "wsa" else (R, Cc, 24) if f == "hor" else (R, Cc)
         if f in soilc_optional and soilc.get(f) is None:
             setattr(gi.soilc, f, None)
             continue
-        setattr(gi.soilc, f, m._f64(soilc[f], shape, f"soilc${f}"))
+        setattr(gi.soilc, f, m.f64(soilc[f], shape, f"soilc${f}"))
     if array_forcing:
-        gi.lats = m._f64(lat, (R, Cc), "lats")
-        gi.lons = m._f64(lon, (R, Cc), "lons")
+        gi.lats = m.f64(lat, (R, Cc), "lats")
+        gi.lons = m.f64(lon, (R, Cc), "lons")
         gi.lat = gi.lon = float("nan")
     else:
         gi.lat, gi.lon = float(lat), float(lon)
@@ -167,21 +213,74 @@ def marshal(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping,
 
 
 def alloc_outputs(m: Marshalled):
-    """Host output arrays [rows, cols, tsteps] (column-major) for requested vars."""
+    """Host output arrays [rows, cols, tsteps] (column-major) for requested vars; the struct holds the owner of its pointers."""
     outs = _abi.Outputs()
+    outs._owner = b = Buffers()
     arrays = {}
+    shape = (m.rows, m.cols, m.tsteps)
     for v, name in enumerate(_abi.OUT_NAMES):
-        if m.options.out[v]:
-            if os.environ.get("MCF_TEST_PLAIN_OUTPUTS"):
-                # (measurement aid, tools/oneshot_rate.py: an anonymous mapping without numpy's own huge-page advice —
-                # what an R vector's malloc gives the library to write into)
-                import mmap
-                buf = mmap.mmap(-1, m.rows * m.cols * m.tsteps * 8, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
-                a = np.frombuffer(buf, dtype=np.float64).reshape((m.rows, m.cols, m.tsteps), order="F")
-            else:
-                a = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            arrays[name] = a
-            outs.var[v] = a.ctypes.data_as(_abi.c_double_p)
-        else:
+        if not m.options.out[v]:
             outs.var[v] = None
+        elif os.environ.get("MCF_TEST_PLAIN_OUTPUTS"):
+            # (measurement aid, tools/oneshot_rate.py: an anonymous mapping without numpy's own huge-page advice —
+            # what an R vector's malloc gives the library to write into)
+            import mmap
+            buf = mmap.mmap(-1, m.rows * m.cols * m.tsteps * 8, flags=mmap.MAP_PRIVATE | mmap.MAP_ANONYMOUS)
+            arrays[name] = np.frombuffer(buf, dtype=np.float64).reshape(shape, order="F")
+            outs.var[v] = b.ptr(arrays[name])
+        else:
+            arrays[name], outs.var[v] = b.out(shape)
     return outs, arrays
+
+
+def build_summary_spec(struct, names, field: str, what: str, periods, vars, stats, thresholds=None, nperiods: int | None = None):
+    """A summary spec of include/mcf.h (`struct`: mcf_summary_spec or mcf_snowpack_summary_spec, whose selection member is
+    `field`) over the series `names`: `periods` one integer per day (-1 = not counted), `vars` names or indices, `stats` names of
+    _abi.STAT_NAMES or indices, `thresholds` for hours_above — one number for every selected series or {series: number}.
+    -> (spec, the selected series' indices, the selected statistics' indices, the period table); the spec holds the table."""
+    pod = np.ascontiguousarray(np.asarray(periods).astype(np.int32)).ravel()
+    vi = sorted({names.index(v) if isinstance(v, str) else int(v) for v in ((vars,) if isinstance(vars, str) else vars)})
+    si = sorted({_abi.STAT_NAMES.index(s) if isinstance(s, str) else int(s) for s in ((stats,) if isinstance(stats, str) else stats)})
+    if any(v < 0 or v >= len(names) for v in vi) or any(s < 0 or s >= _abi.NSTAT for s in si):
+        raise ValueError(f"{what} of {names}, statistics of {_abi.STAT_NAMES}")
+    sp = struct()
+    sp.nperiods = int(nperiods) if nperiods is not None else int(pod.max()) + 1 if pod.size and pod.max() >= 0 else 1
+    sp._owner = b = Buffers()
+    sp.period_of_day = b.ptr(pod)
+    for v in vi:
+        getattr(sp, field)[v] = 1
+        if isinstance(thresholds, Mapping):
+            t = thresholds.get(names[v], thresholds.get(v, float("nan")))
+        else:
+            t = float("nan") if thresholds is None else thresholds
+        sp.threshold[v] = float(t)
+    for s in si:
+        sp.stat[s] = 1
+    return sp, vi, si, pod
+
+
+def summary_sink(b: Buffers, rows: int, cols: int, spec, names, so=None, plane=None, days=None) -> dict:
+    """The host side of a summary's sink for `spec` (as build_summary_spec returns it) over the series `names`: one
+    [rows, cols, nperiods] plane per selected (series, statistic) and the counted days per period, held by `b`.  Their pointers
+    go into `so` (a struct with `val[series][statistic]` and `days`, filled by the call that follows) or, plane by plane, to
+    `plane(series, statistic, pointer)` and `days(pointer)` (fetches that fill them now; `days` None: no day counts here).
+    -> {series: {statistic: plane}, "days": counted days per period (where they are asked for)}"""
+    sp, vi, si, _pod = spec
+    npd = max(int(sp.nperiods), 0)
+    res = {}
+    for v in vi:
+        res[names[v]] = {}
+        for k in si:
+            res[names[v]][_abi.STAT_NAMES[k]], p = b.out((rows, cols, npd))
+            if so is not None:
+                so.val[v][k] = p
+            else:
+                plane(v, k, p)
+    if so is not None or days is not None:
+        d, p = b.out(max(npd, 1), np.int32, zero=True)
+        if so is not None:
+            so.days = p
+        else:
+            days(p)
+        res["days"] = d[:npd]
+    return res

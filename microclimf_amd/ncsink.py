@@ -15,6 +15,7 @@ from typing import Mapping, Sequence
 import numpy as np
 
 from . import _abi
+from .marshal import Buffers
 
 # writetonc's default `vars` per height (dataprep.R:1108, 1179, 1232)
 DEFAULT_VARS_ABOVE = ("Tz", "tleaf", "relhum", "windspeed", "Rdirdown", "Rdifdown", "Rlwdown", "Rswup", "Rlwup")
@@ -60,9 +61,8 @@ class NcWriter:
             raise ValueError("east / north must have one entry per raster column / row")
         sp = _abi.NcSpec()
         sp.rows, sp.cols, sp.nsteps = rows, cols, len(self._t)
-        sp.east = self._e.ctypes.data_as(_abi.c_double_p)
-        sp.north = self._n.ctypes.data_as(_abi.c_double_p)
-        sp.time_hours = self._t.ctypes.data_as(_abi.c_double_p)
+        b = Buffers()
+        sp.east, sp.north, sp.time_hours = b.ptr(self._e), b.ptr(self._n), b.ptr(self._t)
         self._wkt = crs_wkt.encode()
         sp.crs_wkt = self._wkt
         sp.reqhgt = float(reqhgt)
@@ -80,7 +80,7 @@ class NcWriter:
     def write_host(self, step0: int, arrays: Mapping[str, np.ndarray]):
         """arrays[name]: [rows, cols, n] as runmicro*Cpp return them"""
         ptrs = (_abi.c_double_p * 10)()
-        keep, n = [], None
+        b, n = Buffers(), None
         for name in self.vars:
             if name not in arrays:
                 continue
@@ -88,8 +88,7 @@ class NcWriter:
             if a.shape[:2] != (self.rows, self.cols) or (n is not None and a.shape[2] != n):
                 raise ValueError(f"{name}: expected [rows, cols, n]")
             n = a.shape[2]
-            keep.append(a)
-            ptrs[_abi.OUT_NAMES.index(name)] = a.ctypes.data_as(_abi.c_double_p)
+            ptrs[_abi.OUT_NAMES.index(name)] = b.ptr(a)
         if n is None:
             raise ValueError("no variable of the file given")
         _abi.check(self._lib.mcf_nc_write_host(self._h, int(step0), int(n), C.byref(ptrs)))

@@ -15,6 +15,7 @@ from typing import Mapping
 import numpy as np
 
 from . import _abi
+from .marshal import Buffers
 
 
 def _vec(a, n=None, name="?"):
@@ -24,30 +25,42 @@ def _vec(a, n=None, name="?"):
     return v
 
 
-def _weather(climdata: Mapping, n: int, need_precip: bool):
+def _mat(a, shape, name):
+    v = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+    if v.shape != shape:
+        raise ValueError(f"{name}: expected shape {shape}, got {v.shape}")
+    return v
+
+
+def _outputs(b: Buffers, out, fields, shape) -> dict:
+    """{field: zeros of `shape` (a batch's [P, n]: one point's series after the other, C order)}, its pointer in that member of
+    the struct `out`"""
+    res = {}
+    for f in fields:
+        res[f] = np.zeros(shape(f) if callable(shape) else shape)
+        setattr(out, f, b.ptr(res[f]))
+    return res
+
+
+def _weather(b: Buffers, climdata: Mapping, shape: tuple, need_precip: bool):
+    """mcf_point_weather over series of `shape` ((n,): one point; (P, n): a batch), held by `b`; `precip` null unless it is
+    needed or, for one point, given"""
     w = _abi.PointWeather()
-    keep = []
     for f in _abi.POINT_WEATHER_FIELDS:
-        if f == "precip" and not need_precip and "precip" not in climdata:
+        if f == "precip" and not need_precip and (len(shape) == 2 or "precip" not in climdata):
             setattr(w, f, None)
             continue
-        v = _vec(climdata[f], n, f"climdata${f}")
-        keep.append(v)
-        setattr(w, f, v.ctypes.data_as(_abi.c_double_p))
-    return w, keep
+        v = _vec(climdata[f], shape[0], f"climdata${f}") if len(shape) == 1 else _mat(climdata[f], shape, f"climdata${f}")
+        setattr(w, f, b.ptr(v))
+    return w
 
 
-def _obstime(obstime: Mapping, n: int):
+def _obstime(b: Buffers, obstime: Mapping, n: int):
     t = _abi.Obstime()
-    keep = []
     for f in ("year", "month", "day"):
-        v = np.ascontiguousarray(np.asarray(obstime[f]).astype(np.int32))
-        keep.append(v)
-        setattr(t, f, v.ctypes.data_as(_abi.c_int32_p))
-    h = _vec(obstime["hour"], n, "obstime$hour")
-    keep.append(h)
-    t.hour = h.ctypes.data_as(_abi.c_double_p)
-    return t, keep
+        setattr(t, f, b.i32_plain(obstime[f]))
+    t.hour = b.ptr(_vec(obstime["hour"], n, "obstime$hour"))
+    return t
 
 
 def BigLeafCpp(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, zref=2.0, maxiter=100, bwgt=0.5,
@@ -56,18 +69,14 @@ def BigLeafCpp(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, zre
     reference, unused."""
     lib = _abi.load()
     n = len(np.asarray(climdata["temp"]))
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather(climdata, n, False)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (n,), False)
     vp, gp, sm = _vec(vegp), _vec(groundp), _vec(soilm, n, "soilm")
     if vp.size < 9 or gp.size < 12:
         raise ValueError("vegp needs >= 9 and groundp 12 entries")
     out = _abi.BigLeafOut()
-    res = {}
-    for f in _abi.BIGLEAF_FIELDS:
-        res[f] = np.zeros(n)
-        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
-    _abi.check(lib.mcf_bigleaf(n, C.byref(t), C.byref(w), vp.ctypes.data_as(_abi.c_double_p),
-                               gp.ctypes.data_as(_abi.c_double_p), sm.ctypes.data_as(_abi.c_double_p), float(lat),
+    res = _outputs(b, out, _abi.BIGLEAF_FIELDS, n)
+    _abi.check(lib.mcf_bigleaf(n, C.byref(t), C.byref(w), b.ptr(vp), b.ptr(gp), b.ptr(sm), float(lat),
                                float(lon), float(dTmx), float(zref), int(maxiter), float(bwgt), float(tol),
                                1 if yearG else 0, C.byref(out)))
     res["err"] = out.err
@@ -79,11 +88,12 @@ def soilmCpp(climdata, rmu, mult, pwr, Smax, Smin, Ksat, a) -> np.ndarray:
     """Drop-in for soilmCpp (src/microclimfCpp.cpp:931-972): daily soil moisture of the two-layer bucket model."""
     lib = _abi.load()
     n = len(np.asarray(climdata["temp"]))
-    w, keep = _weather({**{f: np.zeros(n) for f in ("relhum", "pres", "difrad", "windspeed")}, **climdata}, n, True)
-    out = np.zeros(max(n // 24, 1))
+    b = Buffers()
+    w = _weather(b, {**{f: np.zeros(n) for f in ("relhum", "pres", "difrad", "windspeed")}, **climdata}, (n,), True)
+    out, optr = b.out(max(n // 24, 1), zero=True)
     nd = C.c_int64()
     _abi.check(lib.mcf_soilm(n, C.byref(w), float(rmu), float(mult), float(pwr), float(Smax), float(Smin), float(Ksat),
-                             float(a), out.ctypes.data_as(_abi.c_double_p), C.byref(nd)))
+                             float(a), optr, C.byref(nd)))
     return out[:nd.value]
 
 
@@ -92,12 +102,11 @@ def pointmprocess(pointvars, zref, h, pai, rho, Vm, Vq, Mc) -> dict:
     soilm, RabsG."""
     lib = _abi.load()
     n = len(np.asarray(pointvars["tc"]))
-    ins = [_vec(pointvars[k], n, k) for k in ("windspeed", "tc", "rh", "pk", "uf", "soilm", "RabsG")]
+    b = Buffers()
+    ins = [b.ptr(_vec(pointvars[k], n, k)) for k in ("windspeed", "tc", "rh", "pk", "uf", "soilm", "RabsG")]
     res = {k: np.zeros(n) for k in ("umu", "kp", "muGp", "DDp", "T0p", "dtrp")}
-    _abi.check(lib.mcf_pointmprocess(n, *[v.ctypes.data_as(_abi.c_double_p) for v in ins], float(zref), float(h),
-                                     float(pai), float(rho), float(Vm), float(Vq), float(Mc),
-                                     *[res[k].ctypes.data_as(_abi.c_double_p) for k in ("umu", "kp", "muGp", "DDp", "T0p",
-                                                                                        "dtrp")]))
+    _abi.check(lib.mcf_pointmprocess(n, *ins, float(zref), float(h), float(pai), float(rho), float(Vm), float(Vq), float(Mc),
+                                     *[b.ptr(v) for v in res.values()]))
     return res
 
 
@@ -106,37 +115,17 @@ def weatherhgtCpp(obstime, climdata, zin, uzin, zout, lat, lon) -> dict:
     windspeed moved from zin / uzin to zout."""
     lib = _abi.load()
     n = len(np.asarray(climdata["temp"]))
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather(climdata, n, False)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (n,), False)
     res = {k: np.zeros(n) for k in ("temp", "relhum", "windspeed")}
     _abi.check(lib.mcf_weatherhgt(n, C.byref(t), C.byref(w), float(zin), float(uzin), float(zout), float(lat), float(lon),
-                                  *[res[k].ctypes.data_as(_abi.c_double_p) for k in ("temp", "relhum", "windspeed")]))
+                                  *[b.ptr(v) for v in res.values()]))
     out = {k: np.array(v, dtype=np.float64, copy=True) for k, v in climdata.items()}
     out.update(res)
     return out
 
 
 # ---- many points at once, on the device (include/mcf.h: the `_batch` entries) ---------------------------------------------
-def _mat(a, shape, name):
-    v = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
-    if v.shape != shape:
-        raise ValueError(f"{name}: expected shape {shape}, got {v.shape}")
-    return v
-
-
-def _weather_batch(climdata: Mapping, P: int, n: int, need_precip: bool = False):
-    w = _abi.PointWeather()
-    keep = []
-    for f in _abi.POINT_WEATHER_FIELDS:
-        if f == "precip" and not need_precip:
-            setattr(w, f, None)
-            continue
-        v = _mat(climdata[f], (P, n), f"climdata${f}")
-        keep.append(v)
-        setattr(w, f, v.ctypes.data_as(_abi.c_double_p))
-    return w, keep
-
-
 def BigLeafBatch(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, zref=2.0, maxiter=100, bwgt=0.5, tol=0.5,
                  yearG=True, *, device: int = 0, points_per_block: int = 0) -> dict:
     """BigLeafCpp for P points on device `device` (mcf_bigleaf_batch).  `climdata[k]` and `soilm`: [P, n]; `obstime`:
@@ -147,8 +136,8 @@ def BigLeafBatch(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, z
     if sm.ndim != 2:
         raise ValueError("soilm: expected [P, n]")
     P, n = sm.shape
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather_batch(climdata, P, n)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (P, n), False)
     vp = np.asarray(vegp, dtype=np.float64)
     gp = np.asarray(groundp, dtype=np.float64)
     if vp.ndim != 2 or gp.ndim != 2 or vp.shape[0] != P or gp.shape[0] != P or vp.shape[1] < 9 or gp.shape[1] < 12:
@@ -158,15 +147,10 @@ def BigLeafBatch(obstime, climdata, vegp, groundp, soilm, lat, lon, dTmx=25.0, z
     gp12 = np.ascontiguousarray(gp[:, :12])
     la, lo = _vec(lat, P, "lat"), _vec(lon, P, "lon")
     out = _abi.BigLeafBatchOut()
-    res = {}
-    for f in _abi.BIGLEAF_FIELDS:
-        res[f] = np.zeros((P, n))
-        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
-    res["err"] = np.zeros(P)
-    res["iters"] = np.zeros(P, dtype=np.int32)
-    out.err = res["err"].ctypes.data_as(_abi.c_double_p)
-    out.iters = res["iters"].ctypes.data_as(_abi.c_int32_p)
-    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    res = _outputs(b, out, _abi.BIGLEAF_FIELDS, (P, n))
+    res["err"], out.err = b.out(P, zero=True)
+    res["iters"], out.iters = b.out(P, np.int32, zero=True)
+    d = b.ptr
     _abi.check(lib.mcf_bigleaf_batch(P, n, C.byref(t), C.byref(w), d(vp10), d(gp12), d(sm), d(la), d(lo), float(dTmx),
                                      float(zref), int(maxiter), float(bwgt), float(tol), 1 if yearG else 0,
                                      int(points_per_block), int(device), C.byref(out)))
@@ -181,11 +165,11 @@ def weatherhgt_batch(obstime, climdata, zin, uzin, zout, lat, lon, *, device: in
     if tc.ndim != 2:
         raise ValueError("climdata$temp: expected [P, n]")
     P, n = tc.shape
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather_batch(climdata, P, n)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (P, n), False)
     la, lo = _vec(lat, P, "lat"), _vec(lon, P, "lon")
     res = {k: np.zeros((P, n)) for k in ("temp", "relhum", "windspeed")}
-    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    d = b.ptr
     _abi.check(lib.mcf_weatherhgt_batch(P, n, C.byref(t), C.byref(w), float(zin), float(uzin), float(zout), d(la), d(lo),
                                         int(points_per_block), int(device), *[d(res[k]) for k in ("temp", "relhum", "windspeed")]))
     out = {k: np.array(v, dtype=np.float64, copy=True) for k, v in climdata.items()}
@@ -205,7 +189,7 @@ def pointmprocess_batch(pointvars, zref, h, pai, rho, Vm, Vq, Mc, *, device: int
     par = [_vec(v, P, k) for k, v in (("h", h), ("pai", pai), ("rho", rho), ("Vm", Vm), ("Vq", Vq), ("Mc", Mc))]
     keys = ("umu", "kp", "muGp", "DDp", "T0p", "dtrp")
     res = {k: np.zeros((P, n)) for k in keys}
-    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
+    d = Buffers().ptr
     _abi.check(lib.mcf_pointmprocess_batch(P, n, *[d(v) for v in ins], float(zref), *[d(v) for v in par], int(device),
                                            *[d(res[k]) for k in keys]))
     return res
@@ -216,19 +200,15 @@ def pointmodelsnow(obstime, climdata, vegp, other, snowenv, tol: float = 0.5, ma
     aspect, lat, lon, zref, initial snow depth, initial snow age), snowenv a name as in the reference."""
     lib = _abi.load()
     n = len(np.asarray(climdata["temp"]))
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather(climdata, n, True)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (n,), True)
     vp, ot = _vec(vegp), _vec(other)
     if vp.size < 4 or ot.size < 7:
         raise ValueError("vegp needs 4 and other 7 entries")
     out = _abi.PointSnowOut()
-    res = {}
-    for f in _abi.POINTSNOW_FIELDS:
-        res[f] = np.zeros(n + 1 if f in ("sdepc", "sdepg") else n)
-        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
+    res = _outputs(b, out, _abi.POINTSNOW_FIELDS, lambda f: n + 1 if f in ("sdepc", "sdepg") else n)
     env = lib.mcf_snowenv_from_name(str(snowenv).encode())
-    _abi.check(lib.mcf_pointmodelsnow(n, C.byref(t), C.byref(w), vp.ctypes.data_as(_abi.c_double_p),
-                                      ot.ctypes.data_as(_abi.c_double_p), env, float(tol), float(maxiter), C.byref(out)))
+    _abi.check(lib.mcf_pointmodelsnow(n, C.byref(t), C.byref(w), b.ptr(vp), b.ptr(ot), env, float(tol), float(maxiter), C.byref(out)))
     res["mxdif"] = out.mxdif
     res["iters"] = out.iters
     return res
@@ -245,8 +225,8 @@ def pointmodelsnow_batch(obstime, climdata, vegp, other, snowenv, tol: float = 0
     if tc.ndim != 2:
         raise ValueError("climdata$temp: expected [P, n]")
     P, n = tc.shape
-    t, k1 = _obstime(obstime, n)
-    w, k2 = _weather_batch(climdata, P, n, need_precip=True)
+    b = Buffers()
+    t, w = _obstime(b, obstime, n), _weather(b, climdata, (P, n), True)
     vp = np.ascontiguousarray(np.asarray(vegp, dtype=np.float64))
     ot = np.ascontiguousarray(np.asarray(other, dtype=np.float64))
     if vp.shape != (P, 4) or ot.shape != (P, 7):
@@ -256,16 +236,11 @@ def pointmodelsnow_batch(obstime, climdata, vegp, other, snowenv, tol: float = 0
         raise ValueError("snowenv: one name or P names")
     env = np.array([lib.mcf_snowenv_from_name(str(s).encode()) for s in names], dtype=np.int32)
     out = _abi.PointSnowBatchOut()
-    res = {}
-    for f in _abi.POINTSNOW_FIELDS:
-        res[f] = np.zeros((P, n + 1 if f in ("sdepc", "sdepg") else n))
-        setattr(out, f, res[f].ctypes.data_as(_abi.c_double_p))
-    res["mxdif"] = np.zeros(P)
-    res["iters"] = np.zeros(P, dtype=np.int32)
-    out.mxdif = res["mxdif"].ctypes.data_as(_abi.c_double_p)
-    out.iters = res["iters"].ctypes.data_as(_abi.c_int32_p)
-    d = lambda a: a.ctypes.data_as(_abi.c_double_p)                                     # noqa: E731
-    _abi.check(lib.mcf_pointmodelsnow_batch(P, n, C.byref(t), C.byref(w), d(vp), d(ot), env.ctypes.data_as(_abi.c_int32_p),
+    res = _outputs(b, out, _abi.POINTSNOW_FIELDS, lambda f: (P, n + 1 if f in ("sdepc", "sdepg") else n))
+    res["mxdif"], out.mxdif = b.out(P, zero=True)
+    res["iters"], out.iters = b.out(P, np.int32, zero=True)
+    d = b.ptr
+    _abi.check(lib.mcf_pointmodelsnow_batch(P, n, C.byref(t), C.byref(w), d(vp), d(ot), d(env),
                                             float(tol), float(maxiter), int(points_per_block), int(device), C.byref(out)))
     return res
 
@@ -273,9 +248,9 @@ def pointmodelsnow_batch(obstime, climdata, vegp, other, snowenv, tol: float = 0
 def manCpp(x, n: int) -> np.ndarray:
     """Drop-in for manCpp (src/microclimfCpp.cpp:597-627)."""
     lib = _abi.load()
-    v = _vec(x)
-    out = np.zeros(len(v))
-    _abi.check(lib.mcf_man(len(v), v.ctypes.data_as(_abi.c_double_p), int(n), out.ctypes.data_as(_abi.c_double_p)))
+    b, v = Buffers(), _vec(x)
+    out, optr = b.out(len(v), zero=True)
+    _abi.check(lib.mcf_man(len(v), b.ptr(v), int(n), optr))
     return out
 
 

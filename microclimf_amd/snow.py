@@ -14,40 +14,7 @@ from typing import Mapping, Sequence
 import numpy as np
 
 from . import _abi
-
-
-class SnowMarshalled:
-    def __init__(self):
-        self.inputs = _abi.SnowInputs()
-        self._keep = []
-        self.rows = self.cols = self.tsteps = 0
-
-    def f64(self, a, shape, name):
-        arr = np.asarray(a, dtype=np.float64)
-        if tuple(arr.shape) != tuple(shape):
-            if arr.size != int(np.prod(shape)):
-                raise ValueError(f"{name}: expected shape {tuple(shape)}, got {arr.shape}")
-            arr = arr.reshape(shape, order="F")
-        arr = np.asfortranarray(arr)
-        self._keep.append(arr)
-        return arr.ctypes.data_as(_abi.c_double_p)
-
-    def i32(self, a, shape, name):
-        # Rcpp's as<IntegerVector/IntegerMatrix>() truncates doubles towards zero
-        # (NA cells: NA_integer_, as Rcpp's conversion gives)
-        v = np.trunc(np.asarray(a, dtype=np.float64))
-        arr = np.asfortranarray(np.where(np.isnan(v), float(np.iinfo(np.int32).min), v).astype(np.int32))
-        if tuple(arr.shape) != tuple(shape):
-            raise ValueError(f"{name}: expected shape {tuple(shape)}, got {arr.shape}")
-        self._keep.append(arr)
-        return arr.ctypes.data_as(_abi.c_int32_p)
-
-
-def _get(d: Mapping, *names):
-    for n in names:
-        if n in d:
-            return d[n]
-    raise KeyError(f"none of {names} present (have {sorted(d)})")
+from .marshal import Buffers, SnowMarshalled, _get, alloc_outputs, build_summary_spec, marshal, summary_sink
 
 
 def marshal_snow(obstime: Mapping, climdata: Mapping, vegp: Mapping, other: Mapping, array_forcing: bool,
@@ -111,18 +78,22 @@ def marshal_snow(obstime: Mapping, climdata: Mapping, vegp: Mapping, other: Mapp
     return m
 
 
+def _out_arrays(out, shapes: Mapping) -> dict:
+    """{member: shape} -> {member: a new column-major array}, its pointer in that member of the struct `out`, which holds the
+    owner of the pointers it is given here"""
+    out._owner = b = Buffers()
+    arrays = {}
+    for f, shape in shapes.items():
+        arrays[f], ptr = b.out(shape)
+        setattr(out, f, ptr)
+    return arrays
+
+
 def alloc_snowmodel_out(m: SnowMarshalled):
     out = _abi.SnowModelOut()
-    arrays = {}
-    for f in _abi.SNOWMODEL_OUT3:
-        a = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-        arrays[f] = a
-        setattr(out, f, a.ctypes.data_as(_abi.c_double_p))
-    for f in _abi.SNOWMODEL_OUT2:
-        a = np.empty((m.rows, m.cols), dtype=np.float64, order="F")
-        arrays[f] = a
-        setattr(out, f, a.ctypes.data_as(_abi.c_double_p))
-    return out, arrays
+    arrays = {f: (m.rows, m.cols, m.tsteps) for f in _abi.SNOWMODEL_OUT3}
+    arrays.update({f: (m.rows, m.cols) for f in _abi.SNOWMODEL_OUT2})
+    return out, _out_arrays(out, arrays)
 
 
 def marshal_snowm(m: SnowMarshalled, snowm: Mapping):
@@ -141,15 +112,13 @@ def marshal_micro(m: SnowMarshalled, micro: Mapping, out: Sequence):
         raise ValueError("out must have 10 entries")
     sel = (C.c_int32 * _abi.NOUT)(*[1 if v else 0 for v in out])
     outs = _abi.Outputs()
+    outs._owner = b = Buffers()
     arrays = {}
     shape = (m.rows, m.cols, m.tsteps)
     for v, name in enumerate(_abi.OUT_NAMES):
         if out[v]:
-            a = np.array(np.asarray(micro[name], dtype=np.float64).reshape(shape, order="F"), order="F", copy=True)
-            arrays[name] = a
-            outs.var[v] = a.ctypes.data_as(_abi.c_double_p)
-        else:
-            outs.var[v] = None
+            arrays[name] = np.array(np.asarray(micro[name], dtype=np.float64).reshape(shape, order="F"), order="F", copy=True)
+        outs.var[v] = b.ptr(arrays.get(name))
     return sel, outs, arrays
 
 
@@ -206,11 +175,21 @@ def _terrain_placeholders(other, R, Cc) -> dict:
 
 def _driver_out(R, Cc, T):
     """-> (mcf_snowdriver_out, {name: the F-ordered [R, Cc, T] array it points to}) for the snow model's five series"""
-    out, arrays = _abi.SnowDriverOut(), {}
-    for f in _abi.SNOWDRIVER_OUT:
-        arrays[f] = np.empty((R, Cc, T), dtype=np.float64, order="F")
-        setattr(out, f, arrays[f].ctypes.data_as(_abi.c_double_p))
-    return out, arrays
+    out = _abi.SnowDriverOut()
+    return out, _out_arrays(out, {f: (R, Cc, T) for f in _abi.SNOWDRIVER_OUT})
+
+
+def _driver_in(m: SnowMarshalled, dtm, res, tfact, chunk_steps: int = 0, af_wind=None, wsa_s: int = 0):
+    """include/mcf.h mcf_snowdriver_in around the marshalled mcf_snow_inputs (copied as it is now); `af_wind`: the chunk wind
+    series of array weather, with the wind-shelter factor `wsa_s`"""
+    din = _abi.SnowDriverIn()
+    din.base = m.inputs
+    din.dtm = m.f64(dtm, (m.rows, m.cols), "dtm")
+    din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
+    if af_wind is not None:
+        din.af_wsa_s = int(wsa_s)
+        din.af_wind = m.f64(af_wind, (m.tsteps,), "af_wind")
+    return din
 
 
 def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *,
@@ -226,10 +205,7 @@ def snowmodel1_chunks(obstime, climdata, pointm, vegp, other, snowenv, dtm, res,
     lib = _abi.load()
     R, Cc = np.shape(vegp["pai"])
     m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
-    din = _abi.SnowDriverIn()
-    din.base = m.inputs
-    din.dtm = m.f64(dtm, (R, Cc), "dtm")
-    din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
+    din = _driver_in(m, dtm, res, tfact, chunk_steps)
     out, arrays = _driver_out(R, Cc, m.tsteps)
     mu = _abi.multi(devices, n_blocks)
     if mu:
@@ -243,26 +219,9 @@ def snowpack_summary_spec(periods, vars=("totalSWE",), stats=("mean", "min", "ma
     """include/mcf.h mcf_snowpack_summary_spec from `periods` (one integer per day, -1 = not counted; a day past the last whole
     chunk must be -1), series names of _abi.SNOWDRIVER_OUT or indices, statistics of _abi.STAT_NAMES or indices, and
     `thresholds` for hours_above: one number for every selected series or {series: number} (totalSWE with 0: the snow-cover
-    duration).  -> (spec, the selected series' indices, the selected statistics' indices, the array its table points into)"""
-    pod = np.ascontiguousarray(np.asarray(periods).astype(np.int32)).ravel()
-    names = _abi.SNOWDRIVER_OUT
-    vi = sorted({names.index(v) if isinstance(v, str) else int(v) for v in ((vars,) if isinstance(vars, str) else vars)})
-    si = sorted({_abi.STAT_NAMES.index(k) if isinstance(k, str) else int(k) for k in ((stats,) if isinstance(stats, str) else stats)})
-    if any(v < 0 or v >= 5 for v in vi) or any(k < 0 or k >= _abi.NSTAT for k in si):
-        raise ValueError(f"snowpack summary: series of {names}, statistics of {_abi.STAT_NAMES}")
-    sp = _abi.SnowpackSummarySpec()
-    sp.nperiods = int(nperiods) if nperiods is not None else int(pod.max()) + 1 if pod.size and pod.max() >= 0 else 1
-    sp.period_of_day = pod.ctypes.data_as(_abi.c_int32_p)
-    for v in vi:
-        sp.series[v] = 1
-        if isinstance(thresholds, Mapping):
-            t = thresholds.get(names[v], thresholds.get(v, float("nan")))
-        else:
-            t = float("nan") if thresholds is None else thresholds
-        sp.threshold[v] = float(t)
-    for k in si:
-        sp.stat[k] = 1
-    return sp, vi, si, pod
+    duration).  -> (spec, the selected series' indices, the selected statistics' indices, the period table the spec holds)"""
+    return build_summary_spec(_abi.SnowpackSummarySpec, _abi.SNOWDRIVER_OUT, "series", "snowpack summary: series", periods, vars, stats,
+                              thresholds, nperiods)
 
 
 def _micro_summary_spec(summary: Mapping):
@@ -279,16 +238,6 @@ def _pack_summary_spec(summary: Mapping):
                                  summary.get("thresholds"), summary.get("nperiods"))
 
 
-def _planes(R, Cc, sp, vi, si):
-    return {(v, k): np.empty((R, Cc, max(int(sp.nperiods), 0)), dtype=np.float64, order="F") for v in vi for k in si}
-
-
-def _summary_dict(names, vi, si, planes, days):
-    res = {names[v]: {_abi.STAT_NAMES[k]: planes[v, k] for k in si} for v in vi}
-    res["days"] = days
-    return res
-
-
 def snowmodel1_summary(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *, periods, vars=("totalSWE",),
                        stats=("mean", "min", "max"), thresholds=None, nperiods: int | None = None, chunk_steps: int = 120,
                        devices=None, n_blocks: int = 0) -> dict:
@@ -299,33 +248,20 @@ def snowmodel1_summary(obstime, climdata, pointm, vegp, other, snowenv, dtm, res
     lib = _abi.load()
     R, Cc = np.shape(vegp["pai"])
     m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
-    din = _abi.SnowDriverIn()
-    din.base = m.inputs
-    din.dtm = m.f64(dtm, (R, Cc), "dtm")
-    din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
-    sp, vi, si, _pod = snowpack_summary_spec(periods, vars, stats, thresholds, nperiods)
-    planes = _planes(R, Cc, sp, vi, si)
+    din = _driver_in(m, dtm, res, tfact, chunk_steps)
+    spec = snowpack_summary_spec(periods, vars, stats, thresholds, nperiods)
     so = _abi.SnowpackSummaryOut()
-    for (v, k), a in planes.items():
-        so.val[v][k] = a.ctypes.data_as(_abi.c_double_p)
-    days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
-    so.days = days.ctypes.data_as(_abi.c_int32_p)
+    planes = summary_sink(m, R, Cc, spec, _abi.SNOWDRIVER_OUT, so)
     mu = _abi.multi(devices, n_blocks)
-    _abi.check(lib.mcf_snowmodel1_summary(C.byref(din), C.byref(sp), C.byref(mu[0]) if mu else None, C.byref(so)))
-    return _summary_dict(_abi.SNOWDRIVER_OUT, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+    _abi.check(lib.mcf_snowmodel1_summary(C.byref(din), C.byref(spec[0]), C.byref(mu[0]) if mu else None, C.byref(so)))
+    return planes
 
 
 def _driver_in_array(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact, af_wind, wsa_s, chunk_steps):
     """mcf_snowdriver_in for array weather at the raster's resolution (include/mcf.h mcf_snowmodel2)"""
     R, Cc = np.shape(vegp["pai"])
     m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), True, pointm=pointm, snowenv=snowenv)
-    din = _abi.SnowDriverIn()
-    din.base = m.inputs
-    din.dtm = m.f64(dtm, (R, Cc), "dtm")
-    din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
-    din.af_wsa_s = int(wsa_s)
-    din.af_wind = m.f64(af_wind, (m.tsteps,), "af_wind")
-    return m, din
+    return m, _driver_in(m, dtm, res, tfact, chunk_steps, af_wind, wsa_s)
 
 
 def snowmodel2_device(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *, af_wind, wsa_s: int = 0,
@@ -350,9 +286,9 @@ def canintfrac(hgt, pai, uf: float, prec: float, tc: float, Li: float = 0.0, *, 
     p = np.asfortranarray(np.asarray(pai, dtype=np.float64))
     if h.shape != p.shape:
         raise ValueError("hgt and pai differ in shape")
-    out = np.empty(h.shape, dtype=np.float64, order="F")
-    args = (C.c_int64(h.size), h.ctypes.data_as(_abi.c_double_p), p.ctypes.data_as(_abi.c_double_p), C.c_double(uf), C.c_double(prec),
-            C.c_double(tc), C.c_double(Li), out.ctypes.data_as(_abi.c_double_p))
+    b = Buffers()
+    out, optr = b.out(h.shape)
+    args = (C.c_int64(h.size), b.ptr(h), b.ptr(p), C.c_double(uf), C.c_double(prec), C.c_double(tc), C.c_double(Li), optr)
     _abi.check(lib.mcf_canintfrac(*args) if device is None else lib.mcf_canintfrac_device(*args, C.c_int32(device)))
     return out
 
@@ -366,9 +302,9 @@ def meltmu(skyview, stemp, tc, *, device: int | None = None) -> np.ndarray:
     ta = np.ascontiguousarray(tc, dtype=np.float64)
     if st.shape != ta.shape or st.ndim != 1:
         raise ValueError("stemp and tc must be vectors of one length")
-    out = np.empty(sv.shape, dtype=np.float64, order="F")
-    args = (C.c_int64(sv.size), sv.ctypes.data_as(_abi.c_double_p), C.c_int64(st.size), st.ctypes.data_as(_abi.c_double_p),
-            ta.ctypes.data_as(_abi.c_double_p), out.ctypes.data_as(_abi.c_double_p))
+    b = Buffers()
+    out, optr = b.out(sv.shape)
+    args = (C.c_int64(sv.size), b.ptr(sv), C.c_int64(st.size), b.ptr(st), b.ptr(ta), optr)
     _abi.check(lib.mcf_meltmu(*args) if device is None else lib.mcf_meltmu_device(*args, C.c_int32(device)))
     return out
 
@@ -377,9 +313,10 @@ def tpicalc(af: int, dtm, tfact: float, *, device: int = 0) -> np.ndarray:
     """`.tpicalc(af, min(dim), dtm, tfact)` (R/internal.R:2483-2496) on the device"""
     lib = _abi.load()
     z = np.asfortranarray(np.asarray(dtm, dtype=np.float64))
-    out = np.empty(z.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_tpicalc(C.c_int64(z.shape[0]), C.c_int64(z.shape[1]), z.ctypes.data_as(_abi.c_double_p), C.c_int32(int(af)),
-                               C.c_double(tfact), out.ctypes.data_as(_abi.c_double_p), C.c_int32(device)))
+    b = Buffers()
+    out, optr = b.out(z.shape)
+    _abi.check(lib.mcf_tpicalc(C.c_int64(z.shape[0]), C.c_int64(z.shape[1]), b.ptr(z), C.c_int32(int(af)), C.c_double(tfact), optr,
+                               C.c_int32(device)))
     return out
 
 
@@ -470,22 +407,17 @@ def marshal_snowfast(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, 
     o = m.inputs.other                                          # ignored by the entry (isnowdg is formed on the device)
     o.slope = o.aspect = o.skyview = o.wsa = o.hor = o.isnowdg = None
     fin = _abi.SnowFastIn()
-    fin.drv.base = m.inputs
-    fin.drv.dtm = m.f64(dtm, (R, Cc), "dtm")
-    fin.drv.res, fin.drv.tfact = float(res), float(tfact)
+    fin.drv = _driver_in(m, dtm, res, tfact)
     n_all = len(np.asarray(temp_all))
-    sub = np.ascontiguousarray(subs, dtype=np.int64)
-    if sub.size != m.tsteps:
+    if np.size(subs) != m.tsteps:
         raise ValueError("subs must name every selected hour")
-    m._keep.append(sub)
-    fin.n_all, fin.subs = n_all, sub.ctypes.data_as(C.POINTER(C.c_int64))
+    fin.n_all, fin.subs = n_all, m.i64(subs)
     whole = dict(pmod, temp_all=temp_all, snow_all=snow_all)
     for k in _abi.SNOWFAST_SERIES:
         v = np.ascontiguousarray(whole[k], dtype=np.float64)
         if v.ndim != 1 or v.size < n_all:
             raise ValueError(f"{k}: expected the whole series ({n_all} hours), got shape {v.shape}")
-        m._keep.append(v)
-        setattr(fin, k, v.ctypes.data_as(_abi.c_double_p))
+        setattr(fin, k, m.ptr(v))
     return m, fin
 
 
@@ -495,12 +427,7 @@ def _wanted_series(m: SnowMarshalled, series, every: tuple, out) -> dict:
     names = every if series is None else tuple(series)
     if not names or any(k not in every for k in names):
         raise ValueError(f"series: names out of {every}")
-    arrays = {}
-    for k in every:
-        if k in names:
-            arrays[k] = np.empty((m.rows, m.cols, m.tsteps), dtype=np.float64, order="F")
-            setattr(out, k, arrays[k].ctypes.data_as(_abi.c_double_p))
-    return arrays
+    return _out_arrays(out, {k: (m.rows, m.cols, m.tsteps) for k in every if k in names})
 
 
 def snowmodelq1(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp, other, snowenv, dtm, res, tfact=0.02, *,
@@ -517,6 +444,18 @@ def snowmodelq1(obstime, climdata, pointm, pmod, temp_all, snow_all, subs, vegp,
     arrays = _wanted_series(m, series, _abi.SNOWDRIVER_OUT, out)
     _abi.check(lib.mcf_snowmodelq1(C.byref(fin), C.byref(out), device))
     return arrays
+
+
+def coarse_wind(windspeed, winddir):
+    """The wind of coarse array weather as the snow branch uses it (R/internal.R:2905-2908): the components of each coarse cell
+    [crows, ccols, T] from speed and direction (degrees), their spatial means over the cells that have one, and from the means
+    the one direction per step [T] and the chunk wind series `af_wind` = sqrt(wuv^2 + wvv^2) [T].  The device entries and the
+    host loops they are compared with bit for bit all take these from here.  -> (wu_c, wv_c, winddir, af_wind)"""
+    wd = np.asarray(winddir, dtype=np.float64) * np.pi / 180
+    wu_c = np.asarray(windspeed, dtype=np.float64) * np.cos(wd)
+    wv_c = np.asarray(windspeed, dtype=np.float64) * np.sin(wd)
+    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
+    return wu_c, wv_c, (np.arctan2(wvv, wuv) * 180 / np.pi) % 360, np.sqrt(wuv ** 2 + wvv ** 2)
 
 
 def _fine_snow_inputs(clim_c, pointm_c, sl, z, zc, rowpos, colpos, altcorrect, wu_c, wv_c, winddir):
@@ -569,11 +508,10 @@ def _fine_micro_inputs(clim_c, umu_c, sl, z, zc, rowpos, colpos, altcorrect):
             elevd = (up(zc) - z)[:, :, None]
             temp = (5 / 1000 if altcorrect == 1 else lapserate_R(temp, ea, pres)) * elevd + temp
         relhum = np.clip((ea / satvap_R(temp)) * 100, 20.0, 100.0)
-        wd = wc["winddir"] * np.pi / 180
-        wu, wv = wc["windspeed"] * np.cos(wd), wc["windspeed"] * np.sin(wd)
+        wu, wv, winddir, _ = coarse_wind(wc["windspeed"], wc["winddir"])
         return {"temp": temp, "relhum": relhum, "pres": pres, "swdown": cca(wc["swdown"]), "difrad": cca(wc["difrad"]),
                 "lwdown": cca(wc["lwdown"]), "windspeed": np.sqrt(up(wu) ** 2 + up(wv) ** 2),
-                "winddir": (np.arctan2(np.nanmean(wv, axis=(0, 1)), np.nanmean(wu, axis=(0, 1))) * 180 / np.pi) % 360,
+                "winddir": winddir,
                 "precip": cca(wc["precip"]), "umu": cca(np.asarray(umu_c)[:, :, sl])}
 
 
@@ -582,10 +520,9 @@ def micro_coarse_arrays(clim_c, umu_c) -> dict:
     the vapour pressure and the wind components of each coarse cell's own direction; the rest as given"""
     from .rformulas import satvap_R
     f = lambda k: np.asarray(clim_c[k], dtype=np.float64)                                    # noqa: E731
-    wd = f("winddir") * np.pi / 180
+    windu, windv = coarse_wind(clim_c["windspeed"], clim_c["winddir"])[:2]
     a = {k: f(k) for k in ("temp", "pres", "swdown", "difrad", "lwdown", "precip")}
-    a.update(ea=satvap_R(f("temp")) * (f("relhum") / 100), windu=f("windspeed") * np.cos(wd), windv=f("windspeed") * np.sin(wd),
-             umu=np.asarray(umu_c, dtype=np.float64))
+    a.update(ea=satvap_R(f("temp")) * (f("relhum") / 100), windu=windu, windv=windv, umu=np.asarray(umu_c, dtype=np.float64))
     return a
 
 
@@ -608,8 +545,7 @@ def marshal_microcoarse(clim_c, umu_c, dtm, dtmc, rowpos, colpos, altcorrect=0):
     for k in _abi.MICRO_COARSE:
         setattr(mi, k, m.f64(arrays[k], (cr, cc, n), k))
     with np.errstate(invalid="ignore"):
-        winddir = (np.arctan2(np.nanmean(arrays["windv"], axis=(0, 1)), np.nanmean(arrays["windu"], axis=(0, 1))) * 180 / np.pi) % 360
-    return m, mi, winddir
+        return m, mi, coarse_wind(clim_c["windspeed"], clim_c["winddir"])[2]
 
 
 def expand_micro_coarse(clim_c, umu_c, dtm, dtmc, *, rowpos, colpos, altcorrect: int = 0, step0: int = 0, nsteps: int | None = None,
@@ -626,8 +562,8 @@ def expand_micro_coarse(clim_c, umu_c, dtm, dtmc, *, rowpos, colpos, altcorrect:
     if not names or any(k not in _abi.MICRO_FINE_SERIES for k in names):
         raise ValueError(f"series: names out of {_abi.MICRO_FINE_SERIES}")
     shape = (m.rows, m.cols, max(n, 0))
-    fine = {}
-    for k in _abi.MICRO_FINE_SERIES:
+    fine, ptrs = {}, (_abi.c_double_p * 9)()
+    for i, k in enumerate(_abi.MICRO_FINE_SERIES):
         if out is not None and k in out:
             a = out[k]
             if a.shape != shape or a.dtype != np.float64 or not a.flags.f_contiguous:
@@ -635,7 +571,8 @@ def expand_micro_coarse(clim_c, umu_c, dtm, dtmc, *, rowpos, colpos, altcorrect:
             fine[k] = a
         elif k in names:
             fine[k] = np.empty(shape, dtype=np.float64, order="F")
-    ptrs = (_abi.c_double_p * 9)(*[fine[k].ctypes.data_as(_abi.c_double_p) if k in names else None for k in _abi.MICRO_FINE_SERIES])
+        if k in names:
+            ptrs[i] = m.ptr(fine[k])
     _abi.check(lib.mcf_microsnow_expand_coarse_device(C.byref(mi), C.c_int64(step0), C.c_int64(n), ptrs, device))
     clim = {k: fine[k] for k in _abi.MICRO_FINE_SERIES if k in fine}
     clim["winddir"] = winddir[step0:step0 + n]
@@ -651,10 +588,9 @@ def meltmu2(mu, stemp, tc) -> np.ndarray:
     ta = np.asfortranarray(np.asarray(tc, dtype=np.float64))
     if st.shape != ta.shape or st.shape[:2] != m.shape:
         raise ValueError("stemp and tc must be [rows, cols, n] over mu's raster")
-    out = np.empty(m.shape, dtype=np.float64, order="F")
-    _abi.check(lib.mcf_meltmu2(C.c_int64(m.size), C.c_int64(st.shape[2]), m.ctypes.data_as(_abi.c_double_p),
-                               st.ctypes.data_as(_abi.c_double_p), ta.ctypes.data_as(_abi.c_double_p),
-                               out.ctypes.data_as(_abi.c_double_p)))
+    b = Buffers()
+    out, optr = b.out(m.shape)
+    _abi.check(lib.mcf_meltmu2(C.c_int64(m.size), C.c_int64(st.shape[2]), b.ptr(m), b.ptr(st), b.ptr(ta), optr))
     return out
 
 
@@ -677,11 +613,7 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
     if n % 24 or n == 0:
         raise ValueError("the fast snow method works on whole selected days")
     zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0)
-    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
-    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
-    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
-    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
-    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
+    wu_c, wv_c, winddir, af_wind = coarse_wind(clim_c["windspeed"], clim_c["winddir"])
     oth = dict(other)
     oth.update(T.snow_terrain(z, res, float(other["zref"]), device=device))
     vg = dict(vegp)
@@ -719,7 +651,7 @@ def snowmodelq2_days(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowen
             smod = gridmodelsnow2({k: np.asarray(v)[sl] for k, v in obstime.items()}, clim, pointm, vg, oth, snowenv, device=device)
             dsnow = smod["sdepc"] - isnowdc[:, :, None]
             dsnowg = smod["sdepg"] - isnowdg[:, :, None]
-            af = int(np.round(10 * np.mean(np.sqrt(wuv[sl] ** 2 + wvv[sl] ** 2)) ** 0.5 / res))
+            af = int(np.round(10 * np.mean(af_wind[sl]) ** 0.5 / res))
             tpi = tpicalc(af, z, tfact, device=device)
             dsnowg2 = dsnowg * tpi[:, :, None]
             sdc = (dsnow - dsnowg) + dsnowg2 + isnowdc[:, :, None]
@@ -746,15 +678,11 @@ def _marshal_coarse(cin, clim_c, pointm_c, dtm, dtmc, rowpos, colpos, altcorrect
     cr, cc, n = np.shape(clim_c["temp"])
     m = SnowMarshalled()
     m.rows, m.cols, m.tsteps = R, Cc, n
-    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
-    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
-    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
-    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
-    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
+    wu_c, wv_c, winddir, af_wind = coarse_wind(clim_c["windspeed"], clim_c["winddir"])
     si = cin.drv.base
     si.rows, si.cols, si.tsteps, si.array_forcing = R, Cc, n, 1
     cin.drv.dtm = m.f64(z, (R, Cc), "dtm")
-    cin.drv.af_wind = m.f64(np.sqrt(wuv ** 2 + wvv ** 2), (n,), "af_wind")
+    cin.drv.af_wind = m.f64(af_wind, (n,), "af_wind")
     cin.coarse_rows, cin.coarse_cols, cin.altcorrect = cr, cc, int(altcorrect)
     cin.coarse_rowpos = m.f64(rowpos, (R,), "rowpos")
     cin.coarse_colpos = m.f64(colpos, (Cc,), "colpos")
@@ -795,16 +723,14 @@ def marshal_snowfast2(obstime, clim_c, pointm_c, pm2_c, subs, vegp, other, snowe
     """-> (the marshalling that keeps the arrays alive, mcf_snowfast2_in) for `snowmodelq2`'s arguments: the coarse arrays
     stay coarse; the wind components, the one direction per hour and `af_wind` are formed here as `snowmodelq2_days` forms them"""
     cr, cc, n = np.shape(clim_c["temp"])
-    sub = np.ascontiguousarray(subs, dtype=np.int64)
-    if sub.size != n or len(np.asarray(obstime["year"])) != n:
+    if np.size(subs) != n or len(np.asarray(obstime["year"])) != n:
         raise ValueError("subs and obstime must name every selected hour")
     fin = _abi.SnowFast2In()
     m, winddir = _marshal_coarse(fin, clim_c, pointm_c, dtm, dtmc, rowpos, colpos, altcorrect)
     _marshal_model(m, fin.drv.base, obstime, winddir, vegp, other, snowenv, 0.01, False)
     fin.drv.res, fin.drv.tfact = float(res), float(tfact)
     n_all = np.shape(pm2_c["tc"])[2]
-    m._keep.append(sub)
-    fin.n_all, fin.subs = n_all, sub.ctypes.data_as(C.POINTER(C.c_int64))
+    fin.n_all, fin.subs = n_all, m.i64(subs)
     for k in _abi.SNOWFAST2_SERIES:
         setattr(fin, k, m.f64(pm2_c[k], (cr, cc, n_all), k))
     return m, fin
@@ -839,8 +765,8 @@ def meltmu2_coarse(skyview, dtm, sstemp_c, tc_c, rowpos, colpos, device: int = 0
     rp, cp = np.ascontiguousarray(rowpos, dtype=np.float64), np.ascontiguousarray(colpos, dtype=np.float64)
     if st.shape != ta.shape or st.ndim != 3 or sv.shape != z.shape or rp.shape != (z.shape[0],) or cp.shape != (z.shape[1],):
         raise ValueError("sstemp_c and tc_c must be [crows, ccols, n], skyview and dtm one raster with a position per row and column")
-    out = np.empty(z.shape, dtype=np.float64, order="F")
-    p = lambda a: a.ctypes.data_as(_abi.c_double_p)                                      # noqa: E731
+    b = Buffers()
+    out, p = b.out(z.shape)[0], b.ptr
     _abi.check(lib.mcf_meltmu2_device(C.c_int64(z.shape[0]), C.c_int64(z.shape[1]), p(sv), p(z), C.c_int64(st.shape[0]),
                                       C.c_int64(st.shape[1]), p(rp), p(cp), C.c_int64(st.shape[2]), p(st), p(ta), p(out),
                                       C.c_int32(device)))
@@ -867,11 +793,7 @@ def snowmodel2_chunks(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc
         raise ValueError("the array snow model needs at least one whole 5-day chunk")
     hole = np.isnan(z)
     zc = np.nan_to_num(np.asarray(dtmc, dtype=np.float64), nan=0.0)
-    wd = np.asarray(clim_c["winddir"], dtype=np.float64) * np.pi / 180
-    wu_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.cos(wd)
-    wv_c = np.asarray(clim_c["windspeed"], dtype=np.float64) * np.sin(wd)
-    wuv, wvv = np.nanmean(wu_c, axis=(0, 1)), np.nanmean(wv_c, axis=(0, 1))
-    winddir = (np.arctan2(wvv, wuv) * 180 / np.pi) % 360
+    wu_c, wv_c, winddir, af_wind = coarse_wind(clim_c["windspeed"], clim_c["winddir"])
     names = ("Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden", "umu")
     out = {k: np.full((R, Cc, h), np.nan, order="F") for k in names}
     oth = dict(other)
@@ -885,7 +807,7 @@ def snowmodel2_chunks(obstime, clim_c, pointm_c, vegp, other, snowenv, dtm, dtmc
             oth.update(T.snow_terrain(dtms, res, float(other["zref"]), agg=agg, mask=z, device=device))
             clim, pointm = _fine_snow_inputs(clim_c, pointm_c, sl, z, zc, rowpos, colpos, altcorrect, wu_c, wv_c, winddir)
             smod = gridmodelsnow2({k: np.asarray(v)[sl] for k, v in obstime.items()}, clim, pointm, vg, oth, snowenv, device=device)
-            af = max(int(np.round(10 * np.mean(np.sqrt(wuv[sl] ** 2 + wvv[sl] ** 2)) ** 0.5 / res)), 2)
+            af = max(int(np.round(10 * np.mean(af_wind[sl]) ** 0.5 / res)), 2)
             tpi = tpicalc(af, dtms, tfact, device=device)[:, :, None]
             asd = isnowdg[:, :, None]
             dsnow = smod["sdepg"] - asd
@@ -952,8 +874,9 @@ def expand_coarse(clim_c, pointm_c, dtm, dtmc, *, rowpos, colpos, altcorrect: in
     lib = _abi.load()
     m, cin, winddir = marshal_snowcoarse(None, clim_c, pointm_c, None, None, None, dtm, dtmc, 1.0, 0.0, rowpos, colpos, altcorrect)
     n = m.tsteps - step0 if nsteps is None else int(nsteps)
-    fine = {k: np.empty((m.rows, m.cols, max(n, 0)), dtype=np.float64, order="F") for k in _abi.SNOW_FINE_SERIES}
-    ptrs = (_abi.c_double_p * 13)(*[fine[k].ctypes.data_as(_abi.c_double_p) for k in _abi.SNOW_FINE_SERIES])
+    fine, ptrs = {}, (_abi.c_double_p * 13)()
+    for i, k in enumerate(_abi.SNOW_FINE_SERIES):
+        fine[k], ptrs[i] = m.out((m.rows, m.cols, max(n, 0)))
     _abi.check(lib.mcf_snow_expand_coarse_device(C.byref(cin), C.c_int64(step0), C.c_int64(n), ptrs, device))
     clim = {k: fine[k] for k in _abi.SNOW_FINE_SERIES[:8]}
     clim["winddir"] = winddir[step0:step0 + n]
@@ -974,11 +897,9 @@ def applycpp3(a, fun_name: str, *, device: int = 0, with_count: bool = False):
     if arr.ndim != 3:
         raise ValueError("applycpp3 needs a [rows, cols, tsteps] array")
     R, Cc, T = arr.shape
-    res = np.empty(T)
-    cnt = np.empty(T) if with_count else None
-    _abi.check(lib.mcf_applycpp3(arr.ctypes.data_as(_abi.c_double_p), R, Cc, T, APPLY_FUNS[fun_name],
-                                 res.ctypes.data_as(_abi.c_double_p),
-                                 cnt.ctypes.data_as(_abi.c_double_p) if with_count else None, device))
+    b = Buffers()
+    res, cnt = np.empty(T), np.empty(T) if with_count else None
+    _abi.check(lib.mcf_applycpp3(b.ptr(arr), R, Cc, T, APPLY_FUNS[fun_name], b.ptr(res), b.ptr(cnt), device))
     return (res, cnt) if with_count else res
 
 
@@ -1032,10 +953,7 @@ class SnowPlan:
         self._lib = _abi.load()
         R, Cc = np.shape(vegp["pai"])
         self._m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
-        din = _abi.SnowDriverIn()
-        din.base = self._m.inputs
-        din.dtm = self._m.f64(dtm, (R, Cc), "dtm")
-        din.res, din.tfact, din.chunk_steps = float(res), float(tfact), int(chunk_steps)
+        din = _driver_in(self._m, dtm, res, tfact, chunk_steps)
         self._p = C.c_void_p()
         _abi.check(self._lib.mcf_snowplan_create(C.byref(din), int(row0), int(rows_total), device, C.byref(self._p)))
         self.rows, self.cols, self.tsteps = R, Cc, self._m.tsteps
@@ -1067,22 +985,21 @@ class SnowPlan:
         a = np.empty((self.rows, self.cols), dtype=np.float64, order="F") if out is None else out
         if a.shape != (self.rows, self.cols) or not a.flags.f_contiguous:
             raise ValueError("out must be a column-major [rows, cols] array")
-        _abi.check(self._lib.mcf_snowplan_surface(self._p, a.ctypes.data_as(_abi.c_double_p)))
+        _abi.check(self._lib.mcf_snowplan_surface(self._p, Buffers().ptr(a)))
         return a
 
     def handover(self) -> np.ndarray:
         """The pack depth handed to the next chunk (`other$isnowdc`), own rows."""
-        a = np.empty((self.rows, self.cols), dtype=np.float64, order="F")
-        _abi.check(self._lib.mcf_snowplan_handover(self._p, a.ctypes.data_as(_abi.c_double_p)))
+        a, ptr = Buffers().out((self.rows, self.cols))
+        _abi.check(self._lib.mcf_snowplan_handover(self._p, ptr))
         return a
 
     def apply3(self, chunk: int, fun_name: str):
         """applycpp3 of the chunk's totalSWE on the device: (result, non-NA counts), each [steps of the chunk]"""
         fun = {"mean": 0, "sum": 1, "max": 2, "min": 3}[fun_name]
         n = min(self._chunk_steps, self.tsteps - chunk * self._chunk_steps)
-        r, c = np.empty(n), np.empty(n)
-        _abi.check(self._lib.mcf_snowplan_apply3(self._p, int(chunk), fun, r.ctypes.data_as(_abi.c_double_p),
-                                                 c.ctypes.data_as(_abi.c_double_p)))
+        (r, rp), (c, cp) = Buffers().out(n), Buffers().out(n)
+        _abi.check(self._lib.mcf_snowplan_apply3(self._p, int(chunk), fun, rp, cp))
         return r, c
 
     def surface_partial(self):
@@ -1097,7 +1014,7 @@ class SnowPlan:
             e = np.asfortranarray(np.asarray(ext, dtype=np.float64))
             if e.shape != (halo_north + self.rows + halo_south, self.cols):
                 raise ValueError("ext must be [halo_north + rows + halo_south, cols]")
-            p = e.ctypes.data_as(_abi.c_double_p)
+            p = Buffers().ptr(e)
         _abi.check(self._lib.mcf_snowplan_prepare_chunk(self._p, int(chunk), p, int(halo_north), int(halo_south),
                                                         float(surface_mean), C.byref(s), C.byref(n)))
         return s.value, n.value
@@ -1136,13 +1053,9 @@ class SnowPlan:
 
     def fetch_summary(self) -> dict:
         """-> {series: {statistic: [rows, cols, nperiods]}, "days": counted days per period}"""
-        sp, vi, si, _pod = self._psum
-        planes = _planes(self.rows, self.cols, sp, vi, si)
-        for (v, k), a in planes.items():
-            _abi.check(self._lib.mcf_snowplan_summary_fetch(self._p, v, k, a.ctypes.data_as(_abi.c_double_p), 0))
-        days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
-        _abi.check(self._lib.mcf_snowplan_summary_days(self._p, days.ctypes.data_as(_abi.c_int32_p)))
-        return _summary_dict(_abi.SNOWDRIVER_OUT, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+        return summary_sink(Buffers(), self.rows, self.cols, self._psum, _abi.SNOWDRIVER_OUT,
+                            plane=lambda v, k, ptr: _abi.check(self._lib.mcf_snowplan_summary_fetch(self._p, v, k, ptr, 0)),
+                            days=lambda ptr: _abi.check(self._lib.mcf_snowplan_summary_days(self._p, ptr)))
 
     # ---- the snow-day microclimate inside the chunk loop (include/mcf.h: two passes over the year) ------------------
     def reset(self):
@@ -1157,10 +1070,9 @@ class SnowPlan:
         indices within the block): the hand-over state, the chunk's terrain, the series of the chunk run last."""
         c = np.ascontiguousarray(cells, dtype=np.int64)
         depth = {"wsa": 8, "hor": 24}.get(what, self._chunk_steps if self.FETCH[what] >= 8 else 1)
-        out = np.empty((c.size, depth), dtype=np.float64, order="F")
+        out, optr = Buffers().out((c.size, depth))
         d = C.c_int32()
-        _abi.check(self._lib.mcf_snowplan_fetch_cells(self._p, self.FETCH[what], c.ctypes.data_as(C.POINTER(C.c_int64)),
-                                                      int(c.size), out.ctypes.data_as(_abi.c_double_p), C.byref(d)))
+        _abi.check(self._lib.mcf_snowplan_fetch_cells(self._p, self.FETCH[what], Buffers().ptr(c), int(c.size), optr, C.byref(d)))
         assert d.value == depth
         return out
 
@@ -1196,7 +1108,7 @@ class SnowPlan:
 
     def meand_accumulate(self, chunk: int, snowday):
         sd = np.ascontiguousarray(snowday, dtype=np.int32)
-        _abi.check(self._lib.mcf_snowplan_meand_accumulate(self._p, int(chunk), sd.ctypes.data_as(_abi.c_int32_p)))
+        _abi.check(self._lib.mcf_snowplan_meand_accumulate(self._p, int(chunk), Buffers().ptr(sd)))
 
     def micro_setup(self, reqhgt, obstime, climdata, vegp, other, mat, out, sub_of_day, reuse_static: bool = False):
         """gridmicrosnow1's inputs for the snow-day SUBSET series (what `.prepsnowinputs1` hands it: subset weather incl.
@@ -1220,17 +1132,17 @@ class SnowPlan:
             self._micro_static = m
         sod = np.ascontiguousarray(sub_of_day, dtype=np.int32)
         sel = (C.c_int32 * _abi.NOUT)(*[1 if v else 0 for v in out])
-        _abi.check(self._lib.mcf_snowplan_micro_setup(self._p, C.byref(m.inputs), sod.ctypes.data_as(_abi.c_int32_p),
+        _abi.check(self._lib.mcf_snowplan_micro_setup(self._p, C.byref(m.inputs), Buffers().ptr(sod),
                                                       int(sod.size), float(reqhgt), float(mat), C.byref(sel), 1 if reuse_static else 0))
 
     def covered_tiles(self, plan, chunk: int, day: int, ndays: int):
         """uint8 [tiles of `plan`]: 1 where every cell of the tile lies under snow at every step of the chunk's days
         [day, day + ndays) — mcf_snowplan_microsnow overwrites all its values, the solver may leave the tile out
         (include/mcf.h mcf_snowplan_covered_tiles); and the number of such tiles"""
-        sk = np.zeros(plan.n_tiles, np.uint8)
+        sk, skp = Buffers().out(plan.n_tiles, np.uint8, zero=True)
         n = C.c_int64(0)
         _abi.check(self._lib.mcf_snowplan_covered_tiles(self._p, plan._p, int(chunk), int(day), int(ndays),
-                                                        sk.ctypes.data_as(C.POINTER(C.c_uint8)), int(sk.size), C.byref(n)))
+                                                        skp, int(sk.size), C.byref(n)))
         return sk, int(n.value)
 
     def free_cells(self, plan, chunk: int, day: int, ndays: int):
@@ -1244,7 +1156,7 @@ class SnowPlan:
     def microsnow(self, plan, chunk: int, slot: int, nosnowday):
         """gridmicrosnow1 on the chunk's snow days, written over the solver's outputs in ring slot `slot` of `plan`."""
         nd = np.ascontiguousarray(nosnowday, dtype=np.int32)
-        _abi.check(self._lib.mcf_snowplan_microsnow(self._p, plan._p, int(chunk), int(slot), nd.ctypes.data_as(_abi.c_int32_p)))
+        _abi.check(self._lib.mcf_snowplan_microsnow(self._p, plan._p, int(chunk), int(slot), Buffers().ptr(nd)))
 
 
 def _dev_piece(t, cols):
@@ -1331,6 +1243,15 @@ def snowmodel1_chunks_tiled(plan, rank: int, world: int, *, exchange=None, allre
     return plan.result
 
 
+def _marshal_grid(g: Mapping, array_forcing: bool, device: int, cells_per_block: int = 0, coarse: Mapping | None = None):
+    """marshal() of a `grid` mapping: the arguments of api.runmicro1Cpp by name (array weather: "lats" / "lons" for lat / lon),
+    with the defaults a mapping may leave out"""
+    return marshal(g["obstime"], g["climdata"], g["pointm"], g["vegp"], g["soilc"], g["reqhgt"], g["zref"],
+                   g["lats"] if "lats" in g else g["lat"], g["lons"] if "lons" in g else g["lon"],
+                   g.get("Sminp", 0.0), g.get("Smaxp", 0.0), g["tfact"], g.get("complete", True), g.get("mat", 0.0),
+                   g.get("out", (1,) * 10), array_forcing, device, 0, cells_per_block, g.get("dfsel"), coarse)
+
+
 # ---- `runmicro(..., snow = TRUE)` as one library call (include/mcf.h mcf_runmicrosnow1 / mcf_snowrun_*) -------------------
 class SnowRun:
     """`.snowmodel1` + `.runmicrosnow1` (R/internal.R:2498-2619, 3581-3659) device-resident, staged:
@@ -1365,9 +1286,9 @@ class SnowRun:
         self._p = C.c_void_p()
         if self.coarse:
             # (pointm$umu of every step leaves with pass 1: the coarse handle hands it out of the chunks' slabs)
-            self.umu = np.empty((self.rows, self.cols, self.tsteps), dtype=np.float64, order="F") if want_umu else None
+            self.umu, umup = self._sm.out((self.rows, self.cols, self.tsteps)) if want_umu else (None, None)
             _abi.check(self._lib.mcf_snowrun_create_coarse(C.byref(self._cin_all), C.byref(self._gm.options), C.byref(mu[0]) if mu else None,
-                                                           self.umu.ctypes.data_as(_abi.c_double_p) if want_umu else None, C.byref(self._p)))
+                                                           umup, C.byref(self._p)))
             self.days = int(self._lib.mcf_snowrun_days(self._p))
             return
         create = self._lib.mcf_snowrun_create_below if below else self._lib.mcf_snowrun_create
@@ -1375,15 +1296,11 @@ class SnowRun:
         self.days = int(self._lib.mcf_snowrun_days(self._p))
 
     def _marshal(self, grid: Mapping, snow: Mapping, device: int, cells_per_block: int):
-        from .marshal import alloc_outputs, marshal
         self._lib = _abi.load()
         g = grid
         # array weather (mcf_runmicrosnow2): `snow` carries "af_wind" (and optionally "wsa_s"), every weather array is [rows, cols, T]
         self.array_weather = "af_wind" in snow
-        self._gm = marshal(g["obstime"], g["climdata"], g["pointm"], g["vegp"], g["soilc"], g["reqhgt"], g["zref"],
-                           g["lats"] if "lats" in g else g["lat"], g["lons"] if "lons" in g else g["lon"],
-                           g.get("Sminp", 0.0), g.get("Smaxp", 0.0), g["tfact"], g.get("complete", True), g.get("mat", 0.0),
-                           g.get("out", (1,) * 10), self.array_weather, device, 0, cells_per_block, g.get("dfsel"))
+        self._gm = _marshal_grid(g, self.array_weather, device, cells_per_block)
         self._alloc_outputs = lambda: alloc_outputs(self._gm)
         R, Cc = np.shape(snow["vegp"]["pai"])
         oth = _terrain_placeholders(snow["other"], R, Cc)
@@ -1394,11 +1311,7 @@ class SnowRun:
         else:
             self._sm = marshal_snow(snow["obstime"], snow["climdata"], snow["vegp"], oth, False, pointm=snow["pointm"],
                                     snowenv=snow.get("snowenv", "Alpine"))
-            self._din = _abi.SnowDriverIn()
-            self._din.base = self._sm.inputs
-            self._din.dtm = self._sm.f64(snow["dtm"], (R, Cc), "dtm")
-            self._din.res, self._din.tfact = float(snow["res"]), float(snow.get("tfact", 0.02))
-            self._din.chunk_steps = int(snow.get("chunk_steps", 120))
+            self._din = _driver_in(self._sm, snow["dtm"], snow["res"], snow.get("tfact", 0.02), snow.get("chunk_steps", 120))
         self._in = _abi.MicrosnowIn()
         self._in.grid = C.pointer(self._gm.inputs)
         self._in.snow = C.pointer(self._din)
@@ -1409,16 +1322,12 @@ class SnowRun:
         self._msum = self._psum = None      # (spec, variables, statistics, table) of the enabled summaries
 
     def _marshal_coarse(self, grid: Mapping, snow: Mapping, micro_coarse: Mapping, device: int):
-        from .marshal import alloc_outputs, marshal
         self._lib = _abi.load()
         g = grid
         if "coarse" not in g:
             raise ValueError('the coarse snow run takes grid["coarse"] = {"rowpos", "colpos"[, "altcorrect", "dtmc", "dtm"]}')
         self.array_weather = True
-        self._gm = marshal(g["obstime"], g["climdata"], g["pointm"], g["vegp"], g["soilc"], g["reqhgt"], g["zref"],
-                           g["lats"] if "lats" in g else g["lat"], g["lons"] if "lons" in g else g["lon"],
-                           g.get("Sminp", 0.0), g.get("Smaxp", 0.0), g["tfact"], g.get("complete", True), g.get("mat", 0.0),
-                           g.get("out", (1,) * 10), True, device, 0, 0, g.get("dfsel"), g["coarse"])
+        self._gm = _marshal_grid(g, True, device, 0, g["coarse"])
         self._alloc_outputs = lambda: alloc_outputs(self._gm)
         alt = int(snow.get("altcorrect", 0))
         self._sm, self._cin, _ = marshal_snowcoarse(snow["obstime"], snow["clim_c"], snow["pointm_c"], snow["vegp"], snow["other"],
@@ -1453,7 +1362,7 @@ class SnowRun:
         """Between pass1 and pass2, layered vegetation: the solver's day -> layer map (include/mcf.h mcf_snowrun_set_day_layers);
         one 0-based layer per day of the whole series, -1: none"""
         lod = np.ascontiguousarray(layer_of_day, dtype=np.int32)
-        _abi.check(self._lib.mcf_snowrun_set_day_layers(self._p, lod.ctypes.data_as(_abi.c_int32_p), int(lod.size)))
+        _abi.check(self._lib.mcf_snowrun_set_day_layers(self._p, Buffers().ptr(lod), int(lod.size)))
 
     def stats(self) -> dict:
         """What pass 2 was spared (include/mcf.h mcf_snowrun_stats)."""
@@ -1495,13 +1404,9 @@ class SnowRun:
         for pack, spec, names in ((0, self._msum, _abi.OUT_NAMES), (1, self._psum, _abi.SNOWDRIVER_OUT)):
             if spec is None:
                 continue
-            sp, vi, si, _pod = spec
-            planes = _planes(self.rows, self.cols, sp, vi, si)
-            for (v, k), a in planes.items():
-                _abi.check(self._lib.mcf_snowrun_summary_fetch(self._p, pack, v, k, a.ctypes.data_as(_abi.c_double_p)))
-            days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
-            _abi.check(self._lib.mcf_snowrun_summary_days(self._p, pack, days.ctypes.data_as(_abi.c_int32_p)))
-            d = _summary_dict(names, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+            d = summary_sink(Buffers(), self.rows, self.cols, spec, names,
+                             plane=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_summary_fetch(self._p, pack, v, k, ptr)),
+                             days=lambda ptr: _abi.check(self._lib.mcf_snowrun_summary_days(self._p, pack, ptr)))
             if pack:
                 res["snow"] = d
             else:
@@ -1510,10 +1415,9 @@ class SnowRun:
 
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
-        sd, nd = np.zeros(self.days, np.int32), np.zeros(self.days, np.int32)
+        (sd, sdp), (nd, ndp) = Buffers().out(self.days, np.int32, zero=True), Buffers().out(self.days, np.int32, zero=True)
         so, smod = _driver_out(self.rows, self.cols, self.tsteps) if want_smod else (None, None)
-        _abi.check(self._lib.mcf_snowrun_pass1(self._p, C.byref(so) if so is not None else None, sd.ctypes.data_as(_abi.c_int32_p),
-                                               nd.ctypes.data_as(_abi.c_int32_p)))
+        _abi.check(self._lib.mcf_snowrun_pass1(self._p, C.byref(so) if so is not None else None, sdp, ndp))
         return (sd, nd, smod) if want_smod else (sd, nd)
 
     def pass2(self, micro: Mapping | None, mat: float, want_arrays: bool = True):
@@ -1540,7 +1444,6 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
     summary / pack_summary (mappings as for SnowRun.summary_enable): the run through mcf_runmicrosnow_summary, either weather
     geometry -> {"out": the merged outputs, or None with want_arrays False (nothing of size cells x steps is moved), "summary":
     as SnowRun.fetch_summary, "snowdays", "nosnowdays"[, "smod"]}"""
-    from .marshal import alloc_outputs
     with SnowRun(grid, snow, device=device, cells_per_block=cells_per_block, handle=False) as run:
         if micro is not None:
             run._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], run.array_weather, micro=True)
@@ -1565,22 +1468,15 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
 
 
 def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, devices, n_blocks) -> dict:
-    from .marshal import alloc_outputs
     lib = _abi.load()
     ms = _micro_summary_spec(summary) if summary is not None else None
     ps = _pack_summary_spec(pack_summary) if pack_summary is not None else None
     so = _abi.SnowrunSummaryOut()
-    res, keep = {"out": None, "summary": {}}, []
+    res = {"out": None, "summary": {}}
     for spec, names, dst, key in ((ms, _abi.OUT_NAMES, so.micro, None), (ps, _abi.SNOWDRIVER_OUT, so.pack, "snow")):
         if spec is None:
             continue
-        sp, vi, si, _pod = spec
-        planes = _planes(run.rows, run.cols, sp, vi, si)
-        for (v, k), a in planes.items():
-            dst.val[v][k] = a.ctypes.data_as(_abi.c_double_p)
-        days = np.zeros(max(int(sp.nperiods), 1), dtype=np.int32)
-        dst.days = days.ctypes.data_as(_abi.c_int32_p)
-        d = _summary_dict(names, vi, si, planes, days[:max(int(sp.nperiods), 0)])
+        d = summary_sink(run._gm, run.rows, run.cols, spec, names, dst)
         if key:
             res["summary"][key] = d
         else:
@@ -1592,9 +1488,8 @@ def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, de
         sm, res["smod"] = _driver_out(run.rows, run.cols, run.tsteps)
         so.smod = C.pointer(sm)
     nd = run.tsteps // 24
-    res["snowdays"], res["nosnowdays"] = np.zeros(nd, np.int32), np.zeros(nd, np.int32)
-    so.snowday = res["snowdays"].ctypes.data_as(_abi.c_int32_p)
-    so.nosnowday = res["nosnowdays"].ctypes.data_as(_abi.c_int32_p)
+    res["snowdays"], so.snowday = run._gm.out(nd, np.int32, zero=True)
+    res["nosnowdays"], so.nosnowday = run._gm.out(nd, np.int32, zero=True)
     mu = _abi.multi(devices, n_blocks)
     _abi.check(lib.mcf_runmicrosnow_summary(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
                                             C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))

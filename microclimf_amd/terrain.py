@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from .marshal import Buffers
 
 HALO = 128          # >= 100 + 2.5 * s for s = 10
 WHAT = ("slope", "aspect", "hor", "svfa", "wsa")
@@ -32,7 +33,8 @@ def precompute_terrain(dtm, res: float, zref: float, *, agg: int = 10, halo_nort
     tin = _abi.TerrainIn()
     tin.rows, tin.cols = rows, cols
     tin.halo_north, tin.halo_south = halo_north, halo_south
-    tin.dtm = z.ctypes.data_as(_abi.c_double_p)
+    b = Buffers()
+    tin.dtm = b.ptr(z)
     tin.res, tin.zref, tin.agg = float(res), float(zref), int(agg)
     tin.row0, tin.rows_total = int(row0), int(rows_total)
     shapes = {"slope": (rows, cols), "aspect": (rows, cols), "hor": (rows, cols, 24),
@@ -40,18 +42,14 @@ def precompute_terrain(dtm, res: float, zref: float, *, agg: int = 10, halo_nort
     tout = _abi.TerrainOut()
     res_arrays = {}
     for k in WHAT:
-        if k in what:
-            a = np.empty(shapes[k], dtype=np.float64, order="F")
-            res_arrays[k] = a
-            setattr(tout, k, a.ctypes.data_as(_abi.c_double_p))
-        else:
-            setattr(tout, k, None)
+        res_arrays[k], ptr = b.out(shapes[k]) if k in what else (None, None)
+        setattr(tout, k, ptr)
     mu = _abi.multi(devices, n_blocks)
     if mu:
         _abi.check(lib.mcf_precompute_terrain_multi(C.byref(tin), C.byref(tout), C.byref(mu[0])))
     else:
         _abi.check(lib.mcf_precompute_terrain(C.byref(tin), C.byref(tout), device))
-    return res_arrays
+    return {k: a for k, a in res_arrays.items() if a is not None}
 
 
 def snow_terrain(dtm, res: float, zref: float, *, agg: int | None = None, mask=None, device: int = 0) -> dict:
@@ -138,8 +136,9 @@ def flowaccCpp(dm, device=None) -> np.ndarray:
     values, exactly."""
     lib = _abi.load()
     z = np.asfortranarray(np.asarray(dm, dtype=np.float64))
-    fa = np.empty(z.shape, dtype=np.float64, order="F")
-    args = (z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), fa.ctypes.data_as(_abi.c_double_p))
+    b = Buffers()
+    fa, faptr = b.out(z.shape)
+    args = (z.shape[0], z.shape[1], b.ptr(z), faptr)
     _abi.check(lib.mcf_flowacc(*args) if device is None else lib.mcf_flowacc_device(*args, int(device)))
     return fa
 
@@ -150,7 +149,8 @@ def topidx(dtm, res, device=None) -> np.ndarray:
     lib = _abi.load()
     z = np.asfortranarray(np.asarray(dtm, dtype=np.float64))
     xres, yres = (res, res) if np.isscalar(res) else res
-    twi = np.empty(z.shape, dtype=np.float64, order="F")
-    args = (z.shape[0], z.shape[1], z.ctypes.data_as(_abi.c_double_p), float(xres), float(yres), twi.ctypes.data_as(_abi.c_double_p))
+    b = Buffers()
+    twi, twiptr = b.out(z.shape)
+    args = (z.shape[0], z.shape[1], b.ptr(z), float(xres), float(yres), twiptr)
     _abi.check(lib.mcf_topidx(*args) if device is None else lib.mcf_topidx_device(*args, int(device)))
     return twi

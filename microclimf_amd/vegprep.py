@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
+from .marshal import Buffers
 
 
 def _raster(a, name, shape=None):
@@ -25,7 +26,7 @@ def _raster(a, name, shape=None):
 
 
 def _p(a):
-    return a.ctypes.data_as(_abi.c_double_p)
+    return Buffers().ptr(a)          # (every array is a local of the entry that makes the call)
 
 
 def _call(name, device, *args):
