@@ -703,6 +703,84 @@ typedef struct mcf_depth_summary_out {
 int mcf_runmicro_depths_summary(const mcf_grid_inputs *in, const mcf_options *opt, const double *depths, int32_t ndepths,
                                 const double *tbp, const mcf_summary_spec *spec, int32_t chunk_days, mcf_depth_summary_out *out);
 
+/* ---- series sink --------------------------------------------------------------------------------------------------------
+ * The sinks above reduce over time or keep everything; this one reduces over SPACE, or keeps the full hourly series at a few
+ * cells: per-step statistics of the outputs over zones of the raster (terra::zonal / global(..., na.rm = TRUE) layer by layer)
+ * and the series at logger sites, accumulated on the device from each ring chunk as it is produced.  For reqhgt >= 0 (the
+ * tiled ring).  DESIGN.md §27.
+ *
+ * `series`, defined here once.  A series spec is
+ *   - npoints cells[npoints]: int64, 0-based, row + rows * col, as mcf_plan_fetch_cells takes them;
+ *   - nzones, 0 .. MCF_MAX_ZONES, and zone[rows * cols]: int32, column-major, -1 = in no zone, else 0 .. nzones - 1.  A point
+ *     needs no zone; npoints or nzones may be 0, not both;
+ *   - a selection var[] of output variables, each one the plan was created with;
+ *   - a selection zstat[] of the four statistics below (read when nzones > 0).
+ * Point series of a selected variable: [tsteps, npoints], column-major (each point's series contiguous); every step holds the
+ * ring's value bit for bit, NA payload included; steps of days never folded, and steps behind the last whole day, are NA_real_.
+ * Zone series of a selected (variable, statistic): [tsteps, nzones], column-major.  For one (zone z, step k, variable), over
+ * the cells with zone == z: a NaN value is skipped (na.rm = TRUE); a value that is not NaN with !(|v| < 4096) is BAD (that covers
+ * +-inf); n = the number of values neither skipped nor bad.
+ *   COUNT   (double)n
+ *   MEAN    ((double)S * 2^-24) / (double)n with S = sum of (int64)rint(v * 2^24) over the counted values, rint rounding half to
+ *           even: an INTEGER sum, so it does not depend on order, tiling, chunking or device count.  Its distance from the exact
+ *           mean of the counted values is at most 2^-25 (each term is off by at most 2^-25, so is their mean; (double)S is exact
+ *           while |S| < 2^53 and rounds once beyond; the divide rounds once).  |v| < 4096 keeps |S| < 2^62 for up to 2^26 cells; a
+ *           larger raster is MCF_ERR_ARG.
+ *   MIN, MAX  the minimum / maximum of the counted values, with + 0.0 applied (a -0.0 never appears)
+ *   If any value of the zone-step is bad, or n == 0, every statistic except COUNT is NA_real_ (with n == 0, COUNT is 0).
+ *   Steps of days never folded, and steps behind the last whole day, are NA_real_ in every statistic.
+ * The result is a function of the ring's values alone: it does not depend on ring days, chunking, slot placement, tile size or
+ * the order in which days are folded. */
+#define MCF_MAX_ZONES 64
+enum mcf_zstat {
+    MCF_ZSTAT_MEAN = 0,
+    MCF_ZSTAT_MIN = 1,
+    MCF_ZSTAT_MAX = 2,
+    MCF_ZSTAT_COUNT = 3,
+    MCF_NZSTAT = 4
+};
+typedef struct mcf_series_spec {
+    int64_t npoints;
+    const int64_t *cells;          /* [npoints]                                    */
+    int32_t nzones;
+    const int32_t *zone;           /* [rows * cols]; read when nzones > 0          */
+    int32_t var[MCF_NOUT];         /* != 0: kept                                   */
+    int32_t zstat[MCF_NZSTAT];     /* != 0: kept (nzones > 0)                      */
+} mcf_series_spec;
+/* Switches the sink on: allocates the point buffer, nvars x npoints x tsteps x 8 bytes, and the zone state, nvars x 4 x nzones x
+ * whole days x 24 x 8 bytes (MCF_ERR_NOMEM when they do not fit).  MCF_ERR_ARG, the message starting with the entry's name:
+ * reqhgt < 0 or a streamed plan, a selected variable the plan was not created with, an empty selection (no variable; neither
+ * points nor zones; zones without a statistic), nzones > MCF_MAX_ZONES, a label outside -1 .. nzones - 1, a cell index outside
+ * the raster, more than 2^26 cells.  MCF_ERR_STATE when called twice.  May be enabled beside the period summary and on a
+ * diagnostics plan (it reads the ten outputs only). */
+int mcf_plan_series_enable(mcf_plan *plan, const mcf_series_spec *spec);
+/* Folds days [slot_day0, slot_day0 + ndays) of ring slot `slot` as calendar days [day0, day0 + ndays), on the plan's stream
+ * behind the run that filled them.  Days may come in any order, each at most once: a second fold of a day is MCF_ERR_STATE,
+ * as is a call before the enable. */
+int mcf_plan_series_accumulate(mcf_plan *plan, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays);
+/* dst: [tsteps, npoints] / [tsteps, nzones], column-major (selected in the enable: MCF_ERR_ARG otherwise; MCF_ERR_STATE
+ * before the enable) */
+int mcf_plan_series_fetch_points(mcf_plan *plan, int32_t var, double *dst);
+int mcf_plan_series_fetch_zones(mcf_plan *plan, int32_t var, int32_t zstat, double *dst);
+/* Back to the state of the enable: nothing folded, any day may come next. */
+int mcf_plan_series_reset(mcf_plan *plan);
+/* One call, host to host, as mcf_runmicro_summary runs it (vector, fine array and coarse array forcing, with or without dfsel;
+ * the plan is created with out = spec->var; chunk_days = 0: the same ring budget).  points[v]: caller-allocated
+ * [tsteps, npoints] for every selected variable when npoints > 0; zones[v][s]: [tsteps, nzones] for every selected pair when
+ * nzones > 0 (a null one is MCF_ERR_ARG). */
+typedef struct mcf_series_out {
+    double *points[MCF_NOUT];
+    double *zones[MCF_NOUT][MCF_NZSTAT];
+} mcf_series_out;
+int mcf_runmicro_series(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_series_spec *spec, int32_t chunk_days,
+                        mcf_series_out *out);
+/* The zone series of a caller's host array x[rows, cols, nsteps] (column-major, any nsteps >= 1: the arrays mcf_runmicro*
+ * returned, the snow series), by the same kernel: out[s] = [nsteps, nzones] for every selected statistic (a null one is
+ * MCF_ERR_ARG).  The array goes through the device in pieces of whole days, tiled as the output ring is (32-cell tiles;
+ * MCF_ZONAL_CPB = 16, 21, 32 or 42 overrides).  Refusals as for the enable, before a device is touched. */
+int mcf_zonal_series(const double *x, int64_t rows, int64_t cols, int64_t nsteps, const int32_t *zone, int32_t nzones,
+                     const int32_t zstat[MCF_NZSTAT], int32_t device, double *const out[MCF_NZSTAT]);
+
 /* ---- terrain pre-compute (the solver's terrain inputs, built on the device) ------
  * Restates the R-side arithmetic of the reference's marshaller (R/internal.R):
  *   hor   = .horizon(dtm, 15*d), d = 0..23            R/internal.R:909-925, 1144

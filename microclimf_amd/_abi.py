@@ -137,6 +137,23 @@ class SummaryOut(C.Structure):
     _fields_ = [("val", (c_double_p * NSTAT) * NOUT), ("days", c_int32_p)]
 
 
+NZSTAT = 4
+MAX_ZONES = 64      # include/mcf.h MCF_MAX_ZONES
+# include/mcf.h mcf_zstat: the statistics of a zone series, in the enum's order
+ZSTAT_NAMES = ("mean", "min", "max", "count")
+
+
+class SeriesSpec(C.Structure):
+    """include/mcf.h mcf_series_spec"""
+    _fields_ = [("npoints", C.c_int64), ("cells", C.POINTER(C.c_int64)), ("nzones", C.c_int32), ("zone", c_int32_p),
+                ("var", C.c_int32 * NOUT), ("zstat", C.c_int32 * NZSTAT)]
+
+
+class SeriesOut(C.Structure):
+    """include/mcf.h mcf_series_out"""
+    _fields_ = [("points", c_double_p * NOUT), ("zones", (c_double_p * NZSTAT) * NOUT)]
+
+
 MAX_DEPTHS = 8      # include/mcf.h MCF_MAX_DEPTHS
 
 
@@ -372,6 +389,8 @@ EXPORTS = (
     "mcf_plan_set_day_layers", "mcf_snowrun_set_day_layers", "mcf_plan_fetch_mxtc",
     "mcf_foliageden", "mcf_foliageden_device", "mcf_plan_set_height", "mcf_plan_fetch_foliage", "mcf_runmicro_heights",
     "mcf_selftest_step", "mcf_selftest_snow",
+    "mcf_plan_series_enable", "mcf_plan_series_accumulate", "mcf_plan_series_fetch_points", "mcf_plan_series_fetch_zones",
+    "mcf_plan_series_reset", "mcf_runmicro_series", "mcf_zonal_series",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -545,6 +564,23 @@ def load() -> C.CDLL:
             for fn in (lib.mcf_runmicro2_diag, lib.mcf_runmicro4_diag):
                 fn.restype = C.c_int
                 fn.argtypes = [GI, OP, DSEL, OU, C.POINTER(DiagOutputs)]
+    if hasattr(lib, "mcf_plan_series_enable"):      # (absent from an older library named by MCF_LIB for an A/B run)
+        RS = C.POINTER(SeriesSpec)
+        lib.mcf_plan_series_enable.restype = C.c_int
+        lib.mcf_plan_series_enable.argtypes = [P, RS]
+        lib.mcf_plan_series_accumulate.restype = C.c_int
+        lib.mcf_plan_series_accumulate.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+        lib.mcf_plan_series_fetch_points.restype = C.c_int
+        lib.mcf_plan_series_fetch_points.argtypes = [P, C.c_int32, c_double_p]
+        lib.mcf_plan_series_fetch_zones.restype = C.c_int
+        lib.mcf_plan_series_fetch_zones.argtypes = [P, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_plan_series_reset.restype = C.c_int
+        lib.mcf_plan_series_reset.argtypes = [P]
+        lib.mcf_runmicro_series.restype = C.c_int
+        lib.mcf_runmicro_series.argtypes = [GI, OP, RS, C.c_int32, C.POINTER(SeriesOut)]
+        lib.mcf_zonal_series.restype = C.c_int
+        lib.mcf_zonal_series.argtypes = [c_double_p, C.c_int64, C.c_int64, C.c_int64, c_int32_p, C.c_int32, c_int32_p, C.c_int32,
+                                         C.POINTER(c_double_p)]
     if hasattr(lib, "mcf_plan_summary_enable"):     # (absent from an older library named by MCF_LIB for an A/B run)
         SS, SO_ = C.POINTER(SummarySpec), C.POINTER(SummaryOut)
         lib.mcf_plan_summary_enable.restype = C.c_int

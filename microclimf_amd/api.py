@@ -108,6 +108,100 @@ def runmicro_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp:
     return res
 
 
+def _names_to_indices(sel, names, what):
+    idx = sorted({names.index(v) if isinstance(v, str) else int(v) for v in ((sel,) if isinstance(sel, str) else sel)})
+    if any(v < 0 or v >= len(names) for v in idx):
+        raise ValueError(f"{what} of {names}")
+    return idx
+
+
+def series_spec(rows: int, cols: int, points=None, zones=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None):
+    """include/mcf.h mcf_series_spec: `points` 0-based cell indices row + rows * col (None: no points), `zones` a [rows, cols]
+    integer array of labels (negative or masked: in no zone; None: no zones), `nzones` default the largest label + 1, `vars`
+    output names or indices, `stats` names of _abi.ZSTAT_NAMES or indices.
+    -> (spec, the selected variables' indices, the selected statistics' indices); the spec holds its arrays"""
+    vi = _names_to_indices(vars, _abi.OUT_NAMES, "series: variables")
+    si = _names_to_indices(stats, _abi.ZSTAT_NAMES, "series: statistics")
+    sp = _abi.SeriesSpec()
+    sp._owner = b = Buffers()
+    if points is not None:
+        cells = np.ascontiguousarray(np.asarray(points, dtype=np.int64)).ravel()
+        sp.npoints, sp.cells = cells.size, b.ptr(cells)
+    if zones is not None:
+        z = np.ma.masked_invalid(zones) if np.asarray(zones).dtype.kind == "f" else np.ma.asarray(zones)
+        if z.shape != (rows, cols):
+            raise ValueError(f"zones: expected shape {(rows, cols)}, got {z.shape}")
+        lab = np.asfortranarray(np.where(np.ma.getmaskarray(z) | (z.filled(-1) < 0), -1, z.filled(-1)).astype(np.int32))
+        sp.nzones = int(nzones) if nzones is not None else int(lab.max()) + 1
+        sp.zone = b.ptr(lab)
+    for v in vi:
+        sp.var[v] = 1
+    for k in si:
+        sp.zstat[k] = 1
+    return sp, vi, si
+
+
+def _series_sink(b: Buffers, tsteps: int, sp, vi, si, so=None, points=None, zones=None) -> dict:
+    """The host side of a series sink: one [tsteps, npoints] array per selected variable and one [tsteps, nzones] array per
+    selected (variable, statistic), held by `b`; their pointers go into `so` (mcf_series_out) or to points(v, pointer) /
+    zones(v, k, pointer) -> {"points": {variable: array}, "zones": {variable: {statistic: array}}}"""
+    res = {"points": {}, "zones": {}}
+    for v in vi:
+        name = _abi.OUT_NAMES[v]
+        if sp.npoints > 0:
+            res["points"][name], ptr = b.out((tsteps, int(sp.npoints)))
+            if so is not None:
+                so.points[v] = ptr
+            else:
+                points(v, ptr)
+        if sp.nzones > 0:
+            res["zones"][name] = {}
+            for k in si:
+                res["zones"][name][_abi.ZSTAT_NAMES[k]], ptr = b.out((tsteps, int(sp.nzones)))
+                if so is not None:
+                    so.zones[v][k] = ptr
+                else:
+                    zones(v, k, ptr)
+    return res
+
+
+def runmicro_series(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, reqhgt: float,
+                    zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, points=None,
+                    zones=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None, chunk_days: int = 0,
+                    array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                    cells_per_block: int = 0) -> dict:
+    """The hourly series at a few cells and per-step statistics over zones of the raster, accumulated on the device chunk by
+    chunk (include/mcf.h "series sink", mcf_runmicro_series): runmicro_summary's argument lists; `points`, `zones`, `vars`,
+    `stats`, `nzones` as series_spec takes them.
+    -> {"points": {variable: [tsteps, npoints]}, "zones": {variable: {statistic: [tsteps, nzones]}}}"""
+    hgt = np.asarray(vegp["hgt"])
+    sp, vi, si = series_spec(hgt.shape[0], hgt.shape[1], points, zones, vars, stats, nzones)
+    out = [1 if v in vi else 0 for v in range(_abi.NOUT)]
+    lib = _abi.load()
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out,
+                bool(array_forcing) or coarse is not None, device, 0, cells_per_block, dfsel, coarse)
+    so = _abi.SeriesOut()
+    res = _series_sink(m, m.tsteps, sp, vi, si, so)
+    _abi.check(lib.mcf_runmicro_series(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(so)))
+    return res
+
+
+def zonal_series(x, zones, stats=("mean", "min", "max"), device: int = 0, nzones: int | None = None) -> dict:
+    """The zone series of a host array x[rows, cols, nsteps] (include/mcf.h mcf_zonal_series): `zones` and `stats` as
+    series_spec takes them -> {statistic: [nsteps, nzones]}"""
+    x = np.asarray(x, dtype=np.float64)
+    if x.ndim != 3:
+        raise ValueError("x: a [rows, cols, nsteps] array")
+    sp, _vi, si = series_spec(x.shape[0], x.shape[1], None, zones, (0,), stats, nzones)
+    b = Buffers()
+    res, ptrs = {}, (_abi.c_double_p * _abi.NZSTAT)()
+    for k in si:
+        res[_abi.ZSTAT_NAMES[k]], ptrs[k] = b.out((x.shape[2], max(int(sp.nzones), 0)))
+    _abi.check(_abi.load().mcf_zonal_series(b.ptr(np.asfortranarray(x)), x.shape[0], x.shape[1], x.shape[2], sp.zone, sp.nzones,
+                                            sp.zstat, int(device), ptrs))
+    return res
+
+
 def _depth_list(depths, tbp, tsteps):
     """(depths as float64, tbp as C-ordered [ndepths, tsteps] or None) for the C ABI"""
     d = np.ascontiguousarray(np.atleast_1d(np.asarray(depths, dtype=np.float64))).ravel()
@@ -767,6 +861,39 @@ class Plan:
     def summary_reset(self):
         """Back to the state of summary_enable: nothing folded."""
         _abi.check(self._lib.mcf_plan_summary_reset(self._p))
+
+    def series_enable(self, points=None, zones=None, vars=("Tz",), stats=("mean", "min", "max"), *, nzones=None):
+        """The series sink (include/mcf.h mcf_plan_series_enable): the hourly series of `vars` at `points` (cell indices
+        row + rows * col) and their per-step statistics `stats` (names of _abi.ZSTAT_NAMES) over `zones` ([rows, cols] labels,
+        negative or masked: in no zone), kept on the device.  -> (variables, statistics) selected"""
+        sp, vi, si = series_spec(self.rows, self.cols, points, zones, vars, stats, nzones)
+        _abi.check(self._lib.mcf_plan_series_enable(self._p, C.byref(sp)))
+        self._series_shape = (int(sp.npoints), int(sp.nzones))
+        return [_abi.OUT_NAMES[v] for v in vi], [_abi.ZSTAT_NAMES[k] for k in si]
+
+    def series_accumulate(self, slot: int, slot_day0: int, day0: int, ndays: int):
+        """Fold days [slot_day0, slot_day0 + ndays) of the slot as calendar days [day0, day0 + ndays), behind the run that
+        filled them; days in any order, each at most once (include/mcf.h mcf_plan_series_accumulate)."""
+        _abi.check(self._lib.mcf_plan_series_accumulate(self._p, slot, slot_day0, day0, ndays))
+
+    def fetch_point_series(self, var) -> np.ndarray:
+        """[tsteps, npoints] of one selected variable (name or index)"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        a, ptr = Buffers().out((self.tsteps, getattr(self, "_series_shape", (1, 1))[0]))
+        _abi.check(self._lib.mcf_plan_series_fetch_points(self._p, v, ptr))
+        return a
+
+    def fetch_zone_series(self, var, stat) -> np.ndarray:
+        """[tsteps, nzones] of one selected statistic of one selected variable (names or indices)"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        k = _abi.ZSTAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
+        a, ptr = Buffers().out((self.tsteps, getattr(self, "_series_shape", (1, 1))[1]))
+        _abi.check(self._lib.mcf_plan_series_fetch_zones(self._p, v, k, ptr))
+        return a
+
+    def series_reset(self):
+        """Back to the state of series_enable: nothing folded."""
+        _abi.check(self._lib.mcf_plan_series_reset(self._p))
 
     def fetch(self, slot: int, var, step0: int, nsteps: int) -> np.ndarray:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)

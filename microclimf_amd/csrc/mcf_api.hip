@@ -145,6 +145,18 @@ struct mcf_plan {
     uint32_t sum_init_codes = 0;
     std::vector<int32_t> sum_pod, sum_days;
     int sum_next_day = 0;           // the first day that may still be folded
+    // series sink (mcf_plan_series_enable; ser_on): the points' [selected var][point][tsteps] buffer, the zones' state
+    // (mcf_kernels.h SeriesZonesArgs), one statistic [tsteps][zone] on its way to the host, the folded days
+    bool ser_on = false;
+    int64_t ser_npoints = 0;
+    int ser_nzones = 0, ser_nsel = 0, ser_workgroups = 0;
+    int ser_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
+    int ser_zstat[MCF_NZSTAT] = {};
+    int64_t* d_ser_cells = nullptr;
+    int32_t *d_ser_zone = nullptr, *d_ser_done = nullptr;
+    double *d_ser_points = nullptr, *d_ser_plane = nullptr;
+    long long* d_ser_state = nullptr;
+    std::vector<int32_t> ser_done;  // [days] 1: folded
     // reqhgt < 0
     double *d_tgser = nullptr, *d_ddsum = nullptr, *d_scratch = nullptr;
     const double *d_Tgp = nullptr, *d_Tbp = nullptr;
@@ -2690,6 +2702,266 @@ static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, con
 int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_summary_spec* spec, int32_t chunk_days,
                          mcf_summary_out* out) {
     return run_summary(in, opt, spec, chunk_days, out);
+}
+
+// ---- series sink (include/mcf.h "series sink"; kernels: mcf_series.hip) ---------------------------------------
+// the zones of a spec, judged without a device: the count, the labels, a statistic
+static int check_series_zones(const std::string& who, const int32_t* zone, int64_t N, int32_t nzones, const int32_t* zstat) {
+    if (nzones < 0 || nzones > MCF_MAX_ZONES)
+        return fail(MCF_ERR_ARG, who + ": nzones = " + std::to_string(nzones) + " is outside 0 .. " + std::to_string(MCF_MAX_ZONES));
+    if (nzones == 0) return MCF_OK;
+    if (!zone) return fail(MCF_ERR_ARG, who + ": null zone map");
+    int ns = 0;
+    for (int k = 0; k < MCF_NZSTAT; ++k) ns += zstat[k] ? 1 : 0;
+    if (ns == 0) return fail(MCF_ERR_ARG, who + ": no statistic selected");
+    for (int64_t c = 0; c < N; ++c)
+        if (zone[c] < -1 || zone[c] >= nzones)
+            return fail(MCF_ERR_ARG, who + ": zone[" + std::to_string(c) + "] = " + std::to_string(zone[c]) + " is outside -1 .. nzones - 1");
+    return MCF_OK;
+}
+// everything of a series spec that can be judged without a device; `requested`: the plan's var_slot (null: any variable)
+static int check_series_spec(const std::string& who, const mcf_series_spec* s, int64_t rows, int64_t cols, const int* requested) {
+    if (!s) return fail(MCF_ERR_ARG, who + ": null mcf_series_spec");
+    const int64_t N = rows * cols;
+    if (N > ((int64_t)1 << 26)) return fail(MCF_ERR_ARG, who + ": more than 2^26 cells (the fixed-point sum's range)");
+    int nv = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nv += s->var[v] ? 1 : 0;
+    if (nv == 0) return fail(MCF_ERR_ARG, who + ": no variable selected");
+    if (s->npoints < 0) return fail(MCF_ERR_ARG, who + ": negative npoints");
+    if (s->npoints == 0 && s->nzones == 0) return fail(MCF_ERR_ARG, who + ": neither points nor zones selected");
+    for (int v = 0; v < MCF_NOUT; ++v)
+        if (s->var[v] && requested && requested[v] < 0)
+            return fail(MCF_ERR_ARG, who + ": a selected variable was not requested in out[] at plan creation");
+    if (const int rc = check_series_zones(who, s->zone, N, s->nzones, s->zstat)) return rc;
+    if (s->npoints > 0 && !s->cells) return fail(MCF_ERR_ARG, who + ": null cells");
+    for (int64_t i = 0; i < s->npoints; ++i)
+        if (s->cells[i] < 0 || s->cells[i] >= N)
+            return fail(MCF_ERR_ARG, who + ": cells[" + std::to_string(i) + "] = " + std::to_string(s->cells[i]) + " is a cell index outside the raster");
+    return MCF_OK;
+}
+// persistent workgroups per selected variable: one per compute unit (the kernel's LDS lets one reside on each)
+static int series_workgroups(int device) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n < 1) n = 256;
+    return n;
+}
+
+int mcf_plan_series_enable(mcf_plan* p, const mcf_series_spec* spec) {
+    const std::string who = "mcf_plan_series_enable";
+    if (!p || !spec) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (p->bg_stream) return fail(MCF_ERR_ARG, who + ": the series sink is not available on a streamed plan");
+    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
+    if (p->ser_on) return fail(MCF_ERR_STATE, who + ": the series sink is already enabled on this plan");
+    int rc = check_series_spec(who, spec, p->rows, p->cols, p->var_slot);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(p->device));
+    int nsel = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nsel += spec->var[v] ? 1 : 0;
+    const int64_t np = spec->npoints, nz = spec->nzones, steps = (int64_t)p->ndays * 24, T = std::max<int64_t>(p->tsteps, 1);
+    const int64_t point_bytes = nsel * np * T * 8, state_bytes = nsel * mcf::kSeriesRows * nz * steps * 8;
+    if ((rc = check_room(point_bytes, "mcf_plan_series_enable: the point buffer"))) return rc;
+    if ((rc = check_room(point_bytes + state_bytes + nz * T * 8 + p->N * 4, "mcf_plan_series_enable: the zone state"))) return rc;
+    if (np > 0) {
+        if ((rc = p->dev.make(&p->d_ser_cells, np))) return rc;
+        HIP_TRY(hipMemcpy(p->d_ser_cells, spec->cells, (size_t)np * 8, hipMemcpyHostToDevice));
+        if ((rc = p->dev.make(&p->d_ser_points, nsel * np * T))) return rc;
+    }
+    if (nz > 0) {
+        if ((rc = p->dev.make(&p->d_ser_zone, p->N))) return rc;
+        HIP_TRY(hipMemcpy(p->d_ser_zone, spec->zone, (size_t)p->N * 4, hipMemcpyHostToDevice));
+        if ((rc = p->dev.make(&p->d_ser_state, state_bytes / 8))) return rc;
+        if ((rc = p->dev.make(&p->d_ser_plane, nz * T))) return rc;
+        if ((rc = p->dev.make(&p->d_ser_done, std::max(p->ndays, 1)))) return rc;
+    }
+    p->ser_npoints = np; p->ser_nzones = (int)nz; p->ser_nsel = nsel;
+    p->ser_workgroups = series_workgroups(p->device);
+    int place = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) p->ser_sel1[v] = spec->var[v] ? ++place : 0;
+    for (int k = 0; k < MCF_NZSTAT; ++k) p->ser_zstat[k] = nz > 0 && spec->zstat[k] ? 1 : 0;
+    p->ser_on = true;
+    return mcf_plan_series_reset(p);
+}
+
+int mcf_plan_series_reset(mcf_plan* p) {
+    if (!p) return fail(MCF_ERR_ARG, "mcf_plan_series_reset: null plan");
+    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->d_ser_points)
+        mcf::launch_fill(p->d_ser_points, p->ser_nsel * p->ser_npoints * std::max<int64_t>(p->tsteps, 1), mcf::na_real_host(), p->stream);
+    if (p->d_ser_state) mcf::launch_series_init(p->d_ser_state, p->ser_nsel, p->ser_nzones, (int64_t)p->ndays * 24, p->stream);
+    HIP_TRY(hipGetLastError());
+    p->ser_done.assign((size_t)std::max(p->ndays, 1), 0);
+    return MCF_OK;
+}
+
+int mcf_plan_series_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays) {
+    if (!p) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: null plan");
+    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: slot out of range");
+    if (day0 < 0 || ndays < 1 || (int64_t)day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: day range out of bounds");
+    if (slot_day0 < 0 || (int64_t)slot_day0 + ndays > p->ring_days)
+        return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: more days than the ring slot holds");
+    for (int d = day0; d < day0 + ndays; ++d)
+        if (p->ser_done[(size_t)d])
+            return fail(MCF_ERR_STATE, "mcf_plan_series_accumulate: day " + std::to_string(d) + " has been folded already (each day at most once)");
+    HIP_TRY(hipSetDevice(p->device));
+    if (p->ser_npoints > 0) {
+        mcf::SeriesPointsArgs a{};
+        for (int v = 0; v < MCF_NOUT; ++v)
+            if (p->ser_sel1[v]) a.src[p->ser_sel1[v] - 1] = ring_view(p, slot, v);
+        a.nsel = p->ser_nsel;
+        a.step0 = (int64_t)slot_day0 * 24; a.nsteps = (int64_t)ndays * 24;
+        a.cells = p->d_ser_cells; a.ncells = p->ser_npoints;
+        a.dst = p->d_ser_points; a.dst_steps = std::max<int64_t>(p->tsteps, 1); a.dst_step0 = (int64_t)day0 * 24;
+        mcf::launch_series_points(a, p->stream);
+    }
+    if (p->ser_nzones > 0) {
+        mcf::SeriesZonesArgs a{};
+        a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
+        a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
+        a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
+        a.nsel = p->ser_nsel;
+        for (int v = 0; v < MCF_NOUT; ++v)
+            if (p->ser_sel1[v]) a.slab[p->ser_sel1[v] - 1] = p->var_slot[v];
+        a.zone = p->d_ser_zone; a.nzones = p->ser_nzones;
+        a.steps = (int64_t)p->ndays * 24;
+        a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
+        a.state = p->d_ser_state;
+        mcf::launch_series_zones(a, p->ser_workgroups, p->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    for (int d = day0; d < day0 + ndays; ++d) p->ser_done[(size_t)d] = 1;
+    return MCF_OK;
+}
+
+int mcf_plan_series_fetch_points(mcf_plan* p, int32_t var, double* dst) {
+    if (!p || !dst) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: null argument");
+    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+    if (var < 0 || var >= MCF_NOUT || !p->ser_sel1[var])
+        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: variable was not selected in mcf_plan_series_enable");
+    if (p->ser_npoints == 0) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: no points were selected in mcf_plan_series_enable");
+    HIP_TRY(hipSetDevice(p->device));
+    const int64_t n = p->ser_npoints * std::max<int64_t>(p->tsteps, 1);
+    HIP_TRY(p->tohost.dense(dst, p->d_ser_points + (int64_t)(p->ser_sel1[var] - 1) * n, (size_t)n * 8, p->stream));
+    return MCF_OK;
+}
+
+int mcf_plan_series_fetch_zones(mcf_plan* p, int32_t var, int32_t zstat, double* dst) {
+    if (!p || !dst) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: null argument");
+    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+    if (var < 0 || var >= MCF_NOUT || !p->ser_sel1[var])
+        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: variable was not selected in mcf_plan_series_enable");
+    if (zstat < 0 || zstat >= MCF_NZSTAT || !p->ser_zstat[zstat])
+        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: statistic was not selected in mcf_plan_series_enable");
+    HIP_TRY(hipSetDevice(p->device));
+    const int64_t steps = (int64_t)p->ndays * 24, T = std::max<int64_t>(p->tsteps, 1);
+    HIP_TRY(hipMemcpyAsync(p->d_ser_done, p->ser_done.data(), (size_t)std::max(p->ndays, 1) * 4, hipMemcpyHostToDevice, p->stream));
+    mcf::launch_series_fin(p->d_ser_state + (int64_t)(p->ser_sel1[var] - 1) * mcf::kSeriesRows * p->ser_nzones * steps, p->ser_nzones,
+                           steps, T, p->d_ser_done, zstat, p->d_ser_plane, p->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(p->tohost.dense(dst, p->d_ser_plane, (size_t)(T * p->ser_nzones) * 8, p->stream));
+    return MCF_OK;
+}
+
+int mcf_runmicro_series(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_series_spec* spec, int32_t chunk_days,
+                        mcf_series_out* out) {
+    const std::string who = "mcf_runmicro_series";
+    if (!spec || !out) return fail(MCF_ERR_ARG, who + ": null argument");
+    int rc = check_inputs(in, opt_in);
+    if (rc) return rc;
+    if (opt_in->reqhgt < 0.0) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
+    if (chunk_days < 0) return fail(MCF_ERR_ARG, who + ": negative chunk_days");
+    if ((rc = check_series_spec(who, spec, in->rows, in->cols, nullptr))) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!spec->var[v]) continue;
+        if (spec->npoints > 0 && !out->points[v]) return fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (spec->nzones > 0 && spec->zstat[k] && !out->zones[v][k])
+                return fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
+    }
+    const int ndays = (int)(in->tsteps / 24);
+    mcf_options opt = *opt_in;
+    int nsel = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) nsel += (opt.out[v] = spec->var[v] ? 1 : 0);
+    if ((rc = ensure_device(opt.device))) return rc;
+    int chunk = chunk_days;
+    if (chunk == 0)
+        chunk = ring_budget_days("MCF_SUMMARY_RING_GB", nsel + (in->array_forcing == 1 ? 15 : 0), in->rows * in->cols,
+                                 opt.cells_per_block ? opt.cells_per_block : 21);
+    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
+    mcf_plan* p = nullptr;
+    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
+    PlanHolder holder(p);
+    if ((rc = mcf_plan_series_enable(p, spec))) return rc;
+    if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return mcf_plan_series_accumulate(p, 0, 0, d0, nd); }))) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!spec->var[v]) continue;
+        if (spec->npoints > 0 && (rc = mcf_plan_series_fetch_points(p, v, out->points[v]))) return rc;
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (spec->nzones > 0 && spec->zstat[k] && (rc = mcf_plan_series_fetch_zones(p, v, k, out->zones[v][k]))) return rc;
+    }
+    return mcf_plan_sync(p);
+}
+
+int mcf_zonal_series(const double* x, int64_t rows, int64_t cols, int64_t nsteps, const int32_t* zone, int32_t nzones,
+                     const int32_t* zstat, int32_t device, double* const* out) {
+    const std::string who = "mcf_zonal_series";
+    if (!x || !zone || !zstat || !out) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (rows <= 0 || cols <= 0 || nsteps < 1) return fail(MCF_ERR_ARG, who + ": rows, cols and nsteps must be positive");
+    const int64_t N = rows * cols;
+    if (N > ((int64_t)1 << 26)) return fail(MCF_ERR_ARG, who + ": more than 2^26 cells (the fixed-point sum's range)");
+    if (nzones < 1) return fail(MCF_ERR_ARG, who + ": nzones = " + std::to_string(nzones) + " is outside 1 .. " + std::to_string(MCF_MAX_ZONES));
+    int rc = check_series_zones(who, zone, N, nzones, zstat);
+    if (rc) return rc;
+    for (int k = 0; k < MCF_NZSTAT; ++k)
+        if (zstat[k] && !out[k]) return fail(MCF_ERR_ARG, who + ": a selected statistic has a null buffer");
+    int cpb = 32;
+    if (const char* e = getenv("MCF_ZONAL_CPB")) {
+        cpb = atoi(e);
+        if (!(cpb == 16 || cpb == 21 || cpb == 32 || cpb == 42)) return fail(MCF_ERR_ARG, who + ": MCF_ZONAL_CPB must be 16, 21, 32 or 42");
+    }
+    if ((rc = ensure_device(device))) return rc;
+    const int64_t ndays = (nsteps + 23) / 24, steps = ndays * 24, ntiles = (N + cpb - 1) / cpb, B = mcf::ring_block_doubles(cpb);
+    // pieces of whole days: about 1 GB of staging (the array's steps as they lie, and their tiled copy)
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ndays, 2730), (int64_t)(1e9 / (8.0 * (24.0 * N + (double)ntiles * B)))));
+    mcf::DevOwner own;
+    double *d_lin = nullptr, *d_til = nullptr, *d_plane = nullptr;
+    int32_t* d_zone = nullptr;
+    long long* d_state = nullptr;
+    if ((rc = own.make(&d_lin, N * 24 * chunk))) return rc;
+    if ((rc = own.make(&d_til, ntiles * chunk * B))) return rc;
+    if ((rc = own.make(&d_plane, nsteps * nzones))) return rc;
+    if ((rc = own.make(&d_state, mcf::kSeriesRows * (int64_t)nzones * steps))) return rc;
+    if ((rc = own.up(const_cast<const int32_t**>(&d_zone), zone, N, "zone"))) return rc;
+    hipStream_t s = nullptr;
+    mcf::launch_series_init(d_state, 1, nzones, steps, s);
+    const int workgroups = series_workgroups(device);
+    for (int64_t d0 = 0; d0 < ndays; d0 += chunk) {
+        const int64_t nd = std::min(chunk, ndays - d0), ns = std::min(nd * 24, nsteps - d0 * 24);
+        // the hours behind the array's last step are NaN: skipped, and never asked for
+        if (ns < nd * 24) mcf::launch_fill(d_til, ntiles * chunk * B, __builtin_nan(""), s);
+        HIP_TRY(hipMemcpyAsync(d_lin, x + N * d0 * 24, (size_t)(N * ns) * 8, hipMemcpyHostToDevice, s));
+        mcf::RingView til{};
+        til.base = d_til; til.N = N; til.tile_stride = chunk * B; til.day_stride = B; til.cpb = cpb;
+        mcf::launch_tile_series(d_lin, ns, til, s);
+        mcf::SeriesZonesArgs a{};
+        a.ring = d_til; a.tile_stride = til.tile_stride; a.day_stride = til.day_stride; a.var_stride = 0;
+        a.N = N; a.ntiles = ntiles; a.cpb = cpb; a.nsel = 1; a.slab[0] = 0;
+        a.zone = d_zone; a.nzones = nzones; a.steps = steps;
+        a.day0 = (int)d0; a.ndays = (int)nd; a.slot_day0 = 0;
+        a.state = d_state;
+        mcf::launch_series_zones(a, workgroups, s);
+        HIP_TRY(hipGetLastError());
+    }
+    mcf::ToHost tohost;
+    for (int k = 0; k < MCF_NZSTAT; ++k) {
+        if (!zstat[k]) continue;
+        mcf::launch_series_fin(d_state, nzones, steps, nsteps, nullptr, k, d_plane, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(tohost.dense(out[k], d_plane, (size_t)(nsteps * nzones) * 8));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return MCF_OK;
 }
 
 // ---- below ground at several depths from one solve (include/mcf.h mcf_runmicro_depths) ----------------------

@@ -373,6 +373,43 @@ struct SummaryPlanesArgs {
     double* state;
 };
 void launch_summary_planes(const SummaryPlanesArgs& a, hipStream_t s);
+// ---- series sink (mcf_series.hip; include/mcf.h "series sink") ------------------------------------------------
+// Zone state [selected var][kSeriesRows][zone][step] of int64, a zone's steps contiguous: the fixed-point sum, the counted
+// values (low 32 bits) and the bad ones (high 32 bits) in one word, the minimum and the maximum as order-preserving keys.
+constexpr int kSeriesRows = 4;
+enum { kSeriesSum = 0, kSeriesCount = 1, kSeriesMin = 2, kSeriesMax = 3 };
+struct SeriesZonesArgs {
+    const double* ring;          // the slot, addressed as SummaryAccArgs' ring
+    int64_t tile_stride, day_stride, var_stride;
+    int64_t N, ntiles;
+    int32_t cpb;                 // 16, 21, 32 or 42
+    int32_t nsel;                // selected variables (the grid's y)
+    int32_t slab[10];            // ring slab of each selected variable
+    const int32_t* zone;         // [N] labels, -1 .. nzones - 1
+    int32_t nzones;
+    int64_t steps;               // steps per zone in the state (whole days x 24)
+    int32_t day0, ndays;         // days of the state this call folds ...
+    int32_t slot_day0;           // ... and where the first of them lies in the slot
+    long long* state;
+};
+// `workgroups`: persistent workgroups per selected variable (each walks many tile groups and flushes once per day)
+void launch_series_zones(const SeriesZonesArgs& a, int workgroups, hipStream_t s);
+void launch_series_init(long long* state, int64_t nsel, int64_t nzones, int64_t steps, hipStream_t s);
+// one statistic of one variable's state -> out[k + nsteps * z], k < nsteps; steps >= `steps` and steps of days with
+// day_done[day] == 0 (null: every day is folded) are NA
+void launch_series_fin(const long long* state, int nzones, int64_t steps, int64_t nsteps, const int32_t* day_done, int zstat,
+                       double* out, hipStream_t s);
+// dst[(i * ncells + ci) * dst_steps + dst_step0 + k] = src[i](cells[ci], step0 + k), k < nsteps, i < nsel
+struct SeriesPointsArgs {
+    RingView src[10];
+    int32_t nsel;
+    int64_t step0, nsteps;
+    const int64_t* cells;
+    int64_t ncells;
+    double* dst;
+    int64_t dst_steps, dst_step0;
+};
+void launch_series_points(const SeriesPointsArgs& a, hipStream_t s);
 // dst[ci + ncells*k] = src(cells[ci], step0 + k), k < nsteps
 void launch_gather_cells(const RingView& src, int64_t step0, int64_t nsteps, const int64_t* cells, int64_t ncells, double* dst,
                          hipStream_t s);

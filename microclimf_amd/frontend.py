@@ -510,6 +510,86 @@ def runmicro_summary(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, d
     return res
 
 
+# ---- series at logger sites and per-step zonal statistics, straight from the device -------------------------------------------------
+def series_cells(dtm: Mapping, rows: int, cols: int, points=None, xy=None) -> np.ndarray:
+    """0-based cell indices row + rows * col of `points` ((row, col) pairs) followed by those of `xy` (map coordinates (x, y),
+    placed with dtm["xmin"], dtm["ymax"] and dtm["res"] as runmicro_big lays out its files: row 0 is the northern edge).  A
+    point or coordinate outside the raster is a ValueError."""
+    cells = []
+    if points is not None:
+        for r, c in np.asarray(points, dtype=np.int64).reshape(-1, 2):
+            if not (0 <= r < rows and 0 <= c < cols):
+                raise ValueError(f"points: ({r}, {c}) is outside the {rows} x {cols} raster")
+            cells.append(int(r) + rows * int(c))
+    if xy is not None:
+        res = dtm["res"]
+        xres, yres = (res, res) if np.isscalar(res) else res
+        for x, y in np.asarray(xy, dtype=np.float64).reshape(-1, 2):
+            c, r = int(np.floor((x - dtm["xmin"]) / xres)), int(np.floor((dtm["ymax"] - y) / yres))
+            if not (0 <= r < rows and 0 <= c < cols):
+                raise ValueError(f"xy: ({x}, {y}) is outside the raster")
+            cells.append(int(r) + rows * int(c))
+    return np.asarray(cells, dtype=np.int64)
+
+
+def runmicro_series(micropoint, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, points=None, xy=None, zones=None,
+                    vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), pai_a=None, tfact: float = 1.5, slr=None,
+                    apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0, from_dtm: bool = False,
+                    crows: int | None = None, ccols: int | None = None, lats=None, lons=None, altcorrect: int = 0, dtmc=None,
+                    chunk_days: int = 0) -> dict:
+    """`runmicro()` reduced over space on the device: the hourly series of `vars` at logger sites — `points` ((row, col) pairs)
+    and / or `xy` (map coordinates, see series_cells) — and their per-step statistics `stats` (names of api._abi.ZSTAT_NAMES)
+    over `zones`, a [rows, cols] integer array of labels 0 .. 63 (negative or masked: in no zone) — what terra::zonal or
+    global(..., na.rm = TRUE) over mout$Tz give layer by layer, without cells x steps values ever leaving the solver's ring.
+    The other arguments as for runmicro_summary.  reqhgt == 0 masks the variables as runmicro does; reqhgt < 0 is not available.
+    -> {"points": {variable: [tsteps, npoints]}, "zones": {variable: {statistic: [tsteps, nzones]}}, "cells": the points' cell
+    indices row + rows * col}"""
+    if reqhgt < 0:
+        raise ValueError("the series sink needs reqhgt >= 0")
+    names, out = _out_mask(vars)
+    if any(s not in api._abi.ZSTAT_NAMES for s in ((stats,) if isinstance(stats, str) else stats)):
+        raise ValueError(f"stats: names of {api._abi.ZSTAT_NAMES}")
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    cells = series_cells(dtm, rows, cols, points, xy)
+    ter = dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf)
+    array = not isinstance(micropoint, Mapping)
+    plan_kw = {}
+    if array:
+        if crows is None or ccols is None or lats is None or lons is None:
+            raise ValueError("a list of micropoints (array weather) needs crows, ccols, lats and lons")
+        if from_dtm:
+            raise ValueError("from_dtm is not available with array weather")
+        a = prepare_grid_inputs_array(micropoint, crows, ccols, reqhgt, vegp, soilc, dtm, lats=lats, lons=lons, pai_a=pai_a, out=out,
+                                      device=device, **ter)
+        coarse = api._coarse_spec(a["vegp"], a["climdata"], None, None, altcorrect, dtmc,
+                                  cleanvars(vegp, soilc, dtm["z"])[2] if altcorrect else None, refuse_missing=False)
+        extra = dict(array_forcing=True, coarse=coarse)
+    else:
+        a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device, from_dtm=from_dtm, **ter)
+        extra = {}
+        if from_dtm:
+            plan_kw["dtm"] = a.pop("dtm")
+    a["tfact"] = float(tfact)
+    kept = [n for n, o in zip(api._abi.OUT_NAMES, a.pop("out")) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
+    if not kept:
+        raise ValueError("none of the selected variables exists at this reqhgt")
+    sel = dict(points=cells if cells.size else None, zones=zones, vars=kept, stats=stats)
+    if plan_kw:      # missing terrain planes derived on the device: the plan API from here, as runmicro_summary's dtm route
+        nd = len(np.asarray(a["obstime"]["year"])) // 24
+        ring = max(1, min(nd, int(chunk_days) if chunk_days else 8))
+        with api.Plan(**a, out=[n in kept for n in api._abi.OUT_NAMES], ring_days=ring, device=device, **plan_kw) as p:
+            vs, ss = p.series_enable(**sel)
+            for d0 in range(0, nd, ring):
+                p.run_days(d0, min(ring, nd - d0), 0)
+                p.series_accumulate(0, 0, d0, min(ring, nd - d0))
+            res = {"points": {v: p.fetch_point_series(v) for v in vs} if cells.size else {},
+                   "zones": {v: {s: p.fetch_zone_series(v, s) for s in ss} for v in vs} if zones is not None else {}}
+    else:
+        res = api.runmicro_series(**a, **sel, chunk_days=chunk_days, device=device, **extra)
+    res["cells"] = cells
+    return res
+
+
 # ---- below ground at several depths from one solve ---------------------------------------------------------------------------------
 def _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, ter, device):
     """runmicro1Cpp's arguments at depths[0] with `depths` in place of reqhgt, and the point model's soil temperature at every
