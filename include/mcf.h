@@ -64,7 +64,10 @@ extern "C" {
                              *    mcf_plan_set_day_layers, mcf_snowrun_set_day_layers, mcf_plan_fetch_mxtc, mcf_plan_below_set_depths,
                              *    mcf_plan_fetch_depth*, mcf_plan_summary_enable_below, mcf_plan_summary_fetch_depth, mcf_runmicro_depths,
                              *    mcf_runmicro_depths_summary, mcf_plan_diag_enable_array, mcf_runmicro2_diag, mcf_runmicro4_diag,
-                             *    mcf_foliageden, mcf_foliageden_device, mcf_plan_set_height, mcf_plan_fetch_foliage, mcf_runmicro_heights) */
+                             *    mcf_foliageden, mcf_foliageden_device, mcf_plan_set_height, mcf_plan_fetch_foliage, mcf_runmicro_heights,
+                             *    mcf_plan_series_*, mcf_runmicro_series, mcf_zonal_series, mcf_series_state_merge, mcf_series_state_finish,
+                             *    mcf_runmicro_series_multi, mcf_runmicro_depths_series, mcf_snowplan_series_*, mcf_snowrun_series_*,
+                             *    mcf_runmicrosnow_series, mcf_snowmodel1_series) */
 
 /* Output variables, in the order of the reference's returned list
  * (src/microclimfCpp.cpp:2326-2335) and of its `out` logical(10). */
@@ -780,6 +783,54 @@ int mcf_runmicro_series(const mcf_grid_inputs *in, const mcf_options *opt, const
  * MCF_ZONAL_CPB = 16, 21, 32 or 42 overrides).  Refusals as for the enable, before a device is touched. */
 int mcf_zonal_series(const double *x, int64_t rows, int64_t cols, int64_t nsteps, const int32_t *zone, int32_t nzones,
                      const int32_t zstat[MCF_NZSTAT], int32_t device, double *const out[MCF_NZSTAT]);
+/* MCF_ZONAL_CPB = 0 takes another route to the same numbers: a column-major x[rows, cols, nsteps] IS step-major planes, so it
+ * goes up in pieces of whole days without re-tiling and is folded by the planes kernel (below), a last day shorter than 24
+ * steps included.  The default route does not change. */
+
+/* ---- series sink: further sources ----------------------------------------------------------------------------
+ * Everything of the block above holds unchanged for every source below: NaN skipped, !(|v| < 4096) BAD, the mean from the integer
+ * sum of rint(v * 2^24), minimum and maximum with + 0.0 applied, a bad value or n == 0 makes everything but COUNT NA_real_,
+ * steps never folded and steps behind the last whole day NA_real_ in every statistic (COUNT too), point series bit for bit.
+ *
+ * Row blocks.  The zone state of one (variable, zone, step) is four integers: S, the sum of rint(v * 2^24); a count word, its low
+ * half the values kept (n), its high half the bad ones; the minimum and the maximum as order-preserving keys.  The state of a
+ * raster cut into row blocks is the element-wise combination of the blocks' states: S adds, the count words add, the minimum
+ * keys take the minimum, the maximum keys the maximum.  All of it is integer, so the result has the bits of the one-block
+ * run, whatever the number of blocks or devices.  The finish (the divide and the NA rules) runs once, on the combined state.
+ * The 2^26-cell limit is tested on the whole raster.  A point belongs to the block that holds its row.  The caller's cells[]
+ * and zone[] are given for the whole raster (row + R * col; [R * cols], column-major); each block takes its rows of them.
+ * The combination is a host loop over the blocks' fetched states (a few MB); the two functions below are that loop and the
+ * finish, as pure host functions: state [4][nzones][steps] of int64 in the order S, count word, minimum key, maximum key
+ * (untouched: 0, 0, INT64_MAX, INT64_MIN; key of a value: its bits if they are >= 0 as int64, else bits ^ INT64_MAX).
+ * finish: out [nsteps, nzones], column-major; steps >= `steps`, and steps of days with day_done[day] == 0 (NULL: all done), NA. */
+int mcf_series_state_merge(int64_t *into, const int64_t *from, int32_t nzones, int64_t steps);
+int mcf_series_state_finish(const int64_t *state, int32_t nzones, int64_t steps, int64_t nsteps, const int32_t *day_done,
+                            int32_t zstat, double *out);
+/* The one-call form over row blocks on several devices from one process, as mcf_runmicro_summary_multi (vector forcing):
+ * bit for bit mcf_runmicro_series' results. */
+int mcf_runmicro_series_multi(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_series_spec *spec, int32_t chunk_days,
+                              const mcf_multi *multi, mcf_series_out *out);
+/* Below ground: the sink on a streamed below-ground plan (mcf_plan_create_streamed, reqhgt < 0), after
+ * mcf_plan_below_set_depths if there is a depth list.  spec->var may select Tz and soilm (MCF_ERR_ARG otherwise); Tz is kept per
+ * depth, soilm has depth 0 alone, as mcf_plan_summary_enable_below lays out its places.  mcf_plan_series_accumulate / _reset
+ * work on such a plan as above ground (the fold reads each depth's slab of the slot).  The whole-series plan (mcf_plan_create,
+ * reqhgt < 0) is refused (MCF_ERR_STATE), and mcf_plan_series_enable keeps refusing streamed and below-ground plans.
+ * fetch_*_depth: mcf_plan_series_fetch_* for one depth's Tz; with var = MCF_OUT_SOILM the depth must be 0; a depth outside the
+ * list is MCF_ERR_ARG. */
+int mcf_plan_series_enable_below(mcf_plan *plan, const mcf_series_spec *spec);
+int mcf_plan_series_fetch_points_depth(mcf_plan *plan, int32_t depth, int32_t var, double *dst);
+int mcf_plan_series_fetch_zones_depth(mcf_plan *plan, int32_t depth, int32_t var, int32_t zstat, double *dst);
+/* One call, host to host, as mcf_runmicro_depths_summary drives the plan.  tz_points[d] / soilm_points: [tsteps, npoints] when
+ * npoints > 0; tz_zones[d][s] / soilm_zones[s]: [tsteps, nzones] for every depth and selected statistic when nzones > 0 (a
+ * null one of a selected variable is MCF_ERR_ARG). */
+typedef struct mcf_depth_series_out {
+    double *tz_points[MCF_MAX_DEPTHS];
+    double *tz_zones[MCF_MAX_DEPTHS][MCF_NZSTAT];
+    double *soilm_points;
+    double *soilm_zones[MCF_NZSTAT];
+} mcf_depth_series_out;
+int mcf_runmicro_depths_series(const mcf_grid_inputs *in, const mcf_options *opt, const double *depths, int32_t ndepths,
+                               const double *tbp, const mcf_series_spec *spec, int32_t chunk_days, mcf_depth_series_out *out);
 
 /* ---- terrain pre-compute (the solver's terrain inputs, built on the device) ------
  * Restates the R-side arithmetic of the reference's marshaller (R/internal.R):
@@ -1258,6 +1309,61 @@ int mcf_runmicrosnow_summary(const mcf_microsnow_in *in, const mcf_options *opt,
  * names it). */
 int mcf_snowmodel1_summary(const mcf_snowdriver_in *in, const mcf_snowpack_summary_spec *spec, const mcf_multi *multi,
                            mcf_snowpack_summary_out *out);
+
+/* ---- series sink of the snow run and of the snowpack (definitions: "series sink" and "series sink: further sources" above;
+ * DESIGN.md §28) ------------------------------------------------------------------------------------------------------------
+ * Snowpack: the five series in mcf_snowdriver_out's order (Tc, Tg, groundsnowdepth, totalSWE, snowden; totalSWE after the
+ * redistribution), folded from a chunk's device series right after run_chunk — the values mcf_snowmodel1 copies to the host.
+ * The whole days of a folded chunk are done; days behind the last whole chunk are never folded (NA in every statistic).  A
+ * totalSWE of 4096 or more in its own unit falls under the BAD rule like any other value.
+ * Snow run, merged outputs: pass 2 folds every merged ring chunk.  A day in neither class (no-snow days and snow days are the
+ * run's two classes) is never folded: its steps are NA in every statistic, COUNT too.  reqhgt >= 0. */
+typedef struct mcf_snowpack_series_spec {      /* as mcf_series_spec, over the five snowpack series */
+    int64_t npoints;
+    const int64_t *cells;
+    int32_t nzones;
+    const int32_t *zone;
+    int32_t series[5];
+    int32_t zstat[MCF_NZSTAT];
+} mcf_snowpack_series_spec;
+typedef struct mcf_snowpack_series_out {
+    double *points[5];                 /* [tsteps, npoints] for every selected series when npoints > 0 */
+    double *zones[5][MCF_NZSTAT];      /* [tsteps, nzones] for every selected pair when nzones > 0     */
+} mcf_snowpack_series_out;
+/* The snow plan's sink.  enable: MCF_ERR_ARG, the message starting with the entry's name, for a null spec, an empty selection,
+ * nzones > MCF_MAX_ZONES, a label or cell out of range, more than 2^26 cells, chunk_steps that are not whole days;
+ * MCF_ERR_STATE when called twice.  accumulate(chunk): folds the series of the chunk run last, on the stream the model wrote
+ * them on; chunks may come in any order, each at most once (a second fold is MCF_ERR_STATE), and every selected series must have
+ * been written (mcf_snowplan_set_series): MCF_ERR_STATE otherwise.  fetch: [tsteps, npoints] / [tsteps, nzones], column-major.
+ * reset: nothing folded. */
+int mcf_snowplan_series_enable(mcf_snowplan *plan, const mcf_snowpack_series_spec *spec);
+int mcf_snowplan_series_accumulate(mcf_snowplan *plan, int32_t chunk);
+int mcf_snowplan_series_fetch_points(mcf_snowplan *plan, int32_t series, double *dst);
+int mcf_snowplan_series_fetch_zones(mcf_snowplan *plan, int32_t series, int32_t zstat, double *dst);
+int mcf_snowplan_series_reset(mcf_snowplan *plan);
+/* Switches the sinks of a run on, before mcf_snowrun_pass1 (MCF_ERR_STATE after it, or when called twice); either spec may be
+ * NULL, not both; both are given for the whole raster.  `micro` selects among the variables the run was created with.  May sit
+ * beside mcf_snowrun_summary_enable.  A reqhgt < 0 run is refused (MCF_ERR_ARG).  With a series enabled mcf_snowrun_pass2 accepts
+ * out == NULL or null arrays; mcf_snowrun_pass1 starts the series over (a second year on one handle).  The fetches combine the
+ * row blocks; pack = 0: variable `var` of the merged outputs (after pass 2), pack != 0: series `var` of the snowpack (after
+ * pass 1); MCF_ERR_STATE before that. */
+int mcf_snowrun_series_enable(mcf_snowrun *run, const mcf_series_spec *micro, const mcf_snowpack_series_spec *pack);
+int mcf_snowrun_series_fetch_points(mcf_snowrun *run, int32_t pack, int32_t var, double *dst);
+int mcf_snowrun_series_fetch_zones(mcf_snowrun *run, int32_t pack, int32_t var, int32_t zstat, double *dst);
+/* One call, as mcf_runmicrosnow_summary: data.frame weather with or without `multi`, array weather as one block. */
+typedef struct mcf_snowrun_series_out {
+    mcf_series_out micro;
+    mcf_snowpack_series_out pack;
+    mcf_outputs *arrays;
+    const mcf_snowdriver_out *smod;
+    int32_t *snowday, *nosnowday;
+} mcf_snowrun_series_out;
+int mcf_runmicrosnow_series(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi,
+                            const mcf_series_spec *micro_spec, const mcf_snowpack_series_spec *pack_spec,
+                            mcf_snowrun_series_out *outs);
+/* The snow model alone with the snowpack series sink and no series output, as mcf_snowmodel1_summary (`multi` may be NULL). */
+int mcf_snowmodel1_series(const mcf_snowdriver_in *in, const mcf_snowpack_series_spec *spec, const mcf_multi *multi,
+                          mcf_snowpack_series_out *out);
 
 /* applycpp3 (src/microclimfCpp.cpp:5553-5588; `.runmicrosnow1/2` use it on totalSWE, R/internal.R:3592-3593):
  * reduction of a [rows,cols,tsteps] array over space, per time step, skipping NA.  fun: 0 mean, 1 sum,

@@ -325,6 +325,29 @@ class MicrosnowCoarseIn(C.Structure):
                 ("micro_static", C.POINTER(SnowInputs)), ("mat", C.c_double)]
 
 
+class SnowpackSeriesSpec(C.Structure):
+    """include/mcf.h mcf_snowpack_series_spec (series in SNOWDRIVER_OUT's order)"""
+    _fields_ = [("npoints", C.c_int64), ("cells", C.POINTER(C.c_int64)), ("nzones", C.c_int32), ("zone", c_int32_p),
+                ("series", C.c_int32 * 5), ("zstat", C.c_int32 * NZSTAT)]
+
+
+class SnowpackSeriesOut(C.Structure):
+    """include/mcf.h mcf_snowpack_series_out"""
+    _fields_ = [("points", c_double_p * 5), ("zones", (c_double_p * NZSTAT) * 5)]
+
+
+class SnowrunSeriesOut(C.Structure):
+    """include/mcf.h mcf_snowrun_series_out"""
+    _fields_ = [("micro", SeriesOut), ("pack", SnowpackSeriesOut), ("arrays", C.POINTER(Outputs)), ("smod", C.POINTER(SnowDriverOut)),
+                ("snowday", c_int32_p), ("nosnowday", c_int32_p)]
+
+
+class DepthSeriesOut(C.Structure):
+    """include/mcf.h mcf_depth_series_out"""
+    _fields_ = [("tz_points", c_double_p * MAX_DEPTHS), ("tz_zones", (c_double_p * NZSTAT) * MAX_DEPTHS), ("soilm_points", c_double_p),
+                ("soilm_zones", c_double_p * NZSTAT)]
+
+
 class SnowrunSummaryOut(C.Structure):
     """include/mcf.h mcf_snowrun_summary_out"""
     _fields_ = [("micro", SummaryOut), ("pack", SnowpackSummaryOut), ("arrays", C.POINTER(Outputs)), ("smod", C.POINTER(SnowDriverOut)),
@@ -391,6 +414,11 @@ EXPORTS = (
     "mcf_selftest_step", "mcf_selftest_snow",
     "mcf_plan_series_enable", "mcf_plan_series_accumulate", "mcf_plan_series_fetch_points", "mcf_plan_series_fetch_zones",
     "mcf_plan_series_reset", "mcf_runmicro_series", "mcf_zonal_series",
+    "mcf_series_state_merge", "mcf_series_state_finish", "mcf_runmicro_series_multi", "mcf_plan_series_enable_below",
+    "mcf_plan_series_fetch_points_depth", "mcf_plan_series_fetch_zones_depth", "mcf_runmicro_depths_series",
+    "mcf_snowplan_series_enable", "mcf_snowplan_series_accumulate", "mcf_snowplan_series_fetch_points",
+    "mcf_snowplan_series_fetch_zones", "mcf_snowplan_series_reset", "mcf_snowrun_series_enable", "mcf_snowrun_series_fetch_points",
+    "mcf_snowrun_series_fetch_zones", "mcf_runmicrosnow_series", "mcf_snowmodel1_series",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -846,6 +874,43 @@ def load() -> C.CDLL:
         lib.mcf_runmicrosnow_summary.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), SS, PS, C.POINTER(SnowrunSummaryOut)]
         lib.mcf_snowmodel1_summary.restype = C.c_int
         lib.mcf_snowmodel1_summary.argtypes = [C.POINTER(SnowDriverIn), PS, C.POINTER(Multi), PO]
+    if hasattr(lib, "mcf_snowrun_series_enable"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        RS, ZS, ZO = C.POINTER(SeriesSpec), C.POINTER(SnowpackSeriesSpec), C.POINTER(SnowpackSeriesOut)
+        c_int64_p = C.POINTER(C.c_int64)
+        lib.mcf_series_state_merge.restype = C.c_int
+        lib.mcf_series_state_merge.argtypes = [c_int64_p, c_int64_p, C.c_int32, C.c_int64]
+        lib.mcf_series_state_finish.restype = C.c_int
+        lib.mcf_series_state_finish.argtypes = [c_int64_p, C.c_int32, C.c_int64, C.c_int64, c_int32_p, C.c_int32, c_double_p]
+        lib.mcf_runmicro_series_multi.restype = C.c_int
+        lib.mcf_runmicro_series_multi.argtypes = [GI, OP, RS, C.c_int32, C.POINTER(Multi), C.POINTER(SeriesOut)]
+        lib.mcf_plan_series_enable_below.restype = C.c_int
+        lib.mcf_plan_series_enable_below.argtypes = [P, RS]
+        lib.mcf_plan_series_fetch_points_depth.restype = C.c_int
+        lib.mcf_plan_series_fetch_points_depth.argtypes = [P, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_plan_series_fetch_zones_depth.restype = C.c_int
+        lib.mcf_plan_series_fetch_zones_depth.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_runmicro_depths_series.restype = C.c_int
+        lib.mcf_runmicro_depths_series.argtypes = [GI, OP, c_double_p, C.c_int32, c_double_p, RS, C.c_int32, C.POINTER(DepthSeriesOut)]
+        lib.mcf_snowplan_series_enable.restype = C.c_int
+        lib.mcf_snowplan_series_enable.argtypes = [P, ZS]
+        lib.mcf_snowplan_series_accumulate.restype = C.c_int
+        lib.mcf_snowplan_series_accumulate.argtypes = [P, C.c_int32]
+        lib.mcf_snowplan_series_fetch_points.restype = C.c_int
+        lib.mcf_snowplan_series_fetch_points.argtypes = [P, C.c_int32, c_double_p]
+        lib.mcf_snowplan_series_fetch_zones.restype = C.c_int
+        lib.mcf_snowplan_series_fetch_zones.argtypes = [P, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_snowplan_series_reset.restype = C.c_int
+        lib.mcf_snowplan_series_reset.argtypes = [P]
+        lib.mcf_snowrun_series_enable.restype = C.c_int
+        lib.mcf_snowrun_series_enable.argtypes = [P, RS, ZS]
+        lib.mcf_snowrun_series_fetch_points.restype = C.c_int
+        lib.mcf_snowrun_series_fetch_points.argtypes = [P, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_snowrun_series_fetch_zones.restype = C.c_int
+        lib.mcf_snowrun_series_fetch_zones.argtypes = [P, C.c_int32, C.c_int32, C.c_int32, c_double_p]
+        lib.mcf_runmicrosnow_series.restype = C.c_int
+        lib.mcf_runmicrosnow_series.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), RS, ZS, C.POINTER(SnowrunSeriesOut)]
+        lib.mcf_snowmodel1_series.restype = C.c_int
+        lib.mcf_snowmodel1_series.argtypes = [C.POINTER(SnowDriverIn), ZS, C.POINTER(Multi), ZO]
     if hasattr(lib, "mcf_runmicrosnow2_coarse"):     # (absent from an older library named by MCF_LIB for an A/B run)
         MC = C.POINTER(MicrosnowCoarseIn)
         lib.mcf_microsnow_expand_coarse_device.restype = C.c_int

@@ -115,14 +115,16 @@ def _names_to_indices(sel, names, what):
     return idx
 
 
-def series_spec(rows: int, cols: int, points=None, zones=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None):
+def series_spec(rows: int, cols: int, points=None, zones=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None,
+                *, struct=_abi.SeriesSpec, names=_abi.OUT_NAMES, field: str = "var"):
     """include/mcf.h mcf_series_spec: `points` 0-based cell indices row + rows * col (None: no points), `zones` a [rows, cols]
     integer array of labels (negative or masked: in no zone; None: no zones), `nzones` default the largest label + 1, `vars`
-    output names or indices, `stats` names of _abi.ZSTAT_NAMES or indices.
+    output names or indices, `stats` names of _abi.ZSTAT_NAMES or indices.  struct / names / field: another spec of the same
+    layout (mcf_snowpack_series_spec: its five series under "series").
     -> (spec, the selected variables' indices, the selected statistics' indices); the spec holds its arrays"""
-    vi = _names_to_indices(vars, _abi.OUT_NAMES, "series: variables")
+    vi = _names_to_indices(vars, names, "series: variables")
     si = _names_to_indices(stats, _abi.ZSTAT_NAMES, "series: statistics")
-    sp = _abi.SeriesSpec()
+    sp = struct()
     sp._owner = b = Buffers()
     if points is not None:
         cells = np.ascontiguousarray(np.asarray(points, dtype=np.int64)).ravel()
@@ -135,19 +137,19 @@ def series_spec(rows: int, cols: int, points=None, zones=None, vars=("Tz",), sta
         sp.nzones = int(nzones) if nzones is not None else int(lab.max()) + 1
         sp.zone = b.ptr(lab)
     for v in vi:
-        sp.var[v] = 1
+        getattr(sp, field)[v] = 1
     for k in si:
         sp.zstat[k] = 1
     return sp, vi, si
 
 
-def _series_sink(b: Buffers, tsteps: int, sp, vi, si, so=None, points=None, zones=None) -> dict:
+def _series_sink(b: Buffers, tsteps: int, sp, vi, si, so=None, points=None, zones=None, names=_abi.OUT_NAMES) -> dict:
     """The host side of a series sink: one [tsteps, npoints] array per selected variable and one [tsteps, nzones] array per
     selected (variable, statistic), held by `b`; their pointers go into `so` (mcf_series_out) or to points(v, pointer) /
     zones(v, k, pointer) -> {"points": {variable: array}, "zones": {variable: {statistic: array}}}"""
     res = {"points": {}, "zones": {}}
     for v in vi:
-        name = _abi.OUT_NAMES[v]
+        name = names[v]
         if sp.npoints > 0:
             res["points"][name], ptr = b.out((tsteps, int(sp.npoints)))
             if so is not None:
@@ -169,10 +171,11 @@ def runmicro_series(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: 
                     zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, points=None,
                     zones=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None, chunk_days: int = 0,
                     array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
-                    cells_per_block: int = 0) -> dict:
+                    cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> dict:
     """The hourly series at a few cells and per-step statistics over zones of the raster, accumulated on the device chunk by
     chunk (include/mcf.h "series sink", mcf_runmicro_series): runmicro_summary's argument lists; `points`, `zones`, `vars`,
-    `stats`, `nzones` as series_spec takes them.
+    `stats`, `nzones` as series_spec takes them.  `devices` / `n_blocks`: row blocks over several devices (vector forcing;
+    mcf_runmicro_series_multi), same bits.
     -> {"points": {variable: [tsteps, npoints]}, "zones": {variable: {statistic: [tsteps, nzones]}}}"""
     hgt = np.asarray(vegp["hgt"])
     sp, vi, si = series_spec(hgt.shape[0], hgt.shape[1], points, zones, vars, stats, nzones)
@@ -182,7 +185,12 @@ def runmicro_series(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: 
                 bool(array_forcing) or coarse is not None, device, 0, cells_per_block, dfsel, coarse)
     so = _abi.SeriesOut()
     res = _series_sink(m, m.tsteps, sp, vi, si, so)
-    _abi.check(lib.mcf_runmicro_series(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(so)))
+    mu = _abi.multi(devices, n_blocks)
+    if mu:
+        _abi.check(lib.mcf_runmicro_series_multi(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(mu[0]),
+                                                 C.byref(so)))
+    else:
+        _abi.check(lib.mcf_runmicro_series(C.byref(m.inputs), C.byref(m.options), C.byref(sp), int(chunk_days), C.byref(so)))
     return res
 
 
@@ -275,6 +283,43 @@ def runmicro_depths_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping
     res["days"] = sink(None, None, days=lambda ptr: setattr(so, "days", ptr))["days"]
     _abi.check(lib.mcf_runmicro_depths_summary(C.byref(m.inputs), C.byref(m.options), m.ptr(d), int(d.size), m.ptr(t), C.byref(sp),
                                                int(chunk_days), C.byref(so)))
+    return res
+
+
+def runmicro_depths_series(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths,
+                           zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *,
+                           points=None, zones=None, tbp=None, vars=("Tz",), stats=("mean", "min", "max"), nzones: int | None = None,
+                           chunk_days: int = 0, array_forcing: bool = False, dfsel: Mapping | None = None,
+                           coarse: Mapping | None = None, device: int = 0, cells_per_block: int = 0) -> dict:
+    """The series sink below ground at several depths (include/mcf.h mcf_runmicro_depths_series): runmicro_depths with each
+    chunk folded on the device as it is produced.  `vars` among Tz and soilm; `points`, `zones`, `stats`, `nzones` as
+    series_spec takes them.
+    -> {"Tz": [per depth {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}], "soilm": {...} (if selected),
+    "depths"}"""
+    lib = _abi.load()
+    hgt = np.asarray(vegp["hgt"])
+    sp, vi, si = series_spec(hgt.shape[0], hgt.shape[1], points, zones, vars, stats, nzones)
+    af = bool(array_forcing) or coarse is not None
+    T = len(np.asarray(obstime["year"]))
+    d, t = _depth_list(depths, tbp, T)
+    reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
+                [1, 0, 0, 1, 0, 0, 0, 0, 0, 0], af, device, 0, cells_per_block, dfsel, coarse)
+    so = _abi.DepthSeriesOut()
+    res = {"depths": d.copy()}
+
+    def sink(v, set_points, zrow):
+        """the arrays of one (variable, depth): {"points": ..., "zones": {statistic: ...}}"""
+        one = _series_sink(m, m.tsteps, sp, [v], si, points=lambda _v, ptr: set_points(ptr), zones=lambda _v, k, ptr: zrow.__setitem__(k, ptr))
+        name = _abi.OUT_NAMES[v]
+        return {"points": one["points"].get(name), "zones": one["zones"].get(name, {})}
+    tz, sm = _abi.OUT_NAMES.index("Tz"), _abi.OUT_NAMES.index("soilm")
+    if tz in vi:
+        res["Tz"] = [sink(tz, lambda ptr, i=i: so.tz_points.__setitem__(i, ptr), so.tz_zones[i]) for i in range(min(d.size, _abi.MAX_DEPTHS))]
+    if sm in vi:
+        res["soilm"] = sink(sm, lambda ptr: setattr(so, "soilm_points", ptr), so.soilm_zones)
+    _abi.check(lib.mcf_runmicro_depths_series(C.byref(m.inputs), C.byref(m.options), m.ptr(d), int(d.size), m.ptr(t), C.byref(sp),
+                                              int(chunk_days), C.byref(so)))
     return res
 
 
@@ -894,6 +939,30 @@ class Plan:
     def series_reset(self):
         """Back to the state of series_enable: nothing folded."""
         _abi.check(self._lib.mcf_plan_series_reset(self._p))
+
+    def series_enable_below(self, points=None, zones=None, vars=("Tz",), stats=("mean", "min", "max"), *, nzones=None):
+        """series_enable() for a streamed below-ground plan, after below_set_depths() if there is a list (include/mcf.h
+        mcf_plan_series_enable_below): `vars` among Tz and soilm, Tz kept per depth.  series_accumulate / series_reset work as
+        above ground; fetch_point_series_depth / fetch_zone_series_depth read the series."""
+        sp, vi, si = series_spec(self.rows, self.cols, points, zones, vars, stats, nzones)
+        _abi.check(self._lib.mcf_plan_series_enable_below(self._p, C.byref(sp)))
+        self._series_shape = (int(sp.npoints), int(sp.nzones))
+        return [_abi.OUT_NAMES[v] for v in vi], [_abi.ZSTAT_NAMES[k] for k in si]
+
+    def fetch_point_series_depth(self, depth: int, var) -> np.ndarray:
+        """fetch_point_series() of Tz at depth index `depth`; soilm has depth 0 alone"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        a, ptr = Buffers().out((self.tsteps, getattr(self, "_series_shape", (1, 1))[0]))
+        _abi.check(self._lib.mcf_plan_series_fetch_points_depth(self._p, int(depth), v, ptr))
+        return a
+
+    def fetch_zone_series_depth(self, depth: int, var, stat) -> np.ndarray:
+        """fetch_zone_series() of Tz at depth index `depth`; soilm has depth 0 alone"""
+        v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)
+        k = _abi.ZSTAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
+        a, ptr = Buffers().out((self.tsteps, getattr(self, "_series_shape", (1, 1))[1]))
+        _abi.check(self._lib.mcf_plan_series_fetch_zones_depth(self._p, int(depth), v, k, ptr))
+        return a
 
     def fetch(self, slot: int, var, step0: int, nsteps: int) -> np.ndarray:
         v = _abi.OUT_NAMES.index(var) if isinstance(var, str) else int(var)

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <future>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -26,6 +27,7 @@
 #include "mcf_nc4file.hpp"
 #include "mcf_rowblocks.hpp"
 #include "mcf_hiphost.hpp"
+#include "mcf_series_host.hpp"
 
 namespace {
 
@@ -150,6 +152,10 @@ struct mcf_plan {
     bool ser_on = false;
     int64_t ser_npoints = 0;
     int ser_nzones = 0, ser_nsel = 0, ser_workgroups = 0;
+    // mcf_plan_series_enable_below: the first ser_nmain places are the ring's selected variables, the places behind them Tz at
+    // depths 1 .. D - 1 (ser_nmain = ser_nsel everywhere else)
+    int ser_nmain = 0;
+    bool ser_below = false;
     int ser_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
     int ser_zstat[MCF_NZSTAT] = {};
     int64_t* d_ser_cells = nullptr;
@@ -2746,16 +2752,13 @@ static int series_workgroups(int device) {
     return n;
 }
 
-int mcf_plan_series_enable(mcf_plan* p, const mcf_series_spec* spec) {
-    const std::string who = "mcf_plan_series_enable";
-    if (!p || !spec) return fail(MCF_ERR_ARG, who + ": null argument");
-    if (p->bg_stream) return fail(MCF_ERR_ARG, who + ": the series sink is not available on a streamed plan");
-    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
+// the enable behind its checks; extra: places behind the selected variables' (below ground: Tz at depths 1 .. D - 1)
+static int series_enable_checked(const std::string& who, mcf_plan* p, const mcf_series_spec* spec, int extra) {
     if (p->ser_on) return fail(MCF_ERR_STATE, who + ": the series sink is already enabled on this plan");
     int rc = check_series_spec(who, spec, p->rows, p->cols, p->var_slot);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    int nsel = 0;
+    int nsel = extra;
     for (int v = 0; v < MCF_NOUT; ++v) nsel += spec->var[v] ? 1 : 0;
     const int64_t np = spec->npoints, nz = spec->nzones, steps = (int64_t)p->ndays * 24, T = std::max<int64_t>(p->tsteps, 1);
     const int64_t point_bytes = nsel * np * T * 8, state_bytes = nsel * mcf::kSeriesRows * nz * steps * 8;
@@ -2773,13 +2776,39 @@ int mcf_plan_series_enable(mcf_plan* p, const mcf_series_spec* spec) {
         if ((rc = p->dev.make(&p->d_ser_plane, nz * T))) return rc;
         if ((rc = p->dev.make(&p->d_ser_done, std::max(p->ndays, 1)))) return rc;
     }
-    p->ser_npoints = np; p->ser_nzones = (int)nz; p->ser_nsel = nsel;
+    p->ser_npoints = np; p->ser_nzones = (int)nz; p->ser_nsel = nsel; p->ser_nmain = nsel - extra;
     p->ser_workgroups = series_workgroups(p->device);
     int place = 0;
     for (int v = 0; v < MCF_NOUT; ++v) p->ser_sel1[v] = spec->var[v] ? ++place : 0;
     for (int k = 0; k < MCF_NZSTAT; ++k) p->ser_zstat[k] = nz > 0 && spec->zstat[k] ? 1 : 0;
     p->ser_on = true;
     return mcf_plan_series_reset(p);
+}
+
+int mcf_plan_series_enable(mcf_plan* p, const mcf_series_spec* spec) {
+    const std::string who = "mcf_plan_series_enable";
+    if (!p || !spec) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (p->bg_stream) return fail(MCF_ERR_ARG, who + ": the series sink is not available on a streamed plan");
+    if (p->bg || p->opt.reqhgt < 0.0 || !p->tiled) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
+    return series_enable_checked(who, p, spec, 0);
+}
+
+// below ground Tz and soilm alone have a series (the streamed plan's other outputs are not made)
+static int check_series_below_vars(const std::string& who, const mcf_series_spec* s) {
+    for (int v = 0; s && v < MCF_NOUT; ++v)
+        if (s->var[v] && v != MCF_OUT_TZ && v != MCF_OUT_SOILM)
+            return fail(MCF_ERR_ARG, who + ": below ground Tz and soilm have a series, nothing else");
+    return MCF_OK;
+}
+int mcf_plan_series_enable_below(mcf_plan* p, const mcf_series_spec* spec) {
+    const std::string who = "mcf_plan_series_enable_below";
+    if (!p || !spec) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (!p->bg_stream || !p->tiled) return fail(MCF_ERR_STATE, who + " needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
+    if (const int rc = check_series_below_vars(who, spec)) return rc;
+    const int D = std::max<int>(1, (int)p->depths.size());
+    if (const int rc = series_enable_checked(who, p, spec, spec->var[MCF_OUT_TZ] ? D - 1 : 0)) return rc;
+    p->ser_below = true;
+    return MCF_OK;
 }
 
 int mcf_plan_series_reset(mcf_plan* p) {
@@ -2809,18 +2838,25 @@ int mcf_plan_series_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int
         mcf::SeriesPointsArgs a{};
         for (int v = 0; v < MCF_NOUT; ++v)
             if (p->ser_sel1[v]) a.src[p->ser_sel1[v] - 1] = ring_view(p, slot, v);
-        a.nsel = p->ser_nsel;
+        a.nsel = p->ser_nmain;
         a.step0 = (int64_t)slot_day0 * 24; a.nsteps = (int64_t)ndays * 24;
         a.cells = p->d_ser_cells; a.ncells = p->ser_npoints;
         a.dst = p->d_ser_points; a.dst_steps = std::max<int64_t>(p->tsteps, 1); a.dst_step0 = (int64_t)day0 * 24;
         mcf::launch_series_points(a, p->stream);
+        // below ground: Tz at depths 1 .. D - 1, each one variable of its own slab beside the ring
+        for (int d = 1; d <= p->ser_nsel - p->ser_nmain; ++d) {
+            a.src[0] = depth_view(p, slot, d);
+            a.nsel = 1;
+            a.dst = p->d_ser_points + (int64_t)(p->ser_nmain + d - 1) * p->ser_npoints * a.dst_steps;
+            mcf::launch_series_points(a, p->stream);
+        }
     }
     if (p->ser_nzones > 0) {
         mcf::SeriesZonesArgs a{};
         a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
         a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
         a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
-        a.nsel = p->ser_nsel;
+        a.nsel = p->ser_nmain;
         for (int v = 0; v < MCF_NOUT; ++v)
             if (p->ser_sel1[v]) a.slab[p->ser_sel1[v] - 1] = p->var_slot[v];
         a.zone = p->d_ser_zone; a.nzones = p->ser_nzones;
@@ -2828,51 +2864,129 @@ int mcf_plan_series_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int
         a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
         a.state = p->d_ser_state;
         mcf::launch_series_zones(a, p->ser_workgroups, p->stream);
+        for (int d = 1; d <= p->ser_nsel - p->ser_nmain; ++d) {      // (the existing kernel serves: only the view changes)
+            const mcf::RingView v = depth_view(p, slot, d);
+            a.ring = v.base; a.tile_stride = v.tile_stride; a.day_stride = v.day_stride; a.var_stride = 0;
+            a.nsel = 1; a.slab[0] = 0;
+            a.state = p->d_ser_state + (int64_t)(p->ser_nmain + d - 1) * mcf::kSeriesRows * p->ser_nzones * a.steps;
+            mcf::launch_series_zones(a, p->ser_workgroups, p->stream);
+        }
     }
     HIP_TRY(hipGetLastError());
     for (int d = day0; d < day0 + ndays; ++d) p->ser_done[(size_t)d] = 1;
     return MCF_OK;
 }
 
-int mcf_plan_series_fetch_points(mcf_plan* p, int32_t var, double* dst) {
-    if (!p || !dst) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: null argument");
-    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+// the place of (variable, depth) in the point buffer and the zone state: the variable's own, or (below ground) that of Tz at a
+// depth behind the first; -1 with the error set
+static int series_place(const std::string& who, mcf_plan* p, int32_t var, int32_t depth) {
     if (var < 0 || var >= MCF_NOUT || !p->ser_sel1[var])
-        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: variable was not selected in mcf_plan_series_enable");
-    if (p->ser_npoints == 0) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_points: no points were selected in mcf_plan_series_enable");
+        return fail(MCF_ERR_ARG, who + ": variable was not selected in mcf_plan_series_enable"), -1;
+    if (depth < 0 || depth > (var == MCF_OUT_TZ ? p->ser_nsel - p->ser_nmain : 0))
+        return fail(MCF_ERR_ARG, var == MCF_OUT_TZ ? who + ": depth " + std::to_string(depth) + " is outside the plan's list"
+                                                   : who + ": only Tz is kept per depth (depth 0 for soilm)"), -1;
+    return depth == 0 ? p->ser_sel1[var] - 1 : p->ser_nmain + depth - 1;
+}
+static int series_fetch_points(const std::string& who, mcf_plan* p, int32_t depth, int32_t var, double* dst) {
+    if (!p || !dst) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
+    const int place = series_place(who, p, var, depth);
+    if (place < 0) return MCF_ERR_ARG;
+    if (p->ser_npoints == 0) return fail(MCF_ERR_ARG, who + ": no points were selected in mcf_plan_series_enable");
     HIP_TRY(hipSetDevice(p->device));
     const int64_t n = p->ser_npoints * std::max<int64_t>(p->tsteps, 1);
-    HIP_TRY(p->tohost.dense(dst, p->d_ser_points + (int64_t)(p->ser_sel1[var] - 1) * n, (size_t)n * 8, p->stream));
+    HIP_TRY(p->tohost.dense(dst, p->d_ser_points + (int64_t)place * n, (size_t)n * 8, p->stream));
     return MCF_OK;
 }
+int mcf_plan_series_fetch_points(mcf_plan* p, int32_t var, double* dst) {
+    return series_fetch_points("mcf_plan_series_fetch_points", p, 0, var, dst);
+}
+int mcf_plan_series_fetch_points_depth(mcf_plan* p, int32_t depth, int32_t var, double* dst) {
+    if (p && !p->ser_below)
+        return fail(MCF_ERR_STATE, "mcf_plan_series_fetch_points_depth: the plan has no below-ground series sink (mcf_plan_series_enable_below)");
+    return series_fetch_points("mcf_plan_series_fetch_points_depth", p, depth, var, dst);
+}
 
-int mcf_plan_series_fetch_zones(mcf_plan* p, int32_t var, int32_t zstat, double* dst) {
-    if (!p || !dst) return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: null argument");
+static int series_fetch_zones(const std::string& who, mcf_plan* p, int32_t depth, int32_t var, int32_t zstat, double* dst) {
+    if (!p || !dst) return fail(MCF_ERR_ARG, who + ": null argument");
     if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
-    if (var < 0 || var >= MCF_NOUT || !p->ser_sel1[var])
-        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: variable was not selected in mcf_plan_series_enable");
+    const int place = series_place(who, p, var, depth);
+    if (place < 0) return MCF_ERR_ARG;
     if (zstat < 0 || zstat >= MCF_NZSTAT || !p->ser_zstat[zstat])
-        return fail(MCF_ERR_ARG, "mcf_plan_series_fetch_zones: statistic was not selected in mcf_plan_series_enable");
+        return fail(MCF_ERR_ARG, who + ": statistic was not selected in mcf_plan_series_enable");
     HIP_TRY(hipSetDevice(p->device));
     const int64_t steps = (int64_t)p->ndays * 24, T = std::max<int64_t>(p->tsteps, 1);
     HIP_TRY(hipMemcpyAsync(p->d_ser_done, p->ser_done.data(), (size_t)std::max(p->ndays, 1) * 4, hipMemcpyHostToDevice, p->stream));
-    mcf::launch_series_fin(p->d_ser_state + (int64_t)(p->ser_sel1[var] - 1) * mcf::kSeriesRows * p->ser_nzones * steps, p->ser_nzones,
+    mcf::launch_series_fin(p->d_ser_state + (int64_t)place * mcf::kSeriesRows * p->ser_nzones * steps, p->ser_nzones,
                            steps, T, p->d_ser_done, zstat, p->d_ser_plane, p->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(p->tohost.dense(dst, p->d_ser_plane, (size_t)(T * p->ser_nzones) * 8, p->stream));
     return MCF_OK;
 }
+int mcf_plan_series_fetch_zones(mcf_plan* p, int32_t var, int32_t zstat, double* dst) {
+    return series_fetch_zones("mcf_plan_series_fetch_zones", p, 0, var, zstat, dst);
+}
+int mcf_plan_series_fetch_zones_depth(mcf_plan* p, int32_t depth, int32_t var, int32_t zstat, double* dst) {
+    if (p && !p->ser_below)
+        return fail(MCF_ERR_STATE, "mcf_plan_series_fetch_zones_depth: the plan has no below-ground series sink (mcf_plan_series_enable_below)");
+    return series_fetch_zones("mcf_plan_series_fetch_zones_depth", p, depth, var, zstat, dst);
+}
 
-int mcf_runmicro_series(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_series_spec* spec, int32_t chunk_days,
-                        mcf_series_out* out) {
-    const std::string who = "mcf_runmicro_series";
-    if (!spec || !out) return fail(MCF_ERR_ARG, who + ": null argument");
+// the combination of row blocks and the finish, on the host (include/mcf.h "Row blocks"; mcf_series_host.hpp)
+int mcf_series_state_merge(int64_t* into, const int64_t* from, int32_t nzones, int64_t steps) {
+    if (!into || !from || nzones < 0 || steps < 0) return fail(MCF_ERR_ARG, "mcf_series_state_merge: null or negative argument");
+    mcf::series_state_merge(into, from, nzones, steps);
+    return MCF_OK;
+}
+int mcf_series_state_finish(const int64_t* state, int32_t nzones, int64_t steps, int64_t nsteps, const int32_t* day_done,
+                            int32_t zstat, double* out) {
+    if (!state || !out || nzones < 0 || steps < 0 || nsteps < 0 || steps % 24) return fail(MCF_ERR_ARG, "mcf_series_state_finish: bad argument");
+    if (zstat < 0 || zstat >= MCF_NZSTAT) return fail(MCF_ERR_ARG, "mcf_series_state_finish: statistic out of range");
+    mcf::series_state_finish(state, nzones, steps, nsteps, day_done, zstat, out);
+    return MCF_OK;
+}
+
+}  // extern "C"
+namespace mcf {   // mcf_snowrun.hip: the snow run's series over row blocks
+// what mcf_series_spec can be refused for without a plan; out_mask: the variables a run was created with (null: any)
+int series_spec_check(const std::string& who, const mcf_series_spec* s, int64_t rows, int64_t cols, const int32_t* out_mask) {
+    int requested[MCF_NOUT];
+    for (int v = 0; v < MCF_NOUT; ++v) requested[v] = !out_mask || out_mask[v] ? 0 : -1;
+    return check_series_spec(who, s, rows, cols, requested);
+}
+// a plan's raw zone state of one variable, [4][nzones][whole days x 24] of int64, and its folded days [days] (either may be
+// null), behind everything on the plan's stream
+int plan_series_state(mcf_plan* p, int32_t var, int64_t* host_state, int32_t* day_done) {
+    if (!p || !p->ser_on || var < 0 || var >= MCF_NOUT || !p->ser_sel1[var] || p->ser_nzones == 0)
+        return fail(MCF_ERR_STATE, "plan: no zone state of this variable");
+    HIP_TRY(hipSetDevice(p->device));
+    const int64_t n = (int64_t)kSeriesRows * p->ser_nzones * p->ndays * 24;
+    if (host_state && n > 0)
+        HIP_TRY(hipMemcpyAsync(host_state, p->d_ser_state + (int64_t)(p->ser_sel1[var] - 1) * n, (size_t)n * 8, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (day_done) std::copy(p->ser_done.begin(), p->ser_done.begin() + p->ndays, day_done);
+    return MCF_OK;
+}
+}  // namespace mcf
+extern "C" {
+
+// a row block's results on their way to the combination (mcf_runmicro_series_multi): per selected variable the points'
+// [tsteps, block's points] and the raw zone state; the folded days
+struct SeriesRaw {
+    std::vector<double> points[MCF_NOUT];
+    std::vector<int64_t> state[MCF_NOUT];
+    std::vector<int32_t> done;
+};
+// twi_mean / raw: a row block of a taller raster (mcf_runmicro_series_multi) — the results stay raw, `out` is not read
+static int run_series(const std::string& who, const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_series_spec* spec,
+                      int32_t chunk_days, mcf_series_out* out, const double* twi_mean = nullptr, SeriesRaw* raw = nullptr) {
+    if (!spec || (!out && !raw)) return fail(MCF_ERR_ARG, who + ": null argument");
     int rc = check_inputs(in, opt_in);
     if (rc) return rc;
     if (opt_in->reqhgt < 0.0) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, who + ": negative chunk_days");
     if ((rc = check_series_spec(who, spec, in->rows, in->cols, nullptr))) return rc;
-    for (int v = 0; v < MCF_NOUT; ++v) {
+    for (int v = 0; v < MCF_NOUT && !raw; ++v) {
         if (!spec->var[v]) continue;
         if (spec->npoints > 0 && !out->points[v]) return fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
         for (int k = 0; k < MCF_NZSTAT; ++k)
@@ -2892,15 +3006,73 @@ int mcf_runmicro_series(const mcf_grid_inputs* in, const mcf_options* opt_in, co
     mcf_plan* p = nullptr;
     if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
     PlanHolder holder(p);
+    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
     if ((rc = mcf_plan_series_enable(p, spec))) return rc;
     if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return mcf_plan_series_accumulate(p, 0, 0, d0, nd); }))) return rc;
+    const int64_t T = std::max<int64_t>(in->tsteps, 1);
     for (int v = 0; v < MCF_NOUT; ++v) {
         if (!spec->var[v]) continue;
+        if (raw) {
+            if (spec->npoints > 0) {
+                raw->points[v].resize((size_t)(T * spec->npoints));
+                if ((rc = mcf_plan_series_fetch_points(p, v, raw->points[v].data()))) return rc;
+            }
+            if (spec->nzones > 0) {
+                raw->state[v].resize((size_t)((int64_t)mcf::kSeriesRows * spec->nzones * ndays * 24));
+                raw->done.assign((size_t)std::max(ndays, 1), 0);
+                if ((rc = mcf::plan_series_state(p, v, raw->state[v].data(), raw->done.data()))) return rc;
+            }
+            continue;
+        }
         if (spec->npoints > 0 && (rc = mcf_plan_series_fetch_points(p, v, out->points[v]))) return rc;
         for (int k = 0; k < MCF_NZSTAT; ++k)
             if (spec->nzones > 0 && spec->zstat[k] && (rc = mcf_plan_series_fetch_zones(p, v, k, out->zones[v][k]))) return rc;
     }
     return mcf_plan_sync(p);
+}
+int mcf_runmicro_series(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_series_spec* spec, int32_t chunk_days,
+                        mcf_series_out* out) {
+    return run_series("mcf_runmicro_series", in, opt, spec, chunk_days, out);
+}
+
+// MCF_ZONAL_CPB = 0: a column-major x[rows, cols, nsteps] IS step-major planes, so it goes up in pieces of whole days as it lies
+// and k_series_planes folds it (the last piece may end in a day shorter than 24 steps)
+static int zonal_series_planes(const double* x, int64_t N, int64_t nsteps, const int32_t* zone, int32_t nzones, const int32_t* zstat,
+                               int32_t device, double* const* out) {
+    int rc;
+    const int64_t ndays = (nsteps + 23) / 24, steps = ndays * 24;
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(ndays, (int64_t)(1e9 / (8.0 * 24.0 * (double)N))));
+    mcf::DevOwner own;
+    double *d_lin = nullptr, *d_plane = nullptr;
+    int32_t* d_zone = nullptr;
+    long long* d_state = nullptr;
+    if ((rc = own.make(&d_lin, N * 24 * chunk))) return rc;
+    if ((rc = own.make(&d_plane, nsteps * nzones))) return rc;
+    if ((rc = own.make(&d_state, mcf::kSeriesRows * (int64_t)nzones * steps))) return rc;
+    if ((rc = own.up(const_cast<const int32_t**>(&d_zone), zone, N, "zone"))) return rc;
+    hipStream_t s = nullptr;
+    mcf::launch_series_init(d_state, 1, nzones, steps, s);
+    const int workgroups = series_workgroups(device);
+    for (int64_t d0 = 0; d0 < ndays; d0 += chunk) {
+        const int64_t nd = std::min(chunk, ndays - d0), ns = std::min(nd * 24, nsteps - d0 * 24);
+        HIP_TRY(hipMemcpyAsync(d_lin, x + N * d0 * 24, (size_t)(N * ns) * 8, hipMemcpyHostToDevice, s));
+        mcf::SeriesPlanesArgs a{};
+        a.series[0] = d_lin; a.N = N; a.nsel = 1;
+        a.zone = d_zone; a.nzones = nzones; a.steps = steps; a.nsteps = ns;
+        a.day0 = (int)d0; a.ndays = (int)nd;
+        a.state = d_state;
+        mcf::launch_series_planes(a, workgroups, s);
+        HIP_TRY(hipGetLastError());
+    }
+    mcf::ToHost tohost;
+    for (int k = 0; k < MCF_NZSTAT; ++k) {
+        if (!zstat[k]) continue;
+        mcf::launch_series_fin(d_state, nzones, steps, nsteps, nullptr, k, d_plane, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(tohost.dense(out[k], d_plane, (size_t)(nsteps * nzones) * 8));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return MCF_OK;
 }
 
 int mcf_zonal_series(const double* x, int64_t rows, int64_t cols, int64_t nsteps, const int32_t* zone, int32_t nzones,
@@ -2918,9 +3090,11 @@ int mcf_zonal_series(const double* x, int64_t rows, int64_t cols, int64_t nsteps
     int cpb = 32;
     if (const char* e = getenv("MCF_ZONAL_CPB")) {
         cpb = atoi(e);
-        if (!(cpb == 16 || cpb == 21 || cpb == 32 || cpb == 42)) return fail(MCF_ERR_ARG, who + ": MCF_ZONAL_CPB must be 16, 21, 32 or 42");
+        if (!(cpb == 0 || cpb == 16 || cpb == 21 || cpb == 32 || cpb == 42))
+            return fail(MCF_ERR_ARG, who + ": MCF_ZONAL_CPB must be 0, 16, 21, 32 or 42");
     }
     if ((rc = ensure_device(device))) return rc;
+    if (cpb == 0) return zonal_series_planes(x, N, nsteps, zone, nzones, zstat, device, out);
     const int64_t ndays = (nsteps + 23) / 24, steps = ndays * 24, ntiles = (N + cpb - 1) / cpb, B = mcf::ring_block_doubles(cpb);
     // pieces of whole days: about 1 GB of staging (the array's steps as they lie, and their tiled copy)
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ndays, 2730), (int64_t)(1e9 / (8.0 * (24.0 * N + (double)ntiles * B)))));
@@ -3064,12 +3238,18 @@ static int bioclim_depths_finish(mcf_plan* p, const mcf_grid_inputs* in, const B
     return mcf_plan_sync(p);
 }
 
-// the one-call entries: `out` (every step of every depth), `spec` + `sout` (the period summaries) or `bio` (the bioclim variables)
+// the series sink's arguments (mcf_runmicro_depths_series)
+struct SeriesDepthsSink {
+    const mcf_series_spec* spec;
+    mcf_depth_series_out* out;
+};
+// the one-call entries: `out` (every step of every depth), `spec` + `sout` (the period summaries), `bio` (the bioclim variables)
+// or `ser` (the series sink)
 static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
                       const double* tbp, mcf_depth_outputs* out, const mcf_summary_spec* spec, int32_t chunk_days,
-                      mcf_depth_summary_out* sout, const BioDepthsSink* bio = nullptr) {
+                      mcf_depth_summary_out* sout, const BioDepthsSink* bio = nullptr, const SeriesDepthsSink* ser = nullptr) {
     const std::string w = std::string(who) + ": ";
-    if (!in || !opt_in || (!out && !sout && !bio) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
+    if (!in || !opt_in || (!out && !sout && !bio && !ser) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
     mcf_options opt = *opt_in;
     if (bio) opt.complete = 1;                                          // cpp:3576: complete = true
     int rc = check_depths(who, depths, D, tbp, opt.complete != 0, in->array_forcing != 0);
@@ -3089,6 +3269,21 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
             if (!out->tz[d]) return fail(MCF_ERR_ARG, w + "tz[" + std::to_string(d) + "] is a null buffer");
         opt.out[MCF_OUT_TZ] = 1;
         opt.out[MCF_OUT_SOILM] = out->soilm ? 1 : 0;
+    } else if (ser) {      // (mcf_runmicro_depths_series has judged the spec)
+        for (int d = 0; ser->spec->var[MCF_OUT_TZ] && d < D; ++d) {
+            if (ser->spec->npoints > 0 && !ser->out->tz_points[d]) return fail(MCF_ERR_ARG, w + "a depth has a null point buffer");
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (ser->spec->nzones > 0 && ser->spec->zstat[k] && !ser->out->tz_zones[d][k])
+                    return fail(MCF_ERR_ARG, w + "a selected (depth, statistic) has a null buffer");
+        }
+        if (ser->spec->var[MCF_OUT_SOILM]) {
+            if (ser->spec->npoints > 0 && !ser->out->soilm_points) return fail(MCF_ERR_ARG, w + "soilm has a null point buffer");
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (ser->spec->nzones > 0 && ser->spec->zstat[k] && !ser->out->soilm_zones[k])
+                    return fail(MCF_ERR_ARG, w + "a selected statistic of soilm has a null buffer");
+        }
+        opt.out[MCF_OUT_TZ] = 1;
+        opt.out[MCF_OUT_SOILM] = ser->spec->var[MCF_OUT_SOILM] ? 1 : 0;
     } else {
         if ((rc = check_summary_below_vars(who, spec))) return rc;
         if ((rc = check_summary_spec(spec, ndays, nullptr))) return rc;
@@ -3117,11 +3312,13 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
     if ((rc = mcf_plan_below_prepare(p, in))) return rc;
     if (sout && (rc = mcf_plan_summary_enable_below(p, spec))) return rc;
+    if (ser && (rc = mcf_plan_series_enable_below(p, ser->spec))) return rc;
     mcf::BioAccDepthsArgs acc{};
     if (bio && (rc = bioclim_depths_begin(p, bio->sel, acc))) return rc;
     const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
     rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
         if (sout) return mcf_plan_summary_accumulate(p, 0, 0, d0, nd);
+        if (ser) return mcf_plan_series_accumulate(p, 0, 0, d0, nd);
         if (bio) {
             ++g_bioclim_chunks;
             return bioclim_depths_fold(p, bio->sel, acc, d0, nd);
@@ -3145,6 +3342,20 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
         if (sout->days && (rc = mcf_plan_summary_days(p, sout->days))) return rc;
         return mcf_plan_sync(p);
     }
+    if (ser) {
+        const mcf_series_spec* sp = ser->spec;
+        for (int d = 0; sp->var[MCF_OUT_TZ] && d < D; ++d) {
+            if (sp->npoints > 0 && (rc = mcf_plan_series_fetch_points_depth(p, d, MCF_OUT_TZ, ser->out->tz_points[d]))) return rc;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (sp->nzones > 0 && sp->zstat[k] && (rc = mcf_plan_series_fetch_zones_depth(p, d, MCF_OUT_TZ, k, ser->out->tz_zones[d][k]))) return rc;
+        }
+        if (sp->var[MCF_OUT_SOILM]) {
+            if (sp->npoints > 0 && (rc = mcf_plan_series_fetch_points_depth(p, 0, MCF_OUT_SOILM, ser->out->soilm_points))) return rc;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (sp->nzones > 0 && sp->zstat[k] && (rc = mcf_plan_series_fetch_zones_depth(p, 0, MCF_OUT_SOILM, k, ser->out->soilm_zones[k]))) return rc;
+        }
+        return mcf_plan_sync(p);
+    }
     if (out->soilm) fill_tail_na(out->soilm, in, ndays);
     return mcf_plan_sync(p);
 }
@@ -3157,6 +3368,18 @@ int mcf_runmicro_depths_summary(const mcf_grid_inputs* in, const mcf_options* op
                                 const double* tbp, const mcf_summary_spec* spec, int32_t chunk_days, mcf_depth_summary_out* out) {
     if (!out || !spec) return fail(MCF_ERR_ARG, "mcf_runmicro_depths_summary: null argument");
     return run_depths("mcf_runmicro_depths_summary", in, opt, depths, ndepths, tbp, nullptr, spec, chunk_days, out);
+}
+
+int mcf_runmicro_depths_series(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths,
+                               const double* tbp, const mcf_series_spec* spec, int32_t chunk_days, mcf_depth_series_out* out) {
+    const std::string who = "mcf_runmicro_depths_series";
+    if (!spec) return fail(MCF_ERR_ARG, who + ": null mcf_series_spec");
+    if (!out || !in) return fail(MCF_ERR_ARG, who + ": null argument");
+    int rc = check_series_spec(who, spec, in->rows, in->cols, nullptr);      // (nothing here needs a device)
+    if (!rc) rc = check_series_below_vars(who, spec);
+    if (rc) return rc;
+    const SeriesDepthsSink ser{spec, out};
+    return run_depths("mcf_runmicro_depths_series", in, opt, depths, ndepths, tbp, nullptr, nullptr, chunk_days, nullptr, nullptr, &ser);
 }
 
 // the bioclim sink on that driver (include/mcf.h); layered vegetation as run_bioclim takes it
@@ -3514,6 +3737,58 @@ int mcf_runmicro_summary_multi(const mcf_grid_inputs* in, const mcf_options* opt
         if (r0 != 0) so.days = nullptr;      // (the same for every block: the first one reports them)
         return run_summary(&sub, &o, spec, chunk_days, &so, twi_mean, pitch);
     });
+}
+
+// the series sink over row blocks: each block folds its rows of the spec; the points go to their places in the caller's list,
+// the blocks' zone states are combined and finished on the host (mcf_series_host.hpp)
+int mcf_runmicro_series_multi(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_series_spec* spec, int32_t chunk_days,
+                              const mcf_multi* mu, mcf_series_out* out) {
+    const std::string who = "mcf_runmicro_series_multi";
+    if (!spec) return fail(MCF_ERR_ARG, who + ": null mcf_series_spec");
+    if (!out || !in || !opt) return fail(MCF_ERR_ARG, who + ": null argument");
+    if (in->array_forcing != 0) return fail(MCF_ERR_ARG, who + " takes vector forcing (array_forcing = 0)");
+    if (opt->reqhgt < 0.0) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
+    if (chunk_days < 0) return fail(MCF_ERR_ARG, who + ": negative chunk_days");
+    int rc = check_series_spec(who, spec, in->rows, in->cols, nullptr);
+    if (rc) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!spec->var[v]) continue;
+        if (spec->npoints > 0 && !out->points[v]) return fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (spec->nzones > 0 && spec->zstat[k] && !out->zones[v][k])
+                return fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
+    }
+    struct BlockResult { mcf::SeriesBlockCut cut; SeriesRaw raw; };
+    std::vector<std::unique_ptr<BlockResult>> results;
+    std::mutex results_lock;
+    rc = for_row_blocks(in, opt, mu, [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int) {
+        auto res = std::make_unique<BlockResult>();
+        res->cut.cut(spec->npoints, spec->cells, spec->nzones, spec->zone, in->rows, in->cols, r0, sub.rows);
+        if (res->cut.empty(spec->nzones)) return (int)MCF_OK;      // none of the points lies in this block, and there are no zones
+        mcf_series_spec bs = *spec;
+        bs.npoints = (int64_t)res->cut.cells.size(); bs.cells = res->cut.cells.data(); bs.zone = res->cut.zone.data();
+        const int rcb = run_series(who, &sub, &o, &bs, chunk_days, nullptr, twi_mean, &res->raw);
+        if (rcb) return rcb;
+        std::lock_guard<std::mutex> hold(results_lock);
+        results.push_back(std::move(res));
+        return (int)MCF_OK;
+    });
+    if (rc) return rc;
+    const int64_t T = std::max<int64_t>(in->tsteps, 1), steps = in->tsteps / 24 * 24;
+    std::vector<int64_t> state;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!spec->var[v]) continue;
+        for (const auto& res : results)
+            for (size_t i = 0; i < res->cut.where.size(); ++i)
+                memcpy(out->points[v] + res->cut.where[i] * T, res->raw.points[v].data() + (int64_t)i * T, (size_t)T * 8);
+        if (spec->nzones == 0) continue;
+        state.resize((size_t)((int64_t)mcf::kSeriesStateRows * spec->nzones * steps));
+        mcf::series_state_init(state.data(), spec->nzones, steps);
+        for (const auto& res : results) mcf::series_state_merge(state.data(), res->raw.state[v].data(), spec->nzones, steps);
+        for (int k = 0; k < MCF_NZSTAT; ++k)      // (every block has folded every whole day)
+            if (spec->zstat[k]) mcf::series_state_finish(state.data(), spec->nzones, steps, T, nullptr, k, out->zones[v][k]);
+    }
+    return MCF_OK;
 }
 
 int mcf_runmicro1(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {

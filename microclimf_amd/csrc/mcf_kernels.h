@@ -394,6 +394,32 @@ struct SeriesZonesArgs {
 };
 // `workgroups`: persistent workgroups per selected variable (each walks many tile groups and flushes once per day)
 void launch_series_zones(const SeriesZonesArgs& a, int workgroups, hipStream_t s);
+// The same fold over step-major planes (the snow plan's chunk series): value of (step k of the call, cell c) at
+// series[i][k * N + c], step 0 = hour 0 of state day `day0`; nsteps <= 24 * ndays steps exist (a shorter last day: the rest
+// count as NaN).  State as above; (day0 + ndays) * 24 <= steps.
+struct SeriesPlanesArgs {
+    const double* series[5];     // the selected series, in selection order
+    int64_t N;
+    int32_t nsel;                // selected series (the grid's y)
+    const int32_t* zone;         // [N], -1: in no zone
+    int32_t nzones;
+    int64_t steps, nsteps;
+    int32_t day0, ndays;
+    long long* state;
+};
+void launch_series_planes(const SeriesPlanesArgs& a, int workgroups, hipStream_t s);
+// dst[(i * ncells + ci) * dst_steps + dst_step0 + k] = series[i][k * N + cells[ci]], k < nsteps, i < nsel
+struct SeriesPointsPlanesArgs {
+    const double* series[5];
+    int64_t N;
+    int32_t nsel;
+    int64_t nsteps;
+    const int64_t* cells;
+    int64_t ncells;
+    double* dst;
+    int64_t dst_steps, dst_step0;
+};
+void launch_series_points_planes(const SeriesPointsPlanesArgs& a, hipStream_t s);
 void launch_series_init(long long* state, int64_t nsel, int64_t nzones, int64_t steps, hipStream_t s);
 // one statistic of one variable's state -> out[k + nsteps * z], k < nsteps; steps >= `steps` and steps of days with
 // day_done[day] == 0 (null: every day is folded) are NA

@@ -18,6 +18,8 @@
 // k_series_init   the state before the first day: sums and counts 0, minimum key INT64_MAX, maximum key INT64_MIN.
 // k_series_points the points' values of the chunk's days into the resident [var][point][step] buffer (k_gather_cells'
 //                 addressing, a point's steps contiguous).
+// k_series_planes / k_series_points_planes  the same two over step-major planes [step][cell] (the snow plan's chunk series, a
+//                 host array as it lies: DESIGN.md §28), described where they stand.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -179,6 +181,135 @@ __global__ __launch_bounds__(kSumLanes) void k_series_zones(SeriesZonesArgs a) {
     }
 }
 
+// ---- the same fold over step-major planes ---------------------------------------------------------------------
+// fold_hours / flush_day are k_series_zones' per-item body and its flush, word for word, as functions.  k_series_zones keeps its
+// own copy: calling these from it costs its 21-cell instantiation one more VGPR (228 against 227), and that kernel stays as
+// it was measured.
+// One item's 24 hours into the LDS table; z: the lane's label (-1: in no zone), value(h): its value at hour h.
+template <class V>
+__device__ __forceinline__ void fold_hours(long long (*tab)[kTab], int z, int lane, V value) {
+    const unsigned long long in_zone = __ballot(z >= 0);
+    if (in_zone == 0) return;                                     // (wave-uniform)
+    const int z0 = __shfl(z, __ffsll((long long)in_zone) - 1, 64);
+    if (__ballot(z >= 0 && z != z0) == 0) {
+        // one label in the wave: counts by ballot, the rest by butterflies; lane h keeps hour h's results
+        long long rs = 0, rmn = kKeyMax, rmx = kKeyMin;
+        unsigned long long rcb = 0;
+#pragma unroll
+        for (int h = 0; h < 24; ++h) {
+            const double v = value(h);
+            const bool seen = z >= 0 && v == v, ok = seen && fabs(v) < 4096.0;
+            const unsigned long long cb = (unsigned long long)__popcll(__ballot(ok)) |
+                                          ((unsigned long long)__popcll(__ballot(seen && !ok)) << 32);
+            if (cb == 0) continue;                                // (wave-uniform)
+            const long long ky = key_of(v);
+            const long long s = wave_sum(ok ? (long long)rint(v * 16777216.0) : 0ll);
+            const long long mn = wave_min(ok ? ky : kKeyMax), mx = wave_max(ok ? ky : kKeyMin);
+            if (lane == h) { rs = s; rmn = mn; rmx = mx; rcb = cb; }
+        }
+        if (lane < 24 && rcb != 0) {
+            const int e = z0 * 24 + lane;
+            LDS_ADD(&tab[kSeriesCount][e], (long long)rcb);
+            if ((uint32_t)rcb != 0) {
+                LDS_ADD(&tab[kSeriesSum][e], rs);
+                LDS_MIN(&tab[kSeriesMin][e], rmn);
+                LDS_MAX(&tab[kSeriesMax][e], rmx);
+            }
+        }
+    } else if (z >= 0) {
+#pragma unroll
+        for (int h = 0; h < 24; ++h) {
+            const double v = value(h);
+            if (v != v) continue;
+            const int e = z * 24 + h;
+            if (fabs(v) < 4096.0) {
+                const long long ky = key_of(v);
+                LDS_ADD(&tab[kSeriesCount][e], 1ll);
+                LDS_ADD(&tab[kSeriesSum][e], (long long)rint(v * 16777216.0));
+                LDS_MIN(&tab[kSeriesMin][e], ky);
+                LDS_MAX(&tab[kSeriesMax][e], ky);
+            } else {
+                LDS_ADD(&tab[kSeriesCount][e], (long long)kOneBad);
+            }
+        }
+    }
+}
+// The day's table to the state (sd: the state's entry of zone 0 at hour 0 of the day), touched entries only, and back to its
+// start.  The barriers are the caller's: one before (the day's folds are in), one behind (before the next day's folds).
+__device__ __forceinline__ void flush_day(long long (*tab)[kTab], int tid, int nzones, int64_t steps, long long* sd) {
+    const int nent = nzones * 24;
+    const int64_t row = (int64_t)nzones * steps;
+    for (int e = tid; e < nent; e += kSumLanes) {
+        const long long cb = tab[kSeriesCount][e];
+        if (cb == 0) continue;
+        const int zz = e / 24, h = e - zz * 24;
+        long long* g = sd + (int64_t)zz * steps + h;
+        DEV_ADD(g + kSeriesCount * row, cb);
+        tab[kSeriesCount][e] = 0;
+        if ((uint32_t)cb != 0) {
+            DEV_ADD(g + kSeriesSum * row, tab[kSeriesSum][e]);
+            DEV_MIN(g + kSeriesMin * row, tab[kSeriesMin][e]);
+            DEV_MAX(g + kSeriesMax * row, tab[kSeriesMax][e]);
+            tab[kSeriesSum][e] = 0; tab[kSeriesMin][e] = kKeyMax; tab[kSeriesMax][e] = kKeyMin;
+        }
+    }
+}
+
+// k_series_planes  the value of (step k of the call, cell c) at series[i][k * N + c], step 0 = hour 0 of state day day0.
+//                  Persistent workgroups of kSumLanes lanes per selected series; each walks every gridDim.x-th span of kSumLanes
+//                  consecutive cells, one lane per cell.  Per (day, span) a lane reads its label once and issues the day's 24
+//                  loads together (per hour one contiguous 512-byte run per wave: no LDS staging), then folds as above.  A last
+//                  day with fewer than 24 steps loads the steps that exist; the rest count as NaN.
+__global__ __launch_bounds__(kSumLanes) void k_series_planes(SeriesPlanesArgs a) {
+    __shared__ long long tab[kSeriesRows][kTab];
+    static_assert(sizeof(long long) * kSeriesRows * kTab <= 160 * 1024, "the table fits the LDS");
+    const int tid = (int)threadIdx.x, lane = tid & 63, k = (int)blockIdx.y;
+    const double* src = a.series[0];
+#pragma unroll
+    for (int i = 1; i < 5; ++i)                                   // (constant indices: the argument block stays in scalar registers)
+        if (i == k) src = a.series[i];
+    long long* st = a.state + (int64_t)k * kSeriesRows * a.nzones * a.steps;
+    const int64_t spans = (a.N + kSumLanes - 1) / kSumLanes;
+    const int nmine = (int)((spans - (int64_t)blockIdx.x + (int64_t)gridDim.x - 1) / (int64_t)gridDim.x);   // this workgroup's spans per day
+    if (nmine <= 0) return;                                       // (the whole workgroup: no barrier has been met)
+    for (int e = tid; e < a.nzones * 24; e += kSumLanes) {
+        tab[kSeriesSum][e] = 0; tab[kSeriesCount][e] = 0; tab[kSeriesMin][e] = kKeyMax; tab[kSeriesMax][e] = kKeyMin;
+    }
+    __syncthreads();
+    for (int d = 0; d < a.ndays; ++d) {
+        const int64_t left = a.nsteps - (int64_t)d * 24;
+        const int nh = left < 24 ? (int)left : 24;                // steps of this day that exist
+        const double* day = src + (int64_t)d * 24 * a.N;          // (64-bit: k * N + c passes 2^31 at 1024^2 cells x 2048 steps)
+        for (int j = 0; j < nmine; ++j) {
+            const int64_t c = ((int64_t)blockIdx.x + (int64_t)j * gridDim.x) * kSumLanes + tid;
+            const bool in = c < a.N;
+            int z = -1;
+            if (in) z = a.zone[c];
+            if (z >= a.nzones) z = -1;                            // (the host has checked the labels)
+            double v[24];
+#pragma unroll
+            for (int h = 0; h < 24; ++h) v[h] = in && h < nh ? day[(int64_t)h * a.N + c] : __builtin_nan("");
+            fold_hours(tab, z, lane, [&](int h) { return v[h]; });
+        }
+        __syncthreads();
+        flush_day(tab, tid, a.nzones, a.steps, st + (int64_t)(a.day0 + d) * 24);
+        __syncthreads();
+    }
+}
+
+// dst[(i * ncells + ci) * dst_steps + dst_step0 + k] = series[i][k * N + cells[ci]], k < nsteps
+__global__ __launch_bounds__(256) void k_series_points_planes(SeriesPointsPlanesArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.ncells * a.nsteps) return;
+    const int k = (int)blockIdx.y;
+    const double* src = a.series[0];
+#pragma unroll
+    for (int j = 1; j < 5; ++j)
+        if (j == k) src = a.series[j];
+    const int64_t ci = i / a.nsteps, kk = i - ci * a.nsteps;
+    a.dst[((int64_t)k * a.ncells + ci) * a.dst_steps + a.dst_step0 + kk] = src[kk * a.N + a.cells[ci]];
+}
+
 __global__ __launch_bounds__(256) void k_series_init(long long* state, int64_t total, int64_t row_elems) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
@@ -235,6 +366,19 @@ void launch_series_zones(const SeriesZonesArgs& a, int workgroups, hipStream_t s
         case 42: launch_zones<42>(a, workgroups, s); break;
         default: break;      // (the linear ring is refused by the host)
     }
+}
+
+void launch_series_planes(const SeriesPlanesArgs& a, int workgroups, hipStream_t s) {
+    if (a.N <= 0 || a.nsel <= 0 || a.ndays <= 0 || a.nsteps <= 0 || a.nzones <= 0 || workgroups <= 0) return;
+    const int64_t spans = (a.N + kSumLanes - 1) / kSumLanes;
+    const int64_t wg = spans < workgroups ? spans : workgroups;
+    hipLaunchKernelGGL(k_series_planes, dim3((unsigned)wg, (unsigned)a.nsel), dim3(kSumLanes), 0, s, a);
+}
+
+void launch_series_points_planes(const SeriesPointsPlanesArgs& a, hipStream_t s) {
+    const int64_t n = a.ncells * a.nsteps;
+    if (n <= 0 || a.nsel <= 0) return;
+    hipLaunchKernelGGL(k_series_points_planes, dim3((unsigned)((n + 255) / 256), (unsigned)a.nsel), dim3(256), 0, s, a);
 }
 
 void launch_series_init(long long* state, int64_t nsel, int64_t nzones, int64_t steps, hipStream_t s) {

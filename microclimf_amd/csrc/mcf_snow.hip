@@ -1902,6 +1902,20 @@ struct mcf_snowplan {
     int ps_row[MCF_NSTAT] = {}, ps_sel1[5] = {};  // ps_sel1: 1-based place of a series in the state, 0: not selected
     double ps_thr[5] = {};
     std::vector<int32_t> ps_pod, ps_days;
+    // series sink of the five series (mcf_snowplan_series_enable; se_on): as the solver plan keeps it — the points'
+    // [selected series][point][T] buffer, the zones' state (mcf_kernels.h SeriesPlanesArgs), one statistic [T][zone] on its
+    // way to the host, the folded days
+    bool se_on = false;
+    int64_t se_npoints = 0;
+    int se_nzones = 0, se_nsel = 0, se_workgroups = 0;
+    uint32_t se_bits = 0;                         // the selected series as a mcf_snowplan_set_series mask
+    int se_sel1[5] = {}, se_zstat[MCF_NZSTAT] = {};
+    int64_t* d_se_cells = nullptr;
+    int32_t *d_se_zone = nullptr, *d_se_done = nullptr;
+    double *d_se_points = nullptr, *d_se_plane = nullptr;
+    long long* d_se_state = nullptr;
+    std::vector<int32_t> se_done;                 // [days] 1: folded
+    std::vector<char> se_chunk_done;              // [chunks] 1: folded
     ~mcf_snowplan() { twork.release(); }
 };
 
@@ -4117,6 +4131,170 @@ extern "C" int mcf_snowplan_summary_days(mcf_snowplan* sp, int32_t* days) {
     if (!sp || !days) return mcf::api_fail(MCF_ERR_ARG, "null argument");
     if (!sp->d_ps_state) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no summary: mcf_snowplan_summary_enable first");
     for (int k = 0; k < sp->ps_nperiods; ++k) days[k] = sp->ps_days[(size_t)k];
+    return MCF_OK;
+}
+
+// ---- series sink of the five series (include/mcf.h "series sink of the snow run and of the snowpack"; the kernels:
+// mcf_series.hip k_series_planes / _points_planes / _fin / _init) -----------------------------------------------
+namespace mcf {   // mcf_snowrun.hip judges a spec with it before a device is needed
+int snowpack_series_check(const std::string& who, const mcf_snowpack_series_spec* s, int64_t rows, int64_t cols, int64_t chunk_steps) {
+    if (!s) return api_fail(MCF_ERR_ARG, who + ": null mcf_snowpack_series_spec");
+    const int64_t N = rows * cols;
+    if (N > ((int64_t)1 << 26)) return api_fail(MCF_ERR_ARG, who + ": more than 2^26 cells (the fixed-point sum's range)");
+    if (chunk_steps <= 0) chunk_steps = 120;
+    if (chunk_steps % 24) return api_fail(MCF_ERR_ARG, who + ": chunk_steps must be a multiple of 24");
+    int nv = 0, ns = 0;
+    for (int v = 0; v < 5; ++v) nv += s->series[v] ? 1 : 0;
+    for (int k = 0; k < MCF_NZSTAT; ++k) ns += s->zstat[k] ? 1 : 0;
+    if (nv == 0) return api_fail(MCF_ERR_ARG, who + ": no series selected");
+    if (s->npoints < 0) return api_fail(MCF_ERR_ARG, who + ": negative npoints");
+    if (s->npoints == 0 && s->nzones == 0) return api_fail(MCF_ERR_ARG, who + ": neither points nor zones selected");
+    if (s->nzones < 0 || s->nzones > MCF_MAX_ZONES)
+        return api_fail(MCF_ERR_ARG, who + ": nzones = " + std::to_string(s->nzones) + " is outside 0 .. " + std::to_string(MCF_MAX_ZONES));
+    if (s->nzones > 0) {
+        if (!s->zone) return api_fail(MCF_ERR_ARG, who + ": null zone map");
+        if (ns == 0) return api_fail(MCF_ERR_ARG, who + ": no statistic selected");
+        for (int64_t c = 0; c < N; ++c)
+            if (s->zone[c] < -1 || s->zone[c] >= s->nzones)
+                return api_fail(MCF_ERR_ARG, who + ": zone[" + std::to_string(c) + "] = " + std::to_string(s->zone[c]) + " is outside -1 .. nzones - 1");
+    }
+    if (s->npoints > 0 && !s->cells) return api_fail(MCF_ERR_ARG, who + ": null cells");
+    for (int64_t i = 0; i < s->npoints; ++i)
+        if (s->cells[i] < 0 || s->cells[i] >= N)
+            return api_fail(MCF_ERR_ARG, who + ": cells[" + std::to_string(i) + "] = " + std::to_string(s->cells[i]) + " is a cell index outside the raster");
+    return MCF_OK;
+}
+// a block's raw zone state of one series, [4][nzones][whole days x 24] of int64, and its folded days (mcf_series_host.hpp
+// combines the blocks'); sizes: snowplan_series_steps
+int64_t snowplan_series_steps(const mcf_snowplan* sp) { return (int64_t)(sp->T / 24) * 24; }
+int snowplan_series_state(mcf_snowplan* sp, int32_t series, int64_t* host_state, int32_t* day_done) {
+    if (!sp || !sp->se_on || series < 0 || series >= 5 || !sp->se_sel1[series] || sp->se_nzones == 0)
+        return api_fail(MCF_ERR_STATE, "snow plan: no zone state of this series");
+    HIP_TRY(hipSetDevice(sp->device));
+    const int64_t n = (int64_t)kSeriesRows * sp->se_nzones * snowplan_series_steps(sp);
+    if (host_state) HIP_TRY(hipMemcpy(host_state, sp->d_se_state + (int64_t)(sp->se_sel1[series] - 1) * n, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (day_done) std::copy(sp->se_done.begin(), sp->se_done.end(), day_done);
+    return MCF_OK;
+}
+}  // namespace mcf
+
+extern "C" int mcf_snowplan_series_reset(mcf_snowplan* sp) {
+    if (!sp) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_reset: null snow plan");
+    if (!sp->se_on) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no series sink: mcf_snowplan_series_enable first");
+    HIP_TRY(hipSetDevice(sp->device));
+    if (sp->d_se_points) mcf::launch_fill(sp->d_se_points, sp->se_nsel * sp->se_npoints * std::max(sp->T, 1), mcf::na_real_host(), nullptr);
+    if (sp->d_se_state) mcf::launch_series_init(sp->d_se_state, sp->se_nsel, sp->se_nzones, mcf::snowplan_series_steps(sp), nullptr);
+    HIP_TRY(hipGetLastError());
+    sp->se_done.assign((size_t)std::max(sp->T / 24, 1), 0);
+    sp->se_chunk_done.assign((size_t)std::max(sp->nchunks, 1), 0);
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_series_enable(mcf_snowplan* sp, const mcf_snowpack_series_spec* spec) {
+    const std::string who = "mcf_snowplan_series_enable";
+    if (!sp || !spec) return mcf::api_fail(MCF_ERR_ARG, who + ": null argument");
+    if (sp->se_on) return mcf::api_fail(MCF_ERR_STATE, who + ": the series sink is already enabled on this plan");
+    int rc = mcf::snowpack_series_check(who, spec, sp->rows, sp->cols, sp->chunk);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(sp->device));
+    int nsel = 0;
+    for (int v = 0; v < 5; ++v) nsel += spec->series[v] ? 1 : 0;
+    const int64_t np = spec->npoints, nz = spec->nzones, steps = mcf::snowplan_series_steps(sp), T = std::max(sp->T, 1);
+    const int64_t point_bytes = nsel * np * T * 8, state_bytes = nsel * mcf::kSeriesRows * nz * steps * 8;
+    if ((rc = check_room(point_bytes + state_bytes + nz * T * 8 + sp->N * 4))) return rc;
+    if (np > 0) {
+        if ((rc = sp->b.make(&sp->d_se_cells, np))) return rc;
+        HIP_TRY(hipMemcpy(sp->d_se_cells, spec->cells, (size_t)np * 8, hipMemcpyHostToDevice));
+        if ((rc = sp->b.make(&sp->d_se_points, nsel * np * T))) return rc;
+    }
+    if (nz > 0) {
+        if ((rc = sp->b.make(&sp->d_se_zone, sp->N))) return rc;
+        HIP_TRY(hipMemcpy(sp->d_se_zone, spec->zone, (size_t)sp->N * 4, hipMemcpyHostToDevice));
+        if ((rc = sp->b.make(&sp->d_se_state, std::max<int64_t>(state_bytes / 8, 1)))) return rc;
+        if ((rc = sp->b.make(&sp->d_se_plane, nz * T))) return rc;
+        if ((rc = sp->b.make(&sp->d_se_done, std::max(sp->T / 24, 1)))) return rc;
+    }
+    sp->se_npoints = np; sp->se_nzones = (int)nz; sp->se_nsel = nsel;
+    int cus = 0;      // persistent workgroups per selected series: one per compute unit
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, sp->device) != hipSuccess || cus < 1) cus = 256;
+    sp->se_workgroups = cus;
+    static const uint32_t bit[5] = {1u, 2u, 8u, 4u, 16u};      // (as snowpack_series_bits: bit 2 is totalSWE, bit 3 the ground snow depth)
+    int place = 0;
+    sp->se_bits = 0;
+    for (int v = 0; v < 5; ++v) {
+        sp->se_sel1[v] = spec->series[v] ? ++place : 0;
+        if (spec->series[v]) sp->se_bits |= bit[v];
+    }
+    for (int k = 0; k < MCF_NZSTAT; ++k) sp->se_zstat[k] = nz > 0 && spec->zstat[k] ? 1 : 0;
+    sp->se_on = true;
+    return mcf_snowplan_series_reset(sp);
+}
+
+extern "C" int mcf_snowplan_series_accumulate(mcf_snowplan* sp, int32_t ch) {
+    if (!sp) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_accumulate: null snow plan");
+    if (!sp->se_on) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no series sink: mcf_snowplan_series_enable first");
+    if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_accumulate: chunk out of range");
+    if (sp->se_chunk_done[(size_t)ch])
+        return mcf::api_fail(MCF_ERR_STATE, "mcf_snowplan_series_accumulate: chunk " + std::to_string(ch) + " has been folded already (each chunk at most once)");
+    if ((sp->series_valid & sp->se_bits) != sp->se_bits)
+        return mcf::api_fail(MCF_ERR_STATE, "mcf_snowplan_series_accumulate: a selected series of the chunk was switched off (mcf_snowplan_set_series)");
+    const int cd = sp->chunk / 24, day0 = ch * cd;
+    const int nd = std::min(sp->chunk, sp->T - ch * sp->chunk) / 24;       // (whole days of the chunk: a one-chunk series shorter than a chunk)
+    sp->se_chunk_done[(size_t)ch] = 1;
+    if (nd < 1) return MCF_OK;
+    HIP_TRY(hipSetDevice(sp->device));
+    const double* const dev[5] = {sp->a.Tc, sp->a.Tg, sp->a.sdepg, sp->a.sdepc, sp->a.sden};      // (sdepc: totalSWE after the redistribution)
+    if (sp->se_npoints > 0) {
+        mcf::SeriesPointsPlanesArgs a{};
+        for (int v = 0; v < 5; ++v)
+            if (sp->se_sel1[v]) a.series[sp->se_sel1[v] - 1] = dev[v];
+        a.N = sp->N; a.nsel = sp->se_nsel; a.nsteps = (int64_t)nd * 24;
+        a.cells = sp->d_se_cells; a.ncells = sp->se_npoints;
+        a.dst = sp->d_se_points; a.dst_steps = std::max(sp->T, 1); a.dst_step0 = (int64_t)day0 * 24;
+        mcf::launch_series_points_planes(a, nullptr);      // the null stream: behind k_snowmodel, which wrote the series on it
+    }
+    if (sp->se_nzones > 0) {
+        mcf::SeriesPlanesArgs a{};
+        for (int v = 0; v < 5; ++v)
+            if (sp->se_sel1[v]) a.series[sp->se_sel1[v] - 1] = dev[v];
+        a.N = sp->N; a.nsel = sp->se_nsel;
+        a.zone = sp->d_se_zone; a.nzones = sp->se_nzones;
+        a.steps = mcf::snowplan_series_steps(sp); a.nsteps = (int64_t)nd * 24;
+        a.day0 = day0; a.ndays = nd;
+        a.state = sp->d_se_state;
+        mcf::launch_series_planes(a, sp->se_workgroups, nullptr);
+    }
+    HIP_TRY(hipGetLastError());
+    for (int d = day0; d < day0 + nd; ++d) sp->se_done[(size_t)d] = 1;
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_series_fetch_points(mcf_snowplan* sp, int32_t series, double* dst) {
+    if (!sp || !dst) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_points: null argument");
+    if (!sp->se_on) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no series sink: mcf_snowplan_series_enable first");
+    if (series < 0 || series >= 5 || !sp->se_sel1[series])
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_points: series was not selected in mcf_snowplan_series_enable");
+    if (sp->se_npoints == 0) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_points: no points were selected in mcf_snowplan_series_enable");
+    HIP_TRY(hipSetDevice(sp->device));
+    const int64_t n = sp->se_npoints * std::max(sp->T, 1);
+    HIP_TRY(sp->dl.dense(dst, sp->d_se_points + (int64_t)(sp->se_sel1[series] - 1) * n, (size_t)n * 8));
+    return MCF_OK;
+}
+
+extern "C" int mcf_snowplan_series_fetch_zones(mcf_snowplan* sp, int32_t series, int32_t zstat, double* dst) {
+    if (!sp || !dst) return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_zones: null argument");
+    if (!sp->se_on) return mcf::api_fail(MCF_ERR_STATE, "the snow plan has no series sink: mcf_snowplan_series_enable first");
+    if (series < 0 || series >= 5 || !sp->se_sel1[series])
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_zones: series was not selected in mcf_snowplan_series_enable");
+    if (zstat < 0 || zstat >= MCF_NZSTAT || !sp->se_zstat[zstat])
+        return mcf::api_fail(MCF_ERR_ARG, "mcf_snowplan_series_fetch_zones: statistic was not selected in mcf_snowplan_series_enable");
+    HIP_TRY(hipSetDevice(sp->device));
+    const int64_t steps = mcf::snowplan_series_steps(sp), T = std::max(sp->T, 1);
+    HIP_TRY(hipMemcpy(sp->d_se_done, sp->se_done.data(), (size_t)std::max(sp->T / 24, 1) * 4, hipMemcpyHostToDevice));
+    mcf::launch_series_fin(sp->d_se_state + (int64_t)(sp->se_sel1[series] - 1) * mcf::kSeriesRows * sp->se_nzones * steps, sp->se_nzones,
+                           steps, T, sp->d_se_done, zstat, sp->d_se_plane, nullptr);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(sp->dl.dense(dst, sp->d_se_plane, (size_t)(T * sp->se_nzones) * 8));
     return MCF_OK;
 }
 

@@ -4,6 +4,8 @@
 
 #include <stdint.h>
 
+#include <string>
+
 #include "../../include/mcf.h"
 #include "mcf_rowblocks.hpp"
 
@@ -29,4 +31,9 @@ void subset_days(mcf_snow_inputs& in, bool series, const int32_t* sub_of_day, in
 // the summaries' specs judged without a device, and the selected series as a mcf_snowplan_set_series mask
 int snowpack_spec_check(const mcf_snowpack_summary_spec* s, int64_t tsteps, int64_t chunk_steps);
 uint32_t snowpack_series_bits(const mcf_snowpack_summary_spec* s);
+// the series sink's spec judged without a device (`who`: the entry's name, at the start of every message), and a block's raw
+// zone state of one series, [4][nzones][snowplan_series_steps] of int64, with its folded days [steps / 24] (either may be null)
+int snowpack_series_check(const std::string& who, const mcf_snowpack_series_spec* s, int64_t rows, int64_t cols, int64_t chunk_steps);
+int64_t snowplan_series_steps(const mcf_snowplan* sp);
+int snowplan_series_state(mcf_snowplan* sp, int32_t series, int64_t* host_state, int32_t* day_done);
 }  // namespace mcf

@@ -51,11 +51,14 @@
 #include "../../include/mcf.h"
 #include "mcf_rowblocks.hpp"
 #include "mcf_snow_plan.hpp"
+#include "mcf_series_host.hpp"
 
 namespace mcf {   // mcf_api.hip
 int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask);
 int plan_summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double* host_dst, int64_t row_pitch);
 int plan_summary_retable(mcf_plan* p, const int32_t* period_of_day);
+int series_spec_check(const std::string& who, const mcf_series_spec* s, int64_t rows, int64_t cols, const int32_t* out_mask);
+int plan_series_state(mcf_plan* p, int32_t var, int64_t* host_state, int32_t* day_done);
 }
 
 namespace {
@@ -78,6 +81,9 @@ struct Block {
     mcf_grid_inputs gsub{};                    // the block's view of the solver's inputs (array weather: a chunk's forcing is uploaded from it)
     std::vector<uint8_t> skip;                 // pass 2: the tiles a run of days leaves out
     bool sum_on = false;                       // the solver plan's summary has been enabled (block_setup)
+    // series sink: the block's rows of the caller's specs (mcf_series_host.hpp), and whether anything of them lies in the block
+    mcf::SeriesBlockCut mcut, pcut;
+    bool ser_micro = false, ser_pack = false;
 };
 
 // The raster in nb contiguous row blocks, block b (rows R*b/nb ..) on devs[b % nt] driven by worker b % nt, each with its snow
@@ -195,6 +201,52 @@ void snow_chunk(SnowBlocks& sb, Worker& w, int ch, const mcf_snowdriver_out* out
     w.wait();
 }
 
+// ---- the series sink over the blocks (include/mcf.h "Row blocks") ------------------------------------------------
+// a block's snow plan takes its rows of the snowpack's spec
+int block_pack_series(SnowBlocks& sb, Block& k, const mcf_snowpack_series_spec* spec) {
+    k.pcut.cut(spec->npoints, spec->cells, spec->nzones, spec->zone, sb.R, sb.C, k.r0, k.nr);
+    if (k.pcut.empty(spec->nzones)) return MCF_OK;
+    mcf_snowpack_series_spec bs = *spec;
+    bs.npoints = (int64_t)k.pcut.cells.size(); bs.cells = k.pcut.cells.data(); bs.zone = k.pcut.zone.data();
+    const int rc = mcf_snowplan_series_enable(k.sp, &bs);
+    k.ser_pack = !rc;
+    return rc;
+}
+// [T, npoints] of one series / variable: every block's points into their places of the caller's list.  pack: the snow plans'
+// sink, else the solver plans'
+int blocks_fetch_points(SnowBlocks& sb, bool pack, int32_t var, int64_t T, double* dst) {
+    mcf::RestoreDevice restore;
+    std::vector<double> tmp;
+    for (Block& k : sb.blocks) {
+        const mcf::SeriesBlockCut& cut = pack ? k.pcut : k.mcut;
+        if (!(pack ? k.ser_pack : k.ser_micro) || cut.where.empty()) continue;
+        tmp.resize((size_t)(T * (int64_t)cut.where.size()));
+        const int rc = pack ? mcf_snowplan_series_fetch_points(k.sp, var, tmp.data()) : mcf_plan_series_fetch_points(k.plan, var, tmp.data());
+        if (rc) return rc;
+        if (!pack)
+            if (const int rcs = mcf_plan_sync(k.plan)) return rcs;
+        for (size_t i = 0; i < cut.where.size(); ++i) memcpy(dst + cut.where[i] * T, tmp.data() + (int64_t)i * T, (size_t)T * 8);
+    }
+    return MCF_OK;
+}
+// [T, nzones] of one statistic: the blocks' states combined, finished once.  steps: whole days x 24
+int blocks_fetch_zones(SnowBlocks& sb, bool pack, int32_t var, int32_t nzones, int64_t steps, int64_t T, int32_t zstat, double* dst) {
+    mcf::RestoreDevice restore;
+    const size_t n = (size_t)((int64_t)mcf::kSeriesStateRows * nzones * steps);
+    std::vector<int64_t> state(std::max<size_t>(n, 1)), part(std::max<size_t>(n, 1));
+    std::vector<int32_t> done((size_t)std::max<int64_t>(steps / 24, 1), 0);
+    mcf::series_state_init(state.data(), nzones, steps);
+    for (Block& k : sb.blocks) {
+        if (!(pack ? k.ser_pack : k.ser_micro)) continue;
+        const int rc = pack ? mcf::snowplan_series_state(k.sp, var, part.data(), done.data())      // (every block has folded the same days)
+                            : mcf::plan_series_state(k.plan, var, part.data(), done.data());
+        if (rc) return rc;
+        mcf::series_state_merge(state.data(), part.data(), nzones, steps);
+    }
+    mcf::series_state_finish(state.data(), nzones, steps, T, done.data(), zstat, dst);
+    return MCF_OK;
+}
+
 }  // namespace
 
 struct mcf_snowrun : SnowBlocks {
@@ -226,6 +278,13 @@ struct mcf_snowrun : SnowBlocks {
     mcf_snowpack_summary_spec pspec{};
     std::vector<int32_t> mtable, ptable, mtable_year;
     uint32_t pack_bits = 0;
+    // series sink (mcf_snowrun_series_enable): the caller's specs with their cells and labels copied
+    bool ser_micro = false, ser_pack = false;
+    mcf_series_spec sspec{};
+    mcf_snowpack_series_spec spspec{};
+    std::vector<int64_t> scells, spcells;
+    std::vector<int32_t> szone, spzone;
+    uint32_t ser_pack_bits = 0;
 };
 
 namespace {
@@ -444,6 +503,8 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                 if (!rc2 && h->layers_set) rc2 = mcf_plan_set_day_layers(k.plan, nullptr, h->ndays);      // (a period's map is its own)
                 if (h->coarse) mcf::snowplan_coarse_umu_out(k.sp, h->umu_out);      // (pass 1 hands pointm$umu out, pass 2's re-runs do not)
                 if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_reset(k.sp);      // (a second year starts the summaries over)
+                if (!rc2 && k.ser_pack) rc2 = mcf_snowplan_series_reset(k.sp);        // (and the series)
+                if (!rc2 && k.ser_micro) rc2 = mcf_plan_series_reset(k.plan);
                 if (!rc2) rc2 = mcf_snowplan_release_kept(k.sp);
                 if (!rc2) std::fill(k.kept.begin(), k.kept.end(), 0);
                 return rc2;
@@ -456,7 +517,7 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                     // series, pass 1 writes only what it reads itself of such a chunk (totalSWE, density: mcf_snowplan_set_series)
                     int32_t room = 0;
                     if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
-                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u | h->pack_bits));
+                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u | h->pack_bits | h->ser_pack_bits));
                     return rc2;
                 });
                 snow_chunk(*h, w, ch, smod);
@@ -466,6 +527,7 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                     if (!rc2) rc2 = mcf_snowplan_apply3(k.sp, ch, MCF_APPLY_MIN, k.mn.data(), k.cmn.data());
                     // the snowpack's summaries: from the series where they lie, before keep_chunk hands the buffers over
                     if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_accumulate(k.sp, ch);
+                    if (!rc2 && k.ser_pack) rc2 = mcf_snowplan_series_accumulate(k.sp, ch);
                     return rc2;
                 });
                 mcf::reduce_on_first(w, [&] {
@@ -685,6 +747,18 @@ int fetch_days(Pass2& p, Block& k, int slot, int d0, int nd) {
     return MCF_OK;
 }
 
+// the series sink of the merged outputs: the slot's days that are in a class, run by run (a day in neither class is no day of
+// either model, fetch_days: never folded)
+int fold_series_days(const mcf_snowrun* h, Block& k, int slot, int d0, int nd) {
+    for (int q = 0, e; q < nd; q = e) {
+        e = q + 1;
+        if (!h->snowday[(size_t)(d0 + q)] && !h->nosnowday[(size_t)(d0 + q)]) continue;
+        while (e < nd && (h->snowday[(size_t)(d0 + e)] || h->nosnowday[(size_t)(d0 + e)])) ++e;
+        if (const int rc = mcf_plan_series_accumulate(k.plan, slot, q, d0 + q, e - q)) return rc;
+    }
+    return MCF_OK;
+}
+
 // per chunk: restore + re-run the snow chunk unless its series were kept; the solver on its no-snow days; the snow-day kernel
 // over the slot; the slot's merged days to the caller.  Collective: every worker walks every chunk.
 void chunk_loop(Pass2& p, Worker& w) {
@@ -708,6 +782,7 @@ void chunk_loop(Pass2& p, Worker& w) {
             // the slot holds the merged days: folded on the plan's stream — behind the solver's launches on it, and behind the
             // snow-day kernel, whose null stream mcf_snowplan_microsnow has synchronised the device on before it returned
             if (!rc && nd > 0 && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, slot, 0, d0, nd);
+            if (!rc && nd > 0 && k.ser_micro) rc = fold_series_days(h, k, slot, d0, nd);
             if (!rc && nd > 0) rc = fetch_days(p, k, slot, d0, nd);
             return rc;
         });
@@ -725,10 +800,11 @@ void tail_days(Pass2& p, Worker& w) {
             const int nd = std::min(cd, h->ndays - d0);
             int rc = solver_days(p, k, 0, -1, d0, nd, false);
             if (!rc && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, 0, 0, d0, nd);
+            if (!rc && k.ser_micro) rc = fold_series_days(h, k, 0, d0, nd);
             if (!rc) rc = fetch_days(p, k, 0, d0, nd);
             if (rc) return rc;
         }
-        if (h->sum_micro)                          // (a summary-only run has no fetch that waits for the plan's stream)
+        if (h->sum_micro || h->ser_micro)          // (a sink-only run has no fetch that waits for the plan's stream)
             if (const int rc = mcf_plan_sync(k.plan)) return rc;
         for (int v = 0; v < MCF_NOUT; ++v)
             if (h->opt.out[v] && p.out && p.out->var[v])
@@ -741,11 +817,11 @@ void tail_days(Pass2& p, Worker& w) {
 }  // namespace
 
 extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, double mat, mcf_outputs* out) {
-    if (!h || (!out && !h->sum_micro)) return api_fail(MCF_ERR_ARG, "null snow-run argument");
+    if (!h || (!out && !h->sum_micro && !h->ser_micro)) return api_fail(MCF_ERR_ARG, "null snow-run argument");
     if (!h->pass1_done) return api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
     try {
         for (int v = 0; v < MCF_NOUT; ++v)       // (with a summary enabled a variable may go without a host array: it is folded only)
-            if (!h->sum_micro && h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
+            if (!h->sum_micro && !h->ser_micro && h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
         Pass2 p{h, micro, mat, out};
         p.no_skip = getenv("MCF_SNOW_NO_TILE_SKIP") != nullptr;
         p.no_cells = getenv("MCF_SNOW_NO_CELL_GATHER") != nullptr;      // (A/B: tiles as the unit, as in round 4)
@@ -879,6 +955,136 @@ extern "C" int mcf_runmicrosnow_summary(const mcf_microsnow_in* in, const mcf_op
     return MCF_OK;
 }
 
+// ---- series sink of the run (include/mcf.h "series sink of the snow run and of the snowpack") -------------------
+static const char* const kSeriesBelow =
+    ": the series sink of the snow run needs reqhgt >= 0 (a below-ground run's solver plan is a streamed plan over the no-snow days)";
+
+// what can be judged of the two specs from the arguments alone; `who`: the entry's name, at the start of every message
+static int check_series_specs(const std::string& who, const mcf_series_spec* micro, const mcf_snowpack_series_spec* pack, const int32_t* out_mask,
+                              double reqhgt, int64_t rows, int64_t cols, int64_t chunk_steps) {
+    if (!micro && !pack) return api_fail(MCF_ERR_ARG, who + ": null spec (one of the two is needed)");
+    if (reqhgt < 0) return api_fail(MCF_ERR_ARG, who + kSeriesBelow);
+    if (micro)
+        if (const int rc = mcf::series_spec_check(who, micro, rows, cols, out_mask)) return rc;
+    return pack ? mcf::snowpack_series_check(who, pack, rows, cols, chunk_steps) : MCF_OK;
+}
+
+extern "C" int mcf_snowrun_series_enable(mcf_snowrun* h, const mcf_series_spec* micro, const mcf_snowpack_series_spec* pack) {
+    const std::string who = "mcf_snowrun_series_enable";
+    if (!h) return api_fail(MCF_ERR_ARG, who + ": null snow run");
+    if (h->below) return api_fail(MCF_ERR_ARG, who + kSeriesBelow);
+    if (const int rc = check_series_specs(who, micro, pack, h->opt.out, h->opt.reqhgt, h->R, h->C, h->snow.chunk_steps)) return rc;
+    if (h->ser_micro || h->ser_pack) return api_fail(MCF_ERR_STATE, who + ": the series sink is already enabled on this run");
+    if (h->pass1_ever) return api_fail(MCF_ERR_STATE, who + ": the series sink is enabled before mcf_snowrun_pass1");
+    try {
+        mcf::RestoreDevice restore;
+        if (pack) {
+            h->spspec = *pack;
+            if (pack->npoints > 0) h->spcells.assign(pack->cells, pack->cells + pack->npoints);
+            if (pack->nzones > 0) h->spzone.assign(pack->zone, pack->zone + h->R * h->C);
+            h->spspec.cells = h->spcells.data(); h->spspec.zone = h->spzone.data();
+            for (Block& k : h->blocks)
+                if (const int rc = block_pack_series(*h, k, &h->spspec)) return rc;
+            static const uint32_t bit[5] = {1u, 2u, 8u, 4u, 16u};      // (mcf_snowplan_set_series: bit 2 is totalSWE, bit 3 the ground snow depth)
+            for (int v = 0; v < 5; ++v) h->ser_pack_bits |= pack->series[v] ? bit[v] : 0u;
+            h->ser_pack = true;
+        }
+        if (micro) {
+            h->sspec = *micro;
+            if (micro->npoints > 0) h->scells.assign(micro->cells, micro->cells + micro->npoints);
+            if (micro->nzones > 0) h->szone.assign(micro->zone, micro->zone + h->R * h->C);
+            h->sspec.cells = h->scells.data(); h->sspec.zone = h->szone.data();
+            for (Block& k : h->blocks) {
+                k.mcut.cut(micro->npoints, h->sspec.cells, micro->nzones, h->sspec.zone, h->R, h->C, k.r0, k.nr);
+                if (k.mcut.empty(micro->nzones)) continue;
+                mcf_series_spec bs = h->sspec;
+                bs.npoints = (int64_t)k.mcut.cells.size(); bs.cells = k.mcut.cells.data(); bs.zone = k.mcut.zone.data();
+                if (const int rc = mcf_plan_series_enable(k.plan, &bs)) return rc;
+                k.ser_micro = true;
+            }
+            h->ser_micro = true;
+        }
+        return MCF_OK;
+    } catch (const std::exception& e) {
+        return api_fail(MCF_ERR_NOMEM, who + ": " + e.what());
+    }
+}
+
+// the checks the two fetches share
+static int series_fetch_ready(const char* who, mcf_snowrun* h, int32_t pack, int32_t var, const void* dst) {
+    const std::string w = who;
+    if (!h || !dst) return api_fail(MCF_ERR_ARG, w + ": null argument");
+    if (!(pack ? h->ser_pack : h->ser_micro)) return api_fail(MCF_ERR_STATE, w + ": this series was not enabled (mcf_snowrun_series_enable)");
+    if (pack ? !h->pass1_done : !h->pass2_done)
+        return api_fail(MCF_ERR_STATE, w + (pack ? ": the snowpack's series are there after mcf_snowrun_pass1" : ": the series of the outputs are there after mcf_snowrun_pass2"));
+    if (var < 0 || var >= (pack ? 5 : MCF_NOUT) || !(pack ? h->spspec.series[var] : h->sspec.var[var]))
+        return api_fail(MCF_ERR_ARG, w + ": variable was not selected in mcf_snowrun_series_enable");
+    return MCF_OK;
+}
+extern "C" int mcf_snowrun_series_fetch_points(mcf_snowrun* h, int32_t pack, int32_t var, double* dst) {
+    if (const int rc = series_fetch_ready("mcf_snowrun_series_fetch_points", h, pack, var, dst)) return rc;
+    const int64_t np = pack ? h->spspec.npoints : h->sspec.npoints, T = std::max<int64_t>(h->T, 1);
+    if (np == 0) return api_fail(MCF_ERR_ARG, "mcf_snowrun_series_fetch_points: no points were selected in mcf_snowrun_series_enable");
+    return blocks_fetch_points(*h, pack != 0, var, T, dst);
+}
+extern "C" int mcf_snowrun_series_fetch_zones(mcf_snowrun* h, int32_t pack, int32_t var, int32_t zstat, double* dst) {
+    if (const int rc = series_fetch_ready("mcf_snowrun_series_fetch_zones", h, pack, var, dst)) return rc;
+    const int32_t nz = pack ? h->spspec.nzones : h->sspec.nzones;
+    if (zstat < 0 || zstat >= MCF_NZSTAT || nz == 0 || !(pack ? h->spspec.zstat[zstat] : h->sspec.zstat[zstat]))
+        return api_fail(MCF_ERR_ARG, "mcf_snowrun_series_fetch_zones: statistic was not selected in mcf_snowrun_series_enable");
+    return blocks_fetch_zones(*h, pack != 0, var, nz, (int64_t)h->ndays * 24, std::max<int64_t>(h->T, 1), zstat, dst);
+}
+
+// null buffers of the selected (series, statistic) pairs of a snowpack spec
+static int check_pack_series_out(const std::string& who, const mcf_snowpack_series_spec* s, const mcf_snowpack_series_out* o) {
+    for (int v = 0; v < 5; ++v) {
+        if (!s->series[v]) continue;
+        if (s->npoints > 0 && !o->points[v]) return api_fail(MCF_ERR_ARG, who + ": a selected series has a null point buffer");
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (s->nzones > 0 && s->zstat[k] && !o->zones[v][k]) return api_fail(MCF_ERR_ARG, who + ": a selected (series, statistic) has a null buffer");
+    }
+    return MCF_OK;
+}
+
+extern "C" int mcf_runmicrosnow_series(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu,
+                                       const mcf_series_spec* micro_spec, const mcf_snowpack_series_spec* pack_spec,
+                                       mcf_snowrun_series_out* outs) {
+    const std::string who = "mcf_runmicrosnow_series";
+    if (!micro_spec && !pack_spec) return api_fail(MCF_ERR_ARG, who + ": null spec (one of the two is needed)");
+    if (!outs || !in || !in->grid || !in->snow || !opt) return api_fail(MCF_ERR_ARG, who + ": null argument");
+    int rc = check_series_specs(who, micro_spec, pack_spec, opt->out, opt->reqhgt, in->grid->rows, in->grid->cols, in->snow->chunk_steps);
+    if (rc) return rc;                                           // (nothing above needs a device or reads an input array)
+    if ((rc = check_create(in, opt, mu, false))) return rc;
+    for (int v = 0; micro_spec && v < MCF_NOUT; ++v) {
+        if (!micro_spec->var[v]) continue;
+        if (micro_spec->npoints > 0 && !outs->micro.points[v]) return api_fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (micro_spec->nzones > 0 && micro_spec->zstat[k] && !outs->micro.zones[v][k])
+                return api_fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
+    }
+    if (pack_spec && (rc = check_pack_series_out(who, pack_spec, &outs->pack))) return rc;
+    mcf_snowrun* h = nullptr;
+    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
+    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
+    if ((rc = mcf_snowrun_series_enable(h, micro_spec, pack_spec))) return rc;
+    if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
+    // (a run for the snowpack's series alone ends behind pass 1, unless the caller asks for the arrays)
+    if ((micro_spec || outs->arrays) && (rc = mcf_snowrun_pass2(h, in->micro, in->mat, outs->arrays))) return rc;
+    for (int v = 0; micro_spec && v < MCF_NOUT; ++v) {
+        if (!micro_spec->var[v]) continue;
+        if (micro_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 0, v, outs->micro.points[v]))) return rc;
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (micro_spec->nzones > 0 && micro_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 0, v, k, outs->micro.zones[v][k]))) return rc;
+    }
+    for (int v = 0; pack_spec && v < 5; ++v) {
+        if (!pack_spec->series[v]) continue;
+        if (pack_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 1, v, outs->pack.points[v]))) return rc;
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (pack_spec->nzones > 0 && pack_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 1, v, k, outs->pack.zones[v][k]))) return rc;
+    }
+    return MCF_OK;
+}
+
 static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out,
                               const mcf_snowdriver_out* smod, bool below = false) {
     mcf_snowrun* h = nullptr;
@@ -944,9 +1150,11 @@ extern "C" int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in* in, const m
 // EVERY block's plan stays resident, the chunk loop couples the blocks at every chunk)
 // spec / sout: the snowpack's period summaries (mcf_snowmodel1_summary, which has checked them), folded behind every chunk
 // co / umu_out: coarse array weather (mcf_snowmodel2_coarse, which has checked it; `in` is &co->drv) and where pointm$umu goes
+// zspec / zout: the snowpack's series sink (mcf_snowmodel1_series, which has checked them), folded behind every chunk too
 static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device,
                      const mcf_snowpack_summary_spec* spec = nullptr, mcf_snowpack_summary_out* sout = nullptr,
-                     const mcf_snowcoarse_in* co = nullptr, double* umu_out = nullptr) {
+                     const mcf_snowcoarse_in* co = nullptr, double* umu_out = nullptr,
+                     const mcf_snowpack_series_spec* zspec = nullptr, mcf_snowpack_series_out* zout = nullptr) {
     if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     try {
         SnowBlocks sb;
@@ -965,9 +1173,14 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
                 sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_enable(k.sp, spec); });
                 w.wait();
             }
+            if (zspec) {
+                sb.each_block(w, [&](Block& k) { return block_pack_series(sb, k, zspec); });
+                w.wait();
+            }
             for (int ch = 0; ch < nchunks; ++ch) {
                 snow_chunk(sb, w, ch, out);
                 if (spec) sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_accumulate(k.sp, ch); });
+                if (zspec) sb.each_block(w, [&](Block& k) { return k.ser_pack ? mcf_snowplan_series_accumulate(k.sp, ch) : (int)MCF_OK; });
             }
             if (spec)      // every block's rows of the planes in place, through the row pitch
                 sb.each_block(w, [&](Block& k) -> int {
@@ -979,6 +1192,15 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
                 });
         });
         if (!rc && spec && sout->days) rc = mcf_snowplan_summary_days(sb.blocks[0].sp, sout->days);
+        // the series: the blocks' points to their places, their zone states combined and finished once
+        const int64_t T = std::max<int64_t>(in->base.tsteps, 1);
+        for (int v = 0; !rc && zspec && v < 5; ++v) {
+            if (!zspec->series[v]) continue;
+            if (zspec->npoints > 0) rc = blocks_fetch_points(sb, true, v, T, zout->points[v]);
+            for (int q = 0; !rc && q < MCF_NZSTAT; ++q)
+                if (zspec->nzones > 0 && zspec->zstat[q])
+                    rc = blocks_fetch_zones(sb, true, v, zspec->nzones, in->base.tsteps / 24 * 24, T, q, zout->zones[v][q]);
+        }
         if (!rc && !mu && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
         return rc;
     } catch (const std::exception& e) {
@@ -1007,6 +1229,20 @@ extern "C" int mcf_snowmodel1_summary(const mcf_snowdriver_in* in, const mcf_sno
     if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
     mcf_snowdriver_out none{};
     return snowmodel(in, &none, mu, 0, spec, out);
+}
+// mcf_snowmodel1 / _multi with the snowpack's series sink as the only sink
+extern "C" int mcf_snowmodel1_series(const mcf_snowdriver_in* in, const mcf_snowpack_series_spec* spec, const mcf_multi* mu,
+                                     mcf_snowpack_series_out* out) {
+    const std::string who = "mcf_snowmodel1_series";
+    if (!spec) return api_fail(MCF_ERR_ARG, who + ": null mcf_snowpack_series_spec");
+    if (!in || !out) return api_fail(MCF_ERR_ARG, who + ": null snow driver argument");
+    if (const int rc = mcf::snowpack_series_check(who, spec, in->base.rows, in->base.cols, in->chunk_steps)) return rc;      // no device yet
+    if (in->base.array_forcing) return api_fail(MCF_ERR_ARG, who + " takes data.frame (vector) climate");
+    if (const int rc = check_pack_series_out(who, spec, out)) return rc;
+    if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, who + ": snow driver needs the raster and its dtm");
+    if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, who + ": null input: a vegetation or initial-snow raster");
+    mcf_snowdriver_out none{};
+    return snowmodel(in, &none, mu, 0, nullptr, nullptr, nullptr, nullptr, spec, out);
 }
 // `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
 // (mcf_snow.hip, k_coarse_hours) and hands pointm$umu out of the chunk's slab

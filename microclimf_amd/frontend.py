@@ -636,6 +636,29 @@ def runmicro_depths_summary(micropoint: Mapping, depths, vegp: Mapping, soilc: M
     return res
 
 
+def runmicro_depths_series(micropoint: Mapping, depths, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, points=None, xy=None,
+                           zones=None, vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), pai_a=None,
+                           tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None, wsa=None, svf=None, device: int = 0,
+                           chunk_days: int = 0) -> dict:
+    """runmicro_depths reduced over space on the device, as runmicro_series reduces runmicro: the hourly soil temperature at
+    logger sites (`points`, `xy`: see series_cells) and per-step statistics over `zones` at several depths, without a
+    cells x steps array anywhere.  `vars` among "Tz" and "soilm".
+    -> {"Tz": [per depth {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}], "soilm": {...} (if selected),
+    "depths", "cells"}"""
+    names = (vars,) if isinstance(vars, str) else tuple(vars)
+    if not names or any(n not in ("Tz", "soilm") for n in names):
+        raise ValueError('vars: below ground "Tz" and "soilm" have a series')
+    if any(s not in api._abi.ZSTAT_NAMES for s in ((stats,) if isinstance(stats, str) else stats)):
+        raise ValueError(f"stats: names of {api._abi.ZSTAT_NAMES}")
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    cells = series_cells(dtm, rows, cols, points, xy)
+    a, depths, tbp = _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device)
+    res = api.runmicro_depths_series(**a, depths=depths, tbp=tbp, points=cells if cells.size else None, zones=zones, vars=names,
+                                     stats=stats, chunk_days=chunk_days, device=device)
+    res["cells"] = cells
+    return res
+
+
 # ---- height profiles from one plan ----------------------------------------------------------------------------------------------
 def _height_inputs(micropoint, heights, vegp, soilc, dtm, pai_a, tfact, ter, device, out=(1,) * 10):
     """runmicro1Cpp's (runmicro3Cpp's) arguments without reqhgt and without the two foliage planes, the heights, and `pai_a` per
@@ -1545,6 +1568,74 @@ def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soi
         res = run.fetch_summary()
     res.setdefault("days", None)
     res.update(periods=labels, snowdays=sd, nosnowdays=nd)
+    return res
+
+
+def runmicro_snow_series(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, snow_inputs: Mapping, *,
+                         points=None, xy=None, zones=None, vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"),
+                         snow_vars: Sequence = (), pai_a=None, tfact: float = 1.5, device: int = 0, devices=None, n_blocks: int = 0,
+                         _terrain=None) -> dict:
+    """`runmicro(..., snow = TRUE)` reduced over space on the device: the snow run with the series sink of include/mcf.h as
+    its only sink — the hourly series of the merged outputs `vars` and, with `snow_vars` (names of Tc, Tg, groundsnowdepth,
+    totalSWE, snowden), of the snow model's series at logger sites (`points`, `xy`: see series_cells), and their per-step
+    statistics `stats` over `zones` ("mean Tz under snow in the heath class, hour by hour").  Days that are neither snow nor
+    no-snow days, and the snow series' days past the last whole 5-day chunk, are NA.  reqhgt < 0 is not available.
+    -> {variable: {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}, "snow": {series: {...}}, "cells",
+    "snowdays", "nosnowdays"}"""
+    from . import snow as S
+    if reqhgt < 0:
+        raise ValueError("the series sink of the snow run needs reqhgt >= 0")
+    names = _names(vars, api._abi.OUT_NAMES, "vars")
+    snames = _names(snow_vars, api._abi.SNOWDRIVER_OUT, "snow_vars")
+    if not names and not snames:
+        raise ValueError("nothing selected: vars and snow_vars are both empty")
+    if snow_inputs is None:
+        raise ValueError("snow_inputs = runsnowmodel(weather, micropoint, vegp, soilc, dtm, inputs_only=True) is needed")
+    if len(micropoint["subs"]) != micropoint["ntme"]:
+        raise ValueError("the one-call snow run takes a complete micropoint")
+    out = _out_mask(names)[1]
+    a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device)
+    a["tfact"] = float(tfact)
+    kept = [n for n, o in zip(api._abi.OUT_NAMES, a["out"]) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
+    if names and not kept:
+        raise ValueError("none of the selected variables exists at this reqhgt")
+    if not kept:                                                       # (the snowpack's series alone: the run still needs an output)
+        a["out"] = [1] + [0] * 9
+    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    cells = series_cells(dtm, rows, cols, points, xy)
+    sel = dict(points=cells if cells.size else None, zones=zones, stats=stats)
+    snow = {k: v for k, v in snow_inputs.items() if k != "umu"}
+    with S.SnowRun(a, snow, device=device, devices=devices, n_blocks=n_blocks) as run:
+        run.series_enable(dict(sel, vars=kept) if kept else None, dict(sel, vars=snames) if snames else None)
+        sd, nd = run.pass1()
+        if kept:
+            run.pass2(_one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain),
+                      float(micropoint["matemp"]), want_arrays=False)
+        res = run.fetch_series()
+    res.update(cells=cells, snowdays=sd, nosnowdays=nd)
+    return res
+
+
+def runsnowmodel_series(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, points=None, xy=None,
+                        zones=None, vars: Sequence = ("totalSWE",), stats: Sequence = ("mean", "min", "max"), snowenv: str = "Taiga",
+                        snowinitd=0.0, snowinita=0.0, stfact: float = 0.01, devices=None, n_blocks: int = 0) -> dict:
+    """`runsnowmodel()` (the slow method, data.frame weather, a complete micropoint) reduced over space on the device: the snow
+    model's series `vars` at logger sites and their per-step statistics over `zones` instead of the five [rows, cols, steps]
+    arrays.  The days past the last whole 5-day chunk (NA in runsnowmodel's arrays) are NA.
+    -> {"points": {series: [tsteps, npoints]}, "zones": {series: {statistic: [tsteps, nzones]}}, "cells"}"""
+    from . import snow as S
+    names = _names(vars, api._abi.SNOWDRIVER_OUT, "vars")
+    if not names:
+        raise ValueError("vars: nothing selected")
+    si = runsnowmodel(weather, micropoint, vegp, soilc, dtm, snowenv=snowenv, method="slow", snowinitd=snowinitd, snowinita=snowinita,
+                      stfact=stfact, inputs_only=True)
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    cells = series_cells(dtm, rows, cols, points, xy)
+    res = S.snowmodel1_series(si["obstime"], si["climdata"], si["pointm"], si["vegp"], si["other"], si["snowenv"], si["dtm"], si["res"],
+                              si["tfact"], points=cells if cells.size else None, zones=zones, vars=names, stats=stats, devices=devices,
+                              n_blocks=n_blocks)
+    res["cells"] = cells
     return res
 
 

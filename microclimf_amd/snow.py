@@ -257,6 +257,46 @@ def snowmodel1_summary(obstime, climdata, pointm, vegp, other, snowenv, dtm, res
     return planes
 
 
+def snowpack_series_spec(rows: int, cols: int, points=None, zones=None, vars=("totalSWE",), stats=("mean", "min", "max"),
+                         nzones: int | None = None):
+    """include/mcf.h mcf_snowpack_series_spec: api.series_spec over the five series (names of _abi.SNOWDRIVER_OUT or indices)
+    -> (spec, the selected series' indices, the selected statistics' indices)"""
+    from .api import series_spec
+    return series_spec(rows, cols, points, zones, vars, stats, nzones, struct=_abi.SnowpackSeriesSpec, names=_abi.SNOWDRIVER_OUT,
+                       field="series")
+
+
+def _micro_series_spec(rows, cols, series: Mapping):
+    from .api import series_spec
+    return series_spec(rows, cols, series.get("points"), series.get("zones"), series.get("vars", ("Tz",)),
+                       series.get("stats", ("mean", "min", "max")), series.get("nzones"))
+
+
+def _pack_series_spec(rows, cols, series: Mapping):
+    return snowpack_series_spec(rows, cols, series.get("points"), series.get("zones"), series.get("vars", ("totalSWE",)),
+                                series.get("stats", ("mean", "min", "max")), series.get("nzones"))
+
+
+def snowmodel1_series(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *, points=None, zones=None,
+                      vars=("totalSWE",), stats=("mean", "min", "max"), nzones: int | None = None, chunk_steps: int = 120,
+                      devices=None, n_blocks: int = 0) -> dict:
+    """snowmodel1_chunks with the series sink of the five series as its only sink (include/mcf.h mcf_snowmodel1_series): the
+    hourly series at `points` and per-step statistics over `zones` (as api.series_spec takes them), no [rows, cols, steps]
+    array on either side.  Days past the last whole chunk are NA.
+    -> {"points": {series: [tsteps, npoints]}, "zones": {series: {statistic: [tsteps, nzones]}}}"""
+    from .api import _series_sink
+    lib = _abi.load()
+    R, Cc = np.shape(vegp["pai"])
+    m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
+    din = _driver_in(m, dtm, res, tfact, chunk_steps)
+    sp, vi, si = snowpack_series_spec(R, Cc, points, zones, vars, stats, nzones)
+    so = _abi.SnowpackSeriesOut()
+    out = _series_sink(m, m.tsteps, sp, vi, si, so, names=_abi.SNOWDRIVER_OUT)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_snowmodel1_series(C.byref(din), C.byref(sp), C.byref(mu[0]) if mu else None, C.byref(so)))
+    return out
+
+
 def _driver_in_array(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact, af_wind, wsa_s, chunk_steps):
     """mcf_snowdriver_in for array weather at the raster's resolution (include/mcf.h mcf_snowmodel2)"""
     R, Cc = np.shape(vegp["pai"])
@@ -1057,6 +1097,34 @@ class SnowPlan:
                             plane=lambda v, k, ptr: _abi.check(self._lib.mcf_snowplan_summary_fetch(self._p, v, k, ptr, 0)),
                             days=lambda ptr: _abi.check(self._lib.mcf_snowplan_summary_days(self._p, ptr)))
 
+    # ---- series sink of the five series (include/mcf.h mcf_snowplan_series_*) ------------------------------------------------
+    def series_enable(self, points=None, zones=None, vars=("totalSWE",), stats=("mean", "min", "max"), nzones: int | None = None):
+        """arguments as snowpack_series_spec, cells and labels of this plan's rows; the state is allocated here"""
+        self._pser = snowpack_series_spec(self.rows, self.cols, points, zones, vars, stats, nzones)
+        _abi.check(self._lib.mcf_snowplan_series_enable(self._p, C.byref(self._pser[0])))
+
+    def series_accumulate(self, chunk: int):
+        """folds the series of the chunk run last (after run_chunk, before keep_chunk): chunks in any order, each once"""
+        _abi.check(self._lib.mcf_snowplan_series_accumulate(self._p, int(chunk)))
+
+    def series_reset(self):
+        _abi.check(self._lib.mcf_snowplan_series_reset(self._p))
+
+    def fetch_point_series(self, var) -> np.ndarray:
+        """[tsteps, npoints] of one selected series (name of _abi.SNOWDRIVER_OUT or index)"""
+        v = _abi.SNOWDRIVER_OUT.index(var) if isinstance(var, str) else int(var)
+        a, ptr = Buffers().out((self.tsteps, int(self._pser[0].npoints)))
+        _abi.check(self._lib.mcf_snowplan_series_fetch_points(self._p, v, ptr))
+        return a
+
+    def fetch_zone_series(self, var, stat) -> np.ndarray:
+        """[tsteps, nzones] of one selected statistic of one selected series (names or indices)"""
+        v = _abi.SNOWDRIVER_OUT.index(var) if isinstance(var, str) else int(var)
+        k = _abi.ZSTAT_NAMES.index(stat) if isinstance(stat, str) else int(stat)
+        a, ptr = Buffers().out((self.tsteps, int(self._pser[0].nzones)))
+        _abi.check(self._lib.mcf_snowplan_series_fetch_zones(self._p, v, k, ptr))
+        return a
+
     # ---- the snow-day microclimate inside the chunk loop (include/mcf.h: two passes over the year) ------------------
     def reset(self):
         """Back to the series' start (hand-over depths, ages, snow surface): the second pass."""
@@ -1413,6 +1481,34 @@ class SnowRun:
                 res.update(d)
         return res
 
+    def series_enable(self, series: Mapping | None = None, pack_series: Mapping | None = None):
+        """The series sink (include/mcf.h mcf_snowrun_series_enable), before pass1.  Each a mapping with "points" and / or "zones"
+        (whole-raster cell indices and labels, as api.series_spec takes them) and optionally "vars", "stats", "nzones": `series`
+        over the merged outputs (vars: output names the run was created with; days of neither class are never folded),
+        `pack_series` over the snow model's five series (vars: names of _abi.SNOWDRIVER_OUT)."""
+        ms = _micro_series_spec(self.rows, self.cols, series) if series is not None else None
+        ps = _pack_series_spec(self.rows, self.cols, pack_series) if pack_series is not None else None
+        _abi.check(self._lib.mcf_snowrun_series_enable(self._p, C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None))
+        self._mser, self._pser = ms, ps
+
+    def fetch_series(self) -> dict:
+        """-> {variable: {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}} of the outputs' series (after
+        pass2) and, under "snow", the same per series of the snowpack (after pass1)"""
+        from .api import _series_sink
+        res = {}
+        for pack, spec, names in ((0, getattr(self, "_mser", None), _abi.OUT_NAMES), (1, getattr(self, "_pser", None), _abi.SNOWDRIVER_OUT)):
+            if spec is None:
+                continue
+            d = _series_sink(Buffers(), self.tsteps, *spec, names=names,
+                             points=lambda v, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_points(self._p, pack, v, ptr)),
+                             zones=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_zones(self._p, pack, v, k, ptr)))
+            d = _series_by_variable(d)
+            if pack:
+                res["snow"] = d
+            else:
+                res.update(d)
+        return res
+
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
         (sd, sdp), (nd, ndp) = Buffers().out(self.days, np.int32, zero=True), Buffers().out(self.days, np.int32, zero=True)
@@ -1436,9 +1532,15 @@ class SnowRun:
         return arrays
 
 
+def _series_by_variable(d: dict) -> dict:
+    """_series_sink's {"points": {v: a}, "zones": {v: {stat: a}}} -> {v: {"points": a or None, "zones": {stat: a}}}"""
+    return {v: {"points": d["points"].get(v), "zones": d["zones"].get(v, {})} for v in list(d["points"]) + [k for k in d["zones"] if k not in d["points"]]}
+
+
 def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, *, device: int = 0, devices=None, n_blocks: int = 0,
                   want_smod: bool = False, cells_per_block: int = 0, below: bool = False, summary: Mapping | None = None,
-                  pack_summary: Mapping | None = None, want_arrays: bool = True):
+                  pack_summary: Mapping | None = None, want_arrays: bool = True, series: Mapping | None = None,
+                  pack_series: Mapping | None = None):
     """mcf_runmicrosnow1 / mcf_runmicrosnow1_multi: the whole snow run as ONE library call (arguments as `SnowRun`, `micro` as
     `SnowRun.pass2`) -> the merged outputs[, smod].  below: reqhgt < 0 through mcf_runmicrosnow1_below / _below_multi.
     summary / pack_summary (mappings as for SnowRun.summary_enable): the run through mcf_runmicrosnow_summary, either weather
@@ -1449,6 +1551,10 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
             run._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], run.array_weather, micro=True)
             run._in.micro = C.pointer(run._mm.inputs)
         run._in.mat = float(mat)
+        if series is not None or pack_series is not None:
+            if summary is not None or pack_summary is not None:
+                raise ValueError("one call takes the summaries or the series sink: both on one run through SnowRun")
+            return _runmicrosnow_series(run, series, pack_series, want_arrays, want_smod, devices, n_blocks)
         if summary is not None or pack_summary is not None:
             if below:
                 raise ValueError("period summaries of the snow run need reqhgt >= 0")
@@ -1493,6 +1599,37 @@ def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, de
     mu = _abi.multi(devices, n_blocks)
     _abi.check(lib.mcf_runmicrosnow_summary(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
                                             C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
+    return res
+
+
+def _runmicrosnow_series(run, series, pack_series, want_arrays, want_smod, devices, n_blocks) -> dict:
+    """-> {"out": the merged outputs or None, "series": as SnowRun.fetch_series, "snowdays", "nosnowdays"[, "smod"]}"""
+    from .api import _series_sink
+    lib = _abi.load()
+    ms = _micro_series_spec(run.rows, run.cols, series) if series is not None else None
+    ps = _pack_series_spec(run.rows, run.cols, pack_series) if pack_series is not None else None
+    so = _abi.SnowrunSeriesOut()
+    res = {"out": None, "series": {}}
+    for spec, names, dst, key in ((ms, _abi.OUT_NAMES, so.micro, None), (ps, _abi.SNOWDRIVER_OUT, so.pack, "snow")):
+        if spec is None:
+            continue
+        d = _series_by_variable(_series_sink(run._gm, run.tsteps, *spec, so=dst, names=names))
+        if key:
+            res["series"][key] = d
+        else:
+            res["series"].update(d)
+    if want_arrays:
+        outs, res["out"] = alloc_outputs(run._gm)
+        so.arrays = C.pointer(outs)
+    if want_smod:
+        sm, res["smod"] = _driver_out(run.rows, run.cols, run.tsteps)
+        so.smod = C.pointer(sm)
+    nd = run.tsteps // 24
+    res["snowdays"], so.snowday = run._gm.out(nd, np.int32, zero=True)
+    res["nosnowdays"], so.nosnowday = run._gm.out(nd, np.int32, zero=True)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_runmicrosnow_series(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
+                                           C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
     return res
 
 
