@@ -13,6 +13,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdlib>
+#include <functional>
 #include <future>
 #include <memory>
 #include <mutex>
@@ -28,6 +29,7 @@
 #include "mcf_rowblocks.hpp"
 #include "mcf_hiphost.hpp"
 #include "mcf_series_host.hpp"
+#include "mcf_sinks_host.hpp"
 
 namespace {
 
@@ -43,6 +45,8 @@ int fail(int code, const std::string& msg) {
 namespace mcf {
 int api_fail(int code, const std::string& msg) { return fail(code, msg); }
 }
+
+using mcf::SinkPlaces;
 
 struct mcf_plan {
     int device = 0;
@@ -136,12 +140,8 @@ struct mcf_plan {
     // (mcf_kernels.h SummaryAccArgs), the day tables on the device, one statistic plane on its way to the host
     double *d_sum_state = nullptr, *d_sum_plane = nullptr;
     int32_t *d_sum_pod = nullptr, *d_sum_prev = nullptr, *d_sum_next = nullptr, *d_sum_days = nullptr;
-    int sum_nperiods = 0, sum_nrows = 0, sum_nsel = 0;
-    // mcf_plan_summary_enable_below: the state's first sum_nmain places are the ring's selected variables, the places behind
-    // them Tz at depths 1 .. D - 1 (sum_nmain = sum_nsel everywhere else)
-    int sum_nmain = 0;
-    bool sum_below = false;
-    int sum_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
+    int sum_nperiods = 0, sum_nrows = 0;
+    SinkPlaces sum_places;
     int sum_row[MCF_NSTAT] = {};    // state row of a statistic, -1: not selected
     double sum_thr[MCF_NOUT] = {};
     uint32_t sum_init_codes = 0;
@@ -151,12 +151,8 @@ struct mcf_plan {
     // (mcf_kernels.h SeriesZonesArgs), one statistic [tsteps][zone] on its way to the host, the folded days
     bool ser_on = false;
     int64_t ser_npoints = 0;
-    int ser_nzones = 0, ser_nsel = 0, ser_workgroups = 0;
-    // mcf_plan_series_enable_below: the first ser_nmain places are the ring's selected variables, the places behind them Tz at
-    // depths 1 .. D - 1 (ser_nmain = ser_nsel everywhere else)
-    int ser_nmain = 0;
-    bool ser_below = false;
-    int ser_sel1[MCF_NOUT] = {};    // 1 + place among the selected variables, 0: not selected
+    int ser_nzones = 0, ser_workgroups = 0;
+    SinkPlaces ser_places;
     int ser_zstat[MCF_NZSTAT] = {};
     int64_t* d_ser_cells = nullptr;
     int32_t *d_ser_zone = nullptr, *d_ser_done = nullptr;
@@ -932,6 +928,26 @@ void fill_tail_na(double* buf, const mcf_grid_inputs* in, int ndays) {
             for (int64_t i = 0; i < in->rows; ++i) buf[i + pitch * j + HS * k] = na;
 }
 
+// The sink of a one-call entry's chunked run (run_sink above ground, run_depths below), built by the entry that has judged its
+// arguments.  What the driver needs before the plan exists: the variables the plan is created with, the per-cell doubles of
+// device state the sink adds to a below-ground plan's, and `check` (may be empty), the sink's refusals that need no device,
+// made behind the driver's own.  Then its three steps on the plan.
+struct RunSink {
+    int32_t out[MCF_NOUT] = {};
+    double state_doubles = 0.0;
+    std::function<int()> check;
+    std::function<int(mcf_plan*)> enable;
+    std::function<int(mcf_plan*, int, int)> fold;      // days [d0, d0 + nd) lie in slot 0
+    std::function<int(mcf_plan*)> finish;
+};
+int run_sink_chunks(mcf_plan* p, const mcf_grid_inputs* in, int ndays, int chunk, const RunSink& sink) {
+    int rc = sink.enable(p);
+    if (rc) return rc;
+    if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return sink.fold(p, d0, nd); }))) return rc;
+    if ((rc = sink.finish(p))) return rc;
+    return mcf_plan_sync(p);
+}
+
 // the four quarter-index vectors of a bioclim call (wet, dry, hot, cold) as plan buffers, their copies queued on its stream
 int upload_quarters(mcf_plan* p, const int32_t* const q[4], const int32_t nq[4], const int32_t* dq[4]) {
     for (int i = 0; i < 4; ++i) {
@@ -1411,6 +1427,34 @@ mcf::RingView depth_view(const mcf_plan* p, int slot, int depth) {
     v.tile_stride = p->tg_tile_stride; v.day_stride = mcf::ring_block_doubles(p->cpb);
     v.base = p->d_tzx + ((int64_t)(depth - 1) * p->ring_slots + slot) * p->ntiles * p->tg_tile_stride;
     return v;
+}
+// What a sink folds out of ring slot `slot`, launch by launch: `nsel` variables, the i-th in slab slab[i] (var_stride apart) of
+// `view` and requested as var[i]; its results start at `place` of the sink's state.
+struct SinkSource {
+    mcf::RingView view;
+    int64_t var_stride;
+    int nsel, place;
+    int slab[MCF_NOUT], var[MCF_NOUT];
+};
+// f(source) for the slot itself with the selected variables' slabs, then for Tz at depths 1 .. D - 1 of a below-ground sink, each
+// one variable of its own slab beside the ring
+extern "C++" template <class F>
+void for_sink_sources(const mcf_plan* p, const SinkPlaces& places, int slot, F&& f) {
+    SinkSource s{};
+    s.view.N = p->N; s.view.cpb = p->cpb;
+    s.view.base = p->d_ring + (int64_t)slot * p->slot_elems;
+    s.view.tile_stride = p->ring_tile_stride; s.view.day_stride = p->ring_day_stride;
+    s.var_stride = p->ring_var_stride;
+    s.nsel = places.nmain;
+    for (int v = 0; v < MCF_NOUT; ++v)
+        if (places.sel1[v]) { s.slab[places.sel1[v] - 1] = p->var_slot[v]; s.var[places.sel1[v] - 1] = v; }
+    f(s);
+    for (int d = 1; d <= places.nsel - places.nmain; ++d) {
+        s.view = depth_view(p, slot, d);
+        s.var_stride = 0; s.nsel = 1; s.place = places.nmain + d - 1;
+        s.slab[0] = 0; s.var[0] = MCF_OUT_TZ;
+        f(s);
+    }
 }
 // the state of a streamed plan as k_below_* see it; the chunk fields are the caller's
 mcf::BelowStreamArgs below_args(mcf_plan* p, int slot) {
@@ -2469,21 +2513,13 @@ static int summary_enable_checked(mcf_plan* p, const mcf_summary_spec* spec, int
         if (row[k] > 0 && k == MCF_STAT_MIN) codes |= 1u << (4 * row[k]);
         if (row[k] > 0 && k == MCF_STAT_MAX) codes |= 2u << (4 * row[k]);
     }
-    int nmain = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) nmain += spec->var[v] ? 1 : 0;
-    const int nsel = nmain + extra_places;
+    SinkPlaces places;
+    places.select(spec->var, extra_places);
     const int64_t nd = std::max(p->ndays, 1), np = spec->nperiods;
-    const int64_t state_bytes = (int64_t)nsel * np * nrows * p->N * 8, plane_bytes = np * p->N * 8;
+    const int64_t state_bytes = (int64_t)places.nsel * np * nrows * p->N * 8, plane_bytes = np * p->N * 8;
     if ((rc = check_room(state_bytes + plane_bytes + (3 * nd + np) * 4, "the summary state"))) return rc;
-    // the previous / next day of each day's period
-    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)p->ndays), last((size_t)np, -1);
-    for (int d = 0; d < p->ndays; ++d) {
-        const int per = pod[(size_t)d] = spec->period_of_day[d];
-        if (per < 0) continue;
-        prev[(size_t)d] = last[(size_t)per];
-        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
-        last[(size_t)per] = d;
-    }
+    std::vector<int32_t> pod, prev, next;
+    if ((rc = mcf::period_tables(spec->period_of_day, p->ndays, (int)np, pod, prev, next))) return rc;
     int32_t** tabs[3] = {&p->d_sum_pod, &p->d_sum_prev, &p->d_sum_next};
     const std::vector<int32_t>* host[3] = {&pod, &prev, &next};
     for (int i = 0; i < 3; ++i) {
@@ -2494,13 +2530,9 @@ static int summary_enable_checked(mcf_plan* p, const mcf_summary_spec* spec, int
     if ((rc = p->dev.make(&p->d_sum_plane, plane_bytes / 8))) return rc;
     double* state = nullptr;      // (the plan gets it last: d_sum_state says that the summary is on)
     if ((rc = p->dev.make(&state, state_bytes / 8))) return rc;
-    p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_nsel = nsel; p->sum_nmain = nmain; p->sum_init_codes = codes;
+    p->sum_nperiods = (int)np; p->sum_nrows = nrows; p->sum_places = places; p->sum_init_codes = codes;
     for (int k = 0; k < MCF_NSTAT; ++k) p->sum_row[k] = row[k];
-    int place = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) {
-        p->sum_sel1[v] = spec->var[v] ? ++place : 0;
-        p->sum_thr[v] = spec->var[v] && spec->stat[MCF_STAT_HOURS_ABOVE] ? spec->threshold[v] : 0.0;
-    }
+    for (int v = 0; v < MCF_NOUT; ++v) p->sum_thr[v] = spec->var[v] && spec->stat[MCF_STAT_HOURS_ABOVE] ? spec->threshold[v] : 0.0;
     p->sum_pod = std::move(pod);
     p->d_sum_state = state;
     return mcf_plan_summary_reset(p);
@@ -2516,26 +2548,18 @@ int mcf_plan_summary_enable(mcf_plan* p, const mcf_summary_spec* spec) {
     return summary_enable_checked(p, spec, 0);
 }
 
-// below ground only Tz and soilm exist (what .runmodel1Cpp keeps there)
-static int check_summary_below_vars(const char* who, const mcf_summary_spec* s) {
-    for (int v = 0; s && v < MCF_NOUT; ++v)
-        if (s->var[v] && v != MCF_OUT_TZ && v != MCF_OUT_SOILM)
-            return fail(MCF_ERR_ARG, std::string(who) + ": below ground Tz and soilm can be summarised, nothing else");
-    return MCF_OK;
-}
-
 int mcf_plan_summary_enable_below(mcf_plan* p, const mcf_summary_spec* spec) {
     const char* who = "mcf_plan_summary_enable_below";
     if (!p || !spec) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
     if (!p->bg_stream || !p->tiled)
         return fail(MCF_ERR_STATE, std::string(who) + " needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
     if (p->d_sum_state) return fail(MCF_ERR_STATE, "period summaries are already enabled on this plan");
-    int rc = check_summary_below_vars(who, spec);
+    int rc = mcf::check_below_vars(who, spec->var, "can be summarised");
     if (rc) return rc;
     if ((rc = check_summary_spec(spec, p->ndays, p->var_slot))) return rc;
     const int D = std::max<int>(1, (int)p->depths.size());
     if ((rc = summary_enable_checked(p, spec, spec->var[MCF_OUT_TZ] ? D - 1 : 0))) return rc;
-    p->sum_below = true;
+    p->sum_places.below = true;
     return MCF_OK;
 }
 
@@ -2543,7 +2567,7 @@ int mcf_plan_summary_reset(mcf_plan* p) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
     if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
     HIP_TRY(hipSetDevice(p->device));
-    mcf::launch_summary_init(p->d_sum_state, (int64_t)p->sum_nsel * p->sum_nperiods * p->sum_nrows * p->N, p->N, p->sum_nrows,
+    mcf::launch_summary_init(p->d_sum_state, (int64_t)p->sum_places.nsel * p->sum_nperiods * p->sum_nrows * p->N, p->N, p->sum_nrows,
                              p->sum_init_codes, p->stream);
     HIP_TRY(hipGetLastError());
     p->sum_days.assign((size_t)p->sum_nperiods, 0);
@@ -2554,37 +2578,24 @@ int mcf_plan_summary_reset(mcf_plan* p) {
 int mcf_plan_summary_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays) {
     if (!p) return fail(MCF_ERR_ARG, "null plan");
     if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
-    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "slot out of range");
-    if (day0 < 0 || ndays < 1 || (int64_t)day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "day range out of bounds");
-    if (slot_day0 < 0 || (int64_t)slot_day0 + ndays > p->ring_days) return fail(MCF_ERR_ARG, "more days than the ring slot holds");
+    if (const int rc = mcf::check_fold_range("", p->ring_slots, p->ring_days, p->ndays, slot, slot_day0, day0, ndays)) return rc;
     if (day0 < p->sum_next_day)
         return fail(MCF_ERR_STATE, "summary: days arrive in ascending order, each at most once (day " + std::to_string(day0) +
                                        " after day " + std::to_string(p->sum_next_day - 1) + ")");
     HIP_TRY(hipSetDevice(p->device));
     mcf::SummaryAccArgs a{};
-    a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
-    a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
     a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
-    a.nsel = p->sum_nmain;
-    for (int v = 0; v < MCF_NOUT; ++v)
-        if (p->sum_sel1[v]) {
-            a.slab[p->sum_sel1[v] - 1] = p->var_slot[v];
-            a.threshold[p->sum_sel1[v] - 1] = p->sum_thr[v];
-        }
     a.nperiods = p->sum_nperiods; a.nrows = p->sum_nrows;
     for (int k = 0; k < MCF_NSTAT; ++k) a.row[k] = p->sum_row[k];
     a.period_of_day = p->d_sum_pod; a.prev_same = p->d_sum_prev; a.next_same = p->d_sum_next;
     a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
-    a.state = p->d_sum_state;
-    mcf::launch_summary_acc(a, p->stream);
-    // below ground: Tz at depths 1 .. D - 1, each one variable of its own slab beside the ring
-    for (int d = 1; d <= p->sum_nsel - p->sum_nmain; ++d) {
-        const mcf::RingView v = depth_view(p, slot, d);
-        a.ring = v.base; a.tile_stride = v.tile_stride; a.day_stride = v.day_stride; a.var_stride = 0;
-        a.nsel = 1; a.slab[0] = 0; a.threshold[0] = p->sum_thr[MCF_OUT_TZ];
-        a.state = p->d_sum_state + (int64_t)(p->sum_nmain + d - 1) * p->sum_nperiods * p->sum_nrows * p->N;
+    for_sink_sources(p, p->sum_places, slot, [&](const SinkSource& s) {
+        a.ring = s.view.base; a.tile_stride = s.view.tile_stride; a.day_stride = s.view.day_stride; a.var_stride = s.var_stride;
+        a.nsel = s.nsel;
+        for (int i = 0; i < s.nsel; ++i) { a.slab[i] = s.slab[i]; a.threshold[i] = p->sum_thr[s.var[i]]; }
+        a.state = p->d_sum_state + (int64_t)s.place * p->sum_nperiods * p->sum_nrows * p->N;
         mcf::launch_summary_acc(a, p->stream);
-    }
+    });
     HIP_TRY(hipGetLastError());
     for (int d = day0; d < day0 + ndays; ++d)
         if (p->sum_pod[(size_t)d] >= 0) p->sum_days[(size_t)p->sum_pod[(size_t)d]] += 1;
@@ -2597,13 +2608,10 @@ static int summary_fetch_pitched(mcf_plan* p, int32_t var, int32_t stat, double*
     if (!p || !host_dst) return fail(MCF_ERR_ARG, "null argument");
     if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
     if (var < 0 || var >= MCF_NOUT || stat < 0 || stat >= MCF_NSTAT) return fail(MCF_ERR_ARG, "bad variable / statistic");
-    if (!p->sum_sel1[var]) return fail(MCF_ERR_ARG, "variable was not selected in mcf_plan_summary_enable");
+    if (!p->sum_places.sel1[var]) return fail(MCF_ERR_ARG, "variable was not selected in mcf_plan_summary_enable");
     if (p->sum_row[stat] < 0) return fail(MCF_ERR_ARG, "statistic was not selected in mcf_plan_summary_enable");
-    // the place in the state: the variable's own, or (below ground) that of Tz at a depth behind the first
-    if (depth < 0 || depth > (var == MCF_OUT_TZ ? p->sum_nsel - p->sum_nmain : 0))
-        return fail(MCF_ERR_ARG, var == MCF_OUT_TZ ? "mcf_plan_summary_fetch_depth: depth " + std::to_string(depth) + " is outside the plan's list"
-                                                   : std::string("mcf_plan_summary_fetch_depth: only Tz is kept per depth (depth 0 for soilm)"));
-    const int place = depth == 0 ? p->sum_sel1[var] - 1 : p->sum_nmain + depth - 1;
+    const int place = p->sum_places.place("mcf_plan_summary_fetch_depth", var, depth);
+    if (place < 0) return MCF_ERR_ARG;
     if (row_pitch == 0) row_pitch = p->rows;
     if (row_pitch < p->rows) return fail(MCF_ERR_ARG, "row_pitch smaller than rows");
     HIP_TRY(hipSetDevice(p->device));
@@ -2621,7 +2629,7 @@ int mcf_plan_summary_fetch(mcf_plan* p, int32_t var, int32_t stat, double* host_
     return summary_fetch_pitched(p, var, stat, host_dst, 0);
 }
 int mcf_plan_summary_fetch_depth(mcf_plan* p, int32_t depth, int32_t var, int32_t stat, double* host_dst) {
-    if (p && !p->sum_below) return fail(MCF_ERR_STATE, "mcf_plan_summary_fetch_depth: the plan has no below-ground summary (mcf_plan_summary_enable_below)");
+    if (p && !p->sum_places.below) return fail(MCF_ERR_STATE, "mcf_plan_summary_fetch_depth: the plan has no below-ground summary (mcf_plan_summary_enable_below)");
     return summary_fetch_pitched(p, var, stat, host_dst, 0, depth);
 }
 
@@ -2649,15 +2657,8 @@ int plan_summary_retable(mcf_plan* p, const int32_t* period_of_day) {
     if (!p || !period_of_day) return fail(MCF_ERR_ARG, "null argument");
     if (!p->d_sum_state) return fail(MCF_ERR_STATE, "the plan has no summary: mcf_plan_summary_enable first");
     const int64_t nd = std::max(p->ndays, 1);
-    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)p->ndays), last((size_t)p->sum_nperiods, -1);
-    for (int d = 0; d < p->ndays; ++d) {
-        const int per = pod[(size_t)d] = period_of_day[d];
-        if (per < -1 || per >= p->sum_nperiods) return fail(MCF_ERR_ARG, "summary: a table entry is outside -1 .. nperiods - 1");
-        if (per < 0) continue;
-        prev[(size_t)d] = last[(size_t)per];
-        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
-        last[(size_t)per] = d;
-    }
+    std::vector<int32_t> pod, prev, next;
+    if (const int rc = period_tables(period_of_day, p->ndays, p->sum_nperiods, pod, prev, next)) return rc;
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipStreamSynchronize(p->stream));                     // (a fold of the year before may still read the tables)
     HIP_TRY(hipMemcpy(p->d_sum_pod, pod.data(), (size_t)nd * 4, hipMemcpyHostToDevice));
@@ -2669,7 +2670,29 @@ int plan_summary_retable(mcf_plan* p, const int32_t* period_of_day) {
 }  // namespace mcf
 extern "C" {
 
-// twi_mean / out_pitch: a row block of a taller raster (mcf_runmicro_summary_multi), as for run_bioclim
+// The chunked run of the tiled-ring sinks (period summaries, the series sink) for an entry that has judged its arguments: a plan
+// of the sink's variables whose ring holds `chunk_days` days (0: what the ring budget gives), the sink's three steps on it.
+// twi_mean: a row block of a taller raster (the `_multi` entries), as for run_bioclim
+static int run_sink(const mcf_grid_inputs* in, const mcf_options* opt_in, int32_t chunk_days, const RunSink& sink, const double* twi_mean) {
+    mcf_options opt = *opt_in;
+    int nsel = 0, rc;
+    for (int v = 0; v < MCF_NOUT; ++v) nsel += (opt.out[v] = sink.out[v]);
+    if ((rc = ensure_device(opt.device))) return rc;
+    const int ndays = (int)(in->tsteps / 24);
+    int chunk = chunk_days;
+    // the ring of the selected variables (and, fine array forcing, the forcing ring's 15 series) from the byte budget
+    if (chunk == 0)
+        chunk = ring_budget_days("MCF_SUMMARY_RING_GB", nsel + (in->array_forcing == 1 ? 15 : 0), in->rows * in->cols,
+                                 opt.cells_per_block ? opt.cells_per_block : 21);
+    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
+    mcf_plan* p = nullptr;
+    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
+    PlanHolder holder(p);
+    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
+    return run_sink_chunks(p, in, ndays, chunk, sink);
+}
+
+// twi_mean / out_pitch: a row block of a taller raster (mcf_runmicro_summary_multi)
 static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_summary_spec* spec, int32_t chunk_days,
                        mcf_summary_out* out, const double* twi_mean = nullptr, int64_t out_pitch = 0) {
     if (!spec || !out) return fail(MCF_ERR_ARG, "null summary argument");
@@ -2677,33 +2700,20 @@ static int run_summary(const mcf_grid_inputs* in, const mcf_options* opt_in, con
     if (rc) return rc;
     if (opt_in->reqhgt < 0.0) return fail(MCF_ERR_ARG, "period summaries need reqhgt >= 0 (the tiled ring)");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, "summary: negative chunk_days");
-    const int ndays = (int)(in->tsteps / 24);
-    if ((rc = check_summary_spec(spec, ndays, nullptr))) return rc;
-    for (int v = 0; v < MCF_NOUT; ++v)
-        for (int k = 0; k < MCF_NSTAT; ++k)
-            if (spec->var[v] && spec->stat[k] && !out->val[v][k]) return fail(MCF_ERR_ARG, "summary: a selected (variable, statistic) has a null buffer");
-    mcf_options opt = *opt_in;
-    int nsel = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) nsel += (opt.out[v] = spec->var[v] ? 1 : 0);
-    if ((rc = ensure_device(opt.device))) return rc;
-    const int64_t N = in->rows * in->cols;
-    int chunk = chunk_days;
-    // the ring of the selected variables (and, fine array forcing, the forcing ring's 15 series) from the byte budget
-    if (chunk == 0)
-        chunk = ring_budget_days("MCF_SUMMARY_RING_GB", nsel + (in->array_forcing == 1 ? 15 : 0), N,
-                                 opt.cells_per_block ? opt.cells_per_block : 21);
-    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
-    mcf_plan* p = nullptr;
-    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
-    PlanHolder holder(p);
-    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
-    if ((rc = mcf_plan_summary_enable(p, spec))) return rc;
-    if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return mcf_plan_summary_accumulate(p, 0, 0, d0, nd); }))) return rc;
-    for (int v = 0; v < MCF_NOUT; ++v)
-        for (int k = 0; k < MCF_NSTAT; ++k)
-            if (spec->var[v] && spec->stat[k] && (rc = summary_fetch_pitched(p, v, k, out->val[v][k], out_pitch))) return rc;
-    if (out->days && (rc = mcf_plan_summary_days(p, out->days))) return rc;
-    return mcf_plan_sync(p);
+    if ((rc = check_summary_spec(spec, in->tsteps / 24, nullptr))) return rc;
+    if ((rc = mcf::check_summary_out(spec, out))) return rc;
+    RunSink sink;
+    for (int v = 0; v < MCF_NOUT; ++v) sink.out[v] = spec->var[v] ? 1 : 0;
+    sink.enable = [&](mcf_plan* p) { return mcf_plan_summary_enable(p, spec); };
+    sink.fold = [](mcf_plan* p, int d0, int nd) { return mcf_plan_summary_accumulate(p, 0, 0, d0, nd); };
+    sink.finish = [&](mcf_plan* p) -> int {
+        for (int v = 0; v < MCF_NOUT; ++v)
+            for (int k = 0; k < MCF_NSTAT; ++k)
+                if (spec->var[v] && spec->stat[k])
+                    if (const int rcf = summary_fetch_pitched(p, v, k, out->val[v][k], out_pitch)) return rcf;
+        return out->days ? mcf_plan_summary_days(p, out->days) : (int)MCF_OK;
+    };
+    return run_sink(in, opt_in, chunk_days, sink, twi_mean);
 }
 int mcf_runmicro_summary(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_summary_spec* spec, int32_t chunk_days,
                          mcf_summary_out* out) {
@@ -2758,8 +2768,9 @@ static int series_enable_checked(const std::string& who, mcf_plan* p, const mcf_
     int rc = check_series_spec(who, spec, p->rows, p->cols, p->var_slot);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(p->device));
-    int nsel = extra;
-    for (int v = 0; v < MCF_NOUT; ++v) nsel += spec->var[v] ? 1 : 0;
+    SinkPlaces places;
+    places.select(spec->var, extra);
+    const int nsel = places.nsel;
     const int64_t np = spec->npoints, nz = spec->nzones, steps = (int64_t)p->ndays * 24, T = std::max<int64_t>(p->tsteps, 1);
     const int64_t point_bytes = nsel * np * T * 8, state_bytes = nsel * mcf::kSeriesRows * nz * steps * 8;
     if ((rc = check_room(point_bytes, "mcf_plan_series_enable: the point buffer"))) return rc;
@@ -2776,10 +2787,8 @@ static int series_enable_checked(const std::string& who, mcf_plan* p, const mcf_
         if ((rc = p->dev.make(&p->d_ser_plane, nz * T))) return rc;
         if ((rc = p->dev.make(&p->d_ser_done, std::max(p->ndays, 1)))) return rc;
     }
-    p->ser_npoints = np; p->ser_nzones = (int)nz; p->ser_nsel = nsel; p->ser_nmain = nsel - extra;
+    p->ser_npoints = np; p->ser_nzones = (int)nz; p->ser_places = places;
     p->ser_workgroups = series_workgroups(p->device);
-    int place = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) p->ser_sel1[v] = spec->var[v] ? ++place : 0;
     for (int k = 0; k < MCF_NZSTAT; ++k) p->ser_zstat[k] = nz > 0 && spec->zstat[k] ? 1 : 0;
     p->ser_on = true;
     return mcf_plan_series_reset(p);
@@ -2793,21 +2802,14 @@ int mcf_plan_series_enable(mcf_plan* p, const mcf_series_spec* spec) {
     return series_enable_checked(who, p, spec, 0);
 }
 
-// below ground Tz and soilm alone have a series (the streamed plan's other outputs are not made)
-static int check_series_below_vars(const std::string& who, const mcf_series_spec* s) {
-    for (int v = 0; s && v < MCF_NOUT; ++v)
-        if (s->var[v] && v != MCF_OUT_TZ && v != MCF_OUT_SOILM)
-            return fail(MCF_ERR_ARG, who + ": below ground Tz and soilm have a series, nothing else");
-    return MCF_OK;
-}
 int mcf_plan_series_enable_below(mcf_plan* p, const mcf_series_spec* spec) {
     const std::string who = "mcf_plan_series_enable_below";
     if (!p || !spec) return fail(MCF_ERR_ARG, who + ": null argument");
     if (!p->bg_stream || !p->tiled) return fail(MCF_ERR_STATE, who + " needs a streamed plan (mcf_plan_create_streamed) with reqhgt < 0");
-    if (const int rc = check_series_below_vars(who, spec)) return rc;
+    if (const int rc = mcf::check_below_vars(who, spec->var, "have a series")) return rc;
     const int D = std::max<int>(1, (int)p->depths.size());
     if (const int rc = series_enable_checked(who, p, spec, spec->var[MCF_OUT_TZ] ? D - 1 : 0)) return rc;
-    p->ser_below = true;
+    p->ser_places.below = true;
     return MCF_OK;
 }
 
@@ -2816,8 +2818,8 @@ int mcf_plan_series_reset(mcf_plan* p) {
     if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
     HIP_TRY(hipSetDevice(p->device));
     if (p->d_ser_points)
-        mcf::launch_fill(p->d_ser_points, p->ser_nsel * p->ser_npoints * std::max<int64_t>(p->tsteps, 1), mcf::na_real_host(), p->stream);
-    if (p->d_ser_state) mcf::launch_series_init(p->d_ser_state, p->ser_nsel, p->ser_nzones, (int64_t)p->ndays * 24, p->stream);
+        mcf::launch_fill(p->d_ser_points, p->ser_places.nsel * p->ser_npoints * std::max<int64_t>(p->tsteps, 1), mcf::na_real_host(), p->stream);
+    if (p->d_ser_state) mcf::launch_series_init(p->d_ser_state, p->ser_places.nsel, p->ser_nzones, (int64_t)p->ndays * 24, p->stream);
     HIP_TRY(hipGetLastError());
     p->ser_done.assign((size_t)std::max(p->ndays, 1), 0);
     return MCF_OK;
@@ -2826,66 +2828,51 @@ int mcf_plan_series_reset(mcf_plan* p) {
 int mcf_plan_series_accumulate(mcf_plan* p, int32_t slot, int32_t slot_day0, int32_t day0, int32_t ndays) {
     if (!p) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: null plan");
     if (!p->ser_on) return fail(MCF_ERR_STATE, "the plan has no series sink: mcf_plan_series_enable first");
-    if (slot < 0 || slot >= p->ring_slots) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: slot out of range");
-    if (day0 < 0 || ndays < 1 || (int64_t)day0 + ndays > p->ndays) return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: day range out of bounds");
-    if (slot_day0 < 0 || (int64_t)slot_day0 + ndays > p->ring_days)
-        return fail(MCF_ERR_ARG, "mcf_plan_series_accumulate: more days than the ring slot holds");
+    if (const int rc = mcf::check_fold_range("mcf_plan_series_accumulate", p->ring_slots, p->ring_days, p->ndays, slot, slot_day0, day0, ndays))
+        return rc;
     for (int d = day0; d < day0 + ndays; ++d)
         if (p->ser_done[(size_t)d])
             return fail(MCF_ERR_STATE, "mcf_plan_series_accumulate: day " + std::to_string(d) + " has been folded already (each day at most once)");
     HIP_TRY(hipSetDevice(p->device));
     if (p->ser_npoints > 0) {
         mcf::SeriesPointsArgs a{};
-        for (int v = 0; v < MCF_NOUT; ++v)
-            if (p->ser_sel1[v]) a.src[p->ser_sel1[v] - 1] = ring_view(p, slot, v);
-        a.nsel = p->ser_nmain;
         a.step0 = (int64_t)slot_day0 * 24; a.nsteps = (int64_t)ndays * 24;
         a.cells = p->d_ser_cells; a.ncells = p->ser_npoints;
-        a.dst = p->d_ser_points; a.dst_steps = std::max<int64_t>(p->tsteps, 1); a.dst_step0 = (int64_t)day0 * 24;
-        mcf::launch_series_points(a, p->stream);
-        // below ground: Tz at depths 1 .. D - 1, each one variable of its own slab beside the ring
-        for (int d = 1; d <= p->ser_nsel - p->ser_nmain; ++d) {
-            a.src[0] = depth_view(p, slot, d);
-            a.nsel = 1;
-            a.dst = p->d_ser_points + (int64_t)(p->ser_nmain + d - 1) * p->ser_npoints * a.dst_steps;
+        a.dst_steps = std::max<int64_t>(p->tsteps, 1); a.dst_step0 = (int64_t)day0 * 24;
+        for_sink_sources(p, p->ser_places, slot, [&](const SinkSource& s) {
+            for (int i = 0; i < s.nsel; ++i) {
+                a.src[i] = s.view;
+                a.src[i].base += s.slab[i] * s.var_stride;
+            }
+            a.nsel = s.nsel;
+            a.dst = p->d_ser_points + (int64_t)s.place * p->ser_npoints * a.dst_steps;
             mcf::launch_series_points(a, p->stream);
-        }
+        });
     }
     if (p->ser_nzones > 0) {
         mcf::SeriesZonesArgs a{};
-        a.ring = p->d_ring + (int64_t)slot * p->slot_elems;
-        a.tile_stride = p->ring_tile_stride; a.day_stride = p->ring_day_stride; a.var_stride = p->ring_var_stride;
         a.N = p->N; a.ntiles = p->ntiles; a.cpb = p->cpb;
-        a.nsel = p->ser_nmain;
-        for (int v = 0; v < MCF_NOUT; ++v)
-            if (p->ser_sel1[v]) a.slab[p->ser_sel1[v] - 1] = p->var_slot[v];
         a.zone = p->d_ser_zone; a.nzones = p->ser_nzones;
         a.steps = (int64_t)p->ndays * 24;
         a.day0 = day0; a.ndays = ndays; a.slot_day0 = slot_day0;
-        a.state = p->d_ser_state;
-        mcf::launch_series_zones(a, p->ser_workgroups, p->stream);
-        for (int d = 1; d <= p->ser_nsel - p->ser_nmain; ++d) {      // (the existing kernel serves: only the view changes)
-            const mcf::RingView v = depth_view(p, slot, d);
-            a.ring = v.base; a.tile_stride = v.tile_stride; a.day_stride = v.day_stride; a.var_stride = 0;
-            a.nsel = 1; a.slab[0] = 0;
-            a.state = p->d_ser_state + (int64_t)(p->ser_nmain + d - 1) * mcf::kSeriesRows * p->ser_nzones * a.steps;
+        for_sink_sources(p, p->ser_places, slot, [&](const SinkSource& s) {      // (one kernel serves: only the view changes)
+            a.ring = s.view.base; a.tile_stride = s.view.tile_stride; a.day_stride = s.view.day_stride; a.var_stride = s.var_stride;
+            a.nsel = s.nsel;
+            for (int i = 0; i < s.nsel; ++i) a.slab[i] = s.slab[i];
+            a.state = p->d_ser_state + (int64_t)s.place * mcf::kSeriesRows * p->ser_nzones * a.steps;
             mcf::launch_series_zones(a, p->ser_workgroups, p->stream);
-        }
+        });
     }
     HIP_TRY(hipGetLastError());
     for (int d = day0; d < day0 + ndays; ++d) p->ser_done[(size_t)d] = 1;
     return MCF_OK;
 }
 
-// the place of (variable, depth) in the point buffer and the zone state: the variable's own, or (below ground) that of Tz at a
-// depth behind the first; -1 with the error set
+// the place of (variable, depth) in the point buffer and the zone state; -1 with the error set
 static int series_place(const std::string& who, mcf_plan* p, int32_t var, int32_t depth) {
-    if (var < 0 || var >= MCF_NOUT || !p->ser_sel1[var])
+    if (var < 0 || var >= MCF_NOUT || !p->ser_places.sel1[var])
         return fail(MCF_ERR_ARG, who + ": variable was not selected in mcf_plan_series_enable"), -1;
-    if (depth < 0 || depth > (var == MCF_OUT_TZ ? p->ser_nsel - p->ser_nmain : 0))
-        return fail(MCF_ERR_ARG, var == MCF_OUT_TZ ? who + ": depth " + std::to_string(depth) + " is outside the plan's list"
-                                                   : who + ": only Tz is kept per depth (depth 0 for soilm)"), -1;
-    return depth == 0 ? p->ser_sel1[var] - 1 : p->ser_nmain + depth - 1;
+    return p->ser_places.place(who, var, depth);
 }
 static int series_fetch_points(const std::string& who, mcf_plan* p, int32_t depth, int32_t var, double* dst) {
     if (!p || !dst) return fail(MCF_ERR_ARG, who + ": null argument");
@@ -2902,7 +2889,7 @@ int mcf_plan_series_fetch_points(mcf_plan* p, int32_t var, double* dst) {
     return series_fetch_points("mcf_plan_series_fetch_points", p, 0, var, dst);
 }
 int mcf_plan_series_fetch_points_depth(mcf_plan* p, int32_t depth, int32_t var, double* dst) {
-    if (p && !p->ser_below)
+    if (p && !p->ser_places.below)
         return fail(MCF_ERR_STATE, "mcf_plan_series_fetch_points_depth: the plan has no below-ground series sink (mcf_plan_series_enable_below)");
     return series_fetch_points("mcf_plan_series_fetch_points_depth", p, depth, var, dst);
 }
@@ -2927,7 +2914,7 @@ int mcf_plan_series_fetch_zones(mcf_plan* p, int32_t var, int32_t zstat, double*
     return series_fetch_zones("mcf_plan_series_fetch_zones", p, 0, var, zstat, dst);
 }
 int mcf_plan_series_fetch_zones_depth(mcf_plan* p, int32_t depth, int32_t var, int32_t zstat, double* dst) {
-    if (p && !p->ser_below)
+    if (p && !p->ser_places.below)
         return fail(MCF_ERR_STATE, "mcf_plan_series_fetch_zones_depth: the plan has no below-ground series sink (mcf_plan_series_enable_below)");
     return series_fetch_zones("mcf_plan_series_fetch_zones_depth", p, depth, var, zstat, dst);
 }
@@ -2957,12 +2944,12 @@ int series_spec_check(const std::string& who, const mcf_series_spec* s, int64_t 
 // a plan's raw zone state of one variable, [4][nzones][whole days x 24] of int64, and its folded days [days] (either may be
 // null), behind everything on the plan's stream
 int plan_series_state(mcf_plan* p, int32_t var, int64_t* host_state, int32_t* day_done) {
-    if (!p || !p->ser_on || var < 0 || var >= MCF_NOUT || !p->ser_sel1[var] || p->ser_nzones == 0)
+    if (!p || !p->ser_on || var < 0 || var >= MCF_NOUT || !p->ser_places.sel1[var] || p->ser_nzones == 0)
         return fail(MCF_ERR_STATE, "plan: no zone state of this variable");
     HIP_TRY(hipSetDevice(p->device));
     const int64_t n = (int64_t)kSeriesRows * p->ser_nzones * p->ndays * 24;
     if (host_state && n > 0)
-        HIP_TRY(hipMemcpyAsync(host_state, p->d_ser_state + (int64_t)(p->ser_sel1[var] - 1) * n, (size_t)n * 8, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipMemcpyAsync(host_state, p->d_ser_state + (int64_t)(p->ser_places.sel1[var] - 1) * n, (size_t)n * 8, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     if (day_done) std::copy(p->ser_done.begin(), p->ser_done.begin() + p->ndays, day_done);
     return MCF_OK;
@@ -2986,49 +2973,36 @@ static int run_series(const std::string& who, const mcf_grid_inputs* in, const m
     if (opt_in->reqhgt < 0.0) return fail(MCF_ERR_ARG, who + ": the series sink needs reqhgt >= 0 (the tiled ring)");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, who + ": negative chunk_days");
     if ((rc = check_series_spec(who, spec, in->rows, in->cols, nullptr))) return rc;
-    for (int v = 0; v < MCF_NOUT && !raw; ++v) {
-        if (!spec->var[v]) continue;
-        if (spec->npoints > 0 && !out->points[v]) return fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (spec->nzones > 0 && spec->zstat[k] && !out->zones[v][k])
-                return fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
-    }
-    const int ndays = (int)(in->tsteps / 24);
-    mcf_options opt = *opt_in;
-    int nsel = 0;
-    for (int v = 0; v < MCF_NOUT; ++v) nsel += (opt.out[v] = spec->var[v] ? 1 : 0);
-    if ((rc = ensure_device(opt.device))) return rc;
-    int chunk = chunk_days;
-    if (chunk == 0)
-        chunk = ring_budget_days("MCF_SUMMARY_RING_GB", nsel + (in->array_forcing == 1 ? 15 : 0), in->rows * in->cols,
-                                 opt.cells_per_block ? opt.cells_per_block : 21);
-    chunk = std::max(1, std::min(chunk, std::max(ndays, 1)));
-    mcf_plan* p = nullptr;
-    if ((rc = plan_create(in, &opt, chunk, 1, false, &p, nullptr))) return rc;
-    PlanHolder holder(p);
-    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
-    if ((rc = mcf_plan_series_enable(p, spec))) return rc;
-    if ((rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) { return mcf_plan_series_accumulate(p, 0, 0, d0, nd); }))) return rc;
-    const int64_t T = std::max<int64_t>(in->tsteps, 1);
-    for (int v = 0; v < MCF_NOUT; ++v) {
-        if (!spec->var[v]) continue;
-        if (raw) {
-            if (spec->npoints > 0) {
-                raw->points[v].resize((size_t)(T * spec->npoints));
-                if ((rc = mcf_plan_series_fetch_points(p, v, raw->points[v].data()))) return rc;
+    if (!raw && (rc = mcf::check_series_out(who, spec, out))) return rc;
+    RunSink sink;
+    for (int v = 0; v < MCF_NOUT; ++v) sink.out[v] = spec->var[v] ? 1 : 0;
+    sink.enable = [&](mcf_plan* p) { return mcf_plan_series_enable(p, spec); };
+    sink.fold = [](mcf_plan* p, int d0, int nd) { return mcf_plan_series_accumulate(p, 0, 0, d0, nd); };
+    sink.finish = [&](mcf_plan* p) -> int {
+        const int ndays = (int)(in->tsteps / 24);
+        const int64_t T = std::max<int64_t>(in->tsteps, 1);
+        int rcf;
+        for (int v = 0; v < MCF_NOUT; ++v) {
+            if (!spec->var[v]) continue;
+            if (raw) {
+                if (spec->npoints > 0) {
+                    raw->points[v].resize((size_t)(T * spec->npoints));
+                    if ((rcf = mcf_plan_series_fetch_points(p, v, raw->points[v].data()))) return rcf;
+                }
+                if (spec->nzones > 0) {
+                    raw->state[v].resize((size_t)((int64_t)mcf::kSeriesRows * spec->nzones * ndays * 24));
+                    raw->done.assign((size_t)std::max(ndays, 1), 0);
+                    if ((rcf = mcf::plan_series_state(p, v, raw->state[v].data(), raw->done.data()))) return rcf;
+                }
+                continue;
             }
-            if (spec->nzones > 0) {
-                raw->state[v].resize((size_t)((int64_t)mcf::kSeriesRows * spec->nzones * ndays * 24));
-                raw->done.assign((size_t)std::max(ndays, 1), 0);
-                if ((rc = mcf::plan_series_state(p, v, raw->state[v].data(), raw->done.data()))) return rc;
-            }
-            continue;
+            if (spec->npoints > 0 && (rcf = mcf_plan_series_fetch_points(p, v, out->points[v]))) return rcf;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (spec->nzones > 0 && spec->zstat[k] && (rcf = mcf_plan_series_fetch_zones(p, v, k, out->zones[v][k]))) return rcf;
         }
-        if (spec->npoints > 0 && (rc = mcf_plan_series_fetch_points(p, v, out->points[v]))) return rc;
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (spec->nzones > 0 && spec->zstat[k] && (rc = mcf_plan_series_fetch_zones(p, v, k, out->zones[v][k]))) return rc;
-    }
-    return mcf_plan_sync(p);
+        return MCF_OK;
+    };
+    return run_sink(in, opt_in, chunk_days, sink, twi_mean);
 }
 int mcf_runmicro_series(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_series_spec* spec, int32_t chunk_days,
                         mcf_series_out* out) {
@@ -3238,72 +3212,30 @@ static int bioclim_depths_finish(mcf_plan* p, const mcf_grid_inputs* in, const B
     return mcf_plan_sync(p);
 }
 
-// the series sink's arguments (mcf_runmicro_depths_series)
-struct SeriesDepthsSink {
-    const mcf_series_spec* spec;
-    mcf_depth_series_out* out;
-};
-// the one-call entries: `out` (every step of every depth), `spec` + `sout` (the period summaries), `bio` (the bioclim variables)
-// or `ser` (the series sink)
+// The one-call entries' driver: a streamed below-ground plan with the depth list, through day chunks of `chunk_days` days (0: what
+// the free memory gives), for the entry's sink: every step of every depth, the period summaries, the bioclim variables or the series
 static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
-                      const double* tbp, mcf_depth_outputs* out, const mcf_summary_spec* spec, int32_t chunk_days,
-                      mcf_depth_summary_out* sout, const BioDepthsSink* bio = nullptr, const SeriesDepthsSink* ser = nullptr) {
+                      const double* tbp, int32_t chunk_days, const RunSink& sink) {
     const std::string w = std::string(who) + ": ";
-    if (!in || !opt_in || (!out && !sout && !bio && !ser) || (sout && !spec)) return fail(MCF_ERR_ARG, w + "null argument");
+    if (!in || !opt_in) return fail(MCF_ERR_ARG, w + "null argument");
     mcf_options opt = *opt_in;
-    if (bio) opt.complete = 1;                                          // cpp:3576: complete = true
     int rc = check_depths(who, depths, D, tbp, opt.complete != 0, in->array_forcing != 0);
     if (rc) return rc;
-    if (bio && (rc = check_bioclim_depths(w, in, bio, D))) return rc;
     opt.reqhgt = depths[0];
     if ((rc = check_inputs(in, &opt))) return rc;
     const int64_t T = in->tsteps;
     const int ndays = (int)(T / 24);
     if (ndays < 1) return fail(MCF_ERR_ARG, w + "the series is shorter than a day");
     if (chunk_days < 0) return fail(MCF_ERR_ARG, w + "negative chunk_days");
-    for (int v = 0; v < MCF_NOUT; ++v) opt.out[v] = 0;
-    if (bio) {
-        opt.out[MCF_OUT_TZ] = opt.out[MCF_OUT_SOILM] = 1;               // cpp:3569-3575 with air = 1
-    } else if (out) {
-        for (int d = 0; d < D; ++d)
-            if (!out->tz[d]) return fail(MCF_ERR_ARG, w + "tz[" + std::to_string(d) + "] is a null buffer");
-        opt.out[MCF_OUT_TZ] = 1;
-        opt.out[MCF_OUT_SOILM] = out->soilm ? 1 : 0;
-    } else if (ser) {      // (mcf_runmicro_depths_series has judged the spec)
-        for (int d = 0; ser->spec->var[MCF_OUT_TZ] && d < D; ++d) {
-            if (ser->spec->npoints > 0 && !ser->out->tz_points[d]) return fail(MCF_ERR_ARG, w + "a depth has a null point buffer");
-            for (int k = 0; k < MCF_NZSTAT; ++k)
-                if (ser->spec->nzones > 0 && ser->spec->zstat[k] && !ser->out->tz_zones[d][k])
-                    return fail(MCF_ERR_ARG, w + "a selected (depth, statistic) has a null buffer");
-        }
-        if (ser->spec->var[MCF_OUT_SOILM]) {
-            if (ser->spec->npoints > 0 && !ser->out->soilm_points) return fail(MCF_ERR_ARG, w + "soilm has a null point buffer");
-            for (int k = 0; k < MCF_NZSTAT; ++k)
-                if (ser->spec->nzones > 0 && ser->spec->zstat[k] && !ser->out->soilm_zones[k])
-                    return fail(MCF_ERR_ARG, w + "a selected statistic of soilm has a null buffer");
-        }
-        opt.out[MCF_OUT_TZ] = 1;
-        opt.out[MCF_OUT_SOILM] = ser->spec->var[MCF_OUT_SOILM] ? 1 : 0;
-    } else {
-        if ((rc = check_summary_below_vars(who, spec))) return rc;
-        if ((rc = check_summary_spec(spec, ndays, nullptr))) return rc;
-        for (int k = 0; k < MCF_NSTAT; ++k) {
-            if (!spec->stat[k]) continue;
-            for (int d = 0; spec->var[MCF_OUT_TZ] && d < D; ++d)
-                if (!sout->tz[d][k]) return fail(MCF_ERR_ARG, w + "a selected (depth, statistic) has a null buffer");
-            if (spec->var[MCF_OUT_SOILM] && !sout->soilm[k]) return fail(MCF_ERR_ARG, w + "a selected statistic of soilm has a null buffer");
-        }
-        // (the depth list lives on a plan with Tz; soilm alone is summarised beside it)
-        opt.out[MCF_OUT_TZ] = 1;
-        opt.out[MCF_OUT_SOILM] = spec->var[MCF_OUT_SOILM] ? 1 : 0;
-    }
+    if (sink.check && (rc = sink.check())) return rc;
+    for (int v = 0; v < MCF_NOUT; ++v) opt.out[v] = sink.out[v];
     if ((rc = ensure_device(opt.device))) return rc;
     const int nvars = 1 + opt.out[MCF_OUT_SOILM];
     const bool tail = T > (int64_t)ndays * 24;      // the steps behind the last whole day: one day more per slot
-    int chunk = out ? opt.days_per_chunk : chunk_days;
+    int chunk = chunk_days;
     // (the solver's variables, the forcing ring, the chunk's Tg ring and the D - 1 depth slabs per day)
     if (chunk <= 0 && (rc = free_memory_chunk_days(in->rows * in->cols, ndays, 1, nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1),
-                                                   below_state_doubles(D, ndays) + (bio ? bioclim_state_doubles(D) : 0.0), tail, &chunk)))
+                                                   below_state_doubles(D, ndays) + sink.state_doubles, tail, &chunk)))
         return rc;
     chunk = std::max(1, std::min(chunk, ndays));
     mcf_plan* p = nullptr;
@@ -3311,90 +3243,125 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     PlanHolder holder(p);
     if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
     if ((rc = mcf_plan_below_prepare(p, in))) return rc;
-    if (sout && (rc = mcf_plan_summary_enable_below(p, spec))) return rc;
-    if (ser && (rc = mcf_plan_series_enable_below(p, ser->spec))) return rc;
-    mcf::BioAccDepthsArgs acc{};
-    if (bio && (rc = bioclim_depths_begin(p, bio->sel, acc))) return rc;
-    const int64_t pitch = host_pitch(in), HS = pitch * in->cols;
-    rc = for_day_chunks(p, in, ndays, chunk, [&](int d0, int nd) -> int {
-        if (sout) return mcf_plan_summary_accumulate(p, 0, 0, d0, nd);
-        if (ser) return mcf_plan_series_accumulate(p, 0, 0, d0, nd);
-        if (bio) {
-            ++g_bioclim_chunks;
-            return bioclim_depths_fold(p, bio->sel, acc, d0, nd);
-        }
+    return run_sink_chunks(p, in, ndays, chunk, sink);
+}
+// every step of every depth; the chunk size is the options' own (days_per_chunk)
+int mcf_runmicro_depths(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t D, const double* tbp,
+                        mcf_depth_outputs* out) {
+    const std::string w = "mcf_runmicro_depths: ";
+    if (!out) return fail(MCF_ERR_ARG, w + "null argument");
+    RunSink sink;
+    sink.out[MCF_OUT_TZ] = 1;
+    sink.out[MCF_OUT_SOILM] = out->soilm ? 1 : 0;
+    sink.check = [&]() -> int {
+        for (int d = 0; d < D; ++d)
+            if (!out->tz[d]) return fail(MCF_ERR_ARG, w + "tz[" + std::to_string(d) + "] is a null buffer");
+        return MCF_OK;
+    };
+    sink.enable = [](mcf_plan*) { return (int)MCF_OK; };
+    sink.fold = [&](mcf_plan* p, int d0, int nd) -> int {
+        const int64_t T = in->tsteps, pitch = host_pitch(in), HS = pitch * in->cols;
         // ... the last chunk with the steps it left behind its days
-        const int64_t steps = (int64_t)nd * 24 + (d0 + nd == ndays ? T - (int64_t)ndays * 24 : 0);
+        const int64_t steps = (int64_t)nd * 24 + (d0 + nd == (int)(T / 24) ? T % 24 : 0);
         for (int d = 0; d < D; ++d)
             if (const int rcf = mcf_plan_fetch_depth_pitched(p, 0, d, 0, steps, out->tz[d] + HS * (int64_t)d0 * 24, pitch)) return rcf;
         if (!out->soilm) return MCF_OK;
         return mcf_plan_fetch_pitched(p, 0, MCF_OUT_SOILM, 0, (int64_t)nd * 24, out->soilm + HS * (int64_t)d0 * 24, pitch);
-    });
-    if (rc) return rc;
-    if (bio) return bioclim_depths_finish(p, in, bio, acc);
-    if (sout) {
+    };
+    sink.finish = [&](mcf_plan*) {
+        if (out->soilm) fill_tail_na(out->soilm, in, (int)(in->tsteps / 24));
+        return (int)MCF_OK;
+    };
+    return run_depths("mcf_runmicro_depths", in, opt, depths, D, tbp, opt ? std::max(opt->days_per_chunk, 0) : 0, sink);
+}
+int mcf_runmicro_depths_summary(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t D,
+                                const double* tbp, const mcf_summary_spec* spec, int32_t chunk_days, mcf_depth_summary_out* out) {
+    const char* who = "mcf_runmicro_depths_summary";
+    if (!out || !spec) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
+    RunSink sink;
+    // (the depth list lives on a plan with Tz; soilm alone is summarised beside it)
+    sink.out[MCF_OUT_TZ] = 1;
+    sink.out[MCF_OUT_SOILM] = spec->var[MCF_OUT_SOILM] ? 1 : 0;
+    sink.check = [&]() -> int {
+        int rc = mcf::check_below_vars(who, spec->var, "can be summarised");
+        if (!rc) rc = check_summary_spec(spec, in->tsteps / 24, nullptr);
+        return rc ? rc : mcf::check_depth_summary_out(who, spec, D, out);
+    };
+    sink.enable = [&](mcf_plan* p) { return mcf_plan_summary_enable_below(p, spec); };
+    sink.fold = [](mcf_plan* p, int d0, int nd) { return mcf_plan_summary_accumulate(p, 0, 0, d0, nd); };
+    sink.finish = [&](mcf_plan* p) -> int {
+        int rc;
         for (int k = 0; k < MCF_NSTAT; ++k) {
             if (!spec->stat[k]) continue;
             for (int d = 0; spec->var[MCF_OUT_TZ] && d < D; ++d)
-                if ((rc = summary_fetch_pitched(p, MCF_OUT_TZ, k, sout->tz[d][k], 0, d))) return rc;
-            if (spec->var[MCF_OUT_SOILM] && (rc = summary_fetch_pitched(p, MCF_OUT_SOILM, k, sout->soilm[k], 0))) return rc;
+                if ((rc = summary_fetch_pitched(p, MCF_OUT_TZ, k, out->tz[d][k], 0, d))) return rc;
+            if (spec->var[MCF_OUT_SOILM] && (rc = summary_fetch_pitched(p, MCF_OUT_SOILM, k, out->soilm[k], 0))) return rc;
         }
-        if (sout->days && (rc = mcf_plan_summary_days(p, sout->days))) return rc;
-        return mcf_plan_sync(p);
-    }
-    if (ser) {
-        const mcf_series_spec* sp = ser->spec;
-        for (int d = 0; sp->var[MCF_OUT_TZ] && d < D; ++d) {
-            if (sp->npoints > 0 && (rc = mcf_plan_series_fetch_points_depth(p, d, MCF_OUT_TZ, ser->out->tz_points[d]))) return rc;
-            for (int k = 0; k < MCF_NZSTAT; ++k)
-                if (sp->nzones > 0 && sp->zstat[k] && (rc = mcf_plan_series_fetch_zones_depth(p, d, MCF_OUT_TZ, k, ser->out->tz_zones[d][k]))) return rc;
-        }
-        if (sp->var[MCF_OUT_SOILM]) {
-            if (sp->npoints > 0 && (rc = mcf_plan_series_fetch_points_depth(p, 0, MCF_OUT_SOILM, ser->out->soilm_points))) return rc;
-            for (int k = 0; k < MCF_NZSTAT; ++k)
-                if (sp->nzones > 0 && sp->zstat[k] && (rc = mcf_plan_series_fetch_zones_depth(p, 0, MCF_OUT_SOILM, k, ser->out->soilm_zones[k]))) return rc;
-        }
-        return mcf_plan_sync(p);
-    }
-    if (out->soilm) fill_tail_na(out->soilm, in, ndays);
-    return mcf_plan_sync(p);
-}
-int mcf_runmicro_depths(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths, const double* tbp,
-                        mcf_depth_outputs* out) {
-    if (!out) return fail(MCF_ERR_ARG, "mcf_runmicro_depths: null argument");
-    return run_depths("mcf_runmicro_depths", in, opt, depths, ndepths, tbp, out, nullptr, 0, nullptr);
-}
-int mcf_runmicro_depths_summary(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths,
-                                const double* tbp, const mcf_summary_spec* spec, int32_t chunk_days, mcf_depth_summary_out* out) {
-    if (!out || !spec) return fail(MCF_ERR_ARG, "mcf_runmicro_depths_summary: null argument");
-    return run_depths("mcf_runmicro_depths_summary", in, opt, depths, ndepths, tbp, nullptr, spec, chunk_days, out);
+        return out->days ? mcf_plan_summary_days(p, out->days) : (int)MCF_OK;
+    };
+    return run_depths(who, in, opt, depths, D, tbp, chunk_days, sink);
 }
 
-int mcf_runmicro_depths_series(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t ndepths,
+int mcf_runmicro_depths_series(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t D,
                                const double* tbp, const mcf_series_spec* spec, int32_t chunk_days, mcf_depth_series_out* out) {
     const std::string who = "mcf_runmicro_depths_series";
     if (!spec) return fail(MCF_ERR_ARG, who + ": null mcf_series_spec");
     if (!out || !in) return fail(MCF_ERR_ARG, who + ": null argument");
     int rc = check_series_spec(who, spec, in->rows, in->cols, nullptr);      // (nothing here needs a device)
-    if (!rc) rc = check_series_below_vars(who, spec);
+    if (!rc) rc = mcf::check_below_vars(who, spec->var, "have a series");
     if (rc) return rc;
-    const SeriesDepthsSink ser{spec, out};
-    return run_depths("mcf_runmicro_depths_series", in, opt, depths, ndepths, tbp, nullptr, nullptr, chunk_days, nullptr, nullptr, &ser);
+    RunSink sink;
+    sink.out[MCF_OUT_TZ] = 1;
+    sink.out[MCF_OUT_SOILM] = spec->var[MCF_OUT_SOILM] ? 1 : 0;
+    sink.check = [&] { return mcf::check_depth_series_out(who, spec, D, out); };
+    sink.enable = [&](mcf_plan* p) { return mcf_plan_series_enable_below(p, spec); };
+    sink.fold = [](mcf_plan* p, int d0, int nd) { return mcf_plan_series_accumulate(p, 0, 0, d0, nd); };
+    sink.finish = [&](mcf_plan* p) -> int {
+        int rcf;
+        for (int d = 0; spec->var[MCF_OUT_TZ] && d < D; ++d) {
+            if (spec->npoints > 0 && (rcf = mcf_plan_series_fetch_points_depth(p, d, MCF_OUT_TZ, out->tz_points[d]))) return rcf;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (spec->nzones > 0 && spec->zstat[k] && (rcf = mcf_plan_series_fetch_zones_depth(p, d, MCF_OUT_TZ, k, out->tz_zones[d][k]))) return rcf;
+        }
+        if (!spec->var[MCF_OUT_SOILM]) return MCF_OK;
+        if (spec->npoints > 0 && (rcf = mcf_plan_series_fetch_points_depth(p, 0, MCF_OUT_SOILM, out->soilm_points))) return rcf;
+        for (int k = 0; k < MCF_NZSTAT; ++k)
+            if (spec->nzones > 0 && spec->zstat[k] && (rcf = mcf_plan_series_fetch_zones_depth(p, 0, MCF_OUT_SOILM, k, out->soilm_zones[k]))) return rcf;
+        return MCF_OK;
+    };
+    return run_depths("mcf_runmicro_depths_series", in, opt, depths, D, tbp, chunk_days, sink);
 }
 
 // the bioclim sink on that driver (include/mcf.h); layered vegetation as run_bioclim takes it
-int mcf_runbioclim_depths(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_bioclim_sel* sel, const double* depths,
-                          int32_t ndepths, int32_t chunk_days, mcf_bioclim_depths_out* out) {
+int mcf_runbioclim_depths(const mcf_grid_inputs* in, const mcf_options* opt_in, const mcf_bioclim_sel* sel, const double* depths,
+                          int32_t D, int32_t chunk_days, mcf_bioclim_depths_out* out) {
     const char* who = "mcf_runbioclim_depths";
     g_bioclim_chunks = 0;
-    if (!in || !opt || !sel || !out) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
+    if (!in || !opt_in || !sel || !out) return fail(MCF_ERR_ARG, std::string(who) + ": null argument");
     mcf_grid_inputs in_l = *in;
     if (in->veg_layers > 1) {      // runbioclim3Cpp's fixed dfsel: fourteen one-day layers; later days belong to no layer
         if (in->veg_layers < 14) return fail(MCF_ERR_ARG, std::string(who) + ": layered vegetation needs the fourteen layers of runbioclim3Cpp");
         in_l.veg_layers = 14; in_l.lyr_st = kBioSt; in_l.lyr_ed = kBioEd;
     }
+    mcf_options opt = *opt_in;
+    opt.complete = 1;                                                   // cpp:3576: complete = true
     const BioDepthsSink bio{sel, out};
-    const int rc = run_depths(who, &in_l, opt, depths, ndepths, nullptr, nullptr, nullptr, chunk_days, nullptr, &bio);
+    mcf::BioAccDepthsArgs acc{};
+    // the sink's own refusals come behind the depth list's (they read D buffers) and ahead of the driver's other checks
+    int rc = check_depths(who, depths, D, nullptr, true, in_l.array_forcing != 0);
+    if (!rc) rc = check_bioclim_depths(std::string(who) + ": ", &in_l, &bio, D);
+    if (!rc) {
+        RunSink sink;
+        sink.out[MCF_OUT_TZ] = sink.out[MCF_OUT_SOILM] = 1;             // cpp:3569-3575 with air = 1
+        sink.state_doubles = bioclim_state_doubles(D);
+        sink.enable = [&](mcf_plan* p) { return bioclim_depths_begin(p, sel, acc); };
+        sink.fold = [&](mcf_plan* p, int d0, int nd) {
+            ++g_bioclim_chunks;
+            return bioclim_depths_fold(p, sel, acc, d0, nd);
+        };
+        sink.finish = [&](mcf_plan* p) { return bioclim_depths_finish(p, &in_l, &bio, acc); };
+        rc = run_depths(who, &in_l, &opt, depths, D, nullptr, chunk_days, sink);
+    }
     if (rc && g_err.compare(0, strlen(who), who) != 0) g_err = std::string(who) + ": " + g_err;      // (the shared checks' messages)
     return rc;
 }
@@ -3751,13 +3718,7 @@ int mcf_runmicro_series_multi(const mcf_grid_inputs* in, const mcf_options* opt,
     if (chunk_days < 0) return fail(MCF_ERR_ARG, who + ": negative chunk_days");
     int rc = check_series_spec(who, spec, in->rows, in->cols, nullptr);
     if (rc) return rc;
-    for (int v = 0; v < MCF_NOUT; ++v) {
-        if (!spec->var[v]) continue;
-        if (spec->npoints > 0 && !out->points[v]) return fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (spec->nzones > 0 && spec->zstat[k] && !out->zones[v][k])
-                return fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
-    }
+    if ((rc = mcf::check_series_out(who, spec, out))) return rc;
     struct BlockResult { mcf::SeriesBlockCut cut; SeriesRaw raw; };
     std::vector<std::unique_ptr<BlockResult>> results;
     std::mutex results_lock;

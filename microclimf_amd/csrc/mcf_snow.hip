@@ -27,6 +27,7 @@
 #include "mcf_hiphost.hpp"
 #include "mcf_snow_device.hpp"
 #include "mcf_snow_plan.hpp"
+#include "mcf_sinks_host.hpp"
 
 // the ring kernel (lane per cell-hour, cell table in LDS, step record through scalar loads): 141 VGPRs without scratch at three
 // waves per SIMD, 128 + 44 B (eight spill stores and loads per hour) at four — measured 0.515 against 0.55 s per simulated year
@@ -4040,14 +4041,8 @@ extern "C" int mcf_snowplan_summary_enable(mcf_snowplan* sp, const mcf_snowpack_
     const int64_t nd = std::max(ndays, 1), np = spec->nperiods;
     const int64_t state_bytes = (int64_t)nsel * np * nrows * sp->N * 8, plane_bytes = np * sp->N * 8;
     if ((rc = check_room(state_bytes + plane_bytes + (3 * nd + np) * 4))) return rc;
-    std::vector<int32_t> pod((size_t)nd, -1), prev((size_t)nd, -1), next((size_t)nd, (int32_t)ndays), last((size_t)np, -1);
-    for (int d = 0; d < ndays; ++d) {
-        const int per = pod[(size_t)d] = spec->period_of_day[d];
-        if (per < 0) continue;
-        prev[(size_t)d] = last[(size_t)per];
-        if (last[(size_t)per] >= 0) next[(size_t)last[(size_t)per]] = d;
-        last[(size_t)per] = d;
-    }
+    std::vector<int32_t> pod, prev, next;
+    if ((rc = mcf::period_tables(spec->period_of_day, ndays, (int)np, pod, prev, next))) return rc;
     int32_t** tabs[3] = {&sp->d_ps_pod, &sp->d_ps_prev, &sp->d_ps_next};
     const std::vector<int32_t>* host[3] = {&pod, &prev, &next};
     for (int i = 0; i < 3; ++i) {

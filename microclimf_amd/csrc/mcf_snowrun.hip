@@ -45,6 +45,7 @@
 #include <algorithm>
 #include <atomic>
 #include <exception>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -52,6 +53,7 @@
 #include "mcf_rowblocks.hpp"
 #include "mcf_snow_plan.hpp"
 #include "mcf_series_host.hpp"
+#include "mcf_sinks_host.hpp"
 
 namespace mcf {   // mcf_api.hip
 int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask);
@@ -115,15 +117,19 @@ struct SnowBlocks {
     }
 };
 
-// block b's snow plan on `device`: one block reads the caller's arrays in place, more gather their rows.  co: coarse array
-// weather (one block; `snow` is co->drv) — the plan expands its chunks from the resident coarse arrays, pointm$umu goes to umu_out
-int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& snow, const mcf_snowcoarse_in* co = nullptr,
-                   double* umu_out = nullptr) {
+// coarse array weather as a snow plan's source (one block; the driver's inputs are co->drv): the plan expands its chunks from the
+// resident coarse arrays, pointm$umu goes to umu_out.  Empty: the weather is the driver's own
+struct CoarseSource {
+    const mcf_snowcoarse_in* co;
+    double* umu_out;
+};
+// block b's snow plan on `device`: one block reads the caller's arrays in place, more gather their rows
+int block_snowplan(SnowBlocks& sb, int b, int device, const mcf_snowdriver_in& snow, const CoarseSource& coarse = {}) {
     Block& k = sb.blocks[(size_t)b];
     const int64_t R = sb.R, C = sb.C;
     k.device = device;
     k.r0 = R * b / sb.nb; k.nr = R * (b + 1) / sb.nb - k.r0;
-    if (co) return mcf::snowplan_create_coarse(co, umu_out, device, &k.sp);
+    if (coarse.co) return mcf::snowplan_create_coarse(coarse.co, coarse.umu_out, device, &k.sp);
     mcf_snowdriver_in bi = snow;
     mcf::model_rasters_of_block(bi, sb.nb > 1 ? &k.model_rows : nullptr, R, C, k.r0, k.nr);
     return mcf_snowplan_create(&bi, k.r0, R, k.device, &k.sp);
@@ -286,6 +292,9 @@ struct mcf_snowrun : SnowBlocks {
     std::vector<int32_t> szone, spzone;
     uint32_t ser_pack_bits = 0;
 };
+// a run on its way to the caller, or a one-call entry's own: destroyed on every path that does not release() it
+struct SnowRunDestroy { void operator()(mcf_snowrun* h) const { mcf_snowrun_destroy(h); } };
+using SnowRunHolder = std::unique_ptr<mcf_snowrun, SnowRunDestroy>;
 
 namespace {
 
@@ -393,9 +402,9 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
         int rc = co ? MCF_OK : check_create(in, opt, mu, below);
         if (rc) return rc;
         mcf_snowrun* h = new mcf_snowrun();
+        SnowRunHolder holder(h);
         h->below = below;
         h->coarse = co != nullptr; h->umu_out = umu_out;
-        struct Guard { mcf_snowrun* p; ~Guard() { delete p; } } guard{h};
         if ((rc = mcf::device_list(mu, opt->device, &h->devs))) return rc;
         h->grid = co ? *co->grid : *in->grid; h->opt = *opt; h->snow = co ? co->snow->drv : *in->snow;
         h->af = h->grid.array_forcing != 0;
@@ -415,7 +424,7 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
             mcf::for_blocks(w, h->nb, h->nt, [&](int b) -> int {
                 Block& k = h->blocks[(size_t)b];
                 // (the coarse run: one block, whose snow plan expands its chunks, and the microclimate's snow days, from coarse arrays)
-                int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow, co ? co->snow : nullptr, umu_out);
+                int rc2 = block_snowplan(*h, b, h->devs[(size_t)w.t], h->snow, {co ? co->snow : nullptr, umu_out});
                 if (!rc2 && co) rc2 = mcf::snowplan_micro_attach_coarse(k.sp, co->micro);
                 if (rc2) return rc2;
                 // ---- ... and its solver plan: the caller's arrays read in place through the row pitch
@@ -437,8 +446,7 @@ static int snowrun_create(const mcf_microsnow_in* in, const mcf_options* opt, co
             }
         });
         if (rc) return rc;
-        guard.p = nullptr;
-        *out = h;
+        *out = holder.release();
         return MCF_OK;
     } catch (const std::exception& e) {
         return api_fail(MCF_ERR_NOMEM, std::string("mcf_snowrun_create: ") + e.what());
@@ -759,6 +767,15 @@ int fold_series_days(const mcf_snowrun* h, Block& k, int slot, int d0, int nd) {
     return MCF_OK;
 }
 
+// a slot's merged days [d0, d0 + nd): into the summary, into the series sink, to the caller
+int fold_and_fetch(Pass2& p, Block& k, int slot, int d0, int nd) {
+    const mcf_snowrun* h = p.h;
+    int rc = MCF_OK;
+    if (h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, slot, 0, d0, nd);
+    if (!rc && k.ser_micro) rc = fold_series_days(h, k, slot, d0, nd);
+    return rc ? rc : fetch_days(p, k, slot, d0, nd);
+}
+
 // per chunk: restore + re-run the snow chunk unless its series were kept; the solver on its no-snow days; the snow-day kernel
 // over the slot; the slot's merged days to the caller.  Collective: every worker walks every chunk.
 void chunk_loop(Pass2& p, Worker& w) {
@@ -781,9 +798,7 @@ void chunk_loop(Pass2& p, Worker& w) {
             if (!rc && has_snow) rc = mcf_snowplan_microsnow(k.sp, k.plan, ch, slot, &h->nosnowday[(size_t)d0]);
             // the slot holds the merged days: folded on the plan's stream — behind the solver's launches on it, and behind the
             // snow-day kernel, whose null stream mcf_snowplan_microsnow has synchronised the device on before it returned
-            if (!rc && nd > 0 && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, slot, 0, d0, nd);
-            if (!rc && nd > 0 && k.ser_micro) rc = fold_series_days(h, k, slot, d0, nd);
-            if (!rc && nd > 0) rc = fetch_days(p, k, slot, d0, nd);
+            if (!rc && nd > 0) rc = fold_and_fetch(p, k, slot, d0, nd);
             return rc;
         });
         w.wait();
@@ -799,9 +814,7 @@ void tail_days(Pass2& p, Worker& w) {
         for (int d0 = h->nchunks * cd; d0 < h->ndays && !w.failed(); d0 += cd) {
             const int nd = std::min(cd, h->ndays - d0);
             int rc = solver_days(p, k, 0, -1, d0, nd, false);
-            if (!rc && h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, 0, 0, d0, nd);
-            if (!rc && k.ser_micro) rc = fold_series_days(h, k, 0, d0, nd);
-            if (!rc) rc = fetch_days(p, k, 0, d0, nd);
+            if (!rc) rc = fold_and_fetch(p, k, 0, d0, nd);
             if (rc) return rc;
         }
         if (h->sum_micro || h->ser_micro)          // (a sink-only run has no fetch that waits for the plan's stream)
@@ -920,39 +933,46 @@ extern "C" int mcf_snowrun_summary_days(mcf_snowrun* h, int32_t pack, int32_t* d
     return pack ? mcf_snowplan_summary_days(h->blocks[0].sp, days) : mcf_plan_summary_days(h->blocks[0].plan, days);
 }
 
+// The one-call entries with a sink: `check` (the entry's refusals, none of which needs a device), the run created and held, the
+// sink enabled, pass 1 — where a run for the snowpack's sink alone ends, unless the caller asks for the arrays — pass 2, `fetch`
+template <class Outs, class Check, class Enable, class Fetch>
+static int run_with_sink(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool micro, Outs* outs, Check&& check,
+                         Enable&& enable, Fetch&& fetch) {
+    int rc = check();
+    if (rc) return rc;
+    mcf_snowrun* h = nullptr;
+    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
+    SnowRunHolder holder(h);
+    if ((rc = enable(h))) return rc;
+    if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
+    if ((micro || outs->arrays) && (rc = mcf_snowrun_pass2(h, in->micro, in->mat, outs->arrays))) return rc;
+    return fetch(h);
+}
+
 extern "C" int mcf_runmicrosnow_summary(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu,
                                         const mcf_summary_spec* micro_spec, const mcf_snowpack_summary_spec* pack_spec,
                                         mcf_snowrun_summary_out* outs) {
     if (!outs) return api_fail(MCF_ERR_ARG, "null snow-run argument");
-    if (!micro_spec && !pack_spec) return api_fail(MCF_ERR_ARG, "snow-run summaries: null spec (one of the two is needed)");
-    if (opt && opt->reqhgt < 0) return api_fail(MCF_ERR_ARG, kSummaryBelow);
-    int rc = check_create(in, opt, mu, false);
-    if (rc) return rc;
-    if ((rc = check_summary_specs(micro_spec, pack_spec, *opt, in->grid->tsteps, in->snow->chunk_steps))) return rc;
-    for (int k = 0; k < MCF_NSTAT; ++k) {
-        for (int v = 0; micro_spec && v < MCF_NOUT; ++v)
-            if (micro_spec->var[v] && micro_spec->stat[k] && !outs->micro.val[v][k])
-                return api_fail(MCF_ERR_ARG, "summary: a selected (variable, statistic) has a null buffer");
-        for (int v = 0; pack_spec && v < 5; ++v)
-            if (pack_spec->series[v] && pack_spec->stat[k] && !outs->pack.val[v][k])
-                return api_fail(MCF_ERR_ARG, "snowpack summary: a selected (series, statistic) has a null buffer");
-    }
-    mcf_snowrun* h = nullptr;
-    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
-    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
-    if ((rc = mcf_snowrun_summary_enable(h, micro_spec, pack_spec))) return rc;
-    if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
-    // (a run for the snowpack's summaries alone ends behind pass 1, unless the caller asks for the arrays)
-    if ((micro_spec || outs->arrays) && (rc = mcf_snowrun_pass2(h, in->micro, in->mat, outs->arrays))) return rc;
-    for (int k = 0; k < MCF_NSTAT; ++k) {
-        for (int v = 0; micro_spec && v < MCF_NOUT; ++v)
-            if (micro_spec->var[v] && micro_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 0, v, k, outs->micro.val[v][k]))) return rc;
-        for (int v = 0; pack_spec && v < 5; ++v)
-            if (pack_spec->series[v] && pack_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 1, v, k, outs->pack.val[v][k]))) return rc;
-    }
-    if (micro_spec && outs->micro.days && (rc = mcf_snowrun_summary_days(h, 0, outs->micro.days))) return rc;
-    if (pack_spec && outs->pack.days && (rc = mcf_snowrun_summary_days(h, 1, outs->pack.days))) return rc;
-    return MCF_OK;
+    return run_with_sink(in, opt, mu, micro_spec != nullptr, outs, [&]() -> int {
+        if (!micro_spec && !pack_spec) return api_fail(MCF_ERR_ARG, "snow-run summaries: null spec (one of the two is needed)");
+        if (opt && opt->reqhgt < 0) return api_fail(MCF_ERR_ARG, kSummaryBelow);
+        int rc = check_create(in, opt, mu, false);
+        if (!rc) rc = check_summary_specs(micro_spec, pack_spec, *opt, in->grid->tsteps, in->snow->chunk_steps);
+        if (!rc && micro_spec) rc = mcf::check_summary_out(micro_spec, &outs->micro);
+        if (!rc && pack_spec) rc = mcf::check_snowpack_summary_out(pack_spec, &outs->pack);
+        return rc;
+    }, [&](mcf_snowrun* h) { return mcf_snowrun_summary_enable(h, micro_spec, pack_spec); }, [&](mcf_snowrun* h) -> int {
+        int rc;
+        for (int k = 0; k < MCF_NSTAT; ++k) {
+            for (int v = 0; micro_spec && v < MCF_NOUT; ++v)
+                if (micro_spec->var[v] && micro_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 0, v, k, outs->micro.val[v][k]))) return rc;
+            for (int v = 0; pack_spec && v < 5; ++v)
+                if (pack_spec->series[v] && pack_spec->stat[k] && (rc = mcf_snowrun_summary_fetch(h, 1, v, k, outs->pack.val[v][k]))) return rc;
+        }
+        if (micro_spec && outs->micro.days && (rc = mcf_snowrun_summary_days(h, 0, outs->micro.days))) return rc;
+        if (pack_spec && outs->pack.days && (rc = mcf_snowrun_summary_days(h, 1, outs->pack.days))) return rc;
+        return MCF_OK;
+    });
 }
 
 // ---- series sink of the run (include/mcf.h "series sink of the snow run and of the snowpack") -------------------
@@ -1035,54 +1055,34 @@ extern "C" int mcf_snowrun_series_fetch_zones(mcf_snowrun* h, int32_t pack, int3
     return blocks_fetch_zones(*h, pack != 0, var, nz, (int64_t)h->ndays * 24, std::max<int64_t>(h->T, 1), zstat, dst);
 }
 
-// null buffers of the selected (series, statistic) pairs of a snowpack spec
-static int check_pack_series_out(const std::string& who, const mcf_snowpack_series_spec* s, const mcf_snowpack_series_out* o) {
-    for (int v = 0; v < 5; ++v) {
-        if (!s->series[v]) continue;
-        if (s->npoints > 0 && !o->points[v]) return api_fail(MCF_ERR_ARG, who + ": a selected series has a null point buffer");
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (s->nzones > 0 && s->zstat[k] && !o->zones[v][k]) return api_fail(MCF_ERR_ARG, who + ": a selected (series, statistic) has a null buffer");
-    }
-    return MCF_OK;
-}
-
 extern "C" int mcf_runmicrosnow_series(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu,
                                        const mcf_series_spec* micro_spec, const mcf_snowpack_series_spec* pack_spec,
                                        mcf_snowrun_series_out* outs) {
     const std::string who = "mcf_runmicrosnow_series";
     if (!micro_spec && !pack_spec) return api_fail(MCF_ERR_ARG, who + ": null spec (one of the two is needed)");
     if (!outs || !in || !in->grid || !in->snow || !opt) return api_fail(MCF_ERR_ARG, who + ": null argument");
-    int rc = check_series_specs(who, micro_spec, pack_spec, opt->out, opt->reqhgt, in->grid->rows, in->grid->cols, in->snow->chunk_steps);
-    if (rc) return rc;                                           // (nothing above needs a device or reads an input array)
-    if ((rc = check_create(in, opt, mu, false))) return rc;
-    for (int v = 0; micro_spec && v < MCF_NOUT; ++v) {
-        if (!micro_spec->var[v]) continue;
-        if (micro_spec->npoints > 0 && !outs->micro.points[v]) return api_fail(MCF_ERR_ARG, who + ": a selected variable has a null point buffer");
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (micro_spec->nzones > 0 && micro_spec->zstat[k] && !outs->micro.zones[v][k])
-                return api_fail(MCF_ERR_ARG, who + ": a selected (variable, statistic) has a null buffer");
-    }
-    if (pack_spec && (rc = check_pack_series_out(who, pack_spec, &outs->pack))) return rc;
-    mcf_snowrun* h = nullptr;
-    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
-    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
-    if ((rc = mcf_snowrun_series_enable(h, micro_spec, pack_spec))) return rc;
-    if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
-    // (a run for the snowpack's series alone ends behind pass 1, unless the caller asks for the arrays)
-    if ((micro_spec || outs->arrays) && (rc = mcf_snowrun_pass2(h, in->micro, in->mat, outs->arrays))) return rc;
-    for (int v = 0; micro_spec && v < MCF_NOUT; ++v) {
-        if (!micro_spec->var[v]) continue;
-        if (micro_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 0, v, outs->micro.points[v]))) return rc;
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (micro_spec->nzones > 0 && micro_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 0, v, k, outs->micro.zones[v][k]))) return rc;
-    }
-    for (int v = 0; pack_spec && v < 5; ++v) {
-        if (!pack_spec->series[v]) continue;
-        if (pack_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 1, v, outs->pack.points[v]))) return rc;
-        for (int k = 0; k < MCF_NZSTAT; ++k)
-            if (pack_spec->nzones > 0 && pack_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 1, v, k, outs->pack.zones[v][k]))) return rc;
-    }
-    return MCF_OK;
+    return run_with_sink(in, opt, mu, micro_spec != nullptr, outs, [&]() -> int {
+        int rc = check_series_specs(who, micro_spec, pack_spec, opt->out, opt->reqhgt, in->grid->rows, in->grid->cols, in->snow->chunk_steps);
+        if (!rc) rc = check_create(in, opt, mu, false);             // (nothing above needs a device or reads an input array)
+        if (!rc && micro_spec) rc = mcf::check_series_out(who, micro_spec, &outs->micro);
+        if (!rc && pack_spec) rc = mcf::check_snowpack_series_out(who, pack_spec, &outs->pack);
+        return rc;
+    }, [&](mcf_snowrun* h) { return mcf_snowrun_series_enable(h, micro_spec, pack_spec); }, [&](mcf_snowrun* h) -> int {
+        int rc;
+        for (int v = 0; micro_spec && v < MCF_NOUT; ++v) {
+            if (!micro_spec->var[v]) continue;
+            if (micro_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 0, v, outs->micro.points[v]))) return rc;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (micro_spec->nzones > 0 && micro_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 0, v, k, outs->micro.zones[v][k]))) return rc;
+        }
+        for (int v = 0; pack_spec && v < 5; ++v) {
+            if (!pack_spec->series[v]) continue;
+            if (pack_spec->npoints > 0 && (rc = mcf_snowrun_series_fetch_points(h, 1, v, outs->pack.points[v]))) return rc;
+            for (int k = 0; k < MCF_NZSTAT; ++k)
+                if (pack_spec->nzones > 0 && pack_spec->zstat[k] && (rc = mcf_snowrun_series_fetch_zones(h, 1, v, k, outs->pack.zones[v][k]))) return rc;
+        }
+        return MCF_OK;
+    });
 }
 
 static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out,
@@ -1090,7 +1090,7 @@ static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt
     mcf_snowrun* h = nullptr;
     int rc = snowrun_create(in, opt, mu, below, &h);
     if (rc) return rc;
-    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
+    SnowRunHolder holder(h);
     if ((rc = mcf_snowrun_pass1(h, smod, nullptr, nullptr))) return rc;
     return mcf_snowrun_pass2(h, in->micro, in->mat, out);
 }
@@ -1128,7 +1128,7 @@ extern "C" int mcf_runmicrosnow2_coarse(const mcf_microsnow_coarse_in* in, const
     mcf_snowrun* h = nullptr;
     int rc = snowrun_create(nullptr, opt, nullptr, false, &h, in, smod ? smod->umu : nullptr);
     if (rc) return rc;
-    struct Guard { mcf_snowrun* p; ~Guard() { mcf_snowrun_destroy(p); } } guard{h};
+    SnowRunHolder holder(h);
     if ((rc = mcf_snowrun_pass1(h, smod ? &smod->smod : nullptr, nullptr, nullptr))) return rc;
     rc = mcf_snowrun_pass2(h, in->micro_static, in->mat, out);
     if (!rc && getenv("MCF_TIMING")) mcf::snowplan_print_timing(h->blocks[0].sp);
@@ -1148,13 +1148,17 @@ extern "C" int mcf_runmicrosnow1_below_multi(const mcf_microsnow_in* in, const m
 // ---- the snow model alone: `.snowmodel1` / `.snowmodel2`'s chunk loop (mcf_snowmodel1 / 2: one plan on `device`, mu = NULL)
 // or over row blocks of ONE raster held by this process (include/mcf.h mcf_snowmodel1_multi: block b on devices[b % n_devices];
 // EVERY block's plan stays resident, the chunk loop couples the blocks at every chunk)
-// spec / sout: the snowpack's period summaries (mcf_snowmodel1_summary, which has checked them), folded behind every chunk
-// co / umu_out: coarse array weather (mcf_snowmodel2_coarse, which has checked it; `in` is &co->drv) and where pointm$umu goes
-// zspec / zout: the snowpack's series sink (mcf_snowmodel1_series, which has checked them), folded behind every chunk too
-static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device,
-                     const mcf_snowpack_summary_spec* spec = nullptr, mcf_snowpack_summary_out* sout = nullptr,
-                     const mcf_snowcoarse_in* co = nullptr, double* umu_out = nullptr,
-                     const mcf_snowpack_series_spec* zspec = nullptr, mcf_snowpack_series_out* zout = nullptr) {
+// The snowpack's sinks, each folded behind every chunk: spec / sout, the period summaries (mcf_snowmodel1_summary, which has
+// checked them); zspec / zout, the series sink (mcf_snowmodel1_series, which has checked them)
+struct PackSinks {
+    const mcf_snowpack_summary_spec* spec;
+    mcf_snowpack_summary_out* sout;
+    const mcf_snowpack_series_spec* zspec;
+    mcf_snowpack_series_out* zout;
+};
+// coarse: mcf_snowmodel2_coarse, which has checked it (`in` is &coarse.co->drv)
+static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device, const PackSinks& sinks = {},
+                     const CoarseSource& coarse = {}) {
     if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     try {
         SnowBlocks sb;
@@ -1164,42 +1168,42 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
         else if ((rc = mcf::device_list(mu, 0, &sb.devs))) return rc;
         sb.cut(mu ? mu->n_blocks : 1);
         rc = mcf::run_workers(sb.nt, [&](Worker& w) {
-            mcf::for_blocks(w, sb.nb, sb.nt, [&](int b) { return block_snowplan(sb, b, sb.devs[(size_t)w.t], *in, co, umu_out); });
+            mcf::for_blocks(w, sb.nb, sb.nt, [&](int b) { return block_snowplan(sb, b, sb.devs[(size_t)w.t], *in, coarse); });
         });
         if (rc) return rc;
         const int nchunks = mcf_snowplan_chunks(sb.blocks[0].sp);
         rc = mcf::run_workers(sb.nt, [&](Worker& w) {
-            if (spec) {
-                sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_enable(k.sp, spec); });
+            if (sinks.spec) {
+                sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_enable(k.sp, sinks.spec); });
                 w.wait();
             }
-            if (zspec) {
-                sb.each_block(w, [&](Block& k) { return block_pack_series(sb, k, zspec); });
+            if (sinks.zspec) {
+                sb.each_block(w, [&](Block& k) { return block_pack_series(sb, k, sinks.zspec); });
                 w.wait();
             }
             for (int ch = 0; ch < nchunks; ++ch) {
                 snow_chunk(sb, w, ch, out);
-                if (spec) sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_accumulate(k.sp, ch); });
-                if (zspec) sb.each_block(w, [&](Block& k) { return k.ser_pack ? mcf_snowplan_series_accumulate(k.sp, ch) : (int)MCF_OK; });
+                if (sinks.spec) sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_accumulate(k.sp, ch); });
+                if (sinks.zspec) sb.each_block(w, [&](Block& k) { return k.ser_pack ? mcf_snowplan_series_accumulate(k.sp, ch) : (int)MCF_OK; });
             }
-            if (spec)      // every block's rows of the planes in place, through the row pitch
+            if (sinks.spec)      // every block's rows of the planes in place, through the row pitch
                 sb.each_block(w, [&](Block& k) -> int {
                     for (int v = 0; v < 5; ++v)
                         for (int q = 0; q < MCF_NSTAT; ++q)
-                            if (spec->series[v] && spec->stat[q])
-                                if (const int rc2 = mcf_snowplan_summary_fetch(k.sp, v, q, sout->val[v][q] + k.r0, sb.R)) return rc2;
+                            if (sinks.spec->series[v] && sinks.spec->stat[q])
+                                if (const int rc2 = mcf_snowplan_summary_fetch(k.sp, v, q, sinks.sout->val[v][q] + k.r0, sb.R)) return rc2;
                     return MCF_OK;
                 });
         });
-        if (!rc && spec && sout->days) rc = mcf_snowplan_summary_days(sb.blocks[0].sp, sout->days);
+        if (!rc && sinks.spec && sinks.sout->days) rc = mcf_snowplan_summary_days(sb.blocks[0].sp, sinks.sout->days);
         // the series: the blocks' points to their places, their zone states combined and finished once
         const int64_t T = std::max<int64_t>(in->base.tsteps, 1);
-        for (int v = 0; !rc && zspec && v < 5; ++v) {
-            if (!zspec->series[v]) continue;
-            if (zspec->npoints > 0) rc = blocks_fetch_points(sb, true, v, T, zout->points[v]);
+        for (int v = 0; !rc && sinks.zspec && v < 5; ++v) {
+            if (!sinks.zspec->series[v]) continue;
+            if (sinks.zspec->npoints > 0) rc = blocks_fetch_points(sb, true, v, T, sinks.zout->points[v]);
             for (int q = 0; !rc && q < MCF_NZSTAT; ++q)
-                if (zspec->nzones > 0 && zspec->zstat[q])
-                    rc = blocks_fetch_zones(sb, true, v, zspec->nzones, in->base.tsteps / 24 * 24, T, q, zout->zones[v][q]);
+                if (sinks.zspec->nzones > 0 && sinks.zspec->zstat[q])
+                    rc = blocks_fetch_zones(sb, true, v, sinks.zspec->nzones, in->base.tsteps / 24 * 24, T, q, sinks.zout->zones[v][q]);
         }
         if (!rc && !mu && getenv("MCF_TIMING")) mcf::snowplan_print_timing(sb.blocks[0].sp);
         return rc;
@@ -1221,14 +1225,11 @@ extern "C" int mcf_snowmodel1_summary(const mcf_snowdriver_in* in, const mcf_sno
     if (!in || !out) return api_fail(MCF_ERR_ARG, "null snow driver argument");
     if (in->base.array_forcing) return api_fail(MCF_ERR_ARG, "mcf_snowmodel1_summary takes data.frame (vector) climate");
     if (const int rc = mcf::snowpack_spec_check(spec, in->base.tsteps, in->chunk_steps)) return rc;
-    for (int v = 0; v < 5; ++v)
-        for (int q = 0; q < MCF_NSTAT; ++q)
-            if (spec->series[v] && spec->stat[q] && !out->val[v][q])
-                return api_fail(MCF_ERR_ARG, "snowpack summary: a selected (series, statistic) has a null buffer");
+    if (const int rc = mcf::check_snowpack_summary_out(spec, out)) return rc;
     if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, "snow driver needs the raster and its dtm");
     if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
     mcf_snowdriver_out none{};
-    return snowmodel(in, &none, mu, 0, spec, out);
+    return snowmodel(in, &none, mu, 0, {spec, out, nullptr, nullptr});
 }
 // mcf_snowmodel1 / _multi with the snowpack's series sink as the only sink
 extern "C" int mcf_snowmodel1_series(const mcf_snowdriver_in* in, const mcf_snowpack_series_spec* spec, const mcf_multi* mu,
@@ -1238,17 +1239,17 @@ extern "C" int mcf_snowmodel1_series(const mcf_snowdriver_in* in, const mcf_snow
     if (!in || !out) return api_fail(MCF_ERR_ARG, who + ": null snow driver argument");
     if (const int rc = mcf::snowpack_series_check(who, spec, in->base.rows, in->base.cols, in->chunk_steps)) return rc;      // no device yet
     if (in->base.array_forcing) return api_fail(MCF_ERR_ARG, who + " takes data.frame (vector) climate");
-    if (const int rc = check_pack_series_out(who, spec, out)) return rc;
+    if (const int rc = mcf::check_snowpack_series_out(who, spec, out)) return rc;
     if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, who + ": snow driver needs the raster and its dtm");
     if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, who + ": null input: a vegetation or initial-snow raster");
     mcf_snowdriver_out none{};
-    return snowmodel(in, &none, mu, 0, nullptr, nullptr, nullptr, nullptr, spec, out);
+    return snowmodel(in, &none, mu, 0, {nullptr, nullptr, spec, out});
 }
 // `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
 // (mcf_snow.hip, k_coarse_hours) and hands pointm$umu out of the chunk's slab
 extern "C" int mcf_snowmodel2_coarse(const mcf_snowcoarse_in* in, mcf_snowfast2_out* out, int32_t device) {
     if (const int rc = mcf::snowcoarse_checks(in, true, "mcf_snowmodel2_coarse", out ? nullptr : "out")) return rc;      // no device yet
-    return snowmodel(&in->drv, &out->smod, nullptr, device, nullptr, nullptr, in, out->umu);
+    return snowmodel(&in->drv, &out->smod, nullptr, device, {}, {in, out->umu});
 }
 extern "C" int mcf_snowmodel1_multi(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu) {
     if (!in || !out || !mu) return api_fail(MCF_ERR_ARG, "null snow driver argument");

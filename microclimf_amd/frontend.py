@@ -23,6 +23,7 @@ SpatRaster carries besides values is passed as `dtm = {"z": array, "res": xres |
 from __future__ import annotations
 
 import warnings
+from types import SimpleNamespace
 from typing import Mapping, Sequence
 
 import numpy as np
@@ -1519,22 +1520,12 @@ def _pack_table(tab, tsteps: int, chunk_steps: int):
     return tab
 
 
-def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, snow_inputs: Mapping, *,
-                          periods="month", vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None,
-                          snow_vars: Sequence = (), snow_stats: Sequence = ("mean", "max", "hours_above"), snow_thresholds=None,
-                          pai_a=None, tfact: float = 1.5, device: int = 0, devices=None, n_blocks: int = 0, _terrain=None) -> dict:
-    """`runmicro(..., snow = TRUE)` reduced over time on the device: runmicro_snow(..., one_call=True) with the period summaries
-    of include/mcf.h as its only sink — per-cell statistics `stats` of the merged outputs `vars` and, with `snow_vars` (names
-    of Tc, Tg, groundsnowdepth, totalSWE, snowden), `snow_stats` of the snow model's series, over `periods` (summary_periods).
-    No [rows, cols, steps] array is made on either side.  Days that are neither snow nor no-snow days are never counted (they
-    are NA in runmicro_snow's arrays); the snow series' days past the last whole 5-day chunk neither.  `snow_thresholds`
-    defaults to 0 (hours_above of totalSWE: the snow-cover duration).  reqhgt == 0 masks the variables as runmicro does;
-    reqhgt < 0 is not available.  `devices` / `n_blocks`: row blocks over several devices.
-    -> {variable: {statistic: [rows, cols, nperiods]}, "snow": {series: {statistic: ...}, "days"}, "periods": labels, "days":
-    counted days per period, "snowdays", "nosnowdays": one flag per day}"""
-    from . import snow as S
+def _snow_sink_inputs(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, vars, snow_vars, pai_a, tfact, device, what):
+    """What the snow run's sink-only calls share ahead of the run; `what`: the refusal of reqhgt < 0.  -> a namespace with `a`
+    (the solver's inputs), `kept` (the selected outputs that exist at this reqhgt), `snames` (the selected snow series), `snow`
+    (the snow model's inputs) and what pass 2's microclimate is made from"""
     if reqhgt < 0:
-        raise ValueError("period summaries of the snow run need reqhgt >= 0")
+        raise ValueError(what)
     names = _names(vars, api._abi.OUT_NAMES, "vars")
     snames = _names(snow_vars, api._abi.SNOWDRIVER_OUT, "snow_vars")
     if not names and not snames:
@@ -1549,25 +1540,50 @@ def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soi
     kept = [n for n, o in zip(api._abi.OUT_NAMES, a["out"]) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
     if names and not kept:
         raise ValueError("none of the selected variables exists at this reqhgt")
-    if not kept:                                                       # (the snowpack's summaries alone: the run still needs an output)
+    if not kept:                                                       # (the snowpack's sink alone: the run still needs an output)
         a["out"] = [1] + [0] * 9
-    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
-    snow = {k: v for k, v in snow_inputs.items() if k != "umu"}
-    tab, labels = summary_periods(a["obstime"], periods)
-    summary = dict(periods=tab, nperiods=len(labels), vars=kept, stats=stats, thresholds=thresholds) if kept else None
-    pack = None
-    if snames:
-        pack = dict(periods=_pack_table(tab, len(a["obstime"]["year"]), int(snow.get("chunk_steps", 120))), nperiods=len(labels),
-                    vars=snames, stats=snow_stats, thresholds=0.0 if snow_thresholds is None else snow_thresholds)
-    with S.SnowRun(a, snow, device=device, devices=devices, n_blocks=n_blocks) as run:
-        run.summary_enable(summary, pack)
+    return SimpleNamespace(a=a, kept=kept, snames=snames, snow={k: v for k, v in snow_inputs.items() if k != "umu"},
+                           micro=(micropoint, reqhgt, *cleanvars(vegp, soilc, dtm["z"]), dtm, snow_inputs), pai_a=pai_a, device=device)
+
+
+def _snow_sink_run(i, devices, n_blocks, _terrain, enable, fetch) -> dict:
+    """The run of _snow_sink_inputs' `i` with a sink as its only output: enable(run), pass 1, pass 2 when an output of the solver
+    is selected, fetch(run) -> its result with the day classes"""
+    from . import snow as S
+    with S.SnowRun(i.a, i.snow, device=i.device, devices=devices, n_blocks=n_blocks) as run:
+        enable(run)
         sd, nd = run.pass1()
-        if summary is not None:
-            run.pass2(_one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain),
-                      float(micropoint["matemp"]), want_arrays=False)
-        res = run.fetch_summary()
+        if i.kept:
+            run.pass2(_one_call_micro(*i.micro, sd, i.pai_a, i.device, _terrain), float(i.micro[0]["matemp"]), want_arrays=False)
+        res = fetch(run)
+    res.update(snowdays=sd, nosnowdays=nd)
+    return res
+
+
+def runmicro_snow_summary(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, snow_inputs: Mapping, *,
+                          periods="month", vars: Sequence = ("Tz",), stats: Sequence = ("mean", "min", "max"), thresholds=None,
+                          snow_vars: Sequence = (), snow_stats: Sequence = ("mean", "max", "hours_above"), snow_thresholds=None,
+                          pai_a=None, tfact: float = 1.5, device: int = 0, devices=None, n_blocks: int = 0, _terrain=None) -> dict:
+    """`runmicro(..., snow = TRUE)` reduced over time on the device: runmicro_snow(..., one_call=True) with the period summaries
+    of include/mcf.h as its only sink — per-cell statistics `stats` of the merged outputs `vars` and, with `snow_vars` (names
+    of Tc, Tg, groundsnowdepth, totalSWE, snowden), `snow_stats` of the snow model's series, over `periods` (summary_periods).
+    No [rows, cols, steps] array is made on either side.  Days that are neither snow nor no-snow days are never counted (they
+    are NA in runmicro_snow's arrays); the snow series' days past the last whole 5-day chunk neither.  `snow_thresholds`
+    defaults to 0 (hours_above of totalSWE: the snow-cover duration).  reqhgt == 0 masks the variables as runmicro does;
+    reqhgt < 0 is not available.  `devices` / `n_blocks`: row blocks over several devices.
+    -> {variable: {statistic: [rows, cols, nperiods]}, "snow": {series: {statistic: ...}, "days"}, "periods": labels, "days":
+    counted days per period, "snowdays", "nosnowdays": one flag per day}"""
+    i = _snow_sink_inputs(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, vars, snow_vars, pai_a, tfact, device,
+                          "period summaries of the snow run need reqhgt >= 0")
+    tab, labels = summary_periods(i.a["obstime"], periods)
+    summary = dict(periods=tab, nperiods=len(labels), vars=i.kept, stats=stats, thresholds=thresholds) if i.kept else None
+    pack = None
+    if i.snames:
+        pack = dict(periods=_pack_table(tab, len(i.a["obstime"]["year"]), int(i.snow.get("chunk_steps", 120))), nperiods=len(labels),
+                    vars=i.snames, stats=snow_stats, thresholds=0.0 if snow_thresholds is None else snow_thresholds)
+    res = _snow_sink_run(i, devices, n_blocks, _terrain, lambda run: run.summary_enable(summary, pack), lambda run: run.fetch_summary())
     res.setdefault("days", None)
-    res.update(periods=labels, snowdays=sd, nosnowdays=nd)
+    res["periods"] = labels
     return res
 
 
@@ -1582,38 +1598,15 @@ def runmicro_snow_series(micropoint: Mapping, reqhgt: float, vegp: Mapping, soil
     no-snow days, and the snow series' days past the last whole 5-day chunk, are NA.  reqhgt < 0 is not available.
     -> {variable: {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}, "snow": {series: {...}}, "cells",
     "snowdays", "nosnowdays"}"""
-    from . import snow as S
-    if reqhgt < 0:
-        raise ValueError("the series sink of the snow run needs reqhgt >= 0")
-    names = _names(vars, api._abi.OUT_NAMES, "vars")
-    snames = _names(snow_vars, api._abi.SNOWDRIVER_OUT, "snow_vars")
-    if not names and not snames:
-        raise ValueError("nothing selected: vars and snow_vars are both empty")
-    if snow_inputs is None:
-        raise ValueError("snow_inputs = runsnowmodel(weather, micropoint, vegp, soilc, dtm, inputs_only=True) is needed")
-    if len(micropoint["subs"]) != micropoint["ntme"]:
-        raise ValueError("the one-call snow run takes a complete micropoint")
-    out = _out_mask(names)[1]
-    a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, device=device)
-    a["tfact"] = float(tfact)
-    kept = [n for n, o in zip(api._abi.OUT_NAMES, a["out"]) if o]      # (reqhgt == 0: tleaf, relhum and windspeed are masked)
-    if names and not kept:
-        raise ValueError("none of the selected variables exists at this reqhgt")
-    if not kept:                                                       # (the snowpack's series alone: the run still needs an output)
-        a["out"] = [1] + [0] * 9
-    veg, soil, z = cleanvars(vegp, soilc, dtm["z"])
+    i = _snow_sink_inputs(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, vars, snow_vars, pai_a, tfact, device,
+                          "the series sink of the snow run needs reqhgt >= 0")
     rows, cols = np.asarray(dtm["z"]).shape[:2]
     cells = series_cells(dtm, rows, cols, points, xy)
     sel = dict(points=cells if cells.size else None, zones=zones, stats=stats)
-    snow = {k: v for k, v in snow_inputs.items() if k != "umu"}
-    with S.SnowRun(a, snow, device=device, devices=devices, n_blocks=n_blocks) as run:
-        run.series_enable(dict(sel, vars=kept) if kept else None, dict(sel, vars=snames) if snames else None)
-        sd, nd = run.pass1()
-        if kept:
-            run.pass2(_one_call_micro(micropoint, reqhgt, veg, soil, z, dtm, snow_inputs, sd, pai_a, device, _terrain),
-                      float(micropoint["matemp"]), want_arrays=False)
-        res = run.fetch_series()
-    res.update(cells=cells, snowdays=sd, nosnowdays=nd)
+    res = _snow_sink_run(i, devices, n_blocks, _terrain, lambda run: run.series_enable(dict(sel, vars=i.kept) if i.kept else None,
+                                                                                     dict(sel, vars=i.snames) if i.snames else None),
+                         lambda run: run.fetch_series())
+    res["cells"] = cells
     return res
 
 

@@ -1343,6 +1343,7 @@ class SnowRun:
     def __init__(self, grid: Mapping, snow: Mapping, *, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0,
                  below: bool = False, handle: bool = True, micro_coarse: Mapping | None = None, want_umu: bool = False):
         self._p = None
+        self._msum = self._psum = self._mser = self._pser = None      # the specs of the enabled summaries and series
         self.coarse = micro_coarse is not None
         if self.coarse:
             self._marshal_coarse(grid, snow, micro_coarse, device)
@@ -1387,7 +1388,6 @@ class SnowRun:
         self._in.mat = 0.0
         self.rows, self.cols, self.tsteps = R, Cc, self._sm.tsteps
         self._mm = None
-        self._msum = self._psum = None      # (spec, variables, statistics, table) of the enabled summaries
 
     def _marshal_coarse(self, grid: Mapping, snow: Mapping, micro_coarse: Mapping, device: int):
         self._lib = _abi.load()
@@ -1412,7 +1412,6 @@ class SnowRun:
         self._cin_all.mat = 0.0
         self.rows, self.cols, self.tsteps = self._sm.rows, self._sm.cols, self._sm.tsteps
         self._mm = None
-        self._msum = self._psum = None
 
     def _marshal_micro(self, micro: Mapping):
         """gridmicrosnow's inputs for the whole series (the coarse run: no weather arrays, the direction per step its own)"""
@@ -1468,18 +1467,10 @@ class SnowRun:
     def fetch_summary(self) -> dict:
         """-> {variable: {statistic: [rows, cols, nperiods]}, "days": ...} of the outputs' summaries (after pass2) and, under
         "snow", {series: {statistic: plane}, "days": ...} of the snowpack's (after pass1)"""
-        res = {}
-        for pack, spec, names in ((0, self._msum, _abi.OUT_NAMES), (1, self._psum, _abi.SNOWDRIVER_OUT)):
-            if spec is None:
-                continue
-            d = summary_sink(Buffers(), self.rows, self.cols, spec, names,
-                             plane=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_summary_fetch(self._p, pack, v, k, ptr)),
-                             days=lambda ptr: _abi.check(self._lib.mcf_snowrun_summary_days(self._p, pack, ptr)))
-            if pack:
-                res["snow"] = d
-            else:
-                res.update(d)
-        return res
+        return _merge_micro_and_pack(self._msum, self._psum, lambda pack, spec, names: summary_sink(
+            Buffers(), self.rows, self.cols, spec, names,
+            plane=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_summary_fetch(self._p, pack, v, k, ptr)),
+            days=lambda ptr: _abi.check(self._lib.mcf_snowrun_summary_days(self._p, pack, ptr))))
 
     def series_enable(self, series: Mapping | None = None, pack_series: Mapping | None = None):
         """The series sink (include/mcf.h mcf_snowrun_series_enable), before pass1.  Each a mapping with "points" and / or "zones"
@@ -1494,20 +1485,10 @@ class SnowRun:
     def fetch_series(self) -> dict:
         """-> {variable: {"points": [tsteps, npoints], "zones": {statistic: [tsteps, nzones]}}} of the outputs' series (after
         pass2) and, under "snow", the same per series of the snowpack (after pass1)"""
-        from .api import _series_sink
-        res = {}
-        for pack, spec, names in ((0, getattr(self, "_mser", None), _abi.OUT_NAMES), (1, getattr(self, "_pser", None), _abi.SNOWDRIVER_OUT)):
-            if spec is None:
-                continue
-            d = _series_sink(Buffers(), self.tsteps, *spec, names=names,
-                             points=lambda v, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_points(self._p, pack, v, ptr)),
-                             zones=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_zones(self._p, pack, v, k, ptr)))
-            d = _series_by_variable(d)
-            if pack:
-                res["snow"] = d
-            else:
-                res.update(d)
-        return res
+        return _merge_micro_and_pack(self._mser, self._pser, lambda pack, spec, names: _series_sink_by_variable(
+            Buffers(), self.tsteps, spec, names,
+            points=lambda v, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_points(self._p, pack, v, ptr)),
+            zones=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_zones(self._p, pack, v, k, ptr))))
 
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
@@ -1532,8 +1513,24 @@ class SnowRun:
         return arrays
 
 
-def _series_by_variable(d: dict) -> dict:
-    """_series_sink's {"points": {v: a}, "zones": {v: {stat: a}}} -> {v: {"points": a or None, "zones": {stat: a}}}"""
+def _merge_micro_and_pack(micro_spec, pack_spec, sink) -> dict:
+    """sink(pack, spec, names) -> dict for each of the two specs that is there: the outputs' at the top, the snowpack's under the key "snow" """
+    res = {}
+    for pack, spec, names in ((0, micro_spec, _abi.OUT_NAMES), (1, pack_spec, _abi.SNOWDRIVER_OUT)):
+        if spec is None:
+            continue
+        d = sink(pack, spec, names)
+        if pack:
+            res["snow"] = d
+        else:
+            res.update(d)
+    return res
+
+
+def _series_sink_by_variable(b, tsteps, spec, names, **to) -> dict:
+    """api._series_sink's {"points": {v: a}, "zones": {v: {stat: a}}} -> {v: {"points": a or None, "zones": {stat: a}}}"""
+    from .api import _series_sink
+    d = _series_sink(b, tsteps, *spec, names=names, **to)
     return {v: {"points": d["points"].get(v), "zones": d["zones"].get(v, {})} for v in list(d["points"]) + [k for k in d["zones"] if k not in d["points"]]}
 
 
@@ -1554,11 +1551,11 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
         if series is not None or pack_series is not None:
             if summary is not None or pack_summary is not None:
                 raise ValueError("one call takes the summaries or the series sink: both on one run through SnowRun")
-            return _runmicrosnow_series(run, series, pack_series, want_arrays, want_smod, devices, n_blocks)
+            return _runmicrosnow_sink(run, "series", series, pack_series, want_arrays, want_smod, devices, n_blocks)
         if summary is not None or pack_summary is not None:
             if below:
                 raise ValueError("period summaries of the snow run need reqhgt >= 0")
-            return _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, devices, n_blocks)
+            return _runmicrosnow_sink(run, "summary", summary, pack_summary, want_arrays, want_smod, devices, n_blocks)
         outs, arrays = alloc_outputs(run._gm)
         so, smod = _driver_out(run.rows, run.cols, run.tsteps) if want_smod else (None, None)
         sop = C.byref(so) if so is not None else None
@@ -1573,20 +1570,23 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
     return (arrays, smod) if want_smod else arrays
 
 
-def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, devices, n_blocks) -> dict:
-    lib = _abi.load()
-    ms = _micro_summary_spec(summary) if summary is not None else None
-    ps = _pack_summary_spec(pack_summary) if pack_summary is not None else None
-    so = _abi.SnowrunSummaryOut()
-    res = {"out": None, "summary": {}}
-    for spec, names, dst, key in ((ms, _abi.OUT_NAMES, so.micro, None), (ps, _abi.SNOWDRIVER_OUT, so.pack, "snow")):
-        if spec is None:
-            continue
-        d = summary_sink(run._gm, run.rows, run.cols, spec, names, dst)
-        if key:
-            res["summary"][key] = d
-        else:
-            res["summary"].update(d)
+# kind -> the two spec builders, the out struct, the sink filler (run, spec, names, destination struct) and the library entry
+_SINK_KINDS = {
+    "summary": (lambda run, m: _micro_summary_spec(m), lambda run, m: _pack_summary_spec(m), _abi.SnowrunSummaryOut,
+                lambda run, spec, names, dst: summary_sink(run._gm, run.rows, run.cols, spec, names, dst), "mcf_runmicrosnow_summary"),
+    "series": (lambda run, m: _micro_series_spec(run.rows, run.cols, m), lambda run, m: _pack_series_spec(run.rows, run.cols, m),
+               _abi.SnowrunSeriesOut, lambda run, spec, names, dst: _series_sink_by_variable(run._gm, run.tsteps, spec, names, so=dst),
+               "mcf_runmicrosnow_series"),
+}
+
+
+def _runmicrosnow_sink(run, kind, micro, pack, want_arrays, want_smod, devices, n_blocks) -> dict:
+    """-> {"out": the merged outputs or None, kind: as SnowRun.fetch_summary / fetch_series, "snowdays", "nosnowdays"[, "smod"]}"""
+    micro_spec, pack_spec, out_struct, fill, entry = _SINK_KINDS[kind]
+    ms = micro_spec(run, micro) if micro is not None else None
+    ps = pack_spec(run, pack) if pack is not None else None
+    so = out_struct()
+    res = {"out": None, kind: _merge_micro_and_pack(ms, ps, lambda p, spec, names: fill(run, spec, names, so.pack if p else so.micro))}
     if want_arrays:
         outs, res["out"] = alloc_outputs(run._gm)
         so.arrays = C.pointer(outs)
@@ -1597,39 +1597,8 @@ def _runmicrosnow_summary(run, summary, pack_summary, want_arrays, want_smod, de
     res["snowdays"], so.snowday = run._gm.out(nd, np.int32, zero=True)
     res["nosnowdays"], so.nosnowday = run._gm.out(nd, np.int32, zero=True)
     mu = _abi.multi(devices, n_blocks)
-    _abi.check(lib.mcf_runmicrosnow_summary(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
-                                            C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
-    return res
-
-
-def _runmicrosnow_series(run, series, pack_series, want_arrays, want_smod, devices, n_blocks) -> dict:
-    """-> {"out": the merged outputs or None, "series": as SnowRun.fetch_series, "snowdays", "nosnowdays"[, "smod"]}"""
-    from .api import _series_sink
-    lib = _abi.load()
-    ms = _micro_series_spec(run.rows, run.cols, series) if series is not None else None
-    ps = _pack_series_spec(run.rows, run.cols, pack_series) if pack_series is not None else None
-    so = _abi.SnowrunSeriesOut()
-    res = {"out": None, "series": {}}
-    for spec, names, dst, key in ((ms, _abi.OUT_NAMES, so.micro, None), (ps, _abi.SNOWDRIVER_OUT, so.pack, "snow")):
-        if spec is None:
-            continue
-        d = _series_by_variable(_series_sink(run._gm, run.tsteps, *spec, so=dst, names=names))
-        if key:
-            res["series"][key] = d
-        else:
-            res["series"].update(d)
-    if want_arrays:
-        outs, res["out"] = alloc_outputs(run._gm)
-        so.arrays = C.pointer(outs)
-    if want_smod:
-        sm, res["smod"] = _driver_out(run.rows, run.cols, run.tsteps)
-        so.smod = C.pointer(sm)
-    nd = run.tsteps // 24
-    res["snowdays"], so.snowday = run._gm.out(nd, np.int32, zero=True)
-    res["nosnowdays"], so.nosnowday = run._gm.out(nd, np.int32, zero=True)
-    mu = _abi.multi(devices, n_blocks)
-    _abi.check(lib.mcf_runmicrosnow_series(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
-                                           C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
+    _abi.check(getattr(_abi.load(), entry)(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
+                                          C.byref(ms[0]) if ms else None, C.byref(ps[0]) if ps else None, C.byref(so)))
     return res
 
 
