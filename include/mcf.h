@@ -1365,6 +1365,111 @@ int mcf_runmicrosnow_series(const mcf_microsnow_in *in, const mcf_options *opt, 
 int mcf_snowmodel1_series(const mcf_snowdriver_in *in, const mcf_snowpack_series_spec *spec, const mcf_multi *multi,
                           mcf_snowpack_series_out *out);
 
+/* ---- netCDF sink: further sources --------------------------------------------------------------------------
+ * The `writetonc` file (mcf_nc_create above) behind more than the ring slot of one plan: a row block's plan as a row strip of
+ * the file, a depth slab of a streamed below-ground plan, the snow plan's chunk series; and the one-call entries that end in
+ * a file instead of [rows, cols, tsteps] doubles on the host.  The ABI version stays: entries and structs are added, none
+ * changes.
+ *
+ * Row strips.  The device packs a plan's rows as records of their own, [step][8 B | var][plan rows][cols] (k_pack_nc with the
+ * plan's rows), and the file side writes one run per (step, variable) at
+ *     rec_begin + step * rec_bytes + 8 + var * rows * cols * 4 + row0 * cols * 4
+ * of the classic container, with the step's time word beside it: a record has its time value whichever block wrote it, in
+ * whatever order.  Several host threads (the row-block workers) may write strips of one file at once, as long as their strips
+ * do not overlap.  The netCDF-4 container chunks a step into row strips of the whole raster, which a block cut need not respect:
+ * it takes whole rasters only (MCF_ERR_ARG for a strip, and for a one-call entry with more than one block).
+ *
+ * mcf_nc_write_plan_rows: the plan's rows are rows [row0, row0 + plan rows) of the file, the columns are the file's.  `depth`
+ * selects the Tz slab of a streamed below-ground plan with a depth list (mcf_plan_below_set_depths); 0 otherwise, anything else
+ * is MCF_ERR_ARG.  mcf_nc_write_plan is this call with row0 = 0, depth = 0 and a plan of the file's grid.
+ * mcf_nc_write_missing (host only): missval in every variable of those rows of records [file_step0, file_step0 + nsteps) —
+ * steps past the last whole day, the snow run's days of neither class.
+ * mcf_nc_write_host_rows (host only): mcf_nc_write_host for a row block's arrays, vars[v] = [nrows, cols, nsteps]. */
+int mcf_nc_write_plan_rows(mcf_ncfile *nc, mcf_plan *plan, int32_t slot, int32_t depth, int64_t row0, int64_t slot_step0,
+                           int64_t file_step0, int64_t nsteps, float *kernel_ms);
+int mcf_nc_write_missing(mcf_ncfile *nc, int64_t row0, int64_t nrows, int64_t file_step0, int64_t nsteps);
+int mcf_nc_write_host_rows(mcf_ncfile *nc, int64_t row0, int64_t nrows, int64_t step0, int64_t nsteps,
+                           const double *const vars[MCF_NOUT]);
+/* One call: plan, file, chunk loop and close.  The file holds every step of tsteps; a step past the last whole day holds what
+ * the array entry of the same run returns there — missval above ground; below ground Tz's values (Tbelowgroundv runs over every
+ * step) with soilm missval — so the classic file is, byte for byte, the file mcf_nc_write_host writes from the arrays of
+ * mcf_runmicro1 / 2 of the same run.  reqhgt >= 0: vector, fine-array and coarse-array forcing; reqhgt < 0: the streamed
+ * below-ground plan, complete 0 and 1.  Chunks of opt->days_per_chunk days (0: sized as for the other sinks).  `multi` NULL: one
+ * device (opt->device); set: row blocks as in mcf_runmicro_summary_multi, each block writing its strips (the blocks' values are
+ * bit for bit the single device's, and so is the file).  The spec's rows, cols, nsteps and reqhgt must agree with `in` / `opt`
+ * (MCF_ERR_ARG naming the field); the plan is created with exactly the file's variables.  Every refusal that needs no device —
+ * null arguments, a variable writetonc does not define at that height, netcdf4 with several blocks (`multi` with n_blocks
+ * other than 1) — comes before a device is touched, and its message starts with the entry's name. */
+int mcf_runmicro_nc(const mcf_grid_inputs *in, const mcf_options *opt, const mcf_multi *multi, const char *path,
+                    const mcf_nc_spec *spec);
+/* One streamed solve, one file per depth: file d (paths[d]) holds Tz at depths[d] with that depth's long name ("Soil
+ * temperature at depth h m") and, when selected, soilm — the same plane in every file.  The spec's reqhgt is not read.  The
+ * refusals of mcf_plan_below_set_depths that need no plan come before a device is touched, under this entry's name. */
+int mcf_runmicro_depths_nc(const mcf_grid_inputs *in, const mcf_options *opt, const double *depths, int32_t ndepths,
+                           const double *tbp, const char *const *paths, const mcf_nc_spec *spec);
+/* The snowpack's file.  The reference defines no such file (writetonc knows the solver's outputs only), so the convention is
+ * this project's: variables named as mcf_snowdriver_out's fields, int32, missval -9999, on writetonc's dimensions, with
+ *     series           stored as   units            long_name
+ *     Tc               x 100       "deg C x 100"    "Canopy snow temperature"
+ *     Tg               x 100       "deg C x 100"    "Ground snow temperature"
+ *     groundsnowdepth  x 1000      "mm"             "Ground snow depth"            (the series is in m)
+ *     totalSWE         x 100       "mm x 100"       "Total snow water equivalent"  (the series is in mm, after the redistribution)
+ *     snowden          x 1         "kg / m^3"       "Snow density"
+ * round half to even, NA and values outside int32 -> missval.  series[5] selects, in that order; scale[v] = 0 and a NULL
+ * units[v] / long_name[v] take the table's.  Grid, coordinates, time, crs, format and deflate level as in mcf_nc_spec. */
+typedef struct mcf_ncpack_spec {
+    int32_t rows, cols;
+    int64_t nsteps;
+    const double *east, *north, *time_hours;
+    const char *crs_wkt;
+    int32_t series[5];
+    double scale[5];
+    const char *units[5];
+    const char *long_name[5];
+    int32_t format;
+    int32_t deflate_level;
+} mcf_ncpack_spec;
+int mcf_nc_create_snowpack(const char *path, const mcf_ncpack_spec *spec, mcf_ncfile **nc);
+/* The steps of chunk `chunk`, run last on the plan (mcf_snowplan_run_chunk), as rows [row0, row0 + plan rows) of a snowpack
+ * file's records: packed on the device from the plan's step-major chunk series (k_pack_nc_planes; 4 B per value leave the
+ * device), on the stream the model wrote them on.  Behind the last chunk the steps no chunk covers are written as missval.
+ * MCF_ERR_STATE when a series of the file was switched off for the chunk (mcf_snowplan_set_series); MCF_ERR_ARG for a file that
+ * is not a snowpack file, whose columns or steps are not the plan's, or a strip outside its grid. */
+int mcf_snowplan_nc_write(mcf_snowplan *plan, mcf_ncfile *nc, int32_t chunk, int64_t row0);
+/* The snow model alone (data.frame weather) with the file as its only sink: mcf_snowmodel1's chunk loop on device 0 (`multi`
+ * NULL) or over row blocks, mcf_snowplan_nc_write behind every chunk.  The spec's rows, cols and nsteps must be the inputs'. */
+int mcf_snowmodel1_nc(const mcf_snowdriver_in *in, const mcf_multi *multi, const char *path, const mcf_ncpack_spec *spec);
+/* The snow run's files.  mcf_snowrun_nc_enable comes before mcf_snowrun_pass1, like the run's other two sinks (MCF_ERR_STATE
+ * after it, or when called twice); either file may be NULL, not both; the run does not own them (close them after the passes).
+ * micro_file (mcf_nc_create): pass 2 writes every merged ring chunk — runs of days in a class through mcf_nc_write_plan_rows at the
+ * block's first row, days of neither class through mcf_nc_write_missing — then the days past the last whole chunk the same way and
+ * the steps past the last whole day as missval: what the arrays of mcf_runmicrosnow1 / 2 hold there.  reqhgt >= 0 and the
+ * below-ground run alike (the merged days lie in the slot either way).  Its variables must be among the run's.  pack_file
+ * (mcf_nc_create_snowpack): mcf_snowplan_nc_write behind every chunk of pass 1.  With micro_file enabled mcf_snowrun_pass2 accepts
+ * out == NULL or null arrays.  The grids and steps must be the run's; netcdf4 with more than one block is MCF_ERR_ARG.  Works on a
+ * handle of mcf_snowrun_create_coarse as on any other (enable acts on the handle).
+ * mcf_runmicrosnow_nc: one call — data.frame or array weather (mcf_runmicrosnow1 / 2 geometry), `multi` as there, reqhgt < 0 the
+ * below-ground run; path / spec and pack_path / pack_spec: either pair may be NULL.  The files are created once the run exists
+ * (no file without a device); every refusal that needs no device comes first, under the entry's name.  outs: all optional. */
+typedef struct mcf_snowrun_nc_out {
+    mcf_outputs *arrays;               /* or NULL: no host array */
+    const mcf_snowdriver_out *smod;    /* or NULL */
+    int32_t *snowday, *nosnowday;      /* [days] or NULL */
+} mcf_snowrun_nc_out;
+int mcf_snowrun_nc_enable(mcf_snowrun *run, mcf_ncfile *micro_file, mcf_ncfile *pack_file);
+/* Between mcf_snowrun_pass1 and mcf_snowrun_pass2 (MCF_ERR_STATE otherwise): days with drop[d] != 0 leave the run's classes, so
+ * that pass 2 treats them as days of neither class — not solved, NA in the arrays, missval in the file, never folded by a sink.
+ * Only a day that is a no-snow day and no snow day may be dropped (MCF_ERR_ARG for a snow day: pass 1 has folded it into the
+ * snow model's means).  For a caller that wants days left out of pass 2 (a gap it will not read), and the way the tests reach
+ * the path that a melted pack's rounding residue takes by itself.  ndays: mcf_snowrun_days. */
+int mcf_snowrun_drop_days(mcf_snowrun *run, const int32_t *drop, int32_t ndays);
+int mcf_runmicrosnow_nc(const mcf_microsnow_in *in, const mcf_options *opt, const mcf_multi *multi, const char *path,
+                        const mcf_nc_spec *spec, const char *pack_path, const mcf_ncpack_spec *pack_spec, mcf_snowrun_nc_out *outs);
+/* Packs host planes through the device kernel, for its tests: series[v] = [nsteps][rows * cols] step-major doubles (cell
+ * row + rows * col) or NULL for a series the file does not hold, as rows [row0, row0 + rows) of records [file_step0, ...). */
+int mcf_nc_write_planes(mcf_ncfile *nc, const double *const series[5], int64_t rows, int64_t row0, int64_t file_step0,
+                        int64_t nsteps, int32_t device, float *kernel_ms);
+
 /* applycpp3 (src/microclimfCpp.cpp:5553-5588; `.runmicrosnow1/2` use it on totalSWE, R/internal.R:3592-3593):
  * reduction of a [rows,cols,tsteps] array over space, per time step, skipping NA.  fun: 0 mean, 1 sum,
  * 2 max, 3 min (max / min of an all-NA step: -Inf / +Inf, mean: NaN).  `count` (optional, [tsteps])

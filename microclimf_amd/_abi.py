@@ -238,6 +238,14 @@ class NcSpec(C.Structure):
                 ("deflate_level", C.c_int32)]
 
 
+class NcPackSpec(C.Structure):
+    """include/mcf.h mcf_ncpack_spec"""
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("nsteps", C.c_int64), ("east", c_double_p),
+                ("north", c_double_p), ("time_hours", c_double_p), ("crs_wkt", C.c_char_p), ("series", C.c_int32 * 5),
+                ("scale", C.c_double * 5), ("units", C.c_char_p * 5), ("long_name", C.c_char_p * 5), ("format", C.c_int32),
+                ("deflate_level", C.c_int32)]
+
+
 POINTSNOW_FIELDS = ("Tc", "Tg", "sdepc", "sdepg", "sdenc", "sdeng", "G", "RswabsG", "RlwabsG", "tr", "umu", "sublmelt",
                     "tempmelt", "rainmelt", "sstemp")
 
@@ -342,6 +350,11 @@ class SnowrunSeriesOut(C.Structure):
                 ("snowday", c_int32_p), ("nosnowday", c_int32_p)]
 
 
+class SnowrunNcOut(C.Structure):
+    """include/mcf.h mcf_snowrun_nc_out"""
+    _fields_ = [("arrays", C.POINTER(Outputs)), ("smod", C.POINTER(SnowDriverOut)), ("snowday", c_int32_p), ("nosnowday", c_int32_p)]
+
+
 class DepthSeriesOut(C.Structure):
     """include/mcf.h mcf_depth_series_out"""
     _fields_ = [("tz_points", c_double_p * MAX_DEPTHS), ("tz_zones", (c_double_p * NZSTAT) * MAX_DEPTHS), ("soilm_points", c_double_p),
@@ -419,6 +432,9 @@ EXPORTS = (
     "mcf_snowplan_series_enable", "mcf_snowplan_series_accumulate", "mcf_snowplan_series_fetch_points",
     "mcf_snowplan_series_fetch_zones", "mcf_snowplan_series_reset", "mcf_snowrun_series_enable", "mcf_snowrun_series_fetch_points",
     "mcf_snowrun_series_fetch_zones", "mcf_runmicrosnow_series", "mcf_snowmodel1_series",
+    "mcf_nc_write_plan_rows", "mcf_nc_write_missing", "mcf_nc_write_host_rows", "mcf_runmicro_nc", "mcf_runmicro_depths_nc",
+    "mcf_nc_create_snowpack", "mcf_snowplan_nc_write", "mcf_snowmodel1_nc", "mcf_nc_write_planes",
+    "mcf_snowrun_nc_enable", "mcf_runmicrosnow_nc", "mcf_snowrun_drop_days",
 )
 
 ABI_VERSION = 8     # include/mcf.h MCF_ABI_VERSION this mirror was written against
@@ -911,6 +927,35 @@ def load() -> C.CDLL:
         lib.mcf_runmicrosnow_series.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), RS, ZS, C.POINTER(SnowrunSeriesOut)]
         lib.mcf_snowmodel1_series.restype = C.c_int
         lib.mcf_snowmodel1_series.argtypes = [C.POINTER(SnowDriverIn), ZS, C.POINTER(Multi), ZO]
+    if hasattr(lib, "mcf_nc_write_plan_rows"):     # (absent from an older library named by MCF_LIB for an A/B run)
+        NS = C.POINTER(NcSpec)
+        lib.mcf_nc_write_plan_rows.restype = C.c_int
+        lib.mcf_nc_write_plan_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64,
+                                               C.c_int64, C.POINTER(C.c_float)]
+        lib.mcf_nc_write_missing.restype = C.c_int
+        lib.mcf_nc_write_missing.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64]
+        lib.mcf_nc_write_host_rows.restype = C.c_int
+        lib.mcf_nc_write_host_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(c_double_p * 10)]
+        lib.mcf_runmicro_nc.restype = C.c_int
+        lib.mcf_runmicro_nc.argtypes = [GI, OP, C.POINTER(Multi), C.c_char_p, NS]
+        lib.mcf_runmicro_depths_nc.restype = C.c_int
+        lib.mcf_runmicro_depths_nc.argtypes = [GI, OP, c_double_p, C.c_int32, c_double_p, C.POINTER(C.c_char_p), NS]
+        lib.mcf_nc_create_snowpack.restype = C.c_int
+        lib.mcf_nc_create_snowpack.argtypes = [C.c_char_p, C.POINTER(NcPackSpec), C.POINTER(C.c_void_p)]
+        lib.mcf_snowplan_nc_write.restype = C.c_int
+        lib.mcf_snowplan_nc_write.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64]
+        lib.mcf_snowmodel1_nc.restype = C.c_int
+        lib.mcf_snowmodel1_nc.argtypes = [C.POINTER(SnowDriverIn), C.POINTER(Multi), C.c_char_p, C.POINTER(NcPackSpec)]
+        lib.mcf_snowrun_nc_enable.restype = C.c_int
+        lib.mcf_snowrun_nc_enable.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mcf_snowrun_drop_days.restype = C.c_int
+        lib.mcf_snowrun_drop_days.argtypes = [C.c_void_p, c_int32_p, C.c_int32]
+        lib.mcf_runmicrosnow_nc.restype = C.c_int
+        lib.mcf_runmicrosnow_nc.argtypes = [C.POINTER(MicrosnowIn), OP, C.POINTER(Multi), C.c_char_p, NS, C.c_char_p,
+                                            C.POINTER(NcPackSpec), C.POINTER(SnowrunNcOut)]
+        lib.mcf_nc_write_planes.restype = C.c_int
+        lib.mcf_nc_write_planes.argtypes = [C.c_void_p, C.POINTER(c_double_p * 5), C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_int32, C.POINTER(C.c_float)]
     if hasattr(lib, "mcf_runmicrosnow2_coarse"):     # (absent from an older library named by MCF_LIB for an A/B run)
         MC = C.POINTER(MicrosnowCoarseIn)
         lib.mcf_microsnow_expand_coarse_device.restype = C.c_int

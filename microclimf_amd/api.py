@@ -249,6 +249,58 @@ def runmicro_depths(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: 
     return res
 
 
+def runmicro_nc(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, reqhgt: float, zref: float,
+                lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, fileout: str, grid: Mapping,
+                vars=None, format: str = "classic", deflate_level: int = 0, reference_puts_only: bool = False,
+                array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                days_per_chunk: int = 0, cells_per_block: int = 0, devices=None, n_blocks: int = 0) -> tuple:
+    """The solver's outputs straight into a `writetonc` file (include/mcf.h mcf_runmicro_nc): the argument lists of runmicro1Cpp ..
+    4Cpp without `out` — the file's variables `vars` (ncsink.default_vars(reqhgt) by default) are what the solver computes —
+    every chunk packed on the device and written while the next is solved; no [rows, cols, tsteps] array on the host.  reqhgt < 0
+    runs the streamed below-ground plan.  `grid`: the mapping ncsink.writetonc takes as `dtm` (extent, res, crs).  `devices` /
+    `n_blocks`: row blocks, each writing its row strips of the one file (classic container).  The classic file is byte for byte
+    ncsink.writetonc of runmicro1Cpp's arrays.  -> the file's variable names"""
+    from . import ncsink
+    lib = _abi.load()
+    hours, east, north, crs = ncsink.grid_of(grid, obstime)
+    hgt = np.asarray(vegp["hgt"])
+    sp, names = ncsink.nc_spec(hgt.shape[0], hgt.shape[1], hours, east, north, reqhgt, vars, crs, reference_puts_only, format,
+                               deflate_level)
+    out = [1 if n in names else 0 for n in _abi.OUT_NAMES]
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat, out,
+                bool(array_forcing) or coarse is not None, device, days_per_chunk, cells_per_block, dfsel, coarse)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_runmicro_nc(C.byref(m.inputs), C.byref(m.options), C.byref(mu[0]) if mu else None, str(fileout).encode(),
+                                   C.byref(sp)))
+    return names
+
+
+def runmicro_depths_nc(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths, zref: float,
+                       lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *, files, grid: Mapping,
+                       tbp=None, soilm: bool = True, format: str = "classic", deflate_level: int = 0,
+                       array_forcing: bool = False, dfsel: Mapping | None = None, coarse: Mapping | None = None, device: int = 0,
+                       days_per_chunk: int = 0, cells_per_block: int = 0) -> None:
+    """runmicro_depths into one `writetonc` file per depth (include/mcf.h mcf_runmicro_depths_nc): files[d] holds Tz at
+    depths[d] under that depth's long name and, with soilm=True, the soil moisture (the same plane in every file)."""
+    from . import ncsink
+    lib = _abi.load()
+    af = bool(array_forcing) or coarse is not None
+    T = len(np.asarray(obstime["year"]))
+    d, t = _depth_list(depths, tbp, T)
+    files = [str(f).encode() for f in files]
+    if len(files) != d.size:
+        raise ValueError("files: one path per depth")
+    reqhgt = float(d[0]) if d.size and d[0] < 0 else -1.0          # (the library judges the list)
+    hours, east, north, crs = ncsink.grid_of(grid, obstime)
+    hgt = np.asarray(vegp["hgt"])
+    sp, names = ncsink.nc_spec(hgt.shape[0], hgt.shape[1], hours, east, north, reqhgt, ("Tz", "soilm") if soilm else ("Tz",), crs,
+                               False, format, deflate_level)
+    m = marshal(obstime, climdata, pointm, vegp, soilc, reqhgt, zref, lat, lon, Sminp, Smaxp, tfact, complete, mat,
+                [1, 0, 0, 1 if soilm else 0, 0, 0, 0, 0, 0, 0], af, device, days_per_chunk, cells_per_block, dfsel, coarse)
+    paths = (C.c_char_p * max(len(files), 1))(*files)
+    _abi.check(lib.mcf_runmicro_depths_nc(C.byref(m.inputs), C.byref(m.options), m.ptr(d), int(d.size), m.ptr(t), paths, C.byref(sp)))
+
+
 def runmicro_depths_summary(obstime: Mapping, climdata: Mapping, pointm: Mapping, vegp: Mapping, soilc: Mapping, depths,
                             zref: float, lat, lon, Sminp: float, Smaxp: float, tfact: float, complete: bool, mat: float, *,
                             periods, tbp=None, vars=("Tz",), stats=("mean", "min", "max"), thresholds=None,

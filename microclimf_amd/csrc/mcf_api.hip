@@ -26,6 +26,7 @@
 #include "mcf_terrain.h"
 #include "mcf_ncfile.hpp"
 #include "mcf_nc4file.hpp"
+#include "mcf_ncsink.hpp"
 #include "mcf_rowblocks.hpp"
 #include "mcf_hiphost.hpp"
 #include "mcf_series_host.hpp"
@@ -962,20 +963,7 @@ int upload_quarters(mcf_plan* p, const int32_t* const q[4], const int32_t nq[4],
 }  // namespace
 
 // ---- writetonc sink (R/dataprep.R:1063-1260) -------------------------------------------------------------------
-struct mcf_ncfile {
-    std::unique_ptr<mcf::NcFile> f;
-    int var_of[MCF_NOUT];        // file variable index of solver output v, or -1
-    int out_of[MCF_NOUT];        // solver output of file variable k
-    double scale[MCF_NOUT];      // per file variable
-    int fill_only[MCF_NOUT];
-    // staging of records on their way to the file; plain arrays, not vectors: no zero-fill of memory about to be overwritten
-    std::unique_ptr<uint8_t[]> stage[2];
-    size_t stage_bytes[2] = {0, 0};
-    uint8_t* staging(int i, size_t n) {
-        if (stage_bytes[i] < n) { stage[i].reset(new uint8_t[n]); stage_bytes[i] = n; }
-        return stage[i].get();
-    }
-};
+// struct mcf_ncfile: mcf_ncsink.hpp (mcf_snow.hip writes the snowpack's records into it too)
 
 namespace {
 
@@ -1026,6 +1014,30 @@ bool nc_var_def(int v, double reqhgt, mcf::NcVarDef* d, double* scale, bool* put
 inline int32_t nc_pack(double x, double scale) {
     const double q = rint(x * scale);
     return (q > -2147483648.0 && q < 2147483648.0) ? (int32_t)q : mcf::NcFile::kMissval;
+}
+
+// the container of a judged handle: created, or the handle deleted with the reason set
+int nc_open(const char* who, mcf_ncfile* nc, const char* path, int32_t format, int32_t deflate_level, int64_t rows, int64_t cols,
+            int64_t nsteps, const double* east, const double* north, const double* time_hours, const char* crs_wkt,
+            const std::vector<mcf::NcVarDef>& defs, mcf_ncfile** out) {
+    std::string e;
+    if (format == MCF_NC_NETCDF4) {
+        // the reference's container (dataprep.R:1110: compression = 9); deflate_level 0 = the reference's 9, -1 = none
+        const int level = deflate_level == 0 ? 9 : deflate_level < 0 ? 0 : deflate_level;
+        mcf::Nc4File* f4 = new mcf::Nc4File();
+        nc->f.reset(f4);
+        if (nsteps == 0) e = "a netCDF-4 file needs at least one time step";
+        else if (level > 9) e = "deflate_level above 9";
+        else e = f4->create4(path, rows, cols, nsteps, east, north, time_hours, crs_wkt, defs, level);
+    } else if (format == MCF_NC_CLASSIC) {
+        nc->f.reset(new mcf::NcFile());
+        e = nc->f->create(path, rows, cols, nsteps, east, north, time_hours, crs_wkt, defs);
+    } else {
+        e = "unknown format";
+    }
+    if (!e.empty()) { delete nc; return fail(MCF_ERR_ARG, std::string(who) + ": " + e); }
+    *out = nc;
+    return MCF_OK;
 }
 
 }  // namespace
@@ -2060,24 +2072,40 @@ int mcf_nc_create(const char* path, const mcf_nc_spec* sp, mcf_ncfile** out) {
         defs.push_back(d);
     }
     if (defs.empty()) { delete nc; return fail(MCF_ERR_ARG, "mcf_nc_create: no variable selected"); }
-    std::string e;
-    if (sp->format == MCF_NC_NETCDF4) {
-        // the reference's container (dataprep.R:1110: compression = 9); deflate_level 0 = the reference's 9, -1 = none
-        const int level = sp->deflate_level == 0 ? 9 : sp->deflate_level < 0 ? 0 : sp->deflate_level;
-        mcf::Nc4File* f4 = new mcf::Nc4File();
-        nc->f.reset(f4);
-        if (sp->nsteps == 0) e = "a netCDF-4 file needs at least one time step";
-        else if (level > 9) e = "deflate_level above 9";
-        else e = f4->create4(path, sp->rows, sp->cols, sp->nsteps, sp->east, sp->north, sp->time_hours, sp->crs_wkt, defs, level);
-    } else if (sp->format == MCF_NC_CLASSIC) {
-        nc->f.reset(new mcf::NcFile());
-        e = nc->f->create(path, sp->rows, sp->cols, sp->nsteps, sp->east, sp->north, sp->time_hours, sp->crs_wkt, defs);
-    } else {
-        e = "unknown format";
+    return nc_open("mcf_nc_create", nc, path, sp->format, sp->deflate_level, sp->rows, sp->cols, sp->nsteps, sp->east, sp->north,
+                   sp->time_hours, sp->crs_wkt, defs, out);
+}
+
+// The snowpack's file (include/mcf.h "netCDF sink: further sources"): the five series of mcf_snowdriver_out as int variables
+int mcf_nc_create_snowpack(const char* path, const mcf_ncpack_spec* sp, mcf_ncfile** out) {
+    const std::string w = "mcf_nc_create_snowpack: ";
+    if (!path || !sp || !out) return fail(MCF_ERR_ARG, w + "null argument");
+    if (sp->rows <= 0 || sp->cols <= 0 || sp->nsteps < 0 || !sp->east || !sp->north || (sp->nsteps > 0 && !sp->time_hours))
+        return fail(MCF_ERR_ARG, w + "bad dimensions or null coordinate vector");
+    static const char* names[5] = {"Tc", "Tg", "groundsnowdepth", "totalSWE", "snowden"};
+    static const char* longs[5] = {"Canopy snow temperature", "Ground snow temperature", "Ground snow depth", "Total snow water equivalent",
+                                   "Snow density"};
+    static const char* units[5] = {"deg C x 100", "deg C x 100", "mm", "mm x 100", "kg / m^3"};
+    static const double scales[5] = {100, 100, 1000, 100, 1};
+    mcf_ncfile* nc = new mcf_ncfile();
+    nc->snowpack = true;
+    std::vector<mcf::NcVarDef> defs;
+    for (int v = 0; v < MCF_NOUT; ++v) nc->var_of[v] = -1;
+    for (int v = 0; v < 5; ++v) {
+        if (!sp->series[v]) continue;
+        if (!(sp->scale[v] >= 0.0 && sp->scale[v] < HUGE_VAL)) { delete nc; return fail(MCF_ERR_ARG, w + "scale of '" + names[v] + "' is negative or not finite"); }
+        const int k = (int)defs.size();
+        nc->var_of[v] = k; nc->out_of[k] = v; nc->scale[k] = sp->scale[v] > 0.0 ? sp->scale[v] : scales[v];
+        nc->fill_only[k] = 0;
+        mcf::NcVarDef d;
+        d.name = names[v];
+        d.long_name = sp->long_name[v] ? sp->long_name[v] : longs[v];
+        d.units = sp->units[v] ? sp->units[v] : units[v];
+        defs.push_back(d);
     }
-    if (!e.empty()) { delete nc; return fail(MCF_ERR_ARG, "mcf_nc_create: " + e); }
-    *out = nc;
-    return MCF_OK;
+    if (defs.empty()) { delete nc; return fail(MCF_ERR_ARG, w + "no series selected"); }
+    return nc_open("mcf_nc_create_snowpack", nc, path, sp->format, sp->deflate_level, sp->rows, sp->cols, sp->nsteps, sp->east, sp->north,
+                   sp->time_hours, sp->crs_wkt, defs, out);
 }
 
 int mcf_nc_close(mcf_ncfile* nc) {
@@ -2111,25 +2139,36 @@ int mcf_nc_write_host(mcf_ncfile* nc, int64_t step0, int64_t nsteps, const doubl
     return MCF_OK;
 }
 
-int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_step0, int64_t file_step0, int64_t nsteps,
-                      float* kernel_ms) {
+// Steps [slot_step0, slot_step0 + nsteps) of ring slot `slot` as rows [row0, row0 + plan rows) of records [file_step0, ...):
+// k_pack_nc packs the plan's rows as records of their own ([step][8 B | var][plan rows][cols]), which are the file's records
+// where the plan's grid is the file's and a row strip of them otherwise.  tz_only: every variable but Tz holds missval (the steps a
+// streamed below-ground chunk leaves behind its last whole day).
+static int nc_write_rows(const std::string& w, mcf_ncfile* nc, mcf_plan* p, int32_t slot, int32_t depth, int64_t row0, int64_t slot_step0,
+                         int64_t file_step0, int64_t nsteps, float* kernel_ms, bool tz_only) {
     if (!nc || !p) return fail(MCF_ERR_ARG, "null argument");
-    if (nc->f->rows != p->rows || nc->f->cols != p->cols) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: the file's grid is not the plan's");
+    if (nc->snowpack) return fail(MCF_ERR_ARG, w + "the file holds the snowpack's series (mcf_snowplan_nc_write)");
+    const bool whole = row0 == 0 && nc->f->rows == p->rows;
+    if (nc->f->cols != p->cols || row0 < 0 || row0 + p->rows > nc->f->rows)
+        return fail(MCF_ERR_ARG, w + (row0 == 0 ? "the file's grid is not the plan's" : "the plan's rows at row0 are not a row strip of the file's grid"));
+    if (!whole && !nc->f->takes_strips())
+        return fail(MCF_ERR_ARG, w + "the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block, not a row strip");
+    if (depth != 0 && (!p->bg_stream || depth < 0 || depth >= std::max<int>(1, (int)p->depths.size())))
+        return fail(MCF_ERR_ARG, w + "depth " + std::to_string(depth) + " is outside the plan's list (0 unless the plan is streamed below ground with depths)");
     if (const int rc = check_slot_range(p, slot, kAnyVar, slot_step0, nsteps)) return rc;
-    if (file_step0 < 0 || file_step0 + nsteps > nc->f->nsteps) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: step range outside the file");
+    if (file_step0 < 0 || file_step0 + nsteps > nc->f->nsteps) return fail(MCF_ERR_ARG, w + "step range outside the file");
     mcf::PackNcArgs a{};
     a.nv = nc->f->nvars; a.missval = mcf::NcFile::kMissval; a.rows = p->rows; a.cols = p->cols;
-    a.rec_words = nc->f->rec_bytes / 4;
+    const int64_t rb = 8 + (int64_t)a.nv * p->N * 4;      // a packed record of the plan's rows: the file's own where the grids agree
+    a.rec_words = rb / 4;
     for (int k = 0; k < a.nv; ++k) {
         const int v = nc->out_of[k];
         a.scale[k] = nc->scale[k];
-        a.fill_only[k] = nc->fill_only[k];
+        a.fill_only[k] = nc->fill_only[k] || (tz_only && v != MCF_OUT_TZ);
         if (a.fill_only[k]) { a.src[k] = mcf::RingView{p->d_ring, p->N, 0, 0, 0}; continue; }   // never read
-        if (p->var_slot[v] < 0) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: a variable of the file was not requested in out[]");
-        a.src[k] = ring_view(p, slot, v);
+        if (p->var_slot[v] < 0) return fail(MCF_ERR_ARG, w + "a variable of the file was not requested in out[]");
+        a.src[k] = v == MCF_OUT_TZ && depth != 0 ? depth_view(p, slot, depth) : ring_view(p, slot, v);
     }
     HIP_TRY(hipSetDevice(p->device));
-    const int64_t rb = nc->f->rec_bytes;
     int64_t piece = std::min<int64_t>(65535 / a.nv, std::max<int64_t>(1, ((int64_t)256 << 20) / rb));
     piece = std::min(piece, std::max<int64_t>(nsteps, 1));
     if (p->pack_elems < piece * (rb / 4)) {
@@ -2139,6 +2178,8 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
         p->pack_elems = piece * (rb / 4);
     }
     a.dst = p->d_pack;
+    // a row strip is staged in this call's own buffers: the blocks' workers write strips of one file at the same time
+    std::unique_ptr<uint8_t[]> own[2];
     std::future<std::string> pending;            // the previous piece going to disk while this one is packed and copied
     float kms = 0;
     int rc = MCF_OK;
@@ -2154,7 +2195,12 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
         if (e == hipSuccess && kernel_ms) e = hipEventRecord(p->ev1, p->stream);
         // stage[i & 1] was handed to the writer two pieces ago: that write has been joined (below) before piece i-1 began
         const size_t bytes = (size_t)(n * rb);
-        uint8_t* st = nc->staging((int)(i & 1), bytes);
+        uint8_t* st;
+        if (whole) st = nc->staging((int)(i & 1), bytes);
+        else {
+            if (!own[i & 1]) own[i & 1].reset(new uint8_t[(size_t)(piece * rb)]);
+            st = own[i & 1].get();
+        }
         if (e == hipSuccess) e = p->tohost.dense(st, p->d_pack, bytes, p->stream);
         if (e == hipSuccess && kernel_ms) {
             float ms = 0;
@@ -2162,20 +2208,71 @@ int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_st
             kms += ms;
         }
         if (pending.valid()) werr = pending.get();
-        if (e != hipSuccess) { rc = fail(MCF_ERR_HIP, std::string("mcf_nc_write_plan: ") + hipGetErrorString(e)); break; }
+        if (e != hipSuccess) { rc = fail(MCF_ERR_HIP, w + hipGetErrorString(e)); break; }
         if (!werr.empty()) break;
         mcf::NcFile* f = nc->f.get();
         uint8_t* data = st;
-        const int64_t fs = file_step0 + s0;
-        pending = std::async(std::launch::async, [f, fs, n, data] { return f->write_records(fs, n, data); });
+        const int64_t fs = file_step0 + s0, nr = p->rows;
+        if (whole) pending = std::async(std::launch::async, [f, fs, n, data] { return f->write_records(fs, n, data); });
+        else pending = std::async(std::launch::async, [f, fs, n, row0, nr, data] { return f->write_strip(fs, n, row0, nr, data); });
     }
     if (pending.valid()) {
         const std::string e2 = pending.get();
         if (werr.empty()) werr = e2;
     }
     if (rc != MCF_OK) return rc;
-    if (!werr.empty()) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: " + werr);
+    if (!werr.empty()) return fail(MCF_ERR_ARG, w + werr);
     if (kernel_ms) *kernel_ms = kms;
+    return MCF_OK;
+}
+int mcf_nc_write_plan(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int64_t slot_step0, int64_t file_step0, int64_t nsteps,
+                      float* kernel_ms) {
+    if (nc && p && nc->f->rows != p->rows) return fail(MCF_ERR_ARG, "mcf_nc_write_plan: the file's grid is not the plan's");
+    return nc_write_rows("mcf_nc_write_plan: ", nc, p, slot, 0, 0, slot_step0, file_step0, nsteps, kernel_ms, false);
+}
+int mcf_nc_write_plan_rows(mcf_ncfile* nc, mcf_plan* p, int32_t slot, int32_t depth, int64_t row0, int64_t slot_step0, int64_t file_step0,
+                           int64_t nsteps, float* kernel_ms) {
+    return nc_write_rows("mcf_nc_write_plan_rows: ", nc, p, slot, depth, row0, slot_step0, file_step0, nsteps, kernel_ms, false);
+}
+// Host only: missval in every variable of rows [row0, row0 + nrows) of records [file_step0, file_step0 + nsteps)
+int mcf_nc_write_missing(mcf_ncfile* nc, int64_t row0, int64_t nrows, int64_t file_step0, int64_t nsteps) {
+    const std::string w = "mcf_nc_write_missing: ";
+    if (!nc) return fail(MCF_ERR_ARG, w + "null argument");
+    if (file_step0 < 0 || nsteps < 0 || file_step0 + nsteps > nc->f->nsteps) return fail(MCF_ERR_ARG, w + "step range outside the file");
+    if (row0 < 0 || nrows < 1 || row0 + nrows > nc->f->rows) return fail(MCF_ERR_ARG, w + "row strip outside the file's grid");
+    if (!(row0 == 0 && nrows == nc->f->rows) && !nc->f->takes_strips())
+        return fail(MCF_ERR_ARG, w + "the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block, not a row strip");
+    const std::string e = mcf::nc_write_missing(nc->f.get(), row0, nrows, file_step0, nsteps);
+    return e.empty() ? (int)MCF_OK : fail(MCF_ERR_ARG, w + e);
+}
+// Host only: rows [row0, row0 + nrows) of records [step0, step0 + nsteps) from host arrays, vars[v] = [nrows, cols, nsteps]
+// column-major doubles (a row block's arrays); mcf_nc_write_host is this with the whole raster
+int mcf_nc_write_host_rows(mcf_ncfile* nc, int64_t row0, int64_t nrows, int64_t step0, int64_t nsteps, const double* const vars[MCF_NOUT]) {
+    const std::string w = "mcf_nc_write_host_rows: ";
+    if (!nc || !vars) return fail(MCF_ERR_ARG, w + "null argument");
+    if (step0 < 0 || nsteps < 0 || step0 + nsteps > nc->f->nsteps) return fail(MCF_ERR_ARG, w + "step range outside the file");
+    if (row0 < 0 || nrows < 1 || row0 + nrows > nc->f->rows) return fail(MCF_ERR_ARG, w + "row strip outside the file's grid");
+    if (!(row0 == 0 && nrows == nc->f->rows) && !nc->f->takes_strips())
+        return fail(MCF_ERR_ARG, w + "the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block, not a row strip");
+    const int nv = nc->f->nvars;
+    const int64_t R = nrows, C = nc->f->cols, N = R * C, rb = 8 + (int64_t)nv * N * 4;
+    for (int k = 0; k < nv; ++k)
+        if (!nc->fill_only[k] && !vars[nc->out_of[k]]) return fail(MCF_ERR_ARG, w + "a variable of the file is missing");
+    const int64_t piece = std::max<int64_t>(1, std::min(std::max<int64_t>(nsteps, 1), ((int64_t)64 << 20) / rb));
+    std::unique_ptr<uint8_t[]> st(new uint8_t[(size_t)(piece * rb)]);      // (this call's own: several threads write strips at once)
+    for (int64_t s0 = 0; s0 < nsteps; s0 += piece) {
+        const int64_t n = std::min(piece, nsteps - s0);
+        for (int64_t s = 0; s < n; ++s)
+            for (int k = 0; k < nv; ++k) {
+                uint8_t* dst = st.get() + s * rb + 8 + (int64_t)k * N * 4;
+                const double* src = nc->fill_only[k] ? nullptr : vars[nc->out_of[k]] + (s0 + s) * N;
+                for (int64_t r = 0; r < R; ++r)
+                    for (int64_t c = 0; c < C; ++c)
+                        mcf::NcFile::store_i32(dst + 4 * (c + C * r), src ? nc_pack(src[r + R * c], nc->scale[k]) : mcf::NcFile::kMissval);
+            }
+        const std::string e = nc->f->write_strip(step0 + s0, n, row0, nrows, st.get());
+        if (!e.empty()) return fail(MCF_ERR_ARG, w + e);
+    }
     return MCF_OK;
 }
 
@@ -3214,14 +3311,18 @@ static int bioclim_depths_finish(mcf_plan* p, const mcf_grid_inputs* in, const B
 
 // The one-call entries' driver: a streamed below-ground plan with the depth list, through day chunks of `chunk_days` days (0: what
 // the free memory gives), for the entry's sink: every step of every depth, the period summaries, the bioclim variables or the series
+// D = 0 (depths null): no list, the one depth of opt->reqhgt (mcf_runmicro_nc below ground); twi_mean / sharers: a row block of a
+// taller raster, as for run_oneshot
 static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_options* opt_in, const double* depths, int32_t D,
-                      const double* tbp, int32_t chunk_days, const RunSink& sink) {
+                      const double* tbp, int32_t chunk_days, const RunSink& sink, const double* twi_mean = nullptr, int sharers = 1) {
     const std::string w = std::string(who) + ": ";
     if (!in || !opt_in) return fail(MCF_ERR_ARG, w + "null argument");
     mcf_options opt = *opt_in;
-    int rc = check_depths(who, depths, D, tbp, opt.complete != 0, in->array_forcing != 0);
+    const bool listed = depths != nullptr || D != 0;
+    int rc = listed ? check_depths(who, depths, D, tbp, opt.complete != 0, in->array_forcing != 0) : (int)MCF_OK;
     if (rc) return rc;
-    opt.reqhgt = depths[0];
+    if (listed) opt.reqhgt = depths[0];
+    else D = 1;
     if ((rc = check_inputs(in, &opt))) return rc;
     const int64_t T = in->tsteps;
     const int ndays = (int)(T / 24);
@@ -3234,14 +3335,15 @@ static int run_depths(const char* who, const mcf_grid_inputs* in, const mcf_opti
     const bool tail = T > (int64_t)ndays * 24;      // the steps behind the last whole day: one day more per slot
     int chunk = chunk_days;
     // (the solver's variables, the forcing ring, the chunk's Tg ring and the D - 1 depth slabs per day)
-    if (chunk <= 0 && (rc = free_memory_chunk_days(in->rows * in->cols, ndays, 1, nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1),
+    if (chunk <= 0 && (rc = free_memory_chunk_days(in->rows * in->cols, ndays, sharers, nvars + (in->array_forcing ? 15 : 0) + 1 + (D - 1),
                                                    below_state_doubles(D, ndays) + sink.state_doubles, tail, &chunk)))
         return rc;
     chunk = std::max(1, std::min(chunk, ndays));
     mcf_plan* p = nullptr;
     if ((rc = plan_create(in, &opt, chunk + (tail ? 1 : 0), 1, true, &p, nullptr))) return rc;
     PlanHolder holder(p);
-    if ((rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
+    if (twi_mean && (rc = mcf_plan_set_twi_mean(p, *twi_mean))) return rc;
+    if (listed && (rc = mcf_plan_below_set_depths(p, depths, D, tbp))) return rc;
     if ((rc = mcf_plan_below_prepare(p, in))) return rc;
     return run_sink_chunks(p, in, ndays, chunk, sink);
 }
@@ -3750,6 +3852,149 @@ int mcf_runmicro_series_multi(const mcf_grid_inputs* in, const mcf_options* opt,
             if (spec->zstat[k]) mcf::series_state_finish(state.data(), spec->nzones, steps, T, nullptr, k, out->zones[v][k]);
     }
     return MCF_OK;
+}
+
+// ---- netCDF sink: the one-call solver entries (include/mcf.h "netCDF sink: further sources") ------------------
+}  // extern "C"
+namespace mcf {   // mcf_ncsink.hpp: the one-call entries' refusals that need no device, shared with mcf_snowrun.hip
+static const char* const kNc4OneBlock =
+    "the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block (multi = NULL or n_blocks = 1)";
+int nc_spec_check(const std::string& w, const mcf_nc_spec* spec, int64_t rows, int64_t cols, int64_t tsteps, double reqhgt,
+                  const int32_t* out, bool several_blocks) {
+    if (spec->rows != rows) return fail(MCF_ERR_ARG, w + "rows of the mcf_nc_spec are not the inputs' rows");
+    if (spec->cols != cols) return fail(MCF_ERR_ARG, w + "cols of the mcf_nc_spec are not the inputs' cols");
+    if (spec->nsteps != tsteps) return fail(MCF_ERR_ARG, w + "nsteps of the mcf_nc_spec is not the inputs' tsteps");
+    if (!(spec->reqhgt == reqhgt)) return fail(MCF_ERR_ARG, w + "reqhgt of the mcf_nc_spec is not the run's");
+    if (!spec->east || !spec->north || (spec->nsteps > 0 && !spec->time_hours)) return fail(MCF_ERR_ARG, w + "null coordinate vector");
+    int n = 0;
+    for (int v = 0; v < MCF_NOUT; ++v) {
+        if (!spec->vars[v]) continue;
+        mcf::NcVarDef d;
+        double sc;
+        bool put;
+        if (!nc_var_def(v, reqhgt, &d, &sc, &put)) return fail(MCF_ERR_ARG, w + "writetonc defines no variable '" + d.name + "' at this reqhgt");
+        if (out && !out[v]) return fail(MCF_ERR_ARG, w + "a variable of the mcf_nc_spec is not among the run's (opt->out)");
+        ++n;
+    }
+    if (n == 0) return fail(MCF_ERR_ARG, w + "no variable selected");
+    if (spec->format != MCF_NC_CLASSIC && spec->format != MCF_NC_NETCDF4) return fail(MCF_ERR_ARG, w + "unknown format");
+    if (spec->format == MCF_NC_NETCDF4 && several_blocks) return fail(MCF_ERR_ARG, w + kNc4OneBlock);
+    return MCF_OK;
+}
+int ncpack_spec_check(const std::string& w, const mcf_ncpack_spec* spec, int64_t rows, int64_t cols, int64_t tsteps, bool several_blocks) {
+    if (spec->rows != rows) return fail(MCF_ERR_ARG, w + "rows of the mcf_ncpack_spec are not the inputs' rows");
+    if (spec->cols != cols) return fail(MCF_ERR_ARG, w + "cols of the mcf_ncpack_spec are not the inputs' cols");
+    if (spec->nsteps != tsteps) return fail(MCF_ERR_ARG, w + "nsteps of the mcf_ncpack_spec is not the inputs' tsteps");
+    if (!spec->east || !spec->north || (spec->nsteps > 0 && !spec->time_hours)) return fail(MCF_ERR_ARG, w + "null coordinate vector");
+    int n = 0;
+    for (int v = 0; v < 5; ++v) n += spec->series[v] ? 1 : 0;
+    if (n == 0) return fail(MCF_ERR_ARG, w + "no series selected");
+    if (spec->format != MCF_NC_CLASSIC && spec->format != MCF_NC_NETCDF4) return fail(MCF_ERR_ARG, w + "unknown format");
+    if (spec->format == MCF_NC_NETCDF4 && several_blocks) return fail(MCF_ERR_ARG, w + kNc4OneBlock);
+    return MCF_OK;
+}
+}  // namespace mcf
+extern "C" {
+using mcf::NcHolder;
+
+// the sink of one block (or the whole raster, r0 = 0) at a height above ground, and below ground with the tail's Tz
+static RunSink nc_run_sink(const std::string& w, mcf_ncfile* nc, const mcf_nc_spec* spec, const mcf_grid_inputs* in, int64_t r0, bool below) {
+    RunSink sink;
+    for (int v = 0; v < MCF_NOUT; ++v) sink.out[v] = spec->vars[v] ? 1 : 0;      // the plan has exactly the file's variables
+    const int64_t T = in->tsteps, nrows = in->rows;
+    const int ndays = (int)(T / 24);
+    sink.enable = [](mcf_plan*) { return (int)MCF_OK; };
+    sink.fold = [=](mcf_plan* p, int d0, int nd) -> int {
+        int rc = nc_write_rows(w, nc, p, 0, 0, r0, 0, (int64_t)d0 * 24, (int64_t)nd * 24, nullptr, false);
+        // below ground the last chunk leaves the steps behind the last whole day in its slot, Tz only
+        if (!rc && below && d0 + nd == ndays && T % 24)
+            rc = nc_write_rows(w, nc, p, 0, 0, r0, (int64_t)nd * 24, (int64_t)ndays * 24, T % 24, nullptr, true);
+        return rc;
+    };
+    sink.finish = [=](mcf_plan*) -> int {
+        if (below || T % 24 == 0) return MCF_OK;
+        const std::string e = mcf::nc_write_missing(nc->f.get(), r0, nrows, (int64_t)ndays * 24, T % 24);
+        return e.empty() ? (int)MCF_OK : fail(MCF_ERR_ARG, w + e);
+    };
+    return sink;
+}
+
+int mcf_runmicro_nc(const mcf_grid_inputs* in, const mcf_options* opt, const mcf_multi* mu, const char* path, const mcf_nc_spec* spec) {
+    const char* who = "mcf_runmicro_nc";
+    const std::string w = std::string(who) + ": ";
+    if (!in || !opt || !path || !spec) return fail(MCF_ERR_ARG, w + "null argument");
+    int rc = check_inputs(in, opt);
+    if (!rc) rc = mcf::nc_spec_check(w, spec, in->rows, in->cols, in->tsteps, opt->reqhgt, nullptr, mu && mu->n_blocks != 1);
+    const bool below = opt->reqhgt < 0.0;
+    if (!rc && below && in->tsteps < 24) rc = fail(MCF_ERR_ARG, w + "the series is shorter than a day");
+    if (!rc && opt->days_per_chunk < 0) rc = fail(MCF_ERR_ARG, w + "negative days_per_chunk");
+    if (!rc && mu && mu->n_devices > 0 && !mu->devices) rc = fail(MCF_ERR_ARG, w + "n_devices > 0 with a null device list");
+    if (rc) {
+        if (g_err.compare(0, w.size(), w) != 0) g_err = w + g_err;      // (the shared checks' messages)
+        return rc;
+    }
+    if ((rc = mu ? mcf::device_list(mu, 0, nullptr) : ensure_device(opt->device))) return rc;      // no file without a device to fill it
+    mcf_ncfile* nc = nullptr;
+    if ((rc = mcf_nc_create(path, spec, &nc))) return rc;
+    NcHolder holder(nc);
+    const int chunk_days = opt->days_per_chunk;
+    auto block = [&](const mcf_grid_inputs& sub, const mcf_options& o, int64_t r0, const double* twi_mean, int sharers) -> int {
+        const RunSink sink = nc_run_sink(w, nc, spec, &sub, r0, below);
+        if (below) return run_depths(who, &sub, &o, nullptr, 0, nullptr, chunk_days, sink, twi_mean, sharers);
+        return run_sink(&sub, &o, chunk_days, sink, twi_mean);
+    };
+    rc = mu ? for_row_blocks(in, opt, mu, block) : block(*in, *opt, 0, nullptr, 1);
+    return rc ? rc : mcf::close_file(holder);      // (a failed run's file is closed by its holder, the run's message kept)
+}
+
+int mcf_runmicro_depths_nc(const mcf_grid_inputs* in, const mcf_options* opt, const double* depths, int32_t D, const double* tbp,
+                           const char* const* paths, const mcf_nc_spec* spec) {
+    const char* who = "mcf_runmicro_depths_nc";
+    const std::string w = std::string(who) + ": ";
+    if (!in || !opt || !paths || !spec) return fail(MCF_ERR_ARG, w + "null argument");
+    int rc = check_depths(who, depths, D, tbp, opt->complete != 0, in->array_forcing != 0);
+    if (rc) return rc;
+    for (int d = 0; d < D; ++d)
+        if (!paths[d]) return fail(MCF_ERR_ARG, w + "paths[" + std::to_string(d) + "] is null");
+    if (!spec->vars[MCF_OUT_TZ]) return fail(MCF_ERR_ARG, w + "a file per depth holds Tz (vars[MCF_OUT_TZ])");
+    {   // (the spec's own reqhgt is not read: file d is made at depths[d])
+        mcf_nc_spec s0 = *spec;
+        s0.reqhgt = depths[0];
+        if ((rc = mcf::nc_spec_check(w, &s0, in->rows, in->cols, in->tsteps, depths[0], nullptr, false))) return rc;
+    }
+    if (opt->days_per_chunk < 0) return fail(MCF_ERR_ARG, w + "negative days_per_chunk");
+    if (in->tsteps < 24) return fail(MCF_ERR_ARG, w + "the series is shorter than a day");
+    if ((rc = ensure_device(opt->device))) return rc;
+    std::vector<NcHolder> files;
+    for (int d = 0; d < D; ++d) {
+        mcf_nc_spec sd = *spec;
+        sd.reqhgt = depths[d];
+        mcf_ncfile* nc = nullptr;
+        if ((rc = mcf_nc_create(paths[d], &sd, &nc))) return rc;
+        files.emplace_back(nc);
+    }
+    const int64_t T = in->tsteps;
+    const int ndays = (int)(T / 24);
+    RunSink sink;
+    sink.out[MCF_OUT_TZ] = 1;
+    sink.out[MCF_OUT_SOILM] = spec->vars[MCF_OUT_SOILM] ? 1 : 0;
+    sink.enable = [](mcf_plan*) { return (int)MCF_OK; };
+    sink.fold = [&](mcf_plan* p, int d0, int nd) -> int {
+        for (int d = 0; d < D; ++d) {
+            int rcf = nc_write_rows(w, files[(size_t)d].get(), p, 0, d, 0, 0, (int64_t)d0 * 24, (int64_t)nd * 24, nullptr, false);
+            if (!rcf && d0 + nd == ndays && T % 24)
+                rcf = nc_write_rows(w, files[(size_t)d].get(), p, 0, d, 0, (int64_t)nd * 24, (int64_t)ndays * 24, T % 24, nullptr, true);
+            if (rcf) return rcf;
+        }
+        return MCF_OK;
+    };
+    sink.finish = [](mcf_plan*) { return (int)MCF_OK; };
+    rc = run_depths(who, in, opt, depths, D, tbp, opt->days_per_chunk, sink);
+    for (auto& f : files) {
+        const int rcc = rc ? (int)MCF_OK : mcf::close_file(f);
+        if (rcc) rc = rcc;
+    }
+    return rc;
 }
 
 int mcf_runmicro1(const mcf_grid_inputs* in, const mcf_options* opt, mcf_outputs* out) {

@@ -465,6 +465,20 @@ struct PackNcArgs {
 };
 // at most 65535 / nv steps per launch
 void launch_pack_nc(const PackNcArgs& a, int64_t nsteps, hipStream_t s);
+// k_pack_nc_planes (mcf_ncpack.hip): the same records from step-major planes — series[k][step * N + c], N = rows * cols,
+// c = row + rows * col (the snow plan's chunk series) — for up to 5 variables, none of them null
+struct PackNcPlanesArgs {
+    const double* series[5];
+    int64_t step0;           // first step (of the planes) of this launch
+    double scale[5];
+    int32_t nv;
+    int32_t missval;
+    int64_t rows, cols;
+    int64_t rec_words;       // record length in 4-byte words (2 + nv * rows * cols)
+    int32_t* dst;            // first record
+};
+// at most 65535 / nv steps per launch
+void launch_pack_nc_planes(const PackNcPlanesArgs& a, int64_t nsteps, hipStream_t s);
 void launch_pack_transpose(const RingView& src, int64_t step0, int64_t rows, int64_t cols, int64_t nsteps, double scale,
                            int32_t* dst, hipStream_t s);
 // out2: twi_scratch_doubles() doubles; [0] = sum, [1] = count on completion

@@ -248,6 +248,9 @@ public:
         return "";
     }
 
+    // a step is chunked into row strips of the whole raster, which a row block's cut need not respect: whole rasters only
+    bool takes_strips() const override { return false; }
+
     // records [step0, step0 + n) in the classic container's record shape (8 time bytes, then per variable [rows][cols] big-endian int32)
     std::string write_records(int64_t step0, int64_t n, uint8_t* recs) override {
         if (file_ < 0) return "file is closed";

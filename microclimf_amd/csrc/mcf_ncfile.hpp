@@ -146,6 +146,35 @@ public:
         return "";
     }
 
+    // Whether rows [row0, row0 + nrows) of a step may be written on their own.  Here a variable's step is rows x cols
+    // contiguous values, so a row strip is one contiguous run; the netCDF-4 container chunks a step by its own strips.
+    virtual bool takes_strips() const { return true; }
+
+    // Rows [row0, row0 + nrows) of records [step0, step0 + n): `strip` holds them as the device packs a row block,
+    // [step][8 B unused | var][nrows][cols] big-endian int32, 8 + nvars * nrows * cols * 4 bytes per step.  One pwrite per
+    // (step, var) at rec_begin + step * rec_bytes + 8 + var * slab + row0 * cols * 4, and the step's time word with it:
+    // every strip writer sets the same 8 bytes, so a record has its time whichever block wrote it, in whatever order.
+    // Safe from several threads at once on strips that do not overlap: pwrite carries its own offset and nothing of the
+    // object changes.  A strip that is the whole raster goes through write_records (and so into either container).
+    std::string write_strip(int64_t step0, int64_t n, int64_t row0, int64_t nrows, uint8_t* strip) {
+        if (fd_ < 0 && takes_strips()) return "file is closed";
+        if (step0 < 0 || n < 0 || step0 + n > nsteps) return "record range outside the file";
+        if (row0 < 0 || nrows < 1 || row0 + nrows > rows) return "row strip outside the file's grid";
+        if (row0 == 0 && nrows == rows) return write_records(step0, n, strip);
+        if (!takes_strips()) return "this container takes whole rasters only";
+        const int64_t slab = rows * cols * 4, part = nrows * cols * 4, srec = 8 + (int64_t)nvars * part;
+        for (int64_t s = 0; s < n; ++s) {
+            const int64_t rec = rec_begin + (step0 + s) * rec_bytes;
+            uint8_t tw[8];
+            store_f64(tw, time_hours[step0 + s]);
+            std::string e = write_at(tw, 8, rec);
+            for (int k = 0; e.empty() && k < nvars; ++k)
+                e = write_at(strip + s * srec + 8 + (int64_t)k * part, (size_t)part, rec + 8 + (int64_t)k * slab + row0 * cols * 4);
+            if (!e.empty()) return e;
+        }
+        return "";
+    }
+
     virtual std::string close() {
         std::string e;
         if (fd_ >= 0 && ::close(fd_) != 0) e = std::string("close: ") + strerror(errno);

@@ -28,6 +28,8 @@
 #include "mcf_snow_device.hpp"
 #include "mcf_snow_plan.hpp"
 #include "mcf_sinks_host.hpp"
+#include "mcf_ncsink.hpp"
+#include "mcf_kernels.h"
 
 // the ring kernel (lane per cell-hour, cell table in LDS, step record through scalar loads): 141 VGPRs without scratch at three
 // waves per SIMD, 128 + 44 B (eight spill stores and loads per hour) at four — measured 0.515 against 0.55 s per simulated year
@@ -1877,6 +1879,8 @@ struct mcf_snowplan {
     // mcf_snowplan_set_series: which of the five device series (bit 0 Tc, 1 Tg, 2 totalSWE, 3 ground snow depth, 4 density) the
     // next run_chunk writes; series_valid: what the plan's working buffers hold of the chunk run last
     uint32_t series_mask = 31, series_valid = 0;
+    int32_t* d_ncpack = nullptr;         // mcf_snowplan_nc_write: a piece of packed records on its way to the host
+    int64_t ncpack_elems = 0;
     uint8_t* d_tflag = nullptr;          // mcf_snowplan_covered_tiles: one flag per tile of the solver plan
     int64_t tflag_cap = 0;
     uint8_t* d_need = nullptr;           // mcf_snowplan_free_cells: one flag per cell + an 8-byte count behind them
@@ -4291,6 +4295,112 @@ extern "C" int mcf_snowplan_series_fetch_zones(mcf_snowplan* sp, int32_t series,
     HIP_TRY(hipGetLastError());
     HIP_TRY(sp->dl.dense(dst, sp->d_se_plane, (size_t)(T * sp->se_nzones) * 8));
     return MCF_OK;
+}
+
+// ---- netCDF sink of the five series (include/mcf.h "netCDF sink: further sources"; the kernel: mcf_ncpack.hip)
+namespace mcf {
+// Steps [step0, step0 + nsteps) of step-major device planes (dev[v]: series v of the file's, null: not held) as rows
+// [row0, row0 + rows) of records [file_step0, ...) of a snowpack file: packed a piece at a time into *d_pack (grown through
+// `grow`), copied and written before the next piece is packed.  On the null stream, behind the kernel that wrote the planes.
+template <class Grow>
+static int pack_planes_to_file(const std::string& w, mcf_ncfile* nc, const double* const dev[5], int64_t rows, int64_t cols, int64_t row0,
+                               int64_t step0, int64_t file_step0, int64_t nsteps, int32_t** d_pack, int64_t* pack_elems, Grow&& grow,
+                               ToHost& dl, float* kernel_ms) {
+    NcFile* f = nc->f.get();
+    if (!nc->snowpack) return api_fail(MCF_ERR_ARG, w + "the file does not hold the snowpack's series (mcf_nc_create_snowpack)");
+    if (f->cols != cols || row0 < 0 || rows < 1 || row0 + rows > f->rows) return api_fail(MCF_ERR_ARG, w + "the rows at row0 are not a row strip of the file's grid");
+    if (!(row0 == 0 && rows == f->rows) && !f->takes_strips())
+        return api_fail(MCF_ERR_ARG, w + "the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block, not a row strip");
+    if (file_step0 < 0 || nsteps < 0 || file_step0 + nsteps > f->nsteps) return api_fail(MCF_ERR_ARG, w + "step range outside the file");
+    PackNcPlanesArgs a{};
+    a.nv = f->nvars; a.missval = NcFile::kMissval; a.rows = rows; a.cols = cols;
+    const int64_t rb = 8 + (int64_t)a.nv * rows * cols * 4;
+    a.rec_words = rb / 4;
+    for (int k = 0; k < a.nv; ++k) {
+        a.series[k] = dev[nc->out_of[k]];
+        a.scale[k] = nc->scale[k];
+        if (!a.series[k]) return api_fail(MCF_ERR_ARG, w + "a series of the file is missing");
+    }
+    if (kernel_ms) *kernel_ms = 0;
+    if (nsteps == 0) return MCF_OK;
+    const int64_t piece = std::min<int64_t>(nsteps, std::min<int64_t>(65535 / a.nv, std::max<int64_t>(1, ((int64_t)256 << 20) / rb)));
+    if (*pack_elems < piece * (rb / 4)) {
+        if (const int rc = grow(d_pack, piece * (rb / 4))) return rc;
+        *pack_elems = piece * (rb / 4);
+    }
+    a.dst = *d_pack;
+    std::unique_ptr<uint8_t[]> st(new uint8_t[(size_t)(piece * rb)]);      // this call's own: the blocks' workers write at the same time
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    if (kernel_ms) { HIP_TRY(hipEventCreate(&ev0)); HIP_TRY(hipEventCreate(&ev1)); }
+    int rc = MCF_OK;
+    for (int64_t s0 = 0; s0 < nsteps && !rc; s0 += piece) {
+        const int64_t n = std::min(piece, nsteps - s0);
+        a.step0 = step0 + s0;
+        hipError_t e = kernel_ms ? hipEventRecord(ev0, nullptr) : hipSuccess;
+        launch_pack_nc_planes(a, n, nullptr);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess && kernel_ms) e = hipEventRecord(ev1, nullptr);
+        if (e == hipSuccess) e = dl.dense(st.get(), *d_pack, (size_t)(n * rb));
+        if (e == hipSuccess && kernel_ms) {
+            float ms = 0;
+            e = hipEventSynchronize(ev1);
+            if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev0, ev1);
+            *kernel_ms += ms;
+        }
+        if (e != hipSuccess) { rc = api_fail(MCF_ERR_HIP, w + hipGetErrorString(e)); break; }
+        const std::string we = f->write_strip(file_step0 + s0, n, row0, rows, st.get());
+        if (!we.empty()) rc = api_fail(MCF_ERR_ARG, w + we);
+    }
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    return rc;
+}
+}  // namespace mcf
+
+extern "C" int mcf_snowplan_nc_write(mcf_snowplan* sp, mcf_ncfile* nc, int32_t ch, int64_t row0) {
+    const std::string w = "mcf_snowplan_nc_write: ";
+    if (!sp || !nc) return mcf::api_fail(MCF_ERR_ARG, w + "null argument");
+    if (ch < 0 || ch >= sp->nchunks) return mcf::api_fail(MCF_ERR_ARG, w + "chunk out of range");
+    if (nc->f->nsteps != sp->T) return mcf::api_fail(MCF_ERR_ARG, w + "the file's steps are not the plan's");
+    static const uint32_t bit[5] = {1u, 2u, 8u, 4u, 16u};      // (as the series sink: bit 2 is totalSWE, bit 3 the ground snow depth)
+    for (int v = 0; v < 5; ++v)
+        if (nc->snowpack && nc->var_of[v] >= 0 && !(sp->series_valid & bit[v]))
+            return mcf::api_fail(MCF_ERR_STATE, w + "a series of the file was switched off for the chunk (mcf_snowplan_set_series)");
+    HIP_TRY(hipSetDevice(sp->device));
+    const double* const dev[5] = {sp->a.Tc, sp->a.Tg, sp->a.sdepg, sp->a.sdepc, sp->a.sden};      // (sdepc: totalSWE after the redistribution)
+    const int64_t k0 = (int64_t)ch * sp->chunk, ns = std::min<int64_t>(sp->chunk, sp->T - k0);
+    int rc = mcf::pack_planes_to_file(w, nc, dev, sp->rows, sp->cols, row0, 0, k0, ns, &sp->d_ncpack, &sp->ncpack_elems,
+                                      [&](int32_t** d, int64_t n) { return sp->b.make(d, n); }, sp->dl, nullptr);
+    if (rc || ch != sp->nchunks - 1) return rc;
+    // the steps no chunk covers stay missval (R pre-fills its arrays with NA, int:2554-2558)
+    const int64_t covered = std::min<int64_t>(sp->T, (int64_t)sp->nchunks * sp->chunk);
+    const std::string e = mcf::nc_write_missing(nc->f.get(), row0, sp->rows, covered, sp->T - covered);
+    return e.empty() ? (int)MCF_OK : mcf::api_fail(MCF_ERR_ARG, w + e);
+}
+
+extern "C" int mcf_nc_write_planes(mcf_ncfile* nc, const double* const series[5], int64_t rows, int64_t row0, int64_t file_step0,
+                                   int64_t nsteps, int32_t device, float* kernel_ms) {
+    const std::string w = "mcf_nc_write_planes: ";
+    if (!nc || !series) return mcf::api_fail(MCF_ERR_ARG, w + "null argument");
+    if (rows < 1 || nsteps < 0) return mcf::api_fail(MCF_ERR_ARG, w + "bad rows / nsteps");
+    if (const int rc = mcf::check_device(device)) return rc;
+    mcf::RestoreDevice restore;
+    HIP_TRY(hipSetDevice(device));
+    mcf::DevOwner b;
+    mcf::ToHost dl;
+    const int64_t n = rows * nc->f->cols * nsteps;
+    const double* dev[5] = {};
+    for (int v = 0; v < 5; ++v) {
+        if (!series[v] || n == 0) continue;
+        double* d = nullptr;
+        if (const int rc = b.make(&d, n)) return rc;
+        HIP_TRY(hipMemcpy(d, series[v], (size_t)n * 8, hipMemcpyHostToDevice));
+        dev[v] = d;
+    }
+    int32_t* d_pack = nullptr;
+    int64_t pack_elems = 0;
+    return mcf::pack_planes_to_file(w, nc, dev, rows, nc->f->cols, row0, 0, file_step0, nsteps, &d_pack, &pack_elems,
+                                    [&](int32_t** d, int64_t m) { return b.make(d, m); }, dl, kernel_ms);
 }
 
 extern "C" int32_t mcf_snowenv_from_name(const char* name) {

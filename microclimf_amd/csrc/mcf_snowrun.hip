@@ -54,6 +54,7 @@
 #include "mcf_snow_plan.hpp"
 #include "mcf_series_host.hpp"
 #include "mcf_sinks_host.hpp"
+#include "mcf_ncsink.hpp"
 
 namespace mcf {   // mcf_api.hip
 int summary_spec_check(const mcf_summary_spec* s, int64_t ndays, const int32_t* out_mask);
@@ -291,6 +292,9 @@ struct mcf_snowrun : SnowBlocks {
     std::vector<int64_t> scells, spcells;
     std::vector<int32_t> szone, spzone;
     uint32_t ser_pack_bits = 0;
+    // netCDF sink (mcf_snowrun_nc_enable): the caller's files, not owned — the merged outputs' (pass 2) and the snowpack's (pass 1)
+    mcf_ncfile *nc_micro = nullptr, *nc_pack = nullptr;
+    uint32_t nc_pack_bits = 0;
 };
 // a run on its way to the caller, or a one-call entry's own: destroyed on every path that does not release() it
 struct SnowRunDestroy { void operator()(mcf_snowrun* h) const { mcf_snowrun_destroy(h); } };
@@ -490,6 +494,19 @@ extern "C" int mcf_snowrun_set_day_layers(mcf_snowrun* h, const int32_t* layer_o
     h->layers_set = true;
     return MCF_OK;
 }
+// between the passes: days that are no-snow days only leave the run's classes (include/mcf.h)
+extern "C" int mcf_snowrun_drop_days(mcf_snowrun* h, const int32_t* drop, int32_t ndays) {
+    const std::string w = "mcf_snowrun_drop_days: ";
+    if (!h || !drop) return api_fail(MCF_ERR_ARG, w + "null argument");
+    if (ndays != h->ndays) return api_fail(MCF_ERR_ARG, w + "one entry per day of the run");
+    if (!h->pass1_done || h->pass2_done) return api_fail(MCF_ERR_STATE, w + "between mcf_snowrun_pass1 (which gives the day classes) and mcf_snowrun_pass2");
+    for (int d = 0; d < ndays; ++d)
+        if (drop[d] && h->snowday[(size_t)d])
+            return api_fail(MCF_ERR_ARG, w + "day " + std::to_string(d) + " is a snow day: pass 1 has folded it into the snow model's means, only a day of the solver alone can be left out");
+    for (int d = 0; d < ndays; ++d)
+        if (drop[d]) h->nosnowday[(size_t)d] = 0;
+    return MCF_OK;
+}
 extern "C" int mcf_snowrun_stats(const mcf_snowrun* h, int64_t stats[4]) {
     if (!h || !stats) return api_fail(MCF_ERR_ARG, "null argument");
     stats[0] = h->st_tile_days; stats[1] = h->st_tile_days_left_out; stats[2] = h->st_chunks_kept; stats[3] = h->st_chunks_rerun;
@@ -525,7 +542,7 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                     // series, pass 1 writes only what it reads itself of such a chunk (totalSWE, density: mcf_snowplan_set_series)
                     int32_t room = 0;
                     if (!rc2 && h->keep) rc2 = mcf_snowplan_can_keep(k.sp, h->keep_reserve, &room);
-                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u | h->pack_bits | h->ser_pack_bits));
+                    if (!rc2) rc2 = mcf_snowplan_set_series(k.sp, (room || smod) ? 31u : (4u | 16u | h->pack_bits | h->ser_pack_bits | h->nc_pack_bits));
                     return rc2;
                 });
                 snow_chunk(*h, w, ch, smod);
@@ -536,6 +553,7 @@ extern "C" int mcf_snowrun_pass1(mcf_snowrun* h, const mcf_snowdriver_out* smod,
                     // the snowpack's summaries: from the series where they lie, before keep_chunk hands the buffers over
                     if (!rc2 && h->sum_pack) rc2 = mcf_snowplan_summary_accumulate(k.sp, ch);
                     if (!rc2 && k.ser_pack) rc2 = mcf_snowplan_series_accumulate(k.sp, ch);
+                    if (!rc2 && h->nc_pack) rc2 = mcf_snowplan_nc_write(k.sp, h->nc_pack, ch, k.r0);      // (its strips of the snowpack's file)
                     return rc2;
                 });
                 mcf::reduce_on_first(w, [&] {
@@ -767,12 +785,28 @@ int fold_series_days(const mcf_snowrun* h, Block& k, int slot, int d0, int nd) {
     return MCF_OK;
 }
 
-// a slot's merged days [d0, d0 + nd): into the summary, into the series sink, to the caller
+// the netCDF sink of the merged outputs: the block's row strips of the slot's days — runs of days in a class packed on the
+// device, days in neither class (NA for every cell, fetch_days) as missval
+int write_nc_days(const mcf_snowrun* h, Block& k, int slot, int d0, int nd) {
+    for (int q = 0, e; q < nd; q = e) {
+        e = q + 1;
+        const bool in_class = h->snowday[(size_t)(d0 + q)] || h->nosnowday[(size_t)(d0 + q)];
+        while (e < nd && (h->snowday[(size_t)(d0 + e)] || h->nosnowday[(size_t)(d0 + e)]) == in_class) ++e;
+        const int rc = in_class ? mcf_nc_write_plan_rows(h->nc_micro, k.plan, slot, 0, k.r0, (int64_t)q * 24, (int64_t)(d0 + q) * 24,
+                                                         (int64_t)(e - q) * 24, nullptr)
+                                : mcf_nc_write_missing(h->nc_micro, k.r0, k.nr, (int64_t)(d0 + q) * 24, (int64_t)(e - q) * 24);
+        if (rc) return rc;
+    }
+    return MCF_OK;
+}
+
+// a slot's merged days [d0, d0 + nd): into the summary, into the series sink, into the file, to the caller
 int fold_and_fetch(Pass2& p, Block& k, int slot, int d0, int nd) {
     const mcf_snowrun* h = p.h;
     int rc = MCF_OK;
     if (h->sum_micro) rc = mcf_plan_summary_accumulate(k.plan, slot, 0, d0, nd);
     if (!rc && k.ser_micro) rc = fold_series_days(h, k, slot, d0, nd);
+    if (!rc && h->nc_micro) rc = write_nc_days(h, k, slot, d0, nd);
     return rc ? rc : fetch_days(p, k, slot, d0, nd);
 }
 
@@ -819,6 +853,8 @@ void tail_days(Pass2& p, Worker& w) {
         }
         if (h->sum_micro || h->ser_micro)          // (a sink-only run has no fetch that waits for the plan's stream)
             if (const int rc = mcf_plan_sync(k.plan)) return rc;
+        if (h->nc_micro && h->T > (int64_t)h->ndays * 24)      // the steps past the last whole day: missval, as the arrays' NA
+            if (const int rc = mcf_nc_write_missing(h->nc_micro, k.r0, k.nr, (int64_t)h->ndays * 24, h->T - (int64_t)h->ndays * 24)) return rc;
         for (int v = 0; v < MCF_NOUT; ++v)
             if (h->opt.out[v] && p.out && p.out->var[v])
                 for (int64_t lc = (int64_t)h->ndays * 24 * C; lc < h->T * C; ++lc)
@@ -830,11 +866,11 @@ void tail_days(Pass2& p, Worker& w) {
 }  // namespace
 
 extern "C" int mcf_snowrun_pass2(mcf_snowrun* h, const mcf_snow_inputs* micro, double mat, mcf_outputs* out) {
-    if (!h || (!out && !h->sum_micro && !h->ser_micro)) return api_fail(MCF_ERR_ARG, "null snow-run argument");
+    if (!h || (!out && !h->sum_micro && !h->ser_micro && !h->nc_micro)) return api_fail(MCF_ERR_ARG, "null snow-run argument");
     if (!h->pass1_done) return api_fail(MCF_ERR_STATE, "snow run: mcf_snowrun_pass1 first");
     try {
         for (int v = 0; v < MCF_NOUT; ++v)       // (with a summary enabled a variable may go without a host array: it is folded only)
-            if (!h->sum_micro && !h->ser_micro && h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
+            if (!h->sum_micro && !h->ser_micro && !h->nc_micro && h->opt.out[v] && !out->var[v]) return api_fail(MCF_ERR_ARG, "null output array for a requested variable");
         Pass2 p{h, micro, mat, out};
         p.no_skip = getenv("MCF_SNOW_NO_TILE_SKIP") != nullptr;
         p.no_cells = getenv("MCF_SNOW_NO_CELL_GATHER") != nullptr;      // (A/B: tiles as the unit, as in round 4)
@@ -937,11 +973,11 @@ extern "C" int mcf_snowrun_summary_days(mcf_snowrun* h, int32_t pack, int32_t* d
 // sink enabled, pass 1 — where a run for the snowpack's sink alone ends, unless the caller asks for the arrays — pass 2, `fetch`
 template <class Outs, class Check, class Enable, class Fetch>
 static int run_with_sink(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, bool micro, Outs* outs, Check&& check,
-                         Enable&& enable, Fetch&& fetch) {
+                         Enable&& enable, Fetch&& fetch, bool below = false) {
     int rc = check();
     if (rc) return rc;
     mcf_snowrun* h = nullptr;
-    if ((rc = snowrun_create(in, opt, mu, false, &h))) return rc;
+    if ((rc = snowrun_create(in, opt, mu, below, &h))) return rc;
     SnowRunHolder holder(h);
     if ((rc = enable(h))) return rc;
     if ((rc = mcf_snowrun_pass1(h, outs->smod, outs->snowday, outs->nosnowday))) return rc;
@@ -1085,6 +1121,75 @@ extern "C" int mcf_runmicrosnow_series(const mcf_microsnow_in* in, const mcf_opt
     });
 }
 
+// ---- netCDF sink of the run (include/mcf.h "netCDF sink: further sources") -------------------------------------
+// what can be judged of a pair of files for a run of these dimensions and variables; nb: the run's row blocks (0: not known yet)
+static int check_nc_files(const std::string& w, const mcf_ncfile* micro, const mcf_ncfile* pack, int64_t R, int64_t C, int64_t T,
+                          const int32_t* out, int nb) {
+    if (!micro && !pack) return api_fail(MCF_ERR_ARG, w + "null files (one of the two is needed)");
+    for (const mcf_ncfile* f : {micro, pack}) {
+        if (!f) continue;
+        const char* what = f == pack ? "the snowpack's file" : "the outputs' file";
+        if (f->snowpack != (f == pack))
+            return api_fail(MCF_ERR_ARG, w + what + (f == pack ? " was not made by mcf_nc_create_snowpack" : " holds the snowpack's series"));
+        if (f->f->rows != R || f->f->cols != C) return api_fail(MCF_ERR_ARG, w + what + ": its grid is not the run's");
+        if (f->f->nsteps != T) return api_fail(MCF_ERR_ARG, w + what + ": its steps are not the run's");
+        if (nb > 1 && !f->f->takes_strips())
+            return api_fail(MCF_ERR_ARG, w + what + ": the netCDF-4 container chunks a step into row strips of the whole raster: it takes one block");
+    }
+    for (int k = 0; micro && k < micro->f->nvars; ++k)
+        if (!micro->fill_only[k] && !out[micro->out_of[k]])
+            return api_fail(MCF_ERR_ARG, w + "a variable of the outputs' file is not among the run's (opt->out)");
+    return MCF_OK;
+}
+extern "C" int mcf_snowrun_nc_enable(mcf_snowrun* h, mcf_ncfile* micro_file, mcf_ncfile* pack_file) {
+    const std::string w = "mcf_snowrun_nc_enable: ";
+    if (!h) return api_fail(MCF_ERR_ARG, w + "null snow run");
+    if (const int rc = check_nc_files(w, micro_file, pack_file, h->R, h->C, h->T, h->opt.out, h->nb)) return rc;
+    if (h->nc_micro || h->nc_pack) return api_fail(MCF_ERR_STATE, w + "the files are already enabled on this run");
+    if (h->pass1_ever) return api_fail(MCF_ERR_STATE, w + "the files are enabled before mcf_snowrun_pass1");
+    static const uint32_t bit[5] = {1u, 2u, 8u, 4u, 16u};      // (bit 2 is totalSWE, bit 3 the ground snow depth)
+    for (int v = 0; pack_file && v < 5; ++v)
+        if (pack_file->var_of[v] >= 0) h->nc_pack_bits |= bit[v];
+    h->nc_micro = micro_file; h->nc_pack = pack_file;
+    return MCF_OK;
+}
+
+using mcf::NcHolder;
+
+extern "C" int mcf_runmicrosnow_nc(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, const char* path,
+                                   const mcf_nc_spec* spec, const char* pack_path, const mcf_ncpack_spec* pack_spec, mcf_snowrun_nc_out* outs) {
+    const std::string who = "mcf_runmicrosnow_nc", w = who + ": ";
+    if ((!path || !spec) && (!pack_path || !pack_spec)) return api_fail(MCF_ERR_ARG, w + "null path / spec (one of the two files is needed)");
+    if ((path != nullptr) != (spec != nullptr) || (pack_path != nullptr) != (pack_spec != nullptr))
+        return api_fail(MCF_ERR_ARG, w + "null path / spec: a file needs both");
+    if (!outs || !in || !in->grid || !in->snow || !opt) return api_fail(MCF_ERR_ARG, w + "null argument");
+    const bool below = opt->reqhgt < 0;
+    NcHolder micro_file, pack_file;
+    return run_with_sink(in, opt, mu, spec != nullptr, outs, [&]() -> int {
+        int rc = check_create(in, opt, mu, below);
+        if (rc) {
+            if (strncmp(mcf_last_error(), w.c_str(), w.size()) != 0) rc = api_fail(rc, w + mcf_last_error());      // (the shared checks' messages)
+            return rc;
+        }
+        const mcf_grid_inputs& g = *in->grid;
+        const bool several = mu && mu->n_blocks != 1;
+        if (spec && (rc = mcf::nc_spec_check(w, spec, g.rows, g.cols, g.tsteps, opt->reqhgt, opt->out, several))) return rc;
+        if (pack_spec && (rc = mcf::ncpack_spec_check(w, pack_spec, g.rows, g.cols, g.tsteps, several))) return rc;
+        return MCF_OK;
+    }, [&](mcf_snowrun* h) -> int {      // the run exists, so there is a device to fill the files
+        mcf_ncfile* nc = nullptr;
+        int rc = spec ? mcf_nc_create(path, spec, &nc) : (int)MCF_OK;
+        micro_file.reset(nc);
+        nc = nullptr;
+        if (!rc && pack_spec) rc = mcf_nc_create_snowpack(pack_path, pack_spec, &nc);
+        pack_file.reset(nc);
+        return rc ? rc : mcf_snowrun_nc_enable(h, micro_file.get(), pack_file.get());
+    }, [&](mcf_snowrun*) -> int {
+        const int rc = mcf::close_file(micro_file), rc2 = mcf::close_file(pack_file);
+        return rc ? rc : rc2;
+    }, below);
+}
+
 static int runmicrosnow1_impl(const mcf_microsnow_in* in, const mcf_options* opt, const mcf_multi* mu, mcf_outputs* out,
                               const mcf_snowdriver_out* smod, bool below = false) {
     mcf_snowrun* h = nullptr;
@@ -1155,6 +1260,7 @@ struct PackSinks {
     mcf_snowpack_summary_out* sout;
     const mcf_snowpack_series_spec* zspec;
     mcf_snowpack_series_out* zout;
+    mcf_ncfile* nc;      // the snowpack's file (mcf_snowmodel1_nc, which has made it): every block writes its strips
 };
 // coarse: mcf_snowmodel2_coarse, which has checked it (`in` is &coarse.co->drv)
 static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const mcf_multi* mu, int32_t device, const PackSinks& sinks = {},
@@ -1185,6 +1291,7 @@ static int snowmodel(const mcf_snowdriver_in* in, mcf_snowdriver_out* out, const
                 snow_chunk(sb, w, ch, out);
                 if (sinks.spec) sb.each_block(w, [&](Block& k) { return mcf_snowplan_summary_accumulate(k.sp, ch); });
                 if (sinks.zspec) sb.each_block(w, [&](Block& k) { return k.ser_pack ? mcf_snowplan_series_accumulate(k.sp, ch) : (int)MCF_OK; });
+                if (sinks.nc) sb.each_block(w, [&](Block& k) { return mcf_snowplan_nc_write(k.sp, sinks.nc, ch, k.r0); });
             }
             if (sinks.spec)      // every block's rows of the planes in place, through the row pitch
                 sb.each_block(w, [&](Block& k) -> int {
@@ -1229,7 +1336,7 @@ extern "C" int mcf_snowmodel1_summary(const mcf_snowdriver_in* in, const mcf_sno
     if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, "snow driver needs the raster and its dtm");
     if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, "null input: a vegetation or initial-snow raster");
     mcf_snowdriver_out none{};
-    return snowmodel(in, &none, mu, 0, {spec, out, nullptr, nullptr});
+    return snowmodel(in, &none, mu, 0, {spec, out, nullptr, nullptr, nullptr});
 }
 // mcf_snowmodel1 / _multi with the snowpack's series sink as the only sink
 extern "C" int mcf_snowmodel1_series(const mcf_snowdriver_in* in, const mcf_snowpack_series_spec* spec, const mcf_multi* mu,
@@ -1243,7 +1350,23 @@ extern "C" int mcf_snowmodel1_series(const mcf_snowdriver_in* in, const mcf_snow
     if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, who + ": snow driver needs the raster and its dtm");
     if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, who + ": null input: a vegetation or initial-snow raster");
     mcf_snowdriver_out none{};
-    return snowmodel(in, &none, mu, 0, {nullptr, nullptr, spec, out});
+    return snowmodel(in, &none, mu, 0, {nullptr, nullptr, spec, out, nullptr});
+}
+// mcf_snowmodel1 / _multi with the snowpack's netCDF file as the only sink: 4 B per value leave the device, no series array on the host
+extern "C" int mcf_snowmodel1_nc(const mcf_snowdriver_in* in, const mcf_multi* mu, const char* path, const mcf_ncpack_spec* spec) {
+    const std::string who = "mcf_snowmodel1_nc";
+    if (!in || !path || !spec) return api_fail(MCF_ERR_ARG, who + ": null argument");
+    if (in->base.array_forcing) return api_fail(MCF_ERR_ARG, who + " takes data.frame (vector) climate");
+    if (in->base.rows <= 0 || in->base.cols <= 0 || !in->dtm) return api_fail(MCF_ERR_ARG, who + ": snow driver needs the raster and its dtm");
+    if (!mcf::model_rasters_given(in->base)) return api_fail(MCF_ERR_ARG, who + ": null input: a vegetation or initial-snow raster");
+    if (const int rc = mcf::ncpack_spec_check(who + ": ", spec, in->base.rows, in->base.cols, in->base.tsteps, mu && mu->n_blocks != 1)) return rc;
+    if (const int rc = mcf::device_list(mu, 0, nullptr)) return rc;      // no file without a device to fill it
+    mcf_ncfile* nc = nullptr;
+    if (const int rc = mcf_nc_create_snowpack(path, spec, &nc)) return rc;
+    mcf_snowdriver_out none{};
+    NcHolder holder(nc);
+    const int rc = snowmodel(in, &none, mu, 0, {nullptr, nullptr, nullptr, nullptr, nc});
+    return rc ? rc : mcf::close_file(holder);
 }
 // `.snowmodel2` from the coarse arrays: the same chunk loop over one block whose plan expands a chunk's series on the device
 // (mcf_snow.hip, k_coarse_hours) and hands pointm$umu out of the chunk's slab

@@ -28,7 +28,7 @@ from typing import Mapping, Sequence
 
 import numpy as np
 
-from . import api, pointmodel, terrain
+from . import api, ncsink, pointmodel, terrain
 from .vegprep import fill_na, find_gref, find_lref, leafrfromalb      # noqa: F401  (leafrfromalb(), R/dataprep.R:1000-1050)
 from .soil_tables import SOILPARAMETERS, SOILPARAMSP
 from .rformulas import dewpoint_R as _dewpoint, satvap_R as _satvap   # .satvap / .dewpoint, R/internal.R:501-521
@@ -425,6 +425,44 @@ def runmicro(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, 
     if dfsel is None:
         return api.runmicro1Cpp(**a, device=device)
     return api.runmicro3Cpp(dfsel, **a, device=device)
+
+
+def nc_extent(dtm: Mapping, rows: int, cols: int, r0: int = 0, c0: int = 0) -> dict:
+    """The mapping ncsink.writetonc takes as `dtm` for rows [r0, r0 + rows) x columns [c0, c0 + cols) of the raster `dtm`
+    ("xmin", "ymax", "res"[, "crs"]; row 0 is the northern edge)"""
+    res = dtm["res"] if np.isscalar(dtm["res"]) else dtm["res"][0]
+    return {"xmin": dtm["xmin"] + c0 * res, "xmax": dtm["xmin"] + (c0 + cols) * res, "ymin": dtm["ymax"] - (r0 + rows) * res,
+            "ymax": dtm["ymax"] - r0 * res, "res": res, "crs": dtm.get("crs", "")}
+
+
+def runmicro_nc(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, fileout: str, *, vars=None,
+                format: str = "classic", deflate_level: int = 0, pai_a=None, tfact: float = 1.5, slr=None, apr=None, hor=None, twi=None,
+                wsa=None, svf=None, device: int = 0, devices=None, n_blocks: int = 0, days_per_chunk: int = 0, extent: Mapping | None = None):
+    """`runmicro()` followed by `writetonc()` without the arrays in between (include/mcf.h mcf_runmicro_nc): data.frame weather,
+    any reqhgt — below ground the streamed plan — every chunk packed on the device and written while the next is solved.  `vars`:
+    writetonc's default for the height.  `dtm` needs "xmin", "ymax" besides "z" / "res" for the file's coordinates (`extent`: the
+    mapping itself, for a tile of a larger raster).  `devices` / `n_blocks`: row blocks, each writing its strips (classic
+    container).  -> the file's variable names; the classic file is byte for byte ncsink.writetonc(runmicro(...))."""
+    names = tuple(ncsink.default_vars(reqhgt) if vars is None else vars)
+    out = [1 if n in names else 0 for n in api._abi.OUT_NAMES]
+    a = prepare_grid_inputs(micropoint, reqhgt, vegp, soilc, dtm, pai_a=pai_a, out=out, slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa,
+                            svf=svf, device=device)
+    a["tfact"] = float(tfact)
+    a.pop("out")
+    rows, cols = np.shape(as3d(a["vegp"]["hgt"])[:, :, 0])
+    return api.runmicro_nc(**a, fileout=fileout, grid=nc_extent(dtm, rows, cols) if extent is None else extent, vars=names, format=format,
+                           deflate_level=deflate_level, device=device, devices=devices, n_blocks=n_blocks, days_per_chunk=days_per_chunk)
+
+
+def runmicro_depths_nc(micropoint: Mapping, depths, vegp: Mapping, soilc: Mapping, dtm: Mapping, files, *, soilm: bool = True,
+                       format: str = "classic", deflate_level: int = 0, pai_a=None, tfact: float = 1.5, slr=None, apr=None, hor=None,
+                       twi=None, wsa=None, svf=None, device: int = 0, days_per_chunk: int = 0) -> None:
+    """runmicro_depths into one `writetonc` file per depth (include/mcf.h mcf_runmicro_depths_nc): files[d] holds Tz at depths[d]
+    under that depth's long name and, with soilm, the soil moisture.  `dtm` as for runmicro_nc."""
+    a, depths, tbp = _depth_inputs(micropoint, depths, vegp, soilc, dtm, pai_a, tfact, dict(slr=slr, apr=apr, hor=hor, twi=twi, wsa=wsa, svf=svf), device)
+    rows, cols = np.shape(as3d(a["vegp"]["hgt"])[:, :, 0])
+    api.runmicro_depths_nc(**a, depths=depths, tbp=tbp, files=files, grid=nc_extent(dtm, rows, cols), soilm=soilm, format=format,
+                           deflate_level=deflate_level, device=device, days_per_chunk=days_per_chunk)
 
 
 # ---- period summaries: monthly (yearly, daily, ...) maps straight from the device ------------------------------------------------
@@ -1632,6 +1670,57 @@ def runsnowmodel_series(weather: Mapping, micropoint: Mapping, vegp: Mapping, so
     return res
 
 
+def runmicro_snow_nc(micropoint: Mapping, reqhgt: float, vegp: Mapping, soilc: Mapping, dtm: Mapping, snow_inputs: Mapping,
+                     fileout=None, *, snow_fileout=None, vars=None, snow_vars=None, format: str = "classic", deflate_level: int = 0,
+                     pai_a=None, tfact: float = 1.5, device: int = 0, devices=None, n_blocks: int = 0, _terrain=None) -> dict:
+    """`runmicro(..., snow = TRUE)` followed by `writetonc()` without the arrays in between: the snow run with the netCDF sink of
+    include/mcf.h as its only sink — `fileout` the merged outputs `vars` (writetonc's default for the height) as a `writetonc`
+    file, `snow_fileout` the snow model's series `snow_vars` (default all five) in the snowpack's file; either may be None.
+    Every merged ring chunk is packed on the device and written as int32; no [rows, cols, steps] array is made on either side.
+    Days that are neither snow nor no-snow days, the steps past the last whole day and the snow series' days past the last
+    whole 5-day chunk are missval.  `dtm` needs "xmin", "ymax" besides "z" / "res" for the files' coordinates.  reqhgt < 0 is
+    not available here (snow.runmicrosnow_nc runs it).  `devices` / `n_blocks`: row blocks, each writing its strips (classic
+    container).  -> {"vars": the outputs' file's variables, "snow_vars": the snowpack's, "snowdays", "nosnowdays"}; the classic
+    file is byte for byte ncsink.writetonc(runmicro_snow(..., one_call=True))."""
+    if fileout is None and snow_fileout is None:
+        raise ValueError("fileout and snow_fileout are both None")
+    names = tuple(ncsink.default_vars(reqhgt) if vars is None else vars) if fileout is not None else ()
+    snames = tuple(api._abi.SNOWDRIVER_OUT if snow_vars is None else snow_vars) if snow_fileout is not None else ()
+    i = _snow_sink_inputs(micropoint, reqhgt, vegp, soilc, dtm, snow_inputs, names, snames, pai_a, tfact, device,
+                          "the front end's file sink of the snow run needs reqhgt >= 0 (snow.runmicrosnow_nc runs below ground)")
+    if fileout is not None and tuple(i.kept) != tuple(n for n in api._abi.OUT_NAMES if n in names):
+        raise ValueError("a selected variable does not exist at this reqhgt")
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    hours, east, north, crs = ncsink.grid_of(nc_extent(dtm, rows, cols), i.a["obstime"])
+    kw = dict(crs_wkt=crs, format=format, deflate_level=deflate_level)
+    w = ncsink.NcWriter(fileout, rows, cols, hours, east, north, reqhgt, i.kept, **kw) if fileout is not None else None
+    pw = ncsink.SnowpackNcWriter(snow_fileout, rows, cols, hours, east, north, vars=i.snames, **kw) if snow_fileout is not None else None
+    try:
+        res = _snow_sink_run(i, devices, n_blocks, _terrain, lambda run: run.nc_enable(w, pw), lambda run: {})
+    finally:
+        for f in (w, pw):
+            if f is not None:
+                f.close()
+    res.update(vars=tuple(i.kept) if w is not None else (), snow_vars=tuple(i.snames))
+    return res
+
+
+def runsnowmodel_nc(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, fileout, *, vars=None,
+                    format: str = "classic", deflate_level: int = 0, snowenv: str = "Taiga", snowinitd=0.0, snowinita=0.0,
+                    stfact: float = 0.01, devices=None, n_blocks: int = 0) -> tuple:
+    """`runsnowmodel()` (the slow method, data.frame weather, a complete micropoint) into the snowpack's netCDF file (include/mcf.h
+    mcf_snowmodel1_nc; the convention: ncsink.SNOWPACK_SCALE / _UNITS / _LONG_NAME) instead of the five [rows, cols, steps]
+    arrays: every chunk packed on the device, SWE maps straight to disk.  The days past the last whole 5-day chunk (NA in
+    runsnowmodel's arrays) are missval.  `dtm` needs "xmin", "ymax".  -> the file's series names"""
+    from . import snow as S
+    si = runsnowmodel(weather, micropoint, vegp, soilc, dtm, snowenv=snowenv, method="slow", snowinitd=snowinitd, snowinita=snowinita,
+                      stfact=stfact, inputs_only=True)
+    rows, cols = np.asarray(dtm["z"]).shape[:2]
+    return S.snowmodel1_nc(si["obstime"], si["climdata"], si["pointm"], si["vegp"], si["other"], si["snowenv"], si["dtm"], si["res"],
+                           si["tfact"], fileout=fileout, grid=nc_extent(dtm, rows, cols), vars=vars, format=format,
+                           deflate_level=deflate_level, devices=devices, n_blocks=n_blocks)
+
+
 def runsnowmodel_summary(weather: Mapping, micropoint: Mapping, vegp: Mapping, soilc: Mapping, dtm: Mapping, *, periods="month",
                          vars: Sequence = ("totalSWE",), stats: Sequence = ("mean", "max", "hours_above"), thresholds=None,
                          snowenv: str = "Taiga", snowinitd=0.0, snowinita=0.0, stfact: float = 0.01, devices=None, n_blocks: int = 0) -> dict:
@@ -1991,11 +2080,11 @@ def runmicro_big(micropoint, reqhgt: float, pathout: str, vegp: Mapping, soilc: 
     Array weather (`runmicro_big(micropointa, ..., dtm, dtmc, altcorrect)`, vignette "Running the model over large
     areas"): `micropoint` is `runpointmodela`'s list for a `crows` x `ccols` climate grid over the whole raster, `lats`,
     `lons` [rows, cols]; every tile interpolates the coarse arrays inside the solver at its own place in that grid, so
-    tiles join without a seam in the forcing."""
+    tiles join without a seam in the forcing.
+    reqhgt < 0: every tile runs the streamed below-ground plan through api.runmicro_nc (include/mcf.h mcf_runmicro_nc), so the
+    whole series need not be resident; each file is ncsink.writetonc(runmicro(tile))."""
     import os
     from . import pipeline
-    if reqhgt < 0:
-        raise ValueError("below ground the whole series has to be resident: use runmicro() per tile and writetonc()")
     z_all = np.asarray(dtm["z"], dtype=np.float64)
     rows, cols = z_all.shape
     res = dtm["res"] if np.isscalar(dtm["res"]) else dtm["res"][0]
@@ -2042,6 +2131,10 @@ def runmicro_big(micropoint, reqhgt: float, pathout: str, vegp: Mapping, soilc: 
             fo = os.path.join(pathout, "microut", f"area_{rw:02d}_{cl:02d}.nc")
             ext = {"xmin": dtm["xmin"] + c0 * res, "xmax": dtm["xmin"] + c1 * res, "ymin": dtm["ymax"] - r1 * res,
                    "ymax": dtm["ymax"] - r0 * res, "res": res, "crs": dtm.get("crs", "")}
-            pipeline.run_to_nc(a, fo, ext, vars=vars, days_per_chunk=days_per_chunk, device=device, array_forcing=array)
+            if reqhgt < 0:      # below ground: the streamed plan's chunks through the same file sink (mcf_runmicro_nc)
+                b = {k: v for k, v in a.items() if k != "out"}      # (the file's variables are what the solver computes)
+                api.runmicro_nc(**b, fileout=fo, grid=ext, vars=vars, days_per_chunk=days_per_chunk, device=device, array_forcing=array)
+            else:
+                pipeline.run_to_nc(a, fo, ext, vars=vars, days_per_chunk=days_per_chunk, device=device, array_forcing=array)
             written.append(fo)
     return written

@@ -257,6 +257,26 @@ def snowmodel1_summary(obstime, climdata, pointm, vegp, other, snowenv, dtm, res
     return planes
 
 
+def snowmodel1_nc(obstime, climdata, pointm, vegp, other, snowenv, dtm, res, tfact=0.02, *, fileout: str, grid: Mapping, vars=None,
+                  format: str = "classic", deflate_level: int = 0, chunk_steps: int = 120, devices=None, n_blocks: int = 0,
+                  **table) -> tuple:
+    """snowmodel1_chunks with the snowpack's netCDF file as its only sink (include/mcf.h mcf_snowmodel1_nc): every chunk's
+    series packed on the device (k_pack_nc_planes) and written as int32 — no [rows, cols, steps] array on either side.  `vars`:
+    series of _abi.SNOWDRIVER_OUT (default all five); `grid`: the mapping ncsink.writetonc takes as `dtm`; scale= / units= /
+    long_name= replace entries of ncsink's SNOWPACK_* tables.  Steps past the last whole chunk hold missval.
+    -> the file's series names"""
+    from . import ncsink
+    lib = _abi.load()
+    R, Cc = np.shape(vegp["pai"])
+    m = marshal_snow(obstime, climdata, vegp, _terrain_placeholders(other, R, Cc), False, pointm=pointm, snowenv=snowenv)
+    din = _driver_in(m, dtm, res, tfact, chunk_steps)
+    hours, east, north, crs = ncsink.grid_of(grid, obstime)
+    sp, names = ncsink.ncpack_spec(R, Cc, hours, east, north, vars, crs, format, deflate_level, **table)
+    mu = _abi.multi(devices, n_blocks)
+    _abi.check(lib.mcf_snowmodel1_nc(C.byref(din), C.byref(mu[0]) if mu else None, str(fileout).encode(), C.byref(sp)))
+    return names
+
+
 def snowpack_series_spec(rows: int, cols: int, points=None, zones=None, vars=("totalSWE",), stats=("mean", "min", "max"),
                          nzones: int | None = None):
     """include/mcf.h mcf_snowpack_series_spec: api.series_spec over the five series (names of _abi.SNOWDRIVER_OUT or indices)
@@ -1110,6 +1130,11 @@ class SnowPlan:
     def series_reset(self):
         _abi.check(self._lib.mcf_snowplan_series_reset(self._p))
 
+    def nc_write(self, writer, chunk: int, row0: int = 0):
+        """the steps of the chunk run last as rows [row0, row0 + rows) of a ncsink.SnowpackNcWriter's records, packed on the
+        device (include/mcf.h mcf_snowplan_nc_write); behind the last chunk the steps no chunk covers become missval"""
+        _abi.check(self._lib.mcf_snowplan_nc_write(self._p, writer._h, int(chunk), int(row0)))
+
     def fetch_point_series(self, var) -> np.ndarray:
         """[tsteps, npoints] of one selected series (name of _abi.SNOWDRIVER_OUT or index)"""
         v = _abi.SNOWDRIVER_OUT.index(var) if isinstance(var, str) else int(var)
@@ -1490,6 +1515,21 @@ class SnowRun:
             points=lambda v, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_points(self._p, pack, v, ptr)),
             zones=lambda v, k, ptr: _abi.check(self._lib.mcf_snowrun_series_fetch_zones(self._p, pack, v, k, ptr))))
 
+    def drop_days(self, days):
+        """Between pass1 and pass2: the listed days (0-based; each a no-snow day that is no snow day) leave the run's classes —
+        pass2 does not solve them, they are NA in the arrays and missval in the file (include/mcf.h mcf_snowrun_drop_days)"""
+        drop = np.zeros(self.days, dtype=np.int32)
+        drop[np.asarray(days, dtype=np.int64)] = 1
+        _abi.check(self._lib.mcf_snowrun_drop_days(self._p, Buffers().ptr(drop), int(drop.size)))
+
+    def nc_enable(self, writer=None, pack_writer=None):
+        """The netCDF sink (include/mcf.h mcf_snowrun_nc_enable), before pass1: `writer` a ncsink.NcWriter for the merged outputs
+        (pass2 writes every chunk's row strips, packed on the device; pass2(want_arrays=False) then moves no array), `pack_writer`
+        a ncsink.SnowpackNcWriter for the snow model's series (pass1).  The caller closes the writers after the passes."""
+        _abi.check(self._lib.mcf_snowrun_nc_enable(self._p, writer._h if writer is not None else None,
+                                                   pack_writer._h if pack_writer is not None else None))
+        self._ncw = (writer, pack_writer)
+
     def pass1(self, want_smod: bool = False):
         """-> (snowdays, nosnowdays[, smod]): one 0/1 flag per day; smod = `.snowmodel1`'s five [rows, cols, tsteps] arrays"""
         (sd, sdp), (nd, ndp) = Buffers().out(self.days, np.int32, zero=True), Buffers().out(self.days, np.int32, zero=True)
@@ -1568,6 +1608,49 @@ def runmicrosnow1(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: floa
             fn = lib.mcf_runmicrosnow1_below if below else lib.mcf_runmicrosnow2 if run.array_weather else lib.mcf_runmicrosnow1
             _abi.check(fn(C.byref(run._in), C.byref(run._gm.options), C.byref(outs), sop))
     return (arrays, smod) if want_smod else arrays
+
+
+def runmicrosnow_nc(grid: Mapping, snow: Mapping, micro: Mapping | None, mat: float, *, fileout=None, pack_fileout=None, nc_grid: Mapping,
+                    vars=None, pack_vars=None, format: str = "classic", deflate_level: int = 0, want_arrays: bool = False,
+                    want_smod: bool = False, device: int = 0, devices=None, n_blocks: int = 0, cells_per_block: int = 0) -> dict:
+    """The whole snow run into netCDF files as ONE library call (include/mcf.h mcf_runmicrosnow_nc; arguments as runmicrosnow1):
+    `fileout` the merged outputs as a `writetonc` file (`vars`: among the run's outputs, default ncsink.default_vars(reqhgt) that
+    the run has), `pack_fileout` the snow model's five series (`pack_vars`); either may be None.  reqhgt < 0 runs the below-ground
+    run.  `nc_grid`: the mapping ncsink.writetonc takes as `dtm`.  The classic file is byte for byte ncsink.writetonc of
+    runmicrosnow1's arrays (of the same block count).
+    -> {"out": the merged outputs or None, "snowdays", "nosnowdays"[, "smod"]}"""
+    from . import ncsink
+    with SnowRun(grid, snow, device=device, cells_per_block=cells_per_block, handle=False) as run:
+        if micro is not None:
+            run._mm = marshal_snow(micro["obstime"], micro["climdata"], micro["vegp"], micro["other"], run.array_weather, micro=True)
+            run._in.micro = C.pointer(run._mm.inputs)
+        run._in.mat = float(mat)
+        hours, east, north, crs = ncsink.grid_of(nc_grid, snow["obstime"])
+        reqhgt = float(run._gm.options.reqhgt)
+        sp = ps = None
+        if fileout is not None:
+            has = [n for n, o in zip(_abi.OUT_NAMES, run._gm.options.out) if o]
+            names = [n for n in ncsink.default_vars(reqhgt) if n in has] if vars is None else vars
+            sp, _ = ncsink.nc_spec(run.rows, run.cols, hours, east, north, reqhgt, names, crs, False, format, deflate_level)
+        if pack_fileout is not None:
+            ps, _ = ncsink.ncpack_spec(run.rows, run.cols, hours, east, north, pack_vars, crs, format, deflate_level)
+        so = _abi.SnowrunNcOut()
+        res = {"out": None}
+        if want_arrays:
+            outs, res["out"] = alloc_outputs(run._gm)
+            so.arrays = C.pointer(outs)
+        if want_smod:
+            sm, res["smod"] = _driver_out(run.rows, run.cols, run.tsteps)
+            so.smod = C.pointer(sm)
+        nd = run.tsteps // 24
+        res["snowdays"], so.snowday = run._gm.out(nd, np.int32, zero=True)
+        res["nosnowdays"], so.nosnowday = run._gm.out(nd, np.int32, zero=True)
+        mu = _abi.multi(devices, n_blocks)
+        _abi.check(_abi.load().mcf_runmicrosnow_nc(C.byref(run._in), C.byref(run._gm.options), C.byref(mu[0]) if mu else None,
+                                                   str(fileout).encode() if sp is not None else None, C.byref(sp) if sp is not None else None,
+                                                   str(pack_fileout).encode() if ps is not None else None,
+                                                   C.byref(ps) if ps is not None else None, C.byref(so)))
+    return res
 
 
 # kind -> the two spec builders, the out struct, the sink filler (run, spec, names, destination struct) and the library entry
